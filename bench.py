@@ -14,6 +14,11 @@ Workloads (config.workload):
 
 Rank 0 prints ONE JSON line. `roofline` is measured live with HIP events on the library's stream; `cpu_baseline` times the
 oracle's -O3 -march=native build (kind "port": the reference itself cannot be built here) on a bounded sample.
+
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure needs: set up, W warm-up steps, N timed steps, the line (`value`,
+`ms_per_step`, and the `roofline` of ba_linearize read from the timed region). `--full` adds everything else to the same line, as the default run
+did before: HBM calibration, per-scope kernel times, pose delta vs the oracle, CPU baselines, the pipelined / upload variants and the extra legs.
+`--dump-outputs DIR` writes what the last timed step computed (dump_outputs); the inputs are seeded, the same for the same arguments.
 """
 import argparse
 import json
@@ -116,6 +121,7 @@ class GpuJob:
         import ctypes as _C
         self._ev5, self._n5 = (_C.c_int * 5)(), (_C.c_int * 5)()
         self.last_T = [None] * TRACKED_PER_KF                           # tracked poses of the last step (pose_delta_vs_oracle)
+        self.last_track = [None] * TRACKED_PER_KF                       # (aff, lastResiduals, lastFlowIndicators, ok) of the same frames (--dump-outputs)
         self._pinned = None
 
     def enable_raw_uploads(self):
@@ -187,6 +193,7 @@ class GpuJob:
                     self.trk_frames += 1
                 if keep:
                     self.last_T[k] = self._T.reshape(3, 4).copy()
+                    self.last_track[k] = (self._aff.copy(), self._lr.copy(), self._lf.copy(), self._ok.value)
         rm = c.ba_optimize(6, never_break=True)
         if track:
             # a2 for the new keyframe: setCoarseTrackingRef FOLLOWS the optimisation, as in makeKeyFrame (FullSystem.cpp:1404) - the next step's frames are tracked
@@ -273,6 +280,40 @@ def pose_delta_vs_oracle(job, win, st6, trk):
     st_o = ba.slots()[0]
     return dict(window_max=max(d_win), tracked_max=max(d_trk), residual_decisions_differ=int((st_g != st_o).sum()), residual_slots=int((st_o >= 0).sum()),
                 oracle="strict fp32 restatement (liboracle_f32.so), same inputs, same keyframe", target="< 1e-5 (BASELINE.json)")
+
+
+DUMP_CAP = 1 << 20             # --dump-outputs: elements per array; a larger output is written as a fixed sample of its rows
+
+
+def dump_outputs(path, job, rmse, tracked):
+    """--dump-outputs DIR: what the timed path computed in its LAST timed step, as a caller of that path receives it, one DIR/<name>.npy per array:
+    the three tracked frames (nalo_trk_track: refToNew pose, aff_g2l, lastResiduals of the evaluated levels, lastFlowIndicators, ok), the optimised window (worldToCam and state of
+    every frame, point inverse depths, residual states and energies) and the rmse nalo_ba_optimize returns. float64 where the C ABI hands out doubles,
+    float32 otherwise. An array of more than DUMP_CAP elements keeps a sample of its rows drawn with a fixed seed (RandomState(0), sorted): the same rows
+    for the same arguments, so two builds compare output for output."""
+    os.makedirs(path, exist_ok=True)
+    c = job.ctx
+    out = {"ba_rmse": np.array([rmse], np.float64)}
+    if tracked:
+        out["tracked_ref_to_new"] = np.stack(job.last_T).astype(np.float64)
+        out["tracked_aff_g2l"] = np.stack([t[0] for t in job.last_track]).astype(np.float64)
+        # lastResiduals per pyramid level: the step descends from level c.levels - 1, levels beyond it are never evaluated (NaN by contract)
+        out["tracked_last_residuals"] = np.stack([t[1][:c.levels] for t in job.last_track]).astype(np.float64)
+        out["tracked_last_flow"] = np.stack([t[2] for t in job.last_track]).astype(np.float64)
+        out["tracked_ok"] = np.array([t[3] for t in job.last_track], np.float64)
+    fs, w2c, _ = c.ba_get_frames()
+    out["window_world_to_cam"] = np.asarray(w2c, np.float64)
+    out["window_state"] = np.array([list(f.state) for f in fs], np.float64)
+    out["point_idepth"] = np.asarray(c.ba_get_points()["idepth"], np.float32)
+    st, _, _, en, _ = c.ba_get_residuals()
+    out["residual_state"] = st.astype(np.float32)
+    out["residual_energy"] = np.asarray(en, np.float32)
+    for name, a in out.items():
+        if a.size > DUMP_CAP:
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], DUMP_CAP // (a.size // a.shape[0]), replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log("outputs of the last timed step: %s" % ", ".join("%s %s" % (k, tuple(v.shape)) for k, v in out.items()))
 
 
 def cpu_baseline(win, st6, trk, budget_s=20.0, track=True, nthreads=6, linearize_mt=False):
@@ -398,12 +439,16 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="kitti00_8kf", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline legs, no pose delta against the oracle")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo + NALO_BENCH_ONE_DEVICE=1 rehearses the multi-rank flow on a single GPU (all ranks on device 0)")
-    ap.add_argument("--no-extra", action="store_true", help="the main leg only: no pipelined / upload variants, no stress250k / shard1m / front-end legs (the command the rocprofv3 summaries are taken of)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: the main leg only: no pipelined / upload variants, no stress250k / shard1m / front-end legs (the command the rocprofv3 summaries are taken of)")
     ap.add_argument("--ba-only", action="store_true", help="the step is optimize() alone (no tracked frames, no setCoarseTrackingRef)")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous only (gloo, no GPU): proves that --gpus N starts N ranks")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure too: HBM calibration, per-scope kernel times, pose delta vs the oracle, "
+                                                         "CPU baselines, pipelined / upload variants and the extra legs (stress250k, shard1m, front end, immature points, "
+                                                         "pixel selector, initialiser). Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64), see dump_outputs")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -467,9 +512,10 @@ def main():
     import gc
     gc.collect(); gc.disable()                                   # harness hygiene: no Python garbage collection inside the timed region
     barrier()
+    keep_at = args.steps - 1 if args.dump_outputs else -1         # --dump-outputs: the last timed step keeps the tracker's outputs
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        rm = job.step(do_track)
+    for i in range(args.steps):
+        rm = job.step(do_track, keep=(i == keep_at))
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
@@ -480,25 +526,30 @@ def main():
     job.ctx.profile_enable(False)
     units = args.steps * (1 if sharded else world)       # replicas: every rank processed its own keyframes
     value = units / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, job, rm, do_track)
 
     prof = {"ba_linearize": job.ctx.profile_get("ba_linearize")}
     lin_stats = launch_stats(job.ctx.profile_samples("ba_linearize"), every=lin_every)
     job.ctx.profile_sample(1)
-    # the roofline's denominator measured on this device in the same run: streaming copy / triad over 1 GiB buffers
-    try:
-        hbm_copy, hbm_triad = job.ctx.hbm_calibrate(1 << 30, 10)
-    except Exception:
-        hbm_copy = hbm_triad = None
-    evals_timed = job.evals
-    job.ctx.profile_select(None); job.ctx.profile_enable(True); job.ctx.profile_reset()
-    nprof = max(2, min(5, args.steps))
-    job.count_trk_bytes = True
-    for _ in range(nprof):                                       # untimed: every scope bracketed
-        job.step(do_track)
-    job.count_trk_bytes = False
-    job.ctx.profile_enable(False)
-    prof.update({k: job.ctx.profile_get(k) for k in ("ba_sc", "ba_reduce", "ba_resub", "trk_eval", "trk_lm", "pyramid")})
-    job.evals = evals_timed
+    hbm_copy = hbm_triad = None
+    nprof = 0
+    if args.full:
+        # the roofline's denominator measured on this device in the same run: streaming copy / triad over 1 GiB buffers
+        try:
+            hbm_copy, hbm_triad = job.ctx.hbm_calibrate(1 << 30, 10)
+        except Exception:
+            hbm_copy = hbm_triad = None
+        evals_timed = job.evals
+        job.ctx.profile_select(None); job.ctx.profile_enable(True); job.ctx.profile_reset()
+        nprof = max(2, min(5, args.steps))
+        job.count_trk_bytes = True
+        for _ in range(nprof):                                       # untimed: every scope bracketed
+            job.step(do_track)
+        job.count_trk_bytes = False
+        job.ctx.profile_enable(False)
+        prof.update({k: job.ctx.profile_get(k) for k in ("ba_sc", "ba_reduce", "ba_resub", "trk_eval", "trk_lm", "pyramid")})
+        job.evals = evals_timed
     out = None
     cpu_legs_pending, cpu_baseline_legs = False, None          # rank 0 of a default run: the CPU baseline legs are run behind the GPU legs
     if rank == 0:
@@ -529,12 +580,13 @@ def main():
                        "multi_gpu": ("points sharded, all-reduce of stitched H,b" if sharded else "replicas (window too small to shard)")},
             "roofline": roof,
             "kernel_ms": {k: {"total_ms": round(v[0], 3), "launches": v[1]} for k, v in prof.items()},
-            "kernel_ms_note": "ba_linearize: HIP events over the timed region (%d steps%s); the other scopes: %d untimed steps right after it" % (args.steps, ", one launch in %d bracketed" % lin_every if lin_every > 1 else "", nprof),
+            "kernel_ms_note": "ba_linearize: HIP events over the timed region (%d steps%s); the other scopes: %s" % (args.steps, ", one launch in %d bracketed" % lin_every if lin_every > 1 else "",
+                                                                                                                        "%d untimed steps right after it" % nprof if args.full else "with --full"),
             "tracker_evals_per_step": job.evals / max(args.steps, 1),
             "rccl_ranks": (min(main_rccl) if main_rccl else None),
             "fine_track_rmse": round(float(rm), 4),
         }
-        if do_track and prof["trk_lm"][1] > 0 and job.trk_frames > 0:
+        if do_track and "trk_lm" in prof and prof["trk_lm"][1] > 0 and job.trk_frames > 0:
             # the headline's OWN dominant kernel: the persistent LM kernel of the tracker, one launch per tracked frame. Algorithmic bytes =
             # sum over its evaluations of 64 B per point of the evaluated level; time = dispatch timestamps of the launch.
             tms, tn = prof["trk_lm"]
@@ -546,7 +598,7 @@ def main():
                                             note="one persistent launch per tracked frame runs the whole LM descent (%.1f evaluations): a serial chain of ~8 us per evaluation (gather 1.3 + block "
                                                  "reduction 1.8 + exchange between workgroups 2.6 + the 8x8 solve / SE3 on one wave 2.3), latency bound by construction on ~25 k points; "
                                                  "alg_bytes = sum_l evals_l n_l 64 B" % (job.evals / max(args.steps, 1) / TRACKED_PER_KF))
-        if world == 1 and do_track and not args.no_extra:       # --no-extra: the main leg only (the command the rocprofv3 summaries are taken of: nothing concurrent in the trace)
+        if args.full and world == 1 and do_track and not args.no_extra:       # --no-extra: the main leg only (the command the rocprofv3 summaries are taken of: nothing concurrent in the trace)
             try:
                 out["pipelined"] = pipelined_leg(win, st6, trk, local_rank, steps=max(20, min(200, args.steps)))
                 out["value_with_uploads"] = None                             # filled below (promoted beside value)
@@ -603,7 +655,7 @@ def main():
                 out["cpu_baseline_all_cores"].update(cpu_model=info["model"], physical_cores=info["physical_cores"], usable_cpus=info["usable_cpus"])
             except Exception as e:
                 out["cpu_baseline"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if do_track:
                 out["pose_delta_vs_oracle"] = pose_delta_vs_oracle(job, win, st6, trk)
             if args.workload == "kitti00_8kf" and not args.no_extra:
@@ -615,7 +667,7 @@ def main():
     # extra legs of the default run (same JSON line):
     #  shard1m    configs[4]: the 1M-point 12-KF window sharded over ALL ranks with the RCCL all-reduce (strong scaling, every N)
     #  stress250k configs[3]: single GPU only, where the kernels saturate the chip
-    if args.workload == "kitti00_8kf" and not args.no_extra:
+    if args.full and args.workload == "kitti00_8kf" and not args.no_extra:
         log("main leg done: %.1f keyframes/s; starting the shard1m leg" % value)
         job.ctx.close()
         # The extra legs must never cost the main line: they run under a deadline (a collective that never completes on some fabric would otherwise

@@ -46,7 +46,7 @@ k = line("%s_kitti00_bench_line_under_profiler.json" % tag)
 fe = line("%s_frontend_line.json" % tag)
 if d:
     r = d["roofline"]
-    F.append(entry("roofline (ba_linearize on stress250k, full steps) as printed by `python bench.py`", "%s_default_bench_line.json" % tag, dict(avg_us=r.get("avg_us"), frac=r.get("frac"), stats=r.get("stats")),
+    F.append(entry("roofline (ba_linearize on stress250k, full steps) as printed by `python bench.py --full`", "%s_default_bench_line.json" % tag, dict(avg_us=r.get("avg_us"), frac=r.get("frac"), stats=r.get("stats")),
                    "%s_stress250k_kernel_stats.csv" % tag, "ba_linearize_kernel<0, 0, 256>", r.get("alg_bytes"),
                    "the CSV is the trace of `bench.py --workload stress250k --steps 10 --warmup 2 --no-cpu-baseline --no-extra`: the same full steps (tracking + setCoarseTrackingRef + optimize) as the stress leg of the default run"))
     rh = d.get("roofline_headline")
