@@ -297,6 +297,10 @@ int nalo_ba_get_residuals(nalo_ctx* ctx, int8_t* state, uint8_t* active, float* 
  * index h + t*W, fp64 */
 int nalo_ba_get_acc13(nalo_ctx* ctx, double* H13 /* W*W x 169 */);
 int nalo_ba_counts(nalo_ctx* ctx, int* resInA, int* resInL, int* resInM);
+/* the kernel variants the window setup chose (read only, no side effect): {nblocks, Ppad, lin_sub, sc_split, sc_bpw, T,
+ * precalc records pulled by a kernel (0/1), threshold by the radix select (0/1), back-substitution mode (1: xAd as kernel
+ * arguments, 2: built on the device from x), eligible for the pre-launch of optimize() (0/1)} */
+int nalo_ba_get_launch_config(nalo_ctx* ctx, int cfg[10]);
 
 /* bench/test utility (no reference counterpart): snapshot / restore the mutable window state (idepths, residual states,
  * frame states, calibration, HM/bM) on the device, so the same synthetic keyframe can be replayed without host uploads */

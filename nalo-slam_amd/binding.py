@@ -31,7 +31,7 @@ EXPORTS = [
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
-    "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
+    "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
@@ -113,6 +113,7 @@ def load():
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
     L.nalo_ba_counts.argtypes = [vp, c_ip, c_ip, c_ip]
+    L.nalo_ba_get_launch_config.argtypes = [vp, c_ip]
     L.nalo_ba_set_allreduce.argtypes = [vp, ALLREDUCE_FN, vp]
     L.nalo_ba_set_allreduce_mode.argtypes = [vp, C.c_int]
     L.nalo_ba_set_allreduce_side.argtypes = [vp, ALLREDUCE_FN, vp]
@@ -493,6 +494,13 @@ class Context:
         a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
         self._ck(self.L.nalo_ba_counts(self.h_, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def ba_launch_config(self):
+        """the kernel variants the window setup chose (nalo_ba_get_launch_config)"""
+        a = (C.c_int * 10)()
+        self._ck(self.L.nalo_ba_get_launch_config(self.h_, a))
+        keys = ("nblocks", "Ppad", "lin_sub", "sc_split", "sc_bpw", "T", "pull", "radix", "resub_mode", "prelaunch_eligible")
+        return dict(zip(keys, list(a)))
 
     # ---- two-frame initialiser (SURVEY 8(f) rank 2)
     def init_calc_res_and_gs(self, slot_first, slot_new, lvl, refToNew, aff, pts, alphaW=150.0 * 150.0, alphaK=2.5 * 2.5, couplingWeight=1.0):

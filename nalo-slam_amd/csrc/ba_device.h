@@ -14,6 +14,8 @@ constexpr int kBlk = 256;            // points per linearize block
 constexpr int kTopVals = 93;         // 91 AccumulatorApprox entries + residual count + energy
 constexpr int kTopStride = 96;       // floats per (block, target) partial
 constexpr int kPreStride = 40;       // floats per (host,target) precalc record
+constexpr int kThSmallSlots = 16384; // Ppad up to this: frameEnergyTH by ba_th_small_kernel (one workgroup); beyond: the radix select of ba_th_fill_kernel
+constexpr int kPreDirectSlots = 32768;   // Ppad up to this: ba_linearize reads the precalc records from mapped host memory; beyond: ba_pull_kernel copies them
 
 // residual slot state byte
 enum : uint8_t { RS_STATE_MASK = 3, RS_EXISTS = 4, RS_ACTIVE = 8, RS_LINEARIZED = 16 };
@@ -73,7 +75,9 @@ struct BADev {
 };
 
 // {xc (4) | xAd [W*W][8]} of resubstituteFPt for windows of up to 8 frames, passed by value as kernel arguments (ba_resub_kernel)
-struct XadArg { float v[4 + 8 * 64]; };
+constexpr int kXadArgFrames = 8;     // windows up to this many frames pass {xc, xAd} to the back-substitution as kernel arguments (XadArg); larger ones pass x
+                                     // and every workgroup builds its host's rows of xAd (ba_resub_kernel, XMODE 2)
+struct XadArg { float v[4 + kXadArgFrames * kXadArgFrames * 8]; };
 
 // Gate of a kernel that is enqueued BEFORE its inputs exist (round 4, small single-GPU windows): the host still solves the system while the back-substitution and
 // the next linearisation already sit in the stream; each spins (one lane per workgroup, bounded) on a word of host-mapped memory until the host has written the

@@ -279,7 +279,7 @@ static int set_precalc(nalo_ctx* c) {
     // Round 4, measured and NOT kept for large windows: read in place there too, the records are fetched from the host once per XCD (its L2 keeps them for the launch),
     // W^2 x 160 B x 8 over PCIe per linearisation = 3 us at W = 8, 7 us at W = 12, INSIDE ba_linearize (the roofline kernel: 161 -> 164-171 us on stress250k), against ~10 us
     // of pull kernel + boundary beside it: stress250k 2.064 -> 2.002 ms per keyframe, the emulated N = 8 shard of the 12-frame window 1.72 -> 1.76 ms (same-box A/B).
-    const bool direct = w.points_set && w.Ppad <= 32768;
+    const bool direct = w.points_set && w.Ppad <= kPreDirectSlots;
     // Either way the records are written into a ring of four mapped, coherent host blocks (a block's last readers may still run: the ring is what lets do_step ->
     // set_precalc and the epilogue's set_precalc follow each other without a wait). Large windows: ONE workgroup pulls the block into device memory (ba_pull_kernel)
     // instead of a copy packet + its event.
@@ -524,7 +524,7 @@ static int sc_async(nalo_ctx* c, int shift, float margScale, int margOnly) {
 // (set_precalc): the device picks both up ~1.5 us after the stores instead of 5-6 us after a launch call - the two launch latencies that sat on the critical
 // path of every Gauss-Newton iteration (FullSystemOptimize.cpp:478-545 is one serial chain of such steps).
 static bool prelaunch_eligible(const nalo_ctx* c, const BAWindow& w) {
-    return !w.hook && c->set.forceAcceptStep && w.points_set && w.Ppad <= 32768 && w.W <= 8;
+    return !w.hook && c->set.forceAcceptStep && w.points_set && w.Ppad <= kPreDirectSlots && w.W <= 8;
 }
 static int prelaunch_iteration(nalo_ctx* c) {
     BAWindow& w = *c->ba;
@@ -591,7 +591,7 @@ static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to
         // misc-only fetch publishes its tail from the reduce launch too: the last pass of optimize() is [linearize | reduce] instead of [linearize | th | tail | reduce | publish]
         // (only where the host waits for the threshold anyway: behind a regular iteration's publish the separate 7 us launch runs under the host's solve, inside the reduce
         // launch it would sit on the critical path in front of the stitch)
-        const bool small_th = !w.hook && w.th_pending && th_to_host && w.dev.Ppad <= 16384 && (top || sc);
+        const bool small_th = !w.hook && w.th_pending && th_to_host && w.dev.Ppad <= kThSmallSlots && (top || sc);
         const bool pub_in_reduce = misc_only && !w.hook && (top || sc) && (small_th || !w.th_pending);
         if ((top || sc) && (th_to_host || w.hook) && !fuse_lo && !pub_in_reduce) {      // the threshold rides in the tail {TH, 1.0}: compute it before the publish
             if (!small_th) { int rc = flush_th(c); if (rc) return rc; }
@@ -824,7 +824,7 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
     for (int h = 0; h < W; ++h) {
         for (int i = 0; i < 8; ++i) w.frames[h].step[i] = -x[4 + 8 * h + i];
         w.frames[h].step[8] = w.frames[h].step[9] = 0;
-        if (W > 8) continue;                                   // larger windows: every back-substitution workgroup builds its host's rows of xAd from x (ba_resub_kernel, XMODE 2)
+        if (W > kXadArgFrames) continue;                       // larger windows: every back-substitution workgroup builds its host's rows of xAd from x (ba_resub_kernel, XMODE 2)
         for (int t = 0; t < W; ++t) {
             const float *AH = &w.adHostF[(size_t)(h + W * t) * 64], *AT = &w.adTargetF[(size_t)(h + W * t) * 64];
             // xAd = x_h^T adHost + x_t^T adTarget: rows of the adjoints are contiguous in j, so j is the inner (vector) loop; per entry the same
@@ -843,15 +843,15 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
         return NALO_OK;
     }
     XadArg karg;
-    if (W <= 8) { std::memcpy(karg.v, xc, 16); std::memcpy(karg.v + 4, xAd, (size_t)W * W * 8 * 4); }      // small window: {xc, xAd} travel as kernel arguments, no copy
+    if (W <= kXadArgFrames) { std::memcpy(karg.v, xc, 16); std::memcpy(karg.v + 4, xAd, (size_t)W * W * 8 * 4); }      // small window: {xc, xAd} travel as kernel arguments, no copy
     else std::memcpy(karg.v, xF, (size_t)n * 4);                 // larger windows: x itself (8W + 4 floats); xAd is built on the device from the float adjoints
     {
         ProfScope ps(c, "ba_resub");
         if (fuse_step) {
             NALO_HIP(c, w.step_partial.reserve((size_t)(w.Ppad / 256 + 1) * 4));
-            ba_launch_resub_step(c->stream, w.dev, 1.f, w.step_partial.p, karg, W > 8);
+            ba_launch_resub_step(c->stream, w.dev, 1.f, w.step_partial.p, karg, W > kXadArgFrames);
             w.step_fused = true;
-        } else ba_launch_resub(c->stream, w.dev, karg, W > 8);
+        } else ba_launch_resub(c->stream, w.dev, karg, W > kXadArgFrames);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
@@ -1522,6 +1522,16 @@ int nalo_ba_get_acc13(nalo_ctx* c, double* H13) {
 int nalo_ba_counts(nalo_ctx* c, int* a, int* l, int* m) {
     if (!c || !c->ba) return fail(c, NALO_ERR_STATE, "nalo_ba_counts: no window");
     if (a) *a = c->ba->resInA; if (l) *l = c->ba->resInL; if (m) *m = c->ba->resInM;
+    return NALO_OK;
+}
+int nalo_ba_get_launch_config(nalo_ctx* c, int cfg[10]) {
+    if (!c || !c->ba || !c->ba->points_set || !cfg) return fail(c, NALO_ERR_STATE, "nalo_ba_get_launch_config: set window and points first");
+    const BAWindow& w = *c->ba;
+    cfg[0] = w.nblocks; cfg[1] = w.Ppad; cfg[2] = w.dev.lin_sub; cfg[3] = w.dev.sc_split; cfg[4] = w.dev.sc_bpw; cfg[5] = w.T;
+    cfg[6] = w.Ppad > kPreDirectSlots;                              // set_precalc: ba_pull_kernel
+    cfg[7] = w.Ppad > kThSmallSlots;                                // ba_launch_energy_th: radix select
+    cfg[8] = w.W > kXadArgFrames ? 2 : 1;                           // the back-substitution's xAd: from x on the device (ba_resub_kernel XMODE 2) or kernel arguments
+    cfg[9] = prelaunch_eligible(c, w);
     return NALO_OK;
 }
 int nalo_ba_set_allreduce_mode(nalo_ctx* c, int stream_ordered) {

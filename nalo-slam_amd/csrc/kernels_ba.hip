@@ -1105,7 +1105,7 @@ void ba_launch_energy_th_step(hipStream_t s, const BADev& B, int step) {
     else ba_th_final_kernel<<<1, 256, 0, s>>>(Cc, B.th_state, A, B.frameTH + (B.W - 1));
 }
 void ba_launch_energy_th(hipStream_t s, const BADev& B) {
-    if (B.Ppad <= 16384) { ba_th_small_kernel<<<1, 1024, 0, s>>>(B.en_new, B.Ppad, B.frameTH + (B.W - 1)); return; }
+    if (B.Ppad <= kThSmallSlots) { ba_th_small_kernel<<<1, 1024, 0, s>>>(B.en_new, B.Ppad, B.frameTH + (B.W - 1)); return; }
     for (int step = 0; step < 4; ++step) ba_launch_energy_th_step(s, B, step);
 }
 

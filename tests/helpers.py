@@ -23,6 +23,24 @@ def assert_fp32_faithful(gpu, o32, o64, factor=1.5, floor=1e-7):
         assert np.quantile(mine, q) <= factor * np.quantile(ref, q) + floor, (q, np.quantile(mine, [0.5, 0.99, 1.0]), np.quantile(ref, [0.5, 0.99, 1.0]))
 
 
+def x_floor(win, st6, x32, x64):
+    """How far the reference's own fp32 arithmetic puts the solved increment x of solveSystemF from the all-fp64 evaluation: the larger distance of the
+    strict fp32 oracle in its two summation orders (orc_set_sum_mode 0: fp64 sums of fp32 terms, x32; 1: the reference's fp32 accumulator order, solved
+    here). On a weakly constrained window either one alone is a single sample of the fp32 rounding, scattered by the system's conditioning: the two sit
+    0.3x to 3x apart. Leaves the fp32 oracle in mode 0."""
+    L = orc.lib("f32")
+    L.orc_set_sum_mode(1)
+    try:
+        ba = orc.ba_from_window(win, "f32", state6=st6)
+        ba.linearize_all(False)
+        ba.apply_res()
+        x_ref = np.array(ba.solve_system(0))
+        del ba
+    finally:
+        L.orc_set_sum_mode(0)
+    return max(rel_err(x32, x64), rel_err(x_ref, x64))
+
+
 def tracker_inputs(win, n=3000, seed=1):
     """Residuals targeting the newest keyframe (W-1): centerProjectedTo + HdiF, from the true depth."""
     rng = np.random.RandomState(seed)

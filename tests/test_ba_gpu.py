@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import orc
-from helpers import rel_err, pose_dist, assert_fp32_faithful
+from helpers import rel_err, pose_dist, assert_fp32_faithful, x_floor
 from nalo_slam_amd import binding, synth
 
 pytestmark = pytest.mark.gpu
@@ -138,7 +138,7 @@ def test_solve_and_step_on_the_well_conditioned_window():
     c.close()
 
 
-@pytest.mark.parametrize("cfg", [dict(W=4, P=400, tol=None), dict(W=8, P=3000, tol=1e-5)])
+@pytest.mark.parametrize("cfg", [dict(W=4, P=400, tol=None), dict(W=8, P=3000, tol=1e-5), dict(W=12, P=3600, tol=1e-5)])
 def test_optimize_matches_oracle_and_converges(cfg):
     """Full FullSystem::optimize(6). Pose delta |log(T_gpu T_ref^-1)| vs the fp32 oracle: < 1e-5 on the KITTI-sized window
     (BASELINE.json target). On the tiny 400-point window the problem is so weakly constrained that two valid fp32
@@ -226,6 +226,33 @@ def test_window_sizes(W, P):
     st_o, ac_o, _, _ = ba.slots()
     st, ac, _, _, _ = c.ba_get_residuals()
     assert np.array_equal(st, st_o) and np.array_equal(ac, ac_o)
+    if W > 8:
+        # above 8 frames the back-substitution builds its host's rows of xAd from x on the device (ba_resub_kernel, mode 2): the solution x and the
+        # back-substituted point steps by the floor rule of test_solve_and_step_on_the_well_conditioned_window, then the step applied by do_step
+        assert c.ba_launch_config()["resub_mode"] == 2
+        x32, s32 = np.array(ba.solve_system(0)), ba.points()["step"].copy()
+        del ba
+        orc.lib("f64").orc_set_sum_mode(0)
+        ba64 = orc.ba_from_window(win, "f64", state6=st6)
+        ba64.linearize_all(False); ba64.apply_res()
+        x64, s64 = np.array(ba64.solve_system(0)), ba64.points()["step"].copy()
+        del ba64
+        idp0 = c.ba_get_points()["idepth"]
+        c.ba_backup_state()
+        x = np.array(c.ba_solve_system(0))
+        step = c.ba_get_points()["step"]
+        # the fp64 floor of x over both summation orders of the fp32 oracle (helpers.x_floor): on this 150-points-per-host window they sit 2.8x apart
+        floor32, floor_x, mine_x = rel_err(x32, x64), x_floor(win, st6, x32, x64), rel_err(x, x64)
+        scale = np.abs(s32).max()
+        print("W=%d x: GPU vs fp64 %.2e, fp32 oracle vs fp64 %.2e (both summation orders: %.2e); steps: GPU vs fp32 oracle %.2e of max"
+              % (W, mine_x, floor32, floor_x, np.abs(step - s32).max() / scale))
+        assert mine_x < 1.5 * floor_x + 1e-6, (mine_x, floor_x)
+        assert rel_err(x, x32) < max(2e-4, 2.0 * floor32)
+        assert np.abs(step - s32).max() < max(1e-4, 1.5 * np.abs(s64 - s32).max() / scale) * scale
+        c.ba_do_step(1.0)
+        idp1 = c.ba_get_points()["idepth"]
+        assert np.abs((idp1 - idp0) - step).max() <= 2 * np.spacing(np.abs(idp0).max())
+        assert np.abs((idp1 - idp0) - s32).max() < max(1e-4, 1.5 * np.abs(s64 - s32).max() / scale) * scale + 2 * np.spacing(np.abs(idp0).max())
     c.close()
 
 

@@ -1,5 +1,6 @@
 """BASELINE.json configs[4] AT ITS OWN SIZE on one GPU: the synthetic 1 M active points / 12-keyframe window (bench.make_inputs("shard1m"):
-1920x1072, R = 11 M residual slots). The oracle cannot finish this size in seconds, so the checks are the size-independent properties of the path:
+1920x1072, R = 11 M residual slots). The large-window variants this window runs (sc_bpw 8 point blocks per SC workgroup, the radix select, the
+device-built xAd) are compared with the oracle in tests/test_ba_large_gpu.py; the checks here are the size-independent properties of the path:
   determinism    the same pass twice (nalo_ba_snapshot / nalo_ba_restore) gives BIT-IDENTICAL stitched systems, energy, count and threshold: every sum of
                  the path has a fixed order (no float atomics), as the reference's per-thread replicas summed in order (AccumulatedTopHessian.h:144-149)
   linearity      two shards (nalo_shard_points through bench.shard: the partition the 8-GPU run uses) driven through the all-reduce hooks: residual counts
