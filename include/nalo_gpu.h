@@ -179,8 +179,13 @@ int nalo_trk_track(nalo_ctx* ctx, int slot_new, double T_io[12], double aff_io[2
                    double lastResiduals[5], double lastFlowIndicators[3], int* ok, int* n_evals);
 
 /* measurement aid: LM evaluations per pyramid level (evals[l]) and point-cloud sizes (n[l]) of the last nalo_trk_track; the algorithmic bytes of that frame are
- * sum_l evals[l] * n[l] * 64 B. Either array may be NULL. */
+ * sum_l evals[l] * n[l] * 64 B. Either array may be NULL. An evaluation is one calcRes: the first one of a level, its cutoff repeats and every LM
+ * candidate; a level re-run through haveRepeated adds both runs to its entry. */
 int nalo_trk_last_evals(nalo_ctx* ctx, int evals[5], int n[5]);
+/* how the last nalo_trk_track ran (read only, no side effect): {lanes per workgroup, workgroups, driver (1: the persistent LM kernel, 2: the host-driven loop,
+ * 0: no track yet), rounds per level 0..4 (ceil(n_l / (workgroups * lanes)): 1 = the level's points stay in registers for all its evaluations; 0 for levels
+ * not run), haveRepeated (a level was re-run)}. With the host-driven loop only the driver and haveRepeated are set. */
+int nalo_trk_get_launch_config(nalo_ctx* ctx, int cfg[9]);
 
 /* ------------------------------------------------------------------------------------------------
  * Back-end: sliding-window photometric bundle adjustment.

@@ -27,7 +27,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream",
     "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download",
-    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_set_shard",
+    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
@@ -145,6 +145,7 @@ def load():
     L.nalo_init_get_state.argtypes = [vp, c_dp, c_dp, c_ip, c_ip, c_ip, c_ip]
     L.nalo_init_get_points.argtypes = [vp, C.c_int, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp, c_u8p, c_fp, c_fp, c_fp, c_fp, c_ip, c_fp, c_ip, c_fp]
     L.nalo_trk_last_evals.argtypes = [vp, c_ip, c_ip]
+    L.nalo_trk_get_launch_config.argtypes = [vp, c_ip]
     L.nalo_init_set_state.argtypes = [vp, c_dp, c_dp, C.c_int, C.c_int, C.c_int]
     L.nalo_init_set_points.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_u8p, c_fp, c_fp, c_fp, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_init_get_carried.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_u8p]
@@ -349,6 +350,18 @@ class Context:
         self._ck(self.L.nalo_trk_track(self.h_, slot_new, _d(T), _d(aff), _d(np.asarray(ref_aff, np.float64)),
                                        _f(np.asarray(exposures, np.float32)), coarsest, _d(mr), _d(lr), _d(lf), C.byref(ok), C.byref(ne)))
         return ok.value, T.reshape(3, 4), aff, lr, lf, ne.value
+
+    def trk_last_evals(self):
+        """LM evaluations per pyramid level of the last trk_track and the point-cloud sizes of the levels (nalo_trk_last_evals)"""
+        ev, n = np.zeros(5, np.int32), np.zeros(5, np.int32)
+        self._ck(self.L.nalo_trk_last_evals(self.h_, _i(ev), _i(n)))
+        return ev, n
+
+    def trk_launch_config(self):
+        """how the last trk_track ran (nalo_trk_get_launch_config): driver 1 = persistent LM kernel, 2 = host-driven loop"""
+        a = (C.c_int * 9)()
+        self._ck(self.L.nalo_trk_get_launch_config(self.h_, a))
+        return dict(lanes=a[0], nblocks=a[1], driver=a[2], rounds=list(a[3:8]), have_repeated=a[8])
 
     # ---- BA
     def ba_set_window(self, slots, evalPT, aff=None, exposure=None, th=None, frame_ids=None, state6=None, calib=None, calib_zero=None,

@@ -481,11 +481,16 @@ int nalo_trk_eval(nalo_ctx* c, int slot_new, int lvl, const double R[9], const d
     return NALO_OK;
 }
 
-// evaluations per pyramid level and point-cloud sizes of the last nalo_trk_track that ran in the persistent kernel: the algorithmic bytes of that launch are
+// evaluations per pyramid level and point-cloud sizes of the last nalo_trk_track (either LM driver): the algorithmic bytes of that frame are
 // sum_l evals[l] * n[l] * 64 (16 B point + four 12-B taps per point and evaluation)
 int nalo_trk_last_evals(nalo_ctx* c, int evals[5], int n[5]) {
     if (!c) return NALO_ERR_ARG;
     for (int i = 0; i < 5; ++i) { if (evals) evals[i] = c->lm_evals_lvl[i]; if (n) n[i] = i < c->levels ? c->pc_n[i] : 0; }
+    return NALO_OK;
+}
+int nalo_trk_get_launch_config(nalo_ctx* c, int cfg[9]) {
+    if (!c || !cfg) return fail(c, NALO_ERR_ARG, "nalo_trk_get_launch_config: bad argument");
+    std::memcpy(cfg, c->trk_cfg, sizeof(c->trk_cfg));
     return NALO_OK;
 }
 int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2], const double ref_aff[2], const float exposures[2],
@@ -501,6 +506,7 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
     double aff_cur[2] = {aff_io[0], aff_io[1]};
     bool haveRepeated = false, good = true;
     int evals = 0, start_lvl = coarsestLvl;
+    for (int& e : c->lm_evals_lvl) e = 0;
     // The whole pyramid descent runs in ONE persistent multi-block kernel (kernels_trk_lm.hip): ~10 us per LM evaluation against ~19 us for
     // the host-driven loop below (a launch, a finish kernel and a polled flag per evaluation). NALO_TRK_HOST_LM=1 selects the host loop,
     // which is also what a caller gets by driving nalo_trk_eval itself.
@@ -519,6 +525,7 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
                 // the persistent kernel's workgroups were not co-resident (another context holds the CUs): nothing was written back, so the frame is
                 // redone by the host-driven loop below (same kernels per evaluation, same results to 1e-5), and so is every later frame of this context
                 c->lm_host_only = true;
+                for (int& e : c->lm_evals_lvl) e = 0;
                 std::fprintf(stderr, "[nalo] trk_lm_kernel: a workgroup's partial never arrived; this context now drives the tracker's LM loop from the host\n");
             } else {
             if (rc) return rc;
@@ -547,9 +554,13 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
         const double R[9] = {T.R(0, 0), T.R(0, 1), T.R(0, 2), T.R(1, 0), T.R(1, 1), T.R(1, 2), T.R(2, 0), T.R(2, 1), T.R(2, 2)};
         const double tt[3] = {T.t(0), T.t(1), T.t(2)};
         if (aLL0) *aLL0 = aLL[0];
-        ++evals;
+        ++evals; ++c->lm_evals_lvl[lvl];
         return nalo_trk_eval(c, slot_new, lvl, R, tt, aLLf, (float)ref_aff[1], cutoff, 1, st, H, b);
     };
+    if (start_lvl >= 0) {                                                     // the host-driven loop runs the frame: no persistent launch to describe
+        for (int& v : c->trk_cfg) v = 0;
+        c->trk_cfg[2] = 2;
+    }
     for (int lvl = start_lvl; lvl >= 0; --lvl) {
         double H[64], b[8], Hn[64], bn[8], resOld[6], resNew[6];
         float levelCutoffRepeat = 1;
@@ -609,6 +620,7 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
         if (minResForAbort && lastRes[lvl] > 1.5 * minResForAbort[lvl]) { good = false; break; }
         if (levelCutoffRepeat > 1 && !haveRepeated) { lvl++; haveRepeated = true; }
     }
+    if (start_lvl >= 0) c->trk_cfg[8] = haveRepeated;
     if (lastResiduals) std::memcpy(lastResiduals, lastRes, sizeof(lastRes));
     if (lastFlow) std::memcpy(lastFlow, flow, sizeof(flow));
     if (n_evals) *n_evals = evals;

@@ -199,7 +199,7 @@ int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], cons
 // ------------------------------------------------------------------------------------------------ a2
 // step 1 (CoarseTracker.cpp:388-405): weighted scatter. Two points on one pixel commute exactly in fp32; three or more (rare) would make the sum depend on
 // the arrival order of the atomics while the reference adds them serially, in residual order. The scatter therefore also counts the hits per pixel, and
-// trk_scatter_fix_kernel redoes the pixels with >= 3 hits in ascending residual index: the result is the serial loop's, bit for bit, run to run.
+// the fix pass (trk_scatter_hot_kernel) redoes the pixels with >= 3 hits in ascending residual index: the result is the serial loop's, bit for bit, run to run.
 __global__ __launch_bounds__(256) void trk_scatter_kernel(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid,
                                                           const float* __restrict__ HdiF, int n, int w0, int h0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -212,78 +212,93 @@ __global__ __launch_bounds__(256) void trk_scatter_kernel(const float* __restric
     atomicAdd(cnt + u + w0 * v, 1);
 }
 // Pass 1 (trk_scatter_hot_kernel, the whole grid) lists the residuals whose pixel took three or more hits - in any order: the rounds below order by INDEX,
-// not by list position; pass 2 (trk_scatter_fix_kernel, ONE workgroup) zeroes those pixels and adds the listed residuals back one per pixel and round, always
+// not by list position; pass 2 (trk_scatter_fix_body, ONE workgroup) zeroes those pixels and adds the listed residuals back one per pixel and round, always
 // the lowest remaining index first (the pixel's count word is reused as the "next index allowed" gate). Usually the list is empty and pass 2 is one read.
 // (The list used to be built by the single workgroup itself, striding all n residuals: 530 us at n = 250 000.)
-constexpr int kScatterFixCap = 4096;
-template <int NT>
-__device__ __forceinline__ void trk_scatter_fix_body(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid, const float* __restrict__ HdiF,
-                                                     int n, int w0, int h0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt, int* __restrict__ glist, int* list);
-// Round 4: ONE launch for both passes (the fix pass was a launch of its own, 4.6 us for what is almost always one read): every workgroup lists its residuals on hot pixels
-// (agent-scope stores, acknowledged before its ticket), the workgroup that draws the last ticket runs the fix.
-__global__ __launch_bounds__(256) void trk_scatter_hot_kernel(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid, const float* __restrict__ HdiF,
-                                                              int n, int w0, int h0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt,
-                                                              int* __restrict__ list /* [kScatterFixCap] + counter + ticket */) {
-    __shared__ int slist[kScatterFixCap];
-    __shared__ int is_last;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const int u = (int)(Ku[i] + 0.5f), v = (int)(Kv[i] + 0.5f);
-        if (!(u < 0 || v < 0 || u >= w0 || v >= h0) && __hip_atomic_load(cnt + u + w0 * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 3) {       // written by the scatter's atomics: read at L2
-            const int at = atomicAdd(list + kScatterFixCap, 1);
-            if (at < kScatterFixCap) __hip_atomic_store(list + at, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) is_last = __hip_atomic_fetch_add((unsigned*)(list + kScatterFixCap + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
-    __syncthreads();
-    if (!is_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(list + kScatterFixCap + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ticket re-armed for the next (stream-ordered) call
-    trk_scatter_fix_body<256>(Ku, Kv, nid, HdiF, n, w0, h0, idepth, wsum, cnt, list, slist);
-}
-template <int NT>
-__device__ __forceinline__ void trk_scatter_fix_body(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid, const float* __restrict__ HdiF,
-                                                     int n, int w0, int h0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt, int* __restrict__ glist, int* list) {
+// The global list has room for all n residuals (a residual is listed at most once), so no count is ever dropped. Up to kScatterFixLds entries the rounds
+// run on an LDS copy; a longer list (a full-size window's residuals on the newest frame: tens of thousands) runs them on the global list itself.
+constexpr int kScatterFixLds = 4096;
+struct ScatterListLds {                              // the LDS copy: written and read by the fixing workgroup only
+    int* p;
+    __device__ int ld(int k) const { return p[k]; }
+    __device__ void st(int k, int v) const { p[k] = v; }
+};
+struct ScatterListGlobal {                           // the global list: every access at L2 (its entries were stored by other workgroups)
+    int* p;
+    __device__ int ld(int k) const { return __hip_atomic_load(p + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ void st(int k, int v) const { __hip_atomic_store(p + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+template <int NT, class List>
+__device__ __forceinline__ void trk_scatter_fix_rounds(List list, int m, const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid,
+                                                       const float* __restrict__ HdiF, int w0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt) {
     const int tid = threadIdx.x;
-    const int total = __hip_atomic_load(glist + kScatterFixCap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (total == 0) return;
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(glist + kScatterFixCap, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // re-armed for the next (stream-ordered) call
-    for (int k = tid; k < total && k < kScatterFixCap; k += NT) list[k] = __hip_atomic_load(glist + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const int m = total;
-    if (m == 0 || m > kScatterFixCap) return;            // (more than 4096 colliding residuals — never seen —: the atomic sums stay)
     for (int k = tid; k < m; k += NT) {
-        const int i = list[k], p = (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f);
+        const int i = list.ld(k), p = (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f);
         // every access to the pixel's words below goes to L2 (atomics / agent-scope loads): the atomics of the scatter and of the gate bypass this CU's L1,
         // a plain load could return a stale line
         atomicExch(idepth + p, 0.f); atomicExch(wsum + p, 0.f); atomicExch(cnt + p, 0x7fffffff);       // gate = lowest listed index of the pixel, found next
     }
     __syncthreads();
-    for (int k = tid; k < m; k += NT) { const int i = list[k]; atomicMin(cnt + (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f), i); }
+    for (int k = tid; k < m; k += NT) { const int i = list.ld(k); atomicMin(cnt + (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f), i); }
     __syncthreads();
     // rounds: a listed residual adds itself when the gate of its pixel shows its index, then passes the gate to the next listed index of that pixel
     for (int round = 0; round < m; ++round) {
         bool any = false;
         for (int k = tid; k < m; k += NT) {
-            const int i = list[k];
+            const int i = list.ld(k);
             if (i < 0) continue;
             const int p = (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f);
             if (__hip_atomic_load(cnt + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i) {
                 const float weight = sqrtf((float)(1e-3 / ((double)HdiF[i] + 1e-12)));
                 atomicAdd(idepth + p, __fmul_rn(nid[i], weight)); atomicAdd(wsum + p, weight);         // one adder per pixel and round: the order is the index order
-                list[k] = -1 - i;                                                                   // done (kept negative so that the gate search can skip it)
+                list.st(k, -1 - i);                                                                 // done (kept negative so that the gate search can skip it)
             } else any = true;
         }
         __syncthreads();
         if (!__syncthreads_or(any)) break;
         // next gate per pixel: the lowest not-yet-added listed index
-        for (int k = tid; k < m; k += NT) { const int i = list[k]; if (i < 0) { const int j = -1 - i, p = (int)(Ku[j] + 0.5f) + w0 * (int)(Kv[j] + 0.5f); atomicCAS(cnt + p, j, 0x7fffffff); } }
+        for (int k = tid; k < m; k += NT) { const int i = list.ld(k); if (i < 0) { const int j = -1 - i, p = (int)(Ku[j] + 0.5f) + w0 * (int)(Kv[j] + 0.5f); atomicCAS(cnt + p, j, 0x7fffffff); } }
         __syncthreads();
-        for (int k = tid; k < m; k += NT) { const int i = list[k]; if (i >= 0) atomicMin(cnt + (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f), i); }
+        for (int k = tid; k < m; k += NT) { const int i = list.ld(k); if (i >= 0) atomicMin(cnt + (int)(Ku[i] + 0.5f) + w0 * (int)(Kv[i] + 0.5f), i); }
         __syncthreads();
     }
+}
+// hot = {counter, ticket, list[n]}
+template <int NT>
+__device__ __forceinline__ void trk_scatter_fix_body(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid, const float* __restrict__ HdiF,
+                                                     int w0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt, int* __restrict__ hot, int* slist) {
+    const int tid = threadIdx.x;
+    const int m = __hip_atomic_load(hot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (m == 0) return;
+    __syncthreads();
+    if (tid == 0) __hip_atomic_store(hot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          // re-armed for the next (stream-ordered) call
+    if (m > kScatterFixLds) { trk_scatter_fix_rounds<NT>(ScatterListGlobal{hot + 2}, m, Ku, Kv, nid, HdiF, w0, idepth, wsum, cnt); return; }
+    for (int k = tid; k < m; k += NT) slist[k] = __hip_atomic_load(hot + 2 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    trk_scatter_fix_rounds<NT>(ScatterListLds{slist}, m, Ku, Kv, nid, HdiF, w0, idepth, wsum, cnt);
+}
+// Round 4: ONE launch for both passes (the fix pass was a launch of its own, 4.6 us for what is almost always one read): every workgroup lists its residuals on hot pixels
+// (agent-scope stores, acknowledged before its ticket), the workgroup that draws the last ticket runs the fix.
+__global__ __launch_bounds__(256) void trk_scatter_hot_kernel(const float* __restrict__ Ku, const float* __restrict__ Kv, const float* __restrict__ nid, const float* __restrict__ HdiF,
+                                                              int n, int w0, int h0, float* __restrict__ idepth, float* __restrict__ wsum, int* __restrict__ cnt,
+                                                              int* __restrict__ hot /* counter, ticket, list[n] */) {
+    __shared__ int slist[kScatterFixLds];
+    __shared__ int is_last;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const int u = (int)(Ku[i] + 0.5f), v = (int)(Kv[i] + 0.5f);
+        if (!(u < 0 || v < 0 || u >= w0 || v >= h0) && __hip_atomic_load(cnt + u + w0 * v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= 3) {       // written by the scatter's atomics: read at L2
+            const int at = atomicAdd(hot, 1);                                                    // < n: every residual is listed at most once
+            __hip_atomic_store(hot + 2 + at, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    if (threadIdx.x == 0) is_last = __hip_atomic_fetch_add((unsigned*)(hot + 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
+    __syncthreads();
+    if (!is_last) return;
+    if (threadIdx.x == 0) __hip_atomic_store(hot + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ticket re-armed for the next (stream-ordered) call
+    trk_scatter_fix_body<256>(Ku, Kv, nid, HdiF, w0, idepth, wsum, cnt, hot, slist);
 }
 // All levels of steps 2-5 go through ONE launch per step (the per-level launches were ~30 dependent kernels of a few microseconds each).
 struct TrkLevels {
@@ -298,7 +313,7 @@ struct TrkLevels {
 __global__ __launch_bounds__(256) void trk_zero2_kernel(float* __restrict__ a, float* __restrict__ b, int* __restrict__ cnt, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { a[i] = 0.f; b[i] = 0.f; cnt[i] = 0; }
-    if (i == 0) { cnt[n + kScatterFixCap] = 0; cnt[n + kScatterFixCap + 1] = 0; }   // the hot list's counter and the ticket of trk_scatter_hot_kernel
+    if (i == 0) { cnt[n] = 0; cnt[n + 1] = 0; }              // the hot list's counter and the ticket of trk_scatter_hot_kernel
 }
 // step 2 (:408-433): 2x2 SUM pyramid, every level from one pass over level 0. A block owns a 32x32 level-0 tile = 16x16 level-1 pixels, and
 // walks up through LDS (8x8, 4x4, 2x2, 1); each parent is a + b + c + d of its four children in the reference's order, so the values
@@ -526,7 +541,7 @@ int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const 
     dil0[L] = dil_blocks; cmp0[L] = cmp_blocks; P.scan0[L] = scan_total;
     NALO_HIP(c, c->scan_tmp.reserve((size_t)scan_total));
     const int n0 = c->wl[0] * c->hl[0];
-    NALO_HIP(c, c->trk_cnt.reserve((size_t)n0 + kScatterFixCap + 16));        // hits per level-0 pixel, then the hot list and its counter
+    NALO_HIP(c, c->trk_cnt.reserve((size_t)n0 + 2 + std::max(n, 0)));        // hits per level-0 pixel, then the hot list's counter, its ticket and room for every residual
     trk_zero2_kernel<<<(n0 + 255) / 256, 256, 0, c->stream>>>(P.id[0], P.ws[0], c->trk_cnt.p, n0);
     if (n > 0) {
         trk_scatter_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(dKu, dKv, dId, dHdi, n, c->wl[0], c->hl[0], P.id[0], P.ws[0], c->trk_cnt.p);

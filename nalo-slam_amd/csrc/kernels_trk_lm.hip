@@ -535,6 +535,14 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
     }
 }
 
+// workgroups of the persistent launch for a largest level of maxn points: one per kLmThreads points, at most NALO_LM_MAX_BLOCKS (64) on KITTI-sized clouds (the
+// exchange between them is the cost that grows), twice that once the largest level has 8+ rounds of the 64-workgroup grid (8 x 64 x 512 = 262 144 points;
+// 1920x1072, 250 k points: 513 us per frame with 64, 469 with 128, 499 with 192, 544 with 256)
+int trk_lm_blocks(int maxn) {
+    const int max_blocks = (maxn >= 8 * NALO_LM_MAX_BLOCKS * kLmThreads ? 2 * NALO_LM_MAX_BLOCKS : NALO_LM_MAX_BLOCKS);
+    return std::min(max_blocks, std::max(1, (maxn + kLmThreads - 1) / kLmThreads));
+}
+
 int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2],
                   int coarsest, int stop_lvl, const double* minRes, double out24[32]) {
     TrkLmParams P;
@@ -554,10 +562,9 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
     P.seq = (double)(++c->trk_seq);
     int maxn = 1;
     for (int l = stop_lvl; l <= coarsest; ++l) maxn = std::max(maxn, c->pc_n[l]);
-    // workgroups: 64 at most on KITTI-sized clouds (the exchange between them is the cost that grows), 128 once the largest level has 8+ rounds of 64 x 256 points
-    // (1920x1072, 250 k points: 513 us per frame with 64, 469 with 128, 499 with 192, 544 with 256)
-    const int max_blocks = (maxn >= 8 * NALO_LM_MAX_BLOCKS * kLmThreads ? 2 * NALO_LM_MAX_BLOCKS : NALO_LM_MAX_BLOCKS);
-    const int NB = std::min(max_blocks, (maxn + kLmThreads - 1) / kLmThreads);
+    const int NB = trk_lm_blocks(maxn);
+    c->trk_cfg[0] = kLmThreads; c->trk_cfg[1] = NB; c->trk_cfg[2] = 1;
+    for (int l = 0; l < 5; ++l) c->trk_cfg[3 + l] = (l >= stop_lvl && l <= coarsest) ? (c->pc_n[l] + NB * kLmThreads - 1) / (NB * kLmThreads) : 0;
     if (!c->lm_partial.p || (c->lm_launches & 0xFFFFFu) == 0) {      // first use / tag wrap-around: no stale word may carry a live tag
         NALO_HIP(c, c->lm_partial.reserve((size_t)2 * 256 * 64));
         NALO_HIP(c, hipMemsetAsync(c->lm_partial.p, 0, (size_t)2 * 256 * 64 * 8, c->stream));
@@ -577,6 +584,7 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
     { const double* t = c->trk_out_host + 64 + 26; fprintf(stderr, "[lm ticks] evals=%d eval=%.0f blockred=%.0f gridsum=%.0f lane0=%.0f (shader clocks per eval)\n", (int)out24[23], t[0] / out24[23], t[1] / out24[23], t[2] / out24[23], t[3] / out24[23]); }
 #endif
     static const bool test_timeout = std::getenv("NALO_LM_TEST_TIMEOUT") != nullptr;          // tests: exercise the caller's degraded path once per context
+    c->trk_cfg[8] = out24[25] != 0.0;
     if (out24[22] < 0 || (test_timeout && c->lm_launches == 1)) return NALO_LM_LOST_BLOCK;
     return NALO_OK;
 }

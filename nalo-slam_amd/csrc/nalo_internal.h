@@ -81,7 +81,8 @@ struct nalo_ctx {
     unsigned long long trk_seq = 0;
     nalo::DevBuf<unsigned long long> lm_partial;   // persistent LM kernel: [2][blocks][64] block partials {fp32, tag}
     unsigned long long lm_launches = 0;
-    int lm_evals_lvl[5] = {};                // LM evaluations per pyramid level of the last persistent-kernel launch (nalo_trk_last_evals)
+    int lm_evals_lvl[5] = {};                // LM evaluations per pyramid level of the last nalo_trk_track (nalo_trk_last_evals)
+    int trk_cfg[9] = {};                     // launch of the last nalo_trk_track (nalo_trk_get_launch_config)
     int trk_rank = 0, trk_world = 1; nalo_allreduce_fn trk_hook = nullptr; void* trk_hook_user = nullptr; bool trk_hook_stream_ordered = false;   // nalo_trk_set_shard
     nalo::DevBuf<double> trk_shard_sums;     // a sharded evaluation's 52 sums on the device, summed over the ranks in place by the hook
     bool lm_host_only = false;                 // latched when a trk_lm launch lost a workgroup (CUs taken by another context): the host-driven LM loop from then on
@@ -227,6 +228,8 @@ void hbm_stream_launch(hipStream_t st, const float4* a, const float4* b, float4*
 int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOrg, int hOrg, const float* G, const float* vinv, const float2* remapXY, int photometric,
                   float factor, const uint8_t* mask_org, const uint8_t* bgr_org, float* out_I, float* out_mask, uint8_t* out_bgr);
 // kernels_tracker.hip
+// kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points
+int trk_lm_blocks(int maxn);
 int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi);
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev);
 int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], const float t[3], const float Ki[9],

@@ -65,6 +65,8 @@ def lib(kind="f32"):
     L.orc_trk_track.restype = C.c_int
     L.orc_trk_counter.argtypes = [C.c_void_p, C.c_int]
     L.orc_trk_counter.restype = C.c_long
+    L.orc_trk_last_evals.argtypes = [C.c_void_p, c_ip]
+    L.orc_trk_last_evals.restype = C.c_int
     L.orc_make_images.argtypes = [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp]
     L.orc_pyr_offset.argtypes = [C.c_int, C.c_int, C.c_int]
     L.orc_pyr_offset.restype = C.c_long
@@ -381,6 +383,12 @@ class Tracker:
         ok = self.L.orc_trk_track(self.h_, fp(dI_new), dp(T), dp(aff), dp(np.asarray(ref_aff, np.float64)),
                                   fp(np.asarray(exposures, np.float32)), coarsest, dp(mr), dp(lr), dp(lf))
         return ok, T.reshape(3, 4), aff, lr, lf
+
+    def last_evals(self):
+        """calcRes evaluations per level of the last track() (cutoff repeats and a re-run level included) and whether the haveRepeated re-run happened"""
+        ev = np.zeros(5, np.int32)
+        rep = self.L.orc_trk_last_evals(self.h_, ip(ev))
+        return ev, bool(rep)
 
 
 class BA:

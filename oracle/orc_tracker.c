@@ -76,6 +76,7 @@ typedef struct {
     const float* dI_ref;    /* borrowed: reference frame pyramid (AoS 3) */
     double lastResiduals[5], lastFlow[3];
     long n_calcres, n_calcgs;   /* call counters for the baseline report */
+    int evals_lvl[5], have_repeated;   /* last orc_trk_track: calcRes evaluations per level (cutoff repeats and the re-run level included), haveRepeated */
     double affA, affB;          /* setting_affineOptModeA / B (util/settings.cpp:128-129); set by orc_trk_set_affine_modes, default 1e12 / 1e8 */
     int aff_set;
 } OrcTracker;
@@ -385,9 +386,12 @@ int orc_trk_track(OrcTracker* T, const float* dI_new, double T_io[12], double af
     double cur[12]; memcpy(cur,T_io,sizeof(cur));
     double aff_cur[2]={aff_io[0],aff_io[1]};
     int haveRepeated=0, ok=1;
+    for (int i=0;i<5;i++) T->evals_lvl[i]=0;
+    T->have_repeated=0;
     for (int lvl=coarsestLvl; lvl>=0; lvl--) {
         double H[64], b[8], resOld[6], resNew[6], aLL[2]; float affLLf[2];
         float levelCutoffRepeat=1;
+        const long n_lvl0 = T->n_calcres;
         double R[9]={cur[0],cur[1],cur[2],cur[4],cur[5],cur[6],cur[8],cur[9],cur[10]}, tr[3]={cur[3],cur[7],cur[11]};
         orc_aff_from_to(exposures[0],exposures[1],ref_aff[0],ref_aff[1],aff_cur[0],aff_cur[1],aLL);
         affLLf[0]=(float)aLL[0]; affLLf[1]=(float)aLL[1];
@@ -440,11 +444,13 @@ int orc_trk_track(OrcTracker* T, const float* dI_new, double T_io[12], double af
             double nrm=0; for (int i=0;i<8;i++) nrm+=inc[i]*inc[i];
             if (!(sqrt(nrm) > 1e-3)) break;
         }
+        T->evals_lvl[lvl] += (int)(T->n_calcres - n_lvl0);
         T->lastResiduals[lvl] = sqrtf((float)(resOld[0]/resOld[1]));
         T->lastFlow[0]=resOld[2]; T->lastFlow[1]=resOld[3]; T->lastFlow[2]=resOld[4];
         if (T->lastResiduals[lvl] > 1.5*minResForAbort[lvl]) { ok=0; break; }
         if (levelCutoffRepeat > 1 && !haveRepeated) { lvl++; haveRepeated=1; }
     }
+    T->have_repeated=haveRepeated;
     for (int i=0;i<5;i++) lastResiduals_out[i]=T->lastResiduals[i];
     for (int i=0;i<3;i++) lastFlow_out[i]=T->lastFlow[i];
     if (!ok) return 0;
@@ -461,3 +467,7 @@ int orc_trk_track(OrcTracker* T, const float* dI_new, double T_io[12], double af
 }
 void orc_trk_set_affine_modes(OrcTracker* T, double affA, double affB) { T->affA=affA; T->affB=affB; T->aff_set=1; }
 long orc_trk_counter(OrcTracker* T, int which) { return which ? T->n_calcgs : T->n_calcres; }
+/* calcRes evaluations per pyramid level of the last orc_trk_track: every call of calcRes counts (the first one of a level, its cutoff repeats, every LM
+ * candidate; a level run twice through haveRepeated adds both runs to its entry) - what trk_lm_kernel's evals_lvl and nalo_trk_last_evals count.
+ * Returns haveRepeated: whether a level was re-run. */
+int orc_trk_last_evals(OrcTracker* T, int evals[5]) { for (int i=0;i<5;i++) evals[i]=T->evals_lvl[i]; return T->have_repeated; }

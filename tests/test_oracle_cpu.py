@@ -98,6 +98,25 @@ def _tracker(win, kind="f32"):
     return trk, dI_new
 
 
+def test_tracker_counts_its_evaluations_per_level(small_window):
+    """Tracker.last_evals: every calcRes call of the last track() is counted on its level (cutoff repeats and a re-run level included), the counts add up
+    to the calls made, and haveRepeated is reported. A brightness jump the start estimate does not know (+45 grey levels) saturates the coarsest level's
+    residuals: the cutoff-repeat loop and the re-run of that level follow."""
+    win = small_window
+    trk, _ = _tracker(win)
+    T0 = orc.se3_exp(orc.se3_log(true_rel_pose(win, win.W - 1, win.W)) * 0.9)
+    top = win.levels - 1
+    for off, want_rep in ((0.0, False), (45.0, True)):
+        dI_new, _ = orc.make_images(win.images[win.W] + np.float32(off), win.levels)
+        n0 = trk.L.orc_trk_counter(trk.h_, 0)
+        ok = trk.track(dI_new, T0, [0, 0], [0, 0], [1, 1], top)[0]
+        ev, rep = trk.last_evals()
+        assert ok == 1 and ev.sum() == trk.L.orc_trk_counter(trk.h_, 0) - n0 and (ev[:win.levels] >= 2).all(), ev
+        assert rep == want_rep, (ev, rep)
+        if want_rep:                                       # the first run of the coarsest level doubled its cutoff at least twice, the re-run did not
+            assert ev[top] >= 6
+
+
 def test_tracker_gradient_matches_finite_differences(small_window):
     """b (Vec8) is the gradient of the mean energy w.r.t. the scaled left increment: compare with central differences of
     calcRes' energy (Huber inactive region dominates; image gradients are interpolated, not exact): 10% + absolute floor."""
