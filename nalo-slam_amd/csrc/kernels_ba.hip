@@ -142,11 +142,7 @@ __global__ __launch_bounds__(64 * NW) void ba_sc_kernel(BADev B, int margOnly, i
     // fp32 levels for 1000 adds, MatrixAccumulators.h), so the ~100x cancellation in H_A - H_sc does not amplify summation noise into the poses.
     // Round 4 measured 64-point runs: 4 % (250 k points) to 9 % (1 M) faster on this kernel, but the solved step of the well-conditioned toy window moves from
     // 1.0x to 1.6x the fp32 oracle's own distance to the fp64 truth (tests/test_ba_gpu.py::test_solve_and_step_on_the_well_conditioned_window): not taken.
-#ifdef SC_RUN
-    constexpr int RUN = SC_RUN < SUB ? SC_RUN : SUB;
-#else
     constexpr int RUN = 16;
-#endif
     // this wave's upper-triangular tiles (row-major enumeration of ti <= tj): wave, wave + 4, ...
     constexpr int NTILES = T * (T + 1) / 2, MAXM = (NTILES + NW - 1) / NW;
     const int wave = tid >> 6, lane = tid & 63;
@@ -303,14 +299,11 @@ __global__ __launch_bounds__(64 * NW) void ba_sc_kernel(BADev B, int margOnly, i
     }
 }
 
-#ifndef SC_NW
-#define SC_NW 8
-#endif
-// large windows run the SYRK with SC_NW waves per workgroup: eight waves hold two or three 16x16 tiles each instead of five or six (the fp32 + fp64 accumulators
+// large windows run the SYRK with eight waves per workgroup: eight waves hold two or three 16x16 tiles each instead of five or six (the fp32 + fp64 accumulators
 // of six tiles cost 72 registers: two waves per SIMD), so four waves per SIMD take turns on the matrix pipe
 template <int KS>
 static void launch_sc_ks(hipStream_t s, const BADev& B, int T, int margOnly, int shift, float priorScaleMarg) {
-    constexpr int NW = KS == 1 ? SC_NW : 4;
+    constexpr int NW = KS == 1 ? 8 : 4;
     const int grid = B.sc_groups * KS;
     switch (T) {
         case 1: ba_sc_kernel<1, KS, 4><<<grid, 256, 0, s>>>(B, margOnly, shift, priorScaleMarg); break;        // one tile: nothing to deal out
@@ -545,23 +538,14 @@ void ba_launch_reduce(hipStream_t s, const BADev& B, const int* host_blk, int NP
 // SC rows of frame a. FAST: every operand is staged in LDS with coalesced single-pass loads (phase 1: G_a, the slot rows of the other hosts'
 // G_i and frame a's adjoints; phase 2: all adjoints, over the same region) so the inner 8-wide loops run on ds_read with no global latency
 // in the dependency chain. The generic path (large windows, LDS too small) reads G and the adjoints through L2.
-#ifdef NALO_STITCH_TICKS
-#define STITCH_TICK(i) do { __syncthreads(); tk[i] = clock64(); } while (0)
-#else
-#define STITCH_TICK(i) do { } while (0)
-#endif
 constexpr int kAdRow = 9, kAdMat = 73;        // padded 8x8 adjoint in LDS
 // WC: the window size as a compile-time constant (0 = run time). With it the 2 x (W - 1) x 8-term sums of phase 2 and the 56-term sums of phase 1 unroll, and
 // their LDS loads are issued in batches instead of one dependent group per loop trip (W = 8, headline window: phase 2 9.4 -> see DESIGN 5).
 template <bool FAST, int WC, typename Put>
 __device__ __forceinline__ void stitch_sc_rows(const StitchDev& D, double* lds, int a, int r0, int nr, Put put) {      // rows r0 .. r0 + nr - 1 of frame a's eight
     const int W = WC ? WC : D.W, n1 = WC ? 8 * WC + 5 : D.n1, n = n1 - 1, NPL = WC ? 16 * ((8 * (WC - 1) + 5 + 15) / 16) : D.NPL, tid = threadIdx.x, NT = blockDim.x, cb = 8 * (W - 1);
-#ifdef NALO_STITCH_TICKS
-    long long tk[5] = {0, 0, 0, 0, 0};
-#endif
     double* U = lds;                                           // [W][8][NPL]
     double* R = U + W * 8 * NPL;                               // staging region (FAST)
-    STITCH_TICK(0);
     if constexpr (FAST) {
         double* Ga = R;                                        // [NPL][NPL]
         double* Gi = Ga + NPL * NPL;                           // [W][8][NPL]: rows of slot g_i(a) of host i != a
@@ -578,7 +562,6 @@ __device__ __forceinline__ void stitch_sc_rows(const StitchDev& D, double* lds, 
             if (f != a) { Ah[e] = D.AD[(size_t)(a + f * W) * 64 + o]; At[e] = D.AD[(size_t)W * W * 64 + (size_t)(f + a * W) * 64 + o]; }
         }
         __syncthreads();
-        STITCH_TICK(1);
         for (int e = tid; e < W * nr * NPL; e += NT) {
             const int i = e / (nr * NPL), o = e - i * nr * NPL, r = r0 + o / NPL, l = o % NPL;
             double s = 0;
@@ -597,11 +580,9 @@ __device__ __forceinline__ void stitch_sc_rows(const StitchDev& D, double* lds, 
             U[(i * 8 + r) * NPL + l] = s;
         }
         __syncthreads();
-        STITCH_TICK(2);
         // padded copy of all adjoints: row stride 9, matrix stride 73 doubles -> the (cp, j) pattern of phase 2 spreads over the LDS banks
         for (int e = tid; e < 2 * W * W * 64; e += NT) R[(e >> 6) * kAdMat + ((e >> 3) & 7) * kAdRow + (e & 7)] = D.AD[e];
         __syncthreads();
-        STITCH_TICK(3);
     } else {
         for (int e = tid; e < W * nr * NPL; e += NT) {
             const int i = e / (nr * NPL), o = e - i * nr * NPL, r = r0 + o / NPL, l = o % NPL;
@@ -654,22 +635,12 @@ __device__ __forceinline__ void stitch_sc_rows(const StitchDev& D, double* lds, 
         }
     };
     if constexpr (FAST) phase2(R, R + W * W * kAdMat, kAdMat, kAdRow); else phase2(D.AD, D.AD + (size_t)W * W * 64, 64, 8);
-    STITCH_TICK(4);
-#ifdef NALO_STITCH_TICKS
-    if (tid == 0) printf("sc a=%d stage1=%lld ph1=%lld stage2=%lld ph2=%lld\n", a, tk[1] - tk[0], tk[2] - tk[1], tk[3] - tk[2], tk[4] - tk[3]);
-#endif
 }
 
-#ifndef NALO_STITCH_SC_SPLIT
-#define NALO_STITCH_SC_SPLIT 8
-#endif
-#ifndef NALO_STITCH_TOP_SPLIT
-#define NALO_STITCH_TOP_SPLIT 8
-#endif
-constexpr int kTopSplit = NALO_STITCH_TOP_SPLIT;     // workgroups per frame for the rows of the top system (8 / kTopSplit rows each): with the Schur-complement rows on
+constexpr int kTopSplit = 8;                         // workgroups per frame for the rows of the top system (8 / kTopSplit rows each): with the Schur-complement rows on
                                                      // eight workgroups the top system's one workgroup per frame was the long pole. 1 / 2 / 4 / 8: 11.2 / 10.3 / 11.3 / 10.7 us
                                                      // at W = 8 (noise ~0.5), 14.3 / 13.1 / 12.0 / 10.9 us at W = 12
-constexpr int kScSplit = NALO_STITCH_SC_SPLIT;       // workgroups per frame for the Schur-complement rows (8 / kScSplit rows each). Round 3, kernel trace: 2 / 4 / 8 workgroups
+constexpr int kScSplit = 8;                          // workgroups per frame for the Schur-complement rows (8 / kScSplit rows each). Round 3, kernel trace: 2 / 4 / 8 workgroups
                                                      // = 13.6 / 12.1 / 11.3 us at W = 8 and 22.7 / 17.0 / 14.4 us at W = 12 (phase 2 is LDS-bandwidth bound; the operand
                                                      // staging every workgroup repeats is the smaller part). Same loops per output element: bit-identical results
 __global__ __launch_bounds__(1024) void ba_stitch_kernel(StitchDev D, int mask, int ad_in_lds, double* mapped, int ntail, double seq) {

@@ -32,13 +32,6 @@
 #include "ba_device.h"
 #include "reduce.h"
 
-#ifndef NALO_LIN_COOP_NPB
-#define NALO_LIN_COOP_NPB 2        // pattern pixels per gather batch: 2 (8 loads in flight per lane) x 4 waves per SIMD. Round-2 sweep (profiles/r02_tune_lin.log):
-#endif                             // 3 waves x 3+3+2 pixels 207.6 / 919.9 us (stress250k / shard1m), 4 x 2: 208.4 / 871.4, 4 x 3 (spills) 228.6 / 958.7, 5 x 2: 237.1 / 975.5
-#ifndef NALO_LIN_COOP_WAVES
-#define NALO_LIN_COOP_WAVES 4      // waves per SIMD the gather kernel's register allocation leaves room for (128 VGPRs)
-#endif
-
 namespace nalo {
 
 __device__ __forceinline__ float4 lin_bilinear(const float4* __restrict__ img, float x, float y, int width) {
@@ -123,24 +116,13 @@ __device__ __forceinline__ LinWhere lin_where(const BADev& B, int tid) {
 // The per-residual outputs (JpJdF, the point-sum shares, the energies: 64 B per residual, 114 MB on stress250k) are written once here and read once by the
 // next kernels: stored with the nontemporal hint they do not evict image lines from the L2 the gathers live in (stress250k: 203.0 -> 193.3 us on one box, back to
 // back; shard1m unchanged). The same hint on the point-record LOADS costs 3-5 % (they are re-read per target frame and do hit) - not used.
-#ifndef NALO_LIN_NT_STORES
-#define NALO_LIN_NT_STORES 1
-#endif
 typedef float lin_f4 __attribute__((ext_vector_type(4)));
 typedef float lin_f2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void lin_store(float4* p, const float4& v) {
-#if NALO_LIN_NT_STORES
     lin_f4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; __builtin_nontemporal_store(t, reinterpret_cast<lin_f4*>(p));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ void lin_store(float2* p, const float2& v) {
-#if NALO_LIN_NT_STORES
     lin_f2 t; t.x = v.x; t.y = v.y; __builtin_nontemporal_store(t, reinterpret_cast<lin_f2*>(p));
-#else
-    *p = v;
-#endif
 }
 
 // x = (Jpdc[0], Jpdxi[0]), y = (Jpdc[1], Jpdxi[1]) of a residual (Residuals.cpp:108-156) from the point and the precalc record. A function of its own so that the
@@ -362,8 +344,9 @@ template <int R_> __device__ __forceinline__ int lin_quad_bcast(int v) {        
 
 // MODE 0: active residuals (optimize). MODE 2: marginalisation of the flagged points (resApprox = res_toZeroF).
 // FIX: linearizeAll(true) — residuals that do not end IN are dropped; centerProjectedTo / relBS are stored.
+constexpr int kLinCoopWaves = 4;      // waves per SIMD the gather kernel's register allocation leaves room for (128 VGPRs)
 template <int MODE, int FIX, int WG>
-__global__ __launch_bounds__(WG, NALO_LIN_COOP_WAVES) void ba_linearize_kernel(BADev B) {
+__global__ __launch_bounds__(WG, kLinCoopWaves) void ba_linearize_kernel(BADev B) {
     __shared__ __attribute__((aligned(16))) float smem[(WG / 4) * kTopStride];
     static_assert(16 * kTopStride * 4 >= 4 * 65 * 16, "a wave's reduction rows must hold its exchange buffer");
     const int tid = threadIdx.x;
@@ -428,7 +411,9 @@ __global__ __launch_bounds__(WG, NALO_LIN_COOP_WAVES) void ba_linearize_kernel(B
             oX = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
             oY = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
         };
-        // a batch = two pattern pixels: 8 sixteen-byte loads in flight per lane, then the two exchanges, then (per lane) their photometric part
+        // a batch = two pattern pixels: 8 sixteen-byte loads in flight per lane, then the two exchanges, then (per lane) their photometric part. Two pixels per
+        // batch x 4 waves per SIMD. Round-2 sweep (profiles/r02_tune_lin.log): 3 waves x 3+3+2 pixels 207.6 / 919.9 us (stress250k / shard1m), 4 x 2: 208.4 / 871.4,
+        // 4 x 3 (spills) 228.6 / 958.7, 5 x 2: 237.1 / 975.5
         auto batch = [&](auto HALF) __attribute__((always_inline)) {
             constexpr int k0 = 2 * decltype(HALF)::value, k1 = k0 + 1;
             const int o0 = R.need ? pack(R.Kus[k0], R.Kvs[k0]) : 0, o1 = R.need ? pack(R.Kus[k1], R.Kvs[k1]) : 0;
@@ -439,24 +424,7 @@ __global__ __launch_bounds__(WG, NALO_LIN_COOP_WAVES) void ba_linearize_kernel(B
             exchange(b0_, b1_, b2_, b3_, R.Kus[k1], R.Kvs[k1], h1I, h1X, h1Y);
             if (R.need) { lin_pixel<MODE>(R, w.pc, h0I, h0X, h0Y, color[k0], wgt[k0], fixA, fixB); lin_pixel<MODE>(R, w.pc, h1I, h1X, h1Y, color[k1], wgt[k1], fixA, fixB); }
         };
-#if NALO_LIN_COOP_NPB == 3
-        // 3 + 3 + 2 pattern pixels: 12 loads in flight per lane
-        auto batch3 = [&](auto FIRST) __attribute__((always_inline)) {
-            constexpr int k0 = decltype(FIRST)::value, k1 = k0 + 1, k2 = k0 + 2;
-            const int o0 = R.need ? pack(R.Kus[k0], R.Kvs[k0]) : 0, o1 = R.need ? pack(R.Kus[k1], R.Kvs[k1]) : 0, o2 = R.need ? pack(R.Kus[k2], R.Kvs[k2]) : 0;
-            const LinTexel a0 = tap(lin_quad_bcast<0>(o0)), a1 = tap(lin_quad_bcast<1>(o0)), a2 = tap(lin_quad_bcast<2>(o0)), a3 = tap(lin_quad_bcast<3>(o0));
-            const LinTexel b0_ = tap(lin_quad_bcast<0>(o1)), b1_ = tap(lin_quad_bcast<1>(o1)), b2_ = tap(lin_quad_bcast<2>(o1)), b3_ = tap(lin_quad_bcast<3>(o1));
-            const LinTexel c0_ = tap(lin_quad_bcast<0>(o2)), c1_ = tap(lin_quad_bcast<1>(o2)), c2_ = tap(lin_quad_bcast<2>(o2)), c3_ = tap(lin_quad_bcast<3>(o2));
-            float h0I, h0X, h0Y, h1I, h1X, h1Y, h2I, h2X, h2Y;
-            exchange(a0, a1, a2, a3, R.Kus[k0], R.Kvs[k0], h0I, h0X, h0Y);
-            exchange(b0_, b1_, b2_, b3_, R.Kus[k1], R.Kvs[k1], h1I, h1X, h1Y);
-            exchange(c0_, c1_, c2_, c3_, R.Kus[k2], R.Kvs[k2], h2I, h2X, h2Y);
-            if (R.need) { lin_pixel<MODE>(R, w.pc, h0I, h0X, h0Y, color[k0], wgt[k0], fixA, fixB); lin_pixel<MODE>(R, w.pc, h1I, h1X, h1Y, color[k1], wgt[k1], fixA, fixB); lin_pixel<MODE>(R, w.pc, h2I, h2X, h2Y, color[k2], wgt[k2], fixA, fixB); }
-        };
-        batch3(std::integral_constant<int, 0>{}); batch3(std::integral_constant<int, 3>{}); batch(std::integral_constant<int, 3>{});
-#else
         batch(std::integral_constant<int, 0>{}); batch(std::integral_constant<int, 1>{}); batch(std::integral_constant<int, 2>{}); batch(std::integral_constant<int, 3>{});
-#endif
     }
     lin_commit<MODE, FIX>(B, w, R);
     if (FIX == 2) {

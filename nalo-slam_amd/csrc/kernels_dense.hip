@@ -58,10 +58,7 @@ struct DenseParams {
     float* out6;                                 // {minx, maxx, miny, maxy, minz, maxz} of the serial loop
     int* n_out;
 };
-#ifndef NALO_DENSE_CHUNK
-#define NALO_DENSE_CHUNK 1024    // pixels of the box per workgroup. Round 4: 2048 -> 1024 (twice the workgroups for the 256 CUs: 764 instead of 382 on the 460 x 1700 box of the bench)
-#endif
-constexpr int kDenseChunk = NALO_DENSE_CHUNK;
+constexpr int kDenseChunk = 1024;    // pixels of the box per workgroup. Round 4: 2048 -> 1024 (twice the workgroups for the 256 CUs: 764 instead of 382 on the 460 x 1700 box of the bench)
 // e / rw and e % rw for 0 <= e < 2^24 without the ~40-instruction integer division: float quotient, one correction step either way
 struct DnDiv { int rw; float rcp; };
 __device__ __forceinline__ void dn_divmod(const DnDiv& d, int e, int& q, int& r) {

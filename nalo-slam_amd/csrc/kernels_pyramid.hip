@@ -93,28 +93,15 @@ __device__ __forceinline__ float pyr_box_at(const float* __restrict__ I0, int w0
         return 0.25f * (((a + b) + c) + d);
     }
 }
-#ifndef NALO_PYR_TW
-#define NALO_PYR_TW 64      // tile of level 0 per workgroup. Same box, 1920x1072 (5 levels) / 1224x368 (4 levels, one launch): 64x32 17.9 / 8.3 us, 32x32 19.0 / 7.2,
-#define NALO_PYR_TH 16      // **64x16 17.7 / 6.6**, 32x16 21.2 / 7.1, 128x16 18.2 / 8.4: twice the workgroups of 64x32 for the KITTI frame's 240 tiles (< 256 CUs)
-#endif
-#ifndef NALO_PYR_NT
-#define NALO_PYR_NT 1      // nontemporal stores of the texels: 14.6 -> 12.9 us at 1920x1072 (the pyramid is written once, read by later kernels)
-#endif
-constexpr int kPyrTW = NALO_PYR_TW, kPyrTH = NALO_PYR_TH;
+constexpr int kPyrTW = 64, kPyrTH = 16;   // tile of level 0 per workgroup. Same box, 1920x1072 (5 levels) / 1224x368 (4 levels, one launch): 64x32 17.9 / 8.3 us, 32x32 19.0 / 7.2,
+                                          // **64x16 17.7 / 6.6**, 32x16 21.2 / 7.1, 128x16 18.2 / 8.4: twice the workgroups of 64x32 for the KITTI frame's 240 tiles (< 256 CUs)
+// nontemporal stores of the texels: 14.6 -> 12.9 us at 1920x1072 (the pyramid is written once, read by later kernels)
 typedef float pyr_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void pyr_store(float4* p, float c, float dx, float dy) {
-#if NALO_PYR_NT
     pyr_f4 t; t.x = c; t.y = dx; t.z = dy; t.w = 0.f; __builtin_nontemporal_store(t, reinterpret_cast<pyr_f4*>(p));
-#else
-    *p = make_float4(c, dx, dy, 0.f);
-#endif
 }
 __device__ __forceinline__ void pyr_store(float* p, float v) {
-#if NALO_PYR_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 template <int NL> struct PyrLds {                              // LDS layout of the staged levels 0 .. NL-1 (with halo) and of the halo-free levels above
     static constexpr int H = 1 << (NL - 1);
@@ -179,12 +166,8 @@ __device__ __forceinline__ void pyr_emit_level(const PyrLevels& P, const float* 
 // level 4); a lane folds a 4 x 4 block of level 0 (four 16-byte loads) into one value of level 2 - the same 0.25f * (((a + b) + c) + d) nesting, twice -, the levels
 // 3 and 4 follow in LDS. The flat-index neighbours of the border columns (I_l(w_l - 1, y - 1) left of x = 0, I_l(0, y + 1) right of x = w_l - 1) are rebuilt the
 // same way by the border tiles: 4 (level 3) or 16 (level 4) extra level-2 values each. Read amplification (kCW + 4)(kCH + 4) / (kCW kCH) on 4 of ~25 bytes per pixel.
-#ifndef NALO_PYR_CW
-#define NALO_PYR_CW 16
-#define NALO_PYR_CH 4
-#endif
 struct PyrCoarse {
-    static constexpr int kCW = NALO_PYR_CW, kCH = NALO_PYR_CH;              // tile of level 3 (level 4: kCW / 2 x kCH / 2)
+    static constexpr int kCW = 16, kCH = 4;                                 // tile of level 3 (level 4: kCW / 2 x kCH / 2)
     static constexpr int R3W = kCW + 4, R3H = kCH + 4, R2W = 2 * R3W, R2H = 2 * R3H, R4W = kCW / 2 + 2, R4H = kCH / 2 + 2;
     static constexpr int N2 = R2W * R2H, N3 = R3W * R3H, N4 = R4W * R4H;
     static constexpr int NX3 = 4 * kCH, NX4 = 16 * (kCH / 2);              // extra level-2 values per border side: level 3 / level 4 edge values
@@ -318,15 +301,6 @@ __device__ __forceinline__ void pyr_box_level(const PyrLevels& P, float* __restr
         }
     }
 }
-#ifndef NALO_PYR_EARLY
-#define NALO_PYR_EARLY 1
-#endif
-#ifndef NALO_PYR_LD4
-#define NALO_PYR_LD4 1
-#endif
-#ifndef NALO_PYR_COARSE
-#define NALO_PYR_COARSE 1
-#endif
 template <int NL, int LV>
 __device__ __forceinline__ void pyr_walk(const PyrLevels& P, float* __restrict__ lds, const float* __restrict__ edge, const float* __restrict__ gammaB, int x0, int y0, int tid, int Lbox) {
     if constexpr (LV <= NALO_MAX_LEVELS) {                      // step LV: emit level LV - 1 (complete since the last barrier), box level LV out of it
@@ -357,7 +331,6 @@ __global__ __launch_bounds__(256) void pyr_one_pass_kernel(PyrLevels P, const fl
         const float* __restrict__ I0 = P.I[0];
         // all loads of the tile first (registers), then the LDS stores: a rolled loop waits for every load before its own LDS store, i.e. a dozen
         // dependent HBM round trips per tile (measured: 8 us for ONE tile of a KITTI frame)
-#if NALO_PYR_LD4
         // round 4: the haloed tile starts H = 4 or 8 pixels left of a multiple of 64, so with w0 % 4 == 0 every aligned group of four pixels lies wholly inside or
         // wholly outside the image: 16-byte loads (432 / 640 per tile instead of 1728 / 2560 4-byte ones); any other width takes the scalar loop
         static_assert(RW % 4 == 0 && H % 4 == 0 || NL < 3, "haloed row in whole float4s");
@@ -373,22 +346,20 @@ __global__ __launch_bounds__(256) void pyr_one_pass_kernel(PyrLevels P, const fl
             }
 #pragma unroll
             for (int k = 0; k < N4; ++k) { const int i = tid + 256 * k; if (i < RW4 * RH) { pyr_f4 t = v4[k]; if (!in4[k]) t = pyr_f4{0.f, 0.f, 0.f, 0.f}; *reinterpret_cast<pyr_f4*>(lds + 4 * i) = t; } }
-        } else
-#endif
-        {
-        constexpr int NLD = (RW * RH + 255) / 256;
-        float v[NLD];
-        bool inb[NLD];
+        } else {
+            constexpr int NLD = (RW * RH + 255) / 256;
+            float v[NLD];
+            bool inb[NLD];
 #pragma unroll
-        for (int k = 0; k < NLD; ++k) {                         // branch-free: an out-of-image lane loads pixel 0 and discards it (a load under a divergent
-            const int i = tid + 256 * k, rx = i % RW, ry = i / RW, gx = x0 - H + rx, gy = y0 - H + ry;   // branch is waited for at the join: one round trip each)
-            inb[k] = i < RW * RH && gx >= 0 && gx < w0 && gy >= 0 && gy < h0;
-            v[k] = I0[inb[k] ? gx + gy * w0 : 0];
-        }
+            for (int k = 0; k < NLD; ++k) {                     // branch-free: an out-of-image lane loads pixel 0 and discards it (a load under a divergent
+                const int i = tid + 256 * k, rx = i % RW, ry = i / RW, gx = x0 - H + rx, gy = y0 - H + ry;   // branch is waited for at the join: one round trip each)
+                inb[k] = i < RW * RH && gx >= 0 && gx < w0 && gy >= 0 && gy < h0;
+                v[k] = I0[inb[k] ? gx + gy * w0 : 0];
+            }
 #pragma unroll
-        for (int k = 0; k < NLD; ++k) v[k] = inb[k] ? v[k] : 0.f;
+            for (int k = 0; k < NLD; ++k) v[k] = inb[k] ? v[k] : 0.f;
 #pragma unroll
-        for (int k = 0; k < NLD; ++k) { const int i = tid + 256 * k; if (i < RW * RH) lds[i] = v[k]; }
+            for (int k = 0; k < NLD; ++k) { const int i = tid + 256 * k; if (i < RW * RH) lds[i] = v[k]; }
         }
         // the flat-index neighbours of the border columns (only border tiles load anything): wave l owns level l, so the four levels' dependent loads run
         // side by side instead of as four masked branches of one wave
@@ -402,21 +373,9 @@ __global__ __launch_bounds__(256) void pyr_one_pass_kernel(PyrLevels P, const fl
 
     }
     __syncthreads();
-#if NALO_PYR_EARLY
     // round 4: level l leaves for HBM while level l + 1 is being boxed out of it (both only READ level l's LDS image): the texel stores drain under the rest of
     // the LDS walk instead of forming one store phase at the end of every (lockstep) workgroup
     pyr_walk<NL, 1>(P, lds, edge, gammaB, x0, y0, tid, Lbox);
-#else
-#pragma unroll
-    for (int l = 1; l < NALO_MAX_LEVELS; ++l) {                 // the box pyramid inside LDS: levels < NL over the haloed region, the ones above over the tile only
-        if (l < Lbox) pyr_box_level<NL>(P, lds, l, x0, y0, tid);
-        __syncthreads();
-    }
-    pyr_emit_level<NL, 0>(P, lds, edge, gammaB, x0, y0, tid);
-    if constexpr (NL > 1) pyr_emit_level<NL, 1>(P, lds, edge, gammaB, x0, y0, tid);
-    if constexpr (NL > 2) pyr_emit_level<NL, 2>(P, lds, edge, gammaB, x0, y0, tid);
-    if constexpr (NL > 3) pyr_emit_level<NL, 3>(P, lds, edge, gammaB, x0, y0, tid);
-#endif
 }
 // gradients of the levels >= l0 from their planar box values (the second launch of a pyramid with more than four levels)
 __global__ __launch_bounds__(256) void pyr_grad_tail_kernel(PyrLevels P, const float* __restrict__ gammaB, int l0) {
@@ -472,14 +431,12 @@ __device__ __forceinline__ void ingest_pair(const void* __restrict__ raw, int p,
     else { uint32_t v; __builtin_memcpy(&v, reinterpret_cast<const uint16_t*>(raw) + p, 4); a = v & 0xFFFFu; b = v >> 16; }
 }
 // Round 4: a pixel is a chain of two dependent round trips (remap entry -> taps), and with one pixel per lane a 1920x1072 frame is four rounds of the
-// resident grid: ~8 round trips end to end (15 us at 0.30 of the roofline). Now every lane owns NALO_INGEST_U pixels (stride 256 inside its workgroup's run of consecutive
+// resident grid: ~8 round trips end to end (15 us at 0.30 of the roofline). Now every lane owns four pixels (stride 256 inside its workgroup's run of consecutive
 // pixels: every instruction still covers one contiguous run per wave): the U remap loads leave together, then the 4 U taps, then the stores - the whole frame is resident at once.
-#ifndef NALO_INGEST_U
-#define NALO_INGEST_U 4
-#endif
+constexpr int kIngestU = 4;
 template <int BPP, int PHOTO>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestParams P) {
-    constexpr int U = NALO_INGEST_U;
+    constexpr int U = kIngestU;
     __shared__ float sG[BPP == 1 && PHOTO > 0 ? 256 : 1];
     // the 8-bit response table goes to LDS BEHIND the issue of the pixel loads (its own load leaves first, the LDS store and the barrier follow the taps' issue): staged
     // in front of them it was a third round trip at the head of every workgroup
@@ -554,7 +511,7 @@ int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOr
     P.raw = raw; P.bpp = bpp; P.wOrg = wOrg; P.hOrg = hOrg; P.w = c->w; P.h = c->h; P.G = G; P.vinv = vinv; P.remapXY = remapXY; P.photometric = photometric;
     P.factor = factor; P.mask_org = mask_org; P.bgr_org = bgr_org; P.out_I = out_I; P.out_mask = out_mask; P.out_bgr = out_bgr;
     P.ifx = 1.0 / ((double)c->w / wOrg); P.ify = 1.0 / ((double)c->h / hOrg);
-    const int n = c->w * c->h, grid = (n + 256 * NALO_INGEST_U - 1) / (256 * NALO_INGEST_U);   // NALO_INGEST_U pixels per lane, consecutive workgroups on consecutive memory
+    const int n = c->w * c->h, grid = (n + 256 * kIngestU - 1) / (256 * kIngestU);   // four pixels per lane, consecutive workgroups on consecutive memory
     ProfScope ps(c, "ingest", true);                                       // dispatch-attached timestamps
 #define NALO_INGEST(B_, P_) do { if (ps.a) hipExtLaunchKernelGGL((ingest_kernel<B_, P_>), dim3(grid), dim3(256), 0, st, ps.a, ps.b, 0, P); else ingest_kernel<B_, P_><<<grid, 256, 0, st>>>(P); } while (0)
     if (bpp == 1) { if (photometric == 0) NALO_INGEST(1, 0); else if (photometric == 1) NALO_INGEST(1, 1); else NALO_INGEST(1, 2); }
@@ -635,7 +592,7 @@ int pyramid_build(nalo_ctx* c, FrameSlot& s, const float* gammaB_dev) {
             default: {
                 // five levels: the levels 3 and 4 by the first workgroups of the same launch (pyr_coarse_tile; the 16-byte loads want w0 % 16 == 0, which five even levels imply)
                 const int nc = ((c->wl[3] + PyrCoarse::kCW - 1) / PyrCoarse::kCW) * ((c->hl[3] + PyrCoarse::kCH - 1) / PyrCoarse::kCH);
-                if (NALO_PYR_COARSE && c->levels == 5) { NALO_PYR1(3, nc, ps.a, ps.b); break; }
+                if (c->levels == 5) { NALO_PYR1(3, nc, ps.a, ps.b); break; }
                 NALO_PYR1(3, 0, ps.a, nullptr);
                 if (ps.a) hipExtLaunchKernelGGL(pyr_grad_tail_kernel, dim3(nb - P.blk0[3]), dim3(256), 0, c->stream, nullptr, ps.b, 0, P, gammaB_dev, 3);
                 else pyr_grad_tail_kernel<<<nb - P.blk0[3], 256, 0, c->stream>>>(P, gammaB_dev, 3);

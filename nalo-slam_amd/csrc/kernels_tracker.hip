@@ -38,10 +38,7 @@ __device__ __forceinline__ float4 bilinear4(const float4* __restrict__ img, floa
     return r;
 }
 
-#ifndef NALO_TRK_EVAL_NT
-#define NALO_TRK_EVAL_NT 512
-#endif
-constexpr int kTrkEvalNT = NALO_TRK_EVAL_NT;      // lanes per workgroup of the evaluation. 256 -> 512 (round 4, same box): half as many grid-stride rounds at 250 k points and half as many
+constexpr int kTrkEvalNT = 512;                   // lanes per workgroup of the evaluation. 256 -> 512 (round 4, same box): half as many grid-stride rounds at 250 k points and half as many
                                                   // partial rows for the last workgroup: 21.0 -> 19.0 us at 250 k points, 40.0 -> 35.7 us at full density (1920x1072)
 constexpr int kTrkEvalNG = kTrkEvalNT / 13;        // lane groups of the last workgroup's sum: 13 lanes x 16 bytes = one block's 52 partials
 __global__ __launch_bounds__(kTrkEvalNT) void trk_eval_kernel(TrkEvalParams P, float* __restrict__ partial, unsigned* __restrict__ ticket, double* __restrict__ out, double seq) {

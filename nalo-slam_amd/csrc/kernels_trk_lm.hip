@@ -2,7 +2,7 @@
 //
 // The reference's LM loop does up to ~180 calcRes/calcGSSSE evaluations per frame with an 8x8 solve and an SE3::exp in between. Driven from the host every
 // evaluation costs a launch + a completion round trip (~19 us) although the kernels themselves run a few microseconds on a KITTI-sized point cloud: the loop
-// is latency bound. Here ONE persistent launch of up to NALO_LM_MAX_BLOCKS (64) workgroups of NALO_LM_THREADS (512) lanes runs the whole pyramid descent, ALL levels:
+// is latency bound. Here ONE persistent launch of up to kLmMaxBlocks (64) workgroups of kLmThreads (512) lanes runs the whole pyramid descent, ALL levels:
 // every workgroup evaluates its share of the level's points (fused calcRes + calcGS), reduces it (DPP quad adds -> LDS rows -> fp64 column sums) and
 // publishes the partial as 8-byte {fp32 value, tag} words (agent-scope atomics: the data is the arrival flag, double-buffered by evaluation parity, bounded
 // poll); then EVERY workgroup sums the partials in a fixed order and replays the control flow on its wave 0: 8x8 LDL^T with one matrix row per lane and
@@ -19,19 +19,7 @@ namespace nalo {
 // lanes per workgroup: 512 (one point per lane and round, half as many workgroups as with 256 lanes -> half as many partials to exchange and to
 // sum in every workgroup per evaluation; 214 VGPRs, no spill). Headline window, same box, back to back: 256: 696, 384: 708, **512: 717-769**, 768 (spills): 670-678,
 // 1024 (spills): 633-640 keyframes/s.
-#ifndef NALO_LM_THREADS
-#define NALO_LM_THREADS 512
-#endif
-#ifndef NALO_LM_G
-#define NALO_LM_G 1
-#endif
-#ifndef NALO_LM_CACHE_PT
-#define NALO_LM_CACHE_PT 1
-#endif
-#ifndef NALO_LM_MAX_BLOCKS
-#define NALO_LM_MAX_BLOCKS 64
-#endif
-constexpr int kLmThreads = NALO_LM_THREADS;
+constexpr int kLmThreads = 512;
 constexpr int kLmVals = 52;                  // 45 H entries + E, nE, nSat, nWarped, sT, sRT, sN (same order as trk_eval_kernel)
 constexpr int kLmStride = 56;
 
@@ -216,20 +204,11 @@ __device__ __forceinline__ int lm_max_iterations(int lvl) { return lvl == 0 ? 10
 // evaluation number. A reader polls the words of the blocks it sums until their tags match: the data IS the arrival flag, so there is no
 // counter, no fence and no second round trip (the scheme of low-latency collective protocols). Slots are double-buffered by evaluation
 // parity: a block can run at most one evaluation ahead of the slowest reader, because the next one needs that reader's own partial.
-// The grid is small (<= NALO_LM_MAX_BLOCKS workgroups, far below the 256 CUs) so all blocks are co-resident; the poll is bounded anyway, a
+// The grid is small (<= 2 kLmMaxBlocks workgroups, far below the 256 CUs) so all blocks are co-resident; the poll is bounded anyway, a
 // lost block ends the kernel with an error instead of hanging the device.
 __device__ __forceinline__ unsigned long long lm_pack(float v, unsigned tag) { return ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v); }
 
-// NALO_LM_TICKS: per-phase shader-clock accounting of block 0 (debug builds only), reported in out[26..30]
-#ifdef NALO_LM_TICKS
-#define LM_TICK(i) do { if (tid == 0) { const long long now__ = clock64(); if ((i) > 0) tick_sum[(i) - 1] += now__ - tick_last; else if (tick_last) tick_sum[4] += now__ - tick_last; tick_last = now__; } } while (0)
-#else
-#define LM_TICK(i) do { } while (0)
-#endif
 __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
-#ifdef NALO_LM_TICKS
-    long long tick_sum[5] = {0, 0, 0, 0, 0}, tick_last = 0;
-#endif
     __shared__ float rows[(kLmThreads / 4) * kLmStride];
     __shared__ double sums[64];
     __shared__ double part[kLmThreads / 64][64];
@@ -263,7 +242,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
     // phase 1: evaluation of an LM candidate (:1184)
     for (int guard = 0; guard < 4096; ++guard) {
         if (S.done) break;
-        LM_TICK(0);
         // ------------------------------------------------------------- fused calcRes + calcGS over this level's points
         const TrkLmLevel& L = P.lv[S.lvl];
         float acc[kLmVals];
@@ -277,13 +255,15 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
 #pragma unroll
             for (int q = 0; q < 9; ++q) { RK[q] = S.RKi[q]; Kq[q] = S.Ki[q]; }
             tt[0] = S.t[0]; tt[1] = S.t[1]; tt[2] = S.t[2];
-            // G points per lane per round in flight (point loads, then the texel gathers, then the arithmetic); the rounds stride over the grid
-            constexpr int G = NALO_LM_G;
+            // G = 1 point per lane per round in flight (point loads, then the texel gathers, then the arithmetic); the rounds stride over the grid. Two
+            // points per lane measured within +-2 %. The [G] arrays and one-trip g loops stay: written with scalars, the same
+            // evaluation compiles to a different instruction schedule
+            constexpr int G = 1;
             const int gthreads = NB * kLmThreads;
             // A level whose points fit ONE round of the grid (every level of a KITTI-sized cloud: <= 64 x 512 points) gives each lane one point for all the
             // ~5 evaluations of the level: it is loaded once and stays in four registers, which takes one of the two dependent memory round trips (point ->
             // texels) out of every later evaluation.
-            const bool one_round = NALO_LM_CACHE_PT && G == 1 && L.n <= gthreads;
+            const bool one_round = L.n <= gthreads;
             if (one_round && cached_lvl != lvl) {
                 const int i = blk * kLmThreads + tid, ii = i < L.n ? i : 0;
                 c_id = L.id[ii]; c_x = L.u[ii]; c_y = L.v[ii]; c_rc = L.col[ii];
@@ -360,7 +340,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
                 }
             }
         }
-        LM_TICK(1);
         // ------------------------------------------------------------- block reduction (same scheme as reduce.h), then the grid sum
         const int nbl = min(NB, (L.n + kLmThreads - 1) / kLmThreads);          // blocks that own points of this level
         if (blk < nbl) {
@@ -385,7 +364,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
                 else __hip_atomic_store(&P.partial[((size_t)(S.evals & 1) * NB + blk) * 64 + tid], lm_pack((float)s, P.tag0 + (unsigned)S.evals), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        LM_TICK(2);
         if (NB > 1) {                                        // block partials -> every block sums them in the same fixed order
             const int j = tid & 63, g = tid >> 6;
             const unsigned long long* pp = P.partial + (size_t)(S.evals & 1) * NB * 64;
@@ -407,7 +385,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             if (tid < kLmVals) { double t2 = 0; for (int g2 = 0; g2 < kLmThreads / 64; ++g2) t2 += part[g2][tid]; sums[tid] = t2; }
         }
         __syncthreads();
-        LM_TICK(3);
         // ------------------------------------------------------------- wave 0 = the host of the reference
         // Scalars of the control flow are computed by every lane of the wave (uniform); the 8x8 solve puts one row per lane; lane 0 writes
         // the state back. Nothing here waits on memory other than a handful of LDS broadcasts.
@@ -513,7 +490,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             }
         }
         __syncthreads();
-        LM_TICK(4);
     }
     if (blk == 0 && tid == 0) {
         double* o = P.out;
@@ -524,22 +500,19 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
         for (int i = 0; i < 3; ++i) o[19 + i] = S.flow[i];
         if (ok && (fabsf((float)S.aff[0]) > 1.2f || fabsf((float)S.aff[1]) > 200.f)) ok = 2;   // :1243-1245: pose is still written, return false
         if (timed_out) ok = -1;
-#ifdef NALO_LM_TICKS
-        for (int i = 0; i < 5; ++i) o[26 + i] = (double)tick_sum[i];
-#else
         for (int i = 0; i < 5; ++i) o[26 + i] = (double)S.evals_lvl[i];
-#endif
         o[22] = (double)ok; o[23] = (double)S.evals; o[24] = (double)S.next_lvl; o[25] = (double)S.haveRepeated;
         __threadfence_system();
         __hip_atomic_store(&o[31], P.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
-// workgroups of the persistent launch for a largest level of maxn points: one per kLmThreads points, at most NALO_LM_MAX_BLOCKS (64) on KITTI-sized clouds (the
+// workgroups of the persistent launch for a largest level of maxn points: one per kLmThreads points, at most kLmMaxBlocks (64) on KITTI-sized clouds (the
 // exchange between them is the cost that grows), twice that once the largest level has 8+ rounds of the 64-workgroup grid (8 x 64 x 512 = 262 144 points;
 // 1920x1072, 250 k points: 513 us per frame with 64, 469 with 128, 499 with 192, 544 with 256)
+constexpr int kLmMaxBlocks = 64;
 int trk_lm_blocks(int maxn) {
-    const int max_blocks = (maxn >= 8 * NALO_LM_MAX_BLOCKS * kLmThreads ? 2 * NALO_LM_MAX_BLOCKS : NALO_LM_MAX_BLOCKS);
+    const int max_blocks = (maxn >= 8 * kLmMaxBlocks * kLmThreads ? 2 * kLmMaxBlocks : kLmMaxBlocks);
     return std::min(max_blocks, std::max(1, (maxn + kLmThreads - 1) / kLmThreads));
 }
 
@@ -580,9 +553,6 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
     if (!poll_flag(c, &c->trk_out_host[64 + 31], P.seq)) return NALO_ERR_HIP;
     std::memcpy(out24, c->trk_out_host + 64, sizeof(double) * 26);
     for (int i = 0; i < 5; ++i) c->lm_evals_lvl[i] = (int)c->trk_out_host[64 + 26 + i];
-#ifdef NALO_LM_TICKS
-    { const double* t = c->trk_out_host + 64 + 26; fprintf(stderr, "[lm ticks] evals=%d eval=%.0f blockred=%.0f gridsum=%.0f lane0=%.0f (shader clocks per eval)\n", (int)out24[23], t[0] / out24[23], t[1] / out24[23], t[2] / out24[23], t[3] / out24[23]); }
-#endif
     static const bool test_timeout = std::getenv("NALO_LM_TEST_TIMEOUT") != nullptr;          // tests: exercise the caller's degraded path once per context
     c->trk_cfg[8] = out24[25] != 0.0;
     if (out24[22] < 0 || (test_timeout && c->lm_launches == 1)) return NALO_LM_LOST_BLOCK;

@@ -1,5 +1,5 @@
 """the gate-cancel flow of tests/test_ba_gpu.py as a probe: N child processes per mode (plain / cancelled first optimize), the poses after restore + optimize hashed;
-every line should be the same. usage: gate_probe.py [repeats]   (through scripts/ab.sh for library variants)"""
+every line should be the same. usage: gate_probe.py [repeats]"""
 import hashlib, json, os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "tests"))

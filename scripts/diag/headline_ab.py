@@ -1,4 +1,4 @@
-"""A/B driver: the headline step alone, ms per keyframe (same box, library variants swapped by scripts/ab.sh)"""
+"""A/B driver: the headline step alone, ms per keyframe, timed on the library in the tree"""
 import os, sys, time, gc
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))

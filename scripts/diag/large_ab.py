@@ -1,4 +1,4 @@
-"""A/B driver: stress250k BA-only keyframe, ba_linearize mean, and the emulated N = 8 shard keyframe (same box, library variants swapped by scripts/ab.sh)"""
+"""A/B driver: stress250k BA-only keyframe, ba_linearize mean, and the emulated N = 8 shard keyframe, timed on the library in the tree"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
