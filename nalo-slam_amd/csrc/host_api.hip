@@ -2,6 +2,7 @@
 // src/FullSystem/CoarseTracker.{h,cpp}). The LM loop of trackNewestCoarse stays on the host exactly as in the
 // reference (8x8 LDL^T, SE3::exp); every calcRes/calcGSSSE pair is one fused kernel launch.
 #include "nalo_internal.h"
+#include "trk_device.h"
 #include <cstdlib>
 
 using namespace nalo;
@@ -467,16 +468,17 @@ int nalo_trk_eval(nalo_ctx* c, int slot_new, int lvl, const double R[9], const d
     double o[64];
     int rc = trk_eval_launch(c, slot_new, lvl, RKi, tf, Ki, affLL[0], affLL[1], b0, cutoffTH, maxEnergy, o);
     if (rc) return rc;
-    const double E = o[45], nE = o[46], nSat = o[47], nW = o[48], sT = o[49], sRT = o[50], sN = o[51];
+    const double E = o[kTrkE], nE = o[kTrkNE], nSat = o[kTrkNSat], nW = o[kTrkNWarped], sT = o[kTrkST], sRT = o[kTrkSRT], sN = o[kTrkSN];
     stats6[0] = E; stats6[1] = nE; stats6[2] = sT / (sN + 0.1); stats6[3] = 0; stats6[4] = sRT / (sN + 0.1);
     stats6[5] = (double)((float)nSat / (float)nE);
     if (want_gs) {
         const double npad = (double)(((long)nW + 3) & ~3L);          // divided by the padded count
         const double inv = 1.0 / npad;
         static const double sc[8] = {kScaleXiRot, kScaleXiRot, kScaleXiRot, kScaleXiTrans, kScaleXiTrans, kScaleXiTrans, kScaleA, kScaleB};
-        double Hf[81]; int k = 0;
-        for (int r = 0; r < 9; ++r) for (int cc = r; cc < 9; ++cc) { Hf[r * 9 + cc] = Hf[cc * 9 + r] = o[k]; ++k; }
-        for (int r = 0; r < 8; ++r) { for (int cc = 0; cc < 8; ++cc) H[r * 8 + cc] = Hf[r * 9 + cc] * inv * sc[r] * sc[cc]; b[r] = Hf[r * 9 + 8] * inv * sc[r]; }
+        for (int r = 0; r < 8; ++r) {
+            for (int cc = 0; cc < 8; ++cc) H[r * 8 + cc] = o[r < cc ? trk_ut(r, cc) : trk_ut(cc, r)] * inv * sc[r] * sc[cc];
+            b[r] = o[trk_ut(r, 8)] * inv * sc[r];
+        }
     }
     return NALO_OK;
 }

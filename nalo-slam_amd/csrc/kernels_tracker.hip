@@ -7,36 +7,19 @@
 // column sums -> one fp32 partial per block -> fp64 finish kernel (deterministic: no float atomics on sums).
 #include "nalo_internal.h"
 #include "reduce.h"
+#include "trk_device.h"
 
 namespace nalo {
 
 // ------------------------------------------------------------------------------------------------ a3 + a4
 struct TrkEvalParams {
-    const float *u, *v, *id, *col;
-    const float4* dI;
-    int n, wl, hl, lvl;
+    TrkLevel L;
+    int lvl;
     int i0, i1;                     // this rank's share [i0, i1) of the level's points (all of them unless the tracker is sharded, nalo_trk_set_shard)
-    float fx, fy, cx, cy;
     float RKi[9], t[3], Ki[9];
     float affa, affb, b0, cutoff, maxEnergy;
 };
 typedef float trk_f4 __attribute__((ext_vector_type(4)));
-constexpr int kTrkVals = 52;     // 45 upper-tri H entries + E, numTermsInE, numSaturated, numTermsInWarped, sT, sRT, sNum
-
-__device__ __forceinline__ float4 bilinear4(const float4* __restrict__ img, float x, float y, int width) {
-    // getInterpolatedElement33 (util/globalFuncs.h:75-89) on 16-byte texels
-    const int ix = (int)x, iy = (int)y;
-    const float dx = x - ix, dy = y - iy, dxdy = dx * dy;
-    const float4* bp = img + ix + iy * width;
-    const float4 p00 = bp[0], p10 = bp[1], p01 = bp[width], p11 = bp[1 + width];
-    const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-    float4 r;
-    r.x = w11 * p11.x + w01 * p01.x + w10 * p10.x + w00 * p00.x;
-    r.y = w11 * p11.y + w01 * p01.y + w10 * p10.y + w00 * p00.y;
-    r.z = w11 * p11.z + w01 * p01.z + w10 * p10.z + w00 * p00.z;
-    r.w = 0.f;
-    return r;
-}
 
 constexpr int kTrkEvalNT = 512;                   // lanes per workgroup of the evaluation. 256 -> 512 (round 4, same box): half as many grid-stride rounds at 250 k points and half as many
                                                   // partial rows for the last workgroup: 21.0 -> 19.0 us at 250 k points, 40.0 -> 35.7 us at full density (1920x1072)
@@ -46,56 +29,31 @@ __global__ __launch_bounds__(kTrkEvalNT) void trk_eval_kernel(TrkEvalParams P, f
     float acc[kTrkVals];
 #pragma unroll
     for (int k = 0; k < kTrkVals; ++k) acc[k] = 0.f;
-    const float wlm3 = (float)(P.wl - 3), hlm3 = (float)(P.hl - 3);
+    const TrkLevel& L = P.L;
+    const float wlm3 = (float)(L.wl - 3), hlm3 = (float)(L.hl - 3);
     for (int i = P.i0 + blockIdx.x * blockDim.x + threadIdx.x; i < P.i1; i += gridDim.x * blockDim.x) {
-        const float id = P.id[i], x = P.u[i], y = P.v[i];
-        const float pt0 = P.RKi[0] * x + P.RKi[1] * y + P.RKi[2] + P.t[0] * id;
-        const float pt1 = P.RKi[3] * x + P.RKi[4] * y + P.RKi[5] + P.t[1] * id;
-        const float pt2 = P.RKi[6] * x + P.RKi[7] * y + P.RKi[8] + P.t[2] * id;
-        const float u = pt0 / pt2, v = pt1 / pt2;
-        const float Ku = P.fx * u + P.cx, Kv = P.fy * v + P.cy;
-        const float new_idepth = id / pt2;
-        if (P.lvl == 0 && (i & 31) == 0) {                       // flow indicators, CoarseTracker.cpp:948-979
-            const float a0 = P.Ki[0] * x + P.Ki[1] * y + P.Ki[2], a1 = P.Ki[3] * x + P.Ki[4] * y + P.Ki[5], a2 = P.Ki[6] * x + P.Ki[7] * y + P.Ki[8];
-            const float T2 = a2 + P.t[2] * id, U2 = a2 - P.t[2] * id, r2 = P.RKi[6] * x + P.RKi[7] * y + P.RKi[8] - P.t[2] * id;
-            const float KuT = P.fx * ((a0 + P.t[0] * id) / T2) + P.cx, KvT = P.fy * ((a1 + P.t[1] * id) / T2) + P.cy;
-            const float KuT2 = P.fx * ((a0 - P.t[0] * id) / U2) + P.cx, KvT2 = P.fy * ((a1 - P.t[1] * id) / U2) + P.cy;
-            const float Ku3 = P.fx * ((P.RKi[0] * x + P.RKi[1] * y + P.RKi[2] - P.t[0] * id) / r2) + P.cx;
-            const float Kv3 = P.fy * ((P.RKi[3] * x + P.RKi[4] * y + P.RKi[5] - P.t[1] * id) / r2) + P.cy;
-            acc[49] += (KuT - x) * (KuT - x) + (KvT - y) * (KvT - y);
-            acc[49] += (KuT2 - x) * (KuT2 - x) + (KvT2 - y) * (KvT2 - y);
-            acc[50] += (Ku - x) * (Ku - x) + (Kv - y) * (Kv - y);
-            acc[50] += (Ku3 - x) * (Ku3 - x) + (Kv3 - y) * (Kv3 - y);
-            acc[51] += 2.f;
-        }
+        const float id = L.id[i], x = L.u[i], y = L.v[i];
+        float u, v, Ku, Kv, new_idepth;
+        trk_project(P.RKi, P.t, L, x, y, id, u, v, Ku, Kv, new_idepth);
+        if (P.lvl == 0 && (i & 31) == 0) trk_flow(acc, P.RKi, P.Ki, P.t, L, x, y, id, Ku, Kv);
         if (!(Ku > 2.f && Kv > 2.f && Ku < wlm3 && Kv < hlm3 && new_idepth > 0.f)) continue;      // :981
-        const float refColor = P.col[i];
-        const float4 hit = bilinear4(P.dI, Ku, Kv, P.wl);
+        const float refColor = L.col[i];
+        const float4* bp = L.dI + (int)Ku + (int)Kv * L.wl;                      // the taps are loaded only for points inside the level
+        const float3 hit = trk_interp(Ku, Kv, bp[0], bp[1], bp[L.wl], bp[1 + L.wl]);
         if (!isfinite(hit.x)) continue;
-        const float residual = hit.x - (P.affa * refColor + P.affb);
-        const float ar = fabsf(residual);
-        const float hw = ar < kHuberTH ? 1.f : kHuberTH / ar;
-        acc[46] += 1.f;                                          // numTermsInE
-        if (ar > P.cutoff) { acc[45] += P.maxEnergy; acc[47] += 1.f; }
+        float hw; const float residual = trk_residual(hit.x, refColor, P.affa, P.affb, hw);
+        acc[kTrkNE] += 1.f;
+        if (fabsf(residual) > P.cutoff) { acc[kTrkE] += P.maxEnergy; acc[kTrkNSat] += 1.f; }
         else {
-            acc[45] += hw * residual * residual * (2.f - hw);
-            acc[48] += 1.f;                                      // numTermsInWarped
-            const float dx = hit.y * P.fx, dy = hit.z * P.fy;
+            acc[kTrkE] += hw * residual * residual * (2.f - hw);
+            acc[kTrkNWarped] += 1.f;
             float J[9];
-            J[0] = new_idepth * dx;
-            J[1] = new_idepth * dy;
-            J[2] = -(new_idepth * (u * dx + v * dy));
-            J[3] = -(u * v * dx + dy * (1.f + v * v));
-            J[4] = u * v * dy + dx * (1.f + u * u);
-            J[5] = u * dy - v * dx;
-            J[6] = P.affa * (P.b0 - refColor);
-            J[7] = -1.f;
-            J[8] = residual;
+            trk_jacobian(J, hit, refColor, u, v, new_idepth, L.fx, L.fy, P.affa, P.b0, residual);
 #pragma unroll
             for (int r = 0; r < 9; ++r) {                    // constant indices after unrolling: acc[] stays in VGPRs (a running `k++` index sent it to scratch)
                 const float Jw = J[r] * hw;
 #pragma unroll
-                for (int c2 = r; c2 < 9; ++c2) acc[r * 9 - r * (r - 1) / 2 + (c2 - r)] += Jw * J[c2];
+                for (int c2 = r; c2 < 9; ++c2) acc[trk_ut(r, c2)] += Jw * J[c2];
             }
         }
     }
@@ -156,13 +114,10 @@ __global__ __launch_bounds__(64) void trk_publish_kernel(const double* __restric
 int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], const float t[3], const float Ki[9],
                     float affa, float affb, float b0, float cutoff, float maxEnergy, double out64[64]) {
     TrkEvalParams P;
-    P.u = c->pc_u[lvl].p; P.v = c->pc_v[lvl].p; P.id = c->pc_id[lvl].p; P.col = c->pc_col[lvl].p;
-    P.dI = c->slots[slot_new].dI[lvl];
-    P.n = c->pc_n[lvl]; P.wl = c->wl[lvl]; P.hl = c->hl[lvl]; P.lvl = lvl;
+    P.L = trk_level(c, slot_new, lvl); P.lvl = lvl;
     const bool sharded = c->trk_world > 1 && c->trk_hook;
-    P.i0 = sharded ? (int)((long long)P.n * c->trk_rank / c->trk_world) : 0;
-    P.i1 = sharded ? (int)((long long)P.n * (c->trk_rank + 1) / c->trk_world) : P.n;
-    P.fx = c->fx[lvl]; P.fy = c->fy[lvl]; P.cx = c->cx[lvl]; P.cy = c->cy[lvl];
+    P.i0 = sharded ? (int)((long long)P.L.n * c->trk_rank / c->trk_world) : 0;
+    P.i1 = sharded ? (int)((long long)P.L.n * (c->trk_rank + 1) / c->trk_world) : P.L.n;
     for (int i = 0; i < 9; ++i) { P.RKi[i] = RKi[i]; P.Ki[i] = Ki[i]; }
     for (int i = 0; i < 3; ++i) P.t[i] = t[i];
     P.affa = affa; P.affb = affb; P.b0 = b0; P.cutoff = cutoff; P.maxEnergy = maxEnergy;

@@ -13,19 +13,18 @@
 #include "nalo_internal.h"
 #include <hip/hip_ext.h>
 #include "reduce.h"
+#include "trk_device.h"
 
 namespace nalo {
 
 // lanes per workgroup: 512 (one point per lane and round, half as many workgroups as with 256 lanes -> half as many partials to exchange and to
-// sum in every workgroup per evaluation; 214 VGPRs, no spill). Headline window, same box, back to back: 256: 696, 384: 708, **512: 717-769**, 768 (spills): 670-678,
-// 1024 (spills): 633-640 keyframes/s.
+// sum in every workgroup per evaluation). The compiler reports 256 VGPRs with 6 spilled (28 bytes of scratch per lane), 106 SGPRs, 34424 bytes of LDS.
+// Headline window, same box, back to back: 256: 696, 384: 708, **512: 717-769**, 768 (spills): 670-678, 1024 (spills): 633-640 keyframes/s.
 constexpr int kLmThreads = 512;
-constexpr int kLmVals = 52;                  // 45 H entries + E, nE, nSat, nWarped, sT, sRT, sN (same order as trk_eval_kernel)
 constexpr int kLmStride = 56;
 
-struct TrkLmLevel { const float *u, *v, *id, *col; const float4* dI; int n, wl, hl; float fx, fy, cx, cy; };
 struct TrkLmParams {
-    TrkLmLevel lv[NALO_MAX_LEVELS];
+    TrkLevel lv[NALO_MAX_LEVELS];
     double T0[12], aff0[2], ref_aff[2], minRes[5];
     float expRef, expNew;
     int coarsest, has_minres, stop_lvl, have_repeated_in;   // levels coarsest..stop_lvl run here; the caller continues below
@@ -174,7 +173,7 @@ __device__ __forceinline__ void lm_ldlt8_uniform(double (&U)[36], const double (
 
 // prepare the float parameters of an evaluation at (T, aff) for level lvl (CoarseTracker.cpp:907-916); the caller's lane 0 passes write = true
 __device__ __forceinline__ void lm_prepare_eval(LmState& S, const TrkLmParams& P, int lvl, float levelCutoffRepeat, const double (&T)[12], double aff0, double aff1, bool write) {
-    const TrkLmLevel& L = P.lv[lvl];
+    const TrkLevel& L = P.lv[lvl];
     float expF = P.expRef, expT = P.expNew;
     if (expF == 0 || expT == 0) expT = expF = 1;                                        // AffLight::fromToVecExposure, util/NumType.h:173-185
     const double a = exp(aff0 - P.ref_aff[0]) * expT / expF, bq = aff1 - a * P.ref_aff[1];
@@ -243,10 +242,10 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
     for (int guard = 0; guard < 4096; ++guard) {
         if (S.done) break;
         // ------------------------------------------------------------- fused calcRes + calcGS over this level's points
-        const TrkLmLevel& L = P.lv[S.lvl];
-        float acc[kLmVals];
+        const TrkLevel& L = P.lv[S.lvl];
+        float acc[kTrkVals];
 #pragma unroll
-        for (int k = 0; k < kLmVals; ++k) acc[k] = 0.f;
+        for (int k = 0; k < kTrkVals; ++k) acc[k] = 0.f;
         {
             const float wlm3 = (float)(L.wl - 3), hlm3 = (float)(L.hl - 3);
             const float affa = S.affa, affb = S.affb, b0 = S.b0, cutoff = S.cutoff, maxEnergy = S.maxEnergy;
@@ -283,12 +282,7 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
                 float4 p00[G], p10[G], p01[G], p11[G];
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
-                    const float pt0 = RK[0] * x[g] + RK[1] * y[g] + RK[2] + tt[0] * id[g];
-                    const float pt1 = RK[3] * x[g] + RK[4] * y[g] + RK[5] + tt[1] * id[g];
-                    const float pt2 = RK[6] * x[g] + RK[7] * y[g] + RK[8] + tt[2] * id[g];
-                    uu[g] = pt0 / pt2; vv[g] = pt1 / pt2;
-                    Ku[g] = L.fx * uu[g] + L.cx; Kv[g] = L.fy * vv[g] + L.cy;
-                    nid[g] = id[g] / pt2;
+                    trk_project(RK, tt, L, x[g], y[g], id[g], uu[g], vv[g], Ku[g], Kv[g], nid[g]);
                     ok[g] = inb[g] && (Ku[g] > 2.f && Kv[g] > 2.f && Ku[g] < wlm3 && Kv[g] < hlm3 && nid[g] > 0.f);        // :981
                     const int ix = ok[g] ? (int)Ku[g] : 2, iy = ok[g] ? (int)Kv[g] : 2;
                     const float4* bp = L.dI + ix + iy * L.wl;
@@ -297,44 +291,23 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
 #pragma unroll
                 for (int g = 0; g < G; ++g) {
                     const int i = base + g * gthreads;
-                    if (inb[g] && lvl == 0 && (i & 31) == 0) {                   // flow indicators (:948-979)
-                        const float a0 = Kq[0] * x[g] + Kq[1] * y[g] + Kq[2], a1 = Kq[3] * x[g] + Kq[4] * y[g] + Kq[5], a2 = Kq[6] * x[g] + Kq[7] * y[g] + Kq[8];
-                        const float T2 = a2 + tt[2] * id[g], U2 = a2 - tt[2] * id[g], r2 = RK[6] * x[g] + RK[7] * y[g] + RK[8] - tt[2] * id[g];
-                        const float KuT = L.fx * ((a0 + tt[0] * id[g]) / T2) + L.cx, KvT = L.fy * ((a1 + tt[1] * id[g]) / T2) + L.cy;
-                        const float KuT2 = L.fx * ((a0 - tt[0] * id[g]) / U2) + L.cx, KvT2 = L.fy * ((a1 - tt[1] * id[g]) / U2) + L.cy;
-                        const float Ku3 = L.fx * ((RK[0] * x[g] + RK[1] * y[g] + RK[2] - tt[0] * id[g]) / r2) + L.cx;
-                        const float Kv3 = L.fy * ((RK[3] * x[g] + RK[4] * y[g] + RK[5] - tt[1] * id[g]) / r2) + L.cy;
-                        acc[49] += (KuT - x[g]) * (KuT - x[g]) + (KvT - y[g]) * (KvT - y[g]);
-                        acc[49] += (KuT2 - x[g]) * (KuT2 - x[g]) + (KvT2 - y[g]) * (KvT2 - y[g]);
-                        acc[50] += (Ku[g] - x[g]) * (Ku[g] - x[g]) + (Kv[g] - y[g]) * (Kv[g] - y[g]);
-                        acc[50] += (Ku3 - x[g]) * (Ku3 - x[g]) + (Kv3 - y[g]) * (Kv3 - y[g]);
-                        acc[51] += 2.f;
-                    }
+                    if (inb[g] && lvl == 0 && (i & 31) == 0) trk_flow(acc, RK, Kq, tt, L, x[g], y[g], id[g], Ku[g], Kv[g]);
                     if (!ok[g]) continue;
-                    const float dx = Ku[g] - (int)Ku[g], dy = Kv[g] - (int)Kv[g], dxdy = dx * dy;     // getInterpolatedElement33
-                    const float w11 = dxdy, w01 = dy - dxdy, w10 = dx - dxdy, w00 = 1 - dx - dy + dxdy;
-                    const float hI = w11 * p11[g].x + w01 * p01[g].x + w10 * p10[g].x + w00 * p00[g].x;
-                    const float hx = w11 * p11[g].y + w01 * p01[g].y + w10 * p10[g].y + w00 * p00[g].y;
-                    const float hy = w11 * p11[g].z + w01 * p01[g].z + w10 * p10[g].z + w00 * p00[g].z;
-                    if (!isfinite(hI)) continue;
-                    const float residual = hI - (affa * rc[g] + affb);
-                    const float ar = fabsf(residual);
-                    const float hw = ar < kHuberTH ? 1.f : kHuberTH / ar;
-                    acc[46] += 1.f;
-                    if (ar > cutoff) { acc[45] += maxEnergy; acc[47] += 1.f; }
+                    const float3 hit = trk_interp(Ku[g], Kv[g], p00[g], p10[g], p01[g], p11[g]);
+                    if (!isfinite(hit.x)) continue;
+                    float hw; const float residual = trk_residual(hit.x, rc[g], affa, affb, hw);
+                    acc[kTrkNE] += 1.f;
+                    if (fabsf(residual) > cutoff) { acc[kTrkE] += maxEnergy; acc[kTrkNSat] += 1.f; }
                     else {
-                        acc[45] += hw * residual * residual * (2.f - hw);
-                        acc[48] += 1.f;
-                        const float gx = hx * L.fx, gy = hy * L.fy, u = uu[g], v = vv[g];
+                        acc[kTrkE] += hw * residual * residual * (2.f - hw);
+                        acc[kTrkNWarped] += 1.f;
                         float J[9];
-                        J[0] = nid[g] * gx; J[1] = nid[g] * gy; J[2] = -(nid[g] * (u * gx + v * gy));
-                        J[3] = -(u * v * gx + gy * (1.f + v * v)); J[4] = u * v * gy + gx * (1.f + u * u); J[5] = u * gy - v * gx;
-                        J[6] = affa * (b0 - rc[g]); J[7] = -1.f; J[8] = residual;
+                        trk_jacobian(J, hit, rc[g], uu[g], vv[g], nid[g], L.fx, L.fy, affa, b0, residual);
 #pragma unroll
                         for (int r = 0; r < 9; ++r) {
                             const float Jw = J[r] * hw;
 #pragma unroll
-                            for (int c2 = r; c2 < 9; ++c2) acc[r * 9 - r * (r - 1) / 2 + (c2 - r)] += Jw * J[c2];
+                            for (int c2 = r; c2 < 9; ++c2) acc[trk_ut(r, c2)] += Jw * J[c2];
                         }
                     }
                 }
@@ -344,21 +317,21 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
         const int nbl = min(NB, (L.n + kLmThreads - 1) / kLmThreads);          // blocks that own points of this level
         if (blk < nbl) {
 #pragma unroll
-            for (int k = 0; k < kLmVals; ++k) acc[k] = dpp_quad_sum(acc[k]);
+            for (int k = 0; k < kTrkVals; ++k) acc[k] = dpp_quad_sum(acc[k]);
             if ((tid & 3) == 0) {
                 float* row = rows + (tid >> 2) * kLmStride;
 #pragma unroll
-                for (int k = 0; k < kLmVals; ++k) row[k] = acc[k];
+                for (int k = 0; k < kTrkVals; ++k) row[k] = acc[k];
             }
             __syncthreads();
             {                                                // fp64 column sums over the quad rows: (T/64) lane groups x 16 rows, fixed order
                 const int j = tid & 63, g = tid >> 6;
                 double s = 0;
-                if (j < kLmVals) for (int r = g * 16; r < g * 16 + 16; ++r) s += (double)rows[r * kLmStride + j];
+                if (j < kTrkVals) for (int r = g * 16; r < g * 16 + 16; ++r) s += (double)rows[r * kLmStride + j];
                 part[g][j] = s;
             }
             __syncthreads();
-            if (tid < kLmVals) {
+            if (tid < kTrkVals) {
                 double s = 0; for (int g = 0; g < kLmThreads / 64; ++g) s += part[g][tid];
                 if (NB == 1) sums[tid] = s;
                 else __hip_atomic_store(&P.partial[((size_t)(S.evals & 1) * NB + blk) * 64 + tid], lm_pack((float)s, P.tag0 + (unsigned)S.evals), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -369,7 +342,7 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             const unsigned long long* pp = P.partial + (size_t)(S.evals & 1) * NB * 64;
             const unsigned want = P.tag0 + (unsigned)S.evals;
             double s = 0;
-            bool pending = j < kLmVals;
+            bool pending = j < kTrkVals;
             for (unsigned spins = 0; pending; ++spins) {     // all words of this lane's blocks in flight together; repeat until every tag matches
                 pending = false; s = 0;
                 for (int b2 = g; b2 < nbl; b2 += kLmThreads / 64) {
@@ -382,7 +355,7 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             part[g][j] = s;
             __syncthreads();
             if (!bar_ok) { timed_out = 1; break; }
-            if (tid < kLmVals) { double t2 = 0; for (int g2 = 0; g2 < kLmThreads / 64; ++g2) t2 += part[g2][tid]; sums[tid] = t2; }
+            if (tid < kTrkVals) { double t2 = 0; for (int g2 = 0; g2 < kLmThreads / 64; ++g2) t2 += part[g2][tid]; sums[tid] = t2; }
         }
         __syncthreads();
         // ------------------------------------------------------------- wave 0 = the host of the reference
@@ -395,13 +368,14 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             const int evals = S.evals + 1;
             if (lane == 0) S.evals_lvl[S.lvl] += 1;
             // sums (52 doubles) -> stats6 and this lane's entry of the scaled H / b (CoarseTracker.cpp:1040-1046, 869-884)
-            const double E = sums[45], nE = sums[46], nSat = sums[47], nW = sums[48], sT = sums[49], sRT = sums[50], sN = sums[51];
+            const double E = sums[kTrkE], nE = sums[kTrkNE], nSat = sums[kTrkNSat], nW = sums[kTrkNWarped], sT = sums[kTrkST], sRT = sums[kTrkSRT], sN = sums[kTrkSN];
             // (round 4: the three fp64 divisions an evaluation does not need are off wave 0's path - the two flow indicators are divided when a level ends, from the
             // sums kept meanwhile; the accepted estimate's E / nE is kept as a quotient instead of being divided again at every later test; same operands, same bits)
             const double st[6] = {E, nE, sT, sN, sRT, E / nE};
             const double inv = 1.0 / (double)(((long)nW + 3) & ~3L);
             const int hr = lane >> 3, hc = lane & 7, lo = hr < hc ? hr : hc, hi = hr < hc ? hc : hr;
-            const double Hval = sums[lo * 9 - lo * (lo - 1) / 2 + (hi - lo)] * inv * lm_scale(hr) * lm_scale(hc);     // upper-triangular index of the 9x9
+            // trk_ut(lo, hi) and trk_ut(bl, 8) written out: through the function the same index compiles to a different instruction schedule
+            const double Hval = sums[lo * 9 - lo * (lo - 1) / 2 + (hi - lo)] * inv * lm_scale(hr) * lm_scale(hc);
             const int bl = lane & 7;
             const double bval = sums[bl * 9 - bl * (bl - 1) / 2 + (8 - bl)] * inv * lm_scale(bl);
             double ro[6];
@@ -520,11 +494,7 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
                   int coarsest, int stop_lvl, const double* minRes, double out24[32]) {
     TrkLmParams P;
     std::memset(&P, 0, sizeof(P));
-    for (int l = 0; l < c->levels; ++l) {
-        TrkLmLevel& L = P.lv[l];
-        L.u = c->pc_u[l].p; L.v = c->pc_v[l].p; L.id = c->pc_id[l].p; L.col = c->pc_col[l].p; L.dI = c->slots[slot_new].dI[l];
-        L.n = c->pc_n[l]; L.wl = c->wl[l]; L.hl = c->hl[l]; L.fx = c->fx[l]; L.fy = c->fy[l]; L.cx = c->cx[l]; L.cy = c->cy[l];
-    }
+    for (int l = 0; l < c->levels; ++l) P.lv[l] = trk_level(c, slot_new, l);
     std::memcpy(P.T0, T0, sizeof(P.T0)); P.aff0[0] = aff0[0]; P.aff0[1] = aff0[1]; P.ref_aff[0] = ref_aff[0]; P.ref_aff[1] = ref_aff[1];
     P.expRef = exposures[0]; P.expNew = exposures[1]; P.coarsest = coarsest; P.stop_lvl = stop_lvl; P.have_repeated_in = 0;
     P.has_minres = 0;
