@@ -385,8 +385,9 @@ class Context:
                 a, b = (0.0, 0.0) if aff is None else aff[i]
                 # FrameHessian::setEvalPT_scaled (HessianBlocks.h:247-255): state = [0.., a/SCALE_A, b/SCALE_B, 0, 0], state_zero = state
                 st = np.zeros(10)
-                st[6] = np.float32(1.0 / 10.0) * a
-                st[7] = np.float32(1.0 / 1000.0) * b
+                # (1.0f / SCALE_A) * a in double, whatever type a has (numpy >= 2 would round float32 * Python float to float32)
+                st[6] = float(np.float32(1.0 / 10.0)) * float(a)
+                st[7] = float(np.float32(1.0 / 1000.0)) * float(b)
                 for k in range(10):
                     fs.state_zero[k] = st[k]
                 if state6 is not None:

@@ -598,13 +598,14 @@ class BA:
         return [self.L.orc_ba_counts(self.h_, i) for i in range(3)]
 
 
-def ba_from_window(win, kind="f32", state6=None, aff=None, th=None):
-    """Builds a BA oracle from a synth.Window (keyframes 0..W-1)."""
+def ba_from_window(win, kind="f32", state6=None, aff=None, th=None, exposure=None):
+    """Builds a BA oracle from a synth.Window (keyframes 0..W-1); aff [W,2], th [W] and exposure [W] (ab_exposure) are per frame."""
     ba = BA(win.W, len(win.host), win.w, win.h, win.K, kind)
     for i in range(win.W):
         dI, _ = make_images(win.images[i], 1, kind)
         ba.set_frame(i, dI, win.world_to_cam[i], aff=(0.0, 0.0) if aff is None else tuple(aff[i]),
-                     th=8 * 8 * 8.0 if th is None else th[i], state6=None if state6 is None else state6[i])
+                     exposure=1.0 if exposure is None else exposure[i], th=8 * 8 * 8.0 if th is None else th[i],
+                     state6=None if state6 is None else state6[i])
     ba.set_points(win.host, win.u, win.v, win.idepth, win.color, win.weights)
     ba.set_residuals(win.exists)
     ba.prepare()
