@@ -141,6 +141,15 @@ int nalo_trk_set_ref(nalo_ctx* ctx, int slot_ref, int n, const float* Ku, const 
  * The block stays valid until the next nalo_trk_ref_upload; nalo_trk_set_ref leaves it untouched. Results are those of nalo_trk_set_ref on the same arrays, bit for bit. */
 int nalo_trk_ref_upload(nalo_ctx* ctx, int n, const float* Ku, const float* Kv, const float* new_idepth, const float* HdiF);
 int nalo_trk_set_ref_resident(nalo_ctx* ctx, int slot_ref);
+/* a2 fed from the window: makeCoarseDepthL0 (CoarseTracker.cpp:382-538) on the IN residuals that target the window's newest frame,
+ * read on the device. The reference slot is frames[W-1].slot of the last nalo_ba_set_window.
+ * One entry per point whose residual to frame W-1 is IN at the window's last linearizeAll(true) (lastResiduals[0]), with that residual's
+ * centerProjectedTo and the HdiF nalo_ba_get_points would return at this moment, in the reference's loop order (window host index, then the
+ * nalo_ba_set_points order inside a host). Results are those of nalo_trk_set_ref(ctx, frames[W-1].slot, ...) on those arrays, bit for bit; no window
+ * data crosses to the host. NALO_ERR_STATE: no window or no points, no pyramid in the newest frame's slot, the window's last linearisation was not a
+ * fix = 1 one (nalo_ba_optimize ends with one), or the window is sharded (a rank holds its own points only: collect the inputs and call
+ * nalo_trk_set_ref). The block of nalo_trk_ref_upload is left alone. */
+int nalo_trk_set_ref_from_window(nalo_ctx* ctx);
 /* direct injection of one level's point cloud (synthetic stress windows) */
 int nalo_trk_set_pc(nalo_ctx* ctx, int slot_ref, int lvl, int n, const float* u, const float* v,
                     const float* idepth, const float* color);

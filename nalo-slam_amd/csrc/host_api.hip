@@ -377,6 +377,15 @@ int nalo_trk_set_ref_resident(nalo_ctx* c, int slot_ref) {
     const float* b = c->ref_res.p;
     return trk_build_ref(c, c->ref_res_n, b, b + n, b + 2 * n, b + 3 * n);
 }
+int nalo_trk_set_ref_from_window(nalo_ctx* c) {
+    if (!c) return NALO_ERR_ARG;
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "trk_set_ref");
+    int slot = -1, n = 0; const float* b = nullptr;
+    const int rc = ba_trk_ref_inputs(c, &slot, &n, &b); if (rc) return rc;     // the gather is in the stream: no host copy, no round trip
+    c->slot_ref = slot;
+    return trk_build_ref(c, n, b, b + n, b + 2 * (size_t)n, b + 3 * (size_t)n);
+}
 
 int nalo_trk_set_pc(nalo_ctx* c, int slot_ref, int lvl, int n, const float* u, const float* v, const float* idepth, const float* color) {
     if (!c || slot_ref < 0 || slot_ref >= (int)c->slots.size() || lvl < 0 || lvl >= c->levels || n < 0) return fail(c, NALO_ERR_ARG, "nalo_trk_set_pc: bad argument");

@@ -30,6 +30,7 @@ void ba_launch_lenergy(hipStream_t s, const BADev& B, double* partial);
 void ba_launch_load_backup(hipStream_t s, const BADev& B);
 void ba_launch_swgray(hipStream_t s, const BADev& B, const double* Rt, double* partial);
 void ba_launch_set_idepth(hipStream_t s, const BADev& B, int mode, int host_sel, double scale);
+void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, float* out);
 
 struct HostFrame {
     int slot = 0, frameID = 0;
@@ -108,6 +109,10 @@ struct BAWindow {
     int opt_iterations = 0, opt_rejected = 0;
     bool prior_next = false;                                        // nalo_ba_marginalize_frame has left HM / bM for the NEXT nalo_ba_set_window (kept or extended there)
     bool prior_carry = false;                                       // nalo_ba_set_prior_carry: the context is ONE continuing EnergyFunctional, every set_window keeps / extends
+    // nalo_trk_set_ref_from_window: the newest frame's IN residuals as makeCoarseDepthL0 reads them (ba_trk_ref_inputs)
+    bool lin_fixed = false;                                         // the last linearisation was a linearizeAll(true): rs_cpt of the IN residuals to W-1 are its centerProjectedTo
+    std::vector<int> ref_kmap_h; DevBuf<int> ref_kmap; bool ref_kmap_ok = false;   // reference loop order (host, submission order) -> device slot; rebuilt after set_points
+    DevBuf<float> ref_in;                                           // the gathered inputs {Ku | Kv | new_idepth | HdiF}, P each (not nalo_trk_ref_upload's block)
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -118,7 +123,7 @@ void ba_destroy(nalo_ctx* c) {
     w->pt_geo.release(); w->pt_col0.release(); w->pt_col1.release(); w->pt_w0.release(); w->pt_w1.release(); w->pt_acc.release(); w->pt_hcd.release();
     w->rs_jp0.release(); w->rs_jp1.release(); w->rs_cpt.release(); w->rs_energy.release(); w->rs_pp0.release(); w->rs_pp1.release(); w->pt_flags.release(); w->pt_ngood.release(); w->rs_state.release();
     w->blk_host.release(); w->host_blk.release(); w->sc_grp.release(); w->blk_order.release(); w->acc13.release(); w->G.release(); w->AD.release(); w->st_ticket.release();
-    w->stitched.release(); w->th_hist.release();
+    w->stitched.release(); w->th_hist.release(); w->ref_kmap.release(); w->ref_in.release();
     if (w->ev_lin) (void)hipEventDestroy(w->ev_lin);
     if (w->ev_th) (void)hipEventDestroy(w->ev_th);
     w->snap_geo.release(); w->snap_state.release(); w->snap_flags.release(); w->snap_prior.release();
@@ -404,6 +409,7 @@ static int ensure_tiled(nalo_ctx* c) {
 }
 static int linearize_async(nalo_ctx* c, int mode, int fix, bool keep_th = false) {
     BAWindow& w = *c->ba;
+    w.lin_fixed = false;                                              // set again below by a linearizeAll(true) that has been enqueued
     if (w.lin_pre) {
         // the kernel of this pass is already in the stream (prelaunch_iteration), and set_precalc has just opened its gate: what is left is the bookkeeping
         w.lin_pre = false;
@@ -457,6 +463,7 @@ static int linearize_async(nalo_ctx* c, int mode, int fix, bool keep_th = false)
     } else if (mode == 0) w.th_pending = true;
     if (fix != 2) { w.have_lin = true; w.have_sc = false; w.stitched_top = false; w.stitched_sc = false; }
     NALO_HIP(c, hipGetLastError());
+    w.lin_fixed = mode == 0 && fix == 1;
     return NALO_OK;
 }
 // linearizeAll(false) without applyRes: the energy of the current states (lastEnergyP), nothing else changes but state_NewEnergy and the threshold input
@@ -902,6 +909,37 @@ static int do_step(nalo_ctx* c, float fC, float fT, float fR, float fA, float fD
     return NALO_OK;
 }
 
+// nalo_trk_set_ref_from_window (host_api.hip): the inputs of makeCoarseDepthL0 gathered on the device, on c->stream behind the window's last fix pass. *dev =
+// {Ku | Kv | new_idepth | HdiF}, *n entries each (one per point, holes included: ba_trk_ref_gather_kernel), *slot = the newest frame's slot.
+int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev) {
+    if (!c->ba || c->ba->W < 2 || !c->ba->points_set || !c->ba->res_set || c->ba->P == 0)
+        return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: no window or no points");
+    BAWindow& w = *c->ba;
+    if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: the window is sharded (a rank holds only its own points); collect every rank's inputs and call nalo_trk_set_ref");
+    if (!w.lin_fixed) return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: the window's last linearisation was not a linearizeAll(true) (nalo_ba_optimize, nalo_ba_linearize(fix=1))");
+    const int s = w.frames[w.W - 1].slot;
+    if (!c->slots[s].valid) return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: the newest frame's slot has no pyramid");
+    const int P = w.P;
+    if (!w.ref_kmap_ok) {
+        // the reference's loop: for fh in frameHessians, for ph in fh->pointHessians (CoarseTracker.cpp:388-390) = host index, then submission order
+        std::vector<int> start(w.W + 1, 0);
+        for (int p = 0; p < P; ++p) start[w.blk_host_h[w.p2d[p] / kBlk] + 1]++;
+        for (int h = 0; h < w.W; ++h) start[h + 1] += start[h];
+        w.ref_kmap_h.assign(P, 0);
+        for (int p = 0; p < P; ++p) { const int d = w.p2d[p]; w.ref_kmap_h[start[w.blk_host_h[d / kBlk]]++] = d; }
+        NALO_HIP(c, w.ref_kmap.reserve(P));
+        NALO_HIP(c, hipMemcpyAsync(w.ref_kmap.p, w.ref_kmap_h.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));   // the host copy lives until the next rebuild
+        w.ref_kmap_ok = true;
+    }
+    // HdiF as nalo_ba_get_points would return it: after an explicit nalo_ba_linearize, the accumulation of that linearisation (the same on-demand pass)
+    if (w.have_lin && !w.have_sc && w.pt_acc_on_read) { int rc = sc_async(c, 1, 1.f, 0); if (rc) return rc; }
+    NALO_HIP(c, w.ref_in.reserve((size_t)4 * P));
+    ba_launch_trk_ref_gather(c->stream, w.dev, w.ref_kmap.p, w.ref_in.p);
+    NALO_HIP(c, hipGetLastError());
+    *slot = s; *n = P; *dev = w.ref_in.p;
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -974,7 +1012,7 @@ int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const
     rc = set_adjoints(c); if (rc) return rc;
     rc = set_precalc(c); if (rc) return rc;
     NALO_HIP(c, hipStreamSynchronize(c->stream));
-    w.have_lin = w.have_sc = false;
+    w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
 
@@ -1087,7 +1125,7 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
     D.pt_flags = w.pt_flags.p; D.pt_acc = w.pt_acc.p; D.pt_hcd = w.pt_hcd.p; D.pt_ngood = w.pt_ngood.p; D.pt_step = w.pt_step.p; D.pt_backup = w.pt_backup.p; D.pt_relbs = w.pt_relbs.p; D.pt_relbs_next = w.pt_relbs2.p;
     D.rs_state = w.rs_state.p; D.rs_energy = w.rs_energy.p; D.rs_jp0 = w.rs_jp0.p; D.rs_jp1 = w.rs_jp1.p; D.rs_cpt = w.rs_cpt.p; D.rs_pp0 = w.rs_pp0.p; D.rs_pp1 = w.rs_pp1.p; D.en_new = w.en_new.p;
     D.top_partial = w.top_partial.p; D.sc_partial = w.sc_partial.p;
-    w.points_set = true; w.res_set = false; w.have_lin = w.have_sc = false;
+    w.points_set = true; w.res_set = false; w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false;
     return NALO_OK;
 }
 
@@ -1099,7 +1137,7 @@ int nalo_ba_set_residuals(nalo_ctx* c, const uint8_t* exists) {
     for (int p = 0; p < w.P; ++p) { const int d = w.p2d[p]; for (int t = 0; t < W; ++t) if (exists[(size_t)p * W + t]) st[(size_t)t * w.Ppad + d] = RS_EXISTS; }   // state IN (0), resetOOB
     NALO_HIP(c, hipMemcpy(w.rs_state.p, st.data(), st.size(), hipMemcpyHostToDevice));
     NALO_HIP(c, hipMemset(w.rs_energy.p, 0, st.size() * 8));
-    w.res_set = true; w.have_lin = w.have_sc = false;
+    w.res_set = true; w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
 
@@ -1385,7 +1423,7 @@ int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, dou
     for (int d = 0; d < w.Ppad; ++d) if (w.flags_h[d] & PT_MARG) { w.flags_h[d] = 0; for (int t = 0; t < W; ++t) st[(size_t)t * w.Ppad + d] = 0; }
     NALO_HIP(c, hipMemcpy(w.rs_state.p, st.data(), st.size(), hipMemcpyHostToDevice));
     NALO_HIP(c, hipMemcpy(w.pt_flags.p, w.flags_h.data(), w.Ppad, hipMemcpyHostToDevice));
-    w.have_lin = w.have_sc = false;
+    w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
 
@@ -1427,7 +1465,7 @@ int nalo_ba_marginalize_frame(nalo_ctx* c, int idx) {
     // for the frames that remain — with the next keyframe appended, set_window extends HM/bM like insertFrame does.
     w.frames.erase(w.frames.begin() + idx);
     w.W -= 1; w.n = 8 * w.W + 4; w.n1 = w.n + 1;
-    w.points_set = false; w.res_set = false; w.have_lin = w.have_sc = false; w.proj_valid = false; w.have_snap = false;
+    w.points_set = false; w.res_set = false; w.have_lin = w.have_sc = false; w.proj_valid = false; w.have_snap = false; w.lin_fixed = false;
     w.lastX.assign(w.n, 0.0);
     w.prior_next = true;
     return NALO_OK;
@@ -1701,7 +1739,7 @@ int nalo_ba_restore(nalo_ctx* c) {
     std::memcpy(w.c_scaledf, w.snap_scaledf, sizeof(w.snap_scaledf)); std::memcpy(w.c_scaledi, w.snap_scaledi, sizeof(w.snap_scaledi));
     int rc = set_adjoints(c); if (rc) return rc;
     rc = set_precalc(c); if (rc) return rc;
-    w.have_lin = w.have_sc = false;
+    w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
 

@@ -1166,4 +1166,29 @@ void ba_launch_set_idepth(hipStream_t s, const BADev& B, int mode, int host_sel,
 
 void ba_launch_load_backup(hipStream_t s, const BADev& B) { ba_load_backup_kernel<<<(B.Ppad + 255) / 256, 256, 0, s>>>(B); }
 
+// ------------------------------------------------------------------------------------------------ a2 inputs from the window
+// nalo_trk_set_ref_from_window: the inputs of CoarseTracker::makeCoarseDepthL0 (CoarseTracker.cpp:388-405) where the window's last linearizeAll(true) left them.
+// Entry k is the point in device slot kmap[k], the k-th of the reference's loop (host frame, then submission order inside a host). {Ku, Kv, new_idepth} =
+// centerProjectedTo of its residual to frame W-1 (ba_linearize writes it for IN residuals of a fix pass) when that residual exists and is IN, HdiF = the
+// point's last accumulation (pt_acc.z); any other entry is a hole at Ku = Kv = -2, which the scatter's bounds test rejects ((int)(-2 + 0.5f) = -1, whereas -1
+// would round to pixel 0). Holes are never scattered and keep the order of the other entries, so the ordered redo of the hot pixels (trk_scatter_hot_kernel)
+// adds what a compacted array would give it, and the host never needs the count. Output SoA {Ku | Kv | new_idepth | HdiF}, P each.
+__global__ __launch_bounds__(256) void ba_trk_ref_gather_kernel(const int* __restrict__ kmap, int P, const uint8_t* __restrict__ st_last, const float4* __restrict__ cpt_last,
+                                                                const float4* __restrict__ pt_acc, float* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= P) return;
+    const int d = kmap[k];
+    const uint8_t s = st_last[d];
+    float ku = -2.f, kv = -2.f, id = 0.f, hdi = 0.f;
+    if ((s & RS_EXISTS) && (s & RS_STATE_MASK) == 0) {                  // IN (state 0)
+        const float4 cp = cpt_last[d];
+        ku = cp.x; kv = cp.y; id = cp.z; hdi = pt_acc[d].z;
+    }
+    out[k] = ku; out[P + k] = kv; out[2 * (size_t)P + k] = id; out[3 * (size_t)P + k] = hdi;
+}
+void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, float* out) {
+    const size_t last = (size_t)(B.W - 1) * B.Ppad;                    // residual slots [W][Ppad], t-major: the row of the newest frame
+    ba_trk_ref_gather_kernel<<<(B.P + 255) / 256, 256, 0, s>>>(kmap, B.P, B.rs_state + last, B.rs_cpt + last, B.pt_acc, out);
+}
+
 }  // namespace nalo

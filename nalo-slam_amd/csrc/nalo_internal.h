@@ -177,6 +177,8 @@ int imm_optimize_launch(nalo_ctx* c, const float4* const* dI, int W, const float
                         int minObs, int* result, float* idepth_out, uint8_t* res_in);
 int dist_make_launch(nalo_ctx* c, const float4* pt_geo, const uint8_t* pt_flags, const int* blk_host, int Ppad, int frame, const float* KRKi, const float* Kt, uint8_t* seed, float* out);
 int pixsel_hists_launch(nalo_ctx* c, const float* absg0, float* ths, float* thsSmoothed);
+// host_ba.hip: nalo_trk_set_ref_from_window's inputs gathered from the window on c->stream ({Ku | Kv | new_idepth | HdiF}, *n each, holes included)
+int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
 // host_rccl.hip
 void rccl_release(nalo_ctx* c);
 // host_init.hip
