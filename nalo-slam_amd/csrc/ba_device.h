@@ -16,6 +16,7 @@ constexpr int kTopStride = 96;       // floats per (block, target) partial
 constexpr int kPreStride = 40;       // floats per (host,target) precalc record
 constexpr int kThSmallSlots = 16384; // Ppad up to this: frameEnergyTH by ba_th_small_kernel (one workgroup); beyond: the radix select of ba_th_fill_kernel
 constexpr int kPreDirectSlots = 32768;   // Ppad up to this: ba_linearize reads the precalc records from mapped host memory; beyond: ba_pull_kernel copies them
+constexpr int kThDblAB = 1024, kThDblC = 256;   // setNewFrameEnergyTH: the three radix histograms (2048 + 2048 + 512 bins) as doubles, two bins per double = the cross-rank payloads of a sharded window
 
 // residual slot state byte
 enum : uint8_t { RS_STATE_MASK = 3, RS_EXISTS = 4, RS_ACTIVE = 8, RS_LINEARIZED = 16 };
@@ -124,9 +125,50 @@ struct RedExtra {
 struct StitchDev {
     const double* AD;                           // [adHost (W*W*64) | adTarget (W*W*64)], index (h + t*W)*64 + i*8 + k
     const double *M_top, *M_sc;                 // acc13 [W*W][169], G [W][NPL*NPL]
-    double* H;                                  // [H~_A (n1*n1) | H~_sc (n1*n1) | tail]
+    double* H;                                  // the stitched block (StitchLayout)
     unsigned* ticket;
     int W, n1, NPL;
 };
+
+// The stitched block of a window of W frames (n1 = 8W + 5), in doubles. The reduce and stitch kernels fill it on the device (BAWindow::stitched) and publish it
+// into a mapped host mirror (BAWindow::stitched_host):
+//   [H~_A (n1^2) | H~_sc (n1^2) | misc: {count, energy} per (host, target) (2 W^2) | step sums (3) | {TH sum, ranks} (2)] = npub doubles.
+// In the mirror the sequence number the host polls follows them (flag, written last); the mirror's tail is padded to 16 doubles. On the device level C's
+// histogram of the threshold's radix select (kThDblC doubles) starts at the next multiple of 16 doubles: a sharded window sums it with the systems in one all-reduce.
+struct StitchLayout {
+    size_t top, sc, misc, step, th, flag, npub, lo, dev_size, host_size;
+    constexpr StitchLayout(int n1, int W)
+        : top(0), sc((size_t)n1 * n1), misc(2 * sc), step(misc + 2 * (size_t)W * W), th(step + 3), flag(th + 2), npub(flag),
+          lo((npub + 15) & ~(size_t)15), dev_size(lo + kThDblC), host_size(step + 16) {}
+};
+// ba_reduce_kernel (kernels_ba.hip) publishes the tail from misc on with its own count, ntail = 2 W^2 + 5, and puts {TH, 1.0} at ntail - 2
+static_assert(StitchLayout(21, 2).npub - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 && StitchLayout(21, 2).th - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 - 2,
+              "StitchLayout and ba_reduce_kernel's tail disagree");
+
+// Launchers of kernels_ba.hip and kernels_ba_lin.hip
+void ba_launch_sc(hipStream_t s, const BADev& B, int T, int shift, float priorScaleMarg, int margOnly);
+void ba_launch_linearize(hipStream_t s, const BADev& B, int mode, int fix, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void ba_launch_reset_oob(hipStream_t s, const BADev& B);
+void ba_launch_restore(hipStream_t s, const BADev& B, const float4* geo, const uint8_t* state, const uint8_t* flags, const float* prior, const float* th);
+void ba_launch_reduce(hipStream_t s, const BADev& B, const int* host_blk, int NPL, double* acc13, double* misc, double* G, bool top, bool sc,
+                      const float* step_partial, int step_blocks, double* step_out, bool with_th, double* pub, double seq, unsigned* ticket);
+void ba_launch_resub_step(hipStream_t s, const BADev& B, float stepfacD, float* partial, const XadArg& karg, bool karg_is_x);
+int ba_launch_stitch(hipStream_t s, const StitchDev& D, bool top, bool sc, double* mapped, int ntail, double seq);
+void ba_launch_resub(hipStream_t s, const BADev& B, const XadArg& karg, bool karg_is_x);
+void ba_launch_resub_step_gated(hipStream_t s, const BADev& B, float stepfacD, float* partial, const GateArg& gate);
+void ba_launch_pull(hipStream_t s, float* dst, const float* src_mapped, int n);
+void ba_launch_step(hipStream_t s, const BADev& B, float stepfacD, float* partial, double* out3);
+void ba_launch_step_sums(hipStream_t s, const BADev& B, const float* partial, double* out3);
+void ba_launch_publish(hipStream_t s, const double* src, double* dst_mapped, int n, double seq, unsigned* ticket);
+void ba_launch_th_install(hipStream_t s, const double* tail2, float* th);
+void ba_launch_th_tail(hipStream_t s, const float* th, double* tail2);
+void ba_launch_energy_th(hipStream_t s, const BADev& B);
+void ba_launch_set_th(hipStream_t s, float* dst, const float* th, int W);
+void ba_launch_energy_th_step(hipStream_t s, const BADev& B, int step);
+void ba_launch_lenergy(hipStream_t s, const BADev& B, double* partial);
+void ba_launch_load_backup(hipStream_t s, const BADev& B);
+void ba_launch_swgray(hipStream_t s, const BADev& B, const double* Rt, double* partial);
+void ba_launch_set_idepth(hipStream_t s, const BADev& B, int mode, int host_sel, double scale);
+void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, float* out);
 
 }  // namespace nalo

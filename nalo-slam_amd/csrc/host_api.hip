@@ -7,10 +7,6 @@
 
 using namespace nalo;
 
-namespace nalo { int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2], int coarsest, int stop_lvl, const double* minRes, double out24[32]); }
-
-namespace nalo { void ba_destroy(nalo_ctx* c); }
-
 static int pyr_levels_rule(int w, int h) {           // util/globalCalib.cpp:50-55
     int wl = w, hl = h, lv = 1;
     while (wl % 2 == 0 && hl % 2 == 0 && wl * hl > 5000 && lv < NALO_MAX_LEVELS) { wl /= 2; hl /= 2; lv++; }
@@ -38,16 +34,14 @@ int nalo_create(nalo_ctx** out, int device, int w, int h, int levels, const floa
     for (int l = 0; l < c->levels; ++l) { c->wl[l] = w >> l; c->hl[l] = h >> l; }
     for (int i = 0; i < 4; ++i) c->K0[i] = K[i];
     set_pyr_calib(c, K[0], K[1], K[2], K[3]);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) { delete c; return NALO_ERR_HIP; }
+    if (c->stream.create() != hipSuccess || c->side.create() != hipSuccess) { delete c; return NALO_ERR_HIP; }   // the context owns whatever it got so far
     c->slots.resize(n_slots);
     for (auto& s : c->slots)
         for (int l = 0; l < c->levels; ++l) {
             const size_t npx = (size_t)c->wl[l] * c->hl[l];
-            if (hipMalloc((void**)&s.I[l], npx * 4) != hipSuccess || hipMalloc((void**)&s.dI[l], npx * 16) != hipSuccess ||
-                hipMalloc((void**)&s.absg[l], npx * 4) != hipSuccess) { nalo_destroy(c); return NALO_ERR_HIP; }
+            if (s.I[l].reserve(npx) != hipSuccess || s.dI[l].reserve(npx) != hipSuccess || s.absg[l].reserve(npx) != hipSuccess) { nalo_destroy(c); return NALO_ERR_HIP; }
         }
-    if (hipHostMalloc((void**)&c->trk_out_host, 128 * sizeof(double), hipHostMallocMapped) != hipSuccess) { nalo_destroy(c); return NALO_ERR_HIP; }
+    if (c->trk_out_host.reserve(128, hipHostMallocMapped) != hipSuccess) { nalo_destroy(c); return NALO_ERR_HIP; }
     *out = c;
     return NALO_OK;
 }
@@ -62,31 +56,9 @@ void nalo_destroy(nalo_ctx* c) {
     pixsel_destroy(c);
     init_destroy(c);
     if (c->copy) (void)hipStreamSynchronize(c->copy);
-    for (auto& s : c->slots) {
-        if (s.ev_up) (void)hipEventDestroy(s.ev_up);
-        for (int l = 0; l < NALO_MAX_LEVELS; ++l) { if (s.I[l]) (void)hipFree(s.I[l]); if (s.dI[l]) (void)hipFree(s.dI[l]); if (s.absg[l]) (void)hipFree(s.absg[l]); }
-        if (s.mask) (void)hipFree(s.mask);
-        if (s.bgr) (void)hipFree(s.bgr);
-        if (s.raw) (void)hipFree(s.raw);
-        if (s.dI0t) (void)hipFree(s.dI0t);
-    }
-    for (int l = 0; l < NALO_MAX_LEVELS; ++l) {
-        c->trk_idepth[l].release(); c->trk_wsum[l].release(); c->trk_wbak[l].release();
-        c->pc_u[l].release(); c->pc_v[l].release(); c->pc_id[l].release(); c->pc_col[l].release();
-    }
-    c->dense_lb.release(); c->trk_partial.release(); c->trk_ticket.release(); c->ref_res.release(); c->trk_out.release(); c->lm_partial.release(); c->trk_shard_sums.release(); c->scan_tmp.release(); c->trk_cnt.release(); c->upload_tmp.release();
-    if (c->trk_out_host) (void)hipHostFree(c->trk_out_host);
-    if (c->pinned_f) (void)hipHostFree(c->pinned_f);
-    if (c->imm_host) (void)hipHostFree(c->imm_host);
-    c->imm_dev.release(); c->imm_res.release();
-    c->und_G.release(); c->und_vinv.release(); c->und_rxy.release(); c->und_raw.release(); c->und_mask.release(); c->und_bgr.release();
+    // the profiling events are raw handles (they move between the pool and the pending pairs): this is where they end
     for (auto& kv : c->prof) for (auto& ev : kv.second.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (hipEvent_t e : c->prof_pool) (void)hipEventDestroy(e);
-    if (c->ev_main) (void)hipEventDestroy(c->ev_main);
-    if (c->gamma_dev) (void)hipFree(c->gamma_dev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->copy) (void)hipStreamDestroy(c->copy);
     delete c;
 }
 
@@ -120,14 +92,12 @@ int nalo_constants_device(nalo_ctx* c, int cap, double* values) {
     if (!c || !values) return fail(c, NALO_ERR_ARG, "nalo_constants_device: bad argument");
     const int n = nalo_constants(0, nullptr, nullptr);
     NALO_HIP(c, hipSetDevice(c->device));
-    double* d = nullptr;
-    NALO_HIP(c, hipMalloc((void**)&d, (size_t)n * 8));
-    nalo_constants_kernel<<<1, 1, 0, c->stream>>>(d);
+    DevBuf<double> d;
+    NALO_HIP(c, d.reserve(n));
+    nalo_constants_kernel<<<1, 1, 0, c->stream>>>(d.p);
     std::vector<double> h(n);
-    hipError_t e = hipMemcpyAsync(h.data(), d, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    NALO_HIP(c, e);
+    NALO_HIP(c, hipMemcpyAsync(h.data(), d.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n && i < cap; ++i) values[i] = h[i];
     return n;
 }
@@ -143,9 +113,9 @@ int nalo_frame_upload(nalo_ctx* c, int slot, const float* irradiance, const floa
     NALO_HIP(c, hipSetDevice(c->device));
     FrameSlot& s = c->slots[slot];
     const size_t n0 = (size_t)c->w * c->h;
-    NALO_HIP(c, hipMemcpyAsync(s.I[0], irradiance, n0 * 4, hipMemcpyHostToDevice, c->stream));
-    if (mask) { if (!s.mask) NALO_HIP(c, hipMalloc((void**)&s.mask, n0 * 4)); NALO_HIP(c, hipMemcpyAsync(s.mask, mask, n0 * 4, hipMemcpyHostToDevice, c->stream)); }
-    if (bgr) { if (!s.bgr) NALO_HIP(c, hipMalloc((void**)&s.bgr, n0 * 3)); NALO_HIP(c, hipMemcpyAsync(s.bgr, bgr, n0 * 3, hipMemcpyHostToDevice, c->stream)); }
+    NALO_HIP(c, hipMemcpyAsync(s.I[0].p, irradiance, n0 * 4, hipMemcpyHostToDevice, c->stream));
+    if (mask) { NALO_HIP(c, s.mask.reserve(n0)); NALO_HIP(c, hipMemcpyAsync(s.mask.p, mask, n0 * 4, hipMemcpyHostToDevice, c->stream)); }
+    if (bgr) { NALO_HIP(c, s.bgr.reserve(n0 * 3)); NALO_HIP(c, hipMemcpyAsync(s.bgr.p, bgr, n0 * 3, hipMemcpyHostToDevice, c->stream)); }
     const float* gdev = nullptr;
     if (gammaB) { NALO_HIP(c, c->upload_tmp.reserve(256)); NALO_HIP(c, hipMemcpyAsync(c->upload_tmp.p, gammaB, 256 * 4, hipMemcpyHostToDevice, c->stream)); gdev = c->upload_tmp.p; }
     int rc = pyramid_build(c, s, gdev);
@@ -169,7 +139,7 @@ static int gamma_upload_async(nalo_ctx* c, const float* gammaB) {
     NALO_HIP(c, hipEventRecord(c->ev_main, c->stream));
     NALO_HIP(c, hipStreamWaitEvent(c->copy, c->ev_main, 0));
     std::memcpy(c->gamma_last, gammaB, sizeof(c->gamma_last));
-    NALO_HIP(c, hipMemcpyAsync(c->gamma_dev, c->gamma_last, 256 * 4, hipMemcpyHostToDevice, c->copy));   // from the context's copy: the caller's table may change after the call
+    NALO_HIP(c, hipMemcpyAsync(c->gamma_dev.p, c->gamma_last, 256 * 4, hipMemcpyHostToDevice, c->copy));   // from the context's copy: the caller's table may change after the call
     c->gamma_have = true;
     return NALO_OK;
 }
@@ -177,23 +147,23 @@ int nalo_frame_upload_async(nalo_ctx* c, int slot, const float* irradiance, cons
     if (!c || !irradiance || slot < 0 || slot >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_frame_upload_async: bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
     FrameSlot& s = c->slots[slot];
-    if (!c->copy) { NALO_HIP(c, hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking)); NALO_HIP(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming)); }
-    if (!s.ev_up) NALO_HIP(c, hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
+    NALO_HIP(c, c->copy.create()); NALO_HIP(c, c->ev_main.create(hipEventDisableTiming));
+    NALO_HIP(c, s.ev_up.create(hipEventDisableTiming));
     const size_t n0 = (size_t)c->w * c->h;
-    if (mask && !s.mask) NALO_HIP(c, hipMalloc((void**)&s.mask, n0 * 4));
-    if (bgr && !s.bgr) NALO_HIP(c, hipMalloc((void**)&s.bgr, n0 * 3));
-    if (gammaB && !c->gamma_dev) NALO_HIP(c, hipMalloc((void**)&c->gamma_dev, 256 * 4));
+    if (mask) NALO_HIP(c, s.mask.reserve(n0));
+    if (bgr) NALO_HIP(c, s.bgr.reserve(n0 * 3));
+    if (gammaB) NALO_HIP(c, c->gamma_dev.reserve(256));
     if (s.valid) {                                                   // kernels already queued on the main stream may still read this slot
         NALO_HIP(c, hipEventRecord(c->ev_main, c->stream));
         NALO_HIP(c, hipStreamWaitEvent(c->copy, c->ev_main, 0));
     }
-    NALO_HIP(c, hipMemcpyAsync(s.I[0], irradiance, n0 * 4, hipMemcpyHostToDevice, c->copy));
-    if (mask) NALO_HIP(c, hipMemcpyAsync(s.mask, mask, n0 * 4, hipMemcpyHostToDevice, c->copy));
-    if (bgr) NALO_HIP(c, hipMemcpyAsync(s.bgr, bgr, n0 * 3, hipMemcpyHostToDevice, c->copy));
+    NALO_HIP(c, hipMemcpyAsync(s.I[0].p, irradiance, n0 * 4, hipMemcpyHostToDevice, c->copy));
+    if (mask) NALO_HIP(c, hipMemcpyAsync(s.mask.p, mask, n0 * 4, hipMemcpyHostToDevice, c->copy));
+    if (bgr) NALO_HIP(c, hipMemcpyAsync(s.bgr.p, bgr, n0 * 3, hipMemcpyHostToDevice, c->copy));
     { int rg = gamma_upload_async(c, gammaB); if (rg) return rg; }
     NALO_HIP(c, hipEventRecord(s.ev_up, c->copy));
     NALO_HIP(c, hipStreamWaitEvent(c->stream, s.ev_up, 0));
-    int rc = pyramid_build(c, s, gammaB ? c->gamma_dev : nullptr);
+    int rc = pyramid_build(c, s, gammaB ? c->gamma_dev.p : nullptr);
     if (rc) return rc;
     pixsel_invalidate_hists(c, slot);
     s.valid = true;
@@ -237,12 +207,12 @@ int nalo_frame_upload_raw(nalo_ctx* c, int slot, const void* raw, int bytes_per_
     if (photometric > 0 && bytes_per_px == 2 && c->und_GDepth < 65536) return fail(c, NALO_ERR_ARG, "nalo_frame_upload_raw: 16-bit frames index G beyond its depth");
     NALO_HIP(c, c->und_raw.reserve(no * 2));
     NALO_HIP(c, hipMemcpyAsync(c->und_raw.p, raw, no * bytes_per_px, hipMemcpyHostToDevice, c->stream));
-    if (mask_org) { NALO_HIP(c, c->und_mask.reserve(no)); NALO_HIP(c, hipMemcpyAsync(c->und_mask.p, mask_org, no, hipMemcpyHostToDevice, c->stream)); if (!s.mask) NALO_HIP(c, hipMalloc((void**)&s.mask, n0 * 4)); }
-    if (bgr_org) { NALO_HIP(c, c->und_bgr.reserve(no * 3)); NALO_HIP(c, hipMemcpyAsync(c->und_bgr.p, bgr_org, no * 3, hipMemcpyHostToDevice, c->stream)); if (!s.bgr) NALO_HIP(c, hipMalloc((void**)&s.bgr, n0 * 3)); }
+    if (mask_org) { NALO_HIP(c, c->und_mask.reserve(no)); NALO_HIP(c, hipMemcpyAsync(c->und_mask.p, mask_org, no, hipMemcpyHostToDevice, c->stream)); NALO_HIP(c, s.mask.reserve(n0)); }
+    if (bgr_org) { NALO_HIP(c, c->und_bgr.reserve(no * 3)); NALO_HIP(c, hipMemcpyAsync(c->und_bgr.p, bgr_org, no * 3, hipMemcpyHostToDevice, c->stream)); NALO_HIP(c, s.bgr.reserve(n0 * 3)); }
     const float* gdev = nullptr;
     if (gammaB) { NALO_HIP(c, c->upload_tmp.reserve(256)); NALO_HIP(c, hipMemcpyAsync(c->upload_tmp.p, gammaB, 256 * 4, hipMemcpyHostToDevice, c->stream)); gdev = c->upload_tmp.p; }
     int rc = ingest_launch(c, c->stream, c->und_raw.p, bytes_per_px, c->und_wOrg, c->und_hOrg, c->und_G.p, c->und_vig ? c->und_vinv.p : nullptr, c->und_remap ? reinterpret_cast<const float2*>(c->und_rxy.p) : nullptr,
-                           photometric, factor, mask_org ? c->und_mask.p : nullptr, bgr_org ? c->und_bgr.p : nullptr, s.I[0], s.mask, s.bgr);
+                           photometric, factor, mask_org ? c->und_mask.p : nullptr, bgr_org ? c->und_bgr.p : nullptr, s.I[0].p, s.mask.p, s.bgr.p);
     if (rc) return rc;
     rc = pyramid_build(c, s, gdev);
     if (rc) return rc;
@@ -264,22 +234,22 @@ int nalo_frame_upload_raw_async(nalo_ctx* c, int slot, const void* raw, int byte
     int photometric = c->und_photometric;
     if (exposure_time <= 0) photometric = 0;
     if (photometric > 0 && bytes_per_px == 2 && c->und_GDepth < 65536) return fail(c, NALO_ERR_ARG, "nalo_frame_upload_raw_async: 16-bit frames index G beyond its depth");
-    if (!c->copy) { NALO_HIP(c, hipStreamCreateWithFlags(&c->copy, hipStreamNonBlocking)); NALO_HIP(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming)); }
-    if (!s.ev_up) NALO_HIP(c, hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming));
-    if (s.raw_cap < no * 2) { if (s.raw) { NALO_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(s.raw); } s.raw = nullptr; s.raw_cap = 0; NALO_HIP(c, hipMalloc((void**)&s.raw, no * 2)); s.raw_cap = no * 2; }
-    if (gammaB && !c->gamma_dev) NALO_HIP(c, hipMalloc((void**)&c->gamma_dev, 256 * 4));
+    NALO_HIP(c, c->copy.create()); NALO_HIP(c, c->ev_main.create(hipEventDisableTiming));
+    NALO_HIP(c, s.ev_up.create(hipEventDisableTiming));
+    if (s.raw.cap < no * 2) { if (s.raw.p) NALO_HIP(c, hipStreamSynchronize(c->stream)); NALO_HIP(c, s.raw.reserve(no * 2)); }   // the ingest kernel of an earlier frame may still read the old block
+    if (gammaB) NALO_HIP(c, c->gamma_dev.reserve(256));
     if (s.valid) {                                                   // kernels already queued on the main stream may still read this slot (incl. its raw buffer)
         NALO_HIP(c, hipEventRecord(c->ev_main, c->stream));
         NALO_HIP(c, hipStreamWaitEvent(c->copy, c->ev_main, 0));
     }
-    NALO_HIP(c, hipMemcpyAsync(s.raw, raw, no * bytes_per_px, hipMemcpyHostToDevice, c->copy));
+    NALO_HIP(c, hipMemcpyAsync(s.raw.p, raw, no * bytes_per_px, hipMemcpyHostToDevice, c->copy));
     { int rg = gamma_upload_async(c, gammaB); if (rg) return rg; }
     NALO_HIP(c, hipEventRecord(s.ev_up, c->copy));
     NALO_HIP(c, hipStreamWaitEvent(c->stream, s.ev_up, 0));
-    int rc = ingest_launch(c, c->stream, s.raw, bytes_per_px, c->und_wOrg, c->und_hOrg, c->und_G.p, c->und_vig ? c->und_vinv.p : nullptr, c->und_remap ? reinterpret_cast<const float2*>(c->und_rxy.p) : nullptr,
-                           photometric, factor, nullptr, nullptr, s.I[0], nullptr, nullptr);
+    int rc = ingest_launch(c, c->stream, s.raw.p, bytes_per_px, c->und_wOrg, c->und_hOrg, c->und_G.p, c->und_vig ? c->und_vinv.p : nullptr, c->und_remap ? reinterpret_cast<const float2*>(c->und_rxy.p) : nullptr,
+                           photometric, factor, nullptr, nullptr, s.I[0].p, nullptr, nullptr);
     if (rc) return rc;
-    rc = pyramid_build(c, s, gammaB ? c->gamma_dev : nullptr);
+    rc = pyramid_build(c, s, gammaB ? c->gamma_dev.p : nullptr);
     if (rc) return rc;
     pixsel_invalidate_hists(c, slot);
     s.valid = true;
@@ -309,10 +279,10 @@ int nalo_frame_download(nalo_ctx* c, int slot, int lvl, float* dI3, float* absg)
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     if (dI3) {
         std::vector<float4> tmp(npx);
-        NALO_HIP(c, hipMemcpy(tmp.data(), s.dI[lvl], npx * 16, hipMemcpyDeviceToHost));
+        NALO_HIP(c, hipMemcpy(tmp.data(), s.dI[lvl].p, npx * 16, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < npx; ++i) { dI3[3 * i] = tmp[i].x; dI3[3 * i + 1] = tmp[i].y; dI3[3 * i + 2] = tmp[i].z; }
     }
-    if (absg) NALO_HIP(c, hipMemcpy(absg, s.absg[lvl], npx * 4, hipMemcpyDeviceToHost));
+    if (absg) NALO_HIP(c, hipMemcpy(absg, s.absg[lvl].p, npx * 4, hipMemcpyDeviceToHost));
     return NALO_OK;
 }
 
@@ -327,16 +297,11 @@ static int upload4(nalo_ctx* c, int n, const float* a, const float* b, const flo
     // one pinned staging buffer, one H2D copy (four pageable copies cost four blocking round trips); the previous upload has been consumed:
     // trk_build_ref ends on a flag published after it in stream order
     NALO_HIP(c, c->upload_tmp.reserve((size_t)4 * n + 256));
-    if (c->pinned_f_cap < (size_t)4 * n) {
-        if (c->pinned_f) (void)hipHostFree(c->pinned_f);
-        c->pinned_f = nullptr; c->pinned_f_cap = 0;
-        NALO_HIP(c, hipHostMalloc((void**)&c->pinned_f, (size_t)4 * n * 4 + 1024));
-        c->pinned_f_cap = (size_t)4 * n + 256;
-    }
+    if (c->pinned_f.cap < (size_t)4 * n) NALO_HIP(c, c->pinned_f.reserve((size_t)4 * n + 256));   // 256 floats of slack: a slightly larger cloud does not reallocate
     float* base = c->upload_tmp.p + 256;
     const float* src[4] = {a, b, d, e};
-    for (int k = 0; k < 4; ++k) { std::memcpy(c->pinned_f + (size_t)k * n, src[k], (size_t)n * 4); dev[k] = base + (size_t)k * n; }
-    NALO_HIP(c, hipMemcpyAsync(base, c->pinned_f, (size_t)4 * n * 4, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 4; ++k) { std::memcpy(c->pinned_f.p + (size_t)k * n, src[k], (size_t)n * 4); dev[k] = base + (size_t)k * n; }
+    NALO_HIP(c, hipMemcpyAsync(base, c->pinned_f.p, (size_t)4 * n * 4, hipMemcpyHostToDevice, c->stream));
     return NALO_OK;
 }
 
@@ -406,7 +371,7 @@ int nalo_trk_append_plane_points(nalo_ctx* c, const float dir[3], float dis_plan
     if (!c || !dir || !rect) return fail(c, NALO_ERR_ARG, "nalo_trk_append_plane_points: bad argument");
     if (c->slot_ref < 0 || !c->slots[c->slot_ref].valid || !c->pc_u[0].p) return fail(c, NALO_ERR_STATE, "nalo_trk_append_plane_points: no tracking reference");
     const FrameSlot& s = c->slots[c->slot_ref];
-    if (!s.mask) return fail(c, NALO_ERR_STATE, "nalo_trk_append_plane_points: the reference frame was uploaded without a mask");
+    if (!s.mask.p) return fail(c, NALO_ERR_STATE, "nalo_trk_append_plane_points: the reference frame was uploaded without a mask");
     const int minx = rect[0], maxx = rect[1], miny = rect[2], maxy = rect[3];
     // `if(maxx>w[0]-1||minx<1||maxy>h[0]-1||miny<1) continue;` and `if (refMaskColor==0) continue;` (:621-630): nothing is appended
     if (n_added) *n_added = 0;
@@ -418,7 +383,7 @@ int nalo_trk_append_plane_points(nalo_ctx* c, const float dir[3], float dis_plan
     if ((size_t)n0 + 2 + (size_t)nx * ny > c->pc_u[0].cap) return fail(c, NALO_ERR_STATE, "nalo_trk_append_plane_points: the level-0 cloud would outgrow its w*h buffer");
     if (nx == 0 || ny == 0) return NALO_OK;
     NALO_HIP(c, c->scan_tmp.reserve(64));
-    int rc = trk_append_plane_launch(c, s.mask, s.dI[0], dir, dis_plane, (float)refMaskColor, x0, nx, y0, ny, n0, c->scan_tmp.p); if (rc) return rc;
+    int rc = trk_append_plane_launch(c, s.mask.p, s.dI[0].p, dir, dis_plane, (float)refMaskColor, x0, nx, y0, ny, n0, c->scan_tmp.p); if (rc) return rc;
     int added = 0;
     NALO_HIP(c, hipMemcpyAsync(&added, c->scan_tmp.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
@@ -658,15 +623,16 @@ int nalo_imm_create(nalo_ctx* c, int slot_host, int n, const int* u, const int* 
     // words: u(n) v(n) | color(8n) weights(8n) gradH(3n) energyTH(n)
     const size_t N = (size_t)n;
     int rc = imm_stage(c, 22 * N); if (rc) return rc;
-    std::memcpy(c->imm_host, u, N * 4); std::memcpy(c->imm_host + N, v, N * 4);
+    float* hst = c->imm_host.p;
+    std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4);
     float* d = c->imm_dev.p;
-    NALO_HIP(c, hipMemcpyAsync(d, c->imm_host, 2 * N * 4, hipMemcpyHostToDevice, c->stream));
-    rc = imm_create_launch(c, c->slots[slot_host].dI[0], n, (const int*)d, (const int*)(d + N), d + 2 * N, d + 10 * N, d + 18 * N, d + 21 * N);
+    NALO_HIP(c, hipMemcpyAsync(d, hst, 2 * N * 4, hipMemcpyHostToDevice, c->stream));
+    rc = imm_create_launch(c, c->slots[slot_host].dI[0].p, n, (const int*)d, (const int*)(d + N), d + 2 * N, d + 10 * N, d + 18 * N, d + 21 * N);
     if (rc) return rc;
-    NALO_HIP(c, hipMemcpyAsync(c->imm_host + 2 * N, d + 2 * N, 20 * N * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(hst + 2 * N, d + 2 * N, 20 * N * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
-    std::memcpy(color, c->imm_host + 2 * N, 8 * N * 4); std::memcpy(weights, c->imm_host + 10 * N, 8 * N * 4);
-    std::memcpy(gradH, c->imm_host + 18 * N, 3 * N * 4); std::memcpy(energyTH, c->imm_host + 21 * N, N * 4);
+    std::memcpy(color, hst + 2 * N, 8 * N * 4); std::memcpy(weights, hst + 10 * N, 8 * N * 4);
+    std::memcpy(gradH, hst + 18 * N, 3 * N * 4); std::memcpy(energyTH, hst + 21 * N, N * 4);
     return NALO_OK;
 }
 
@@ -684,7 +650,7 @@ int nalo_imm_trace(nalo_ctx* c, int slot_new, int n, const float* u, const float
     // words: [0,22n) u v color weights gradH energyTH | [22n,23n) host_idx | [23n,30n) idmin idmax status quality lastUV(2) lastInterval | [30n, +14nh) KRKi Kt aff
     const size_t N = (size_t)n, H = (size_t)nh;
     int rc = imm_stage(c, 30 * N + 14 * H); if (rc) return rc;
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4); std::memcpy(hst + 2 * N, color, 8 * N * 4); std::memcpy(hst + 10 * N, weights, 8 * N * 4);
     std::memcpy(hst + 18 * N, gradH, 3 * N * 4); std::memcpy(hst + 21 * N, energyTH, N * 4); std::memcpy(hst + 22 * N, host_idx, N * 4);
     std::memcpy(hst + 23 * N, idepth_min, N * 4); std::memcpy(hst + 24 * N, idepth_max, N * 4); std::memcpy(hst + 25 * N, status, N * 4); std::memcpy(hst + 26 * N, quality, N * 4);
@@ -692,7 +658,7 @@ int nalo_imm_trace(nalo_ctx* c, int slot_new, int n, const float* u, const float
     std::memcpy(hst + 30 * N, KRKi, 9 * H * 4); std::memcpy(hst + 30 * N + 9 * H, Kt, 3 * H * 4); std::memcpy(hst + 30 * N + 12 * H, aff, 2 * H * 4);
     float* d = c->imm_dev.p;
     NALO_HIP(c, hipMemcpyAsync(d, hst, (30 * N + 14 * H) * 4, hipMemcpyHostToDevice, c->stream));
-    rc = imm_trace_launch(c, c->slots[slot_new].dI[0], n, d, (const int*)(d + 22 * N), d + 30 * N, d + 30 * N + 9 * H, d + 30 * N + 12 * H,
+    rc = imm_trace_launch(c, c->slots[slot_new].dI[0].p, n, d, (const int*)(d + 22 * N), d + 30 * N, d + 30 * N + 9 * H, d + 30 * N + 12 * H,
                           d + 23 * N, d + 24 * N, (int*)(d + 25 * N), d + 26 * N, d + 27 * N, d + 29 * N);
     if (rc) return rc;
     NALO_HIP(c, hipMemcpyAsync(hst + 23 * N, d + 23 * N, 7 * N * 4, hipMemcpyDeviceToHost, c->stream));
@@ -714,7 +680,7 @@ int nalo_imm_resident_set(nalo_ctx* c, int n, const float* u, const float* v, co
     const size_t N = (size_t)n;
     int rc = imm_stage(c, 30 * N); if (rc) return rc;
     NALO_HIP(c, c->imm_res.reserve(30 * N + 256));
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     for (int i = 0; i < n; ++i) { if (host_idx[i] < 0) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_set: negative host_idx"); c->imm_res_maxhost = std::max(c->imm_res_maxhost, host_idx[i]); }
     std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4); std::memcpy(hst + 2 * N, color, 8 * N * 4); std::memcpy(hst + 10 * N, weights, 8 * N * 4);
     std::memcpy(hst + 18 * N, gradH, 3 * N * 4); std::memcpy(hst + 21 * N, energyTH, N * 4); std::memcpy(hst + 22 * N, host_idx, N * 4);
@@ -737,7 +703,7 @@ int nalo_imm_resident_trace(nalo_ctx* c, int slot_new, int nh, const float* KRKi
     std::memcpy(hk, KRKi, 9 * H * 4); std::memcpy(hk + 9 * H, Kt, 3 * H * 4); std::memcpy(hk + 12 * H, aff, 2 * H * 4);
     float* d = c->imm_res.p;
     int rc = imm_put_launch(c, d + 30 * N, hk, (int)(14 * H)); if (rc) return rc;
-    return imm_trace_launch(c, c->slots[slot_new].dI[0], c->imm_res_n, d, (const int*)(d + 22 * N), d + 30 * N, d + 30 * N + 9 * H, d + 30 * N + 12 * H,
+    return imm_trace_launch(c, c->slots[slot_new].dI[0].p, c->imm_res_n, d, (const int*)(d + 22 * N), d + 30 * N, d + 30 * N + 9 * H, d + 30 * N + 12 * H,
                             d + 23 * N, d + 24 * N, (int*)(d + 25 * N), d + 26 * N, d + 27 * N, d + 29 * N);
 }
 int nalo_imm_resident_get(nalo_ctx* c, float* idepth_min, float* idepth_max, int* status, float* quality, float* lastTraceUV, float* lastTracePixelInterval) {
@@ -747,7 +713,7 @@ int nalo_imm_resident_get(nalo_ctx* c, float* idepth_min, float* idepth_max, int
     NALO_HIP(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->imm_res_n;
     int rc = imm_stage(c, 7 * N); if (rc) return rc;
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     NALO_HIP(c, hipMemcpyAsync(hst, c->imm_res.p + 23 * N, 7 * N * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(idepth_min, hst, N * 4); std::memcpy(idepth_max, hst + N, N * 4); std::memcpy(status, hst + 2 * N, N * 4); std::memcpy(quality, hst + 3 * N, N * 4);
@@ -776,7 +742,7 @@ int nalo_init_calc_res_and_gs(nalo_ctx* c, int slot_first, int slot_new, int lvl
         // words in: [u | v | idepth_new | iR | energy(2n) | outlierTH | isGood bytes]; out: [energy_new(2n) | maxstep | lastHessian_new | Jb(10n) | isGood_new bytes]; then 96 doubles
         const size_t N = (size_t)n, NB = (N + 3) / 4, in_w = 7 * N + NB, out_w = 14 * N + NB, tot = in_w + out_w + 2 * 96 + 2;
         int rc = imm_stage(c, tot); if (rc) return rc;
-        float* hst = c->imm_host;
+        float* hst = c->imm_host.p;
         std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4); std::memcpy(hst + 2 * N, idepth_new, N * 4); std::memcpy(hst + 3 * N, iR, N * 4);
         std::memcpy(hst + 4 * N, energy, 2 * N * 4); std::memcpy(hst + 6 * N, outlierTH, N * 4); std::memcpy(hst + 7 * N, isGood, N);
         float* ho = hst + in_w;
@@ -784,7 +750,7 @@ int nalo_init_calc_res_and_gs(nalo_ctx* c, int slot_first, int slot_new, int lvl
         float* d = c->imm_dev.p;
         const size_t sums_off = (in_w + out_w + 1) & ~(size_t)1;                                                      // 8-byte aligned
         NALO_HIP(c, hipMemcpyAsync(d, hst, (in_w + out_w) * 4, hipMemcpyHostToDevice, c->stream));
-        P.colorRef = c->slots[slot_first].dI[lvl]; P.colorNew = c->slots[slot_new].dI[lvl];
+        P.colorRef = c->slots[slot_first].dI[lvl].p; P.colorNew = c->slots[slot_new].dI[lvl].p;
         P.u = d; P.v = d + N; P.idepth = nullptr; P.idepth_new = d + 2 * N; P.iR = d + 3 * N; P.energy = d + 4 * N; P.outlierTH = d + 6 * N; P.isGood = (const uint8_t*)(d + 7 * N);
         float* outw = d + in_w;
         P.energy_new = outw; P.maxstep = outw + 2 * N; P.lastHessian_new = outw + 3 * N; P.Jb = outw + 4 * N; P.isGood_new = (uint8_t*)(outw + 14 * N);
@@ -807,7 +773,7 @@ int nalo_init_do_step(nalo_ctx* c, int n, const uint8_t* isGood, const float* Jb
     // words: [Jb(10n) | maxstep | idepth | idepth_new (in/out) | isGood bytes]
     const size_t N = (size_t)n, tot = 13 * N + (N + 3) / 4;
     int rc = imm_stage(c, tot); if (rc) return rc;
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     std::memcpy(hst, JbBuffer, 10 * N * 4); std::memcpy(hst + 10 * N, maxstep, N * 4); std::memcpy(hst + 11 * N, idepth, N * 4); std::memcpy(hst + 12 * N, idepth_new, N * 4);
     std::memcpy(hst + 13 * N, isGood, N);
     float* d = c->imm_dev.p;
@@ -866,26 +832,25 @@ int nalo_hbm_calibrate(nalo_ctx* c, size_t bytes, int iters, double* copy_GBs, d
     bytes &= ~(size_t)15;
     if (!c || bytes < ((size_t)1 << 20) || iters < 1) return fail(c, NALO_ERR_ARG, "nalo_hbm_calibrate: bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
-    float4 *a = nullptr, *b = nullptr, *d = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto done = [&](int rc) { if (a) (void)hipFree(a); if (b) (void)hipFree(b); if (d) (void)hipFree(d); if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); return rc; };
-    if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess || hipMalloc((void**)&d, bytes) != hipSuccess ||
-        hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return done(fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: allocation failed"));
-    if (hipMemsetAsync(a, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(b, 0, bytes, c->stream) != hipSuccess) return done(fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: memset failed"));
     const size_t n = bytes / 16;
+    DevBuf<float4> a, b, d;
+    Event e0, e1;
+    if (a.reserve(n) != hipSuccess || b.reserve(n) != hipSuccess || d.reserve(n) != hipSuccess ||
+        e0.create() != hipSuccess || e1.create() != hipSuccess) return fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: allocation failed");
+    if (hipMemsetAsync(a.p, 0, bytes, c->stream) != hipSuccess || hipMemsetAsync(b.p, 0, bytes, c->stream) != hipSuccess) return fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: memset failed");
     for (int which = 0; which < 2; ++which) {
         double* out = which ? triad_GBs : copy_GBs;
         if (!out) continue;
-        hbm_stream_launch(c->stream, a, b, d, n, which);                               // untimed: first touch, clocks
+        hbm_stream_launch(c->stream, a.p, b.p, d.p, n, which);                               // untimed: first touch, clocks
         (void)hipEventRecord(e0, c->stream);
-        for (int i = 0; i < iters; ++i) hbm_stream_launch(c->stream, a, b, d, n, which);
+        for (int i = 0; i < iters; ++i) hbm_stream_launch(c->stream, a.p, b.p, d.p, n, which);
         (void)hipEventRecord(e1, c->stream);
-        if (hipEventSynchronize(e1) != hipSuccess) return done(fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: kernel failed"));
+        if (hipEventSynchronize(e1) != hipSuccess) return fail(c, NALO_ERR_HIP, "nalo_hbm_calibrate: kernel failed");
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
         *out = (which ? 3.0 : 2.0) * (double)bytes * iters / ((double)ms * 1e-3) / 1e9;
     }
-    return done(NALO_OK);
+    return NALO_OK;
 }
 
 }  // extern "C"

@@ -7,31 +7,6 @@
 
 namespace nalo {
 
-void ba_launch_sc(hipStream_t s, const BADev& B, int T, int shift, float priorScaleMarg, int margOnly);
-void ba_launch_linearize(hipStream_t s, const BADev& B, int mode, int fix, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-void ba_launch_reset_oob(hipStream_t s, const BADev& B);
-void ba_launch_restore(hipStream_t s, const BADev& B, const float4* geo, const uint8_t* state, const uint8_t* flags, const float* prior, const float* th);
-void ba_launch_reduce(hipStream_t s, const BADev& B, const int* host_blk, int NPL, double* acc13, double* misc, double* G, bool top, bool sc,
-                      const float* step_partial, int step_blocks, double* step_out, bool with_th, double* pub, double seq, unsigned* ticket);
-void ba_launch_resub_step(hipStream_t s, const BADev& B, float stepfacD, float* partial, const XadArg& karg, bool karg_is_x);
-int ba_launch_stitch(hipStream_t s, const StitchDev& D, bool top, bool sc, double* mapped, int ntail, double seq);
-void ba_launch_resub(hipStream_t s, const BADev& B, const XadArg& karg, bool karg_is_x);
-void ba_launch_resub_step_gated(hipStream_t s, const BADev& B, float stepfacD, float* partial, const GateArg& gate);
-void ba_launch_pull(hipStream_t s, float* dst, const float* src_mapped, int n);
-void ba_launch_step(hipStream_t s, const BADev& B, float stepfacD, float* partial, double* out3);
-void ba_launch_step_sums(hipStream_t s, const BADev& B, const float* partial, double* out3);
-void ba_launch_publish(hipStream_t s, const double* src, double* dst_mapped, int n, double seq, unsigned* ticket);
-void ba_launch_th_install(hipStream_t s, const double* tail2, float* th);
-void ba_launch_th_tail(hipStream_t s, const float* th, double* tail2);
-void ba_launch_energy_th(hipStream_t s, const BADev& B);
-void ba_launch_set_th(hipStream_t s, float* dst, const float* th, int W);
-void ba_launch_energy_th_step(hipStream_t s, const BADev& B, int step);
-void ba_launch_lenergy(hipStream_t s, const BADev& B, double* partial);
-void ba_launch_load_backup(hipStream_t s, const BADev& B);
-void ba_launch_swgray(hipStream_t s, const BADev& B, const double* Rt, double* partial);
-void ba_launch_set_idepth(hipStream_t s, const BADev& B, int mode, int host_sel, double scale);
-void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, float* out);
-
 struct HostFrame {
     int slot = 0, frameID = 0;
     SE3 evalPT, PRE_worldToCam, PRE_camToWorld;
@@ -71,18 +46,17 @@ struct BAWindow {
     DevBuf<unsigned> th_hist;                                        // the radix select's state words (kernels_ba.hip: ba_th_fill_kernel)
     bool step_fused = false, step_sums_deferred = false;            // optimize(): resubstitute + point step in one kernel, its sums finished by the reduce launch
     bool th_pending = false;                                        // a linearize pass whose frameEnergyTH quantile has not been launched yet
-    DevBuf<double> acc13, G, AD, stitched;                      // stitched: [H~_A ((n1)^2) | H~_sc ((n1)^2) | misc (2 W^2) | step sums (3) | TH sum, ranks]
+    DevBuf<double> acc13, G, AD, stitched;
+    StitchLayout lay = StitchLayout(0, 0);                           // of stitched and stitched_host, as nalo_ba_set_window allocated them
     DevBuf<unsigned> st_ticket;
     StitchDev sd{};
-    double* ad_host = nullptr; size_t ad_cap = 0;                   // pinned staging of AD
-    hipEvent_t ev_ad = nullptr;
-    double* stitched_host = nullptr;                                // pinned mirror
-    float* up_host = nullptr;                                       // pinned staging of the step: [- | calib 16 | xc 64 | xAd] (the precalc records live in pre_map)
-    size_t up_cap = 0;
+    HostBuf<double> ad_host;                                        // pinned staging of AD
+    Event ev_ad;
+    HostBuf<double> stitched_host;                                  // pinned, mapped mirror
+    HostBuf<float> up_host;                                         // pinned staging of the step: [- | calib 16 | xc 64 | xAd] (the precalc records live in pre_map)
     // small windows: the precalc records are not copied at all - ba_linearize reads them (scalar loads, one record per workgroup) straight from mapped host
     // memory; four rotating blocks, a block is rewritten only after the host has seen the stream drain past its last reader (pre_synced)
-    float* pre_map[4] = {nullptr, nullptr, nullptr, nullptr}; float* pre_map_dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t pre_map_cap = 0; long pre_pos = 0, pre_synced = 0;
+    HostBuf<float> pre_map[4]; long pre_pos = 0, pre_synced = 0;    // the four blocks are (re)allocated together
     bool have_lin = false, have_sc = false, stitched_top = false, stitched_sc = false, points_set = false, res_set = false;
     bool pt_acc_on_read = false;                                    // nalo_ba_get_points may run the per-point accumulation of an explicit nalo_ba_linearize
     int sc_shift = -1;
@@ -92,17 +66,16 @@ struct BAWindow {
     double snap_calib[4] = {}, snap_calib_scaled[4] = {}; float snap_scaledf[4] = {}, snap_scaledi[4] = {};   // CalibHessian as it is: a fresh window holds value_scaled = K exactly,
                                                                     // setValue(value) would round it through SCALE_F * (SCALE_F_INVERSE * K)
     // small single-GPU windows: the back-substitution and the next linearisation of optimize() are enqueued BEFORE the host has solved the system (ba_device.h: GateBlock)
-    GateBlock* gate_h = nullptr; GateBlock* gate_d = nullptr; unsigned gate_x_seq = 0, gate_p_seq = 0;
+    HostBuf<GateBlock> gate_h; unsigned gate_x_seq = 0, gate_p_seq = 0;
     bool want_prelaunch = false, resub_pre = false, lin_pre = false;
     nalo_allreduce_fn hook = nullptr;
     void* hook_user = nullptr;
     bool hook_stream_ordered = false;                               // the hook enqueues its collective on nalo_stream(ctx): no host synchronisation around it
     nalo_allreduce_fn hook_side = nullptr; void* hook_side_user = nullptr;   // same sum, enqueued on nalo_side_stream(ctx): the threshold's histograms
     DevBuf<double> th_buf;                                          // level A | level B histograms of the radix select as doubles (2 x kThDblAB: the side stream's all-reduce payloads)
-    hipEvent_t ev_lin = nullptr, ev_th = nullptr; bool th_side_inflight = false;   // sharded windows run the quantile kernels on the side stream, under the SC kernel
-    bool th_lo_pending = false;                                     // level C's histogram sits behind the stitched systems (lo_off), not yet summed over the ranks: the next
+    Event ev_lin, ev_th; bool th_side_inflight = false;   // sharded windows run the quantile kernels on the side stream, under the SC kernel
+    bool th_lo_pending = false;                                     // level C's histogram sits behind the stitched systems (lay.lo), not yet summed over the ranks: the next
                                                                     // stitch sums it WITH the systems in one all-reduce, anything else that needs the threshold sums it alone
-    size_t lo_off = 0;
     bool never_break = false;
     DevBuf<double> small_sum;                                        // a few scalars on their way through the all-reduce hook (sum_over_ranks)
     DevBuf<double> noapply_E; std::vector<double> noapply_h;          // energy partials of a linearisation that is not applied (forceAcceptStep = false)
@@ -116,24 +89,7 @@ struct BAWindow {
 };
 
 void ba_destroy(nalo_ctx* c) {
-    BAWindow* w = c->ba;
-    if (!w) return;
-    w->pre.release(); w->frameTH.release(); w->pt_prior.release(); w->pt_step.release(); w->pt_backup.release(); w->pt_relbs.release(); w->pt_relbs2.release();
-    w->small_sum.release(); w->th_buf.release(); w->en_new.release(); w->top_partial.release(); w->sc_partial.release(); w->step_partial.release();
-    w->pt_geo.release(); w->pt_col0.release(); w->pt_col1.release(); w->pt_w0.release(); w->pt_w1.release(); w->pt_acc.release(); w->pt_hcd.release();
-    w->rs_jp0.release(); w->rs_jp1.release(); w->rs_cpt.release(); w->rs_energy.release(); w->rs_pp0.release(); w->rs_pp1.release(); w->pt_flags.release(); w->pt_ngood.release(); w->rs_state.release();
-    w->blk_host.release(); w->host_blk.release(); w->sc_grp.release(); w->blk_order.release(); w->acc13.release(); w->G.release(); w->AD.release(); w->st_ticket.release();
-    w->stitched.release(); w->th_hist.release(); w->ref_kmap.release(); w->ref_in.release();
-    if (w->ev_lin) (void)hipEventDestroy(w->ev_lin);
-    if (w->ev_th) (void)hipEventDestroy(w->ev_th);
-    w->snap_geo.release(); w->snap_state.release(); w->snap_flags.release(); w->snap_prior.release();
-    if (w->gate_h) (void)hipHostFree(w->gate_h);
-    if (w->stitched_host) (void)hipHostFree(w->stitched_host);
-    if (w->up_host) (void)hipHostFree(w->up_host);
-    for (float* p : w->pre_map) if (p) (void)hipHostFree(p);
-    if (w->ad_host) (void)hipHostFree(w->ad_host);
-    if (w->ev_ad) (void)hipEventDestroy(w->ev_ad);
-    delete w;
+    delete c->ba;
     c->ba = nullptr;
 }
 
@@ -236,16 +192,16 @@ static int upload_adjoints(nalo_ctx* c) {
     // the stitch kernel reads the fp64 adjoints: AD = [adHost | adTarget]
     // (behind them, in the same upload: the float adjoints the back-substitution of a window of more than 8 frames builds its xAd rows from)
     const size_t nad = (size_t)2 * W * W * 64;
-    if (w.ad_cap < nad) { if (w.ad_host) (void)hipHostFree(w.ad_host); NALO_HIP(c, hipHostMalloc((void**)&w.ad_host, nad * 12)); w.ad_cap = nad; }
-    if (!w.ev_ad) NALO_HIP(c, hipEventCreateWithFlags(&w.ev_ad, hipEventDisableTiming));
+    NALO_HIP(c, w.ad_host.reserve(nad + nad / 2));                   // nad doubles + nad floats
+    if (!w.ev_ad) NALO_HIP(c, w.ev_ad.create(hipEventDisableTiming));
     else NALO_HIP(c, hipEventSynchronize(w.ev_ad));                  // the previous upload has left the staging buffer
-    std::memcpy(w.ad_host, w.adHost.data(), (size_t)W * W * 64 * 8);
-    std::memcpy(w.ad_host + (size_t)W * W * 64, w.adTarget.data(), (size_t)W * W * 64 * 8);
-    float* adf = reinterpret_cast<float*>(w.ad_host + nad);
+    std::memcpy(w.ad_host.p, w.adHost.data(), (size_t)W * W * 64 * 8);
+    std::memcpy(w.ad_host.p + (size_t)W * W * 64, w.adTarget.data(), (size_t)W * W * 64 * 8);
+    float* adf = reinterpret_cast<float*>(w.ad_host.p + nad);
     std::memcpy(adf, w.adHostF.data(), (size_t)W * W * 64 * 4);
     std::memcpy(adf + (size_t)W * W * 64, w.adTargetF.data(), (size_t)W * W * 64 * 4);
     NALO_HIP(c, w.AD.reserve(nad + nad / 2));
-    NALO_HIP(c, hipMemcpyAsync(w.AD.p, w.ad_host, nad * 12, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.AD.p, w.ad_host.p, nad * 12, hipMemcpyHostToDevice, c->stream));
     w.dev.adF = reinterpret_cast<const float*>(w.AD.p + nad);
     NALO_HIP(c, hipEventRecord(w.ev_ad, c->stream));
     w.sd.AD = w.AD.p;
@@ -272,12 +228,7 @@ static int set_precalc(nalo_ctx* c) {
     for (int i = 0; i < 4; ++i) w.cDeltaF[i] = (float)(w.c_value[i] - w.c_value_zero[i]);
     for (auto& f : w.frames) frame_take_data(c->set, f);
     const size_t nfl = (size_t)W * W * kPreStride;
-    if (w.up_cap < nfl + 80) {                                             // [pre | calib 16 | xc 64 | xAd]; hipHostFree waits for copies in flight
-        if (w.up_host) (void)hipHostFree(w.up_host);
-        w.up_host = nullptr; w.up_cap = 0;
-        NALO_HIP(c, hipHostMalloc((void**)&w.up_host, (nfl + 80 + (size_t)W * W * 8) * 4));
-        w.up_cap = nfl + 80;
-    }
+    NALO_HIP(c, w.up_host.reserve(nfl + 80 + (size_t)W * W * 8));          // [pre | calib 16 | xc 64 | xAd]; growing frees the old block, and hipHostFree waits for copies in flight
     // Small windows (the KITTI-sized ones, latency bound): no copy. The H2D blit of these 8 KB sat between the back-substitution and the next linearisation
     // with ~10 us of pipeline gaps around it plus ~5 us of runtime calls on the host; the kernels read the records from mapped host memory instead (scalar
     // loads, a few hundred bytes per workgroup over PCIe: +2 us inside ba_linearize). Large windows keep the device copy (thousands of workgroups).
@@ -291,19 +242,14 @@ static int set_precalc(nalo_ctx* c) {
     float* rec;
     {
         const size_t nfl4 = (nfl + 16 + 3) & ~(size_t)3;
-        if (w.pre_map_cap < nfl4) {
+        if (w.pre_map[3].cap < nfl4) {                                     // the last of the four to grow: an allocation that failed half way is redone
             NALO_HIP(c, hipStreamSynchronize(c->stream));
-            for (int i = 0; i < 4; ++i) {
-                if (w.pre_map[i]) (void)hipHostFree(w.pre_map[i]);
-                w.pre_map[i] = nullptr;
-                NALO_HIP(c, hipHostMalloc((void**)&w.pre_map[i], nfl4 * 4, hipHostMallocMapped | hipHostMallocCoherent));
-                NALO_HIP(c, hipHostGetDevicePointer((void**)&w.pre_map_dev[i], w.pre_map[i], 0));
-            }
-            w.pre_map_cap = nfl4; w.pre_synced = w.pre_pos;
+            for (auto& b : w.pre_map) NALO_HIP(c, b.reserve(nfl4, hipHostMallocMapped | hipHostMallocCoherent));
+            w.pre_synced = w.pre_pos;
         }
         ++w.pre_pos;
         if (w.pre_pos - 4 > w.pre_synced) { NALO_HIP(c, hipStreamSynchronize(c->stream)); w.pre_synced = w.pre_pos - 1; }   // the block's last readers may still run
-        rec = w.pre_map[w.pre_pos & 3];
+        rec = w.pre_map[w.pre_pos & 3].p;
     }
     const float fx = w.c_scaledf[0], fy = w.c_scaledf[1], cx = w.c_scaledf[2], cy = w.c_scaledf[3];
     const float K[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1}, Ki[9] = {1.0f / fx, 0, -cx / fx, 0, 1.0f / fy, -cy / fy, 0, 0, 1};
@@ -330,12 +276,12 @@ static int set_precalc(nalo_ctx* c) {
     for (int i = 0; i < 4; ++i) cal[6 + i] = w.cDeltaF[i];
     NALO_HIP(c, w.pre.reserve(nfl + 32));
     if (direct) {
-        w.dev.pre = w.pre_map_dev[w.pre_pos & 3]; w.dev.calib = w.dev.pre + nfl;
+        w.dev.pre = w.pre_map[w.pre_pos & 3].dev; w.dev.calib = w.dev.pre + nfl;
         // a linearisation that was enqueued ahead of these records waits for this word (x86 stores are not reordered with earlier stores; the fence keeps the compiler honest)
-        if (w.lin_pre && w.gate_h) { __atomic_thread_fence(__ATOMIC_RELEASE); __atomic_store_n(&w.gate_h->p_seq, w.gate_p_seq, __ATOMIC_RELEASE); }
+        if (w.lin_pre && w.gate_h.p) { __atomic_thread_fence(__ATOMIC_RELEASE); __atomic_store_n(&w.gate_h.p->p_seq, w.gate_p_seq, __ATOMIC_RELEASE); }
         return NALO_OK;
     }
-    ba_launch_pull(c->stream, w.pre.p, w.pre_map_dev[w.pre_pos & 3], (int)(nfl + 16));
+    ba_launch_pull(c->stream, w.pre.p, w.pre_map[w.pre_pos & 3].dev, (int)(nfl + 16));
     NALO_HIP(c, hipGetLastError());
     w.dev.pre = w.pre.p; w.dev.calib = w.pre.p + nfl;
 
@@ -384,7 +330,7 @@ static int flush_th(nalo_ctx* c) {
     if (w.th_lo_pending) {                                            // no stitch took level C's histogram along: its own all-reduce, then the search
         w.th_lo_pending = false;
         if (!w.hook_stream_ordered) NALO_HIP(c, hipStreamSynchronize(c->stream));
-        { int rh = call_hook(c, w.hook, w.hook_user, w.stitched.p + w.lo_off, kThDblC); if (rh) return rh; }
+        { int rh = call_hook(c, w.hook, w.hook_user, w.stitched.p + w.lay.lo, kThDblC); if (rh) return rh; }
         ba_launch_energy_th_step(c->stream, w.dev, 3);
         NALO_HIP(c, hipGetLastError());
     }
@@ -402,7 +348,7 @@ static int ensure_tiled(nalo_ctx* c) {
     for (int i = 0; i < w.W; ++i) {
         FrameSlot& s = c->slots[w.frames[i].slot];
         if (!s.tiled_valid) { int rc = frame_tile_level0(c, s); if (rc) return rc; }
-        w.dev.img_t[i] = s.dI0t;
+        w.dev.img_t[i] = s.dI0t.p;
     }
     w.dev.wt = (c->w + 4) / 5;
     return NALO_OK;
@@ -433,13 +379,13 @@ static int linearize_async(nalo_ctx* c, int mode, int fix, bool keep_th = false)
     const bool th_sharded = mode == 0 && w.hook;
     const bool on_side = th_sharded && !(w.hook_stream_ordered && !w.hook_side);
     // (device-scope events: both sides of these dependencies are kernels of this context; a system-scope release behind the linearisation writes its output back first)
-    if (th_sharded && !w.ev_lin) { NALO_HIP(c, hipEventCreateWithFlags(&w.ev_lin, hipEventDisableTiming | hipEventDisableSystemFence)); NALO_HIP(c, hipEventCreateWithFlags(&w.ev_th, hipEventDisableTiming | hipEventDisableSystemFence)); }
+    if (th_sharded) { NALO_HIP(c, w.ev_lin.create(hipEventDisableTiming | hipEventDisableSystemFence)); NALO_HIP(c, w.ev_th.create(hipEventDisableTiming | hipEventDisableSystemFence)); }
     hipEvent_t lin_done = nullptr;
     {
         // the side stream's dependency on this pass is the dispatch's own completion signal (hipExtLaunchKernelGGL's stop event): an event RECORDED behind the kernel
         // is a marker packet of its own, and the next kernel of the main stream stood 14 us behind it
         ProfScope ps(c, "ba_linearize", true);
-        lin_done = ps.b ? ps.b : (on_side ? w.ev_lin : nullptr);
+        lin_done = ps.b ? ps.b : (on_side ? w.ev_lin.e : nullptr);
         ba_launch_linearize(c->stream, w.dev, mode, fix, ps.a, lin_done);
     }
     if (th_sharded) {
@@ -535,30 +481,30 @@ static bool prelaunch_eligible(const nalo_ctx* c, const BAWindow& w) {
 }
 static int prelaunch_iteration(nalo_ctx* c) {
     BAWindow& w = *c->ba;
-    if (!w.gate_h) {
-        NALO_HIP(c, hipHostMalloc((void**)&w.gate_h, sizeof(GateBlock), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(w.gate_h, 0, sizeof(GateBlock));
-        NALO_HIP(c, hipHostGetDevicePointer((void**)&w.gate_d, w.gate_h, 0));
+    if (!w.gate_h.p) {
+        NALO_HIP(c, w.gate_h.reserve(1, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(w.gate_h.p, 0, sizeof(GateBlock));
     }
-    if (w.pre_pos + 1 - 4 > w.pre_synced || !w.pre_map_dev[0]) return NALO_OK;    // the ring slot of the next records may still have readers: this iteration launches the ordinary way
+    GateBlock* const gh = w.gate_h.p; GateBlock* const gd = w.gate_h.dev;
+    if (w.pre_pos + 1 - 4 > w.pre_synced || !w.pre_map[0].dev) return NALO_OK;    // the ring slot of the next records may still have readers: this iteration launches the ordinary way
     // a cancelled pass (prelaunch_cancel) leaves kGateCancel in both words and nothing waiting on them (it drained the stream): a kernel enqueued now must find
     // them merely closed
-    if (w.gate_h->x_seq == kGateCancel) __atomic_store_n(&w.gate_h->x_seq, 0u, __ATOMIC_RELEASE);
-    if (w.gate_h->p_seq == kGateCancel) __atomic_store_n(&w.gate_h->p_seq, 0u, __ATOMIC_RELEASE);
+    if (gh->x_seq == kGateCancel) __atomic_store_n(&gh->x_seq, 0u, __ATOMIC_RELEASE);
+    if (gh->p_seq == kGateCancel) __atomic_store_n(&gh->p_seq, 0u, __ATOMIC_RELEASE);
     if (++w.gate_x_seq == kGateCancel) w.gate_x_seq = 1;
     if (++w.gate_p_seq == kGateCancel) w.gate_p_seq = 1;
     {
         ProfScope ps(c, "ba_resub");
         NALO_HIP(c, w.step_partial.reserve((size_t)(w.Ppad / 256 + 1) * 4));
-        const GateArg g{&w.gate_d->x_seq, &w.gate_d->err, w.gate_d->x, w.gate_x_seq};
+        const GateArg g{&gd->x_seq, &gd->err, gd->x, w.gate_x_seq};
         ba_launch_resub_step_gated(c->stream, w.dev, 1.f, w.step_partial.p, g);
     }
     w.resub_pre = true;
     {
         BADev D = w.dev;                                       // the records this pass will read: the ring slot set_precalc takes next
         const size_t nfl = (size_t)w.W * w.W * kPreStride;
-        D.pre = w.pre_map_dev[(w.pre_pos + 1) & 3]; D.calib = D.pre + nfl;
-        D.gate_p = &w.gate_d->p_seq; D.gate_err = &w.gate_d->err; D.gate_p_want = w.gate_p_seq;
+        D.pre = w.pre_map[(w.pre_pos + 1) & 3].dev; D.calib = D.pre + nfl;
+        D.gate_p = &gd->p_seq; D.gate_err = &gd->err; D.gate_p_want = w.gate_p_seq;
         ProfScope ps(c, "ba_linearize", true);
         ba_launch_linearize(c->stream, D, 0, 0, ps.a, ps.b);
     }
@@ -569,8 +515,8 @@ static int prelaunch_iteration(nalo_ctx* c) {
 // error paths: no kernel may be left spinning on a gate nobody will open
 static void prelaunch_cancel(nalo_ctx* c) {
     BAWindow& w = *c->ba;
-    if (!(w.resub_pre || w.lin_pre) || !w.gate_h) return;
-    __atomic_store_n(&w.gate_h->x_seq, kGateCancel, __ATOMIC_RELEASE); __atomic_store_n(&w.gate_h->p_seq, kGateCancel, __ATOMIC_RELEASE);
+    if (!(w.resub_pre || w.lin_pre) || !w.gate_h.p) return;
+    __atomic_store_n(&w.gate_h.p->x_seq, kGateCancel, __ATOMIC_RELEASE); __atomic_store_n(&w.gate_h.p->p_seq, kGateCancel, __ATOMIC_RELEASE);
     (void)hipStreamSynchronize(c->stream);
     w.resub_pre = w.lin_pre = false; w.want_prelaunch = false;
     w.have_lin = false; w.have_sc = false;
@@ -581,13 +527,12 @@ static void prelaunch_cancel(nalo_ctx* c) {
 static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to_host = false, bool misc_only = false) {
     BAWindow& w = *c->ba;
     if (w.ad_pending && !misc_only) { int ra = upload_adjoints(c); if (ra) return ra; }   // the stitch (and a large window's back-substitution behind it) reads the device copy of the adjoints
-    const int n1 = w.n1, NPL = w.NPL, W = w.W;
-    const size_t blk = (size_t)n1 * n1;
+    const int NPL = w.NPL, W = w.W;
+    const StitchLayout& L = w.lay;
     bool did = false;
-    const int npub = (int)(2 * blk + 2 * W * W + 5);                 // [H~_A | H~_sc | misc (2 W^2) | step sums (3) | TH sum, rank count]
+    const int ntail = (int)(L.npub - L.misc);                        // what a misc-only fetch and the stitch kernel publish behind the systems
     const double seq = (double)(w.pub_seq + 1);
-    double* dmap = nullptr;
-    NALO_HIP(c, hipHostGetDevicePointer((void**)&dmap, w.stitched_host, 0));
+    double* const dmap = w.stitched_host.dev;
     const bool top = want_top && !w.stitched_top, sc = want_sc && !w.stitched_sc;
     const bool sc_was_summed = w.stitched_sc;                        // a hooked window: its block already holds the sum over the ranks
     // this stitch's all-reduce takes level C's histogram of the newest frame's threshold along - when the summed range reaches the tail it sits behind
@@ -602,21 +547,21 @@ static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to
         const bool pub_in_reduce = misc_only && !w.hook && (top || sc) && (small_th || !w.th_pending);
         if ((top || sc) && (th_to_host || w.hook) && !fuse_lo && !pub_in_reduce) {      // the threshold rides in the tail {TH, 1.0}: compute it before the publish
             if (!small_th) { int rc = flush_th(c); if (rc) return rc; }
-            if (!small_th) ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + 2 * blk + 2 * W * W + 3);
+            if (!small_th) ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + L.th);
         }
         ProfScope ps(c, "ba_reduce");                                 // reduce + stitch only: the threshold search above is its own chain (and holds collectives)
         if (top || sc) {
             // misc {count, energy} per bin lands in the tail of the stitched buffer; without a cross-rank hook step B publishes
             // rows + tail + sequence number straight into host-mapped memory
-            ba_launch_reduce(c->stream, w.dev, w.host_blk.p, NPL, w.acc13.p, w.stitched.p + 2 * blk, w.G.p, top, sc,
-                             w.step_sums_deferred ? w.step_partial.p : nullptr, (w.Ppad + 255) / 256, w.stitched.p + 2 * blk + 2 * W * W, small_th,
-                             pub_in_reduce ? dmap + 2 * blk : nullptr, seq, w.st_ticket.p + 2);
+            ba_launch_reduce(c->stream, w.dev, w.host_blk.p, NPL, w.acc13.p, w.stitched.p + L.misc, w.G.p, top, sc,
+                             w.step_sums_deferred ? w.step_partial.p : nullptr, (w.Ppad + 255) / 256, w.stitched.p + L.step, small_th,
+                             pub_in_reduce ? dmap + L.misc : nullptr, seq, w.st_ticket.p + 2);
             if (small_th) w.th_pending = false;
             w.step_sums_deferred = false;
-            if (misc_only) { if (!w.hook && !pub_in_reduce) ba_launch_publish(c->stream, w.stitched.p + 2 * blk, dmap + 2 * blk, npub - (int)(2 * blk), seq, w.st_ticket.p + 1); }
+            if (misc_only) { if (!w.hook && !pub_in_reduce) ba_launch_publish(c->stream, w.stitched.p + L.misc, dmap + L.misc, ntail, seq, w.st_ticket.p + 1); }
             else {
-                if (small_th && th_to_host) ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + 2 * blk + 2 * W * W + 3);   // the stitch publishes the tail: {TH, 1.0} must be in it
-                if (ba_launch_stitch(c->stream, w.sd, top, sc, w.hook ? nullptr : dmap, npub - (int)(2 * blk), seq)) return fail(c, NALO_ERR_HIP, "ba_stitch_kernel: LDS size rejected");
+                if (small_th && th_to_host) ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + L.th);   // the stitch publishes the tail: {TH, 1.0} must be in it
+                if (ba_launch_stitch(c->stream, w.sd, top, sc, w.hook ? nullptr : dmap, ntail, seq)) return fail(c, NALO_ERR_HIP, "ba_stitch_kernel: LDS size rejected");
                 if (top) w.stitched_top = true;
                 if (sc) w.stitched_sc = true;
             }
@@ -629,17 +574,17 @@ static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to
         if (w.hook) {
             // sharded window: tail = {step sums (3), frameEnergyTH of the newest frame, 1.0}. Every rank already holds the SAME threshold (the order
             // statistic over all ranks' residuals, linearize_async), so sum / count below re-installs that value; the tail keeps its layout.
-            const size_t off = misc_only ? 2 * blk : 0;               // misc_only: only the tail is summed and published
+            const size_t off = misc_only ? L.misc : 0;              // misc_only: only the tail is summed and published
             // What is summed over the ranks is what THIS call produced, once: the freshly stitched block(s) and - with the top system, whose reduce writes it - the
             // tail {per-bin count / energy, step sums, threshold pair}. A second fetch of the same linearisation (nalo_ba_linearize, then nalo_ba_accumulate_sc or
             // nalo_ba_solve_system: the step-by-step mapping of ef->solveSystemF) stitches the Schur complement alone and sums ITS block alone:
             // H_A, b_A and the tail already hold the window's totals (rounds 2-3 summed them again: world x H_A).
-            const size_t tail_end = fuse_lo ? w.lo_off + kThDblC : (size_t)npub;
+            const size_t tail_end = fuse_lo ? L.lo + kThDblC : L.npub;
             size_t ra[2], rb[2]; int nr = 0;
-            if (misc_only) { ra[nr] = 2 * blk; rb[nr++] = tail_end; }
-            else if (top && (sc || !sc_was_summed)) { ra[nr] = 0; rb[nr++] = tail_end; }     // the SC block in between is fresh, or dead (re-stitched before anyone reads it)
-            else if (top) { ra[nr] = 0; rb[nr++] = blk; ra[nr] = 2 * blk; rb[nr++] = tail_end; }
-            else { ra[nr] = blk; rb[nr++] = 2 * blk; }
+            if (misc_only) { ra[nr] = L.misc; rb[nr++] = tail_end; }
+            else if (top && (sc || !sc_was_summed)) { ra[nr] = L.top; rb[nr++] = tail_end; }     // the SC block in between is fresh, or dead (re-stitched before anyone reads it)
+            else if (top) { ra[nr] = L.top; rb[nr++] = L.sc; ra[nr] = L.misc; rb[nr++] = tail_end; }
+            else { ra[nr] = L.sc; rb[nr++] = L.misc; }
             if (fuse_lo) {
                 // [systems | tail | level C]: one sum over the ranks, then the search on the summed histogram gives every rank the same threshold
                 if (w.th_side_inflight) { NALO_HIP(c, hipStreamWaitEvent(c->stream, w.ev_th, 0)); w.th_side_inflight = false; }
@@ -650,20 +595,20 @@ static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to
             if (fuse_lo) {
                 if (th_to_host) {                                    // the caller reads the threshold from the published tail: search first
                     ba_launch_energy_th_step(c->stream, w.dev, 3);
-                    ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + 2 * blk + 2 * W * W + 3);    // what tail_th() reads: {TH, 1.0}
+                    ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + L.th);    // what tail_th() reads: {TH, 1.0}
                 } else th_after_publish = true;                      // optimize(): the host only waits for the systems; the search runs under its solve
-            } else if (top || misc_only) ba_launch_th_install(c->stream, w.stitched.p + 2 * blk + 2 * W * W + 3, w.frameTH.p + (W - 1));   // the tail's {sum of TH, ranks}: the common threshold
-            ba_launch_publish(c->stream, w.stitched.p + off, dmap + off, npub - (int)off, seq, w.st_ticket.p + 1);
+            } else if (top || misc_only) ba_launch_th_install(c->stream, w.stitched.p + L.th, w.frameTH.p + (W - 1));   // the tail's {sum of TH, ranks}: the common threshold
+            ba_launch_publish(c->stream, w.stitched.p + off, dmap + off, (int)(L.npub - off), seq, w.st_ticket.p + 1);
             if (th_after_publish) ba_launch_energy_th_step(c->stream, w.dev, 3);
             NALO_HIP(c, hipGetLastError());
         }
         { int rc = flush_th(c); if (rc) return rc; }                  // behind the publish: overlaps the host's solve
         if (w.want_prelaunch) { w.want_prelaunch = false; int rc = prelaunch_iteration(c); if (rc) return rc; }
-        if (!poll_flag(c, &w.stitched_host[npub], seq)) return NALO_ERR_HIP;
-        if (w.gate_h && w.gate_h->err) return fail(c, NALO_ERR_HIP, "a pre-enqueued kernel gave up waiting for its inputs (gate timeout)");
+        if (!poll_flag(c, &w.stitched_host.p[L.flag], seq)) return NALO_ERR_HIP;
+        if (w.gate_h.p && w.gate_h.p->err) return fail(c, NALO_ERR_HIP, "a pre-enqueued kernel gave up waiting for its inputs (gate timeout)");
         w.pre_synced = w.pre_pos;                               // everything launched on the main stream so far has run (the side stream reads no precalc record)
         if (w.step_pending) {                                   // finish doStepFromBackup's break test with the sums of the last step
-            const double* s3 = w.stitched_host + 2 * blk + 2 * W * W;
+            const double* s3 = w.stitched_host.p + L.step;
             const float numID = (float)s3[2];
             const float sumNID = numID > 0 ? (float)(s3[1] / numID) : 0.f;
             const float th = kThOptIterations;
@@ -683,7 +628,7 @@ static int stitch_and_fetch_for_break(nalo_ctx* c) {
 }
 // frameEnergyTH of the newest frame as published in the tail {sum over ranks, rank count} (stitch_and_fetch with th_to_host)
 static float tail_th(const BAWindow& w) {
-    const double* tl = w.stitched_host + 2 * (size_t)w.n1 * w.n1 + 2 * w.W * w.W + 3;
+    const double* tl = w.stitched_host.p + w.lay.th;
     return (float)(tl[0] / tl[1]);
 }
 // a threshold search that lost a workgroup at its arrival counter reports NaN from then on (ba_th_find_kernel, sticky): fail instead of installing it
@@ -696,7 +641,7 @@ static void unpack_system(const BAWindow& w, const double* Ht, double* H, double
     for (int r = 0; r < n; ++r) { for (int cc = 0; cc < n; ++cc) H[(size_t)r * n + cc] = Ht[(size_t)r * n1 + cc]; b[r] = Ht[(size_t)r * n1 + n]; }
 }
 static void misc_totals(const BAWindow& w, double* energy, int* nres) {
-    const double* m = w.stitched_host + 2 * (size_t)w.n1 * w.n1;
+    const double* m = w.stitched_host.p + w.lay.misc;
     double e = 0, cnt = 0;
     for (int i = 0; i < w.W * w.W; ++i) { cnt += m[2 * i]; e += m[2 * i + 1]; }
     if (energy) *energy = e;
@@ -790,7 +735,7 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
     // w*a_k*a_j), so the upper triangle the factorisation reads is filled from the lower one: entry (r, c >= r) is computed from the sources' (c, r).
     // Scratch lives in the window: no allocation per iteration.
     std::vector<double>& x = w.lastX; x.resize(n);
-    const double* HAp = w.stitched_host; const double* HSp = w.stitched_host + (size_t)n1 * n1;
+    const double* HAp = w.stitched_host.p + w.lay.top; const double* HSp = w.stitched_host.p + w.lay.sc;
     misc_totals(w, nullptr, &w.resInA);
     const double fsc = 1.0 / (1 + lambda);
     { HostTimer hl(c, "ba.solve.math.assemble");
@@ -824,8 +769,8 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
     if (x_out) std::memcpy(x_out, x.data(), n * 8);
     // resubstituteF_MT (:263-289)
     for (int i = 0; i < 4; ++i) w.c_step[i] = -x[i];
-    float* xAd = w.up_host + (size_t)W * W * kPreStride + 16 + 64;
-    float* xc = w.up_host + (size_t)W * W * kPreStride + 16;
+    float* xAd = w.up_host.p + (size_t)W * W * kPreStride + 16 + 64;
+    float* xc = w.up_host.p + (size_t)W * W * kPreStride + 16;
     for (int i = 0; i < n; ++i) xF[i] = (float)x[i];
     for (int i = 0; i < 4; ++i) xc[i] = xF[i];
     for (int h = 0; h < W; ++h) {
@@ -843,9 +788,9 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
     }
     if (w.resub_pre) {                                          // the kernel is already in the stream, spinning on its gate: hand it {xc, xAd} and open
         w.resub_pre = false;
-        std::memcpy(w.gate_h->x, xc, 16); std::memcpy(w.gate_h->x + 4, xAd, (size_t)W * W * 8 * 4);
+        std::memcpy(w.gate_h.p->x, xc, 16); std::memcpy(w.gate_h.p->x + 4, xAd, (size_t)W * W * 8 * 4);
         __atomic_thread_fence(__ATOMIC_RELEASE);
-        __atomic_store_n(&w.gate_h->x_seq, w.gate_x_seq, __ATOMIC_RELEASE);
+        __atomic_store_n(&w.gate_h.p->x_seq, w.gate_x_seq, __ATOMIC_RELEASE);
         w.step_fused = true;
         return NALO_OK;
     }
@@ -885,7 +830,7 @@ static int do_step(nalo_ctx* c, float fC, float fT, float fR, float fA, float fD
         sumR += fh.step[3] * fh.step[3] + fh.step[4] * fh.step[4] + fh.step[5] * fh.step[5];
     }
     NALO_HIP(c, w.step_partial.reserve((size_t)(w.Ppad / 256 + 1) * 4));
-    double* out3 = w.stitched.p + 2 * (size_t)w.n1 * w.n1 + 2 * w.W * w.W;      // scratch tail of the stitched buffer
+    double* out3 = w.stitched.p + w.lay.step;                               // the step sums' place in the stitched block
     if (w.step_fused) {                                                        // points already stepped by solve_system (fD = 1)
         w.step_fused = false;
         if (canbreak) ba_launch_step_sums(c->stream, w.dev, w.step_partial.p, out3);     // the caller wants the break test now (round 4: it read the sums of the step before)
@@ -975,7 +920,7 @@ int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const
         frame_set_state_zero(f, z6);
         frame_set_state(f, s.state);
         frame_take_data(c->set, f);
-        w.dev.img[i] = c->slots[s.slot].dI[0];
+        w.dev.img[i] = c->slots[s.slot].dI[0].p;
     }
     w.dev.W = W; w.dev.w = c->w; w.dev.h = c->h;
     w.dev.fix_a = c->set.affineOptModeA < 0; w.dev.fix_b = c->set.affineOptModeB < 0; w.dev.no_th = 0;
@@ -996,18 +941,17 @@ int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const
         w.HM.swap(H2); w.bM.swap(b2);
     } else if (w.HM.size() != (size_t)w.n * w.n) { w.HM.assign((size_t)w.n * w.n, 0.0); w.bM.assign(w.n, 0.0); }
     w.lastX.assign(w.n, 0.0);
-    const size_t blk = (size_t)w.n1 * w.n1;
     NALO_HIP(c, w.acc13.reserve((size_t)W * W * 169));
     NALO_HIP(c, w.G.reserve((size_t)W * w.NPL * w.NPL));
-    w.lo_off = (2 * blk + 2 * W * W + 5 + 15) & ~(size_t)15;                       // behind the published doubles: level C's histogram of the threshold's radix select (a sharded window sums it with the systems) search
-    NALO_HIP(c, w.stitched.reserve(w.lo_off + kThDblC));
-    NALO_HIP(c, hipMemsetAsync(w.stitched.p, 0, (w.lo_off + kThDblC) * 8, c->stream));
-    w.dev.th_bufC = w.stitched.p + w.lo_off;
+    w.lay = StitchLayout(w.n1, W);
+    NALO_HIP(c, w.stitched.reserve(w.lay.dev_size));
+    NALO_HIP(c, hipMemsetAsync(w.stitched.p, 0, w.lay.dev_size * 8, c->stream));
+    w.dev.th_bufC = w.stitched.p + w.lay.lo;
     w.th_lo_pending = false; w.th_pending = false; w.th_side_inflight = false;
     w.sd.M_top = w.acc13.p; w.sd.M_sc = w.G.p; w.sd.H = w.stitched.p;
-    if (w.stitched_host) { (void)hipHostFree(w.stitched_host); w.stitched_host = nullptr; }
-    NALO_HIP(c, hipHostMalloc((void**)&w.stitched_host, (2 * blk + 2 * W * W + 16) * 8, hipHostMallocMapped));
-    w.stitched_host[2 * blk + 2 * W * W + 5] = -1.0; w.pub_seq = 0;
+    w.stitched_host.release();                                             // a fresh mirror for every window, whatever its size
+    NALO_HIP(c, w.stitched_host.reserve(w.lay.host_size, hipHostMallocMapped));
+    w.stitched_host.p[w.lay.flag] = -1.0; w.pub_seq = 0;
     int rc = upload_frame_th(c); if (rc) return rc;
     rc = set_adjoints(c); if (rc) return rc;
     rc = set_precalc(c); if (rc) return rc;
@@ -1175,7 +1119,7 @@ int nalo_ba_linearize(nalo_ctx* c, int fix, double* energy) {
 int nalo_ba_accumulate(nalo_ctx* c, int mode, double* H, double* b) {
     NALO_BA_READY("nalo_ba_accumulate")
     if (!H || !b) return fail(c, NALO_ERR_ARG, "nalo_ba_accumulate: H/b required");
-    if (mode == 0) { int rc = do_accumulate_top(c); if (rc) return rc; unpack_system(w, w.stitched_host, H, b); misc_totals(w, nullptr, &w.resInA); return NALO_OK; }
+    if (mode == 0) { int rc = do_accumulate_top(c); if (rc) return rc; unpack_system(w, w.stitched_host.p + w.lay.top, H, b); misc_totals(w, nullptr, &w.resInA); return NALO_OK; }
     if (mode == 1) { prior_system(w, H, b); w.resInL = 0; return NALO_OK; }
     return fail(c, NALO_ERR_UNSUPPORTED, "nalo_ba_accumulate: mode 2 runs inside nalo_ba_marginalize_points");
 }
@@ -1183,7 +1127,7 @@ int nalo_ba_accumulate_sc(nalo_ctx* c, int shiftPriorToZero, double* H, double* 
     NALO_BA_READY("nalo_ba_accumulate_sc")
     if (!H || !b) return fail(c, NALO_ERR_ARG, "nalo_ba_accumulate_sc: H/b required");
     int rc = do_accumulate_sc(c, shiftPriorToZero ? 1 : 0); if (rc) return rc;
-    unpack_system(w, w.stitched_host + (size_t)w.n1 * w.n1, H, b);
+    unpack_system(w, w.stitched_host.p + w.lay.sc, H, b);
     return NALO_OK;
 }
 int nalo_ba_solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out) {
@@ -1403,15 +1347,15 @@ int nalo_set_settings(nalo_ctx* c, const nalo_settings* in) {
 int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, double* Mb, double* Msc, double* Mbsc) {
     NALO_BA_READY("nalo_ba_marginalize_points")
     if (!flags) return fail(c, NALO_ERR_ARG, "nalo_ba_marginalize_points: flags required");
-    const int n = w.n, n1 = w.n1, W = w.W;
+    const int n = w.n, W = w.W;
     for (int p = 0; p < w.P; ++p) { const int d = w.p2d[p]; if (flags[p] && (w.flags_h[d] & PT_VALID)) w.flags_h[d] |= PT_MARG; }
     NALO_HIP(c, hipMemcpyAsync(w.pt_flags.p, w.flags_h.data(), w.Ppad, hipMemcpyHostToDevice, c->stream));
     int rc = linearize_async(c, 2, 0); if (rc) return rc;                                   // relinearise + fixLinearizationF + addPoint<2>
     rc = sc_async(c, 0, kIdepthFixPriorMargFac, 1); if (rc) return rc;                      // priorF *= margFac; addPoint(p, false)
     rc = stitch_and_fetch(c, true, true); if (rc) return rc;
     std::vector<double> m((size_t)n * n), mb(n), ms((size_t)n * n), mbs(n);
-    unpack_system(w, w.stitched_host, m.data(), mb.data());
-    unpack_system(w, w.stitched_host + (size_t)n1 * n1, ms.data(), mbs.data());
+    unpack_system(w, w.stitched_host.p + w.lay.top, m.data(), mb.data());
+    unpack_system(w, w.stitched_host.p + w.lay.sc, ms.data(), mbs.data());
     int nres = 0; misc_totals(w, nullptr, &nres); w.resInM += nres;
     for (size_t i = 0; i < (size_t)n * n; ++i) w.HM[i] += kMargWeightFac * (m[i] - ms[i]);  // EnergyFunctional.cpp:654-669
     for (int i = 0; i < n; ++i) w.bM[i] += kMargWeightFac * (mb[i] - mbs[i]);
@@ -1610,7 +1554,7 @@ int nalo_dist_make_map(nalo_ctx* c, int frame, const float* KRKi, const float* K
     const int W = w.W, w1 = c->wl[1], h1 = c->hl[1];
     const size_t npx = (size_t)w1 * h1, words = 12 * (size_t)W + npx + (npx + 3) / 4 + 8;
     int rc = imm_stage(c, words); if (rc) return rc;
-    float* hst = c->imm_host; float* d = c->imm_dev.p;
+    float* hst = c->imm_host.p; float* d = c->imm_dev.p;
     std::memcpy(hst, KRKi, 9 * (size_t)W * 4); std::memcpy(hst + 9 * W, Kt, 3 * (size_t)W * 4);
     NALO_HIP(c, hipMemcpyAsync(d, hst, 12 * (size_t)W * 4, hipMemcpyHostToDevice, c->stream));
     float* dout = d + 12 * W; uint8_t* seed = (uint8_t*)(dout + npx);
@@ -1637,7 +1581,7 @@ int nalo_imm_optimize(nalo_ctx* c, int n, const int* host, const float* u, const
     // words: [0,21n) u v color weights energyTH idmin idmax | [21n,22n) host | [22n, +14 W^2) Rt aff | outputs: result(n) idepth(n) res_in(n*W bytes)
     const size_t N = (size_t)n, PW = (size_t)W * W, out0 = 22 * N + 14 * PW, outw = 2 * N + (N * W + 3) / 4;
     int rc = imm_stage(c, out0 + outw); if (rc) return rc;
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4); std::memcpy(hst + 2 * N, color, 8 * N * 4); std::memcpy(hst + 10 * N, weights, 8 * N * 4);
     std::memcpy(hst + 18 * N, energyTH, N * 4); std::memcpy(hst + 19 * N, idepth_min, N * 4); std::memcpy(hst + 20 * N, idepth_max, N * 4); std::memcpy(hst + 21 * N, host, N * 4);
     float* Rt = hst + 22 * N; float* af = Rt + 12 * PW;
@@ -1679,7 +1623,7 @@ int nalo_imm_resident_optimize(nalo_ctx* c, int n, const int* sel, int minObs, i
     // words: [0, n) sel | [n, n + 14 W^2) Rt aff | outputs: result(n) idepth(n) res_in(n*W bytes)
     const size_t N = (size_t)n, PW = (size_t)W * W, out0 = N + 14 * PW, outw = 2 * N + (N * W + 3) / 4;
     int rc = imm_stage(c, out0 + outw); if (rc) return rc;
-    float* hst = c->imm_host;
+    float* hst = c->imm_host.p;
     if (sel) std::memcpy(hst, sel, N * 4);
     float* Rt = hst + N; float* af = Rt + 12 * PW;
     for (int h = 0; h < W; ++h) for (int t = 0; t < W; ++t) {               // FrameFramePrecalc::set (HessianBlocks.cpp:203-221) at the current states

@@ -229,8 +229,8 @@ struct Initializer {
     bool static_on_dev = false;                          // u, v, outlierTH and the tables are uploaded
     bool dev_valid = false, host_valid = true;           // which side holds the current Pnt state
     int jb_cur = 0;
-    float* pin = nullptr; size_t pin_half = 0;           // pinned staging: [0, pin_half) host -> device, [pin_half, 2 pin_half) device -> host
-    double* sums_host = nullptr; double* sums_dev = nullptr; double sums_seq = 0;    // an evaluation's 94 sums land in mapped host memory, sequence number last: polled, no copy, no sync
+    HostBuf<float> pin;                                  // pinned staging: the first half (pin.cap / 2 floats) host -> device, the second half device -> host
+    HostBuf<double> sums_host; double sums_seq = 0;      // an evaluation's 94 sums land in mapped host memory, sequence number last: polled, no copy, no sync
 };
 
 // word offsets inside a level's device block: the static members, then the members a level's LM loop changes ("dyn": one packed upload / download per level), the last
@@ -247,14 +247,6 @@ static LvlOff lvl_off(size_t n) {
 }
 
 void init_destroy(nalo_ctx* c) {
-    if (!c->init) return;
-    c->init->map_dev.release(); c->init->cnt_dev.release();
-    for (auto& b : c->init->lvl_dev) b.release();
-    for (auto& b : c->init->tab_dev) b.release();
-    c->init->sweep_scratch.release();
-    for (auto& b : c->init->jb_dev) b.release();
-    if (c->init->pin) (void)hipHostFree(c->init->pin);
-    if (c->init->sums_host) (void)hipHostFree(c->init->sums_host);
     delete c->init; c->init = nullptr;
 }
 
@@ -318,16 +310,10 @@ static int dev_prepare(nalo_ctx* c, Initializer& I) {                           
     for (int l = 0; l < I.levels; ++l) { const LvlOff o = lvl_off((size_t)I.L[l].n); NALO_HIP(c, I.lvl_dev[l].reserve(o.total)); maxn = std::max(maxn, (size_t)I.L[l].n); maxtot = std::max(maxtot, o.total); }
     for (auto& b : I.jb_dev) NALO_HIP(c, b.reserve(10 * maxn + 16));
     NALO_HIP(c, I.sweep_scratch.reserve(2 * (maxn + 8) + 32));
-    if (I.pin_half < maxtot) {
-        if (I.pin) (void)hipHostFree(I.pin);
-        I.pin = nullptr; I.pin_half = 0;
-        NALO_HIP(c, hipHostMalloc((void**)&I.pin, 2 * maxtot * sizeof(float)));
-        I.pin_half = maxtot;
-    }
-    if (!I.sums_host) {
-        NALO_HIP(c, hipHostMalloc((void**)&I.sums_host, 96 * sizeof(double), hipHostMallocMapped));
-        std::memset(I.sums_host, 0, 96 * sizeof(double));
-        NALO_HIP(c, hipHostGetDevicePointer((void**)&I.sums_dev, I.sums_host, 0));
+    NALO_HIP(c, I.pin.reserve(2 * maxtot));
+    if (!I.sums_host.p) {
+        NALO_HIP(c, I.sums_host.reserve(96, hipHostMallocMapped));
+        std::memset(I.sums_host.p, 0, 96 * sizeof(double));
     }
     if (I.static_on_dev) return NALO_OK;
     HostTimer ht(c, "init.tables");
@@ -336,8 +322,8 @@ static int dev_prepare(nalo_ctx* c, Initializer& I) {                           
         const InitLevel& P = I.L[l]; const size_t n = (size_t)P.n; const LvlOff o = lvl_off(n);
         I.nsteps[l] = 0;
         if (!n) continue;
-        std::memcpy(I.pin + o.u, P.u.data(), n * 4); std::memcpy(I.pin + o.v, P.v.data(), n * 4); std::memcpy(I.pin + o.outlierTH, P.outlierTH.data(), n * 4);
-        NALO_HIP(c, hipMemcpyAsync(I.lvl_dev[l].p, I.pin, 3 * n * 4, hipMemcpyHostToDevice, c->stream));
+        std::memcpy(I.pin.p + o.u, P.u.data(), n * 4); std::memcpy(I.pin.p + o.v, P.v.data(), n * 4); std::memcpy(I.pin.p + o.outlierTH, P.outlierTH.data(), n * 4);
+        NALO_HIP(c, hipMemcpyAsync(I.lvl_dev[l].p, I.pin.p, 3 * n * 4, hipMemcpyHostToDevice, c->stream));
         build_sweep(P, off, order);
         const size_t ns = off.size() - 1, n_below = l > 0 ? (size_t)I.L[l - 1].n : 0;
         I.nsteps[l] = (int)ns;
@@ -365,19 +351,19 @@ static int dev_prepare(nalo_ctx* c, Initializer& I) {                           
 static int level_upload(nalo_ctx* c, Initializer& I, int lvl) {
     const InitLevel& P = I.L[lvl]; const size_t n = (size_t)P.n; const LvlOff o = lvl_off(n);
     if (!n) return NALO_OK;
-    float* h = I.pin - o.dyn;
+    float* h = I.pin.p - o.dyn;
     std::memcpy(h + o.idepth, P.idepth.data(), n * 4); std::memcpy(h + o.iR, P.iR.data(), n * 4); std::memcpy(h + o.lastHessian, P.lastHessian.data(), n * 4);
     std::memcpy(h + o.lastHessian_new, P.lastHessian_new.data(), n * 4); std::memcpy(h + o.maxstep, P.maxstep.data(), n * 4); std::memcpy(h + o.energy, P.energy.data(), 2 * n * 4);
     std::memcpy(h + o.energy_new, P.energy_new.data(), 2 * n * 4); std::memcpy(h + o.isGood, P.isGood.data(), n); std::memcpy(h + o.idepth_new, P.idepth_new.data(), n * 4);
     std::memcpy(h + o.isGood_new, P.isGood_new.data(), n);
-    NALO_HIP(c, hipMemcpyAsync(I.lvl_dev[lvl].p + o.dyn, I.pin, (o.dyn_end - o.dyn) * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(I.lvl_dev[lvl].p + o.dyn, I.pin.p, (o.dyn_end - o.dyn) * 4, hipMemcpyHostToDevice, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));                                               // the staging block is reused by the next level
     return NALO_OK;
 }
 static int level_download(nalo_ctx* c, Initializer& I, int lvl) {
     InitLevel& P = I.L[lvl]; const size_t n = (size_t)P.n; const LvlOff o = lvl_off(n);
     if (!n) return NALO_OK;
-    float* hd = I.pin + I.pin_half;
+    float* hd = I.pin.p + I.pin.cap / 2;
     NALO_HIP(c, hipMemcpyAsync(hd, I.lvl_dev[lvl].p + o.dyn, (o.dyn_end - o.dyn) * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     const float* h = hd - o.dyn;
@@ -459,13 +445,13 @@ static int calc(nalo_ctx* c, Initializer& I, int lvl, int slot_new, const SE3& T
     if (n) {
         float* d = I.lvl_dev[lvl].p;
         const LvlPtr q = lvl_ptr(I, lvl);
-        P.colorRef = c->slots[I.slot_first].dI[lvl]; P.colorNew = c->slots[slot_new].dI[lvl];
+        P.colorRef = c->slots[I.slot_first].dI[lvl].p; P.colorNew = c->slots[slot_new].dI[lvl].p;
         P.u = d + o.u; P.v = d + o.v; P.outlierTH = d + o.outlierTH; P.idepth = q.idepth; P.idepth_new = q.idepth_new; P.iR = q.iR; P.energy = q.energy;
         P.isGood = q.isGood; P.isGood_new = q.isGood_new; P.energy_new = q.energy_new; P.maxstep = q.maxstep; P.lastHessian_new = q.lastHessian_new; P.Jb = I.jb_dev[1 - I.jb_cur].p;
         I.sums_seq += 1;
-        int rc = init_calc_launch(c, P, lvl, I.sums_dev, 1, I.sums_seq); if (rc) return rc;
-        if (!poll_flag(c, &I.sums_host[95], I.sums_seq)) return NALO_ERR_HIP;
-        std::memcpy(sums, I.sums_host, 94 * 8);
+        int rc = init_calc_launch(c, P, lvl, I.sums_host.dev, 1, I.sums_seq); if (rc) return rc;
+        if (!poll_flag(c, &I.sums_host.p[95], I.sums_seq)) return NALO_ERR_HIP;
+        std::memcpy(sums, I.sums_host.p, 94 * 8);
     }
     double E3[3];
     init_sums_to_system(sums, T, L.n, P, X, H, b, Hsc, bsc, E3);
@@ -526,7 +512,7 @@ static int make_pixel_status(nalo_ctx* c, Initializer& I, int slot, int lvl, flo
         int good = 0;
         if (ncx > 0 && ncy > 0) {
             const int cells = ncx * ncy;
-            grid_max_kernel<<<(cells + 255) / 256, 256, 0, c->stream>>>(c->slots[slot].dI[lvl], I.map_dev.p, w, h, pot, ncx, ncy, THFac, I.cnt_dev.p);
+            grid_max_kernel<<<(cells + 255) / 256, 256, 0, c->stream>>>(c->slots[slot].dI[lvl].p, I.map_dev.p, w, h, pot, ncx, ncy, THFac, I.cnt_dev.p);
             NALO_HIP(c, hipGetLastError());
         }
         NALO_HIP(c, hipMemcpyAsync(&good, I.cnt_dev.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));

@@ -289,7 +289,7 @@ extern "C" int nalo_dense_make_map(nalo_ctx* c, int slot, const float plane[4], 
     if (!c || !plane || !camToWorld || !n_out || !accept || cap < 0 || slot < 0 || slot >= (int)c->slots.size())
         return fail(c, NALO_ERR_ARG, "nalo_dense_make_map: bad argument");
     FrameSlot& s = c->slots[slot];
-    if (!s.valid || !s.mask) return fail(c, NALO_ERR_STATE, "nalo_dense_make_map: slot has no pyramid / mask (nalo_frame_upload with mask)");
+    if (!s.valid || !s.mask.p) return fail(c, NALO_ERR_STATE, "nalo_dense_make_map: slot has no pyramid / mask (nalo_frame_upload with mask)");
     NALO_HIP(c, hipSetDevice(c->device));
     *n_out = 0; *accept = 0;
     // ---- bbox scan (MapPoint.cpp:287-310), makeMap and the accept test: three launches back to back, the box never leaves the device in between
@@ -305,8 +305,8 @@ extern "C" int nalo_dense_make_map(nalo_ctx* c, int slot, const float plane[4], 
     NALO_HIP(c, c->scan_tmp.reserve(8));
     {   // dispatch-attached timestamps (no barrier packets around the launch: an event pair recorded on the stream adds several microseconds to a 5 us kernel)
         ProfScope ps(c, "dense_bbox", true);
-        if (ps.a) hipExtLaunchKernelGGL(dense_rows_kernel, dim3(std::max(1, c->h - 4)), dim3(256), 0, c->stream, ps.a, ps.b, 0, s.mask, c->w, c->h, mask_value, rows);
-        else dense_rows_kernel<<<std::max(1, c->h - 4), 256, 0, c->stream>>>(s.mask, c->w, c->h, mask_value, rows);
+        if (ps.a) hipExtLaunchKernelGGL(dense_rows_kernel, dim3(std::max(1, c->h - 4)), dim3(256), 0, c->stream, ps.a, ps.b, 0, s.mask.p, c->w, c->h, mask_value, rows);
+        else dense_rows_kernel<<<std::max(1, c->h - 4), 256, 0, c->stream>>>(s.mask.p, c->w, c->h, mask_value, rows);
     }
     int rect[4];
     float ext[6] = {FLT_MAX, FLT_MIN, FLT_MAX, FLT_MIN, FLT_MAX, FLT_MIN};
@@ -318,7 +318,7 @@ extern "C" int nalo_dense_make_map(nalo_ctx* c, int slot, const float plane[4], 
     uint8_t* dbgr = (uint8_t*)(dcol + capz);
     NALO_HIP(c, c->trk_partial.reserve(16));
     DenseParams P;
-    P.mask = s.mask; P.I0 = s.I[0]; P.bgr = s.bgr; P.w = c->w; P.h = c->h; P.rows = rows; P.rect = c->scan_tmp.p;
+    P.mask = s.mask.p; P.I0 = s.I[0].p; P.bgr = s.bgr.p; P.w = c->w; P.h = c->h; P.rows = rows; P.rect = c->scan_tmp.p;
     P.p0 = plane[0]; P.p1 = plane[1]; P.p2 = plane[2]; P.p3 = plane[3]; P.pcolor = mask_value;
     P.fxi = 1.0f / c->fx[0]; P.fyi = 1.0f / c->fy[0]; P.cx = c->cx[0]; P.cy = c->cy[0];            // DenseMapping::makeK level 0
     std::memcpy(P.c2w, camToWorld, sizeof(P.c2w));
@@ -362,7 +362,7 @@ extern "C" int nalo_dense_make_map(nalo_ctx* c, int slot, const float plane[4], 
         if (out_v) NALO_HIP(c, hipMemcpyAsync(out_v, dv, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out_idepth) NALO_HIP(c, hipMemcpyAsync(out_idepth, did, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out_color) NALO_HIP(c, hipMemcpyAsync(out_color, dcol, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (out_bgr && s.bgr) NALO_HIP(c, hipMemcpyAsync(out_bgr, dbgr, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
+        if (out_bgr && s.bgr.p) NALO_HIP(c, hipMemcpyAsync(out_bgr, dbgr, (size_t)n * 3, hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
     }
     NALO_HIP(c, hipGetLastError());

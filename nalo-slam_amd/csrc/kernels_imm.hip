@@ -473,13 +473,10 @@ int imm_put_launch(nalo_ctx* c, float* dst, const float* src, int n) {
 
 // ---------------------------------------------------------------------------------------------------------------- launchers
 int imm_stage(nalo_ctx* c, size_t words) {
-    if (c->imm_cap >= words) return NALO_OK;
-    if (c->imm_host) (void)hipHostFree(c->imm_host);
-    c->imm_host = nullptr; c->imm_cap = 0;
+    if (c->imm_host.cap >= words && c->imm_dev.cap >= words) return NALO_OK;
     const size_t cap = words + words / 2 + 1024;
-    NALO_HIP(c, hipHostMalloc((void**)&c->imm_host, cap * 4));
+    NALO_HIP(c, c->imm_host.reserve(cap));
     NALO_HIP(c, c->imm_dev.reserve(cap));
-    c->imm_cap = cap;
     return NALO_OK;
 }
 

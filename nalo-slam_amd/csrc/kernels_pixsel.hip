@@ -25,8 +25,7 @@ struct PixSel {
     DevBuf<uint8_t> rp, map, has, sel;
     DevBuf<int> draws, pre, chunk, list, cnt;   // cnt: [0] mismatch [1..3] n2 n3 n4 [4] list length [5] kept (sub-select) [6,7] fused n1 n2 [8..] mask histogram (257)
     DevBuf<float> ths;                           // [ths (nb + 100) | thsSmoothed (nb + 100)], zero tails (see pixsel_state)
-    int* host = nullptr;                         // pinned: [0..15] counters, [16..] list
-    size_t host_cap = 0;
+    HostBuf<int> host;                           // pinned: [0..15] counters, [16..] list
     int hist_slot = -1;
     bool have_rp = false, have_draws = false, have_map = false;
     int list_n = 0;
@@ -246,11 +245,7 @@ __global__ __launch_bounds__(256) void pixsel_fuse_kernel(const float* __restric
 }
 
 void pixsel_destroy(nalo_ctx* c) {
-    PixSel* p = c->pixsel;
-    if (!p) return;
-    p->rp.release(); p->map.release(); p->has.release(); p->sel.release(); p->draws.release(); p->pre.release(); p->chunk.release(); p->list.release(); p->cnt.release(); p->ths.release();
-    if (p->host) (void)hipHostFree(p->host);
-    delete p;
+    delete c->pixsel;
     c->pixsel = nullptr;
 }
 void pixsel_invalidate_hists(nalo_ctx* c, int slot) { if (c->pixsel && c->pixsel->hist_slot == slot) c->pixsel->hist_slot = -1; }
@@ -265,18 +260,13 @@ static int pixsel_state(nalo_ctx* c, PixSel** out) {
     // not multiples of 32 (KITTI 1224x368) reaches the next row or the uninitialised tail. Same indexing here; the tail is DEFINED as 0.
     const size_t nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
     if (p->ths.cap < 2 * nbp) { NALO_HIP(c, p->ths.reserve(2 * nbp)); NALO_HIP(c, hipMemsetAsync(p->ths.p, 0, 2 * nbp * sizeof(float), c->stream)); }
-    if (p->host_cap < n + 16) {
-        if (p->host) (void)hipHostFree(p->host);
-        p->host = nullptr; p->host_cap = 0;
-        NALO_HIP(c, hipHostMalloc((void**)&p->host, (n + 16) * sizeof(int)));
-        p->host_cap = n + 16;
-    }
+    NALO_HIP(c, p->host.reserve(n + 16));
     *out = p;
     return NALO_OK;
 }
 static int pixsel_hists(nalo_ctx* c, PixSel* p, int slot) {
     const size_t nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
-    int rc = pixsel_hists_launch(c, c->slots[slot].absg[0], p->ths.p, p->ths.p + nbp);
+    int rc = pixsel_hists_launch(c, c->slots[slot].absg[0].p, p->ths.p, p->ths.p + nbp);
     if (rc) return rc;
     p->hist_slot = slot;
     return NALO_OK;
@@ -286,7 +276,7 @@ static int pixsel_select_dev(nalo_ctx* c, PixSel* p, int slot, int pot, float th
     const FrameSlot& s = c->slots[slot];
     const size_t npx = (size_t)c->w * c->h, nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
     PixSelArgs A;
-    A.dI = s.dI[0]; A.ag0 = s.absg[0]; A.ag1 = s.absg[1]; A.ag2 = s.absg[2]; A.thsSmoothed = p->ths.p + nbp; A.rp = p->rp.p;
+    A.dI = s.dI[0].p; A.ag0 = s.absg[0].p; A.ag1 = s.absg[1].p; A.ag2 = s.absg[2].p; A.thsSmoothed = p->ths.p + nbp; A.rp = p->rp.p;
     A.w = c->w; A.h = c->h; A.pot = pot; A.nb4x = (c->w + 4 * pot - 1) / (4 * pot);
     A.nslots = A.nb4x * ((c->h + 4 * pot - 1) / (4 * pot)) * 16;
     A.thFactor = thFactor;
@@ -310,12 +300,12 @@ static int pixsel_select_dev(nalo_ctx* c, PixSel* p, int slot, int pot, float th
         pixsel_scan_bytes_kernel<<<1, 1024, 0, c->stream>>>(flags, A.nslots, p->pre.p, p->cnt.p);
         NALO_HIP(c, hipMemsetAsync(p->map.p, 0, npx, c->stream));
         cells(true, flags, other);
-        NALO_HIP(c, hipMemcpyAsync(p->host, p->cnt.p, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(p->host.p, p->cnt.p, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
-        if (!p->host[0]) break;
+        if (!p->host.p[0]) break;
         std::swap(flags, other);                                // a cell's flag was wrong: redo the scan with the flags the selection produced
     }
-    n[0] = p->host[1]; n[1] = p->host[2]; n[2] = p->host[3];
+    n[0] = p->host.p[1]; n[1] = p->host.p[2]; n[2] = p->host.p[3];
     p->have_map = true;
     return NALO_OK;
 }
@@ -327,22 +317,22 @@ static int pixsel_fetch(nalo_ctx* c, PixSel* p, int charTH, float* map_out, int*
     pixsel_count_kernel<<<nch, 256, 0, c->stream>>>(p->map.p, npx, p->chunk.p);
     pixsel_scan_ints_kernel<<<1, 1024, 0, c->stream>>>(p->chunk.p, nch, p->cnt.p + 4, p->cnt.p + 5);
     pixsel_compact_kernel<<<nch, 256, 0, c->stream>>>(p->map.p, npx, p->chunk.p, p->rp.p, charTH, p->list.p, p->cnt.p);
-    NALO_HIP(c, hipMemcpyAsync(p->host, p->cnt.p, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (expect > 0) NALO_HIP(c, hipMemcpyAsync(p->host + 16, p->list.p, (size_t)expect * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(p->host.p, p->cnt.p, 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (expect > 0) NALO_HIP(c, hipMemcpyAsync(p->host.p + 16, p->list.p, (size_t)expect * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
-    const int total = p->host[4];
-    if (kept) *kept = p->host[5];
+    const int total = p->host.p[4];
+    if (kept) *kept = p->host.p[5];
     if (total > 0 && total != expect) {                     // no expectation, or not the count the device found (never seen): the list at its real length
-        NALO_HIP(c, hipMemcpyAsync(p->host + 16, p->list.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(p->host.p + 16, p->list.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
     }
     // the list keeps only live entries (sub-selected ones are dropped here)
     int m = 0;
-    for (int i = 0; i < total; ++i) { const int e = p->host[16 + i]; if (e >> 28) p->host[16 + m++] = e; }
+    for (int i = 0; i < total; ++i) { const int e = p->host.p[16 + i]; if (e >> 28) p->host.p[16 + m++] = e; }
     p->list_n = m;
     if (map_out) {
         std::memset(map_out, 0, sizeof(float) * (size_t)npx);
-        for (int i = 0; i < m; ++i) { const int e = p->host[16 + i]; map_out[e & 0x0FFFFFFF] = (float)(e >> 28); }
+        for (int i = 0; i < m; ++i) { const int e = p->host.p[16 + i]; map_out[e & 0x0FFFFFFF] = (float)(e >> 28); }
     }
     return NALO_OK;
 }
@@ -352,7 +342,7 @@ static int pixsel_check(nalo_ctx* c, int slot, const char* who, bool need_draws)
     if (c->levels < 3) return fail(c, NALO_ERR_STATE, std::string(who) + ": needs 3 pyramid levels");
     if (!c->pixsel || !c->pixsel->have_rp) return fail(c, NALO_ERR_STATE, std::string(who) + ": nalo_pixsel_set_random has not been called");
     if (need_draws && !c->pixsel->have_draws) return fail(c, NALO_ERR_STATE, std::string(who) + ": no mask_draws were given to nalo_pixsel_set_random");
-    if (need_draws && !c->slots[slot].mask) return fail(c, NALO_ERR_STATE, std::string(who) + ": the frame was uploaded without a mask");
+    if (need_draws && !c->slots[slot].mask.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the frame was uploaded without a mask");
     return NALO_OK;
 }
 
@@ -390,10 +380,10 @@ int nalo_pixsel_make_hists(nalo_ctx* c, int slot, float* ths, float* thsSmoothed
     if (nb == 0) return NALO_OK;
     rc = pixsel_hists(c, p, slot); if (rc) return rc;
     if (ths || thsSmoothed) {
-        NALO_HIP(c, hipMemcpyAsync(p->host, p->ths.p, 2 * (nb + 100) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(p->host.p, p->ths.p, 2 * (nb + 100) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
-        if (ths) std::memcpy(ths, p->host, nb * sizeof(float));
-        if (thsSmoothed) std::memcpy(thsSmoothed, reinterpret_cast<float*>(p->host) + nb + 100, nb * sizeof(float));
+        if (ths) std::memcpy(ths, p->host.p, nb * sizeof(float));
+        if (thsSmoothed) std::memcpy(thsSmoothed, reinterpret_cast<float*>(p->host.p) + nb + 100, nb * sizeof(float));
     }
     return NALO_OK;
 }
@@ -451,10 +441,10 @@ int nalo_pixsel_make_maps_lidar(nalo_ctx* c, int slot, float thFactor, int curre
     rc = pixsel_select_dev(c, p, slot, currentPotential, thFactor, n); if (rc) return rc;
     const int npx = c->w * c->h;
     NALO_HIP(c, hipMemsetAsync(p->cnt.p + 6, 0, (2 + 257) * sizeof(int), c->stream));
-    pixsel_mask_hist_kernel<<<std::min((npx + 255) / 256, 512), 256, 0, c->stream>>>(c->slots[slot].mask, npx, p->cnt.p + 8);
-    pixsel_fuse_kernel<<<(npx + 255) / 256, 256, 0, c->stream>>>(c->slots[slot].mask, p->draws.p, npx, p->map.p, p->cnt.p);
+    pixsel_mask_hist_kernel<<<std::min((npx + 255) / 256, 512), 256, 0, c->stream>>>(c->slots[slot].mask.p, npx, p->cnt.p + 8);
+    pixsel_fuse_kernel<<<(npx + 255) / 256, 256, 0, c->stream>>>(c->slots[slot].mask.p, p->draws.p, npx, p->map.p, p->cnt.p);
     rc = pixsel_fetch(c, p, -1, map_out, nullptr); if (rc) return rc;
-    *numHave = p->host[6] + p->host[7];                         // m[0] + m[1] + m[2] with m[2] = 0 (:313)
+    *numHave = p->host.p[6] + p->host.p[7];                         // m[0] + m[1] + m[2] with m[2] = 0 (:313)
     return NALO_OK;
 }
 
@@ -463,7 +453,7 @@ int nalo_pixsel_get_selected(nalo_ctx* c, int cap, int* idx, uint8_t* status, in
     if (!c->pixsel || !c->pixsel->have_map) return fail(c, NALO_ERR_STATE, "nalo_pixsel_get_selected: no selection has been made");
     const PixSel* p = c->pixsel;
     *n = p->list_n;
-    for (int i = 0; i < std::min(cap, p->list_n); ++i) { const int e = p->host[16 + i]; idx[i] = e & 0x0FFFFFFF; status[i] = (uint8_t)(e >> 28); }
+    for (int i = 0; i < std::min(cap, p->list_n); ++i) { const int e = p->host.p[16 + i]; idx[i] = e & 0x0FFFFFFF; status[i] = (uint8_t)(e >> 28); }
     return NALO_OK;
 }
 

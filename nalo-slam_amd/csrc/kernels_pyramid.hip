@@ -538,8 +538,8 @@ __global__ __launch_bounds__(256) void tile_level0_kernel(const float4* __restri
 int frame_tile_level0(nalo_ctx* c, FrameSlot& s) {
     const int wt = (c->w + 4) / 5, ht = (c->h + 1) / 2;
     const size_t n = (size_t)c->w * c->h;
-    if (!s.dI0t) NALO_HIP(c, hipMalloc((void**)&s.dI0t, (size_t)wt * ht * 128 + 16));         // + 16: the 12-byte load of a tile's last texel may be issued as 16
-    tile_level0_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(s.dI[0], s.dI0t, c->w, c->h, wt);
+    NALO_HIP(c, s.dI0t.reserve((size_t)wt * ht * 32 + 4));         // + 4 floats: the 12-byte load of a tile's last texel may be issued as 16
+    tile_level0_kernel<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(s.dI[0].p, s.dI0t.p, c->w, c->h, wt);
     NALO_HIP(c, hipGetLastError());
     s.tiled_valid = true;
     return NALO_OK;
@@ -571,7 +571,7 @@ int pyramid_build(nalo_ctx* c, FrameSlot& s, const float* gammaB_dev) {
     P.L = c->levels;
     int nb = 0;
     for (int l = 0; l < c->levels; ++l) {
-        P.I[l] = s.I[l]; P.dI[l] = s.dI[l]; P.absg[l] = s.absg[l]; P.wl[l] = c->wl[l]; P.hl[l] = c->hl[l];
+        P.I[l] = s.I[l].p; P.dI[l] = s.dI[l].p; P.absg[l] = s.absg[l].p; P.wl[l] = c->wl[l]; P.hl[l] = c->hl[l];
         P.blk0[l] = nb; nb += (c->wl[l] * c->hl[l] + 255) / 256;
     }
     P.blk0[c->levels] = nb;
@@ -605,7 +605,7 @@ int pyramid_build(nalo_ctx* c, FrameSlot& s, const float* gammaB_dev) {
     if (ps.a) (void)hipEventRecord(ps.a, c->stream);
     for (int l = 1; l < c->levels; ++l) {                     // a pyramid with an odd parent level (explicit `levels`): level by level
         const int n = c->wl[l] * c->hl[l];
-        pyr_down_kernel<<<std::min((n + 255) / 256, 2048), 256, 0, c->stream>>>(s.I[l - 1], s.I[l], c->wl[l], c->hl[l], c->wl[l - 1]);
+        pyr_down_kernel<<<std::min((n + 255) / 256, 2048), 256, 0, c->stream>>>(s.I[l - 1].p, s.I[l].p, c->wl[l], c->hl[l], c->wl[l - 1]);
     }
     pyr_grad_all_kernel<<<nb, 256, 0, c->stream>>>(P, gammaB_dev);
     if (ps.b) (void)hipEventRecord(ps.b, c->stream);

@@ -125,8 +125,7 @@ int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], cons
     nblocks = nblocks < 1 ? 1 : (nblocks > 512 ? 512 : nblocks);
     NALO_HIP(c, c->trk_partial.reserve((size_t)2048 * 64));
     if (!c->trk_ticket.p) { NALO_HIP(c, c->trk_ticket.reserve(4)); NALO_HIP(c, hipMemsetAsync(c->trk_ticket.p, 0, 16, c->stream)); }
-    double* dout = nullptr;
-    NALO_HIP(c, hipHostGetDevicePointer((void**)&dout, c->trk_out_host, 0));
+    double* const dout = c->trk_out_host.dev;
     const double seq = (double)(++c->trk_seq);
     if (sharded) NALO_HIP(c, c->trk_shard_sums.reserve(64));
     {
@@ -143,8 +142,8 @@ int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], cons
         trk_publish_kernel<<<1, 64, 0, c->stream>>>(c->trk_shard_sums.p, dout, seq);
     }
     NALO_HIP(c, hipGetLastError());
-    if (!poll_flag(c, &c->trk_out_host[63], seq)) return NALO_ERR_HIP;
-    std::memcpy(out64, c->trk_out_host, sizeof(double) * kTrkVals);
+    if (!poll_flag(c, &c->trk_out_host.p[63], seq)) return NALO_ERR_HIP;
+    std::memcpy(out64, c->trk_out_host.p, sizeof(double) * kTrkVals);
     return NALO_OK;
 }
 
@@ -481,7 +480,7 @@ int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const 
         const size_t npx = (size_t)c->wl[l] * c->hl[l];
         NALO_HIP(c, c->trk_idepth[l].reserve(npx)); NALO_HIP(c, c->trk_wsum[l].reserve(npx)); NALO_HIP(c, c->trk_wbak[l].reserve(npx));
         NALO_HIP(c, c->pc_u[l].reserve(npx)); NALO_HIP(c, c->pc_v[l].reserve(npx)); NALO_HIP(c, c->pc_id[l].reserve(npx)); NALO_HIP(c, c->pc_col[l].reserve(npx));
-        P.id[l] = c->trk_idepth[l].p; P.ws[l] = c->trk_wsum[l].p; P.wb[l] = c->trk_wbak[l].p; P.dI[l] = c->slots[c->slot_ref].dI[l];
+        P.id[l] = c->trk_idepth[l].p; P.ws[l] = c->trk_wsum[l].p; P.wb[l] = c->trk_wbak[l].p; P.dI[l] = c->slots[c->slot_ref].dI[l].p;
         P.pu[l] = c->pc_u[l].p; P.pv[l] = c->pc_v[l].p; P.pid[l] = c->pc_id[l].p; P.pcol[l] = c->pc_col[l].p;
         P.wl[l] = c->wl[l]; P.hl[l] = c->hl[l];
         dil0[l] = dil_blocks; dil_blocks += (int)((npx + 255) / 256);
@@ -503,16 +502,15 @@ int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const 
     for (int l = 0; l <= L; ++l) P.blk0[l] = dil0[l];
     trk_dilate_all_kernel<<<dil_blocks, 256, 0, c->stream>>>(P);
     for (int l = 0; l <= L; ++l) P.blk0[l] = cmp0[l];
-    double* dout = nullptr;
-    NALO_HIP(c, hipHostGetDevicePointer((void**)&dout, c->trk_out_host, 0));
+    double* const dout = c->trk_out_host.dev;
     const double seq = (double)(++c->trk_seq);
     if (cmp_blocks > 0) trk_compact_all_kernel<0><<<cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
     trk_scan_all_kernel<<<1, 1024, 0, c->stream>>>(P, c->scan_tmp.p, dout + 96, seq);
     if (cmp_blocks > 0) trk_compact_all_kernel<1><<<cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
     NALO_HIP(c, hipGetLastError());
     for (int l = 0; l < L; ++l) std::swap(c->trk_wsum[l], c->trk_wbak[l]);      // the dilated (then normalised) weights are the level's weightSums now
-    if (!poll_flag(c, &c->trk_out_host[96 + NALO_MAX_LEVELS], seq)) return NALO_ERR_HIP;   // pc_n for the host; the point clouds follow in stream order
-    for (int l = 0; l < L; ++l) c->pc_n[l] = (int)c->trk_out_host[96 + l];
+    if (!poll_flag(c, &c->trk_out_host.p[96 + NALO_MAX_LEVELS], seq)) return NALO_ERR_HIP;   // pc_n for the host; the point clouds follow in stream order
+    for (int l = 0; l < L; ++l) c->pc_n[l] = (int)c->trk_out_host.p[96 + l];
     return NALO_OK;
 }
 

@@ -499,8 +499,7 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
     P.expRef = exposures[0]; P.expNew = exposures[1]; P.coarsest = coarsest; P.stop_lvl = stop_lvl; P.have_repeated_in = 0;
     P.has_minres = 0;
     if (minRes) { P.has_minres = 1; for (int i = 0; i < 5; ++i) { P.minRes[i] = minRes[i]; } }
-    double* dout = nullptr;
-    NALO_HIP(c, hipHostGetDevicePointer((void**)&dout, c->trk_out_host, 0));
+    double* const dout = c->trk_out_host.dev;
     P.out = dout + 64;                                   // second half of the mapped buffer (first half: per-eval results)
     P.seq = (double)(++c->trk_seq);
     int maxn = 1;
@@ -520,9 +519,9 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
         else trk_lm_kernel<<<NB, kLmThreads, 0, c->stream>>>(P);
     }
     NALO_HIP(c, hipGetLastError());
-    if (!poll_flag(c, &c->trk_out_host[64 + 31], P.seq)) return NALO_ERR_HIP;
-    std::memcpy(out24, c->trk_out_host + 64, sizeof(double) * 26);
-    for (int i = 0; i < 5; ++i) c->lm_evals_lvl[i] = (int)c->trk_out_host[64 + 26 + i];
+    if (!poll_flag(c, &c->trk_out_host.p[64 + 31], P.seq)) return NALO_ERR_HIP;
+    std::memcpy(out24, c->trk_out_host.p + 64, sizeof(double) * 26);
+    for (int i = 0; i < 5; ++i) c->lm_evals_lvl[i] = (int)c->trk_out_host.p[64 + 26 + i];
     static const bool test_timeout = std::getenv("NALO_LM_TEST_TIMEOUT") != nullptr;          // tests: exercise the caller's degraded path once per context
     c->trk_cfg[8] = out24[25] != 0.0;
     if (out24[22] < 0 || (test_timeout && c->lm_launches == 1)) return NALO_LM_LOST_BLOCK;

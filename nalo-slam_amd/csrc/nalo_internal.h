@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 #include <chrono>
 
@@ -16,10 +17,18 @@
 
 namespace nalo {
 
+// The owners below wrap the HIP allocation calls and nothing else: each frees what it holds in its destructor and is move-only, so a struct
+// that holds one releases it without a list anywhere. Kernel-argument structs take raw views (.p / .dev).
 template <typename T>
-struct DevBuf {                  // owning device buffer, grows on demand
+struct DevBuf {                  // device buffer, grows on demand (contents are not kept), freed with its holder
     T* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
         if (p) (void)hipFree(p);
@@ -31,16 +40,60 @@ struct DevBuf {                  // owning device buffer, grows on demand
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+template <typename T>
+struct HostBuf {                 // pinned host block with DevBuf's grow rule; cap is the allocation, in elements
+    T* p = nullptr;
+    T* dev = nullptr;            // the device alias of a hipHostMallocMapped block, fetched once per allocation
+    size_t cap = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    HostBuf(HostBuf&& o) noexcept : p(o.p), dev(o.dev), cap(o.cap) { o.p = o.dev = nullptr; o.cap = 0; }
+    HostBuf& operator=(HostBuf&& o) noexcept { std::swap(p, o.p); std::swap(dev, o.dev); std::swap(cap, o.cap); return *this; }
+    ~HostBuf() { release(); }
+    hipError_t reserve(size_t n, unsigned flags = 0) {
+        if (n <= cap) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T), flags);
+        if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer((void**)&dev, p, 0);
+        if (e == hipSuccess) cap = n; else release();
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree(p); p = dev = nullptr; cap = 0; }   // hipHostFree waits for copies in flight
+};
+
+struct Event {                   // one hipEvent_t, created on first use with the flags its site asks for; passes as the raw handle
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { std::swap(e, o.e); return *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create(unsigned flags = 0) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+struct Stream {                  // one non-blocking hipStream_t; passes as the raw handle. A nalo_ctx is never copied or moved, so neither is this
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
 struct FrameSlot {
-    float* I[NALO_MAX_LEVELS] = {};          // planar irradiance per level
-    float4* dI[NALO_MAX_LEVELS] = {};        // {I, dx, dy, 0} per level: one 16-B load per bilinear tap
-    float* absg[NALO_MAX_LEVELS] = {};       // absSquaredGrad
-    float* mask = nullptr;                   // level 0 (densemap only)
-    uint8_t* bgr = nullptr;
+    DevBuf<float> I[NALO_MAX_LEVELS];        // planar irradiance per level
+    DevBuf<float4> dI[NALO_MAX_LEVELS];      // {I, dx, dy, 0} per level: one 16-B load per bilinear tap
+    DevBuf<float> absg[NALO_MAX_LEVELS];     // absSquaredGrad
+    DevBuf<float> mask;                      // level 0 (densemap only)
+    DevBuf<uint8_t> bgr;
     bool valid = false;
-    hipEvent_t ev_up = nullptr;              // nalo_frame_upload_async: the slot's H2D copies (copy stream) have completed
-    uint8_t* raw = nullptr; size_t raw_cap = 0;   // nalo_frame_upload_raw_async: this slot's sensor frame as uploaded (several frames may be in flight)
-    float* dI0t = nullptr; bool tiled_valid = false;    // level 0 again as 12-byte texels in 5x2 tiles of 128 bytes (ba_linearize's gathers), made on demand (frame_tile_level0)
+    Event ev_up;                             // nalo_frame_upload_async: the slot's H2D copies (copy stream) have completed
+    DevBuf<uint8_t> raw;                     // nalo_frame_upload_raw_async: this slot's sensor frame as uploaded (several frames may be in flight)
+    DevBuf<float> dI0t; bool tiled_valid = false;    // level 0 again as 12-byte texels in 5x2 tiles of 128 bytes (ba_linearize's gathers), made on demand (frame_tile_level0)
 };
 
 struct ProfEntry { double ms = 0; int n = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; std::vector<float> samples; };   // samples: every bracketed launch, in launch order (nalo_profile_samples)
@@ -58,9 +111,11 @@ struct nalo_ctx {
     int wl[NALO_MAX_LEVELS], hl[NALO_MAX_LEVELS];
     float fx[NALO_MAX_LEVELS], fy[NALO_MAX_LEVELS], cx[NALO_MAX_LEVELS], cy[NALO_MAX_LEVELS];   // tracker pyramid intrinsics
     float K0[4];
-    hipStream_t stream = nullptr, side = nullptr, copy = nullptr;   // copy: H2D frame uploads of nalo_frame_upload_async (overlap the kernels of `stream`)
-    hipEvent_t ev_main = nullptr;            // main-stream marker the copy stream waits on before it overwrites a slot that has been used
-    float* gamma_dev = nullptr;              // 256-entry gamma table of the asynchronous upload path
+    // Members are destroyed in reverse order of declaration: the streams stand before every buffer and event of the context, so they outlive all of them
+    // (nalo_destroy has drained them, and deleted ba / pixsel / init, before the context goes).
+    nalo::Stream stream, side, copy;         // copy: H2D frame uploads of nalo_frame_upload_async (overlap the kernels of `stream`), created on first use
+    nalo::Event ev_main;                     // main-stream marker the copy stream waits on before it overwrites a slot that has been used
+    nalo::DevBuf<float> gamma_dev;           // 256-entry gamma table of the asynchronous upload path
     float gamma_last[256]; bool gamma_have = false;   // what gamma_dev holds: the table is re-sent only when the caller's differs (and then behind every kernel that may read it)
     // raw-frame ingest (nalo_undist_set / nalo_frame_upload_raw): photometric + geometric undistortion tables, raw staging
     int und_wOrg = 0, und_hOrg = 0, und_photometric = 0, und_GDepth = 0; bool und_set = false, und_remap = false, und_vig = false;
@@ -77,7 +132,7 @@ struct nalo_ctx {
     nalo::DevBuf<unsigned> trk_ticket;       // trk_eval_kernel's arrival counter (zero between launches)
     nalo::DevBuf<float> ref_res; int ref_res_n = -1;   // nalo_trk_ref_upload: {Ku, Kv, new_idepth, HdiF} of the tracking reference, resident (n = -1: none)
     nalo::DevBuf<double> trk_out;            // 64 doubles
-    double* trk_out_host = nullptr;          // pinned, host-mapped: results + sequence flag
+    nalo::HostBuf<double> trk_out_host;      // pinned, host-mapped: results + sequence flag
     unsigned long long trk_seq = 0;
     nalo::DevBuf<unsigned long long> lm_partial;   // persistent LM kernel: [2][blocks][64] block partials {fp32, tag}
     unsigned long long lm_launches = 0;
@@ -90,11 +145,11 @@ struct nalo_ctx {
     nalo::DevBuf<unsigned long long> dense_lb;   // nalo_dense_make_map scratch: row table | chunk aggregates | last[2] | ticket
     nalo::DevBuf<int> trk_cnt;               // hits per level-0 pixel of the reference scatter (ordered redo of pixels with >= 3 hits)
     nalo::DevBuf<float> upload_tmp;
-    float* pinned_f = nullptr; size_t pinned_f_cap = 0;
-    float* imm_host = nullptr; nalo::DevBuf<float> imm_dev; size_t imm_cap = 0;   // immature-point staging (pinned / device)
+    nalo::HostBuf<float> pinned_f;           // nalo_trk_set_ref's staging (upload4)
+    nalo::HostBuf<float> imm_host; nalo::DevBuf<float> imm_dev;   // immature-point staging (pinned / device), grown together (imm_stage)
     nalo::DevBuf<float> imm_res; int imm_res_n = 0, imm_res_maxhost = -1;         // device-resident immature points (nalo_imm_resident_*)
 
-    // ---- BA (opaque; defined in host_ba.cpp)
+    // ---- BA (opaque; defined in host_ba.hip)
     nalo::BAWindow* ba = nullptr;
     nalo::PixSel* pixsel = nullptr;          // pixel selector state (kernels_pixsel.hip)
     void* rccl = nullptr;                    // RCCL communicators of the sharded BA (host_rccl.hip)
@@ -109,7 +164,7 @@ struct nalo_ctx {
     bool prof_on = false;
     std::string prof_only;                   // empty = every scope; else only the scope of that name is bracketed
     int prof_every = 1; unsigned prof_tick = 0;   // nalo_profile_sample: bracket one launch in prof_every (the brackets perturb a latency-bound pipeline)
-    std::vector<hipEvent_t> prof_pool;       // idle events
+    std::vector<hipEvent_t> prof_pool;       // idle events (raw handles: they move between this pool and ProfEntry::pending; nalo_destroy destroys both)
     std::map<std::string, nalo::ProfEntry> prof;
 };
 
@@ -179,6 +234,8 @@ int dist_make_launch(nalo_ctx* c, const float4* pt_geo, const uint8_t* pt_flags,
 int pixsel_hists_launch(nalo_ctx* c, const float* absg0, float* ths, float* thsSmoothed);
 // host_ba.hip: nalo_trk_set_ref_from_window's inputs gathered from the window on c->stream ({Ku | Kv | new_idepth | HdiF}, *n each, holes included)
 int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
+// host_ba.hip
+void ba_destroy(nalo_ctx* c);
 // host_rccl.hip
 void rccl_release(nalo_ctx* c);
 // host_init.hip
@@ -203,7 +260,6 @@ int init_do_step_launch(nalo_ctx* c, int n, const uint8_t* isGood, const float* 
 int init_apply_step_launch(nalo_ctx* c, int n, uint8_t* isGood, const uint8_t* isGood_new, float* idepth, float* idepth_new, const float* iR, float* energy, const float* energy_new,
                            float* lastHessian, const float* lastHessian_new);
 // the dependency-ordered sweeps (optReg: mode 0, the top level's resetPoints: mode 1) and the per-point parts of resetPoints / propagateDown / propagateUp
-constexpr int kThDblAB = 1024, kThDblC = 256;   // setNewFrameEnergyTH: the three radix histograms (2048 + 2048 + 512 bins) as doubles, two bins per double = the cross-rank payloads of a sharded window
 constexpr int kSweepNT = 128;                          // lanes of the sweep workgroup = the most points a schedule step may hold. trackFrame at 1224x368, same box:
                                                        // 64 lanes (no second wave at the barrier, 37 % more steps) 8.1 ms, 128: 7.4 ms, 256: 8.0 ms
 constexpr size_t kSweepLdsBytes = 158 * 1024;          // of the 160 KB per workgroup
@@ -226,9 +282,10 @@ int frame_tile_level0(nalo_ctx* c, nalo::FrameSlot& s);
 void hbm_stream_launch(hipStream_t st, const float4* a, const float4* b, float4* d, size_t n, int triad);
 int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOrg, int hOrg, const float* G, const float* vinv, const float2* remapXY, int photometric,
                   float factor, const uint8_t* mask_org, const uint8_t* bgr_org, float* out_I, float* out_mask, uint8_t* out_bgr);
-// kernels_tracker.hip
-// kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points
+// kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points; the whole pyramid descent of nalo_trk_track in one persistent launch
 int trk_lm_blocks(int maxn);
+int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2], int coarsest, int stop_lvl, const double* minRes, double out24[32]);
+// kernels_tracker.hip
 int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi);
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev);
 int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], const float t[3], const float Ki[9],

@@ -17,7 +17,7 @@ __host__ __device__ constexpr int trk_ut(int r, int c) { return r * 9 - r * (r -
 // one pyramid level of the tracking reference's point cloud and of the new frame
 struct TrkLevel { const float *u, *v, *id, *col; const float4* dI; int n, wl, hl; float fx, fy, cx, cy; };
 inline TrkLevel trk_level(const nalo_ctx* c, int slot_new, int l) {
-    return {c->pc_u[l].p, c->pc_v[l].p, c->pc_id[l].p, c->pc_col[l].p, c->slots[slot_new].dI[l], c->pc_n[l], c->wl[l], c->hl[l], c->fx[l], c->fy[l], c->cx[l], c->cy[l]};
+    return {c->pc_u[l].p, c->pc_v[l].p, c->pc_id[l].p, c->pc_col[l].p, c->slots[slot_new].dI[l].p, c->pc_n[l], c->wl[l], c->hl[l], c->fx[l], c->fy[l], c->cx[l], c->cy[l]};
 }
 
 // the point (x, y) with inverse depth id warped into the new frame (:941-946)
