@@ -442,6 +442,27 @@ int nalo_imm_optimize(nalo_ctx* ctx, int n, const int* host, const float* u, con
  * idepth_max] - as the device's last trace left it, FullSystem.cpp:700-760 activates right after traceNewCoarse - are read on the device; 4 bytes per point cross PCIe
  * on the way down instead of 88. Outputs as nalo_imm_optimize. */
 int nalo_imm_resident_optimize(nalo_ctx* ctx, int n, const int* sel, int minObs, int* result, float* idepth_out, uint8_t* res_in);
+/* FullSystem::activatePointsMT's steps 1-3 (FullSystem.cpp:794-889) for the resident set, on the device: makeDistanceMap of the window's active points for the
+ * newest keyframe `frame` (as nalo_dist_make_map; KRKi[W][9], Kt[W][3] host -> frame at level 1), the loop :805-876 that deletes / keeps / selects every immature
+ * point against that map and adds each selected point into it (addIntoDistFinal) before the next is looked at, and optimizeImmaturePoint of the selected points
+ * (as nalo_imm_resident_optimize). The loop's order is the reference's: by host_idx, and inside a host by index in the resident set. The result is the
+ * sequential loop's for every input; the host waits once, at the end (more often only when the selection needs more than 12 dependent rounds).
+ *   nalo_imm_resident_set_type   my_type[n] (ImmaturePoint::my_type, 1 / 2 / 4) of the resident points, once after nalo_imm_resident_set (which invalidates it).
+ *   nalo_imm_resident_activate   host_flagged[W]: FrameHessian::flaggedForMarginalization; currentMinActDist as the reference keeps it, in [0, 4].
+ *       fate[n] per resident point:  1 selected;  0 kept (cannot activate yet);  2 kept (too close to an active or an earlier selected point);
+ *                                   -1 deleted (never traced, or OUTLIER: :820);  -2 deleted (not ready and host flagged or OOB: :843);
+ *                                   -3 deleted (projects outside the frame: :870);  3 not visited (hosted by `frame`: :807).
+ *       *n_sel, sel[n]: the selected points' indices in the resident set in the order of the reference's toOptimize (the first *n_sel are written);
+ *       result / idepth_out / res_in[n][W]: rows k < *n_sel as nalo_imm_resident_optimize(sel) returns them; all three NULL = selection only.
+ *       NALO_ERR_STATE: no window / points, no resident set or no types, a sharded window (a rank holds only part of the map's seeds), a resident host_idx
+ *       outside the window. NALO_ERR_ARG: NULL pointers, frame outside the window, currentMinActDist negative or not finite, and currentMinActDist * my_type
+ *       above 16 for any resident point (REFUSED, not computed: the parallel selection looks 16 level-1 pixels around a point, the reference's ranges give <= 16).
+ *   nalo_imm_activate_last       of the last call: stats = {points that pass the test on the initial map, selected, rejected because of an earlier selected
+ *                                point, dependent rounds run}. */
+int nalo_imm_resident_set_type(nalo_ctx* ctx, const float* my_type);
+int nalo_imm_resident_activate(nalo_ctx* ctx, int frame, const float* KRKi, const float* Kt, const int* host_flagged, float currentMinActDist, int minObs,
+                               int* fate, int* n_sel, int* sel, int* result, float* idepth_out, uint8_t* res_in);
+int nalo_imm_activate_last(nalo_ctx* ctx, int stats[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * the two-frame initialiser's Gauss-Newton pass.

@@ -32,7 +32,7 @@ EXPORTS = [
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
     "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
-    "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
+    "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
@@ -165,6 +165,9 @@ def load():
     L.nalo_imm_resident_get.argtypes = [vp, c_fp, c_fp, c_ip, c_fp, c_fp, c_fp]
     L.nalo_imm_optimize.argtypes = [vp, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_int, c_ip, c_fp, c_u8p]
     L.nalo_imm_resident_optimize.argtypes = [vp, C.c_int, c_ip, C.c_int, c_ip, c_fp, c_u8p]
+    L.nalo_imm_resident_set_type.argtypes = [vp, c_fp]
+    L.nalo_imm_resident_activate.argtypes = [vp, C.c_int, c_fp, c_fp, c_ip, C.c_float, C.c_int, c_ip, c_ip, c_ip, c_ip, c_fp, c_u8p]
+    L.nalo_imm_activate_last.argtypes = [vp, c_ip]
     L.nalo_ba_restore.argtypes = [vp]
     L.nalo_dense_make_map.argtypes = [vp, C.c_int, c_fp, C.c_float, c_dp, C.c_int, c_ip, c_ip, c_ip, c_fp, c_fp, c_u8p, c_ip, c_ip]
     L.nalo_profile_enable.argtypes = [vp, C.c_int]
@@ -774,6 +777,35 @@ class Context:
         res, idp, rin = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, self.W), np.uint8)
         self._ck(self.L.nalo_imm_resident_optimize(self.h_, n, sp, int(min_obs), _i(res), _f(idp), _u8(rin)))
         return res, idp, rin
+
+    def imm_resident_set_type(self, my_type):
+        """ImmaturePoint::my_type of every resident point, once after imm_resident_set"""
+        t = np.ascontiguousarray(my_type, np.float32)
+        if len(t) != self._imm_n:
+            raise ValueError("my_type needs one entry per resident point")
+        self._ck(self.L.nalo_imm_resident_set_type(self.h_, _f(t)))
+
+    def imm_resident_activate(self, frame, KRKi, Kt, host_flagged, min_act_dist, min_obs=None):
+        """activatePointsMT's distance map + selection loop (+ optimizeImmaturePoint of the selected points when min_obs is given) for the resident set:
+        fate [n], sel [n_sel] and, with min_obs, (result, idepth, res_in) rows for sel; see nalo_imm_resident_activate"""
+        n = self._imm_n
+        fate, sel, nsel = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(1, np.int32)
+        fl = np.ascontiguousarray(host_flagged, np.int32)
+        k = [np.ascontiguousarray(x, np.float32) for x in (KRKi, Kt)]
+        if min_obs is None:
+            self._ck(self.L.nalo_imm_resident_activate(self.h_, int(frame), _f(k[0]), _f(k[1]), _i(fl), float(min_act_dist), 0, _i(fate), _i(nsel), _i(sel), None, None, None))
+            return fate, sel[:nsel[0]].copy()
+        res, idp, rin = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, self.W), np.uint8)
+        self._ck(self.L.nalo_imm_resident_activate(self.h_, int(frame), _f(k[0]), _f(k[1]), _i(fl), float(min_act_dist), int(min_obs), _i(fate), _i(nsel), _i(sel),
+                                                    _i(res), _f(idp), _u8(rin)))
+        m = int(nsel[0])
+        return fate, sel[:m].copy(), (res[:m].copy(), idp[:m].copy(), rin[:m].copy())
+
+    def imm_activate_last(self):
+        """(survivors of the test on the initial map, selected, rejected because of an earlier selected point, rounds) of the last imm_resident_activate"""
+        st = np.zeros(4, np.int32)
+        self._ck(self.L.nalo_imm_activate_last(self.h_, _i(st)))
+        return tuple(int(x) for x in st)
 
     def ba_snapshot(self):
         self._ck(self.L.nalo_ba_snapshot(self.h_))

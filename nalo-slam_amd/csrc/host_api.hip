@@ -675,7 +675,7 @@ int nalo_imm_resident_set(nalo_ctx* c, int n, const float* u, const float* v, co
     if (!c || n < 0 || (n > 0 && (!u || !v || !color || !weights || !gradH || !energyTH || !host_idx || !idepth_min || !idepth_max || !status || !quality)))
         return fail(c, NALO_ERR_ARG, "nalo_imm_resident_set: bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
-    c->imm_res_n = n; c->imm_res_maxhost = -1;
+    c->imm_res_n = n; c->imm_res_maxhost = -1; c->imm_type_set = false;
     if (n == 0) return NALO_OK;
     const size_t N = (size_t)n;
     int rc = imm_stage(c, 30 * N); if (rc) return rc;
@@ -689,6 +689,28 @@ int nalo_imm_resident_set(nalo_ctx* c, int n, const float* u, const float* v, co
     std::memset(hst + 29 * N, 0, N * 4);
     NALO_HIP(c, hipMemcpyAsync(c->imm_res.p, hst, 30 * N * 4, hipMemcpyHostToDevice, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));                             // the staging buffer is shared with the other immature-point calls
+    return NALO_OK;
+}
+// ImmaturePoint::my_type of every resident point (the selector's status 1 / 2 / 4, PixelSelector2.h:36): activation's threshold is currentMinActDist * my_type
+int nalo_imm_resident_set_type(nalo_ctx* c, const float* my_type) {
+    if (!c || (c->imm_res_n > 0 && !my_type)) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_set_type: bad argument");
+    const size_t N = (size_t)c->imm_res_n;
+    float mx = 0;
+    for (size_t i = 0; i < N; ++i) { if (!std::isfinite(my_type[i])) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_set_type: my_type is not finite"); mx = std::max(mx, my_type[i]); }
+    c->imm_type_set = false; c->imm_type_max = mx;
+    if (N == 0) { c->imm_type_set = true; return NALO_OK; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    int rc = imm_stage(c, N); if (rc) return rc;
+    NALO_HIP(c, c->imm_type.reserve(N));
+    std::memcpy(c->imm_host.p, my_type, N * 4);
+    NALO_HIP(c, hipMemcpyAsync(c->imm_type.p, c->imm_host.p, N * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                             // the staging buffer is shared with the other immature-point calls
+    c->imm_type_set = true;
+    return NALO_OK;
+}
+int nalo_imm_activate_last(nalo_ctx* c, int stats[4]) {
+    if (!c || !stats) return fail(c, NALO_ERR_ARG, "nalo_imm_activate_last: bad argument");
+    std::memcpy(stats, c->imm_act_stats, sizeof(c->imm_act_stats));
     return NALO_OK;
 }
 int nalo_imm_resident_trace(nalo_ctx* c, int slot_new, int nh, const float* KRKi, const float* Kt, const float* aff) {

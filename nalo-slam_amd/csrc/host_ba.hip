@@ -1566,6 +1566,20 @@ int nalo_dist_make_map(nalo_ctx* c, int frame, const float* KRKi, const float* K
     return NALO_OK;
 }
 
+// FrameFramePrecalc::set (HessianBlocks.cpp:203-221) at the current states, as optimizeImmaturePoint reads it: Rt[W*W][12] = PRE_RTll | PRE_tTll, af[W*W][2] = PRE_aff_mode
+static void imm_precalc(const BAWindow& w, float* Rt, float* af) {
+    const int W = w.W;
+    for (int h = 0; h < W; ++h) for (int t = 0; t < W; ++t) {
+        const HostFrame &hf = w.frames[h], &tf = w.frames[t];
+        const SE3 ll = tf.PRE_worldToCam * hf.PRE_camToWorld;
+        float* o = Rt + (size_t)(h * W + t) * 12;
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)ll.R(i, j); o[9 + i] = (float)ll.t(i); }
+        double a[2];
+        aff_from_to(hf.ab_exposure, tf.ab_exposure, hf.state_scaled[6], hf.state_scaled[7], tf.state_scaled[6], tf.state_scaled[7], a);
+        af[(h * W + t) * 2] = (float)a[0]; af[(h * W + t) * 2 + 1] = (float)a[1];
+    }
+}
+
 // FullSystem::optimizeImmaturePoint for a batch of immature points against the current window (FullSystemOptPoint.cpp:51-206)
 int nalo_imm_optimize(nalo_ctx* c, int n, const int* host, const float* u, const float* v, const float* color, const float* weights,
                       const float* energyTH, const float* idepth_min, const float* idepth_max, int minObs, int* result, float* idepth_out, uint8_t* res_in) {
@@ -1585,15 +1599,7 @@ int nalo_imm_optimize(nalo_ctx* c, int n, const int* host, const float* u, const
     std::memcpy(hst, u, N * 4); std::memcpy(hst + N, v, N * 4); std::memcpy(hst + 2 * N, color, 8 * N * 4); std::memcpy(hst + 10 * N, weights, 8 * N * 4);
     std::memcpy(hst + 18 * N, energyTH, N * 4); std::memcpy(hst + 19 * N, idepth_min, N * 4); std::memcpy(hst + 20 * N, idepth_max, N * 4); std::memcpy(hst + 21 * N, host, N * 4);
     float* Rt = hst + 22 * N; float* af = Rt + 12 * PW;
-    for (int h = 0; h < W; ++h) for (int t = 0; t < W; ++t) {               // FrameFramePrecalc::set (HessianBlocks.cpp:203-221) at the current states
-        const HostFrame &hf = w.frames[h], &tf = w.frames[t];
-        const SE3 ll = tf.PRE_worldToCam * hf.PRE_camToWorld;
-        float* o = Rt + (size_t)(h * W + t) * 12;
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)ll.R(i, j); o[9 + i] = (float)ll.t(i); }
-        double a[2];
-        aff_from_to(hf.ab_exposure, tf.ab_exposure, hf.state_scaled[6], hf.state_scaled[7], tf.state_scaled[6], tf.state_scaled[7], a);
-        af[(h * W + t) * 2] = (float)a[0]; af[(h * W + t) * 2 + 1] = (float)a[1];
-    }
+    imm_precalc(w, Rt, af);
     float* d = c->imm_dev.p;
     NALO_HIP(c, hipMemcpyAsync(d, hst, out0 * 4, hipMemcpyHostToDevice, c->stream));
     const float K[4] = {w.c_scaledf[0], w.c_scaledf[1], w.c_scaledf[2], w.c_scaledf[3]};
@@ -1626,15 +1632,7 @@ int nalo_imm_resident_optimize(nalo_ctx* c, int n, const int* sel, int minObs, i
     float* hst = c->imm_host.p;
     if (sel) std::memcpy(hst, sel, N * 4);
     float* Rt = hst + N; float* af = Rt + 12 * PW;
-    for (int h = 0; h < W; ++h) for (int t = 0; t < W; ++t) {               // FrameFramePrecalc::set (HessianBlocks.cpp:203-221) at the current states
-        const HostFrame &hf = w.frames[h], &tf = w.frames[t];
-        const SE3 ll = tf.PRE_worldToCam * hf.PRE_camToWorld;
-        float* o = Rt + (size_t)(h * W + t) * 12;
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) o[i * 3 + j] = (float)ll.R(i, j); o[9 + i] = (float)ll.t(i); }
-        double a[2];
-        aff_from_to(hf.ab_exposure, tf.ab_exposure, hf.state_scaled[6], hf.state_scaled[7], tf.state_scaled[6], tf.state_scaled[7], a);
-        af[(h * W + t) * 2] = (float)a[0]; af[(h * W + t) * 2 + 1] = (float)a[1];
-    }
+    imm_precalc(w, Rt, af);
     float* d = c->imm_dev.p;
     NALO_HIP(c, hipMemcpyAsync(d, hst, out0 * 4, hipMemcpyHostToDevice, c->stream));
     const float K[4] = {w.c_scaledf[0], w.c_scaledf[1], w.c_scaledf[2], w.c_scaledf[3]};
@@ -1644,6 +1642,80 @@ int nalo_imm_resident_optimize(nalo_ctx* c, int n, const int* sel, int minObs, i
     NALO_HIP(c, hipMemcpyAsync(hst + out0, d + out0, outw * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     std::memcpy(result, hst + out0, N * 4); std::memcpy(idepth_out, hst + out0 + N, N * 4); std::memcpy(res_in, hst + out0 + 2 * N, N * W);
+    return NALO_OK;
+}
+
+// FullSystem::activatePointsMT steps 1-3 (FullSystem.cpp:794-889) for the resident set: the distance map, the selection loop and optimizeImmaturePoint of the
+// selected points, enqueued back to back on c->stream; nothing but the per-host matrices goes down, and the host waits once, at the end. The selection's rounds
+// (kernels_imm.hip) are enqueued as a batch; in the rare case that the batch leaves survivors undecided (a long chain of points that each depend on the one
+// before), larger batches follow, each with a wait of its own, and the list and the optimisation are made again from the complete selection.
+int nalo_imm_resident_activate(nalo_ctx* c, int frame, const float* KRKi, const float* Kt, const int* host_flagged, float currentMinActDist, int minObs,
+                               int* fate, int* n_sel, int* sel, int* result, float* idepth_out, uint8_t* res_in) {
+    if (!c || !c->ba || !c->ba->points_set || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_activate: set the window and its points first");
+    BAWindow& w = *c->ba;
+    if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_activate: the window is sharded (a rank holds only part of the distance map's seeds)");
+    if (!c->imm_type_set) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_activate: no resident set with its types (nalo_imm_resident_set, then nalo_imm_resident_set_type)");
+    const int W = w.W, n = c->imm_res_n;
+    if (c->imm_res_maxhost >= W) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_activate: a resident point's host_idx is outside the window");
+    const bool opt = result || idepth_out || res_in;
+    if (!KRKi || !Kt || !host_flagged || !n_sel || (n > 0 && (!fate || !sel)) || (opt && !(result && idepth_out && res_in)) || frame < 0 || frame >= W || c->levels < 2)
+        return fail(c, NALO_ERR_ARG, "nalo_imm_resident_activate: bad argument");
+    if (!(currentMinActDist >= 0) || !std::isfinite(currentMinActDist)) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_activate: currentMinActDist is negative or not finite");
+    if (currentMinActDist * c->imm_type_max > 16.f)
+        return fail(c, NALO_ERR_ARG, "nalo_imm_resident_activate: currentMinActDist * my_type above 16 (the reference keeps currentMinActDist in [0, 4] and my_type in {1, 2, 4})");
+    const int w1 = c->wl[1], h1 = c->hl[1];
+    if (w1 > 0xFFFF || h1 > 0xFFFF || (unsigned)n > kActIdxMaxN) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_imm_resident_activate: level 1 beyond 65535 pixels a side or more than 2^27 points");
+    *n_sel = 0;
+    std::memset(c->imm_act_stats, 0, sizeof(c->imm_act_stats));
+    if (n == 0) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "imm_activate");
+    // staging words: [0, in) KRKi Kt flagged Rt aff | map w1*h1 | seed bytes | outputs: fate(n) sel(n) result(n) idepth(n) res_in(n*W bytes)
+    const size_t N = (size_t)n, PW = (size_t)W * W, npx = (size_t)w1 * h1, in = 13 * (size_t)W + 14 * PW, out0 = in + npx + (npx + 3) / 4;
+    const size_t outw = 2 * N + (opt ? 2 * N + (N * W + 3) / 4 : 0);
+    int rc = imm_stage(c, out0 + outw + 16); if (rc) return rc;
+    float* hst = c->imm_host.p; float* d = c->imm_dev.p;
+    std::memcpy(hst, KRKi, 9 * (size_t)W * 4); std::memcpy(hst + 9 * W, Kt, 3 * (size_t)W * 4); std::memcpy(hst + 12 * W, host_flagged, (size_t)W * 4);
+    imm_precalc(w, hst + 13 * W, hst + 13 * W + 12 * PW);
+    NALO_HIP(c, hipMemcpyAsync(d, hst, in * 4, hipMemcpyHostToDevice, c->stream));
+    float* dmap = d + in;
+    rc = dist_make_launch(c, w.pt_geo.p, w.pt_flags.p, w.blk_host.p, w.Ppad, frame, d, d + 9 * W, (uint8_t*)(dmap + npx), dmap);
+    if (rc) return rc;
+    // scratch ints: zeroed per call [stats 4 | cell_off ncells+1 | cell_fill ncells] | ctr kActMaxRounds | cnt W*nb+1 | rec 4n | items 2n
+    ActParams P;
+    P.n = n; P.W = W; P.frame = frame; P.w1 = w1; P.h1 = h1; P.cw = (w1 + 15) / 16; P.ch = (h1 + 15) / 16; P.minActDist = currentMinActDist;
+    const size_t ncells = (size_t)P.cw * P.ch, nb = (N + 255) / 256, zero = 4 + 2 * ncells + 1, o_ctr = zero, o_cnt = o_ctr + kActMaxRounds, o_rec = (o_cnt + W * nb + 1 + 3) & ~(size_t)3;
+    NALO_HIP(c, c->imm_act.reserve(o_rec + 6 * N));
+    int* a = c->imm_act.p;
+    P.res = c->imm_res.p; P.type = c->imm_type.p; P.KRKi = d; P.Kt = d + 9 * W; P.flagged = (const int*)(d + 12 * W); P.D0 = dmap;
+    P.fate = (int*)(d + out0); P.rec = (uint4*)(a + o_rec); P.items = (uint2*)(a + o_rec + 4 * N);
+    P.stats = a; P.cell_off = a + 4; P.cell_fill = a + 4 + ncells + 1;
+    int* dsel = (int*)(d + out0 + N);
+    NALO_HIP(c, hipMemsetAsync(a, 0, zero * 4, c->stream));
+    const float K[4] = {w.c_scaledf[0], w.c_scaledf[1], w.c_scaledf[2], w.c_scaledf[3]};
+    int* tail = (int*)(hst + out0 + outw);                                    // stats(4) | n_sel | undecided
+    for (int rounds = kActFirstRounds, pass = 0;; rounds = std::min(4 * rounds, kActMaxRounds), ++pass) {
+        NALO_HIP(c, hipMemsetAsync(a + o_ctr, 0, (size_t)rounds * 4, c->stream));
+        rc = act_launch(c, P, pass == 0, rounds, a + o_ctr, a + o_cnt, dsel);
+        if (rc) return rc;
+        if (opt) {
+            rc = imm_optimize_resident_launch(c, w.dev.img, W, K, d + 13 * W, d + 13 * W + 12 * PW, n, dsel, c->imm_res.p, N, minObs,
+                                              (int*)(d + out0 + 2 * N), d + out0 + 3 * N, (uint8_t*)(d + out0 + 4 * N), a + o_cnt + W * nb);
+            if (rc) return rc;
+        }
+        NALO_HIP(c, hipMemcpyAsync(hst + out0, d + out0, outw * 4, hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(tail, a, 16, hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(tail + 4, a + o_cnt + W * nb, 4, hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(tail + 5, a + o_ctr + rounds - 1, 4, hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipStreamSynchronize(c->stream));
+        if (tail[5] == 0) break;
+    }
+    std::memcpy(c->imm_act_stats, tail, 16);
+    const size_t ns = (size_t)tail[4];
+    if (ns > N) return fail(c, NALO_ERR_HIP, "nalo_imm_resident_activate: the device returned an impossible count");
+    *n_sel = (int)ns;
+    std::memcpy(fate, hst + out0, N * 4); std::memcpy(sel, hst + out0 + N, ns * 4);
+    if (opt) { std::memcpy(result, hst + out0 + 2 * N, ns * 4); std::memcpy(idepth_out, hst + out0 + 3 * N, ns * 4); std::memcpy(res_in, hst + out0 + 4 * N, ns * W); }
     return NALO_OK;
 }
 

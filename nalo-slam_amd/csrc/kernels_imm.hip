@@ -301,54 +301,15 @@ __device__ __forceinline__ double imm_linearize8(const ImmOptParams& P, int hf, 
 }
 
 __global__ __launch_bounds__(256) void imm_optimize8_kernel(ImmOptParams P) {
-    __shared__ double en_s[(NALO_MAX_WINDOW - 1) * kImmGroups], nen_s[(NALO_MAX_WINDOW - 1) * kImmGroups];
-    const int l = threadIdx.x & 7, tid = threadIdx.x >> 3;                     // tid = group (point) inside the block
-    const int p = blockIdx.x * kImmGroups + tid;
-    if (p >= P.n) return;
-    double* en = en_s + tid; double* nen = nen_s + tid;
-    const int q = P.sel ? P.sel[p] : p;                                        // where the point's inputs are; the outputs are indexed by p
-    const int W = P.W, hf = P.host[q], nres = W - 1;
-    const float color_l = P.color[(size_t)q * 8 + l], weight_l = P.weights[(size_t)q * 8 + l];
-    const float u = P.u[q], v = P.v[q], energyTH = P.energyTH[q];
-    unsigned st = 0, nst = 0;                                                  // state = IN (0) for every residual; newState = OUTLIER
-    for (int i = 0; i < nres; ++i) { en[i * kImmGroups] = 0; nen[i * kImmGroups] = 0; nst |= (unsigned)IRS_OUTLIER << (2 * i); }
-    if (l == 0) for (int t = 0; t < W; ++t) P.res_in[(size_t)p * W + t] = 0;
-    if (l == 0) P.idepth_out[p] = NAN;
-    auto tgt = [&](int i) { return i < hf ? i : i + 1; };                      // residual i <-> the i-th frame that is not the host
-    float lastEnergy = 0, lastHdd = 0, lastbd = 0;
-    float currentIdepth = (P.idmax[q] + P.idmin[q]) * 0.5f;
-    for (int i = 0; i < nres; ++i) {
-        // `float += double`: formed in double, rounded once (FullSystemOptPoint.cpp:79)
-        lastEnergy = (float)((double)lastEnergy + imm_linearize8(P, hf, tgt(i), u, v, color_l, weight_l, l, energyTH, 1000.f, st, nst, en, nen, i, lastHdd, lastbd, currentIdepth));
-        st = (st & ~(3u << (2 * i))) | (((nst >> (2 * i)) & 3u) << (2 * i));
-        en[i * kImmGroups] = nen[i * kImmGroups];
-    }
-    if (!isfinite(lastEnergy) || lastHdd < kImmMinIdepthHAct) { if (l == 0) P.result[p] = 0; return; }
-    float lambda = 0.1f;
-    for (int it = 0; it < kImmGNItsActivation; ++it) {
-        float H = lastHdd; H *= 1 + lambda;
-        const float step = (float)((1.0 / (double)H) * (double)lastbd);        // `(1.0/H) * lastbd` is a double expression, :99
-        const float newIdepth = currentIdepth - step;
-        float newHdd = 0, newbd = 0, newEnergy = 0;
-        for (int i = 0; i < nres; ++i)
-            newEnergy = (float)((double)newEnergy + imm_linearize8(P, hf, tgt(i), u, v, color_l, weight_l, l, energyTH, 1.f, st, nst, en, nen, i, newHdd, newbd, newIdepth));
-        if (!isfinite(lastEnergy) || newHdd < kImmMinIdepthHAct) { if (l == 0) P.result[p] = 0; return; }
-        if (newEnergy < lastEnergy) {
-            currentIdepth = newIdepth; lastHdd = newHdd; lastbd = newbd; lastEnergy = newEnergy;
-            st = nst;
-            for (int i = 0; i < nres; ++i) en[i * kImmGroups] = nen[i * kImmGroups];
-            lambda *= 0.5f;
-        } else lambda *= 5;
-        if ((double)fabsf(step) < 0.0001 * (double)currentIdepth) break;
-    }
-    if (!isfinite(currentIdepth)) { if (l == 0) P.result[p] = -1; return; }
-    int numGood = 0;
-    for (int i = 0; i < nres; ++i) if (((st >> (2 * i)) & 3u) == IRS_IN) numGood++;
-    if (numGood < P.minObs) { if (l == 0) P.result[p] = -1; return; }
-    if (!isfinite(energyTH)) { if (l == 0) P.result[p] = -1; return; }                     // PointHessian inherits energyTH, :158
-    if (l == 0) for (int i = 0; i < nres; ++i) if (((st >> (2 * i)) & 3u) == IRS_IN) P.res_in[(size_t)p * W + tgt(i)] = 1;
-    if (l == 0) P.idepth_out[p] = currentIdepth;
-    if (l == 0) P.result[p] = 1;
+#define NALO_IMM_OPT_COUNT P.n
+#include "imm_optimize8_body.h"
+#undef NALO_IMM_OPT_COUNT
+}
+// the number of points is read on the device: nalo_imm_resident_activate hands over its selection without the host seeing it
+__global__ __launch_bounds__(256) void imm_optimize8_dev_kernel(ImmOptParams P, const int* __restrict__ n_dev) {
+#define NALO_IMM_OPT_COUNT (*n_dev)
+#include "imm_optimize8_body.h"
+#undef NALO_IMM_OPT_COUNT
 }
 
 // ---------------------------------------------------------------------------------------------------------------- CoarseDistanceMap
@@ -410,6 +371,237 @@ int dist_make_launch(nalo_ctx* c, const float4* pt_geo, const uint8_t* pt_flags,
     {
         ProfScope ps(c, "dist_bfs");
         dist_bfs_kernel<<<((w1 + kDistTile - 1) / kDistTile) * ((h1 + kDistTile - 1) / kDistTile), 256, 0, c->stream>>>(seed, w1, h1, out);
+    }
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- activatePointsMT's selection loop
+// FullSystem.cpp:805-876 over the resident set, against the distance map above (DESIGN.md 5b has the argument). The loop visits the points in the order
+// key = (host, index in the set) and accepts a point when D(U, V) + frac >= th on the map as the earlier acceptances left it (addIntoDistFinal = a seed + one
+// growDistBFS on the current map). Away from the image corners that map is min(D0, delta(s_j, .) over the accepted s_j), delta the single-seed BFS distance, so:
+//   act_classify_kernel  everything that needs no other point: the fates -1 / -2 / -3 / 0 / 3, the D0 test (a point that fails on D0 fails for good: D only
+//                        falls), and for the survivors need = the smallest integer D with D + frac >= th (<= 16, th <= 16) and their 16x16 cell's count
+//   act_scan_kernel      exclusive scan (cell offsets; later the per-host, per-workgroup offsets of the selection list)
+//   act_scatter_kernel   survivors into their cells. The position inside a cell comes from an atomic and means nothing: order is always the key's
+//   act_round_kernel     one round per launch: an undecided survivor looks at the earlier survivors s_j of the 3x3 cells around it with delta(s_j, p) < need
+//                        (need <= 16: Chebyshev distance <= 15): one of them accepted -> rejected; none undecided -> accepted; else it waits. A decision is
+//                        final, so the fates are updated in place; the undecided survivor with the smallest key is decided in every round: <= n rounds.
+//   act_count / act_emit sel = the accepted points in key order (per host and workgroup counts, scan, ballot ranks inside the workgroup)
+// The bottom-right corner C = (w1-1, h1-1) is the one pixel a candidate can hit whose value depends on the history (its only way in is the diagonal from
+// I = (w1-2, h1-2) on an odd level): an acceptance j gives it v + 1 when it LOWERS D(I) to an even v, and 0 when s_j = C. act_round_kernel decides a
+// candidate on C by that rule once every earlier survivor that can reach I in need - 2 steps is decided.
+enum { ACT_UNDECIDED = 4 };
+constexpr unsigned kActNoRec = 0xFFFFFFFFu;
+__device__ __forceinline__ int act_wave_count(bool b) { return __popcll(__ballot(b)); }
+
+__global__ __launch_bounds__(256) void act_classify_kernel(ActParams P) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool survivor = false;
+    if (i < P.n) {
+        const size_t N = (size_t)P.n;
+        const int host = ((const int*)(P.res + 22 * N))[i];
+        uint4 rec = make_uint4(0, 0, kActNoRec, 0);
+        int fate;
+        do {
+            if (host == P.frame) { fate = 3; break; }                                                                   // :807
+            const float idmin = P.res[23 * N + i], idmax = P.res[24 * N + i];
+            const int status = ((const int*)(P.res + 25 * N))[i];
+            if (!isfinite(idmax) || status == IPS_OUTLIER) { fate = -1; break; }                                        // :820
+            const bool canActivate = (status == IPS_GOOD || status == IPS_SKIPPED || status == IPS_BADCONDITION || status == IPS_OOB) &&
+                                     P.res[29 * N + i] < 8 && P.res[26 * N + i] > kMinTraceQuality && (idmax + idmin) > 0;   // :830-836
+            if (!canActivate) { fate = (P.flagged[host] || status == IPS_OOB) ? -2 : 0; break; }                        // :840-851
+            const float gx = P.res[i], gy = P.res[N + i], gz = 0.5f * (idmax + idmin);
+            const float* M = P.KRKi + host * 9; const float* T = P.Kt + host * 3;
+            float ptp[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ptp[k] = M[k * 3] * gx + M[k * 3 + 1] * gy + M[k * 3 + 2] * 1 + T[k] * gz;       // :855, term by term as dist_seed_kernel
+            const int U = (int)(ptp[0] / ptp[2] + 0.5f), V = (int)(ptp[1] / ptp[2] + 0.5f);                              // NaN -> 0, out of range saturates: both outside
+            if (!(U > 0 && V > 0 && U < P.w1 && V < P.h1)) { fate = -3; break; }                                        // :859, :870-874
+            const float frac = ptp[0] - floorf(ptp[0]), th = P.minActDist * P.type[i];
+            if (!(P.D0[U + P.w1 * V] + frac >= th)) { fate = 2; break; }                                                // :862-864 on D0
+            unsigned need = 0;
+            while (need < 16 && !((float)need + frac >= th)) ++need;
+            const unsigned cell = (unsigned)((V >> 4) * P.cw + (U >> 4));
+            rec = make_uint4((unsigned)U | ((unsigned)V << 16), ((unsigned)host << kActIdxBits) | (unsigned)i, need, cell);
+            fate = need == 0 ? 1 : ACT_UNDECIDED;                                                                       // need 0: accepted whatever came before
+            survivor = true;
+            atomicAdd(&P.cell_off[cell], 1);
+            if (need == 0) atomicAdd(&P.stats[1], 1);
+        } while (false);
+        P.fate[i] = fate; P.rec[i] = rec;
+    }
+    const int ns = act_wave_count(survivor);
+    if (ns && (threadIdx.x & 63) == 0) atomicAdd(&P.stats[0], ns);
+}
+
+// exclusive scan of a[0..m) in place, the total into a[m]; one workgroup (m is a few thousand cells, or hosts x workgroups)
+__global__ __launch_bounds__(1024) void act_scan_kernel(int* __restrict__ a, int m) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x, per = (m + 1023) / 1024, b = t * per, e = min(b + per, m);
+    int s = 0;
+    for (int k = b; k < e; ++k) s += a[k];
+    part[t] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int x = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += x;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int k = b; k < e; ++k) { const int x = a[k]; a[k] = run; run += x; }
+    if (t == 1023) a[m] = part[1023];
+}
+
+__global__ __launch_bounds__(256) void act_scatter_kernel(ActParams P) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.n) return;
+    const uint4 r = P.rec[i];
+    if (r.z == kActNoRec) return;
+    P.items[P.cell_off[r.w] + atomicAdd(&P.cell_fill[r.w], 1)] = make_uint2(r.x, r.y);
+}
+
+// single-seed BFS distance between interior pixels |dx|, |dy| apart: level k moves one pixel, diagonally too when k is odd (an octagon)
+__device__ __forceinline__ int act_free_dist(int dx, int dy) {
+    dx = abs(dx); dy = abs(dy);
+    int k = max(dx, dy);
+    while (k + ((k + 1) >> 1) < dx + dy) ++k;
+    return k;
+}
+__device__ __forceinline__ bool act_on_border(int x, int y, int w1, int h1) { return x == 0 || y == 0 || x == w1 - 1 || y == h1 - 1; }
+// delta(s, p) <= r for a candidate pixel p that is not the corner C. A seed on the border never expands (growDistBFS skips it, like dist_bfs_kernel's taps);
+// a border pixel p is entered from its interior neighbours q at level delta(s, q) + 1, diagonally only when that level is odd.
+__device__ __forceinline__ bool act_reaches(int sx, int sy, int U, int V, int r, int w1, int h1) {
+    if (sx == U && sy == V) return true;
+    if (act_on_border(sx, sy, w1, h1)) return false;
+    const int dx = abs(sx - U), dy = abs(sy - V);
+    if (max(dx, dy) > r) return false;
+    if (!act_on_border(U, V, w1, h1)) return dx + dy <= r + ((r + 1) >> 1);
+    for (int oy = -1; oy <= 1; ++oy) for (int ox = -1; ox <= 1; ++ox) {
+        const int qx = U + ox, qy = V + oy;
+        if ((ox == 0 && oy == 0) || qx < 0 || qy < 0 || qx >= w1 || qy >= h1 || act_on_border(qx, qy, w1, h1)) continue;
+        const int d = act_free_dist(qx - sx, qy - sy);
+        if (d + 1 <= r && (ox == 0 || oy == 0 || !(d & 1))) return true;
+    }
+    return false;
+}
+// f(pixel, key) over the survivors of the 3x3 cells around cell (cx, cy), until it returns true
+template <typename F>
+__device__ __forceinline__ void act_neighbours(const ActParams& P, int cx, int cy, F f) {
+    for (int y = max(cy - 1, 0); y <= min(cy + 1, P.ch - 1); ++y)
+        for (int x = max(cx - 1, 0); x <= min(cx + 1, P.cw - 1); ++x) {
+            const int c = y * P.cw + x;
+            for (int k = P.cell_off[c], e = P.cell_off[c + 1]; k < e; ++k) { const uint2 it = P.items[k]; if (f(it.x, it.y)) return; }
+        }
+}
+__device__ __forceinline__ int act_fate(const ActParams& P, unsigned key) { return __atomic_load_n(&P.fate[key & kActIdxMask], __ATOMIC_RELAXED); }
+
+// prev == NULL: the first round of a batch; else the round leaves at once when its predecessor left nothing undecided. left: this round's undecided survivors.
+__global__ __launch_bounds__(256) void act_round_kernel(ActParams P, const int* __restrict__ prev, int* __restrict__ left) {
+    if (prev && *prev == 0) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int out = 0;                                                                // 0: nothing to do, 1 accepted, 2 rejected, ACT_UNDECIDED: waits
+    if (i < P.n && __atomic_load_n(&P.fate[i], __ATOMIC_RELAXED) == ACT_UNDECIDED) {
+        const uint4 r = P.rec[i];
+        const int U = r.x & 0xFFFF, V = r.x >> 16, need = (int)r.z, w1 = P.w1, h1 = P.h1;
+        const unsigned key = r.y;
+        bool rej = false, wait = false;
+        if (U == w1 - 1 && V == h1 - 1) {                                       // the corner C
+            const int Ix = w1 - 2, Iy = h1 - 2;
+            const bool I_in = !act_on_border(Ix, Iy, w1, h1);
+            auto toI = [&](unsigned pix) {                                      // delta(s, I), 99 when s cannot reach it
+                const int sx = pix & 0xFFFF, sy = pix >> 16;
+                return (!I_in || act_on_border(sx, sy, w1, h1)) ? 99 : act_free_dist(sx - Ix, sy - Iy);
+            };
+            act_neighbours(P, U >> 4, V >> 4, [&](unsigned pix, unsigned k) {
+                if (k < key && (pix == r.x || toI(pix) <= need - 2) && act_fate(P, k) == ACT_UNDECIDED) wait = true;
+                return wait;
+            });
+            if (!wait) {
+                const float DI = I_in ? P.D0[Ix + w1 * Iy] : 0.f;
+                act_neighbours(P, U >> 4, V >> 4, [&](unsigned pix, unsigned k) {
+                    if (k >= key || act_fate(P, k) != 1) return false;
+                    if (pix == r.x) { rej = true; return true; }
+                    const int v = toI(pix);
+                    if (v > need - 2 || (v & 1) || !(DI > (float)v)) return false;
+                    bool lowered = true;                                         // D(I) was above v when j came: no earlier acceptance within v of I
+                    act_neighbours(P, U >> 4, V >> 4, [&](unsigned pix2, unsigned k2) {
+                        if (k2 < k && toI(pix2) <= v && act_fate(P, k2) == 1) lowered = false;
+                        return !lowered;
+                    });
+                    rej = lowered;
+                    return rej;
+                });
+            }
+        } else {
+            act_neighbours(P, U >> 4, V >> 4, [&](unsigned pix, unsigned k) {
+                if (k >= key || !act_reaches(pix & 0xFFFF, pix >> 16, U, V, need - 1, w1, h1)) return false;
+                const int f = act_fate(P, k);
+                if (f == 1) rej = true; else if (f == ACT_UNDECIDED) wait = true;
+                return rej;
+            });
+        }
+        out = rej ? 2 : wait ? ACT_UNDECIDED : 1;
+        if (out != ACT_UNDECIDED) __atomic_store_n(&P.fate[i], out, __ATOMIC_RELAXED);
+    }
+    const int nw = act_wave_count(out == ACT_UNDECIDED), na = act_wave_count(out == 1), nr = act_wave_count(out == 2);
+    if ((threadIdx.x & 63) == 0) {                                              // whole waves arrive here
+        if (nw) atomicAdd(left, nw);
+        if (na) atomicAdd(&P.stats[1], na);
+        if (nr) atomicAdd(&P.stats[2], nr);
+    }
+    if (i == 0) P.stats[3] += 1;                                                // rounds that ran (launches are ordered: one writer at a time)
+}
+
+// the selection list, ordered by key: cnt[host * nb + workgroup] accepted points, scanned by act_scan_kernel, then every accepted point takes
+// offset + its rank among the workgroup's accepted points of the same host (ballots: lanes and waves are in index order)
+__global__ __launch_bounds__(256) void act_count_kernel(ActParams P, int* __restrict__ cnt, int nb) {
+    __shared__ int hc[NALO_MAX_WINDOW];
+    if (threadIdx.x < NALO_MAX_WINDOW) hc[threadIdx.x] = 0;
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P.n && P.fate[i] == 1) atomicAdd(&hc[P.rec[i].y >> kActIdxBits], 1);
+    __syncthreads();
+    if ((int)threadIdx.x < P.W) cnt[threadIdx.x * nb + blockIdx.x] = hc[threadIdx.x];
+}
+__global__ __launch_bounds__(256) void act_emit_kernel(ActParams P, const int* __restrict__ off, int nb, int* __restrict__ sel) {
+    __shared__ int wc[4][NALO_MAX_WINDOW];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool acc = i < P.n && P.fate[i] == 1;
+    const int host = acc ? (int)(P.rec[i].y >> kActIdxBits) : -1;
+    int rank = 0;
+    for (int h = 0; h < P.W; ++h) {
+        const unsigned long long m = __ballot(host == h);
+        if (host == h) rank = __popcll(m & ((1ull << lane) - 1));
+        if (lane == 0) wc[wave][h] = __popcll(m);
+    }
+    __syncthreads();
+    if (!acc) return;
+    int pos = off[host * nb + blockIdx.x] + rank;
+    for (int k = 0; k < wave; ++k) pos += wc[k][host];
+    sel[pos] = i;
+}
+
+// the selection on c->stream: `rounds` rounds behind classify (first = true) or behind the rounds before (the continuation of a call whose batch left survivors
+// undecided), then the list. ctr: `rounds` zeroed ints; ctr[rounds - 1] = the survivors still undecided at the end. cnt: W * nb + 1 ints, cnt[W * nb] = n_sel.
+int act_launch(nalo_ctx* c, const ActParams& P, bool first, int rounds, int* ctr, int* cnt, int* sel) {
+    const int nb = (P.n + 255) / 256, ncells = P.cw * P.ch;
+    if (first) {
+        ProfScope ps(c, "act_classify");
+        act_classify_kernel<<<nb, 256, 0, c->stream>>>(P);
+        act_scan_kernel<<<1, 1024, 0, c->stream>>>(P.cell_off, ncells);
+        act_scatter_kernel<<<nb, 256, 0, c->stream>>>(P);
+    }
+    {
+        ProfScope ps(c, "act_resolve");
+        for (int r = 0; r < rounds; ++r) act_round_kernel<<<nb, 256, 0, c->stream>>>(P, r ? ctr + r - 1 : nullptr, ctr + r);
+    }
+    {
+        ProfScope ps(c, "act_emit");
+        act_count_kernel<<<nb, 256, 0, c->stream>>>(P, cnt, nb);
+        act_scan_kernel<<<1, 1024, 0, c->stream>>>(cnt, P.W * nb);
+        act_emit_kernel<<<nb, 256, 0, c->stream>>>(P, cnt, nb, sel);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
@@ -500,8 +692,9 @@ int imm_trace_launch(nalo_ctx* c, const float4* dI, int n, const float* base /* 
     return NALO_OK;
 }
 // the resident set's layout (nalo_imm_resident_set): u | v | color8 | weights8 | gradH3 | energyTH | host | idmin | idmax | ..., N entries each; sel picks n of them
+// n_dev != NULL: sel and its length live on the device (act_launch's list); the launch is sized by n, the most it can hold, and the groups behind *n_dev leave at once
 int imm_optimize_resident_launch(nalo_ctx* c, const float4* const* dI, int W, const float K[4], const float* Rt, const float* aff, int n, const int* sel, const float* res, size_t N,
-                                 int minObs, int* result, float* idepth_out, uint8_t* res_in) {
+                                 int minObs, int* result, float* idepth_out, uint8_t* res_in, const int* n_dev) {
     ImmOptParams P;
     std::memset(&P, 0, sizeof(P));
     for (int i = 0; i < W; ++i) P.dI[i] = dI[i];
@@ -512,7 +705,8 @@ int imm_optimize_resident_launch(nalo_ctx* c, const float4* const* dI, int W, co
     P.result = result; P.idepth_out = idepth_out; P.res_in = res_in;
     if (n > 0) {
         ProfScope ps(c, "imm_optimize");
-        imm_optimize8_kernel<<<(n + kImmGroups - 1) / kImmGroups, 256, 0, c->stream>>>(P);
+        if (n_dev) imm_optimize8_dev_kernel<<<(n + kImmGroups - 1) / kImmGroups, 256, 0, c->stream>>>(P, n_dev);
+        else imm_optimize8_kernel<<<(n + kImmGroups - 1) / kImmGroups, 256, 0, c->stream>>>(P);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;

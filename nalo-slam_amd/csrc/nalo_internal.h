@@ -148,6 +148,8 @@ struct nalo_ctx {
     nalo::HostBuf<float> pinned_f;           // nalo_trk_set_ref's staging (upload4)
     nalo::HostBuf<float> imm_host; nalo::DevBuf<float> imm_dev;   // immature-point staging (pinned / device), grown together (imm_stage)
     nalo::DevBuf<float> imm_res; int imm_res_n = 0, imm_res_maxhost = -1;         // device-resident immature points (nalo_imm_resident_*)
+    nalo::DevBuf<float> imm_type; bool imm_type_set = false; float imm_type_max = 0;   // their my_type (nalo_imm_resident_set_type; a new set invalidates it)
+    nalo::DevBuf<int> imm_act; int imm_act_stats[4] = {};                         // nalo_imm_resident_activate's scratch; the last call's counts (nalo_imm_activate_last)
 
     // ---- BA (opaque; defined in host_ba.hip)
     nalo::BAWindow* ba = nullptr;
@@ -227,10 +229,21 @@ int imm_create_launch(nalo_ctx* c, const float4* dI, int n, const int* u, const 
 int imm_trace_launch(nalo_ctx* c, const float4* dI, int n, const float* base, const int* host_idx, const float* KRKi, const float* Kt, const float* aff,
                      float* idmin, float* idmax, int* status, float* quality, float* lastUV, float* lastInterval);
 int imm_optimize_resident_launch(nalo_ctx* c, const float4* const* dI, int W, const float K[4], const float* Rt, const float* aff, int n, const int* sel, const float* res, size_t N,
-                                 int minObs, int* result, float* idepth_out, uint8_t* res_in);
+                                 int minObs, int* result, float* idepth_out, uint8_t* res_in, const int* n_dev = nullptr);
 int imm_optimize_launch(nalo_ctx* c, const float4* const* dI, int W, const float K[4], const float* Rt, const float* aff, int n, const int* host, const float* base,
                         int minObs, int* result, float* idepth_out, uint8_t* res_in);
 int dist_make_launch(nalo_ctx* c, const float4* pt_geo, const uint8_t* pt_flags, const int* blk_host, int Ppad, int frame, const float* KRKi, const float* Kt, uint8_t* seed, float* out);
+// the selection loop of activatePointsMT over the resident set (nalo_imm_resident_activate)
+constexpr unsigned kActIdxBits = 27, kActIdxMask = (1u << kActIdxBits) - 1, kActIdxMaxN = kActIdxMask;   // key = host << 27 | index: NALO_MAX_WINDOW = 16 hosts
+constexpr int kActFirstRounds = 12, kActMaxRounds = 768;                    // rounds enqueued before the host looks: 12, then 48, 192, 768, 768, ...
+struct ActParams {
+    int n, W, frame, w1, h1, cw, ch;
+    float minActDist;
+    const float *res, *type, *KRKi, *Kt, *D0; const int* flagged;               // res: the resident block (N = n entries per array); flagged[W]
+    int* fate; uint4* rec; uint2* items;                                        // rec[i] = {U | V << 16, key, need, cell} (need = kActNoRec: no survivor); items: {pixel, key} by cell
+    int *cell_off, *cell_fill, *stats;                                          // cell_off[cw*ch + 1]: counts, then offsets; stats: survivors, accepted, rejected by an earlier point, rounds
+};
+int act_launch(nalo_ctx* c, const ActParams& P, bool first, int rounds, int* ctr, int* cnt, int* sel);
 int pixsel_hists_launch(nalo_ctx* c, const float* absg0, float* ths, float* thsSmoothed);
 // host_ba.hip: nalo_trk_set_ref_from_window's inputs gathered from the window on c->stream ({Ku | Kv | new_idepth | HdiF}, *n each, holes included)
 int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
