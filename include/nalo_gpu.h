@@ -277,6 +277,41 @@ int nalo_ba_optimize_stats(nalo_ctx* ctx, int* iterations, int* rejected);
  * M, Mb, Msc, Mbsc (optional outputs) are the stitched systems. */
 int nalo_ba_marginalize_points(nalo_ctx* ctx, const uint8_t* flags, double* M, double* Mb, double* Msc, double* Mbsc);
 
+/* The point lifecycle of FullSystem::makeKeyFrame between optimize() and marginalizeFrame, resident on the device.
+ *
+ * nalo_ba_set_point_history / nalo_ba_get_point_history   what the decisions read besides the residuals, per point in submission order:
+ *     numGood          PointHessian::numGoodResiduals (FullSystem/HessianBlocks.h:452), an int at full range
+ *     last_target[2]   the window index of the frame lastResiduals[k].first targets (HessianBlocks.h:476; [0] = latest), -1 when .first == 0
+ *     last_state[2]    lastResiduals[k].second: 0 IN, 1 OOB, 2 OUTLIER
+ *   Call nalo_ba_set_point_history after nalo_ba_set_residuals. numGood NULL = zeros. last_target and last_state NULL (both) = what optimizeImmaturePoint leaves
+ *   on a freshly activated point (FullSystemOptPoint.cpp:173-199): [0] = (W-1, IN) if the residual to frame W-1 exists, else (-1, OOB); [1] alike for W-2.
+ *   The shift at keyframe insertion ([1] = [0]; [0] = (new residual, IN), FullSystem.cpp:1344-1345) is the caller's, who re-issues the window there anyway.
+ *   While the window carries a history every linearizeAll(true) - nalo_ba_linearize(fix = 1) and the final pass of nalo_ba_optimize - updates it once:
+ *   numGood += the point's residuals that end the pass active (FullSystemOptimize.cpp:63-77; isNew is never cleared in this fork, Residuals.cpp:72),
+ *   last_state[k] = state_state of the residual last_target[k] names when it took part in the pass (:172-179), last_target[k] = -1 when the pass removed
+ *   it (:187-194). nalo_ba_marginalize_frame(idx) remaps the targets (== idx -> -1, > idx -> one down: FullSystemMarginalize.cpp:174-177; read them back
+ *   before the next nalo_ba_set_points); nalo_ba_snapshot / nalo_ba_restore include the history; nalo_ba_set_points drops it.
+ *   A pointer to a residual that has been deleted is kept as -1: it compares unequal to every live residual, which is all the reference does with it. So
+ *   where last_target[0] == last_target[1] (the ABI allows it, the reference never produces it) and a pass removes that residual, BOTH become -1, where the
+ *   reference's else-if (FullSystemOptimize.cpp:191-194) would leave [1] dangling; last_state[1] is not rewritten in that case, as in the reference.
+ *
+ * nalo_ba_flag_points   removeOutliers' predicate (FullSystemOptimize.cpp:631-653) and FullSystem::flagPointsForRemoval (FullSystem.cpp:937-1031) with
+ *   PointHessian::isOOB / isInlierNew (HessianBlocks.h:484-514), one kernel. frame_flagged[W] = FrameHessian::flaggedForMarginalization. Per point
+ *   (all outputs optional, submission order): decision 0 keep, 1 drop (idepth_scaled < 0 or no residuals), 2 drop, 3 marginalise; idepth_hessian = the
+ *   float PointHessian::idepth_hessian that is compared with setting_minIdepthH_marg: H of AccumulatedSCHessianSSE::addPoint at the last accumulation
+ *   (AccumulatedSCHessian.cpp:36-50), 0 when the point had no active residual then - NOT 1 / HdiF, which is rounded twice. counts[W][4] = {kept,
+ *   drop (no residuals), drop, marginalised} of every host: the addends of flagFramesForMarginalization's in / out (FullSystemMarginalize.cpp:76-77).
+ *   idepth_hessian is that of the last accumulation: after nalo_ba_optimize its last solveSystemF's; after an explicit nalo_ba_linearize the accumulation
+ *   of that linearisation, which the call runs itself if nalo_ba_get_points / nalo_ba_accumulate_sc have not yet.
+ *   The decisions stay on the device. Needs a history (NALO_ERR_STATE without one). On a sharded window the call is local to the rank's points.
+ *
+ * nalo_ba_marginalize_flagged   nalo_ba_marginalize_points for the points nalo_ba_flag_points decided to marginalise (EnergyFunctional::marginalizePointsF,
+ *   EnergyFunctional.cpp:615-676), then dropPointsF / removePoint (:678-714) of all three removed classes on the device: no residual state crosses the bus. */
+int nalo_ba_set_point_history(nalo_ctx* ctx, const int* numGood /* P */, const int8_t* last_target /* P x 2 */, const int8_t* last_state /* P x 2 */);
+int nalo_ba_get_point_history(nalo_ctx* ctx, int* numGood, int8_t* last_target, int8_t* last_state);
+int nalo_ba_flag_points(nalo_ctx* ctx, const uint8_t* frame_flagged /* W */, uint8_t* decision /* P */, float* idepth_hessian /* P */, int* counts /* W x 4 */);
+int nalo_ba_marginalize_flagged(nalo_ctx* ctx, double* M, double* Mb, double* Msc, double* Mbsc);
+
 /* EnergyFunctional::marginalizeFrame (OptimizationBackend/EnergyFunctional.cpp:498-610), call site FullSystem::marginalizeFrame
  * (FullSystem/FullSystemMarginalize.cpp:155). Host fp64 on HM/bM: the frame `idx` (window index) is permuted to the end, its prior is added,
  * the scaled 8x8 block is inverted and eliminated by a Schur complement; HM/bM shrink to 8(W-1)+4. The frame must not host active points any more

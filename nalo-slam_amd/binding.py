@@ -32,6 +32,7 @@ EXPORTS = [
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
     "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
+    "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
@@ -109,6 +110,10 @@ def load():
     L.nalo_ba_optimize.argtypes = [vp, C.c_int, C.c_int, c_dp]
     L.nalo_ba_marginalize_points.argtypes = [vp, c_u8p, c_dp, c_dp, c_dp, c_dp]
     L.nalo_ba_marginalize_frame.argtypes = [vp, C.c_int]
+    L.nalo_ba_set_point_history.argtypes = [vp, c_ip, c_i8p, c_i8p]
+    L.nalo_ba_get_point_history.argtypes = [vp, c_ip, c_i8p, c_i8p]
+    L.nalo_ba_flag_points.argtypes = [vp, c_u8p, c_u8p, c_fp, c_ip]
+    L.nalo_ba_marginalize_flagged.argtypes = [vp, c_dp, c_dp, c_dp, c_dp]
     L.nalo_ba_get_frames.argtypes = [vp, C.POINTER(FrameState), c_dp, c_dp]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
@@ -482,6 +487,36 @@ class Context:
         n = self.n
         M, Mb, Ms, Mbs = np.zeros(n * n), np.zeros(n), np.zeros(n * n), np.zeros(n)
         self._ck(self.L.nalo_ba_marginalize_points(self.h_, _u8(np.ascontiguousarray(flags, np.uint8)), _d(M), _d(Mb), _d(Ms), _d(Mbs)))
+        return M.reshape(n, n), Mb, Ms.reshape(n, n), Mbs
+
+    def ba_set_point_history(self, num_good=None, last_target=None, last_state=None):
+        """PointHessian::numGoodResiduals [P] and lastResiduals[2] as (window index of .first or -1, .second) [P][2]; None = the defaults of the header"""
+        ng = None if num_good is None else np.ascontiguousarray(num_good, np.int32)
+        lt = None if last_target is None else np.ascontiguousarray(last_target, np.int8)
+        ls = None if last_state is None else np.ascontiguousarray(last_state, np.int8)
+        assert (ng is None or ng.shape == (self.P,)) and (lt is None or lt.shape == (self.P, 2)) and (ls is None or ls.shape == (self.P, 2))
+        self._ck(self.L.nalo_ba_set_point_history(self.h_, _i(ng), None if lt is None else lt.ctypes.data_as(c_i8p), None if ls is None else ls.ctypes.data_as(c_i8p)))
+
+    def ba_get_point_history(self):
+        ng, lt, ls = np.zeros(self.P, np.int32), np.zeros((self.P, 2), np.int8), np.zeros((self.P, 2), np.int8)
+        self._ck(self.L.nalo_ba_get_point_history(self.h_, _i(ng), lt.ctypes.data_as(c_i8p), ls.ctypes.data_as(c_i8p)))
+        return ng, lt, ls
+
+    def ba_flag_points(self, frame_flagged, outputs=True):
+        """flagPointsForRemoval on the device -> (decision [P], idepth_hessian [P], counts [W][4]); outputs=False leaves the decisions resident and returns None"""
+        ff = np.ascontiguousarray(frame_flagged, np.uint8)
+        assert ff.shape == (self.W,)
+        if not outputs:
+            self._ck(self.L.nalo_ba_flag_points(self.h_, _u8(ff), None, None, None))
+            return None
+        dec, H, cnt = np.zeros(self.P, np.uint8), np.zeros(self.P, np.float32), np.zeros((self.W, 4), np.int32)
+        self._ck(self.L.nalo_ba_flag_points(self.h_, _u8(ff), _u8(dec), _f(H), _i(cnt)))
+        return dec, H, cnt
+
+    def ba_marginalize_flagged(self):
+        n = self.n
+        M, Mb, Ms, Mbs = np.zeros(n * n), np.zeros(n), np.zeros(n * n), np.zeros(n)
+        self._ck(self.L.nalo_ba_marginalize_flagged(self.h_, _d(M), _d(Mb), _d(Ms), _d(Mbs)))
         return M.reshape(n, n), Mb, Ms.reshape(n, n), Mbs
 
     def ba_get_frames(self):

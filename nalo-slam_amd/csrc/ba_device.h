@@ -21,7 +21,9 @@ constexpr int kThDblAB = 1024, kThDblC = 256;   // setNewFrameEnergyTH: the thre
 // residual slot state byte
 enum : uint8_t { RS_STATE_MASK = 3, RS_EXISTS = 4, RS_ACTIVE = 8, RS_LINEARIZED = 16 };
 // point flags
-enum : uint8_t { PT_VALID = 1, PT_MARG = 2, PT_HAS_PRIOR = 4 };
+enum : uint8_t { PT_VALID = 1, PT_MARG = 2, PT_HAS_PRIOR = 4, PT_DROP = 8 };   // PT_MARG / PT_DROP: the resident decisions of ba_flag_points_kernel (MARGINALIZE / both DROP classes)
+// decision of flagPointsForRemoval per point (nalo_ba_flag_points)
+enum : uint8_t { DEC_KEEP = 0, DEC_DROP_NORES = 1, DEC_DROP = 2, DEC_MARGINALIZE = 3 };
 
 // precalc record (FrameFramePrecalc, reference src/FullSystem/HessianBlocks.h:80-107 + adHTdeltaF):
 //  [0..8] PRE_KRKiTll  [9..11] PRE_KtTll  [12..20] PRE_RTll_0  [21..23] PRE_tTll_0  [24,25] PRE_aff_mode  [26] PRE_b0_mode
@@ -46,6 +48,9 @@ struct BADev {
     float4* pt_acc;                             // {Hdd_accAF, bd_accAF, HdiF, bdSumF}
     float4* pt_hcd;                             // Hcd_accAF
     uint8_t* pt_ngood;
+    // point history (nalo_ba_set_point_history), NULL without one: PointHessian::numGoodResiduals and lastResiduals[2] packed in one word,
+    // byte 0 / 1 = window index of lastResiduals[0 / 1].first (int8, -1 = null), byte 2 / 3 = lastResiduals[0 / 1].second
+    int* pt_numgood; uint32_t* pt_last;
     float* pt_step;
     float* pt_backup;
     const unsigned* gate_p; unsigned* gate_err; unsigned gate_p_want;   // ba_linearize_kernel: NULL, or the gate of its precalc records (GateBlock::p_seq)
@@ -170,5 +175,9 @@ void ba_launch_load_backup(hipStream_t s, const BADev& B);
 void ba_launch_swgray(hipStream_t s, const BADev& B, const double* Rt, double* partial);
 void ba_launch_set_idepth(hipStream_t s, const BADev& B, int mode, int host_sel, double scale);
 void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, float* out);
+void ba_launch_hist_update(hipStream_t s, const BADev& B, int scrub_only);
+void ba_launch_hist_remap(hipStream_t s, const BADev& B, int idx);
+void ba_launch_flag_points(hipStream_t s, const BADev& B, unsigned frame_mask, uint8_t* decision, float* idepth_hessian, int* counts, int* counts_next);
+void ba_launch_remove_flagged(hipStream_t s, const BADev& B);
 
 }  // namespace nalo

@@ -86,6 +86,11 @@ struct BAWindow {
     bool lin_fixed = false;                                         // the last linearisation was a linearizeAll(true): rs_cpt of the IN residuals to W-1 are its centerProjectedTo
     std::vector<int> ref_kmap_h; DevBuf<int> ref_kmap; bool ref_kmap_ok = false;   // reference loop order (host, submission order) -> device slot; rebuilt after set_points
     DevBuf<float> ref_in;                                           // the gathered inputs {Ku | Kv | new_idepth | HdiF}, P each (not nalo_trk_ref_upload's block)
+    // point lifecycle (nalo_ba_set_point_history / nalo_ba_flag_points / nalo_ba_marginalize_flagged)
+    DevBuf<int> pt_numgood, snap_numgood; DevBuf<uint32_t> pt_last, snap_last;
+    bool hist_set = false, snap_hist = false;                       // the window carries a history (dev.pt_numgood / dev.pt_last are set); so did it when the snapshot was taken
+    DevBuf<uint8_t> flag_dec; DevBuf<float> flag_H; DevBuf<int> flag_counts; int flag_buf = 0;   // the decision kernel's outputs; counts: two buffers of 4 * NALO_MAX_WINDOW, the idle one zero
+    bool flagged = false;                                           // pt_flags hold the decisions of a nalo_ba_flag_points nobody has consumed yet
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -388,6 +393,7 @@ static int linearize_async(nalo_ctx* c, int mode, int fix, bool keep_th = false)
         lin_done = ps.b ? ps.b : (on_side ? w.ev_lin.e : nullptr);
         ba_launch_linearize(c->stream, w.dev, mode, fix, ps.a, lin_done);
     }
+    if (mode == 0 && fix == 1 && w.hist_set) { ProfScope ph(c, "ba_hist_update"); ba_launch_hist_update(c->stream, w.dev, 0); }     // numGoodResiduals / lastResiduals of a window that carries them (FullSystemOptimize.cpp:63-77, 169-205)
     if (th_sharded) {
         // sharded window: the threshold is the EXACT order statistic over all ranks' residuals (what one GPU holding the whole window computes): each level's
         // histogram of the three-level radix select (kernels_ba.hip) is summed across the ranks before the next level's search. Levels A and B (8 KB each) are
@@ -1070,6 +1076,7 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
     D.rs_state = w.rs_state.p; D.rs_energy = w.rs_energy.p; D.rs_jp0 = w.rs_jp0.p; D.rs_jp1 = w.rs_jp1.p; D.rs_cpt = w.rs_cpt.p; D.rs_pp0 = w.rs_pp0.p; D.rs_pp1 = w.rs_pp1.p; D.en_new = w.en_new.p;
     D.top_partial = w.top_partial.p; D.sc_partial = w.sc_partial.p;
     w.points_set = true; w.res_set = false; w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false;
+    w.hist_set = false; w.flagged = false; D.pt_numgood = nullptr; D.pt_last = nullptr;           // a history belongs to the points it was set for
     return NALO_OK;
 }
 
@@ -1344,12 +1351,11 @@ int nalo_set_settings(nalo_ctx* c, const nalo_settings* in) {
     return NALO_OK;
 }
 
-int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, double* Mb, double* Msc, double* Mbsc) {
-    NALO_BA_READY("nalo_ba_marginalize_points")
-    if (!flags) return fail(c, NALO_ERR_ARG, "nalo_ba_marginalize_points: flags required");
-    const int n = w.n, W = w.W;
-    for (int p = 0; p < w.P; ++p) { const int d = w.p2d[p]; if (flags[p] && (w.flags_h[d] & PT_VALID)) w.flags_h[d] |= PT_MARG; }
-    NALO_HIP(c, hipMemcpyAsync(w.pt_flags.p, w.flags_h.data(), w.Ppad, hipMemcpyHostToDevice, c->stream));
+// marginalizePointsF for the points whose device flags carry PT_MARG (EnergyFunctional.cpp:615-669): what nalo_ba_marginalize_points and
+// nalo_ba_marginalize_flagged share
+static int marginalize_marked(nalo_ctx* c, double* M, double* Mb, double* Msc, double* Mbsc) {
+    BAWindow& w = *c->ba;
+    const int n = w.n;
     int rc = linearize_async(c, 2, 0); if (rc) return rc;                                   // relinearise + fixLinearizationF + addPoint<2>
     rc = sc_async(c, 0, kIdepthFixPriorMargFac, 1); if (rc) return rc;                      // priorF *= margFac; addPoint(p, false)
     rc = stitch_and_fetch(c, true, true); if (rc) return rc;
@@ -1361,12 +1367,130 @@ int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, dou
     for (int i = 0; i < n; ++i) w.bM[i] += kMargWeightFac * (mb[i] - mbs[i]);
     if (M) std::memcpy(M, m.data(), m.size() * 8); if (Mb) std::memcpy(Mb, mb.data(), n * 8);
     if (Msc) std::memcpy(Msc, ms.data(), ms.size() * 8); if (Mbsc) std::memcpy(Mbsc, mbs.data(), n * 8);
+    return NALO_OK;
+}
+
+int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, double* Mb, double* Msc, double* Mbsc) {
+    NALO_BA_READY("nalo_ba_marginalize_points")
+    if (!flags) return fail(c, NALO_ERR_ARG, "nalo_ba_marginalize_points: flags required");
+    const int W = w.W;
+    for (int p = 0; p < w.P; ++p) { const int d = w.p2d[p]; if (flags[p] && (w.flags_h[d] & PT_VALID)) w.flags_h[d] |= PT_MARG; }
+    NALO_HIP(c, hipMemcpyAsync(w.pt_flags.p, w.flags_h.data(), w.Ppad, hipMemcpyHostToDevice, c->stream));
+    w.flagged = false;                                              // the upload replaced whatever nalo_ba_flag_points left
+    int rc = marginalize_marked(c, M, Mb, Msc, Mbsc); if (rc) return rc;
     // removePoint: drop the points and all their residuals
     std::vector<uint8_t> st((size_t)W * w.Ppad);
     NALO_HIP(c, hipMemcpy(st.data(), w.rs_state.p, st.size(), hipMemcpyDeviceToHost));
     for (int d = 0; d < w.Ppad; ++d) if (w.flags_h[d] & PT_MARG) { w.flags_h[d] = 0; for (int t = 0; t < W; ++t) st[(size_t)t * w.Ppad + d] = 0; }
     NALO_HIP(c, hipMemcpy(w.rs_state.p, st.data(), st.size(), hipMemcpyHostToDevice));
     NALO_HIP(c, hipMemcpy(w.pt_flags.p, w.flags_h.data(), w.Ppad, hipMemcpyHostToDevice));
+    w.have_lin = w.have_sc = false; w.lin_fixed = false;
+    return NALO_OK;
+}
+
+// ---- the point lifecycle on the device: PointHessian::numGoodResiduals / lastResiduals resident beside the points, flagPointsForRemoval as one kernel, and
+// marginalizePointsF + dropPointsF from the decisions it left (FullSystem::makeKeyFrame, FullSystem.cpp:1397, 1446-1453)
+static uint32_t pack_last(int t0, int t1, int s0, int s1) {
+    return (uint32_t)(uint8_t)(int8_t)t0 | ((uint32_t)(uint8_t)(int8_t)t1 << 8) | ((uint32_t)s0 << 16) | ((uint32_t)s1 << 24);
+}
+int nalo_ba_set_point_history(nalo_ctx* c, const int* numGood, const int8_t* last_target, const int8_t* last_state) {
+    NALO_BA_READY("nalo_ba_set_point_history")
+    if ((last_target == nullptr) != (last_state == nullptr)) return fail(c, NALO_ERR_ARG, "nalo_ba_set_point_history: last_target and last_state come together");
+    const int W = w.W; const size_t N = w.Ppad;
+    std::vector<int> ng(N, 0);
+    std::vector<uint32_t> last(N, pack_last(-1, -1, 1, 1));
+    std::vector<uint8_t> ex;                                        // the rows of the two newest frames: what optimizeImmaturePoint leaves depends on the residuals it made
+    if (!last_target) {
+        ex.resize(2 * N);
+        NALO_HIP(c, hipStreamSynchronize(c->stream));
+        NALO_HIP(c, hipMemcpy(ex.data(), w.rs_state.p + (size_t)(W - 2) * N, 2 * N, hipMemcpyDeviceToHost));
+    }
+    for (int p = 0; p < w.P; ++p) {
+        const int d = w.p2d[p];
+        if (numGood) ng[d] = numGood[p];
+        if (last_target) {
+            const int t0 = last_target[2 * p], t1 = last_target[2 * p + 1], s0 = last_state[2 * p], s1 = last_state[2 * p + 1];
+            if (t0 < -1 || t0 >= W || t1 < -1 || t1 >= W || s0 < 0 || s0 > 2 || s1 < 0 || s1 > 2) return fail(c, NALO_ERR_ARG, "nalo_ba_set_point_history: target or state out of range");
+            last[d] = pack_last(t0, t1, s0, s1);
+        } else {                                                    // FullSystemOptPoint.cpp:173-199
+            const bool e0 = ex[N + d] & RS_EXISTS, e1 = ex[d] & RS_EXISTS;
+            last[d] = pack_last(e0 ? W - 1 : -1, e1 ? W - 2 : -1, e0 ? 0 : 1, e1 ? 0 : 1);
+        }
+    }
+    NALO_HIP(c, w.pt_numgood.reserve(N)); NALO_HIP(c, w.pt_last.reserve(N));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    NALO_HIP(c, hipMemcpy(w.pt_numgood.p, ng.data(), N * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.pt_last.p, last.data(), N * 4, hipMemcpyHostToDevice));
+    w.dev.pt_numgood = w.pt_numgood.p; w.dev.pt_last = w.pt_last.p;
+    w.hist_set = true;
+    ba_launch_hist_update(c->stream, w.dev, 1);                     // slots an earlier fix pass removed are old news to this history
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+int nalo_ba_get_point_history(nalo_ctx* c, int* numGood, int8_t* last_target, int8_t* last_state) {
+    if (!c || !c->ba || !c->ba->hist_set || !c->ba->pt_numgood.p) return fail(c, NALO_ERR_STATE, "nalo_ba_get_point_history: the window carries no point history");
+    BAWindow& w = *c->ba;
+    NALO_HIP(c, hipSetDevice(c->device));
+    const size_t N = w.Ppad;
+    std::vector<int> ng(N); std::vector<uint32_t> last(N);
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    NALO_HIP(c, hipMemcpy(ng.data(), w.pt_numgood.p, N * 4, hipMemcpyDeviceToHost));
+    NALO_HIP(c, hipMemcpy(last.data(), w.pt_last.p, N * 4, hipMemcpyDeviceToHost));
+    for (int p = 0; p < w.P; ++p) {
+        const int d = w.p2d[p];
+        if (numGood) numGood[p] = ng[d];
+        if (last_target) { last_target[2 * p] = (int8_t)(last[d] & 0xFF); last_target[2 * p + 1] = (int8_t)((last[d] >> 8) & 0xFF); }
+        if (last_state) { last_state[2 * p] = (int8_t)((last[d] >> 16) & 0xFF); last_state[2 * p + 1] = (int8_t)((last[d] >> 24) & 0xFF); }
+    }
+    return NALO_OK;
+}
+
+int nalo_ba_flag_points(nalo_ctx* c, const uint8_t* frame_flagged, uint8_t* decision, float* idepth_hessian, int* counts) {
+    NALO_BA_READY("nalo_ba_flag_points")
+    if (!w.hist_set) return fail(c, NALO_ERR_STATE, "nalo_ba_flag_points: the window carries no point history (nalo_ba_set_point_history)");
+    if (!frame_flagged) return fail(c, NALO_ERR_ARG, "nalo_ba_flag_points: frame_flagged required");
+    const int W = w.W; const size_t N = w.Ppad;
+    unsigned mask = 0;
+    for (int i = 0; i < W; ++i) if (frame_flagged[i]) mask |= 1u << i;
+    // idepth_hessian is a value of the last ACCUMULATION: after an explicit nalo_ba_linearize the accumulation of that linearisation is run here if nobody has
+    // asked for it yet (as nalo_ba_get_points does); after nalo_ba_optimize it is the last solve's, which is what the reference compares
+    if (w.have_lin && !w.have_sc && w.pt_acc_on_read) { int rc = sc_async(c, 1, 1.f, 0); if (rc) return rc; }
+    if (!w.flag_counts.p) { NALO_HIP(c, w.flag_counts.reserve(8 * NALO_MAX_WINDOW)); NALO_HIP(c, hipMemsetAsync(w.flag_counts.p, 0, 8 * NALO_MAX_WINDOW * 4, c->stream)); w.flag_buf = 0; }
+    if (decision) NALO_HIP(c, w.flag_dec.reserve(N));
+    if (idepth_hessian) NALO_HIP(c, w.flag_H.reserve(N));
+    int* const cnt = w.flag_counts.p + w.flag_buf * 4 * NALO_MAX_WINDOW;
+    w.flag_buf ^= 1;
+    {
+        ProfScope ps(c, "ba_flag_points");
+        ba_launch_flag_points(c->stream, w.dev, mask, decision ? w.flag_dec.p : nullptr, idepth_hessian ? w.flag_H.p : nullptr, cnt, w.flag_counts.p + w.flag_buf * 4 * NALO_MAX_WINDOW);
+    }
+    NALO_HIP(c, hipGetLastError());
+    w.flagged = true;
+    if (!decision && !idepth_hessian && !counts) return NALO_OK;     // the decisions stay resident: nothing to wait for
+    std::vector<uint8_t> dec; std::vector<float> H;
+    if (decision) { dec.resize(N); NALO_HIP(c, hipMemcpyAsync(dec.data(), w.flag_dec.p, N, hipMemcpyDeviceToHost, c->stream)); }
+    if (idepth_hessian) { H.resize(N); NALO_HIP(c, hipMemcpyAsync(H.data(), w.flag_H.p, N * 4, hipMemcpyDeviceToHost, c->stream)); }
+    if (counts) NALO_HIP(c, hipMemcpyAsync(counts, cnt, (size_t)W * 4 * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    for (int p = 0; p < w.P && (decision || idepth_hessian); ++p) {
+        const int d = w.p2d[p];
+        if (decision) decision[p] = dec[d];
+        if (idepth_hessian) idepth_hessian[p] = H[d];
+    }
+    return NALO_OK;
+}
+
+int nalo_ba_marginalize_flagged(nalo_ctx* c, double* M, double* Mb, double* Msc, double* Mbsc) {
+    NALO_BA_READY("nalo_ba_marginalize_flagged")
+    if (!w.flagged) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_flagged: no decisions (nalo_ba_flag_points first)");
+    int rc = marginalize_marked(c, M, Mb, Msc, Mbsc); if (rc) return rc;
+    // dropPointsF / removePoint of all three removed classes on the device; only the host mirror of the point flags comes back (nalo_ba_marginalize_frame's
+    // "still hosts points" test reads it)
+    ba_launch_remove_flagged(c->stream, w.dev);
+    NALO_HIP(c, hipGetLastError());
+    NALO_HIP(c, hipMemcpyAsync(w.flags_h.data(), w.pt_flags.p, w.Ppad, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    w.flagged = false;
     w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
@@ -1407,9 +1531,14 @@ int nalo_ba_marginalize_frame(nalo_ctx* c, int idx) {
     // the frame leaves the window (:583-590; FullSystem::marginalizeFrame drops every residual that targets it and re-runs setPrecalcValues / setAdjointsF,
     // FullSystemMarginalize.cpp:155-212): the device arrays are laid out per window size, so the caller re-issues nalo_ba_set_window (+ points, residuals)
     // for the frames that remain — with the next keyframe appended, set_window extends HM/bM like insertFrame does.
+    if (w.points_set && w.hist_set) {                               // lastResiduals of the points that stay: FullSystemMarginalize.cpp:174-177 (nalo_ba_get_point_history still answers)
+        NALO_HIP(c, hipSetDevice(c->device));
+        ba_launch_hist_remap(c->stream, w.dev, idx);
+        NALO_HIP(c, hipGetLastError());
+    }
     w.frames.erase(w.frames.begin() + idx);
     w.W -= 1; w.n = 8 * w.W + 4; w.n1 = w.n + 1;
-    w.points_set = false; w.res_set = false; w.have_lin = w.have_sc = false; w.proj_valid = false; w.have_snap = false; w.lin_fixed = false;
+    w.points_set = false; w.res_set = false; w.have_lin = w.have_sc = false; w.proj_valid = false; w.have_snap = false; w.lin_fixed = false; w.flagged = false;
     w.lastX.assign(w.n, 0.0);
     w.prior_next = true;
     return NALO_OK;
@@ -1727,6 +1856,12 @@ int nalo_ba_snapshot(nalo_ctx* c) {
     NALO_HIP(c, hipMemcpyAsync(w.snap_state.p, w.rs_state.p, NS, hipMemcpyDeviceToDevice, c->stream));
     NALO_HIP(c, hipMemcpyAsync(w.snap_flags.p, w.pt_flags.p, N, hipMemcpyDeviceToDevice, c->stream));
     NALO_HIP(c, hipMemcpyAsync(w.snap_prior.p, w.pt_prior.p, N * 4, hipMemcpyDeviceToDevice, c->stream));
+    w.snap_hist = w.hist_set;
+    if (w.hist_set) {
+        NALO_HIP(c, w.snap_numgood.reserve(N)); NALO_HIP(c, w.snap_last.reserve(N));
+        NALO_HIP(c, hipMemcpyAsync(w.snap_numgood.p, w.pt_numgood.p, N * 4, hipMemcpyDeviceToDevice, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(w.snap_last.p, w.pt_last.p, N * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     w.snap_frames = w.frames; w.snap_HM = w.HM; w.snap_bM = w.bM; w.snap_flags_h = w.flags_h;
     std::memcpy(w.snap_calib, w.c_value, sizeof(w.snap_calib)); std::memcpy(w.snap_calib_scaled, w.c_value_scaled, sizeof(w.snap_calib_scaled));
@@ -1739,7 +1874,7 @@ int nalo_ba_restore(nalo_ctx* c) {
     HostTimer ht(c, "ba_restore");
     if (!w.have_snap) return fail(c, NALO_ERR_STATE, "nalo_ba_restore: no snapshot");
     const size_t N = w.Ppad, NS = (size_t)w.W * N;
-    (void)N; (void)NS;
+    (void)NS;
     w.frames = w.snap_frames; w.HM = w.snap_HM; w.bM = w.snap_bM; w.flags_h = w.snap_flags_h;
     {   // one launch: device state from the snapshot, energies zeroed, thresholds installed (a pending quantile pass is flushed first: it clears its histogram)
         int rf = flush_th(c); if (rf) return rf;
@@ -1749,6 +1884,15 @@ int nalo_ba_restore(nalo_ctx* c) {
         w.dev.frameTH = w.frameTH.p;
         ba_launch_restore(c->stream, w.dev, w.snap_geo.p, w.snap_state.p, w.snap_flags.p, w.snap_prior.p, th);
         w.th_pending = false;
+        NALO_HIP(c, hipGetLastError());
+    }
+    w.flagged = false;
+    w.hist_set = w.snap_hist;                                       // the history as the snapshot held it (none: the window is back to carrying none)
+    w.dev.pt_numgood = w.hist_set ? w.pt_numgood.p : nullptr; w.dev.pt_last = w.hist_set ? w.pt_last.p : nullptr;
+    if (w.hist_set) {
+        NALO_HIP(c, hipMemcpyAsync(w.pt_numgood.p, w.snap_numgood.p, N * 4, hipMemcpyDeviceToDevice, c->stream));
+        NALO_HIP(c, hipMemcpyAsync(w.pt_last.p, w.snap_last.p, N * 4, hipMemcpyDeviceToDevice, c->stream));
+        ba_launch_hist_update(c->stream, w.dev, 1);                 // bytes of slots a fix pass removed before the snapshot carry no news
         NALO_HIP(c, hipGetLastError());
     }
     std::memcpy(w.c_value, w.snap_calib, sizeof(w.snap_calib)); std::memcpy(w.c_value_scaled, w.snap_calib_scaled, sizeof(w.snap_calib_scaled));

@@ -1191,4 +1191,118 @@ void ba_launch_trk_ref_gather(hipStream_t s, const BADev& B, const int* kmap, fl
     ba_trk_ref_gather_kernel<<<(B.P + 255) / 256, 256, 0, s>>>(kmap, B.P, B.rs_state + last, B.rs_cpt + last, B.pt_acc, out);
 }
 
+// ------------------------------------------------------------------------------------------------ point lifecycle: history, flagPointsForRemoval, removal
+// The point history of a window that carries one (nalo_ba_set_point_history) after a linearizeAll(true), one lane per point slot, launched behind the fix pass:
+//   numGoodResiduals += the point's residuals that end the pass active (FullSystemOptimize.cpp:63-77; isNew is never cleared in this fork, Residuals.cpp:72)
+//   lastResiduals[k].second = state_state of the residual it points at, when that residual took part in the pass (:172-179: [0] first, else [1])
+//   lastResiduals[k].first = 0 when the pass removed that residual (:187-194)
+// The fix pass leaves the state bits in the byte of a slot it removes and clears RS_EXISTS (kernels_ba_lin.hip: lin_commit): a byte without RS_EXISTS and with
+// state bits IS a residual this pass removed, because this kernel zeroes every such byte once it has read it (and scrub_only = 1 zeroes the ones an earlier pass
+// without a history left, when a history is installed or restored).
+__global__ __launch_bounds__(256) void ba_hist_update_kernel(BADev B, int scrub_only) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= B.Ppad) return;
+    const bool valid = (B.pt_flags[d] & PT_VALID) != 0;
+    const uint32_t last = B.pt_last[d];
+    int lt[2] = {(int)(int8_t)(last & 0xFF), (int)(int8_t)((last >> 8) & 0xFF)};
+    uint32_t ls[2] = {(last >> 16) & 0xFF, (last >> 24) & 0xFF};
+    int nact = 0;
+    for (int t = 0; t < B.W; ++t) {                                    // t-major slots: every load is coalesced
+        const size_t si = (size_t)t * B.Ppad + d;
+        const uint8_t st = B.rs_state[si];
+        const bool removed = !(st & RS_EXISTS) && (st & RS_STATE_MASK);
+        if (removed) B.rs_state[si] = 0;
+        if (scrub_only || !valid) continue;
+        const bool took_part = removed || ((st & RS_EXISTS) && !(st & RS_LINEARIZED));
+        if ((st & RS_EXISTS) && (st & RS_ACTIVE)) ++nact;
+        if (!took_part) continue;
+        if (lt[0] == t) ls[0] = st & RS_STATE_MASK; else if (lt[1] == t) ls[1] = st & RS_STATE_MASK;
+        if (removed) { if (lt[0] == t) lt[0] = -1; if (lt[1] == t) lt[1] = -1; }      // a pointer to a deleted residual equals nothing any more: null
+    }
+    if (scrub_only || !valid) return;
+    B.pt_numgood[d] += nact;
+    B.pt_last[d] = (uint32_t)(uint8_t)(int8_t)lt[0] | ((uint32_t)(uint8_t)(int8_t)lt[1] << 8) | (ls[0] << 16) | (ls[1] << 24);
+}
+void ba_launch_hist_update(hipStream_t s, const BADev& B, int scrub_only) { ba_hist_update_kernel<<<(B.Ppad + 255) / 256, 256, 0, s>>>(B, scrub_only); }
+
+// FullSystem::marginalizeFrame's remap of lastResiduals (FullSystemMarginalize.cpp:174-177) for the window indices: == idx -> null, > idx -> one down
+__global__ __launch_bounds__(256) void ba_hist_remap_kernel(uint32_t* __restrict__ pt_last, int n, int idx) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n) return;
+    uint32_t last = pt_last[d];
+    for (int k = 0; k < 2; ++k) {
+        int t = (int)(int8_t)((last >> (8 * k)) & 0xFF);
+        if (t == idx) t = -1; else if (t > idx) --t;
+        last = (last & ~(0xFFu << (8 * k))) | ((uint32_t)(uint8_t)(int8_t)t << (8 * k));
+    }
+    pt_last[d] = last;
+}
+void ba_launch_hist_remap(hipStream_t s, const BADev& B, int idx) { ba_hist_remap_kernel<<<(B.Ppad + 255) / 256, 256, 0, s>>>(B.pt_last, B.Ppad, idx); }
+
+// flagPointsForRemoval (FullSystem.cpp:937-1031) with PointHessian::isOOB / isInlierNew (HessianBlocks.h:484-514), one lane per point slot; the first clause also
+// is removeOutliers' (FullSystemOptimize.cpp:631-653). A 256-point block holds one host, so "host flagged" is uniform; the flagged frames travel as a bit mask.
+// idepth_hessian is the float H of AccumulatedSCHessianSSE::addPoint (AccumulatedSCHessian.cpp:36-50), rebuilt from the stored addends of the last accumulation
+// (Hdd_accAF + priorF, one float add, floor 1e-10; 0 when the point had no active residual: HdiF = 0). The decision stays in pt_flags (PT_MARG / PT_DROP);
+// counts[h] = {kept, drop_nores, drop, marginalised}: ballot + popcount, one integer atomic per wave and class. The first workgroup zeroes the counts of the
+// NEXT call (two buffers), so the path holds no fill.
+__global__ __launch_bounds__(256) void ba_flag_points_kernel(BADev B, unsigned frame_mask, uint8_t* __restrict__ decision, float* __restrict__ idepth_hessian,
+                                                             int* __restrict__ counts, int* __restrict__ counts_next) {
+    const int d = blockIdx.x * kBlk + threadIdx.x;                      // grid = nblocks: d < Ppad
+    if (blockIdx.x == 0 && threadIdx.x < 4 * NALO_MAX_WINDOW) counts_next[threadIdx.x] = 0;
+    const int h = B.blk_host[blockIdx.x];
+    const bool host_flagged = (frame_mask >> h) & 1u;
+    const uint8_t pf = B.pt_flags[d];
+    const bool valid = (pf & PT_VALID) != 0;
+    int nres = 0, visInToMarg = 0;
+    for (int t = 0; t < B.W; ++t) {
+        const uint8_t st = B.rs_state[(size_t)t * B.Ppad + d];
+        if (!(st & RS_EXISTS)) continue;
+        ++nres;
+        if ((st & RS_STATE_MASK) == 0 && ((frame_mask >> t) & 1u)) ++visInToMarg;
+    }
+    const float4 pa = B.pt_acc[d];
+    float H = 0.f;
+    if (pa.z != 0.f) { H = pa.x + B.pt_prior[d]; if (H < 1e-10f) H = 1e-10f; }
+    int dec = DEC_KEEP;
+    if (valid) {
+        const float idepth_scaled = kScaleIdepth * B.pt_geo[d].z;
+        const int numGood = B.pt_numgood[d];
+        const uint32_t last = B.pt_last[d];
+        const int s0 = (last >> 16) & 0xFF, s1 = (last >> 24) & 0xFF;
+        if (idepth_scaled < 0 || nres == 0) dec = DEC_DROP_NORES;
+        else {
+            bool oob = false;                                           // isOOB, the four clauses in their order
+            if (nres >= kMinGoodActiveResForMarg && numGood > kMinGoodResForMarg + 10 && nres - visInToMarg < kMinGoodActiveResForMarg) oob = true;
+            else if (s0 == 1) oob = true;
+            else if (nres < 2) oob = false;
+            else if (s0 == 2 && s1 == 2) oob = true;
+            if (oob || host_flagged) {
+                const bool inlier = nres >= kMinGoodActiveResForMarg && numGood >= kMinGoodResForMarg;      // isInlierNew
+                dec = (inlier && H > kMinIdepthHMarg) ? DEC_MARGINALIZE : DEC_DROP;
+            }
+        }
+        B.pt_flags[d] = (uint8_t)((pf & ~(PT_MARG | PT_DROP)) | (dec == DEC_MARGINALIZE ? PT_MARG : (dec == DEC_KEEP ? 0 : PT_DROP)));
+    }
+    if (decision) decision[d] = (uint8_t)dec;
+    if (idepth_hessian) idepth_hessian[d] = H;
+    const bool lead = (threadIdx.x & 63) == 0;
+#pragma unroll
+    for (int cls = 0; cls < 4; ++cls) {
+        const int n = __popcll(__ballot(valid && dec == cls));
+        if (lead && n) atomicAdd(&counts[h * 4 + cls], n);
+    }
+}
+void ba_launch_flag_points(hipStream_t s, const BADev& B, unsigned frame_mask, uint8_t* decision, float* idepth_hessian, int* counts, int* counts_next) {
+    ba_flag_points_kernel<<<B.nblocks, kBlk, 0, s>>>(B, frame_mask, decision, idepth_hessian, counts, counts_next);
+}
+
+// dropPointsF / removePoint of the flagged points (EnergyFunctional.cpp:678-714): the slots and the flags of every point that carries a decision go
+__global__ __launch_bounds__(256) void ba_remove_flagged_kernel(BADev B) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= B.Ppad || !(B.pt_flags[d] & (PT_MARG | PT_DROP))) return;
+    for (int t = 0; t < B.W; ++t) B.rs_state[(size_t)t * B.Ppad + d] = 0;
+    B.pt_flags[d] = 0;
+}
+void ba_launch_remove_flagged(hipStream_t s, const BADev& B) { ba_remove_flagged_kernel<<<(B.Ppad + 255) / 256, 256, 0, s>>>(B); }
+
 }  // namespace nalo

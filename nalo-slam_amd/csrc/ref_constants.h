@@ -34,6 +34,8 @@
     X(int, kForceAcceptStep, "setting_forceAceptStep", 1)                                            \
     X(float, kMinIdepthHAct, "setting_minIdepthH_act", 100.0f)                                       \
     X(float, kMinIdepthHMarg, "setting_minIdepthH_marg", 50.0f)                                      \
+    X(int, kMinGoodActiveResForMarg, "setting_minGoodActiveResForMarg", 3)                           \
+    X(int, kMinGoodResForMarg, "setting_minGoodResForMarg", 4)                                       \
     X(int, kMinFrames, "setting_minFrames", 5)                                                       \
     X(int, kMaxFrames, "setting_maxFrames", 7)                                                       \
     X(int, kMaxOptIterations, "setting_maxOptIterations", 6)                                         \

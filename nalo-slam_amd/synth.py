@@ -101,7 +101,7 @@ class Scene:
 
 
 def make_window(w=640, h=480, W=8, P=2000, seed=7, n_extra=1, idepth_noise=0.01, f=None,
-                step_z=0.8, yaw_deg=0.5, full_graph=True, pose_seed_scene=20240601, min_grad2=50.0, freq_scale=1.0) -> Window:
+                step_z=0.8, yaw_deg=0.5, full_graph=True, pose_seed_scene=20240601, min_grad2=50.0, freq_scale=1.0, step_x=0.03) -> Window:
     f = float(f if f is not None else 0.52 * w)
     K = (f, f, (w - 1) / 2.0, (h - 1) / 2.0)
     scene = Scene(pose_seed_scene, freq_scale=freq_scale)
@@ -109,7 +109,7 @@ def make_window(w=640, h=480, W=8, P=2000, seed=7, n_extra=1, idepth_noise=0.01,
     w2c = np.zeros((F, 3, 4))
     for i in range(F):
         R_c2w = so3_exp(np.array([0.0, np.deg2rad(yaw_deg) * i, 0.0]))
-        t_c2w = np.array([0.03 * i, 0.0, step_z * i])
+        t_c2w = np.array([step_x * i, 0.0, step_z * i])
         c2w = np.concatenate([R_c2w, t_c2w[:, None]], axis=1)
         w2c[i] = se3_inv(c2w)
     imgs = np.zeros((F, h, w), np.float32)
