@@ -54,6 +54,16 @@ int nalo_levels(nalo_ctx* ctx);
 int nalo_sync(nalo_ctx* ctx);
 void* nalo_stream(nalo_ctx* ctx);                 /* hipStream_t every kernel of this ctx is launched on */
 
+/* For tests only: arm one injected failure on this context. The count-th matching event from now fails once and the injector disarms itself;
+ * count = 0 disarms. NALO_ERR_ARG for a null context, an unknown `what` or a negative count. Needs no window and makes no device call.
+ *   NALO_INJECT_LM_LOST_BLOCK  a persistent LM launch of nalo_trk_track reports a lost workgroup after it has completed: the frame is redone by
+ *                              the host-driven loop, which the context keeps to from then on;
+ *   NALO_INJECT_GATED_SOLVE    a solve of nalo_ba_optimize that has pre-launched its back-substitution fails between the pre-launch and its gates.
+ * The library reads one environment variable, NALO_HOST_TIMING, once per context in nalo_create (host-side accounting printed at nalo_destroy). */
+#define NALO_INJECT_LM_LOST_BLOCK 1
+#define NALO_INJECT_GATED_SOLVE   2
+int nalo_test_inject(nalo_ctx* ctx, int what, int count);
+
 /* ------------------------------------------------------------------------------------------------
  * Settings of the reference that change the arithmetic of this path (util/settings.cpp). Defaults = the reference's; nalo_set_settings before
  * nalo_ba_set_window / nalo_trk_track. Everything else in settings.cpp that this path reads is a compile-time constant here, as it is never changed by

@@ -23,9 +23,10 @@ class FrameState(C.Structure):
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_int)
+INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what` (include/nalo_gpu.h)
 
 EXPORTS = [
-    "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream",
+    "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
     "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download",
     "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
@@ -77,6 +78,7 @@ def load():
     L.nalo_sync.argtypes = [vp]
     L.nalo_stream.argtypes = [vp]
     L.nalo_stream.restype = vp
+    L.nalo_test_inject.argtypes = [vp, C.c_int, C.c_int]
     L.nalo_frame_upload.argtypes = [vp, C.c_int, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_frame_upload_async.argtypes = [vp, C.c_int, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_frame_wait.argtypes = [vp, C.c_int]
@@ -264,6 +266,10 @@ class Context:
 
     def sync(self):
         self._ck(self.L.nalo_sync(self.h_))
+
+    def test_inject(self, what, count=1):
+        """tests only: the count-th matching event from now fails once (nalo_test_inject); count 0 disarms"""
+        self._ck(self.L.nalo_test_inject(self.h_, what, count))
 
     # ---- frames
     def frame_upload(self, slot, img, mask=None, bgr=None, gammaB=None):

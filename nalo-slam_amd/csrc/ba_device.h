@@ -158,7 +158,7 @@ void ba_launch_restore(hipStream_t s, const BADev& B, const float4* geo, const u
 void ba_launch_reduce(hipStream_t s, const BADev& B, const int* host_blk, int NPL, double* acc13, double* misc, double* G, bool top, bool sc,
                       const float* step_partial, int step_blocks, double* step_out, bool with_th, double* pub, double seq, unsigned* ticket);
 void ba_launch_resub_step(hipStream_t s, const BADev& B, float stepfacD, float* partial, const XadArg& karg, bool karg_is_x);
-int ba_launch_stitch(hipStream_t s, const StitchDev& D, bool top, bool sc, double* mapped, int ntail, double seq);
+int ba_launch_stitch(hipStream_t s, const StitchDev& D, size_t* lds_allowed, bool top, bool sc, double* mapped, int ntail, double seq);
 void ba_launch_resub(hipStream_t s, const BADev& B, const XadArg& karg, bool karg_is_x);
 void ba_launch_resub_step_gated(hipStream_t s, const BADev& B, float stepfacD, float* partial, const GateArg& gate);
 void ba_launch_pull(hipStream_t s, float* dst, const float* src_mapped, int n);

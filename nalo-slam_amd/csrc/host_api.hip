@@ -29,6 +29,7 @@ int nalo_create(nalo_ctx** out, int device, int w, int h, int levels, const floa
     if (hipSetDevice(device) != hipSuccess) return NALO_ERR_NO_DEVICE;
     nalo_ctx* c = new nalo_ctx();
     c->device = device; c->w = w; c->h = h;
+    c->host_timing = std::getenv("NALO_HOST_TIMING") != nullptr;          // the one environment variable the library reads, here and nowhere else
     c->levels = levels > 0 ? levels : pyr_levels_rule(w, h);
     if (c->levels > NALO_MAX_LEVELS) { delete c; return NALO_ERR_ARG; }
     for (int l = 0; l < c->levels; ++l) { c->wl[l] = w >> l; c->hl[l] = h >> l; }
@@ -48,7 +49,7 @@ int nalo_create(nalo_ctx** out, int device, int w, int h, int levels, const floa
 
 void nalo_destroy(nalo_ctx* c) {
     if (!c) return;
-    if (std::getenv("NALO_HOST_TIMING")) for (auto& kv : c->host_t) fprintf(stderr, "[nalo host] %-28s calls=%6ld total=%10.1f us  avg=%8.2f us\n", kv.first.c_str(), kv.second.second, kv.second.first, kv.second.first / std::max(1L, kv.second.second));
+    if (c->host_timing) for (auto& kv : c->host_t) fprintf(stderr, "[nalo host] %-28s calls=%6ld total=%10.1f us  avg=%8.2f us\n", kv.first.c_str(), kv.second.second, kv.second.first, kv.second.first / std::max(1L, kv.second.second));
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rccl_release(c);
@@ -100,6 +101,14 @@ int nalo_constants_device(nalo_ctx* c, int cap, double* values) {
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n && i < cap; ++i) values[i] = h[i];
     return n;
+}
+
+int nalo_test_inject(nalo_ctx* c, int what, int count) {
+    if (!c || count < 0) return NALO_ERR_ARG;
+    if (what == NALO_INJECT_LM_LOST_BLOCK) c->inject_lm_lost_block = count;
+    else if (what == NALO_INJECT_GATED_SOLVE) c->inject_gated_solve = count;
+    else return NALO_ERR_ARG;
+    return NALO_OK;
 }
 
 const char* nalo_last_error(nalo_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
@@ -484,13 +493,12 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
     int evals = 0, start_lvl = coarsestLvl;
     for (int& e : c->lm_evals_lvl) e = 0;
     // The whole pyramid descent runs in ONE persistent multi-block kernel (kernels_trk_lm.hip): ~10 us per LM evaluation against ~19 us for
-    // the host-driven loop below (a launch, a finish kernel and a polled flag per evaluation). NALO_TRK_HOST_LM=1 selects the host loop,
-    // which is also what a caller gets by driving nalo_trk_eval itself.
+    // the host-driven loop below (a launch, a finish kernel and a polled flag per evaluation), which is also what a caller gets by driving
+    // nalo_trk_eval itself.
     {
         // a fixed affine parameter changes the system the LM solves (:1140-1162): those variants live in the host loop below
-        static const bool env_host = std::getenv("NALO_TRK_HOST_LM") != nullptr;
         const bool sharded = c->trk_world > 1 && c->trk_hook;          // the persistent kernel cannot exchange sums with other GPUs: a sharded tracker runs the host-driven loop
-        const bool force_host = env_host || sharded || c->lm_host_only || c->set.affineOptModeA < 0 || c->set.affineOptModeB < 0;
+        const bool force_host = sharded || c->lm_host_only || c->set.affineOptModeA < 0 || c->set.affineOptModeB < 0;
         const int stop = 0;                                            // levels coarsestLvl..0 on the device
         if (!force_host) {
             if (c->slot_ref < 0 || slot_new < 0 || slot_new >= (int)c->slots.size() || !c->slots[slot_new].valid)

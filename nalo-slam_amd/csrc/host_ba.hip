@@ -48,6 +48,7 @@ struct BAWindow {
     bool th_pending = false;                                        // a linearize pass whose frameEnergyTH quantile has not been launched yet
     DevBuf<double> acc13, G, AD, stitched;
     StitchLayout lay = StitchLayout(0, 0);                           // of stitched and stitched_host, as nalo_ba_set_window allocated them
+    size_t stitch_lds_allowed = 48 * 1024;                           // dynamic LDS ba_stitch_kernel has been opted in to on this context's device (ba_launch_stitch raises it)
     DevBuf<unsigned> st_ticket;
     StitchDev sd{};
     HostBuf<double> ad_host;                                        // pinned staging of AD
@@ -567,7 +568,7 @@ static int stitch_and_fetch(nalo_ctx* c, bool want_top, bool want_sc, bool th_to
             if (misc_only) { if (!w.hook && !pub_in_reduce) ba_launch_publish(c->stream, w.stitched.p + L.misc, dmap + L.misc, ntail, seq, w.st_ticket.p + 1); }
             else {
                 if (small_th && th_to_host) ba_launch_th_tail(c->stream, w.frameTH.p + (W - 1), w.stitched.p + L.th);   // the stitch publishes the tail: {TH, 1.0} must be in it
-                if (ba_launch_stitch(c->stream, w.sd, top, sc, w.hook ? nullptr : dmap, ntail, seq)) return fail(c, NALO_ERR_HIP, "ba_stitch_kernel: LDS size rejected");
+                if (ba_launch_stitch(c->stream, w.sd, &w.stitch_lds_allowed, top, sc, w.hook ? nullptr : dmap, ntail, seq)) return fail(c, NALO_ERR_HIP, "ba_stitch_kernel: LDS size rejected");
                 if (top) w.stitched_top = true;
                 if (sc) w.stitched_sc = true;
             }
@@ -729,11 +730,8 @@ static int solve_system(nalo_ctx* c, int iteration, double lambda, double* x_out
     { HostTimer h2(c, "ba.solve.fetch_wait"); rc = stitch_and_fetch(c, true, true); }
     w.want_prelaunch = false;
     if (rc) return rc;
-    {   // tests: the error path BETWEEN a pre-launch and its gates (tests/test_ba_gpu.py, child process): the second solve of the process fails here, once
-        static const bool test_cancel = std::getenv("NALO_BA_TEST_GATE_CANCEL") != nullptr;
-        static int solves = 0;
-        if (test_cancel && w.resub_pre && ++solves == 2) return fail(c, NALO_ERR_HIP, "test: failure between a pre-launch and its gates");
-    }
+    // nalo_test_inject: the error path BETWEEN a pre-launch and its gates (tests/test_ba_gpu.py)
+    if (w.resub_pre && c->inject_gated_solve > 0 && --c->inject_gated_solve == 0) return fail(c, NALO_ERR_HIP, "test: failure between a pre-launch and its gates");
     HostTimer h3(c, "ba.solve.host_math");
     // H = (HL + HM + HA) with the diagonal * (1+lambda), minus Hsc/(1+lambda); b = bL + (bM + HM delta) + bA - bsc   (:795-868), then the Jacobi scaling
     // (:872-885): TWO passes over the published systems (the diagonal first: the scaling needs it), written straight into the padded, scaled matrix the

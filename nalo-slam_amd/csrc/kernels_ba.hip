@@ -755,7 +755,7 @@ __global__ __launch_bounds__(1024) void ba_stitch_kernel(StitchDev D, int mask, 
         __hip_atomic_store(&mapped[t0 + ntail], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-int ba_launch_stitch(hipStream_t s, const StitchDev& D, bool top, bool sc, double* mapped, int ntail, double seq) {
+int ba_launch_stitch(hipStream_t s, const StitchDev& D, size_t* lds_allowed, bool top, bool sc, double* mapped, int ntail, double seq) {
     const int mask = (top ? 1 : 0) | (sc ? 2 : 0);
     const size_t lds_top = (size_t)2 * (D.W - 1) * (169 + 2 * kAdMat + 104) * 8, lds_ad = (size_t)2 * D.W * D.W * kAdMat * 8;
     size_t lds_sc = (size_t)D.W * 8 * D.NPL * 8;
@@ -765,10 +765,9 @@ int ba_launch_stitch(hipStream_t s, const StitchDev& D, bool top, bool sc, doubl
     if (ad_in_lds) lds_sc += lds_stage;
     size_t lds = lds_top > lds_sc ? lds_top : lds_sc;
     if (lds < (size_t)D.W * D.W * 25 * 8) lds = (size_t)D.W * D.W * 25 * 8;
-    static size_t lds_allowed = 48 * 1024;
-    if (lds > lds_allowed) {
+    if (lds > *lds_allowed) {                                              // the opt-in holds per (device, function): the window's latch, 48 KB on a fresh one
         if (hipFuncSetAttribute((const void*)ba_stitch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
-        lds_allowed = lds;
+        *lds_allowed = lds;
     }
     ba_stitch_kernel<<<(kScSplit + kTopSplit) * D.W + 2, 1024, lds, s>>>(D, mask, ad_in_lds, mapped, ntail, seq);
     return 0;

@@ -7,7 +7,7 @@
 // publishes the partial as 8-byte {fp32 value, tag} words (agent-scope atomics: the data is the arrival flag, double-buffered by evaluation parity, bounded
 // poll); then EVERY workgroup sums the partials in a fixed order and replays the control flow on its wave 0: 8x8 LDL^T with one matrix row per lane and
 // v_readlane broadcasts, SE3::exp, accept / reject, lambda schedule, cutoff repeat, level descent - exactly the control flow of the host mirror in
-// host_api.hip (NALO_TRK_HOST_LM=1 selects that one, and so do the fixed-affine settings). The workgroups must be co-resident (no cooperative launch is
+// host_api.hip (a sharded tracker and the fixed-affine settings run that one). The workgroups must be co-resident (no cooperative launch is
 // used: 64 workgroups of 512 lanes fit 256 CUs by a wide margin; a violation - the CUs held by another context's long kernel - ends in the bounded poll, not in
 // a hang: the launch returns NALO_LM_LOST_BLOCK and nalo_trk_track redoes the frame with the host-driven loop and keeps to it for this context).
 #include "nalo_internal.h"
@@ -522,9 +522,9 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
     if (!poll_flag(c, &c->trk_out_host.p[64 + 31], P.seq)) return NALO_ERR_HIP;
     std::memcpy(out24, c->trk_out_host.p + 64, sizeof(double) * 26);
     for (int i = 0; i < 5; ++i) c->lm_evals_lvl[i] = (int)c->trk_out_host.p[64 + 26 + i];
-    static const bool test_timeout = std::getenv("NALO_LM_TEST_TIMEOUT") != nullptr;          // tests: exercise the caller's degraded path once per context
     c->trk_cfg[8] = out24[25] != 0.0;
-    if (out24[22] < 0 || (test_timeout && c->lm_launches == 1)) return NALO_LM_LOST_BLOCK;
+    if (out24[22] < 0) return NALO_LM_LOST_BLOCK;
+    if (c->inject_lm_lost_block > 0 && --c->inject_lm_lost_block == 0) return NALO_LM_LOST_BLOCK;   // nalo_test_inject: the caller's degraded path
     return NALO_OK;
 }
 

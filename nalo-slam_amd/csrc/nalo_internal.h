@@ -159,8 +159,12 @@ struct nalo_ctx {
     nalo::Initializer* init = nullptr;       // two-frame initialiser state (host_init.hip)
     nalo_settings set = {1, nalo::kAffineOptModeA, nalo::kAffineOptModeB, 1};   // util/settings.cpp:71,128-129,74
 
-    // ---- host wall-clock accounting (NALO_HOST_TIMING=1 prints it at nalo_destroy)
+    // ---- host wall-clock accounting (NALO_HOST_TIMING=1, read by nalo_create, prints it at nalo_destroy)
+    bool host_timing = false;
     std::map<std::string, std::pair<double, long>> host_t;
+
+    // ---- nalo_test_inject: the matching event that takes a count to zero fails once (0 = disarmed)
+    int inject_lm_lost_block = 0, inject_gated_solve = 0;
 
     // ---- profiling
     bool prof_on = false;
@@ -201,11 +205,10 @@ inline bool poll_flag(nalo_ctx* c, volatile double* flag, double seq) {
     }
 }
 
-struct HostTimer {                // wall-clock scope, accumulated per name; a no-op unless NALO_HOST_TIMING is set (two clock reads, a std::string and a map
-    nalo_ctx* c; const char* name; std::chrono::steady_clock::time_point t0;      // lookup per scope, ~50 scopes per keyframe, are not free on a 1.3 ms step)
-    static bool on() { static const bool v = std::getenv("NALO_HOST_TIMING") != nullptr; return v; }
-    HostTimer(nalo_ctx* ctx, const char* n) : c(ctx), name(n) { if (on()) t0 = std::chrono::steady_clock::now(); }
-    ~HostTimer() { if (!on()) return; auto& e = c->host_t[name]; e.first += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); e.second++; }
+struct HostTimer {                // wall-clock scope, accumulated per name; a no-op unless the context was created under NALO_HOST_TIMING (two clock reads, a std::string
+    nalo_ctx* c; const char* name; std::chrono::steady_clock::time_point t0;      // and a map lookup per scope, ~50 scopes per keyframe, are not free on a 1.3 ms step)
+    HostTimer(nalo_ctx* ctx, const char* n) : c(ctx), name(n) { if (c->host_timing) t0 = std::chrono::steady_clock::now(); }
+    ~HostTimer() { if (!c->host_timing) return; auto& e = c->host_t[name]; e.first += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); e.second++; }
 };
 
 struct ProfScope {               // HIP-event bracket on the ctx stream (only when profiling is enabled, and selected: nalo_profile_select)

@@ -31,6 +31,16 @@ def test_create_rejects_bad_arguments():
     assert not h.value
 
 
+def test_test_inject_rejects_bad_arguments():
+    c = binding.Context(64, 64, (50, 50, 31.5, 31.5), n_slots=1)
+    L, h = c.L, c.h_
+    assert L.nalo_test_inject(h, 0, 1) == ERR_ARG                                          # unknown `what`
+    assert L.nalo_test_inject(h, binding.INJECT_LM_LOST_BLOCK, -1) == ERR_ARG
+    assert L.nalo_test_inject(None, binding.INJECT_GATED_SOLVE, 1) == ERR_ARG              # no context
+    assert L.nalo_test_inject(h, binding.INJECT_LM_LOST_BLOCK, 0) == 0 and L.nalo_test_inject(h, binding.INJECT_GATED_SOLVE, 0) == 0
+    c.close()
+
+
 def test_frame_and_tracker_entry_points_reject_and_recover(small_window):
     win = small_window
     c = binding.Context(win.w, win.h, win.K, n_slots=2)

@@ -166,8 +166,8 @@ def test_track_recovers_pose_and_matches_oracle(ctx, small_window):
 
 def test_track_abort_and_exposure_paths(small_window):
     """trackNewestCoarse's early exit on minResForAbort (CoarseTracker.cpp:1227-1229: outputs untouched, returns false) and the affine-brightness path with
-    unequal exposures (AffLight::fromToVecExposure). Runs with whichever LM driver the process selected (persistent kernel by default, host loop
-    under NALO_TRK_HOST_LM=1)."""
+    unequal exposures (AffLight::fromToVecExposure). Runs with the persistent LM kernel, the driver of a fresh
+    unsharded context."""
     win = small_window
     c = binding.Context(win.w, win.h, win.K, n_slots=2)
     c.frame_upload(0, win.images[win.W - 1]); c.frame_upload(1, (win.images[win.W] * 1.25 + 3.0).astype(np.float32))
@@ -194,59 +194,40 @@ def test_track_abort_and_exposure_paths(small_window):
     c.close()
 
 
-_LOST_BLOCK_SCRIPT = r"""
-import sys, json, numpy as np
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests"); sys.path.insert(0, sys.argv[1] + "/oracle")
-import nalo_pkg
-nalo_pkg.load()
-from helpers import tracker_inputs
-from nalo_slam_amd import binding, synth
-win = synth.make_window(w=640, h=480, W=4, P=400, seed=7)
-c = binding.Context(win.w, win.h, win.K, n_slots=2)
-c.frame_upload(0, win.images[win.W - 1]); c.frame_upload(1, win.images[win.W])
-Ku, Kv, nid, hdi = tracker_inputs(win)
-c.trk_set_ref(0, Ku, Kv, nid, hdi)
-T0 = np.asarray(json.loads(sys.argv[2]))
-out = []
-for _ in range(2):                                   # frame 1: the launch is reported lost and redone from the host; frame 2: host loop straight away
-    ok, T, aff, lr, lf, nev = c.trk_track(1, T0, [0, 0], [0, 0], [1, 1], win.levels - 1)
-    out.append(dict(ok=int(ok), T=np.asarray(T).tolist(), aff=np.asarray(aff).tolist(), nev=int(nev)))
-c.close()
-print("RESULT " + json.dumps(out))
-"""
-
-
-def test_lost_workgroup_degrades_to_the_host_driven_loop(ctx, small_window, tmp_path):
+def test_lost_workgroup_degrades_to_the_host_driven_loop(ctx, small_window, monkeypatch, capfd):
     """Hygiene item of the round-1 review: trk_lm_kernel needs its workgroups co-resident. When one never arrives (CUs held by another context) the launch ends
     in its bounded poll and nalo_trk_track REDOES the frame with the host-driven LM loop (the same fused evaluation kernel per step - still the HIP path) and keeps
-    to it for the context. NALO_LM_TEST_TIMEOUT makes a context's first launch report the loss; the env is read once per process, hence the child process."""
-    import json, os, subprocess, sys
+    to it for the context. nalo_test_inject makes a context's next launch report the loss; NALO_HOST_TIMING is read by nalo_create, per context."""
     win = small_window
     Ku, Kv, nid, hdi = tracker_inputs(win)
     ctx.trk_set_ref(win.W - 1, Ku, Kv, nid, hdi)
     T0 = orc.se3_exp(orc.se3_log(true_rel_pose(win, win.W - 1, win.W)) * 0.8)
     ok, T, aff, lr, lf, nev = ctx.trk_track(win.W, T0, [0, 0], [0, 0], [1, 1], win.levels - 1)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = tmp_path / "lost_block.py"
-    script.write_text(_LOST_BLOCK_SCRIPT)
-    env = dict(os.environ, NALO_LM_TEST_TIMEOUT="1", NALO_HOST_TIMING="1")      # the second switch: the host-side wall-clock accounting printed at nalo_destroy
-    p = subprocess.run([sys.executable, str(script), root, json.dumps(np.asarray(T0).tolist())], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    assert "drives the tracker's LM loop from the host" in p.stderr
-    res = json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
-    for r in res:
-        assert r["ok"] == ok == 1
-        assert pose_dist(np.asarray(r["T"]), T) < 1e-5 and np.abs(np.asarray(r["aff"]) - aff).max() < 1e-3
-    assert p.stderr.count("drives the tracker's LM loop from the host") == 1          # latched: the second frame did not try the persistent kernel again
-    acct = [l for l in p.stderr.splitlines() if l.startswith("[nalo host]")]
-    assert any("trk_track" in l and "calls=     2" in l for l in acct) and any("trk_set_ref" in l for l in acct), p.stderr[-1500:]
-    # the third switch of the library: NALO_TRK_HOST_LM=1 selects the host-driven loop from the first frame on (no lost launch, no message), same poses
-    env = dict({k: v for k, v in os.environ.items() if k not in ("NALO_LM_TEST_TIMEOUT", "NALO_HOST_TIMING")}, NALO_TRK_HOST_LM="1")
-    p = subprocess.run([sys.executable, str(script), root, json.dumps(np.asarray(T0).tolist())], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stderr[-2000:]
-    assert "drives the tracker's LM loop from the host" not in p.stderr and "[nalo host]" not in p.stderr
-    for r in json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:]):
-        assert r["ok"] == 1 and pose_dist(np.asarray(r["T"]), T) < 1e-5 and np.abs(np.asarray(r["aff"]) - aff).max() < 1e-3
+    msg = "drives the tracker's LM loop from the host"
+
+    def lost_then_host():                                # frame 1: the launch is reported lost and redone from the host; frame 2: host loop straight away
+        c = binding.Context(win.w, win.h, win.K, n_slots=2)
+        c.frame_upload(0, win.images[win.W - 1]); c.frame_upload(1, win.images[win.W])
+        c.trk_set_ref(0, Ku, Kv, nid, hdi)
+        c.test_inject(binding.INJECT_LM_LOST_BLOCK)
+        capfd.readouterr()
+        errs = []
+        for _ in range(2):
+            r = c.trk_track(1, T0, [0, 0], [0, 0], [1, 1], win.levels - 1)
+            errs.append(capfd.readouterr().err)
+            assert r[0] == ok == 1
+            assert pose_dist(r[1], T) < 1e-5 and np.abs(r[2] - aff).max() < 1e-3
+        c.close()
+        return errs + [capfd.readouterr().err]
+    monkeypatch.setenv("NALO_HOST_TIMING", "1")          # the host-side wall-clock accounting printed at nalo_destroy
+    e1, e2, closing = lost_then_host()
+    assert (e1 + e2 + closing).count(msg) == 1 and msg in e1     # latched: the second frame did not try the persistent kernel again
+    acct = [l for l in closing.splitlines() if l.startswith("[nalo host]")]
+    assert any("trk_track" in l and "calls=     2" in l for l in acct) and any("trk_set_ref" in l for l in acct), closing[-1500:]
+    # a context created without the variable: the same degraded path and poses, one message on the lost frame, none after it, no accounting
+    monkeypatch.delenv("NALO_HOST_TIMING")
+    e1, e2, closing = lost_then_host()
+    assert e1.count(msg) == 1 and msg not in e2 and "[nalo host]" not in e1 + e2 + closing
 
 
 def test_sharded_tracker_sums_and_tracks_like_one_gpu(small_window):
