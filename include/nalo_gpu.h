@@ -327,7 +327,7 @@ int nalo_ba_marginalize_flagged(nalo_ctx* ctx, double* M, double* Mb, double* Ms
  * the scaled 8x8 block is inverted and eliminated by a Schur complement; HM/bM shrink to 8(W-1)+4. The frame must not host active points any more
  * (the reference asserts it: marginalise or drop them with nalo_ba_marginalize_points / by not re-submitting them). The frame leaves the window:
  * W decreases by one, nalo_ba_get_frames / nalo_ba_get_prior return the remaining frames, and the device window must be re-issued with
- * nalo_ba_set_window (+ set_points, set_residuals) before the next linearisation — FullSystem::marginalizeFrame likewise drops every residual
+ * nalo_ba_set_window (+ set_points, set_residuals), or carried with nalo_ba_carry_window, before the next linearisation — FullSystem::marginalizeFrame likewise drops every residual
  * that targets the frame and recomputes the precalc values and adjoints (:161-212). The shrunk HM/bM are handed to exactly that NEXT nalo_ba_set_window:
  * kept if it names the remaining frames, extended by a zero block if it appends one keyframe (EnergyFunctional::insertFrame, :437-442); any other size
  * resets the prior to zero.
@@ -337,6 +337,44 @@ int nalo_ba_marginalize_flagged(nalo_ctx* ctx, double* M, double* Mb, double* Ms
  * it calls nalo_ba_set_prior after every nalo_ba_set_window. */
 int nalo_ba_marginalize_frame(nalo_ctx* ctx, int idx);
 int nalo_ba_set_prior_carry(nalo_ctx* ctx, int on);
+
+/* The seam between two keyframes on the device: the window re-issued from what is resident, instead of nalo_ba_get_* -> nalo_ba_set_window + nalo_ba_set_points
+ * + nalo_ba_set_residuals + nalo_ba_set_point_history. The result is, in everything a caller can read or compute from, the window that re-issue would build.
+ *
+ * nalo_ba_carry_window(ctx, entering, insert_activated)
+ *   Frames    those nalo_ba_get_frames returns now, in their order - what remains after any number of nalo_ba_marginalize_frame calls since the last issue -
+ *             with their host state (evalPT, state, state_zero, frameEnergyTH); `entering` (NULL: none) is appended as the newest frame
+ *             (EnergyFunctional::insertFrame, EnergyFunctional.cpp:429-461). HM / bM are always kept, and extended by a zero block for an entering frame;
+ *             the CalibHessian continues (value and value_zero as they are). Adjoints and precalc values are recomputed as nalo_ba_set_window does.
+ *             More than NALO_MAX_WINDOW frames: NALO_ERR_ARG. An entering slot without a pyramid: NALO_ERR_STATE.
+ *   Points    the valid points in their old submission order, renumbered densely, each with u, v, idepth, idepth_zero, color, weights and its depth-prior flag.
+ *             A frame that left must host no valid point (nalo_ba_marginalize_frame sees to it on its first call; NALO_ERR_STATE otherwise).
+ *   Residuals a carried point keeps the residual to target t iff it has one now and t remains; with an entering frame every carried point gets one to it
+ *             (FullSystem.cpp:1335-1348). All come out as nalo_ba_set_residuals leaves them (IN, energies zero, resetOOB); accumulators, steps, backups and
+ *             relBS are zero as after nalo_ba_set_points; decisions of a nalo_ba_flag_points nobody consumed are dropped.
+ *   History   (a window that carries one) numGood and both last_* pairs are carried - the targets as nalo_ba_marginalize_frame remapped them -, and with an
+ *             entering frame shifted: [1] = [0]; [0] = (W_new - 1, IN) (FullSystem.cpp:1344-1345).
+ *   insert_activated != 0   step 4 of activatePointsMT (FullSystem.cpp:893-917) with the tail of optimizeImmaturePoint (FullSystemOptPoint.cpp:170-200) for the
+ *             last nalo_imm_resident_activate that was asked for its optimisation outputs: every selected point k with result[k] == 1 becomes a window point
+ *             behind the carried ones, in toOptimize order; host = its host_idx; u, v, color, weights from the resident immature record (read on the device);
+ *             idepth = idepth_zero = idepth_out[k]; no depth prior; a residual to t iff res_in[k][t]; the history of a fresh point (numGood 0, the defaults
+ *             above). The resident immature set is not modified. The pending result is consumed by this call and dropped by nalo_imm_resident_set, a later
+ *             activation, nalo_ba_set_window and nalo_ba_set_points. NALO_ERR_STATE when none is pending, when the window's frames (or points) changed since
+ *             the activation, or together with an entering frame (the reference appends the frame, activates, then inserts: two calls).
+ *   Layout    exactly nalo_ba_set_points' for the new point list (one shared function): slot order per host in stable Hilbert-cell order - a new point is merged
+ *             between carried ones -, padding, block tables, work distribution, partial sizes; nalo_ba_get_launch_config reports it. nalo_trk_set_ref_from_window's
+ *             map and the snapshot are invalidated: nalo_ba_restore after a carry gives NALO_ERR_STATE.
+ *   Allowed with points and residuals set, or with them unset only because nalo_ba_marginalize_frame was called since the last issue (the device arrays still
+ *             stand). Refused with NALO_ERR_STATE on a sharded window and on a context whose exchange failed. A refusal leaves the window as it was.
+ *   Bus       per call the two integer maps and the block tables go down in stream-ordered copies from pinned memory: 4 bytes per new slot for the map,
+ *             under 5 with the tables (at most 8). Nothing comes up, no float array of points or residuals goes either way, and the call does not wait for
+ *             the stream. In steady state it allocates nothing: the gather writes a second set of buffers that then changes places with the first.
+ * nalo_ba_carry_map   old_p[p_new] = the submission index before the last carry, or -(k + 1) for the k-th selected point of the activation: what the caller
+ *             re-keys its PointHessian objects with.
+ * nalo_ba_carry_last  {points carried, points inserted, P_new, Ppad_new} of the last carry. */
+int nalo_ba_carry_window(nalo_ctx* ctx, const nalo_frame_state* entering /* NULL: none */, int insert_activated);
+int nalo_ba_carry_map(nalo_ctx* ctx, int* old_p /* P_new */);
+int nalo_ba_carry_last(nalo_ctx* ctx, int stats[4]);
 
 /* read-back of window state (host pointers, any may be NULL) */
 int nalo_ba_get_frames(nalo_ctx* ctx, nalo_frame_state* frames /* W */, double* worldToCam /* W x 12 PRE_worldToCam */,

@@ -34,6 +34,7 @@ EXPORTS = [
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
     "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
     "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
+    "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
@@ -117,6 +118,9 @@ def load():
     L.nalo_ba_flag_points.argtypes = [vp, c_u8p, c_u8p, c_fp, c_ip]
     L.nalo_ba_marginalize_flagged.argtypes = [vp, c_dp, c_dp, c_dp, c_dp]
     L.nalo_ba_get_frames.argtypes = [vp, C.POINTER(FrameState), c_dp, c_dp]
+    L.nalo_ba_carry_window.argtypes = [vp, C.POINTER(FrameState), C.c_int]
+    L.nalo_ba_carry_map.argtypes = [vp, c_ip]
+    L.nalo_ba_carry_last.argtypes = [vp, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -524,6 +528,41 @@ class Context:
         M, Mb, Ms, Mbs = np.zeros(n * n), np.zeros(n), np.zeros(n * n), np.zeros(n)
         self._ck(self.L.nalo_ba_marginalize_flagged(self.h_, _d(M), _d(Mb), _d(Ms), _d(Mbs)))
         return M.reshape(n, n), Mb, Ms.reshape(n, n), Mbs
+
+    def frame_state(self, slot, evalPT, frame_id=0, aff=(0.0, 0.0), exposure=1.0, th=8 * 8 * 8.0, state6=None):
+        """one nalo_frame_state as ba_set_window builds it without states / states_zero (FrameHessian::setEvalPT_scaled plus an optional state6)"""
+        fs = FrameState()
+        fs.slot, fs.frame_id = int(slot), int(frame_id)
+        e = np.ascontiguousarray(evalPT, np.float64).reshape(-1)
+        st = np.zeros(10)
+        st[6] = float(np.float32(1.0 / 10.0)) * float(aff[0])
+        st[7] = float(np.float32(1.0 / 1000.0)) * float(aff[1])
+        for k in range(12):
+            fs.worldToCam_evalPT[k] = e[k]
+        for k in range(10):
+            fs.state_zero[k] = st[k]
+        if state6 is not None:
+            st[:6] = state6
+        for k in range(10):
+            fs.state[k] = st[k]
+        fs.ab_exposure, fs.frameEnergyTH = float(exposure), float(th)
+        return fs
+
+    def ba_carry_window(self, entering=None, insert_activated=False):
+        """the window re-issued from what is resident (nalo_ba_carry_window): entering = a FrameState appended as the newest frame, insert_activated = the
+        pending imm_resident_activate result becomes window points -> (points carried, points inserted, P, Ppad)"""
+        self._ck(self.L.nalo_ba_carry_window(self.h_, None if entering is None else C.byref(entering), int(bool(insert_activated))))
+        st = np.zeros(4, np.int32)
+        self._ck(self.L.nalo_ba_carry_last(self.h_, _i(st)))
+        self.W += 0 if entering is None else 1
+        self.P = int(st[2])
+        return tuple(int(x) for x in st)
+
+    def ba_carry_map(self):
+        """old submission index of every point of the carried window, -(k + 1) for the k-th selected point of the activation"""
+        m = np.zeros(self.P, np.int32)
+        self._ck(self.L.nalo_ba_carry_map(self.h_, _i(m)))
+        return m
 
     def ba_get_frames(self):
         arr = (FrameState * self.W)()

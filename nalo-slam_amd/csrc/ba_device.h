@@ -150,6 +150,20 @@ struct StitchLayout {
 static_assert(StitchLayout(21, 2).npub - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 && StitchLayout(21, 2).th - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 - 2,
               "StitchLayout and ba_reduce_kernel's tail disagree");
 
+// Operands of ba_carry_kernel (kernels_ba_carry.hip): the old window's arrays (o_*), the second set they are gathered into, what is zeroed beside them, and the
+// pending activation's rows. ng / last (and o_ng / o_last) are NULL for a window without a history; imm / a_* are read only where src names a selected point.
+struct CarryDev {
+    const int* src;                             // [Ppad_new]: old slot, -1 padding, -(k + 2) the k-th selected point
+    int trow[16];                               // [W_new]: old residual row, -1 the entering frame
+    int W_new, Ppad_new, Ppad_old, enter;
+    const float4 *o_geo, *o_col0, *o_col1, *o_w0, *o_w1; const float* o_prior; const uint8_t *o_flags, *o_state; const int* o_ng; const uint32_t* o_last;
+    float4 *geo, *col0, *col1, *w0, *w1; float* prior; uint8_t *flags, *state; int* ng; uint32_t* last;
+    float4 *acc, *hcd; float *step, *backup, *relbs, *relbs2; uint8_t* ngood; float2* energy; float4 *jp0, *jp1, *cpt;
+    const float* imm; int immN;                 // the resident immature block ([30][immN], host_api.hip) and its size
+    const int* a_sel; const float* a_idepth; const uint8_t* a_in;   // selected indices, idepth_out, res_in [k][W_new] of the pending activation
+};
+void ba_launch_carry(hipStream_t s, const CarryDev& A, int nblocks);
+
 // Launchers of kernels_ba.hip and kernels_ba_lin.hip
 void ba_launch_sc(hipStream_t s, const BADev& B, int T, int shift, float priorScaleMarg, int margOnly);
 void ba_launch_linearize(hipStream_t s, const BADev& B, int mode, int fix, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);

@@ -684,8 +684,11 @@ int nalo_imm_resident_set(nalo_ctx* c, int n, const float* u, const float* v, co
         return fail(c, NALO_ERR_ARG, "nalo_imm_resident_set: bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
     c->imm_res_n = n; c->imm_res_maxhost = -1; c->imm_type_set = false;
+    c->act_pend_n = -1;                                                       // an activation result names points of the set it was made on
+    c->imm_uv_h.clear(); c->imm_host_h.clear();
     if (n == 0) return NALO_OK;
     const size_t N = (size_t)n;
+    c->imm_uv_h.assign(u, u + N); c->imm_uv_h.insert(c->imm_uv_h.end(), v, v + N); c->imm_host_h.assign(host_idx, host_idx + N);   // nalo_ba_carry_window's slot order of an inserted point
     int rc = imm_stage(c, 30 * N); if (rc) return rc;
     NALO_HIP(c, c->imm_res.reserve(30 * N + 256));
     float* hst = c->imm_host.p;

@@ -92,6 +92,15 @@ struct BAWindow {
     bool hist_set = false, snap_hist = false;                       // the window carries a history (dev.pt_numgood / dev.pt_last are set); so did it when the snapshot was taken
     DevBuf<uint8_t> flag_dec; DevBuf<float> flag_H; DevBuf<int> flag_counts; int flag_buf = 0;   // the decision kernel's outputs; counts: two buffers of 4 * NALO_MAX_WINDOW, the idle one zero
     bool flagged = false;                                           // pt_flags hold the decisions of a nalo_ba_flag_points nobody has consumed yet
+    // nalo_ba_carry_window: the second set of the buffers ba_carry_kernel gathers into (each swaps with its first-set twin when the call has launched), the integer
+    // mirrors the maps are worked out from, and the maps' pinned staging
+    DevBuf<float4> pt_geo2, pt_col0_2, pt_col1_2, pt_w0_2, pt_w1_2; DevBuf<float> pt_prior2; DevBuf<uint8_t> pt_flags2, rs_state2; DevBuf<int> pt_numgood2; DevBuf<uint32_t> pt_last2;
+    std::vector<unsigned long long> key_h;                          // Hilbert key of every device slot's point (nalo_ba_set_points' sort key without the host bits)
+    std::vector<int> row_of;                                        // the device residual row (= device host index) of every frame of `frames`: identity until a frame leaves
+    bool carry_ok = false;                                          // points and residuals are unset ONLY because nalo_ba_marginalize_frame was called: the device arrays still stand
+    unsigned frames_epoch = 0;                                      // counts the changes of the frame list (a pending activation result belongs to one value)
+    HostBuf<int> carry_host; DevBuf<int> carry_src; Event ev_carry; // [trow 16 | src Ppad | blk_host | host_blk | sc_grp | blk_order], and the device copy of [trow | src]
+    std::vector<int> carry_map_h; int carry_stats[4] = {}; bool carried = false;   // nalo_ba_carry_map / nalo_ba_carry_last of the last carry
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -895,28 +904,34 @@ using namespace nalo;
 
 extern "C" {
 
-int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const double calib[4], const double calib_zero[4]) {
-    if (!c || !frames || !calib || W < 2 || W > NALO_MAX_WINDOW) return fail(c, NALO_ERR_ARG, "nalo_ba_set_window: bad argument");
-    NALO_HIP(c, hipSetDevice(c->device));
-    if (!c->ba) c->ba = new BAWindow();
+// The frame half of a window issue, shared by nalo_ba_set_window and nalo_ba_carry_window: the frames' host state, the prior's size, the per-window buffers.
+// calib != NULL (nalo_ba_set_window): the CalibHessian starts again from it, HM / bM follow the ownership rules of the header. calib == NULL (a carry): the
+// CalibHessian continues, HM / bM are kept and - entering - extended by the zero block of EnergyFunctional::insertFrame; nothing here blocks on the stream and
+// the mapped mirror is kept when it is large enough.
+static int window_frames(nalo_ctx* c, int W, const nalo_frame_state* frames, const double* calib, const double* calib_zero, bool entering) {
     BAWindow& w = *c->ba;
-    if (w.W != W) { w.points_set = false; w.res_set = false; }
+    const bool carry = calib == nullptr;
+    for (int i = 0; i < W; ++i)
+        if (frames[i].slot < 0 || frames[i].slot >= (int)c->slots.size() || !c->slots[frames[i].slot].valid) return fail(c, NALO_ERR_STATE, "nalo_ba_set_window: frame slot has no pyramid");
+    if (!carry && w.W != W) { w.points_set = false; w.res_set = false; }
+    const int n_old = w.n;
     w.W = W; w.n = 8 * W + 4; w.n1 = w.n + 1;
     w.T = (8 * (W - 1) + 5 + 15) / 16; w.NPL = 16 * w.T;
-    // CalibHessian(): setValueScaled(K) then value_zero (HessianBlocks.h:347-361, 381-395)
-    double v[4], vz[4];
-    const double* cz = calib_zero ? calib_zero : calib;
-    v[0] = (1.0f / kScaleF) * calib[0]; v[1] = (1.0f / kScaleF) * calib[1]; v[2] = (1.0f / kScaleC) * calib[2]; v[3] = (1.0f / kScaleC) * calib[3];
-    vz[0] = (1.0f / kScaleF) * cz[0]; vz[1] = (1.0f / kScaleF) * cz[1]; vz[2] = (1.0f / kScaleC) * cz[2]; vz[3] = (1.0f / kScaleC) * cz[3];
-    calib_set_value(w, v);
-    for (int i = 0; i < 4; ++i) { w.c_value_scaled[i] = calib[i]; w.c_scaledf[i] = (float)calib[i]; w.c_value_zero[i] = vz[i]; }
-    w.c_scaledi[0] = 1.0f / w.c_scaledf[0]; w.c_scaledi[1] = 1.0f / w.c_scaledf[1];
-    w.c_scaledi[2] = -w.c_scaledf[2] / w.c_scaledf[0]; w.c_scaledi[3] = -w.c_scaledf[3] / w.c_scaledf[1];
+    if (!carry) {
+        // CalibHessian(): setValueScaled(K) then value_zero (HessianBlocks.h:347-361, 381-395)
+        double v[4], vz[4];
+        const double* cz = calib_zero ? calib_zero : calib;
+        v[0] = (1.0f / kScaleF) * calib[0]; v[1] = (1.0f / kScaleF) * calib[1]; v[2] = (1.0f / kScaleC) * calib[2]; v[3] = (1.0f / kScaleC) * calib[3];
+        vz[0] = (1.0f / kScaleF) * cz[0]; vz[1] = (1.0f / kScaleF) * cz[1]; vz[2] = (1.0f / kScaleC) * cz[2]; vz[3] = (1.0f / kScaleC) * cz[3];
+        calib_set_value(w, v);
+        for (int i = 0; i < 4; ++i) { w.c_value_scaled[i] = calib[i]; w.c_scaledf[i] = (float)calib[i]; w.c_value_zero[i] = vz[i]; }
+        w.c_scaledi[0] = 1.0f / w.c_scaledf[0]; w.c_scaledi[1] = 1.0f / w.c_scaledf[1];
+        w.c_scaledi[2] = -w.c_scaledf[2] / w.c_scaledf[0]; w.c_scaledi[3] = -w.c_scaledf[3] / w.c_scaledf[1];
+    }
     w.frames.assign(W, HostFrame());
     for (int i = 0; i < W; ++i) {
         HostFrame& f = w.frames[i];
         const nalo_frame_state& s = frames[i];
-        if (s.slot < 0 || s.slot >= (int)c->slots.size() || !c->slots[s.slot].valid) return fail(c, NALO_ERR_STATE, "nalo_ba_set_window: frame slot has no pyramid");
         f.slot = s.slot; f.frameID = s.frame_id; f.evalPT = SE3::from(s.worldToCam_evalPT);
         f.ab_exposure = s.ab_exposure; f.frameEnergyTH = s.frameEnergyTH;
         double z6[10]; std::memcpy(z6, s.state_zero, sizeof(z6));
@@ -928,15 +943,16 @@ int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const
     }
     w.dev.W = W; w.dev.w = c->w; w.dev.h = c->h;
     w.dev.fix_a = c->set.affineOptModeA < 0; w.dev.fix_b = c->set.affineOptModeB < 0; w.dev.no_th = 0;
-    NALO_HIP(c, w.th_hist.reserve(64)); NALO_HIP(c, hipMemset(w.th_hist.p, 0, 64 * 4));
-    NALO_HIP(c, w.th_buf.reserve(2 * kThDblAB)); NALO_HIP(c, hipMemset(w.th_buf.p, 0, 2 * kThDblAB * 8));      // zero = ready; ba_th_final_kernel leaves them zeroed again
+    NALO_HIP(c, w.th_hist.reserve(64)); NALO_HIP(c, w.th_buf.reserve(2 * kThDblAB));
+    if (carry) { NALO_HIP(c, hipMemsetAsync(w.th_hist.p, 0, 64 * 4, c->stream)); NALO_HIP(c, hipMemsetAsync(w.th_buf.p, 0, 2 * kThDblAB * 8, c->stream)); }
+    else { NALO_HIP(c, hipMemset(w.th_hist.p, 0, 64 * 4)); NALO_HIP(c, hipMemset(w.th_buf.p, 0, 2 * kThDblAB * 8)); }      // zero = ready; ba_th_final_kernel leaves them zeroed again
     w.dev.th_state = w.th_hist.p; w.dev.th_bufAB = w.th_buf.p;
     // HM / bM survive a nalo_ba_set_window only when that is asked for: right after nalo_ba_marginalize_frame (whose result is meant for this very call) or on a
     // context declared continuing (nalo_ba_set_prior_carry). Any other window starts from a zero prior, whatever an earlier, unrelated window left behind.
-    const bool keep_prior = w.prior_next || w.prior_carry;
+    const bool keep_prior = carry || w.prior_next || w.prior_carry;
     w.prior_next = false;
     if (!keep_prior) { w.HM.assign((size_t)w.n * w.n, 0.0); w.bM.assign(w.n, 0.0); }
-    else if (w.HM.size() == (size_t)(w.n - 8) * (w.n - 8) && w.n > 12) {
+    else if (carry ? (entering && w.HM.size() == (size_t)n_old * n_old && n_old == w.n - 8) : (w.HM.size() == (size_t)(w.n - 8) * (w.n - 8) && w.n > 12)) {
         // one frame appended to a window that carries a prior = EnergyFunctional::insertFrame (EnergyFunctional.cpp:437-442): conservativeResize, the new
         // frame's rows / columns zero
         const int no = w.n - 8;
@@ -953,70 +969,82 @@ int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const
     w.dev.th_bufC = w.stitched.p + w.lay.lo;
     w.th_lo_pending = false; w.th_pending = false; w.th_side_inflight = false;
     w.sd.M_top = w.acc13.p; w.sd.M_sc = w.G.p; w.sd.H = w.stitched.p;
-    w.stitched_host.release();                                             // a fresh mirror for every window, whatever its size
+    // a fresh mirror for every window, whatever its size; a carry keeps one that is large enough (every publication into it has been waited for by the fetch
+    // that asked for it, and the caller has cancelled a gated pre-launch: no kernel in the stream writes to it)
+    if (!carry) w.stitched_host.release();
     NALO_HIP(c, w.stitched_host.reserve(w.lay.host_size, hipHostMallocMapped));
     w.stitched_host.p[w.lay.flag] = -1.0; w.pub_seq = 0;
+    ++w.frames_epoch;
+    return NALO_OK;
+}
+// ... and what follows once the point layout of the window is known: thresholds, adjoints, precalc values
+static int window_finish(nalo_ctx* c) {
+    BAWindow& w = *c->ba;
     int rc = upload_frame_th(c); if (rc) return rc;
     rc = set_adjoints(c); if (rc) return rc;
     rc = set_precalc(c); if (rc) return rc;
-    NALO_HIP(c, hipStreamSynchronize(c->stream));
     w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
 }
 
-int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, const float* v, const float* idepth, const float* idepth_zero,
-                       const float* color, const float* weights, const int* has_prior) {
-    if (!c || !c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_ba_set_points: set the window first");
-    if (P < 0 || (P > 0 && (!host || !u || !v || !idepth || !color || !weights))) return fail(c, NALO_ERR_ARG, "nalo_ba_set_points: bad argument");
+int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const double calib[4], const double calib_zero[4]) {
+    if (!c || !frames || !calib || W < 2 || W > NALO_MAX_WINDOW) return fail(c, NALO_ERR_ARG, "nalo_ba_set_window: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    if (!c->ba) c->ba = new BAWindow();
+    BAWindow& w = *c->ba;
+    w.carry_ok = false; c->act_pend_n = -1;                                 // the frames are the caller's again: nothing resident is tied to them any more
+    int rc = window_frames(c, W, frames, calib, calib_zero, false); if (rc) return rc;
+    rc = window_finish(c); if (rc) return rc;
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    return NALO_OK;
+}
+
+// The point layout of a window, shared by nalo_ba_set_points and nalo_ba_carry_window so that the two cannot drift: from the points' hosts and sort keys to the
+// slot order, the padding, the block tables, the kernels' work distribution and the sizes of every per-point, per-slot and partial buffer (first set). The
+// window's host mirrors (P, Ppad, nblocks, host_blk_h, blk_host_h, d2p, p2d, dev.lin_sub / sc_*) are written here; the small device tables come back in `L` for
+// the caller to send its own way (blocking copies there, one pinned block and stream-ordered copies here).
+struct PointLayout { std::vector<int> grp, order; int xcd_len = 0; };
+// inside a host: HILBERT order of the 8x8-pixel cell. Any run of consecutive points then covers a compact, connected patch of the host image (a
+// Morton range can jump across a quadrant boundary), so the 64 residuals of a wave project into a small window of the target image: that window is
+// what ba_linearize_tile_kernel stages in LDS, and what keeps the gather kernel's texels in L1/L2. Sums are order independent up to rounding.
+static unsigned long long hilbert_cell_key(const nalo_ctx* c, float u, float v) {
+    unsigned hn = 1; while ((int)hn * 8 < std::max(c->w, c->h)) hn <<= 1;
+    unsigned x = std::min(hn - 1, (unsigned)std::max(0.f, u) >> 3), y = std::min(hn - 1, (unsigned)std::max(0.f, v) >> 3);
+    unsigned long long d = 0;
+    for (unsigned s = hn / 2; s > 0; s /= 2) {
+        const unsigned rx = (x & s) ? 1u : 0u, ry = (y & s) ? 1u : 0u;
+        d += (unsigned long long)s * s * ((3u * rx) ^ ry);
+        if (ry == 0) { if (rx == 1) { x = hn - 1 - x; y = hn - 1 - y; } const unsigned tmp = x; x = y; y = tmp; }
+    }
+    return d;
+}
+constexpr int kKeyHostShift = 40;                                   // sort key = host << 40 | Hilbert key of the cell
+// sorted: NULL, or the points already in the order the stable sort by key gives (a carry knows it: the old slot order IS that order for the carried points)
+static int build_point_layout(nalo_ctx* c, int P, const int* host, const unsigned long long* key, PointLayout& L, const int* sorted = nullptr) {
     BAWindow& w = *c->ba;
     const int W = w.W;
-    NALO_HIP(c, hipSetDevice(c->device));
     // sort by host (stable: keeps the caller's order inside a host, i.e. the reference's frame->points iteration order), pad each host to kBlk
     std::vector<int> cnt(W, 0);
-    for (int p = 0; p < P; ++p) { if (host[p] < 0 || host[p] >= W) return fail(c, NALO_ERR_ARG, "nalo_ba_set_points: host index out of range"); cnt[host[p]]++; }
+    for (int p = 0; p < P; ++p) cnt[host[p]]++;
     w.host_blk_h.assign(W + 1, 0);
     for (int h = 0; h < W; ++h) w.host_blk_h[h + 1] = w.host_blk_h[h] + (cnt[h] + kBlk - 1) / kBlk;
     w.nblocks = std::max(w.host_blk_h[W], 1);
-    if (w.host_blk_h[W] == 0) w.host_blk_h[W] = 0;
     w.Ppad = w.nblocks * kBlk; w.P = P;
     w.blk_host_h.assign(w.nblocks, 0);
     for (int h = 0; h < W; ++h) for (int b = w.host_blk_h[h]; b < w.host_blk_h[h + 1]; ++b) w.blk_host_h[b] = h;
     w.d2p.assign(w.Ppad, -1); w.p2d.assign(P, -1);
-    // inside a host: HILBERT order of the 8x8-pixel cell. Any run of consecutive points then covers a compact, connected patch of the host image (a
-    // Morton range can jump across a quadrant boundary), so the 64 residuals of a wave project into a small window of the target image: that window is
-    // what ba_linearize_tile_kernel stages in LDS, and what keeps the gather kernel's texels in L1/L2. Sums are order independent up to rounding.
-    unsigned hn = 1; while ((int)hn * 8 < std::max(c->w, c->h)) hn <<= 1;
-    auto hilbert = [hn](unsigned x, unsigned y) {
-        unsigned long long d = 0;
-        for (unsigned s = hn / 2; s > 0; s /= 2) {
-            const unsigned rx = (x & s) ? 1u : 0u, ry = (y & s) ? 1u : 0u;
-            d += (unsigned long long)s * s * ((3u * rx) ^ ry);
-            if (ry == 0) { if (rx == 1) { x = hn - 1 - x; y = hn - 1 - y; } const unsigned tmp = x; x = y; y = tmp; }
-        }
-        return d;
-    };
     std::vector<int> order(P);
-    for (int p = 0; p < P; ++p) order[p] = p;
-    std::vector<unsigned long long> key(P);
-    for (int p = 0; p < P; ++p) key[p] = ((unsigned long long)host[p] << 40) | hilbert(std::min(hn - 1, (unsigned)std::max(0.f, u[p]) >> 3), std::min(hn - 1, (unsigned)std::max(0.f, v[p]) >> 3));
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
+    if (sorted) std::memcpy(order.data(), sorted, (size_t)P * sizeof(int));
+    else {
+        for (int p = 0; p < P; ++p) order[p] = p;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
+    }
     std::vector<int> fill(W);
     for (int h = 0; h < W; ++h) fill[h] = w.host_blk_h[h] * kBlk;
     for (int q = 0; q < P; ++q) { const int p = order[q]; const int d = fill[host[p]]++; w.d2p[d] = p; w.p2d[p] = d; }
+    w.key_h.assign(w.Ppad, 0);
+    for (int p = 0; p < P; ++p) w.key_h[w.p2d[p]] = key[p] & ((1ull << kKeyHostShift) - 1);
     const size_t N = w.Ppad;
-    std::vector<float4> geo(N, make_float4(8.f, 8.f, 1.f, 1.f)), c0(N, make_float4(0, 0, 0, 0)), c1(N, make_float4(0, 0, 0, 0)), w0(N, make_float4(0, 0, 0, 0)), w1(N, make_float4(0, 0, 0, 0));
-    std::vector<float> prior(N, 0.f);
-    w.flags_h.assign(N, 0);
-    for (size_t d = 0; d < N; ++d) {
-        const int p = w.d2p[d];
-        if (p < 0) continue;
-        geo[d] = make_float4(u[p], v[p], idepth[p], idepth_zero ? idepth_zero[p] : idepth[p]);
-        c0[d] = make_float4(color[8 * p], color[8 * p + 1], color[8 * p + 2], color[8 * p + 3]); c1[d] = make_float4(color[8 * p + 4], color[8 * p + 5], color[8 * p + 6], color[8 * p + 7]);
-        w0[d] = make_float4(weights[8 * p], weights[8 * p + 1], weights[8 * p + 2], weights[8 * p + 3]); w1[d] = make_float4(weights[8 * p + 4], weights[8 * p + 5], weights[8 * p + 6], weights[8 * p + 7]);
-        const bool hp = has_prior && has_prior[p];
-        prior[d] = hp ? kIdepthFixPrior * kScaleIdepth * kScaleIdepth : 0.f;        // EFPoint::takeData (EnergyFunctionalStructs.cpp:79-85)
-        w.flags_h[d] = PT_VALID | (hp ? PT_HAS_PRIOR : 0);
-    }
     NALO_HIP(c, w.pt_geo.reserve(N)); NALO_HIP(c, w.pt_col0.reserve(N)); NALO_HIP(c, w.pt_col1.reserve(N)); NALO_HIP(c, w.pt_w0.reserve(N)); NALO_HIP(c, w.pt_w1.reserve(N));
     NALO_HIP(c, w.pt_acc.reserve(N)); NALO_HIP(c, w.pt_hcd.reserve(N)); NALO_HIP(c, w.pt_prior.reserve(N)); NALO_HIP(c, w.pt_step.reserve(N)); NALO_HIP(c, w.pt_backup.reserve(N));
     NALO_HIP(c, w.pt_relbs.reserve(N)); NALO_HIP(c, w.pt_relbs2.reserve(N)); NALO_HIP(c, w.en_new.reserve(N)); NALO_HIP(c, w.pt_flags.reserve(N)); NALO_HIP(c, w.pt_ngood.reserve(N));
@@ -1028,20 +1056,13 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
         // ones put up to 8 blocks of a host through one workgroup so that the NPL^2 fp64 partial is written once per group.
         w.dev.sc_split = w.nblocks <= 256 ? 4 : 1;          // measured (scripts/tune_sc.sh): beyond ~256 blocks more workgroups only add partial traffic
         w.dev.sc_bpw = w.dev.sc_split > 1 ? 1 : (w.nblocks >= 2048 ? 8 : (w.nblocks >= 1024 ? 4 : 2));
-        std::vector<int> grp(W + 1, 0);
-        for (int h = 0; h < W; ++h) grp[h + 1] = grp[h] + (w.host_blk_h[h + 1] - w.host_blk_h[h] + w.dev.sc_bpw - 1) / w.dev.sc_bpw;
-        w.dev.sc_groups = std::max(grp[W], 1);
+        L.grp.assign(W + 1, 0);
+        for (int h = 0; h < W; ++h) L.grp[h + 1] = L.grp[h] + (w.host_blk_h[h + 1] - w.host_blk_h[h] + w.dev.sc_bpw - 1) / w.dev.sc_bpw;
+        w.dev.sc_groups = std::max(L.grp[W], 1);
         NALO_HIP(c, w.sc_grp.reserve(W + 1));
-        NALO_HIP(c, hipMemcpy(w.sc_grp.p, grp.data(), (size_t)(W + 1) * 4, hipMemcpyHostToDevice));
         w.dev.sc_grp = w.sc_grp.p;
     }
     NALO_HIP(c, w.sc_partial.reserve((size_t)w.dev.sc_groups * w.dev.sc_split * (w.T * (w.T + 1) / 2) * 256));
-    NALO_HIP(c, hipMemcpy(w.pt_geo.p, geo.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_col0.p, c0.data(), N * 16, hipMemcpyHostToDevice));
-    NALO_HIP(c, hipMemcpy(w.pt_col1.p, c1.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_w0.p, w0.data(), N * 16, hipMemcpyHostToDevice));
-    NALO_HIP(c, hipMemcpy(w.pt_w1.p, w1.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_prior.p, prior.data(), N * 4, hipMemcpyHostToDevice));
-    NALO_HIP(c, hipMemcpy(w.pt_flags.p, w.flags_h.data(), N, hipMemcpyHostToDevice));
-    NALO_HIP(c, hipMemcpy(w.blk_host.p, w.blk_host_h.data(), (size_t)w.nblocks * 4, hipMemcpyHostToDevice));
-    NALO_HIP(c, hipMemcpy(w.host_blk.p, w.host_blk_h.data(), (size_t)(W + 1) * 4, hipMemcpyHostToDevice));
     {   // XCD walk lists: list x = the x-th eighth (in Morton = spatial order) of every host's blocks
         std::vector<std::vector<int>> lists(8);
         for (int h = 0; h < W; ++h) {
@@ -1057,24 +1078,69 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
         }
         size_t len = 1;
         for (auto& l : lists) len = std::max(len, l.size());
-        std::vector<int> order(8 * len, -1);
-        for (int x = 0; x < 8; ++x) for (size_t k = 0; k < lists[x].size(); ++k) order[x * len + k] = lists[x][k];
-        NALO_HIP(c, w.blk_order.reserve(order.size()));
-        NALO_HIP(c, hipMemcpy(w.blk_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice));
-        w.dev.blk_order = w.blk_order.p; w.dev.xcd_len = (int)len;
+        L.order.assign(8 * len, -1);
+        for (int x = 0; x < 8; ++x) for (size_t k = 0; k < lists[x].size(); ++k) L.order[x * len + k] = lists[x][k];
+        NALO_HIP(c, w.blk_order.reserve(L.order.size()));
+        w.dev.blk_order = w.blk_order.p; w.dev.xcd_len = (int)len; L.xcd_len = (int)len;
     }
-    NALO_HIP(c, hipMemset(w.pt_acc.p, 0, N * 16)); NALO_HIP(c, hipMemset(w.pt_hcd.p, 0, N * 16)); NALO_HIP(c, hipMemset(w.pt_step.p, 0, N * 4));
-    NALO_HIP(c, hipMemset(w.pt_backup.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs2.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_ngood.p, 0, N));
-    NALO_HIP(c, hipMemset(w.rs_state.p, 0, NS)); NALO_HIP(c, hipMemset(w.rs_energy.p, 0, NS * 8)); NALO_HIP(c, hipMemset(w.rs_jp0.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.rs_jp1.p, 0, NS * 16));
-    NALO_HIP(c, hipMemset(w.rs_cpt.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8));
+    return NALO_OK;
+}
+// the kernels' view of the first set, and what a new point list resets on the host
+static void bind_points(BAWindow& w) {
     BADev& D = w.dev;
-    D.P = P; D.Ppad = w.Ppad; D.nblocks = w.nblocks; D.blk_host = w.blk_host.p; D.host_blk = w.host_blk.p;
+    D.P = w.P; D.Ppad = w.Ppad; D.nblocks = w.nblocks; D.blk_host = w.blk_host.p; D.host_blk = w.host_blk.p;
     D.pt_geo = w.pt_geo.p; D.pt_col0 = w.pt_col0.p; D.pt_col1 = w.pt_col1.p; D.pt_w0 = w.pt_w0.p; D.pt_w1 = w.pt_w1.p; D.pt_prior = w.pt_prior.p;
     D.pt_flags = w.pt_flags.p; D.pt_acc = w.pt_acc.p; D.pt_hcd = w.pt_hcd.p; D.pt_ngood = w.pt_ngood.p; D.pt_step = w.pt_step.p; D.pt_backup = w.pt_backup.p; D.pt_relbs = w.pt_relbs.p; D.pt_relbs_next = w.pt_relbs2.p;
     D.rs_state = w.rs_state.p; D.rs_energy = w.rs_energy.p; D.rs_jp0 = w.rs_jp0.p; D.rs_jp1 = w.rs_jp1.p; D.rs_cpt = w.rs_cpt.p; D.rs_pp0 = w.rs_pp0.p; D.rs_pp1 = w.rs_pp1.p; D.en_new = w.en_new.p;
     D.top_partial = w.top_partial.p; D.sc_partial = w.sc_partial.p;
-    w.points_set = true; w.res_set = false; w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false;
-    w.hist_set = false; w.flagged = false; D.pt_numgood = nullptr; D.pt_last = nullptr;           // a history belongs to the points it was set for
+    w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false; w.flagged = false;
+    w.row_of.resize(w.W); for (int i = 0; i < w.W; ++i) w.row_of[i] = i;
+    w.carry_ok = false;
+}
+
+int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, const float* v, const float* idepth, const float* idepth_zero,
+                       const float* color, const float* weights, const int* has_prior) {
+    if (!c || !c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_ba_set_points: set the window first");
+    if (P < 0 || (P > 0 && (!host || !u || !v || !idepth || !color || !weights))) return fail(c, NALO_ERR_ARG, "nalo_ba_set_points: bad argument");
+    BAWindow& w = *c->ba;
+    const int W = w.W;
+    NALO_HIP(c, hipSetDevice(c->device));
+    for (int p = 0; p < P; ++p) if (host[p] < 0 || host[p] >= W) return fail(c, NALO_ERR_ARG, "nalo_ba_set_points: host index out of range");
+    std::vector<unsigned long long> key(P);
+    for (int p = 0; p < P; ++p) key[p] = ((unsigned long long)host[p] << kKeyHostShift) | hilbert_cell_key(c, u[p], v[p]);
+    PointLayout L;
+    { int rc = build_point_layout(c, P, host, key.data(), L); if (rc) return rc; }
+    c->act_pend_n = -1;                                               // a pending activation result was made against the points that just went
+    const size_t N = w.Ppad;
+    std::vector<float4> geo(N, make_float4(8.f, 8.f, 1.f, 1.f)), c0(N, make_float4(0, 0, 0, 0)), c1(N, make_float4(0, 0, 0, 0)), w0(N, make_float4(0, 0, 0, 0)), w1(N, make_float4(0, 0, 0, 0));
+    std::vector<float> prior(N, 0.f);
+    w.flags_h.assign(N, 0);
+    for (size_t d = 0; d < N; ++d) {
+        const int p = w.d2p[d];
+        if (p < 0) continue;
+        geo[d] = make_float4(u[p], v[p], idepth[p], idepth_zero ? idepth_zero[p] : idepth[p]);
+        c0[d] = make_float4(color[8 * p], color[8 * p + 1], color[8 * p + 2], color[8 * p + 3]); c1[d] = make_float4(color[8 * p + 4], color[8 * p + 5], color[8 * p + 6], color[8 * p + 7]);
+        w0[d] = make_float4(weights[8 * p], weights[8 * p + 1], weights[8 * p + 2], weights[8 * p + 3]); w1[d] = make_float4(weights[8 * p + 4], weights[8 * p + 5], weights[8 * p + 6], weights[8 * p + 7]);
+        const bool hp = has_prior && has_prior[p];
+        prior[d] = hp ? kIdepthFixPrior * kScaleIdepth * kScaleIdepth : 0.f;        // EFPoint::takeData (EnergyFunctionalStructs.cpp:79-85)
+        w.flags_h[d] = PT_VALID | (hp ? PT_HAS_PRIOR : 0);
+    }
+    const size_t NS = (size_t)W * N;
+    NALO_HIP(c, hipMemcpy(w.sc_grp.p, L.grp.data(), (size_t)(W + 1) * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.pt_geo.p, geo.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_col0.p, c0.data(), N * 16, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.pt_col1.p, c1.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_w0.p, w0.data(), N * 16, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.pt_w1.p, w1.data(), N * 16, hipMemcpyHostToDevice)); NALO_HIP(c, hipMemcpy(w.pt_prior.p, prior.data(), N * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.pt_flags.p, w.flags_h.data(), N, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.blk_host.p, w.blk_host_h.data(), (size_t)w.nblocks * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.host_blk.p, w.host_blk_h.data(), (size_t)(W + 1) * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemcpy(w.blk_order.p, L.order.data(), L.order.size() * 4, hipMemcpyHostToDevice));
+    NALO_HIP(c, hipMemset(w.pt_acc.p, 0, N * 16)); NALO_HIP(c, hipMemset(w.pt_hcd.p, 0, N * 16)); NALO_HIP(c, hipMemset(w.pt_step.p, 0, N * 4));
+    NALO_HIP(c, hipMemset(w.pt_backup.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs2.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_ngood.p, 0, N));
+    NALO_HIP(c, hipMemset(w.rs_state.p, 0, NS)); NALO_HIP(c, hipMemset(w.rs_energy.p, 0, NS * 8)); NALO_HIP(c, hipMemset(w.rs_jp0.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.rs_jp1.p, 0, NS * 16));
+    NALO_HIP(c, hipMemset(w.rs_cpt.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8));
+    bind_points(w);
+    w.points_set = true; w.res_set = false;
+    w.hist_set = false; w.dev.pt_numgood = nullptr; w.dev.pt_last = nullptr;           // a history belongs to the points it was set for
     return NALO_OK;
 }
 
@@ -1500,8 +1566,14 @@ int nalo_ba_marginalize_frame(nalo_ctx* c, int idx) {
     BAWindow& w = *c->ba;
     if (idx < 0 || idx >= w.W) return fail(c, NALO_ERR_ARG, "nalo_ba_marginalize_frame: frame index out of range");
     if (w.W < 3) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_frame: a window needs two frames");
-    if (w.points_set) for (int d = 0; d < w.Ppad; ++d)              // assert((int)fh->points.size()==0) at :505
-        if ((w.flags_h[d] & PT_VALID) && w.blk_host_h[d / kBlk] == idx) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_frame: the frame still hosts active points (marginalise or drop them first)");
+    // (the device arrays keep the layout they were issued with until the window is re-issued or carried: a frame's points sit under its device row, row_of)
+    const bool resident = (w.points_set || w.carry_ok) && (int)w.row_of.size() == w.W;
+    const int row = resident ? w.row_of[idx] : idx;
+    bool hosts = false;
+    if (w.points_set || w.carry_ok) for (int d = 0; d < w.Ppad && !hosts; ++d) hosts = (w.flags_h[d] & PT_VALID) && w.blk_host_h[d / kBlk] == row;
+    // assert((int)fh->points.size()==0) at :505. Once an earlier call has unset the points the caller may drop a frame's points by not re-submitting them, as
+    // before; the resident arrays then cannot be carried any more
+    if (hosts && w.points_set) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_frame: the frame still hosts active points (marginalise or drop them first)");
     const int odim = w.n, ndim = odim - 8;
     std::vector<int> perm; perm.reserve(odim);
     for (int i = 0; i < odim; ++i) if (i < 4 || (i - 4) / 8 != idx) perm.push_back(i);
@@ -1529,12 +1601,16 @@ int nalo_ba_marginalize_frame(nalo_ctx* c, int idx) {
     // the frame leaves the window (:583-590; FullSystem::marginalizeFrame drops every residual that targets it and re-runs setPrecalcValues / setAdjointsF,
     // FullSystemMarginalize.cpp:155-212): the device arrays are laid out per window size, so the caller re-issues nalo_ba_set_window (+ points, residuals)
     // for the frames that remain — with the next keyframe appended, set_window extends HM/bM like insertFrame does.
-    if (w.points_set && w.hist_set) {                               // lastResiduals of the points that stay: FullSystemMarginalize.cpp:174-177 (nalo_ba_get_point_history still answers)
+    if ((w.points_set || w.carry_ok) && w.hist_set) {               // lastResiduals of the points that stay: FullSystemMarginalize.cpp:174-177 (nalo_ba_get_point_history still answers)
         NALO_HIP(c, hipSetDevice(c->device));
         ba_launch_hist_remap(c->stream, w.dev, idx);
         NALO_HIP(c, hipGetLastError());
     }
     w.frames.erase(w.frames.begin() + idx);
+    // nalo_ba_carry_window can still re-issue the window from the device arrays: it needs to know which row each remaining frame is
+    w.carry_ok = resident && !hosts && (w.carry_ok || (w.points_set && w.res_set));
+    if (resident) w.row_of.erase(w.row_of.begin() + idx);
+    ++w.frames_epoch;
     w.W -= 1; w.n = 8 * w.W + 4; w.n1 = w.n + 1;
     w.points_set = false; w.res_set = false; w.have_lin = w.have_sc = false; w.proj_valid = false; w.have_snap = false; w.lin_fixed = false; w.flagged = false;
     w.lastX.assign(w.n, 0.0);
@@ -1794,6 +1870,7 @@ int nalo_imm_resident_activate(nalo_ctx* c, int frame, const float* KRKi, const 
     if (w1 > 0xFFFF || h1 > 0xFFFF || (unsigned)n > kActIdxMaxN) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_imm_resident_activate: level 1 beyond 65535 pixels a side or more than 2^27 points");
     *n_sel = 0;
     std::memset(c->imm_act_stats, 0, sizeof(c->imm_act_stats));
+    c->act_pend_n = -1;                                                       // a later activation replaces (or, without outputs, drops) the pending result
     if (n == 0) return NALO_OK;
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "imm_activate");
@@ -1842,7 +1919,19 @@ int nalo_imm_resident_activate(nalo_ctx* c, int frame, const float* KRKi, const 
     if (ns > N) return fail(c, NALO_ERR_HIP, "nalo_imm_resident_activate: the device returned an impossible count");
     *n_sel = (int)ns;
     std::memcpy(fate, hst + out0, N * 4); std::memcpy(sel, hst + out0 + N, ns * 4);
-    if (opt) { std::memcpy(result, hst + out0 + 2 * N, ns * 4); std::memcpy(idepth_out, hst + out0 + 3 * N, ns * 4); std::memcpy(res_in, hst + out0 + 4 * N, ns * W); }
+    if (opt) {
+        std::memcpy(result, hst + out0 + 2 * N, ns * 4); std::memcpy(idepth_out, hst + out0 + 3 * N, ns * 4); std::memcpy(res_in, hst + out0 + 4 * N, ns * W);
+        // the result stays readable on the device until nalo_ba_carry_window(insert_activated) consumes it: out of the staging block every immature-point call
+        // shares, into a place of its own (device to device, behind the kernels that wrote it; the next user of the staging block is ordered behind these copies)
+        NALO_HIP(c, c->act_pend.reserve(2 * ns + (ns * W + 3) / 4 + 1));
+        if (ns) {
+            NALO_HIP(c, hipMemcpyAsync(c->act_pend.p, dsel, ns * 4, hipMemcpyDeviceToDevice, c->stream));
+            NALO_HIP(c, hipMemcpyAsync(c->act_pend.p + ns, d + out0 + 3 * N, ns * 4, hipMemcpyDeviceToDevice, c->stream));
+            NALO_HIP(c, hipMemcpyAsync(c->act_pend.p + 2 * ns, d + out0 + 4 * N, ns * W, hipMemcpyDeviceToDevice, c->stream));
+        }
+        c->act_sel_h.assign(sel, sel + ns); c->act_result_h.assign(result, result + ns);
+        c->act_pend_n = (int)ns; c->act_pend_W = W; c->act_pend_epoch = w.frames_epoch;
+    }
     return NALO_OK;
 }
 
@@ -1901,5 +1990,152 @@ int nalo_ba_restore(nalo_ctx* c) {
     return NALO_OK;
 }
 
+// ---- the seam between two keyframes on the device (FullSystem::makeKeyFrame: marginalizeFrame -> insertFrame + the new residuals, FullSystem.cpp:1310-1348;
+// activatePointsMT step 4, :893-917). The host's share is integer work on mirrors it keeps anyway - the flag bytes, the slot keys, the resident set's u / v /
+// host_idx, the activation's sel / result -: it works out src[d_new] and trow[t_new] through the layout function nalo_ba_set_points uses, sends them with one
+// stream-ordered copy (4 bytes per new slot; with the block tables under 4.2), and ba_carry_kernel moves every float. Nothing comes back, nothing blocks.
+int nalo_ba_carry_window(nalo_ctx* c, const nalo_frame_state* entering, int insert_activated) {
+    if (!c || !c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: no window to carry (nalo_ba_set_window, nalo_ba_set_points, nalo_ba_set_residuals first)");
+    BAWindow& w = *c->ba;
+    if (c->xchg_failed) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: a cross-rank sum of this context failed earlier; rebuild the window on a new context");
+    if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the window is sharded (every rank would have to carry the same frames and its own points; re-issue it)");
+    if (!((w.points_set && w.res_set) || w.carry_ok) || (int)w.row_of.size() != w.W)
+        return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: points / residuals are not set (and not merely unset by nalo_ba_marginalize_frame)");
+    const int W_old = w.W, W = W_old + (entering ? 1 : 0);
+    if (W > NALO_MAX_WINDOW || W < 2) return fail(c, NALO_ERR_ARG, "nalo_ba_carry_window: the window would hold more than NALO_MAX_WINDOW (or fewer than 2) frames");
+    if (entering && (entering->slot < 0 || entering->slot >= (int)c->slots.size() || !c->slots[entering->slot].valid))
+        return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the entering frame's slot has no pyramid");
+    const int n_act = insert_activated ? c->act_pend_n : 0;
+    if (insert_activated) {
+        if (entering) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the reference appends the frame, activates, then inserts: carry the entering frame first, insert in a second call");
+        if (c->act_pend_n < 0) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: no activation result is pending (nalo_imm_resident_activate with its optimisation outputs)");
+        if (c->act_pend_epoch != w.frames_epoch || c->act_pend_W != W_old || !w.points_set)
+            return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the window's frames changed since the activation");
+    }
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "ba_carry_window");
+    // the carried points in their old submission order, then the inserted ones in toOptimize order: the new point list, with nalo_ba_set_points' sort keys
+    int new_host_of_row[NALO_MAX_WINDOW];
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) new_host_of_row[i] = -1;
+    for (int i = 0; i < W_old; ++i) new_host_of_row[w.row_of[i]] = i;
+    std::vector<int> host, from, map;                               // from: old device slot, or -(k + 2) (-1 is the padding's)
+    std::vector<unsigned long long> key;
+    host.reserve(w.P + n_act); from.reserve(w.P + n_act); map.reserve(w.P + n_act); key.reserve(w.P + n_act);
+    for (int p = 0; p < w.P; ++p) {
+        const int d = w.p2d[p];
+        if (!(w.flags_h[d] & PT_VALID)) continue;
+        const int h = new_host_of_row[w.blk_host_h[d / kBlk]];
+        if (h < 0) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: a frame that left the window still hosts a valid point");
+        host.push_back(h); from.push_back(d); map.push_back(p); key.push_back(((unsigned long long)h << kKeyHostShift) | w.key_h[d]);
+    }
+    const int n_carried = (int)host.size();
+    for (int k = 0; k < n_act; ++k) {
+        if (c->act_result_h[k] != 1) continue;                      // FullSystem.cpp:899-911: only a point optimizeImmaturePoint returned becomes a PointHessian
+        const int i = c->act_sel_h[k];
+        if (i < 0 || i >= c->imm_res_n || (size_t)i >= c->imm_host_h.size() || c->imm_host_h[i] >= W)
+            return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the pending activation names a point outside the resident set or the window");
+        const int h = c->imm_host_h[i];
+        host.push_back(h); from.push_back(-(k + 2)); map.push_back(-(k + 1));
+        key.push_back(((unsigned long long)h << kKeyHostShift) | hilbert_cell_key(c, c->imm_uv_h[i], c->imm_uv_h[(size_t)c->imm_res_n + i]));
+    }
+    const int P = (int)host.size();
+    // The stable sort by key, without sorting the carried points: the old slot order is (device row, key, submission index), the rows map monotonically to the new
+    // hosts and the renumbering keeps the submission order, so walking the old slots gives the carried points sorted; the inserted ones (few) are sorted and merged
+    // in behind their equals, as their larger submission indices place them
+    std::vector<int> sorted(P);
+    {
+        std::vector<int> newp(w.P, -1);
+        for (int q = 0; q < n_carried; ++q) newp[map[q]] = q;
+        int n = 0;
+        for (int d = 0; d < w.Ppad; ++d) { const int p = w.d2p[d]; if (p >= 0 && newp[p] >= 0) sorted[n++] = newp[p]; }
+        for (int q = n_carried; q < P; ++q) sorted[q] = q;
+        const auto less = [&](int a, int b) { return key[a] < key[b]; };
+        std::stable_sort(sorted.begin() + n_carried, sorted.end(), less);
+        std::inplace_merge(sorted.begin(), sorted.begin() + n_carried, sorted.end(), less);
+    }
+    // nothing of the old window may still be enqueued against gates or thresholds of its own
+    prelaunch_cancel(c);
+    { int rc = flush_th(c); if (rc) return rc; }
+    // ---- frames: the remaining ones as nalo_ba_get_frames returns them (+ the entering one), through nalo_ba_set_window's own code
+    std::vector<nalo_frame_state> fs(W);
+    for (int i = 0; i < W_old; ++i) {
+        const HostFrame& f = w.frames[i];
+        nalo_frame_state& s = fs[i];
+        s.slot = f.slot; s.frame_id = f.frameID; std::memcpy(s.worldToCam_evalPT, f.evalPT.m, 96);
+        std::memcpy(s.state, f.state, 80); std::memcpy(s.state_zero, f.state_zero, 80); s.ab_exposure = f.ab_exposure; s.frameEnergyTH = f.frameEnergyTH;
+    }
+    if (entering) fs[W_old] = *entering;
+    int trow[16];
+    for (int t = 0; t < 16; ++t) trow[t] = t < W_old ? w.row_of[t] : -1;
+    // ---- what the kernel reads of the old window, before the buffers change hands
+    CarryDev A{};
+    A.W_new = W; A.Ppad_old = w.Ppad; A.enter = entering ? 1 : 0;
+    A.o_geo = w.pt_geo.p; A.o_col0 = w.pt_col0.p; A.o_col1 = w.pt_col1.p; A.o_w0 = w.pt_w0.p; A.o_w1 = w.pt_w1.p; A.o_prior = w.pt_prior.p;
+    A.o_flags = w.pt_flags.p; A.o_state = w.rs_state.p; A.o_ng = w.hist_set ? w.pt_numgood.p : nullptr; A.o_last = w.hist_set ? w.pt_last.p : nullptr;
+    const std::vector<uint8_t> old_flags = w.flags_h;
+    { int rc = window_frames(c, W, fs.data(), nullptr, nullptr, entering != nullptr); if (rc) return rc; }
+    // the second set becomes the first (the layout function sizes the first set; growing a buffer does not keep its contents, and the old ones are the source)
+    std::swap(w.pt_geo, w.pt_geo2); std::swap(w.pt_col0, w.pt_col0_2); std::swap(w.pt_col1, w.pt_col1_2); std::swap(w.pt_w0, w.pt_w0_2); std::swap(w.pt_w1, w.pt_w1_2);
+    std::swap(w.pt_prior, w.pt_prior2); std::swap(w.pt_flags, w.pt_flags2); std::swap(w.rs_state, w.rs_state2);
+    if (w.hist_set) { std::swap(w.pt_numgood, w.pt_numgood2); std::swap(w.pt_last, w.pt_last2); }
+    w.points_set = false; w.res_set = false; w.carry_ok = false;    // until the launch below is in the stream, the window is neither
+    PointLayout L;
+    { int rc = build_point_layout(c, P, host.data(), key.data(), L, sorted.data()); if (rc) return rc; }
+    const size_t N = w.Ppad;
+    if (w.hist_set) { NALO_HIP(c, w.pt_numgood.reserve(N)); NALO_HIP(c, w.pt_last.reserve(N)); }
+    // ---- the maps and the block tables: one pinned block, stream-ordered copies (the block is rewritten only after the copies of the carry before have left it)
+    const size_t o_src = 16, o_bh = o_src + N, o_hb = o_bh + w.nblocks, o_grp = o_hb + (W + 1), o_ord = o_grp + (W + 1), words = o_ord + L.order.size();
+    if (w.ev_carry) NALO_HIP(c, hipEventSynchronize(w.ev_carry)); else NALO_HIP(c, w.ev_carry.create(hipEventDisableTiming));
+    NALO_HIP(c, w.carry_host.reserve(words)); NALO_HIP(c, w.carry_src.reserve(o_bh));
+    int* hb = w.carry_host.p;
+    std::memcpy(hb, trow, sizeof(trow));
+    w.flags_h.assign(N, 0);
+    for (size_t d = 0; d < N; ++d) {
+        const int p = w.d2p[d];
+        hb[o_src + d] = p < 0 ? -1 : from[p];
+        if (p < 0) continue;
+        w.flags_h[d] = from[p] >= 0 ? (uint8_t)(old_flags[from[p]] & (PT_VALID | PT_HAS_PRIOR)) : (uint8_t)PT_VALID;
+    }
+    std::memcpy(hb + o_bh, w.blk_host_h.data(), (size_t)w.nblocks * 4); std::memcpy(hb + o_hb, w.host_blk_h.data(), (size_t)(W + 1) * 4);
+    std::memcpy(hb + o_grp, L.grp.data(), (size_t)(W + 1) * 4); std::memcpy(hb + o_ord, L.order.data(), L.order.size() * 4);
+    NALO_HIP(c, hipMemcpyAsync(w.carry_src.p, hb, o_bh * 4, hipMemcpyHostToDevice, c->stream));                       // [trow | src]: the maps
+    NALO_HIP(c, hipMemcpyAsync(w.blk_host.p, hb + o_bh, (size_t)w.nblocks * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.host_blk.p, hb + o_hb, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.sc_grp.p, hb + o_grp, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.blk_order.p, hb + o_ord, L.order.size() * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipEventRecord(w.ev_carry, c->stream));
+    // ---- one launch: gather, insert, pad, zero
+    A.src = w.carry_src.p + o_src; std::memcpy(A.trow, trow, sizeof(trow)); A.Ppad_new = w.Ppad;
+    A.geo = w.pt_geo.p; A.col0 = w.pt_col0.p; A.col1 = w.pt_col1.p; A.w0 = w.pt_w0.p; A.w1 = w.pt_w1.p; A.prior = w.pt_prior.p; A.flags = w.pt_flags.p; A.state = w.rs_state.p;
+    A.ng = w.hist_set ? w.pt_numgood.p : nullptr; A.last = w.hist_set ? w.pt_last.p : nullptr;
+    A.acc = w.pt_acc.p; A.hcd = w.pt_hcd.p; A.step = w.pt_step.p; A.backup = w.pt_backup.p; A.relbs = w.pt_relbs.p; A.relbs2 = w.pt_relbs2.p; A.ngood = w.pt_ngood.p;
+    A.energy = w.rs_energy.p; A.jp0 = w.rs_jp0.p; A.jp1 = w.rs_jp1.p; A.cpt = w.rs_cpt.p;
+    A.imm = c->imm_res.p; A.immN = c->imm_res_n;
+    A.a_sel = c->act_pend.p; A.a_idepth = reinterpret_cast<const float*>(c->act_pend.p + std::max(n_act, 0)); A.a_in = reinterpret_cast<const uint8_t*>(c->act_pend.p + 2 * std::max(n_act, 0));
+    { ProfScope ps(c, "ba_carry"); ba_launch_carry(c->stream, A, w.nblocks); }
+    NALO_HIP(c, hipGetLastError());
+    NALO_HIP(c, hipMemsetAsync(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8, c->stream));
+    bind_points(w);
+    w.dev.pt_numgood = w.hist_set ? w.pt_numgood.p : nullptr; w.dev.pt_last = w.hist_set ? w.pt_last.p : nullptr;
+    w.points_set = true; w.res_set = true;
+    w.have_snap = false;                                            // a snapshot is of the arrays that just became the source
+    if (insert_activated) c->act_pend_n = -1;                       // consumed
+    w.carry_map_h.swap(map);
+    w.carry_stats[0] = n_carried; w.carry_stats[1] = P - n_carried; w.carry_stats[2] = P; w.carry_stats[3] = w.Ppad; w.carried = true;
+    return window_finish(c);
+}
+
+int nalo_ba_carry_map(nalo_ctx* c, int* old_p) {
+    if (!c || !c->ba || !c->ba->carried) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_map: no carry has been made");
+    if (!old_p && !c->ba->carry_map_h.empty()) return fail(c, NALO_ERR_ARG, "nalo_ba_carry_map: bad argument");
+    if (!c->ba->carry_map_h.empty()) std::memcpy(old_p, c->ba->carry_map_h.data(), c->ba->carry_map_h.size() * sizeof(int));
+    return NALO_OK;
+}
+int nalo_ba_carry_last(nalo_ctx* c, int stats[4]) {
+    if (!c || !c->ba || !c->ba->carried) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_last: no carry has been made");
+    if (!stats) return fail(c, NALO_ERR_ARG, "nalo_ba_carry_last: bad argument");
+    std::memcpy(stats, c->ba->carry_stats, sizeof(c->ba->carry_stats));
+    return NALO_OK;
+}
 
 }  // extern "C"

@@ -150,6 +150,11 @@ struct nalo_ctx {
     nalo::DevBuf<float> imm_res; int imm_res_n = 0, imm_res_maxhost = -1;         // device-resident immature points (nalo_imm_resident_*)
     nalo::DevBuf<float> imm_type; bool imm_type_set = false; float imm_type_max = 0;   // their my_type (nalo_imm_resident_set_type; a new set invalidates it)
     nalo::DevBuf<int> imm_act; int imm_act_stats[4] = {};                         // nalo_imm_resident_activate's scratch; the last call's counts (nalo_imm_activate_last)
+    // what nalo_ba_carry_window(insert_activated) needs of the resident set and of the last activation that was asked for its optimisation outputs
+    std::vector<float> imm_uv_h; std::vector<int> imm_host_h;                     // host copy of the set's u | v and host_idx (12 bytes per point, nalo_imm_resident_set)
+    nalo::DevBuf<int> act_pend;                                                  // the pending result on the device, out of the shared staging: sel (n) | idepth_out (n) | res_in (n x W bytes)
+    std::vector<int> act_sel_h, act_result_h;                                    // its sel / result as they went to the caller
+    int act_pend_n = -1, act_pend_W = 0; unsigned act_pend_epoch = 0;            // n = -1: none pending; the window's frames (BAWindow::frames_epoch) when it was made
 
     // ---- BA (opaque; defined in host_ba.hip)
     nalo::BAWindow* ba = nullptr;
