@@ -546,6 +546,52 @@ int nalo_imm_resident_set_type(nalo_ctx* ctx, const float* my_type);
 int nalo_imm_resident_activate(nalo_ctx* ctx, int frame, const float* KRKi, const float* Kt, const int* host_flagged, float currentMinActDist, int minObs,
                                int* fate, int* n_sel, int* sel, int* result, float* idepth_out, uint8_t* res_in);
 int nalo_imm_activate_last(nalo_ctx* ctx, int stats[4]);
+/* The resident immature set across a keyframe, on the device: what the caller otherwise rebuilds once per keyframe through nalo_imm_resident_get, its own
+ * bookkeeping, nalo_imm_create and nalo_imm_resident_set / _set_type. All of a resident point's state is carried, lastTraceUV and lastTracePixelInterval
+ * included (nalo_imm_resident_set resets both; the reference keeps them on the ImmaturePoint and canActivate reads the interval, FullSystem.cpp:833).
+ * nalo_imm_resident_carry applies up to three parts, in the order A, C, B; each is optional and any combination may come in one call:
+ *   (A) the end of activatePointsMT for the immature set. fate[n] as nalo_imm_resident_activate returned it, sel[n_sel] its toOptimize list, result[n_sel]
+ *       optimizeImmaturePoint's verdicts. A point is removed when its fate is -1, -2 or -3 (FullSystem.cpp:820-826, :840-851, :870-874), when it is selected
+ *       and result == 1 (it became a PointHessian, :898-907) or result == -1 (:908-912), and when it is selected, result == 0 and its resident status is IPS_OOB
+ *       (:908, read on the device). Every other point stays: fates 0, 2 and 3, and selected points with result == 0 that are not OOB (:913). Then every host's
+ *       vector - the host's points in ascending resident index - is compacted by the loop :920-931 exactly as written there: a hole takes the vector's back and
+ *       is looked at again, so the order after the call is the reference's swap-with-back order, which decides what the next activation selects.
+ *       NALO_ERR_ARG: sel does not list exactly the points with fate 1; result missing with n_sel > 0; a fate outside [-3, 3], a result outside {1, 0, -1}.
+ *       fate == NULL skips the part.
+ *   (C) frames that left the window: host_map[h_old] = h_new, or -1 for a frame that left; its points go with it (FrameHessian's destructor,
+ *       HessianBlocks.cpp:117), the others are renumbered, order inside a host is untouched. The kept entries must be 0 .. W_new-1 in increasing order and every
+ *       resident host_idx must be < n_hosts_old (NALO_ERR_ARG otherwise). host_map == NULL: identity.
+ *   (B) makeNewTraces (FullSystem.cpp:1677-1687) for the frame in append_slot, hosted by append_host (NEW numbering; append_slot < 0: no append). The list is
+ *       append_idx / append_status[append_n] (idx = x + y*w, status = the selection map's value), or with append_idx == NULL the raster-ordered list of the
+ *       selector's last map, which is already on the device. The walk is the loop's: entries with status 0 and entries outside
+ *       patternPadding+1 <= x < w-patternPadding-2 (y likewise, :1677-1678) are skipped, not refused; every other entry gets the ImmaturePoint constructor
+ *       (ImmaturePoint.cpp:32-60, the arithmetic of nalo_imm_create); a point whose energyTH is not finite is dropped (:1684); the others are appended behind the
+ *       host's carried points, in list order, with my_type = status, idepth_min = 0, idepth_max = NaN, status IPS_UNINITIALIZED, quality 10000,
+ *       lastTraceUV = (-1,-1), lastTracePixelInterval = 0. NALO_ERR_STATE: append_idx == NULL and no map was made on append_slot (or the slot was uploaded to
+ *       since, or
+ *       nalo_pixsel_make_hists read its thresholds back since); a slot without a pyramid; a resident set without types (nalo_imm_resident_set_type). NALO_ERR_ARG:
+ *       append_host outside [0, NALO_MAX_WINDOW), an entry outside the image, a status above 15, an explicit list that is not in raster order with every pixel once.
+ * The new set is ordered by new host index, ascending; inside a host it is the reference's vector. It may be empty. The set's size, its largest host index and
+ * the host copies nalo_ba_carry_window(insert_activated) orders inserted points by are updated; a set with types keeps them (the bound that
+ * nalo_imm_resident_activate checks currentMinActDist * my_type against keeps the types of deleted points). A pending activation result is DROPPED: call
+ * nalo_ba_carry_window(..., insert_activated) before this call. A refusal leaves the set as it was. Down go one byte per old point, the host map and an explicit
+ * append list; up come the 4-byte map and the counts; the call waits for the stream once and, once its buffers have grown to the set, allocates nothing.
+ *   nalo_imm_resident_carry_map   src[n_new]: the old index of every point of the new set, or -(k + 2) for the k-th entry of the append list (of the caller's
+ *                                 list, or of nalo_pixsel_get_selected's). NALO_ERR_STATE when the resident set does not come from a carry.
+ *   nalo_imm_resident_carry_last  {n_new, deleted by (A), dropped with their host by (C), appended, points per new host [NALO_MAX_WINDOW]} of the last call.
+ *   nalo_imm_resident_get_points  the resident points' constant part and my_type (any pointer NULL; arrays as nalo_imm_resident_set takes them): with
+ *                                 nalo_imm_resident_get the whole state, for tests and a debugging caller. */
+typedef struct {
+    const int* fate;                                  /* (A) [n]; NULL: skip */
+    int n_sel; const int* sel; const int* result;
+    const int* host_map; int n_hosts_old;             /* (C) NULL: identity */
+    int append_slot, append_host;                     /* (B) append_slot < 0: none; append_host in the NEW numbering */
+    int append_n; const int* append_idx; const unsigned char* append_status;   /* append_idx NULL: the selector's last map */
+} nalo_imm_carry_args;
+int nalo_imm_resident_carry(nalo_ctx* ctx, const nalo_imm_carry_args* args);
+int nalo_imm_resident_carry_map(nalo_ctx* ctx, int* src /* n_new */);
+int nalo_imm_resident_carry_last(nalo_ctx* ctx, int stats[4 + NALO_MAX_WINDOW]);
+int nalo_imm_resident_get_points(nalo_ctx* ctx, int* n, float* u, float* v, float* color, float* weights, float* gradH, float* energyTH, int* host_idx, float* my_type);
 
 /* ------------------------------------------------------------------------------------------------
  * the two-frame initialiser's Gauss-Newton pass.

@@ -35,10 +35,17 @@ EXPORTS = [
     "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
     "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
-    "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
+    "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
+    "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
+
+
+class ImmCarryArgs(C.Structure):
+    """nalo_imm_carry_args (include/nalo_gpu.h)"""
+    _fields_ = [("fate", c_ip), ("n_sel", C.c_int), ("sel", c_ip), ("result", c_ip), ("host_map", c_ip), ("n_hosts_old", C.c_int),
+                ("append_slot", C.c_int), ("append_host", C.c_int), ("append_n", C.c_int), ("append_idx", c_ip), ("append_status", c_u8p)]
 
 
 class Settings(C.Structure):
@@ -179,6 +186,10 @@ def load():
     L.nalo_imm_resident_set_type.argtypes = [vp, c_fp]
     L.nalo_imm_resident_activate.argtypes = [vp, C.c_int, c_fp, c_fp, c_ip, C.c_float, C.c_int, c_ip, c_ip, c_ip, c_ip, c_fp, c_u8p]
     L.nalo_imm_activate_last.argtypes = [vp, c_ip]
+    L.nalo_imm_resident_carry.argtypes = [vp, C.POINTER(ImmCarryArgs)]
+    L.nalo_imm_resident_carry_map.argtypes = [vp, c_ip]
+    L.nalo_imm_resident_carry_last.argtypes = [vp, c_ip]
+    L.nalo_imm_resident_get_points.argtypes = [vp, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_ip, c_fp]
     L.nalo_ba_restore.argtypes = [vp]
     L.nalo_dense_make_map.argtypes = [vp, C.c_int, c_fp, C.c_float, c_dp, C.c_int, c_ip, c_ip, c_ip, c_fp, c_fp, c_u8p, c_ip, c_ip]
     L.nalo_profile_enable.argtypes = [vp, C.c_int]
@@ -886,6 +897,57 @@ class Context:
         st = np.zeros(4, np.int32)
         self._ck(self.L.nalo_imm_activate_last(self.h_, _i(st)))
         return tuple(int(x) for x in st)
+
+    def imm_resident_carry(self, fate=None, sel=None, result=None, host_map=None, append_slot=-1, append_host=0, append_idx=None, append_status=None):
+        """the resident set across a keyframe on the device (nalo_imm_resident_carry): (A) fate / sel / result of imm_resident_activate, (C) host_map[h_old] = h_new
+        or -1, (B) append_slot / append_host with an explicit list or, with append_idx None, the selector's last map. -> the counts of imm_resident_carry_last"""
+        a = ImmCarryArgs()
+        a.append_slot, a.append_host = int(append_slot), int(append_host)
+        keep = []
+
+        def ints(x):
+            keep.append(np.ascontiguousarray(x, np.int32))
+            return _i(keep[-1])
+        if fate is not None:
+            a.fate = ints(fate)
+            a.n_sel = 0 if sel is None else len(sel)
+            if sel is not None:
+                a.sel = ints(sel)
+            if result is not None:
+                a.result = ints(result)
+        if host_map is not None:
+            a.host_map, a.n_hosts_old = ints(host_map), len(host_map)
+        if append_idx is not None:
+            a.append_idx, a.append_n = ints(append_idx), len(append_idx)
+            keep.append(np.ascontiguousarray(append_status, np.uint8))
+            a.append_status = _u8(keep[-1])
+        self._ck(self.L.nalo_imm_resident_carry(self.h_, C.byref(a)))
+        st = self.imm_resident_carry_last()
+        self._imm_n = st[0]
+        return st
+
+    def imm_resident_carry_last(self):
+        """(n_new, deleted by (A), dropped with their host by (C), appended, points per new host [16])"""
+        st = np.zeros(4 + 16, np.int32)
+        self._ck(self.L.nalo_imm_resident_carry_last(self.h_, _i(st)))
+        return int(st[0]), int(st[1]), int(st[2]), int(st[3]), st[4:].copy()
+
+    def imm_resident_carry_map(self):
+        src = np.zeros(max(self._imm_n, 1), np.int32)
+        self._ck(self.L.nalo_imm_resident_carry_map(self.h_, _i(src)))
+        return src[:self._imm_n]
+
+    def imm_resident_get_points(self, with_type=True):
+        """dict(u, v, color [n,8], weights [n,8], gradH [n,3], energyTH, host_idx, my_type) of the resident set"""
+        n = np.zeros(1, np.int32)
+        self._ck(self.L.nalo_imm_resident_get_points(self.h_, _i(n), None, None, None, None, None, None, None, None))
+        n = int(n[0])
+        m = max(n, 1)
+        o = dict(u=np.zeros(m, np.float32), v=np.zeros(m, np.float32), color=np.zeros((m, 8), np.float32), weights=np.zeros((m, 8), np.float32),
+                 gradH=np.zeros((m, 3), np.float32), energyTH=np.zeros(m, np.float32), host_idx=np.zeros(m, np.int32), my_type=np.zeros(m, np.float32))
+        self._ck(self.L.nalo_imm_resident_get_points(self.h_, None, _f(o["u"]), _f(o["v"]), _f(o["color"]), _f(o["weights"]), _f(o["gradH"]), _f(o["energyTH"]),
+                                                     _i(o["host_idx"]), _f(o["my_type"]) if with_type else None))
+        return {k: a[:n] for k, a in o.items()}
 
     def ba_snapshot(self):
         self._ck(self.L.nalo_ba_snapshot(self.h_))

@@ -685,6 +685,7 @@ int nalo_imm_resident_set(nalo_ctx* c, int n, const float* u, const float* v, co
     NALO_HIP(c, hipSetDevice(c->device));
     c->imm_res_n = n; c->imm_res_maxhost = -1; c->imm_type_set = false;
     c->act_pend_n = -1;                                                       // an activation result names points of the set it was made on
+    c->imm_carry_have = false;                                                // and so does the map of the last nalo_imm_resident_carry
     c->imm_uv_h.clear(); c->imm_host_h.clear();
     if (n == 0) return NALO_OK;
     const size_t N = (size_t)n;
@@ -752,6 +753,159 @@ int nalo_imm_resident_get(nalo_ctx* c, float* idepth_min, float* idepth_max, int
     std::memcpy(idepth_min, hst, N * 4); std::memcpy(idepth_max, hst + N, N * 4); std::memcpy(status, hst + 2 * N, N * 4); std::memcpy(quality, hst + 3 * N, N * 4);
     if (lastTraceUV) std::memcpy(lastTraceUV, hst + 4 * N, 2 * N * 4);
     if (lastTracePixelInterval) std::memcpy(lastTracePixelInterval, hst + 6 * N, N * 4);
+    return NALO_OK;
+}
+
+// The resident set across a keyframe (include/nalo_gpu.h has the semantics; kernels_imm_carry.hip the device side). Everything resident is read on the device:
+// a byte per old point (what (A) decides without the device's status), the host map and an explicit append list go down, the 4-byte map and the counts come up,
+// behind ONE wait. The new set is written into a second buffer that then changes places with the first, so a refusal leaves the set as it was.
+int nalo_imm_resident_carry(nalo_ctx* c, const nalo_imm_carry_args* a) {
+    if (!c || !a) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: bad argument");
+    const int n = c->imm_res_n;
+    const size_t N = (size_t)n;
+    if (n > 0 && (c->imm_host_h.size() != N || c->imm_uv_h.size() != 2 * N)) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry: the resident set has no host copy");
+    // ---- (C)
+    int H = std::max(c->imm_res_maxhost + 1, 1), hmap[NALO_MAX_WINDOW];
+    for (int h = 0; h < NALO_MAX_WINDOW; ++h) hmap[h] = h;
+    if (a->host_map) {
+        if (a->n_hosts_old < 0 || a->n_hosts_old > NALO_MAX_WINDOW) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: n_hosts_old outside [0, NALO_MAX_WINDOW]");
+        int next = 0;
+        for (int h = 0; h < a->n_hosts_old; ++h) {
+            if (a->host_map[h] != -1 && a->host_map[h] != next) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: host_map's kept entries must be 0, 1, ... in increasing order");
+            if (a->host_map[h] != -1) ++next;
+            hmap[h] = a->host_map[h];
+        }
+        if (c->imm_res_maxhost >= a->n_hosts_old) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: a resident point's host_idx is outside host_map");
+        H = std::max(a->n_hosts_old, 1);
+        if (a->n_hosts_old == 0) hmap[0] = -1;
+    }
+    // ---- (B)
+    const bool app = a->append_slot >= 0;
+    if (app && n > 0 && !c->imm_type_set) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry: the resident set has no types (nalo_imm_resident_set_type) and the appended points would bring theirs");
+    const int *list_dev = nullptr, *list_live = nullptr;
+    int m = 0, m_up = 0, n_live = 0;
+    if (app) {
+        if (a->append_host < 0 || a->append_host >= NALO_MAX_WINDOW) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: append_host outside the window");
+        if (a->append_slot >= (int)c->slots.size() || !c->slots[a->append_slot].valid) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry: the append slot has no pyramid");
+        if (a->append_idx) {
+            if (a->append_n < 0 || (a->append_n > 0 && !a->append_status)) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: bad append list");
+            for (int k = 0; k < a->append_n; ++k) {
+                if (a->append_idx[k] < 0 || a->append_idx[k] >= c->w * c->h || a->append_status[k] > 15) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: an append entry is outside the image or its status above 15");
+                if (k > 0 && a->append_idx[k] <= a->append_idx[k - 1]) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: the append list must be in raster order, every pixel once (makeNewTraces walks the map)");
+            }
+            m = m_up = a->append_n;
+        } else if (!pixsel_last_list(c, a->append_slot, &list_dev, &m, &list_live, &n_live))
+            return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry: no selection map has been made on the append slot (nalo_pixsel_make_maps)");
+    }
+    if ((size_t)n + (size_t)m >= (size_t)0x3FFFFFFF) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: too many points");
+    // ---- (A): what the host can decide per point. 0 stays, 1 deleted, 2 deleted when the resident status is IPS_OOB (FullSystem.cpp:908)
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "imm_resident_carry");
+    const size_t code_w = a->fate ? (N + 3) / 4 : 0, up_w = 16 + (size_t)m_up + code_w, down_w = 32 + N + (size_t)m;
+    int rc = imm_stage(c, up_w + down_w); if (rc) return rc;
+    int* hst = reinterpret_cast<int*>(c->imm_host.p);
+    static_assert(NALO_MAX_WINDOW <= 16 && 4 + NALO_MAX_WINDOW <= 32, "the staging block keeps 16 words for the host map and 32 for the counts");
+    std::memcpy(hst, hmap, sizeof(hmap));
+    for (int k = 0; k < m_up; ++k) hst[16 + k] = a->append_idx[k] | ((int)a->append_status[k] << 28);
+    if (a->fate) {
+        if (a->n_sel < 0 || (a->n_sel > 0 && (!a->sel || !a->result))) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: sel and result are required with n_sel > 0");
+        uint8_t* code = reinterpret_cast<uint8_t*>(hst + 16 + m_up);
+        int n1 = 0;
+        for (int i = 0; i < n; ++i) {
+            const int f = a->fate[i];
+            if (f < -3 || f > 3) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: a fate outside [-3, 3]");
+            code[i] = f < 0 ? 1 : (f == 1 ? 255 : 0);                           // 255: selected, waits for its verdict
+            n1 += f == 1;
+        }
+        if (n1 != a->n_sel) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: sel must list exactly the points with fate 1");
+        for (int k = 0; k < a->n_sel; ++k) {
+            const int i = a->sel[k], r = a->result[k];
+            if (i < 0 || i >= n || code[i] != 255) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: sel must list exactly the points with fate 1");
+            if (r != 1 && r != 0 && r != -1) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry: a result outside {1, 0, -1}");
+            code[i] = r == 0 ? 2 : 1;                                           // :898-907 became a PointHessian, :908 optimizeImmaturePoint's -1: both leave the set
+        }
+    }
+    const int n_slots = n + m;
+    int st[4 + NALO_MAX_WINDOW] = {};
+    std::vector<int> map;
+    if (n_slots > 0) {
+        const size_t grow = (size_t)n_slots + n_slots / 2 + 1024;               // room for the sets of the next keyframes: nothing is allocated in steady state
+        if (c->imm_res2.cap < 30 * (size_t)n_slots + 256) NALO_HIP(c, c->imm_res2.reserve(30 * grow + 256));
+        if (c->imm_type2.cap < (size_t)n_slots) NALO_HIP(c, c->imm_type2.reserve(grow));
+        ImmCarryParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.n = n; P.nb = (n + 255) / 256; P.m = m; P.mb = (m + 255) / 256; P.H = H;
+        P.w = c->w; P.h = c->h; P.append_host = app ? a->append_host : -1; P.rank_live = app && !a->append_idx;
+        const size_t cnt_w = 2 * (size_t)H * P.nb + 2 * (size_t)P.mb + P.nb + 1, scr_w = cnt_w + 32 + (size_t)n_slots + N + (size_t)m;
+        if (c->imm_carry_scr.cap < scr_w) NALO_HIP(c, c->imm_carry_scr.reserve(scr_w + scr_w / 2 + 1024));
+        NALO_HIP(c, hipMemcpyAsync(c->imm_dev.p, hst, up_w * 4, hipMemcpyHostToDevice, c->stream));
+        const int* dv = reinterpret_cast<const int*>(c->imm_dev.p);
+        P.host_map = dv; P.list = a->append_idx ? dv + 16 : list_dev; P.code = a->fate ? reinterpret_cast<const uint8_t*>(dv + 16 + m_up) : nullptr;
+        P.res = c->imm_res.p; P.type = (n > 0 && c->imm_type_set) ? c->imm_type.p : nullptr; P.res2 = c->imm_res2.p; P.type2 = c->imm_type2.p;
+        P.dI = app ? c->slots[a->append_slot].dI[0].p : nullptr;
+        P.cnt = c->imm_carry_scr.p; P.out = P.cnt + cnt_w; P.src = P.out + 32; P.mover = P.src + n_slots; P.arank = P.mover + n;
+        rc = imm_carry_launch(c, P); if (rc) return rc;
+        NALO_HIP(c, hipMemcpyAsync(hst + up_w, P.out, down_w * 4, hipMemcpyDeviceToHost, c->stream));
+        NALO_HIP(c, hipStreamSynchronize(c->stream));
+        std::memcpy(st, hst + up_w, sizeof(st));
+        if (st[0] < 0 || st[0] > n_slots) return fail(c, NALO_ERR_HIP, "nalo_imm_resident_carry: the device returned an impossible count");
+        map.assign(hst + up_w + 32, hst + up_w + 32 + st[0]);
+    }
+    // ---- commit: the host copies nalo_ba_carry_window(insert_activated) orders inserted points by, then the buffers change places
+    const int n_new = st[0];
+    std::vector<float> uv(2 * (size_t)n_new); std::vector<int> hh((size_t)n_new);
+    float tmax = (n > 0 && c->imm_type_set) ? c->imm_type_max : 0.f;
+    for (int j = 0; j < n_new; ++j) {
+        const int s = map[j];
+        if (s >= 0) { uv[j] = c->imm_uv_h[s]; uv[(size_t)n_new + j] = c->imm_uv_h[N + s]; hh[j] = hmap[c->imm_host_h[s]]; continue; }
+        const int k = -(s + 2);
+        if (k < 0 || k >= (a->append_idx ? m : n_live)) return fail(c, NALO_ERR_HIP, "nalo_imm_resident_carry: the device named an append entry outside the list");
+        const int e = a->append_idx ? (a->append_idx[k] | ((int)a->append_status[k] << 28)) : list_live[k], idx = e & 0x0FFFFFFF;
+        uv[j] = (float)(idx % c->w); uv[(size_t)n_new + j] = (float)(idx / c->w); hh[j] = a->append_host;
+        tmax = std::max(tmax, (float)((unsigned)e >> 28));
+    }
+    if (n_slots > 0) { std::swap(c->imm_res, c->imm_res2); std::swap(c->imm_type, c->imm_type2); }
+    c->imm_uv_h.swap(uv); c->imm_host_h.swap(hh);
+    c->imm_type_set = c->imm_type_set || n == 0;                              // carried points keep their types, appended ones bring theirs; a set without types stays without
+    c->imm_type_max = tmax;                                                     // an upper bound: deleted points are not taken out of it
+    c->imm_res_n = n_new; c->imm_res_maxhost = -1;
+    for (int h = 0; h < NALO_MAX_WINDOW; ++h) if (st[4 + h] > 0) c->imm_res_maxhost = h;
+    c->act_pend_n = -1;                                                       // an activation result names points of the set it was made on
+    c->imm_carry_map.swap(map); std::memcpy(c->imm_carry_stats, st, sizeof(st)); c->imm_carry_have = true;
+    return NALO_OK;
+}
+int nalo_imm_resident_carry_map(nalo_ctx* c, int* src) {
+    if (!c || (c->imm_carry_have && !c->imm_carry_map.empty() && !src)) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry_map: bad argument");
+    if (!c->imm_carry_have) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry_map: the resident set does not come from nalo_imm_resident_carry");
+    if (!c->imm_carry_map.empty()) std::memcpy(src, c->imm_carry_map.data(), c->imm_carry_map.size() * sizeof(int));
+    return NALO_OK;
+}
+int nalo_imm_resident_carry_last(nalo_ctx* c, int stats[4 + NALO_MAX_WINDOW]) {
+    if (!c || !stats) return fail(c, NALO_ERR_ARG, "nalo_imm_resident_carry_last: bad argument");
+    if (!c->imm_carry_have) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_carry_last: the resident set does not come from nalo_imm_resident_carry");
+    std::memcpy(stats, c->imm_carry_stats, sizeof(c->imm_carry_stats));
+    return NALO_OK;
+}
+int nalo_imm_resident_get_points(nalo_ctx* c, int* n, float* u, float* v, float* color, float* weights, float* gradH, float* energyTH, int* host_idx, float* my_type) {
+    if (!c) return NALO_ERR_ARG;
+    if (n) *n = c->imm_res_n;
+    if (c->imm_res_n == 0 || !(u || v || color || weights || gradH || energyTH || host_idx || my_type)) return NALO_OK;
+    if (my_type && !c->imm_type_set) return fail(c, NALO_ERR_STATE, "nalo_imm_resident_get_points: the resident set has no types (nalo_imm_resident_set_type)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->imm_res_n;
+    int rc = imm_stage(c, 24 * N); if (rc) return rc;
+    float* hst = c->imm_host.p;
+    NALO_HIP(c, hipMemcpyAsync(hst, c->imm_res.p, 23 * N * 4, hipMemcpyDeviceToHost, c->stream));
+    if (my_type) NALO_HIP(c, hipMemcpyAsync(hst + 23 * N, c->imm_type.p, N * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    if (u) std::memcpy(u, hst, N * 4);
+    if (v) std::memcpy(v, hst + N, N * 4);
+    if (color) std::memcpy(color, hst + 2 * N, 8 * N * 4);
+    if (weights) std::memcpy(weights, hst + 10 * N, 8 * N * 4);
+    if (gradH) std::memcpy(gradH, hst + 18 * N, 3 * N * 4);
+    if (energyTH) std::memcpy(energyTH, hst + 21 * N, N * 4);
+    if (host_idx) std::memcpy(host_idx, hst + 22 * N, N * 4);
+    if (my_type) std::memcpy(my_type, hst + 23 * N, N * 4);
     return NALO_OK;
 }
 

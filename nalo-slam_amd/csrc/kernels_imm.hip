@@ -9,12 +9,12 @@
 // bit-identical to the fp32 restatement (tests/test_imm_gpu.py). The per-step energies of the discrete search and the per-residual
 // energies of the point optimisation live in LDS, transposed ([step][lane]): no scratch memory.
 #include "nalo_internal.h"
+#include "imm_ctor_body.h"
 
 namespace nalo {
 
 // setting_maxPixSearch, setting_trace_*, setting_minTraceTestRadius, setting_GNItsOnPointActivation, setting_minIdepthH_act, setting_outlierTH: ref_constants.h
 constexpr float kImmOutlierTH = kOutlierTH, kImmMinIdepthHAct = kMinIdepthHAct;
-enum { IPS_GOOD = 0, IPS_OOB, IPS_OUTLIER, IPS_SKIPPED, IPS_BADCONDITION, IPS_UNINITIALIZED };   // ImmaturePoint.h:47-53
 enum { IRS_IN = 0, IRS_OOB = 1, IRS_OUTLIER = 2 };
 #define NALO_PAT(i) {kPatternDx[i], kPatternDy[i]}
 __constant__ int kImmPattern[8][2] = {NALO_PAT(0), NALO_PAT(1), NALO_PAT(2), NALO_PAT(3), NALO_PAT(4), NALO_PAT(5), NALO_PAT(6), NALO_PAT(7)};   // settings.cpp:297 (ref_constants.h)
@@ -42,26 +42,14 @@ __global__ __launch_bounds__(256) void imm_create_kernel(const float4* __restric
                                                          float* __restrict__ color, float* __restrict__ weights, float* __restrict__ gradH, float* __restrict__ energyTH) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    float gxx = 0, gxy = 0, gyy = 0;
-    bool bad = false;
-    for (int idx = 0; idx < 8; ++idx) {
-        const float x = (float)(u[p] + kImmPattern[idx][0]), y = (float)(v[p] + kImmPattern[idx][1]);
-        const int ix = (int)x, iy = (int)y;
-        const float4* bp = dI + ix + iy * w;                                   // getInterpolatedElement33BiLin, globalFuncs.h:166-188
-        const float tl = bp[0].x, tr = bp[1].x, bl = bp[w].x, br = bp[w + 1].x;
-        const float dx = x - ix, dy = y - iy;
-        const float topInt = dx * tr + (1 - dx) * tl, botInt = dx * br + (1 - dx) * bl, leftInt = dy * bl + (1 - dy) * tl, rightInt = dy * br + (1 - dy) * tr;
-        const float c0 = dx * rightInt + (1 - dx) * leftInt, g0 = rightInt - leftInt, g1 = botInt - topInt;
-        color[p * 8 + idx] = c0;
-        if (!isfinite(c0)) { energyTH[p] = NAN; bad = true; break; }
-        gxx += g0 * g0; gxy += g0 * g1; gyy += g1 * g1;
-        weights[p * 8 + idx] = sqrtf(kOutlierTHSumComponent / (kOutlierTHSumComponent + (g0 * g0 + g1 * g1)));
+    const ImmCtor r = imm_ctor(dI, w, u[p], v[p]);                            // imm_ctor_body.h
+#pragma unroll
+    for (int idx = 0; idx < 8; ++idx) {                                        // what the constructor wrote before it returned
+        if (idx <= r.n_ok) color[p * 8 + idx] = r.color[idx];
+        if (idx < r.n_ok) weights[p * 8 + idx] = r.weights[idx];
     }
-    gradH[p * 3] = gxx; gradH[p * 3 + 1] = gxy; gradH[p * 3 + 2] = gyy;
-    if (bad) return;
-    float eth = 8 * kImmOutlierTH;
-    eth *= kOverallEnergyTHWeight * kOverallEnergyTHWeight;
-    energyTH[p] = eth;
+    gradH[p * 3] = r.gxx; gradH[p * 3 + 1] = r.gxy; gradH[p * 3 + 2] = r.gyy;
+    energyTH[p] = r.energyTH;
 }
 
 struct ImmTraceParams {
@@ -452,6 +440,12 @@ __global__ __launch_bounds__(1024) void act_scan_kernel(int* __restrict__ a, int
     int run = part[t] - s;
     for (int k = b; k < e; ++k) { const int x = a[k]; a[k] = run; run += x; }
     if (t == 1023) a[m] = part[1023];
+}
+
+int scan_ints_launch(nalo_ctx* c, int* a, int m) {
+    act_scan_kernel<<<1, 1024, 0, c->stream>>>(a, m);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
 }
 
 __global__ __launch_bounds__(256) void act_scatter_kernel(ActParams P) {

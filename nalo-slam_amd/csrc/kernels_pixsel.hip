@@ -28,7 +28,7 @@ struct PixSel {
     HostBuf<int> host;                           // pinned: [0..15] counters, [16..] list
     int hist_slot = -1;
     bool have_rp = false, have_draws = false, have_map = false;
-    int list_n = 0;
+    int list_n = 0, list_total = 0, map_slot = -1;   // list_total: the device list's length (entries the sub-selection dropped stay, with status 0); map_slot: the frame of the last map
 };
 
 __constant__ float c_dirs[16][2] = {{0.f, 1.0000f},     {0.3827f, 0.9239f},  {0.1951f, 0.9808f},  {0.9239f, 0.3827f}, {0.7071f, 0.7071f},  {0.3827f, -0.9239f},
@@ -248,7 +248,16 @@ void pixsel_destroy(nalo_ctx* c) {
     delete c->pixsel;
     c->pixsel = nullptr;
 }
-void pixsel_invalidate_hists(nalo_ctx* c, int slot) { if (c->pixsel && c->pixsel->hist_slot == slot) c->pixsel->hist_slot = -1; }
+void pixsel_invalidate_hists(nalo_ctx* c, int slot) {
+    if (c->pixsel && c->pixsel->hist_slot == slot) c->pixsel->hist_slot = -1;
+    if (c->pixsel && c->pixsel->map_slot == slot) c->pixsel->map_slot = -1;    // the map no longer describes the slot's image
+}
+bool pixsel_last_list(nalo_ctx* c, int slot, const int** dev, int* n_dev, const int** host_live, int* n_live) {
+    const PixSel* p = c->pixsel;
+    if (!p || !p->have_map || p->map_slot != slot || slot < 0) return false;
+    *dev = p->list.p; *n_dev = p->list_total; *host_live = p->host.p + 16; *n_live = p->list_n;
+    return true;
+}
 
 static int pixsel_state(nalo_ctx* c, PixSel** out) {
     if (!c->pixsel) c->pixsel = new PixSel();
@@ -273,6 +282,7 @@ static int pixsel_hists(nalo_ctx* c, PixSel* p, int slot) {
 }
 // select on the device: map (bytes) + counters. n[3] = {n2, n3, n4} of PixelSelector::select.
 static int pixsel_select_dev(nalo_ctx* c, PixSel* p, int slot, int pot, float thFactor, int n[3]) {
+    p->map_slot = -1;                                               // until this selection stands
     const FrameSlot& s = c->slots[slot];
     const size_t npx = (size_t)c->w * c->h, nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
     PixSelArgs A;
@@ -306,7 +316,7 @@ static int pixsel_select_dev(nalo_ctx* c, PixSel* p, int slot, int pot, float th
         std::swap(flags, other);                                // a cell's flag was wrong: redo the scan with the flags the selection produced
     }
     n[0] = p->host.p[1]; n[1] = p->host.p[2]; n[2] = p->host.p[3];
-    p->have_map = true;
+    p->have_map = true; p->map_slot = slot; p->list_total = 0;
     return NALO_OK;
 }
 // compaction (+ optional sub-selection) and the host copies: list -> pinned, map_out filled from the list
@@ -329,7 +339,7 @@ static int pixsel_fetch(nalo_ctx* c, PixSel* p, int charTH, float* map_out, int*
     // the list keeps only live entries (sub-selected ones are dropped here)
     int m = 0;
     for (int i = 0; i < total; ++i) { const int e = p->host.p[16 + i]; if (e >> 28) p->host.p[16 + m++] = e; }
-    p->list_n = m;
+    p->list_n = m; p->list_total = total;
     if (map_out) {
         std::memset(map_out, 0, sizeof(float) * (size_t)npx);
         for (int i = 0; i < m; ++i) { const int e = p->host.p[16 + i]; map_out[e & 0x0FFFFFFF] = (float)(e >> 28); }
@@ -380,6 +390,7 @@ int nalo_pixsel_make_hists(nalo_ctx* c, int slot, float* ths, float* thsSmoothed
     if (nb == 0) return NALO_OK;
     rc = pixsel_hists(c, p, slot); if (rc) return rc;
     if (ths || thsSmoothed) {
+        p->map_slot = -1;                                           // the read-back goes through the pinned block that holds the last map's list
         NALO_HIP(c, hipMemcpyAsync(p->host.p, p->ths.p, 2 * (nb + 100) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
         if (ths) std::memcpy(ths, p->host.p, nb * sizeof(float));

@@ -152,6 +152,9 @@ struct nalo_ctx {
     nalo::DevBuf<int> imm_act; int imm_act_stats[4] = {};                         // nalo_imm_resident_activate's scratch; the last call's counts (nalo_imm_activate_last)
     // what nalo_ba_carry_window(insert_activated) needs of the resident set and of the last activation that was asked for its optimisation outputs
     std::vector<float> imm_uv_h; std::vector<int> imm_host_h;                     // host copy of the set's u | v and host_idx (12 bytes per point, nalo_imm_resident_set)
+    // nalo_imm_resident_carry: the buffers the set is gathered into (they change places with imm_res / imm_type), its scratch, and the last call's map and counts
+    nalo::DevBuf<float> imm_res2, imm_type2; nalo::DevBuf<int> imm_carry_scr;
+    std::vector<int> imm_carry_map; int imm_carry_stats[4 + NALO_MAX_WINDOW] = {}; bool imm_carry_have = false;
     nalo::DevBuf<int> act_pend;                                                  // the pending result on the device, out of the shared staging: sel (n) | idepth_out (n) | res_in (n x W bytes)
     std::vector<int> act_sel_h, act_result_h;                                    // its sel / result as they went to the caller
     int act_pend_n = -1, act_pend_W = 0; unsigned act_pend_epoch = 0;            // n = -1: none pending; the window's frames (BAWindow::frames_epoch) when it was made
@@ -253,6 +256,20 @@ struct ActParams {
 };
 int act_launch(nalo_ctx* c, const ActParams& P, bool first, int rounds, int* ctr, int* cnt, int* sel);
 int pixsel_hists_launch(nalo_ctx* c, const float* absg0, float* ths, float* thsSmoothed);
+int scan_ints_launch(nalo_ctx* c, int* a, int m);                              // exclusive scan of a[0..m) in place on c->stream, the total into a[m] (one workgroup)
+// kernels_imm_carry.hip: the resident set across a keyframe (nalo_imm_resident_carry). Every pointer is device memory.
+struct ImmCarryParams {
+    int n, nb, m, mb, H;                                                        // old points and append-list entries with their 256-thread workgroups; OLD hosts
+    int w, h, append_host, rank_live;                                           // append_host: NEW numbering, -1 none; rank_live: name an appended point by its rank among the list's live entries
+    const int* host_map;                                                        // [H] old host -> new host, -1: the frame left
+    const float *res, *type; float *res2, *type2;                               // the set and my_type (type NULL: none given), and the second buffer they are gathered into
+    const uint8_t* code;                                                        // per old point 0 stays, 1 deleted, 2 deleted if its status is IPS_OOB; NULL: all stay
+    const int* list; const float4* dI;                                          // append list (idx | status << 28) and level 0 of the new frame
+    int *cnt, *src, *mover, *arank, *out;                                       // cnt: 2 H nb + 2 mb + nb + 1; src: n + m; mover: n; arank: m; out: 4 + NALO_MAX_WINDOW
+};
+int imm_carry_launch(nalo_ctx* c, const ImmCarryParams& P);
+// kernels_pixsel.hip: the last map's compact list when it was made on `slot` (false otherwise): on the device with its holes (status 0), on the host without
+bool pixsel_last_list(nalo_ctx* c, int slot, const int** dev, int* n_dev, const int** host_live, int* n_live);
 // host_ba.hip: nalo_trk_set_ref_from_window's inputs gathered from the window on c->stream ({Ku | Kv | new_idepth | HdiF}, *n each, holes included)
 int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
 // host_ba.hip
