@@ -165,7 +165,7 @@ int nalo_trk_set_pc(nalo_ctx* ctx, int slot_ref, int lvl, int n, const float* u,
                     const float* idepth, const float* color);
 int nalo_trk_get_pc(nalo_ctx* ctx, int lvl, int* n, float* u, float* v, float* idepth, float* color);
 /* dense=1: the plane-sampled points makeCoarseDepthL0 appends to the LEVEL-0 cloud after step 5 (CoarseTracker.cpp:600-655), one call per mask cluster, on
- * the device (no round trip of the cloud): dir / dis_plane = the cluster's fitted plane (fitPlane, a PCL RANSAC on the caller's side), refMaskColor =
+ * the device (no round trip of the cloud): dir / dis_plane = the cluster's fitted plane (fitPlane: nalo_trk_fit_planes below, or a PCL RANSAC on the caller's side), refMaskColor =
  * clusters[i][0][3], rect = {minx, maxx, miny, maxy} of the cluster's pixels. Uses the mask and I of the tracking reference's slot (frameHessians.back() is
  * lastRef). Appends, in the reference's x-outer / y-inner order, every (x % 5 == 0, y % 5 == 0) pixel of [minx,maxx) x [miny,maxy) whose mask equals
  * refMaskColor with new_idepth = dir^T Ki (x,y,1) / -dis_plane and colour I_ref(x,y) — INCLUDING the reference's off-by-one (the k-th point is stored at
@@ -450,12 +450,76 @@ int nalo_shard_points(int P, int W, const int* host, const float* u, const float
 
 /* ------------------------------------------------------------------------------------------------
  * a14  DenseMapping::updateMap bbox scan + makeMap (FullSystem/MapPoint.cpp:300-310, 334-407), call site
- * FullSystem.cpp:1494. plane = (pi1..pi4) from the caller's RANSAC. rect_out = {minx,maxx,miny,maxy}.
+ * FullSystem.cpp:1494. plane = (pi1..pi4) from nalo_dense_fit_planes or the caller's RANSAC. rect_out = {minx,maxx,miny,maxy}.
  * Outputs at most cap points in raster order; *n = count; *accept = the extent test of MapPoint.cpp:403.
  * ------------------------------------------------------------------------------------------------ */
 int nalo_dense_make_map(nalo_ctx* ctx, int slot, const float plane[4], float mask_value, const double camToWorld[12],
                         int cap, int rect_out[4], int* out_u, int* out_v, float* out_idepth, float* out_color,
                         uint8_t* out_bgr, int* n, int* accept);
+
+/* ------------------------------------------------------------------------------------------------
+ * dense=1 / densemap=1: DenseMapping::makeMaskDistMap (FullSystem/MapPoint.cpp:445-513) + fitPlane (:522-584) on the device, for both call sites:
+ * CoarseTracker.cpp:559,591 (nalo_trk_fit_planes) and MapPoint.cpp:261,280 (nalo_dense_fit_planes). The points are grouped by the mask value under them and a
+ * plane is fitted to every group; the records come back in the reference's cluster order. One wait, at the end of the call; `draws` go down, cap records come up.
+ *
+ * Clustering - exact. For every input point xx = (int)u, yy = (int)v: the reference's `if(dx<0.5) xx = ix; else xx = ix++;` (:469-472) post-increments, so xx
+ *   NEVER rounds up; reproduced. A point is a member when xx>2 && xx<w-2 && yy>2 && yy<h-2 (:477). The reference reads the mask BEFORE that test (out of bounds
+ *   for a point outside the image); here the read is guarded and a point that fails the test has no mask value; a coordinate that is not finite or outside
+ *   int's range fails the test. Two points share a cluster when their mask values compare equal as floats: -0 equals +0 (the record carries +0). DIFFERENCE: a
+ *   point under a NaN mask value is dropped (in the reference every such point is a cluster of its own, NaN != NaN).
+ *   Discovery order and member order are those of the reference's alternating sweeps (:482-505): cluster 1 is the value under the LAST member, its members in
+ *   descending input index; cluster 2 the value under the FIRST remaining member, in ascending index; and so on alternating. The clusters are then ordered by
+ *   size, descending (:509). DEFINED READ: the reference's std::sort leaves the order of equal sizes unspecified; here ties keep discovery order.
+ *   More than 2048 clusters: NALO_ERR_UNSUPPORTED (REFUSED, not computed; *n_clusters holds their number).
+ * Fit - a defined algorithm (PCL's RANSAC is unseeded: no fit can be compared with it bit for bit). All fp32, IEEE division and square root, no FMA:
+ *   cloud     per member, in member order: X = (fxi*xx + cxi) / id, Y = (fyi*yy + cyi) / id, Z = 1 / id with Ki[0] = {fxi = 1/fx, cxi = -cx/fx, fyi = 1/fy,
+ *             cyi = -cy/fy} of the context's level-0 calibration (fitPlane :542-543). A member with a coordinate that is not finite is left out of the cloud
+ *             (:544-548) but stays in n and rect. fitted = 0 when n_cloud < max(min_points, 3) (:560).
+ *   triplets  sample i over the m cloud points, d = draws[3i .. 3i+2]: i0 = d0 % m; i1 = d1 % (m-1), plus one if >= i0; i2 = d2 % (m-2), plus one if >= the
+ *             smaller of i0, i1, then plus one if >= the larger. The caller owns the random stream (as nalo_pixsel_set_random); all clusters share it.
+ *   model     n = (p1-p0) x (p2-p0), every product rounded; len = sqrtf((nx*nx + ny*ny) + nz*nz); a zero or non-finite len is a degenerate sample: it scores
+ *             nothing and never wins (all samples degenerate: fitted = 0). (a, b, c) = n / len, d = -((a*x0 + b*y0) + c*z0).
+ *   score     the cloud points with fabsf(((a*x + b*y) + c*z) + d) < threshold. ALL n_samples candidates are scored (PCL's adaptive stop only saves serial
+ *             time); the first with the largest count wins: best_sample, inliers.
+ *   refine    (setOptimizeCoefficients(true)) with more than 3 inliers: centroid and 3x3 scatter of the winner's inliers about it in fp64 from their fp32
+ *             coordinates, the eigenvector of its smallest eigenvalue (cyclic Jacobi, fp64, on the device) normalised, signed so that its dot product with the
+ *             sample normal is >= 0, dis_plane = -n . centroid; rounded to float at the end. With 3 inliers or fewer the sample model is the result.
+ * nalo_trk_fit_planes   input: the level-0 cloud as it stands (pc_u, pc_v, pc_idepth, pc_n[0]); mask: the tracking reference's slot. append = 1 also runs the
+ *   loop of CoarseTracker.cpp:582-666 on the device with the fitted planes, through the code of nalo_trk_append_plane_points: nothing with fewer than 4 clusters
+ *   (:563); per cluster, in order: skipped when not fitted (:591), when its rect touches the border (:627: maxx>w-1||minx<1||maxy>h-1||miny<1) or when
+ *   (int)mask_value == 0 (:635); else appended (the off-by-one slot included), `appended` = the growth of pc_n[0]. The clusters are formed before the first
+ *   append, as in the reference. NOT done here: the ground choice by `score` (:609-625) reads a variable fitPlane never writes; it stays with the caller.
+ * nalo_dense_fit_planes input: what updateMap collects for the window's frame host_frame (MapPoint.cpp:246-259): its valid window points in submission order
+ *   with idepth, then the resident immature points with that host_idx in resident order with (idepth_max + idepth_min) * 0.5f; mask: the frame's slot. The caller
+ *   loops nalo_dense_make_map over the fitted clusters as before. Read on the device; the slot map of the window's points (4 bytes per point) goes down once
+ *   per issued point list, shared with nalo_trk_set_ref_from_window.
+ * nalo_plane_fit_members the last completed call's member lists: cluster_of[i] = the record index of input point i or -1 (cap >= the input count), order = the
+ *   members of cluster 0, then 1, ... each in the reference's vector order (sum of n entries): what clusters[i][k] held, for tests and callers that keep objects.
+ * Refusals: NALO_ERR_STATE no level-0 cloud / no window or points; no mask in the slot; a sharded window (dense). NALO_ERR_ARG cap < the number of clusters
+ *   (*n_clusters still reports the need; nothing is appended), n_samples < 1 or > 4096, draws == NULL, a negative or NaN threshold. A refused call leaves the
+ *   cloud and the context usable.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_plane_cluster {
+    float mask_value;      /* clusters[i][0][3] */
+    int   n;               /* members after the border test */
+    int   n_cloud;         /* members whose back-projection is finite (fitPlane's cloud) */
+    int   rect[4];         /* minx, maxx, miny, maxy over the members' (xx, yy), CoarseTracker.cpp:597-607 */
+    int   fitted;          /* 1: n_cloud >= min_points and at least one non-degenerate sample */
+    float plane[4];        /* dir_vector, dis_plane (zeros when not fitted) */
+    int   best_sample;     /* index of the winning triplet (-1 when not fitted) */
+    int   inliers;         /* its count */
+    int   appended;        /* tracker variant with append = 1: growth of pc_n[0] for this cluster, else 0 */
+} nalo_plane_cluster;
+typedef struct nalo_plane_fit_args {
+    float threshold;       /* the reference's setDistanceThreshold(0.01) */
+    int   min_points;      /* the reference's 10 */
+    int   n_samples;       /* triplets; PCL's SACSegmentation default of 50 iterations is the documented default */
+    const uint32_t* draws; /* 3 * n_samples values of the caller's stream, shared by all clusters */
+    int   append;          /* tracker variant only */
+} nalo_plane_fit_args;
+int nalo_trk_fit_planes(nalo_ctx* ctx, const nalo_plane_fit_args* args, int cap, nalo_plane_cluster* out, int* n_clusters);
+int nalo_dense_fit_planes(nalo_ctx* ctx, int host_frame, const nalo_plane_fit_args* args, int cap, nalo_plane_cluster* out, int* n_clusters);
+int nalo_plane_fit_members(nalo_ctx* ctx, int cap, int* cluster_of, int* order);
 
 /* ------------------------------------------------------------------------------------------------
  * the immature-point depth filter and point activation that run either side of the BA.

@@ -38,7 +38,7 @@ EXPORTS = [
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
-    "nalo_dense_make_map", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
+    "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
 
 
@@ -46,6 +46,22 @@ class ImmCarryArgs(C.Structure):
     """nalo_imm_carry_args (include/nalo_gpu.h)"""
     _fields_ = [("fate", c_ip), ("n_sel", C.c_int), ("sel", c_ip), ("result", c_ip), ("host_map", c_ip), ("n_hosts_old", C.c_int),
                 ("append_slot", C.c_int), ("append_host", C.c_int), ("append_n", C.c_int), ("append_idx", c_ip), ("append_status", c_u8p)]
+
+
+class PlaneCluster(C.Structure):
+    """nalo_plane_cluster (include/nalo_gpu.h)"""
+    _fields_ = [("mask_value", C.c_float), ("n", C.c_int), ("n_cloud", C.c_int), ("rect", C.c_int * 4), ("fitted", C.c_int), ("plane", C.c_float * 4),
+                ("best_sample", C.c_int), ("inliers", C.c_int), ("appended", C.c_int)]
+
+
+class PlaneFitArgs(C.Structure):
+    """nalo_plane_fit_args (include/nalo_gpu.h)"""
+    _fields_ = [("threshold", C.c_float), ("min_points", C.c_int), ("n_samples", C.c_int), ("draws", C.POINTER(C.c_uint32)), ("append", C.c_int)]
+
+
+PLANE_DTYPE = np.dtype([("mask_value", np.float32), ("n", np.int32), ("n_cloud", np.int32), ("rect", np.int32, 4), ("fitted", np.int32), ("plane", np.float32, 4),
+                        ("best_sample", np.int32), ("inliers", np.int32), ("appended", np.int32)])
+assert PLANE_DTYPE.itemsize == C.sizeof(PlaneCluster)
 
 
 class Settings(C.Structure):
@@ -148,6 +164,9 @@ def load():
                                             c_u8p, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp, c_dp, c_dp, c_dp]
     L.nalo_init_do_step.argtypes = [vp, C.c_int, c_u8p, c_fp, c_fp, c_fp, C.c_float, c_fp, c_fp]
     L.nalo_trk_append_plane_points.argtypes = [vp, c_fp, C.c_float, C.c_int, c_ip, c_ip]
+    L.nalo_trk_fit_planes.argtypes = [vp, C.POINTER(PlaneFitArgs), C.c_int, vp, c_ip]
+    L.nalo_dense_fit_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneFitArgs), C.c_int, vp, c_ip]
+    L.nalo_plane_fit_members.argtypes = [vp, C.c_int, c_ip, c_ip]
     L.nalo_undist_set.argtypes = [vp, C.c_int, C.c_int, c_fp, C.c_int, c_fp, C.c_int, c_fp, c_fp]
     L.nalo_frame_upload_raw.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, c_u8p, c_u8p, c_fp]
     L.nalo_frame_upload_raw_async.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, c_fp]
@@ -648,6 +667,34 @@ class Context:
                                             cap, _i(rect), _i(u), _i(v), _f(idp), _f(col), _u8(bgr), _i(n), _i(acc)))
         k = min(int(n[0]), cap)
         return dict(n=int(n[0]), accept=int(acc[0]), rect=rect, u=u[:k], v=v[:k], idepth=idp[:k], color=col[:k], bgr=bgr[:k])
+
+    def _fit_planes(self, call, draws, threshold, min_points, append, cap):
+        """-> (records as a PLANE_DTYPE array, n_clusters); draws=None passes a NULL stream, a cap below the need raises NaloError with .n_clusters set"""
+        d = None if draws is None else np.ascontiguousarray(draws, np.uint32)
+        n_samples = self._plane_n_samples if d is None else len(d) // 3
+        a = PlaneFitArgs(float(threshold), int(min_points), int(n_samples), None if d is None else d.ctypes.data_as(C.POINTER(C.c_uint32)), int(append))
+        out = np.zeros(max(cap, 1), PLANE_DTYPE)
+        n = np.zeros(1, np.int32)
+        rc = call(C.byref(a), cap, out.ctypes.data_as(C.c_void_p) if cap > 0 else None, _i(n))
+        self.plane_n_clusters = int(n[0])
+        self._ck(rc)
+        return out[:int(n[0])].copy(), int(n[0])
+
+    _plane_n_samples = 50
+
+    def trk_fit_planes(self, draws, threshold=0.01, min_points=10, append=0, cap=2048):
+        """makeMaskDistMap + fitPlane on the level-0 cloud (nalo_trk_fit_planes) -> (records, n_clusters); self.plane_n_clusters holds the count after a refusal too"""
+        return self._fit_planes(lambda a, cap_, o, n: self.L.nalo_trk_fit_planes(self.h_, a, cap_, o, n), draws, threshold, min_points, append, cap)
+
+    def dense_fit_planes(self, host_frame, draws, threshold=0.01, min_points=10, cap=2048):
+        """the same on the window points and resident immature points of one host frame (nalo_dense_fit_planes)"""
+        return self._fit_planes(lambda a, cap_, o, n: self.L.nalo_dense_fit_planes(self.h_, int(host_frame), a, cap_, o, n), draws, threshold, min_points, 0, cap)
+
+    def plane_fit_members(self, n_input, n_members):
+        """the last call's member lists (nalo_plane_fit_members) -> (cluster_of[n_input], order[n_members])"""
+        cl, order = np.full(max(n_input, 1), -1, np.int32), np.zeros(max(n_input, 1), np.int32)     # the members are at most the input
+        self._ck(self.L.nalo_plane_fit_members(self.h_, int(n_input), _i(cl), _i(order)))
+        return cl[:n_input], order[:n_members]
 
     def trk_append_plane_points(self, dirv, dis, ref_color, rect):
         n = np.zeros(1, np.int32)

@@ -869,6 +869,22 @@ static int do_step(nalo_ctx* c, float fC, float fT, float fR, float fA, float fD
 
 // nalo_trk_set_ref_from_window (host_api.hip): the inputs of makeCoarseDepthL0 gathered on the device, on c->stream behind the window's last fix pass. *dev =
 // {Ku | Kv | new_idepth | HdiF}, *n entries each (one per point, holes included: ba_trk_ref_gather_kernel), *slot = the newest frame's slot.
+// the reference's loop `for fh in frameHessians, for ph in fh->pointHessians` (CoarseTracker.cpp:388-390, MapPoint.cpp:246) = host index, then submission order:
+// entry k -> device slot, kept on the device until the point list changes
+static int ref_kmap_build(nalo_ctx* c, BAWindow& w) {
+    if (w.ref_kmap_ok) return NALO_OK;
+    const int P = w.P;
+    std::vector<int> start(w.W + 1, 0);
+    for (int p = 0; p < P; ++p) start[w.blk_host_h[w.p2d[p] / kBlk] + 1]++;
+    for (int h = 0; h < w.W; ++h) start[h + 1] += start[h];
+    w.ref_kmap_h.assign(P, 0);
+    for (int p = 0; p < P; ++p) { const int d = w.p2d[p]; w.ref_kmap_h[start[w.blk_host_h[d / kBlk]]++] = d; }
+    NALO_HIP(c, w.ref_kmap.reserve(P));
+    NALO_HIP(c, hipMemcpyAsync(w.ref_kmap.p, w.ref_kmap_h.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));   // the host copy lives until the next rebuild
+    w.ref_kmap_ok = true;
+    return NALO_OK;
+}
+
 int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev) {
     if (!c->ba || c->ba->W < 2 || !c->ba->points_set || !c->ba->res_set || c->ba->P == 0)
         return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: no window or no points");
@@ -878,23 +894,34 @@ int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev) {
     const int s = w.frames[w.W - 1].slot;
     if (!c->slots[s].valid) return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_window: the newest frame's slot has no pyramid");
     const int P = w.P;
-    if (!w.ref_kmap_ok) {
-        // the reference's loop: for fh in frameHessians, for ph in fh->pointHessians (CoarseTracker.cpp:388-390) = host index, then submission order
-        std::vector<int> start(w.W + 1, 0);
-        for (int p = 0; p < P; ++p) start[w.blk_host_h[w.p2d[p] / kBlk] + 1]++;
-        for (int h = 0; h < w.W; ++h) start[h + 1] += start[h];
-        w.ref_kmap_h.assign(P, 0);
-        for (int p = 0; p < P; ++p) { const int d = w.p2d[p]; w.ref_kmap_h[start[w.blk_host_h[d / kBlk]]++] = d; }
-        NALO_HIP(c, w.ref_kmap.reserve(P));
-        NALO_HIP(c, hipMemcpyAsync(w.ref_kmap.p, w.ref_kmap_h.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));   // the host copy lives until the next rebuild
-        w.ref_kmap_ok = true;
-    }
+    { const int rc = ref_kmap_build(c, w); if (rc) return rc; }
     // HdiF as nalo_ba_get_points would return it: after an explicit nalo_ba_linearize, the accumulation of that linearisation (the same on-demand pass)
     if (w.have_lin && !w.have_sc && w.pt_acc_on_read) { int rc = sc_async(c, 1, 1.f, 0); if (rc) return rc; }
     NALO_HIP(c, w.ref_in.reserve((size_t)4 * P));
     ba_launch_trk_ref_gather(c->stream, w.dev, w.ref_kmap.p, w.ref_in.p);
     NALO_HIP(c, hipGetLastError());
     *slot = s; *n = P; *dev = w.ref_in.p;
+    return NALO_OK;
+}
+
+int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, int* seg, int* n_valid, const float4** geo, const uint8_t** flags) {
+    if (!c->ba || c->ba->W < 1 || !c->ba->points_set) return fail(c, NALO_ERR_STATE, "nalo_dense_fit_planes: no window or no points");
+    BAWindow& w = *c->ba;
+    if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_dense_fit_planes: the window is sharded (a rank holds only its own points)");
+    if (host_frame < 0 || host_frame >= w.W) return fail(c, NALO_ERR_ARG, "nalo_dense_fit_planes: host_frame outside the window");
+    *slot = w.frames[host_frame].slot;
+    *kmap = nullptr; *seg = 0; *n_valid = 0; *geo = w.pt_geo.p; *flags = w.pt_flags.p;
+    if (w.P == 0) return NALO_OK;
+    { const int rc = ref_kmap_build(c, w); if (rc) return rc; }
+    const int row = w.row_of.empty() ? host_frame : w.row_of[host_frame];      // the device host index of the frame
+    int first = -1, cnt = 0, valid = 0;
+    for (int k = 0; k < w.P; ++k) {
+        const int d = w.ref_kmap_h[k];
+        if (w.blk_host_h[d / kBlk] != row) continue;
+        if (first < 0) first = k;
+        ++cnt; valid += (w.flags_h[d] & PT_VALID) != 0;
+    }
+    if (cnt) { *kmap = w.ref_kmap.p + first; *seg = cnt; *n_valid = valid; }
     return NALO_OK;
 }
 

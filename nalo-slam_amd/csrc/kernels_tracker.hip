@@ -429,13 +429,13 @@ __global__ __launch_bounds__(1024) void trk_scan_all_kernel(TrkLevels P, int* __
 // point k at index pc_n + 1 + k and then counts pc_n += 1 per point (:646-650): slot [old pc_n] is never written (stale heap there, ZERO here) and the last
 // sampled point falls just outside the count. Reproduced. ONE workgroup: the candidates (multiples of 5: <= w h / 25) are compacted in order, chunk by
 // chunk, with ballot counts and an LDS scan over the 16 waves.
-__global__ __launch_bounds__(1024) void trk_append_plane_kernel(const float* __restrict__ mask, const float4* __restrict__ dIref, int w, float d0, float d1, float d2, float dis,
-                                                                float Ki00, float Ki02, float Ki11, float Ki12, float refColor, int x0, int nx, int y0, int ny, int n0,
-                                                                float* __restrict__ pu, float* __restrict__ pv, float* __restrict__ pid, float* __restrict__ pcol, int* __restrict__ n_out) {
-    __shared__ int wave_cnt[16];
-    __shared__ int base_s;
+// One cluster's points, by all 1024 lanes of the workgroup (wave_cnt[16] and base_s in LDS); returns the growth of pc_n.
+__device__ __forceinline__ int trk_append_plane_body(int* wave_cnt, int* base_s, const float* __restrict__ mask, const float4* __restrict__ dIref, int w, float d0, float d1, float d2,
+                                                     float dis, float Ki00, float Ki02, float Ki11, float Ki12, float refColor, int x0, int nx, int y0, int ny, int n0,
+                                                     float* __restrict__ pu, float* __restrict__ pv, float* __restrict__ pid, float* __restrict__ pcol) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) { base_s = 0; pu[n0] = 0.f; pv[n0] = 0.f; pid[n0] = 0.f; pcol[n0] = 0.f; }
+    __syncthreads();
+    if (tid == 0) { *base_s = 0; pu[n0] = 0.f; pv[n0] = 0.f; pid[n0] = 0.f; pcol[n0] = 0.f; }
     __syncthreads();
     // dir^T * Ki as Eigen evaluates it (row vector times matrix, then times the point): t = dir^T Ki
     const float t0 = d0 * Ki00 + d1 * 0.f + d2 * 0.f, t1 = d0 * 0.f + d1 * Ki11 + d2 * 0.f, t2 = d0 * Ki02 + d1 * Ki12 + d2 * 1.f;
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(1024) void trk_append_plane_kernel(const float* __r
         const unsigned long long b = __ballot(take);
         if (lane == 0) wave_cnt[wv] = __popcll(b);
         __syncthreads();
-        int off = base_s;
+        int off = *base_s;
         for (int k = 0; k < wv; ++k) off += wave_cnt[k];
         if (take) {
             const int at = n0 + 1 + off + __popcll(b & ((1ull << lane) - 1ull));
@@ -456,10 +456,53 @@ __global__ __launch_bounds__(1024) void trk_append_plane_kernel(const float* __r
             pu[at] = (float)x; pv[at] = (float)y; pid[at] = nid; pcol[at] = dIref[x + y * w].x;
         }
         __syncthreads();
-        if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wave_cnt[k]; base_s += s; }
+        if (tid == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wave_cnt[k]; *base_s += s; }
         __syncthreads();
     }
-    if (tid == 0) *n_out = base_s;
+    return *base_s;
+}
+__global__ __launch_bounds__(1024) void trk_append_plane_kernel(const float* __restrict__ mask, const float4* __restrict__ dIref, int w, float d0, float d1, float d2, float dis,
+                                                                float Ki00, float Ki02, float Ki11, float Ki12, float refColor, int x0, int nx, int y0, int ny, int n0,
+                                                                float* __restrict__ pu, float* __restrict__ pv, float* __restrict__ pid, float* __restrict__ pcol, int* __restrict__ n_out) {
+    __shared__ int wave_cnt[16];
+    __shared__ int base_s;
+    const int added = trk_append_plane_body(wave_cnt, &base_s, mask, dIref, w, d0, d1, d2, dis, Ki00, Ki02, Ki11, Ki12, refColor, x0, nx, y0, ny, n0, pu, pv, pid, pcol);
+    if (threadIdx.x == 0) *n_out = added;
+}
+// nalo_trk_fit_planes(append = 1): the loop of CoarseTracker.cpp:582-666 over the cluster records the fit has just written, in their order, each cluster with the
+// checks and the arithmetic of nalo_trk_append_plane_points on that record (the same body). hdr[1] != 0: the fit refused; hdr[4]: clusters; nothing is appended
+// with fewer than 4 (:563) or when the caller's array cannot take every record. hdr[5] receives pc_n[0]; a cluster the buffer cannot hold sets bit 4 of hdr[1] and ends the loop.
+__global__ __launch_bounds__(1024) void trk_append_clusters_kernel(const float* __restrict__ mask, const float4* __restrict__ dIref, int w, int h, float Ki00, float Ki02, float Ki11,
+                                                                   float Ki12, nalo_plane_cluster* __restrict__ rec, int* __restrict__ hdr, int cap_clusters, int n0, int pc_cap,
+                                                                   float* __restrict__ pu, float* __restrict__ pv, float* __restrict__ pid, float* __restrict__ pcol) {
+    __shared__ int wave_cnt[16];
+    __shared__ int base_s;
+    const int C = hdr[4];
+    int n_cur = n0;
+    if (hdr[1] == 0 && C >= 4 && C <= cap_clusters) {
+        for (int r = 0; r < C; ++r) {                                   // every condition below is uniform over the workgroup
+            const int fitted = rec[r].fitted, minx = rec[r].rect[0], maxx = rec[r].rect[1], miny = rec[r].rect[2], maxy = rec[r].rect[3];
+            const float mv = rec[r].mask_value, dis = rec[r].plane[3];
+            const int refMaskColor = (int)fminf(fmaxf(mv, -2.0e9f), 2.0e9f);                      // `int refMaskColor = clusters[i][0][3]` (:632)
+            if (!fitted || maxx > w - 1 || minx < 1 || maxy > h - 1 || miny < 1 || refMaskColor == 0 || dis == 0.f) continue;
+            const int x0 = ((minx + 4) / 5) * 5, y0 = ((miny + 4) / 5) * 5;
+            const int nx = x0 < maxx ? (maxx - 1 - x0) / 5 + 1 : 0, ny = y0 < maxy ? (maxy - 1 - y0) / 5 + 1 : 0;
+            if ((long long)n_cur + 2 + (long long)nx * ny > (long long)pc_cap) { if (threadIdx.x == 0) hdr[1] |= 4; break; }
+            if (nx == 0 || ny == 0) continue;
+            const int added = trk_append_plane_body(wave_cnt, &base_s, mask, dIref, w, rec[r].plane[0], rec[r].plane[1], rec[r].plane[2], dis, Ki00, Ki02, Ki11, Ki12,
+                                                    (float)refMaskColor, x0, nx, y0, ny, n_cur, pu, pv, pid, pcol);
+            if (threadIdx.x == 0) rec[r].appended = added;
+            n_cur += added;
+        }
+    }
+    if (threadIdx.x == 0) hdr[5] = n_cur;
+}
+int trk_append_clusters_launch(nalo_ctx* c, const float* mask, const float4* dIref, nalo_plane_cluster* rec, int* hdr, int cap_clusters) {
+    const float fx = c->fx[0], fy = c->fy[0], cx = c->cx[0], cy = c->cy[0];
+    trk_append_clusters_kernel<<<1, 1024, 0, c->stream>>>(mask, dIref, c->w, c->h, 1.0f / fx, -cx / fx, 1.0f / fy, -cy / fy, rec, hdr, cap_clusters, c->pc_n[0], (int)c->pc_u[0].cap,
+                                                          c->pc_u[0].p, c->pc_v[0].p, c->pc_id[0].p, c->pc_col[0].p);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
 }
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev) {
     const float fx = c->fx[0], fy = c->fy[0], cx = c->cx[0], cy = c->cy[0];

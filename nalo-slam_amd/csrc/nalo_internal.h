@@ -159,6 +159,10 @@ struct nalo_ctx {
     std::vector<int> act_sel_h, act_result_h;                                    // its sel / result as they went to the caller
     int act_pend_n = -1, act_pend_W = 0; unsigned act_pend_epoch = 0;            // n = -1: none pending; the window's frames (BAWindow::frames_epoch) when it was made
 
+    // ---- mask clusters and their planes (kernels_plane.hip): the call's device scratch (the member lists of the last call stay in it), rocPRIM's sort storage,
+    // the pinned block the draws go down and the records come up through; plane_last_n = -1: no completed call
+    nalo::DevBuf<unsigned> plane_w; nalo::DevBuf<unsigned char> plane_sort; nalo::HostBuf<int> plane_host; int plane_last_n = -1, plane_last_members = 0;
+
     // ---- BA (opaque; defined in host_ba.hip)
     nalo::BAWindow* ba = nullptr;
     nalo::PixSel* pixsel = nullptr;          // pixel selector state (kernels_pixsel.hip)
@@ -272,6 +276,9 @@ int imm_carry_launch(nalo_ctx* c, const ImmCarryParams& P);
 bool pixsel_last_list(nalo_ctx* c, int slot, const int** dev, int* n_dev, const int** host_live, int* n_live);
 // host_ba.hip: nalo_trk_set_ref_from_window's inputs gathered from the window on c->stream ({Ku | Kv | new_idepth | HdiF}, *n each, holes included)
 int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
+// host_ba.hip: nalo_dense_fit_planes' window half. The device slots of host_frame's points in submission order (*kmap, *seg entries: a segment of the map
+// nalo_trk_set_ref_from_window keeps), how many of them are valid (the host's mirror of the flags), the arrays the gather reads and the frame's slot
+int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, int* seg, int* n_valid, const float4** geo, const uint8_t** flags);
 // host_ba.hip
 void ba_destroy(nalo_ctx* c);
 // host_rccl.hip
@@ -326,6 +333,8 @@ int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double a
 // kernels_tracker.hip
 int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi);
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev);
+// the append loop of CoarseTracker.cpp:582-666 over the records nalo_trk_fit_planes has just written on the device (hdr: kernels_plane.hip's header words)
+int trk_append_clusters_launch(nalo_ctx* c, const float* mask, const float4* dIref, nalo_plane_cluster* rec, int* hdr, int cap_clusters);
 int trk_eval_launch(nalo_ctx* c, int slot_new, int lvl, const float RKi[9], const float t[3], const float Ki[9],
                     float affa, float affb, float b0, float cutoff, float maxEnergy, double out64[64]);
 
