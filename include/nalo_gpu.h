@@ -376,6 +376,49 @@ int nalo_ba_carry_window(nalo_ctx* ctx, const nalo_frame_state* entering /* NULL
 int nalo_ba_carry_map(nalo_ctx* ctx, int* old_p /* P_new */);
 int nalo_ba_carry_last(nalo_ctx* ctx, int stats[4]);
 
+/* The beginning of that chain: the first window issued from the initialiser's level-0 points on the device, instead of nalo_init_get_points -> the host loop of
+ * FullSystem::initializeFromInitializer (FullSystem.cpp:1567-1654) -> nalo_imm_create -> nalo_ba_set_window + nalo_ba_set_points + nalo_ba_set_residuals +
+ * nalo_ba_set_point_history. A window holds at least two frames, and the reference inserts the second one right after initializeFromInitializer
+ * (deliverTrackedFrame(fh, true) -> makeKeyFrame, FullSystem.cpp:1327-1348): the call does both steps and issues the window {firstFrame, newFrame}. The result is,
+ * in everything a caller can read or compute from, the window that re-issue would build. Arithmetic is the reference's, operation for operation.
+ *
+ * nalo_ba_window_from_initializer(ctx, a)
+ *   Scale     (:1589-1595) on the initialiser's current level-0 state (the host mirror is uploaded first when it is the newer side): sumID = 1e-5f, then
+ *             sumID += iR[i] for i = 0 .. n-1 in float and in index order - one wave on the device, no tree and no atomics, the bits are the sequential loop's -;
+ *             numID = 1e-5f, then += 1 n times in float; rescaleFactor = 1 / (sumID / numID).
+ *   Keep rule (:1598, 1607) keepPercentage = desired_point_density / n (float / int); point i is skipped iff (float)draws[i] / 2147483648.0f > keepPercentage.
+ *             draws[i] is the rand() of the caller's libc stream that the reference consumes for point i: every level-0 point consumes exactly one, in index
+ *             order, whatever becomes of it. 2147483648.0f is (float)RAND_MAX of a libc with 31-bit rand(); other values of RAND_MAX are the caller's to rescale.
+ *   Points    (:1610-1626) a kept point i is constructed at ui = (int)(u[i] + 0.5f), vi = (int)(v[i] + 0.5f) on level 0 of first.slot as the slot holds it at call
+ *             time (ImmaturePoint::ImmaturePoint, as nalo_imm_create) and rejected when its energyTH is not finite. The others become window points in index
+ *             order: host 0, u = (float)ui, v = (float)vi, color and weights from the constructor, idepth = idepth_zero = iR[i] * rescaleFactor (the idepth of
+ *             nalo_ba_set_points), the depth prior set. Layout: exactly nalo_ba_set_points' for that point list (one shared function).
+ *   Frames    (:1631-1648, setEvalPT_scaled) first: worldToCam_evalPT = identity; entering: thisToNext with its translation divided by rescaleFactor (promoted to
+ *             double), inverted to camToWorld and inverted again; state = state_zero = 0 for both. slot, frame_id, ab_exposure and frameEnergyTH are the caller's;
+ *             evalPT, state and state_zero are written back into *a. calib / calib_zero as nalo_ba_set_window; HM / bM start at zero whatever
+ *             nalo_ba_set_prior_carry says; adjoints and precalc values as nalo_ba_set_window computes them.
+ *   Residuals (:1335-1348) every point gets one residual, to frame 1, as nalo_ba_set_residuals leaves it.
+ *   History   numGood = 0, last_target = {1, -1}, last_state = {IN, IN}. The IN of entry [1] is the reference's: PointHessian never initialises lastResiduals, so
+ *             the pair is value-initialised to (0, ResState(0) = IN) and then shifted - not the (-1, OOB) nalo_ba_set_point_history's NULL default gives.
+ *   The initialiser is not modified; a second call gives the same window. nalo_init_set_first must have been called; `snapped` is the caller's decision.
+ *   Bus       no float array of points or residuals crosses in either direction. Up: one byte per level-0 point (the non-finite rejections) and sumID, in one
+ *             copy the call waits for - its only wait besides what nalo_ba_set_window's frame half does -; down: the integer map (4 bytes per window slot) and
+ *             the block tables, stream-ordered from pinned memory as in nalo_ba_carry_window.
+ *   NALO_ERR_ARG: a NULL argument; n_draws != numPoints[0]; desired_point_density not finite or <= 0; first.slot is not the initialiser's first slot;
+ *             first.slot == entering.slot. NALO_ERR_STATE: no initialiser; an entering slot without a pyramid; no point kept; a sharded context; a context
+ *             whose exchange failed. A refused call leaves the context's window exactly as it was.
+ * nalo_ba_init_window_map    src[p] = the level-0 index of window point p (submission order; strictly increasing).
+ * nalo_ba_init_window_last   scale = {sumID, numID, rescaleFactor}, stats = {n, skipped by their draw, rejected as non-finite, P} of the last call; either may be NULL. */
+typedef struct nalo_init_window_args {
+    nalo_frame_state first, entering;  /* in: slot, frame_id, ab_exposure, frameEnergyTH.  out: worldToCam_evalPT, state, state_zero as the call set them */
+    double calib[4], calib_zero[4];    /* as nalo_ba_set_window */
+    float desired_point_density;       /* setting_desiredPointDensity */
+    int n_draws; const int* draws;     /* draws[i] = rand() of the caller's libc stream, one per level-0 point, in index order (FullSystem.cpp:1607) */
+} nalo_init_window_args;
+int nalo_ba_window_from_initializer(nalo_ctx* ctx, nalo_init_window_args* a);
+int nalo_ba_init_window_map(nalo_ctx* ctx, int* src /* P: level-0 index of window point p, submission order */);
+int nalo_ba_init_window_last(nalo_ctx* ctx, float scale[3] /* sumID, numID, rescaleFactor */, int stats[4] /* n, skipped by draw, rejected non-finite, P */);
+
 /* read-back of window state (host pointers, any may be NULL) */
 int nalo_ba_get_frames(nalo_ctx* ctx, nalo_frame_state* frames /* W */, double* worldToCam /* W x 12 PRE_worldToCam */,
                        double calib[4]);

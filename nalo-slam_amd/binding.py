@@ -35,11 +35,18 @@ EXPORTS = [
     "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
     "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
+    "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
+
+
+class InitWindowArgs(C.Structure):
+    """nalo_init_window_args (include/nalo_gpu.h)"""
+    _fields_ = [("first", FrameState), ("entering", FrameState), ("calib", C.c_double * 4), ("calib_zero", C.c_double * 4),
+                ("desired_point_density", C.c_float), ("n_draws", C.c_int), ("draws", c_ip)]
 
 
 class ImmCarryArgs(C.Structure):
@@ -144,6 +151,9 @@ def load():
     L.nalo_ba_carry_window.argtypes = [vp, C.POINTER(FrameState), C.c_int]
     L.nalo_ba_carry_map.argtypes = [vp, c_ip]
     L.nalo_ba_carry_last.argtypes = [vp, c_ip]
+    L.nalo_ba_window_from_initializer.argtypes = [vp, C.POINTER(InitWindowArgs)]
+    L.nalo_ba_init_window_map.argtypes = [vp, c_ip]
+    L.nalo_ba_init_window_last.argtypes = [vp, c_fp, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -593,6 +603,45 @@ class Context:
         m = np.zeros(self.P, np.int32)
         self._ck(self.L.nalo_ba_carry_map(self.h_, _i(m)))
         return m
+
+    def init_window_args(self, first, entering, draws, density=2000.0, calib=None, calib_zero=None):
+        """nalo_init_window_args from two FrameStates (slot, frame_id, ab_exposure, frameEnergyTH are read), the draws and setting_desiredPointDensity; the
+        draws array is kept alive by the returned object"""
+        a = InitWindowArgs()
+        C.memmove(C.byref(a.first), C.byref(first), C.sizeof(FrameState))
+        C.memmove(C.byref(a.entering), C.byref(entering), C.sizeof(FrameState))
+        cal = np.asarray(self.K if calib is None else calib, np.float64)
+        calz = cal if calib_zero is None else np.asarray(calib_zero, np.float64)
+        for k in range(4):
+            a.calib[k], a.calib_zero[k] = float(cal[k]), float(calz[k])
+        a.desired_point_density = float(density)
+        a._draws = None if draws is None else np.ascontiguousarray(draws, np.int32)
+        a.n_draws = 0 if draws is None else len(a._draws)
+        a.draws = None if draws is None else _i(a._draws)
+        return a
+
+    def ba_window_from_initializer(self, first, entering, draws, density=2000.0, calib=None, calib_zero=None):
+        """the first window {first, entering} issued from the initialiser's level-0 points on the device (nalo_ba_window_from_initializer)
+        -> (the two FrameStates as the call set them, (sumID, numID, rescaleFactor), (n, skipped by draw, rejected non-finite, P))"""
+        a = self.init_window_args(first, entering, draws, density, calib, calib_zero)
+        self._ck(self.L.nalo_ba_window_from_initializer(self.h_, C.byref(a)))
+        scale, stats = self.ba_init_window_last()
+        self.W, self.P = 2, int(stats[3])
+        out = [FrameState(), FrameState()]
+        C.memmove(C.byref(out[0]), C.byref(a.first), C.sizeof(FrameState))
+        C.memmove(C.byref(out[1]), C.byref(a.entering), C.sizeof(FrameState))
+        return out, scale, stats
+
+    def ba_init_window_map(self):
+        """level-0 index of every point of the window issued from the initialiser, in submission order"""
+        m = np.zeros(self.P, np.int32)
+        self._ck(self.L.nalo_ba_init_window_map(self.h_, _i(m)))
+        return m
+
+    def ba_init_window_last(self):
+        scale, stats = np.zeros(3, np.float32), np.zeros(4, np.int32)
+        self._ck(self.L.nalo_ba_init_window_last(self.h_, _f(scale), _i(stats)))
+        return scale, tuple(int(x) for x in stats)
 
     def ba_get_frames(self):
         arr = (FrameState * self.W)()

@@ -101,6 +101,9 @@ struct BAWindow {
     unsigned frames_epoch = 0;                                      // counts the changes of the frame list (a pending activation result belongs to one value)
     HostBuf<int> carry_host; DevBuf<int> carry_src; Event ev_carry; // [trow 16 | src Ppad | blk_host | host_blk | sc_grp | blk_order], and the device copy of [trow | src]
     std::vector<int> carry_map_h; int carry_stats[4] = {}; bool carried = false;   // nalo_ba_carry_map / nalo_ba_carry_last of the last carry
+    // nalo_ba_window_from_initializer: [the constructor's verdict per level-0 point | sumID] on the device and in pinned memory, and what the last call reports
+    DevBuf<uint8_t> iw_scr; HostBuf<uint8_t> iw_host;
+    std::vector<int> iw_map_h; float iw_scale[3] = {}; int iw_stats[4] = {}; bool iw_have = false;   // nalo_ba_init_window_map / nalo_ba_init_window_last
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -2162,6 +2165,135 @@ int nalo_ba_carry_last(nalo_ctx* c, int stats[4]) {
     if (!c || !c->ba || !c->ba->carried) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_last: no carry has been made");
     if (!stats) return fail(c, NALO_ERR_ARG, "nalo_ba_carry_last: bad argument");
     std::memcpy(stats, c->ba->carry_stats, sizeof(c->ba->carry_stats));
+    return NALO_OK;
+}
+
+// ---- the device chain's beginning: FullSystem::initializeFromInitializer (FullSystem.cpp:1567-1654) and the insertion of the second frame that follows it
+// (makeKeyFrame, :1327-1348) as one issue of the window {firstFrame, newFrame} from the initialiser's level-0 arrays where they are. The ordered sum of iR and
+// the constructor's verdicts run first (kernels_init_window.hip) and come up in one copy - n bytes and one float, the call's only wait -; the host evaluates the
+// keep rule on the caller's draws, lays the kept points out with nalo_ba_set_points' function and sends the map and the block tables as nalo_ba_carry_window
+// does; one kernel writes every point, slot and history array. Everything that can refuse the call is decided before the window is touched.
+int nalo_ba_window_from_initializer(nalo_ctx* c, nalo_init_window_args* a) {
+    const char* const who = "nalo_ba_window_from_initializer";
+    if (!c || !a) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
+    InitLevel0 V;
+    { const int rc = init_level0(c, who, &V); if (rc) return rc; }
+    const int n = V.n;
+    if (!a->draws || a->n_draws != n) return fail(c, NALO_ERR_ARG, std::string(who) + ": one draw per level-0 point of the initialiser (n_draws != numPoints[0])");
+    if (!std::isfinite(a->desired_point_density) || !(a->desired_point_density > 0)) return fail(c, NALO_ERR_ARG, std::string(who) + ": desired_point_density must be finite and positive");
+    if (a->first.slot != V.slot_first) return fail(c, NALO_ERR_ARG, std::string(who) + ": first.slot is not the slot nalo_init_set_first was given");
+    if (a->first.slot == a->entering.slot) return fail(c, NALO_ERR_ARG, std::string(who) + ": the entering frame needs a slot of its own");
+    for (const int s : {a->first.slot, a->entering.slot})
+        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid) return fail(c, NALO_ERR_STATE, std::string(who) + ": frame slot has no pyramid");
+    if (c->xchg_failed) return fail(c, NALO_ERR_STATE, std::string(who) + ": a cross-rank sum of this context failed earlier; build the window on a new context");
+    if (c->ba && c->ba->hook) return fail(c, NALO_ERR_STATE, std::string(who) + ": the context is sharded (every rank would issue all points; set its own share with nalo_ba_set_points)");
+    if (n <= 0) return fail(c, NALO_ERR_STATE, std::string(who) + ": no point kept (the initialiser has no level-0 point)");
+    HostTimer ht(c, "ba_window_from_initializer");
+    if (!c->ba) c->ba = new BAWindow();
+    BAWindow& w = *c->ba;
+    prelaunch_cancel(c);                                            // nothing of an old window may still wait on a gate when the stream is waited for
+    // ---- scale (:1589-1595) and the constructor's verdicts (:1612), then the call's one wait
+    const size_t o_sum = ((size_t)n + 3) & ~(size_t)3, scr = o_sum + 4;
+    NALO_HIP(c, w.iw_scr.reserve(scr)); NALO_HIP(c, w.iw_host.reserve(scr));
+    { const int rc = init_window_scan_launch(c, c->slots[V.slot_first].dI[0].p, V.u, V.v, V.iR, n, w.iw_scr.p, reinterpret_cast<float*>(w.iw_scr.p + o_sum)); if (rc) return rc; }
+    NALO_HIP(c, hipMemcpyAsync(w.iw_host.p, w.iw_scr.p, scr, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    float sumID; std::memcpy(&sumID, w.iw_host.p + o_sum, 4);
+    float numID = 1e-5f;
+    for (int i = 0; i < n; ++i) numID++;
+    const float rescaleFactor = 1 / (sumID / numID);
+    // ---- the keep rule (:1598, 1607): one draw per point, in index order
+    const float keepPercentage = a->desired_point_density / n;
+    std::vector<int> kept;
+    int skipped = 0, rejected = 0;
+    for (int i = 0; i < n; ++i) {
+        if ((float)a->draws[i] / 2147483648.0f > keepPercentage) { ++skipped; continue; }      // rand() / (float)RAND_MAX of a 31-bit libc
+        if (!w.iw_host.p[i]) { ++rejected; continue; }
+        kept.push_back(i);
+    }
+    const int P = (int)kept.size();
+    if (P == 0) return fail(c, NALO_ERR_STATE, std::string(who) + ": no point kept");
+    // ---- frames (:1631-1648, setEvalPT_scaled with AffLight(0, 0)): state = state_zero = 0 at both linearisation points
+    nalo_frame_state fs[2] = {a->first, a->entering};
+    for (auto& f : fs) { std::memset(f.state, 0, sizeof(f.state)); std::memset(f.state_zero, 0, sizeof(f.state_zero)); }
+    std::memcpy(fs[0].worldToCam_evalPT, SE3::identity().m, 96);
+    {
+        SE3 firstToNew = SE3::from(V.thisToNext);
+        for (int i = 0; i < 3; ++i) firstToNew.m[i * 4 + 3] /= (double)rescaleFactor;
+        const SE3 camToWorld = firstToNew.inverse();                // shell->camToWorld, then setEvalPT_scaled(camToWorld.inverse(), .): two inversions, as written
+        std::memcpy(fs[1].worldToCam_evalPT, camToWorld.inverse().m, 96);
+    }
+    // ---- from here on the window is re-issued (as nalo_ba_set_window + nalo_ba_set_points + nalo_ba_set_residuals + nalo_ba_set_point_history would)
+    w.carry_ok = false; c->act_pend_n = -1;
+    { const int rc = window_frames(c, 2, fs, a->calib, a->calib_zero, false); if (rc) return rc; }
+    w.HM.assign((size_t)w.n * w.n, 0.0); w.bM.assign(w.n, 0.0);     // a fresh EnergyFunctional: no prior, whatever nalo_ba_set_prior_carry says
+    std::vector<int> host(P, 0);
+    std::vector<unsigned long long> key(P);
+    for (int q = 0; q < P; ++q) {
+        const int ui = (int)(V.u_host[kept[q]] + 0.5f), vi = (int)(V.v_host[kept[q]] + 0.5f);
+        key[q] = hilbert_cell_key(c, (float)ui, (float)vi);        // host 0
+    }
+    w.points_set = false; w.res_set = false;
+    PointLayout L;
+    { const int rc = build_point_layout(c, P, host.data(), key.data(), L); if (rc) return rc; }
+    const size_t N = w.Ppad;
+    NALO_HIP(c, w.pt_numgood.reserve(N)); NALO_HIP(c, w.pt_last.reserve(N));
+    // the map and the block tables: one pinned block, stream-ordered copies (the staging of nalo_ba_carry_window)
+    const int W = 2;
+    const size_t o_bh = N, o_hb = o_bh + w.nblocks, o_grp = o_hb + (W + 1), o_ord = o_grp + (W + 1), words = o_ord + L.order.size();
+    if (w.ev_carry) NALO_HIP(c, hipEventSynchronize(w.ev_carry)); else NALO_HIP(c, w.ev_carry.create(hipEventDisableTiming));
+    NALO_HIP(c, w.carry_host.reserve(words)); NALO_HIP(c, w.carry_src.reserve(N));
+    int* hb = w.carry_host.p;
+    w.flags_h.assign(N, 0);
+    for (size_t d = 0; d < N; ++d) {
+        const int p = w.d2p[d];
+        hb[d] = p < 0 ? -1 : kept[p];
+        if (p >= 0) w.flags_h[d] = PT_VALID | PT_HAS_PRIOR;
+    }
+    std::memcpy(hb + o_bh, w.blk_host_h.data(), (size_t)w.nblocks * 4); std::memcpy(hb + o_hb, w.host_blk_h.data(), (size_t)(W + 1) * 4);
+    std::memcpy(hb + o_grp, L.grp.data(), (size_t)(W + 1) * 4); std::memcpy(hb + o_ord, L.order.data(), L.order.size() * 4);
+    NALO_HIP(c, hipMemcpyAsync(w.carry_src.p, hb, N * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.blk_host.p, hb + o_bh, (size_t)w.nblocks * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.host_blk.p, hb + o_hb, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.sc_grp.p, hb + o_grp, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.blk_order.p, hb + o_ord, L.order.size() * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipEventRecord(w.ev_carry, c->stream));
+    // ---- one launch: construct, scale, pad, zero
+    InitWindowDev A{};
+    A.src = w.carry_src.p; A.Ppad = w.Ppad; A.n = n; A.w = c->w; A.h = c->h;
+    A.dI = c->slots[V.slot_first].dI[0].p; A.u = V.u; A.v = V.v; A.iR = V.iR; A.rescale = rescaleFactor;
+    A.prior = kIdepthFixPrior * kScaleIdepth * kScaleIdepth;       // EFPoint::takeData (EnergyFunctionalStructs.cpp:79-85), as nalo_ba_set_points has it
+    A.geo = w.pt_geo.p; A.col0 = w.pt_col0.p; A.col1 = w.pt_col1.p; A.w0 = w.pt_w0.p; A.w1 = w.pt_w1.p; A.prior_out = w.pt_prior.p; A.flags = w.pt_flags.p; A.state = w.rs_state.p;
+    A.ng = w.pt_numgood.p; A.last = w.pt_last.p;
+    A.acc = w.pt_acc.p; A.hcd = w.pt_hcd.p; A.step = w.pt_step.p; A.backup = w.pt_backup.p; A.relbs = w.pt_relbs.p; A.relbs2 = w.pt_relbs2.p; A.ngood = w.pt_ngood.p;
+    A.energy = w.rs_energy.p; A.jp0 = w.rs_jp0.p; A.jp1 = w.rs_jp1.p; A.cpt = w.rs_cpt.p;
+    { const int rc = init_window_gather_launch(c, A, w.nblocks); if (rc) return rc; }
+    NALO_HIP(c, hipMemsetAsync(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8, c->stream));
+    bind_points(w);
+    w.hist_set = true; w.dev.pt_numgood = w.pt_numgood.p; w.dev.pt_last = w.pt_last.p;
+    w.points_set = true; w.res_set = true;
+    w.have_snap = false;
+    w.iw_map_h.swap(kept);
+    w.iw_scale[0] = sumID; w.iw_scale[1] = numID; w.iw_scale[2] = rescaleFactor;
+    w.iw_stats[0] = n; w.iw_stats[1] = skipped; w.iw_stats[2] = rejected; w.iw_stats[3] = P; w.iw_have = true;
+    { const int rc = window_finish(c); if (rc) return rc; }
+    for (int i = 0; i < 2; ++i) {                                   // the frame states as the call set them
+        nalo_frame_state& o = i ? a->entering : a->first;
+        std::memcpy(o.worldToCam_evalPT, fs[i].worldToCam_evalPT, 96); std::memcpy(o.state, fs[i].state, 80); std::memcpy(o.state_zero, fs[i].state_zero, 80);
+    }
+    return NALO_OK;
+}
+
+int nalo_ba_init_window_map(nalo_ctx* c, int* src) {
+    if (!c || !c->ba || !c->ba->iw_have) return fail(c, NALO_ERR_STATE, "nalo_ba_init_window_map: no window has been issued from the initialiser");
+    if (!src) return fail(c, NALO_ERR_ARG, "nalo_ba_init_window_map: bad argument");
+    std::memcpy(src, c->ba->iw_map_h.data(), c->ba->iw_map_h.size() * sizeof(int));
+    return NALO_OK;
+}
+int nalo_ba_init_window_last(nalo_ctx* c, float scale[3], int stats[4]) {
+    if (!c || !c->ba || !c->ba->iw_have) return fail(c, NALO_ERR_STATE, "nalo_ba_init_window_last: no window has been issued from the initialiser");
+    if (scale) std::memcpy(scale, c->ba->iw_scale, sizeof(c->ba->iw_scale));
+    if (stats) std::memcpy(stats, c->ba->iw_stats, sizeof(c->ba->iw_stats));
     return NALO_OK;
 }
 

@@ -392,6 +392,21 @@ static int host_sync(nalo_ctx* c, Initializer& I) {
     return NALO_OK;
 }
 
+int init_level0(nalo_ctx* c, const char* who, InitLevel0* out) {
+    if (!c->init || c->init->slot_first < 0) return fail(c, NALO_ERR_STATE, std::string(who) + ": no initialiser (nalo_init_set_first has not run)");
+    Initializer& I = *c->init;
+    NALO_HIP(c, hipSetDevice(c->device));
+    { const int rc = dev_sync(c, I); if (rc) return rc; }
+    const InitLevel& P = I.L[0];
+    const LvlOff o = lvl_off((size_t)P.n);
+    const float* d = I.lvl_dev[0].p;
+    out->n = P.n; out->slot_first = I.slot_first;
+    out->u_host = P.u.data(); out->v_host = P.v.data();
+    out->u = d + o.u; out->v = d + o.v; out->iR = d + o.iR;
+    std::memcpy(out->thisToNext, I.thisToNext.m, sizeof(out->thisToNext));
+    return NALO_OK;
+}
+
 struct LvlPtr { float *idepth, *idepth_new, *iR, *lastHessian, *lastHessian_new, *maxstep, *energy, *energy_new; uint8_t *isGood, *isGood_new; };
 static LvlPtr lvl_ptr(Initializer& I, int lvl) {
     const LvlOff o = lvl_off((size_t)I.L[lvl].n); float* d = I.lvl_dev[lvl].p;

@@ -1,0 +1,112 @@
+// nalo_ba_window_from_initializer: the first BA window issued from the initialiser's level-0 points where they live (reference paths relative to src/FullSystem/):
+//   FullSystem::initializeFromInitializer   FullSystem.cpp:1567-1654   the mean-scale sum, the PointHessians of the kept points
+//   FullSystem::makeKeyFrame                FullSystem.cpp:1327-1348   the second frame enters: one residual per point, the shift of lastResiduals
+//
+//   iw_sum_kernel      sumID = 1e-5f; sumID += iR[i] for i = 0 .. n-1 (:1589-1594): a chain of n dependent float adds whose result depends on the order, so ONE wave
+//                      runs it in index order. Every lane loads one value of a 64-value run (four runs are in flight), then all lanes add the 64 lanes' values one
+//                      after the other (v_readlane, a uniform operand): no tree, no atomic, no partial sums. ~61 k adds at 1920x1072, once per session.
+//   iw_flag_kernel     one lane per level-0 point: the ImmaturePoint constructor at (int)(u + 0.5f), (int)(v + 0.5f) for its verdict - is energyTH finite (:1612)? One
+//                      byte per point goes up; the host, which owns the draws of the keep rule (:1607), lays the kept points out with nalo_ba_set_points' function.
+//   iw_gather_kernel   one lane per slot of the new window, one workgroup per point block: the constructor again for colour and weights (cheaper than storing
+//                      16 floats per level-0 point for the few that are kept), idepth = idepth_zero = iR * rescaleFactor (:1620-1621), the depth prior (:1622), the
+//                      residual to frame 1 in the state nalo_ba_set_residuals leaves, the history {1, -1} / {IN, IN}, and every zero nalo_ba_set_points fills in.
+// Plain vector stores only. Built without FMA contraction (the constructor's arithmetic is the reference's).
+#include "nalo_internal.h"
+#include "ba_device.h"
+#include "imm_ctor_body.h"
+
+namespace nalo {
+
+__device__ __forceinline__ float iw_lane(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+
+__global__ __launch_bounds__(64) void iw_sum_kernel(const float* __restrict__ iR, int n, float* __restrict__ out) {
+    const int lane = threadIdx.x;
+    float s = 1e-5f;
+    int i = 0;
+    for (; i + 256 <= n; i += 256) {                                    // four full runs: the loads of all four are issued before the first add
+        const float a = iR[i + lane], b = iR[i + 64 + lane], c = iR[i + 128 + lane], d = iR[i + 192 + lane];
+#pragma unroll
+        for (int k = 0; k < 64; ++k) s += iw_lane(a, k);
+#pragma unroll
+        for (int k = 0; k < 64; ++k) s += iw_lane(b, k);
+#pragma unroll
+        for (int k = 0; k < 64; ++k) s += iw_lane(c, k);
+#pragma unroll
+        for (int k = 0; k < 64; ++k) s += iw_lane(d, k);
+    }
+    for (; i < n; i += 64) {                                            // the tail: only the values that exist are added (n is uniform)
+        const float a = i + lane < n ? iR[i + lane] : 0.f;
+        const int m = min(64, n - i);
+        for (int k = 0; k < m; ++k) s += iw_lane(a, k);
+    }
+    if (lane == 0) out[0] = s;
+}
+
+// the pixel initializeFromInitializer constructs the ImmaturePoint at (:1610), and whether imm_ctor may read its pattern
+__device__ __forceinline__ bool iw_pixel(const float* __restrict__ u, const float* __restrict__ v, int i, int w, int h, int& ui, int& vi) {
+    ui = (int)(u[i] + 0.5f); vi = (int)(v[i] + 0.5f);
+    return ui >= 2 && ui <= w - 4 && vi >= 2 && vi <= h - 4;
+}
+
+__global__ __launch_bounds__(256) void iw_flag_kernel(const float4* __restrict__ dI, int w, int h, const float* __restrict__ u, const float* __restrict__ v, int n,
+                                                      uint8_t* __restrict__ ok) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int ui, vi;
+    bool fin = false;
+    if (iw_pixel(u, v, i, w, h, ui, vi)) fin = isfinite(imm_ctor(dI, w, ui, vi).energyTH);      // :1612 (a PointHessian copies the same energyTH: :1618 decides alike)
+    ok[i] = fin ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void iw_gather_kernel(InitWindowDev A) {
+    const int d = blockIdx.x * kBlk + threadIdx.x;                      // grid = the window's point blocks: d < Ppad
+    const size_t N = (size_t)A.Ppad;
+    const int s = A.src[d];
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the filler of a padding slot (nalo_ba_set_points, nalo_ba_set_point_history)
+    float4 geo = make_float4(8.f, 8.f, 1.f, 1.f), c0 = z4, c1 = z4, w0 = z4, w1 = z4;
+    float prior = 0.f;
+    uint8_t flags = 0, st1 = 0;
+    uint32_t last = 0x0101FFFFu;                                        // {-1, -1} / {OOB, OOB}
+    int ui, vi;
+    if (s >= 0 && s < A.n && iw_pixel(A.u, A.v, s, A.w, A.h, ui, vi)) {
+        const ImmCtor c = imm_ctor(A.dI, A.w, ui, vi);
+        const float id = A.iR[s] * A.rescale;                           // setIdepthScaled(iR * rescaleFactor), setIdepthZero(idepth) (SCALE_IDEPTH = 1)
+        geo = make_float4((float)ui, (float)vi, id, id);
+        c0 = make_float4(c.color[0], c.color[1], c.color[2], c.color[3]); c1 = make_float4(c.color[4], c.color[5], c.color[6], c.color[7]);
+        w0 = make_float4(c.weights[0], c.weights[1], c.weights[2], c.weights[3]); w1 = make_float4(c.weights[4], c.weights[5], c.weights[6], c.weights[7]);
+        prior = A.prior;                                                // hasDepthPrior = true: EFPoint::takeData's priorF
+        flags = PT_VALID | PT_HAS_PRIOR;
+        st1 = RS_EXISTS;                                                // the residual to the entering frame (:1340-1343)
+        // lastResiduals is value-initialised to {(0, IN), (0, IN)} by PointHessian and then shifted (:1344-1345): [0] = (frame 1, IN), [1] = (null, IN)
+        last = 0x0000FF01u;
+    }
+    A.geo[d] = geo; A.col0[d] = c0; A.col1[d] = c1; A.w0[d] = w0; A.w1[d] = w1;
+    A.prior_out[d] = prior; A.flags[d] = flags;
+    A.ng[d] = 0; A.last[d] = last;
+    A.acc[d] = z4; A.hcd[d] = z4; A.step[d] = 0.f; A.backup[d] = 0.f; A.relbs[d] = 0.f; A.relbs2[d] = 0.f; A.ngood[d] = 0;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {                                       // t-major rows of the two-frame window
+        const size_t si = (size_t)t * N + d;
+        A.state[si] = t == 1 ? st1 : (uint8_t)0;                        // state IN, energies zero, resetOOB: what nalo_ba_set_residuals leaves
+        A.energy[si] = make_float2(0.f, 0.f);
+        A.jp0[si] = z4; A.jp1[si] = z4; A.cpt[si] = z4;
+    }
+}
+
+int init_window_scan_launch(nalo_ctx* c, const float4* dI, const float* u, const float* v, const float* iR, int n, uint8_t* ok, float* sum) {
+    ProfScope ps(c, "init_window_scan");
+    iw_sum_kernel<<<1, 64, 0, c->stream>>>(iR, n, sum);
+    if (n > 0) iw_flag_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(dI, c->w, c->h, u, v, n, ok);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+int init_window_gather_launch(nalo_ctx* c, const InitWindowDev& A, int nblocks) {
+    ProfScope ps(c, "init_window_gather");
+    iw_gather_kernel<<<nblocks, kBlk, 0, c->stream>>>(A);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+}  // namespace nalo
