@@ -757,6 +757,84 @@ int nalo_init_get_points(nalo_ctx* ctx, int lvl, int cap, int* n, float* u, floa
                          float* my_type, float* outlierTH, int* parent, float* parentDist, int* neighbours, float* neighboursDist);
 
 /* ------------------------------------------------------------------------------------------------
+ * The map side of the device chain: the points nalo_ba_marginalize_flagged removes stay resident in a device archive, and what the reference publishes
+ * per keyframe is produced from resident data. In the reference the removed points ARE the map: flagPointsForRemoval pushes them onto
+ * host->pointHessiansMarginalized / host->pointHessiansOut (FullSystem/FullSystem.cpp:968, 996, 1001, 1008) and publishKeyframes, SampleOutputWrapper and
+ * KeyFrameDisplay read those two vectors. Opt-in: a context that never calls nalo_map_enable enqueues exactly what it did before.
+ *
+ * nalo_map_enable(ctx, on, chunk_points)   while on, nalo_ba_marginalize_flagged appends every point it removes (marginalised and dropped) to the archive
+ *   before the slots are cleared. Call it BEFORE the nalo_ba_flag_points whose decisions are to be archived (the record keeps that call's decision and
+ *   idepth_hessian; nalo_ba_marginalize_flagged returns NALO_ERR_STATE, touching nothing, for decisions made while the map was off). The archive grows
+ *   in chunks of chunk_points records (0 = 65536; the value in force when the first chunk is allocated holds for the context): a new chunk is a new allocation,
+ *   archived records never move; in steady state the call allocates nothing. Room is reserved for every valid point of the window before anything is
+ *   touched (the count of removed points is only known on the device), so a refusal for lack of memory leaves archive and window as they were. NALO_ERR_STATE on a sharded window and on a context whose exchange failed.
+ *   Record    nalo_map_record, 64 bytes: the values the reference's PointHessian holds when it is published. maxRelBaseline is that of the last
+ *             linearizeAll(true). idepth_hessian of a dropped point (status 3) is what nalo_ba_flag_points reports; that of a marginalised point (status 2)
+ *             is rewritten by marginalizePointsF's addPoint (AccumulatedSCHessian.cpp:36-50): H of the re-accumulated Hdd and the scaled prior, and
+ *             idepth_hessian = maxRelBaseline = 0 for a point whose re-linearisation left no active residual.
+ *   Order     per call: host frame in window order, then submission order inside the host (the order of nalo_trk_set_ref_from_window and
+ *             nalo_dense_fit_planes) - an ordered compaction, never an atomic. The reference's pointHessiansOut holds removeOutliers' points before
+ *             flagPointsForRemoval's inside one keyframe and permutes by swap-with-back; the sets and every value are equal, the order inside a keyframe's
+ *             run is the library's.
+ *   frame_id  the caller's, from nalo_frame_state: the archive is keyed by it, so the frames of a session need distinct ids.
+ *   Not archived: points removed by nalo_ba_marginalize_points (host flags). nalo_ba_snapshot / nalo_ba_restore do not include the archive.
+ * nalo_map_reset      empties the archive and keeps its chunks.
+ * nalo_map_counts     counts = {pointHessiansMarginalized.size(), pointHessiansOut.size()} of the frame: the addends of flagFramesForMarginalization's
+ *                     `out` (FullSystemMarginalize.cpp:77). NALO_ERR_ARG for a frame_id the archive has never seen.
+ * nalo_map_get_frame  the frame's records: its status-2 records in archive order, then its status-3 records. *n = their number; cap < *n: NALO_ERR_ARG
+ *                     (with *n set), as is an unknown frame_id.
+ *
+ * nalo_map_world_points   SampleOutputWrapper::publishKeyframes(final = true) for the frame's marginalised points (SampleOutputWrapper.h:110-118), one lane
+ *   per status-2 record, in archive order: xyz [n][3] doubles = camToWorld * back-projection with the float inverse calibration {1/fx, 1/fy, -cx/fx, -cy/fy}
+ *   of the window's current CalibHessian (value_scaledf). The arithmetic is nalo_io_write_pcd_points' (one shared function): equal bit for bit.
+ *   cap < *n: NALO_ERR_ARG with *n set. One wait.
+ * nalo_map_world_points_host  that one function on host arrays (no device, no context): the numbers nalo_io_write_pcd_points formats for the same points.
+ *   calib_inv = {fxi, fyi, cxi, cyi}.
+ *
+ * nalo_map_frame_cloud    KeyFrameDisplay::setFromKF + refreshPC (IOWrapper/Pangolin/KeyFrameDisplay.cpp:92-177, 297-410) for one frame, from resident data.
+ *   Records   [immature | active | marginalised | out], status 0 / 1 / 2 / 3. Status 0: the resident immature points (nalo_imm_resident_*) whose host_idx is
+ *             the frame's window index, in storage order, idepth = (idepth_max + idepth_min) * 0.5f, idepth_hessian = 1000, relObsBaseline = 0; left out
+ *             when with_immature == 0. Status 1: the frame's valid window points in submission order, idepth_hessian by nalo_ba_flag_points' formula.
+ *             Statuses 2, 3: the archive. A frame that has left the window has only the last two classes. NALO_ERR_ARG for a frame_id that is neither in
+ *             the window nor in the archive; NALO_ERR_STATE for a window frame whose points are unset (between nalo_ba_marginalize_frame and the carry).
+ *   Filter    as written at :313-331, mixed precision included: display_mode (0 all, colour-coded; 1 statuses 1, 2; 2 status 1; > 2 nothing); idepth < 0
+ *             skips; depth = 1.0f / idepth; depth4 = (depth * depth)^2; var = (float)(1.0 / ((double)idepth_hessian + 0.01)); var * depth4 > scaledTH skips;
+ *             var > absTH skips; relObsBaseline < minRelBS skips. NaNs take the branch the comparisons give them.
+ *   Vertices  each survivor gives 8, pnt = 0..7, (dx, dy) = patternP[pnt]: x = ((u + dx) * fxi + cxi) * depth, y = ((v + dy) * fyi + cyi) * depth,
+ *             z = depth * (1 + 2 * fxi * (r / (float)RAND_MAX - 0.5f)), RAND_MAX = 2^31 - 1, r = draws[j] for output vertex j (the caller's libc rand()
+ *             stream, as with nalo_pixsel_set_random). draws == NULL is the library's no-jitter form: the bracket is exactly 1, z = depth. With draws,
+ *             n_draws >= 8 x records of the frame is required (NALO_ERR_ARG, *n_needed set), and cap >= 8 x records always (alike).
+ *   Colour    display_mode 0: the constant triples of :349-372; else three times color[pnt], float -> byte by truncation toward zero, saturated to 0..255,
+ *             NaN -> 0 (the reference's conversion is undefined outside that range).
+ *   sparsity > 1 is refused (NALO_ERR_ARG): its rand() % factor makes every later draw index depend on earlier draw values. The pcl::PointXYZ branch of the
+ *             second refreshPC overload (:534-550) reads the vertex after the one it wrote and is not reproduced.
+ *   Output order is record order, then pnt. records[4] / survivors[4]: per status. One wait per call.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_map_record {
+    float u, v, idepth, idepth_hessian;     /* idepth = PointHessian::idepth_scaled (SCALE_IDEPTH is 1) */
+    float maxRelBaseline;
+    int status;                             /* 2 marginalised, 3 out */
+    int decision;                           /* nalo_ba_flag_points' class: 1, 2 or 3 */
+    int frame_id;
+    float color[8];
+} nalo_map_record;                          /* 64 bytes, 16-byte aligned on the device */
+typedef struct nalo_map_cloud_args {
+    int frame_id, display_mode, with_immature, sparsity;
+    float scaledTH, absTH, minRelBS;
+    int n_draws; const int* draws;          /* NULL: no jitter */
+    int cap; float* xyz; uint8_t* rgb;      /* cap vertices: [cap][3] each */
+    int n, n_needed;                        /* out: vertices written; 8 x records (what cap and n_draws must reach) */
+    int records[4], survivors[4];           /* out */
+} nalo_map_cloud_args;
+int nalo_map_enable(nalo_ctx* ctx, int on, int chunk_points);
+int nalo_map_reset(nalo_ctx* ctx);
+int nalo_map_counts(nalo_ctx* ctx, int frame_id, int counts[2]);
+int nalo_map_get_frame(nalo_ctx* ctx, int frame_id, nalo_map_record* records, int cap, int* n);
+int nalo_map_world_points(nalo_ctx* ctx, int frame_id, const double camToWorld[12], double* xyz /* n x 3 */, int cap, int* n);
+int nalo_map_world_points_host(int n, const float* u, const float* v, const float* idepth, const float calib_inv[4], const double camToWorld[12], double* xyz /* n x 3 */);
+int nalo_map_frame_cloud(nalo_ctx* ctx, nalo_map_cloud_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
  * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "ingest". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a

@@ -36,6 +36,7 @@ EXPORTS = [
     "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
+    "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -69,6 +70,19 @@ class PlaneFitArgs(C.Structure):
 PLANE_DTYPE = np.dtype([("mask_value", np.float32), ("n", np.int32), ("n_cloud", np.int32), ("rect", np.int32, 4), ("fitted", np.int32), ("plane", np.float32, 4),
                         ("best_sample", np.int32), ("inliers", np.int32), ("appended", np.int32)])
 assert PLANE_DTYPE.itemsize == C.sizeof(PlaneCluster)
+
+
+class MapCloudArgs(C.Structure):
+    """nalo_map_cloud_args (include/nalo_gpu.h)"""
+    _fields_ = [("frame_id", C.c_int), ("display_mode", C.c_int), ("with_immature", C.c_int), ("sparsity", C.c_int), ("scaledTH", C.c_float), ("absTH", C.c_float),
+                ("minRelBS", C.c_float), ("n_draws", C.c_int), ("draws", c_ip), ("cap", C.c_int), ("xyz", c_fp), ("rgb", c_u8p), ("n", C.c_int), ("n_needed", C.c_int),
+                ("records", C.c_int * 4), ("survivors", C.c_int * 4)]
+
+
+# nalo_map_record (include/nalo_gpu.h)
+MAP_RECORD_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("idepth", np.float32), ("idepth_hessian", np.float32), ("maxRelBaseline", np.float32),
+                             ("status", np.int32), ("decision", np.int32), ("frame_id", np.int32), ("color", np.float32, 8)])
+assert MAP_RECORD_DTYPE.itemsize == 64
 
 
 class Settings(C.Structure):
@@ -154,6 +168,13 @@ def load():
     L.nalo_ba_window_from_initializer.argtypes = [vp, C.POINTER(InitWindowArgs)]
     L.nalo_ba_init_window_map.argtypes = [vp, c_ip]
     L.nalo_ba_init_window_last.argtypes = [vp, c_fp, c_ip]
+    L.nalo_map_enable.argtypes = [vp, C.c_int, C.c_int]
+    L.nalo_map_reset.argtypes = [vp]
+    L.nalo_map_counts.argtypes = [vp, C.c_int, c_ip]
+    L.nalo_map_get_frame.argtypes = [vp, C.c_int, vp, C.c_int, c_ip]
+    L.nalo_map_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
+    L.nalo_map_world_points_host.argtypes = [C.c_int, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp]
+    L.nalo_map_frame_cloud.argtypes = [vp, C.POINTER(MapCloudArgs)]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -642,6 +663,61 @@ class Context:
         scale, stats = np.zeros(3, np.float32), np.zeros(4, np.int32)
         self._ck(self.L.nalo_ba_init_window_last(self.h_, _f(scale), _i(stats)))
         return scale, tuple(int(x) for x in stats)
+
+    # ---- the map: removed points archived on the device, and the clouds published from it
+    def map_enable(self, on=True, chunk_points=0):
+        """nalo_map_enable: from the next ba_flag_points on, ba_marginalize_flagged archives every point it removes"""
+        self._ck(self.L.nalo_map_enable(self.h_, int(bool(on)), int(chunk_points)))
+
+    def map_reset(self):
+        self._ck(self.L.nalo_map_reset(self.h_))
+
+    def map_counts(self, frame_id):
+        """(pointHessiansMarginalized.size(), pointHessiansOut.size()) of the frame"""
+        a = np.zeros(2, np.int32)
+        self._ck(self.L.nalo_map_counts(self.h_, int(frame_id), _i(a)))
+        return int(a[0]), int(a[1])
+
+    def map_get_frame(self, frame_id):
+        """the frame's archive records (MAP_RECORD_DTYPE): marginalised first, then out"""
+        n = C.c_int(0)
+        rc = self.L.nalo_map_get_frame(self.h_, int(frame_id), None, 0, C.byref(n))
+        if n.value == 0:
+            self._ck(rc)
+        rec = np.zeros(n.value, MAP_RECORD_DTYPE)
+        if n.value:
+            self._ck(self.L.nalo_map_get_frame(self.h_, int(frame_id), rec.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return rec
+
+    def map_world_points(self, frame_id, cam_to_world):
+        """publishKeyframes(final = true): the world points [n][3] (float64) of the frame's marginalised points"""
+        m = np.ascontiguousarray(cam_to_world, np.float64).reshape(-1)
+        assert m.size == 12
+        n = C.c_int(0)
+        rc = self.L.nalo_map_world_points(self.h_, int(frame_id), _d(m), None, 0, C.byref(n))
+        if n.value == 0:
+            self._ck(rc)
+        xyz = np.zeros((n.value, 3), np.float64)
+        if n.value:
+            self._ck(self.L.nalo_map_world_points(self.h_, int(frame_id), _d(m), _d(xyz), n.value, C.byref(n)))
+        return xyz
+
+    def map_frame_cloud(self, frame_id, display_mode=1, scaledTH=1e10, absTH=1e10, minRelBS=0.0, with_immature=True, draws=None, sparsity=1):
+        """setFromKF + refreshPC for one frame -> dict(xyz [n][3] float32, rgb [n][3] uint8, records [4], survivors [4])"""
+        a = MapCloudArgs()
+        a.frame_id, a.display_mode, a.with_immature, a.sparsity = int(frame_id), int(display_mode), int(bool(with_immature)), int(sparsity)
+        a.scaledTH, a.absTH, a.minRelBS = float(scaledTH), float(absTH), float(minRelBS)
+        rc = self.L.nalo_map_frame_cloud(self.h_, C.byref(a))                    # cap = 0: answers n_needed (and is the whole call for a frame without records)
+        if a.n_needed == 0:
+            self._ck(rc)
+        cap = a.n_needed
+        xyz, rgb = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.uint8)
+        if cap:
+            d = None if draws is None else np.ascontiguousarray(draws, np.int32)
+            a.cap, a.xyz, a.rgb = cap, _f(xyz), _u8(rgb)
+            a.draws, a.n_draws = (None, 0) if d is None else (_i(d), len(d))
+            self._ck(self.L.nalo_map_frame_cloud(self.h_, C.byref(a)))
+        return dict(xyz=xyz[:a.n], rgb=rgb[:a.n], records=np.array(list(a.records)), survivors=np.array(list(a.survivors)), n_needed=cap)
 
     def ba_get_frames(self):
         arr = (FrameState * self.W)()

@@ -92,6 +92,10 @@ struct BAWindow {
     bool hist_set = false, snap_hist = false;                       // the window carries a history (dev.pt_numgood / dev.pt_last are set); so did it when the snapshot was taken
     DevBuf<uint8_t> flag_dec; DevBuf<float> flag_H; DevBuf<int> flag_counts; int flag_buf = 0;   // the decision kernel's outputs; counts: two buffers of 4 * NALO_MAX_WINDOW, the idle one zero
     bool flagged = false;                                           // pt_flags hold the decisions of a nalo_ba_flag_points nobody has consumed yet
+    bool flag_full = false;                                         // that call left decision and idepth_hessian of every slot in flag_dec / flag_H (the map was on: nalo_map_enable)
+    // the map: maxRelBaseline of the last linearizeAll(true) as it stood before an archiving nalo_ba_marginalize_flagged (its marginalisation pass swaps the relBS
+    // buffers and zeroes that one): what the kept points publish until the next pass that records relBS or the next layout
+    DevBuf<float> relbs_keep; bool relbs_keep_ok = false;
     // nalo_ba_carry_window: the second set of the buffers ba_carry_kernel gathers into (each swaps with its first-set twin when the call has launched), the integer
     // mirrors the maps are worked out from, and the maps' pinned staging
     DevBuf<float4> pt_geo2, pt_col0_2, pt_col1_2, pt_w0_2, pt_w1_2; DevBuf<float> pt_prior2; DevBuf<uint8_t> pt_flags2, rs_state2; DevBuf<int> pt_numgood2; DevBuf<uint32_t> pt_last2;
@@ -393,7 +397,7 @@ static int linearize_async(nalo_ctx* c, int mode, int fix, bool keep_th = false)
     }
     int rc = flush_th(c); if (rc) return rc;                          // frameEnergyTH of the previous pass feeds this one
     // a pass that records relBS (fix / marginalisation) takes the clean buffer of the pair and leaves the other one clean (its idle workgroups zero it): no fill launch
-    if (fix == 1 || mode == 2) std::swap(w.dev.pt_relbs, w.dev.pt_relbs_next);
+    if (fix == 1 || mode == 2) { std::swap(w.dev.pt_relbs, w.dev.pt_relbs_next); w.relbs_keep_ok = false; }
     const bool th_sharded = mode == 0 && w.hook;
     const bool on_side = th_sharded && !(w.hook_stream_ordered && !w.hook_side);
     // (device-scope events: both sides of these dependencies are kernels of this context; a system-scope release behind the linearisation writes its output back first)
@@ -928,6 +932,31 @@ int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, in
     return NALO_OK;
 }
 
+int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V) {
+    if (!c->ba || c->ba->W < 1) return fail(c, NALO_ERR_STATE, "nalo_map: no window (its CalibHessian is the clouds' calibration)");
+    BAWindow& w = *c->ba;
+    *V = MapWindowView{};
+    V->widx = -1; V->sharded = w.hook != nullptr;
+    for (int i = 0; i < 4; ++i) V->ci[i] = w.c_scaledi[i];
+    for (int i = 0; i < w.W && V->widx < 0; ++i) if (w.frames[i].frameID == frame_id) V->widx = i;
+    V->pts_ok = w.points_set && !w.hook;
+    if (V->widx < 0 || !V->pts_ok) return NALO_OK;
+    V->flags = w.pt_flags.p; V->geo = w.pt_geo.p; V->col0 = w.pt_col0.p; V->col1 = w.pt_col1.p; V->acc = w.pt_acc.p; V->prior = w.pt_prior.p;
+    V->relbs = w.relbs_keep_ok ? w.relbs_keep.p : w.dev.pt_relbs;               // PointHessian::maxRelBaseline: the last linearizeAll(true)'s
+    if (w.P == 0) return NALO_OK;
+    { const int rc = ref_kmap_build(c, w); if (rc) return rc; }
+    const int row = w.row_of.empty() ? V->widx : w.row_of[V->widx];           // the device host index of the frame
+    int first = -1;
+    for (int k = 0; k < w.P; ++k) {
+        const int d = w.ref_kmap_h[k];
+        if (w.blk_host_h[d / kBlk] != row) continue;
+        if (first < 0) first = k;
+        ++V->seg; V->n_valid += (w.flags_h[d] & PT_VALID) != 0;
+    }
+    if (V->seg) V->kmap = w.ref_kmap.p + first;
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -1123,7 +1152,7 @@ static void bind_points(BAWindow& w) {
     D.pt_flags = w.pt_flags.p; D.pt_acc = w.pt_acc.p; D.pt_hcd = w.pt_hcd.p; D.pt_ngood = w.pt_ngood.p; D.pt_step = w.pt_step.p; D.pt_backup = w.pt_backup.p; D.pt_relbs = w.pt_relbs.p; D.pt_relbs_next = w.pt_relbs2.p;
     D.rs_state = w.rs_state.p; D.rs_energy = w.rs_energy.p; D.rs_jp0 = w.rs_jp0.p; D.rs_jp1 = w.rs_jp1.p; D.rs_cpt = w.rs_cpt.p; D.rs_pp0 = w.rs_pp0.p; D.rs_pp1 = w.rs_pp1.p; D.en_new = w.en_new.p;
     D.top_partial = w.top_partial.p; D.sc_partial = w.sc_partial.p;
-    w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false; w.flagged = false;
+    w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false; w.flagged = false; w.relbs_keep_ok = false;
     w.row_of.resize(w.W); for (int i = 0; i < w.W; ++i) w.row_of[i] = i;
     w.carry_ok = false;
 }
@@ -1550,16 +1579,17 @@ int nalo_ba_flag_points(nalo_ctx* c, const uint8_t* frame_flagged, uint8_t* deci
     // asked for it yet (as nalo_ba_get_points does); after nalo_ba_optimize it is the last solve's, which is what the reference compares
     if (w.have_lin && !w.have_sc && w.pt_acc_on_read) { int rc = sc_async(c, 1, 1.f, 0); if (rc) return rc; }
     if (!w.flag_counts.p) { NALO_HIP(c, w.flag_counts.reserve(8 * NALO_MAX_WINDOW)); NALO_HIP(c, hipMemsetAsync(w.flag_counts.p, 0, 8 * NALO_MAX_WINDOW * 4, c->stream)); w.flag_buf = 0; }
-    if (decision) NALO_HIP(c, w.flag_dec.reserve(N));
-    if (idepth_hessian) NALO_HIP(c, w.flag_H.reserve(N));
+    const bool arch = map_on(c);                                     // the archive keeps the decision class and this H of every point the call removes
+    if (decision || arch) NALO_HIP(c, w.flag_dec.reserve(N));
+    if (idepth_hessian || arch) NALO_HIP(c, w.flag_H.reserve(N));
     int* const cnt = w.flag_counts.p + w.flag_buf * 4 * NALO_MAX_WINDOW;
     w.flag_buf ^= 1;
     {
         ProfScope ps(c, "ba_flag_points");
-        ba_launch_flag_points(c->stream, w.dev, mask, decision ? w.flag_dec.p : nullptr, idepth_hessian ? w.flag_H.p : nullptr, cnt, w.flag_counts.p + w.flag_buf * 4 * NALO_MAX_WINDOW);
+        ba_launch_flag_points(c->stream, w.dev, mask, (decision || arch) ? w.flag_dec.p : nullptr, (idepth_hessian || arch) ? w.flag_H.p : nullptr, cnt, w.flag_counts.p + w.flag_buf * 4 * NALO_MAX_WINDOW);
     }
     NALO_HIP(c, hipGetLastError());
-    w.flagged = true;
+    w.flagged = true; w.flag_full = arch;
     if (!decision && !idepth_hessian && !counts) return NALO_OK;     // the decisions stay resident: nothing to wait for
     std::vector<uint8_t> dec; std::vector<float> H;
     if (decision) { dec.resize(N); NALO_HIP(c, hipMemcpyAsync(dec.data(), w.flag_dec.p, N, hipMemcpyDeviceToHost, c->stream)); }
@@ -1577,13 +1607,35 @@ int nalo_ba_flag_points(nalo_ctx* c, const uint8_t* frame_flagged, uint8_t* deci
 int nalo_ba_marginalize_flagged(nalo_ctx* c, double* M, double* Mb, double* Msc, double* Mbsc) {
     NALO_BA_READY("nalo_ba_marginalize_flagged")
     if (!w.flagged) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_flagged: no decisions (nalo_ba_flag_points first)");
+    // the map (nalo_map_enable): every point this call removes goes into the device archive first. The records are written before the marginalisation pass
+    // (it swaps the relBS buffers and zeroes the one the last fix pass filled), and those of the marginalised points are finished behind its accumulation
+    const bool arch = map_on(c);
+    if (arch) {
+        if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_flagged: the map is on and the window is sharded (a rank holds only its own points)");
+        if (!w.flag_full) return fail(c, NALO_ERR_STATE, "nalo_ba_marginalize_flagged: the decisions were made while the map was off (nalo_map_enable before nalo_ba_flag_points)");
+        { const int rk = ref_kmap_build(c, w); if (rk) return rk; }
+        MapAppendDev A{};
+        A.P = w.P; A.kmap = w.ref_kmap.p; A.blk_host = w.blk_host.p; A.flags = w.pt_flags.p; A.ngood = w.pt_ngood.p; A.dec = w.flag_dec.p; A.H = w.flag_H.p;
+        A.geo = w.pt_geo.p; A.col0 = w.pt_col0.p; A.col1 = w.pt_col1.p; A.acc = w.pt_acc.p; A.prior = w.pt_prior.p;
+        const bool kept = w.relbs_keep_ok;                           // no pass has recorded relBS since the last archiving call: the values held then still are the last linearizeAll(true)'s
+        A.relbs = kept ? w.relbs_keep.p : w.dev.pt_relbs;
+        for (int i = 0; i < w.W; ++i) A.frame_id[w.row_of.empty() ? i : w.row_of[i]] = w.frames[i].frameID;
+        int ub = 0;
+        for (int d = 0; d < w.Ppad; ++d) ub += (w.flags_h[d] & PT_VALID) != 0;
+        NALO_HIP(c, w.relbs_keep.reserve(w.Ppad));
+        { const int rb = map_append_begin(c, A, w.W, ub); if (rb) return rb; }
+        if (!kept) NALO_HIP(c, hipMemcpyAsync(w.relbs_keep.p, w.dev.pt_relbs, (size_t)w.Ppad * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
     int rc = marginalize_marked(c, M, Mb, Msc, Mbsc); if (rc) return rc;
+    if (arch) { w.relbs_keep_ok = true; rc = map_append_patch(c); if (rc) return rc; }
     // dropPointsF / removePoint of all three removed classes on the device; only the host mirror of the point flags comes back (nalo_ba_marginalize_frame's
     // "still hosts points" test reads it)
     ba_launch_remove_flagged(c->stream, w.dev);
     NALO_HIP(c, hipGetLastError());
     NALO_HIP(c, hipMemcpyAsync(w.flags_h.data(), w.pt_flags.p, w.Ppad, hipMemcpyDeviceToHost, c->stream));
+    if (arch) { rc = map_append_fetch(c); if (rc) return rc; }       // the per-host counts come up in the same wait
     NALO_HIP(c, hipStreamSynchronize(c->stream));
+    if (arch) map_append_commit(c);
     w.flagged = false;
     w.have_lin = w.have_sc = false; w.lin_fixed = false;
     return NALO_OK;
@@ -1988,6 +2040,7 @@ int nalo_ba_snapshot(nalo_ctx* c) {
 }
 int nalo_ba_restore(nalo_ctx* c) {
     NALO_BA_READY("nalo_ba_restore")
+    w.relbs_keep_ok = false;
     HostTimer ht(c, "ba_restore");
     if (!w.have_snap) return fail(c, NALO_ERR_STATE, "nalo_ba_restore: no snapshot");
     const size_t N = w.Ppad, NS = (size_t)w.W * N;

@@ -1,5 +1,6 @@
 // On-disk formats: host-only text I/O behind the C ABI of include/nalo_io.h. Reference paths relative to src/.
 #include "../../include/nalo_io.h"
+#include "map_point_math.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -62,18 +63,15 @@ int nalo_io_write_pcd_points(const char* path, int append, int n, const float* u
     if (!path || n < 0 || !calib_inv || !m || (n > 0 && (!u || !v || !idepth))) return NALO_IO_ERR_ARG;
     std::ofstream f(path, append ? std::ios::app : std::ios::trunc);
     if (!f.good()) return NALO_IO_ERR_FILE;
-    const float fxi = calib_inv[0], fyi = calib_inv[1], cxi = calib_inv[2], cyi = calib_inv[3];
     for (int i = 0; i < n; ++i) {
-        const float depth = 1.0f / idepth[i];
-        const float x = (u[i] * fxi + cxi) * depth, y = (v[i] * fyi + cyi) * depth, z = depth * (1 + 2 * fxi);       // SampleOutputWrapper.h:113-116
-        const double c[4] = {x, y, z, 1.0};
         double wp[3];
-        for (int r = 0; r < 3; ++r) wp[r] = ((m[4 * r] * c[0] + m[4 * r + 1] * c[1]) + m[4 * r + 2] * c[2]) + m[4 * r + 3] * c[3];
+        nalo::map_world_point(u[i], v[i], idepth[i], calib_inv, m, wp);
         f << wp[0] << " " << wp[1] << " " << wp[2] << "\n";
     }
     f.close();
     return f.fail() ? NALO_IO_ERR_FILE : NALO_IO_OK;
 }
+
 
 int nalo_io_read_camera(const char* path, nalo_camera_file* out) {
     if (!path || !out) return NALO_IO_ERR_ARG;

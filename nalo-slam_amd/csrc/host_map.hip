@@ -1,0 +1,263 @@
+// The archive of removed points and the entry points that publish from it (nalo_map_*, include/nalo_gpu.h; kernels: kernels_map.hip).
+// The archive is a list of device chunks of `chunk` records; position q of the archive is record q % chunk of chunk q / chunk. A chunk is allocated once and
+// never moved. The host keeps, per frame_id, the runs (position, count) its records were appended in and the two totals: W small integers per keyframe.
+#include "nalo_internal.h"
+#include "map_point_math.h"
+
+#include <algorithm>
+#include <memory>
+
+namespace nalo {
+
+struct MapRun { long long off; int n; };
+struct MapFrame { std::vector<MapRun> runs; int cnt[2] = {0, 0}; };          // cnt: {marginalised, out}
+
+struct MapArchive {
+    bool on = false;
+    int chunk = 0;                                                          // records per chunk; fixed while the archive holds chunks
+    long long filled = 0;
+    std::vector<DevBuf<nalo_map_record>> chunks;
+    DevBuf<nalo_map_record*> tab; size_t tab_n = 0;                         // the chunks' addresses on the device, re-sent when one is added
+    std::map<int, MapFrame> frames;
+    // the append of nalo_ba_marginalize_flagged: block counts, the per-host counters (two buffers of 2 * NALO_MAX_WINDOW, the idle one zero) and their pinned mirror
+    DevBuf<int> cnt, hs; int hs_buf = 0; HostBuf<int> hs_host;
+    MapAppendDev pend{}; int pend_W = 0; bool pending = false;
+    // the clouds: segment table (pinned staging + device), draws, block counts + statistics, outputs and their pinned mirrors
+    HostBuf<MapSeg> seg_h; DevBuf<MapSeg> seg_d; HostBuf<int> draws_h; DevBuf<int> draws_d, qcnt;
+    DevBuf<double> wxyz; HostBuf<double> wxyz_h;
+    DevBuf<float> cxyz; DevBuf<uint8_t> crgb; HostBuf<float> cxyz_h; HostBuf<uint8_t> crgb_h; HostBuf<int> stats_h;
+};
+
+bool map_on(const nalo_ctx* c) { return c->map && c->map->on; }
+void map_destroy(nalo_ctx* c) { delete c->map; c->map = nullptr; }
+
+// room for positions [0, want): new chunks are new allocations; the table goes down again when one was added
+static int map_reserve(nalo_ctx* c, MapArchive& m, long long want) {
+    const size_t need = (size_t)((want + m.chunk - 1) / m.chunk);
+    if (need <= m.chunks.size()) return NALO_OK;
+    std::vector<DevBuf<nalo_map_record>> fresh(need - m.chunks.size());
+    for (auto& b : fresh) NALO_HIP(c, b.reserve((size_t)m.chunk));          // a failure frees what this call allocated and leaves the archive as it was
+    DevBuf<nalo_map_record*> tab;
+    NALO_HIP(c, tab.reserve(need));
+    std::vector<nalo_map_record*> ptrs;
+    for (auto& b : m.chunks) ptrs.push_back(b.p);
+    for (auto& b : fresh) ptrs.push_back(b.p);
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    NALO_HIP(c, hipMemcpy(tab.p, ptrs.data(), need * sizeof(nalo_map_record*), hipMemcpyHostToDevice));
+    for (auto& b : fresh) m.chunks.push_back(std::move(b));
+    m.tab = std::move(tab); m.tab_n = need;
+    return NALO_OK;
+}
+
+int map_append_begin(nalo_ctx* c, MapAppendDev& A, int W, int ub) {
+    MapArchive& m = *c->map;
+    m.pending = false;
+    A.nb = (A.P + 255) / 256;
+    if (A.nb == 0) return NALO_OK;
+    { int rc = map_reserve(c, m, m.filled + ub); if (rc) return rc; }
+    NALO_HIP(c, m.cnt.reserve((size_t)A.nb + 1));
+    if (!m.hs.p) {
+        NALO_HIP(c, m.hs.reserve(4 * NALO_MAX_WINDOW)); NALO_HIP(c, m.hs_host.reserve(2 * NALO_MAX_WINDOW));
+        NALO_HIP(c, hipMemsetAsync(m.hs.p, 0, 4 * NALO_MAX_WINDOW * 4, c->stream)); m.hs_buf = 0;
+    }
+    A.cnt = m.cnt.p; A.hs = m.hs.p + m.hs_buf * 2 * NALO_MAX_WINDOW; m.hs_buf ^= 1; A.hs_next = m.hs.p + m.hs_buf * 2 * NALO_MAX_WINDOW;
+    A.chunks = m.tab.p; A.base = m.filled; A.cap = (long long)m.chunks.size() * m.chunk; A.chunk = m.chunk;
+    { int rc = map_append_rank_launch(c, A); if (rc) return rc; }
+    { int rc = map_append_write_launch(c, A, false); if (rc) return rc; }
+    m.pend = A; m.pend_W = W; m.pending = true;
+    return NALO_OK;
+}
+int map_append_patch(nalo_ctx* c) {
+    MapArchive& m = *c->map;
+    return m.pending ? map_append_write_launch(c, m.pend, true) : NALO_OK;
+}
+int map_append_fetch(nalo_ctx* c) {
+    MapArchive& m = *c->map;
+    if (m.pending) NALO_HIP(c, hipMemcpyAsync(m.hs_host.p, m.pend.hs, 2 * NALO_MAX_WINDOW * 4, hipMemcpyDeviceToHost, c->stream));
+    return NALO_OK;
+}
+void map_append_commit(nalo_ctx* c) {
+    MapArchive& m = *c->map;
+    if (!m.pending) return;
+    m.pending = false;
+    for (int h = 0; h < m.pend_W; ++h) {
+        const int n2 = m.hs_host.p[2 * h], n3 = m.hs_host.p[2 * h + 1];
+        MapFrame& f = m.frames[m.pend.frame_id[h]];                          // a frame the archive has seen, with or without records
+        f.cnt[0] += n2; f.cnt[1] += n3;
+        for (int left = n2 + n3; left > 0;) {                                // a run that would straddle a chunk border is split here
+            const int n = (int)std::min<long long>(left, m.chunk - m.filled % m.chunk);
+            if (!f.runs.empty() && f.runs.back().off + f.runs.back().n == m.filled && m.filled % m.chunk != 0) f.runs.back().n += n;
+            else f.runs.push_back({m.filled, n});
+            m.filled += n; left -= n;
+        }
+    }
+}
+
+// the archive runs of a frame as segments of `kind` behind `start`
+static void map_push_runs(const MapArchive& m, const MapFrame* f, int kind, std::vector<MapSeg>& segs, int& start) {
+    if (!f) return;
+    for (const MapRun& r : f->runs) {
+        segs.push_back({m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, start, r.n, kind, 0});
+        start += r.n;
+    }
+}
+static int map_send_segs(nalo_ctx* c, MapArchive& m, const std::vector<MapSeg>& segs, int total, MapSrcDev& S) {
+    const size_t n = std::max<size_t>(segs.size(), 1);
+    NALO_HIP(c, m.seg_h.reserve(n)); NALO_HIP(c, m.seg_d.reserve(n));
+    std::copy(segs.begin(), segs.end(), m.seg_h.p);
+    if (!segs.empty()) NALO_HIP(c, hipMemcpyAsync(m.seg_d.p, m.seg_h.p, segs.size() * sizeof(MapSeg), hipMemcpyHostToDevice, c->stream));
+    S.segs = m.seg_d.p; S.nseg = (int)segs.size(); S.total = total; S.nb = (total + 255) / 256;
+    NALO_HIP(c, m.qcnt.reserve((size_t)S.nb + 1 + 8));
+    S.cnt = m.qcnt.p;
+    return NALO_OK;
+}
+
+}  // namespace nalo
+
+using namespace nalo;
+
+extern "C" {
+
+int nalo_map_enable(nalo_ctx* c, int on, int chunk_points) {
+    if (!c) return NALO_ERR_ARG;
+    if (chunk_points < 0) return fail(c, NALO_ERR_ARG, "nalo_map_enable: chunk_points must not be negative");
+    if (on) {
+        if (c->xchg_failed) return fail(c, NALO_ERR_STATE, "nalo_map_enable: a cross-rank sum of this context failed earlier");
+        MapWindowView V;
+        if (c->ba && ba_map_view(c, -1, &V) == NALO_OK && V.sharded) return fail(c, NALO_ERR_STATE, "nalo_map_enable: the window is sharded (a rank holds only its own points)");
+    }
+    if (!c->map) { if (!on) return NALO_OK; c->map = new MapArchive(); }
+    MapArchive& m = *c->map;
+    if (on && m.chunks.empty()) m.chunk = chunk_points > 0 ? chunk_points : 65536;
+    m.on = on != 0;
+    return NALO_OK;
+}
+
+int nalo_map_reset(nalo_ctx* c) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->map) return NALO_OK;
+    c->map->frames.clear(); c->map->filled = 0; c->map->pending = false;
+    return NALO_OK;
+}
+
+int nalo_map_counts(nalo_ctx* c, int frame_id, int counts[2]) {
+    if (!c || !counts) return fail(c, NALO_ERR_ARG, "nalo_map_counts: bad argument");
+    const auto it = c->map ? c->map->frames.find(frame_id) : std::map<int, MapFrame>::iterator();
+    if (!c->map || it == c->map->frames.end()) return fail(c, NALO_ERR_ARG, "nalo_map_counts: the archive has never seen this frame_id");
+    counts[0] = it->second.cnt[0]; counts[1] = it->second.cnt[1];
+    return NALO_OK;
+}
+
+int nalo_map_get_frame(nalo_ctx* c, int frame_id, nalo_map_record* records, int cap, int* n) {
+    if (!c || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_get_frame: bad argument");
+    const auto it = c->map ? c->map->frames.find(frame_id) : std::map<int, MapFrame>::iterator();
+    if (!c->map || it == c->map->frames.end()) return fail(c, NALO_ERR_ARG, "nalo_map_get_frame: the archive has never seen this frame_id");
+    MapArchive& m = *c->map;
+    const MapFrame& f = it->second;
+    *n = f.cnt[0] + f.cnt[1];
+    if (cap < *n || (*n > 0 && !records)) return fail(c, NALO_ERR_ARG, "nalo_map_get_frame: cap is smaller than the frame's record count");
+    if (*n == 0) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<nalo_map_record> all((size_t)*n);
+    size_t at = 0;
+    for (const MapRun& r : f.runs) {
+        NALO_HIP(c, hipMemcpy(all.data() + at, m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, (size_t)r.n * sizeof(nalo_map_record), hipMemcpyDeviceToHost));
+        at += (size_t)r.n;
+    }
+    size_t o = 0;
+    for (int st = 2; st <= 3; ++st) for (const nalo_map_record& r : all) if (r.status == st) records[o++] = r;
+    return NALO_OK;
+}
+
+int nalo_map_world_points(nalo_ctx* c, int frame_id, const double camToWorld[12], double* xyz, int cap, int* n) {
+    if (!c || !camToWorld || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_world_points: bad argument");
+    const auto it = c->map ? c->map->frames.find(frame_id) : std::map<int, MapFrame>::iterator();
+    if (!c->map || it == c->map->frames.end()) return fail(c, NALO_ERR_ARG, "nalo_map_world_points: the archive has never seen this frame_id");
+    MapArchive& m = *c->map;
+    *n = it->second.cnt[0];
+    if (cap < *n || (*n > 0 && !xyz)) return fail(c, NALO_ERR_ARG, "nalo_map_world_points: cap is smaller than the frame's marginalised points");
+    if (*n == 0) return NALO_OK;
+    MapWindowView V;
+    { int rc = ba_map_view(c, frame_id, &V); if (rc) return rc; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "map_world_points");
+    std::vector<MapSeg> segs; int total = 0;
+    map_push_runs(m, &it->second, 2, segs, total);
+    MapWorldDev D{};
+    { int rc = map_send_segs(c, m, segs, total, D.S); if (rc) return rc; }
+    NALO_HIP(c, m.wxyz.reserve(3 * (size_t)*n)); NALO_HIP(c, m.wxyz_h.reserve(3 * (size_t)*n));
+    std::memcpy(D.ci, V.ci, sizeof(D.ci)); std::memcpy(D.m, camToWorld, sizeof(D.m)); D.xyz = m.wxyz.p; D.cap = *n;
+    { int rc = map_world_launch(c, D); if (rc) return rc; }
+    NALO_HIP(c, hipMemcpyAsync(m.wxyz_h.p, m.wxyz.p, 3 * (size_t)*n * 8, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(xyz, m.wxyz_h.p, 3 * (size_t)*n * 8);
+    return NALO_OK;
+}
+
+int nalo_map_world_points_host(int n, const float* u, const float* v, const float* idepth, const float calib_inv[4], const double m[12], double* xyz) {
+    if (n < 0 || !calib_inv || !m || (n > 0 && (!u || !v || !idepth || !xyz))) return NALO_ERR_ARG;
+    for (int i = 0; i < n; ++i) map_world_point(u[i], v[i], idepth[i], calib_inv, m, xyz + 3 * i);
+    return NALO_OK;
+}
+
+int nalo_map_frame_cloud(nalo_ctx* c, nalo_map_cloud_args* a) {
+    if (!c || !a) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: bad argument");
+    a->n = 0; a->n_needed = 0;
+    for (int i = 0; i < 4; ++i) a->records[i] = a->survivors[i] = 0;
+    if (a->sparsity > 1) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: sparsity > 1 is not supported (rand() % factor makes every later draw index depend on earlier draws)");
+    if (a->cap < 0 || a->n_draws < 0) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: bad argument");
+    MapWindowView V;
+    { int rc = ba_map_view(c, a->frame_id, &V); if (rc) return rc; }
+    const MapFrame* f = nullptr;
+    if (c->map) { const auto it = c->map->frames.find(a->frame_id); if (it != c->map->frames.end()) f = &it->second; }
+    if (V.widx < 0 && !f) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: frame_id is neither in the window nor in the archive");
+    if (V.widx >= 0 && !V.pts_ok) return fail(c, NALO_ERR_STATE, "nalo_map_frame_cloud: the frame is in the window but the window's points are unset (or sharded): carry or re-issue the window first");
+    if (!c->map) c->map = new MapArchive();                                 // the clouds' scratch lives there (the archive stays off)
+    MapArchive& m = *c->map;
+    // the record list, counted from the host's mirrors
+    int n_imm = 0;
+    const bool imm = a->with_immature && V.widx >= 0 && c->imm_res_n > 0;
+    if (imm) for (int i = 0; i < c->imm_res_n && i < (int)c->imm_host_h.size(); ++i) n_imm += c->imm_host_h[i] == V.widx;
+    const int records = n_imm + (V.widx >= 0 ? V.n_valid : 0) + (f ? f->cnt[0] + f->cnt[1] : 0);
+    a->n_needed = 8 * records;
+    if (a->cap < a->n_needed || (a->draws && a->n_draws < a->n_needed)) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: cap / n_draws below 8 x the frame's records (n_needed)");
+    if (records > 0 && (!a->xyz || !a->rgb)) return fail(c, NALO_ERR_ARG, "nalo_map_frame_cloud: xyz and rgb required");
+    if (records == 0) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "map_frame_cloud");
+    std::vector<MapSeg> segs; int total = 0;
+    if (imm && n_imm) { segs.push_back({nullptr, total, c->imm_res_n, 0, 0}); total += c->imm_res_n; }
+    if (V.widx >= 0 && V.seg) { segs.push_back({V.kmap, total, V.seg, 1, 0}); total += V.seg; }
+    map_push_runs(m, f, 2, segs, total);
+    map_push_runs(m, f, 3, segs, total);
+    MapCloudDev D{};
+    { int rc = map_send_segs(c, m, segs, total, D.S); if (rc) return rc; }
+    D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n; D.S.widx = V.widx;
+    D.S.flags = V.flags; D.S.geo = V.geo; D.S.col0 = V.col0; D.S.col1 = V.col1; D.S.acc = V.acc; D.S.prior = V.prior; D.S.relbs = V.relbs;
+    D.mode = a->display_mode; D.scaledTH = a->scaledTH; D.absTH = a->absTH; D.minRelBS = a->minRelBS; std::memcpy(D.ci, V.ci, sizeof(D.ci));
+    const size_t nv = (size_t)a->n_needed;
+    NALO_HIP(c, m.cxyz.reserve(3 * nv)); NALO_HIP(c, m.crgb.reserve(3 * nv)); NALO_HIP(c, m.cxyz_h.reserve(3 * nv)); NALO_HIP(c, m.crgb_h.reserve(3 * nv)); NALO_HIP(c, m.stats_h.reserve(9));
+    D.xyz = m.cxyz.p; D.rgb = m.crgb.p; D.cap = records; D.stats = D.S.cnt + D.S.nb + 1;
+    NALO_HIP(c, hipMemsetAsync(D.stats, 0, 8 * 4, c->stream));
+    if (a->draws) {
+        NALO_HIP(c, m.draws_h.reserve(nv)); NALO_HIP(c, m.draws_d.reserve(nv));
+        std::memcpy(m.draws_h.p, a->draws, nv * 4);
+        NALO_HIP(c, hipMemcpyAsync(m.draws_d.p, m.draws_h.p, nv * 4, hipMemcpyHostToDevice, c->stream));
+        D.draws = m.draws_d.p;
+    }
+    { int rc = map_cloud_launch(c, D); if (rc) return rc; }
+    // the vertex count is known only behind the scan: everything the call may have written comes up in the one wait
+    NALO_HIP(c, hipMemcpyAsync(m.stats_h.p, D.S.cnt + D.S.nb, 9 * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.cxyz_h.p, m.cxyz.p, 3 * nv * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.crgb_h.p, m.crgb.p, 3 * nv, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const int ns = m.stats_h.p[0];
+    for (int i = 0; i < 4; ++i) { a->records[i] = m.stats_h.p[1 + i]; a->survivors[i] = m.stats_h.p[5 + i]; }
+    if (ns < 0 || 8 * (size_t)ns > nv) return fail(c, NALO_ERR_HIP, "nalo_map_frame_cloud: the device counted more survivors than the frame has records");
+    a->n = 8 * ns;
+    std::memcpy(a->xyz, m.cxyz_h.p, 3 * (size_t)a->n * 4); std::memcpy(a->rgb, m.crgb_h.p, 3 * (size_t)a->n);
+    return NALO_OK;
+}
+
+}

@@ -102,6 +102,7 @@ struct ProfEntry { double ms = 0; int n = 0; std::vector<std::pair<hipEvent_t, h
 struct BAWindow;
 struct PixSel;
 struct Initializer;
+struct MapArchive;
 
 }  // namespace nalo
 
@@ -169,6 +170,7 @@ struct nalo_ctx {
     void* rccl = nullptr;                    // RCCL communicators of the sharded BA (host_rccl.hip)
     bool xchg_failed = false;                // a cross-rank sum failed (host_rccl.hip): the ranks' systems may differ, every later BA call of this context fails
     nalo::Initializer* init = nullptr;       // two-frame initialiser state (host_init.hip)
+    nalo::MapArchive* map = nullptr;         // the archive of removed points and the clouds made from it (host_map.hip); NULL until nalo_map_enable
     nalo_settings set = {1, nalo::kAffineOptModeA, nalo::kAffineOptModeB, 1};   // util/settings.cpp:71,128-129,74
 
     // ---- host wall-clock accounting (NALO_HOST_TIMING=1, read by nalo_create, prints it at nalo_destroy)
@@ -293,6 +295,45 @@ int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
 // host_ba.hip: nalo_dense_fit_planes' window half. The device slots of host_frame's points in submission order (*kmap, *seg entries: a segment of the map
 // nalo_trk_set_ref_from_window keeps), how many of them are valid (the host's mirror of the flags), the arrays the gather reads and the frame's slot
 int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, int* seg, int* n_valid, const float4** geo, const uint8_t** flags);
+// ---- the map (host_map.hip, kernels_map.hip): removed points archived on the device, and the clouds the reference publishes per keyframe
+// nalo_ba_marginalize_flagged's append: the window's arrays as the kernels read them. Entry k of kmap is the k-th point in (host, submission) order.
+struct MapAppendDev {
+    int P, nb;                                                                  // entries of kmap and their 256-lane workgroups
+    const int *kmap, *blk_host;
+    const uint8_t *flags, *ngood, *dec;                                         // dec / H: ba_flag_points_kernel's outputs per slot
+    const float4 *geo, *col0, *col1, *acc;
+    const float *prior, *relbs, *H;                                             // relbs: the buffer of the last pass that recorded relBS, taken BEFORE the marginalisation pass swaps it
+    int frame_id[NALO_MAX_WINDOW];
+    int *cnt, *hs, *hs_next;                                                    // cnt [nb + 1]: removed points per workgroup, scanned; hs [NALO_MAX_WINDOW][2]: per host {marginalised, out}
+    nalo_map_record* const* chunks; long long base, cap; int chunk;             // record at archive position q lives at chunks[q / chunk][q % chunk]; cap: positions that exist
+};
+int map_append_rank_launch(nalo_ctx* c, const MapAppendDev& A);                 // counts + their scan
+int map_append_write_launch(nalo_ctx* c, const MapAppendDev& A, bool patch);    // the records; patch: the two words marginalizePointsF's addPoint rewrites on a marginalised point
+// a cloud's records: a virtual list of segments. kind 0: the resident immature set (every point; the frame's are picked by host_idx), 1: a segment of kmap (valid points),
+// 2 / 3: an archive run, of which the pass takes the records of that status
+struct MapSeg { const void* p; int start, n, kind, pad; };
+struct MapSrcDev {
+    const MapSeg* segs; int nseg, total, nb;
+    const float* imm; int immN, widx;
+    const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs;
+    int* cnt;                                                                   // [nb + 1] survivors per workgroup, scanned
+};
+struct MapWorldDev { MapSrcDev S; float ci[4]; double m[12]; double* xyz; int cap; };                                           // cap: points xyz holds
+struct MapCloudDev { MapSrcDev S; int mode; float scaledTH, absTH, minRelBS, ci[4]; const int* draws; float* xyz; uint8_t* rgb; int* stats; int cap; };   // stats: records [4] | survivors [4], zero before; cap: records the outputs hold
+int map_world_launch(nalo_ctx* c, const MapWorldDev& D);
+int map_cloud_launch(nalo_ctx* c, const MapCloudDev& D);
+// host_map.hip: what nalo_ba_marginalize_flagged calls around its marginalisation. begin: room for `ub` more records (a refusal touches nothing), the ranks and the
+// records, A.chunks / base / cap / chunk / cnt / hs filled in here; patch: behind the marginalisation's accumulation; fetch: the per-host counts on their way up, before
+// the call's one wait; commit: the host index, after it
+bool map_on(const nalo_ctx* c);
+int map_append_begin(nalo_ctx* c, MapAppendDev& A, int W, int ub);
+int map_append_patch(nalo_ctx* c);
+int map_append_fetch(nalo_ctx* c);
+void map_append_commit(nalo_ctx* c);
+void map_destroy(nalo_ctx* c);
+// host_ba.hip: the window as nalo_map_frame_cloud reads it. widx = -1: frame_id is not in the window; pts_ok: the point arrays stand (kmap: the frame's seg entries, n_valid of them valid). ci: {fxi, fyi, cxi, cyi} of the CalibHessian (value_scaledi)
+struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4]; bool sharded; };
+int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
 // host_ba.hip
 void ba_destroy(nalo_ctx* c);
 // host_rccl.hip
