@@ -173,6 +173,42 @@ int nalo_trk_get_pc(nalo_ctx* ctx, int lvl, int* n, float* u, float* v, float* i
  * sampled point stays outside the count. Nothing is appended when the box touches the border, refMaskColor is 0 (:621-630). *n_added = growth of pc_n[0]. */
 int nalo_trk_append_plane_points(nalo_ctx* ctx, const float dir[3], float dis_plane, int refMaskColor, const int rect[4], int* n_added);
 int nalo_trk_get_depth(nalo_ctx* ctx, int lvl, float* idepth, float* weight_sums);
+/* The counterpart of nalo_trk_get_depth (as nalo_trk_set_pc is of nalo_trk_get_pc): direct injection of one level's inverse-depth map and weight sums, w_lvl * h_lvl
+ * floats each. Allocates the level's buffers when no reference was set (a half that is not given then reads as zeros) and sets slot_ref. Either array may be NULL: a NULL
+ * idepth leaves the level's inverse depths untouched, a NULL weight_sums its weight sums. Nothing else is touched: no cloud, no other level. For tests (maps the scatter
+ * and dilation of nalo_trk_set_ref never produce) and as the missing half of a tracker checkpoint. */
+int nalo_trk_set_depth(nalo_ctx* ctx, int slot_ref, int lvl, const float* idepth, const float* weight_sums);
+
+/* CoarseTracker::debugPlotIDepthMap (CoarseTracker.cpp:1263-1359; FullSystem.cpp:1408 -> Output3DWrapper::pushDepthImage) on the device: the jet-coloured depth image
+ * of the current tracking reference, from the level-0 inverse-depth map (what nalo_trk_get_depth(ctx, 0, ...) returns) and the planar irradiance I[0] of the reference's
+ * slot. Runs on the context's stream behind whatever nalo_trk_set_ref* enqueued; the host waits once. The result equals the reference's loops byte for byte:
+ *   - quantiles (:1271-1281): allID = every idepth[0][i] > 0 (NaN excluded, +inf included and last); with n = size - 1 the order statistics at ranks (int)(n * 0.05) and
+ *     (int)(n * 0.95), the product in double. Found exactly by a radix select on the float bit patterns; the map is not sorted and the count does not visit the host.
+ *   - smoothing (:1286-1313) against minmax_io = {minIdJetVisTracker, maxIdJetVisTracker}, which stay with the caller (start them at -1 as FullSystem.h does): float
+ *     arithmetic as written, maxChange = (float)(0.3 * (double)(max - min)), the four ifs in the reference's order, the `< 0` initialisation; minmax_io is rewritten as the
+ *     reference rewrites its pointers. NULL = the reference's NULL pointers: no smoothing, nothing written.
+ *   - base image (:1318-1323): c = (int)(I * 0.9f), 255 if larger, the byte (unsigned char)c on all three channels (a negative c wraps: -1 -> 255).
+ *   - plot rule (:1325-1344): source (x, y) with 3 <= x < w - 3, 3 <= y < h - 3 plots when bp[0] > 0 || nid >= 3 over the five-point stencil, colour
+ *     makeJet3B(((sid / nid) - minID) / (maxID - minID)) (globalFuncs.h:350-367, branch arithmetic in double, bytes truncated).
+ *   - setPixelCirc (MinimalImage.h:112-126): a plotting source colours the 40 pixels at Chebyshev distance 2 or 3 from it (not itself, not its eight neighbours);
+ *     sources are visited in raster order, so where rings overlap the raster-last source wins. Computed as a gather, without atomics.
+ * Three conversions the reference leaves undefined are DEFINED here:
+ *   1. float -> int of the grey value outside int's range saturates, and NaN gives 0;
+ *   2. a negative c wraps as C++'s int -> unsigned char does;
+ *   3. a NaN id (maxID == minID: 0 / 0) paints the white pixel (255, 255, 255) that x86 produces.
+ * NALO_ERR_ARG: NULL ctx / args / bgr. NALO_ERR_HIP: a cross-rank exchange of this context failed earlier. NALO_ERR_STATE: no tracking reference (the reference's
+ * `w[1] == 0` return), or the map holds no positive value (the reference indexes an empty vector): then n_positive = 0, nothing is painted and bgr / idepth /
+ * minmax_io are left as they were. A sharded tracker (nalo_trk_set_shard) holds the whole reference on every rank: the call works there unchanged.
+ * debugSaveImages' PNG write stays with the caller. */
+typedef struct nalo_depth_image_args {
+    float*   minmax_io;          /* in/out {minID, maxID}; NULL = the reference's NULL pointers */
+    uint8_t* bgr;                /* out, 3 * w * h bytes, raster order, the three bytes of a pixel in Vec3b's order: the MinimalImageB3 handed to pushDepthImage */
+    float*   idepth;             /* out, optional, w * h: idepth[0] for pushDepthImageFloat, from the same call and the same wait */
+    int      n_positive;         /* out: allID.size() */
+    float    min_new, max_new;   /* out: allID[(int)(n*0.05)], allID[(int)(n*0.95)] */
+    float    min_used, max_used; /* out: minID / maxID the image was painted with (after the smoothing) */
+} nalo_depth_image_args;
+int nalo_trk_depth_image(nalo_ctx* ctx, nalo_depth_image_args* args);
 
 /* Sharded tracker (the reference's analogue is the per-thread sum of calcGSSSE, CoarseTracker.cpp:828-885): with world > 1 every rank evaluates
  * points [n rank / world, n (rank + 1) / world) of every pyramid level and the 52 sums of an evaluation (45 H entries, E and the six counters, as doubles) are summed

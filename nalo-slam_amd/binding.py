@@ -28,7 +28,7 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
     "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download",
-    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
+    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
@@ -83,6 +83,12 @@ class MapCloudArgs(C.Structure):
 MAP_RECORD_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("idepth", np.float32), ("idepth_hessian", np.float32), ("maxRelBaseline", np.float32),
                              ("status", np.int32), ("decision", np.int32), ("frame_id", np.int32), ("color", np.float32, 8)])
 assert MAP_RECORD_DTYPE.itemsize == 64
+
+
+class DepthImageArgs(C.Structure):
+    """nalo_depth_image_args (include/nalo_gpu.h)"""
+    _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
+                ("min_used", C.c_float), ("max_used", C.c_float)]
 
 
 class Settings(C.Structure):
@@ -141,6 +147,8 @@ def load():
     L.nalo_trk_set_pc.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_get_pc.argtypes = [vp, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_get_depth.argtypes = [vp, C.c_int, c_fp, c_fp]
+    L.nalo_trk_set_depth.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp]
+    L.nalo_trk_depth_image.argtypes = [vp, C.POINTER(DepthImageArgs)]
     L.nalo_trk_eval.argtypes = [vp, C.c_int, C.c_int, c_dp, c_dp, c_fp, C.c_float, C.c_float, C.c_int, c_dp, c_dp, c_dp]
     L.nalo_trk_track.argtypes = [vp, C.c_int, c_dp, c_dp, c_dp, c_fp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]
     L.nalo_ba_set_window.argtypes = [vp, C.c_int, C.POINTER(FrameState), c_dp, c_dp]
@@ -410,6 +418,30 @@ class Context:
         a, b = np.zeros(n, np.float32), np.zeros(n, np.float32)
         self._ck(self.L.nalo_trk_get_depth(self.h_, lvl, _f(a), _f(b)))
         return a, b
+
+    def trk_set_depth(self, slot, lvl, idepth=None, weight_sums=None):
+        """one level's inverse-depth map / weight sums injected directly (nalo_trk_set_depth); None leaves that half untouched"""
+        n = (self.w >> lvl) * (self.h >> lvl)
+        a = [None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1) for x in (idepth, weight_sums)]
+        assert all(x is None or x.size == n for x in a)
+        self._ck(self.L.nalo_trk_set_depth(self.h_, slot, lvl, _f(a[0]), _f(a[1])))
+
+    def trk_depth_image(self, minmax=None, want_idepth=False):
+        """debugPlotIDepthMap on the device (nalo_trk_depth_image). minmax: the caller's (minIdJetVisTracker, maxIdJetVisTracker) pair, None = the reference's
+        NULL pointers. Returns a dict: bgr (h, w, 3) uint8, minmax (the rewritten pair as float32, or None), n_positive, min_new, max_new, min_used, max_used
+        (float32) and, when asked for, idepth (w * h)"""
+        a = DepthImageArgs()
+        bgr = np.zeros((self.h, self.w, 3), np.uint8)
+        mm = None if minmax is None else np.array(minmax, np.float32).reshape(2)
+        idp = np.zeros(self.w * self.h, np.float32) if want_idepth else None
+        a.minmax_io, a.bgr, a.idepth = _f(mm), _u8(bgr), _f(idp)
+        self._ck(self.L.nalo_trk_depth_image(self.h_, C.byref(a)))
+        out = {"bgr": bgr, "minmax": mm, "n_positive": a.n_positive}
+        for k in ("min_new", "max_new", "min_used", "max_used"):
+            out[k] = np.float32(getattr(a, k))
+        if want_idepth:
+            out["idepth"] = idp
+        return out
 
     def trk_eval(self, slot_new, lvl, T, affLL, b0, cutoff, want_gs=True):
         T = np.ascontiguousarray(T, np.float64).reshape(3, 4)

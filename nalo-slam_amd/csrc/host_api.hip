@@ -424,6 +424,61 @@ int nalo_trk_get_depth(nalo_ctx* c, int lvl, float* idepth, float* wsum) {
     return NALO_OK;
 }
 
+// direct injection of one level's inverse-depth map / weight sums: the counterpart of nalo_trk_get_depth. Nothing else is touched (no cloud, no other level).
+int nalo_trk_set_depth(nalo_ctx* c, int slot_ref, int lvl, const float* idepth, const float* wsum) {
+    if (!c || slot_ref < 0 || slot_ref >= (int)c->slots.size() || lvl < 0 || lvl >= c->levels) return fail(c, NALO_ERR_ARG, "nalo_trk_set_depth: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->wl[lvl] * c->hl[lvl];
+    const bool fresh = !c->trk_idepth[lvl].p;
+    NALO_HIP(c, c->trk_idepth[lvl].reserve(npx)); NALO_HIP(c, c->trk_wsum[lvl].reserve(npx)); NALO_HIP(c, c->trk_wbak[lvl].reserve(npx));
+    if (fresh) {                                                                 // a half that is not given reads as zeros, not as whatever the allocation held
+        NALO_HIP(c, hipMemsetAsync(c->trk_idepth[lvl].p, 0, npx * 4, c->stream));
+        NALO_HIP(c, hipMemsetAsync(c->trk_wsum[lvl].p, 0, npx * 4, c->stream));
+    }
+    c->slot_ref = slot_ref;
+    // on the main stream, behind whatever nalo_trk_set_ref* enqueued on these buffers
+    if (idepth) NALO_HIP(c, hipMemcpyAsync(c->trk_idepth[lvl].p, idepth, npx * 4, hipMemcpyHostToDevice, c->stream));
+    if (wsum) NALO_HIP(c, hipMemcpyAsync(c->trk_wsum[lvl].p, wsum, npx * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                                // the arrays are the caller's: free to reuse on return
+    return NALO_OK;
+}
+
+// CoarseTracker::debugPlotIDepthMap (CoarseTracker.cpp:1263-1359) from the resident level-0 map and the reference slot's irradiance (kernels_depth_image.hip).
+// Everything is enqueued on the main stream; the image, the optional map and the scalars come up through one pinned block behind ONE wait, and reach the
+// caller's arrays only when the call succeeds.
+int nalo_trk_depth_image(nalo_ctx* c, nalo_depth_image_args* a) {
+    if (!c || !a || !a->bgr) return fail(c, NALO_ERR_ARG, "nalo_trk_depth_image: bad argument");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_trk_depth_image: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (c->slot_ref < 0 || !c->slots[c->slot_ref].valid || !c->trk_idepth[0].p) return fail(c, NALO_ERR_STATE, "nalo_trk_depth_image: no tracking reference (nalo_trk_set_ref* / nalo_trk_set_depth on a slot that holds a frame)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "trk_depth_image");
+    const size_t npx = (size_t)c->w * c->h, off_bgr = 64, off_id = off_bgr + ((3 * npx + 15) & ~(size_t)15);
+    NALO_HIP(c, c->di_scr.reserve(kDepthImageScratchWords)); NALO_HIP(c, c->di_bgr.reserve(3 * npx));
+    NALO_HIP(c, c->di_host.reserve(off_id + (a->idepth ? 4 * npx : 0)));
+    const float* const map = c->trk_idepth[0].p;
+    const bool io = a->minmax_io != nullptr;
+    unsigned* const res_dev = c->di_scr.p + kDepthImageScratchWords - 8;
+    {
+        ProfScope ps(c, "trk_depth_image");
+        const int rc = depth_image_launch(c, map, c->slots[c->slot_ref].I[0].p, io ? a->minmax_io[0] : 0.f, io ? a->minmax_io[1] : 0.f, io ? 1 : 0, c->di_scr.p, c->di_bgr.p);
+        if (rc) return rc;
+    }
+    NALO_HIP(c, hipMemcpyAsync(c->di_host.p, res_dev, 32, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(c->di_host.p + off_bgr, c->di_bgr.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
+    if (a->idepth) NALO_HIP(c, hipMemcpyAsync(c->di_host.p + off_id, map, 4 * npx, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned res[8];
+    std::memcpy(res, c->di_host.p, sizeof(res));
+    a->n_positive = (int)res[0];
+    if (res[0] == 0) return fail(c, NALO_ERR_STATE, "nalo_trk_depth_image: the level-0 map holds no positive inverse depth");   // the reference indexes an empty vector here
+    std::memcpy(&a->min_new, &res[1], 4); std::memcpy(&a->max_new, &res[2], 4);
+    std::memcpy(&a->min_used, &res[3], 4); std::memcpy(&a->max_used, &res[4], 4);
+    if (io) std::memcpy(a->minmax_io, &res[5], 8);
+    std::memcpy(a->bgr, c->di_host.p + off_bgr, 3 * npx);
+    if (a->idepth) std::memcpy(a->idepth, c->di_host.p + off_id, 4 * npx);
+    return NALO_OK;
+}
+
 // SURVEY 8(e), tracker: every rank holds the whole reference (nalo_trk_set_ref is replicated: makeCoarseDepthL0's dilation and normalisation need every point's
 // neighbours) and evaluates rank/world of every level's point cloud; the 45 + 7 sums of an evaluation are all-reduced through the hook, so every rank takes the same LM
 // step. Worth it for level sizes of ~1e5 points and more (CoarseTracker.cpp:828-885 sums per thread in the reference).

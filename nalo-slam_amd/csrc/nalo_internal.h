@@ -147,6 +147,8 @@ struct nalo_ctx {
     nalo::DevBuf<int> trk_cnt;               // hits per level-0 pixel of the reference scatter (ordered redo of pixels with >= 3 hits)
     nalo::DevBuf<float> upload_tmp;
     nalo::HostBuf<float> pinned_f;           // nalo_trk_set_ref's staging (upload4)
+    // nalo_trk_depth_image (kernels_depth_image.hip), sized on first use: the select's histograms, state and results; the painted image; the pinned block it comes up through
+    nalo::DevBuf<unsigned> di_scr; nalo::DevBuf<uint8_t> di_bgr; nalo::HostBuf<uint8_t> di_host;
     nalo::HostBuf<float> imm_host; nalo::DevBuf<float> imm_dev;   // immature-point staging (pinned / device), grown together (imm_stage)
     nalo::DevBuf<float> imm_res; int imm_res_n = 0, imm_res_maxhost = -1;         // device-resident immature points (nalo_imm_resident_*)
     nalo::DevBuf<float> imm_type; bool imm_type_set = false; float imm_type_max = 0;   // their my_type (nalo_imm_resident_set_type; a new set invalidates it)
@@ -385,6 +387,10 @@ int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOr
 // kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points; the whole pyramid descent of nalo_trk_track in one persistent launch
 int trk_lm_blocks(int maxn);
 int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2], int coarsest, int stop_lvl, const double* minRes, double out24[32]);
+// kernels_depth_image.hip: debugPlotIDepthMap on c->stream. scr: kDepthImageScratchWords words (zeroed here; the results are its last 8: n_positive, min_new, max_new,
+// min_used, max_used, the rewritten minmax pair), bgr: 3 w h bytes. Nothing is painted when the map holds no positive value (n_positive = 0).
+constexpr int kDepthImageScratchWords = 2048 + 2 * 2048 + 2 * 512 + 16 + 8;
+int depth_image_launch(nalo_ctx* c, const float* idepth, const float* I, float io_min, float io_max, int have_io, unsigned* scr, uint8_t* bgr);
 // kernels_tracker.hip
 int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi);
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev);
