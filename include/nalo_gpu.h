@@ -570,7 +570,7 @@ int nalo_dense_make_map(nalo_ctx* ctx, int slot, const float plane[4], float mas
  *   append, as in the reference. NOT done here: the ground choice by `score` (:609-625) reads a variable fitPlane never writes; it stays with the caller.
  * nalo_dense_fit_planes input: what updateMap collects for the window's frame host_frame (MapPoint.cpp:246-259): its valid window points in submission order
  *   with idepth, then the resident immature points with that host_idx in resident order with (idepth_max + idepth_min) * 0.5f; mask: the frame's slot. The caller
- *   loops nalo_dense_make_map over the fitted clusters as before. Read on the device; the slot map of the window's points (4 bytes per point) goes down once
+ *   loops nalo_dense_make_map over the fitted clusters as before, or calls nalo_dense_update_map, which does both. Read on the device; the slot map of the window's points (4 bytes per point) goes down once
  *   per issued point list, shared with nalo_trk_set_ref_from_window.
  * nalo_plane_fit_members the last completed call's member lists: cluster_of[i] = the record index of input point i or -1 (cap >= the input count), order = the
  *   members of cluster 0, then 1, ... each in the reference's vector order (sum of n entries): what clusters[i][k] held, for tests and callers that keep objects.
@@ -814,7 +814,7 @@ int nalo_init_get_points(nalo_ctx* ctx, int lvl, int cap, int* n, float* u, floa
  *             run is the library's.
  *   frame_id  the caller's, from nalo_frame_state: the archive is keyed by it, so the frames of a session need distinct ids.
  *   Not archived: points removed by nalo_ba_marginalize_points (host flags). nalo_ba_snapshot / nalo_ba_restore do not include the archive.
- * nalo_map_reset      empties the archive and keeps its chunks.
+ * nalo_map_reset      empties the archive (and the dense archive of nalo_map_dense_enable) and keeps its chunks.
  * nalo_map_counts     counts = {pointHessiansMarginalized.size(), pointHessiansOut.size()} of the frame: the addends of flagFramesForMarginalization's
  *                     `out` (FullSystemMarginalize.cpp:77). NALO_ERR_ARG for a frame_id the archive has never seen.
  * nalo_map_get_frame  the frame's records: its status-2 records in archive order, then its status-3 records. *n = their number; cap < *n: NALO_ERR_ARG
@@ -871,8 +871,70 @@ int nalo_map_world_points_host(int n, const float* u, const float* v, const floa
 int nalo_map_frame_cloud(nalo_ctx* ctx, nalo_map_cloud_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * densemap=1: DenseMapping::updateMap (FullSystem/MapPoint.cpp:234-332, call site FullSystem.cpp:1488-1496) in one call, and FrameHessian::mapPoints as a
+ * device archive beside the sparse one. The per-cluster route (nalo_dense_fit_planes, then nalo_dense_make_map per cluster) stays as it is.
+ *
+ * nalo_dense_update_map   for the window's frame host_frame: the clusters and planes nalo_dense_fit_planes returns for the same arguments (the same code path;
+ *   clusters[] is filled as that call fills it), then per cluster, in record order, the loop of MapPoint.cpp:271-331 and makeMap:
+ *     not fitted              the reference's `continue` (:280-281): runs[k] = {zero rect, n = 0, accept = 0, first = -1}
+ *     mask_value == 0         rect = its box of the MASK scan (:300-310), nothing else (`if(pcolor==0) return;`, :355-357)
+ *     otherwise               rect, then the pixel loop of :367-401 over the box with its exclusive upper bounds and the extent test of :403 (the order-dependent
+ *                             maxy / maxz of SURVEY App. C.6 included): n = the points the loop kept, accept = the test (0 when n == 0: nothing to append;
+ *                             nalo_dense_make_map reports the test on the untouched seeds there, which passes).
+ *   rect is {INT_MAX, INT_MIN, INT_MAX, INT_MIN} when the value is nowhere in [2,w-2)x[2,h-2). The arithmetic is nalo_dense_make_map's (shared functions): the
+ *   two routes are equal bit for bit.
+ *   The kept points of every accepted cluster are appended to the dense archive under the frame's frame_id (nalo_frame_state): cluster order, raster order
+ *   inside a cluster - the order of fh->mapPoints.insert(...). A rejected cluster appends nothing; a second call for the same frame appends a second set of runs
+ *   (the reference does the same when a frame is third from last on two keyframes). runs[k].first = the position of the cluster's first point in the frame's
+ *   dense list, -1 when it appended nothing. No point crosses the bus: the records, the runs and the two counts come up.
+ *   Waits: two per call, none per cluster - one for the records and boxes (the host sizes the batched grid from them), one at the end; plus one, with a blocking
+ *   copy of the chunk table, in a call for which the archive allocates a chunk (never in steady state).
+ *   Reservation: room for every candidate of the scanned range (the pixels of [2,w-2)x[2,h-2) with i%3==0 || j%3==0; a pixel belongs to one cluster, so the count
+ *   bounds the call) is reserved before anything is touched: a refusal for lack of memory leaves the archive as it was.
+ *   Refusals (nothing appended, context usable): whatever nalo_dense_fit_planes refuses, with its codes (cap too small: NALO_ERR_ARG with *n_clusters set);
+ *   NALO_ERR_STATE the dense archive is not enabled, the frame's slot has no mask; NALO_ERR_ARG camToWorld, runs or n_appended NULL.
+ *
+ * nalo_map_dense_enable(ctx, on, chunk_points)   the archive grows in chunks of chunk_points 16-byte points; 0 = 262144 (4 MiB: two to three keyframes of ~10^5
+ *   points per allocation, and small enough that the unused tail of the last chunk does not matter). The size in force at the first allocation holds for the
+ *   context. A chunk is allocated once and never moved; in steady state nothing is allocated. Independent of nalo_map_enable. Images wider or higher than 65535
+ *   are refused (NALO_ERR_UNSUPPORTED: u, v are 16 bits). MEMORY: about 1.6 MB per keyframe at 10^5 points, released only by nalo_map_reset (which empties this
+ *   archive too and keeps its chunks for reuse) and nalo_destroy. nalo_ba_snapshot / nalo_ba_restore do not include it.
+ * nalo_map_dense_counts   the frame's points and appended cluster runs. NALO_ERR_ARG for a frame_id the dense archive has never seen (here and below).
+ * nalo_map_dense_get      the frame's points in append order; cap < *n: NALO_ERR_ARG with *n set.
+ * nalo_map_dense_world_points  SampleOutputWrapper's tsdf=1 loop over mapPoints (SampleOutputWrapper.h:152-176): one lane per point, in append order, through the
+ *   function nalo_map_world_points and nalo_io_write_pcd_points share, with (float)u, (float)v and the window's float inverse calibration: equal bit for bit to
+ *   nalo_map_world_points_host on the records of nalo_map_dense_get. cap < *n: NALO_ERR_ARG with *n set. One wait.
+ * nalo_map_dense_cloud    KeyFrameDisplay::refreshPC() (IOWrapper/Pangolin/KeyFrameDisplay.cpp:212-271): idepth < 0 skips (NaN takes the branch the comparison
+ *   gives it: it stays); depth = 1.0f / idepth; x = (u * fxi + cxi) * depth, y alike; z = depth * (1 + 2 * fxi * (r / (float)RAND_MAX - 0.5f)) with
+ *   RAND_MAX = 2^31 - 1 and r = draws[j] for OUTPUT vertex j (rand() is drawn for survivors only: an ordered compaction); draws == NULL: z = depth. Colour is
+ *   {bgr[2], bgr[1], bgr[0]}. {fxi, fyi, cxi, cyi}: the window's CalibHessian values, as nalo_map_frame_cloud takes them. cap (always) or n_draws (with draws)
+ *   below the frame's record count: NALO_ERR_ARG with n_needed set. records = the frame's points, survivors = n. One wait.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_dense_run {             /* one per cluster record, same index as the nalo_plane_cluster beside it */
+    int rect[4];                            /* minx, maxx, miny, maxy of the MASK scan; zeros for a cluster that was not fitted */
+    int n;                                  /* points makeMap's loop kept (mpcache.size()) */
+    int accept;                             /* the extent test of :403; 0 when n == 0 */
+    long long first;                        /* position of the run's first point in the frame's dense list, -1 when nothing was appended */
+} nalo_dense_run;
+typedef struct nalo_dense_point { uint16_t u, v; float idepth; float color; uint8_t bgr[3]; uint8_t pad; } nalo_dense_point;   /* 16 bytes; MapPoint{u, v, idepth, color, bgr} */
+typedef struct nalo_map_dense_cloud_args {
+    int frame_id;
+    int n_draws; const int* draws;          /* NULL: no jitter */
+    int cap; float* xyz; uint8_t* rgb;      /* cap vertices: [cap][3] each */
+    int n, n_needed;                        /* out: vertices written; the frame's records (what cap and n_draws must reach) */
+    int records, survivors;                 /* out */
+} nalo_map_dense_cloud_args;
+int nalo_dense_update_map(nalo_ctx* ctx, int host_frame, const nalo_plane_fit_args* fit, const double camToWorld[12], int cap, nalo_plane_cluster* clusters,
+                          nalo_dense_run* runs, int* n_clusters, int* n_appended);
+int nalo_map_dense_enable(nalo_ctx* ctx, int on, int chunk_points);
+int nalo_map_dense_counts(nalo_ctx* ctx, int frame_id, int* n_points, int* n_runs);
+int nalo_map_dense_get(nalo_ctx* ctx, int frame_id, nalo_dense_point* out, int cap, int* n);
+int nalo_map_dense_world_points(nalo_ctx* ctx, int frame_id, const double camToWorld[12], double* xyz /* n x 3 */, int cap, int* n);
+int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "ingest". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -37,6 +37,7 @@ EXPORTS = [
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
+    "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -83,6 +84,18 @@ class MapCloudArgs(C.Structure):
 MAP_RECORD_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("idepth", np.float32), ("idepth_hessian", np.float32), ("maxRelBaseline", np.float32),
                              ("status", np.int32), ("decision", np.int32), ("frame_id", np.int32), ("color", np.float32, 8)])
 assert MAP_RECORD_DTYPE.itemsize == 64
+
+
+class MapDenseCloudArgs(C.Structure):
+    """nalo_map_dense_cloud_args (include/nalo_gpu.h)"""
+    _fields_ = [("frame_id", C.c_int), ("n_draws", C.c_int), ("draws", c_ip), ("cap", C.c_int), ("xyz", c_fp), ("rgb", c_u8p), ("n", C.c_int), ("n_needed", C.c_int),
+                ("records", C.c_int), ("survivors", C.c_int)]
+
+
+# nalo_dense_run, nalo_dense_point (include/nalo_gpu.h)
+DENSE_RUN_DTYPE = np.dtype([("rect", np.int32, 4), ("n", np.int32), ("accept", np.int32), ("first", np.int64)])
+DENSE_POINT_DTYPE = np.dtype([("u", np.uint16), ("v", np.uint16), ("idepth", np.float32), ("color", np.float32), ("bgr", np.uint8, 3), ("pad", np.uint8)])
+assert DENSE_RUN_DTYPE.itemsize == 32 and DENSE_POINT_DTYPE.itemsize == 16
 
 
 class DepthImageArgs(C.Structure):
@@ -183,6 +196,12 @@ def load():
     L.nalo_map_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
     L.nalo_map_world_points_host.argtypes = [C.c_int, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp]
     L.nalo_map_frame_cloud.argtypes = [vp, C.POINTER(MapCloudArgs)]
+    L.nalo_dense_update_map.argtypes = [vp, C.c_int, C.POINTER(PlaneFitArgs), c_dp, C.c_int, vp, vp, c_ip, c_ip]
+    L.nalo_map_dense_enable.argtypes = [vp, C.c_int, C.c_int]
+    L.nalo_map_dense_counts.argtypes = [vp, C.c_int, c_ip, c_ip]
+    L.nalo_map_dense_get.argtypes = [vp, C.c_int, vp, C.c_int, c_ip]
+    L.nalo_map_dense_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
+    L.nalo_map_dense_cloud.argtypes = [vp, C.POINTER(MapDenseCloudArgs)]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -750,6 +769,72 @@ class Context:
             a.draws, a.n_draws = (None, 0) if d is None else (_i(d), len(d))
             self._ck(self.L.nalo_map_frame_cloud(self.h_, C.byref(a)))
         return dict(xyz=xyz[:a.n], rgb=rgb[:a.n], records=np.array(list(a.records)), survivors=np.array(list(a.survivors)), n_needed=cap)
+
+    # ---- the dense map: updateMap in one call, mapPoints archived on the device
+    def map_dense_enable(self, on=True, chunk_points=0):
+        self._ck(self.L.nalo_map_dense_enable(self.h_, int(bool(on)), int(chunk_points)))
+
+    def dense_update_map(self, host_frame, draws, cam_to_world, threshold=0.01, min_points=10, cap=2048, null_runs=False):
+        """updateMap for one window frame (nalo_dense_update_map) -> (clusters PLANE_DTYPE[C], runs DENSE_RUN_DTYPE[C], n_appended); self.plane_n_clusters holds
+        the count after a refusal too; cam_to_world=None and null_runs pass NULL"""
+        m = None if cam_to_world is None else np.ascontiguousarray(cam_to_world, np.float64).reshape(-1)
+        assert m is None or m.size == 12
+        runs = np.zeros(max(cap, 1), DENSE_RUN_DTYPE)
+        napp = np.zeros(1, np.int32)
+        call = lambda a, cap_, o, n: self.L.nalo_dense_update_map(self.h_, int(host_frame), a, None if m is None else _d(m), cap_, o,
+                                                                  None if null_runs else runs.ctypes.data_as(C.c_void_p), n, _i(napp))
+        recs, n = self._fit_planes(call, draws, threshold, min_points, 0, cap)
+        return recs, runs[:n].copy(), int(napp[0])
+
+    def map_dense_counts(self, frame_id):
+        """(points, appended cluster runs) of the frame's dense list"""
+        a, b = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.L.nalo_map_dense_counts(self.h_, int(frame_id), _i(a), _i(b)))
+        return int(a[0]), int(b[0])
+
+    def map_dense_get(self, frame_id):
+        """the frame's dense points (DENSE_POINT_DTYPE) in append order"""
+        n = C.c_int(0)
+        rc = self.L.nalo_map_dense_get(self.h_, int(frame_id), None, 0, C.byref(n))
+        if n.value == 0:
+            self._ck(rc)
+        pts = np.zeros(n.value, DENSE_POINT_DTYPE)
+        if n.value:
+            self._ck(self.L.nalo_map_dense_get(self.h_, int(frame_id), pts.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return pts
+
+    def map_dense_world_points(self, frame_id, cam_to_world):
+        """SampleOutputWrapper's tsdf=1 loop: the world points [n][3] (float64) of the frame's dense points"""
+        m = np.ascontiguousarray(cam_to_world, np.float64).reshape(-1)
+        assert m.size == 12
+        n = C.c_int(0)
+        rc = self.L.nalo_map_dense_world_points(self.h_, int(frame_id), _d(m), None, 0, C.byref(n))
+        if n.value == 0:
+            self._ck(rc)
+        xyz = np.zeros((n.value, 3), np.float64)
+        if n.value:
+            self._ck(self.L.nalo_map_dense_world_points(self.h_, int(frame_id), _d(m), _d(xyz), n.value, C.byref(n)))
+        return xyz
+
+    def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
+        """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes
+        the call is made with (the refusals); self.dense_cloud_needed holds n_needed after a refusal too"""
+        a = MapDenseCloudArgs()
+        a.frame_id = int(frame_id)
+        rc = self.L.nalo_map_dense_cloud(self.h_, C.byref(a))                    # cap = 0: answers n_needed (and is the whole call for a frame without records)
+        self.dense_cloud_needed = a.n_needed
+        if a.n_needed == 0:
+            self._ck(rc)
+        need = a.n_needed
+        xyz, rgb = np.zeros((need, 3), np.float32), np.zeros((need, 3), np.uint8)
+        if need:
+            d = None if draws is None else np.ascontiguousarray(draws, np.int32)
+            a.cap, a.xyz, a.rgb = need if cap is None else int(cap), _f(xyz), _u8(rgb)
+            a.draws, a.n_draws = (None, 0) if d is None else (_i(d), len(d) if n_draws is None else int(n_draws))
+            rc = self.L.nalo_map_dense_cloud(self.h_, C.byref(a))
+            self.dense_cloud_needed = a.n_needed
+            self._ck(rc)
+        return dict(xyz=xyz[:a.n], rgb=rgb[:a.n], records=int(a.records), survivors=int(a.survivors), n_needed=need)
 
     def ba_get_frames(self):
         arr = (FrameState * self.W)()

@@ -932,6 +932,8 @@ int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, in
     return NALO_OK;
 }
 
+int ba_frame_id(nalo_ctx* c, int host_frame) { return c->ba->frames[host_frame].frameID; }
+
 int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V) {
     if (!c->ba || c->ba->W < 1) return fail(c, NALO_ERR_STATE, "nalo_map: no window (its CalibHessian is the clouds' calibration)");
     BAWindow& w = *c->ba;

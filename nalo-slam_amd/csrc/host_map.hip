@@ -112,6 +112,77 @@ static int map_send_segs(nalo_ctx* c, MapArchive& m, const std::vector<MapSeg>& 
     return NALO_OK;
 }
 
+// ---- the dense map: FrameHessian::mapPoints of every frame, 16-byte points in chunks of their own (the same position -> chunk mapping as the archive above).
+// Per frame_id the host keeps the pieces (position, count) its points lie in, in append order, and the two totals.
+struct DenseFrame { std::vector<MapRun> runs; long long points = 0; int n_runs = 0; };
+struct DenseArchive {
+    bool on = false;
+    int chunk = 0;
+    long long filled = 0;
+    std::vector<DevBuf<nalo_dense_point>> chunks;
+    DevBuf<nalo_dense_point*> tab;
+    std::map<int, DenseFrame> frames;
+    // the consumers: segment table, draws, block counts, outputs and their pinned mirrors
+    HostBuf<MapSeg> seg_h; DevBuf<MapSeg> seg_d; HostBuf<int> draws_h; DevBuf<int> draws_d, cnt; HostBuf<int> cnt_h;
+    DevBuf<double> wxyz; HostBuf<double> wxyz_h; DevBuf<float> cxyz; DevBuf<uint8_t> crgb; HostBuf<float> cxyz_h; HostBuf<uint8_t> crgb_h;
+};
+
+bool map_dense_on(const nalo_ctx* c) { return c->dmap && c->dmap->on; }
+void map_dense_destroy(nalo_ctx* c) { delete c->dmap; c->dmap = nullptr; }
+
+int map_dense_reserve(nalo_ctx* c, long long ub, DenseArchiveView* V) {
+    DenseArchive& m = *c->dmap;
+    const size_t need = (size_t)((m.filled + ub + m.chunk - 1) / m.chunk);
+    if (need > m.chunks.size()) {
+        std::vector<DevBuf<nalo_dense_point>> fresh(need - m.chunks.size());
+        for (auto& b : fresh) NALO_HIP(c, b.reserve((size_t)m.chunk));      // a failure frees what this call allocated and leaves the archive as it was
+        DevBuf<nalo_dense_point*> tab;
+        NALO_HIP(c, tab.reserve(need));
+        std::vector<nalo_dense_point*> ptrs;
+        for (auto& b : m.chunks) ptrs.push_back(b.p);
+        for (auto& b : fresh) ptrs.push_back(b.p);
+        NALO_HIP(c, hipStreamSynchronize(c->stream));
+        NALO_HIP(c, hipMemcpy(tab.p, ptrs.data(), need * sizeof(nalo_dense_point*), hipMemcpyHostToDevice));
+        for (auto& b : fresh) m.chunks.push_back(std::move(b));
+        m.tab = std::move(tab);
+    }
+    V->chunks = m.tab.p; V->base = m.filled; V->cap = (long long)m.chunks.size() * m.chunk; V->chunk = m.chunk;
+    return NALO_OK;
+}
+long long map_dense_frame_points(nalo_ctx* c, int frame_id) {
+    const auto it = c->dmap->frames.find(frame_id);
+    return it == c->dmap->frames.end() ? 0 : it->second.points;
+}
+void map_dense_commit(nalo_ctx* c, int frame_id, int n_points, int n_runs) {
+    DenseArchive& m = *c->dmap;
+    DenseFrame& f = m.frames[frame_id];
+    f.points += n_points; f.n_runs += n_runs;
+    for (int left = n_points; left > 0;) {                                   // a piece never straddles a chunk border
+        const int n = (int)std::min<long long>(left, m.chunk - m.filled % m.chunk);
+        if (!f.runs.empty() && f.runs.back().off + f.runs.back().n == m.filled && m.filled % m.chunk != 0) f.runs.back().n += n;
+        else f.runs.push_back({m.filled, n});
+        m.filled += n; left -= n;
+    }
+}
+// the frame of a consumer call, its pieces as segments on the device, the block counts
+static int map_dense_frame(nalo_ctx* c, const char* who, int frame_id, DenseFrame** f) {
+    const auto it = c->dmap ? c->dmap->frames.find(frame_id) : std::map<int, DenseFrame>::iterator();
+    if (!c->dmap || it == c->dmap->frames.end()) return fail(c, NALO_ERR_ARG, std::string(who) + ": the dense archive has never seen this frame_id");
+    *f = &it->second;
+    return NALO_OK;
+}
+static int map_dense_send(nalo_ctx* c, DenseArchive& m, const DenseFrame& f, MapDenseDev& D) {
+    const size_t n = std::max<size_t>(f.runs.size(), 1);
+    NALO_HIP(c, m.seg_h.reserve(n)); NALO_HIP(c, m.seg_d.reserve(n));
+    int start = 0, k = 0;
+    for (const MapRun& r : f.runs) { m.seg_h.p[k++] = MapSeg{m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, start, r.n, 0, 0}; start += r.n; }
+    if (k) NALO_HIP(c, hipMemcpyAsync(m.seg_d.p, m.seg_h.p, (size_t)k * sizeof(MapSeg), hipMemcpyHostToDevice, c->stream));
+    D.segs = m.seg_d.p; D.nseg = k; D.total = start; D.nb = (start + 255) / 256;
+    NALO_HIP(c, m.cnt.reserve((size_t)D.nb + 1));
+    D.cnt = m.cnt.p;
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -135,6 +206,7 @@ int nalo_map_enable(nalo_ctx* c, int on, int chunk_points) {
 
 int nalo_map_reset(nalo_ctx* c) {
     if (!c) return NALO_ERR_ARG;
+    if (c->dmap) { c->dmap->frames.clear(); c->dmap->filled = 0; }
     if (!c->map) return NALO_OK;
     c->map->frames.clear(); c->map->filled = 0; c->map->pending = false;
     return NALO_OK;
@@ -257,6 +329,106 @@ int nalo_map_frame_cloud(nalo_ctx* c, nalo_map_cloud_args* a) {
     if (ns < 0 || 8 * (size_t)ns > nv) return fail(c, NALO_ERR_HIP, "nalo_map_frame_cloud: the device counted more survivors than the frame has records");
     a->n = 8 * ns;
     std::memcpy(a->xyz, m.cxyz_h.p, 3 * (size_t)a->n * 4); std::memcpy(a->rgb, m.crgb_h.p, 3 * (size_t)a->n);
+    return NALO_OK;
+}
+
+int nalo_map_dense_enable(nalo_ctx* c, int on, int chunk_points) {
+    if (!c) return NALO_ERR_ARG;
+    if (chunk_points < 0) return fail(c, NALO_ERR_ARG, "nalo_map_dense_enable: chunk_points must not be negative");
+    if (on && (c->w > 65535 || c->h > 65535)) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_map_dense_enable: images wider or higher than 65535 (u, v are 16 bits)");
+    if (!c->dmap) { if (!on) return NALO_OK; c->dmap = new DenseArchive(); }
+    DenseArchive& m = *c->dmap;
+    if (on && m.chunks.empty()) m.chunk = chunk_points > 0 ? chunk_points : 262144;
+    m.on = on != 0;
+    return NALO_OK;
+}
+
+int nalo_map_dense_counts(nalo_ctx* c, int frame_id, int* n_points, int* n_runs) {
+    if (!c || !n_points || !n_runs) return fail(c, NALO_ERR_ARG, "nalo_map_dense_counts: bad argument");
+    DenseFrame* f = nullptr;
+    { int rc = map_dense_frame(c, "nalo_map_dense_counts", frame_id, &f); if (rc) return rc; }
+    *n_points = (int)f->points; *n_runs = f->n_runs;
+    return NALO_OK;
+}
+
+int nalo_map_dense_get(nalo_ctx* c, int frame_id, nalo_dense_point* out, int cap, int* n) {
+    if (!c || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_dense_get: bad argument");
+    DenseFrame* f = nullptr;
+    { int rc = map_dense_frame(c, "nalo_map_dense_get", frame_id, &f); if (rc) return rc; }
+    DenseArchive& m = *c->dmap;
+    *n = (int)f->points;
+    if (cap < *n || (*n > 0 && !out)) return fail(c, NALO_ERR_ARG, "nalo_map_dense_get: cap is smaller than the frame's point count");
+    if (*n == 0) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    size_t at = 0;
+    for (const MapRun& r : f->runs) {
+        NALO_HIP(c, hipMemcpy(out + at, m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, (size_t)r.n * sizeof(nalo_dense_point), hipMemcpyDeviceToHost));
+        at += (size_t)r.n;
+    }
+    return NALO_OK;
+}
+
+int nalo_map_dense_world_points(nalo_ctx* c, int frame_id, const double camToWorld[12], double* xyz, int cap, int* n) {
+    if (!c || !camToWorld || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_dense_world_points: bad argument");
+    DenseFrame* f = nullptr;
+    { int rc = map_dense_frame(c, "nalo_map_dense_world_points", frame_id, &f); if (rc) return rc; }
+    DenseArchive& m = *c->dmap;
+    *n = (int)f->points;
+    if (cap < *n || (*n > 0 && !xyz)) return fail(c, NALO_ERR_ARG, "nalo_map_dense_world_points: cap is smaller than the frame's point count");
+    if (*n == 0) return NALO_OK;
+    MapWindowView V;
+    { int rc = ba_map_view(c, frame_id, &V); if (rc) return rc; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "map_dense_world_points");
+    MapDenseDev D{};
+    { int rc = map_dense_send(c, m, *f, D); if (rc) return rc; }
+    NALO_HIP(c, m.wxyz.reserve(3 * (size_t)*n)); NALO_HIP(c, m.wxyz_h.reserve(3 * (size_t)*n));
+    std::memcpy(D.ci, V.ci, sizeof(D.ci)); std::memcpy(D.m, camToWorld, sizeof(D.m)); D.wxyz = m.wxyz.p;
+    { int rc = map_dense_world_launch(c, D); if (rc) return rc; }
+    NALO_HIP(c, hipMemcpyAsync(m.wxyz_h.p, m.wxyz.p, 3 * (size_t)*n * 8, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    std::memcpy(xyz, m.wxyz_h.p, 3 * (size_t)*n * 8);
+    return NALO_OK;
+}
+
+int nalo_map_dense_cloud(nalo_ctx* c, nalo_map_dense_cloud_args* a) {
+    if (!c || !a) return fail(c, NALO_ERR_ARG, "nalo_map_dense_cloud: bad argument");
+    a->n = 0; a->n_needed = 0; a->records = 0; a->survivors = 0;
+    if (a->cap < 0 || a->n_draws < 0) return fail(c, NALO_ERR_ARG, "nalo_map_dense_cloud: bad argument");
+    DenseFrame* f = nullptr;
+    { int rc = map_dense_frame(c, "nalo_map_dense_cloud", a->frame_id, &f); if (rc) return rc; }
+    DenseArchive& m = *c->dmap;
+    const int records = (int)f->points;
+    a->n_needed = records; a->records = records;
+    if (a->cap < records || (a->draws && a->n_draws < records)) return fail(c, NALO_ERR_ARG, "nalo_map_dense_cloud: cap / n_draws below the frame's records (n_needed)");
+    if (records > 0 && (!a->xyz || !a->rgb)) return fail(c, NALO_ERR_ARG, "nalo_map_dense_cloud: xyz and rgb required");
+    if (records == 0) return NALO_OK;
+    MapWindowView V;
+    { int rc = ba_map_view(c, a->frame_id, &V); if (rc) return rc; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "map_dense_cloud");
+    MapDenseDev D{};
+    { int rc = map_dense_send(c, m, *f, D); if (rc) return rc; }
+    const size_t nv = (size_t)records;
+    NALO_HIP(c, m.cxyz.reserve(3 * nv)); NALO_HIP(c, m.crgb.reserve(3 * nv)); NALO_HIP(c, m.cxyz_h.reserve(3 * nv)); NALO_HIP(c, m.crgb_h.reserve(3 * nv)); NALO_HIP(c, m.cnt_h.reserve(1));
+    std::memcpy(D.ci, V.ci, sizeof(D.ci)); D.xyz = m.cxyz.p; D.rgb = m.crgb.p;
+    if (a->draws) {
+        NALO_HIP(c, m.draws_h.reserve(nv)); NALO_HIP(c, m.draws_d.reserve(nv));
+        std::memcpy(m.draws_h.p, a->draws, nv * 4);
+        NALO_HIP(c, hipMemcpyAsync(m.draws_d.p, m.draws_h.p, nv * 4, hipMemcpyHostToDevice, c->stream));
+        D.draws = m.draws_d.p;
+    }
+    { int rc = map_dense_cloud_launch(c, D); if (rc) return rc; }
+    // the vertex count is known only behind the scan: everything the call may have written comes up in the one wait
+    NALO_HIP(c, hipMemcpyAsync(m.cnt_h.p, D.cnt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.cxyz_h.p, m.cxyz.p, 3 * nv * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.crgb_h.p, m.crgb.p, 3 * nv, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const int ns = m.cnt_h.p[0];
+    if (ns < 0 || (size_t)ns > nv) return fail(c, NALO_ERR_HIP, "nalo_map_dense_cloud: the device counted more survivors than the frame has records");
+    a->n = ns; a->survivors = ns;
+    std::memcpy(a->xyz, m.cxyz_h.p, 3 * (size_t)ns * 4); std::memcpy(a->rgb, m.crgb_h.p, 3 * (size_t)ns);
     return NALO_OK;
 }
 

@@ -61,7 +61,7 @@ struct DenseParams {
 constexpr int kDenseChunk = 1024;    // pixels of the box per workgroup. Round 4: 2048 -> 1024 (twice the workgroups for the 256 CUs: 764 instead of 382 on the 460 x 1700 box of the bench)
 // e / rw and e % rw for 0 <= e < 2^24 without the ~40-instruction integer division: float quotient, one correction step either way
 struct DnDiv { int rw; float rcp; };
-__device__ __forceinline__ void dn_divmod(const DnDiv& d, int e, int& q, int& r) {
+__host__ __device__ __forceinline__ void dn_divmod(const DnDiv& d, int e, int& q, int& r) {
     if (d.rcp == 0.f) { q = e / d.rw; r = e - q * d.rw; return; }          // a box of >= 2^24 pixels: (float) e is no longer exact
     q = (int)((float)e * d.rcp); r = e - q * d.rw;
     if (r < 0) { --q; r += d.rw; } else if (r >= d.rw) { ++q; r -= d.rw; }
@@ -80,7 +80,7 @@ __device__ __forceinline__ void dn_world(const DenseParams& P, int i, int j, flo
 // i0 = ry0 - ry0 % 3, `pre` candidates of the first band lie above the box.
 struct DnMap {
     int rx0, rw, cj, j0, i0, B, pre, total; DnDiv dv;
-    __device__ __forceinline__ DnMap(int rx0_, int rx1, int ry0, int ry1, bool any) {
+    __host__ __device__ __forceinline__ DnMap(int rx0_, int rx1, int ry0, int ry1, bool any) {           // (host: the block-offset table of nalo_dense_update_map)
         rx0 = any ? rx0_ : 0; rw = any ? rx1 - rx0 : 1;
         j0 = rx0 + (3 - rx0 % 3) % 3;
         cj = any && j0 < rx1 ? (rx1 - 1 - j0) / 3 + 1 : 0;
@@ -92,7 +92,7 @@ struct DnMap {
         total = any ? full * B + (r >= 1 ? rw : 0) + (r >= 2 ? cj : 0) - pre : 0;
         dv = DnDiv{B, total + pre < (1 << 24) ? 1.0f / (float)B : 0.f};
     }
-    __device__ __forceinline__ void at(int e, int& i, int& j) const {         // candidate e (0 <= e < total) -> pixel (i, j)
+    __host__ __device__ __forceinline__ void at(int e, int& i, int& j) const {         // candidate e (0 <= e < total) -> pixel (i, j)
         int band, rem; dn_divmod(dv, e + pre, band, rem);
         i = i0 + 3 * band;
         if (rem < rw) j = rx0 + rem;
@@ -123,10 +123,40 @@ __device__ __forceinline__ void dn_keep(const DenseParams& P, const DnMap& M, in
         }
     }
 }
-__global__ __launch_bounds__(256) void dense_count_kernel(DenseParams P) {
+// the aggregate of chunk b of a box: {kept points, min x, min y, min z, max x of their world coordinates} -> agg[b]. Shared by dense_count_kernel
+// (nalo_dense_make_map) and dense_count_batch_kernel (nalo_dense_update_map). Every lane of the workgroup calls it; the count comes back on lane 0.
+__device__ __forceinline__ int dn_count_chunk(const DenseParams& P, const DnMap& M, int b) {
     constexpr int R = kDenseChunk / 256;
-    __shared__ int sr[4][4];
     __shared__ float red[4][5];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    bool keep[R]; float idp[R]; int pi[R], pj[R];
+    dn_keep<R>(P, M, b, tid, keep, idp, pi, pj);
+    int cnt = 0;
+    float mnx = FLT_MAX, mny = FLT_MAX, mnz = FLT_MAX, mxx = FLT_MIN;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if (!keep[r]) continue;
+        double m[3]; dn_world(P, pi[r], pj[r], idp[r], m);
+        const float fx = (float)m[0];
+        mnx = fminf(mnx, fx); mxx = fmaxf(mxx, fx); mny = fminf(mny, (float)m[1]); mnz = fminf(mnz, (float)m[2]);
+        ++cnt;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); mnx = fminf(mnx, __shfl_xor(mnx, o)); mny = fminf(mny, __shfl_xor(mny, o)); mnz = fminf(mnz, __shfl_xor(mnz, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o)); }
+    if (lane == 0) { red[wave][0] = __int_as_float(cnt); red[wave][1] = mnx; red[wave][2] = mny; red[wave][3] = mnz; red[wave][4] = mxx; }
+    __syncthreads();
+    int total = 0;
+    if (tid == 0) {
+        float* o = P.agg + (size_t)b * 8;
+        total = __float_as_int(red[0][0]) + __float_as_int(red[1][0]) + __float_as_int(red[2][0]) + __float_as_int(red[3][0]);
+        o[0] = __int_as_float(total);
+        o[1] = fminf(fminf(red[0][1], red[1][1]), fminf(red[2][1], red[3][1])); o[2] = fminf(fminf(red[0][2], red[1][2]), fminf(red[2][2], red[3][2]));
+        o[3] = fminf(fminf(red[0][3], red[1][3]), fminf(red[2][3], red[3][3])); o[4] = fmaxf(fmaxf(red[0][4], red[1][4]), fmaxf(red[2][4], red[3][4]));
+    }
+    return total;
+}
+__global__ __launch_bounds__(256) void dense_count_kernel(DenseParams P) {
+    __shared__ int sr[4][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     // ---- the box from the row table (every workgroup on its own: a few hundred entries from L2, all loads in flight; block 0 publishes it and re-arms `last`).
     // No "last workgroup folds it" scheme: an agent-scope fence per workgroup (__threadfence = L2 write-back) cost 20 us in the row kernel and 80 us here.
@@ -150,28 +180,7 @@ __global__ __launch_bounds__(256) void dense_count_kernel(DenseParams P) {
     const DnMap M(rx0, rx1, ry0, ry1, any);
     const int nb = (M.total + kDenseChunk - 1) / kDenseChunk;
     if (b >= nb) return;
-    bool keep[R]; float idp[R]; int pi[R], pj[R];
-    dn_keep<R>(P, M, b, tid, keep, idp, pi, pj);
-    int cnt = 0;
-    float mnx = FLT_MAX, mny = FLT_MAX, mnz = FLT_MAX, mxx = FLT_MIN;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!keep[r]) continue;
-        double m[3]; dn_world(P, pi[r], pj[r], idp[r], m);
-        const float fx = (float)m[0];
-        mnx = fminf(mnx, fx); mxx = fmaxf(mxx, fx); mny = fminf(mny, (float)m[1]); mnz = fminf(mnz, (float)m[2]);
-        ++cnt;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cnt += __shfl_xor(cnt, o); mnx = fminf(mnx, __shfl_xor(mnx, o)); mny = fminf(mny, __shfl_xor(mny, o)); mnz = fminf(mnz, __shfl_xor(mnz, o)); mxx = fmaxf(mxx, __shfl_xor(mxx, o)); }
-    if (lane == 0) { red[wave][0] = __int_as_float(cnt); red[wave][1] = mnx; red[wave][2] = mny; red[wave][3] = mnz; red[wave][4] = mxx; }
-    __syncthreads();
-    if (tid == 0) {
-        float* o = P.agg + (size_t)b * 8;
-        o[0] = __int_as_float(__float_as_int(red[0][0]) + __float_as_int(red[1][0]) + __float_as_int(red[2][0]) + __float_as_int(red[3][0]));
-        o[1] = fminf(fminf(red[0][1], red[1][1]), fminf(red[2][1], red[3][1])); o[2] = fminf(fminf(red[0][2], red[1][2]), fminf(red[2][2], red[3][2]));
-        o[3] = fminf(fminf(red[0][3], red[1][3]), fminf(red[2][3], red[3][3])); o[4] = fmaxf(fmaxf(red[0][4], red[1][4]), fmaxf(red[2][4], red[3][4]));
-    }
+    (void)dn_count_chunk(P, M, b);
 }
 // inclusive prefix minimum over the 64 lanes of a wave, in lane order, without LDS traffic: Hillis-Steele inside the rows of 16 lanes (DPP row_shr), then the row
 // tails handed on (row_bcast:15 into the rows 1 and 3, row_bcast:31 into the rows 2 and 3). Lanes without a source keep FLT_MAX, the identity. Round 4: the write
@@ -189,18 +198,40 @@ __device__ __forceinline__ float dn_wave_prefix_min(float v) {
     return v;
 }
 __device__ __forceinline__ float dn_lane63(float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); }
-__global__ __launch_bounds__(256) void dense_write_kernel(DenseParams P, int cap, int* __restrict__ ou, int* __restrict__ ov, float* __restrict__ oid, float* __restrict__ ocol,
-                                                          uint8_t* __restrict__ obgr) {
+// where a kept point goes. nalo_dense_make_map: five arrays the host copies up; nalo_dense_update_map: one 16-byte nalo_dense_point of the call's scratch
+// (u | v << 16, idepth, colour, b | g << 8 | r << 16: one dwordx4 store), `base` = the kept points of the clusters in front
+struct DnEmitArrays {
+    int cap; int* __restrict__ ou; int* __restrict__ ov; float* __restrict__ oid; float* __restrict__ ocol; uint8_t* __restrict__ obgr;
+    __device__ __forceinline__ void operator()(const DenseParams& P, int o, int i, int j, float idp) const {
+        if (o < cap) {
+            const int px = j + i * P.w;
+            ou[o] = j; ov[o] = i; oid[o] = idp; ocol[o] = P.I0[px];                             // = dI[px][0] (makeImages keeps level 0's planar image): 4 instead of 64 bytes of sector traffic per point
+            if (P.bgr) { obgr[3 * o] = P.bgr[3 * px]; obgr[3 * o + 1] = P.bgr[3 * px + 1]; obgr[3 * o + 2] = P.bgr[3 * px + 2]; }
+        }
+    }
+};
+struct DnEmitRecords {
+    uint4* __restrict__ out; long long base, cap;
+    __device__ __forceinline__ void operator()(const DenseParams& P, int o, int i, int j, float idp) const {
+        const long long q = base + o;
+        if (q >= cap) return;                                                                   // (the scratch holds every candidate of the scanned range: never)
+        const int px = j + i * P.w;
+        unsigned c3 = 0u;
+        if (P.bgr) c3 = (unsigned)P.bgr[3 * px] | ((unsigned)P.bgr[3 * px + 1] << 8) | ((unsigned)P.bgr[3 * px + 2] << 16);
+        out[q] = make_uint4((unsigned)j | ((unsigned)i << 16), __float_as_uint(idp), __float_as_uint(P.I0[px]), c3);
+    }
+};
+// chunk b of the nb chunks of a box: the exclusive prefix of the aggregates in front (P.agg: the box's own chunks), the points in raster order, the totals of the
+// serial loop (P.n_out, P.out6, P.last). Shared by dense_write_kernel (nalo_dense_make_map) and dense_write_batch_kernel (nalo_dense_update_map), so the two routes
+// run the same arithmetic; every lane of the workgroup calls it.
+template <class Emit>
+__device__ __forceinline__ void dn_write_chunk(const DenseParams& P, const DnMap& M, int b, int nb, const Emit& emit) {
     constexpr int R = kDenseChunk / 256;
     __shared__ int cnt[R][4];
     __shared__ float gmin[R][4][2];              // min of (float) y, (float) z per (round, wave) group of kept points
     __shared__ float red[4][5];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-    const int rx0 = P.rect[0], rx1 = P.rect[1], ry0 = P.rect[2], ry1 = P.rect[3];
-    const bool any = rx0 != INT_MAX && rx1 > rx0 && ry1 > ry0;
-    const DnMap M(rx0, rx1, ry0, ry1, any);
-    const int nb = (M.total + kDenseChunk - 1) / kDenseChunk;
-    if (b < nb) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    {
         // ---- exclusive prefix of the chunks in front: count, min x / y / z, max x (order-free folds; the in-order part happens inside the workgroup).
         // The first four strides are loaded together (a rolled loop waits for every load: three dependent L2 round trips for the last chunks of the bench's box)
         int ecnt = 0; float e1 = FLT_MAX, e2 = FLT_MAX, e3 = FLT_MAX, e4 = FLT_MIN;
@@ -254,12 +285,7 @@ __global__ __launch_bounds__(256) void dense_write_kernel(DenseParams P, int cap
             bool t1 = false, t2 = false;
             const int o = goff + rank[r];
             if (keep[r]) {
-                const int i = pi[r], j = pj[r];
-                if (o < cap) {
-                    const int px = j + i * P.w;
-                    ou[o] = j; ov[o] = i; oid[o] = idp[r]; ocol[o] = P.I0[px];                             // = dI[px][0] (makeImages keeps level 0's planar image): 4 instead of 64 bytes of sector traffic per point
-                    if (P.bgr) { obgr[3 * o] = P.bgr[3 * px]; obgr[3 * o + 1] = P.bgr[3 * px + 1]; obgr[3 * o + 2] = P.bgr[3 * px + 2]; }
-                }
+                emit(P, o, pi[r], pj[r], idp[r]);
                 const float ry_ = fminf(gy, py[r]), rz_ = fminf(gz, pz[r]);       // the running minima AFTER this point's own update
                 t1 = wy[r] > (double)ry_; t2 = wz[r] > (double)rz_;
             }
@@ -278,6 +304,257 @@ __global__ __launch_bounds__(256) void dense_write_kernel(DenseParams P, int cap
             if (q2) atomicMax(&P.last[1], q2);
         }
     }
+}
+__global__ __launch_bounds__(256) void dense_write_kernel(DenseParams P, int cap, int* __restrict__ ou, int* __restrict__ ov, float* __restrict__ oid, float* __restrict__ ocol,
+                                                          uint8_t* __restrict__ obgr) {
+    const int b = blockIdx.x;
+    const int rx0 = P.rect[0], rx1 = P.rect[1], ry0 = P.rect[2], ry1 = P.rect[3];
+    const bool any = rx0 != INT_MAX && rx1 > rx0 && ry1 > ry0;
+    const DnMap M(rx0, rx1, ry0, ry1, any);
+    const int nb = (M.total + kDenseChunk - 1) / kDenseChunk;
+    if (b < nb) dn_write_chunk(P, M, b, nb, DnEmitArrays{cap, ou, ov, oid, ocol, obgr});
+}
+
+// ------------------------------------------------------------------------------------------------ nalo_dense_update_map: every cluster of a frame in one batch
+// The loop of MapPoint.cpp:271-331 without a launch, a wait or a copied point per cluster:
+//   dense_boxes_prep_kernel   ONE workgroup: the fitted call's <= 2048 mask values sorted (rank by counting: they are distinct), the boxes seeded
+//   dense_boxes_kernel        ONE pass over the mask for all clusters: a workgroup takes eight rows, holds the sorted values and a box per cluster in LDS; only the
+//                             first and the last pixel of a run of equal values look their record up (binary search; -0 == +0, NaN equals nothing) and fold
+//                             into the LDS box (integer min / max), and the workgroup flushes the boxes it touched with global integer atomicMin / atomicMax:
+//                             order independent, every run gives the same bits
+//   (the fit's wait: records and boxes come up; the host sizes the grid: per cluster with a plane and a colour the chunks of its own box, DnMap on the host)
+//   dense_count_batch_kernel  a workgroup finds its cluster in the block-offset table, then dn_count_chunk on that cluster's box
+//   scan_ints_launch          the chunks' kept counts of ALL clusters: a cluster's points start where the clusters in front end (boxes overlap: sizing the scratch
+//                             by candidates per box would not be bounded by the image)
+//   dense_write_batch_kernel  dn_write_chunk inside the cluster's segment of the aggregates: prefix minima and "last qualifying point" never cross a cluster
+//   dense_decide_kernel       ONE workgroup: n, the accept bit of :403 and the exclusive prefix of the accepted run lengths
+//   dense_copy_kernel         the accepted runs from the scratch into the archive's chunks, one 16-byte load and store per point
+// No float atomic, no atomic append: order comes from the scans.
+// NOT done as first sketched: a uint16 cluster-index plane. dn_keep compares the float mask with the cluster's value exactly as nalo_dense_make_map does, so both
+// routes share it unchanged, and the plane's 2 bytes per pixel of writes are saved.
+static_assert(sizeof(nalo_dense_point) == 16, "one dwordx4 per dense map point");
+constexpr int kDnRowsPerBlock = 8;
+struct DenseBatchItem { float plane[4]; float pcolor; int rect[4]; int boff; int pad[2]; };      // one per cluster that runs makeMap's loop; boff: its first workgroup
+static_assert(sizeof(DenseBatchItem) == 48, "three 16-byte words");
+struct DenseBatch {
+    DenseParams P;                                // what every cluster shares (mask, image, calibration, camToWorld)
+    const DenseBatchItem* items; int A;
+    float* aggs; int* cnt;                        // [NB][8] chunk aggregates; [NB + 1] kept counts per chunk, then their exclusive scan
+    float* ext; unsigned long long* last;         // per item: {minx, maxx, miny, -, minz, -, n (int)} and the two packed "last qualifying point" words
+    uint4* pts; long long pts_cap;                // the call's scratch: every cluster's kept points, cluster after cluster
+    int* res;                                     // per item {n, accept, first point in pts, first point among the appended}; res[4 A] = appended in all
+};
+
+__global__ __launch_bounds__(1024) void dense_boxes_prep_kernel(const nalo_plane_cluster* __restrict__ rec, const int* __restrict__ n_clusters, float* __restrict__ svals,
+                                                                int* __restrict__ sidx, int* __restrict__ gbox, int* __restrict__ cdev) {
+    __shared__ float v[kDenseMaxClusters];
+    int C = n_clusters[0];
+    if (C < 0 || C > kDenseMaxClusters) C = 0;                                  // (more than 2048 clusters: the call is refused after its wait)
+    for (int k = threadIdx.x; k < C; k += 1024) v[k] = rec[k].mask_value;
+    __syncthreads();
+    for (int k = threadIdx.x; k < C; k += 1024) {
+        const float x = v[k];
+        int r = 0;
+        for (int j = 0; j < C; ++j) r += v[j] < x;
+        svals[r] = x; sidx[r] = k;
+        gbox[4 * k] = INT_MAX; gbox[4 * k + 1] = INT_MIN; gbox[4 * k + 2] = INT_MAX; gbox[4 * k + 3] = INT_MIN;
+    }
+    if (threadIdx.x == 0) cdev[0] = C;
+}
+
+__global__ __launch_bounds__(256) void dense_boxes_kernel(const float* __restrict__ mask, int w, int h, const int* __restrict__ cdev, const float* __restrict__ svals,
+                                                          const int* __restrict__ sidx, int* __restrict__ gbox) {
+    __shared__ float sv[kDenseMaxClusters];
+    __shared__ unsigned short si[kDenseMaxClusters];
+    __shared__ int box[kDenseMaxClusters][4];
+    const int C = cdev[0], tid = threadIdx.x;
+    if (C <= 0) return;
+    for (int k = tid; k < C; k += 256) { sv[k] = svals[k]; si[k] = (unsigned short)sidx[k]; box[k][0] = INT_MAX; box[k][1] = INT_MIN; box[k][2] = INT_MAX; box[k][3] = INT_MIN; }
+    __syncthreads();
+    const int y0 = 2 + blockIdx.x * kDnRowsPerBlock;
+    for (int y = y0; y < y0 + kDnRowsPerBlock && y < h - 2; ++y) {
+        const float* row = mask + (size_t)y * w;
+        for (int x = 2 + tid; x < w - 2; x += 256) {                            // x - 1 >= 1 and x + 1 <= w - 2: the neighbours are inside the row
+            const float m = row[x], ml = row[x - 1], mr = row[x + 1];
+            const bool first = x == 2 || !(ml == m), last = x == w - 3 || !(mr == m);
+            if (!first && !last) continue;                                      // the inside of a run: its ends carry the box
+            int lo = 0, hi = C;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (sv[mid] < m) lo = mid + 1; else hi = mid; }
+            if (lo >= C || !(sv[lo] == m)) continue;                             // a value no point lies under (or NaN)
+            const int k = si[lo];
+            if (first) { atomicMin(&box[k][0], x); atomicMin(&box[k][2], y); atomicMax(&box[k][3], y); }
+            if (last) atomicMax(&box[k][1], x);
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < C; k += 256) {
+        if (box[k][0] == INT_MAX) continue;
+        atomicMin(&gbox[4 * k], box[k][0]); atomicMax(&gbox[4 * k + 1], box[k][1]); atomicMin(&gbox[4 * k + 2], box[k][2]); atomicMax(&gbox[4 * k + 3], box[k][3]);
+    }
+}
+
+// the cluster of this workgroup (the largest a with boff <= blockIdx.x; every item has at least one workgroup) and the parameters of its box
+__device__ __forceinline__ DnMap dn_batch_setup(const DenseBatch& B, DenseParams& P, int& a, int& b, int& nb) {
+    int lo = 0, hi = B.A;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (B.items[mid].boff <= (int)blockIdx.x) lo = mid; else hi = mid; }
+    a = lo;
+    const DenseBatchItem it = B.items[a];
+    P = B.P;
+    P.p0 = it.plane[0]; P.p1 = it.plane[1]; P.p2 = it.plane[2]; P.p3 = it.plane[3]; P.pcolor = it.pcolor;
+    P.agg = B.aggs + (size_t)it.boff * 8; P.last = B.last + 2 * a; P.out6 = B.ext + 8 * a; P.n_out = reinterpret_cast<int*>(B.ext + 8 * a + 6);
+    b = (int)blockIdx.x - it.boff;
+    const DnMap M(it.rect[0], it.rect[1], it.rect[2], it.rect[3], true);
+    nb = (M.total + kDenseChunk - 1) / kDenseChunk;
+    return M;
+}
+__global__ __launch_bounds__(256) void dense_count_batch_kernel(DenseBatch B) {
+    DenseParams P; int a, b, nb;
+    const DnMap M = dn_batch_setup(B, P, a, b, nb);
+    if (b == 0 && threadIdx.x == 0) { P.last[0] = 0ull; P.last[1] = 0ull; P.n_out[0] = 0; }
+    const int n = b < nb ? dn_count_chunk(P, M, b) : 0;
+    if (threadIdx.x == 0) B.cnt[blockIdx.x] = n;
+}
+__global__ __launch_bounds__(256) void dense_write_batch_kernel(DenseBatch B) {
+    DenseParams P; int a, b, nb;
+    const DnMap M = dn_batch_setup(B, P, a, b, nb);
+    if (b < nb) dn_write_chunk(P, M, b, nb, DnEmitRecords{B.pts, (long long)B.cnt[B.items[a].boff], B.pts_cap});
+}
+__global__ __launch_bounds__(1024) void dense_decide_kernel(DenseBatch B) {
+    __shared__ int len[kDenseMaxClusters], part[1024];
+    const int t = threadIdx.x;
+    for (int a = t; a < kDenseMaxClusters; a += 1024) {
+        int n = 0, acc = 0;
+        if (a < B.A) {
+            const float* e = B.ext + 8 * a;
+            n = reinterpret_cast<const int*>(e)[6];
+            if (n > 0) {                                                        // :403 on the serial loop's extrema, as nalo_dense_make_map's host side decides it
+                float mx[2];
+                for (int k = 0; k < 2; ++k) { const unsigned long long q = B.last[2 * a + k]; mx[k] = (q >> 32) ? __uint_as_float((unsigned)q) : FLT_MIN; }
+                acc = (e[1] - e[0] < 30 && mx[0] - e[2] < 30 && mx[1] - e[4] < 30) ? 1 : 0;
+            }
+            B.res[4 * a] = n; B.res[4 * a + 1] = acc; B.res[4 * a + 2] = B.cnt[B.items[a].boff];
+        }
+        len[a] = acc ? n : 0;
+    }
+    __syncthreads();
+    const int s0 = len[2 * t], s1 = len[2 * t + 1];
+    part[t] = s0 + s1;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int x = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += x;
+        __syncthreads();
+    }
+    const int ex = part[t] - (s0 + s1);
+    if (2 * t < B.A) B.res[4 * (2 * t) + 3] = ex;
+    if (2 * t + 1 < B.A) B.res[4 * (2 * t + 1) + 3] = ex + s0;
+    if (t == 1023) B.res[4 * B.A] = part[1023];
+}
+__global__ __launch_bounds__(256) void dense_copy_kernel(DenseBatch B, int NB, nalo_dense_point* const* __restrict__ chunks, long long base, long long cap, int chunk) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= B.cnt[NB] || p >= B.pts_cap) return;
+    int lo = 0, hi = B.A;                                                       // the last item that starts at or before p: the one p belongs to (empty items own nothing)
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (B.res[4 * mid + 2] <= p) lo = mid; else hi = mid; }
+    const int a = lo, t = p - B.res[4 * a + 2];
+    if (!B.res[4 * a + 1] || t >= B.res[4 * a]) return;
+    const long long q = base + B.res[4 * a + 3] + t;
+    if (q >= cap) return;                                                       // (room for every candidate was reserved: never)
+    reinterpret_cast<uint4*>(chunks[q / chunk])[q % chunk] = B.pts[p];
+}
+
+long long dense_candidates_bound(int w, int h) {
+    if (w < 6 || h < 6) return 0;
+    return DnMap(2, w - 2, 2, h - 2, true).total;                                // the scanned range as one box: every pixel a cluster can keep
+}
+
+// the tables of a call, carved from c->dn_tab in 16-byte words
+namespace {
+constexpr size_t K_ = kDenseMaxClusters;
+constexpr size_t o_svals = 0, o_sidx = o_svals + K_ / 4, o_gbox = o_sidx + K_ / 4, o_items = o_gbox + K_, o_ext = o_items + 3 * K_, o_last = o_ext + 2 * K_,
+                 o_res = o_last + K_, o_cdev = o_res + K_ + 1, dn_tab_words = o_cdev + 1;
+}
+
+int dense_boxes_enqueue(nalo_ctx* c, const float* mask, const nalo_plane_cluster* rec, const int* n_clusters_dev, int cap_clusters) {
+    NALO_HIP(c, c->dn_tab.reserve(dn_tab_words));
+    NALO_HIP(c, c->dn_host.reserve(4 * K_ + 12 * K_ + 4 * K_ + 4));
+    uint4* T = c->dn_tab.p;
+    float* svals = (float*)(T + o_svals); int* sidx = (int*)(T + o_sidx); int* gbox = (int*)(T + o_gbox); int* cdev = (int*)(T + o_cdev);
+    ProfScope ps(c, "dense_boxes");
+    dense_boxes_prep_kernel<<<1, 1024, 0, c->stream>>>(rec, n_clusters_dev, svals, sidx, gbox, cdev);
+    const int rows = std::max(c->h - 4, 0);
+    if (rows > 0 && c->w > 4) dense_boxes_kernel<<<(rows + kDnRowsPerBlock - 1) / kDnRowsPerBlock, 256, 0, c->stream>>>(mask, c->w, c->h, cdev, svals, sidx, gbox);
+    NALO_HIP(c, hipGetLastError());
+    if (cap_clusters > 0) NALO_HIP(c, hipMemcpyAsync(c->dn_host.p, gbox, (size_t)std::min<int>(cap_clusters, (int)K_) * 16, hipMemcpyDeviceToHost, c->stream));
+    return NALO_OK;
+}
+
+int dense_update_finish(nalo_ctx* c, int slot, const nalo_plane_cluster* clusters, int C, const double camToWorld[12], const DenseArchiveView& V, long long frame_points,
+                        nalo_dense_run* runs, int* n_appended, int* n_runs) {
+    *n_appended = 0; *n_runs = 0;
+    const FrameSlot& s = c->slots[slot];
+    const int* boxes = c->dn_host.p;
+    DenseBatchItem* items = reinterpret_cast<DenseBatchItem*>(c->dn_host.p + 4 * K_);
+    int* resh = c->dn_host.p + 4 * K_ + 12 * K_;
+    std::vector<int> owner;                                                     // item -> cluster record
+    long long NB = 0, cand = 0;
+    for (int k = 0; k < C; ++k) {
+        nalo_dense_run& r = runs[k];
+        std::memset(&r, 0, sizeof(r)); r.first = -1;
+        const nalo_plane_cluster& cl = clusters[k];
+        if (!cl.fitted) continue;                                               // `continue` of :280-281: no box is scanned for it
+        std::memcpy(r.rect, boxes + 4 * k, 16);
+        if (cl.mask_value == 0.f) continue;                                     // `if(pcolor==0) return;` (:355-357)
+        const int rx0 = r.rect[0], rx1 = r.rect[1], ry0 = r.rect[2], ry1 = r.rect[3];
+        if (!(rx0 != INT_MAX && rx1 > rx0 && ry1 > ry0)) continue;              // the loops' exclusive upper bounds leave nothing
+        const DnMap M(rx0, rx1, ry0, ry1, true);
+        const int nb = (M.total + kDenseChunk - 1) / kDenseChunk;
+        if (nb == 0) continue;
+        DenseBatchItem& it = items[owner.size()];
+        std::memcpy(it.plane, cl.plane, 16); it.pcolor = cl.mask_value; std::memcpy(it.rect, r.rect, 16); it.boff = (int)NB; it.pad[0] = it.pad[1] = 0;
+        owner.push_back(k);
+        NB += nb; cand += M.total;
+        if (NB > INT_MAX / 16) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_dense_update_map: the clusters' boxes hold more than 2^37 candidates");
+    }
+    const int A = (int)owner.size();
+    if (A == 0) return NALO_OK;
+    HostTimer ht(c, "dense_update_map");
+    NALO_HIP(c, c->dn_blk.reserve((size_t)NB * 2 + (size_t)(NB + 1 + 3) / 4));  // aggregates (two 16-byte words per chunk) | counts
+    const long long bound = dense_candidates_bound(c->w, c->h);
+    NALO_HIP(c, c->dn_pts.reserve((size_t)std::max<long long>(bound, 1)));
+    uint4* T = c->dn_tab.p;
+    DenseBatch B;
+    B.P.mask = s.mask.p; B.P.I0 = s.I[0].p; B.P.bgr = s.bgr.p; B.P.w = c->w; B.P.h = c->h; B.P.rows = nullptr; B.P.rect = nullptr;
+    B.P.p0 = B.P.p1 = B.P.p2 = B.P.p3 = B.P.pcolor = 0.f;
+    B.P.fxi = 1.0f / c->fx[0]; B.P.fyi = 1.0f / c->fy[0]; B.P.cx = c->cx[0]; B.P.cy = c->cy[0];            // DenseMapping::makeK level 0, as nalo_dense_make_map
+    std::memcpy(B.P.c2w, camToWorld, sizeof(B.P.c2w));
+    B.P.agg = nullptr; B.P.last = nullptr; B.P.out6 = nullptr; B.P.n_out = nullptr;
+    B.items = reinterpret_cast<const DenseBatchItem*>(T + o_items); B.A = A;
+    B.aggs = reinterpret_cast<float*>(c->dn_blk.p); B.cnt = reinterpret_cast<int*>(c->dn_blk.p + (size_t)NB * 2);
+    B.ext = reinterpret_cast<float*>(T + o_ext); B.last = reinterpret_cast<unsigned long long*>(T + o_last);
+    B.pts = c->dn_pts.p; B.pts_cap = bound; B.res = reinterpret_cast<int*>(T + o_res);
+    NALO_HIP(c, hipMemcpyAsync(T + o_items, items, (size_t)A * sizeof(DenseBatchItem), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, "dense_update_map");
+        dense_count_batch_kernel<<<(int)NB, 256, 0, c->stream>>>(B);
+        { const int rc = scan_ints_launch(c, B.cnt, (int)NB); if (rc) return rc; }
+        dense_write_batch_kernel<<<(int)NB, 256, 0, c->stream>>>(B);
+        dense_decide_kernel<<<1, 1024, 0, c->stream>>>(B);
+        const long long most = std::min(cand, bound);
+        dense_copy_kernel<<<(int)std::max<long long>((most + 255) / 256, 1), 256, 0, c->stream>>>(B, (int)NB, V.chunks, V.base, V.cap, V.chunk);
+        NALO_HIP(c, hipGetLastError());
+    }
+    NALO_HIP(c, hipMemcpyAsync(resh, B.res, ((size_t)4 * A + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                               // the call's second and last wait
+    const int total = resh[4 * A];
+    if (total < 0 || total > bound) return fail(c, NALO_ERR_HIP, "nalo_dense_update_map: the device appended more points than the image has candidates");
+    for (int a = 0; a < A; ++a) {
+        nalo_dense_run& r = runs[owner[a]];
+        r.n = resh[4 * a]; r.accept = resh[4 * a + 1];
+        if (r.accept && r.n > 0) { r.first = frame_points + resh[4 * a + 3]; ++*n_runs; }
+    }
+    *n_appended = total;
+    return NALO_OK;
 }
 
 }  // namespace nalo

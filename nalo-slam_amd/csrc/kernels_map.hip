@@ -255,4 +255,69 @@ int map_cloud_launch(nalo_ctx* c, const MapCloudDev& C) {
     return NALO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ (D) the dense map's two consumers (nalo_map_dense_*)
+// point i of the frame's dense list: its archive pieces in append order (a handful of segments, uniform loads)
+__device__ __forceinline__ bool map_dense_fetch(const MapDenseDev& D, int i, uint4& r) {
+    if (i >= D.total) return false;
+    int s = 0;
+    while (s + 1 < D.nseg && i >= D.segs[s + 1].start) ++s;
+    const MapSeg sg = D.segs[s];
+    const int t = i - sg.start;
+    if (t < 0 || t >= sg.n) return false;
+    r = reinterpret_cast<const uint4*>(sg.p)[t];                                 // {u | v << 16, idepth, colour, b | g << 8 | r << 16}
+    return true;
+}
+// SampleOutputWrapper.h:152-176: one lane per point, no compaction (every point is written)
+__global__ __launch_bounds__(256) void map_dense_world_kernel(MapDenseDev D) {
+    uint4 r;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (!map_dense_fetch(D, i, r)) return;
+    double wp[3];
+    map_world_point((float)(r.x & 0xFFFFu), (float)(r.x >> 16), __uint_as_float(r.y), D.ci, D.m, wp);
+    double* o = D.wxyz + 3 * (size_t)i;
+    o[0] = wp[0]; o[1] = wp[1]; o[2] = wp[2];
+}
+int map_dense_world_launch(nalo_ctx* c, const MapDenseDev& D) {
+    if (D.nb <= 0) return NALO_OK;
+    ProfScope ps(c, "map_dense_world_points");
+    map_dense_world_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+// KeyFrameDisplay::refreshPC() :225-248: `if(idpeth < 0) continue;` - a NaN stays
+__global__ __launch_bounds__(256) void map_dense_cloud_count_kernel(MapDenseDev D) {
+    __shared__ int wsum[4];
+    uint4 r = make_uint4(0, 0, 0, 0);
+    const bool in = map_dense_fetch(D, blockIdx.x * 256 + threadIdx.x, r);
+    const bool keep = in && !(__uint_as_float(r.y) < 0);
+    const int k = map_block_rank(keep, wsum);
+    if (threadIdx.x == 255) D.cnt[blockIdx.x] = k + (keep ? 1 : 0);
+}
+__global__ __launch_bounds__(256) void map_dense_cloud_write_kernel(MapDenseDev D) {
+    __shared__ int wsum[4];
+    uint4 r = make_uint4(0, 0, 0, 0);
+    const bool in = map_dense_fetch(D, blockIdx.x * 256 + threadIdx.x, r);
+    const float idepth = __uint_as_float(r.y);
+    const bool keep = in && !(idepth < 0);
+    const int j = D.cnt[blockIdx.x] + map_block_rank(keep, wsum);                // the output vertex = the draw index
+    if (!keep || j >= D.total) return;
+    const float fxi = D.ci[0], fyi = D.ci[1], cxi = D.ci[2], cyi = D.ci[3];
+    const float depth = 1.0f / idepth;
+    const float u = (float)(r.x & 0xFFFFu), v = (float)(r.x >> 16);
+    const float jit = D.draws ? ((float)D.draws[j] / (float)2147483647 - 0.5f) : 0.f;   // as map_cloud_write_kernel: without draws the bracket is exactly 1
+    float* o = D.xyz + 3 * (size_t)j;
+    o[0] = (u * fxi + cxi) * depth; o[1] = (v * fyi + cyi) * depth; o[2] = depth * (1 + 2 * fxi * jit);
+    uint8_t* q = D.rgb + 3 * (size_t)j;
+    q[0] = (uint8_t)(r.w >> 16); q[1] = (uint8_t)(r.w >> 8); q[2] = (uint8_t)r.w;  // {bgr[2], bgr[1], bgr[0]}
+}
+int map_dense_cloud_launch(nalo_ctx* c, const MapDenseDev& D) {
+    if (D.nb <= 0) return NALO_OK;
+    ProfScope ps(c, "map_dense_cloud");
+    map_dense_cloud_count_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+    int rc = scan_ints_launch(c, D.cnt, D.nb); if (rc) return rc;
+    map_dense_cloud_write_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
 }  // namespace nalo

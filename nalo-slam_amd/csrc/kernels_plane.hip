@@ -25,6 +25,7 @@ namespace nalo {
 
 constexpr unsigned kNoKey = 0xFFFFFFFFu;          // a NaN pattern: no cluster has it
 constexpr int kPlaneMaxClusters = 2048;           // plane_order resolves the cluster order in LDS
+static_assert(kPlaneMaxClusters == kDenseMaxClusters, "nalo_dense_update_map's tables hold one entry per cluster record");
 constexpr int kPlaneTile = 1024;                  // cloud points a scoring workgroup stages (12 KB)
 constexpr int kPlaneMaxSamples = 4096;
 enum { HDR_RAW = 0, HDR_ERR = 1, HDR_MEMBERS = 2, HDR_TILES = 3, HDR_C = 4, HDR_PCN = 5, HDR_NIN = 6, HDR_WORDS = 16 };
@@ -354,9 +355,10 @@ __global__ __launch_bounds__(1024) void plane_dense_gather_kernel(const int* __r
 }
 
 // The whole chain for n input points (u, v, idp device arrays; in_gather: the dense variant's gather is launched first into the call's own input arrays).
+// dense_boxes: nalo_dense_update_map's pass over the mask is enqueued behind the fit, so that its boxes come up in the fit's wait.
 struct PlaneGather { const int* kmap; int seg; const float4* geo; const uint8_t* flags; const float* imm; int N, host; };
 static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* v, const float* idp, const PlaneGather* g, int n, const float* mask,
-                     const nalo_plane_fit_args* a, bool append, int cap, nalo_plane_cluster* out, int* n_clusters) {
+                     const nalo_plane_fit_args* a, bool append, int cap, nalo_plane_cluster* out, int* n_clusters, bool dense_boxes = false) {
     const std::string W(who);
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "plane_fit");
@@ -404,6 +406,7 @@ static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* 
             const int rc = trk_append_clusters_launch(c, s.mask.p, s.dI[0].p, P.rec, P.hdr, capr); if (rc) return rc;
         }
     }
+    if (dense_boxes) { const int rc = dense_boxes_enqueue(c, mask, P.rec, P.hdr + HDR_C, capr); if (rc) return rc; }
     int* h_hdr = hst + 3 * (size_t)S;
     NALO_HIP(c, hipMemcpyAsync(h_hdr, P.hdr, HDR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
     if (capr > 0) NALO_HIP(c, hipMemcpyAsync(h_hdr + HDR_WORDS, P.rec, (size_t)capr * sizeof(nalo_plane_cluster), hipMemcpyDeviceToHost, c->stream));
@@ -431,6 +434,22 @@ static int plane_check_args(nalo_ctx* c, const char* who, const nalo_plane_fit_a
     return NALO_OK;
 }
 
+// what updateMap collects for window frame host_frame, shared by nalo_dense_fit_planes and nalo_dense_update_map: the refusals, the gather's sources, the count
+static int dense_fit_inputs(nalo_ctx* c, const char* who, int host_frame, PlaneGather* g, int* slot, int* n) {
+    int n_valid = 0;
+    int rc = ba_plane_inputs(c, host_frame, slot, &g->kmap, &g->seg, &n_valid, &g->geo, &g->flags); if (rc) return rc;
+    const FrameSlot& s = c->slots[*slot];
+    if (!s.valid || !s.mask.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the frame's slot has no mask (nalo_frame_upload with mask)");
+    g->imm = c->imm_res.p; g->N = c->imm_res_n; g->host = host_frame;
+    int n_imm = 0;
+    if (g->N > 0) {
+        if (c->imm_host_h.size() != (size_t)g->N) return fail(c, NALO_ERR_STATE, std::string(who) + ": the resident set has no host copy");
+        for (int i = 0; i < g->N; ++i) n_imm += c->imm_host_h[i] == host_frame;
+    }
+    *n = n_valid + n_imm;
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -452,17 +471,32 @@ int nalo_dense_fit_planes(nalo_ctx* c, int host_frame, const nalo_plane_fit_args
     int rc = plane_check_args(c, "nalo_dense_fit_planes", a, cap, out, n_clusters); if (rc) return rc;
     *n_clusters = 0;
     PlaneGather g = {};
-    int slot = -1, n_valid = 0;
-    rc = ba_plane_inputs(c, host_frame, &slot, &g.kmap, &g.seg, &n_valid, &g.geo, &g.flags); if (rc) return rc;
-    const FrameSlot& s = c->slots[slot];
-    if (!s.valid || !s.mask.p) return fail(c, NALO_ERR_STATE, "nalo_dense_fit_planes: the frame's slot has no mask (nalo_frame_upload with mask)");
-    g.imm = c->imm_res.p; g.N = c->imm_res_n; g.host = host_frame;
-    int n_imm = 0;
-    if (g.N > 0) {
-        if (c->imm_host_h.size() != (size_t)g.N) return fail(c, NALO_ERR_STATE, "nalo_dense_fit_planes: the resident set has no host copy");
-        for (int i = 0; i < g.N; ++i) n_imm += c->imm_host_h[i] == host_frame;
-    }
-    return plane_run(c, "nalo_dense_fit_planes", nullptr, nullptr, nullptr, &g, n_valid + n_imm, s.mask.p, a, false, cap, out, n_clusters);
+    int slot = -1, n = 0;
+    rc = dense_fit_inputs(c, "nalo_dense_fit_planes", host_frame, &g, &slot, &n); if (rc) return rc;
+    return plane_run(c, "nalo_dense_fit_planes", nullptr, nullptr, nullptr, &g, n, c->slots[slot].mask.p, a, false, cap, out, n_clusters);
+}
+
+int nalo_dense_update_map(nalo_ctx* c, int host_frame, const nalo_plane_fit_args* a, const double camToWorld[12], int cap, nalo_plane_cluster* clusters,
+                          nalo_dense_run* runs, int* n_clusters, int* n_appended) {
+    if (!c) return NALO_ERR_ARG;
+    int rc = plane_check_args(c, "nalo_dense_update_map", a, cap, clusters, n_clusters); if (rc) return rc;
+    *n_clusters = 0;
+    if (!camToWorld || !n_appended || !runs) return fail(c, NALO_ERR_ARG, "nalo_dense_update_map: camToWorld, runs and n_appended are required");
+    *n_appended = 0;
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, "nalo_dense_update_map: the dense archive is not enabled (nalo_map_dense_enable)");
+    PlaneGather g = {};
+    int slot = -1, n = 0;
+    rc = dense_fit_inputs(c, "nalo_dense_update_map", host_frame, &g, &slot, &n); if (rc) return rc;
+    // room for every point the call can keep, before anything is touched
+    DenseArchiveView V;
+    rc = map_dense_reserve(c, dense_candidates_bound(c->w, c->h), &V); if (rc) return rc;
+    rc = plane_run(c, "nalo_dense_update_map", nullptr, nullptr, nullptr, &g, n, c->slots[slot].mask.p, a, false, cap, clusters, n_clusters, true); if (rc) return rc;
+    const int frame_id = ba_frame_id(c, host_frame);
+    int n_runs = 0;
+    rc = dense_update_finish(c, slot, clusters, *n_clusters, camToWorld, V, map_dense_frame_points(c, frame_id), runs, n_appended, &n_runs);
+    if (rc) { *n_appended = 0; return rc; }
+    map_dense_commit(c, frame_id, *n_appended, n_runs);
+    return NALO_OK;
 }
 
 int nalo_plane_fit_members(nalo_ctx* c, int cap, int* cluster_of, int* order) {

@@ -103,6 +103,7 @@ struct BAWindow;
 struct PixSel;
 struct Initializer;
 struct MapArchive;
+struct DenseArchive;
 
 }  // namespace nalo
 
@@ -144,6 +145,9 @@ struct nalo_ctx {
     bool lm_host_only = false;                 // latched when a trk_lm launch lost a workgroup (CUs taken by another context): the host-driven LM loop from then on
     nalo::DevBuf<int> scan_tmp;              // compaction counts
     nalo::DevBuf<unsigned long long> dense_lb;   // nalo_dense_make_map scratch: row table | chunk aggregates | last[2] | ticket
+    // nalo_dense_update_map (kernels_dense.hip): the per-cluster tables, the chunk aggregates and counts, the call's point scratch (one record per candidate of the
+    // scanned range, sized once) and the pinned block the boxes and results come up and the batch table goes down through
+    nalo::DevBuf<uint4> dn_tab, dn_blk, dn_pts; nalo::HostBuf<int> dn_host;
     nalo::DevBuf<int> trk_cnt;               // hits per level-0 pixel of the reference scatter (ordered redo of pixels with >= 3 hits)
     nalo::DevBuf<float> upload_tmp;
     nalo::HostBuf<float> pinned_f;           // nalo_trk_set_ref's staging (upload4)
@@ -173,6 +177,7 @@ struct nalo_ctx {
     bool xchg_failed = false;                // a cross-rank sum failed (host_rccl.hip): the ranks' systems may differ, every later BA call of this context fails
     nalo::Initializer* init = nullptr;       // two-frame initialiser state (host_init.hip)
     nalo::MapArchive* map = nullptr;         // the archive of removed points and the clouds made from it (host_map.hip); NULL until nalo_map_enable
+    nalo::DenseArchive* dmap = nullptr;      // the dense map: FrameHessian::mapPoints on the device (host_map.hip); NULL until nalo_map_dense_enable
     nalo_settings set = {1, nalo::kAffineOptModeA, nalo::kAffineOptModeB, 1};   // util/settings.cpp:71,128-129,74
 
     // ---- host wall-clock accounting (NALO_HOST_TIMING=1, read by nalo_create, prints it at nalo_destroy)
@@ -336,6 +341,28 @@ void map_destroy(nalo_ctx* c);
 // host_ba.hip: the window as nalo_map_frame_cloud reads it. widx = -1: frame_id is not in the window; pts_ok: the point arrays stand (kmap: the frame's seg entries, n_valid of them valid). ci: {fxi, fyi, cxi, cyi} of the CalibHessian (value_scaledi)
 struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4]; bool sharded; };
 int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
+// ---- the dense map (nalo_dense_update_map, nalo_map_dense_*)
+constexpr int kDenseMaxClusters = 2048;      // = the most clusters a fit returns (kernels_plane.hip)
+// host_map.hip: the dense archive as the copy pass writes it (the point at position q lives at chunks[q / chunk][q % chunk]; cap: positions that exist)
+struct DenseArchiveView { nalo_dense_point* const* chunks; long long base, cap; int chunk; };
+bool map_dense_on(const nalo_ctx* c);
+int map_dense_reserve(nalo_ctx* c, long long ub, DenseArchiveView* V);          // room for ub more points; a refusal leaves the archive as it was
+long long map_dense_frame_points(nalo_ctx* c, int frame_id);                   // the frame's points so far (0: none, or never seen)
+void map_dense_commit(nalo_ctx* c, int frame_id, int n_points, int n_runs);     // after the call's last wait: the host index (the frame counts as seen from here on)
+void map_dense_destroy(nalo_ctx* c);
+// kernels_map.hip: the two products of a frame's dense points. segs: the frame's archive pieces in append order (MapSeg::p: nalo_dense_point, kind unused)
+struct MapDenseDev { const MapSeg* segs; int nseg, total, nb; int* cnt; float ci[4]; double m[12]; const int* draws; double* wxyz; float* xyz; uint8_t* rgb; };
+int map_dense_world_launch(nalo_ctx* c, const MapDenseDev& D);
+int map_dense_cloud_launch(nalo_ctx* c, const MapDenseDev& D);                  // cnt[nb]: the survivors in all, behind the scan
+// kernels_dense.hip: nalo_dense_update_map's device half. boxes_enqueue runs behind the fit's kernels and before its wait (rec / n_clusters_dev: the fit's records and
+// their count on the device): every cluster's mask box in one pass, on its way up with the records. finish: the batched makeMap of every fitted cluster with a
+// colour, the accept tests and the copy of the accepted runs into the archive; the call's second wait; runs[C] filled in
+long long dense_candidates_bound(int w, int h);                                // pixels of [2,w-2)x[2,h-2) with i%3==0 || j%3==0: the most points one call can append
+int dense_boxes_enqueue(nalo_ctx* c, const float* mask, const nalo_plane_cluster* rec, const int* n_clusters_dev, int cap_clusters);
+int dense_update_finish(nalo_ctx* c, int slot, const nalo_plane_cluster* clusters, int C, const double camToWorld[12], const DenseArchiveView& V, long long frame_points,
+                        nalo_dense_run* runs, int* n_appended, int* n_runs);
+// host_ba.hip: frame_id (nalo_frame_state) of window frame host_frame, which ba_plane_inputs has validated
+int ba_frame_id(nalo_ctx* c, int host_frame);
 // host_ba.hip
 void ba_destroy(nalo_ctx* c);
 // host_rccl.hip
