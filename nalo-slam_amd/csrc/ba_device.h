@@ -150,19 +150,58 @@ struct StitchLayout {
 static_assert(StitchLayout(21, 2).npub - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 && StitchLayout(21, 2).th - StitchLayout(21, 2).misc == 2 * 2 * 2 + 5 - 2,
               "StitchLayout and ba_reduce_kernel's tail disagree");
 
-// Operands of ba_carry_kernel (kernels_ba_carry.hip): the old window's arrays (o_*), the second set they are gathered into, what is zeroed beside them, and the
-// pending activation's rows. ng / last (and o_ng / o_last) are NULL for a window without a history; imm / a_* are read only where src names a selected point.
+// ---- A window issued on the device (nalo_ba_carry_window, nalo_ba_window_from_initializer). What a fresh slot holds is defined HERE, once: IssuePoint's
+// defaults are the padding slot, issue_store_point / issue_store_row write a slot's point arrays and rows with every zero beside them. nalo_ba_set_points
+// (host_ba.hip), which fills from host arrays, takes the padding from the same struct.
+// PointHessian::lastResiduals[2] in one word (BADev::pt_last): byte 0 / 1 = window index of [0 / 1].first (int8, -1 = null), byte 2 / 3 = [0 / 1].second
+__host__ __device__ constexpr uint32_t pack_last(int t0, int t1, uint32_t s0, uint32_t s1) {
+    return (uint32_t)(uint8_t)(int8_t)t0 | ((uint32_t)(uint8_t)(int8_t)t1 << 8) | (s0 << 16) | (s1 << 24);
+}
+constexpr uint32_t kLastNone = pack_last(-1, -1, 1u, 1u);   // {null, null} / {OOB, OOB}: a slot without a point, or a point no residual was made for
+// The arrays an issue writes: the first set of point / slot buffers as build_point_layout sized them. ng / last are NULL for a window without a history.
+struct IssueDev {
+    int W, Ppad;
+    float4 *geo, *col0, *col1, *w0, *w1; float* prior; uint8_t* flags; int* ng; uint32_t* last;
+    float4 *acc, *hcd; float *step, *backup, *relbs, *relbs2; uint8_t* ngood;
+    uint8_t* state; float2* energy; float4 *jp0, *jp1, *cpt;          // [W][Ppad]
+};
+struct IssuePoint {                             // the values of one point; the defaults are the filler of a padding slot
+    float4 geo = make_float4(8.f, 8.f, 1.f, 1.f), c0 = make_float4(0.f, 0.f, 0.f, 0.f), c1 = c0, w0 = c0, w1 = c0;
+    float prior = 0.f; uint8_t flags = 0; int ng = 0; uint32_t last = kLastNone;
+};
+// One lane writes one slot with plain vector stores; there is no floating-point arithmetic here, so a file built with FMA contraction and one built without mean the same.
+__device__ __forceinline__ void issue_store_point(const IssueDev& I, int d, const IssuePoint& p) {
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    I.geo[d] = p.geo; I.col0[d] = p.c0; I.col1[d] = p.c1; I.w0[d] = p.w0; I.w1[d] = p.w1;
+    I.prior[d] = p.prior; I.flags[d] = p.flags;
+    if (I.ng) { I.ng[d] = p.ng; I.last[d] = p.last; }
+    I.acc[d] = z4; I.hcd[d] = z4; I.step[d] = 0.f; I.backup[d] = 0.f; I.relbs[d] = 0.f; I.relbs2[d] = 0.f; I.ngood[d] = 0;
+}
+__device__ __forceinline__ void issue_store_row(const IssueDev& I, int t, int d, uint8_t st) {   // state IN, energies zero, resetOOB: what nalo_ba_set_residuals leaves
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const size_t si = (size_t)t * (size_t)I.Ppad + d;
+    I.state[si] = st; I.energy[si] = make_float2(0.f, 0.f); I.jp0[si] = z4; I.jp1[si] = z4; I.cpt[si] = z4;
+}
+
+// Operands of ba_carry_kernel (kernels_ba_carry.hip): the old window's arrays (o_*), the second set they are gathered into with what is zeroed beside them (I),
+// and the pending activation's rows. o_ng / o_last are read only where I.ng is set; imm / a_* are read only where src names a selected point.
 struct CarryDev {
-    const int* src;                             // [Ppad_new]: old slot, -1 padding, -(k + 2) the k-th selected point
-    int trow[16];                               // [W_new]: old residual row, -1 the entering frame
-    int W_new, Ppad_new, Ppad_old, enter;
+    const int* src;                             // [I.Ppad]: old slot, -1 padding, -(k + 2) the k-th selected point
+    int trow[16];                               // [I.W]: old residual row, -1 the entering frame
+    int Ppad_old, enter;
     const float4 *o_geo, *o_col0, *o_col1, *o_w0, *o_w1; const float* o_prior; const uint8_t *o_flags, *o_state; const int* o_ng; const uint32_t* o_last;
-    float4 *geo, *col0, *col1, *w0, *w1; float* prior; uint8_t *flags, *state; int* ng; uint32_t* last;
-    float4 *acc, *hcd; float *step, *backup, *relbs, *relbs2; uint8_t* ngood; float2* energy; float4 *jp0, *jp1, *cpt;
+    IssueDev I;
     const float* imm; int immN;                 // the resident immature block ([30][immN], host_api.hip) and its size
-    const int* a_sel; const float* a_idepth; const uint8_t* a_in;   // selected indices, idepth_out, res_in [k][W_new] of the pending activation
+    const int* a_sel; const float* a_idepth; const uint8_t* a_in;   // selected indices, idepth_out, res_in [k][I.W] of the pending activation
 };
 void ba_launch_carry(hipStream_t s, const CarryDev& A, int nblocks);
+// Operands of iw_gather_kernel (kernels_init_window.hip): the kept level-0 points of the initialiser gathered into a two-frame window's arrays (I, with a history).
+// src[d]: level-0 index or -1 for padding. Every pointer is device memory.
+struct InitWindowDev {
+    const int* src; int n, w, h;
+    const float4* dI; const float *u, *v, *iR; float rescale, prior;
+    IssueDev I;
+};
 
 // Launchers of kernels_ba.hip and kernels_ba_lin.hip
 void ba_launch_sc(hipStream_t s, const BADev& B, int T, int shift, float priorScaleMarg, int margOnly);

@@ -103,7 +103,8 @@ struct BAWindow {
     std::vector<int> row_of;                                        // the device residual row (= device host index) of every frame of `frames`: identity until a frame leaves
     bool carry_ok = false;                                          // points and residuals are unset ONLY because nalo_ba_marginalize_frame was called: the device arrays still stand
     unsigned frames_epoch = 0;                                      // counts the changes of the frame list (a pending activation result belongs to one value)
-    HostBuf<int> carry_host; DevBuf<int> carry_src; Event ev_carry; // [trow 16 | src Ppad | blk_host | host_blk | sc_grp | blk_order], and the device copy of [trow | src]
+    // a device issue's tables (stage_issue_tables): pinned [src Ppad | blk_host | host_blk | sc_grp | blk_order], src on the device, the event behind the copies
+    HostBuf<int> carry_host; DevBuf<int> carry_src; Event ev_carry;
     std::vector<int> carry_map_h; int carry_stats[4] = {}; bool carried = false;   // nalo_ba_carry_map / nalo_ba_carry_last of the last carry
     // nalo_ba_window_from_initializer: [the constructor's verdict per level-0 point | sumID] on the device and in pinned memory, and what the last call reports
     DevBuf<uint8_t> iw_scr; HostBuf<uint8_t> iw_host;
@@ -1146,14 +1147,15 @@ static int build_point_layout(nalo_ctx* c, int P, const int* host, const unsigne
     }
     return NALO_OK;
 }
-// the kernels' view of the first set, and what a new point list resets on the host
-static void bind_points(BAWindow& w) {
+// the kernels' view of the first set (hist: with the history arrays), and what a new point list resets on the host
+static void bind_points(BAWindow& w, bool hist) {
     BADev& D = w.dev;
     D.P = w.P; D.Ppad = w.Ppad; D.nblocks = w.nblocks; D.blk_host = w.blk_host.p; D.host_blk = w.host_blk.p;
     D.pt_geo = w.pt_geo.p; D.pt_col0 = w.pt_col0.p; D.pt_col1 = w.pt_col1.p; D.pt_w0 = w.pt_w0.p; D.pt_w1 = w.pt_w1.p; D.pt_prior = w.pt_prior.p;
     D.pt_flags = w.pt_flags.p; D.pt_acc = w.pt_acc.p; D.pt_hcd = w.pt_hcd.p; D.pt_ngood = w.pt_ngood.p; D.pt_step = w.pt_step.p; D.pt_backup = w.pt_backup.p; D.pt_relbs = w.pt_relbs.p; D.pt_relbs_next = w.pt_relbs2.p;
     D.rs_state = w.rs_state.p; D.rs_energy = w.rs_energy.p; D.rs_jp0 = w.rs_jp0.p; D.rs_jp1 = w.rs_jp1.p; D.rs_cpt = w.rs_cpt.p; D.rs_pp0 = w.rs_pp0.p; D.rs_pp1 = w.rs_pp1.p; D.en_new = w.en_new.p;
     D.top_partial = w.top_partial.p; D.sc_partial = w.sc_partial.p;
+    w.hist_set = hist; D.pt_numgood = hist ? w.pt_numgood.p : nullptr; D.pt_last = hist ? w.pt_last.p : nullptr;
     w.have_lin = w.have_sc = false; w.lin_fixed = false; w.ref_kmap_ok = false; w.flagged = false; w.relbs_keep_ok = false;
     w.row_of.resize(w.W); for (int i = 0; i < w.W; ++i) w.row_of[i] = i;
     w.carry_ok = false;
@@ -1173,8 +1175,9 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
     { int rc = build_point_layout(c, P, host, key.data(), L); if (rc) return rc; }
     c->act_pend_n = -1;                                               // a pending activation result was made against the points that just went
     const size_t N = w.Ppad;
-    std::vector<float4> geo(N, make_float4(8.f, 8.f, 1.f, 1.f)), c0(N, make_float4(0, 0, 0, 0)), c1(N, make_float4(0, 0, 0, 0)), w0(N, make_float4(0, 0, 0, 0)), w1(N, make_float4(0, 0, 0, 0));
-    std::vector<float> prior(N, 0.f);
+    const IssuePoint pad;                                             // the filler of a padding slot (ba_device.h)
+    std::vector<float4> geo(N, pad.geo), c0(N, pad.c0), c1(N, pad.c1), w0(N, pad.w0), w1(N, pad.w1);
+    std::vector<float> prior(N, pad.prior);
     w.flags_h.assign(N, 0);
     for (size_t d = 0; d < N; ++d) {
         const int p = w.d2p[d];
@@ -1199,9 +1202,8 @@ int nalo_ba_set_points(nalo_ctx* c, int P, const int* host, const float* u, cons
     NALO_HIP(c, hipMemset(w.pt_backup.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_relbs2.p, 0, N * 4)); NALO_HIP(c, hipMemset(w.pt_ngood.p, 0, N));
     NALO_HIP(c, hipMemset(w.rs_state.p, 0, NS)); NALO_HIP(c, hipMemset(w.rs_energy.p, 0, NS * 8)); NALO_HIP(c, hipMemset(w.rs_jp0.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.rs_jp1.p, 0, NS * 16));
     NALO_HIP(c, hipMemset(w.rs_cpt.p, 0, NS * 16)); NALO_HIP(c, hipMemset(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8));
-    bind_points(w);
+    bind_points(w, false);                                            // a history belongs to the points it was set for
     w.points_set = true; w.res_set = false;
-    w.hist_set = false; w.dev.pt_numgood = nullptr; w.dev.pt_last = nullptr;           // a history belongs to the points it was set for
     return NALO_OK;
 }
 
@@ -1515,15 +1517,12 @@ int nalo_ba_marginalize_points(nalo_ctx* c, const uint8_t* flags, double* M, dou
 
 // ---- the point lifecycle on the device: PointHessian::numGoodResiduals / lastResiduals resident beside the points, flagPointsForRemoval as one kernel, and
 // marginalizePointsF + dropPointsF from the decisions it left (FullSystem::makeKeyFrame, FullSystem.cpp:1397, 1446-1453)
-static uint32_t pack_last(int t0, int t1, int s0, int s1) {
-    return (uint32_t)(uint8_t)(int8_t)t0 | ((uint32_t)(uint8_t)(int8_t)t1 << 8) | ((uint32_t)s0 << 16) | ((uint32_t)s1 << 24);
-}
 int nalo_ba_set_point_history(nalo_ctx* c, const int* numGood, const int8_t* last_target, const int8_t* last_state) {
     NALO_BA_READY("nalo_ba_set_point_history")
     if ((last_target == nullptr) != (last_state == nullptr)) return fail(c, NALO_ERR_ARG, "nalo_ba_set_point_history: last_target and last_state come together");
     const int W = w.W; const size_t N = w.Ppad;
     std::vector<int> ng(N, 0);
-    std::vector<uint32_t> last(N, pack_last(-1, -1, 1, 1));
+    std::vector<uint32_t> last(N, kLastNone);
     std::vector<uint8_t> ex;                                        // the rows of the two newest frames: what optimizeImmaturePoint leaves depends on the residuals it made
     if (!last_target) {
         ex.resize(2 * N);
@@ -1709,16 +1708,18 @@ int nalo_ba_set_prior_carry(nalo_ctx* c, int on) {
     return NALO_OK;
 }
 
+static nalo_frame_state frame_state_of(const HostFrame& f) {
+    nalo_frame_state s;
+    s.slot = f.slot; s.frame_id = f.frameID; std::memcpy(s.worldToCam_evalPT, f.evalPT.m, 96);
+    std::memcpy(s.state, f.state, 80); std::memcpy(s.state_zero, f.state_zero, 80); s.ab_exposure = f.ab_exposure; s.frameEnergyTH = f.frameEnergyTH;
+    return s;
+}
 int nalo_ba_get_frames(nalo_ctx* c, nalo_frame_state* frames, double* worldToCam, double calib[4]) {
     if (!c || !c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_ba_get_frames: set the window first");
     BAWindow& w = *c->ba;
     for (int i = 0; i < w.W; ++i) {
         const HostFrame& f = w.frames[i];
-        if (frames) {
-            nalo_frame_state& s = frames[i];
-            s.slot = f.slot; s.frame_id = f.frameID; std::memcpy(s.worldToCam_evalPT, f.evalPT.m, 96);
-            std::memcpy(s.state, f.state, 80); std::memcpy(s.state_zero, f.state_zero, 80); s.ab_exposure = f.ab_exposure; s.frameEnergyTH = f.frameEnergyTH;
-        }
+        if (frames) frames[i] = frame_state_of(f);
         if (worldToCam) std::memcpy(worldToCam + 12 * i, f.PRE_worldToCam.m, 96);
     }
     if (calib) std::memcpy(calib, w.c_value_scaled, 32);
@@ -2075,6 +2076,52 @@ int nalo_ba_restore(nalo_ctx* c) {
     return NALO_OK;
 }
 
+// ---- what the two device issues of a window (nalo_ba_carry_window, nalo_ba_window_from_initializer) share, between build_point_layout and window_finish
+// the arrays the issuing kernel writes: the first set, with the history arrays where the new window carries one
+static IssueDev issue_dev(const BAWindow& w, bool hist) {
+    IssueDev I{};
+    I.W = w.W; I.Ppad = w.Ppad;
+    I.geo = w.pt_geo.p; I.col0 = w.pt_col0.p; I.col1 = w.pt_col1.p; I.w0 = w.pt_w0.p; I.w1 = w.pt_w1.p; I.prior = w.pt_prior.p; I.flags = w.pt_flags.p;
+    I.ng = hist ? w.pt_numgood.p : nullptr; I.last = hist ? w.pt_last.p : nullptr;
+    I.acc = w.pt_acc.p; I.hcd = w.pt_hcd.p; I.step = w.pt_step.p; I.backup = w.pt_backup.p; I.relbs = w.pt_relbs.p; I.relbs2 = w.pt_relbs2.p; I.ngood = w.pt_ngood.p;
+    I.state = w.rs_state.p; I.energy = w.rs_energy.p; I.jp0 = w.rs_jp0.p; I.jp1 = w.rs_jp1.p; I.cpt = w.rs_cpt.p;
+    return I;
+}
+// The map and the block tables of the layout L: one pinned block [src | blk_host | host_blk | sc_grp | blk_order], rewritten only after the copies of the issue
+// before have left it, and stream-ordered copies. from: the source of every point of the new list (a padding slot gets -1). The host's mirror of the flag bytes is
+// rebuilt on the way: `fresh`, or, where from names a slot of old_flags, what the point carried there (a decision nobody consumed does not outlive its window).
+static int stage_issue_tables(nalo_ctx* c, const PointLayout& L, const std::vector<int>& from, const uint8_t* old_flags, uint8_t fresh, const int** src) {
+    BAWindow& w = *c->ba;
+    const size_t N = w.Ppad, nb = w.nblocks, W1 = w.W + 1;
+    const size_t o_bh = N, o_hb = o_bh + nb, o_grp = o_hb + W1, o_ord = o_grp + W1, words = o_ord + L.order.size();
+    if (w.ev_carry) NALO_HIP(c, hipEventSynchronize(w.ev_carry)); else NALO_HIP(c, w.ev_carry.create(hipEventDisableTiming));
+    NALO_HIP(c, w.carry_host.reserve(words)); NALO_HIP(c, w.carry_src.reserve(N));
+    int* hb = w.carry_host.p;
+    w.flags_h.assign(N, 0);
+    for (size_t d = 0; d < N; ++d) {
+        const int p = w.d2p[d];
+        hb[d] = p < 0 ? -1 : from[p];
+        if (p >= 0) w.flags_h[d] = old_flags && from[p] >= 0 ? (uint8_t)(old_flags[from[p]] & (PT_VALID | PT_HAS_PRIOR)) : fresh;
+    }
+    std::memcpy(hb + o_bh, w.blk_host_h.data(), nb * 4); std::memcpy(hb + o_hb, w.host_blk_h.data(), W1 * 4);
+    std::memcpy(hb + o_grp, L.grp.data(), W1 * 4); std::memcpy(hb + o_ord, L.order.data(), L.order.size() * 4);
+    NALO_HIP(c, hipMemcpyAsync(w.carry_src.p, hb, N * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.blk_host.p, hb + o_bh, nb * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.host_blk.p, hb + o_hb, W1 * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.sc_grp.p, hb + o_grp, W1 * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.blk_order.p, hb + o_ord, L.order.size() * 4, hipMemcpyHostToDevice, c->stream));
+    NALO_HIP(c, hipEventRecord(w.ev_carry, c->stream));
+    *src = w.carry_src.p;
+    return NALO_OK;
+}
+// behind the issuing kernel: the linearisation's partials zeroed, the kernels' view bound, points and residuals set; a snapshot was of other arrays
+static int issue_finish(nalo_ctx* c, bool hist) {
+    BAWindow& w = *c->ba;
+    NALO_HIP(c, hipMemsetAsync(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * w.W * kTopStride * 8, c->stream));
+    bind_points(w, hist);
+    w.points_set = true; w.res_set = true; w.have_snap = false;
+    return NALO_OK;
+}
 // ---- the seam between two keyframes on the device (FullSystem::makeKeyFrame: marginalizeFrame -> insertFrame + the new residuals, FullSystem.cpp:1310-1348;
 // activatePointsMT step 4, :893-917). The host's share is integer work on mirrors it keeps anyway - the flag bytes, the slot keys, the resident set's u / v /
 // host_idx, the activation's sel / result -: it works out src[d_new] and trow[t_new] through the layout function nalo_ba_set_points uses, sends them with one
@@ -2143,18 +2190,12 @@ int nalo_ba_carry_window(nalo_ctx* c, const nalo_frame_state* entering, int inse
     { int rc = flush_th(c); if (rc) return rc; }
     // ---- frames: the remaining ones as nalo_ba_get_frames returns them (+ the entering one), through nalo_ba_set_window's own code
     std::vector<nalo_frame_state> fs(W);
-    for (int i = 0; i < W_old; ++i) {
-        const HostFrame& f = w.frames[i];
-        nalo_frame_state& s = fs[i];
-        s.slot = f.slot; s.frame_id = f.frameID; std::memcpy(s.worldToCam_evalPT, f.evalPT.m, 96);
-        std::memcpy(s.state, f.state, 80); std::memcpy(s.state_zero, f.state_zero, 80); s.ab_exposure = f.ab_exposure; s.frameEnergyTH = f.frameEnergyTH;
-    }
+    for (int i = 0; i < W_old; ++i) fs[i] = frame_state_of(w.frames[i]);
     if (entering) fs[W_old] = *entering;
-    int trow[16];
-    for (int t = 0; t < 16; ++t) trow[t] = t < W_old ? w.row_of[t] : -1;
     // ---- what the kernel reads of the old window, before the buffers change hands
     CarryDev A{};
-    A.W_new = W; A.Ppad_old = w.Ppad; A.enter = entering ? 1 : 0;
+    for (int t = 0; t < 16; ++t) A.trow[t] = t < W_old ? w.row_of[t] : -1;
+    A.Ppad_old = w.Ppad; A.enter = entering ? 1 : 0;
     A.o_geo = w.pt_geo.p; A.o_col0 = w.pt_col0.p; A.o_col1 = w.pt_col1.p; A.o_w0 = w.pt_w0.p; A.o_w1 = w.pt_w1.p; A.o_prior = w.pt_prior.p;
     A.o_flags = w.pt_flags.p; A.o_state = w.rs_state.p; A.o_ng = w.hist_set ? w.pt_numgood.p : nullptr; A.o_last = w.hist_set ? w.pt_last.p : nullptr;
     const std::vector<uint8_t> old_flags = w.flags_h;
@@ -2168,42 +2209,14 @@ int nalo_ba_carry_window(nalo_ctx* c, const nalo_frame_state* entering, int inse
     { int rc = build_point_layout(c, P, host.data(), key.data(), L, sorted.data()); if (rc) return rc; }
     const size_t N = w.Ppad;
     if (w.hist_set) { NALO_HIP(c, w.pt_numgood.reserve(N)); NALO_HIP(c, w.pt_last.reserve(N)); }
-    // ---- the maps and the block tables: one pinned block, stream-ordered copies (the block is rewritten only after the copies of the carry before have left it)
-    const size_t o_src = 16, o_bh = o_src + N, o_hb = o_bh + w.nblocks, o_grp = o_hb + (W + 1), o_ord = o_grp + (W + 1), words = o_ord + L.order.size();
-    if (w.ev_carry) NALO_HIP(c, hipEventSynchronize(w.ev_carry)); else NALO_HIP(c, w.ev_carry.create(hipEventDisableTiming));
-    NALO_HIP(c, w.carry_host.reserve(words)); NALO_HIP(c, w.carry_src.reserve(o_bh));
-    int* hb = w.carry_host.p;
-    std::memcpy(hb, trow, sizeof(trow));
-    w.flags_h.assign(N, 0);
-    for (size_t d = 0; d < N; ++d) {
-        const int p = w.d2p[d];
-        hb[o_src + d] = p < 0 ? -1 : from[p];
-        if (p < 0) continue;
-        w.flags_h[d] = from[p] >= 0 ? (uint8_t)(old_flags[from[p]] & (PT_VALID | PT_HAS_PRIOR)) : (uint8_t)PT_VALID;
-    }
-    std::memcpy(hb + o_bh, w.blk_host_h.data(), (size_t)w.nblocks * 4); std::memcpy(hb + o_hb, w.host_blk_h.data(), (size_t)(W + 1) * 4);
-    std::memcpy(hb + o_grp, L.grp.data(), (size_t)(W + 1) * 4); std::memcpy(hb + o_ord, L.order.data(), L.order.size() * 4);
-    NALO_HIP(c, hipMemcpyAsync(w.carry_src.p, hb, o_bh * 4, hipMemcpyHostToDevice, c->stream));                       // [trow | src]: the maps
-    NALO_HIP(c, hipMemcpyAsync(w.blk_host.p, hb + o_bh, (size_t)w.nblocks * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.host_blk.p, hb + o_hb, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.sc_grp.p, hb + o_grp, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.blk_order.p, hb + o_ord, L.order.size() * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipEventRecord(w.ev_carry, c->stream));
+    { const int rc = stage_issue_tables(c, L, from, old_flags.data(), PT_VALID, &A.src); if (rc) return rc; }
     // ---- one launch: gather, insert, pad, zero
-    A.src = w.carry_src.p + o_src; std::memcpy(A.trow, trow, sizeof(trow)); A.Ppad_new = w.Ppad;
-    A.geo = w.pt_geo.p; A.col0 = w.pt_col0.p; A.col1 = w.pt_col1.p; A.w0 = w.pt_w0.p; A.w1 = w.pt_w1.p; A.prior = w.pt_prior.p; A.flags = w.pt_flags.p; A.state = w.rs_state.p;
-    A.ng = w.hist_set ? w.pt_numgood.p : nullptr; A.last = w.hist_set ? w.pt_last.p : nullptr;
-    A.acc = w.pt_acc.p; A.hcd = w.pt_hcd.p; A.step = w.pt_step.p; A.backup = w.pt_backup.p; A.relbs = w.pt_relbs.p; A.relbs2 = w.pt_relbs2.p; A.ngood = w.pt_ngood.p;
-    A.energy = w.rs_energy.p; A.jp0 = w.rs_jp0.p; A.jp1 = w.rs_jp1.p; A.cpt = w.rs_cpt.p;
+    A.I = issue_dev(w, w.hist_set);
     A.imm = c->imm_res.p; A.immN = c->imm_res_n;
     A.a_sel = c->act_pend.p; A.a_idepth = reinterpret_cast<const float*>(c->act_pend.p + std::max(n_act, 0)); A.a_in = reinterpret_cast<const uint8_t*>(c->act_pend.p + 2 * std::max(n_act, 0));
     { ProfScope ps(c, "ba_carry"); ba_launch_carry(c->stream, A, w.nblocks); }
     NALO_HIP(c, hipGetLastError());
-    NALO_HIP(c, hipMemsetAsync(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8, c->stream));
-    bind_points(w);
-    w.dev.pt_numgood = w.hist_set ? w.pt_numgood.p : nullptr; w.dev.pt_last = w.hist_set ? w.pt_last.p : nullptr;
-    w.points_set = true; w.res_set = true;
-    w.have_snap = false;                                            // a snapshot is of the arrays that just became the source
+    { const int rc = issue_finish(c, w.hist_set); if (rc) return rc; }     // (a snapshot would be of the arrays that just became the source)
     if (insert_activated) c->act_pend_n = -1;                       // consumed
     w.carry_map_h.swap(map);
     w.carry_stats[0] = n_carried; w.carry_stats[1] = P - n_carried; w.carry_stats[2] = P; w.carry_stats[3] = w.Ppad; w.carried = true;
@@ -2293,41 +2306,15 @@ int nalo_ba_window_from_initializer(nalo_ctx* c, nalo_init_window_args* a) {
     { const int rc = build_point_layout(c, P, host.data(), key.data(), L); if (rc) return rc; }
     const size_t N = w.Ppad;
     NALO_HIP(c, w.pt_numgood.reserve(N)); NALO_HIP(c, w.pt_last.reserve(N));
-    // the map and the block tables: one pinned block, stream-ordered copies (the staging of nalo_ba_carry_window)
-    const int W = 2;
-    const size_t o_bh = N, o_hb = o_bh + w.nblocks, o_grp = o_hb + (W + 1), o_ord = o_grp + (W + 1), words = o_ord + L.order.size();
-    if (w.ev_carry) NALO_HIP(c, hipEventSynchronize(w.ev_carry)); else NALO_HIP(c, w.ev_carry.create(hipEventDisableTiming));
-    NALO_HIP(c, w.carry_host.reserve(words)); NALO_HIP(c, w.carry_src.reserve(N));
-    int* hb = w.carry_host.p;
-    w.flags_h.assign(N, 0);
-    for (size_t d = 0; d < N; ++d) {
-        const int p = w.d2p[d];
-        hb[d] = p < 0 ? -1 : kept[p];
-        if (p >= 0) w.flags_h[d] = PT_VALID | PT_HAS_PRIOR;
-    }
-    std::memcpy(hb + o_bh, w.blk_host_h.data(), (size_t)w.nblocks * 4); std::memcpy(hb + o_hb, w.host_blk_h.data(), (size_t)(W + 1) * 4);
-    std::memcpy(hb + o_grp, L.grp.data(), (size_t)(W + 1) * 4); std::memcpy(hb + o_ord, L.order.data(), L.order.size() * 4);
-    NALO_HIP(c, hipMemcpyAsync(w.carry_src.p, hb, N * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.blk_host.p, hb + o_bh, (size_t)w.nblocks * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.host_blk.p, hb + o_hb, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.sc_grp.p, hb + o_grp, (size_t)(W + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipMemcpyAsync(w.blk_order.p, hb + o_ord, L.order.size() * 4, hipMemcpyHostToDevice, c->stream));
-    NALO_HIP(c, hipEventRecord(w.ev_carry, c->stream));
-    // ---- one launch: construct, scale, pad, zero
     InitWindowDev A{};
-    A.src = w.carry_src.p; A.Ppad = w.Ppad; A.n = n; A.w = c->w; A.h = c->h;
+    { const int rc = stage_issue_tables(c, L, kept, nullptr, PT_VALID | PT_HAS_PRIOR, &A.src); if (rc) return rc; }
+    // ---- one launch: construct, scale, pad, zero
+    A.n = n; A.w = c->w; A.h = c->h;
     A.dI = c->slots[V.slot_first].dI[0].p; A.u = V.u; A.v = V.v; A.iR = V.iR; A.rescale = rescaleFactor;
     A.prior = kIdepthFixPrior * kScaleIdepth * kScaleIdepth;       // EFPoint::takeData (EnergyFunctionalStructs.cpp:79-85), as nalo_ba_set_points has it
-    A.geo = w.pt_geo.p; A.col0 = w.pt_col0.p; A.col1 = w.pt_col1.p; A.w0 = w.pt_w0.p; A.w1 = w.pt_w1.p; A.prior_out = w.pt_prior.p; A.flags = w.pt_flags.p; A.state = w.rs_state.p;
-    A.ng = w.pt_numgood.p; A.last = w.pt_last.p;
-    A.acc = w.pt_acc.p; A.hcd = w.pt_hcd.p; A.step = w.pt_step.p; A.backup = w.pt_backup.p; A.relbs = w.pt_relbs.p; A.relbs2 = w.pt_relbs2.p; A.ngood = w.pt_ngood.p;
-    A.energy = w.rs_energy.p; A.jp0 = w.rs_jp0.p; A.jp1 = w.rs_jp1.p; A.cpt = w.rs_cpt.p;
+    A.I = issue_dev(w, true);
     { const int rc = init_window_gather_launch(c, A, w.nblocks); if (rc) return rc; }
-    NALO_HIP(c, hipMemsetAsync(w.top_partial.p, 0, (size_t)w.nblocks * w.dev.lin_sub * W * kTopStride * 8, c->stream));
-    bind_points(w);
-    w.hist_set = true; w.dev.pt_numgood = w.pt_numgood.p; w.dev.pt_last = w.pt_last.p;
-    w.points_set = true; w.res_set = true;
-    w.have_snap = false;
+    { const int rc = issue_finish(c, true); if (rc) return rc; }
     w.iw_map_h.swap(kept);
     w.iw_scale[0] = sumID; w.iw_scale[1] = numID; w.iw_scale[2] = rescaleFactor;
     w.iw_stats[0] = n; w.iw_stats[1] = skipped; w.iw_stats[2] = rejected; w.iw_stats[3] = P; w.iw_have = true;

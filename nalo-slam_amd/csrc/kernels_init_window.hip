@@ -59,39 +59,26 @@ __global__ __launch_bounds__(256) void iw_flag_kernel(const float4* __restrict__
 }
 
 __global__ __launch_bounds__(256) void iw_gather_kernel(InitWindowDev A) {
-    const int d = blockIdx.x * kBlk + threadIdx.x;                      // grid = the window's point blocks: d < Ppad
-    const size_t N = (size_t)A.Ppad;
+    const int d = blockIdx.x * kBlk + threadIdx.x;                      // grid = the window's point blocks: d < I.Ppad
     const int s = A.src[d];
-    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    // the filler of a padding slot (nalo_ba_set_points, nalo_ba_set_point_history)
-    float4 geo = make_float4(8.f, 8.f, 1.f, 1.f), c0 = z4, c1 = z4, w0 = z4, w1 = z4;
-    float prior = 0.f;
-    uint8_t flags = 0, st1 = 0;
-    uint32_t last = 0x0101FFFFu;                                        // {-1, -1} / {OOB, OOB}
+    IssuePoint p;                                                       // the filler of a padding slot, without a history
+    uint8_t st1 = 0;
     int ui, vi;
     if (s >= 0 && s < A.n && iw_pixel(A.u, A.v, s, A.w, A.h, ui, vi)) {
         const ImmCtor c = imm_ctor(A.dI, A.w, ui, vi);
         const float id = A.iR[s] * A.rescale;                           // setIdepthScaled(iR * rescaleFactor), setIdepthZero(idepth) (SCALE_IDEPTH = 1)
-        geo = make_float4((float)ui, (float)vi, id, id);
-        c0 = make_float4(c.color[0], c.color[1], c.color[2], c.color[3]); c1 = make_float4(c.color[4], c.color[5], c.color[6], c.color[7]);
-        w0 = make_float4(c.weights[0], c.weights[1], c.weights[2], c.weights[3]); w1 = make_float4(c.weights[4], c.weights[5], c.weights[6], c.weights[7]);
-        prior = A.prior;                                                // hasDepthPrior = true: EFPoint::takeData's priorF
-        flags = PT_VALID | PT_HAS_PRIOR;
+        p.geo = make_float4((float)ui, (float)vi, id, id);
+        p.c0 = make_float4(c.color[0], c.color[1], c.color[2], c.color[3]); p.c1 = make_float4(c.color[4], c.color[5], c.color[6], c.color[7]);
+        p.w0 = make_float4(c.weights[0], c.weights[1], c.weights[2], c.weights[3]); p.w1 = make_float4(c.weights[4], c.weights[5], c.weights[6], c.weights[7]);
+        p.prior = A.prior;                                              // hasDepthPrior = true: EFPoint::takeData's priorF
+        p.flags = PT_VALID | PT_HAS_PRIOR;
         st1 = RS_EXISTS;                                                // the residual to the entering frame (:1340-1343)
         // lastResiduals is value-initialised to {(0, IN), (0, IN)} by PointHessian and then shifted (:1344-1345): [0] = (frame 1, IN), [1] = (null, IN)
-        last = 0x0000FF01u;
+        p.last = pack_last(1, -1, 0u, 0u);
     }
-    A.geo[d] = geo; A.col0[d] = c0; A.col1[d] = c1; A.w0[d] = w0; A.w1[d] = w1;
-    A.prior_out[d] = prior; A.flags[d] = flags;
-    A.ng[d] = 0; A.last[d] = last;
-    A.acc[d] = z4; A.hcd[d] = z4; A.step[d] = 0.f; A.backup[d] = 0.f; A.relbs[d] = 0.f; A.relbs2[d] = 0.f; A.ngood[d] = 0;
+    issue_store_point(A.I, d, p);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {                                       // t-major rows of the two-frame window
-        const size_t si = (size_t)t * N + d;
-        A.state[si] = t == 1 ? st1 : (uint8_t)0;                        // state IN, energies zero, resetOOB: what nalo_ba_set_residuals leaves
-        A.energy[si] = make_float2(0.f, 0.f);
-        A.jp0[si] = z4; A.jp1[si] = z4; A.cpt[si] = z4;
-    }
+    for (int t = 0; t < 2; ++t) issue_store_row(A.I, t, d, t == 1 ? st1 : (uint8_t)0);     // t-major rows of the two-frame window
 }
 
 int init_window_scan_launch(nalo_ctx* c, const float4* dI, const float* u, const float* v, const float* iR, int n, uint8_t* ok, float* sum) {

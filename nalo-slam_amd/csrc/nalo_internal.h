@@ -286,13 +286,7 @@ int imm_carry_launch(nalo_ctx* c, const ImmCarryParams& P);
 struct InitLevel0 { int n, slot_first; const float *u_host, *v_host, *u, *v, *iR; double thisToNext[12]; };
 int init_level0(nalo_ctx* c, const char* who, InitLevel0* out);
 // kernels_init_window.hip: the ordered sum of iR and the constructor's verdict per level-0 point; then the kept points gathered into a two-frame window's arrays
-// (src[d]: level-0 index or -1 for padding; the first set of point / slot buffers as build_point_layout sized them). Every pointer is device memory.
-struct InitWindowDev {
-    const int* src; int Ppad, n, w, h;
-    const float4* dI; const float *u, *v, *iR; float rescale, prior;
-    float4 *geo, *col0, *col1, *w0, *w1; float* prior_out; uint8_t *flags, *state; int* ng; uint32_t* last;
-    float4 *acc, *hcd; float *step, *backup, *relbs, *relbs2; uint8_t* ngood; float2* energy; float4 *jp0, *jp1, *cpt;
-};
+struct InitWindowDev;                                                           // ba_device.h, beside CarryDev
 int init_window_scan_launch(nalo_ctx* c, const float4* dI, const float* u, const float* v, const float* iR, int n, uint8_t* ok, float* sum);
 int init_window_gather_launch(nalo_ctx* c, const InitWindowDev& A, int nblocks);
 // kernels_pixsel.hip: the last map's compact list when it was made on `slot` (false otherwise): on the device with its holes (status 0), on the host without

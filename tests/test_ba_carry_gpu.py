@@ -9,6 +9,7 @@ it through the step API.
 
   1  a frame leaves from the middle and one enters (W = 6, ~3000 points)
   2  two frames leave and none enters, then one enters in a second carry
+  2b hosts of 517, 517, 0, 256, 257 and 1 points (kBlk = 256: an empty host, a one-point block, an exactly full block, a block plus one): one enters, then one leaves
   3  insertion of an activation's points (the scene and immature points of test_imm_activate_gpu.py's smallest shape)
   4  four keyframes of a sliding window of five frames, A never re-issuing after keyframe 0
   5  W = 16, and the refusal of a 17th frame
@@ -155,8 +156,13 @@ def scene6():
     return win, idepth, exists, st6, (win.host == 0).astype(np.int32)
 
 
-def make_pair6():
+def make_pair6(idx=None):
+    """idx: the points of the scene the window is built from (all of them when None)"""
     win, idepth, exists, st6, has_prior = scene6()
+    if idx is not None:
+        idepth, exists, has_prior = idepth[idx], exists[idx], has_prior[idx]
+        for n in ("host", "u", "v", "color", "weights"):
+            setattr(win, n, np.ascontiguousarray(getattr(win, n)[idx]))
     pair = []
     for _ in range(2):
         c = binding.Context(win.w, win.h, win.K, n_slots=W6 + 1)
@@ -240,6 +246,31 @@ def test_two_frames_leave_then_one_enters_in_a_second_carry():
     reissue(b, new, pre_b, np.ones(len(new.host), bool), [0, 1, 2, 3], entering, prior, b.ba_get_point_history())
     assert a.W == 5 and np.array_equal(a.ba_carry_map(), np.arange(a.P))
     assert_equal_windows(a, b, "then one entered")
+    a.close(); b.close()
+
+
+def test_block_edges_one_enters_then_a_frame_leaves():
+    host = scene6()[0].host
+    counts = [517, 517, 0, BLK, BLK + 1, 1]                                   # (the scene's last two hosts hold 516 points)
+    idx = np.concatenate([np.nonzero(host == h)[0][:n] for h, n in enumerate(counts)])
+    win, a, b, pts, entering = make_pair6(idx)
+    assert np.bincount(pts.host, minlength=W6).tolist() == counts and a.ba_launch_config()["nblocks"] == 3 + 3 + 0 + 1 + 2 + 1
+    # the new keyframe enters, nothing leaves: the block edges as they are
+    prior, pre_b = a.ba_get_prior(), read_points(b)
+    stats = a.ba_carry_window(entering)
+    new, m = reissue(b, pts, pre_b, np.ones(len(pts.host), bool), list(range(W6)), entering, prior, b.ba_get_point_history())
+    assert stats == (len(idx), 0, len(idx), 10 * BLK) and a.W == W6 + 1 and np.array_equal(a.ba_carry_map(), np.arange(len(idx)))
+    assert_equal_windows(a, b, "block edges, one entered")
+    # the host of the exactly full block is marginalised: its points go, the frame leaves, the hosts behind it move down a row
+    dec, (pre_a, pre_b) = fix_flag_remove((a, b), [3])
+    valid = dec == lm.KEEP
+    assert not valid[new.host == 3].any() and valid[new.host == 4].sum() > 0
+    for c in (a, b):
+        c.ba_marginalize_frame(3)
+    prior = a.ba_get_prior()
+    assert a.ba_carry_window()[:3] == (int(valid.sum()), 0, int(valid.sum())) and a.W == W6
+    reissue(b, new, pre_b, valid, [0, 1, 2, 4, 5, 6], None, prior, b.ba_get_point_history())
+    assert_equal_windows(a, b, "block edges, a frame left")
     a.close(); b.close()
 
 
