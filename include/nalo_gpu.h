@@ -813,8 +813,9 @@ int nalo_init_get_points(nalo_ctx* ctx, int lvl, int cap, int* n, float* u, floa
  *             flagPointsForRemoval's inside one keyframe and permutes by swap-with-back; the sets and every value are equal, the order inside a keyframe's
  *             run is the library's.
  *   frame_id  the caller's, from nalo_frame_state: the archive is keyed by it, so the frames of a session need distinct ids.
- *   Not archived: points removed by nalo_ba_marginalize_points (host flags). nalo_ba_snapshot / nalo_ba_restore do not include the archive.
- * nalo_map_reset      empties the archive (and the dense archive of nalo_map_dense_enable) and keeps its chunks.
+ *   Not archived: points removed by nalo_ba_marginalize_points (host flags). nalo_ba_snapshot / nalo_ba_restore do not include the archive (nor the graph of
+ *   nalo_map_graph_enable).
+ * nalo_map_reset      empties the archive (and the dense archive of nalo_map_dense_enable) and keeps its chunks; empties the graph of nalo_map_graph_enable.
  * nalo_map_counts     counts = {pointHessiansMarginalized.size(), pointHessiansOut.size()} of the frame: the addends of flagFramesForMarginalization's
  *                     `out` (FullSystemMarginalize.cpp:77). NALO_ERR_ARG for a frame_id the archive has never seen.
  * nalo_map_get_frame  the frame's records: its status-2 records in archive order, then its status-3 records. *n = their number; cap < *n: NALO_ERR_ARG
@@ -869,6 +870,43 @@ int nalo_map_get_frame(nalo_ctx* ctx, int frame_id, nalo_map_record* records, in
 int nalo_map_world_points(nalo_ctx* ctx, int frame_id, const double camToWorld[12], double* xyz /* n x 3 */, int cap, int* n);
 int nalo_map_world_points_host(int n, const float* u, const float* v, const float* idepth, const float calib_inv[4], const double camToWorld[12], double* xyz /* n x 3 */);
 int nalo_map_frame_cloud(nalo_ctx* ctx, nalo_map_cloud_args* args);
+
+/* ------------------------------------------------------------------------------------------------
+ * The keyframe graph: EnergyFunctional::connectivityMap, the argument of Output3DWrapper::publishGraph (FullSystem.cpp:1498-1502), for a caller that holds no
+ * PointFrameResidual objects. The map's key is (host->frameID << 32) + target->frameID and its value {[0], [1]}; four events touch it in the reference:
+ * insertFrame sets (new, f2) and (f2, new) to {0, 0} for every frame f2 of the window, (new, new) included (EnergyFunctional.cpp:453-458); insertResidual is [0]++
+ * (:423); dropResidual is [0]-- (:493: removePoint of dropped and marginalised points, the removals of linearizeAll(true), FullSystem::marginalizeFrame for every
+ * residual that targets the leaving frame); marginalizePointsF is [1]++ for every residual of a PS_MARGINALIZE point that isActive() after its re-linearisation
+ * (:628-634). Entries are never erased: [0] is the number of residual objects that exist for the pair, in any state, 0 once one of its frames has left; [1] only
+ * grows. Here the keys and [1] (marg) are a host table keyed by the caller's frame_id, and [0] (act) is counted from the resident slots when the graph is read.
+ *
+ * nalo_map_graph_enable(ctx, on)   opt-in and independent of nalo_map_enable: a context that never calls it enqueues and allocates exactly what it did before.
+ *   Pairs     created when frames become co-resident, for every ordered pair of window frames without an entry, (f, f) included; an existing entry keeps its
+ *             counts. nalo_ba_set_window (W frames leave what W insertFrames would: re-issuing the window every keyframe works as well), nalo_ba_carry_window with
+ *             an entering frame and nalo_ba_window_from_initializer create them; turning the graph on while a window is set creates that window's.
+ *             nalo_ba_marginalize_frame erases nothing. nalo_map_reset empties the table and leaves the pairs of the frames then in the window, as a fresh
+ *             EnergyFunctional that has inserted them would. nalo_ba_snapshot / nalo_ba_restore do not include the table.
+ *   marg      added by nalo_ba_marginalize_flagged and nalo_ba_marginalize_points alike, from the per-pair residual counts of the marginalisation pass the call
+ *             fetches anyway (no launch, no wait of its own). Marginalisations made while the graph was off are not counted.
+ *   frame_id  while on, a frame with a negative frame_id is refused by the call that would enter it - nalo_ba_set_window, nalo_ba_carry_window,
+ *             nalo_ba_window_from_initializer: NALO_ERR_ARG, the window as it was (the reference asserts >= 0, PangolinDSOViewer.cpp:542) -, and so is turning the
+ *             graph on over a window that holds one. The frames of a session need distinct ids.
+ *   NALO_ERR_STATE on a sharded window and on a context whose exchange failed, as with nalo_map_enable.
+ * nalo_map_graph   every entry in ascending key order (std::map's iteration order), the (f, f) entries {0, 0} included: *n is connectivity.size(), what
+ *   SampleOutputWrapper::publishGraph prints. act of a pair of frames nalo_ba_get_frames returns now: the slots with a residual that belong to valid points hosted
+ *   by the first frame, in the row of the second, counted by one kernel over the resident arrays; of any other pair: 0. Between nalo_ba_marginalize_frame and the
+ *   carry the arrays stand in the old layout: the departed row is not read, which is what FullSystem::marginalizeFrame's drops leave. One launch, one 1 KB copy,
+ *   one wait per call. cap < *n: NALO_ERR_ARG with *n set. NALO_ERR_STATE, outputs untouched: the graph is off; no window; the window's points are neither set
+ *   nor carriable (nalo_ba_set_window with another size, a frame that left while it hosted points); a sharded window.
+ * nalo_map_graph_connections   PangolinDSOViewer::publishGraph's list (IOWrapper/Pangolin/PangolinDSOViewer.cpp:528-571): the keys with host_id < target_id in
+ *   key order, {fwdAct, fwdMarg} from the key and {bwdAct, bwdMarg} from the inverse key; *n is the viewer's runningID. from_id / to_id are the frame ids (the
+ *   viewer looks its KeyFrameDisplays up by them). Cost and refusals as nalo_map_graph.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_graph_edge { int host_id, target_id, act, marg; } nalo_graph_edge;                       /* one entry of connectivityMap */
+typedef struct nalo_graph_connection { int from_id, to_id, fwdAct, bwdAct, fwdMarg, bwdMarg; } nalo_graph_connection;   /* GraphConnection, ids instead of KeyFrameDisplay* */
+int nalo_map_graph_enable(nalo_ctx* ctx, int on);
+int nalo_map_graph(nalo_ctx* ctx, nalo_graph_edge* edges, int cap, int* n);
+int nalo_map_graph_connections(nalo_ctx* ctx, nalo_graph_connection* conn, int cap, int* n);
 
 /* ------------------------------------------------------------------------------------------------
  * densemap=1: DenseMapping::updateMap (FullSystem/MapPoint.cpp:234-332, call site FullSystem.cpp:1488-1496) in one call, and FrameHessian::mapPoints as a

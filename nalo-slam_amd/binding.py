@@ -37,6 +37,7 @@ EXPORTS = [
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
+    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
@@ -84,6 +85,10 @@ class MapCloudArgs(C.Structure):
 MAP_RECORD_DTYPE = np.dtype([("u", np.float32), ("v", np.float32), ("idepth", np.float32), ("idepth_hessian", np.float32), ("maxRelBaseline", np.float32),
                              ("status", np.int32), ("decision", np.int32), ("frame_id", np.int32), ("color", np.float32, 8)])
 assert MAP_RECORD_DTYPE.itemsize == 64
+GRAPH_EDGE_DTYPE = np.dtype([("host_id", np.int32), ("target_id", np.int32), ("act", np.int32), ("marg", np.int32)])                       # nalo_graph_edge
+GRAPH_CONNECTION_DTYPE = np.dtype([("from_id", np.int32), ("to_id", np.int32), ("fwdAct", np.int32), ("bwdAct", np.int32), ("fwdMarg", np.int32),
+                                   ("bwdMarg", np.int32)])                                                                                    # nalo_graph_connection
+assert GRAPH_EDGE_DTYPE.itemsize == 16 and GRAPH_CONNECTION_DTYPE.itemsize == 24
 
 
 class MapDenseCloudArgs(C.Structure):
@@ -196,6 +201,9 @@ def load():
     L.nalo_map_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
     L.nalo_map_world_points_host.argtypes = [C.c_int, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp]
     L.nalo_map_frame_cloud.argtypes = [vp, C.POINTER(MapCloudArgs)]
+    L.nalo_map_graph_enable.argtypes = [vp, C.c_int]
+    L.nalo_map_graph.argtypes = [vp, vp, C.c_int, c_ip]
+    L.nalo_map_graph_connections.argtypes = [vp, vp, C.c_int, c_ip]
     L.nalo_dense_update_map.argtypes = [vp, C.c_int, C.POINTER(PlaneFitArgs), c_dp, C.c_int, vp, vp, c_ip, c_ip]
     L.nalo_map_dense_enable.argtypes = [vp, C.c_int, C.c_int]
     L.nalo_map_dense_counts.argtypes = [vp, C.c_int, c_ip, c_ip]
@@ -769,6 +777,30 @@ class Context:
             a.draws, a.n_draws = (None, 0) if d is None else (_i(d), len(d))
             self._ck(self.L.nalo_map_frame_cloud(self.h_, C.byref(a)))
         return dict(xyz=xyz[:a.n], rgb=rgb[:a.n], records=np.array(list(a.records)), survivors=np.array(list(a.survivors)), n_needed=cap)
+
+    # ---- the keyframe graph: EnergyFunctional::connectivityMap from the device chain
+    def map_graph_enable(self, on=True):
+        """nalo_map_graph_enable: the pairs of the frames that share a window from now on, and the residuals marginalised between them"""
+        self._ck(self.L.nalo_map_graph_enable(self.h_, int(bool(on))))
+
+    def _graph_get(self, fn, dtype):
+        cap = getattr(self, "_graph_cap", 512)                                    # one device call unless the table has outgrown the last answer
+        while True:
+            out, n = np.zeros(cap, dtype), C.c_int(-1)
+            rc = fn(self.h_, out.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+            if rc != 0 and n.value > cap:
+                cap = self._graph_cap = 2 * n.value
+                continue
+            self._ck(rc)
+            return out[:n.value].copy()
+
+    def map_graph(self):
+        """connectivityMap: every entry (GRAPH_EDGE_DTYPE) in key order, act = [0], marg = [1]"""
+        return self._graph_get(self.L.nalo_map_graph, GRAPH_EDGE_DTYPE)
+
+    def map_graph_connections(self):
+        """PangolinDSOViewer::publishGraph's connections (GRAPH_CONNECTION_DTYPE), frame ids for the KeyFrameDisplay pointers"""
+        return self._graph_get(self.L.nalo_map_graph_connections, GRAPH_CONNECTION_DTYPE)
 
     # ---- the dense map: updateMap in one call, mapPoints archived on the device
     def map_dense_enable(self, on=True, chunk_points=0):

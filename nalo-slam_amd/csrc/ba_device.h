@@ -232,5 +232,7 @@ void ba_launch_hist_update(hipStream_t s, const BADev& B, int scrub_only);
 void ba_launch_hist_remap(hipStream_t s, const BADev& B, int idx);
 void ba_launch_flag_points(hipStream_t s, const BADev& B, unsigned frame_mask, uint8_t* decision, float* idepth_hessian, int* counts, int* counts_next);
 void ba_launch_remove_flagged(hipStream_t s, const BADev& B);
+// residuals that exist per (host row, target row) of the resident slots: out[h * NALO_MAX_WINDOW + t], zero before; out_next (the other buffer) is zeroed for the next call
+void ba_launch_pair_count(hipStream_t s, const BADev& B, int* out, int* out_next);
 
 }  // namespace nalo

@@ -91,6 +91,7 @@ struct BAWindow {
     DevBuf<int> pt_numgood, snap_numgood; DevBuf<uint32_t> pt_last, snap_last;
     bool hist_set = false, snap_hist = false;                       // the window carries a history (dev.pt_numgood / dev.pt_last are set); so did it when the snapshot was taken
     DevBuf<uint8_t> flag_dec; DevBuf<float> flag_H; DevBuf<int> flag_counts; int flag_buf = 0;   // the decision kernel's outputs; counts: two buffers of 4 * NALO_MAX_WINDOW, the idle one zero
+    DevBuf<int> pair_cnt; int pair_buf = 0; HostBuf<int> pair_host;   // the graph's live counts (ba_graph_view): two tables of NALO_MAX_WINDOW^2, the idle one zero, and the pinned mirror
     bool flagged = false;                                           // pt_flags hold the decisions of a nalo_ba_flag_points nobody has consumed yet
     bool flag_full = false;                                         // that call left decision and idepth_hessian of every slot in flag_dec / flag_H (the map was on: nalo_map_enable)
     // the map: maxRelBaseline of the last linearizeAll(true) as it stood before an archiving nalo_ba_marginalize_flagged (its marginalisation pass swaps the relBS
@@ -960,6 +961,46 @@ int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V) {
     return NALO_OK;
 }
 
+int ba_graph_view(nalo_ctx* c, bool count, GraphWindowView* V) {
+    if (!c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_map_graph: no window");
+    BAWindow& w = *c->ba;
+    V->W = w.W; V->sharded = w.hook != nullptr;
+    for (int i = 0; i < w.W; ++i) V->ids[i] = w.frames[i].frameID;
+    if (!count) return NALO_OK;
+    // between nalo_ba_marginalize_frame and the carry the arrays stand in the layout they were issued with: a remaining frame's counts sit under its device row
+    // and the departed rows are not read - what FullSystem::marginalizeFrame's drops leave (FullSystemMarginalize.cpp:155-170)
+    if ((!w.points_set && !w.carry_ok) || (int)w.row_of.size() != w.W)
+        return fail(c, NALO_ERR_STATE, "nalo_map_graph: the window's points are neither set nor carriable (issue or carry the window first)");
+    if (w.hook) return fail(c, NALO_ERR_STATE, "nalo_map_graph: the window is sharded (a rank holds only its own points)");
+    std::memset(V->act, 0, sizeof(V->act));
+    if (w.dev.nblocks == 0) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "map_graph");
+    constexpr int kTab = NALO_MAX_WINDOW * NALO_MAX_WINDOW;
+    if (!w.pair_cnt.p) {
+        NALO_HIP(c, w.pair_cnt.reserve(2 * kTab)); NALO_HIP(c, w.pair_host.reserve(kTab));
+        NALO_HIP(c, hipMemsetAsync(w.pair_cnt.p, 0, 2 * kTab * 4, c->stream)); w.pair_buf = 0;
+    }
+    int* const cnt = w.pair_cnt.p + w.pair_buf * kTab;
+    w.pair_buf ^= 1;
+    {
+        ProfScope ps(c, "ba_pair_count");
+        ba_launch_pair_count(c->stream, w.dev, cnt, w.pair_cnt.p + w.pair_buf * kTab);
+    }
+    NALO_HIP(c, hipGetLastError());
+    NALO_HIP(c, hipMemcpyAsync(w.pair_host.p, cnt, kTab * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < w.W; ++i) for (int j = 0; j < w.W; ++j) V->act[i * NALO_MAX_WINDOW + j] = w.pair_host.p[w.row_of[i] * NALO_MAX_WINDOW + w.row_of[j]];
+    return NALO_OK;
+}
+
+// while the graph is on a window frame needs a frame_id >= 0 (the reference asserts it where it reads the keys, PangolinDSOViewer.cpp:542)
+static int graph_check_ids(nalo_ctx* c, const char* who, int W, const nalo_frame_state* frames) {
+    if (!graph_on(c)) return NALO_OK;
+    for (int i = 0; i < W; ++i) if (frames[i].frame_id < 0) return fail(c, NALO_ERR_ARG, std::string(who) + ": the graph is on and a frame has a negative frame_id");
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -1037,6 +1078,11 @@ static int window_frames(nalo_ctx* c, int W, const nalo_frame_state* frames, con
     NALO_HIP(c, w.stitched_host.reserve(w.lay.host_size, hipHostMallocMapped));
     w.stitched_host.p[w.lay.flag] = -1.0; w.pub_seq = 0;
     ++w.frames_epoch;
+    if (graph_on(c)) {                                               // EnergyFunctional::insertFrame's pairs (EnergyFunctional.cpp:453-458), for the frames that are new to the table
+        int ids[NALO_MAX_WINDOW];
+        for (int i = 0; i < W; ++i) ids[i] = w.frames[i].frameID;
+        graph_add_frames(c, W, ids);
+    }
     return NALO_OK;
 }
 // ... and what follows once the point layout of the window is known: thresholds, adjoints, precalc values
@@ -1051,6 +1097,7 @@ static int window_finish(nalo_ctx* c) {
 
 int nalo_ba_set_window(nalo_ctx* c, int W, const nalo_frame_state* frames, const double calib[4], const double calib_zero[4]) {
     if (!c || !frames || !calib || W < 2 || W > NALO_MAX_WINDOW) return fail(c, NALO_ERR_ARG, "nalo_ba_set_window: bad argument");
+    { const int rg = graph_check_ids(c, "nalo_ba_set_window", W, frames); if (rg) return rg; }
     NALO_HIP(c, hipSetDevice(c->device));
     if (!c->ba) c->ba = new BAWindow();
     BAWindow& w = *c->ba;
@@ -1490,6 +1537,11 @@ static int marginalize_marked(nalo_ctx* c, double* M, double* Mb, double* Msc, d
     unpack_system(w, w.stitched_host.p + w.lay.top, m.data(), mb.data());
     unpack_system(w, w.stitched_host.p + w.lay.sc, ms.data(), mbs.data());
     int nres = 0; misc_totals(w, nullptr, &nres); w.resInM += nres;
+    if (graph_on(c)) {                                               // connectivityMap's [1]++ per residual of :633: the same counts, pair by pair
+        int id_of_row[NALO_MAX_WINDOW];
+        for (int i = 0; i < w.W; ++i) id_of_row[w.row_of.empty() ? i : w.row_of[i]] = w.frames[i].frameID;
+        graph_add_marg(c, w.W, id_of_row, w.stitched_host.p + w.lay.misc);
+    }
     for (size_t i = 0; i < (size_t)n * n; ++i) w.HM[i] += kMargWeightFac * (m[i] - ms[i]);  // EnergyFunctional.cpp:654-669
     for (int i = 0; i < n; ++i) w.bM[i] += kMargWeightFac * (mb[i] - mbs[i]);
     if (M) std::memcpy(M, m.data(), m.size() * 8); if (Mb) std::memcpy(Mb, mb.data(), n * 8);
@@ -2137,6 +2189,7 @@ int nalo_ba_carry_window(nalo_ctx* c, const nalo_frame_state* entering, int inse
     if (W > NALO_MAX_WINDOW || W < 2) return fail(c, NALO_ERR_ARG, "nalo_ba_carry_window: the window would hold more than NALO_MAX_WINDOW (or fewer than 2) frames");
     if (entering && (entering->slot < 0 || entering->slot >= (int)c->slots.size() || !c->slots[entering->slot].valid))
         return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the entering frame's slot has no pyramid");
+    if (entering) { const int rg = graph_check_ids(c, "nalo_ba_carry_window", 1, entering); if (rg) return rg; }
     const int n_act = insert_activated ? c->act_pend_n : 0;
     if (insert_activated) {
         if (entering) return fail(c, NALO_ERR_STATE, "nalo_ba_carry_window: the reference appends the frame, activates, then inserts: carry the entering frame first, insert in a second call");
@@ -2251,6 +2304,7 @@ int nalo_ba_window_from_initializer(nalo_ctx* c, nalo_init_window_args* a) {
     if (!std::isfinite(a->desired_point_density) || !(a->desired_point_density > 0)) return fail(c, NALO_ERR_ARG, std::string(who) + ": desired_point_density must be finite and positive");
     if (a->first.slot != V.slot_first) return fail(c, NALO_ERR_ARG, std::string(who) + ": first.slot is not the slot nalo_init_set_first was given");
     if (a->first.slot == a->entering.slot) return fail(c, NALO_ERR_ARG, std::string(who) + ": the entering frame needs a slot of its own");
+    for (const nalo_frame_state* f : {&a->first, &a->entering}) { const int rg = graph_check_ids(c, who, 1, f); if (rg) return rg; }
     for (const int s : {a->first.slot, a->entering.slot})
         if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid) return fail(c, NALO_ERR_STATE, std::string(who) + ": frame slot has no pyramid");
     if (c->xchg_failed) return fail(c, NALO_ERR_STATE, std::string(who) + ": a cross-rank sum of this context failed earlier; build the window on a new context");

@@ -183,6 +183,33 @@ static int map_dense_send(nalo_ctx* c, DenseArchive& m, const DenseFrame& f, Map
     return NALO_OK;
 }
 
+// ---- the keyframe graph: EnergyFunctional::connectivityMap (EnergyFunctional.cpp:423, 453-458, 493, 628-634). The host keeps the keys and [1]; [0] is counted
+// from the resident slots when the graph is read (ba_graph_view)
+static uint64_t graph_key(int host_id, int target_id) { return ((uint64_t)host_id << 32) + (uint64_t)target_id; }
+void graph_add_frames(nalo_ctx* c, int W, const int* ids) {
+    for (int i = 0; i < W; ++i) for (int j = 0; j < W; ++j) c->graph_marg.emplace(graph_key(ids[i], ids[j]), 0);      // an existing entry keeps its count
+}
+void graph_add_marg(nalo_ctx* c, int W, const int* id_of_row, const double* misc) {
+    for (int h = 0; h < W; ++h) for (int t = 0; t < W; ++t) {
+        const int n = (int)(misc[2 * (h + t * W)] + 0.5);
+        if (n > 0) c->graph_marg[graph_key(id_of_row[h], id_of_row[t])] += n;
+    }
+}
+// every entry in key order with [0] from the window's count; NALO_ERR_STATE while off or without resident points
+static int graph_entries(nalo_ctx* c, const char* who, std::vector<nalo_graph_edge>& E) {
+    if (!c->graph_on) return fail(c, NALO_ERR_STATE, std::string(who) + ": the graph is off (nalo_map_graph_enable)");
+    GraphWindowView V;
+    { const int rc = ba_graph_view(c, true, &V); if (rc) return rc; }
+    std::map<uint64_t, int> act;
+    for (int i = 0; i < V.W; ++i) for (int j = 0; j < V.W; ++j) act[graph_key(V.ids[i], V.ids[j])] = V.act[i * NALO_MAX_WINDOW + j];
+    E.clear(); E.reserve(c->graph_marg.size());
+    for (const auto& kv : c->graph_marg) {
+        const auto a = act.find(kv.first);
+        E.push_back({(int)(kv.first >> 32), (int)(kv.first & 0xFFFFFFFFu), a == act.end() ? 0 : a->second, kv.second});
+    }
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -207,6 +234,11 @@ int nalo_map_enable(nalo_ctx* c, int on, int chunk_points) {
 int nalo_map_reset(nalo_ctx* c) {
     if (!c) return NALO_ERR_ARG;
     if (c->dmap) { c->dmap->frames.clear(); c->dmap->filled = 0; }
+    if (c->graph_on) {                                                      // an EnergyFunctional that has just inserted the window's frames
+        c->graph_marg.clear();
+        GraphWindowView V;
+        if (ba_graph_view(c, false, &V) == NALO_OK) graph_add_frames(c, V.W, V.ids);
+    }
     if (!c->map) return NALO_OK;
     c->map->frames.clear(); c->map->filled = 0; c->map->pending = false;
     return NALO_OK;
@@ -329,6 +361,49 @@ int nalo_map_frame_cloud(nalo_ctx* c, nalo_map_cloud_args* a) {
     if (ns < 0 || 8 * (size_t)ns > nv) return fail(c, NALO_ERR_HIP, "nalo_map_frame_cloud: the device counted more survivors than the frame has records");
     a->n = 8 * ns;
     std::memcpy(a->xyz, m.cxyz_h.p, 3 * (size_t)a->n * 4); std::memcpy(a->rgb, m.crgb_h.p, 3 * (size_t)a->n);
+    return NALO_OK;
+}
+
+int nalo_map_graph_enable(nalo_ctx* c, int on) {
+    if (!c) return NALO_ERR_ARG;
+    if (!on) { c->graph_on = false; return NALO_OK; }
+    if (c->xchg_failed) return fail(c, NALO_ERR_STATE, "nalo_map_graph_enable: a cross-rank sum of this context failed earlier");
+    GraphWindowView V;
+    const bool window = ba_graph_view(c, false, &V) == NALO_OK;
+    if (window && V.sharded) return fail(c, NALO_ERR_STATE, "nalo_map_graph_enable: the window is sharded (a rank holds only its own points)");
+    if (window) for (int i = 0; i < V.W; ++i) if (V.ids[i] < 0) return fail(c, NALO_ERR_ARG, "nalo_map_graph_enable: a window frame has a negative frame_id");
+    c->graph_on = true;
+    if (window) graph_add_frames(c, V.W, V.ids);
+    return NALO_OK;
+}
+
+int nalo_map_graph(nalo_ctx* c, nalo_graph_edge* edges, int cap, int* n) {
+    if (!c || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_graph: bad argument");
+    std::vector<nalo_graph_edge> E;
+    { const int rc = graph_entries(c, "nalo_map_graph", E); if (rc) return rc; }
+    *n = (int)E.size();
+    if (cap < *n || (*n > 0 && !edges)) return fail(c, NALO_ERR_ARG, "nalo_map_graph: cap is smaller than the number of entries");
+    std::copy(E.begin(), E.end(), edges);
+    return NALO_OK;
+}
+
+int nalo_map_graph_connections(nalo_ctx* c, nalo_graph_connection* conn, int cap, int* n) {
+    if (!c || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_graph_connections: bad argument");
+    std::vector<nalo_graph_edge> E;
+    { const int rc = graph_entries(c, "nalo_map_graph_connections", E); if (rc) return rc; }
+    // PangolinDSOViewer::publishGraph (PangolinDSOViewer.cpp:528-571): keys with host < target in key order, the backward pair from the inverse key
+    std::map<uint64_t, const nalo_graph_edge*> by_key;
+    for (const nalo_graph_edge& e : E) by_key[graph_key(e.host_id, e.target_id)] = &e;
+    std::vector<nalo_graph_connection> C;
+    for (const nalo_graph_edge& e : E) {
+        if (e.host_id >= e.target_id) continue;
+        const auto inv = by_key.find(graph_key(e.target_id, e.host_id));
+        const nalo_graph_edge* b = inv == by_key.end() ? nullptr : inv->second;      // (pairs are created in both directions: the reference's .at() never throws)
+        C.push_back({e.host_id, e.target_id, e.act, b ? b->act : 0, e.marg, b ? b->marg : 0});
+    }
+    *n = (int)C.size();
+    if (cap < *n || (*n > 0 && !conn)) return fail(c, NALO_ERR_ARG, "nalo_map_graph_connections: cap is smaller than the number of connections");
+    std::copy(C.begin(), C.end(), conn);
     return NALO_OK;
 }
 

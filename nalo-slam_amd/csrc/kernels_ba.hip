@@ -1304,4 +1304,32 @@ __global__ __launch_bounds__(256) void ba_remove_flagged_kernel(BADev B) {
 }
 void ba_launch_remove_flagged(hipStream_t s, const BADev& B) { ba_remove_flagged_kernel<<<(B.Ppad + 255) / 256, 256, 0, s>>>(B); }
 
+// EnergyFunctional::connectivityMap's [0] (EnergyFunctional.cpp:423, 493): the residual objects that exist per (host, target), in any state, counted from the
+// resident slots: out[h * NALO_MAX_WINDOW + t] = slots with RS_EXISTS of the valid points of host row h in target row t. One lane per point slot as in
+// ba_flag_points_kernel (a block holds one host; padding and removed points carry no PT_VALID). Per target a wave's ballot + popcount goes to LDS, and after the
+// barrier lane t adds the four waves' counts: at most one integer atomic per (block, target), so the sums do not depend on the order of arrival. The first
+// workgroup zeroes the table of the NEXT call (two buffers, NALO_MAX_WINDOW^2 = 256 words = one per lane): the path holds no fill.
+__global__ __launch_bounds__(256) void ba_pair_count_kernel(BADev B, int* __restrict__ out, int* __restrict__ out_next) {
+    static_assert(kBlk == NALO_MAX_WINDOW * NALO_MAX_WINDOW, "one lane per word of the next call's table");
+    __shared__ int wave_cnt[kBlk / 64][NALO_MAX_WINDOW];
+    const int d = blockIdx.x * kBlk + threadIdx.x;                      // grid = nblocks: d < Ppad
+    if (blockIdx.x == 0) out_next[threadIdx.x] = 0;
+    const int h = B.blk_host[blockIdx.x];
+    const bool valid = (B.pt_flags[d] & PT_VALID) != 0;
+    const int wave = threadIdx.x >> 6;
+    const bool lead = (threadIdx.x & 63) == 0;
+    for (int t = 0; t < B.W; ++t) {                                     // t-major slots: every load is coalesced
+        const uint8_t st = B.rs_state[(size_t)t * B.Ppad + d];
+        const int n = __popcll(__ballot(valid && (st & RS_EXISTS)));
+        if (lead) wave_cnt[wave][t] = n;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < B.W) {
+        const int t = threadIdx.x;
+        const int n = wave_cnt[0][t] + wave_cnt[1][t] + wave_cnt[2][t] + wave_cnt[3][t];
+        if (n) atomicAdd(&out[h * NALO_MAX_WINDOW + t], n);
+    }
+}
+void ba_launch_pair_count(hipStream_t s, const BADev& B, int* out, int* out_next) { ba_pair_count_kernel<<<B.nblocks, kBlk, 0, s>>>(B, out, out_next); }
+
 }  // namespace nalo

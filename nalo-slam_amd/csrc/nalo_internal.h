@@ -178,6 +178,10 @@ struct nalo_ctx {
     nalo::Initializer* init = nullptr;       // two-frame initialiser state (host_init.hip)
     nalo::MapArchive* map = nullptr;         // the archive of removed points and the clouds made from it (host_map.hip); NULL until nalo_map_enable
     nalo::DenseArchive* dmap = nullptr;      // the dense map: FrameHessian::mapPoints on the device (host_map.hip); NULL until nalo_map_dense_enable
+    // the keyframe graph (nalo_map_graph_*, host_map.hip): EnergyFunctional::connectivityMap's keys, (host frame_id << 32) + target frame_id, with the count [1] of
+    // marginalised residuals; the count [0] of live residuals is taken from the resident slots when the graph is read
+    bool graph_on = false;
+    std::map<uint64_t, int> graph_marg;
     nalo_settings set = {1, nalo::kAffineOptModeA, nalo::kAffineOptModeB, 1};   // util/settings.cpp:71,128-129,74
 
     // ---- host wall-clock accounting (NALO_HOST_TIMING=1, read by nalo_create, prints it at nalo_destroy)
@@ -332,6 +336,15 @@ int map_append_patch(nalo_ctx* c);
 int map_append_fetch(nalo_ctx* c);
 void map_append_commit(nalo_ctx* c);
 void map_destroy(nalo_ctx* c);
+// ---- the keyframe graph (host_map.hip). add_frames: the pairs EnergyFunctional::insertFrame creates, for every ordered pair of ids without an entry; add_marg:
+// marginalizePointsF's [1]++ from the per-(host row, target row) residual counts of a marginalisation pass (misc[2 (h + t W)], id_of_row: frame_id per device row)
+inline bool graph_on(const nalo_ctx* c) { return c->graph_on; }
+void graph_add_frames(nalo_ctx* c, int W, const int* ids);
+void graph_add_marg(nalo_ctx* c, int W, const int* id_of_row, const double* misc);
+// host_ba.hip: the window as the graph reads it. ids: frame_id of the frames nalo_ba_get_frames returns now; act[i * NALO_MAX_WINDOW + j]: the slots with RS_EXISTS of
+// valid points hosted by frame i in the row of frame j (one launch, one 1 KB copy, one wait). sharded / W only when count is false.
+struct GraphWindowView { int W; int ids[NALO_MAX_WINDOW]; bool sharded; int act[NALO_MAX_WINDOW * NALO_MAX_WINDOW]; };
+int ba_graph_view(nalo_ctx* c, bool count, GraphWindowView* V);
 // host_ba.hip: the window as nalo_map_frame_cloud reads it. widx = -1: frame_id is not in the window; pts_ok: the point arrays stand (kmap: the frame's seg entries, n_valid of them valid). ci: {fxi, fyi, cxi, cyi} of the CalibHessian (value_scaledi)
 struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4]; bool sharded; };
 int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
