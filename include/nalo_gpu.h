@@ -909,6 +909,74 @@ int nalo_map_graph(nalo_ctx* ctx, nalo_graph_edge* edges, int cap, int* n);
 int nalo_map_graph_connections(nalo_ctx* ctx, nalo_graph_connection* conn, int cap, int* n);
 
 /* ------------------------------------------------------------------------------------------------
+ * The window panel: FullSystem::debugPlot (FullSystem/FullSystemDebugStuff.cpp:109-358, called from makeKeyFrame at FullSystem.cpp:1412 with
+ * setting_render_renderWindowFrames = true and freeDebugParam5 = 1 by default) on the device: one image per window frame, the frame's level-0 irradiance (the
+ * slot's planar I[0]) with a ring per point, the argument of IOWrap::displayImageStitch. Everything it reads is resident: the window's valid points, the archive
+ * of removed points (nalo_map_enable), the resident immature set (nalo_imm_resident_*). The call has no side effect on window, archive, immature set, tracker or
+ * graph, and a context that never calls it enqueues exactly what it did before. Kernels on the context's stream, ONE wait; the images come up through a pinned
+ * block of the context and reach bgr only on success.
+ *   Frames    bit i of frame_mask selects window frame i (the order of nalo_ba_get_frames); 0 selects every frame. The selected frames are painted in window
+ *             order: n_frames images of h x w x 3 bytes, frame_id[j] the id of image j.
+ *   Base      every mode (:180-185): c = (int)(I * 0.9f), 255 if larger, the byte (unsigned char)c on all three channels - nalo_trk_depth_image's base image, with
+ *             its conversions (saturating float -> int, NaN -> 0, a negative c wraps).
+ *   Lists     of a window frame, in painting order. active: its valid window points in submission order (status 1 of nalo_map_frame_cloud), idepth_scaled = the
+ *             current inverse depth. marginalised / out: its status-2 / status-3 archive records in archive order, idepth_scaled = the record's idepth; both empty
+ *             without an archive. immature: the resident points whose host_idx is the frame's window index, in storage order; empty without a resident set.
+ *   Ring      setPixelCirc((int)(u + 0.5f), (int)(v + 0.5f), colour) (MinimalImage.h:112-126): the 40 pixels at Chebyshev distance 2 or 3 from the centre, not
+ *             the centre and not its eight neighbours.
+ *   Modes     mode = (int)(freeDebugParam5 + 0.5f). 0: active and marginalised makeRainbow3B(idepth_scaled), out white. 1: active rainbow, marginalised black,
+ *             out white. 2, 8, 9: the base image only (no branch matches, as in the reference). 3: immature points with status IPS_GOOD, IPS_SKIPPED or
+ *             IPS_BADCONDITION, black when idepth_max is not finite, else makeRainbow3B((idepth_min + idepth_max) * 0.5f). 4: the six status colours of :245-256.
+ *             5: immature points that are not IPS_UNINITIALIZED, d = quality_scale * (sqrtf(quality) - 1) clamped to [0, 1] (sqrtf correctly rounded), colour
+ *             Vec3b(0, d * 255, (1 - d) * 255). 6 (PointHessian::my_type, which the resident window does not hold): NALO_ERR_UNSUPPORTED. 7: active
+ *             makeJet3B((idepth_scaled - minID) / (maxID - minID)), marginalised black; out points are not drawn but count in allID.
+ *   Rainbow   makeRainbow3B (globalFuncs.h:334-348): id *= rainbow_scale (freeDebugParam3); !(id > 0) is white; icP = (int)id, ifP = id - icP, icP % 3 selects
+ *             the branch; bytes 255 * (1 - ifP), 255 * ifP in float, truncated.
+ *   Overlap   the reference paints the lists one after another, so the LAST writer of a pixel wins: list order (active, marginalised, out; immature alone), and
+ *             inside a list ascending index. Exactly so here, on every run: a source raises a per-pixel key to its position in the frame's painting order with
+ *             an integer maximum, and a second pass paints the winner. No float atomic, no atomic append.
+ *   Mode 7    range (:118-158): allID = idepth_scaled of every active, marginalised and out point of ALL window frames, whatever frame_mask says; n_values is its
+ *             size. With n = size - 1, minID / maxID are the order statistics at ranks (int)(n * 0.05) and (int)(n * 0.95), the products in double, found exactly
+ *             by a radix select on the float bit patterns (-0 orders before +0); nothing is sorted and the count does not visit the host. Smoothing against
+ *             minmax_io = {minIdJetVisDebug, maxIdJetVisDebug}, which stay with the caller (start them at -1 as FullSystem.cpp does): maxChange =
+ *             (float)(0.1 * (double)(max - min)), 1e5 when either stored value is < 0, the four ifs in the reference's order, minmax_io rewritten. NULL: no
+ *             smoothing, nothing written. minmax_io is read and written in mode 7 only.
+ *   sources   sources[j] = rings painted into image j from {immature, active, marginalised, out} (clipped rings included).
+ * DEFINED differences from the reference:
+ *   1. MinimalImage::at() has no bounds check; here ring pixels outside the image are skipped (a ring wholly outside paints nothing).
+ *   2. (int)(u + 0.5f) of a value int cannot hold saturates, NaN gives 0 (as the base image's conversion).
+ *   3. makeRainbow3B of an id that int cannot hold (>= 2^31, +inf) paints the white pixel x86 produces (INT_MIN % 3 matches no branch); a NaN argument of
+ *      makeJet3B paints white (as nalo_trk_depth_image).
+ *   4. The bytes of mode 5 are truncated toward zero, saturated to 0..255, NaN -> 0 (nalo_map_frame_cloud's conversion).
+ *   5. NaNs are left out of allID (the reference's std::sort is undefined on them).
+ *   6. The order INSIDE a list is the library's (submission / archive / storage order); the reference's pointHessians is permuted by swap-with-back - the
+ *      difference nalo_map_* documents. It shows only where two rings of one list with different colours overlap.
+ * Where to call it: after nalo_ba_marginalize_flagged the lists are those of the reference at FullSystem.cpp:1453. Right after nalo_ba_optimize (the reference's
+ *   place, :1412) the points removeOutliers has already moved to pointHessiansOut are still active in the chain - it decides them in nalo_ba_flag_points - and are
+ *   drawn coloured instead of white.
+ * Refusals, each leaving bgr, minmax_io and the context as they were. NALO_ERR_ARG: NULL ctx / args / bgr; mode outside 0..9; a frame_mask bit at or above the
+ *   window size; rainbow_scale or quality_scale not finite. NALO_ERR_UNSUPPORTED: mode 6; more sources than a 32-bit key can index. NALO_ERR_STATE: no window; the
+ *   window's point arrays are unset (between nalo_ba_marginalize_frame and the carry); a selected frame's slot without a pyramid; a sharded window (a rank holds
+ *   only its own points); mode 7 with an empty allID (the reference indexes an empty vector; n_values = 0). NALO_ERR_HIP: a cross-rank exchange of this context
+ *   failed earlier.
+ * Out of scope: debugPlotTracking, CoarseInitializer::debugPlot, displayImageStitch's tiling, the dead `debugSaveImages && false` block.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_window_plot_args {
+    int      mode;            /* (int)(freeDebugParam5 + 0.5f) of the reference: 0..9 */
+    float    rainbow_scale;   /* freeDebugParam3 (settings.cpp:191), 1 in the reference */
+    float    quality_scale;   /* freeDebugParam1 (mode 5), 1 in the reference */
+    unsigned frame_mask;      /* bit i = window frame i is painted; 0 = every frame */
+    float*   minmax_io;       /* mode 7: {minIdJetVisDebug, maxIdJetVisDebug}, caller-kept, start at -1 (FullSystem.cpp); NULL = no smoothing */
+    uint8_t* bgr;             /* out: [n_frames][h][w][3], selected frames in window order, bytes of a pixel in Vec3b's order */
+    int      n_frames;        /* out */
+    int      frame_id[NALO_MAX_WINDOW];      /* out: of the painted frames */
+    int      sources[NALO_MAX_WINDOW][4];    /* out: per painted frame, sources drawn from {immature, active, marginalised, out} */
+    int      n_values;        /* out, mode 7: allID.size() */
+    float    min_new, max_new, min_used, max_used;   /* out, mode 7, as in nalo_depth_image_args */
+} nalo_window_plot_args;
+int nalo_map_window_plot(nalo_ctx* ctx, nalo_window_plot_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * densemap=1: DenseMapping::updateMap (FullSystem/MapPoint.cpp:234-332, call site FullSystem.cpp:1488-1496) in one call, and FrameHessian::mapPoints as a
  * device archive beside the sparse one. The per-cluster route (nalo_dense_fit_planes, then nalo_dense_make_map per cluster) stays as it is.
  *

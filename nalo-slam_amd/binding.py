@@ -37,7 +37,7 @@ EXPORTS = [
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
-    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections",
+    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
@@ -106,6 +106,13 @@ assert DENSE_RUN_DTYPE.itemsize == 32 and DENSE_POINT_DTYPE.itemsize == 16
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
+                ("min_used", C.c_float), ("max_used", C.c_float)]
+
+
+class WindowPlotArgs(C.Structure):
+    """nalo_window_plot_args (include/nalo_gpu.h)"""
+    _fields_ = [("mode", C.c_int), ("rainbow_scale", C.c_float), ("quality_scale", C.c_float), ("frame_mask", C.c_uint), ("minmax_io", c_fp), ("bgr", c_u8p),
+                ("n_frames", C.c_int), ("frame_id", C.c_int * 16), ("sources", (C.c_int * 4) * 16), ("n_values", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
                 ("min_used", C.c_float), ("max_used", C.c_float)]
 
 
@@ -204,6 +211,7 @@ def load():
     L.nalo_map_graph_enable.argtypes = [vp, C.c_int]
     L.nalo_map_graph.argtypes = [vp, vp, C.c_int, c_ip]
     L.nalo_map_graph_connections.argtypes = [vp, vp, C.c_int, c_ip]
+    L.nalo_map_window_plot.argtypes = [vp, C.POINTER(WindowPlotArgs)]
     L.nalo_dense_update_map.argtypes = [vp, C.c_int, C.POINTER(PlaneFitArgs), c_dp, C.c_int, vp, vp, c_ip, c_ip]
     L.nalo_map_dense_enable.argtypes = [vp, C.c_int, C.c_int]
     L.nalo_map_dense_counts.argtypes = [vp, C.c_int, c_ip, c_ip]
@@ -777,6 +785,25 @@ class Context:
             a.draws, a.n_draws = (None, 0) if d is None else (_i(d), len(d))
             self._ck(self.L.nalo_map_frame_cloud(self.h_, C.byref(a)))
         return dict(xyz=xyz[:a.n], rgb=rgb[:a.n], records=np.array(list(a.records)), survivors=np.array(list(a.survivors)), n_needed=cap)
+
+    def map_window_plot(self, mode=1, frame_mask=0, minmax=None, rainbow_scale=1.0, quality_scale=1.0):
+        """FullSystem::debugPlot on the device (nalo_map_window_plot): one image per selected window frame. minmax: the caller's (minIdJetVisDebug,
+        maxIdJetVisDebug) pair for mode 7, None = no smoothing. Returns a dict: bgr (n_frames, h, w, 3) uint8, frame_id [n_frames], sources [n_frames][4]
+        (immature, active, marginalised, out), minmax (the rewritten pair as float32, or None), n_values, min_new, max_new, min_used, max_used (float32)"""
+        a = WindowPlotArgs()
+        W = max(self.W, 1)
+        nf = bin(frame_mask).count("1") if frame_mask else W
+        bgr = np.zeros((max(nf, 1), self.h, self.w, 3), np.uint8)
+        mm = None if minmax is None else np.array(minmax, np.float32).reshape(2)
+        a.mode, a.rainbow_scale, a.quality_scale, a.frame_mask = int(mode), float(rainbow_scale), float(quality_scale), int(frame_mask)
+        a.minmax_io, a.bgr = _f(mm), _u8(bgr)
+        self._ck(self.L.nalo_map_window_plot(self.h_, C.byref(a)))
+        n = a.n_frames
+        out = {"bgr": bgr[:n], "frame_id": [a.frame_id[j] for j in range(n)], "sources": np.array([list(a.sources[j]) for j in range(n)], np.int32).reshape(n, 4),
+               "minmax": mm, "n_values": a.n_values}
+        for k in ("min_new", "max_new", "min_used", "max_used"):
+            out[k] = np.float32(getattr(a, k))
+        return out
 
     # ---- the keyframe graph: EnergyFunctional::connectivityMap from the device chain
     def map_graph_enable(self, on=True):

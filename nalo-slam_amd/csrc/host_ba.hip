@@ -961,6 +961,30 @@ int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V) {
     return NALO_OK;
 }
 
+int ba_plot_view(nalo_ctx* c, PlotWindowView* V) {
+    if (!c->ba || c->ba->W < 1) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: no window");
+    BAWindow& w = *c->ba;
+    *V = PlotWindowView{};
+    V->W = w.W; V->sharded = w.hook != nullptr; V->pts_ok = w.points_set && !w.hook;
+    for (int i = 0; i < w.W; ++i) { V->frame_id[i] = w.frames[i].frameID; V->slot[i] = w.frames[i].slot; }
+    if (!V->pts_ok) return NALO_OK;
+    V->flags = w.pt_flags.p; V->geo = w.pt_geo.p;
+    if (w.P == 0) return NALO_OK;
+    { const int rc = ref_kmap_build(c, w); if (rc) return rc; }
+    int first[NALO_MAX_WINDOW], frame_of_row[NALO_MAX_WINDOW];
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) first[i] = frame_of_row[i] = -1;
+    for (int i = 0; i < w.W; ++i) { const int row = w.row_of.empty() ? i : w.row_of[i]; if (row >= 0 && row < NALO_MAX_WINDOW) frame_of_row[row] = i; }
+    for (int k = 0; k < w.P; ++k) {                                            // the map is ordered by device row: a frame's entries are one segment
+        const int d = w.ref_kmap_h[k], row = w.blk_host_h[d / kBlk];
+        const int i = row >= 0 && row < NALO_MAX_WINDOW ? frame_of_row[row] : -1;
+        if (i < 0) continue;
+        if (first[i] < 0) first[i] = k;
+        ++V->seg[i]; V->n_valid[i] += (w.flags_h[d] & PT_VALID) != 0;
+    }
+    for (int i = 0; i < w.W; ++i) if (V->seg[i]) V->kmap[i] = w.ref_kmap.p + first[i];
+    return NALO_OK;
+}
+
 int ba_graph_view(nalo_ctx* c, bool count, GraphWindowView* V) {
     if (!c->ba || c->ba->W < 2) return fail(c, NALO_ERR_STATE, "nalo_map_graph: no window");
     BAWindow& w = *c->ba;

@@ -5,6 +5,7 @@
 #include "map_point_math.h"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 
 namespace nalo {
@@ -26,6 +27,10 @@ struct MapArchive {
     HostBuf<MapSeg> seg_h; DevBuf<MapSeg> seg_d; HostBuf<int> draws_h; DevBuf<int> draws_d, qcnt;
     DevBuf<double> wxyz; HostBuf<double> wxyz_h;
     DevBuf<float> cxyz; DevBuf<uint8_t> crgb; HostBuf<float> cxyz_h; HostBuf<uint8_t> crgb_h; HostBuf<int> stats_h;
+    // the window panel (nalo_map_window_plot): segment table (pinned staging + device), the key plane (zero between calls: the resolve pass leaves it so), the sources'
+    // colours, the images, the select's results, the ring counters (two buffers, the idle one zero) and the pinned block results, counters and images come up through
+    HostBuf<PlotSeg> wp_seg_h; DevBuf<PlotSeg> wp_seg_d; DevBuf<unsigned> wp_key, wp_col, wp_res; DevBuf<uint8_t> wp_bgr; DevBuf<int> wp_cnt; int wp_cnt_buf = 0;
+    HostBuf<uint8_t> wp_host; bool wp_key_clean = false;
 };
 
 bool map_on(const nalo_ctx* c) { return c->map && c->map->on; }
@@ -361,6 +366,103 @@ int nalo_map_frame_cloud(nalo_ctx* c, nalo_map_cloud_args* a) {
     if (ns < 0 || 8 * (size_t)ns > nv) return fail(c, NALO_ERR_HIP, "nalo_map_frame_cloud: the device counted more survivors than the frame has records");
     a->n = 8 * ns;
     std::memcpy(a->xyz, m.cxyz_h.p, 3 * (size_t)a->n * 4); std::memcpy(a->rgb, m.crgb_h.p, 3 * (size_t)a->n);
+    return NALO_OK;
+}
+
+// FullSystem::debugPlot (FullSystemDebugStuff.cpp:109-358) for the frames of the window (kernels_window_plot.hip). Everything is enqueued on the main stream; results,
+// counters and images come up through one pinned block behind ONE wait and reach the caller only when the call succeeds.
+int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
+    if (!c || !a || !a->bgr) return fail(c, NALO_ERR_ARG, "nalo_map_window_plot: bad argument");
+    if (a->mode < 0 || a->mode > 9) return fail(c, NALO_ERR_ARG, "nalo_map_window_plot: mode outside 0..9");
+    if (!std::isfinite(a->rainbow_scale) || !std::isfinite(a->quality_scale)) return fail(c, NALO_ERR_ARG, "nalo_map_window_plot: rainbow_scale / quality_scale must be finite");
+    if (a->mode == 6) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_map_window_plot: mode 6 paints PointHessian::my_type, which is not part of the resident window");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_map_window_plot: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (!c->ba) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: no window");
+    NALO_HIP(c, hipSetDevice(c->device));
+    PlotWindowView V;
+    { const int rc = ba_plot_view(c, &V); if (rc) return rc; }
+    if (a->frame_mask >> V.W) return fail(c, NALO_ERR_ARG, "nalo_map_window_plot: frame_mask names a frame outside the window");
+    if (V.sharded) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: the window is sharded (a rank holds only its own points)");
+    if (!V.pts_ok) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: the window's points are unset: carry or re-issue the window first");
+    const unsigned mask = a->frame_mask ? a->frame_mask : (1u << V.W) - 1u;
+    WindowPlotDev D{};
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) D.out_of[i] = -1;
+    for (int i = 0; i < V.W; ++i) {
+        if (!(mask >> i & 1u)) continue;
+        const int s = V.slot[i];
+        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].I[0].p) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: a window frame's slot has no pyramid");
+        D.I[D.n_frames] = c->slots[s].I[0].p; D.out_of[i] = D.n_frames++;
+    }
+    HostTimer ht(c, "map_window_plot");
+    // the sources: a painted frame's sublist in painting order. Mode 7 lists every frame (allID does not know the mask)
+    const MapArchive* const arch = c->map;
+    const int mode = a->mode;
+    std::vector<PlotSeg> segs; long long total = 0;
+    if (mode == 3 || mode == 4 || mode == 5) {
+        if (c->imm_res_n > 0 && c->imm_res.p) { segs.push_back({nullptr, 0, c->imm_res_n, 0, 0, 0, 0}); total = c->imm_res_n; }
+    } else if (mode == 0 || mode == 1 || mode == 7) {
+        for (int i = 0; i < V.W; ++i) {
+            if (D.out_of[i] < 0 && mode != 7) continue;
+            const long long fstart = total;
+            if (D.out_of[i] >= 0) D.fstart[D.out_of[i]] = (int)std::min<long long>(fstart, INT32_MAX);
+            if (V.seg[i]) { segs.push_back({V.kmap[i], (int)total, V.seg[i], 1, i, (int)fstart, 0}); total += V.seg[i]; }
+            const MapFrame* f = nullptr;
+            if (arch) { const auto it = arch->frames.find(V.frame_id[i]); if (it != arch->frames.end()) f = &it->second; }
+            for (int kind = 2; f && kind <= 3 && total <= INT32_MAX; ++kind)
+                for (const MapRun& r : f->runs) {
+                    if (total > INT32_MAX) break;
+                    segs.push_back({arch->chunks[(size_t)(r.off / arch->chunk)].p + r.off % arch->chunk, (int)total, r.n, kind, i, (int)fstart, 0});
+                    total += r.n;
+                }
+            if (total > INT32_MAX) return fail(c, NALO_ERR_UNSUPPORTED, "nalo_map_window_plot: more sources than the key can index");
+        }
+    }
+    if (!c->map) c->map = new MapArchive();                                 // the call's scratch lives there (the archive stays off)
+    MapArchive& m = *c->map;
+    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = window_plot_padded_pixels(px);
+    const size_t nseg = std::max<size_t>(segs.size(), 1), off_cnt = 64, off_bgr = 512;
+    constexpr int kCnt = 4 * NALO_MAX_WINDOW;
+    NALO_HIP(c, m.wp_seg_h.reserve(nseg)); NALO_HIP(c, m.wp_seg_d.reserve(nseg)); NALO_HIP(c, m.wp_col.reserve(std::max<size_t>((size_t)total, 1)));
+    NALO_HIP(c, m.wp_bgr.reserve(3 * padded)); NALO_HIP(c, m.wp_res.reserve(kPlotResWords)); NALO_HIP(c, m.wp_host.reserve(off_bgr + 3 * px));
+    if (!m.wp_cnt.p) { NALO_HIP(c, m.wp_cnt.reserve(2 * kCnt)); NALO_HIP(c, hipMemsetAsync(m.wp_cnt.p, 0, 2 * kCnt * 4, c->stream)); m.wp_cnt_buf = 0; }
+    if (padded > m.wp_key.cap) m.wp_key_clean = false;
+    NALO_HIP(c, m.wp_key.reserve(padded));
+    if (!m.wp_key_clean) NALO_HIP(c, hipMemsetAsync(m.wp_key.p, 0, m.wp_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
+    m.wp_key_clean = false;
+    std::copy(segs.begin(), segs.end(), m.wp_seg_h.p);
+    if (!segs.empty()) NALO_HIP(c, hipMemcpyAsync(m.wp_seg_d.p, m.wp_seg_h.p, segs.size() * sizeof(PlotSeg), hipMemcpyHostToDevice, c->stream));
+    D.segs = m.wp_seg_d.p; D.nseg = (int)segs.size(); D.total = (int)total;
+    D.mode = mode; D.w = c->w; D.h = c->h; D.rainbow_scale = a->rainbow_scale; D.quality_scale = a->quality_scale;
+    D.imm = c->imm_res.p; D.immN = c->imm_res_n; D.flags = V.flags; D.geo = V.geo;
+    D.key = m.wp_key.p; D.col = m.wp_col.p; D.bgr = m.wp_bgr.p; D.res = m.wp_res.p;
+    D.cnt = m.wp_cnt.p + m.wp_cnt_buf * kCnt; m.wp_cnt_buf ^= 1; D.cnt_next = m.wp_cnt.p + m.wp_cnt_buf * kCnt;
+    const bool io = mode == 7 && a->minmax_io != nullptr;
+    D.io_min = io ? a->minmax_io[0] : 0.f; D.io_max = io ? a->minmax_io[1] : 0.f; D.have_io = io ? 1 : 0;
+    { const int rc = window_plot_launch(c, D); if (rc) return rc; }
+    m.wp_key_clean = true;
+    if (mode == 7) NALO_HIP(c, hipMemcpyAsync(m.wp_host.p, m.wp_res.p, kPlotResWords * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.wp_host.p + off_cnt, D.cnt, kCnt * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.wp_host.p + off_bgr, m.wp_bgr.p, 3 * px, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned res[kPlotResWords] = {};
+    if (mode == 7) {
+        std::memcpy(res, m.wp_host.p, sizeof(res));
+        if (res[0] == 0) { a->n_values = 0; return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: mode 7 and the window holds no point with an inverse depth"); }   // the reference indexes an empty vector here
+        if (io) std::memcpy(a->minmax_io, &res[5], 8);
+    }
+    a->n_values = (int)res[0];
+    std::memcpy(&a->min_new, &res[1], 4); std::memcpy(&a->max_new, &res[2], 4); std::memcpy(&a->min_used, &res[3], 4); std::memcpy(&a->max_used, &res[4], 4);
+    a->n_frames = D.n_frames;
+    int cnt[kCnt];
+    std::memcpy(cnt, m.wp_host.p + off_cnt, sizeof(cnt));
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) { a->frame_id[i] = 0; for (int k = 0; k < 4; ++k) a->sources[i][k] = 0; }
+    for (int i = 0; i < V.W; ++i) {
+        const int j = D.out_of[i];
+        if (j < 0) continue;
+        a->frame_id[j] = V.frame_id[i];
+        for (int k = 0; k < 4; ++k) a->sources[j][k] = cnt[4 * j + k];
+    }
+    std::memcpy(a->bgr, m.wp_host.p + off_bgr, 3 * px);
     return NALO_OK;
 }
 

@@ -16,6 +16,7 @@
 // Conversions the reference leaves undefined are DEFINED (include/nalo_gpu.h): float -> int of the grey value saturates with NaN -> 0 (__float2int_rz), a NaN id
 // (maxID == minID, 0 / 0) paints the white pixel x86 produces. The file is compiled without FMA contraction (build.py: NO_CONTRACT).
 #include "nalo_internal.h"
+#include "plot_device.h"
 
 namespace nalo {
 
@@ -32,44 +33,6 @@ constexpr int kDiSW = kDiTW + 6, kDiSH = kDiTH + 6;        // sources: 3 pixels 
 constexpr int kDiIW = kDiTW + 8, kDiIH = kDiTH + 8;        // idepth: one more for the stencil
 constexpr unsigned kDiPlot = 0x80000000u;
 
-// allID[(int)(n*0.05)] / allID[(int)(n*0.95)] with n = size - 1 (:1278-1281): the product in double, truncated. An empty map gives rank 0 (nothing is selected from it).
-__device__ __forceinline__ unsigned di_rank(unsigned total, int which) {
-    const int n = (int)total - 1;
-    return (unsigned)(int)((double)n * (which == 0 ? 0.05 : 0.95));
-}
-
-// the bin of hist[NBINS] whose running count passes k, and k's rank inside that bin (all 256 lanes call; s = 8 shared words). which >= 0: k is that rank of THIS
-// histogram's total. An empty histogram gives the last bin.
-template <int NBINS>
-__device__ __forceinline__ void di_search(const unsigned* __restrict__ hist, int which, unsigned k_in, unsigned* s, unsigned& total, unsigned& bin, unsigned& kres) {
-    constexpr int NB = NBINS / 256;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    unsigned cnt[NB], sum = 0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { cnt[j] = hist[tid * NB + j]; sum += cnt[j]; }
-    unsigned incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    __syncthreads();                                                             // the previous search's words have been read
-    if (lane == 63) s[wave] = incl;
-    if (tid == 0) { s[4] = (unsigned)(NBINS - 1); s[5] = 0u; }
-    __syncthreads();
-    unsigned wpre = 0;
-    total = s[0] + s[1] + s[2] + s[3];
-    for (int i = 0; i < wave; ++i) wpre += s[i];
-    const unsigned k = which >= 0 ? di_rank(total, which) : k_in;
-    const unsigned excl = wpre + incl - sum;
-    __syncthreads();                                                             // lane 0's defaults stand before the one finder overwrites them
-    if (excl <= k && k < excl + sum) {                                           // exactly one lane
-        unsigned run = excl; int b = 0; bool found = false;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) { if (!found && k < run + cnt[j]) { b = j; found = true; } if (!found) run += cnt[j]; }
-        s[4] = (unsigned)(tid * NB + b); s[5] = k - run;
-    }
-    __syncthreads();
-    bin = s[4]; kres = s[5];
-}
-
 template <int LEVEL>
 __global__ __launch_bounds__(256) void di_fill_kernel(const float* __restrict__ id, int n, unsigned* __restrict__ scr) {
     constexpr int NB = LEVEL == 2 ? kDiBinsC : kDiBinsAB, NH = LEVEL == 0 ? 1 : 2;
@@ -82,7 +45,7 @@ __global__ __launch_bounds__(256) void di_fill_kernel(const float* __restrict__ 
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             unsigned total, bin, kres;
-            di_search<kDiBinsAB>(scr + kDiOffA, r, 0u, s, total, bin, kres);
+            plot_search<kDiBinsAB>(scr + kDiOffA, r, 0u, s, total, bin, kres);
             if (blockIdx.x == 0 && tid == 0) { state[0] = total; state[1 + 2 * r] = bin; state[2 + 2 * r] = kres; }
             pre[r] = bin;
         }
@@ -92,7 +55,7 @@ __global__ __launch_bounds__(256) void di_fill_kernel(const float* __restrict__ 
         for (int r = 0; r < 2; ++r) {
             unsigned total, bin, kres;
             const unsigned binA = state[1 + 2 * r];                              // written by the previous launch of this stream
-            di_search<kDiBinsAB>(scr + kDiOffB + r * kDiBinsAB, -1, state[2 + 2 * r], s, total, bin, kres);
+            plot_search<kDiBinsAB>(scr + kDiOffB + r * kDiBinsAB, -1, state[2 + 2 * r], s, total, bin, kres);
             if (blockIdx.x == 0 && tid == 0) { state[5 + 2 * r] = bin; state[6 + 2 * r] = kres; }
             pre[r] = (binA << 11) | bin;
         }
@@ -126,7 +89,7 @@ __global__ __launch_bounds__(256) void di_final_kernel(unsigned* __restrict__ sc
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         unsigned total, bin, kres;
-        di_search<kDiBinsC>(scr + kDiOffC + r * kDiBinsC, -1, state[6 + 2 * r], s, total, bin, kres);
+        plot_search<kDiBinsC>(scr + kDiOffC + r * kDiBinsC, -1, state[6 + 2 * r], s, total, bin, kres);
         val[r] = (state[1 + 2 * r] << 20) | (state[5 + 2 * r] << 9) | bin;
     }
     if (threadIdx.x != 0) return;
@@ -152,26 +115,6 @@ __global__ __launch_bounds__(256) void di_final_kernel(unsigned* __restrict__ sc
     res[5] = __float_as_uint(io_min); res[6] = __float_as_uint(io_max); res[7] = 0u;
 }
 
-// makeJet3B (globalFuncs.h:350-367): byte k of the Vec3b in bits 8k..8k+7. The branch arithmetic is in double as written; every value lies in [0, 255], so the
-// truncation to unsigned char is the one of a non-negative int. NaN fails both comparisons, its (int) conversion is undefined there: DEFINED as white.
-__device__ __forceinline__ unsigned di_jet(float id) {
-    if (id <= 0) return 128u;
-    if (id >= 1) return 128u << 16;
-    if (id != id) return 0xFFFFFFu;
-    const int icP = (int)(id * 8);
-    const float ifP = (id * 8) - icP;
-    auto b = [](double v) { return (unsigned)(int)v; };
-    if (icP == 0) return b(255 * (0.5 + 0.5 * ifP));
-    if (icP == 1) return 255u | (b(255 * (0.5 * ifP)) << 8);
-    if (icP == 2) return 255u | (b(255 * (0.5 + 0.5 * ifP)) << 8);
-    if (icP == 3) return b(255 * (1 - 0.5 * ifP)) | (255u << 8) | (b(255 * (0.5 * ifP)) << 16);
-    if (icP == 4) return b(255 * (0.5 - 0.5 * ifP)) | (255u << 8) | (b(255 * (0.5 + 0.5 * ifP)) << 16);
-    if (icP == 5) return (b(255 * (1 - 0.5 * ifP)) << 8) | (255u << 16);
-    if (icP == 6) return (b(255 * (0.5 - 0.5 * ifP)) << 8) | (255u << 16);
-    if (icP == 7) return b(255 * (1 - 0.5 * ifP)) << 16;
-    return 0xFFFFFFu;
-}
-
 __global__ __launch_bounds__(256) void di_paint_kernel(const float* __restrict__ id, const float* __restrict__ I, int w, int h, const unsigned* __restrict__ scr, uint8_t* __restrict__ bgr) {
     __shared__ float t_id[kDiIH * kDiIW];
     __shared__ unsigned t_src[kDiSH * kDiSW];
@@ -195,7 +138,7 @@ __global__ __launch_bounds__(256) void di_paint_kernel(const float* __restrict__
             if (bp[-1] > 0) { sid += bp[-1]; nid++; }
             if (bp[kDiIW] > 0) { sid += bp[kDiIW]; nid++; }
             if (bp[-kDiIW] > 0) { sid += bp[-kDiIW]; nid++; }
-            if (bp[0] > 0 || nid >= 3) v = kDiPlot | di_jet(((sid / nid) - minID) / ((maxID - minID)));
+            if (bp[0] > 0 || nid >= 3) v = kDiPlot | plot_jet(((sid / nid) - minID) / ((maxID - minID)));
         }
         t_src[e] = v;
     }
@@ -207,9 +150,7 @@ __global__ __launch_bounds__(256) void di_paint_kernel(const float* __restrict__
         const int ly = (tid >> 6) + 4 * j, qy = y0 + ly;
         if (qy >= h) continue;
         const size_t q = (size_t)qy * w + qx;
-        int c = __float2int_rz(I[q] * 0.9f);                                     // `int c = dIp[0][i][0]*0.9f;` saturating, NaN -> 0
-        if (c > 255) c = 255;
-        unsigned col = (unsigned)(unsigned char)c * 0x010101u;
+        unsigned col = plot_grey(I[q]);                                          // `int c = dIp[0][i][0]*0.9f;` saturating, NaN -> 0
         // the last writer: sources from raster-last to raster-first, the first that plots wins
         bool hit = false;
         for (int dy = 3; dy >= -3 && !hit; --dy)

@@ -12,6 +12,7 @@
 #include "nalo_internal.h"
 #include "ba_device.h"
 #include "map_point_math.h"
+#include "plot_device.h"
 
 namespace nalo {
 
@@ -187,9 +188,6 @@ __device__ __forceinline__ bool map_cloud_keep(const MapCloudDev& C, const MapRe
     if (R.relbs < C.minRelBS) return false;
     return true;
 }
-// float -> byte of a colour: truncation toward zero, saturated to 0..255, NaN -> 0
-__device__ __forceinline__ unsigned map_color_byte(float x) { return !(x > 0.f) ? 0u : (x >= 255.f ? 255u : (unsigned)(int)x); }
-
 __global__ __launch_bounds__(256) void map_cloud_count_kernel(MapCloudDev C) {
     __shared__ int wsum[4];
     MapRec R;
@@ -227,7 +225,7 @@ __global__ __launch_bounds__(256) void map_cloud_write_kernel(MapCloudDev C) {
         // rand() / (float)RAND_MAX - 0.5f; without draws the library's no-jitter form: the bracket below is exactly 1
         const float jit = C.draws ? ((float)C.draws[j0 + pnt] / (float)2147483647 - 0.5f) : 0.f;
         vtx[3 * pnt + 2] = depth * (1 + 2 * fxi * jit);
-        cb[pnt] = map_color_byte(R.col[pnt]);
+        cb[pnt] = plot_byte(R.col[pnt]);
     }
     float4* ov = reinterpret_cast<float4*>(C.xyz + 3 * j0);                      // 96 bytes per record: 16-byte aligned
 #pragma unroll

@@ -348,6 +348,32 @@ int ba_graph_view(nalo_ctx* c, bool count, GraphWindowView* V);
 // host_ba.hip: the window as nalo_map_frame_cloud reads it. widx = -1: frame_id is not in the window; pts_ok: the point arrays stand (kmap: the frame's seg entries, n_valid of them valid). ci: {fxi, fyi, cxi, cyi} of the CalibHessian (value_scaledi)
 struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4]; bool sharded; };
 int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
+// ---- the window panel (nalo_map_window_plot; host_map.hip, kernels_window_plot.hip): FullSystem::debugPlot from resident data
+// host_ba.hip: the whole window as the painter reads it. Per window frame: frame_id, slot, its seg entries of the (host, submission) map and how many are valid
+struct PlotWindowView {
+    int W; bool pts_ok, sharded;
+    int frame_id[NALO_MAX_WINDOW], slot[NALO_MAX_WINDOW], seg[NALO_MAX_WINDOW], n_valid[NALO_MAX_WINDOW]; const int* kmap[NALO_MAX_WINDOW];
+    const uint8_t* flags; const float4* geo;
+};
+int ba_plot_view(nalo_ctx* c, PlotWindowView* V);
+// the sources: a virtual list of segments, a frame's in the reference's painting order (its kmap segment, its archive runs once for status 2 and once for status 3), so
+// that a source's position in its frame's sublist IS its priority. kind as MapSeg's; kind 0 is the whole resident set once (fstart 0, the frame from host_idx).
+// widx: the window frame; fstart: where the frame's sublist starts
+struct PlotSeg { const void* p; int start, n, kind, widx, fstart, pad; };
+constexpr int kPlotResWords = 8;                                                // n_values, min_new, max_new, min_used, max_used, the rewritten pair, 0
+struct WindowPlotDev {
+    const PlotSeg* segs; int nseg, total;
+    int mode, w, h, n_frames; float rainbow_scale, quality_scale;
+    const float* imm; int immN;
+    const uint8_t* flags; const float4* geo;
+    int out_of[NALO_MAX_WINDOW];                                                // window frame -> painted frame, -1: masked out
+    int fstart[NALO_MAX_WINDOW]; const float* I[NALO_MAX_WINDOW];               // per PAINTED frame: its sublist's start, its level-0 irradiance
+    unsigned *key, *col; uint8_t* bgr;                                          // key: n_frames w h words rounded up to 16, zero between calls; col: total words; bgr: 3 bytes per key word
+    unsigned* res; int *cnt, *cnt_next;                                         // res [kPlotResWords]; cnt [NALO_MAX_WINDOW][4] rings per painted frame and class, the idle buffer zeroed for the next call
+    float io_min, io_max; int have_io;
+};
+size_t window_plot_padded_pixels(size_t pixels);                                // what key (words) and bgr (3 bytes each) are sized by: whole workgroups of the resolve pass
+int window_plot_launch(nalo_ctx* c, const WindowPlotDev& D);                   // [select, mode 7] scatter, resolve on c->stream
 // ---- the dense map (nalo_dense_update_map, nalo_map_dense_*)
 constexpr int kDenseMaxClusters = 2048;      // = the most clusters a fit returns (kernels_plane.hip)
 // host_map.hip: the dense archive as the copy pass writes it (the point at position q lives at chunks[q / chunk][q % chunk]; cap: positions that exist)
