@@ -115,6 +115,8 @@ int nalo_frame_wait(nalo_ctx* ctx, int slot);
  *                          Undistort.cpp:101-103 does: nalo_io_read_pcalib), vignetteMapInv [wOrg*hOrg] (nalo_io_make_vignette; NULL without a vignette),
  *                          photometricCalibration = setting_photometricCalibration (0 none, 1 response only, 2 response + vignette; util/settings.cpp:40),
  *                          remapX / remapY [w*h] in original-image pixels, -1 = outside (Undistort.cpp:998-1010); NULL = passthrough (wOrg x hOrg = w x h).
+ *                          Every entry with remapX >= 0 needs 0 <= x < wOrg - 1 and 0 <= y < hOrg - 1 (NaN and infinities are refused); the whole table is
+ *                          checked before anything is stored: a refused call (NALO_ERR_ARG) leaves the tables of the last accepted call in place.
  * nalo_frame_upload_raw    raw = wOrg*hOrg pixels of bytes_per_px 1 (uchar) or 2 (ushort); exposure_time <= 0 disables the photometric part for this frame
  *                          (data = factor * raw, :224-231); mask_org [wOrg*hOrg] / bgr_org [wOrg*hOrg*3] optional (dense=1 / densemap=1 inputs);
  *                          gammaB as in nalo_frame_upload. The frame crosses PCIe at 1-2 B/px instead of 4. Synchronous like nalo_frame_upload. */
@@ -132,6 +134,9 @@ void nalo_host_free(void* p);
 int nalo_frame_rebuild(nalo_ctx* ctx, int slot);
 /* test/inspection: level image as AoS {I,dx,dy} (3 floats/px) and absSquaredGrad (1 float/px); either may be NULL */
 int nalo_frame_download(nalo_ctx* ctx, int slot, int lvl, float* dI3, float* abs_sq_grad);
+/* test/inspection: the slot's level-0 mask (w*h floats) and colour (3*w*h bytes) as nalo_frame_upload[_async] stored them or nalo_frame_upload_raw resized them;
+ * either may be NULL (not both). NALO_ERR_STATE when the slot holds no pyramid or lacks a plane that is asked for (nothing is written then), NALO_ERR_ARG on a bad slot. */
+int nalo_frame_download_mask(nalo_ctx* ctx, int slot, float* mask, uint8_t* bgr);
 
 /* ------------------------------------------------------------------------------------------------
  * Front-end tracker.

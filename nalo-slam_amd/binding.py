@@ -27,7 +27,7 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
-    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download",
+    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask",
     "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
@@ -164,6 +164,7 @@ def load():
     L.nalo_host_free.restype = None
     L.nalo_frame_rebuild.argtypes = [vp, C.c_int]
     L.nalo_frame_download.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp]
+    L.nalo_frame_download_mask.argtypes = [vp, C.c_int, c_fp, c_u8p]
     L.nalo_trk_make_k.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
     L.nalo_trk_set_ref.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_ref_upload.argtypes = [vp, C.c_int, c_fp, c_fp, c_fp, c_fp]
@@ -418,6 +419,13 @@ class Context:
         dI, ab = np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
         self._ck(self.L.nalo_frame_download(self.h_, slot, lvl, _f(dI), _f(ab)))
         return dI, ab
+
+    def frame_download_mask(self, slot, mask=True, bgr=True):
+        """(mask [h, w] float32 or None, bgr [h, w, 3] uint8 or None) of the slot: nalo_frame_download_mask"""
+        m = np.zeros((self.h, self.w), np.float32) if mask else None
+        b = np.zeros((self.h, self.w, 3), np.uint8) if bgr else None
+        self._ck(self.L.nalo_frame_download_mask(self.h_, slot, _f(m), _u8(b)))
+        return m, b
 
     # ---- tracker
     def trk_set_ref(self, slot, Ku, Kv, new_idepth, HdiF):
@@ -1017,10 +1025,11 @@ class Context:
         self._ck(self.L.nalo_frame_upload_raw(self.h_, slot, raw.ctypes.data_as(C.c_void_p), raw.dtype.itemsize, C.c_float(exposure), C.c_float(factor),
                                               None if m is None else _u8(m), None if b is None else _u8(b), None if g is None else _f(g)))
 
-    def frame_upload_raw_async(self, slot, raw, exposure=1.0, factor=1.0):
+    def frame_upload_raw_async(self, slot, raw, exposure=1.0, factor=1.0, gammaB=None):
         """raw: a contiguous uint8 / uint16 array that stays alive and untouched until frame_wait(slot) (pinned: pinned_array(..., dtype))"""
         assert raw.flags.c_contiguous and raw.dtype in (np.uint8, np.uint16)
-        self._ck(self.L.nalo_frame_upload_raw_async(self.h_, slot, raw.ctypes.data_as(C.c_void_p), raw.dtype.itemsize, C.c_float(exposure), C.c_float(factor), None))
+        assert gammaB is None or (gammaB.dtype == np.float32 and gammaB.flags.c_contiguous and gammaB.size == 256)
+        self._ck(self.L.nalo_frame_upload_raw_async(self.h_, slot, raw.ctypes.data_as(C.c_void_p), raw.dtype.itemsize, C.c_float(exposure), C.c_float(factor), _f(gammaB)))
 
     def get_settings(self):
         st = Settings()

@@ -186,15 +186,20 @@ int nalo_undist_set(nalo_ctx* c, int wOrg, int hOrg, const float* G, int GDepth,
     if (photometricCalibration > 0 && (!G || GDepth < 256)) return fail(c, NALO_ERR_ARG, "nalo_undist_set: the response G needs >= 256 entries (Undistort.cpp:83-87)");
     if (photometricCalibration == 2 && !vignetteMapInv) return fail(c, NALO_ERR_ARG, "nalo_undist_set: photometricCalibration 2 needs the vignette");
     if (!remapX && (wOrg != c->w || hOrg != c->h)) return fail(c, NALO_ERR_ARG, "nalo_undist_set: passthrough needs wOrg x hOrg = w x h");
-    NALO_HIP(c, hipSetDevice(c->device));
     const size_t no = (size_t)wOrg * hOrg, n = (size_t)c->w * c->h;
+    // the whole table is checked before anything is copied or reserved: a refused call leaves the context as it was (the old response with the old remap).
+    // The four taps of every output pixel must lie inside the original image (the reference's makeOptimalK_crop / the remap construction guarantee it:
+    // out-of-image entries are -1, Undistort.cpp:998-1010); a violated table is an out-of-bounds device read. The test is made in floating point: (int) of a
+    // NaN, an infinity or a value >= 2^31 is not a number to compare with, and x < wOrg - 1 accepts exactly the finite entries (int)x + 1 < wOrg accepts.
+    if (remapX) {
+        const double xmax = wOrg - 1, ymax = hOrg - 1;                  // exact for any int; a float converts to double exactly
+        for (size_t i = 0; i < n; ++i) if (!(remapX[i] < 0) && !(remapX[i] >= 0 && remapY[i] >= 0 && remapX[i] < xmax && remapY[i] < ymax))
+            return fail(c, NALO_ERR_ARG, "nalo_undist_set: remap entry outside the original image");
+    }
+    NALO_HIP(c, hipSetDevice(c->device));
     if (G) { NALO_HIP(c, c->und_G.reserve(GDepth)); NALO_HIP(c, hipMemcpy(c->und_G.p, G, (size_t)GDepth * 4, hipMemcpyHostToDevice)); }
     if (vignetteMapInv) { NALO_HIP(c, c->und_vinv.reserve(no)); NALO_HIP(c, hipMemcpy(c->und_vinv.p, vignetteMapInv, no * 4, hipMemcpyHostToDevice)); }
     if (remapX) {
-        // the four taps of every output pixel must lie inside the original image (the reference's makeOptimalK_crop / the remap construction guarantee it:
-        // out-of-image entries are -1, Undistort.cpp:998-1010); checked here because a violated table is an out-of-bounds device read
-        for (size_t i = 0; i < n; ++i) if (!(remapX[i] < 0) && !(remapX[i] >= 0 && remapY[i] >= 0 && (int)remapX[i] + 1 < wOrg && (int)remapY[i] + 1 < hOrg))
-            return fail(c, NALO_ERR_ARG, "nalo_undist_set: remap entry outside the original image");
         std::vector<float> xy(2 * n);
         for (size_t i = 0; i < n; ++i) { xy[2 * i] = remapX[i]; xy[2 * i + 1] = remapY[i]; }
         NALO_HIP(c, c->und_rxy.reserve(2 * n));
@@ -294,6 +299,18 @@ int nalo_frame_download(nalo_ctx* c, int slot, int lvl, float* dI3, float* absg)
         for (size_t i = 0; i < npx; ++i) { dI3[3 * i] = tmp[i].x; dI3[3 * i + 1] = tmp[i].y; dI3[3 * i + 2] = tmp[i].z; }
     }
     if (absg) NALO_HIP(c, hipMemcpy(absg, s.absg[lvl].p, npx * 4, hipMemcpyDeviceToHost));
+    return NALO_OK;
+}
+
+int nalo_frame_download_mask(nalo_ctx* c, int slot, float* mask, uint8_t* bgr) {
+    if (!c || slot < 0 || slot >= (int)c->slots.size() || (!mask && !bgr)) return fail(c, NALO_ERR_ARG, "nalo_frame_download_mask: bad argument");
+    FrameSlot& s = c->slots[slot];
+    if (!s.valid || (mask && !s.mask.p) || (bgr && !s.bgr.p)) return fail(c, NALO_ERR_STATE, "nalo_frame_download_mask: the slot holds no such plane");
+    const size_t n0 = (size_t)c->w * c->h;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    if (mask) NALO_HIP(c, hipMemcpy(mask, s.mask.p, n0 * 4, hipMemcpyDeviceToHost));
+    if (bgr) NALO_HIP(c, hipMemcpy(bgr, s.bgr.p, n0 * 3, hipMemcpyDeviceToHost));
     return NALO_OK;
 }
 

@@ -76,6 +76,32 @@ def test_frame_and_tracker_entry_points_reject_and_recover(small_window):
     c.close()
 
 
+def test_frame_download_mask_refusals():
+    """nalo_frame_download_mask: a bad slot or nothing asked for is NALO_ERR_ARG, a slot without the plane asked for NALO_ERR_STATE, and nothing is written then"""
+    w, h = 64, 32
+    c = binding.Context(w, h, (50, 50, 31.5, 15.5), n_slots=2)
+    L, h_ = c.L, c.h_
+    m, b = np.full(w * h, 7.0, np.float32), np.full(3 * w * h, 7, np.uint8)
+    assert L.nalo_frame_download_mask(None, 0, binding._f(m), binding._u8(b)) == ERR_ARG
+    assert L.nalo_frame_download_mask(h_, 2, binding._f(m), binding._u8(b)) == ERR_ARG and "nalo_frame_download_mask" in _last(L, h_)
+    assert L.nalo_frame_download_mask(h_, -1, binding._f(m), None) == ERR_ARG
+    assert L.nalo_frame_download_mask(h_, 0, None, None) == ERR_ARG
+    assert L.nalo_frame_download_mask(h_, 0, binding._f(m), None) == ERR_STATE                       # empty slot
+    img = np.random.RandomState(0).rand(h, w).astype(np.float32) * 255
+    c.frame_upload(0, img)                                                                           # a pyramid, no mask, no colour
+    assert L.nalo_frame_download_mask(h_, 0, binding._f(m), None) == ERR_STATE and L.nalo_frame_download_mask(h_, 0, None, binding._u8(b)) == ERR_STATE
+    mask = np.arange(w * h, dtype=np.float32).reshape(h, w)
+    c.frame_upload(1, img, mask=mask)                                                                # a mask, no colour
+    assert L.nalo_frame_download_mask(h_, 1, binding._f(m), binding._u8(b)) == ERR_STATE and L.nalo_frame_download_mask(h_, 1, None, binding._u8(b)) == ERR_STATE
+    assert (m == 7.0).all() and (b == 7).all()                                                       # no refusal wrote anything
+    assert L.nalo_frame_download_mask(h_, 1, binding._f(m), None) == 0 and np.array_equal(m.reshape(h, w), mask)
+    bgr = np.random.RandomState(1).randint(0, 256, (h, w, 3)).astype(np.uint8)
+    c.frame_upload(1, img, mask=mask[::-1], bgr=bgr)
+    gm, gb = c.frame_download_mask(1)
+    assert np.array_equal(gm, mask[::-1]) and np.array_equal(gb, bgr)
+    c.close()
+
+
 def test_bundle_adjustment_call_order_and_arguments(small_window):
     win = small_window
     c = binding.Context(win.w, win.h, win.K, n_slots=win.W)

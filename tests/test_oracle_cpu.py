@@ -579,3 +579,108 @@ def test_l_and_m_energy_closed_forms_and_energy_test_branch():
     ba.set_settings(force_accept_step=False)
     ba.optimize(6)
     assert 0 <= ba.n_rejected() <= 6
+
+
+# ------------------------------------------------------------------ the front end's oracle at the shapes tests/test_frontend_edges_gpu.py runs it at
+def _same_bits(a, b):
+    """equal as uint32 words (-0.0 and +0.0 differ); where one side is NaN the other must be NaN too (payload and sign of a generated NaN are the machine's)"""
+    a, b = np.ascontiguousarray(a, np.float32).reshape(-1), np.ascontiguousarray(b, np.float32).reshape(-1)
+    na, nb = np.isnan(a), np.isnan(b)
+    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def make_images_model(color, w, h, levels, B=None):
+    """FrameHessian::makeImages (HessianBlocks.cpp:127-190) statement by statement on float32 scalars: w >> l sizes, the 2x2 box in the reference's
+    association, the gradient loop over the flat index [w, w(h-1)), getBGradOnly's factor. Rows 0 and h-1 (never written there) are zero."""
+    f = np.float32
+    dI_all, ab_all, prev = [], [], None
+    with np.errstate(all="ignore"):
+        for lvl in range(levels):
+            wl, hl = w >> lvl, h >> lvl
+            dI = np.zeros((wl * hl, 3), f)
+            ab = np.zeros(wl * hl, f)
+            if lvl == 0:
+                dI[:, 0] = np.asarray(color, f).reshape(-1)
+            else:
+                wlm1 = w >> (lvl - 1)
+                for y in range(hl):
+                    for x in range(wl):
+                        dI[x + y * wl, 0] = f(0.25) * (((prev[2 * x + 2 * y * wlm1, 0] + prev[2 * x + 1 + 2 * y * wlm1, 0])
+                                                        + prev[2 * x + 2 * y * wlm1 + wlm1, 0]) + prev[2 * x + 1 + 2 * y * wlm1 + wlm1, 0])
+            for idx in range(wl, wl * (hl - 1)):
+                dx = f(0.5) * (dI[idx + 1, 0] - dI[idx - 1, 0])
+                dy = f(0.5) * (dI[idx + wl, 0] - dI[idx - wl, 0])
+                if not np.isfinite(dx): dx = f(0)
+                if not np.isfinite(dy): dy = f(0)
+                dI[idx, 1], dI[idx, 2] = dx, dy
+                ab[idx] = dx * dx + dy * dy
+                if B is not None:
+                    c = min(max(int(dI[idx, 0] + f(0.5)), 5), 250)            # (int) truncates towards zero, as Python's int()
+                    gw = f(B[c + 1]) - f(B[c])
+                    ab[idx] *= gw * gw
+            dI_all.append(dI); ab_all.append(ab); prev = dI
+    return np.concatenate(dI_all), np.concatenate(ab_all)
+
+
+def _orc_make_images(img, levels, B=None):
+    h, w = img.shape
+    L = orc.lib()
+    tot = L.orc_pyr_offset(w, h, levels)
+    dI, ab = np.zeros((tot, 3), np.float32), np.zeros(tot, np.float32)
+    L.orc_make_images(orc.fp(np.ascontiguousarray(img, np.float32)), w, h, levels, None if B is None else orc.fp(B), orc.fp(dI), orc.fp(ab))
+    return dI, ab
+
+
+@pytest.mark.parametrize("w,h,levels", [(6, 4, 2), (7, 5, 2), (10, 6, 3)], ids=["6x4_L2", "7x5_L2_odd_parent", "10x6_L3"])
+@pytest.mark.parametrize("table", [False, True], ids=["plain", "gamma"])
+def test_make_images_against_literal_model(w, h, levels, table):
+    """orc_make_images against the statement-by-statement model, bit for bit: the odd parent (7x5 -> 3x2: the last column and row of the parent feed nothing),
+    the flat-index wrap (columns 0 and w-1 hold +-1000: a gradient clamped at the border would differ on every level), intensities outside 5..250 under the
+    table. Without the table the image also holds +inf, -inf and NaN: with it (int)(c + 0.5f) of such a value is undefined in the reference itself."""
+    rng = np.random.RandomState(w * 100 + h)
+    img = (rng.rand(h, w) * 320 - 30).astype(np.float32)
+    img[:, 0], img[:, -1] = 1000.0, -1000.0
+    B = (255.0 * (np.arange(256) / 255.0) ** 0.8).astype(np.float32) if table else None
+    if table:
+        img[:, 0], img[:, -1] = 290.0, -25.0                                  # still far from the rest, still exactly representable
+    else:
+        img[1, 2], img[2, 0], img[h - 2, w - 1] = np.inf, -np.inf, np.nan
+    dI_o, ab_o = _orc_make_images(img, levels, B)
+    dI_m, ab_m = make_images_model(img, w, h, levels, B)
+    assert dI_o.shape == dI_m.shape == (sum((w >> l) * (h >> l) for l in range(levels)), 3)
+    for k in range(3):
+        assert _same_bits(dI_o[:, k], dI_m[:, k]), k
+    assert _same_bits(ab_o, ab_m)
+    I0 = dI_o[:w * h, 0].reshape(h, w); dx0 = dI_o[:w * h, 1].reshape(h, w)
+    if table:
+        assert dx0[2, 0] == np.float32(0.5) * (I0[2, 1] - I0[1, w - 1]) and dx0[1, w - 1] == np.float32(0.5) * (I0[2, 0] - I0[1, w - 2])   # the wrap, spelled out
+        assert not np.array_equal(ab_o, _orc_make_images(img, levels)[1])
+    else:
+        assert dx0[1, 1] == 0 and dx0[1, 3] == 0 and np.isinf(I0[1, 2])       # both neighbours of the planted +inf went through the isfinite branch
+        assert not np.isfinite(dI_o[w * h:, 0]).all()                         # ... and the box filter carried it up
+
+
+def test_undistort_and_resize_hand_worked():
+    """orc_undistort / orc_resize_nearest_u8 on 3x3 -> 2x2 cases worked by hand (every product and sum below is exact in binary)"""
+    raw = np.array([[10, 20, 30], [40, 50, 60], [70, 80, 90]], np.uint8)
+    rx = np.array([[1.0, -1.0], [0.5, 1.25]], np.float32)                     # an exact-integer tap, an outside entry, the centre of four pixels, a general tap
+    ry = np.array([[1.0, -1.0], [0.5, 0.75]], np.float32)
+    # photometric 0: data = 0.5 * raw = [[5, 10, 15], [20, 25, 30], [35, 40, 45]]
+    #   (1, 1): weight 1 on data[1][1] = 25; (0.5, 0.5): 0.25 * (25 + 20 + 10 + 5) = 15
+    #   (1.25, 0.75): taps data[0][1..2], data[1][1..2], xx = 0.25, yy = 0.75, xxyy = 0.1875: 0.1875 * 30 + 0.5625 * 25 + 0.0625 * 15 + 0.1875 * 10 = 22.5
+    out = orc.undistort(raw, None, None, 0, 0.5, rx, ry, 2, 2)
+    assert _same_bits(out, np.array([[25.0, 0.0], [15.0, 22.5]], np.float32))
+    # photometric 2: data = G[raw] * vinv with G[v] = v / 2 and vinv = 1 except vinv[1][1] = 2: data[1][1] = 50
+    #   (1, 1): 50; (0.5, 0.5): 0.25 * (50 + 20 + 10 + 5) = 21.25; (1.25, 0.75): 5.625 + 0.5625 * 50 + 0.9375 + 1.875 = 36.5625
+    G = (np.arange(256) / 2.0).astype(np.float32)
+    vinv = np.ones((3, 3), np.float32); vinv[1, 1] = 2.0
+    out = orc.undistort(raw, G, vinv, 2, 0.5, rx, ry, 2, 2)
+    assert _same_bits(out, np.array([[50.0, 0.0], [21.25, 36.5625]], np.float32))
+    assert _same_bits(orc.undistort(raw, G, None, 1, 0.5, rx, ry, 2, 2), np.array([[25.0, 0.0], [15.0, 22.5]], np.float32))   # response only: the vignette is not applied
+    assert _same_bits(orc.undistort(raw, G, vinv, 2, 1.0, None, None, 3, 3), G[raw] * vinv)                                   # passthrough copies data
+    # resize: sx = min(floor(x * ifx), wOrg - 1) with ifx = 1 / (2 / 3) = 1.5: columns and rows {0, 1}; the upscale 2 -> 3 has ifx = 2 / 3: {0, 0, 1}
+    src = np.arange(1, 10, dtype=np.uint8).reshape(3, 3)
+    assert np.array_equal(orc.resize_nearest_u8(src, 2, 2), [[1, 2], [4, 5]])
+    assert np.array_equal(orc.resize_nearest_u8(src[:2, :2], 3, 3), [[1, 1, 2], [1, 1, 2], [4, 4, 5]])
+    col = np.stack([src, src + 10, src + 20], axis=2)
+    assert np.array_equal(orc.resize_nearest_u8(col, 2, 2), col[:2, :2])
