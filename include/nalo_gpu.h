@@ -127,6 +127,64 @@ int nalo_frame_upload_raw(nalo_ctx* ctx, int slot, const void* raw, int bytes_pe
 /* asynchronous form for tracked (non-key) frames, as nalo_frame_upload_async: the raw copy runs on the copy stream, ingest + pyramid are queued behind it; returns
  * at once, raw must stay untouched until nalo_frame_wait(ctx, slot) (pinned memory: nalo_host_alloc). No mask / colour (keyframe inputs). */
 int nalo_frame_upload_raw_async(nalo_ctx* ctx, int slot, const void* raw, int bytes_per_px, float exposure_time, float factor, const float* gammaB);
+/* Frames, masks and colour that already live on the device. The reference loads mask and colour with every frame (util/DatasetReader.h:296-315,
+ * FullSystem.cpp:1053-1059) although only keyframes use them, and whether a frame becomes one is decided after it has been tracked (FullSystem.cpp:1113-1132);
+ * the mask is the output of a network and a decoded frame is a tensor, both in device memory. These calls take such planes where they lie, in stream order, and
+ * attach mask and colour to a slot whose pyramid exists already.
+ * nalo_dev_plane            one plane by byte strides: element (x, y, ch) is at ptr + y * stride_y + x * stride_x + ch * stride_c. A pitched region of a larger
+ *                           tensor, an x-strided view, interleaved (HWC) and planar (CHW) colour are all described this way. No byte outside the described
+ *                           elements is read.
+ * nalo_dev_plane_check      validates a descriptor and launches nothing. NALO_ERR_ARG for: a null descriptor or pointer; a pointer that hipPointerGetAttributes does
+ *                           not report as device memory of the context's GPU (host, pinned host, managed and other devices' memory); a dtype outside NALO_DT_*;
+ *                           channels other than 1 or 3; w or h < 1; a negative stride; a pointer or stride that is no multiple of the element size; stride_x
+ *                           below the element size (w > 1), or a stride_c under which channels overlap inside a row (accepted: 2 * stride_c + element <= stride_x,
+ *                           interleaved, or stride_c >= the bytes a row spans, planar); where hipMemGetAddressRange answers, an extent that leaves the allocation.
+ *                           The runtime's sticky error is cleared after a failed query.
+ * nalo_frame_ingest_device  image  NALO_DT_U8 / _U16: the sensor frame, und_wOrg x und_hOrg, treated exactly as nalo_frame_upload_raw treats raw (photometric modes,
+ *                                  exposure_time <= 0, remap or passthrough; NALO_ERR_STATE before nalo_undist_set, NALO_ERR_ARG for a 16-bit frame over a response
+ *                                  of less than 65536 entries). NALO_DT_F32: rectified irradiance, w x h, copied to level 0 bit for bit (NaN payloads included) as
+ *                                  nalo_frame_upload takes it. The pyramid follows as in the host calls. NULL: attach only - the slot must hold a pyramid
+ *                                  (NALO_ERR_STATE otherwise), which is left untouched.
+ *                           mask   optional, one channel of U8 ((float)v * 1.0f), I32 ((float)v, round to nearest even) or F32 (bit for bit), any size >= 1x1;
+ *                           colour optional, three channels of U8, any size; colour_is_rgb: channel 0 is R. Both are resized to w x h with
+ *                                  cv::resize(INTER_NEAREST) exactly as Undistort::undistort_mask does (util/Undistort.cpp:385-433; at equal size the identity);
+ *                                  the slot stores w*h floats and interleaved B,G,R bytes as after nalo_frame_upload_raw.
+ *                           Stream order: the library lets its main stream wait, on the device, for everything queued on producer_stream at the time of the call
+ *                           (skipped when that is the context's own stream, nalo_stream), queues its kernels on the main stream and records the slot's event
+ *                           behind the last one that reads a caller's plane. nalo_frame_wait(slot) waits for that event on the host, nalo_frame_release lets
+ *                           a stream wait for it on the device; after either the planes may be overwritten or freed. With its buffers sized and the gamma table of
+ *                           the previous call, the call makes no host wait.
+ *                           Every plane goes through nalo_dev_plane_check, and every other condition is tested, before anything is queued or reserved: a refused
+ *                           call (NALO_ERR_ARG / NALO_ERR_STATE) leaves slot and context as they were.
+ * nalo_frame_release        `stream` (NULL: the null stream) waits, on the device, until the slot's last ingest has read its planes. Nothing to wait for: NALO_OK.
+ * nalo_frame_attach         the same attach from HOST memory in the sensor's size (mask_org [und_wOrg*und_hOrg], bgr_org [und_wOrg*und_hOrg*3], either may be
+ *                           NULL, not both): for the frame that nalo_frame_upload_raw_async brought in and that tracking then made a keyframe. Synchronous like
+ *                           nalo_frame_upload_raw; the pyramid stays. NALO_ERR_STATE before nalo_undist_set and on a slot without a pyramid.
+ * After mask or colour changed under an unchanged image the last pixel-selection map made on the slot is dropped (nalo_pixsel_make_maps_lidar reads the mask);
+ * the gradient histograms stay. */
+#define NALO_DT_U8 1
+#define NALO_DT_U16 2
+#define NALO_DT_I32 3
+#define NALO_DT_F32 4
+typedef struct nalo_dev_plane {
+    const void* ptr;                 /* device memory of the context's GPU */
+    int dtype;                       /* NALO_DT_* */
+    int w, h, channels;              /* channels 1, or 3 for colour */
+    long long stride_y, stride_x, stride_c;   /* BYTES; >= 0; stride_c ignored when channels == 1 */
+} nalo_dev_plane;
+typedef struct nalo_frame_ingest_args {
+    const nalo_dev_plane* image;     /* U8/U16: sensor frame und_wOrg x und_hOrg; F32: rectified irradiance w x h; NULL: attach only */
+    float exposure_time, factor;     /* sensor frames only, as nalo_frame_upload_raw */
+    const nalo_dev_plane* mask;      /* optional. U8 / I32 / F32, any size >= 1x1 */
+    const nalo_dev_plane* colour;    /* optional. U8, 3 channels, any size */
+    int colour_is_rgb;               /* channel 0 is R; the slot always stores B,G,R (img_bgr) */
+    const float* gammaB;             /* host, 256 floats or NULL, as elsewhere */
+    void* producer_stream;           /* hipStream_t whose queued work produces the planes; NULL = the null stream */
+} nalo_frame_ingest_args;
+int nalo_frame_ingest_device(nalo_ctx* ctx, int slot, const nalo_frame_ingest_args* args);
+int nalo_frame_release(nalo_ctx* ctx, int slot, void* stream);
+int nalo_dev_plane_check(nalo_ctx* ctx, const nalo_dev_plane* plane);
+int nalo_frame_attach(nalo_ctx* ctx, int slot, const uint8_t* mask_org, const uint8_t* bgr_org);
 void* nalo_host_alloc(size_t bytes);
 void nalo_host_free(void* p);
 /* makeImages again from the level-0 irradiance already resident in the slot (asynchronous on the ctx stream): the

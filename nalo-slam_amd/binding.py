@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -27,7 +28,7 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
-    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask",
+    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_frame_ingest_device", "nalo_frame_release", "nalo_dev_plane_check", "nalo_frame_attach", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask",
     "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
@@ -44,6 +45,19 @@ EXPORTS = [
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
+
+
+DT_U8, DT_U16, DT_I32, DT_F32 = 1, 2, 3, 4               # NALO_DT_* (include/nalo_gpu.h)
+
+
+class DevPlane(C.Structure):                              # nalo_dev_plane; dev_plane() builds one from a device array
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("w", C.c_int), ("h", C.c_int), ("channels", C.c_int),
+                ("stride_y", C.c_longlong), ("stride_x", C.c_longlong), ("stride_c", C.c_longlong)]
+
+
+class FrameIngestArgs(C.Structure):                       # nalo_frame_ingest_args
+    _fields_ = [("image", C.POINTER(DevPlane)), ("exposure_time", C.c_float), ("factor", C.c_float), ("mask", C.POINTER(DevPlane)), ("colour", C.POINTER(DevPlane)),
+                ("colour_is_rgb", C.c_int), ("gammaB", c_fp), ("producer_stream", C.c_void_p)]
 
 
 class InitWindowArgs(C.Structure):
@@ -158,6 +172,10 @@ def load():
     L.nalo_frame_upload.argtypes = [vp, C.c_int, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_frame_upload_async.argtypes = [vp, C.c_int, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_frame_wait.argtypes = [vp, C.c_int]
+    L.nalo_frame_ingest_device.argtypes = [vp, C.c_int, C.POINTER(FrameIngestArgs)]
+    L.nalo_frame_release.argtypes = [vp, C.c_int, vp]
+    L.nalo_dev_plane_check.argtypes = [vp, C.POINTER(DevPlane)]
+    L.nalo_frame_attach.argtypes = [vp, C.c_int, c_u8p, c_u8p]
     L.nalo_host_alloc.argtypes = [C.c_size_t]
     L.nalo_host_alloc.restype = vp
     L.nalo_host_free.argtypes = [vp]
@@ -317,6 +335,49 @@ class NaloError(RuntimeError):
     pass
 
 
+_TYPESTR_DT = {"<u1": DT_U8, "|u1": DT_U8, "<u2": DT_U16, "<i4": DT_I32, "<f4": DT_F32}
+
+
+def dev_plane(obj, channels_layout=None):
+    """nalo_dev_plane (a DevPlane) of a device array: any object with __cuda_array_interface__ (torch tensors on ROCm have it). Pure host code: data, shape,
+    typestr and strides are read, nothing is converted or copied and no library call is made. channels_layout: None for a 2-D (h, w) plane, "hwc" for
+    (h, w, 3), "chw" for (3, h, w). strides None means C-contiguous. TypeError for an object without the interface (a numpy array), NaloError for a dtype
+    outside the table (u1, u2, i4, f4, little-endian), a shape that does not fit the layout, or negative strides. The plane keeps `obj` alive."""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError("dev_plane: %s has no __cuda_array_interface__ (device arrays only: nothing is copied to the device here)" % type(obj).__name__)
+    dt = _TYPESTR_DT.get(cai["typestr"])
+    if dt is None:
+        raise NaloError("dev_plane: typestr %r is outside the table (u1, u2, i4, f4, little-endian); cast on the producer's side" % (cai["typestr"],))
+    item = {DT_U8: 1, DT_U16: 2, DT_I32: 4, DT_F32: 4}[dt]
+    shape = tuple(int(v) for v in cai["shape"])
+    if channels_layout not in (None, "hwc", "chw"):
+        raise NaloError("dev_plane: channels_layout is None, 'hwc' or 'chw'")
+    if len(shape) != (2 if channels_layout is None else 3):
+        raise NaloError("dev_plane: shape %r does not fit channels_layout %r" % (shape, channels_layout))
+    strides = cai.get("strides")
+    if strides is None:
+        strides = [item] * len(shape)
+        for k in range(len(shape) - 2, -1, -1):
+            strides[k] = strides[k + 1] * shape[k + 1]
+    strides = tuple(int(v) for v in strides)
+    if len(strides) != len(shape):
+        raise NaloError("dev_plane: strides %r do not fit shape %r" % (strides, shape))
+    if any(v < 0 for v in strides):
+        raise NaloError("dev_plane: negative strides %r (flip on the producer's side)" % (strides,))
+    if channels_layout is None:
+        (h, w), (sy, sx), ch, sc = shape, strides, 1, 0
+    elif channels_layout == "hwc":
+        (h, w, ch), (sy, sx, sc) = shape, strides
+    else:
+        (ch, h, w), (sc, sy, sx) = shape, strides
+    if ch not in (1, 3):
+        raise NaloError("dev_plane: %d channels (1 or 3)" % ch)
+    d = DevPlane(int(cai["data"][0]) or None, dt, w, h, ch, sy, sx, sc)
+    d._keep = obj
+    return d
+
+
 def shard_points(host, u, v, W, img_w, img_h, rank, world):
     """indices (ascending) of the active points rank `rank` of `world` keeps: nalo_shard_points, host code (no device needed)"""
     L = load()
@@ -400,6 +461,50 @@ class Context:
 
     def frame_wait(self, slot):
         self._ck(self.L.nalo_frame_wait(self.h_, slot))
+
+    def dev_plane_check(self, desc):
+        """nalo_dev_plane_check on a DevPlane (dev_plane()): raises NaloError when the library refuses the descriptor; launches nothing"""
+        self._ck(self.L.nalo_dev_plane_check(self.h_, C.byref(desc)))
+
+    def frame_ingest(self, slot, image=None, mask=None, colour=None, colour_layout="hwc", colour_order="bgr", exposure=1.0, factor=1.0, gammaB=None, stream=None,
+                     release=True):
+        """nalo_frame_ingest_device: image (u1 / u2 sensor frame or f4 rectified irradiance; None attaches mask / colour to the slot's pyramid), mask (u1 / i4 / f4)
+        and colour (u1, colour_layout 'hwc' or 'chw', colour_order 'bgr' or 'rgb') are device arrays with __cuda_array_interface__, read where they lie: nothing is
+        converted or copied here. stream: the hipStream_t (an int) whose queued work produces them; None takes torch.cuda.current_stream of a torch.Tensor and
+        the null stream for anything else. release=True lets that stream wait (on the device) until the planes have been read, so they may be dropped or overwritten
+        on it at once; with release=False call frame_wait(slot) or frame_release(slot, stream) first. Returns without waiting for the device."""
+        if colour_layout not in ("hwc", "chw") or colour_order not in ("bgr", "rgb"):
+            raise NaloError("frame_ingest: colour_layout is 'hwc' or 'chw', colour_order 'bgr' or 'rgb'")
+        planes = [None if o is None else dev_plane(o, lay) for o, lay in ((image, None), (mask, None), (colour, colour_layout))]
+        if stream is None:
+            stream = 0
+            torch = sys.modules.get("torch")                       # a torch.Tensor exists only where torch has been imported: never imported for other producers
+            for o in (image, mask, colour):
+                if torch is not None and isinstance(o, torch.Tensor):
+                    stream = torch.cuda.current_stream(o.device).cuda_stream
+                    break
+        g = None if gammaB is None else np.ascontiguousarray(gammaB, np.float32)
+        assert g is None or g.size == 256
+        ptr = lambda d: None if d is None else C.pointer(d)
+        a = FrameIngestArgs(ptr(planes[0]), exposure, factor, ptr(planes[1]), ptr(planes[2]), int(colour_order == "rgb"), _f(g), stream or None)
+        self._ck(self.L.nalo_frame_ingest_device(self.h_, slot, C.byref(a)))
+        if release:
+            self.frame_release(slot, stream)
+
+    def frame_release(self, slot, stream):
+        """nalo_frame_release: `stream` (a hipStream_t as an int, 0 / None the null stream) waits on the device until the slot's last ingest has read its planes"""
+        self._ck(self.L.nalo_frame_release(self.h_, slot, stream or None))
+
+    def frame_attach(self, slot, mask_org=None, bgr_org=None):
+        """nalo_frame_attach: mask and / or colour (host arrays in the sensor's size) resized into a slot that holds a pyramid already; synchronous"""
+        m = None if mask_org is None else np.ascontiguousarray(mask_org, np.uint8)
+        b = None if bgr_org is None else np.ascontiguousarray(bgr_org, np.uint8)
+        no = getattr(self, "_und_size", None)
+        if no is None:
+            raise NaloError("frame_attach: undist_set has not run on this context")
+        if (m is not None and m.size != no) or (b is not None and b.size != 3 * no):
+            raise NaloError("frame_attach: mask_org is wOrg x hOrg bytes, bgr_org wOrg x hOrg x 3")
+        self._ck(self.L.nalo_frame_attach(self.h_, slot, _u8(m), _u8(b)))
 
     def pinned_array(self, shape, dtype=np.float32):
         """numpy array over page-locked host memory from nalo_host_alloc (freed when the context closes)"""
@@ -1015,6 +1120,7 @@ class Context:
         G, vinv, remapX, remapY = f(G), f(vinv), f(remapX), f(remapY)
         self._ck(self.L.nalo_undist_set(self.h_, wOrg, hOrg, None if G is None else _f(G), 0 if G is None else G.size, None if vinv is None else _f(vinv), int(photometric),
                                         None if remapX is None else _f(remapX), None if remapY is None else _f(remapY)))
+        self._und_size = int(wOrg) * int(hOrg)
 
     def frame_upload_raw(self, slot, raw, exposure=1.0, factor=1.0, mask_org=None, bgr_org=None, gammaB=None):
         raw = np.ascontiguousarray(raw)

@@ -144,7 +144,8 @@ int nalo_frame_upload(nalo_ctx* c, int slot, const float* irradiance, const floa
 // The gamma table is shared by all slots of the context: another slot's pyramid kernel (main stream) may still be reading it when the next frame arrives. A running
 // system passes the same CalibHessian::B every frame, so the table is sent once; a DIFFERENT table is copied only after the copy stream has waited for everything
 // queued on the main stream so far.
-static int gamma_upload_async(nalo_ctx* c, const float* gammaB) {
+static int gamma_upload_async(nalo_ctx* c, const float* gammaB, bool* sent = nullptr) {   // *sent: a copy was queued on the copy stream
+    if (sent) *sent = false;
     if (!gammaB) return NALO_OK;
     if (c->gamma_have && std::memcmp(c->gamma_last, gammaB, sizeof(c->gamma_last)) == 0) return NALO_OK;
     NALO_HIP(c, hipEventRecord(c->ev_main, c->stream));
@@ -152,6 +153,7 @@ static int gamma_upload_async(nalo_ctx* c, const float* gammaB) {
     std::memcpy(c->gamma_last, gammaB, sizeof(c->gamma_last));
     NALO_HIP(c, hipMemcpyAsync(c->gamma_dev.p, c->gamma_last, 256 * 4, hipMemcpyHostToDevice, c->copy));   // from the context's copy: the caller's table may change after the call
     c->gamma_have = true;
+    if (sent) *sent = true;
     return NALO_OK;
 }
 int nalo_frame_upload_async(nalo_ctx* c, int slot, const float* irradiance, const float* mask, const uint8_t* bgr, const float* gammaB) {
@@ -269,6 +271,138 @@ int nalo_frame_upload_raw_async(nalo_ctx* c, int slot, const void* raw, int byte
     if (rc) return rc;
     pixsel_invalidate_hists(c, slot);
     s.valid = true;
+    return NALO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ frames that already live on the device
+static size_t dev_plane_elem(int dtype) { return dtype == NALO_DT_U8 ? 1 : dtype == NALO_DT_U16 ? 2 : (dtype == NALO_DT_I32 || dtype == NALO_DT_F32) ? 4 : 0; }
+// The one validation of a descriptor (nalo_dev_plane_check, and nalo_frame_ingest_device on every plane before it enqueues or reserves anything). Launches nothing;
+// a failed runtime query leaves no sticky error behind.
+static int dev_plane_validate(nalo_ctx* c, const nalo_dev_plane* d, const char* who, const char* what) {
+    const std::string W = std::string(who) + ": " + what + ": ";
+    if (!d || !d->ptr) return fail(c, NALO_ERR_ARG, W + "null pointer");
+    const size_t el = dev_plane_elem(d->dtype);
+    if (!el) return fail(c, NALO_ERR_ARG, W + "dtype outside NALO_DT_*");
+    if (d->channels != 1 && d->channels != 3) return fail(c, NALO_ERR_ARG, W + "channels must be 1 or 3");
+    if (d->w < 1 || d->h < 1) return fail(c, NALO_ERR_ARG, W + "w and h must be >= 1");
+    const long long sy = d->stride_y, sx = d->stride_x, sc = d->channels == 3 ? d->stride_c : 0, e = (long long)el;
+    if (sy < 0 || sx < 0 || sc < 0) return fail(c, NALO_ERR_ARG, W + "negative stride");
+    // the loads are naturally aligned ones: the address of every element is a multiple of its size
+    if ((uintptr_t)d->ptr % el || sy % e || sx % e || sc % e) return fail(c, NALO_ERR_ARG, W + "pointer or stride is not a multiple of the element size");
+    // inside a row no two elements may overlap: pixels at least an element apart, and the three channels either inside the pixel step (interleaved) or a step
+    // beyond the row (planar)
+    const __int128 row = (__int128)(d->w - 1) * sx + e;                    // bytes one channel of a row spans
+    if (d->w > 1 && sx < e) return fail(c, NALO_ERR_ARG, W + "stride_x smaller than the element");
+    if (d->channels == 3) {
+        const bool interleaved = sc >= e && (d->w == 1 || (__int128)2 * sc + e <= sx), planar = (__int128)sc >= row;
+        if (!interleaved && !planar) return fail(c, NALO_ERR_ARG, W + "stride_c makes the channels overlap inside a row");
+    }
+    const __int128 extent = (__int128)(d->h - 1) * sy + (__int128)(d->w - 1) * sx + (__int128)(d->channels - 1) * sc + e;
+    if (extent > ((__int128)1 << 62)) return fail(c, NALO_ERR_ARG, W + "the described extent is not an allocation's");
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, d->ptr) != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_ARG, W + "not memory the runtime knows (a host pointer?)"); }
+    if (at.type != hipMemoryTypeDevice || at.isManaged || at.device != c->device) return fail(c, NALO_ERR_ARG, W + "not device memory of the context's GPU (host, pinned, managed and other devices' memory are refused)");
+    void* base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(d->ptr)) != hipSuccess) (void)hipGetLastError();      // no answer: the extent cannot be checked
+    else if ((__int128)((const char*)d->ptr - (const char*)base) + extent > (__int128)size) return fail(c, NALO_ERR_ARG, W + "the described bytes leave the allocation");
+    return NALO_OK;
+}
+int nalo_dev_plane_check(nalo_ctx* c, const nalo_dev_plane* plane) {
+    if (!c) return NALO_ERR_ARG;
+    return dev_plane_validate(c, plane, "nalo_dev_plane_check", "plane");
+}
+
+// Sensor frame / rectified image, mask and colour from device memory, in stream order: the main stream waits (on the device) for what producer_stream has queued,
+// ingest / copy, attach and the pyramid are queued on it, and the slot's ev_up is recorded behind the last kernel that reads a caller's plane. Everything is
+// checked before anything is queued, reserved or changed. No host wait in steady state (buffers sized, the gamma table of the last call).
+int nalo_frame_ingest_device(nalo_ctx* c, int slot, const nalo_frame_ingest_args* a) {
+    const char* who = "nalo_frame_ingest_device";
+    if (!c || !a || slot < 0 || slot >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: bad argument");
+    if (!a->image && !a->mask && !a->colour) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: no plane given");
+    NALO_HIP(c, hipSetDevice(c->device));
+    FrameSlot& s = c->slots[slot];
+    int rc;
+    if (a->image && (rc = dev_plane_validate(c, a->image, who, "image"))) return rc;
+    if (a->mask && (rc = dev_plane_validate(c, a->mask, who, "mask"))) return rc;
+    if (a->colour && (rc = dev_plane_validate(c, a->colour, who, "colour"))) return rc;
+    int photometric = 0;
+    if (a->image) {
+        const nalo_dev_plane& im = *a->image;
+        if (im.channels != 1) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: the image has one channel");
+        if (im.dtype == NALO_DT_F32) {
+            if (im.w != c->w || im.h != c->h) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: a rectified (F32) image is w x h");
+        } else if (im.dtype == NALO_DT_U8 || im.dtype == NALO_DT_U16) {
+            if (!c->und_set) return fail(c, NALO_ERR_STATE, "nalo_frame_ingest_device: nalo_undist_set has not run");
+            if (im.w != c->und_wOrg || im.h != c->und_hOrg) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: a sensor (U8 / U16) image is und_wOrg x und_hOrg");
+            photometric = a->exposure_time <= 0 ? 0 : c->und_photometric;                                  // as nalo_frame_upload_raw (processFrame, Undistort.cpp:224-231)
+            if (photometric > 0 && im.dtype == NALO_DT_U16 && c->und_GDepth < 65536) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: 16-bit frames index G beyond its depth");
+        } else return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: the image is U8 / U16 (sensor) or F32 (rectified)");
+    } else if (!s.valid) return fail(c, NALO_ERR_STATE, "nalo_frame_ingest_device: attach needs a slot that holds a pyramid");
+    if (a->mask && (a->mask->channels != 1 || (a->mask->dtype != NALO_DT_U8 && a->mask->dtype != NALO_DT_I32 && a->mask->dtype != NALO_DT_F32)))
+        return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: the mask is one channel of U8, I32 or F32");
+    if (a->colour && (a->colour->channels != 3 || a->colour->dtype != NALO_DT_U8)) return fail(c, NALO_ERR_ARG, "nalo_frame_ingest_device: the colour image is three channels of U8");
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "frame_ingest_device");
+    const size_t n0 = (size_t)c->w * c->h;
+    NALO_HIP(c, s.ev_up.create(hipEventDisableTiming)); NALO_HIP(c, c->ev_prod.create(hipEventDisableTiming));
+    if (a->mask) NALO_HIP(c, s.mask.reserve(n0));
+    if (a->colour) NALO_HIP(c, s.bgr.reserve(n0 * 3));
+    const bool gamma = a->image && a->gammaB;
+    if (gamma) {                                                           // the table goes the way the asynchronous uploads send it: only when it differs from the last one
+        NALO_HIP(c, c->copy.create()); NALO_HIP(c, c->ev_main.create(hipEventDisableTiming)); NALO_HIP(c, c->gamma_dev.reserve(256));
+        bool sent = false;
+        rc = gamma_upload_async(c, a->gammaB, &sent); if (rc) return rc;
+        if (sent) { NALO_HIP(c, hipEventRecord(s.ev_up, c->copy)); NALO_HIP(c, hipStreamWaitEvent(c->stream, s.ev_up, 0)); }
+    }
+    hipStream_t prod = (hipStream_t)a->producer_stream;                    // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    if (a->image) {
+        rc = ingest_dev_launch(c, c->stream, *a->image, c->und_G.p, c->und_vig ? c->und_vinv.p : nullptr, c->und_remap ? reinterpret_cast<const float2*>(c->und_rxy.p) : nullptr,
+                               photometric, a->factor, s.I[0].p);
+        if (rc) return rc;
+    }
+    rc = attach_launch(c, c->stream, a->mask, a->colour, a->colour_is_rgb, s.mask.p, s.bgr.p); if (rc) return rc;
+    NALO_HIP(c, hipEventRecord(s.ev_up, c->stream));                       // the caller's planes have been read: nalo_frame_wait / nalo_frame_release
+    if (a->image) {
+        rc = pyramid_build(c, s, gamma ? c->gamma_dev.p : nullptr); if (rc) return rc;
+        pixsel_invalidate_hists(c, slot);
+        s.valid = true;
+    } else pixsel_invalidate_map(c, slot);
+    return NALO_OK;
+}
+
+int nalo_frame_release(nalo_ctx* c, int slot, void* stream) {
+    if (!c || slot < 0 || slot >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_frame_release: bad slot");
+    if (!c->slots[slot].ev_up) return NALO_OK;                             // nothing was ever ingested into the slot: nothing to wait for
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->slots[slot].ev_up, 0));
+    return NALO_OK;
+}
+
+// Mask and colour for a slot that already holds a pyramid, from host memory in the sensor's size: the tracked frame that became a keyframe (FullSystem.cpp:1113-1132)
+// gets the keyframe-only inputs without its image being sent or its pyramid being built again. Staged through und_mask / und_bgr like nalo_frame_upload_raw.
+int nalo_frame_attach(nalo_ctx* c, int slot, const uint8_t* mask_org, const uint8_t* bgr_org) {
+    if (!c || slot < 0 || slot >= (int)c->slots.size() || (!mask_org && !bgr_org)) return fail(c, NALO_ERR_ARG, "nalo_frame_attach: bad argument");
+    if (!c->und_set) return fail(c, NALO_ERR_STATE, "nalo_frame_attach: nalo_undist_set has not run");
+    FrameSlot& s = c->slots[slot];
+    if (!s.valid) return fail(c, NALO_ERR_STATE, "nalo_frame_attach: the slot holds no pyramid");
+    NALO_HIP(c, hipSetDevice(c->device));
+    const size_t no = (size_t)c->und_wOrg * c->und_hOrg, n0 = (size_t)c->w * c->h;
+    nalo_dev_plane m = {}, b = {};
+    if (mask_org) {
+        NALO_HIP(c, c->und_mask.reserve(no)); NALO_HIP(c, s.mask.reserve(n0));
+        NALO_HIP(c, hipMemcpyAsync(c->und_mask.p, mask_org, no, hipMemcpyHostToDevice, c->stream));
+        m.ptr = c->und_mask.p; m.dtype = NALO_DT_U8; m.w = c->und_wOrg; m.h = c->und_hOrg; m.channels = 1; m.stride_y = c->und_wOrg; m.stride_x = 1;
+    }
+    if (bgr_org) {
+        NALO_HIP(c, c->und_bgr.reserve(no * 3)); NALO_HIP(c, s.bgr.reserve(n0 * 3));
+        NALO_HIP(c, hipMemcpyAsync(c->und_bgr.p, bgr_org, no * 3, hipMemcpyHostToDevice, c->stream));
+        b.ptr = c->und_bgr.p; b.dtype = NALO_DT_U8; b.w = c->und_wOrg; b.h = c->und_hOrg; b.channels = 3; b.stride_y = 3LL * c->und_wOrg; b.stride_x = 3; b.stride_c = 1;
+    }
+    int rc = attach_launch(c, c->stream, mask_org ? &m : nullptr, bgr_org ? &b : nullptr, 0, s.mask.p, s.bgr.p); if (rc) return rc;
+    pixsel_invalidate_map(c, slot);
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                          // host buffers are caller-owned: safe to reuse on return
     return NALO_OK;
 }
 

@@ -252,6 +252,9 @@ void pixsel_invalidate_hists(nalo_ctx* c, int slot) {
     if (c->pixsel && c->pixsel->hist_slot == slot) c->pixsel->hist_slot = -1;
     if (c->pixsel && c->pixsel->map_slot == slot) c->pixsel->map_slot = -1;    // the map no longer describes the slot's image
 }
+void pixsel_invalidate_map(nalo_ctx* c, int slot) {
+    if (c->pixsel && c->pixsel->map_slot == slot) c->pixsel->map_slot = -1;    // ... or its mask (nalo_frame_attach); the histograms are made from absSquaredGrad alone
+}
 bool pixsel_last_list(nalo_ctx* c, int slot, const int** dev, int* n_dev, const int** host_live, int* n_live) {
     const PixSel* p = c->pixsel;
     if (!p || !p->have_map || p->map_slot != slot || slot < 0) return false;

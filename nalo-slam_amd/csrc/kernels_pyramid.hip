@@ -5,6 +5,7 @@
 // Output texel = float4 {I, dx, dy, 0}: one aligned 16-byte load per bilinear tap in the gather kernels.
 // Bandwidth-bound streaming kernels: 16 B/lane stores, 256-thread blocks, grid-stride.
 #include "nalo_internal.h"
+#include "ingest_device.h"
 #include <hip/hip_ext.h>
 
 namespace nalo {
@@ -433,7 +434,6 @@ __device__ __forceinline__ void ingest_pair(const void* __restrict__ raw, int p,
 // Round 4: a pixel is a chain of two dependent round trips (remap entry -> taps), and with one pixel per lane a 1920x1072 frame is four rounds of the
 // resident grid: ~8 round trips end to end (15 us at 0.30 of the roofline). Now every lane owns four pixels (stride 256 inside its workgroup's run of consecutive
 // pixels: every instruction still covers one contiguous run per wave): the U remap loads leave together, then the 4 U taps, then the stores - the whole frame is resident at once.
-constexpr int kIngestU = 4;
 template <int BPP, int PHOTO>
 __global__ __launch_bounds__(256) void ingest_kernel(IngestParams P) {
     constexpr int U = kIngestU;
@@ -497,9 +497,7 @@ __global__ __launch_bounds__(256) void ingest_kernel(IngestParams P) {
         P.out_I[idx] = o[u];
         if (P.mask_org || P.bgr_org) {                     // cv::resize(.., INTER_NEAREST): sx = min(floor(x * ifx), wOrg - 1)
             const int y = idx / P.w, x = idx - y * P.w;
-            int sx = (int)floor(x * P.ifx), sy = (int)floor(y * P.ify);
-            sx = sx < P.wOrg - 1 ? sx : P.wOrg - 1; sy = sy < P.hOrg - 1 ? sy : P.hOrg - 1;
-            const int sp = sx + sy * P.wOrg;
+            const int sp = resize_nearest_src(x, P.ifx, P.wOrg) + resize_nearest_src(y, P.ify, P.hOrg) * P.wOrg;   // ingest_device.h, shared with attach_kernel
             if (P.mask_org) P.out_mask[idx] = (float)P.mask_org[sp] * 1.0f;
             if (P.bgr_org) { P.out_bgr[3 * idx] = P.bgr_org[3 * sp]; P.out_bgr[3 * idx + 1] = P.bgr_org[3 * sp + 1]; P.out_bgr[3 * idx + 2] = P.bgr_org[3 * sp + 2]; }
         }
@@ -510,7 +508,7 @@ int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOr
     IngestParams P;
     P.raw = raw; P.bpp = bpp; P.wOrg = wOrg; P.hOrg = hOrg; P.w = c->w; P.h = c->h; P.G = G; P.vinv = vinv; P.remapXY = remapXY; P.photometric = photometric;
     P.factor = factor; P.mask_org = mask_org; P.bgr_org = bgr_org; P.out_I = out_I; P.out_mask = out_mask; P.out_bgr = out_bgr;
-    P.ifx = 1.0 / ((double)c->w / wOrg); P.ify = 1.0 / ((double)c->h / hOrg);
+    P.ifx = resize_nearest_inv(c->w, wOrg); P.ify = resize_nearest_inv(c->h, hOrg);
     const int n = c->w * c->h, grid = (n + 256 * kIngestU - 1) / (256 * kIngestU);   // four pixels per lane, consecutive workgroups on consecutive memory
     ProfScope ps(c, "ingest", true);                                       // dispatch-attached timestamps
 #define NALO_INGEST(B_, P_) do { if (ps.a) hipExtLaunchKernelGGL((ingest_kernel<B_, P_>), dim3(grid), dim3(256), 0, st, ps.a, ps.b, 0, P); else ingest_kernel<B_, P_><<<grid, 256, 0, st>>>(P); } while (0)

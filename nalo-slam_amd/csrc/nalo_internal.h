@@ -91,7 +91,7 @@ struct FrameSlot {
     DevBuf<float> mask;                      // level 0 (densemap only)
     DevBuf<uint8_t> bgr;
     bool valid = false;
-    Event ev_up;                             // nalo_frame_upload_async: the slot's H2D copies (copy stream) have completed
+    Event ev_up;                             // nalo_frame_upload_async: the slot's H2D copies (copy stream) have completed; nalo_frame_ingest_device: its last kernel that reads a caller's plane has
     DevBuf<uint8_t> raw;                     // nalo_frame_upload_raw_async: this slot's sensor frame as uploaded (several frames may be in flight)
     DevBuf<float> dI0t; bool tiled_valid = false;    // level 0 again as 12-byte texels in 5x2 tiles of 128 bytes (ba_linearize's gathers), made on demand (frame_tile_level0)
 };
@@ -117,6 +117,7 @@ struct nalo_ctx {
     // (nalo_destroy has drained them, and deleted ba / pixsel / init, before the context goes).
     nalo::Stream stream, side, copy;         // copy: H2D frame uploads of nalo_frame_upload_async (overlap the kernels of `stream`), created on first use
     nalo::Event ev_main;                     // main-stream marker the copy stream waits on before it overwrites a slot that has been used
+    nalo::Event ev_prod;                     // nalo_frame_ingest_device: recorded on the caller's producer stream, the main stream waits for it
     nalo::DevBuf<float> gamma_dev;           // 256-entry gamma table of the asynchronous upload path
     float gamma_last[256]; bool gamma_have = false;   // what gamma_dev holds: the table is re-sent only when the caller's differs (and then behind every kernel that may read it)
     // raw-frame ingest (nalo_undist_set / nalo_frame_upload_raw): photometric + geometric undistortion tables, raw staging
@@ -405,6 +406,7 @@ void init_destroy(nalo_ctx* c);
 // kernels_pixsel.hip
 void pixsel_destroy(nalo_ctx* c);
 void pixsel_invalidate_hists(nalo_ctx* c, int slot);
+void pixsel_invalidate_map(nalo_ctx* c, int slot);     // the slot's mask changed under an unchanged image: the last map (nalo_pixsel_make_maps_lidar reads the mask) goes, the gradient histograms stay
 // staging for the immature-point entry points: pinned host block + device block of `floats` 4-byte words (grown on demand)
 int imm_stage(nalo_ctx* c, size_t words);
 int imm_put_launch(nalo_ctx* c, float* dst, const float* src, int n);
@@ -444,6 +446,11 @@ int frame_tile_level0(nalo_ctx* c, nalo::FrameSlot& s);
 void hbm_stream_launch(hipStream_t st, const float4* a, const float4* b, float4* d, size_t n, int triad);
 int ingest_launch(nalo_ctx* c, hipStream_t st, const void* raw, int bpp, int wOrg, int hOrg, const float* G, const float* vinv, const float2* remapXY, int photometric,
                   float factor, const uint8_t* mask_org, const uint8_t* bgr_org, float* out_I, float* out_mask, uint8_t* out_bgr);
+// kernels_ingest_dev.hip: the same from planes on the device, every descriptor already validated (host_api.hip: dev_plane_validate). img: NALO_DT_U8 / _U16 sensor
+// frame (und_wOrg x und_hOrg) or NALO_DT_F32 rectified irradiance (w x h, copied word for word; G .. factor unused). attach: mask and / or colour resized into the
+// slot's planes (out_mask w*h floats, out_bgr 3*w*h bytes B,G,R); either descriptor may be null
+int ingest_dev_launch(nalo_ctx* c, hipStream_t st, const nalo_dev_plane& img, const float* G, const float* vinv, const float2* remapXY, int photometric, float factor, float* out_I);
+int attach_launch(nalo_ctx* c, hipStream_t st, const nalo_dev_plane* mask, const nalo_dev_plane* colour, int colour_is_rgb, float* out_mask, uint8_t* out_bgr);
 // kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points; the whole pyramid descent of nalo_trk_track in one persistent launch
 int trk_lm_blocks(int maxn);
 int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2], int coarsest, int stop_lvl, const double* minRes, double out24[32]);
