@@ -369,7 +369,7 @@ int nalo_ba_calc_l_energy(nalo_ctx* ctx, double* E);
 /* planeOpt=1, call sites FullSystem.cpp:1440-1441, without Ceres:
  * nalo_ba_plane_scale_fix    FullSystem::planeOptimize's active part (FullSystem/PlaneOptimize.cpp:183-301) for the newest keyframe: camToWorld =
  *     trackingRef.camToWorld * [R | localscale * t](camToTrackingRef), its own points' idepth /= localscale (idepth_zero alike), setEvalPT at the new pose, adjoints,
- *     precalc. localscale = getlocalgh() / groundP[3] is the caller's (ground plane from its RANSAC); the caller skips the call when scaleFixed / no ground.
+ *     precalc. localscale = getlocalgh() / groundP[3] is the caller's (nalo_ground_local_scale on the state nalo_trk_fit_ground + nalo_ground_update keep, or a RANSAC of its own); the caller skips the call when scaleFixed / no ground.
  * nalo_ba_sw_gray_optimize   FullSystem::SWGrayOptimize_J (:307-454). The reference's Ceres cost functor multiplies every Jacobian by an image gradient it never
  *     reads (a shadowed variable, PlaneOptimize.h:378-381): the gradient is identically zero, Ceres returns its initial point. The call therefore
  *     (a) evaluates the Huber(100) cost 1/2 sum rho(r^2) over all (point, target != host) centre-pixel residuals with 1e-4 <= idepth <= 1e3 on the device
@@ -630,7 +630,8 @@ int nalo_dense_make_map(nalo_ctx* ctx, int slot, const float plane[4], float mas
  *   loop of CoarseTracker.cpp:582-666 on the device with the fitted planes, through the code of nalo_trk_append_plane_points: nothing with fewer than 4 clusters
  *   (:563); per cluster, in order: skipped when not fitted (:591), when its rect touches the border (:627: maxx>w-1||minx<1||maxy>h-1||miny<1) or when
  *   (int)mask_value == 0 (:635); else appended (the off-by-one slot included), `appended` = the growth of pc_n[0]. The clusters are formed before the first
- *   append, as in the reference. NOT done here: the ground choice by `score` (:609-625) reads a variable fitPlane never writes; it stays with the caller.
+ *   append, as in the reference. The ground choice by `score` (:609-625) is nalo_trk_fit_ground below: CoarseTracker::fitPlane, the one this call site uses,
+ *   writes `score` on every path that returns true (:362-376); it is DenseMapping::fitPlane (MapPoint.cpp:522-584) that never does.
  * nalo_dense_fit_planes input: what updateMap collects for the window's frame host_frame (MapPoint.cpp:246-259): its valid window points in submission order
  *   with idepth, then the resident immature points with that host_idx in resident order with (idepth_max + idepth_min) * 0.5f; mask: the frame's slot. The caller
  *   loops nalo_dense_make_map over the fitted clusters as before, or calls nalo_dense_update_map, which does both. Read on the device; the slot map of the window's points (4 bytes per point) goes down once
@@ -654,7 +655,7 @@ typedef struct nalo_plane_cluster {
 } nalo_plane_cluster;
 typedef struct nalo_plane_fit_args {
     float threshold;       /* the reference's setDistanceThreshold(0.01) */
-    int   min_points;      /* the reference's 10 */
+    int   min_points;      /* DenseMapping::fitPlane's 10 (MapPoint.cpp:560); CoarseTracker::fitPlane, the tracker's, has 20 (CoarseTracker.cpp:336) */
     int   n_samples;       /* triplets; PCL's SACSegmentation default of 50 iterations is the documented default */
     const uint32_t* draws; /* 3 * n_samples values of the caller's stream, shared by all clusters */
     int   append;          /* tracker variant only */
@@ -662,6 +663,94 @@ typedef struct nalo_plane_fit_args {
 int nalo_trk_fit_planes(nalo_ctx* ctx, const nalo_plane_fit_args* args, int cap, nalo_plane_cluster* out, int* n_clusters);
 int nalo_dense_fit_planes(nalo_ctx* ctx, int host_frame, const nalo_plane_fit_args* args, int cap, nalo_plane_cluster* out, int* n_clusters);
 int nalo_plane_fit_members(nalo_ctx* ctx, int cap, int* cluster_of, int* order);
+
+/* ------------------------------------------------------------------------------------------------
+ * dense_track = 1 with setPlaneOptimize: the ground plane of setCoarseTrackingRef (CoarseTracker.cpp:582-625), the window points on it (:669-693) and the
+ * scale_fix / scale_rate state machine it feeds (:696-816), then makeKeyFrame's global plane and local scale (FullSystem.cpp:1420-1443, 1911-1976;
+ * PlaneOptimize.cpp:203-211). The device half is one call; the state machine is plain host C over caller-owned structs and needs no device.
+ *
+ * nalo_trk_fit_ground   nalo_trk_fit_planes(ctx, fit, cap, out, n_clusters) with the ground pass enqueued behind the refinement: records, member lists, appended
+ *   cloud and *n_clusters are those of nalo_trk_fit_planes on the same inputs, bit for bit; still one wait, at the end; the call is the "last completed call" of
+ *   nalo_plane_fit_members. All fp32, no FMA.
+ *   score     (CoarseTracker::fitPlane :299-378) a cluster takes part iff fitted && n_cloud == n: fitPlane returns false on a member that does not back-project
+ *             to finite values (:320-324) and on fewer than fit->min_points cloud points (:336 - 20 for the tracker, not DenseMapping's 10).
+ *             mid_z = the float sum, IN MEMBER ORDER, of Z_k / (float)n (:332; a chain of dependent adds, run in order by one wave).
+ *             score = 9999999.0f when n < 100 || mid_z < 0 || mask_value < 200 (:363-368), else ((a + c) * 1000.0f + fabsf(d) * 100.0f) + (float)(100 / n)
+ *             with the reference's INTEGER 100 / n (1 at n == 100, 0 above). The `abs` of :373 and :615 is the float one: CoarseTracker.h includes <math.h> and
+ *             <cstdlib> under `using namespace std`. DEFINED: x_axis . dir + z_axis . dir is a + c for finite planes.
+ *   choice    (:574-625) nothing at all with fewer than 4 clusters (:563-567): pick->ran = 0 and NOTHING else is written (pick's other fields, scores, onground).
+ *             Otherwise ran = 1 and the first cluster in record order with the strictly smallest score below FLT_MAX wins (a NaN score never wins, as with
+ *             the reference's `<`; a cluster scored 9999999 can win): cluster = its record index or -1 when none took part; gp_raw = (-a,-b,-c,-d) when b > 0,
+ *             (a,b,c,d) otherwise (b == -0.0 is not > 0), zeros without a winner; ground_height = fabsf(d), valid only with a winner. The border and
+ *             mask_value == 0 tests (:627,635) come after the choice in the reference and only gate the append: a cluster can be chosen and not appended.
+ *   marking   (:669-693) with g->mark_window_points: the winner's members (xx, yy) set bits in a w x h bitmap (cleared again by a walk over the same members: no
+ *             fill of the plane in steady state); one lane per window point, in the loop order of nalo_trk_set_ref_from_window (host, then submission order):
+ *             a point is tested when lastResiduals[0] (the window's point history) names frame W-1 with state IN and that residual is IN at the window's last
+ *             linearizeAll(true) - in a history the fix passes maintain, the set nalo_trk_set_ref_from_window gathers; u = (int)(cpt.x + 0.5f), v =
+ *             (int)(cpt.y + 0.5f) of its centerProjectedTo (DEFINED as elsewhere: saturating, NaN -> 0; outside the image matches nothing).
+ *             n_ground_points = temp_gp_num; g->onground (optional, onground_cap >= P): one byte per point in nalo_ba_set_points' submission order. The
+ *             reference's flag is sticky on the PointHessian: the caller ORs the byte into its objects, the library keeps no per-point state. Without a
+ *             winner every byte is 0 and the count 0.
+ *   Refusals  those of nalo_trk_fit_planes, plus NALO_ERR_ARG for g == NULL, pick == NULL or onground given with onground_cap < P; with mark_window_points
+ *             NALO_ERR_STATE before anything is queued: no window or no points, no point history (nalo_ba_set_point_history), the window's last linearisation
+ *             was not a fix = 1 one, the window is sharded. A refused call leaves the cloud, *pick and every context state as they were.
+ *             NOT a refusal: with append = 1, NALO_ERR_STATE "the level-0 cloud would outgrow its w*h buffer" is nalo_trk_fit_planes' partial failure - the
+ *             clusters before the overflowing one were appended and the records are written; the ground pass does not depend on the append, so *pick, the
+ *             scores and onground are written as well and are valid.
+ *
+ * Host state, caller-owned, in/out; it mirrors where the reference keeps it:
+ *   nalo_ground_tracker  per CoarseTracker OBJECT - the reference has two, swapped every keyframe (coarseTracker, coarseTracker_forNewKF), so a caller keeps two
+ *                        and alternates them. Starts at {-1, -1, 0} (CoarseTracker.cpp:104-106).
+ *   nalo_ground_globals  the globals of util/settings.cpp:36-40: {scale_fix 0, init_height -1, last_ScaleRate -1, last_gp {-1,-1,-1,-1}, old_rate empty}.
+ *   nalo_ground_frame    one per window frame, in window order, starts at zero (last_ground is uninitialised in the reference: DEFINED as zeros).
+ * nalo_ground_*_init set those values.
+ * nalo_ground_update        :609-616 (ground_height taken over when there is a winner; without one the tracker's old ground_height and a zero gp_raw run the
+ *   machine) and :696-816 as written, float arithmetic as written: the first scale_fix call only primes last_ScaleRate / last_gp / old_rate; the outlier branch
+ *   (all five relative differences > 0.25) rewrites groundP from last_gp WITHOUT setting haveground; old_rate is a 7-deep window; with scale_fix and W > 6,
+ *   last_ground of the newest frame = groundP of the first frame from W-2 down to 1 whose groundP[3] != 0. The assert of :794 is not reproduced.
+ *   pick->ran == 0: nothing is touched (the reference returns at :566). NALO_ERR_ARG: a null pointer or W < 1.
+ * nalo_ground_set_global_plane  FullSystem::setglobalplane (FullSystem.cpp:1911-1976): returns 1 and writes gplane, backup_gplane, *lgh when the plane is fixed,
+ *   0 (nothing written) otherwise, NALO_ERR_ARG (negative) on a null pointer. W < max_frames (setting_maxFrames, 7): 0; DEFINED: W < 2: 0 as well (the
+ *   reference would index fhs[W-2]). worldToCam_frame1 = PRE_worldToCam of window frame 1. DEFINED: the norm of the 4-vector difference pi - lastpi
+ *   (lpNorm<2>, :1939: the Euclidean norm over its four components) and the M^T * pih product (all four rows, the last one (0,0,0,1)) are
+ *   accumulated left to right in double; Eigen's order is not observable except at the 0.2 tie.
+ * nalo_ground_local_scale   PlaneOptimize.cpp:203-211: *localscale = (double)lgh / (double)groundP[3], returns 1; 0 (nothing written) when !haveground. The
+ *   caller's condition around it is makeKeyFrame's (:1420,1438): haveground && groundP[3] != 0 && scale_fix && gplanefixed.
+ * nalo_ground_reset_global_plane  FullSystem::resetGlobalPlane (:1979-2001, uncalled in the reference): the newest frame before W-1 with haveground, its plane in
+ *   the world frame; returns that frame's index or -1. worldToCam: W matrices of 12.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_ground_score {
+    float mid_z;           /* 0 when the cluster took no part */
+    float score;
+    int   scored;          /* 1: fitted && n_cloud == n */
+} nalo_ground_score;
+typedef struct nalo_ground_pick {
+    int   ran;             /* 0: fewer than 4 clusters, nothing else is written */
+    int   cluster;         /* record index of the ground, -1: no cluster took part */
+    float gp_raw[4];
+    float ground_height;   /* valid only with a winner */
+    int   n_ground_points; /* temp_gp_num (0 without mark_window_points) */
+} nalo_ground_pick;
+typedef struct nalo_ground_args {
+    int      mark_window_points;
+    uint8_t* onground;     /* optional: one byte per window point, submission order */
+    int      onground_cap; /* >= P when onground is given */
+    nalo_ground_score* scores;   /* optional: cap entries, the first *n_clusters are written */
+} nalo_ground_args;
+int nalo_trk_fit_ground(nalo_ctx* ctx, const nalo_plane_fit_args* fit, const nalo_ground_args* g, int cap, nalo_plane_cluster* out, int* n_clusters,
+                        nalo_ground_pick* pick);
+
+typedef struct nalo_ground_tracker { float ground_height, last_height; int suc_num; } nalo_ground_tracker;
+typedef struct nalo_ground_globals { int scale_fix; float init_height, last_ScaleRate, last_gp[4]; int n_old; float old_rate[7]; } nalo_ground_globals;
+typedef struct nalo_ground_frame { float groundP[4], last_ground[4]; int haveground, scaleFixed; } nalo_ground_frame;
+void nalo_ground_tracker_init(nalo_ground_tracker* t);
+void nalo_ground_globals_init(nalo_ground_globals* g);
+void nalo_ground_frame_init(nalo_ground_frame* f);
+int nalo_ground_update(const nalo_ground_pick* pick, nalo_ground_tracker* tracker, nalo_ground_globals* globals, nalo_ground_frame* frames, int W);
+int nalo_ground_set_global_plane(const nalo_ground_frame* frames, int W, int max_frames, const double worldToCam_frame1[12], double gplane[4],
+                                 double backup_gplane[4], float* lgh);
+int nalo_ground_local_scale(const nalo_ground_frame* frame_newest, float lgh, double* localscale);
+int nalo_ground_reset_global_plane(const nalo_ground_frame* frames, int W, const double* worldToCam, double gplane[4]);
 
 /* ------------------------------------------------------------------------------------------------
  * the immature-point depth filter and point activation that run either side of the BA.

@@ -43,7 +43,8 @@ EXPORTS = [
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
-    "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
+    "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_trk_fit_ground", "nalo_ground_tracker_init", "nalo_ground_globals_init", "nalo_ground_frame_init", "nalo_ground_update",
+    "nalo_ground_set_global_plane", "nalo_ground_local_scale", "nalo_ground_reset_global_plane", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
 ]
 
 
@@ -86,6 +87,36 @@ class PlaneFitArgs(C.Structure):
 PLANE_DTYPE = np.dtype([("mask_value", np.float32), ("n", np.int32), ("n_cloud", np.int32), ("rect", np.int32, 4), ("fitted", np.int32), ("plane", np.float32, 4),
                         ("best_sample", np.int32), ("inliers", np.int32), ("appended", np.int32)])
 assert PLANE_DTYPE.itemsize == C.sizeof(PlaneCluster)
+
+
+class GroundPick(C.Structure):
+    """nalo_ground_pick (include/nalo_gpu.h)"""
+    _fields_ = [("ran", C.c_int), ("cluster", C.c_int), ("gp_raw", C.c_float * 4), ("ground_height", C.c_float), ("n_ground_points", C.c_int)]
+
+
+class GroundArgs(C.Structure):
+    """nalo_ground_args (include/nalo_gpu.h)"""
+    _fields_ = [("mark_window_points", C.c_int), ("onground", c_u8p), ("onground_cap", C.c_int), ("scores", C.c_void_p)]
+
+
+class GroundTracker(C.Structure):
+    """nalo_ground_tracker: one per CoarseTracker object (the reference swaps two every keyframe)"""
+    _fields_ = [("ground_height", C.c_float), ("last_height", C.c_float), ("suc_num", C.c_int)]
+
+
+class GroundGlobals(C.Structure):
+    """nalo_ground_globals: util/settings.cpp:36-40"""
+    _fields_ = [("scale_fix", C.c_int), ("init_height", C.c_float), ("last_ScaleRate", C.c_float), ("last_gp", C.c_float * 4), ("n_old", C.c_int),
+                ("old_rate", C.c_float * 7)]
+
+
+class GroundFrame(C.Structure):
+    """nalo_ground_frame: one per window frame"""
+    _fields_ = [("groundP", C.c_float * 4), ("last_ground", C.c_float * 4), ("haveground", C.c_int), ("scaleFixed", C.c_int)]
+
+
+GROUND_SCORE_DTYPE = np.dtype([("mid_z", np.float32), ("score", np.float32), ("scored", np.int32)])     # nalo_ground_score
+assert GROUND_SCORE_DTYPE.itemsize == 12 and C.sizeof(GroundPick) == 32
 
 
 class MapCloudArgs(C.Structure):
@@ -147,6 +178,84 @@ def constants():
     names, vals = (C.c_char_p * n)(), (C.c_double * n)()
     assert L.nalo_constants(n, names, vals) == n
     return {names[i].decode(): vals[i] for i in range(n)}
+
+
+_HOST_LIB = None
+
+
+def host_lib():
+    """the library for its context-free host functions (nalo_ground_*): dlopen only, no device call, works on a machine without a GPU"""
+    global _HOST_LIB
+    if _HOST_LIB is None:
+        L = C.CDLL(lib_path())
+        _ground_argtypes(L)
+        _HOST_LIB = L
+    return _HOST_LIB
+
+
+def _ground_argtypes(L):
+    L.nalo_ground_tracker_init.argtypes = [C.POINTER(GroundTracker)]
+    L.nalo_ground_globals_init.argtypes = [C.POINTER(GroundGlobals)]
+    L.nalo_ground_frame_init.argtypes = [C.POINTER(GroundFrame)]
+    for f in (L.nalo_ground_tracker_init, L.nalo_ground_globals_init, L.nalo_ground_frame_init):
+        f.restype = None
+    L.nalo_ground_update.argtypes = [C.POINTER(GroundPick), C.POINTER(GroundTracker), C.POINTER(GroundGlobals), C.POINTER(GroundFrame), C.c_int]
+    L.nalo_ground_set_global_plane.argtypes = [C.POINTER(GroundFrame), C.c_int, C.c_int, c_dp, c_dp, c_dp, c_fp]
+    L.nalo_ground_local_scale.argtypes = [C.POINTER(GroundFrame), C.c_float, c_dp]
+    L.nalo_ground_reset_global_plane.argtypes = [C.POINTER(GroundFrame), C.c_int, c_dp, c_dp]
+
+
+def ground_tracker():
+    t = GroundTracker()
+    host_lib().nalo_ground_tracker_init(C.byref(t))
+    return t
+
+
+def ground_globals():
+    g = GroundGlobals()
+    host_lib().nalo_ground_globals_init(C.byref(g))
+    return g
+
+
+def ground_frames(W):
+    """W zeroed nalo_ground_frame, as a ctypes array (window order)"""
+    fr = (GroundFrame * int(W))()
+    for f in fr:
+        host_lib().nalo_ground_frame_init(C.byref(f))
+    return fr
+
+
+def ground_update(pick, tracker, globals_, frames):
+    """nalo_ground_update on the caller's structs, in place (CoarseTracker.cpp:609-616, 696-816)"""
+    rc = host_lib().nalo_ground_update(C.byref(pick), C.byref(tracker), C.byref(globals_), frames, len(frames))
+    if rc != 0:
+        raise NaloError("nalo_ground_update: %d" % rc)
+
+
+def ground_set_global_plane(frames, worldToCam_frame1, max_frames=7):
+    """FullSystem::setglobalplane -> (fixed, gplane[4], backup_gplane[4], lgh); the outputs are None when it did not fix"""
+    gp, bk, lgh = np.zeros(4), np.zeros(4), np.zeros(1, np.float32)
+    M = np.ascontiguousarray(worldToCam_frame1, np.float64).reshape(-1)
+    rc = host_lib().nalo_ground_set_global_plane(frames, len(frames), int(max_frames), _d(M), _d(gp), _d(bk), _f(lgh))
+    if rc < 0:
+        raise NaloError("nalo_ground_set_global_plane: %d" % rc)
+    return (True, gp, bk, np.float32(lgh[0])) if rc == 1 else (False, None, None, None)
+
+
+def ground_local_scale(frame, lgh):
+    """PlaneOptimize.cpp:203-211 -> localscale (a Python float, the C double) or None when the frame has no ground"""
+    out = np.zeros(1)
+    rc = host_lib().nalo_ground_local_scale(C.byref(frame), C.c_float(lgh), _d(out))
+    if rc < 0:
+        raise NaloError("nalo_ground_local_scale: %d" % rc)
+    return float(out[0]) if rc == 1 else None
+
+
+def ground_reset_global_plane(frames, worldToCam):
+    """FullSystem::resetGlobalPlane -> (index of the frame used or -1, gplane[4])"""
+    gp = np.zeros(4)
+    M = np.ascontiguousarray(worldToCam, np.float64).reshape(-1)
+    return int(host_lib().nalo_ground_reset_global_plane(frames, len(frames), _d(M), _d(gp))), gp
 
 
 def load():
@@ -260,6 +369,8 @@ def load():
     L.nalo_trk_fit_planes.argtypes = [vp, C.POINTER(PlaneFitArgs), C.c_int, vp, c_ip]
     L.nalo_dense_fit_planes.argtypes = [vp, C.c_int, C.POINTER(PlaneFitArgs), C.c_int, vp, c_ip]
     L.nalo_plane_fit_members.argtypes = [vp, C.c_int, c_ip, c_ip]
+    L.nalo_trk_fit_ground.argtypes = [vp, C.POINTER(PlaneFitArgs), C.POINTER(GroundArgs), C.c_int, vp, c_ip, C.POINTER(GroundPick)]
+    _ground_argtypes(L)
     L.nalo_undist_set.argtypes = [vp, C.c_int, C.c_int, c_fp, C.c_int, c_fp, C.c_int, c_fp, c_fp]
     L.nalo_frame_upload_raw.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, c_u8p, c_u8p, c_fp]
     L.nalo_frame_upload_raw_async.argtypes = [vp, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, c_fp]
@@ -1099,6 +1210,18 @@ class Context:
     def trk_fit_planes(self, draws, threshold=0.01, min_points=10, append=0, cap=2048):
         """makeMaskDistMap + fitPlane on the level-0 cloud (nalo_trk_fit_planes) -> (records, n_clusters); self.plane_n_clusters holds the count after a refusal too"""
         return self._fit_planes(lambda a, cap_, o, n: self.L.nalo_trk_fit_planes(self.h_, a, cap_, o, n), draws, threshold, min_points, append, cap)
+
+    def trk_fit_ground(self, draws, threshold=0.01, min_points=20, append=0, cap=2048, mark=False, n_points=0, pick=None, want_scores=True):
+        """nalo_trk_fit_planes + the ground choice of setCoarseTrackingRef (nalo_trk_fit_ground) -> (records, n_clusters, pick, scores, onground).
+        min_points defaults to CoarseTracker::fitPlane's 20. mark: also mark the window's points (n_points = P of nalo_ba_set_points; onground is then a uint8
+        array in submission order, else None). pick: a GroundPick to write into (a fresh zeroed one otherwise); scores: a GROUND_SCORE_DTYPE array of
+        n_clusters entries (all zero when pick.ran == 0)."""
+        pick = GroundPick() if pick is None else pick
+        sc = np.zeros(max(cap, 1), GROUND_SCORE_DTYPE) if want_scores else None
+        on = np.zeros(max(int(n_points), 1), np.uint8) if mark else None
+        g = GroundArgs(int(bool(mark)), _u8(on), int(n_points) if mark else 0, None if sc is None else sc.ctypes.data_as(C.c_void_p))
+        rec, n = self._fit_planes(lambda a, cap_, o, n_: self.L.nalo_trk_fit_ground(self.h_, a, C.byref(g), cap_, o, n_, C.byref(pick)), draws, threshold, min_points, append, cap)
+        return rec, n, pick, (None if sc is None else sc[:n].copy()), (None if on is None else on[:int(n_points)])
 
     def dense_fit_planes(self, host_frame, draws, threshold=0.01, min_points=10, cap=2048):
         """the same on the window points and resident immature points of one host frame (nalo_dense_fit_planes)"""

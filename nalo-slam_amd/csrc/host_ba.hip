@@ -85,7 +85,7 @@ struct BAWindow {
     bool prior_carry = false;                                       // nalo_ba_set_prior_carry: the context is ONE continuing EnergyFunctional, every set_window keeps / extends
     // nalo_trk_set_ref_from_window: the newest frame's IN residuals as makeCoarseDepthL0 reads them (ba_trk_ref_inputs)
     bool lin_fixed = false;                                         // the last linearisation was a linearizeAll(true): rs_cpt of the IN residuals to W-1 are its centerProjectedTo
-    std::vector<int> ref_kmap_h; DevBuf<int> ref_kmap; bool ref_kmap_ok = false;   // reference loop order (host, submission order) -> device slot; rebuilt after set_points
+    std::vector<int> ref_kmap_h, ref_k2p_h; DevBuf<int> ref_kmap; bool ref_kmap_ok = false;   // reference loop order (host, submission order) -> device slot; rebuilt after set_points
     DevBuf<float> ref_in;                                           // the gathered inputs {Ku | Kv | new_idepth | HdiF}, P each (not nalo_trk_ref_upload's block)
     // point lifecycle (nalo_ba_set_point_history / nalo_ba_flag_points / nalo_ba_marginalize_flagged)
     DevBuf<int> pt_numgood, snap_numgood; DevBuf<uint32_t> pt_last, snap_last;
@@ -887,7 +887,8 @@ static int ref_kmap_build(nalo_ctx* c, BAWindow& w) {
     for (int p = 0; p < P; ++p) start[w.blk_host_h[w.p2d[p] / kBlk] + 1]++;
     for (int h = 0; h < w.W; ++h) start[h + 1] += start[h];
     w.ref_kmap_h.assign(P, 0);
-    for (int p = 0; p < P; ++p) { const int d = w.p2d[p]; w.ref_kmap_h[start[w.blk_host_h[d / kBlk]]++] = d; }
+    w.ref_k2p_h.assign(P, 0);                                        // entry k -> submission index (nalo_trk_fit_ground's bytes go up in that order)
+    for (int p = 0; p < P; ++p) { const int d = w.p2d[p]; const int k = start[w.blk_host_h[d / kBlk]]++; w.ref_kmap_h[k] = d; w.ref_k2p_h[k] = p; }
     NALO_HIP(c, w.ref_kmap.reserve(P));
     NALO_HIP(c, hipMemcpyAsync(w.ref_kmap.p, w.ref_kmap_h.data(), (size_t)P * 4, hipMemcpyHostToDevice, c->stream));   // the host copy lives until the next rebuild
     w.ref_kmap_ok = true;
@@ -910,6 +911,23 @@ int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev) {
     ba_launch_trk_ref_gather(c->stream, w.dev, w.ref_kmap.p, w.ref_in.p);
     NALO_HIP(c, hipGetLastError());
     *slot = s; *n = P; *dev = w.ref_in.p;
+    return NALO_OK;
+}
+
+// nalo_trk_fit_ground's marking (kernels_plane.hip): the refusals, the map of nalo_trk_set_ref_from_window, the newest frame's row of residual slots, the
+// point history, and for every entry k of the map the submission index of its point (the order the caller's bytes are in)
+int ba_ground_inputs(nalo_ctx* c, GroundWindowView* V, const int** k2p) {
+    const char* who = "nalo_trk_fit_ground: ";
+    if (!c->ba || c->ba->W < 2 || !c->ba->points_set || !c->ba->res_set || c->ba->P == 0) return fail(c, NALO_ERR_STATE, std::string(who) + "no window or no points");
+    BAWindow& w = *c->ba;
+    if (w.hook) return fail(c, NALO_ERR_STATE, std::string(who) + "the window is sharded (a rank holds only its own points)");
+    if (!w.hist_set || !w.dev.pt_last) return fail(c, NALO_ERR_STATE, std::string(who) + "the window carries no point history (nalo_ba_set_point_history)");
+    if (!w.lin_fixed) return fail(c, NALO_ERR_STATE, std::string(who) + "the window's last linearisation was not a linearizeAll(true) (nalo_ba_optimize, nalo_ba_linearize(fix=1))");
+    { const int rc = ref_kmap_build(c, w); if (rc) return rc; }
+    const int P = w.P;
+    *k2p = w.ref_k2p_h.data();                                          // lives until the point list changes
+    const size_t last = (size_t)(w.dev.W - 1) * w.dev.Ppad;              // residual slots [W][Ppad], t-major: the row of the newest frame
+    V->P = P; V->W = w.dev.W; V->kmap = w.ref_kmap.p; V->st_last = w.dev.rs_state + last; V->cpt_last = w.dev.rs_cpt + last; V->pt_last = w.dev.pt_last;
     return NALO_OK;
 }
 

@@ -14,32 +14,13 @@
 #include "nalo_internal.h"
 #include "ba_device.h"
 #include "imm_ctor_body.h"
+#include "ordered_sum.h"
 
 namespace nalo {
 
-__device__ __forceinline__ float iw_lane(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-
 __global__ __launch_bounds__(64) void iw_sum_kernel(const float* __restrict__ iR, int n, float* __restrict__ out) {
-    const int lane = threadIdx.x;
-    float s = 1e-5f;
-    int i = 0;
-    for (; i + 256 <= n; i += 256) {                                    // four full runs: the loads of all four are issued before the first add
-        const float a = iR[i + lane], b = iR[i + 64 + lane], c = iR[i + 128 + lane], d = iR[i + 192 + lane];
-#pragma unroll
-        for (int k = 0; k < 64; ++k) s += iw_lane(a, k);
-#pragma unroll
-        for (int k = 0; k < 64; ++k) s += iw_lane(b, k);
-#pragma unroll
-        for (int k = 0; k < 64; ++k) s += iw_lane(c, k);
-#pragma unroll
-        for (int k = 0; k < 64; ++k) s += iw_lane(d, k);
-    }
-    for (; i < n; i += 64) {                                            // the tail: only the values that exist are added (n is uniform)
-        const float a = i + lane < n ? iR[i + lane] : 0.f;
-        const int m = min(64, n - i);
-        for (int k = 0; k < m; ++k) s += iw_lane(a, k);
-    }
-    if (lane == 0) out[0] = s;
+    const float s = wave_ordered_sum(1e-5f, n, [&](int i) { return iR[i]; });      // ordered_sum.h, shared with fitPlane's mid_z (kernels_plane.hip)
+    if (threadIdx.x == 0) out[0] = s;
 }
 
 // the pixel initializeFromInitializer constructs the ImmaturePoint at (:1610), and whether imm_ctor may read its pattern

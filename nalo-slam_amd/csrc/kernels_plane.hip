@@ -12,12 +12,18 @@
 //   plane_score      one workgroup per (cluster, tile of cloud points), the tile staged in LDS: every candidate triplet's inlier count over the tile
 //   plane_refine     one workgroup per cluster: first largest count, fp64 centroid and covariance of the winner's inliers, Jacobi eigenvectors, the record
 //   (tracker variant with append: trk_append_clusters_kernel, kernels_tracker.hip)
+// nalo_trk_fit_ground enqueues the ground pass of setCoarseTrackingRef (CoarseTracker.cpp:582-625, 669-693) behind the refinement, in the same wait:
+//   ground_score     one wave per cluster: fitPlane's mid_z, a sum whose bits depend on the member order (ordered_sum.h), and its score (:332, 363-373)
+//   ground_choose    ONE wave: the first strictly smallest score, gp_raw, ground_height (:609-616)
+//   ground_paint     the winner's member pixels into a w x h bitmap (integer atomicOr), and out of it again once the marking has read it
+//   ground_mark      one lane per window point: the pixel under its centerProjectedTo against the bitmap (:675-690)
 #include <algorithm>
 #include <climits>
 #include <cstring>
 
 #include "nalo_internal.h"
 #include "ba_device.h"
+#include "ordered_sum.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -354,11 +360,102 @@ __global__ __launch_bounds__(1024) void plane_dense_gather_kernel(const int* __r
     if (tid == 0) hdr[HDR_NIN] = s_base;
 }
 
+
+// ---- the ground pass (nalo_trk_fit_ground). pick words on the device: {ran, cluster, gp_raw[4], ground_height, n_ground_points}, as nalo_ground_pick
+struct GroundParams {
+    int mark, P, W;
+    nalo_ground_score* gs; nalo_ground_pick* pick; unsigned* bits; uint8_t* on;
+    const int* kmap; const uint8_t* st_last; const float4* cpt_last; const uint32_t* pt_last;
+};
+
+__global__ __launch_bounds__(64) void ground_score_kernel(PlaneParams P, GroundParams G) {
+    if (P.hdr[HDR_ERR]) return;
+    const int C = P.hdr[HDR_C];
+    for (int r = blockIdx.x; r < C; r += gridDim.x) {
+        const nalo_plane_cluster c = P.rec[r];
+        nalo_ground_score o = {0.f, 0.f, 0};
+        if (c.fitted && c.n_cloud == c.n) {                             // uniform: fitPlane returned true
+            const float* cz = P.cz + P.f_off[r];                        // every member is in the cloud: cz is in member order
+            const float fn = (float)c.n;
+            const float mid_z = wave_ordered_sum(0.f, c.n, [&](int i) { return cz[i] / fn; });           // :332
+            o.mid_z = mid_z; o.scored = 1;
+            if (c.n < 100 || mid_z < 0.f || c.mask_value < 200.f) o.score = 9999999.0f;                 // :363-368
+            else o.score = ((c.plane[0] + c.plane[2]) * 1000.0f + fabsf(c.plane[3]) * 100.0f) + (float)(100 / c.n);   // :370-373
+        }
+        if (threadIdx.x == 0) G.gs[r] = o;
+    }
+}
+
+__global__ __launch_bounds__(64) void ground_choose_kernel(PlaneParams P, GroundParams G) {
+    if (P.hdr[HDR_ERR]) return;
+    const int lane = threadIdx.x, C = P.hdr[HDR_C];
+    float bs = 3.402823466e+38f; int br = -1;                           // min_score = FLT_MAX (:574)
+    if (C >= 4)
+        for (int r = lane; r < C; r += 64) { const nalo_ground_score g = G.gs[r]; if (g.scored && g.score < bs) { bs = g.score; br = r; } }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float os = __shfl_xor(bs, o); const int orr = __shfl_xor(br, o);
+        if (orr >= 0 && (br < 0 || os < bs || (os == bs && orr < br))) { bs = os; br = orr; }
+    }
+    if (lane == 0) {
+        nalo_ground_pick k = {};
+        k.ran = C >= 4; k.cluster = -1;
+        if (br >= 0) {
+            const nalo_plane_cluster c = P.rec[br];
+            const bool flip = c.plane[1] > 0.f;                         // :611
+            for (int j = 0; j < 4; ++j) k.gp_raw[j] = flip ? -c.plane[j] : c.plane[j];
+            k.ground_height = fabsf(c.plane[3]); k.cluster = br;
+        }
+        *G.pick = k;
+    }
+}
+
+// the winner's members (xx, yy) into the bitmap (set = 1) and out of it (set = 0: every set bit of a touched word is one of this list's)
+__global__ __launch_bounds__(256) void ground_paint_kernel(PlaneParams P, GroundParams G, int set) {
+    if (P.hdr[HDR_ERR]) return;
+    const int r = G.pick->cluster;
+    if (r < 0) return;
+    const int off = P.f_off[r], cnt = P.f_cnt[r];
+    for (int m = blockIdx.x * 256 + threadIdx.x; m < cnt; m += gridDim.x * 256) {
+        const int i = P.order[off + m];
+        const int xx = (int)P.u[i], yy = (int)P.v[i];                   // in range: the point passed plane_key's test
+        const unsigned px = (unsigned)xx + (unsigned)yy * (unsigned)P.w;
+        if (set) atomicOr(&G.bits[px >> 5], 1u << (px & 31u)); else G.bits[px >> 5] = 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void ground_mark_kernel(PlaneParams P, GroundParams G) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    bool on = false;
+    if (k < G.P && !P.hdr[HDR_ERR] && G.pick->cluster >= 0) {
+        const int d = G.kmap[k];
+        const uint8_t s = G.st_last[d];
+        const uint32_t last = G.pt_last[d];
+        // lastResiduals[0].first != 0 && .second == IN (:675), its target the newest frame (:678), and the residual IN at the last fix pass (its rs_cpt is valid).
+        // The last clause guards a history the caller planted: a fix pass removes every residual it finds OOB / OUTLIER and nulls the history's pointer to it
+        // (ba_hist_update_kernel), so with a maintained history the first two clauses imply it and no test can reach it with the history still saying IN.
+        if ((int)(int8_t)(last & 0xFF) == G.W - 1 && ((last >> 16) & 0xFF) == 0u && (s & RS_EXISTS) && (s & RS_STATE_MASK) == 0) {
+            const float4 cp = G.cpt_last[d];
+            const int u = __float2int_rz(cp.x + 0.5f), v = __float2int_rz(cp.y + 0.5f);              // :679-680
+            if (u >= 0 && u < P.w && v >= 0 && v < P.h) { const unsigned px = (unsigned)u + (unsigned)v * (unsigned)P.w; on = (G.bits[px >> 5] >> (px & 31u)) & 1u; }
+        }
+    }
+    if (k < G.P) G.on[k] = on ? 1 : 0;
+    const unsigned long long b = __ballot(on);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&G.pick->n_ground_points, __popcll(b));
+}
+
+// what nalo_trk_fit_ground adds to plane_run: the caller's arguments, the window's view, and where the results come up
+struct GroundRun {
+    const nalo_ground_args* g; nalo_ground_pick* pick; GroundWindowView V; const int* k2p;
+};
+constexpr size_t kGroundPickWords = sizeof(nalo_ground_pick) / 4, kGroundScoreWords = sizeof(nalo_ground_score) / 4;
+static_assert(sizeof(nalo_ground_pick) == 32 && sizeof(nalo_ground_score) == 12, "nalo_ground_pick / nalo_ground_score are packed words");
+
 // The whole chain for n input points (u, v, idp device arrays; in_gather: the dense variant's gather is launched first into the call's own input arrays).
 // dense_boxes: nalo_dense_update_map's pass over the mask is enqueued behind the fit, so that its boxes come up in the fit's wait.
 struct PlaneGather { const int* kmap; int seg; const float4* geo; const uint8_t* flags; const float* imm; int N, host; };
 static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* v, const float* idp, const PlaneGather* g, int n, const float* mask,
-                     const nalo_plane_fit_args* a, bool append, int cap, nalo_plane_cluster* out, int* n_clusters, bool dense_boxes = false) {
+                     const nalo_plane_fit_args* a, bool append, int cap, nalo_plane_cluster* out, int* n_clusters, bool dense_boxes = false, const GroundRun* gr = nullptr) {
     const std::string W(who);
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "plane_fit");
@@ -369,9 +466,18 @@ static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* 
     constexpr size_t RW = sizeof(nalo_plane_cluster) / 4;
     // words: 12 arrays of n | raw | f_start f_cnt f_desc f_off | tile_start | hdr | counts | draws | records
     const size_t o_raw = 12 * N, o_f = o_raw + 3 * kPlaneMaxClusters, o_tile = o_f + 4 * kPlaneMaxClusters, o_hdr = o_tile + kPlaneMaxClusters + 1,
-                 o_cnt = o_hdr + HDR_WORDS, o_draws = o_cnt + (size_t)nfit * S, o_rec = o_draws + 3 * (size_t)S, total = o_rec + RW * kPlaneMaxClusters;
+                 o_cnt = o_hdr + HDR_WORDS, o_draws = o_cnt + (size_t)nfit * S, o_rec = o_draws + 3 * (size_t)S, o_gpick = o_rec + RW * kPlaneMaxClusters,
+                 o_gs = o_gpick + kGroundPickWords, o_gon = o_gs + kGroundScoreWords * kPlaneMaxClusters;
+    const int GP = gr && gr->g->mark_window_points ? gr->V.P : 0;     // window points the ground pass marks
+    const size_t gon_words = ((size_t)GP + 3) / 4, total = gr ? o_gon + gon_words : o_gpick;
     NALO_HIP(c, c->plane_w.reserve(total));
-    NALO_HIP(c, c->plane_host.reserve(3 * (size_t)S + HDR_WORDS + RW * kPlaneMaxClusters));
+    const size_t h_ground = 3 * (size_t)S + HDR_WORDS + RW * kPlaneMaxClusters;      // the ground pass' words in the pinned block: pick | scores | bytes
+    NALO_HIP(c, c->plane_host.reserve(h_ground + (gr ? kGroundPickWords + kGroundScoreWords * kPlaneMaxClusters + gon_words : 0)));
+    const size_t bit_words = ((size_t)c->w * c->h + 31) / 32;
+    if (GP > 0 && c->ground_bits.cap < bit_words) {                    // once per context: every call leaves the bitmap all zero
+        NALO_HIP(c, c->ground_bits.reserve(bit_words));
+        NALO_HIP(c, hipMemsetAsync(c->ground_bits.p, 0, bit_words * 4, c->stream));
+    }
     unsigned* wb = c->plane_w.p;
     PlaneParams P;
     P.n = n; P.w = c->w; P.h = c->h; P.S = S; P.min_fit = std::max(a->min_points, 3); P.nfit = nfit; P.threshold = a->threshold; P.mask = mask;
@@ -401,6 +507,20 @@ static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* 
         plane_score_kernel<<<512, 256, 0, c->stream>>>(P);
         plane_refine_kernel<<<256, 256, 0, c->stream>>>(P);
         NALO_HIP(c, hipGetLastError());
+        if (gr) {
+            ProfScope ps(c, "ground_pass");
+            GroundParams G = {};
+            G.mark = GP > 0; G.P = GP; G.W = gr->V.W; G.gs = (nalo_ground_score*)(wb + o_gs); G.pick = (nalo_ground_pick*)(wb + o_gpick); G.bits = c->ground_bits.p;
+            G.on = (uint8_t*)(wb + o_gon); G.kmap = gr->V.kmap; G.st_last = gr->V.st_last; G.cpt_last = gr->V.cpt_last; G.pt_last = gr->V.pt_last;
+            ground_score_kernel<<<256, 64, 0, c->stream>>>(P, G);
+            ground_choose_kernel<<<1, 64, 0, c->stream>>>(P, G);
+            if (GP > 0) {
+                ground_paint_kernel<<<64, 256, 0, c->stream>>>(P, G, 1);
+                ground_mark_kernel<<<(GP + 255) / 256, 256, 0, c->stream>>>(P, G);
+                ground_paint_kernel<<<64, 256, 0, c->stream>>>(P, G, 0);
+            }
+            NALO_HIP(c, hipGetLastError());
+        }
         if (append) {
             const FrameSlot& s = c->slots[c->slot_ref];
             const int rc = trk_append_clusters_launch(c, s.mask.p, s.dI[0].p, P.rec, P.hdr, capr); if (rc) return rc;
@@ -410,6 +530,8 @@ static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* 
     int* h_hdr = hst + 3 * (size_t)S;
     NALO_HIP(c, hipMemcpyAsync(h_hdr, P.hdr, HDR_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
     if (capr > 0) NALO_HIP(c, hipMemcpyAsync(h_hdr + HDR_WORDS, P.rec, (size_t)capr * sizeof(nalo_plane_cluster), hipMemcpyDeviceToHost, c->stream));
+    int* h_g = hst + h_ground;
+    if (gr && n > 0) NALO_HIP(c, hipMemcpyAsync(h_g, wb + o_gpick, (o_gon + gon_words - o_gpick) * 4, hipMemcpyDeviceToHost, c->stream));     // pick | scores | bytes
     NALO_HIP(c, hipStreamSynchronize(c->stream));                       // the call's one wait
     const int C = h_hdr[HDR_C];
     *n_clusters = C;
@@ -418,6 +540,17 @@ static int plane_run(nalo_ctx* c, const char* who, const float* u, const float* 
     c->plane_last_n = n; c->plane_last_members = h_hdr[HDR_MEMBERS];
     if (C > cap) return fail(c, NALO_ERR_ARG, W + ": cap too small (*n_clusters holds the need)");
     if (C > 0) std::memcpy(out, h_hdr + HDR_WORDS, (size_t)C * sizeof(nalo_plane_cluster));
+    if (gr) {                                                           // fewer than 4 clusters: ran = 0 and nothing else (CoarseTracker.cpp:563-567)
+        if (n <= 0 || C < 4) gr->pick->ran = 0;
+        else {
+            std::memcpy(gr->pick, h_g, sizeof(nalo_ground_pick));
+            if (gr->g->scores) std::memcpy(gr->g->scores, h_g + kGroundPickWords, (size_t)C * sizeof(nalo_ground_score));
+            if (GP > 0 && gr->g->onground) {
+                const uint8_t* on = (const uint8_t*)(h_g + kGroundPickWords + kGroundScoreWords * kPlaneMaxClusters);
+                for (int k = 0; k < GP; ++k) gr->g->onground[gr->k2p[k]] = on[k];
+            }
+        }
+    }
     if (append && n > 0) {
         c->pc_n[0] = h_hdr[HDR_PCN];
         if (h_hdr[HDR_ERR] & PERR_CLOUD_FULL) return fail(c, NALO_ERR_STATE, W + ": the level-0 cloud would outgrow its w*h buffer (the clusters before that one were appended)");
@@ -464,6 +597,23 @@ int nalo_trk_fit_planes(nalo_ctx* c, const nalo_plane_fit_args* a, int cap, nalo
     const FrameSlot& s = c->slots[c->slot_ref];
     if (!s.mask.p) return fail(c, NALO_ERR_STATE, "nalo_trk_fit_planes: the reference frame was uploaded without a mask");
     return plane_run(c, "nalo_trk_fit_planes", c->pc_u[0].p, c->pc_v[0].p, c->pc_id[0].p, nullptr, c->pc_n[0], s.mask.p, a, a->append != 0, cap, out, n_clusters);
+}
+
+int nalo_trk_fit_ground(nalo_ctx* c, const nalo_plane_fit_args* a, const nalo_ground_args* g, int cap, nalo_plane_cluster* out, int* n_clusters, nalo_ground_pick* pick) {
+    if (!c) return NALO_ERR_ARG;
+    if (!g || !pick) return fail(c, NALO_ERR_ARG, "nalo_trk_fit_ground: ground arguments and pick are required");
+    int rc = plane_check_args(c, "nalo_trk_fit_ground", a, cap, out, n_clusters); if (rc) return rc;
+    if (c->slot_ref < 0 || !c->slots[c->slot_ref].valid || !c->pc_u[0].p || c->pc_n[0] <= 0) return fail(c, NALO_ERR_STATE, "nalo_trk_fit_ground: no level-0 cloud (nalo_trk_set_ref / nalo_trk_set_pc)");
+    const FrameSlot& s = c->slots[c->slot_ref];
+    if (!s.mask.p) return fail(c, NALO_ERR_STATE, "nalo_trk_fit_ground: the reference frame was uploaded without a mask");
+    GroundRun gr = {};
+    gr.g = g; gr.pick = pick;
+    if (g->mark_window_points) {
+        rc = ba_ground_inputs(c, &gr.V, &gr.k2p); if (rc) return rc;
+        if (g->onground && g->onground_cap < gr.V.P) return fail(c, NALO_ERR_ARG, "nalo_trk_fit_ground: onground_cap is below the window's point count");
+    }
+    *n_clusters = 0;
+    return plane_run(c, "nalo_trk_fit_ground", c->pc_u[0].p, c->pc_v[0].p, c->pc_id[0].p, nullptr, c->pc_n[0], s.mask.p, a, a->append != 0, cap, out, n_clusters, false, &gr);
 }
 
 int nalo_dense_fit_planes(nalo_ctx* c, int host_frame, const nalo_plane_fit_args* a, int cap, nalo_plane_cluster* out, int* n_clusters) {

@@ -170,6 +170,7 @@ struct nalo_ctx {
     // ---- mask clusters and their planes (kernels_plane.hip): the call's device scratch (the member lists of the last call stay in it), rocPRIM's sort storage,
     // the pinned block the draws go down and the records come up through; plane_last_n = -1: no completed call
     nalo::DevBuf<unsigned> plane_w; nalo::DevBuf<unsigned char> plane_sort; nalo::HostBuf<int> plane_host; int plane_last_n = -1, plane_last_members = 0;
+    nalo::DevBuf<unsigned> ground_bits;      // nalo_trk_fit_ground's w x h bitmap of ground pixels: zeroed when allocated, and left all zero by every call
 
     // ---- BA (opaque; defined in host_ba.hip)
     nalo::BAWindow* ba = nullptr;
@@ -301,6 +302,9 @@ int ba_trk_ref_inputs(nalo_ctx* c, int* slot, int* n, const float** dev);
 // host_ba.hip: nalo_dense_fit_planes' window half. The device slots of host_frame's points in submission order (*kmap, *seg entries: a segment of the map
 // nalo_trk_set_ref_from_window keeps), how many of them are valid (the host's mirror of the flags), the arrays the gather reads and the frame's slot
 int ba_plane_inputs(nalo_ctx* c, int host_frame, int* slot, const int** kmap, int* seg, int* n_valid, const float4** geo, const uint8_t** flags);
+// host_ba.hip: nalo_trk_fit_ground's window half (the marking of CoarseTracker.cpp:669-693). Entry k of kmap is the k-th point in (host, submission) order
+struct GroundWindowView { int P, W; const int* kmap; const uint8_t* st_last; const float4* cpt_last; const uint32_t* pt_last; };
+int ba_ground_inputs(nalo_ctx* c, GroundWindowView* V, const int** k2p);      // k2p[k]: submission index of entry k, built with the map
 // ---- the map (host_map.hip, kernels_map.hip): removed points archived on the device, and the clouds the reference publishes per keyframe
 // nalo_ba_marginalize_flagged's append: the window's arrays as the kernels read them. Entry k of kmap is the k-th point in (host, submission) order.
 struct MapAppendDev {
