@@ -1129,6 +1129,74 @@ typedef struct nalo_window_plot_args {
 int nalo_map_window_plot(nalo_ctx* ctx, nalo_window_plot_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * The 3-D panel of PangolinDSOViewer (IOWrapper/Pangolin/PangolinDSOViewer.cpp:186-236: per keyframe drawCam, refreshPC, drawPC(1); the dense clouds; the current
+ * camera; drawConstraints :448-526; KeyFrameDisplay::drawCam / drawPC, KeyFrameDisplay.cpp:609-722) for a card without OpenGL or a display: one call, one wait, an
+ * RGB image (and optionally its depth) up. Everything it draws is resident: the window's points, the immature set, the archive of removed points, the dense
+ * archive, the graph's counts. GL's rasterisation is implementation defined, so this is a DEFINED rasteriser; tests/render_model.py is its literal model. The call
+ * has no side effect on window, archives, immature set, tracker or graph.
+ *
+ *   Transforms  per listed frame f, M_f = (float)(viewFromWorld . camToWorld_f): the product on the host in double, entry (r, c) =
+ *               (V[r][0] C[0][c] + V[r][1] C[1][c]) + V[r][2] C[2][c], then + V[r][3] for c = 3, then the cast. V_f = (float)viewFromWorld serves the world-space
+ *               lines. Applying a transform to (x, y, z) is, in float with every operation rounded (no contraction), row r: ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3].
+ *   Points      the records of a listed frame are exactly nalo_map_frame_cloud's for that frame (status 0 from the resident immature set when with_immature, 1 from
+ *               the window, 2 and 3 from the archive), its filter (display_mode, scaledTH, absTH, minRelBS) and its colours, by the same device functions. Each
+ *               survivor gives the 8 vertices of the no-jitter form (z = depth; the viewer's rand() jitter is not reproduced). With with_dense every dense-archive
+ *               point of the frame with !(idepth < 0) gives one vertex, as nalo_map_dense_cloud's no-jitter form. A vertex goes through M_f to (xv, yv, zv) and is
+ *               drawn iff zv > znear && zv < zfar and, with u = fx * (xv / zv) + cx and v = fy * (yv / zv) + cy in float, u >= 0 && u < vw && v >= 0 && v < vh
+ *               (NaNs fall out through the comparisons). It lands on pixel ((int)floorf(u), (int)floorf(v)) with depth zv. Point size 1.
+ *   Lines       one list of segments with float endpoints. drawCam's eight segments per listed frame when show_kf_cams (blue, sz = 0.1f, width 1) and for
+ *               currentCamToWorld when show_current_cam (red, sz = 0.2f, width 2): apex (0, 0, 0) and the corners (sz * (0 - cx) / fx, sz * (0 - cy) / fy, sz) ..
+ *               (sz * (w - 1 - cx) / fx, sz * (h - 1 - cy) / fy, sz) in float as written at :630-649, from the window's current calibration (value_scaledf) and
+ *               the level-0 size, through M_f. The constraints, from nalo_map_graph_connections' list with the rules of :458-491: a connection with an end that
+ *               is not in frames[] is skipped (the reference's `== 0`); nAct == 0 && nMarg > 0 draws green, width 1, when show_all_constraints; nAct > 0 draws
+ *               blue, width 3, when show_active_constraints; the ends are the translations of camToWorld cast to float. show_trajectory: the strip through the
+ *               listed frames' translations, red, width 3; show_full_trajectory: the strip through all_poses, green, width 3. These go through V_f.
+ *               From view space on a segment is handled in double. It is dropped when a coordinate is not finite or both z <= znear. Otherwise an end with
+ *               z < znear is replaced by A + t (B - A), t = (znear - za) / (zb - za), A and B the ends as given. The ends are projected, u = fx * (x / z) + cx;
+ *               a segment with a projection that is not finite is dropped. n_segments counts the segments that remain. n = ceil(max(|ub - ua|, |vb - va|)).
+ *               The parameter range [t0, t1] of the segment inside [-2, vw + 2] x [-2, vh + 2] comes from a Liang-Barsky clip (edges in the order left, right,
+ *               top, bottom; p = -du, du, -dv, dv; q = ua + 2, (vw + 2) - ua, va + 2, (vh + 2) - va; r = q / p); an empty range gives no sample. n == 0: the one
+ *               sample k = 0, t = 0. Else k = k0 .. k1 with k0 = ceil(t0 n), k1 = floor(t1 n), at most vw + vh + 10 of them (the first ones), so the work is
+ *               bounded whatever the ends are. Sample k: t = k / n, (u, v) = (ua + t (ub - ua), va + t (vb - va)), depth = (float)(1 / ((1 - t) / za + t / zb));
+ *               it is kept iff depth > znear && depth < zfar (n_line_samples counts these) and paints, for width L, the pixels (floor(u) + ox, floor(v) + oy),
+ *               ox, oy in [-(L / 2), (L - 1) / 2], that lie inside the image (square caps, no anti-aliasing).
+ *   Depth test  per pixel the candidate with the smallest depth wins (a positive float orders like its bit pattern); among equal depths the smallest
+ *               (R << 16) | (G << 8) | B. One 64-bit integer minimum per candidate: no float atomic, no submission order, the same bytes on every run. A pixel
+ *               without a candidate gets background, and +inf in depth.
+ *   Counts      n_vertices: the vertices of the survivors of refreshPC's filter (8 per sparse survivor, 1 per dense one; without with_dense the sum of
+ *               nalo_map_frame_cloud's n over the listed frames); n_drawn_points: those inside the frustum and the viewport; n_segments, n_line_samples: above.
+ *   Refusals    nothing is enqueued; rgb, depth and every context state stay as they were (the four counts are zeroed). NALO_ERR_ARG: NULL ctx / args / rgb; vw or
+ *               vh < 1, vw * vh > 2^26; a camera value or viewFromWorld entry that is not finite; znear <= 0 or zfar <= znear; n_frames < 0 or frames NULL with
+ *               n_frames > 0 (all_poses alike); a frame_id listed twice, or one that is neither in the window nor in either archive; sparsity > 1.
+ *               NALO_ERR_STATE: no window (its CalibHessian is the clouds' calibration); a listed window frame while the window's points are unset (between
+ *               nalo_ba_marginalize_frame and the carry); a constraint flag with the graph off (and nalo_map_graph's own refusals); with_dense with the dense
+ *               archive off; a sharded window; a context whose exchange failed. n_frames == 0 is legal: the background and the world-space lines.
+ *   Cost        three kernels on the context's stream (points, lines, resolve) and ONE wait; with a constraint flag nalo_map_graph's launch and wait come first.
+ *               The key plane cleans itself: it is filled only when it is allocated or grown.
+ * nalo_view_look_at (host only): pangolin::ModelViewLookAt in double - z = (eye - target) / |eye - target|, x = up x z, y = z x x, x and y normalised, lengths as
+ *   sqrt((a a + b b) + c c) - converted to x right, y down, z forward: rows x, -y, -z, translation row r = -((R[r][0] ex + R[r][1] ey) + R[r][2] ez). The viewer's
+ *   start view is eye (0, -5, -10), target (0, 0, 0), up (0, -1, 0). NALO_ERR_ARG (nothing written) where pangolin throws: x or y of length 0, or not finite.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_view_frame { int frame_id; double camToWorld[12]; } nalo_view_frame;   /* a KeyFrameDisplay: id + the pose it was last set with */
+typedef struct nalo_map_render_args {
+    int vw, vh;                       /* output size */
+    float fx, fy, cx, cy, znear, zfar;/* the panel's camera: the reference uses 400, 400, w/2, h/2, 0.1, 1000 (PangolinDSOViewer.cpp:95) */
+    double viewFromWorld[12];         /* row-major 3x4, x right, y down, z forward */
+    int n_frames; const nalo_view_frame* frames;      /* `keyframes`, in the viewer's order */
+    int display_mode, with_immature, sparsity; float scaledTH, absTH, minRelBS;   /* as nalo_map_cloud_args */
+    int with_dense;                   /* the second loop, :229-233 */
+    int show_kf_cams, show_current_cam; double currentCamToWorld[12];
+    int show_active_constraints, show_all_constraints, show_trajectory, show_full_trajectory;
+    int n_all_poses; const float* all_poses;          /* allFramePoses [n][3] */
+    uint8_t background[3];
+    uint8_t* rgb;                     /* out, vh*vw*3, row 0 on top, R,G,B */
+    float* depth;                     /* out, optional, vh*vw: the winner's view-space z, +inf where nothing was drawn */
+    long long n_vertices, n_drawn_points, n_segments, n_line_samples;   /* out */
+} nalo_map_render_args;
+int nalo_map_render(nalo_ctx* ctx, nalo_map_render_args* args);
+int nalo_view_look_at(const double eye[3], const double target[3], const double up[3], double viewFromWorld[12]);   /* host only */
+
+/* ------------------------------------------------------------------------------------------------
  * densemap=1: DenseMapping::updateMap (FullSystem/MapPoint.cpp:234-332, call site FullSystem.cpp:1488-1496) in one call, and FrameHessian::mapPoints as a
  * device archive beside the sparse one. The per-cluster route (nalo_dense_fit_planes, then nalo_dense_make_map per cluster) stays as it is.
  *

@@ -38,7 +38,7 @@ EXPORTS = [
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
-    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot",
+    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
@@ -161,6 +161,22 @@ class WindowPlotArgs(C.Structure):
                 ("min_used", C.c_float), ("max_used", C.c_float)]
 
 
+class ViewFrame(C.Structure):
+    """nalo_view_frame (include/nalo_gpu.h)"""
+    _fields_ = [("frame_id", C.c_int), ("camToWorld", C.c_double * 12)]
+
+
+class MapRenderArgs(C.Structure):
+    """nalo_map_render_args (include/nalo_gpu.h)"""
+    _fields_ = [("vw", C.c_int), ("vh", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("znear", C.c_float), ("zfar", C.c_float),
+                ("viewFromWorld", C.c_double * 12), ("n_frames", C.c_int), ("frames", C.POINTER(ViewFrame)), ("display_mode", C.c_int), ("with_immature", C.c_int),
+                ("sparsity", C.c_int), ("scaledTH", C.c_float), ("absTH", C.c_float), ("minRelBS", C.c_float), ("with_dense", C.c_int), ("show_kf_cams", C.c_int),
+                ("show_current_cam", C.c_int), ("currentCamToWorld", C.c_double * 12), ("show_active_constraints", C.c_int), ("show_all_constraints", C.c_int),
+                ("show_trajectory", C.c_int), ("show_full_trajectory", C.c_int), ("n_all_poses", C.c_int), ("all_poses", c_fp), ("background", C.c_uint8 * 3),
+                ("rgb", c_u8p), ("depth", c_fp), ("n_vertices", C.c_longlong), ("n_drawn_points", C.c_longlong), ("n_segments", C.c_longlong),
+                ("n_line_samples", C.c_longlong)]
+
+
 class Settings(C.Structure):
     """nalo_settings (include/nalo_gpu.h)"""
     _fields_ = [("forceAcceptStep", C.c_int), ("affineOptModeA", C.c_double), ("affineOptModeB", C.c_double), ("minOptIterations", C.c_int)]
@@ -189,8 +205,19 @@ def host_lib():
     if _HOST_LIB is None:
         L = C.CDLL(lib_path())
         _ground_argtypes(L)
+        L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
         _HOST_LIB = L
     return _HOST_LIB
+
+
+def view_look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)):
+    """nalo_view_look_at: pangolin::ModelViewLookAt as viewFromWorld [3][4] (x right, y down, z forward) for map_render; needs no device. The viewer starts at
+    eye (0, -5, -10)"""
+    e, t, u = (np.ascontiguousarray(x, np.float64).reshape(3) for x in (eye, target, up))
+    out = np.zeros(12, np.float64)
+    if host_lib().nalo_view_look_at(e.ctypes.data_as(c_dp), t.ctypes.data_as(c_dp), u.ctypes.data_as(c_dp), out.ctypes.data_as(c_dp)) != 0:
+        raise NaloError("nalo_view_look_at: degenerate view (up parallel to the viewing direction, eye == target, or a value that is not finite)")
+    return out.reshape(3, 4)
 
 
 def _ground_argtypes(L):
@@ -336,6 +363,8 @@ def load():
     L.nalo_map_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
     L.nalo_map_world_points_host.argtypes = [C.c_int, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp]
     L.nalo_map_frame_cloud.argtypes = [vp, C.POINTER(MapCloudArgs)]
+    L.nalo_map_render.argtypes = [vp, C.POINTER(MapRenderArgs)]
+    L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
     L.nalo_map_graph_enable.argtypes = [vp, C.c_int]
     L.nalo_map_graph.argtypes = [vp, vp, C.c_int, c_ip]
     L.nalo_map_graph_connections.argtypes = [vp, vp, C.c_int, c_ip]
@@ -1028,6 +1057,43 @@ class Context:
         for k in ("min_new", "max_new", "min_used", "max_used"):
             out[k] = np.float32(getattr(a, k))
         return out
+
+    def map_render_args(self, vw, vh, view, frames=(), fx=400.0, fy=400.0, cx=None, cy=None, znear=0.1, zfar=1000.0, display_mode=1, scaledTH=1e10, absTH=1e10,
+                        minRelBS=0.0, with_immature=True, sparsity=1, with_dense=False, show_kf_cams=False, current_cam=None, show_active_constraints=False,
+                        show_all_constraints=False, show_trajectory=False, all_poses=None, background=(255, 255, 255)):
+        """a filled MapRenderArgs without outputs, and the arrays it points into (keep them alive). frames: [(frame_id, camToWorld 3x4)]; current_cam: a 3x4 pose
+        (show_current_cam) or None; all_poses: [n][3] (show_full_trajectory) or None; cx, cy default to vw / 2, vh / 2 as in the viewer"""
+        a = MapRenderArgs()
+        a.vw, a.vh, a.fx, a.fy, a.znear, a.zfar = int(vw), int(vh), float(fx), float(fy), float(znear), float(zfar)
+        a.cx, a.cy = float(vw / 2 if cx is None else cx), float(vh / 2 if cy is None else cy)
+        a.viewFromWorld = (C.c_double * 12)(*np.asarray(view, np.float64).reshape(12))
+        fr = (ViewFrame * max(len(frames), 1))()
+        for i, (fid, m) in enumerate(frames):
+            fr[i].frame_id = int(fid)
+            fr[i].camToWorld = (C.c_double * 12)(*np.asarray(m, np.float64).reshape(12))
+        a.n_frames, a.frames = len(frames), fr
+        a.display_mode, a.with_immature, a.sparsity, a.with_dense = int(display_mode), int(bool(with_immature)), int(sparsity), int(bool(with_dense))
+        a.scaledTH, a.absTH, a.minRelBS = float(scaledTH), float(absTH), float(minRelBS)
+        a.show_kf_cams, a.show_current_cam = int(bool(show_kf_cams)), int(current_cam is not None)
+        if current_cam is not None:
+            a.currentCamToWorld = (C.c_double * 12)(*np.asarray(current_cam, np.float64).reshape(12))
+        a.show_active_constraints, a.show_all_constraints, a.show_trajectory = int(bool(show_active_constraints)), int(bool(show_all_constraints)), int(bool(show_trajectory))
+        poses = None if all_poses is None else np.ascontiguousarray(all_poses, np.float32).reshape(-1, 3)
+        a.show_full_trajectory, a.n_all_poses, a.all_poses = int(poses is not None), 0 if poses is None else len(poses), _f(poses)
+        a.background = (C.c_uint8 * 3)(*[int(b) for b in background])
+        return a, (fr, poses)
+
+    def map_render(self, vw, vh, view, frames=(), want_depth=True, **kw):
+        """the viewer's 3-D panel on the device (nalo_map_render; keywords: map_render_args) -> dict(rgb (vh, vw, 3) uint8, depth (vh, vw) float32 or None,
+        n_vertices, n_drawn_points, n_segments, n_line_samples)"""
+        a, keep = self.map_render_args(vw, vh, view, frames, **kw)
+        rgb = np.zeros((int(vh), int(vw), 3), np.uint8)
+        depth = np.zeros((int(vh), int(vw)), np.float32) if want_depth else None
+        a.rgb, a.depth = _u8(rgb), _f(depth)
+        self._ck(self.L.nalo_map_render(self.h_, C.byref(a)))
+        del keep
+        return dict(rgb=rgb, depth=depth, n_vertices=int(a.n_vertices), n_drawn_points=int(a.n_drawn_points), n_segments=int(a.n_segments),
+                    n_line_samples=int(a.n_line_samples))
 
     # ---- the keyframe graph: EnergyFunctional::connectivityMap from the device chain
     def map_graph_enable(self, on=True):

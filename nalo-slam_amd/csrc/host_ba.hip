@@ -959,7 +959,7 @@ int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V) {
     BAWindow& w = *c->ba;
     *V = MapWindowView{};
     V->widx = -1; V->sharded = w.hook != nullptr;
-    for (int i = 0; i < 4; ++i) V->ci[i] = w.c_scaledi[i];
+    for (int i = 0; i < 4; ++i) { V->ci[i] = w.c_scaledi[i]; V->cf[i] = w.c_scaledf[i]; }
     for (int i = 0; i < w.W && V->widx < 0; ++i) if (w.frames[i].frameID == frame_id) V->widx = i;
     V->pts_ok = w.points_set && !w.hook;
     if (V->widx < 0 || !V->pts_ok) return NALO_OK;

@@ -31,6 +31,11 @@ struct MapArchive {
     // colours, the images, the select's results, the ring counters (two buffers, the idle one zero) and the pinned block results, counters and images come up through
     HostBuf<PlotSeg> wp_seg_h; DevBuf<PlotSeg> wp_seg_d; DevBuf<unsigned> wp_key, wp_col, wp_res; DevBuf<uint8_t> wp_bgr; DevBuf<int> wp_cnt; int wp_cnt_buf = 0;
     HostBuf<uint8_t> wp_host; bool wp_key_clean = false;
+    // the 3-D panel (nalo_map_render): the transform table and the clipped segments (pinned staging + device), the 64-bit key plane (all-ones between calls: the
+    // resolve pass leaves it so), the counters (two buffers, the idle one zero), the images and the pinned block counters and images come up through
+    HostBuf<float> mr_M_h; DevBuf<float> mr_M_d, mr_depth; HostBuf<MrLine> mr_lines_h; DevBuf<MrLine> mr_lines_d;
+    DevBuf<unsigned long long> mr_key, mr_cnt; int mr_cnt_buf = 0; bool mr_key_clean = false;
+    DevBuf<uint8_t> mr_rgb; HostBuf<uint8_t> mr_host;
 };
 
 bool map_on(const nalo_ctx* c) { return c->map && c->map->on; }
@@ -98,11 +103,13 @@ void map_append_commit(nalo_ctx* c) {
     }
 }
 
-// the archive runs of a frame as segments of `kind` behind `start`
-static void map_push_runs(const MapArchive& m, const MapFrame* f, int kind, std::vector<MapSeg>& segs, int& start) {
+// the runs of a frame in an archive (MapArchive / DenseArchive: the same position -> chunk mapping) as segments of `kind` for listed frame `frame` behind `start`.
+// start is 64 bits wide so that a caller can refuse a list an int cannot index; nothing is pushed past that point
+template <typename Archive, typename Frame>
+static void map_push_runs(const Archive& m, const Frame* f, int kind, std::vector<MapSeg>& segs, long long& start, int frame = 0) {
     if (!f) return;
     for (const MapRun& r : f->runs) {
-        segs.push_back({m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, start, r.n, kind, 0});
+        if (start <= INT32_MAX) segs.push_back({m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, (int)start, r.n, kind, frame});
         start += r.n;
     }
 }
@@ -214,6 +221,21 @@ static int graph_entries(nalo_ctx* c, const char* who, std::vector<nalo_graph_ed
     }
     return NALO_OK;
 }
+// PangolinDSOViewer::publishGraph (PangolinDSOViewer.cpp:528-571): keys with host < target in key order, the backward pair from the inverse key
+static int graph_connections(nalo_ctx* c, const char* who, std::vector<nalo_graph_connection>& C) {
+    std::vector<nalo_graph_edge> E;
+    { const int rc = graph_entries(c, who, E); if (rc) return rc; }
+    std::map<uint64_t, const nalo_graph_edge*> by_key;
+    for (const nalo_graph_edge& e : E) by_key[graph_key(e.host_id, e.target_id)] = &e;
+    C.clear();
+    for (const nalo_graph_edge& e : E) {
+        if (e.host_id >= e.target_id) continue;
+        const auto inv = by_key.find(graph_key(e.target_id, e.host_id));
+        const nalo_graph_edge* b = inv == by_key.end() ? nullptr : inv->second;      // (pairs are created in both directions: the reference's .at() never throws)
+        C.push_back({e.host_id, e.target_id, e.act, b ? b->act : 0, e.marg, b ? b->marg : 0});
+    }
+    return NALO_OK;
+}
 
 }  // namespace nalo
 
@@ -291,10 +313,10 @@ int nalo_map_world_points(nalo_ctx* c, int frame_id, const double camToWorld[12]
     { int rc = ba_map_view(c, frame_id, &V); if (rc) return rc; }
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "map_world_points");
-    std::vector<MapSeg> segs; int total = 0;
+    std::vector<MapSeg> segs; long long total = 0;
     map_push_runs(m, &it->second, 2, segs, total);
     MapWorldDev D{};
-    { int rc = map_send_segs(c, m, segs, total, D.S); if (rc) return rc; }
+    { int rc = map_send_segs(c, m, segs, (int)total, D.S); if (rc) return rc; }
     NALO_HIP(c, m.wxyz.reserve(3 * (size_t)*n)); NALO_HIP(c, m.wxyz_h.reserve(3 * (size_t)*n));
     std::memcpy(D.ci, V.ci, sizeof(D.ci)); std::memcpy(D.m, camToWorld, sizeof(D.m)); D.xyz = m.wxyz.p; D.cap = *n;
     { int rc = map_world_launch(c, D); if (rc) return rc; }
@@ -335,14 +357,15 @@ int nalo_map_frame_cloud(nalo_ctx* c, nalo_map_cloud_args* a) {
     if (records == 0) return NALO_OK;
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "map_frame_cloud");
-    std::vector<MapSeg> segs; int total = 0;
-    if (imm && n_imm) { segs.push_back({nullptr, total, c->imm_res_n, 0, 0}); total += c->imm_res_n; }
-    if (V.widx >= 0 && V.seg) { segs.push_back({V.kmap, total, V.seg, 1, 0}); total += V.seg; }
+    std::vector<MapSeg> segs; long long total = 0;
+    if (imm && n_imm) { segs.push_back({nullptr, (int)total, c->imm_res_n, 0, 0}); total += c->imm_res_n; }
+    if (V.widx >= 0 && V.seg) { segs.push_back({V.kmap, (int)total, V.seg, 1, 0}); total += V.seg; }
     map_push_runs(m, f, 2, segs, total);
     map_push_runs(m, f, 3, segs, total);
     MapCloudDev D{};
-    { int rc = map_send_segs(c, m, segs, total, D.S); if (rc) return rc; }
-    D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n; D.S.widx = V.widx;
+    { int rc = map_send_segs(c, m, segs, (int)total, D.S); if (rc) return rc; }
+    D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n;
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) D.S.imm_frame[i] = i == V.widx ? 0 : -1;
     D.S.flags = V.flags; D.S.geo = V.geo; D.S.col0 = V.col0; D.S.col1 = V.col1; D.S.acc = V.acc; D.S.prior = V.prior; D.S.relbs = V.relbs;
     D.mode = a->display_mode; D.scaledTH = a->scaledTH; D.absTH = a->absTH; D.minRelBS = a->minRelBS; std::memcpy(D.ci, V.ci, sizeof(D.ci));
     const size_t nv = (size_t)a->n_needed;
@@ -466,6 +489,135 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
     return NALO_OK;
 }
 
+// The 3-D panel of PangolinDSOViewer (kernels_map_render.hip; the definition: include/nalo_gpu.h). Every check stands before the first enqueue; kernels on the main
+// stream; counters and images come up through one pinned block behind ONE wait (the graph's count, when a constraint flag is set, is nalo_map_graph's own) and
+// reach the caller only when the call succeeds.
+int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
+    const char* const who = "nalo_map_render: ";
+    if (!c || !a || !a->rgb) return fail(c, NALO_ERR_ARG, std::string(who) + "bad argument");
+    a->n_vertices = a->n_drawn_points = a->n_segments = a->n_line_samples = 0;
+    if (a->vw < 1 || a->vh < 1 || (long long)a->vw * a->vh > (1ll << 26)) return fail(c, NALO_ERR_ARG, std::string(who) + "vw, vh must be at least 1 and vw * vh at most 2^26");
+    for (float f : {a->fx, a->fy, a->cx, a->cy, a->znear, a->zfar}) if (!std::isfinite(f)) return fail(c, NALO_ERR_ARG, std::string(who) + "the camera values must be finite");
+    for (double d : a->viewFromWorld) if (!std::isfinite(d)) return fail(c, NALO_ERR_ARG, std::string(who) + "viewFromWorld must be finite");
+    if (a->znear <= 0 || a->zfar <= a->znear) return fail(c, NALO_ERR_ARG, std::string(who) + "0 < znear < zfar required");
+    if (a->n_frames < 0 || (a->n_frames > 0 && !a->frames)) return fail(c, NALO_ERR_ARG, std::string(who) + "n_frames is negative, or frames is NULL");
+    if (a->n_all_poses < 0 || (a->n_all_poses > 0 && !a->all_poses)) return fail(c, NALO_ERR_ARG, std::string(who) + "n_all_poses is negative, or all_poses is NULL");
+    if (a->sparsity > 1) return fail(c, NALO_ERR_ARG, std::string(who) + "sparsity > 1 is not supported (as nalo_map_frame_cloud)");
+    std::map<int, int> index_of;
+    for (int i = 0; i < a->n_frames; ++i) if (!index_of.emplace(a->frames[i].frame_id, i).second) return fail(c, NALO_ERR_ARG, std::string(who) + "a frame_id is listed twice");
+    if (c->xchg_failed) return fail(c, NALO_ERR_STATE, std::string(who) + "a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (a->with_dense && !map_dense_on(c)) return fail(c, NALO_ERR_STATE, std::string(who) + "with_dense and the dense archive is off (nalo_map_dense_enable)");
+    const bool constraints = a->show_active_constraints || a->show_all_constraints;
+    if (constraints && !c->graph_on) return fail(c, NALO_ERR_STATE, std::string(who) + "a constraint flag is set and the graph is off (nalo_map_graph_enable)");
+    MapWindowView V0;
+    { const int rc = ba_map_view(c, -1, &V0); if (rc) return rc; }
+    if (V0.sharded) return fail(c, NALO_ERR_STATE, std::string(who) + "the window is sharded (a rank holds only its own points)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    // the record list of all listed frames: per frame what nalo_map_frame_cloud lists, then its dense pieces
+    const MapArchive* const arch = c->map;
+    const DenseArchive* const dense = a->with_dense ? c->dmap : nullptr;
+    std::vector<MapSeg> segs; long long total = 0;
+    MapWindowView VW{}; bool have_window = false;
+    int imm_frame[NALO_MAX_WINDOW];
+    for (int& v : imm_frame) v = -1;
+    const bool imm = a->with_immature && c->imm_res_n > 0 && c->imm_res.p;
+    if (imm) { segs.push_back({nullptr, 0, c->imm_res_n, 0, 0}); total = c->imm_res_n; }      // the resident set once for all frames: imm_frame names a point's frame
+    for (int i = 0; i < a->n_frames; ++i) {
+        const int fid = a->frames[i].frame_id;
+        MapWindowView V;
+        { const int rc = ba_map_view(c, fid, &V); if (rc) return rc; }
+        const MapFrame* f = nullptr;
+        if (arch) { const auto it = arch->frames.find(fid); if (it != arch->frames.end()) f = &it->second; }
+        const DenseFrame* df = nullptr;
+        if (c->dmap) { const auto it = c->dmap->frames.find(fid); if (it != c->dmap->frames.end()) df = &it->second; }
+        if (V.widx < 0 && !f && !df) return fail(c, NALO_ERR_ARG, std::string(who) + "a frame_id is neither in the window nor in either archive");
+        if (V.widx >= 0 && !V.pts_ok) return fail(c, NALO_ERR_STATE, std::string(who) + "a listed frame is in the window but the window's points are unset: carry or re-issue the window first");
+        if (V.widx >= 0) { VW = V; have_window = true; if (V.widx < NALO_MAX_WINDOW) imm_frame[V.widx] = i; }
+        if (V.widx >= 0 && V.seg) { segs.push_back({V.kmap, (int)total, V.seg, 1, i}); total += V.seg; }
+        if (f) { map_push_runs(*arch, f, 2, segs, total, i); map_push_runs(*arch, f, 3, segs, total, i); }
+        if (dense && df) map_push_runs(*dense, df, 4, segs, total, i);
+        if (total > INT32_MAX) return fail(c, NALO_ERR_UNSUPPORTED, std::string(who) + "more records than a 32-bit index can hold");
+    }
+    std::vector<nalo_graph_connection> conn;
+    if (constraints) { const int rc = graph_connections(c, "nalo_map_render", conn); if (rc) return rc; }
+    HostTimer ht(c, "map_render");
+    // ---- the transforms and the segment list
+    const MrCam cam{a->vw, a->vh, a->fx, a->fy, a->cx, a->cy, a->znear, a->zfar};
+    std::vector<float> M(12 * (size_t)std::max(a->n_frames, 1), 0.f);
+    for (int i = 0; i < a->n_frames; ++i) map_render_transform(a->viewFromWorld, a->frames[i].camToWorld, &M[12 * (size_t)i]);
+    float Vf[12];
+    for (int i = 0; i < 12; ++i) Vf[i] = (float)a->viewFromWorld[i];
+    std::vector<MrLine> lines;
+    long long n_segments = 0;                                                  // reaches the caller with the other counts, behind the wait
+    auto add = [&](const float* Mx, const float p[3], const float q[3], unsigned col, int width) {
+        float pa[3], pb[3];
+        map_render_apply(Mx, p, pa); map_render_apply(Mx, q, pb);
+        MrLine L;
+        if (map_render_line(cam, pa, pb, col, width, &L)) { ++n_segments; if (L.count > 0) lines.push_back(L); }
+    };
+    auto cam_lines = [&](const float* Mx, float sz, unsigned col, int width) {       // drawCam :630-649
+        float p[5][3];
+        map_render_frustum(V0.cf, c->w, c->h, sz, p);
+        constexpr int e[8][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {4, 3}, {3, 2}, {2, 1}, {1, 4}};
+        for (const auto& s : e) add(Mx, p[s[0]], p[s[1]], col, width);
+    };
+    auto translation = [&](int i, float t[3]) { for (int k = 0; k < 3; ++k) t[k] = (float)a->frames[i].camToWorld[4 * k + 3]; };
+    constexpr unsigned kRed = 0xFF0000u, kGreen = 0x00FF00u, kBlue = 0x0000FFu;
+    if (a->show_kf_cams) for (int i = 0; i < a->n_frames; ++i) cam_lines(&M[12 * (size_t)i], 0.1f, kBlue, 1);
+    if (a->show_current_cam) {
+        float Mc[12];
+        map_render_transform(a->viewFromWorld, a->currentCamToWorld, Mc);
+        cam_lines(Mc, 0.2f, kRed, 2);
+    }
+    for (const nalo_graph_connection& g : conn) {                                  // drawConstraints :448-493; an unlisted end is the reference's `== 0`
+        const auto from = index_of.find(g.from_id), to = index_of.find(g.to_id);
+        if (from == index_of.end() || to == index_of.end()) continue;
+        const int nAct = g.bwdAct + g.fwdAct, nMarg = g.bwdMarg + g.fwdMarg;
+        float p[3], q[3];
+        translation(from->second, p); translation(to->second, q);
+        if (a->show_all_constraints && nAct == 0 && nMarg > 0) add(Vf, p, q, kGreen, 1);
+        if (a->show_active_constraints && nAct > 0) add(Vf, p, q, kBlue, 3);
+    }
+    if (a->show_trajectory) for (int i = 0; i + 1 < a->n_frames; ++i) { float p[3], q[3]; translation(i, p); translation(i + 1, q); add(Vf, p, q, kRed, 3); }
+    if (a->show_full_trajectory) for (int i = 0; i + 1 < a->n_all_poses; ++i) add(Vf, a->all_poses + 3 * (size_t)i, a->all_poses + 3 * (size_t)(i + 1), kGreen, 3);
+    // ---- the device side
+    if (!c->map) c->map = new MapArchive();                                 // the call's scratch lives there (the archive stays off)
+    MapArchive& m = *c->map;
+    MapRenderDev D{};
+    { const int rc = map_send_segs(c, m, segs, (int)total, D.S); if (rc) return rc; }
+    D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n; std::memcpy(D.S.imm_frame, imm_frame, sizeof(imm_frame));
+    if (have_window) { D.S.flags = VW.flags; D.S.geo = VW.geo; D.S.col0 = VW.col0; D.S.col1 = VW.col1; D.S.acc = VW.acc; D.S.prior = VW.prior; D.S.relbs = VW.relbs; }
+    const size_t npx = (size_t)a->vw * a->vh, padded = map_render_padded_pixels(npx), off_rgb = 64, off_depth = (off_rgb + 3 * npx + 15) / 16 * 16;
+    NALO_HIP(c, m.mr_M_h.reserve(M.size())); NALO_HIP(c, m.mr_M_d.reserve(M.size()));
+    NALO_HIP(c, m.mr_lines_h.reserve(std::max<size_t>(lines.size(), 1))); NALO_HIP(c, m.mr_lines_d.reserve(std::max<size_t>(lines.size(), 1)));
+    NALO_HIP(c, m.mr_rgb.reserve(3 * padded)); NALO_HIP(c, m.mr_depth.reserve(padded)); NALO_HIP(c, m.mr_host.reserve(off_depth + 4 * npx));
+    if (!m.mr_cnt.p) { NALO_HIP(c, m.mr_cnt.reserve(8)); NALO_HIP(c, hipMemsetAsync(m.mr_cnt.p, 0, 8 * 8, c->stream)); m.mr_cnt_buf = 0; }
+    if (padded > m.mr_key.cap) m.mr_key_clean = false;
+    NALO_HIP(c, m.mr_key.reserve(padded));
+    if (!m.mr_key_clean) NALO_HIP(c, hipMemsetAsync(m.mr_key.p, 0xFF, m.mr_key.cap * 8, c->stream));   // a new plane, or a call that failed between its passes
+    m.mr_key_clean = false;
+    std::copy(M.begin(), M.end(), m.mr_M_h.p);
+    NALO_HIP(c, hipMemcpyAsync(m.mr_M_d.p, m.mr_M_h.p, M.size() * 4, hipMemcpyHostToDevice, c->stream));
+    std::copy(lines.begin(), lines.end(), m.mr_lines_h.p);
+    if (!lines.empty()) NALO_HIP(c, hipMemcpyAsync(m.mr_lines_d.p, m.mr_lines_h.p, lines.size() * sizeof(MrLine), hipMemcpyHostToDevice, c->stream));
+    D.M = m.mr_M_d.p; D.mode = a->display_mode; D.scaledTH = a->scaledTH; D.absTH = a->absTH; D.minRelBS = a->minRelBS; std::memcpy(D.ci, V0.ci, sizeof(D.ci)); D.cam = cam;
+    D.lines = m.mr_lines_d.p; D.n_lines = (int)lines.size(); D.key = m.mr_key.p; D.padded = padded;
+    D.cnt = m.mr_cnt.p + 4 * m.mr_cnt_buf; m.mr_cnt_buf ^= 1; D.cnt_next = m.mr_cnt.p + 4 * m.mr_cnt_buf;
+    D.rgb = m.mr_rgb.p; D.depth = m.mr_depth.p; D.background = ((unsigned)a->background[0] << 16) | ((unsigned)a->background[1] << 8) | a->background[2];
+    { const int rc = map_render_launch(c, D); if (rc) return rc; }
+    m.mr_key_clean = true;
+    NALO_HIP(c, hipMemcpyAsync(m.mr_host.p, D.cnt, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_rgb, m.mr_rgb.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
+    if (a->depth) NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_depth, m.mr_depth.p, 4 * npx, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned long long cnt[4];
+    std::memcpy(cnt, m.mr_host.p, sizeof(cnt));
+    a->n_vertices = (long long)cnt[0]; a->n_drawn_points = (long long)cnt[1]; a->n_segments = n_segments; a->n_line_samples = (long long)cnt[2];
+    std::memcpy(a->rgb, m.mr_host.p + off_rgb, 3 * npx);
+    if (a->depth) std::memcpy(a->depth, m.mr_host.p + off_depth, 4 * npx);
+    return NALO_OK;
+}
+
 int nalo_map_graph_enable(nalo_ctx* c, int on) {
     if (!c) return NALO_ERR_ARG;
     if (!on) { c->graph_on = false; return NALO_OK; }
@@ -491,18 +643,8 @@ int nalo_map_graph(nalo_ctx* c, nalo_graph_edge* edges, int cap, int* n) {
 
 int nalo_map_graph_connections(nalo_ctx* c, nalo_graph_connection* conn, int cap, int* n) {
     if (!c || !n || cap < 0) return fail(c, NALO_ERR_ARG, "nalo_map_graph_connections: bad argument");
-    std::vector<nalo_graph_edge> E;
-    { const int rc = graph_entries(c, "nalo_map_graph_connections", E); if (rc) return rc; }
-    // PangolinDSOViewer::publishGraph (PangolinDSOViewer.cpp:528-571): keys with host < target in key order, the backward pair from the inverse key
-    std::map<uint64_t, const nalo_graph_edge*> by_key;
-    for (const nalo_graph_edge& e : E) by_key[graph_key(e.host_id, e.target_id)] = &e;
     std::vector<nalo_graph_connection> C;
-    for (const nalo_graph_edge& e : E) {
-        if (e.host_id >= e.target_id) continue;
-        const auto inv = by_key.find(graph_key(e.target_id, e.host_id));
-        const nalo_graph_edge* b = inv == by_key.end() ? nullptr : inv->second;      // (pairs are created in both directions: the reference's .at() never throws)
-        C.push_back({e.host_id, e.target_id, e.act, b ? b->act : 0, e.marg, b ? b->marg : 0});
-    }
+    { const int rc = graph_connections(c, "nalo_map_graph_connections", C); if (rc) return rc; }
     *n = (int)C.size();
     if (cap < *n || (*n > 0 && !conn)) return fail(c, NALO_ERR_ARG, "nalo_map_graph_connections: cap is smaller than the number of connections");
     std::copy(C.begin(), C.end(), conn);

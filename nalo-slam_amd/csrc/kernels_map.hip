@@ -13,6 +13,7 @@
 #include "ba_device.h"
 #include "map_point_math.h"
 #include "plot_device.h"
+#include "map_cloud_device.h"
 
 namespace nalo {
 
@@ -95,54 +96,6 @@ int map_append_write_launch(nalo_ctx* c, const MapAppendDev& A, bool patch) {
     return NALO_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ the records of a cloud
-struct MapRec { float u, v, idepth, H, relbs; int status; float col[8]; };
-
-// entry i of the virtual list: false when it is no record of the frame (another host's immature point, an invalid slot, an archive record of the other status)
-template <bool COLOR>
-__device__ __forceinline__ bool map_fetch(const MapSrcDev& S, int i, MapRec& R) {
-    if (i >= S.total) return false;
-    int s = 0;
-    while (s + 1 < S.nseg && i >= S.segs[s + 1].start) ++s;                      // a handful of segments, uniform loads
-    const MapSeg sg = S.segs[s];
-    const int t = i - sg.start;
-    if (t < 0 || t >= sg.n) return false;
-    if (sg.kind == 0) {                                                         // setFromKF :121-134; the set's layout: kernels_imm_carry.hip
-        const size_t N = (size_t)S.immN;
-        if (((const int*)(S.imm + 22 * N))[t] != S.widx) return false;
-        R.u = S.imm[t]; R.v = S.imm[N + t];
-        R.idepth = (S.imm[24 * N + t] + S.imm[23 * N + t]) * 0.5f;
-        R.H = 1000.f; R.relbs = 0.f; R.status = 0;
-        if (COLOR) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) R.col[q] = S.imm[2 * N + 8 * (size_t)t + q];
-        }
-        return true;
-    }
-    if (sg.kind == 1) {                                                         // :136-149
-        const int d = ((const int*)sg.p)[t];
-        if (!(S.flags[d] & PT_VALID)) return false;
-        const float4 g = S.geo[d], pa = S.acc[d];
-        float H = 0.f;
-        if (pa.z != 0.f) { H = pa.x + S.prior[d]; if (H < 1e-10f) H = 1e-10f; }   // ba_flag_points_kernel's idepth_hessian
-        R.u = g.x; R.v = g.y; R.idepth = kScaleIdepth * g.z; R.H = H; R.relbs = S.relbs[d]; R.status = 1;
-        if (COLOR) {
-            const float4 a = S.col0[d], b = S.col1[d];
-            R.col[0] = a.x; R.col[1] = a.y; R.col[2] = a.z; R.col[3] = a.w; R.col[4] = b.x; R.col[5] = b.y; R.col[6] = b.z; R.col[7] = b.w;
-        }
-        return true;
-    }
-    const float4* q = reinterpret_cast<const float4*>((const nalo_map_record*)sg.p + t);   // :151-177
-    const float4 a = q[0], b = q[1];
-    if (__float_as_int(b.y) != sg.kind) return false;
-    R.u = a.x; R.v = a.y; R.idepth = a.z; R.H = a.w; R.relbs = b.x; R.status = sg.kind;
-    if (COLOR) {
-        const float4 x = q[2], y = q[3];
-        R.col[0] = x.x; R.col[1] = x.y; R.col[2] = x.z; R.col[3] = x.w; R.col[4] = y.x; R.col[5] = y.y; R.col[6] = y.z; R.col[7] = y.w;
-    }
-    return true;
-}
-
 // ------------------------------------------------------------------------------------------------ (B) the final cloud of a frame that leaves
 __global__ __launch_bounds__(256) void map_world_count_kernel(MapWorldDev D) {
     __shared__ int wsum[4];
@@ -173,28 +126,14 @@ int map_world_launch(nalo_ctx* c, const MapWorldDev& D) {
 }
 
 // ------------------------------------------------------------------------------------------------ (C) what the viewer gets per keyframe
-// refreshPC's tests in their order and precision (:313-331); depth comes out for the vertices
-__device__ __forceinline__ bool map_cloud_keep(const MapCloudDev& C, const MapRec& R, float& depth) {
-    depth = 0.f;
-    if (C.mode == 1 && R.status != 1 && R.status != 2) return false;
-    if (C.mode == 2 && R.status != 1) return false;
-    if (C.mode > 2) return false;
-    if (R.idepth < 0) return false;
-    depth = 1.0f / R.idepth;
-    float depth4 = depth * depth; depth4 *= depth4;
-    const float var = (float)(1.0 / ((double)R.H + 0.01));                       // the literal 0.01 is a double
-    if (var * depth4 > C.scaledTH) return false;
-    if (var > C.absTH) return false;
-    if (R.relbs < C.minRelBS) return false;
-    return true;
-}
+// refreshPC's filter, the vertices and the colours: map_cloud_device.h (the 3-D panel shares them)
 __global__ __launch_bounds__(256) void map_cloud_count_kernel(MapCloudDev C) {
     __shared__ int wsum[4];
     MapRec R;
     R.status = -1;
     const bool in = map_fetch<false>(C.S, blockIdx.x * 256 + threadIdx.x, R);
     float depth;
-    const bool keep = in && map_cloud_keep(C, R, depth);
+    const bool keep = in && map_cloud_keep(C.mode, C.scaledTH, C.absTH, C.minRelBS, R, depth);
     const bool lead = (threadIdx.x & 63) == 0;
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
@@ -210,18 +149,17 @@ __global__ __launch_bounds__(256) void map_cloud_write_kernel(MapCloudDev C) {
     MapRec R;
     const bool in = map_fetch<true>(C.S, blockIdx.x * 256 + threadIdx.x, R);
     float depth;
-    const bool keep = in && map_cloud_keep(C, R, depth);
+    const bool keep = in && map_cloud_keep(C.mode, C.scaledTH, C.absTH, C.minRelBS, R, depth);
     const int r = C.S.cnt[blockIdx.x] + map_block_rank(keep, wsum);
     if (!keep || r >= C.cap) return;                                            // (survivors <= the frame's records, which the host sized the outputs by)
-    const float fxi = C.ci[0], fyi = C.ci[1], cxi = C.ci[2], cyi = C.ci[3];
+    const float fxi = C.ci[0];
     constexpr int dx[8] = NALO_PATTERN_DX, dy[8] = NALO_PATTERN_DY;
     const size_t j0 = 8 * (size_t)r;                                            // the first of the record's eight output vertices = its first draw
     float vtx[24];
     unsigned cb[8];
 #pragma unroll
     for (int pnt = 0; pnt < 8; ++pnt) {                                         // :334-387
-        vtx[3 * pnt] = ((R.u + dx[pnt]) * fxi + cxi) * depth;
-        vtx[3 * pnt + 1] = ((R.v + dy[pnt]) * fyi + cyi) * depth;
+        map_cloud_vertex_xy(C.ci, R, depth, dx[pnt], dy[pnt], vtx[3 * pnt], vtx[3 * pnt + 1]);
         // rand() / (float)RAND_MAX - 0.5f; without draws the library's no-jitter form: the bracket below is exactly 1
         const float jit = C.draws ? ((float)C.draws[j0 + pnt] / (float)2147483647 - 0.5f) : 0.f;
         vtx[3 * pnt + 2] = depth * (1 + 2 * fxi * jit);
@@ -232,8 +170,8 @@ __global__ __launch_bounds__(256) void map_cloud_write_kernel(MapCloudDev C) {
     for (int k = 0; k < 6; ++k) ov[k] = make_float4(vtx[4 * k], vtx[4 * k + 1], vtx[4 * k + 2], vtx[4 * k + 3]);
     unsigned wd[6];
     if (C.mode == 0) {                                                          // :349-372, little-endian bytes {c0 c1 c2} x 8
-        const unsigned c0 = R.status == 3 ? 255u : 0u, c1 = (R.status == 0 || R.status == 1) ? 255u : 0u, c2 = (R.status == 0 || R.status == 2) ? 255u : 0u;
-        const unsigned t[3] = {c0, c1, c2};
+        unsigned t[3];
+        map_cloud_mode0(R.status, t);
 #pragma unroll
         for (int k = 0; k < 6; ++k) wd[k] = t[(4 * k) % 3] | (t[(4 * k + 1) % 3] << 8) | (t[(4 * k + 2) % 3] << 16) | (t[(4 * k + 3) % 3] << 24);
     } else {
@@ -254,14 +192,10 @@ int map_cloud_launch(nalo_ctx* c, const MapCloudDev& C) {
 }
 
 // ------------------------------------------------------------------------------------------------ (D) the dense map's two consumers (nalo_map_dense_*)
-// point i of the frame's dense list: its archive pieces in append order (a handful of segments, uniform loads)
+// point i of the frame's dense list: its archive pieces in append order
 __device__ __forceinline__ bool map_dense_fetch(const MapDenseDev& D, int i, uint4& r) {
-    if (i >= D.total) return false;
-    int s = 0;
-    while (s + 1 < D.nseg && i >= D.segs[s + 1].start) ++s;
-    const MapSeg sg = D.segs[s];
-    const int t = i - sg.start;
-    if (t < 0 || t >= sg.n) return false;
+    MapSeg sg; int t;
+    if (!map_find_seg(D.segs, D.nseg, D.total, i, sg, t)) return false;
     r = reinterpret_cast<const uint4*>(sg.p)[t];                                 // {u | v << 16, idepth, colour, b | g << 8 | r << 16}
     return true;
 }
@@ -287,7 +221,7 @@ __global__ __launch_bounds__(256) void map_dense_cloud_count_kernel(MapDenseDev 
     __shared__ int wsum[4];
     uint4 r = make_uint4(0, 0, 0, 0);
     const bool in = map_dense_fetch(D, blockIdx.x * 256 + threadIdx.x, r);
-    const bool keep = in && !(__uint_as_float(r.y) < 0);
+    const bool keep = in && map_dense_keep(r);
     const int k = map_block_rank(keep, wsum);
     if (threadIdx.x == 255) D.cnt[blockIdx.x] = k + (keep ? 1 : 0);
 }
@@ -295,16 +229,15 @@ __global__ __launch_bounds__(256) void map_dense_cloud_write_kernel(MapDenseDev 
     __shared__ int wsum[4];
     uint4 r = make_uint4(0, 0, 0, 0);
     const bool in = map_dense_fetch(D, blockIdx.x * 256 + threadIdx.x, r);
-    const float idepth = __uint_as_float(r.y);
-    const bool keep = in && !(idepth < 0);
+    const bool keep = in && map_dense_keep(r);
     const int j = D.cnt[blockIdx.x] + map_block_rank(keep, wsum);                // the output vertex = the draw index
     if (!keep || j >= D.total) return;
-    const float fxi = D.ci[0], fyi = D.ci[1], cxi = D.ci[2], cyi = D.ci[3];
-    const float depth = 1.0f / idepth;
-    const float u = (float)(r.x & 0xFFFFu), v = (float)(r.x >> 16);
+    const float fxi = D.ci[0];
+    float x, y, depth;
+    map_dense_vertex(r, D.ci, x, y, depth);
     const float jit = D.draws ? ((float)D.draws[j] / (float)2147483647 - 0.5f) : 0.f;   // as map_cloud_write_kernel: without draws the bracket is exactly 1
     float* o = D.xyz + 3 * (size_t)j;
-    o[0] = (u * fxi + cxi) * depth; o[1] = (v * fyi + cyi) * depth; o[2] = depth * (1 + 2 * fxi * jit);
+    o[0] = x; o[1] = y; o[2] = depth * (1 + 2 * fxi * jit);
     uint8_t* q = D.rgb + 3 * (size_t)j;
     q[0] = (uint8_t)(r.w >> 16); q[1] = (uint8_t)(r.w >> 8); q[2] = (uint8_t)r.w;  // {bgr[2], bgr[1], bgr[0]}
 }

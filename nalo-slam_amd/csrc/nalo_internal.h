@@ -320,11 +320,13 @@ struct MapAppendDev {
 int map_append_rank_launch(nalo_ctx* c, const MapAppendDev& A);                 // counts + their scan
 int map_append_write_launch(nalo_ctx* c, const MapAppendDev& A, bool patch);    // the records; patch: the two words marginalizePointsF's addPoint rewrites on a marginalised point
 // a cloud's records: a virtual list of segments. kind 0: the resident immature set (every point; the frame's are picked by host_idx), 1: a segment of kmap (valid points),
-// 2 / 3: an archive run, of which the pass takes the records of that status
-struct MapSeg { const void* p; int start, n, kind, pad; };
+// 2 / 3: an archive run, of which the pass takes the records of that status, 4 (nalo_map_render only): a piece of the dense archive. frame: the listed frame the
+// segment belongs to (nalo_map_render's row of its transform table; 0 elsewhere). A kind-0 segment serves every frame at once: imm_frame[host_idx] is the
+// point's frame (-1: the host is not listed)
+struct MapSeg { const void* p; int start, n, kind, frame; };
 struct MapSrcDev {
     const MapSeg* segs; int nseg, total, nb;
-    const float* imm; int immN, widx;
+    const float* imm; int immN, imm_frame[NALO_MAX_WINDOW];
     const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs;
     int* cnt;                                                                   // [nb + 1] survivors per workgroup, scanned
 };
@@ -351,8 +353,27 @@ void graph_add_marg(nalo_ctx* c, int W, const int* id_of_row, const double* misc
 struct GraphWindowView { int W; int ids[NALO_MAX_WINDOW]; bool sharded; int act[NALO_MAX_WINDOW * NALO_MAX_WINDOW]; };
 int ba_graph_view(nalo_ctx* c, bool count, GraphWindowView* V);
 // host_ba.hip: the window as nalo_map_frame_cloud reads it. widx = -1: frame_id is not in the window; pts_ok: the point arrays stand (kmap: the frame's seg entries, n_valid of them valid). ci: {fxi, fyi, cxi, cyi} of the CalibHessian (value_scaledi)
-struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4]; bool sharded; };
+struct MapWindowView { int widx, n_valid, seg; bool pts_ok; const int* kmap; const uint8_t* flags; const float4 *geo, *col0, *col1, *acc; const float *prior, *relbs; float ci[4], cf[4]; bool sharded; };   // cf: {fx, fy, cx, cy} (value_scaledf)
 int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
+// ---- the 3-D panel (nalo_map_render; host_map.hip, kernels_map_render.hip). The host half of kernels_map_render.hip is the call's arithmetic: that file is built
+// without FMA contraction, so the products below are the ones include/nalo_gpu.h defines, operation by operation.
+struct MrLine { double ua, va, ub, vb, za, zb, n, k0; int count, width; unsigned col; int pad; };   // a clipped, projected segment: samples k0 .. k0 + count - 1 of n
+struct MrCam { int vw, vh; float fx, fy, cx, cy, znear, zfar; };
+struct MapRenderDev {
+    MapSrcDev S; const float* M;                                                // M: [n_frames][12], row MapSeg::frame
+    int mode; float scaledTH, absTH, minRelBS, ci[4]; MrCam cam;
+    const MrLine* lines; int n_lines;
+    unsigned long long* key; size_t padded;                                     // one word per pixel, rounded up to whole resolve workgroups; all-ones between calls
+    unsigned long long *cnt, *cnt_next;                                         // n_vertices, n_drawn_points, n_line_samples, 0; the idle buffer zeroed for the next call
+    uint8_t* rgb; float* depth; unsigned background;                            // rgb: 3 bytes per key word; depth: 4
+};
+size_t map_render_padded_pixels(size_t pixels);
+void map_render_transform(const double view[12], const double camToWorld[12], float M[12]);          // (float)(view . camToWorld)
+void map_render_apply(const float M[12], const float p[3], float out[3]);                              // ((M0 x + M1 y) + M2 z) + M3 per row, in float
+// one segment in view space (float endpoints) through the drop rules, the near clip, the projection and the viewport clip; false: dropped (no segment counted)
+bool map_render_line(const MrCam& cam, const float a[3], const float b[3], unsigned col, int width, MrLine* out);
+void map_render_frustum(const float cf[4], int w, int h, float sz, float pts[5][3]);                  // drawCam's apex and four corners (:630-649), camera space
+int map_render_launch(nalo_ctx* c, const MapRenderDev& D);                     // points, lines, resolve on c->stream
 // ---- the window panel (nalo_map_window_plot; host_map.hip, kernels_window_plot.hip): FullSystem::debugPlot from resident data
 // host_ba.hip: the whole window as the painter reads it. Per window frame: frame_id, slot, its seg entries of the (host, submission) map and how many are valid
 struct PlotWindowView {
