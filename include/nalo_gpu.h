@@ -945,6 +945,42 @@ int nalo_init_get_points(nalo_ctx* ctx, int lvl, int cap, int* n, float* u, floa
                          float* my_type, float* outlierTH, int* parent, float* parentDist, int* neighbours, float* neighboursDist);
 
 /* ------------------------------------------------------------------------------------------------
+ * The initialiser's depth panel: CoarseInitializer::debugPlot(lvl, wraps) (FullSystem/CoarseInitializer.cpp:287-335, called at the end of every trackFrame, :280;
+ * on by default with the Pangolin viewer and the only thing the depth panel shows until the system has initialised) on the device: the MinimalImageB3 handed to
+ * Output3DWrapper::pushDepthImage. It reads the initialiser's CURRENT state where it lies - u, v, iR, isGood of the level, after the same "upload the host
+ * mirror if it is the newer side" step nalo_init_sweep takes behind nalo_init_set_points - and the irradiance of the first frame's slot at that level, channel 0
+ * of its texels (firstFrame->dIp[lvl][i][0], what nalo_frame_download returns; the slot's planar I[] is filled at level 0 only by the one-pass pyramid); nothing
+ * of the Pnt arrays visits the host (the route it replaces, nalo_init_get_points, refreshes the host mirror of every member of every level). The call changes
+ * nothing of the initialiser, and a context that never calls it enqueues exactly what it did before. Kernels on the context's stream, ONE wait; results and image
+ * come up through a pinned block and reach the caller only on success.
+ *   Base      (:300-301) Vec3b(I, I, I) from the float, no 0.9f factor. The float -> unsigned char conversion is DEFINED as (unsigned char)__float2int_rz(I):
+ *             truncation toward zero, saturating to int, NaN -> 0, then it wraps - nalo_trk_depth_image's rules, and what x86 produces for values int holds.
+ *   Scale     (:306-316) n_good counts the points with isGood != 0 (`nid`, a float counter in the reference, exact below 2^24). sum_iR (`sid`) is the chain of
+ *             dependent float adds of iR over the good points IN INDEX ORDER, starting from 0.f: no tree, no atomic, no fp64. fac = (float)n_good / sum_iR in
+ *             float: NaN for a level without a good point, +-inf for sum_iR = 0 with good points. A NaN sum_iR or fac is a NaN; its sign and payload are not defined.
+ *   Squares   (:320-329) per point setPixel9((int)(u + 0.5f), (int)(v + 0.5f), c): the 3x3 block around the centre; c is black for a point that is not good, else
+ *             makeRainbow3B(iR * fac) with freeDebugParam3 = rainbow_scale, as nalo_map_window_plot's Rainbow (its DEFINED difference 3 included).
+ *   Overlap   points are painted in ascending index, so the LAST index wins a pixel - exactly so here, on every run: an integer maximum of index + 1 per covered
+ *             pixel, then a pass that paints the winner or the base. No float atomic.
+ * DEFINED differences from the reference: MinimalImage::at() has no bounds check, here pixels of a block outside the image are skipped; (int)(u + 0.5f) of a value
+ *   int cannot hold saturates, NaN gives 0.
+ * A level with no points (the base image) or with no good point (black squares only) is legal.
+ * Refusals, each leaving bgr, the other outputs and the context as they were. NALO_ERR_ARG: NULL ctx / args / bgr; lvl outside the initialiser's levels;
+ *   rainbow_scale not finite. NALO_ERR_STATE: no nalo_init_set_first yet; the first frame's slot has no pyramid. NALO_ERR_HIP: a cross-rank exchange of this
+ *   context failed earlier.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_init_plot_args {
+    int      lvl;             /* the reference passes 0; every level the initialiser holds is legal */
+    float    rainbow_scale;   /* freeDebugParam3 (settings.cpp:191), 1 in the reference */
+    uint8_t* bgr;             /* out: [h][w][3] of the level (at most 3 * w * h bytes of level 0), bytes of a pixel in Vec3b's order */
+    int      w, h;            /* out: the level's size */
+    int      n_points;        /* out: numPoints[lvl] */
+    int      n_good;          /* out: nid */
+    float    sum_iR, fac;     /* out: sid, fac */
+} nalo_init_plot_args;
+int nalo_init_depth_image(nalo_ctx* ctx, nalo_init_plot_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * The map side of the device chain: the points nalo_ba_marginalize_flagged removes stay resident in a device archive, and what the reference publishes
  * per keyframe is produced from resident data. In the reference the removed points ARE the map: flagPointsForRemoval pushes them onto
  * host->pointHessiansMarginalized / host->pointHessiansOut (FullSystem/FullSystem.cpp:968, 996, 1001, 1008) and publishKeyframes, SampleOutputWrapper and
@@ -1111,7 +1147,8 @@ int nalo_map_graph_connections(nalo_ctx* ctx, nalo_graph_connection* conn, int c
  *   window's point arrays are unset (between nalo_ba_marginalize_frame and the carry); a selected frame's slot without a pyramid; a sharded window (a rank holds
  *   only its own points); mode 7 with an empty allID (the reference indexes an empty vector; n_values = 0). NALO_ERR_HIP: a cross-rank exchange of this context
  *   failed earlier.
- * Out of scope: debugPlotTracking, CoarseInitializer::debugPlot, displayImageStitch's tiling, the dead `debugSaveImages && false` block.
+ * Out of scope: displayImageStitch's tiling, the dead `debugSaveImages && false` block. (debugPlotTracking: nalo_ba_residual_plot below; CoarseInitializer::debugPlot:
+ *   nalo_init_depth_image.)
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_window_plot_args {
     int      mode;            /* (int)(freeDebugParam5 + 0.5f) of the reference: 0..9 */
@@ -1127,6 +1164,68 @@ typedef struct nalo_window_plot_args {
     float    min_new, max_new, min_used, max_used;   /* out, mode 7, as in nalo_depth_image_args */
 } nalo_window_plot_args;
 int nalo_map_window_plot(nalo_ctx* ctx, nalo_window_plot_args* args);
+
+/* ------------------------------------------------------------------------------------------------
+ * The residual panel: one outer iteration of FullSystem::debugPlotTracking (FullSystem/FullSystemDebugStuff.cpp:52-107, call sites FullSystemOptimize.cpp:471,598)
+ * with PointFrameResidual::debugPlot (Residuals.cpp:278-302), for host frame `host`, on the device: every window frame brightness-transferred into the host's
+ * photometric frame, the pattern pixels of every residual of the host's points coloured by energy or by state on their TARGET's image, and a 3x3 square per point
+ * on the host's own image - the argument of IOWrap::displayImageStitch. The diagnostic that shows where residuals land and which are outliers. It has no side
+ * effect on the window, and a context that never calls it enqueues exactly what it did before. Kernels on the context's stream, ONE wait; the images come up
+ * through a pinned block of the context and reach bgr only on success.
+ *
+ * nalo_ba_get_pattern_projections(ctx, projected, state_energy): what the painter draws from, for a caller (or a test) that wants the numbers. projected is
+ *   [P*W][8][2], state_energy [P*W], slot order p*W + t as nalo_ba_get_residuals; either may be NULL. projected = PointFrameResidual::projectedTo[idx]
+ *   (Residuals.cpp:186-200): projectPoint (ResidualProjections.h:47-57) of the eight pattern pixels with the precalc record of the (host, target) pair the last
+ *   linearisation read (PRE_KRKiTll, PRE_KtTll) and the point's CURRENT inverse depth - ptp = (KRKi(i,0) x + KRKi(i,1) y + KRKi(i,2)) + Kt(i) idepth per row, in
+ *   float, without FMA contraction; Ku = ptp[0] / ptp[2], Kv = ptp[1] / ptp[2]. One device function computes it for this call and for the painter.
+ *   state_energy = PointFrameResidual::state_energy. A slot that does not exist, whose point has been removed, or whose state is OOB holds the sentinel 2.f in
+ *   all sixteen coordinates (what the linearisation initialises them with) and 0 in state_energy. Preconditions and refusals are nalo_ba_get_residuals' own.
+ *
+ * nalo_ba_residual_plot:
+ *   Frames    bit i of frame_mask selects window frame i (the order of nalo_ba_get_frames) to be RETURNED; 0 selects every frame. n_frames images of h x w x 3
+ *             bytes in window order, frame_id[j] the id of image j. The counters below cover every target, whatever the mask says.
+ *   Base      of image f2 (:72-82): aff[j] = AffLight::fromToVecExposure(f2.ab_exposure, host.ab_exposure, f2.aff_g2l(), host.aff_g2l()) in double on the host,
+ *             from the frame states the context holds (what nalo_ba_get_frames reports): a = exp(SCALE_A (host.state[6] - f2.state[6])) * host.ab_exposure /
+ *             f2.ab_exposure (both exposures 1 when either is 0), b = SCALE_B host.state[7] - a SCALE_B f2.state[7]. Per pixel colL = (float)(a * I + b) with the
+ *             product and the sum in double, clamped <0 -> 0, >255 -> 255, the byte on all three channels. NaN fails both clamps: DEFINED byte 0.
+ *   Residuals for every valid point of the host, in submission order (the active list of nalo_map_window_plot), and every residual slot of it that exists and
+ *             whose state is not OOB: colour cT, energy mode (free_debug_param5 == 0): rT = (float)(20 * sqrt((double)(state_energy / 9))) - the quotient in
+ *             float, ::sqrt and the product in double as the reference's overloads resolve -, clamped to [0, 255], Vec3b(0, 255 - rT, rT), each byte truncated;
+ *             a NaN rT gives (0, 0, 0). State mode (anything else): IN (255, 0, 0), OUTLIER (0, 0, 255), anything else white. For each of the eight pattern
+ *             pixels with Ku > 2 && Kv > 2 && Ku < w - 3 && Kv < h - 3 (float compares), pixel ((int)(Ku + 0.5f), (int)(Kv + 0.5f)) of the TARGET's image
+ *             becomes cT (setPixel1).
+ *   Square    setPixel9((int)(u + 0.5), (int)(v + 0.5), makeRainbow3B(idepth_scaled)) on the HOST's own image: the sums in double as `ph->u + 0.5` is,
+ *             idepth_scaled = SCALE_IDEPTH x the current inverse depth, freeDebugParam3 = rainbow_scale (nalo_map_window_plot's Rainbow).
+ *   Overlap   the last writer in point order wins, exactly so on every run: an integer maximum of (position in the host's list + 1) per pixel, then a pass that
+ *             paints the winner or the base. One point has at most one residual per target, so the order inside a point never matters; squares and pattern
+ *             pixels never share an image, because a residual's target is never its host (a slot in the host's own row is not drawn). No float atomic.
+ *   Counters  n_points: valid points of the host; n_residuals: residuals drawn (existing, not OOB); n_pattern_pixels: pattern pixels that passed the guard.
+ * DEFINED differences from the reference:
+ *   1. The order inside the host's list is the library's (submission order); the reference's pointHessians is permuted by swap-with-back. It shows only where
+ *      pixels of two points with different colours coincide.
+ *   2. Projections are recomputed from the current state instead of being stored by the last linearize. They are the same values right after nalo_ba_optimize /
+ *      nalo_ba_linearize, which is where the reference calls the function (up to FMA contraction inside the linearisation: an ulp, far below the half pixel
+ *      that moves a painted pixel, except for a coordinate that lies on a rounding boundary).
+ *   3. Pixels of a square outside the image are skipped; (int)(u + 0.5) of a value int cannot hold saturates, NaN gives 0; makeRainbow3B as in
+ *      nalo_map_window_plot's difference 3.
+ *   4. displayImageStitch's tiling and waitKey stay with the caller.
+ * Refusals, each leaving the outputs and the context as they were. NALO_ERR_ARG: NULL ctx / args / bgr; host or a frame_mask bit at or above the window size;
+ *   rainbow_scale or free_debug_param5 not finite. NALO_ERR_STATE: no window; the window's point arrays are unset (between nalo_ba_marginalize_frame and the
+ *   carry); a selected frame's slot without a pyramid; a sharded window. NALO_ERR_HIP: a cross-rank exchange of this context failed earlier.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_residual_plot_args {
+    int      host;                /* window index of the host frame */
+    float    free_debug_param5;   /* == 0: energy colours, anything else: state colours (Residuals.cpp:283) */
+    float    rainbow_scale;       /* freeDebugParam3, 1 in the reference */
+    unsigned frame_mask;          /* bit i = the image of window frame i is returned; 0 = every frame */
+    uint8_t* bgr;                 /* out: [n_frames][h][w][3], selected frames in window order, bytes of a pixel in Vec3b's order */
+    int      n_frames;            /* out */
+    int      frame_id[NALO_MAX_WINDOW];      /* out: of the painted frames */
+    double   aff[NALO_MAX_WINDOW][2];        /* out: the affL each painted image was transferred with */
+    int      n_points, n_residuals, n_pattern_pixels;   /* out */
+} nalo_residual_plot_args;
+int nalo_ba_get_pattern_projections(nalo_ctx* ctx, float* projected, float* state_energy);
+int nalo_ba_residual_plot(nalo_ctx* ctx, nalo_residual_plot_args* args);
 
 /* ------------------------------------------------------------------------------------------------
  * The 3-D panel of PangolinDSOViewer (IOWrapper/Pangolin/PangolinDSOViewer.cpp:186-236: per keyframe drawCam, refreshPC, drawPC(1); the dense clouds; the current

@@ -33,7 +33,7 @@ EXPORTS = [
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
-    "nalo_ba_get_residuals", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
+    "nalo_ba_get_residuals", "nalo_ba_get_pattern_projections", "nalo_ba_residual_plot", "nalo_ba_get_idepth_zero", "nalo_ba_get_acc13", "nalo_ba_counts", "nalo_ba_get_launch_config", "nalo_ba_set_allreduce", "nalo_ba_set_allreduce_mode", "nalo_ba_set_allreduce_side", "nalo_ba_exchange_failed", "nalo_side_stream", "nalo_rccl_unique_id", "nalo_ba_rccl_init", "nalo_ba_set_rccl_comm", "nalo_ba_rccl_ranks", "nalo_shard_points", "nalo_ba_snapshot", "nalo_ba_restore",
     "nalo_ba_set_point_history", "nalo_ba_get_point_history", "nalo_ba_flag_points", "nalo_ba_marginalize_flagged",
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
@@ -41,7 +41,7 @@ EXPORTS = [
     "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
-    "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_dist_make_map", "nalo_pixsel_make_hists",
+    "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
     "nalo_dense_make_map", "nalo_trk_fit_planes", "nalo_trk_fit_ground", "nalo_ground_tracker_init", "nalo_ground_globals_init", "nalo_ground_frame_init", "nalo_ground_update",
     "nalo_ground_set_global_plane", "nalo_ground_local_scale", "nalo_ground_reset_global_plane", "nalo_dense_fit_planes", "nalo_plane_fit_members", "nalo_profile_enable", "nalo_profile_select", "nalo_profile_reset", "nalo_profile_get", "nalo_profile_samples", "nalo_profile_sample", "nalo_hbm_calibrate",
@@ -159,6 +159,18 @@ class WindowPlotArgs(C.Structure):
     _fields_ = [("mode", C.c_int), ("rainbow_scale", C.c_float), ("quality_scale", C.c_float), ("frame_mask", C.c_uint), ("minmax_io", c_fp), ("bgr", c_u8p),
                 ("n_frames", C.c_int), ("frame_id", C.c_int * 16), ("sources", (C.c_int * 4) * 16), ("n_values", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
                 ("min_used", C.c_float), ("max_used", C.c_float)]
+
+
+class ResidualPlotArgs(C.Structure):
+    """nalo_residual_plot_args (include/nalo_gpu.h)"""
+    _fields_ = [("host", C.c_int), ("free_debug_param5", C.c_float), ("rainbow_scale", C.c_float), ("frame_mask", C.c_uint), ("bgr", c_u8p), ("n_frames", C.c_int),
+                ("frame_id", C.c_int * 16), ("aff", (C.c_double * 2) * 16), ("n_points", C.c_int), ("n_residuals", C.c_int), ("n_pattern_pixels", C.c_int)]
+
+
+class InitPlotArgs(C.Structure):
+    """nalo_init_plot_args (include/nalo_gpu.h)"""
+    _fields_ = [("lvl", C.c_int), ("rainbow_scale", C.c_float), ("bgr", c_u8p), ("w", C.c_int), ("h", C.c_int), ("n_points", C.c_int), ("n_good", C.c_int),
+                ("sum_iR", C.c_float), ("fac", C.c_float)]
 
 
 class ViewFrame(C.Structure):
@@ -421,6 +433,9 @@ def load():
     L.nalo_init_set_points.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_u8p, c_fp, c_fp, c_fp, c_fp, c_fp, c_u8p, c_fp]
     L.nalo_init_get_carried.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_u8p]
     L.nalo_init_sweep.argtypes = [vp, C.c_int, C.c_int]
+    L.nalo_init_depth_image.argtypes = [vp, C.POINTER(InitPlotArgs)]
+    L.nalo_ba_get_pattern_projections.argtypes = [vp, c_fp, c_fp]
+    L.nalo_ba_residual_plot.argtypes = [vp, C.POINTER(ResidualPlotArgs)]
     L.nalo_pixsel_make_hists.argtypes = [vp, C.c_int, c_fp, c_fp]
     L.nalo_pixsel_set_random.argtypes = [vp, c_u8p, c_ip]
     L.nalo_pixsel_select.argtypes = [vp, C.c_int, C.c_int, C.c_float, c_fp, c_ip]
@@ -1209,6 +1224,26 @@ class Context:
         s = (self.P, self.W)
         return st.reshape(s), ac.reshape(s), jp.reshape(s + (8,)), en.reshape(s), cp.reshape(s + (3,))
 
+    def ba_pattern_projections(self):
+        """PointFrameResidual::projectedTo and state_energy of every slot (nalo_ba_get_pattern_projections) -> (projected [P, W, 8, 2], state_energy [P, W]);
+        a slot that does not exist or is OOB holds 2.0 / 0"""
+        n = self.P * self.W
+        pr, en = np.zeros((max(n, 1), 8, 2), np.float32), np.zeros(max(n, 1), np.float32)
+        self._ck(self.L.nalo_ba_get_pattern_projections(self.h_, _f(pr), _f(en)))
+        return pr[:n].reshape(self.P, self.W, 8, 2), en[:n].reshape(self.P, self.W)
+
+    def ba_residual_plot(self, host, free_debug_param5=0.0, frame_mask=0, rainbow_scale=1.0):
+        """one outer iteration of FullSystem::debugPlotTracking on the device (nalo_ba_residual_plot). Returns a dict: bgr (n_frames, h, w, 3) uint8, frame_id
+        [n_frames], aff [n_frames, 2] float64, n_points, n_residuals, n_pattern_pixels"""
+        a = ResidualPlotArgs()
+        nf = bin(frame_mask).count("1") if frame_mask else max(self.W, 1)
+        bgr = np.zeros((max(nf, 1), self.h, self.w, 3), np.uint8)
+        a.host, a.free_debug_param5, a.rainbow_scale, a.frame_mask, a.bgr = int(host), float(free_debug_param5), float(rainbow_scale), int(frame_mask), _u8(bgr)
+        self._ck(self.L.nalo_ba_residual_plot(self.h_, C.byref(a)))
+        n = a.n_frames
+        return {"bgr": bgr[:n], "frame_id": [a.frame_id[j] for j in range(n)], "aff": np.array([[a.aff[j][0], a.aff[j][1]] for j in range(n)], np.float64).reshape(n, 2),
+                "n_points": a.n_points, "n_residuals": a.n_residuals, "n_pattern_pixels": a.n_pattern_pixels}
+
     def ba_get_acc13(self):
         a = np.zeros(self.W * self.W * 169)
         self._ck(self.L.nalo_ba_get_acc13(self.h_, _d(a)))
@@ -1422,6 +1457,15 @@ class Context:
         self._ck(self.L.nalo_init_get_points(self.h_, lvl, n, _i(nn), _f(o["u"]), _f(o["v"]), _f(o["idepth"]), _f(o["iR"]), _u8(o["isGood"]), _f(o["lastHessian"]), _f(o["energy"]),
                                              _f(o["my_type"]), _f(o["outlierTH"]), _i(o["parent"]), _f(o["parentDist"]), _i(o["neighbours"]), _f(o["neighboursDist"])))
         return {k: a[:n] for k, a in o.items()}
+
+    def init_depth_image(self, lvl=0, rainbow_scale=1.0):
+        """CoarseInitializer::debugPlot on the device (nalo_init_depth_image). Returns a dict: bgr (h, w, 3) uint8 of the level, n_points, n_good, sum_iR and fac
+        (float32)"""
+        a = InitPlotArgs()
+        bgr = np.zeros(3 * self.w * self.h, np.uint8)
+        a.lvl, a.rainbow_scale, a.bgr = int(lvl), float(rainbow_scale), _u8(bgr)
+        self._ck(self.L.nalo_init_depth_image(self.h_, C.byref(a)))
+        return {"bgr": bgr[:3 * a.w * a.h].reshape(a.h, a.w, 3), "n_points": a.n_points, "n_good": a.n_good, "sum_iR": np.float32(a.sum_iR), "fac": np.float32(a.fac)}
 
     def pixsel_make_hists(self, slot):
         nb = (self.w // 32) * (self.h // 32)

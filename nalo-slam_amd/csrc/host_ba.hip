@@ -110,6 +110,9 @@ struct BAWindow {
     // nalo_ba_window_from_initializer: [the constructor's verdict per level-0 point | sumID] on the device and in pinned memory, and what the last call reports
     DevBuf<uint8_t> iw_scr; HostBuf<uint8_t> iw_host;
     std::vector<int> iw_map_h; float iw_scale[3] = {}; int iw_stats[4] = {}; bool iw_have = false;   // nalo_ba_init_window_map / nalo_ba_init_window_last
+    // nalo_ba_residual_plot (kernels_residual_plot.hip), sized on first use: the key plane (zero between calls: the resolve pass leaves it so), the colours, the
+    // painted images, the counters and the pinned block counters and images come up through
+    DevBuf<unsigned> rp_key, rp_col; DevBuf<uint8_t> rp_bgr; DevBuf<int> rp_cnt; HostBuf<uint8_t> rp_host; bool rp_key_clean = false;
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -1873,6 +1876,95 @@ int nalo_ba_get_residuals(nalo_ctx* c, int8_t* state, uint8_t* active, float* Jp
         if (energy_new) energy_new[o] = (t == W - 1) ? en[w.p2d[p]] : -1.f;
         if (center) { center[o * 3] = cp[si].x; center[o * 3 + 1] = cp[si].y; center[o * 3 + 2] = cp[si].z; }
     }
+    return NALO_OK;
+}
+
+static void residual_plot_bind(const BAWindow& w, const nalo_ctx* c, ResidualPlotDev& D) {
+    D.W = w.W; D.Ppad = w.Ppad; D.w = c->w; D.h = c->h;
+    D.pre = w.dev.pre; D.blk_host = w.blk_host.p;
+    D.flags = w.pt_flags.p; D.state = w.rs_state.p; D.geo = w.pt_geo.p; D.energy = w.rs_energy.p;
+}
+
+// PointFrameResidual::projectedTo and state_energy of every slot (kernels_residual_plot.hip: rp_get_kernel), in nalo_ba_get_residuals' order
+int nalo_ba_get_pattern_projections(nalo_ctx* c, float* projected, float* state_energy) {
+    if (!c || !c->ba || !c->ba->points_set) return fail(c, NALO_ERR_STATE, "nalo_ba_get_pattern_projections: no points");
+    BAWindow& w = *c->ba;
+    const int W = w.W; const size_t NS = (size_t)W * w.Ppad;
+    if (!projected && !state_energy) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    DevBuf<float> pr_d, en_d;
+    if (projected) NALO_HIP(c, pr_d.reserve(NS * 16));
+    if (state_energy) NALO_HIP(c, en_d.reserve(NS));
+    ResidualPlotDev D{};
+    residual_plot_bind(w, c, D);
+    D.proj = pr_d.p; D.en_out = en_d.p;
+    if (NS) { const int rc = residual_projections_launch(c, D); if (rc) return rc; }
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    std::vector<float> pr(projected ? NS * 16 : 0), en(state_energy ? NS : 0);
+    if (projected && NS) NALO_HIP(c, hipMemcpy(pr.data(), pr_d.p, NS * 64, hipMemcpyDeviceToHost));
+    if (state_energy && NS) NALO_HIP(c, hipMemcpy(en.data(), en_d.p, NS * 4, hipMemcpyDeviceToHost));
+    for (int p = 0; p < w.P; ++p) for (int t = 0; t < W; ++t) {
+        const size_t si = (size_t)t * w.Ppad + w.p2d[p], o = (size_t)p * W + t;
+        if (projected) std::memcpy(projected + o * 16, pr.data() + si * 16, 64);
+        if (state_energy) state_energy[o] = en[si];
+    }
+    return NALO_OK;
+}
+
+// One outer iteration of FullSystem::debugPlotTracking for host frame a->host (kernels_residual_plot.hip). Every check stands before the first enqueue; kernels on
+// the main stream; counters and images come up through one pinned block behind ONE wait and reach the caller only when the call succeeds.
+int nalo_ba_residual_plot(nalo_ctx* c, nalo_residual_plot_args* a) {
+    if (!c || !a || !a->bgr) return fail(c, NALO_ERR_ARG, "nalo_ba_residual_plot: bad argument");
+    if (!std::isfinite(a->rainbow_scale) || !std::isfinite(a->free_debug_param5)) return fail(c, NALO_ERR_ARG, "nalo_ba_residual_plot: rainbow_scale / free_debug_param5 must be finite");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_ba_residual_plot: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (!c->ba || c->ba->W < 1) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: no window");
+    BAWindow& w = *c->ba;
+    NALO_HIP(c, hipSetDevice(c->device));
+    PlotWindowView V;
+    { const int rc = ba_plot_view(c, &V); if (rc) return rc; }
+    if (a->host < 0 || a->host >= V.W) return fail(c, NALO_ERR_ARG, "nalo_ba_residual_plot: host outside the window");
+    if (a->frame_mask >> V.W) return fail(c, NALO_ERR_ARG, "nalo_ba_residual_plot: frame_mask names a frame outside the window");
+    if (V.sharded) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: the window is sharded (a rank holds only its own points)");
+    if (!V.pts_ok || !w.dev.pre) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: the window's points are unset: carry or re-issue the window first");
+    const unsigned mask = a->frame_mask ? a->frame_mask : (1u << V.W) - 1u;
+    ResidualPlotDev D{};
+    residual_plot_bind(w, c, D);
+    const HostFrame& fh = w.frames[a->host];
+    int frame_of[NALO_MAX_WINDOW];
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) D.out_of[i] = -1;
+    for (int i = 0; i < V.W; ++i) {                                         // while the point arrays stand, frame i is residual row i (bind_points)
+        if (!(mask >> i & 1u)) continue;
+        const int s = V.slot[i];
+        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].I[0].p) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: a window frame's slot has no pyramid");
+        const HostFrame& f2 = w.frames[i];
+        // Vec2 affL = AffLight::fromToVecExposure(f2->ab_exposure, f->ab_exposure, f2->aff_g2l(), f->aff_g2l());
+        aff_from_to(f2.ab_exposure, fh.ab_exposure, f2.state_scaled[6], f2.state_scaled[7], fh.state_scaled[6], fh.state_scaled[7], D.aff[D.n_frames]);
+        D.I[D.n_frames] = c->slots[s].I[0].p; frame_of[D.n_frames] = i; D.out_of[i] = D.n_frames++;
+    }
+    HostTimer ht(c, "ba_residual_plot");
+    D.kmap = V.kmap[a->host]; D.seg = V.seg[a->host]; D.host_row = a->host; D.energy_mode = a->free_debug_param5 == 0.f ? 1 : 0; D.rainbow_scale = a->rainbow_scale;
+    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = residual_plot_padded_pixels(px), off_bgr = 64;
+    NALO_HIP(c, w.rp_col.reserve(std::max<size_t>((size_t)D.seg * D.n_frames, 1))); NALO_HIP(c, w.rp_bgr.reserve(3 * padded)); NALO_HIP(c, w.rp_cnt.reserve(4));
+    NALO_HIP(c, w.rp_host.reserve(off_bgr + 3 * px));
+    if (padded > w.rp_key.cap) w.rp_key_clean = false;
+    NALO_HIP(c, w.rp_key.reserve(padded));
+    if (!w.rp_key_clean) NALO_HIP(c, hipMemsetAsync(w.rp_key.p, 0, w.rp_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
+    w.rp_key_clean = false;
+    NALO_HIP(c, hipMemsetAsync(w.rp_cnt.p, 0, 16, c->stream));
+    D.key = w.rp_key.p; D.col = w.rp_col.p; D.bgr = w.rp_bgr.p; D.cnt = w.rp_cnt.p;
+    { const int rc = residual_plot_launch(c, D); if (rc) return rc; }
+    w.rp_key_clean = true;
+    NALO_HIP(c, hipMemcpyAsync(w.rp_host.p, w.rp_cnt.p, 16, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(w.rp_host.p + off_bgr, w.rp_bgr.p, 3 * px, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    int cnt[4];
+    std::memcpy(cnt, w.rp_host.p, sizeof(cnt));
+    a->n_frames = D.n_frames; a->n_points = cnt[0]; a->n_residuals = cnt[1]; a->n_pattern_pixels = cnt[2];
+    for (int j = 0; j < NALO_MAX_WINDOW; ++j) {
+        a->frame_id[j] = j < D.n_frames ? V.frame_id[frame_of[j]] : 0;
+        a->aff[j][0] = j < D.n_frames ? D.aff[j][0] : 0.0; a->aff[j][1] = j < D.n_frames ? D.aff[j][1] : 0.0;
+    }
+    std::memcpy(a->bgr, w.rp_host.p + off_bgr, 3 * px);
     return NALO_OK;
 }
 

@@ -231,6 +231,9 @@ struct Initializer {
     int jb_cur = 0;
     HostBuf<float> pin;                                  // pinned staging: the first half (pin.cap / 2 floats) host -> device, the second half device -> host
     HostBuf<double> sums_host; double sums_seq = 0;      // an evaluation's 94 sums land in mapped host memory, sequence number last: polled, no copy, no sync
+    // nalo_init_depth_image (kernels_init_plot.hip), sized on first use: the key plane (zero between calls: the resolve pass leaves it so), the points' colours, the
+    // results, the painted image and the pinned block results and image come up through
+    DevBuf<unsigned> ip_key, ip_col, ip_res; DevBuf<uint8_t> ip_bgr; HostBuf<uint8_t> ip_host; bool ip_key_clean = false;
 };
 
 // word offsets inside a level's device block: the static members, then the members a level's LM loop changes ("dyn": one packed upload / download per level), the last
@@ -789,6 +792,49 @@ int nalo_init_sweep(nalo_ctx* c, int which, int lvl) {
     }
     if (rc) return rc;
     NALO_HIP(c, hipStreamSynchronize(c->stream));
+    return NALO_OK;
+}
+
+// CoarseInitializer::debugPlot(lvl, wraps) from the resident arrays (kernels_init_plot.hip). Every check stands before the first enqueue; kernels on the main stream;
+// results and image come up through one pinned block behind ONE wait and reach the caller only when the call succeeds.
+int nalo_init_depth_image(nalo_ctx* c, nalo_init_plot_args* a) {
+    if (!c || !a || !a->bgr) return fail(c, NALO_ERR_ARG, "nalo_init_depth_image: bad argument");
+    if (!std::isfinite(a->rainbow_scale)) return fail(c, NALO_ERR_ARG, "nalo_init_depth_image: rainbow_scale must be finite");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_init_depth_image: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (!c->init || c->init->slot_first < 0) return fail(c, NALO_ERR_STATE, "nalo_init_depth_image: nalo_init_set_first has not run");
+    Initializer& I = *c->init;
+    const int lvl = a->lvl;
+    if (lvl < 0 || lvl >= I.levels) return fail(c, NALO_ERR_ARG, "nalo_init_depth_image: level outside the initialiser's");
+    const int s = I.slot_first;
+    if (s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].dI[lvl].p) return fail(c, NALO_ERR_STATE, "nalo_init_depth_image: the first frame's slot has no pyramid");
+    HostTimer ht(c, "init_depth_image");
+    NALO_HIP(c, hipSetDevice(c->device));
+    { const int rc = dev_sync(c, I); if (rc) return rc; }
+    const InitLevel& P = I.L[lvl];
+    const LvlOff o = lvl_off((size_t)P.n);
+    const float* d = I.lvl_dev[lvl].p;
+    const size_t npx = (size_t)c->wl[lvl] * c->hl[lvl], padded = init_plot_padded_pixels(npx), off_bgr = 64;
+    NALO_HIP(c, I.ip_col.reserve(std::max<size_t>((size_t)P.n, 1))); NALO_HIP(c, I.ip_res.reserve(4)); NALO_HIP(c, I.ip_bgr.reserve(3 * padded));
+    NALO_HIP(c, I.ip_host.reserve(off_bgr + 3 * npx));
+    if (padded > I.ip_key.cap) I.ip_key_clean = false;
+    NALO_HIP(c, I.ip_key.reserve(padded));
+    if (!I.ip_key_clean) NALO_HIP(c, hipMemsetAsync(I.ip_key.p, 0, I.ip_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
+    I.ip_key_clean = false;
+    InitPlotDev D{};
+    D.n = P.n; D.w = c->wl[lvl]; D.h = c->hl[lvl]; D.rainbow_scale = a->rainbow_scale;
+    D.u = d + o.u; D.v = d + o.v; D.iR = d + o.iR; D.good = (const uint8_t*)(d + o.isGood);
+    D.dI = c->slots[s].dI[lvl].p;                                              // dIp[lvl][i][0]: the one-pass pyramid does not fill the planar I[] of the upper levels
+    D.key = I.ip_key.p; D.col = I.ip_col.p; D.res = I.ip_res.p; D.bgr = I.ip_bgr.p;
+    { const int rc = init_plot_launch(c, D); if (rc) return rc; }
+    I.ip_key_clean = true;
+    NALO_HIP(c, hipMemcpyAsync(I.ip_host.p, I.ip_res.p, 16, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(I.ip_host.p + off_bgr, I.ip_bgr.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    unsigned res[4];
+    std::memcpy(res, I.ip_host.p, sizeof(res));
+    a->w = D.w; a->h = D.h; a->n_points = P.n; a->n_good = (int)res[0];
+    std::memcpy(&a->sum_iR, &res[1], 4); std::memcpy(&a->fac, &res[2], 4);
+    std::memcpy(a->bgr, I.ip_host.p + off_bgr, 3 * npx);
     return NALO_OK;
 }
 

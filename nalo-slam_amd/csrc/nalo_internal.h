@@ -400,6 +400,30 @@ struct WindowPlotDev {
 };
 size_t window_plot_padded_pixels(size_t pixels);                                // what key (words) and bgr (3 bytes each) are sized by: whole workgroups of the resolve pass
 int window_plot_launch(nalo_ctx* c, const WindowPlotDev& D);                   // [select, mode 7] scatter, resolve on c->stream
+// ---- the initialiser's depth panel (nalo_init_depth_image; host_init.hip, kernels_init_plot.hip): CoarseInitializer::debugPlot from the resident Pnt arrays
+struct InitPlotDev {
+    int n, w, h; float rainbow_scale;
+    const float *u, *v, *iR; const uint8_t* good; const float4* dI;             // the level's points and the first frame's texels of that level (x: the irradiance)
+    unsigned *key, *col, *res; uint8_t* bgr;                                    // key: w h words rounded up (init_plot_padded_pixels), zero between calls; col: n words;
+};                                                                              // res: {n_good, sid, fac, 0}; bgr: 3 bytes per key word
+size_t init_plot_padded_pixels(size_t pixels);
+int init_plot_launch(nalo_ctx* c, const InitPlotDev& D);                       // sum, scatter, resolve on c->stream
+// ---- the residual panel (nalo_ba_residual_plot) and the read-back of projectedTo / state_energy (nalo_ba_get_pattern_projections); host_ba.hip,
+// kernels_residual_plot.hip. Rows are the window's residual rows = its frames while the point arrays stand.
+struct ResidualPlotDev {
+    int W, Ppad, w, h;                                                          // residual rows, slots per row, image size
+    const float* pre; const int* blk_host;                                      // the precalc records the last linearisation read ([W * W][kPreStride], host * W + target)
+    const uint8_t *flags, *state; const float4* geo; const float2* energy;
+    float *proj, *en_out;                                                       // the read-back: [W][Ppad][8][2] and [W][Ppad], either may be NULL
+    // the painter: the host's points in painting order (entry k of kmap -> device slot), seg of them
+    const int* kmap; int seg, host_row, energy_mode, n_frames; float rainbow_scale;
+    int out_of[NALO_MAX_WINDOW];                                                // residual row -> painted image, -1: masked out
+    const float* I[NALO_MAX_WINDOW]; double aff[NALO_MAX_WINDOW][2];            // per PAINTED image: its level-0 irradiance and the affL it is transferred with
+    unsigned *key, *col; uint8_t* bgr; int* cnt;                                // key: n_frames w h words rounded up, zero between calls; col: n_frames x seg words; bgr: 3 bytes
+};                                                                              // per key word; cnt: {points, residuals, pattern pixels}, zero before
+size_t residual_plot_padded_pixels(size_t pixels);
+int residual_projections_launch(nalo_ctx* c, const ResidualPlotDev& D);        // rp_get_kernel on c->stream
+int residual_plot_launch(nalo_ctx* c, const ResidualPlotDev& D);               // scatter, resolve on c->stream
 // ---- the dense map (nalo_dense_update_map, nalo_map_dense_*)
 constexpr int kDenseMaxClusters = 2048;      // = the most clusters a fit returns (kernels_plane.hip)
 // host_map.hip: the dense archive as the copy pass writes it (the point at position q lives at chunks[q / chunk][q % chunk]; cap: positions that exist)

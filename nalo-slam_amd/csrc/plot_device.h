@@ -1,5 +1,6 @@
-// Device functions the two painters share (kernels_depth_image.hip: debugPlotIDepthMap, kernels_window_plot.hip: FullSystem::debugPlot): the grey base value, the
-// colour maps of util/globalFuncs.h, the float -> byte conversion of a colour (kernels_map.hip's clouds too), and the search step of the radix select. Every file that
+// Device functions the painters share (kernels_depth_image.hip: debugPlotIDepthMap, kernels_window_plot.hip: FullSystem::debugPlot, kernels_init_plot.hip:
+// CoarseInitializer::debugPlot, kernels_residual_plot.hip: debugPlotTracking): the grey base value, the colour maps of util/globalFuncs.h, the float -> byte conversion
+// of a colour (kernels_map.hip's clouds too), the packed store of a resolve pass, and the search step of the radix select. Every file that
 // includes it is built without FMA contraction (build.py: NO_CONTRACT). Conversions the reference leaves undefined are DEFINED as include/nalo_gpu.h states them.
 #pragma once
 #include "nalo_internal.h"
@@ -51,6 +52,17 @@ __device__ __forceinline__ unsigned plot_rainbow(float id, float scale) {
     if (icP == 0) return a | (b << 8);
     if (icP == 1) return (a << 8) | (b << 16);
     return b | (a << 16);
+}
+
+// The four pixels of a lane of a resolve pass (256 lanes x 4 pixels, byte k of a Vec3b in bits 8k..8k+7 of col[]) as 12 bytes {b g r b | g r b g | r b g r}: through
+// LDS (stage: 3 x 256 words) they leave the workgroup as 16-byte stores. block: the workgroup's 3 x 1024 bytes of the image. All 256 lanes call.
+__device__ __forceinline__ void plot_store4(unsigned* stage, const unsigned col[4], uint8_t* block) {
+    const int tid = threadIdx.x;
+    stage[3 * tid] = (col[0] & 0xFFFFFFu) | (col[1] << 24);
+    stage[3 * tid + 1] = ((col[1] >> 8) & 0xFFFFu) | (col[2] << 16);
+    stage[3 * tid + 2] = ((col[2] >> 16) & 0xFFu) | (col[3] << 8);
+    __syncthreads();
+    if (tid < 192) reinterpret_cast<uint4*>(block)[tid] = reinterpret_cast<const uint4*>(stage)[tid];
 }
 
 // allID[(int)(n*0.05)] / allID[(int)(n*0.95)] with n = size - 1: the product in double, truncated. An empty list gives rank 0 (nothing is selected from it).

@@ -1,0 +1,289 @@
+"""nalo_ba_get_pattern_projections and nalo_ba_residual_plot - FullSystem::debugPlotTracking on the device.
+
+  1  the read-back against the oracle: the sixteen projections and state_energy of every existing, non-OOB slot pass helpers.assert_fp32_faithful against the
+     strict fp32 and the all-fp64 oracle, after nalo_ba_linearize(fix = 0), on synth.make_window(640, 480, W = 8, P = 2000) and on a planted W = 3 window. The
+     fp64 oracle returns its projections already rounded to float (orc_ba.c), so its own rounding costs half an ulp: the floor passed is one float ulp relative,
+     2^-23, and nothing else is loosened. How many values differ from the fp32 oracle in any bit is printed, not asserted.
+  2  the painting equals, byte for byte, the model of tests/residual_plot_model.py fed with what nalo_ba_get_pattern_projections, nalo_ba_get_residuals,
+     nalo_ba_get_points and args.aff returned; args.aff is within 1e-14 relative of the numpy formula. Planted windows (tests/residual_plot_scenes.py) at 64x32
+     (W = 2) and 80x48 (W = 3) with hosts of 1, 63, 64, 65 and 257 points: two points on the same pixels with different energies, OOB residuals, a frame with a
+     brightness step (IN and OUTLIER both occur), coordinates in (1.1, 2], exposures and affine parameters that make both clamps of the base fire; both colour
+     modes, every host, two frame_mask subsets; two calls give the same bytes
+  3  three keyframes of the device chain at 1224x368, W = 8: after each nalo_ba_optimize the images equal the model fed from a TWIN context that never plots,
+     and the twin's next nalo_ba_optimize and nalo_ba_flag_points give bit-equal results; between nalo_ba_marginalize_frame and the carry the call is refused
+  4  every other refusal, with sentinel outputs
+
+A window frame's slot without a pyramid cannot be reached through the public calls (nalo_ba_set_window refuses such a window), so that refusal is not provoked."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import lifecycle_model as lm
+import lifecycle_scenes as sc
+import orc
+import residual_plot_model as rp
+import residual_plot_scenes as scenes
+from helpers import assert_fp32_faithful
+from nalo_slam_amd import binding, synth
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+ERR_ARG, ERR_HIP, ERR_STATE = -1, -3, -4
+KC = binding.constants()
+
+
+def make_ctx(win, aff=None, exposure=None, state6=None, frame_ids=None, n_slots=None):
+    c = binding.Context(win.w, win.h, win.K, n_slots=n_slots or win.W + 1)
+    for i in range(win.W):
+        c.frame_upload(i, win.images[i])
+    c.ba_set_window(list(range(win.W)), win.world_to_cam[:win.W], aff=aff, exposure=exposure, state6=state6, frame_ids=frame_ids)
+    c.ba_set_points(win.host, win.u, win.v, win.idepth, win.color, win.weights)
+    c.ba_set_residuals(win.exists)
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ 1: the read-back against the oracle
+def oracle_slots(win, kind, **kw):
+    orc.lib(kind).orc_set_sum_mode(0)
+    ba = orc.ba_from_window(win, kind, **kw)
+    ba.linearize_all(False)
+    ba.apply_res()
+    P, W = len(win.host), win.W
+    st, pr, en = np.zeros((P, W), np.int8), np.zeros((P, W, 16), F), np.zeros((P, W))
+    for p in range(P):
+        for t in range(W):
+            r = ba.residual(p, t)
+            st[p, t], pr[p, t], en[p, t] = r["state"][0], r["proj"][3:], r["energy"][0]
+    return st, pr, en
+
+
+def check_against_oracle(win, what, **kw):
+    c = make_ctx(win, **kw)
+    c.ba_linearize(False)
+    st = c.ba_get_residuals()[0]
+    pr, en = c.ba_pattern_projections()
+    c.close()
+    st32, pr32, en32 = oracle_slots(win, "f32", **kw)
+    st64, pr64, en64 = oracle_slots(win, "f64", **kw)
+    assert np.array_equal(st, st32), "%s: residual states differ from the oracle's" % what
+    live = (st >= 0) & (st != rp.OOB)
+    both = live & (st64 == st32)                                               # the fp64 evaluation may decide a borderline slot the other way
+    assert live.sum() > 100 and both.sum() > 0.98 * live.sum(), what
+    dead = ~live
+    assert np.all(pr[dead] == 2.0) and np.all(en[dead] == 0.0), "%s: the sentinels" % what
+    g = pr.reshape(pr.shape[:2] + (16,))
+    assert_fp32_faithful(g[both], pr32[both], pr64[both], floor=2.0 ** -23)
+    assert_fp32_faithful(en[both].reshape(-1, 1), en32[both].reshape(-1, 1), en64[both].reshape(-1, 1), floor=2.0 ** -23)
+    nbits = int((g[live].view(np.uint32) != pr32[live].view(np.uint32)).sum())
+    ebits = int((en[live].astype(F).view(np.uint32) != en32[live].astype(F).view(np.uint32)).sum())
+    print("RESIDUAL PLOT %s: %d of %d projections and %d of %d energies differ from the fp32 oracle in some bit" % (what, nbits, 16 * int(live.sum()), ebits, int(live.sum())))
+
+
+def test_projections_and_energies_against_the_oracle_640x480():
+    win = synth.make_window(640, 480, W=8, P=2000)
+    check_against_oracle(win, "640x480 W=8 P=2000", state6=synth.perturbed_poses(win, sigma_t=0.004, sigma_r=0.0004))
+
+
+def test_projections_and_energies_against_the_oracle_planted():
+    win, aff, ex = scenes.planted(80, 48, 3, (63, 1, 65), seed=80)
+    check_against_oracle(win, "planted 80x48 W=3", aff=aff, exposure=ex)
+
+
+# ------------------------------------------------------------------------------------------------ 2: the painting against the model
+def want_aff(frames, host):
+    """the numpy formula: AffLight::fromToVecExposure(f2.ab_exposure, f.ab_exposure, f2.aff_g2l(), f.aff_g2l()) from what nalo_ba_get_frames reports"""
+    f = frames[host]
+    out = []
+    for f2 in frames:
+        out.append(rp.aff_l(f2.ab_exposure, f.ab_exposure, KC["SCALE_A"] * f2.state[6], KC["SCALE_B"] * f2.state[7], KC["SCALE_A"] * f.state[6], KC["SCALE_B"] * f.state[7]))
+    return np.array(out)
+
+
+def read_back(c, slots):
+    """what the model is fed with, from the context's getters"""
+    pr, en = c.ba_pattern_projections()
+    return dict(I=[c.frame_download(s, 0)[0][:, 0].copy() for s in slots], state=c.ba_get_residuals()[0], proj=pr, energy=en, idepth=c.ba_get_points()["idepth"],
+                frames=c.ba_get_frames()[0])
+
+
+def check_plot(c, rb, host_arr, u, v, host, p5, mask=0, rs=1.0, fids=None, fn=rp.fast, what=""):
+    got = c.ba_residual_plot(host, p5, mask, rs)
+    W = len(rb["I"])
+    sel = rp.painted(W, mask)
+    aff_all = want_aff(rb["frames"], host)
+    assert got["aff"].shape == (len(sel), 2)
+    assert np.all(np.abs(got["aff"] - aff_all[sel]) <= 1e-14 * np.abs(aff_all[sel])), (what, got["aff"], aff_all[sel])
+    aff = aff_all.copy()
+    aff[sel] = got["aff"]                                                      # the model transfers with what the call returned
+    m = host_arr == host
+    ids = (F(KC["SCALE_IDEPTH"]) * rb["idepth"][m]).astype(F)
+    want = fn(rb["I"], aff, c.w, c.h, host, u[m], v[m], ids, rb["state"][m], rb["energy"][m], rb["proj"][m], p5, rs, mask)
+    tag = "%s host %d param5 %g mask %x" % (what, host, p5, mask)
+    assert got["bgr"].shape == want["bgr"].shape, tag
+    bad = (got["bgr"] != want["bgr"]).any(axis=3)
+    assert not bad.any(), "%s: %d pixels differ, first at (image, y, x) = %s" % (tag, int(bad.sum()), tuple(np.argwhere(bad)[0]))
+    assert (got["n_points"], got["n_residuals"], got["n_pattern_pixels"]) == (want["n_points"], want["n_residuals"], want["n_pattern_pixels"]), tag
+    if fids is not None:
+        assert got["frame_id"] == [fids[i] for i in sel], tag
+    return got, want
+
+
+@pytest.mark.parametrize("w,h,W,sizes,masks", [(64, 32, 2, (257, 64), (0b01, 0b10)), (80, 48, 3, (63, 1, 65), (0b101, 0b010))])
+def test_planted_windows(w, h, W, sizes, masks):
+    win, aff, ex = scenes.planted(w, h, W, sizes, seed=w)
+    fids = [70 + 5 * i for i in range(W)]
+    c = make_ctx(win, aff=aff, exposure=ex, frame_ids=fids)
+    c.ba_linearize(False)
+    rb = read_back(c, list(range(W)))
+    st, pr = rb["state"], rb["proj"]
+    live = (st >= 0) & (st != rp.OOB)
+    # the cases are there, by the read-back
+    assert (st == rp.IN).sum() > 20 and (st == rp.OUTLIER).sum() > 20 and (st == rp.OOB).sum() > 2
+    assert ((pr[live] > 1.1) & (pr[live] <= 2)).sum() > 4, "no coordinate in (1.1, 2]: IN, but behind the plot's guard"
+    same_px = [p for p in range(len(win.host) - 1) if win.host[p] == win.host[p + 1] and win.u[p] == win.u[p + 1] and win.v[p] == win.v[p + 1]]
+    assert same_px and any(live[p, t] and live[p + 1, t] and np.array_equal(pr[p, t], pr[p + 1, t]) and rb["energy"][p, t] != rb["energy"][p + 1, t]
+                           for p in same_px for t in range(W)), "no two points on the same pixels with different energies"
+    clamps = set()
+    for host in range(W):
+        for p5 in (0.0, 1.0):
+            got, want = check_plot(c, rb, win.host, win.u, win.v, host, p5, fids=fids, fn=rp.literal if (host, p5) == (0, 0.0) else rp.fast, what="%dx%d" % (w, h))
+            assert got["n_points"] == sizes[host]
+            again = c.ba_residual_plot(host, p5)
+            assert again["bgr"].tobytes() == got["bgr"].tobytes()
+            for mask in masks:
+                check_plot(c, rb, win.host, win.u, win.v, host, p5, mask, rs=0.6, fids=fids, what="%dx%d" % (w, h))
+        a = want_aff(rb["frames"], host)
+        for f2 in range(W):
+            colL = a[f2][0] * rb["I"][f2].astype(np.float64) + a[f2][1]
+            clamps |= ({"low"} if (colL < 0).any() else set()) | ({"high"} if (colL > 255).any() else set())
+    assert clamps == {"low", "high"}, "the base image's clamps do not both fire"
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3: the device chain, against a twin that never plots
+def bits_of(c):
+    pts = c.ba_get_points()
+    out = [pts[k] for k in sorted(pts)] + list(c.ba_get_residuals()) + list(c.ba_get_prior()) + list(c.ba_pattern_projections())
+    out += [np.frombuffer(bytes(c.ba_get_frames()[0]), np.uint8)]
+    return [np.ascontiguousarray(x) for x in out]
+
+
+def test_three_keyframes_of_the_device_chain_against_a_twin():
+    w, h, WW, P, KF = 1224, 368, 8, 2000, 3
+    s = 3e-4
+    win = synth.make_window(w=w, h=h, W=WW, P=P, seed=sc.SEED, n_extra=KF, step_z=0.8 * s, step_x=0.03 * s, full_graph=False)
+    nF = WW + KF
+    rng = np.random.RandomState(sc.SEED + 3)
+    st6 = np.zeros((nF, 6))
+    st6[1:, :3] = 0.004 * rng.randn(nF - 1, 3) / 0.5
+    st6[1:, 3:] = 0.0004 * rng.randn(nF - 1, 3)
+    A, T = [binding.Context(win.w, win.h, win.K, n_slots=nF) for _ in range(2)]
+    fids, slots = [200 + i for i in range(WW)], list(range(WW))
+    for c in (A, T):
+        for i in range(nF):
+            c.frame_upload(i, win.images[i])
+        c.ba_set_prior_carry(True)
+        c.ba_set_window(slots, win.world_to_cam[:WW], state6=st6[:WW], frame_ids=fids)
+        c.ba_set_points(win.host, win.u, win.v, win.idepth, win.color, win.weights)
+        c.ba_set_residuals(win.exists)
+        ng0, lt0, ls0 = lm.default_history(win.exists)
+        ls0[win.host == WW - 1, 0] = lm.IN
+        c.ba_set_point_history(ng0, lt0, ls0)
+    host, u, v = win.host.copy(), win.u, win.v
+    for kf in range(KF):
+        if kf:
+            for c in (A, T):
+                c.ba_carry_window(c.frame_state(WW - 1 + kf, win.world_to_cam[WW - 1 + kf], frame_id=200 + WW - 1 + kf, state6=st6[WW - 1 + kf]))
+            m = A.ba_carry_map()
+            assert np.array_equal(m, T.ba_carry_map())
+            host, u, v = host[m] - 1, u[m], v[m]
+            fids, slots = fids[1:] + [200 + WW - 1 + kf], slots[1:] + [WW - 1 + kf]
+        for c in (A, T):
+            c.ba_optimize(3)
+        for k, (x, y) in enumerate(zip(bits_of(A), bits_of(T))):
+            assert x.shape == y.shape and x.tobytes() == y.tobytes(), "keyframe %d: the plotting context left its twin at read-back %d" % (kf, k)
+        rb = read_back(T, slots)                                               # the read-back route, on the context that never plots
+        live = (rb["state"] >= 0) & (rb["state"] != rp.OOB)
+        print("RESIDUAL PLOT chain keyframe %d: %d points, %d residuals drawn" % (kf, len(host), int(live.sum())))
+        drawn = 0
+        for hst, p5, mask in ((0, 0.0, 0), (WW - 1, 1.0, 0), (3 + kf, 0.0, 0b10010001)):         # (after a carry the newest frame hosts no point yet)
+            got, _ = check_plot(A, rb, host, u, v, hst, p5, mask, fids=fids, what="chain keyframe %d" % kf)
+            drawn += got["n_residuals"]
+        assert drawn > 200
+        ff = np.zeros(WW, np.uint8); ff[0] = 1
+        da, db = A.ba_flag_points(ff), T.ba_flag_points(ff)
+        for x, y in zip(da, db):
+            assert np.ascontiguousarray(x).tobytes() == np.ascontiguousarray(y).tobytes(), "keyframe %d: nalo_ba_flag_points differs from the twin's" % kf
+        if kf + 1 < KF:
+            for c in (A, T):
+                c.ba_marginalize_flagged()
+                c.ba_marginalize_frame(0)
+            if kf == 0:                                                         # the point arrays are unset until the carry: refused, nothing written
+                sentinel = np.full((WW, h, w, 3), 0xA5, np.uint8)
+                rc, a = _raw(A, sentinel)
+                assert rc == ERR_STATE and b"unset" in A.L.nalo_last_error(A.h_) and (sentinel == 0xA5).all() and a.n_frames == -7
+    A.close()
+    T.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4: refusals
+def _raw(c, bgr, host=0, p5=0.0, rs=1.0, mask=0, null_args=False, null_ctx=False):
+    a = binding.ResidualPlotArgs()
+    a.host, a.free_debug_param5, a.rainbow_scale, a.frame_mask = host, p5, rs, mask
+    a.bgr = None if bgr is None else bgr.ctypes.data_as(binding.c_u8p)
+    a.n_frames = a.n_points = a.n_residuals = a.n_pattern_pixels = -7
+    a.aff[0][0] = -7.0
+    rc = c.L.nalo_ba_residual_plot(None if null_ctx else c.h_, None if null_args else C.byref(a))
+    return rc, a
+
+
+def test_refusals_leave_the_outputs_untouched():
+    w, h, W = 80, 48, 3
+    bgr = np.full((W, h, w, 3), 0xA5, np.uint8)
+
+    def untouched(a=None):
+        return (bgr == 0xA5).all() and (a is None or (a.n_frames, a.n_points, a.n_residuals, a.n_pattern_pixels, a.aff[0][0]) == (-7, -7, -7, -7, -7.0))
+    win, aff, ex = scenes.planted(w, h, W, (65, 0, 64), seed=5)                 # frame 1 hosts nothing
+    # no window
+    c0 = binding.Context(w, h, win.K, n_slots=1)
+    c0.frame_upload(0, win.images[0])
+    rc, a = _raw(c0, bgr)
+    assert rc == ERR_STATE and untouched(a)
+    with pytest.raises(binding.NaloError):
+        c0.ba_pattern_projections()
+    c0.close()
+    c = make_ctx(win, aff=aff, exposure=ex)
+    c.ba_linearize(False)
+    before = bits_of(c)
+    assert _raw(c, bgr, null_ctx=True)[0] == ERR_ARG and _raw(c, bgr, null_args=True)[0] == ERR_ARG
+    for kw in (dict(host=-1), dict(host=W), dict(mask=0b1000), dict(mask=1 << 31), dict(rs=np.nan), dict(rs=np.inf), dict(p5=np.nan), dict(p5=-np.inf)):
+        rc, a = _raw(c, bgr, **kw)
+        assert rc == ERR_ARG and untouched(a), kw
+    rc, a = _raw(c, None)
+    assert rc == ERR_ARG and untouched(a)
+    for x, y in zip(before, bits_of(c)):
+        assert x.tobytes() == y.tobytes()
+    # the call works after the refusals, and writes only the images it paints
+    rb = read_back(c, [0, 1, 2])
+    m = win.host == 2
+    rc, a = _raw(c, bgr, host=2, p5=1.0, mask=0b10)
+    want = rp.fast(rb["I"], want_aff(rb["frames"], 2), w, h, 2, win.u[m], win.v[m], rb["idepth"][m], rb["state"][m], rb["energy"][m], rb["proj"][m], 1.0, 1.0, 0b10)
+    assert rc == 0 and a.n_frames == 1 and a.n_points == 64 and np.array_equal(bgr[0], want["bgr"][0]) and (bgr[1:] == 0xA5).all()
+    bgr[:] = 0xA5
+    # either output of the read-back may be NULL
+    pr, en = c.ba_pattern_projections()
+    pr2, en2 = np.zeros_like(pr), np.zeros_like(en)
+    c._ck(c.L.nalo_ba_get_pattern_projections(c.h_, binding._f(pr2), None))
+    c._ck(c.L.nalo_ba_get_pattern_projections(c.h_, None, binding._f(en2)))
+    assert pr2.tobytes() == pr.tobytes() and en2.tobytes() == en.tobytes()
+    # (point arrays unset between nalo_ba_marginalize_frame and the carry: in the chain test, where a frame can leave)
+    # a sharded window, then a context whose cross-rank exchange failed
+    c.ba_set_allreduce(lambda ptr, n: None)
+    rc, a = _raw(c, bgr)
+    assert rc == ERR_STATE and b"sharded" in c.L.nalo_last_error(c.h_) and untouched(a)
+    c.ba_exchange_failed("link down (residual plot test)")
+    rc, a = _raw(c, bgr)
+    assert rc == ERR_HIP and untouched(a)
+    c.close()
