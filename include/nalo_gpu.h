@@ -195,6 +195,31 @@ int nalo_frame_download(nalo_ctx* ctx, int slot, int lvl, float* dI3, float* abs
 /* test/inspection: the slot's level-0 mask (w*h floats) and colour (3*w*h bytes) as nalo_frame_upload[_async] stored them or nalo_frame_upload_raw resized them;
  * either may be NULL (not both). NALO_ERR_STATE when the slot holds no pyramid or lacks a plane that is asked for (nothing is written then), NALO_ERR_ARG on a bad slot. */
 int nalo_frame_download_mask(nalo_ctx* ctx, int slot, float* mask, uint8_t* bgr);
+/* Views of what is resident: the library describing its own device memory, the reverse of nalo_frame_ingest_device. Host code only: nothing is launched, copied or
+ * waited for. The reference tracks on the caller's thread and maps on its own (FullSystem.cpp:1183-1252), so a binder keeps one context per thread; a view is
+ * the plain struct that crosses between them (see also nalo_trk_ref_export / nalo_trk_ref_import below).
+ * nalo_frame_plane   fills *out with a descriptor of one level-0 plane of the slot, which nalo_dev_plane_check accepts and nalo_frame_ingest_device reads:
+ *                    NALO_PLANE_IRRADIANCE  F32, w x h, contiguous (what nalo_frame_download(slot, 0) returns as I, bit for bit)
+ *                    NALO_PLANE_MASK        F32, w x h, contiguous        NALO_PLANE_COLOUR  U8 x 3, interleaved B,G,R
+ *                    It refuses exactly where nalo_frame_download_mask refuses: NALO_ERR_ARG for a NULL ctx or out, a bad slot or a bad `which`; NALO_ERR_STATE
+ *                    for a slot without a pyramid or without the plane asked for. On a refusal *out is untouched.
+ *   The frame hand-off from a tracking context T to a mapping context M needs no more than this: nalo_frame_plane(T, slot, ...) for the irradiance (and mask and
+ *   colour where the slot has them), then nalo_frame_ingest_device(M, slot', {image = the F32 plane, mask, colour, the same gammaB, producer_stream =
+ *   nalo_stream(T)}). Level 0 is copied as words and the pyramid is rebuilt from it, so M's slot equals T's bit for bit on every level, at 4 bytes read per pixel
+ *   where a copy of the pyramid would move 24 B x 1.33. nalo_frame_release(M, slot', nalo_stream(T)) is the back edge before T reuses its slot.
+ * Lifetime of a view (a nalo_dev_plane from nalo_frame_plane, a nalo_trk_ref_view from nalo_trk_ref_export): a snapshot of pointers and counts that owns nothing.
+ *   It describes what the source's main stream (nalo_stream) has produced once everything queued on that stream at the time of the call has run - a consumer on
+ *   another stream waits for that stream first, which nalo_frame_ingest_device (producer_stream) and nalo_trk_ref_import (view->stream) do on the device. It stays
+ *   good until the next call that rewrites what it names: an upload, ingest or attach into the slot; nalo_trk_set_ref*, nalo_trk_set_pc, nalo_trk_set_depth, the
+ *   append calls (nalo_trk_append_plane_points, nalo_trk_fit_planes / nalo_trk_fit_ground with append) or nalo_trk_ref_import. It never outlives nalo_destroy.
+ * Threads: the library takes no locks. A context is used by one thread at a time; nalo_frame_plane and nalo_trk_ref_export are called by the thread that owns the
+ *   source (or under the lock that orders its rewriting calls - coarseTrackerSwapMutex in the reference), nalo_frame_ingest_device and nalo_trk_ref_import by the
+ *   thread that owns the destination. A wait or a record on the other context's main stream goes through the raw stream handle only: neither the import's wait
+ *   nor nalo_trk_ref_release / nalo_frame_release reads or writes the other nalo_ctx. */
+#define NALO_PLANE_IRRADIANCE 0   /* level 0, F32, w x h, contiguous */
+#define NALO_PLANE_MASK       1   /* F32, w x h */
+#define NALO_PLANE_COLOUR     2   /* U8 x 3, interleaved B,G,R */
+int nalo_frame_plane(nalo_ctx* ctx, int slot, int which, nalo_dev_plane* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Front-end tracker.
@@ -241,6 +266,39 @@ int nalo_trk_get_depth(nalo_ctx* ctx, int lvl, float* idepth, float* weight_sums
  * idepth leaves the level's inverse depths untouched, a NULL weight_sums its weight sums. Nothing else is touched: no cloud, no other level. For tests (maps the scatter
  * and dilation of nalo_trk_set_ref never produce) and as the missing half of a tracker checkpoint. */
 int nalo_trk_set_depth(nalo_ctx* ctx, int slot_ref, int lvl, const float* idepth, const float* weight_sums);
+/* The tracking reference between contexts, on the device. The reference keeps two CoarseTracker objects: makeKeyFrame rebuilds the idle one on the mapping thread
+ * under coarseTrackerSwapMutex (FullSystem.cpp:1401-1410) and addActiveFrame swaps it in on the tracking thread (:1094-1098). Here the mapping context builds the
+ * reference where its window lives (nalo_trk_set_ref_from_window), describes it, and the tracking context clones it from device memory: no cloud or map visits
+ * the host. Lifetime of a view and the thread contract: see nalo_frame_plane above.
+ * nalo_trk_ref_export   fills *out with the context's current reference: per level the cloud's count and arrays, the idepth[] and weightSums[] maps (NULL where the
+ *                       level has none, e.g. after nalo_trk_set_pc alone), CoarseTracker::makeK's intrinsics, and the context's main stream as the producer.
+ *                       Host code only, no launch. NALO_ERR_ARG: NULL ctx / out. NALO_ERR_STATE: the context has no reference; *out is untouched then.
+ * nalo_trk_ref_import   dst becomes a clone of the described reference: the first n[l] floats of u, v, idepth and color and both maps of every level are copied,
+ *                       pc_n and the level intrinsics are taken over (the clouds mean nothing under another K; the reference calls makeK on the same object,
+ *                       :1403), and dst's reference slot becomes slot_ref, which must hold the reference frame's pyramid in dst (nalo_trk_depth_image and the
+ *                       append calls read it). A level whose map pointers are NULL has dst's maps zero-filled: dst never mixes two references. The view need not
+ *                       come from nalo_trk_ref_export - pointers into a caller's device arrays make a reference of the caller's own; they must not overlap dst's.
+ *                       Stream order, as in nalo_frame_ingest_device: dst's main stream waits, on the device, for what view->stream (NULL: the null stream) has
+ *                       queued at the time of the call - skipped when that is dst's own stream -, ONE kernel copies every segment, and an event behind it
+ *                       serves nalo_trk_ref_release. The counts arrive with the view: with its buffers sized, the call makes no host wait and no allocation.
+ *                       Everything is checked before anything is queued or reserved; a refused call leaves dst's reference bit-identical. NALO_ERR_ARG: a NULL
+ *                       ctx or view; w, h or levels that differ from dst's; n[l] < 0 or n[l] > (w>>l)*(h>>l); a NULL cloud pointer with n[l] > 0; a map pointer
+ *                       given for one of the pair only; a pointer that is no multiple of 4 or that hipPointerGetAttributes does not report as device memory of
+ *                       dst's GPU (nalo_dev_plane_check's test: host, pinned, managed and other devices' memory), or whose extent leaves its allocation; a bad
+ *                       slot_ref. NALO_ERR_STATE: slot_ref holds no pyramid. NALO_ERR_HIP: a cross-rank exchange of dst failed earlier (as nalo_trk_track).
+ * nalo_trk_ref_release  `stream` (NULL: the null stream) waits, on the device, until dst's last import has read its source: the back edge before the source
+ *                       rewrites its reference - nalo_trk_ref_release(tracker, nalo_stream(mapper)). Nothing to wait for: NALO_OK. */
+typedef struct nalo_trk_ref_view {
+    int w, h, levels, slot_ref;                       /* of the context that made it */
+    int n[NALO_MAX_LEVELS];                           /* pc_n */
+    const float *u[NALO_MAX_LEVELS], *v[NALO_MAX_LEVELS], *idepth[NALO_MAX_LEVELS], *color[NALO_MAX_LEVELS];   /* n[l] floats each */
+    const float *idepth_map[NALO_MAX_LEVELS], *weight_sums[NALO_MAX_LEVELS];   /* (w>>l) x (h>>l) floats; NULL: the level has none */
+    float fx[NALO_MAX_LEVELS], fy[NALO_MAX_LEVELS], cx[NALO_MAX_LEVELS], cy[NALO_MAX_LEVELS];   /* CoarseTracker::makeK's */
+    void* stream;                                     /* the producer: the source's main stream */
+} nalo_trk_ref_view;
+int nalo_trk_ref_export(nalo_ctx* src, nalo_trk_ref_view* out);
+int nalo_trk_ref_import(nalo_ctx* dst, int slot_ref, const nalo_trk_ref_view* view);
+int nalo_trk_ref_release(nalo_ctx* dst, void* stream);
 
 /* CoarseTracker::debugPlotIDepthMap (CoarseTracker.cpp:1263-1359; FullSystem.cpp:1408 -> Output3DWrapper::pushDepthImage) on the device: the jet-coloured depth image
  * of the current tracking reference, from the level-0 inverse-depth map (what nalo_trk_get_depth(ctx, 0, ...) returns) and the planar irradiance I[0] of the reference's

@@ -28,8 +28,8 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
-    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_frame_ingest_device", "nalo_frame_release", "nalo_dev_plane_check", "nalo_frame_attach", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask",
-    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
+    "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_frame_ingest_device", "nalo_frame_release", "nalo_dev_plane_check", "nalo_frame_attach", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask", "nalo_frame_plane",
+    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_ref_export", "nalo_trk_ref_import", "nalo_trk_ref_release", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
@@ -59,6 +59,18 @@ class DevPlane(C.Structure):                              # nalo_dev_plane; dev_
 class FrameIngestArgs(C.Structure):                       # nalo_frame_ingest_args
     _fields_ = [("image", C.POINTER(DevPlane)), ("exposure_time", C.c_float), ("factor", C.c_float), ("mask", C.POINTER(DevPlane)), ("colour", C.POINTER(DevPlane)),
                 ("colour_is_rgb", C.c_int), ("gammaB", c_fp), ("producer_stream", C.c_void_p)]
+
+
+MAX_LEVELS = 6                                           # NALO_MAX_LEVELS
+PLANE_IRRADIANCE, PLANE_MASK, PLANE_COLOUR = 0, 1, 2      # NALO_PLANE_* (nalo_frame_plane's `which`)
+_PLANE_NAMES = {"irradiance": PLANE_IRRADIANCE, "mask": PLANE_MASK, "colour": PLANE_COLOUR}
+
+
+class TrkRefView(C.Structure):                            # nalo_trk_ref_view; trk_ref_view() builds one from device arrays
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("levels", C.c_int), ("slot_ref", C.c_int), ("n", C.c_int * MAX_LEVELS),
+                ("u", C.c_void_p * MAX_LEVELS), ("v", C.c_void_p * MAX_LEVELS), ("idepth", C.c_void_p * MAX_LEVELS), ("color", C.c_void_p * MAX_LEVELS),
+                ("idepth_map", C.c_void_p * MAX_LEVELS), ("weight_sums", C.c_void_p * MAX_LEVELS),
+                ("fx", C.c_float * MAX_LEVELS), ("fy", C.c_float * MAX_LEVELS), ("cx", C.c_float * MAX_LEVELS), ("cy", C.c_float * MAX_LEVELS), ("stream", C.c_void_p)]
 
 
 class InitWindowArgs(C.Structure):
@@ -340,6 +352,10 @@ def load():
     L.nalo_trk_get_pc.argtypes = [vp, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_get_depth.argtypes = [vp, C.c_int, c_fp, c_fp]
     L.nalo_trk_set_depth.argtypes = [vp, C.c_int, C.c_int, c_fp, c_fp]
+    L.nalo_frame_plane.argtypes = [vp, C.c_int, C.c_int, C.POINTER(DevPlane)]
+    L.nalo_trk_ref_export.argtypes = [vp, C.POINTER(TrkRefView)]
+    L.nalo_trk_ref_import.argtypes = [vp, C.c_int, C.POINTER(TrkRefView)]
+    L.nalo_trk_ref_release.argtypes = [vp, vp]
     L.nalo_trk_depth_image.argtypes = [vp, C.POINTER(DepthImageArgs)]
     L.nalo_trk_eval.argtypes = [vp, C.c_int, C.c_int, c_dp, c_dp, c_fp, C.c_float, C.c_float, C.c_int, c_dp, c_dp, c_dp]
     L.nalo_trk_track.argtypes = [vp, C.c_int, c_dp, c_dp, c_dp, c_fp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]
@@ -533,6 +549,98 @@ def dev_plane(obj, channels_layout=None):
     return d
 
 
+class DeviceView:
+    """Device memory somebody else owns, as an object with __cuda_array_interface__ (version 2): torch.as_tensor(view) is a zero-copy tensor, dev_plane(view)
+    its descriptor. Nothing is copied and nothing is owned: the view is good as long as what it names (include/nalo_gpu.h, "Lifetime of a view"). stream: the
+    hipStream_t (an int) whose queued work produces the memory - frame_ingest and trk_ref_import wait for it on the device; a torch consumer on another stream
+    waits for it itself. owner: kept alive with the view (the Context)."""
+
+    def __init__(self, ptr, shape, typestr, strides=None, stream=0, owner=None):
+        self.ptr, self.shape, self.typestr, self.stream, self.owner = int(ptr or 0), tuple(int(v) for v in shape), typestr, int(stream or 0), owner
+        self.strides = None if strides is None else tuple(int(v) for v in strides)
+        self.__cuda_array_interface__ = dict(shape=self.shape, typestr=typestr, data=(self.ptr, False), strides=self.strides, version=2)
+
+    @classmethod
+    def of_plane(cls, d, stream=0, owner=None):
+        """a DevPlane (nalo_frame_plane's) as a view: (h, w) for one channel, (h, w, 3) for interleaved colour; strides are given only where they are not C-contiguous"""
+        typestr = {DT_U8: "|u1", DT_U16: "<u2", DT_I32: "<i4", DT_F32: "<f4"}[d.dtype]
+        item = int(typestr[2])
+        if d.channels == 1:
+            shape, strides, dense = (d.h, d.w), (d.stride_y, d.stride_x), (d.w * item, item)
+        else:
+            shape, strides, dense = (d.h, d.w, d.channels), (d.stride_y, d.stride_x, d.stride_c), (d.w * d.channels * item, d.channels * item, item)
+        return cls(d.ptr, shape, typestr, None if tuple(strides) == dense else strides, stream, owner)
+
+
+def pyr_intrinsics(K, levels):
+    """(fx, fy, cx, cy) per level as nalo_create derives them from K (CoarseTracker::makeK, CoarseTracker.cpp:97-141): float32 arrays of `levels` entries"""
+    out = np.zeros((4, levels), np.float32)
+    out[:, 0] = np.asarray(K, np.float32)
+    for l in range(1, levels):
+        out[0, l], out[1, l] = np.float32(float(out[0, l - 1]) * 0.5), np.float32(float(out[1, l - 1]) * 0.5)
+        out[2, l], out[3, l] = np.float32((float(out[2, 0]) + 0.5) / (1 << l) - 0.5), np.float32((float(out[3, 0]) + 0.5) / (1 << l) - 0.5)
+    return out
+
+
+def _dense_f4(obj, what, shapes):
+    """(pointer, element count, the object) of a dense little-endian float32 device array whose shape is one of `shapes`"""
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError("trk_ref_view: %s: %s has no __cuda_array_interface__ (device arrays only: nothing is copied to the device here)" % (what, type(obj).__name__))
+    if cai["typestr"] != "<f4":
+        raise NaloError("trk_ref_view: %s: typestr %r, float32 ('<f4') is required" % (what, cai["typestr"]))
+    shape = tuple(int(v) for v in cai["shape"])
+    if shapes is not None and shape not in shapes:
+        raise NaloError("trk_ref_view: %s: shape %r, expected one of %r" % (what, shape, shapes))
+    strides = cai.get("strides")
+    if strides is not None:
+        dense, acc = [], 4
+        for k in reversed(shape):
+            dense.insert(0, acc)
+            acc *= k
+        if any(k > 1 and int(st) != de for k, st, de in zip(shape, strides, dense)):
+            raise NaloError("trk_ref_view: %s: strides %r are not dense (the copy reads consecutive words; make it contiguous on the producer's side)" % (what, tuple(strides)))
+    n = int(np.prod(shape)) if shape else 1
+    return int(cai["data"][0]) or None, n, obj
+
+
+def trk_ref_view(w, h, levels, per_level, intrinsics, stream=0, slot_ref=-1):
+    """nalo_trk_ref_view (a TrkRefView) from device arrays: per_level is a sequence of `levels` dicts with the 1-D float32 arrays u, v, idepth, color (equal
+    length; all absent or None: an empty cloud) and the maps idepth_map, weight_sums ((h>>l, w>>l) or flat; both or neither - neither: the importer zero-fills).
+    Any object with __cuda_array_interface__ serves; a slice 4 bytes off a 16-byte boundary is fine. intrinsics: (fx, fy, cx, cy) per level (pyr_intrinsics).
+    Pure host code; the struct keeps the arrays alive."""
+    if not 1 <= levels <= MAX_LEVELS or len(per_level) != levels:
+        raise NaloError("trk_ref_view: %d levels described, %d expected (at most %d)" % (len(per_level), levels, MAX_LEVELS))
+    intr = np.asarray(intrinsics, np.float32)
+    if intr.shape != (4, levels):
+        raise NaloError("trk_ref_view: intrinsics are (fx, fy, cx, cy) x levels")
+    V = TrkRefView()
+    V.w, V.h, V.levels, V.slot_ref, V.stream = w, h, levels, slot_ref, stream or None
+    keep = []
+    for l, lv in enumerate(per_level):
+        cloud = [lv.get(k) for k in ("u", "v", "idepth", "color")]
+        if any(a is not None for a in cloud):
+            if any(a is None for a in cloud):
+                raise NaloError("trk_ref_view: level %d: u, v, idepth and color come together" % l)
+            got = [_dense_f4(a, "level %d %s" % (l, k), None) for a, k in zip(cloud, ("u", "v", "idepth", "color"))]
+            if any(len(a.__cuda_array_interface__["shape"]) != 1 for a in cloud) or len({g[1] for g in got}) != 1:
+                raise NaloError("trk_ref_view: level %d: u, v, idepth and color are 1-D arrays of equal length" % l)
+            V.n[l] = got[0][1]
+            V.u[l], V.v[l], V.idepth[l], V.color[l] = (g[0] if got[0][1] else None for g in got)
+            keep += cloud
+        maps = [lv.get("idepth_map"), lv.get("weight_sums")]
+        if (maps[0] is None) != (maps[1] is None):
+            raise NaloError("trk_ref_view: level %d: idepth_map and weight_sums are given together or not at all" % l)
+        if maps[0] is not None:
+            wl, hl = w >> l, h >> l
+            got = [_dense_f4(a, "level %d %s" % (l, k), ((hl, wl), (hl * wl,))) for a, k in zip(maps, ("idepth_map", "weight_sums"))]
+            V.idepth_map[l], V.weight_sums[l] = got[0][0], got[1][0]
+            keep += maps
+        V.fx[l], V.fy[l], V.cx[l], V.cy[l] = (float(x) for x in intr[:, l])
+    V._keep = keep
+    return V
+
+
 def shard_points(host, u, v, W, img_w, img_h, rank, world):
     """indices (ascending) of the active points rank `rank` of `world` keeps: nalo_shard_points, host code (no device needed)"""
     L = load()
@@ -635,6 +743,9 @@ class Context:
             stream = 0
             torch = sys.modules.get("torch")                       # a torch.Tensor exists only where torch has been imported: never imported for other producers
             for o in (image, mask, colour):
+                if isinstance(o, DeviceView):                      # a view of another context's slot: that context's main stream produced it
+                    stream = o.stream
+                    break
                 if torch is not None and isinstance(o, torch.Tensor):
                     stream = torch.cuda.current_stream(o.device).cuda_stream
                     break
@@ -728,6 +839,54 @@ class Context:
         a = [None if x is None else np.ascontiguousarray(x, np.float32).reshape(-1) for x in (idepth, weight_sums)]
         assert all(x is None or x.size == n for x in a)
         self._ck(self.L.nalo_trk_set_depth(self.h_, slot, lvl, _f(a[0]), _f(a[1])))
+
+    def frame_plane(self, slot, which):
+        """nalo_frame_plane: a DeviceView of the slot's level-0 irradiance ('irradiance' / PLANE_IRRADIANCE: (h, w) float32), mask ('mask': (h, w) float32) or
+        colour ('colour': (h, w, 3) uint8, B,G,R). Zero-copy: torch.as_tensor(view) aliases the slot, and another context's frame_ingest(slot, image=view, ...)
+        reads it where it lies, waiting on the device for this context's stream. Launches nothing. Good until the slot is rewritten or the context closed."""
+        d = DevPlane()
+        self._ck(self.L.nalo_frame_plane(self.h_, slot, _PLANE_NAMES.get(which, which), C.byref(d)))
+        return DeviceView.of_plane(d, self.stream, self)
+
+    def trk_ref_export(self):
+        """nalo_trk_ref_export: dict(view = the raw TrkRefView for another context's trk_ref_import, n, slot_ref, intrinsics (4, levels), stream, levels = per level a
+        dict of DeviceViews u, v, idepth, color (n[l] floats) and idepth_map, weight_sums ((h>>l, w>>l), or None where the level has none)). Launches nothing."""
+        V = TrkRefView()
+        self._ck(self.L.nalo_trk_ref_export(self.h_, C.byref(V)))
+        st = int(V.stream or 0)
+        lv = []
+        for l in range(V.levels):
+            d = {k: DeviceView(getattr(V, k)[l], (V.n[l],), "<f4", None, st, self) for k in ("u", "v", "idepth", "color")}
+            for k in ("idepth_map", "weight_sums"):
+                d[k] = DeviceView(getattr(V, k)[l], (self.h >> l, self.w >> l), "<f4", None, st, self) if getattr(V, k)[l] else None
+            lv.append(d)
+        intr = np.array([[getattr(V, k)[l] for l in range(V.levels)] for k in ("fx", "fy", "cx", "cy")], np.float32)
+        return dict(view=V, n=[V.n[l] for l in range(V.levels)], slot_ref=V.slot_ref, intrinsics=intr, stream=st, levels=lv)
+
+    def trk_ref_import(self, slot, view, intrinsics=None, stream=None):
+        """nalo_trk_ref_import: this context's tracking reference becomes a clone of `view` - a TrkRefView, what trk_ref_export returned, or a sequence of per-level
+        dicts of device arrays (trk_ref_view; torch tensors serve), for which intrinsics defaults to this context's own (pyr_intrinsics) and stream to torch's
+        current stream of the first tensor found (the null stream otherwise). `slot` holds the reference frame in THIS context. Returns without waiting for the
+        device; trk_ref_release(stream) is the back edge before the source is rewritten."""
+        if isinstance(view, dict) and "view" in view:
+            view = view["view"]
+        if not isinstance(view, TrkRefView):
+            if stream is None:
+                stream = 0
+                torch = sys.modules.get("torch")
+                for o in [a for lv in view for a in lv.values()]:
+                    if isinstance(o, DeviceView):
+                        stream = o.stream
+                        break
+                    if torch is not None and isinstance(o, torch.Tensor):
+                        stream = torch.cuda.current_stream(o.device).cuda_stream
+                        break
+            view = trk_ref_view(self.w, self.h, self.levels, view, pyr_intrinsics(self.K, self.levels) if intrinsics is None else intrinsics, stream)
+        self._ck(self.L.nalo_trk_ref_import(self.h_, slot, C.byref(view)))
+
+    def trk_ref_release(self, stream):
+        """nalo_trk_ref_release: `stream` (a hipStream_t as an int, 0 / None the null stream) waits on the device until this context's last import has read its source"""
+        self._ck(self.L.nalo_trk_ref_release(self.h_, stream or None))
 
     def trk_depth_image(self, minmax=None, want_idepth=False):
         """debugPlotIDepthMap on the device (nalo_trk_depth_image). minmax: the caller's (minIdJetVisTracker, maxIdJetVisTracker) pair, None = the reference's

@@ -3,6 +3,7 @@
 // reference (8x8 LDL^T, SE3::exp); every calcRes/calcGSSSE pair is one fused kernel launch.
 #include "nalo_internal.h"
 #include "trk_device.h"
+#include "handoff_device.h"
 #include <cstdlib>
 
 using namespace nalo;
@@ -592,6 +593,98 @@ int nalo_trk_set_depth(nalo_ctx* c, int slot_ref, int lvl, const float* idepth, 
     if (idepth) NALO_HIP(c, hipMemcpyAsync(c->trk_idepth[lvl].p, idepth, npx * 4, hipMemcpyHostToDevice, c->stream));
     if (wsum) NALO_HIP(c, hipMemcpyAsync(c->trk_wsum[lvl].p, wsum, npx * 4, hipMemcpyHostToDevice, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));                                // the arrays are the caller's: free to reuse on return
+    return NALO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ views and the hand-off between contexts
+// One level-0 plane of a slot as a descriptor (the reverse of nalo_frame_ingest_device). Host code only; the refusals are nalo_frame_download_mask's.
+int nalo_frame_plane(nalo_ctx* c, int slot, int which, nalo_dev_plane* out) {
+    if (!c || !out || slot < 0 || slot >= (int)c->slots.size() || which < NALO_PLANE_IRRADIANCE || which > NALO_PLANE_COLOUR) return fail(c, NALO_ERR_ARG, "nalo_frame_plane: bad argument");
+    const FrameSlot& s = c->slots[slot];
+    if (!s.valid || (which == NALO_PLANE_MASK && !s.mask.p) || (which == NALO_PLANE_COLOUR && !s.bgr.p)) return fail(c, NALO_ERR_STATE, "nalo_frame_plane: the slot holds no such plane");
+    nalo_dev_plane d = {};
+    d.w = c->w; d.h = c->h;
+    if (which == NALO_PLANE_COLOUR) { d.ptr = s.bgr.p; d.dtype = NALO_DT_U8; d.channels = 3; d.stride_y = 3LL * c->w; d.stride_x = 3; d.stride_c = 1; }
+    else { d.ptr = which == NALO_PLANE_MASK ? s.mask.p : s.I[0].p; d.dtype = NALO_DT_F32; d.channels = 1; d.stride_y = 4LL * c->w; d.stride_x = 4; }
+    *out = d;
+    return NALO_OK;
+}
+
+// The current reference as pointers and counts. A level without a cloud (nalo_trk_set_depth alone) reads n = 0, one without maps (nalo_trk_set_pc alone) NULL maps.
+int nalo_trk_ref_export(nalo_ctx* c, nalo_trk_ref_view* out) {
+    if (!c || !out) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_export: bad argument");
+    if (c->slot_ref < 0) return fail(c, NALO_ERR_STATE, "nalo_trk_ref_export: no tracking reference (nalo_trk_set_ref* / nalo_trk_set_pc / nalo_trk_set_depth / nalo_trk_ref_import)");
+    nalo_trk_ref_view v = {};
+    v.w = c->w; v.h = c->h; v.levels = c->levels; v.slot_ref = c->slot_ref;
+    for (int l = 0; l < c->levels; ++l) {
+        const bool cloud = c->pc_u[l].p && c->pc_v[l].p && c->pc_id[l].p && c->pc_col[l].p;
+        v.n[l] = cloud ? c->pc_n[l] : 0;
+        if (cloud) { v.u[l] = c->pc_u[l].p; v.v[l] = c->pc_v[l].p; v.idepth[l] = c->pc_id[l].p; v.color[l] = c->pc_col[l].p; }
+        if (c->trk_idepth[l].p && c->trk_wsum[l].p) { v.idepth_map[l] = c->trk_idepth[l].p; v.weight_sums[l] = c->trk_wsum[l].p; }
+        v.fx[l] = c->fx[l]; v.fy[l] = c->fy[l]; v.cx[l] = c->cx[l]; v.cy[l] = c->cy[l];
+    }
+    v.stream = (void*)(hipStream_t)c->stream;
+    *out = v;
+    return NALO_OK;
+}
+
+// dst becomes a clone of the described reference. Everything is tested before anything is queued or reserved; then the main stream waits (on the device) for the
+// producer, ONE kernel copies every segment (kernels_handoff.hip) and ev_imp is recorded behind it. The other context is never touched: only its stream handle is.
+int nalo_trk_ref_import(nalo_ctx* c, int slot_ref, const nalo_trk_ref_view* v) {
+    const char* who = "nalo_trk_ref_import";
+    if (!c || !v) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: bad argument");
+    if (slot_ref < 0 || slot_ref >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: bad slot_ref");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_trk_ref_import: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    if (v->w != c->w || v->h != c->h || v->levels != c->levels) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: the view's w, h or levels differ from the context's");
+    NALO_HIP(c, hipSetDevice(c->device));
+    for (int l = 0; l < c->levels; ++l) {
+        const long long npx = (long long)c->wl[l] * c->hl[l];
+        if (v->n[l] < 0 || v->n[l] > npx) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: n[l] outside 0 .. (w>>l)*(h>>l)");
+        const float* cloud[4] = {v->u[l], v->v[l], v->idepth[l], v->color[l]};
+        static const char* const cname[4] = {"u", "v", "idepth", "color"};
+        if (v->n[l] > 0) for (int k = 0; k < 4; ++k) {
+            if (!cloud[k]) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: a null cloud pointer with n[l] > 0");
+            nalo_dev_plane d = {};                                             // n floats as one row: dev_plane_validate's pointer, alignment and extent tests
+            d.ptr = cloud[k]; d.dtype = NALO_DT_F32; d.w = v->n[l]; d.h = 1; d.channels = 1; d.stride_y = 4LL * v->n[l]; d.stride_x = 4;
+            const int rc = dev_plane_validate(c, &d, who, cname[k]); if (rc) return rc;
+        }
+        if (!v->idepth_map[l] != !v->weight_sums[l]) return fail(c, NALO_ERR_ARG, "nalo_trk_ref_import: idepth_map and weight_sums are given together or not at all");
+        if (v->idepth_map[l]) for (const float* m : {v->idepth_map[l], v->weight_sums[l]}) {
+            nalo_dev_plane d = {};
+            d.ptr = m; d.dtype = NALO_DT_F32; d.w = c->wl[l]; d.h = c->hl[l]; d.channels = 1; d.stride_y = 4LL * c->wl[l]; d.stride_x = 4;
+            const int rc = dev_plane_validate(c, &d, who, m == v->idepth_map[l] ? "idepth_map" : "weight_sums"); if (rc) return rc;
+        }
+    }
+    if (!c->slots[slot_ref].valid) return fail(c, NALO_ERR_STATE, "nalo_trk_ref_import: slot_ref holds no pyramid");
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "trk_ref_import");
+    HandoffTable T = {};
+    for (int l = 0; l < c->levels; ++l) {
+        const size_t npx = (size_t)c->wl[l] * c->hl[l];
+        NALO_HIP(c, c->trk_idepth[l].reserve(npx)); NALO_HIP(c, c->trk_wsum[l].reserve(npx)); NALO_HIP(c, c->trk_wbak[l].reserve(npx));
+        NALO_HIP(c, c->pc_u[l].reserve(npx)); NALO_HIP(c, c->pc_v[l].reserve(npx)); NALO_HIP(c, c->pc_id[l].reserve(npx)); NALO_HIP(c, c->pc_col[l].reserve(npx));
+        const float* src[6] = {v->u[l], v->v[l], v->idepth[l], v->color[l], v->idepth_map[l], v->weight_sums[l]};
+        float* dst[6] = {c->pc_u[l].p, c->pc_v[l].p, c->pc_id[l].p, c->pc_col[l].p, c->trk_idepth[l].p, c->trk_wsum[l].p};
+        for (int k = 0; k < 6; ++k) {
+            HandoffSeg& S = T.seg[T.nseg++];
+            S.src = reinterpret_cast<const uint32_t*>(src[k]); S.dst = reinterpret_cast<uint32_t*>(dst[k]); S.words = k < 4 ? (size_t)v->n[l] : npx;
+        }
+    }
+    NALO_HIP(c, c->ev_imp.create(hipEventDisableTiming)); NALO_HIP(c, c->ev_prod.create(hipEventDisableTiming));
+    hipStream_t prod = (hipStream_t)v->stream;
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    const int rc = handoff_copy_launch(c, T); if (rc) return rc;
+    NALO_HIP(c, hipEventRecord(c->ev_imp, c->stream));                     // the caller's arrays have been read: nalo_trk_ref_release
+    c->slot_ref = slot_ref;
+    for (int l = 0; l < c->levels; ++l) { c->pc_n[l] = v->n[l]; c->fx[l] = v->fx[l]; c->fy[l] = v->fy[l]; c->cx[l] = v->cx[l]; c->cy[l] = v->cy[l]; }
+    return NALO_OK;
+}
+
+int nalo_trk_ref_release(nalo_ctx* c, void* stream) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->ev_imp) return NALO_OK;                                        // nothing was ever imported: nothing to wait for
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->ev_imp, 0));
     return NALO_OK;
 }
 

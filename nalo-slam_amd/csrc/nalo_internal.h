@@ -117,7 +117,7 @@ struct nalo_ctx {
     // (nalo_destroy has drained them, and deleted ba / pixsel / init, before the context goes).
     nalo::Stream stream, side, copy;         // copy: H2D frame uploads of nalo_frame_upload_async (overlap the kernels of `stream`), created on first use
     nalo::Event ev_main;                     // main-stream marker the copy stream waits on before it overwrites a slot that has been used
-    nalo::Event ev_prod;                     // nalo_frame_ingest_device: recorded on the caller's producer stream, the main stream waits for it
+    nalo::Event ev_prod;                     // nalo_frame_ingest_device, nalo_trk_ref_import: recorded on the caller's producer stream, the main stream waits for it
     nalo::DevBuf<float> gamma_dev;           // 256-entry gamma table of the asynchronous upload path
     float gamma_last[256]; bool gamma_have = false;   // what gamma_dev holds: the table is re-sent only when the caller's differs (and then behind every kernel that may read it)
     // raw-frame ingest (nalo_undist_set / nalo_frame_upload_raw): photometric + geometric undistortion tables, raw staging
@@ -131,6 +131,7 @@ struct nalo_ctx {
     nalo::DevBuf<float> trk_idepth[NALO_MAX_LEVELS], trk_wsum[NALO_MAX_LEVELS], trk_wbak[NALO_MAX_LEVELS];
     nalo::DevBuf<float> pc_u[NALO_MAX_LEVELS], pc_v[NALO_MAX_LEVELS], pc_id[NALO_MAX_LEVELS], pc_col[NALO_MAX_LEVELS];
     int pc_n[NALO_MAX_LEVELS] = {};
+    nalo::Event ev_imp;                      // nalo_trk_ref_import: recorded behind the copy kernel, i.e. the caller's arrays have been read (nalo_trk_ref_release)
     nalo::DevBuf<float> trk_partial;         // [blocks][64]
     nalo::DevBuf<unsigned> trk_ticket;       // trk_eval_kernel's arrival counter (zero between launches)
     nalo::DevBuf<float> ref_res; int ref_res_n = -1;   // nalo_trk_ref_upload: {Ku, Kv, new_idepth, HdiF} of the tracking reference, resident (n = -1: none)
