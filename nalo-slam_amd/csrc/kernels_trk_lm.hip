@@ -22,6 +22,7 @@ namespace nalo {
 // Headline window, same box, back to back: 256: 696, 384: 708, **512: 717-769**, 768 (spills): 670-678, 1024 (spills): 633-640 keyframes/s.
 constexpr int kLmThreads = 512;
 constexpr int kLmStride = 56;
+constexpr int kLmMaxBlocks = 64;                                     // workgroups of a launch: at most this many, or twice as many (trk_lm_blocks)
 
 struct TrkLmParams {
     TrkLevel lv[NALO_MAX_LEVELS];
@@ -206,6 +207,37 @@ __device__ __forceinline__ int lm_max_iterations(int lvl) { return lvl == 0 ? 10
 // The grid is small (<= 2 kLmMaxBlocks workgroups, far below the 256 CUs) so all blocks are co-resident; the poll is bounded anyway, a
 // lost block ends the kernel with an error instead of hanging the device.
 __device__ __forceinline__ unsigned long long lm_pack(float v, unsigned tag) { return ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v); }
+// Entries I, I + 1, ... < cnt of a pass: tag test and sum, in order. cnt is wave-uniform: nested scalar branches (an unrolled loop with a break compiles back
+// into a loop that indexes the registers), each waiting only for the loads up to its own entry.
+template <int I, int N>
+__device__ __forceinline__ void lm_exchange_sum(const unsigned long long (&w)[N], int cnt, unsigned want, bool& pending, double& s) {
+    if constexpr (I < N) {
+        if (I < cnt) {
+            pending |= (unsigned)(w[I] >> 32) != want;
+            s += (double)__uint_as_float((unsigned)w[I]);
+            lm_exchange_sum<I + 1, N>(w, cnt, want, pending, s);
+        }
+    }
+}
+// One pass of a reader lane over column j of the blocks its wave group sums (g, g + 8, ... < nbl, at most N of them): all N words are loaded before any of
+// them is looked at, so the pass costs one memory round trip instead of one per block. The index is clamped rather than the load guarded: with a guard per
+// entry, even a wave-uniform one, the compiler branches around every load and waits for each. An entry past nbl re-reads a block that exists and is ignored.
+// Returns whether a tag is still missing; s = 0 + block g + block g + 8 + ..., each the (double) of its fp32 payload, in that order.
+template <int N>
+__device__ __forceinline__ bool lm_exchange_pass(const unsigned long long* pp, int g, int j, int nbl, unsigned want, double& s) {
+    unsigned long long w[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int b2 = max(min(g + i * (kLmThreads / 64), nbl - 1), 0);
+        w[i] = __hip_atomic_load(&pp[(size_t)b2 * 64 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    int cnt = nbl > g ? (nbl - g + kLmThreads / 64 - 1) / (kLmThreads / 64) : 0;             // this group's blocks are the first cnt entries
+    asm volatile("" : "+s"(cnt));                           // compared per pass (a scalar compare and branch per entry), not kept as N lane masks across the poll
+    bool pending = false;
+    s = 0;
+    lm_exchange_sum<0, N>(w, cnt, want, pending, s);
+    return pending;
+}
 
 __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
     __shared__ float rows[(kLmThreads / 4) * kLmStride];
@@ -259,9 +291,10 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             // evaluation compiles to a different instruction schedule
             constexpr int G = 1;
             const int gthreads = NB * kLmThreads;
-            // A level whose points fit ONE round of the grid (every level of a KITTI-sized cloud: <= 64 x 512 points) gives each lane one point for all the
-            // ~5 evaluations of the level: it is loaded once and stays in four registers, which takes one of the two dependent memory round trips (point ->
-            // texels) out of every later evaluation.
+            // A level whose points fit ONE round of the grid (<= 64 x 512 points) gives each lane one point for all the ~5 evaluations of the level: it is
+            // loaded once and stays in four registers, which takes one of the two dependent memory round trips (point -> texels) out of every later
+            // evaluation. Not every level of a KITTI-sized cloud does: the headline cloud (8750 inputs) has 41 711 and 36 103 points on levels 0 and 1, two
+            // rounds each, the second ragged (18 and 7 of the 64 workgroups); its levels 2 and 3 (21 381 and 6 249 points) fit one round.
             const bool one_round = L.n <= gthreads;
             if (one_round && cached_lvl != lvl) {
                 const int i = blk * kLmThreads + tid, ii = i < L.n ? i : 0;
@@ -338,18 +371,20 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
             }
         }
         if (NB > 1) {                                        // block partials -> every block sums them in the same fixed order
-            const int j = tid & 63, g = tid >> 6;
+            // the wave's group as a scalar, made here in every evaluation (the empty asm keeps what derives from it - block indices, guards - from being hoisted
+            // out of the evaluation loop, where it would be live across the gather, the kernel's register peak)
+            const int j = tid & 63;
+            int g = __builtin_amdgcn_readfirstlane(tid >> 6);
+            asm volatile("" : "+s"(g));
             const unsigned long long* pp = P.partial + (size_t)(S.evals & 1) * NB * 64;
             const unsigned want = P.tag0 + (unsigned)S.evals;
             double s = 0;
             bool pending = j < kTrkVals;
-            for (unsigned spins = 0; pending; ++spins) {     // all words of this lane's blocks in flight together; repeat until every tag matches
-                pending = false; s = 0;
-                for (int b2 = g; b2 < nbl; b2 += kLmThreads / 64) {
-                    const unsigned long long wv = __hip_atomic_load(&pp[(size_t)b2 * 64 + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    pending |= (unsigned)(wv >> 32) != want;
-                    s += (double)__uint_as_float((unsigned)wv);
-                }
+            // a pass loads all words of this lane's blocks back to back and waits once (lm_exchange_pass: 8 words on a grid of <= kLmMaxBlocks workgroups, 16
+            // on the double grid); a pass that finds a tag missing is repeated whole until every tag matches
+            constexpr int kWords = kLmMaxBlocks / (kLmThreads / 64);
+            for (unsigned spins = 0; pending; ++spins) {
+                pending = NB <= kLmMaxBlocks ? lm_exchange_pass<kWords>(pp, g, j, nbl, want, s) : lm_exchange_pass<2 * kWords>(pp, g, j, nbl, want, s);
                 if (pending) { if (spins > (1u << 21)) { bar_ok = 0; break; } __builtin_amdgcn_s_sleep(1); }
             }
             part[g][j] = s;
@@ -484,7 +519,6 @@ __global__ __launch_bounds__(kLmThreads) void trk_lm_kernel(TrkLmParams P) {
 // workgroups of the persistent launch for a largest level of maxn points: one per kLmThreads points, at most kLmMaxBlocks (64) on KITTI-sized clouds (the
 // exchange between them is the cost that grows), twice that once the largest level has 8+ rounds of the 64-workgroup grid (8 x 64 x 512 = 262 144 points;
 // 1920x1072, 250 k points: 513 us per frame with 64, 469 with 128, 499 with 192, 544 with 256)
-constexpr int kLmMaxBlocks = 64;
 int trk_lm_blocks(int maxn) {
     const int max_blocks = (maxn >= 8 * kLmMaxBlocks * kLmThreads ? 2 * kLmMaxBlocks : kLmMaxBlocks);
     return std::min(max_blocks, std::max(1, (maxn + kLmThreads - 1) / kLmThreads));
