@@ -363,6 +363,58 @@ int nalo_trk_last_evals(nalo_ctx* ctx, int evals[5], int n[5]);
  * not run), haveRepeated (a level was re-run)}. With the host-driven loop only the driver and haveRepeated are set. */
 int nalo_trk_get_launch_config(nalo_ctx* ctx, int cfg[9]);
 
+/* FullSystem::trackNewCoarse's loop over motion hypotheses (FullSystem.cpp:595-666) in ONE call: the tries run one after the other, each bounded by the best
+ * residuals so far, with every decision of the loop taken on the device inside one persistent launch (driver 1). Literally:
+ *   achievedRes = five NaNs; for each try i: T = tries[i], aff = aff_init, trackNewestCoarse(T, aff, coarsestLvl, minResForAbort = achievedRes), including its
+ *   tail (CoarseTracker.cpp:1239-1256); taken when ok && isfinite((float)lastRes[0]) && !(lastRes[0] >= achievedRes[0]) (:633); once a try has been taken,
+ *   after EVERY try achievedRes[l] takes over lastRes[l] where it is not finite (as float) or larger (:643-650); the loop ends at
+ *   have_one_good && achievedRes[0] < lastCoarseRMSE[0] * (double)reTrackThreshold (:653).
+ *   No good try (:658-664): T = tries[0], aff = aff_init, flow = 0, winner = -1, achievedRes stays NaN - and is still written to lastCoarseRMSE_io, as the
+ *   reference does (its next frames then never leave the loop early until one tracks).
+ * lastCoarseRMSE_io: in, the caller's FullSystem::lastCoarseRMSE (only [0] is read); out, achievedRes (:666). firstCoarseRMSE and the shell update stay with
+ * the caller. reTrackThreshold <= 0 (or NaN): the compiled-in setting_reTrackThreshold (1.5).
+ * records (optional): min(try_iterations, records_cap) entries, one per try that ran, in order. T / aff of a record: what the try wrote (:1239-1240, also when
+ * the tail then returned false); its input when it aborted on minResForAbort (:1227, abort_lvl >= 0), as nalo_trk_track leaves T_io untouched then.
+ * driver: 1 = one persistent launch; 2 = the literal loop over nalo_trk_track's host-driven form: a sharded tracker, a fixed affine parameter
+ * (affineOptModeA / B < 0), a context that lost a workgroup earlier - or in this call: the WHOLE list is then redone from the host and the context keeps to
+ * the host-driven loop, as with nalo_trk_track. Both drivers honour the same outputs contract. One call over K tries gives the bits of K nalo_trk_track calls
+ * driven by the loop above. nalo_trk_last_evals afterwards: the sums over the tries that ran.
+ * Refusals, each before anything is queued, leaving every output, lastCoarseRMSE_io and the context untouched: NALO_ERR_ARG for a NULL ctx / args / tries,
+ * n_tries < 1 or > NALO_TRK_MAX_TRIES, a non-finite entry of tries, records_cap < 0 or records == NULL with records_cap > 0, coarsestLvl or slot_new out of
+ * range; NALO_ERR_STATE / NALO_ERR_HIP where nalo_trk_track returns them (no reference, an empty slot; a failed cross-rank exchange).
+ * n_tries < 1: the reference's allFrameHistory.size() == 2 branch builds an EMPTY list and then indexes it; pass one identity instead, as
+ * upstream DSO does (nalo_trk_motion_tries with poses_valid = 0 writes it). */
+#define NALO_TRK_MAX_TRIES 64
+typedef struct nalo_trk_try_record {
+    int ok;                      /* the bool trackNewestCoarse returned */
+    int taken;                   /* this try became the winner (:633) */
+    int abort_lvl;               /* level whose residual exceeded 1.5 * achievedRes (:1227); -1: none */
+    int have_repeated, n_evals;
+    int evals[5];                /* evaluations per level of this try */
+    double lastResiduals[5], flow[3], T[12], aff[2];
+} nalo_trk_try_record;
+typedef struct nalo_trk_tries_args {
+    int slot_new, n_tries, coarsestLvl;
+    const double* tries;         /* n_tries x 12, row-major [R|t]: lastF_2_fh_tries */
+    double aff_init[2];          /* aff_last_2_l: every try starts from it (:602) */
+    double ref_aff[2];
+    float  exposures[2];         /* {ref, new} */
+    double lastCoarseRMSE_io[5];
+    double reTrackThreshold;
+    /* out */
+    double T[12], aff[2], flow[3], achievedRes[5];
+    int have_one_good, try_iterations, winner;
+    int driver;
+    nalo_trk_try_record* records; int records_cap;
+} nalo_trk_tries_args;
+int nalo_trk_track_tries(nalo_ctx* ctx, nalo_trk_tries_args* args);
+
+/* The hypothesis list of FullSystem::trackNewCoarse (FullSystem.cpp:535-572), in the reference's order: constant motion, double motion, half motion
+ * (exp(0.5 log)), zero motion, identity, then the 26 variants constant_motion * SE3(Quaterniond(1, +-d, +-d, +-d)), d = 0.02, the quaternion normalised as
+ * Sophus' constructor does (the reference's `rotDelta++` loop runs once: SURVEY App. C.8). Inputs: slast_2_sprelast and lastF_2_slast as row-major [R|t].
+ * poses_valid == 0: the single identity of :575-579. Returns the count (31 or 1), written to out as count x 12; NALO_ERR_ARG for a NULL pointer. Host code. */
+int nalo_trk_motion_tries(const double slast_2_sprelast[12], const double lastF_2_slast[12], int poses_valid, double out[31 * 12]);
+
 /* ------------------------------------------------------------------------------------------------
  * Back-end: sliding-window photometric bundle adjustment.
  * ------------------------------------------------------------------------------------------------ */

@@ -29,7 +29,7 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
     "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_frame_ingest_device", "nalo_frame_release", "nalo_dev_plane_check", "nalo_frame_attach", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask", "nalo_frame_plane",
-    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_ref_export", "nalo_trk_ref_import", "nalo_trk_ref_release", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
+    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_ref_export", "nalo_trk_ref_import", "nalo_trk_ref_release", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_track_tries", "nalo_trk_motion_tries", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
@@ -201,6 +201,27 @@ class MapRenderArgs(C.Structure):
                 ("n_line_samples", C.c_longlong)]
 
 
+TRK_MAX_TRIES = 64                                        # NALO_TRK_MAX_TRIES
+
+
+class TrkTryRecord(C.Structure):                          # nalo_trk_try_record
+    _fields_ = [("ok", C.c_int), ("taken", C.c_int), ("abort_lvl", C.c_int), ("have_repeated", C.c_int), ("n_evals", C.c_int), ("evals", C.c_int * 5),
+                ("lastResiduals", C.c_double * 5), ("flow", C.c_double * 3), ("T", C.c_double * 12), ("aff", C.c_double * 2)]
+
+
+TRY_RECORD_DTYPE = np.dtype([("ok", np.int32), ("taken", np.int32), ("abort_lvl", np.int32), ("have_repeated", np.int32), ("n_evals", np.int32), ("evals", np.int32, 5),
+                             ("lastResiduals", np.float64, 5), ("flow", np.float64, 3), ("T", np.float64, 12), ("aff", np.float64, 2)], align=True)
+assert TRY_RECORD_DTYPE.itemsize == C.sizeof(TrkTryRecord)
+
+
+class TrkTriesArgs(C.Structure):                          # nalo_trk_tries_args
+    _fields_ = [("slot_new", C.c_int), ("n_tries", C.c_int), ("coarsestLvl", C.c_int), ("tries", C.POINTER(C.c_double)), ("aff_init", C.c_double * 2),
+                ("ref_aff", C.c_double * 2), ("exposures", C.c_float * 2), ("lastCoarseRMSE_io", C.c_double * 5), ("reTrackThreshold", C.c_double),
+                ("T", C.c_double * 12), ("aff", C.c_double * 2), ("flow", C.c_double * 3), ("achievedRes", C.c_double * 5),
+                ("have_one_good", C.c_int), ("try_iterations", C.c_int), ("winner", C.c_int), ("driver", C.c_int),
+                ("records", C.POINTER(TrkTryRecord)), ("records_cap", C.c_int)]
+
+
 class Settings(C.Structure):
     """nalo_settings (include/nalo_gpu.h)"""
     _fields_ = [("forceAcceptStep", C.c_int), ("affineOptModeA", C.c_double), ("affineOptModeB", C.c_double), ("minOptIterations", C.c_int)]
@@ -230,8 +251,21 @@ def host_lib():
         L = C.CDLL(lib_path())
         _ground_argtypes(L)
         L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
+        L.nalo_trk_motion_tries.argtypes = [c_dp, c_dp, C.c_int, c_dp]
         _HOST_LIB = L
     return _HOST_LIB
+
+
+def trk_motion_tries(slast_2_sprelast, lastF_2_slast, poses_valid=True):
+    """nalo_trk_motion_tries: trackNewCoarse's hypothesis list (FullSystem.cpp:535-579) as [n, 3, 4], n = 31, or the single identity when a pose is not valid;
+    needs no device"""
+    out = np.zeros(31 * 12)
+    a, b = (np.ascontiguousarray(x, np.float64).reshape(-1) for x in (slast_2_sprelast, lastF_2_slast))
+    assert a.size == 12 and b.size == 12
+    n = host_lib().nalo_trk_motion_tries(_d(a), _d(b), int(bool(poses_valid)), _d(out))
+    if n < 0:
+        raise NaloError("nalo_trk_motion_tries: error %d" % n)
+    return out[:12 * n].reshape(n, 3, 4).copy()
 
 
 def view_look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)):
@@ -358,6 +392,7 @@ def load():
     L.nalo_trk_ref_release.argtypes = [vp, vp]
     L.nalo_trk_depth_image.argtypes = [vp, C.POINTER(DepthImageArgs)]
     L.nalo_trk_eval.argtypes = [vp, C.c_int, C.c_int, c_dp, c_dp, c_fp, C.c_float, C.c_float, C.c_int, c_dp, c_dp, c_dp]
+    L.nalo_trk_track_tries.argtypes = [vp, C.POINTER(TrkTriesArgs)]
     L.nalo_trk_track.argtypes = [vp, C.c_int, c_dp, c_dp, c_dp, c_fp, C.c_int, c_dp, c_dp, c_dp, c_ip, c_ip]
     L.nalo_ba_set_window.argtypes = [vp, C.c_int, C.POINTER(FrameState), c_dp, c_dp]
     L.nalo_ba_set_points.argtypes = [vp, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_ip]
@@ -929,6 +964,28 @@ class Context:
         self._ck(self.L.nalo_trk_track(self.h_, slot_new, _d(T), _d(aff), _d(np.asarray(ref_aff, np.float64)),
                                        _f(np.asarray(exposures, np.float32)), coarsest, _d(mr), _d(lr), _d(lf), C.byref(ok), C.byref(ne)))
         return ok.value, T.reshape(3, 4), aff, lr, lf, ne.value
+
+    def trk_track_tries(self, slot_new, tries, aff_init, ref_aff, exposures, coarsest, last_coarse_rmse, retrack_threshold=0.0, records=True, args=None):
+        """nalo_trk_track_tries: trackNewCoarse's whole hypothesis loop in one call. tries: [n, 3, 4] (or n x 12). Returns a dict: T, aff, flow, achievedRes,
+        lastCoarseRMSE (what the call left in lastCoarseRMSE_io), have_one_good, try_iterations, winner, driver, records (structured array, TRY_RECORD_DTYPE,
+        one entry per try that ran). args: a prepared TrkTriesArgs to pass as it is (tests of the refusals)."""
+        if args is None:
+            t = np.ascontiguousarray(tries, np.float64).reshape(-1, 12)
+            args = TrkTriesArgs()
+            args.slot_new, args.n_tries, args.coarsestLvl = int(slot_new), len(t), int(coarsest)
+            args.tries = _d(t)
+            args.aff_init[:] = [float(x) for x in aff_init]; args.ref_aff[:] = [float(x) for x in ref_aff]; args.exposures[:] = [float(x) for x in exposures]
+            args.lastCoarseRMSE_io[:] = [float(x) for x in np.broadcast_to(np.asarray(last_coarse_rmse, np.float64), (5,))]
+            args.reTrackThreshold = float(retrack_threshold)
+            args._keep = t
+        n = max(args.n_tries, 0)
+        rec = np.zeros(min(n, TRK_MAX_TRIES) if records else 0, TRY_RECORD_DTYPE)
+        if len(rec):
+            args.records, args.records_cap = rec.ctypes.data_as(C.POINTER(TrkTryRecord)), len(rec)
+        self._ck(self.L.nalo_trk_track_tries(self.h_, C.byref(args)))
+        return dict(T=np.array(args.T).reshape(3, 4), aff=np.array(args.aff), flow=np.array(args.flow), achievedRes=np.array(args.achievedRes),
+                    lastCoarseRMSE=np.array(args.lastCoarseRMSE_io), have_one_good=args.have_one_good, try_iterations=args.try_iterations, winner=args.winner,
+                    driver=args.driver, records=rec[:args.try_iterations].copy())
 
     def trk_last_evals(self):
         """LM evaluations per pyramid level of the last trk_track and the point-cloud sizes of the levels (nalo_trk_last_evals)"""

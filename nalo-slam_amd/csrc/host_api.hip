@@ -922,6 +922,122 @@ int nalo_trk_track(nalo_ctx* c, int slot_new, double T_io[12], double aff_io[2],
     return NALO_OK;
 }
 
+// FullSystem::trackNewCoarse's loop (FullSystem.cpp:595-666), see include/nalo_gpu.h. Everything is computed into locals and reaches the caller's struct only
+// when the call succeeds.
+namespace {
+struct TriesResult {
+    double T[12], aff[2], flow[3], ach[5];
+    int have, run, winner, driver;
+    std::vector<nalo_trk_try_record> rec;
+};
+// the literal loop over nalo_trk_track: the definition of the call, and its host-driven driver
+int tries_host_loop(nalo_ctx* c, const nalo_trk_tries_args* a, double thr, TriesResult& r) {
+    for (double& v : r.ach) v = NAN;
+    std::memcpy(r.T, a->tries, sizeof(r.T)); r.aff[0] = a->aff_init[0]; r.aff[1] = a->aff_init[1];
+    r.flow[0] = r.flow[1] = r.flow[2] = 0;
+    r.have = 0; r.run = 0; r.winner = -1; r.driver = 2; r.rec.clear();
+    int evl[5] = {};
+    for (int i = 0; i < a->n_tries; ++i) {
+        nalo_trk_try_record q = {};
+        std::memcpy(q.T, a->tries + 12 * (size_t)i, sizeof(q.T)); q.aff[0] = a->aff_init[0]; q.aff[1] = a->aff_init[1];
+        const int rc = nalo_trk_track(c, a->slot_new, q.T, q.aff, a->ref_aff, a->exposures, a->coarsestLvl, r.ach, q.lastResiduals, q.flow, &q.ok, &q.n_evals);
+        if (rc) return rc;
+        q.abort_lvl = -1;                                                           // the first level of the descent that fails :1227 is where it stopped
+        if (!q.ok) for (int l = a->coarsestLvl; l >= 0; --l) if (q.lastResiduals[l] > 1.5 * r.ach[l]) { q.abort_lvl = l; break; }
+        q.have_repeated = c->trk_cfg[8];
+        for (int l = 0; l < 5; ++l) { q.evals[l] = c->lm_evals_lvl[l]; evl[l] += q.evals[l]; }
+        q.taken = q.ok && std::isfinite((float)q.lastResiduals[0]) && !(q.lastResiduals[0] >= r.ach[0]);      // :633
+        if (q.taken) { std::memcpy(r.T, q.T, sizeof(r.T)); r.aff[0] = q.aff[0]; r.aff[1] = q.aff[1]; std::memcpy(r.flow, q.flow, sizeof(r.flow)); r.have = 1; r.winner = i; }
+        if (r.have) for (int l = 0; l < 5; ++l) if (!std::isfinite((float)r.ach[l]) || r.ach[l] > q.lastResiduals[l]) r.ach[l] = q.lastResiduals[l];   // :643-650
+        r.rec.push_back(q);
+        r.run = i + 1;
+        if (r.have && r.ach[0] < thr) break;                                        // :653
+    }
+    for (int l = 0; l < 5; ++l) c->lm_evals_lvl[l] = evl[l];
+    return NALO_OK;
+}
+}  // namespace
+
+int nalo_trk_track_tries(nalo_ctx* c, nalo_trk_tries_args* a) {
+    if (!c || !a || !a->tries) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: bad argument");
+    if (a->n_tries < 1 || a->n_tries > NALO_TRK_MAX_TRIES) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: n_tries outside 1 .. NALO_TRK_MAX_TRIES (an empty list: pass one identity)");
+    if (a->records_cap < 0 || (a->records_cap > 0 && !a->records)) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: records_cap without records");
+    if (!(a->coarsestLvl >= 0 && a->coarsestLvl < 5 && a->coarsestLvl < c->levels)) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: coarsestLvl out of range");
+    if (a->slot_new < 0 || a->slot_new >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: frame slot out of range");
+    for (size_t i = 0; i < 12 * (size_t)a->n_tries; ++i) if (!std::isfinite(a->tries[i])) return fail(c, NALO_ERR_ARG, "nalo_trk_track_tries: a try is not finite");
+    if (c->slot_ref < 0 || !c->slots[a->slot_new].valid) return fail(c, NALO_ERR_STATE, "nalo_trk_track_tries: no reference (nalo_trk_set_ref) / empty frame slot");
+    if (c->xchg_failed) return fail(c, NALO_ERR_HIP, "nalo_trk_track_tries: a cross-rank sum of this context failed earlier; rebuild on a new context");
+    // ---- accepted
+    HostTimer ht(c, "trk_track_tries");
+    const float rt = a->reTrackThreshold > 0 ? (float)a->reTrackThreshold : kReTrackThreshold;
+    const double thr = a->lastCoarseRMSE_io[0] * (double)rt;
+    TriesResult r;
+    const bool sharded = c->trk_world > 1 && c->trk_hook;
+    bool host = sharded || c->lm_host_only || c->set.affineOptModeA < 0 || c->set.affineOptModeB < 0;
+    if (!host) {
+        double sum[32];
+        std::vector<double> recs((size_t)a->n_tries * kLmRecDoubles);
+        const int rc = trk_lm_tries_launch(c, a->slot_new, a->tries, a->n_tries, a->aff_init, a->ref_aff, a->exposures, a->coarsestLvl, thr, sum, recs.data());
+        if (rc == NALO_LM_LOST_BLOCK) {                                             // as nalo_trk_track: nothing of the launch is used, the whole list is redone below
+            c->lm_host_only = true; host = true;
+            std::fprintf(stderr, "[nalo] trk_lm_kernel: a workgroup's partial never arrived; this context now drives the tracker's LM loop from the host\n");
+        } else {
+            if (rc) return rc;
+            std::memcpy(r.T, sum, sizeof(r.T)); r.aff[0] = sum[12]; r.aff[1] = sum[13];
+            for (int l = 0; l < 5; ++l) r.ach[l] = sum[14 + l];
+            for (int k = 0; k < 3; ++k) r.flow[k] = sum[19 + k];
+            r.have = (int)sum[23]; r.run = (int)sum[24]; r.winner = (int)sum[25]; r.driver = 1;
+            r.rec.resize((size_t)r.run);
+            for (int i = 0; i < r.run; ++i) {
+                const double* s = recs.data() + (size_t)i * kLmRecDoubles;
+                nalo_trk_try_record& q = r.rec[i];
+                q.ok = (int)s[0]; q.taken = (int)s[1]; q.abort_lvl = (int)s[2]; q.have_repeated = (int)s[3]; q.n_evals = (int)s[4];
+                std::memcpy(q.lastResiduals, s + 5, sizeof(q.lastResiduals)); std::memcpy(q.flow, s + 10, sizeof(q.flow));
+                std::memcpy(q.T, s + 13, sizeof(q.T)); q.aff[0] = s[25]; q.aff[1] = s[26];
+                for (int l = 0; l < 5; ++l) q.evals[l] = (int)s[27 + l];
+            }
+        }
+    }
+    if (host) { const int rc = tries_host_loop(c, a, thr, r); if (rc) return rc; }
+    std::memcpy(a->T, r.T, sizeof(r.T)); a->aff[0] = r.aff[0]; a->aff[1] = r.aff[1];
+    std::memcpy(a->flow, r.flow, sizeof(r.flow)); std::memcpy(a->achievedRes, r.ach, sizeof(r.ach));
+    std::memcpy(a->lastCoarseRMSE_io, r.ach, sizeof(r.ach));                        // :666, NaNs included
+    a->have_one_good = r.have; a->try_iterations = r.run; a->winner = r.winner; a->driver = r.driver;
+    for (int i = 0; i < r.run && i < a->records_cap; ++i) a->records[i] = r.rec[i];
+    return NALO_OK;
+}
+
+// FullSystem.cpp:535-579. Host code, no context.
+int nalo_trk_motion_tries(const double slast_2_sprelast[12], const double lastF_2_slast[12], int poses_valid, double out[31 * 12]) {
+    if (!slast_2_sprelast || !lastF_2_slast || !out) return NALO_ERR_ARG;
+    if (!poses_valid) { const SE3 I = SE3::identity(); std::memcpy(out, I.m, sizeof(I.m)); return 1; }
+    const SE3 fh_2_slast = SE3::from(slast_2_sprelast), lastF = SE3::from(lastF_2_slast), inv = fh_2_slast.inverse();
+    double xi[6];
+    se3_log(fh_2_slast, xi);
+    for (double& v : xi) v *= 0.5;
+    const SE3 constant = inv * lastF;
+    const SE3 first[5] = {constant, inv * inv * lastF, se3_exp(xi).inverse() * lastF, lastF, SE3::identity()};
+    int n = 0;
+    for (const SE3& s : first) std::memcpy(out + 12 * n++, s.m, sizeof(s.m));
+    const double d = (double)0.02f;                                                // `float rotDelta = 0.02`
+    static const signed char sg[26][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {-1, 0, 0}, {0, -1, 0}, {0, 0, -1}, {1, 1, 0}, {0, 1, 1}, {1, 0, 1}, {-1, 1, 0}, {0, -1, 1}, {-1, 0, 1},
+                                          {1, -1, 0}, {0, 1, -1}, {1, 0, -1}, {-1, -1, 0}, {0, -1, -1}, {-1, 0, -1}, {-1, -1, -1}, {-1, -1, 1}, {-1, 1, -1}, {-1, 1, 1},
+                                          {1, -1, -1}, {1, -1, 1}, {1, 1, -1}, {1, 1, 1}};
+    for (const auto& s3 : sg) {
+        double q[4] = {1.0, s3[0] * d, s3[1] * d, s3[2] * d};                       // (w, x, y, z); SO3's constructor normalises
+        const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (double& v : q) v /= qn;
+        const double w = q[0], x = q[1], y = q[2], z = q[3];
+        SE3 Rq = SE3::identity();
+        const double Rm[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                              2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Rq.m[i * 4 + j] = Rm[i * 3 + j];
+        const SE3 t = constant * Rq;
+        std::memcpy(out + 12 * n++, t.m, sizeof(t.m));
+    }
+    return n;
+}
+
 // ------------------------------------------------------------------------------------------------ immature points
 int nalo_imm_create(nalo_ctx* c, int slot_host, int n, const int* u, const int* v, float* color, float* weights, float* gradH, float* energyTH) {
     if (!c || n < 0 || (n > 0 && (!u || !v || !color || !weights || !gradH || !energyTH))) return fail(c, NALO_ERR_ARG, "nalo_imm_create: bad argument");

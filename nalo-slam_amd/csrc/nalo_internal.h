@@ -140,6 +140,7 @@ struct nalo_ctx {
     unsigned long long trk_seq = 0;
     nalo::DevBuf<unsigned long long> lm_partial;   // persistent LM kernel: [2][blocks][64] block partials {fp32, tag}
     unsigned long long lm_launches = 0;
+    nalo::HostBuf<double> lm_tries_host;     // nalo_trk_track_tries, host-mapped: summary (32, seq at [31]) | NALO_TRK_MAX_TRIES records | the list of tries
     int lm_evals_lvl[5] = {};                // LM evaluations per pyramid level of the last nalo_trk_track (nalo_trk_last_evals)
     int trk_cfg[9] = {};                     // launch of the last nalo_trk_track (nalo_trk_get_launch_config)
     int trk_rank = 0, trk_world = 1; nalo_allreduce_fn trk_hook = nullptr; void* trk_hook_user = nullptr; bool trk_hook_stream_ordered = false;   // nalo_trk_set_shard
@@ -214,10 +215,9 @@ inline int fail(nalo_ctx* c, int code, const std::string& msg) { if (c) c->err =
 
 // Wait for a kernel to publish `seq` into host-mapped memory (system-scope release on the device side). Spinning on the
 // flag costs a few microseconds; hipStreamSynchronize costs tens. Every 2^20 spins the stream is queried for a fault and the wall clock is
-// checked: after 10 s without the flag the call fails with NALO_ERR_HIP (a faulted kernel or a collective
+// checked: after timeout_s (10 s; a launch that legitimately runs several of today's passes its multiple) without the flag the call fails with NALO_ERR_HIP (a faulted kernel or a collective
 // that never completes must not stall the caller for minutes).
-inline bool poll_flag(nalo_ctx* c, volatile double* flag, double seq) {
-    constexpr double timeout_s = 10.0;
+inline bool poll_flag(nalo_ctx* c, volatile double* flag, double seq, double timeout_s = 10.0) {
     std::chrono::steady_clock::time_point t0;
     bool timing = false;
     for (unsigned long long spins = 0;; ++spins) {
@@ -503,6 +503,10 @@ int ingest_dev_launch(nalo_ctx* c, hipStream_t st, const nalo_dev_plane& img, co
 int attach_launch(nalo_ctx* c, hipStream_t st, const nalo_dev_plane* mask, const nalo_dev_plane* colour, int colour_is_rgb, float* out_mask, uint8_t* out_bgr);
 // kernels_trk_lm.hip: workgroups of trk_lm_kernel for a largest level of maxn points; the whole pyramid descent of nalo_trk_track in one persistent launch
 int trk_lm_blocks(int maxn);
+// nalo_trk_track_tries in one persistent launch (trk_lm_tries_kernel): summary[32] and run x kLmRecDoubles records, see kernels_trk_lm.hip
+constexpr int kLmRecDoubles = 32;            // per try: ok taken abort_lvl have_repeated n_evals | lastRes(5) flow(3) T(12) aff(2) | evals per level(5)
+int trk_lm_tries_launch(nalo_ctx* c, int slot_new, const double* tries, int n_tries, const double aff_init[2], const double ref_aff[2], const float exposures[2],
+                        int coarsest, double thr, double summary[32], double* records);
 int trk_lm_launch(nalo_ctx* c, int slot_new, const double T0[12], const double aff0[2], const double ref_aff[2], const float exposures[2], int coarsest, int stop_lvl, const double* minRes, double out24[32]);
 // kernels_depth_image.hip: debugPlotIDepthMap on c->stream. scr: kDepthImageScratchWords words (zeroed here; the results are its last 8: n_positive, min_new, max_new,
 // min_used, max_used, the rewritten minmax pair), bgr: 3 w h bytes. Nothing is painted when the map holds no positive value (n_positive = 0).

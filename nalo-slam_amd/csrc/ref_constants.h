@@ -53,6 +53,7 @@
     X(float, kFrameEnergyTHFacMedian, "setting_frameEnergyTHFacMedian", 1.5f)                        \
     X(float, kOverallEnergyTHWeight, "setting_overallEnergyTHWeight", 1.0f)                          \
     X(float, kCoarseCutoffTH, "setting_coarseCutoffTH", 20.0f)                                       \
+    X(float, kReTrackThreshold, "setting_reTrackThreshold", 1.5f)                                    \
     X(float, kMinGradHistCut, "setting_minGradHistCut", 0.5f)                                        \
     X(float, kMinGradHistAdd, "setting_minGradHistAdd", 7.0f)                                        \
     X(float, kGradDownweightPerLevel, "setting_gradDownweightPerLevel", 0.75f)                       \
