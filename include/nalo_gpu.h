@@ -133,7 +133,8 @@ int nalo_frame_upload_raw_async(nalo_ctx* ctx, int slot, const void* raw, int by
  * attach mask and colour to a slot whose pyramid exists already.
  * nalo_dev_plane            one plane by byte strides: element (x, y, ch) is at ptr + y * stride_y + x * stride_x + ch * stride_c. A pitched region of a larger
  *                           tensor, an x-strided view, interleaved (HWC) and planar (CHW) colour are all described this way. No byte outside the described
- *                           elements is read.
+ *                           elements is read. A NALO_DT_F32 DEPTH plane whose w x h differ from the context's size is legal in nalo_tsdf_integrate_depth: its
+ *                           intrinsics come with that call.
  * nalo_dev_plane_check      validates a descriptor and launches nothing. NALO_ERR_ARG for: a null descriptor or pointer; a pointer that hipPointerGetAttributes does
  *                           not report as device memory of the context's GPU (host, pinned host, managed and other devices' memory); a dtype outside NALO_DT_*;
  *                           channels other than 1 or 3; w or h < 1; a negative stride; a pointer or stride that is no multiple of the element size; stride_x
@@ -1114,6 +1115,7 @@ int nalo_init_depth_image(nalo_ctx* ctx, nalo_init_plot_args* args);
  *   Not archived: points removed by nalo_ba_marginalize_points (host flags). nalo_ba_snapshot / nalo_ba_restore do not include the archive (nor the graph of
  *   nalo_map_graph_enable).
  * nalo_map_reset      empties the archive (and the dense archive of nalo_map_dense_enable) and keeps its chunks; empties the graph of nalo_map_graph_enable.
+ *                     It does not touch the TSDF volume (nalo_tsdf_reset does that).
  * nalo_map_counts     counts = {pointHessiansMarginalized.size(), pointHessiansOut.size()} of the frame: the addends of flagFramesForMarginalization's
  *                     `out` (FullSystemMarginalize.cpp:77). NALO_ERR_ARG for a frame_id the archive has never seen.
  * nalo_map_get_frame  the frame's records: its status-2 records in archive order, then its status-3 records. *n = their number; cap < *n: NALO_ERR_ARG
@@ -1468,8 +1470,89 @@ int nalo_map_dense_world_points(nalo_ctx* ctx, int frame_id, const double camToW
 int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * tsdf=1: the dense map fused into a TSDF volume on the device. The reference constructs a cpu_tsdf::TSDFVolumeOctree (FullSystem.cpp:192-198), saves a point
+ * file "for tsdf" (SampleOutputWrapper.h:150-176, nalo_map_dense_world_points here) and leaves the fusion to a third-party tool it neither vendors nor pins. This
+ * section is a DEFINED operation instead: a projective integration of one depth image into a dense voxel volume that lives in the context. No colour
+ * (setIntegrateColor(false)), no octree, no de-integration; nalo_ba_snapshot / nalo_ba_restore do not include the volume.
+ *
+ * nalo_tsdf_create   origin: world position of the CORNER of voxel (0,0,0); dims = {nx, ny, nz}. Storage: two contiguous F32 arrays [nz][ny][nx], x fastest;
+ *                    tsdf starts at 1.0f, weight at 0.0f. NALO_ERR_ARG: a dimension outside [1, 2048], nx ny nz above 2^29, voxel_size / trunc / max_weight not
+ *                    finite or <= 0, a non-finite origin. A failed allocation (NALO_ERR_HIP) leaves the context, and a volume it holds, as they were. A second
+ *                    create replaces the volume (it waits for the main stream first).
+ * nalo_tsdf_reset    the initial values again, the memory stays. nalo_tsdf_destroy frees the volume (no volume: NALO_OK); nalo_destroy frees it too.
+ *                    nalo_map_reset does NOT touch the volume. Every other call of this section without a volume: NALO_ERR_STATE.
+ *
+ * nalo_tsdf_integrate_depth   everything in float, no FMA contraction, each operation rounded once:
+ *     M = worldToCam: the 3x3 block of camToWorld transposed and -(R^T t), each row's three products summed left to right, in double; every entry then rounded to float.
+ *     voxel (i, j, k):  px = origin[0] + ((float)i + 0.5f) * voxel_size, py and pz alike;  xc = ((M0 px + M1 py) + M2 pz) + M3, yc and zc alike (rows of M);
+ *     uf = ((fx * (xc / zc)) + cx) + 0.5f, vf alike. Visible iff zc > 0 && uf >= 0 && uf < w && vf >= 0 && vf < h, compared in float BEFORE any conversion
+ *     (a NaN fails); the pixel is ((int)uf, (int)vf). D = depth[pv][pu] is usable iff D >= min_depth && D <= max_depth. sdf = D - zc; skipped when sdf < -trunc.
+ *     Otherwise, with t0 = tsdf, w0 = weight, d = fminf(1.0f, sdf / trunc):   tsdf = (t0 * w0 + d) / (w0 + 1.0f);   weight = fminf(w0 + 1.0f, max_weight).
+ *   One lane owns a voxel for the whole call: no float atomic, the same bytes on every run. The kernel visits only the box of nalo_tsdf_frustum_box; a voxel
+ *   the definition updates is always inside it (the box is conservative), so the result equals the definition evaluated on every voxel.
+ *   depth: F32, one channel, w x h given by the plane - it need NOT be the context's size, K = {fx, fy, cx, cy} comes with the call for that size - any strides
+ *   nalo_dev_plane_check accepts; no byte outside the described elements is read.
+ *   Stream order as nalo_frame_ingest_device: the main stream waits on the device for what producer_stream has queued (skipped for the context's own stream), and
+ *   an event is recorded behind the kernel, the last one that reads the plane; nalo_tsdf_release(ctx, stream) lets `stream` wait for it on the device (nothing to wait
+ *   for: NALO_OK). With the volume allocated the call makes no host wait.
+ *   NALO_ERR_ARG: a plane nalo_dev_plane_check refuses (host memory among them), a dtype other than F32, three channels, a non-finite entry of K or camToWorld,
+ *   min_depth or max_depth not finite, min_depth > max_depth. A refused call queues nothing and leaves volume and context as they were.
+ * nalo_tsdf_integrate_frame   DEFINED as nalo_tsdf_integrate_depth on the plane D[v][u] = 1.0f / idepth of the LAST record at (u, v) of the frame's dense list in
+ *   append order (nalo_map_dense_get's order), 0 where there is none; the plane is context-owned scratch of the context's w x h. A second nalo_dense_update_map of
+ *   the same frame appended a second set of runs: the last record is settled by an integer key (the record's position in the list), never by arrival order.
+ *   NALO_ERR_ARG for a frame_id the dense archive has never seen; NALO_ERR_STATE without the dense archive (nalo_map_dense_enable) or on a sharded window.
+ * nalo_tsdf_last     waits once. The last integration's visited box (lo inclusive, hi exclusive, voxel indices; all zero when the box was empty), the voxels
+ *                    visited (the box's volume) and the voxels updated (an integer sum: a wave reduction, then one atomic per workgroup). NALO_ERR_STATE
+ *                    before the first integration into this volume.
+ * nalo_tsdf_get / nalo_tsdf_set   read-back / injection of the sub-block [lo, lo + size) as [size[2]][size[1]][size[0]] floats, x fastest; either array may be
+ *                    NULL (not both). nalo_tsdf_set is to this volume what nalo_trk_set_depth is to the tracker. NALO_ERR_ARG for a block that is empty or leaves the
+ *                    grid. Synchronous.
+ * nalo_tsdf_view     host code only, launches nothing: the pointers of both arrays, the dimensions and the producing stream (nalo_stream), under "Lifetime of
+ *                    a view" above: good until nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy; the calls that rewrite what it names are nalo_tsdf_reset,
+ *                    nalo_tsdf_set and the two integrations.
+ * nalo_tsdf_surface_points   over the sub-box [lo, lo + size) (use_box == 0: the whole grid): for voxel v in ascending (k, j, i) and axis a = x, y, z, with n the
+ *                    neighbour of v along +a INSIDE the sub-box, (v, a, n) is a crossing iff both weights are >= min_weight and (t0 < 0 && t1 >= 0) || (t0 >= 0 &&
+ *                    t1 < 0) (a NaN fails both clauses); its point is centre(v) + e_a * (voxel_size * (t0 / (t0 - t1))), centre(v) the px, py, pz above.
+ *                    Output in that order: a count pass, a scan, a write pass; no atomic append. n_needed is always set; cap < n_needed: NALO_ERR_ARG and nothing
+ *                    is written. One wait.
+ * nalo_tsdf_frustum_box   host only, needs no context: the culling box. In double: the world box of the camera apex (camToWorld's t) and the four far corners, the
+ *                    rays through (uf, vf) in {0, w} x {0, h}, i.e. x = ((uf - 0.5) - cx) / fx, y = ((vf - 0.5) - cy) / fy, at z = max_depth + trunc. Per axis
+ *                    lo = floor((min - origin) / voxel_size - 0.5) - 1 and hi = ceil((max - origin) / voxel_size - 0.5) + 2, clipped to [0, dim]: the voxels whose
+ *                    centres lie in the box, padded by one voxel on every side (hi exclusive). An empty box on any axis gives all zeros. NALO_ERR_ARG for a
+ *                    descriptor nalo_tsdf_create refuses, w or h < 1, a non-finite K, pose or max_depth.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
+typedef struct nalo_tsdf_integrate_args {
+    nalo_dev_plane depth;                   /* F32, one channel, w x h of its own */
+    float K[4];                             /* fx, fy, cx, cy for that size */
+    double camToWorld[12];
+    float min_depth, max_depth;
+    void* producer_stream;                  /* hipStream_t whose queued work produces the plane; NULL = the null stream */
+} nalo_tsdf_integrate_args;
+typedef struct nalo_tsdf_stats { int lo[3], hi[3]; long long visited, updated; } nalo_tsdf_stats;
+typedef struct nalo_tsdf_volume_view { float* tsdf; float* weight; int dims[3]; void* stream; } nalo_tsdf_volume_view;
+typedef struct nalo_tsdf_surface_args {
+    int use_box; int lo[3], size[3];        /* use_box == 0: the whole grid */
+    float min_weight;
+    long long cap; float* xyz;              /* host, [cap][3] */
+    long long n, n_needed;                  /* out: points written; crossings found */
+} nalo_tsdf_surface_args;
+int nalo_tsdf_create(nalo_ctx* ctx, const nalo_tsdf_desc* desc);
+int nalo_tsdf_reset(nalo_ctx* ctx);
+int nalo_tsdf_destroy(nalo_ctx* ctx);
+int nalo_tsdf_integrate_depth(nalo_ctx* ctx, const nalo_tsdf_integrate_args* args);
+int nalo_tsdf_release(nalo_ctx* ctx, void* stream);
+int nalo_tsdf_integrate_frame(nalo_ctx* ctx, int frame_id, const double camToWorld[12], const float K[4], float min_depth, float max_depth);
+int nalo_tsdf_last(nalo_ctx* ctx, nalo_tsdf_stats* stats);
+int nalo_tsdf_get(nalo_ctx* ctx, const int lo[3], const int size[3], float* tsdf, float* weight);
+int nalo_tsdf_set(nalo_ctx* ctx, const int lo[3], const int size[3], const float* tsdf, const float* weight);
+int nalo_tsdf_view(nalo_ctx* ctx, nalo_tsdf_volume_view* out);
+int nalo_tsdf_surface_points(nalo_ctx* ctx, nalo_tsdf_surface_args* args);
+int nalo_tsdf_frustum_box(const nalo_tsdf_desc* desc, int w, int h, const float K[4], const double camToWorld[12], float max_depth, int lo[3], int hi[3]);   /* host only */
+
+/* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -40,6 +40,7 @@ EXPORTS = [
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
     "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
+    "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -160,6 +161,27 @@ DENSE_POINT_DTYPE = np.dtype([("u", np.uint16), ("v", np.uint16), ("idepth", np.
 assert DENSE_RUN_DTYPE.itemsize == 32 and DENSE_POINT_DTYPE.itemsize == 16
 
 
+class TsdfDesc(C.Structure):                              # nalo_tsdf_desc; tsdf_desc() builds one
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("dims", C.c_int * 3), ("trunc", C.c_float), ("max_weight", C.c_float)]
+
+
+class TsdfIntegrateArgs(C.Structure):                     # nalo_tsdf_integrate_args
+    _fields_ = [("depth", DevPlane), ("K", C.c_float * 4), ("camToWorld", C.c_double * 12), ("min_depth", C.c_float), ("max_depth", C.c_float), ("producer_stream", C.c_void_p)]
+
+
+class TsdfStats(C.Structure):                             # nalo_tsdf_stats
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("visited", C.c_longlong), ("updated", C.c_longlong)]
+
+
+class TsdfVolumeView(C.Structure):                        # nalo_tsdf_volume_view
+    _fields_ = [("tsdf", C.c_void_p), ("weight", C.c_void_p), ("dims", C.c_int * 3), ("stream", C.c_void_p)]
+
+
+class TsdfSurfaceArgs(C.Structure):                       # nalo_tsdf_surface_args
+    _fields_ = [("use_box", C.c_int), ("lo", C.c_int * 3), ("size", C.c_int * 3), ("min_weight", C.c_float), ("cap", C.c_longlong), ("xyz", c_fp),
+                ("n", C.c_longlong), ("n_needed", C.c_longlong)]
+
+
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
@@ -252,6 +274,7 @@ def host_lib():
         _ground_argtypes(L)
         L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
         L.nalo_trk_motion_tries.argtypes = [c_dp, c_dp, C.c_int, c_dp]
+        L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
         _HOST_LIB = L
     return _HOST_LIB
 
@@ -276,6 +299,27 @@ def view_look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)):
     if host_lib().nalo_view_look_at(e.ctypes.data_as(c_dp), t.ctypes.data_as(c_dp), u.ctypes.data_as(c_dp), out.ctypes.data_as(c_dp)) != 0:
         raise NaloError("nalo_view_look_at: degenerate view (up parallel to the viewing direction, eye == target, or a value that is not finite)")
     return out.reshape(3, 4)
+
+
+def tsdf_desc(origin, voxel_size, dims, trunc, max_weight):
+    """nalo_tsdf_desc (a TsdfDesc): origin = world position of the corner of voxel (0, 0, 0), dims = (nx, ny, nz)"""
+    d = TsdfDesc()
+    d.origin[:] = [float(v) for v in origin]
+    d.dims[:] = [int(v) for v in dims]
+    d.voxel_size, d.trunc, d.max_weight = float(voxel_size), float(trunc), float(max_weight)
+    return d
+
+
+def tsdf_frustum_box(desc, w, h, K, cam_to_world, max_depth):
+    """nalo_tsdf_frustum_box: the culling box (lo, hi) of an integration, hi exclusive, all zeros when it is empty; needs no device"""
+    Kf = np.ascontiguousarray(K, np.float32).reshape(-1)
+    m = np.ascontiguousarray(cam_to_world, np.float64).reshape(-1)
+    assert Kf.size == 4 and m.size == 12
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    rc = host_lib().nalo_tsdf_frustum_box(C.byref(desc), int(w), int(h), _f(Kf), _d(m), C.c_float(max_depth), _i(lo), _i(hi))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_frustum_box: bad argument (%d)" % rc)
+    return lo, hi
 
 
 def _ground_argtypes(L):
@@ -438,6 +482,18 @@ def load():
     L.nalo_map_dense_get.argtypes = [vp, C.c_int, vp, C.c_int, c_ip]
     L.nalo_map_dense_world_points.argtypes = [vp, C.c_int, c_dp, c_dp, C.c_int, c_ip]
     L.nalo_map_dense_cloud.argtypes = [vp, C.POINTER(MapDenseCloudArgs)]
+    L.nalo_tsdf_create.argtypes = [vp, C.POINTER(TsdfDesc)]
+    L.nalo_tsdf_reset.argtypes = [vp]
+    L.nalo_tsdf_destroy.argtypes = [vp]
+    L.nalo_tsdf_integrate_depth.argtypes = [vp, C.POINTER(TsdfIntegrateArgs)]
+    L.nalo_tsdf_release.argtypes = [vp, vp]
+    L.nalo_tsdf_integrate_frame.argtypes = [vp, C.c_int, c_dp, c_fp, C.c_float, C.c_float]
+    L.nalo_tsdf_last.argtypes = [vp, C.POINTER(TsdfStats)]
+    L.nalo_tsdf_get.argtypes = [vp, c_ip, c_ip, c_fp, c_fp]
+    L.nalo_tsdf_set.argtypes = [vp, c_ip, c_ip, c_fp, c_fp]
+    L.nalo_tsdf_view.argtypes = [vp, C.POINTER(TsdfVolumeView)]
+    L.nalo_tsdf_surface_points.argtypes = [vp, C.POINTER(TsdfSurfaceArgs)]
+    L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -1395,6 +1451,107 @@ class Context:
         if n.value:
             self._ck(self.L.nalo_map_dense_world_points(self.h_, int(frame_id), _d(m), _d(xyz), n.value, C.byref(n)))
         return xyz
+
+    # ---- the TSDF volume (nalo_tsdf_*)
+    def tsdf_create(self, origin, voxel_size, dims, trunc, max_weight):
+        """nalo_tsdf_create: a dense volume [nz][ny][nx] (tsdf 1.0, weight 0.0) in this context; a second call replaces it"""
+        d = tsdf_desc(origin, voxel_size, dims, trunc, max_weight)
+        self._ck(self.L.nalo_tsdf_create(self.h_, C.byref(d)))
+        self.tsdf_dims = tuple(int(v) for v in dims)
+
+    def tsdf_reset(self):
+        self._ck(self.L.nalo_tsdf_reset(self.h_))
+
+    def tsdf_destroy(self):
+        self._ck(self.L.nalo_tsdf_destroy(self.h_))
+
+    def tsdf_integrate_depth(self, depth, K, cam_to_world, min_depth, max_depth, stream=None, release=True):
+        """nalo_tsdf_integrate_depth: depth is a 2-D float32 device array (anything with __cuda_array_interface__, or a DevPlane), read where it lies through its
+        strides; K = (fx, fy, cx, cy) for ITS size. stream / release as frame_ingest: the producing hipStream_t (None: torch's current stream of a tensor, a
+        DeviceView's own, else the null stream), and whether that stream waits on the device until the plane has been read. Returns without waiting."""
+        a = TsdfIntegrateArgs()
+        a.depth = depth if isinstance(depth, DevPlane) else dev_plane(depth)
+        if stream is None:
+            stream = 0
+            torch = sys.modules.get("torch")
+            if isinstance(depth, DeviceView):
+                stream = depth.stream
+            elif torch is not None and isinstance(depth, torch.Tensor):
+                stream = torch.cuda.current_stream(depth.device).cuda_stream
+        a.K[:] = [float(v) for v in K]
+        a.camToWorld[:] = [float(v) for v in np.asarray(cam_to_world, np.float64).reshape(-1)]
+        a.min_depth, a.max_depth, a.producer_stream = float(min_depth), float(max_depth), stream or None
+        self._ck(self.L.nalo_tsdf_integrate_depth(self.h_, C.byref(a)))
+        if release:
+            self.tsdf_release(stream)
+
+    def tsdf_release(self, stream):
+        """nalo_tsdf_release: `stream` (a hipStream_t as an int, 0 / None the null stream) waits on the device until the last integration has read its plane"""
+        self._ck(self.L.nalo_tsdf_release(self.h_, stream or None))
+
+    def tsdf_integrate_frame(self, frame_id, cam_to_world, K, min_depth, max_depth):
+        """nalo_tsdf_integrate_frame: the frame's dense list (nalo_dense_update_map) as a depth plane, integrated with the pose given here"""
+        m = np.ascontiguousarray(cam_to_world, np.float64).reshape(-1)
+        Kf = np.ascontiguousarray(K, np.float32).reshape(-1)
+        assert m.size == 12 and Kf.size == 4
+        self._ck(self.L.nalo_tsdf_integrate_frame(self.h_, int(frame_id), _d(m), _f(Kf), C.c_float(min_depth), C.c_float(max_depth)))
+
+    def tsdf_last(self):
+        """nalo_tsdf_last -> dict(lo, hi, visited, updated) of the last integration (hi exclusive); waits"""
+        st = TsdfStats()
+        self._ck(self.L.nalo_tsdf_last(self.h_, C.byref(st)))
+        return dict(lo=tuple(st.lo), hi=tuple(st.hi), visited=int(st.visited), updated=int(st.updated))
+
+    def tsdf_get(self, lo=None, size=None):
+        """nalo_tsdf_get -> (tsdf, weight) of the sub-block [lo, lo + size) as float32 [sz][sy][sx]; the whole grid by default"""
+        lo_a = np.zeros(3, np.int32) if lo is None else np.ascontiguousarray(lo, np.int32)
+        size_a = np.asarray(self.tsdf_dims, np.int32) if size is None else np.ascontiguousarray(size, np.int32)
+        shape = tuple(max(int(v), 0) for v in size_a[::-1])
+        t, w = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        self._ck(self.L.nalo_tsdf_get(self.h_, _i(lo_a), _i(size_a), _f(t), _f(w)))
+        return t, w
+
+    def tsdf_set(self, lo, tsdf=None, weight=None):
+        """nalo_tsdf_set: float32 blocks [sz][sy][sx] written at lo, bit for bit; either may be None"""
+        t = None if tsdf is None else np.ascontiguousarray(tsdf, np.float32)
+        w = None if weight is None else np.ascontiguousarray(weight, np.float32)
+        ref = t if t is not None else w
+        if ref is None or ref.ndim != 3 or (t is not None and w is not None and t.shape != w.shape):
+            raise NaloError("tsdf_set: tsdf and / or weight as [sz][sy][sx] blocks of one shape")
+        lo_a, size_a = np.ascontiguousarray(lo, np.int32), np.asarray(ref.shape[::-1], np.int32)
+        self._ck(self.L.nalo_tsdf_set(self.h_, _i(lo_a), _i(size_a), _f(t), _f(w)))
+
+    def tsdf_view(self):
+        """nalo_tsdf_view -> (tsdf, weight) as DeviceViews of shape [nz, ny, nx]: torch.as_tensor(view, device="cuda") is a zero-copy tensor. Launches nothing."""
+        v = TsdfVolumeView()
+        self._ck(self.L.nalo_tsdf_view(self.h_, C.byref(v)))
+        shape = (v.dims[2], v.dims[1], v.dims[0])
+        return DeviceView(v.tsdf, shape, "<f4", None, v.stream, self), DeviceView(v.weight, shape, "<f4", None, v.stream, self)
+
+    def tsdf_surface_points(self, min_weight, lo=None, size=None, cap=None):
+        """nalo_tsdf_surface_points -> float32 [n][3], in (k, j, i, axis) order, over the sub-box [lo, lo + size) or the whole grid. With cap (room for that
+        many points, e.g. the count of the last call plus a margin) it is ONE library call and one wait, refused with NaloError when the surface has more points;
+        without it the library is called twice, first with cap = 0 for n_needed (count and scan run twice, two waits). self.tsdf_surface_needed holds n_needed
+        after either, a refusal included"""
+        a = TsdfSurfaceArgs()
+        if lo is not None:
+            a.use_box = 1
+            a.lo[:] = [int(v) for v in lo]
+            a.size[:] = [int(v) for v in size]
+        a.min_weight = float(min_weight)
+        if cap is None:
+            rc = self.L.nalo_tsdf_surface_points(self.h_, C.byref(a))            # cap = 0: answers n_needed (and is the whole call without a crossing)
+            self.tsdf_surface_needed = int(a.n_needed)
+            if a.n_needed == 0:
+                self._ck(rc)
+                return np.zeros((0, 3), np.float32)
+            cap = int(a.n_needed)
+        xyz = np.zeros((max(int(cap), 0), 3), np.float32)
+        a.cap, a.xyz = int(cap), _f(xyz)
+        rc = self.L.nalo_tsdf_surface_points(self.h_, C.byref(a))
+        self.tsdf_surface_needed = int(a.n_needed)
+        self._ck(rc)
+        return xyz[:int(a.n)].copy()
 
     def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
         """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes

@@ -195,6 +195,22 @@ static int map_dense_send(nalo_ctx* c, DenseArchive& m, const DenseFrame& f, Map
     return NALO_OK;
 }
 
+int map_dense_segments(nalo_ctx* c, const char* who, int frame_id, std::vector<MapSeg>* segs, int* total) {
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, std::string(who) + ": the dense archive is not enabled (nalo_map_dense_enable)");
+    MapWindowView V;
+    if (c->ba && ba_map_view(c, -1, &V) == NALO_OK && V.sharded) return fail(c, NALO_ERR_STATE, std::string(who) + ": the window is sharded (a rank holds only its own points)");
+    DenseFrame* f = nullptr;
+    { int rc = map_dense_frame(c, who, frame_id, &f); if (rc) return rc; }
+    // host code only: the archive's own staging table (map_dense_send) belongs to the calls that wait before they return
+    const DenseArchive& m = *c->dmap;
+    segs->clear();
+    long long start = 0;
+    for (const MapRun& r : f->runs) { segs->push_back(MapSeg{m.chunks[(size_t)(r.off / m.chunk)].p + r.off % m.chunk, (int)start, r.n, 0, 0}); start += r.n; }
+    if (start > INT32_MAX) return fail(c, NALO_ERR_UNSUPPORTED, std::string(who) + ": the frame's dense list has more than 2^31 - 1 points");
+    *total = (int)start;
+    return NALO_OK;
+}
+
 // ---- the keyframe graph: EnergyFunctional::connectivityMap (EnergyFunctional.cpp:423, 453-458, 493, 628-634). The host keeps the keys and [1]; [0] is counted
 // from the resident slots when the graph is read (ba_graph_view)
 static uint64_t graph_key(int host_id, int target_id) { return ((uint64_t)host_id << 32) + (uint64_t)target_id; }

@@ -1,0 +1,67 @@
+// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, and the culling box nalo_tsdf_frustum_box. Plain C++ with no
+// device call, built without FMA contraction: every line below is the operation order the header defines, in double.
+#include <cmath>
+
+#include "tsdf_host.h"
+
+namespace nalo {
+
+const char* tsdf_desc_refusal(const nalo_tsdf_desc* d) {
+    if (!d) return "null descriptor";
+    long long n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (d->dims[a] < 1 || d->dims[a] > 2048) return "a dimension outside [1, 2048]";
+        n *= d->dims[a];
+        if (!std::isfinite(d->origin[a])) return "origin is not finite";
+    }
+    if (n > (1LL << 29)) return "more than 2^29 voxels";
+    if (!std::isfinite(d->voxel_size) || d->voxel_size <= 0) return "voxel_size is not finite or <= 0";
+    if (!std::isfinite(d->trunc) || d->trunc <= 0) return "trunc is not finite or <= 0";
+    if (!std::isfinite(d->max_weight) || d->max_weight <= 0) return "max_weight is not finite or <= 0";
+    return nullptr;
+}
+
+bool tsdf_world_to_cam(const double c[12], float M[12]) {
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(c[i])) return false;
+    for (int r = 0; r < 3; ++r) {
+        // row r of R^T is column r of R
+        const double a = c[0 + r], b = c[4 + r], e = c[8 + r];
+        M[4 * r + 0] = (float)a; M[4 * r + 1] = (float)b; M[4 * r + 2] = (float)e;
+        M[4 * r + 3] = (float)(-((a * c[3] + b * c[7]) + e * c[11]));
+    }
+    return true;
+}
+
+}  // namespace nalo
+
+extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, const float K[4], const double c[12], float max_depth, int lo[3], int hi[3]) {
+    if (!K || !c || !lo || !hi || w < 1 || h < 1 || nalo::tsdf_desc_refusal(d) || !std::isfinite(max_depth)) return NALO_ERR_ARG;
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(K[i])) return NALO_ERR_ARG;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(c[i])) return NALO_ERR_ARG;
+    const double z = (double)max_depth + (double)d->trunc;
+    double mn[3] = {c[3], c[7], c[11]}, mx[3] = {c[3], c[7], c[11]};          // the apex
+    bool bad[3] = {false, false, false};
+    for (int cv = 0; cv < 2; ++cv)
+        for (int cu = 0; cu < 2; ++cu) {
+            const double uf = cu ? (double)w : 0.0, vf = cv ? (double)h : 0.0;
+            const double X = (((uf - 0.5) - (double)K[2]) / (double)K[0]) * z, Y = (((vf - 0.5) - (double)K[3]) / (double)K[1]) * z;
+            for (int a = 0; a < 3; ++a) {
+                const double p = ((c[4 * a] * X + c[4 * a + 1] * Y) + c[4 * a + 2] * z) + c[4 * a + 3];
+                if (std::isnan(p)) bad[a] = true;                                // inf - inf at an absurd pose: the axis takes the whole grid below
+                if (p < mn[a]) mn[a] = p;
+                if (p > mx[a]) mx[a] = p;
+            }
+        }
+    bool empty = false;
+    for (int a = 0; a < 3; ++a) {
+        if (bad[a]) { lo[a] = 0; hi[a] = d->dims[a]; continue; }
+        const double l = std::floor((mn[a] - (double)d->origin[a]) / (double)d->voxel_size - 0.5) - 1.0;
+        const double u = std::ceil((mx[a] - (double)d->origin[a]) / (double)d->voxel_size - 0.5) + 2.0;
+        const int n = d->dims[a];
+        lo[a] = !(l > 0) ? 0 : l > n ? n : (int)l;                             // compared as doubles before any conversion; a NaN gives the grid's own bound
+        hi[a] = !(u < n) ? n : u < 0 ? 0 : (int)u;
+        if (lo[a] >= hi[a]) empty = true;
+    }
+    if (empty) for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
+    return NALO_OK;
+}

@@ -1,0 +1,251 @@
+// The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
+// arithmetic lives in kernels_tsdf.hip (device) and host_tsdf.cpp (worldToCam, the culling box).
+#include <algorithm>
+#include <cmath>
+
+#include "nalo_internal.h"
+#include "tsdf_host.h"
+
+namespace nalo {
+
+struct TsdfVolume {
+    nalo_tsdf_desc d{};
+    size_t n = 0;
+    DevBuf<float> tsdf, weight;
+    Event ev_read;                                   // behind the last kernel that read a caller's depth plane (nalo_tsdf_release)
+    bool read_pending = false;
+    DevBuf<unsigned long long> updated; HostBuf<unsigned long long> updated_h;
+    nalo_tsdf_stats last{}; bool have_last = false;
+    DevBuf<float> block;                             // nalo_tsdf_get / _set staging: one tile of z slices of the sub-block
+    DevBuf<int> cnt; HostBuf<int> cnt_h; DevBuf<float> xyz; HostBuf<float> xyz_h;   // nalo_tsdf_surface_points
+    DevBuf<unsigned long long> key; DevBuf<float> plane;                            // nalo_tsdf_integrate_frame: w h words each; key is zero between calls,
+    bool key_dirty = false;                                                         // unless a call failed between its scatter and its resolve: the next one zeroes it
+    std::vector<MapSeg> segs;                                                       // the frame's segments, host memory: they travel as kernel arguments
+};
+
+constexpr size_t kTsdfTileFloats = (size_t)1 << 22;   // nalo_tsdf_get / _set: 16 MiB of staging
+
+void tsdf_destroy(nalo_ctx* c) { delete c->tsdf; c->tsdf = nullptr; }
+
+static int tsdf_need(nalo_ctx* c, const char* who) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->tsdf) return fail(c, NALO_ERR_STATE, std::string(who) + ": no volume (nalo_tsdf_create)");
+    return NALO_OK;
+}
+
+// the checks of both integrations behind the plane's own; M and the box on success
+static int tsdf_integrate_check(nalo_ctx* c, const char* who, const TsdfVolume& v, int w, int h, const float K[4], const double camToWorld[12], float min_depth, float max_depth,
+                                float M[12], int lo[3], int hi[3]) {
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(K[i])) return fail(c, NALO_ERR_ARG, std::string(who) + ": K is not finite");
+    if (!tsdf_world_to_cam(camToWorld, M)) return fail(c, NALO_ERR_ARG, std::string(who) + ": camToWorld is not finite");
+    if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) return fail(c, NALO_ERR_ARG, std::string(who) + ": min_depth / max_depth not finite, or min_depth > max_depth");
+    if (nalo_tsdf_frustum_box(&v.d, w, h, K, camToWorld, max_depth, lo, hi) != NALO_OK) return fail(c, NALO_ERR_ARG, std::string(who) + ": the culling box refused the arguments");
+    return NALO_OK;
+}
+
+// everything is validated: zero the count, the kernel over the box, the call's record for nalo_tsdf_last. Enqueues only.
+static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth, long long sy, long long sx, int w, int h, const float K[4], const float M[12], float min_depth,
+                                  float max_depth, const int lo[3], const int hi[3]) {
+    NALO_HIP(c, hipMemsetAsync(v.updated.p, 0, sizeof(unsigned long long), c->stream));
+    nalo_tsdf_stats st{};
+    if (hi[0] > lo[0]) {
+        TsdfIntegrateDev D{};
+        D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
+        for (int a = 0; a < 3; ++a) { D.lo[a] = st.lo[a] = lo[a]; D.hi[a] = st.hi[a] = hi[a]; D.origin[a] = v.d.origin[a]; }
+        D.vs = v.d.voxel_size; D.trunc = v.d.trunc; D.max_weight = v.d.max_weight;
+        std::copy(M, M + 12, D.M);
+        D.fx = K[0]; D.fy = K[1]; D.cx = K[2]; D.cy = K[3]; D.min_depth = min_depth; D.max_depth = max_depth;
+        D.depth = depth; D.sy = sy; D.sx = sx; D.w = w; D.h = h; D.updated = v.updated.p;
+        st.visited = (long long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
+        const int rc = tsdf_integrate_launch(c, D); if (rc) return rc;
+    }
+    v.last = st; v.have_last = true;
+    return NALO_OK;
+}
+
+}  // namespace nalo
+
+using namespace nalo;
+
+int nalo_tsdf_create(nalo_ctx* c, const nalo_tsdf_desc* desc) {
+    if (!c) return NALO_ERR_ARG;
+    if (const char* why = tsdf_desc_refusal(desc)) return fail(c, NALO_ERR_ARG, std::string("nalo_tsdf_create: ") + why);
+    NALO_HIP(c, hipSetDevice(c->device));
+    // the new volume is complete before the old one goes: a failed allocation leaves the context as it was
+    TsdfVolume* v = new TsdfVolume();
+    v->d = *desc; v->n = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
+    hipError_t e = v->tsdf.reserve(v->n);
+    if (e == hipSuccess) e = v->weight.reserve(v->n);
+    if (e == hipSuccess) e = v->updated.reserve(1);
+    if (e == hipSuccess) e = v->updated_h.reserve(1);
+    if (e == hipSuccess) e = v->ev_read.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = c->ev_prod.create(hipEventDisableTiming);
+    if (e != hipSuccess) { delete v; (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_create: ") + hipGetErrorString(e)); }
+    if (c->tsdf) { NALO_HIP(c, hipStreamSynchronize(c->stream)); tsdf_destroy(c); }      // kernels of the old volume may still be queued
+    c->tsdf = v;
+    return tsdf_fill_launch(c, v->tsdf.p, v->weight.p, v->n);
+}
+
+int nalo_tsdf_reset(nalo_ctx* c) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_reset"); if (rc) return rc; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    c->tsdf->have_last = false;
+    return tsdf_fill_launch(c, c->tsdf->tsdf.p, c->tsdf->weight.p, c->tsdf->n);
+}
+
+int nalo_tsdf_destroy(nalo_ctx* c) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->tsdf) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    tsdf_destroy(c);
+    return NALO_OK;
+}
+
+int nalo_tsdf_integrate_depth(nalo_ctx* c, const nalo_tsdf_integrate_args* a) {
+    const char* who = "nalo_tsdf_integrate_depth";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_integrate_depth: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    { const int rc = nalo_dev_plane_check(c, &a->depth); if (rc) return rc; }
+    if (a->depth.dtype != NALO_DT_F32 || a->depth.channels != 1) return fail(c, NALO_ERR_ARG, "nalo_tsdf_integrate_depth: the depth plane is one channel of F32");
+    float M[12]; int lo[3], hi[3];
+    { const int rc = tsdf_integrate_check(c, who, v, a->depth.w, a->depth.h, a->K, a->camToWorld, a->min_depth, a->max_depth, M, lo, hi); if (rc) return rc; }
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_integrate_depth");
+    hipStream_t prod = (hipStream_t)a->producer_stream;                      // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    { const int rc = tsdf_integrate_enqueue(c, v, static_cast<const char*>(a->depth.ptr), a->depth.stride_y, a->depth.stride_x, a->depth.w, a->depth.h, a->K, M, a->min_depth,
+                                            a->max_depth, lo, hi); if (rc) return rc; }
+    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));                         // the caller's plane has been read: nalo_tsdf_release
+    v.read_pending = true;
+    return NALO_OK;
+}
+
+int nalo_tsdf_release(nalo_ctx* c, void* stream) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_release"); if (rc) return rc; }
+    if (!c->tsdf->read_pending) return NALO_OK;                                // no plane of a caller's was ever read: nothing to wait for
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamWaitEvent((hipStream_t)stream, c->tsdf->ev_read, 0));
+    return NALO_OK;
+}
+
+int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld[12], const float K[4], float min_depth, float max_depth) {
+    const char* who = "nalo_tsdf_integrate_frame";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!camToWorld || !K) return fail(c, NALO_ERR_ARG, "nalo_tsdf_integrate_frame: bad argument");
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, "nalo_tsdf_integrate_frame: the dense archive is not enabled (nalo_map_dense_enable)");
+    TsdfVolume& v = *c->tsdf;
+    float M[12]; int lo[3], hi[3];
+    { const int rc = tsdf_integrate_check(c, who, v, c->w, c->h, K, camToWorld, min_depth, max_depth, M, lo, hi); if (rc) return rc; }
+    NALO_HIP(c, hipSetDevice(c->device));
+    int total = 0;
+    { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }
+    const size_t npx = (size_t)c->w * c->h;
+    if (v.key.cap < npx) {                                                     // first use: the key plane starts zero and every call leaves it zero
+        DevBuf<unsigned long long> key; DevBuf<float> plane;
+        NALO_HIP(c, key.reserve(npx)); NALO_HIP(c, plane.reserve(npx));
+        NALO_HIP(c, hipMemsetAsync(key.p, 0, npx * sizeof(unsigned long long), c->stream));
+        v.key = std::move(key); v.plane = std::move(plane);
+    }
+    HostTimer ht(c, "tsdf_integrate_frame");
+    if (v.key_dirty) NALO_HIP(c, hipMemsetAsync(v.key.p, 0, npx * sizeof(unsigned long long), c->stream));
+    v.key_dirty = true;                                                        // until the resolve pass, which clears every key, is queued
+    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, c->w, c->h); if (rc) return rc; }
+    v.key_dirty = false;
+    return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi);
+}
+
+int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_last"); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (!stats) return fail(c, NALO_ERR_ARG, "nalo_tsdf_last: bad argument");
+    if (!v.have_last) return fail(c, NALO_ERR_STATE, "nalo_tsdf_last: nothing has been integrated into this volume");
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    *stats = v.last;
+    stats->updated = (long long)v.updated_h.p[0];
+    return NALO_OK;
+}
+
+// nalo_tsdf_get (to_volume = 0) and nalo_tsdf_set (1)
+static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int size[3], float* tsdf, float* weight, int to_volume) {
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (!lo || !size || (!tsdf && !weight)) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
+    for (int a = 0; a < 3; ++a)
+        if (lo[a] < 0 || size[a] < 1 || lo[a] > v.d.dims[a] - size[a]) return fail(c, NALO_ERR_ARG, std::string(who) + ": the block is empty or leaves the grid");
+    NALO_HIP(c, hipSetDevice(c->device));
+    // the block goes through a staging tile of whole z slices, at most kTsdfTileFloats (or one slice, at most 2048 x 2048 floats): never a second volume
+    const size_t slice = (size_t)size[0] * size[1];
+    const int zs = (int)std::max<size_t>(1, std::min<size_t>((size_t)size[2], kTsdfTileFloats / slice));
+    NALO_HIP(c, v.block.reserve(slice * zs));
+    float* host[2] = {tsdf, weight}; float* vol[2] = {v.tsdf.p, v.weight.p};
+    for (int k = 0; k < 2; ++k) {
+        if (!host[k]) continue;
+        for (int z0 = 0; z0 < size[2]; z0 += zs) {
+            const int tlo[3] = {lo[0], lo[1], lo[2] + z0}, tsz[3] = {size[0], size[1], std::min(zs, size[2] - z0)};
+            const size_t nb = slice * tsz[2];
+            float* h = host[k] + slice * z0;
+            if (to_volume) NALO_HIP(c, hipMemcpyAsync(v.block.p, h, nb * 4, hipMemcpyHostToDevice, c->stream));
+            { const int rc = tsdf_block_launch(c, vol[k], v.block.p, v.d.dims, tlo, tsz, to_volume); if (rc) return rc; }
+            if (!to_volume) NALO_HIP(c, hipMemcpyAsync(h, v.block.p, nb * 4, hipMemcpyDeviceToHost, c->stream));
+            NALO_HIP(c, hipStreamSynchronize(c->stream));                    // the tile is used again, and the caller's memory is its own again
+        }
+    }
+    return NALO_OK;
+}
+int nalo_tsdf_get(nalo_ctx* c, const int lo[3], const int size[3], float* tsdf, float* weight) { return tsdf_block(c, "nalo_tsdf_get", lo, size, tsdf, weight, 0); }
+int nalo_tsdf_set(nalo_ctx* c, const int lo[3], const int size[3], const float* tsdf, const float* weight) {
+    return tsdf_block(c, "nalo_tsdf_set", lo, size, const_cast<float*>(tsdf), const_cast<float*>(weight), 1);
+}
+
+int nalo_tsdf_view(nalo_ctx* c, nalo_tsdf_volume_view* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_view: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    out->tsdf = v.tsdf.p; out->weight = v.weight.p;
+    for (int a = 0; a < 3; ++a) out->dims[a] = v.d.dims[a];
+    out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
+}
+
+int nalo_tsdf_surface_points(nalo_ctx* c, nalo_tsdf_surface_args* a) {
+    const char* who = "nalo_tsdf_surface_points";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: bad argument");
+    a->n = 0; a->n_needed = 0;
+    TsdfVolume& v = *c->tsdf;
+    if (a->cap < 0 || (a->cap > 0 && !a->xyz) || std::isnan(a->min_weight)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: bad argument");
+    TsdfSurfaceDev D{};
+    for (int k = 0; k < 3; ++k) {
+        D.lo[k] = a->use_box ? a->lo[k] : 0; D.size[k] = a->use_box ? a->size[k] : v.d.dims[k];
+        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: the sub-box is empty or leaves the grid");
+        D.origin[k] = v.d.origin[k];
+    }
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "tsdf_surface_points");
+    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
+    D.total = D.size[0] * D.size[1] * D.size[2];                               // <= 2^29; three crossings a voxel stay below 2^31
+    D.nb = (D.total + kTsdfSurfVoxPerBlock - 1) / kTsdfSurfVoxPerBlock;
+    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
+    // the device holds room for what the caller has room for, and never for more than the sub-box can give
+    const long long room = std::min<long long>(a->cap, 3LL * D.total);
+    NALO_HIP(c, v.cnt.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.cnt_h.reserve(1));
+    NALO_HIP(c, v.xyz.reserve(3 * (size_t)std::max<long long>(room, 1))); NALO_HIP(c, v.xyz_h.reserve(3 * (size_t)std::max<long long>(room, 1)));
+    D.cnt = v.cnt.p; D.xyz = v.xyz.p; D.cap = room;
+    { const int rc = tsdf_surface_launch(c, D); if (rc) return rc; }
+    // the count is known only behind the scan: everything the call may have written comes up in the one wait
+    NALO_HIP(c, hipMemcpyAsync(v.cnt_h.p, D.cnt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
+    if (room > 0) NALO_HIP(c, hipMemcpyAsync(v.xyz_h.p, v.xyz.p, 3 * (size_t)room * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const long long need = v.cnt_h.p[0];
+    if (need < 0 || need > 3LL * D.total) return fail(c, NALO_ERR_HIP, "nalo_tsdf_surface_points: the device counted more crossings than the sub-box can hold");
+    a->n_needed = need;
+    if (a->cap < need) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: cap is below the crossings found (n_needed)");
+    std::copy(v.xyz_h.p, v.xyz_h.p + 3 * need, a->xyz);
+    a->n = need;
+    return NALO_OK;
+}

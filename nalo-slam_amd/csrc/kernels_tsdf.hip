@@ -1,0 +1,230 @@
+// The TSDF volume's kernels (include/nalo_gpu.h, "tsdf=1"): the projective integration of one depth plane over the culling box, the surface points as an ordered
+// compaction, the sub-block copies and the plane nalo_tsdf_integrate_frame makes of a frame's dense list. Built WITHOUT FMA contraction: every expression below
+// is the header's definition, one rounding per operation.
+#include "nalo_internal.h"
+
+namespace nalo {
+
+// ---- integration. Lanes run along x: a lane owns four voxels that are consecutive in memory and 16-byte aligned (the arrays are allocations of their own, so
+// alignment is a matter of the linear index), one 16-byte load and store per array where all four lie in the box's x range, scalar accesses at a row's two ends.
+// A workgroup is (1 << txl) lanes along x by (256 >> txl) rows of the box, so that a narrow box does not idle most of a wave.
+struct TsdfRow { float m1y, m2z, m5y, m6z, m9y, m10z; };                        // the products of M with py and pz: a row's own, the same operands as per voxel
+
+__device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const TsdfRow& R, int i, float& t, float& w) {
+    const float px = P.origin[0] + ((float)i + 0.5f) * P.vs;
+    const float xc = ((P.M[0] * px + R.m1y) + R.m2z) + P.M[3];
+    const float yc = ((P.M[4] * px + R.m5y) + R.m6z) + P.M[7];
+    const float zc = ((P.M[8] * px + R.m9y) + R.m10z) + P.M[11];
+    const float uf = ((P.fx * (xc / zc)) + P.cx) + 0.5f;
+    const float vf = ((P.fy * (yc / zc)) + P.cy) + 0.5f;
+    if (!(zc > 0.0f && uf >= 0.0f && uf < (float)P.w && vf >= 0.0f && vf < (float)P.h)) return false;
+    const int pu = (int)uf, pv = (int)vf;                                       // 0 <= pu < w, 0 <= pv < h: the comparisons above were made in float
+    const float D = *reinterpret_cast<const float*>(P.depth + (long long)pv * P.sy + (long long)pu * P.sx);
+    if (!(D >= P.min_depth && D <= P.max_depth)) return false;
+    const float sdf = D - zc;
+    if (sdf < -P.trunc) return false;
+    const float d = fminf(1.0f, sdf / P.trunc);
+    const float t0 = t, w0 = w;
+    t = (t0 * w0 + d) / (w0 + 1.0f);
+    w = fminf(w0 + 1.0f, P.max_weight);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P, int txl, int gx, int rows) {
+    __shared__ int wsum[4];
+    const int tx = 1 << txl, ry = 256 >> txl;
+    const int bx = (int)(blockIdx.x % (unsigned)gx), by = (int)(blockIdx.x / (unsigned)gx);
+    const int lx = threadIdx.x & (tx - 1), ly = threadIdx.x >> txl;
+    const int row = by * ry + ly;
+    int n = 0;
+    if (row < rows) {
+        const int bny = P.hi[1] - P.lo[1];
+        const int j = P.lo[1] + row % bny, k = P.lo[2] + row / bny;
+        const long long base = ((long long)k * P.ny + j) * P.nx;                 // linear index of voxel (0, j, k)
+        const long long rb = base + P.lo[0], re = base + P.hi[0];
+        const long long g = (rb & ~3LL) + 4LL * ((long long)bx * tx + lx);
+        if (g < re) {
+            const float py = P.origin[1] + ((float)j + 0.5f) * P.vs, pz = P.origin[2] + ((float)k + 0.5f) * P.vs;
+            const TsdfRow R = {P.M[1] * py, P.M[2] * pz, P.M[5] * py, P.M[6] * pz, P.M[9] * py, P.M[10] * pz};
+            if (g >= rb && g + 4 <= re) {
+                float4 t = *reinterpret_cast<const float4*>(P.tsdf + g), w = *reinterpret_cast<const float4*>(P.weight + g);
+                const int i = (int)(g - base);
+                n += tsdf_voxel(P, R, i, t.x, w.x);
+                n += tsdf_voxel(P, R, i + 1, t.y, w.y);
+                n += tsdf_voxel(P, R, i + 2, t.z, w.z);
+                n += tsdf_voxel(P, R, i + 3, t.w, w.w);
+                if (n) { *reinterpret_cast<float4*>(P.tsdf + g) = t; *reinterpret_cast<float4*>(P.weight + g) = w; }
+            } else {
+                for (long long q = g < rb ? rb : g; q < g + 4 && q < re; ++q) {
+                    float t = P.tsdf[q], w = P.weight[q];
+                    if (tsdf_voxel(P, R, (int)(q - base), t, w)) { P.tsdf[q] = t; P.weight[q] = w; ++n; }
+                }
+            }
+        }
+    }
+    // the updated count: a wave reduction, the four waves through LDS, one atomic per workgroup
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int s = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        if (s) atomicAdd(P.updated, (unsigned long long)s);
+    }
+}
+
+int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D) {
+    const int bnx = D.hi[0] - D.lo[0];
+    const long long rows = (long long)(D.hi[1] - D.lo[1]) * (D.hi[2] - D.lo[2]);
+    if (bnx < 1 || rows < 1 || rows > INT32_MAX) return fail(c, NALO_ERR_ARG, "tsdf_integrate_launch: bad box");
+    const int groups = (bnx + 6) / 4;                                            // aligned groups of four a row's x range can touch, whatever its start
+    int txl = 3;
+    while (txl < 6 && (1 << txl) < groups) ++txl;                               // 8 .. 64 lanes along x
+    const int tx = 1 << txl, ry = 256 >> txl, gx = (groups + tx - 1) / tx;
+    const long long blocks = (long long)gx * ((rows + ry - 1) / ry);
+    if (blocks > INT32_MAX) return fail(c, NALO_ERR_ARG, "tsdf_integrate_launch: the box needs more workgroups than a grid has");
+    ProfScope ps(c, "tsdf_integrate");
+    tsdf_integrate_kernel<<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+__global__ __launch_bounds__(256) void tsdf_fill_kernel(float* tsdf, float* weight, size_t n) {
+    const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += stride) {
+        reinterpret_cast<float4*>(tsdf)[q] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        reinterpret_cast<float4*>(weight)[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < n - 4 * n4) { tsdf[4 * n4 + threadIdx.x] = 1.0f; weight[4 * n4 + threadIdx.x] = 0.0f; }
+}
+int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n) {
+    const size_t want = (n / 4 + 255) / 256;
+    tsdf_fill_kernel<<<(unsigned)std::min<size_t>(std::max<size_t>(want, 1), 2048), 256, 0, c->stream>>>(tsdf, weight, n);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+struct TsdfBlock { int nx, ny, lo[3], size[3]; };
+__global__ __launch_bounds__(256) void tsdf_block_kernel(float* vol, float* block, TsdfBlock B, int total, int to_volume) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= total) return;
+    const int x = q % B.size[0], y = (q / B.size[0]) % B.size[1], z = q / (B.size[0] * B.size[1]);
+    const size_t at = ((size_t)(B.lo[2] + z) * B.ny + (B.lo[1] + y)) * B.nx + (B.lo[0] + x);
+    if (to_volume) vol[at] = block[q]; else block[q] = vol[at];
+}
+int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume) {
+    TsdfBlock B = {dims[0], dims[1], {lo[0], lo[1], lo[2]}, {size[0], size[1], size[2]}};
+    const int total = size[0] * size[1] * size[2];                               // <= 2^29, checked by the caller
+    tsdf_block_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(vol, block, B, total, to_volume);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+// ---- surface points: voxel order (k, j, i) of the sub-box, axis order x, y, z. A lane takes four consecutive voxels of the sub-box, so lane order is output order.
+__device__ __forceinline__ bool tsdf_crossing(float t0, float w0, float t1, float w1, float min_weight) {
+    return w0 >= min_weight && w1 >= min_weight && ((t0 < 0.0f && t1 >= 0.0f) || (t0 >= 0.0f && t1 < 0.0f));
+}
+// the crossings of sub-box voxel q; out != NULL: their points, 3 floats each
+__device__ __forceinline__ int tsdf_surface_voxel(const TsdfSurfaceDev& P, int q, float* out) {
+    const int x = q % P.size[0], y = (q / P.size[0]) % P.size[1], z = q / (P.size[0] * P.size[1]);
+    const int i = P.lo[0] + x, j = P.lo[1] + y, k = P.lo[2] + z;
+    const size_t at = ((size_t)k * P.ny + j) * P.nx + i;
+    const float t0 = P.tsdf[at], w0 = P.weight[at];
+    const size_t step[3] = {1, (size_t)P.nx, (size_t)P.nx * P.ny};
+    const bool inside[3] = {x + 1 < P.size[0], y + 1 < P.size[1], z + 1 < P.size[2]};
+    int n = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!inside[a]) continue;
+        const float t1 = P.tsdf[at + step[a]], w1 = P.weight[at + step[a]];
+        if (!tsdf_crossing(t0, w0, t1, w1, P.min_weight)) continue;
+        if (out) {
+            float p[3] = {P.origin[0] + ((float)i + 0.5f) * P.vs, P.origin[1] + ((float)j + 0.5f) * P.vs, P.origin[2] + ((float)k + 0.5f) * P.vs};
+            p[a] = p[a] + P.vs * (t0 / (t0 - t1));
+            out[3 * n] = p[0]; out[3 * n + 1] = p[1]; out[3 * n + 2] = p[2];
+        }
+        ++n;
+    }
+    return n;
+}
+// exclusive prefix of v over the workgroup's 256 lanes; *sum: the workgroup's total
+__device__ __forceinline__ int tsdf_block_scan(int v, int* sum) {
+    __shared__ int ws[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = v;
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    int off = 0;
+    for (int q = 0; q < wv; ++q) off += ws[q];
+    *sum = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    return off + inc - v;
+}
+__global__ __launch_bounds__(256) void tsdf_surface_count_kernel(TsdfSurfaceDev P) {
+    const long long q0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    int n = 0;
+    for (int e = 0; e < 4; ++e) if (q0 + e < P.total) n += tsdf_surface_voxel(P, (int)(q0 + e), nullptr);
+    int sum;
+    (void)tsdf_block_scan(n, &sum);
+    if (threadIdx.x == 0) P.cnt[blockIdx.x] = sum;
+}
+__global__ __launch_bounds__(256) void tsdf_surface_write_kernel(TsdfSurfaceDev P) {
+    const long long q0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    float pts[4][9];
+    int ne[4] = {0, 0, 0, 0}, n = 0;
+    const bool fits = (long long)P.cnt[P.nb] <= P.cap;                            // the scanned sum: nothing is written when the caller's room is too small
+    if (fits) for (int e = 0; e < 4; ++e) if (q0 + e < P.total) { ne[e] = tsdf_surface_voxel(P, (int)(q0 + e), pts[e]); n += ne[e]; }
+    int sum;
+    long long at = (long long)P.cnt[blockIdx.x] + tsdf_block_scan(n, &sum);
+    for (int e = 0; e < 4; ++e)
+        for (int m = 0; m < ne[e]; ++m, ++at) { P.xyz[3 * at] = pts[e][3 * m]; P.xyz[3 * at + 1] = pts[e][3 * m + 1]; P.xyz[3 * at + 2] = pts[e][3 * m + 2]; }
+}
+int tsdf_surface_launch(nalo_ctx* c, const TsdfSurfaceDev& D) {
+    ProfScope ps(c, "tsdf_surface");
+    tsdf_surface_count_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+    NALO_HIP(c, hipGetLastError());
+    { const int rc = scan_ints_launch(c, D.cnt, D.nb); if (rc) return rc; }
+    if (D.cap > 0) {
+        tsdf_surface_write_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+        NALO_HIP(c, hipGetLastError());
+    }
+    return NALO_OK;
+}
+
+// ---- nalo_tsdf_integrate_frame's plane. A record's key is (its position in the frame's list + 1) << 32 | the bits of its idepth: the maximum per pixel is the
+// last record in append order whatever order the lanes arrive in. The resolve pass leaves the key plane zero for the next call.
+struct TsdfSegs { const nalo_dense_point* p[kTsdfSegsPerLaunch]; int start[kTsdfSegsPerLaunch + 1]; int nseg; };   // start: list positions; [nseg] = the end
+__global__ __launch_bounds__(256) void tsdf_frame_scatter_kernel(TsdfSegs S, unsigned long long* key, int w, int h) {
+    const long long ql = (long long)S.start[0] + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ql >= S.start[S.nseg]) return;
+    const int q = (int)ql;
+    int s = 0;
+    while (s + 1 < S.nseg && q >= S.start[s + 1]) ++s;
+    const nalo_dense_point r = S.p[s][q - S.start[s]];
+    if (r.u >= w || r.v >= h) return;
+    atomicMax(&key[(size_t)r.v * w + r.u], ((unsigned long long)(q + 1) << 32) | (unsigned long long)__float_as_uint(r.idepth));
+}
+__global__ __launch_bounds__(256) void tsdf_frame_resolve_kernel(unsigned long long* key, float* plane, int n) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const unsigned long long k = key[p];
+    plane[p] = k ? 1.0f / __uint_as_float((unsigned)(k & 0xFFFFFFFFull)) : 0.0f;
+    if (k) key[p] = 0;
+}
+int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, int w, int h) {
+    for (int s0 = 0; s0 < nseg; s0 += kTsdfSegsPerLaunch) {
+        TsdfSegs S{};
+        S.nseg = std::min(kTsdfSegsPerLaunch, nseg - s0);
+        for (int k = 0; k < S.nseg; ++k) { S.p[k] = static_cast<const nalo_dense_point*>(segs[s0 + k].p); S.start[k] = segs[s0 + k].start; }
+        S.start[S.nseg] = segs[s0 + S.nseg - 1].start + segs[s0 + S.nseg - 1].n;
+        const int n = S.start[S.nseg] - S.start[0];
+        if (n <= 0) continue;
+        tsdf_frame_scatter_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(S, key, w, h);
+        NALO_HIP(c, hipGetLastError());
+    }
+    const int n = w * h;
+    tsdf_frame_resolve_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(key, plane, n);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+}  // namespace nalo

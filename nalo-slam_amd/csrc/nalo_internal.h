@@ -104,6 +104,7 @@ struct PixSel;
 struct Initializer;
 struct MapArchive;
 struct DenseArchive;
+struct TsdfVolume;
 
 }  // namespace nalo
 
@@ -182,6 +183,7 @@ struct nalo_ctx {
     nalo::Initializer* init = nullptr;       // two-frame initialiser state (host_init.hip)
     nalo::MapArchive* map = nullptr;         // the archive of removed points and the clouds made from it (host_map.hip); NULL until nalo_map_enable
     nalo::DenseArchive* dmap = nullptr;      // the dense map: FrameHessian::mapPoints on the device (host_map.hip); NULL until nalo_map_dense_enable
+    nalo::TsdfVolume* tsdf = nullptr;        // the TSDF volume and its scratch (host_tsdf.hip); NULL until nalo_tsdf_create
     // the keyframe graph (nalo_map_graph_*, host_map.hip): EnergyFunctional::connectivityMap's keys, (host frame_id << 32) + target frame_id, with the count [1] of
     // marginalised residuals; the count [0] of live residuals is taken from the resident slots when the graph is read
     bool graph_on = false;
@@ -445,6 +447,36 @@ long long dense_candidates_bound(int w, int h);                                /
 int dense_boxes_enqueue(nalo_ctx* c, const float* mask, const nalo_plane_cluster* rec, const int* n_clusters_dev, int cap_clusters);
 int dense_update_finish(nalo_ctx* c, int slot, const nalo_plane_cluster* clusters, int C, const double camToWorld[12], const DenseArchiveView& V, long long frame_points,
                         nalo_dense_run* runs, int* n_appended, int* n_runs);
+// host_map.hip: the frame's dense list as segments in append order (MapSeg::p: nalo_dense_point on the device; the list itself is host memory of the caller's:
+// nothing is queued or staged). NALO_ERR_STATE without the dense archive or on a sharded window, NALO_ERR_ARG for a frame_id the archive has never seen; a frame
+// without points gives total = 0
+int map_dense_segments(nalo_ctx* c, const char* who, int frame_id, std::vector<MapSeg>* segs, int* total);
+// ---- the TSDF volume (nalo_tsdf_*; host_tsdf.hip, host_tsdf.cpp, kernels_tsdf.hip). kernels_tsdf.hip is built without FMA contraction: its arithmetic is the
+// definition in include/nalo_gpu.h, operation by operation.
+struct TsdfIntegrateDev {
+    float *tsdf, *weight; int nx, ny, nz;
+    int lo[3], hi[3];                                                           // the culling box, hi exclusive, not empty
+    float origin[3], vs, trunc, max_weight, M[12], fx, fy, cx, cy, min_depth, max_depth;
+    const char* depth; long long sy, sx; int w, h;                              // the plane by byte strides
+    unsigned long long* updated;                                                // zero before
+};
+int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D);
+int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
+// one array's sub-block [lo, lo + size) to (to_volume = 0) or from (1) a contiguous block, x fastest
+int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume);
+constexpr int kTsdfSurfVoxPerBlock = 1024;                                      // 256 lanes x 4 consecutive voxels of the sub-box
+struct TsdfSurfaceDev {
+    const float *tsdf, *weight; int nx, ny, nz, lo[3], size[3], total, nb;      // total: voxels of the sub-box; nb: its workgroups
+    float origin[3], vs, min_weight;
+    int* cnt;                                                                   // [nb + 1]: crossings per workgroup, scanned; [nb] the sum
+    float* xyz; long long cap;                                                  // written only when the sum fits
+};
+int tsdf_surface_launch(nalo_ctx* c, const TsdfSurfaceDev& D);                  // count, scan, write on c->stream
+// nalo_tsdf_integrate_frame's plane: D[v][u] = 1.0f / idepth of the record with the highest position at (u, v), 0 without one. key: w h words, zero between calls.
+// segs is HOST memory: the segments travel as kernel arguments, kTsdfSegsPerLaunch to a launch, so the call stages nothing that a later call could overwrite
+constexpr int kTsdfSegsPerLaunch = 32;
+int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, int w, int h);
+void tsdf_destroy(nalo_ctx* c);
 // host_ba.hip: frame_id (nalo_frame_state) of window frame host_frame, which ba_plane_inputs has validated
 int ba_frame_id(nalo_ctx* c, int host_frame);
 // host_ba.hip
