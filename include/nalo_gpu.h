@@ -902,7 +902,11 @@ int nalo_ground_reset_global_plane(const nalo_ground_frame* frames, int W, const
  *                               with; *numHave the return value. Call site FullSystem.cpp:1668. (The reference reads mhist[256], one past its
  *                               array, in the last quantile iteration: taken as 0 here.)
  *  nalo_pixsel_get_selected     the non-zero pixels of the last map in raster order (idx = x + y*w, status), i.e. what makeNewTraces' loop over
- *                               the map visits (FullSystem.cpp:1672-1690): *n = their number, the first min(cap, *n) are written. */
+ *                               the map visits (FullSystem.cpp:1672-1690): *n = their number, the first min(cap, *n) are written. The list
+ *                               lives in one pinned block from the select / make_maps / make_maps_lidar that made the map until the next of
+ *                               them; nalo_pixsel_make_hists with a non-NULL ths or thsSmoothed reads the thresholds back through that block,
+ *                               and nalo_pixsel_get_selected then answers NALO_ERR_STATE until a new map is made. make_hists(NULL, NULL) and
+ *                               a frame upload (to this or another slot) leave the list as it is. */
 int nalo_pixsel_set_random(nalo_ctx* ctx, const uint8_t* randomPattern, const int* mask_draws);
 int nalo_pixsel_make_hists(nalo_ctx* ctx, int slot, float* ths, float* thsSmoothed);
 int nalo_pixsel_select(nalo_ctx* ctx, int slot, int pot, float thFactor, float* map_out, int n[3]);

@@ -1840,7 +1840,11 @@ class Context:
         self._ck(self.L.nalo_init_depth_image(self.h_, C.byref(a)))
         return {"bgr": bgr[:3 * a.w * a.h].reshape(a.h, a.w, 3), "n_points": a.n_points, "n_good": a.n_good, "sum_iR": np.float32(a.sum_iR), "fac": np.float32(a.fac)}
 
-    def pixsel_make_hists(self, slot):
+    def pixsel_make_hists(self, slot, readback=True):
+        """-> (ths, thsSmoothed); readback=False passes NULL for both (the thresholds stay on the device, the last map's list stays readable) -> None"""
+        if not readback:
+            self._ck(self.L.nalo_pixsel_make_hists(self.h_, slot, None, None))
+            return None
         nb = (self.w // 32) * (self.h // 32)
         ths, sm = np.zeros(nb, np.float32), np.zeros(nb, np.float32)
         self._ck(self.L.nalo_pixsel_make_hists(self.h_, slot, _f(ths), _f(sm)))

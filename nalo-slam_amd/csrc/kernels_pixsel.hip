@@ -24,10 +24,11 @@ namespace nalo {
 struct PixSel {
     DevBuf<uint8_t> rp, map, has, sel;
     DevBuf<int> draws, pre, chunk, list, cnt;   // cnt: [0] mismatch [1..3] n2 n3 n4 [4] list length [5] kept (sub-select) [6,7] fused n1 n2 [8..] mask histogram (257)
-    DevBuf<float> ths;                           // [ths (nb + 100) | thsSmoothed (nb + 100)], zero tails (see pixsel_state)
+    DevBuf<float> ths;                           // [ths | thsSmoothed], pixsel_ths_len() floats each, zero tails (see pixsel_state)
     HostBuf<int> host;                           // pinned: [0..15] counters, [16..] list
     int hist_slot = -1;
     bool have_rp = false, have_draws = false, have_map = false;
+    bool list_valid = false;                     // host[16..] holds the last map's list (a threshold read-back goes through the same block; an upload does not touch it)
     int list_n = 0, list_total = 0, map_slot = -1;   // list_total: the device list's length (entries the sub-selection dropped stay, with status 0); map_slot: the frame of the last map
 };
 
@@ -257,27 +258,32 @@ void pixsel_invalidate_map(nalo_ctx* c, int slot) {
 }
 bool pixsel_last_list(nalo_ctx* c, int slot, const int** dev, int* n_dev, const int** host_live, int* n_live) {
     const PixSel* p = c->pixsel;
-    if (!p || !p->have_map || p->map_slot != slot || slot < 0) return false;
+    if (!p || !p->have_map || !p->list_valid || p->map_slot != slot || slot < 0) return false;
     *dev = p->list.p; *n_dev = p->list_total; *host_live = p->host.p + 16; *n_live = p->list_n;
     return true;
 }
 
+// Floats of one threshold buffer. PixelSelector allocates (w/32)*(h/32)+100 thresholds and fills (w/32)*(h/32); select() indexes (x>>5) + (y>>5)*(w/32), which on
+// sizes that are not multiples of 32 (KITTI 1224x368) reaches the next row or the uninitialised tail: at most (h/32)*(w/32) + ((w-1)>>5), which passes the
+// reference's +100 once w/32 > 100. Same indexing here; the tail is DEFINED as 0 and is long enough for every index select() can form.
+static size_t pixsel_ths_len(const nalo_ctx* c) {
+    const size_t w32 = c->w / 32, h32 = c->h / 32;
+    return w32 * h32 + std::max<size_t>(100, w32 + 1);
+}
 static int pixsel_state(nalo_ctx* c, PixSel** out) {
     if (!c->pixsel) c->pixsel = new PixSel();
     PixSel* p = c->pixsel;
     const size_t n = (size_t)c->w * c->h;
     NALO_HIP(c, p->map.reserve(n + 16)); NALO_HIP(c, p->list.reserve(n)); NALO_HIP(c, p->cnt.reserve(8 + 264));
     NALO_HIP(c, p->chunk.reserve((n + kChunk - 1) / kChunk + 1));
-    // PixelSelector allocates (w/32)*(h/32)+100 thresholds and fills (w/32)*(h/32); select() indexes (x>>5) + (y>>5)*(w/32), which on sizes that are
-    // not multiples of 32 (KITTI 1224x368) reaches the next row or the uninitialised tail. Same indexing here; the tail is DEFINED as 0.
-    const size_t nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
+    const size_t nbp = pixsel_ths_len(c);
     if (p->ths.cap < 2 * nbp) { NALO_HIP(c, p->ths.reserve(2 * nbp)); NALO_HIP(c, hipMemsetAsync(p->ths.p, 0, 2 * nbp * sizeof(float), c->stream)); }
     NALO_HIP(c, p->host.reserve(n + 16));
     *out = p;
     return NALO_OK;
 }
 static int pixsel_hists(nalo_ctx* c, PixSel* p, int slot) {
-    const size_t nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
+    const size_t nbp = pixsel_ths_len(c);
     int rc = pixsel_hists_launch(c, c->slots[slot].absg[0].p, p->ths.p, p->ths.p + nbp);
     if (rc) return rc;
     p->hist_slot = slot;
@@ -285,9 +291,9 @@ static int pixsel_hists(nalo_ctx* c, PixSel* p, int slot) {
 }
 // select on the device: map (bytes) + counters. n[3] = {n2, n3, n4} of PixelSelector::select.
 static int pixsel_select_dev(nalo_ctx* c, PixSel* p, int slot, int pot, float thFactor, int n[3]) {
-    p->map_slot = -1;                                               // until this selection stands
+    p->map_slot = -1; p->list_valid = false;                        // until this selection stands and pixsel_fetch brought its list
     const FrameSlot& s = c->slots[slot];
-    const size_t npx = (size_t)c->w * c->h, nbp = (size_t)(c->w / 32) * (c->h / 32) + 100;
+    const size_t npx = (size_t)c->w * c->h, nbp = pixsel_ths_len(c);
     PixSelArgs A;
     A.dI = s.dI[0].p; A.ag0 = s.absg[0].p; A.ag1 = s.absg[1].p; A.ag2 = s.absg[2].p; A.thsSmoothed = p->ths.p + nbp; A.rp = p->rp.p;
     A.w = c->w; A.h = c->h; A.pot = pot; A.nb4x = (c->w + 4 * pot - 1) / (4 * pot);
@@ -342,7 +348,7 @@ static int pixsel_fetch(nalo_ctx* c, PixSel* p, int charTH, float* map_out, int*
     // the list keeps only live entries (sub-selected ones are dropped here)
     int m = 0;
     for (int i = 0; i < total; ++i) { const int e = p->host.p[16 + i]; if (e >> 28) p->host.p[16 + m++] = e; }
-    p->list_n = m; p->list_total = total;
+    p->list_n = m; p->list_total = total; p->list_valid = true;
     if (map_out) {
         std::memset(map_out, 0, sizeof(float) * (size_t)npx);
         for (int i = 0; i < m; ++i) { const int e = p->host.p[16 + i]; map_out[e & 0x0FFFFFFF] = (float)(e >> 28); }
@@ -393,11 +399,12 @@ int nalo_pixsel_make_hists(nalo_ctx* c, int slot, float* ths, float* thsSmoothed
     if (nb == 0) return NALO_OK;
     rc = pixsel_hists(c, p, slot); if (rc) return rc;
     if (ths || thsSmoothed) {
-        p->map_slot = -1;                                           // the read-back goes through the pinned block that holds the last map's list
-        NALO_HIP(c, hipMemcpyAsync(p->host.p, p->ths.p, 2 * (nb + 100) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        const size_t nbp = pixsel_ths_len(c);
+        p->map_slot = -1; p->list_valid = false;                    // the read-back goes through the pinned block that holds the last map's list
+        NALO_HIP(c, hipMemcpyAsync(p->host.p, p->ths.p, 2 * nbp * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         NALO_HIP(c, hipStreamSynchronize(c->stream));
         if (ths) std::memcpy(ths, p->host.p, nb * sizeof(float));
-        if (thsSmoothed) std::memcpy(thsSmoothed, reinterpret_cast<float*>(p->host.p) + nb + 100, nb * sizeof(float));
+        if (thsSmoothed) std::memcpy(thsSmoothed, reinterpret_cast<float*>(p->host.p) + nbp, nb * sizeof(float));
     }
     return NALO_OK;
 }
@@ -466,6 +473,7 @@ int nalo_pixsel_get_selected(nalo_ctx* c, int cap, int* idx, uint8_t* status, in
     if (!c || !n || cap < 0 || (cap > 0 && (!idx || !status))) return fail(c, NALO_ERR_ARG, "nalo_pixsel_get_selected: bad argument");
     if (!c->pixsel || !c->pixsel->have_map) return fail(c, NALO_ERR_STATE, "nalo_pixsel_get_selected: no selection has been made");
     const PixSel* p = c->pixsel;
+    if (!p->list_valid) return fail(c, NALO_ERR_STATE, "nalo_pixsel_get_selected: the last map's list is gone (nalo_pixsel_make_hists read its thresholds back since)");
     *n = p->list_n;
     for (int i = 0; i < std::min(cap, p->list_n); ++i) { const int e = p->host.p[16 + i]; idx[i] = e & 0x0FFFFFFF; status[i] = (uint8_t)(e >> 28); }
     return NALO_OK;

@@ -193,6 +193,12 @@ def pixsel_libc_tables(n, kind="f32"):
     return rp, dr
 
 
+def pixsel_ths_len(w, h):
+    """floats of a thsSmoothed buffer: the reference's (w/32)*(h/32) + 100, and never fewer than the largest index select() forms needs,
+    (h/32)*(w/32) + ((w-1) >> 5) when h % 32 != 0 (past the + 100 once w/32 > 100); pixsel_ths_len() of kernels_pixsel.hip"""
+    return (w // 32) * (h // 32) + max(100, w // 32 + 1)
+
+
 def _pixsel_imgs(dI, ag0, ag1, ag2):
     f = lambda a: np.ascontiguousarray(a, np.float32)
     return f(dI), f(ag0), f(ag1), f(ag2)
@@ -202,7 +208,7 @@ def pixsel_select(dI, ag0, ag1, ag2, w, h, thsSmoothed, randomPattern, pot, thFa
     dI, ag0, ag1, ag2 = _pixsel_imgs(dI, ag0, ag1, ag2)
     m, n = np.zeros((h, w), np.float32), np.zeros(3, np.int32)
     rp = np.ascontiguousarray(randomPattern, np.uint8)
-    sm = np.zeros((w // 32) * (h // 32) + 100, np.float32)      # the reference's allocation; the tail it never fills is defined as 0 (orc_pixsel.c)
+    sm = np.zeros(pixsel_ths_len(w, h), np.float32)             # the tail the reference never fills is defined as 0 (orc_pixsel.c)
     sm[:len(thsSmoothed)] = thsSmoothed
     lib(kind).orc_pixsel_select(fp(dI), fp(ag0), fp(ag1), fp(ag2), w, h, fp(sm), rp.ctypes.data_as(C.POINTER(C.c_ubyte)),
                                 pot, C.c_float(thFactor), fp(m), ip(n))
