@@ -1524,6 +1524,40 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    lo = floor((min - origin) / voxel_size - 0.5) - 1 and hi = ceil((max - origin) / voxel_size - 0.5) + 2, clipped to [0, dim]: the voxels whose
  *                    centres lie in the box, padded by one voxel on every side (hi exclusive). An empty box on any axis gives all zeros. NALO_ERR_ARG for a
  *                    descriptor nalo_tsdf_create refuses, w or h < 1, a non-finite K, pose or max_depth.
+ *
+ * The mesh. The reference includes cpu_tsdf/marching_cubes_tsdf_octree.h next to the octree volume (FullSystem.h:45-47): what its tsdf=1 mode is built towards is
+ * a surface mesh, extracted by a tool it neither vendors nor pins. nalo_tsdf_mesh is a DEFINED, deterministic, indexed triangle list instead: marching tetrahedra
+ * on the Kuhn split of every cell (no 256-case table, no ambiguous case; the face diagonals of neighbouring cells agree by translation, so the surface is closed
+ * wherever the data is). Everything in float, no FMA contraction, each operation rounded once. Over the sub-box [lo, lo + size) (use_box == 0: the whole grid):
+ *   Validity and sign: a voxel is VALID iff weight >= min_weight and its tsdf is not NaN; it is INSIDE iff tsdf < 0 (-0.0f and 0.0f are outside). centre(v) is
+ *     the px, py, pz of the integration above.
+ *   Edges and vertices: voxel v owns seven edges m = 1..7 from v to n = v + d_m, d_m = (m & 1, (m >> 1) & 1, (m >> 2) & 1): the axis edges m = 1, 2, 4, the face
+ *     diagonals 3, 5, 6, the body diagonal 7. (v, m) carries a vertex iff n lies inside the sub-box, both ends are valid and exactly one end is inside. With
+ *     s = t0 / (t0 - t1) and prod = voxel_size * s, each computed once, its position is centre(v) with prod added to every component a for which d_m[a] == 1.
+ *     Vertices are numbered from 0 in ascending (k, j, i) of v, then ascending m. A vertex that no triangle names is legal (the rim of the valid band).
+ *     The vertices with m in {1, 2, 4}, in order, are exactly nalo_tsdf_surface_points of the same sub-box and min_weight, bit for bit.
+ *   Cells and tetrahedra: cell c has corners c + bits(b), b = dx + 2 dy + 4 dz = 0..7; it is LIVE iff all eight lie inside the sub-box and are valid. A live cell
+ *     is cut into T0..T5 with corners (c0, c1, c2, c3) = (0,1,3,7), (0,1,5,7), (0,2,3,7), (0,2,6,7), (0,4,5,7), (0,4,6,7). Every tetrahedron edge joins corners
+ *     p < q whose bits nest (p & q == p); its vertex is the one owned by voxel c + bits(p) with m = q ^ p.
+ *   Triangles of a tetrahedron: mask has bit r set iff c_r is inside; X.Y is the vertex on edge XY. mask 0 or 15: none. One corner alone (one inside or one
+ *     outside): with L that corner and O1, O2, O3 the others in ascending r, the triangle (L.O1, L.O2, L.O3). Two and two: insiders I1, I2 and outsiders O1, O2
+ *     in ascending r give the quad q0 = I1.O1, q1 = I1.O2, q2 = I2.O2, q3 = I2.O1 and the triangles (q0, q1, q2), (q0, q2, q3).
+ *   Winding: with every vertex at the midpoint of its edge in the unit cube, a triangle (A, B, C) is kept as written when ((B - A) x (C - A)) . (mean of the
+ *     outside corners - mean of the inside corners) > 0, else its last two vertices are swapped (the product is never zero: an integer at doubled coordinates).
+ *     The normal points from tsdf < 0 to tsdf >= 0, towards the camera that saw the surface.
+ *   Order: ascending (k, j, i) of the cell, then T0..T5, then the order above.
+ * nalo_tsdf_mesh     reads the volume only and always builds the mesh into context-owned device buffers; n_vertices / n_triangles are what the device mesh holds.
+ *                    A host array that is given (non-NULL) is filled when its cap suffices. A classify pass (5 B of scratch per sub-box voxel), two scans, a
+ *                    vertex and a triangle pass; no atomic append, the same bytes on every run; one host wait when nothing is downloaded and the buffers suffice
+ *                    (they grow to what a call finds plus a quarter, and the two write passes run again). NALO_ERR_ARG, with nothing written to either host
+ *                    array: a negative cap, a cap > 0 with a NULL array, a NaN min_weight, a sub-box that is empty or leaves the grid or holds more than 2^28
+ *                    voxels (seven vertices a voxel must fit an int index) - such a call queues nothing and leaves volume, context and the previous device mesh as
+ *                    they were, with both counts 0 - and a cap below the count of an array that is given: that is known only behind the scans, so the device
+ *                    mesh IS built and both counts are set. NALO_ERR_STATE without a volume. A failed allocation (NALO_ERR_HIP) leaves the previous mesh whole.
+ * nalo_tsdf_mesh_view   host code only, launches nothing: the device mesh ([n_vertices][3] float, [n_triangles][3] int) and its producing stream, under "Lifetime
+ *                    of a view": good until the next nalo_tsdf_mesh, nalo_tsdf_create, nalo_tsdf_destroy or nalo_destroy. NALO_ERR_STATE before the first mesh.
+ * nalo_tsdf_mesh_table  host only, needs no context: the table the kernels use, built from the rules above at compile time. For tetrahedron t and mask the six
+ *                    entries are the vertices of up to two triangles in output order, each coded 8 p + (q ^ p), -1 as padding; 120 triangles in all.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1553,10 +1587,21 @@ int nalo_tsdf_set(nalo_ctx* ctx, const int lo[3], const int size[3], const float
 int nalo_tsdf_view(nalo_ctx* ctx, nalo_tsdf_volume_view* out);
 int nalo_tsdf_surface_points(nalo_ctx* ctx, nalo_tsdf_surface_args* args);
 int nalo_tsdf_frustum_box(const nalo_tsdf_desc* desc, int w, int h, const float K[4], const double camToWorld[12], float max_depth, int lo[3], int hi[3]);   /* host only */
+typedef struct nalo_tsdf_mesh_args {
+    int use_box; int lo[3], size[3];        /* as nalo_tsdf_surface_args */
+    float min_weight;
+    long long cap_vertices, cap_triangles;
+    float* xyz; int* tri;                   /* host, [cap][3] each; NULL: leave the mesh on the device */
+    long long n_vertices, n_triangles;      /* out: what the device mesh holds */
+} nalo_tsdf_mesh_args;
+typedef struct nalo_tsdf_mesh_dev { float* xyz; int* tri; long long n_vertices, n_triangles; void* stream; } nalo_tsdf_mesh_dev;
+int nalo_tsdf_mesh(nalo_ctx* ctx, nalo_tsdf_mesh_args* args);
+int nalo_tsdf_mesh_view(nalo_ctx* ctx, nalo_tsdf_mesh_dev* out);     /* host only, launches nothing */
+int nalo_tsdf_mesh_table(signed char out[6][16][6]);                 /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -80,4 +80,6 @@ int nalo_io_resize_nearest_u8(const uint8_t* src, int wOrg, int hOrg, int channe
 #ifdef __cplusplus
 }
 #endif
+/* the PLY mesh writer of the tsdf=1 path */
+#include "nalo_io_mesh.h"
 #endif

@@ -40,7 +40,7 @@ EXPORTS = [
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
     "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
-    "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box",
+    "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -182,6 +182,15 @@ class TsdfSurfaceArgs(C.Structure):                       # nalo_tsdf_surface_ar
                 ("n", C.c_longlong), ("n_needed", C.c_longlong)]
 
 
+class TsdfMeshArgs(C.Structure):                          # nalo_tsdf_mesh_args
+    _fields_ = [("use_box", C.c_int), ("lo", C.c_int * 3), ("size", C.c_int * 3), ("min_weight", C.c_float), ("cap_vertices", C.c_longlong), ("cap_triangles", C.c_longlong),
+                ("xyz", c_fp), ("tri", c_ip), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong)]
+
+
+class TsdfMeshDev(C.Structure):                           # nalo_tsdf_mesh_dev
+    _fields_ = [("xyz", C.c_void_p), ("tri", C.c_void_p), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong), ("stream", C.c_void_p)]
+
+
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
@@ -275,6 +284,8 @@ def host_lib():
         L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
         L.nalo_trk_motion_tries.argtypes = [c_dp, c_dp, C.c_int, c_dp]
         L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
+        L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
+        L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         _HOST_LIB = L
     return _HOST_LIB
 
@@ -320,6 +331,24 @@ def tsdf_frustum_box(desc, w, h, K, cam_to_world, max_depth):
     if rc != 0:
         raise NaloError("nalo_tsdf_frustum_box: bad argument (%d)" % rc)
     return lo, hi
+
+
+def tsdf_mesh_table():
+    """nalo_tsdf_mesh_table: int8 [6][16][6], for tetrahedron t and sign mask the vertices of up to two triangles in output order, each coded 8 p + (q ^ p), -1
+    as padding; needs no device"""
+    out = np.zeros((6, 16, 6), np.int8)
+    rc = host_lib().nalo_tsdf_mesh_table(out.ctypes.data)
+    if rc != 0:
+        raise NaloError("nalo_tsdf_mesh_table: error %d" % rc)
+    return out
+
+
+def write_ply_mesh(path, xyz, tri):
+    """nalo_io_write_ply_mesh: xyz float32 [nv][3] and tri int32 [nt][3] as a binary little-endian PLY file; needs no device"""
+    x, t = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3), np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+    rc = host_lib().nalo_io_write_ply_mesh(os.fsencode(path), len(x), _f(x), len(t), _i(t))
+    if rc != 0:
+        raise NaloError("nalo_io_write_ply_mesh: error %d (-1: an index outside the vertices, -2: the file cannot be written)" % rc)
 
 
 def _ground_argtypes(L):
@@ -493,6 +522,9 @@ def load():
     L.nalo_tsdf_set.argtypes = [vp, c_ip, c_ip, c_fp, c_fp]
     L.nalo_tsdf_view.argtypes = [vp, C.POINTER(TsdfVolumeView)]
     L.nalo_tsdf_surface_points.argtypes = [vp, C.POINTER(TsdfSurfaceArgs)]
+    L.nalo_tsdf_mesh.argtypes = [vp, C.POINTER(TsdfMeshArgs)]
+    L.nalo_tsdf_mesh_view.argtypes = [vp, C.POINTER(TsdfMeshDev)]
+    L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
@@ -1552,6 +1584,39 @@ class Context:
         self.tsdf_surface_needed = int(a.n_needed)
         self._ck(rc)
         return xyz[:int(a.n)].copy()
+
+    def tsdf_mesh(self, min_weight, lo=None, size=None, download=True):
+        """nalo_tsdf_mesh -> (xyz float32 [nv][3], tri int32 [nt][3]): the marching-tetrahedra mesh of the sub-box [lo, lo + size) or of the whole grid, in the
+        header's order. The mesh is always built on the device (tsdf_mesh_view); download=False returns the counts (nv, nt) only, after one library call and one
+        wait. With the download the arrays are sized from that call's counts and a second call fills them. self.tsdf_mesh_counts holds the counts of the last
+        call, a refusal included"""
+        a = TsdfMeshArgs()
+        if lo is not None:
+            a.use_box = 1
+            a.lo[:] = [int(v) for v in lo]
+            a.size[:] = [int(v) for v in size]
+        a.min_weight = float(min_weight)
+        rc = self.L.nalo_tsdf_mesh(self.h_, C.byref(a))
+        self.tsdf_mesh_counts = (int(a.n_vertices), int(a.n_triangles))
+        self._ck(rc)
+        if not download:
+            return self.tsdf_mesh_counts
+        nv, nt = self.tsdf_mesh_counts
+        xyz, tri = np.zeros((nv, 3), np.float32), np.zeros((nt, 3), np.int32)
+        if nv == 0 and nt == 0:
+            return xyz, tri
+        a.cap_vertices, a.cap_triangles, a.xyz, a.tri = nv, nt, (_f(xyz) if nv else None), (_i(tri) if nt else None)
+        rc = self.L.nalo_tsdf_mesh(self.h_, C.byref(a))
+        self.tsdf_mesh_counts = (int(a.n_vertices), int(a.n_triangles))
+        self._ck(rc)
+        return xyz, tri
+
+    def tsdf_mesh_view(self):
+        """nalo_tsdf_mesh_view -> (xyz, tri) as DeviceViews of shape [nv, 3] float32 and [nt, 3] int32: torch.as_tensor(view, device="cuda") is a zero-copy
+        tensor of the device mesh the last tsdf_mesh built. Launches nothing; good until the next tsdf_mesh / tsdf_create / tsdf_destroy / close."""
+        v = TsdfMeshDev()
+        self._ck(self.L.nalo_tsdf_mesh_view(self.h_, C.byref(v)))
+        return DeviceView(v.xyz, (v.n_vertices, 3), "<f4", None, v.stream, self), DeviceView(v.tri, (v.n_triangles, 3), "<i4", None, v.stream, self)
 
     def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
         """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes

@@ -72,6 +72,34 @@ int nalo_io_write_pcd_points(const char* path, int append, int n, const float* u
     return f.fail() ? NALO_IO_ERR_FILE : NALO_IO_OK;
 }
 
+int nalo_io_write_ply_mesh(const char* path, long long nv, const float* xyz, long long nt, const int* tri) {
+    if (!path || nv < 0 || nt < 0 || (nv > 0 && !xyz) || (nt > 0 && !tri)) return NALO_IO_ERR_ARG;
+    for (long long k = 0; k < 3 * nt; ++k) if (tri[k] < 0 || tri[k] >= nv) return NALO_IO_ERR_ARG;      // before the file is opened: a refused mesh leaves no file behind
+    std::ofstream f(path, std::ios::binary | std::ios::trunc);
+    if (!f.good()) return NALO_IO_ERR_FILE;
+    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv << "\nproperty float x\nproperty float y\nproperty float z\nelement face " << nt
+      << "\nproperty list uchar int vertex_indices\nend_header\n";
+    // the values byte by byte, least significant first, whatever the host's own order is
+    std::vector<char> buf;
+    buf.reserve(1 << 16);
+    auto put32 = [&](uint32_t u) { for (int b = 0; b < 4; ++b) buf.push_back((char)((u >> (8 * b)) & 0xFFu)); };
+    auto flush = [&]() { f.write(buf.data(), (std::streamsize)buf.size()); buf.clear(); };
+    for (long long k = 0; k < 3 * nv; ++k) {
+        uint32_t u;
+        std::memcpy(&u, xyz + k, 4);
+        put32(u);
+        if (buf.size() >= (1 << 16) - 16) flush();
+    }
+    for (long long t = 0; t < nt; ++t) {
+        buf.push_back((char)3);
+        for (int k = 0; k < 3; ++k) put32((uint32_t)tri[3 * t + k]);
+        if (buf.size() >= (1 << 16) - 16) flush();
+    }
+    flush();
+    f.close();
+    return f.fail() ? NALO_IO_ERR_FILE : NALO_IO_OK;
+}
+
 
 int nalo_io_read_camera(const char* path, nalo_camera_file* out) {
     if (!path || !out) return NALO_IO_ERR_ARG;

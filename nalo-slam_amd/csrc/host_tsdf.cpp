@@ -1,8 +1,9 @@
-// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, and the culling box nalo_tsdf_frustum_box. Plain C++ with no
+// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, the culling box nalo_tsdf_frustum_box and the mesh's triangle table. Plain C++ with no
 // device call, built without FMA contraction: every line below is the operation order the header defines, in double.
 #include <cmath>
 
 #include "tsdf_host.h"
+#include "tsdf_mesh_table.h"
 
 namespace nalo {
 
@@ -63,5 +64,14 @@ extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, cons
         if (lo[a] >= hi[a]) empty = true;
     }
     if (empty) for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
+    return NALO_OK;
+}
+
+extern "C" int nalo_tsdf_mesh_table(signed char out[6][16][6]) {
+    if (!out) return NALO_ERR_ARG;
+    static constexpr nalo::TsdfMeshTable T = nalo::tsdf_mesh_make_table();      // built from the rules at compile time; the kernels hold the same object
+    for (int t = 0; t < 6; ++t)
+        for (int m = 0; m < 16; ++m)
+            for (int k = 0; k < 6; ++k) out[t][m][k] = T.e[t][m][k];
     return NALO_OK;
 }

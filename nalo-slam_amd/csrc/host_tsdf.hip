@@ -1,5 +1,5 @@
 // The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
-// arithmetic lives in kernels_tsdf.hip (device) and host_tsdf.cpp (worldToCam, the culling box).
+// arithmetic lives in kernels_tsdf.hip and kernels_tsdf_mesh.hip (device) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table).
 #include <algorithm>
 #include <cmath>
 
@@ -21,7 +21,14 @@ struct TsdfVolume {
     DevBuf<unsigned long long> key; DevBuf<float> plane;                            // nalo_tsdf_integrate_frame: w h words each; key is zero between calls,
     bool key_dirty = false;                                                         // unless a call failed between its scatter and its resolve: the next one zeroes it
     std::vector<MapSeg> segs;                                                       // the frame's segments, host memory: they travel as kernel arguments
+    // nalo_tsdf_mesh: 5 B of scratch per sub-box voxel, the two count arrays, and the device mesh itself (nalo_tsdf_mesh_view names mesh_xyz / mesh_tri)
+    DevBuf<unsigned char> mesh_mask; DevBuf<int> mesh_base, mesh_cntv, mesh_cntt; HostBuf<int> mesh_cnt_h;
+    DevBuf<float> mesh_xyz; DevBuf<int> mesh_tri;
+    long long mesh_nv = 0, mesh_nt = 0; bool have_mesh = false;
 };
+
+constexpr long long kTsdfMeshMaxVoxels = 1LL << 28;                               // seven vertices a voxel must fit an int index
+constexpr long long kTsdfMeshFirstVertices = 1LL << 14, kTsdfMeshFirstTriangles = 1LL << 15;   // the device mesh's first capacity; it grows to what a call finds plus a quarter
 
 constexpr size_t kTsdfTileFloats = (size_t)1 << 22;   // nalo_tsdf_get / _set: 16 MiB of staging
 
@@ -247,5 +254,80 @@ int nalo_tsdf_surface_points(nalo_ctx* c, nalo_tsdf_surface_args* a) {
     if (a->cap < need) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: cap is below the crossings found (n_needed)");
     std::copy(v.xyz_h.p, v.xyz_h.p + 3 * need, a->xyz);
     a->n = need;
+    return NALO_OK;
+}
+
+int nalo_tsdf_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* a) {
+    const char* who = "nalo_tsdf_mesh";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: bad argument");
+    a->n_vertices = 0; a->n_triangles = 0;
+    TsdfVolume& v = *c->tsdf;
+    if (a->cap_vertices < 0 || a->cap_triangles < 0 || (a->cap_vertices > 0 && !a->xyz) || (a->cap_triangles > 0 && !a->tri) || std::isnan(a->min_weight))
+        return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: bad argument");
+    TsdfMeshDev D{};
+    long long total = 1;
+    for (int k = 0; k < 3; ++k) {
+        D.lo[k] = a->use_box ? a->lo[k] : 0; D.size[k] = a->use_box ? a->size[k] : v.d.dims[k];
+        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: the sub-box is empty or leaves the grid");
+        D.origin[k] = v.d.origin[k];
+        total *= D.size[k];
+    }
+    if (total > kTsdfMeshMaxVoxels) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: the sub-box holds more than 2^28 voxels");
+    // ---- accepted: from here on only the runtime can fail, or a host array turn out too small for what the device found
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "tsdf_mesh");
+    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
+    D.total = (int)total; D.nb = (D.total + kTsdfSurfVoxPerBlock - 1) / kTsdfSurfVoxPerBlock;
+    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
+    NALO_HIP(c, v.mesh_mask.reserve((size_t)total + 3)); NALO_HIP(c, v.mesh_base.reserve((size_t)total + 3));      // whole lanes of four voxels
+    NALO_HIP(c, v.mesh_cntv.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.mesh_cntt.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.mesh_cnt_h.reserve(2));
+    if (!v.mesh_xyz.p || !v.mesh_tri.p) {                                      // both or neither: a failure leaves neither
+        DevBuf<float> xyz; DevBuf<int> tri;
+        NALO_HIP(c, xyz.reserve(3 * (size_t)kTsdfMeshFirstVertices)); NALO_HIP(c, tri.reserve(3 * (size_t)kTsdfMeshFirstTriangles));
+        v.mesh_xyz = std::move(xyz); v.mesh_tri = std::move(tri);
+    }
+    D.vmask = v.mesh_mask.p; D.vbase = v.mesh_base.p; D.cntv = v.mesh_cntv.p; D.cntt = v.mesh_cntt.p;
+    D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = (long long)(v.mesh_xyz.cap / 3); D.capt = (long long)(v.mesh_tri.cap / 3);
+    // all four passes against the room there is: the steady state waits once, for the two totals
+    {
+        ProfScope ps(c, "tsdf_mesh");
+        { const int rc = tsdf_mesh_classify_launch(c, D); if (rc) return rc; }
+        { const int rc = tsdf_mesh_write_launch(c, D); if (rc) return rc; }
+    }
+    NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p, D.cntv + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p + 1, D.cntt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const long long nv = v.mesh_cnt_h.p[0], nt = (long long)(unsigned)v.mesh_cnt_h.p[1];
+    if (nv < 0 || nv > 7 * total || nt > 12 * total) return fail(c, NALO_ERR_HIP, "nalo_tsdf_mesh: the device counted more than the sub-box can hold");
+    if (nv > D.capv || nt > D.capt) {
+        // nothing was written: the previous mesh is still whole, and stays if the new room cannot be had
+        DevBuf<float> xyz; DevBuf<int> tri;
+        const long long rv = std::max(D.capv, nv + nv / 4), rt = std::max(D.capt, nt + nt / 4);
+        hipError_t e = xyz.reserve(3 * (size_t)rv);
+        if (e == hipSuccess) e = tri.reserve(3 * (size_t)rt);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_mesh: ") + hipGetErrorString(e)); }
+        v.mesh_xyz = std::move(xyz); v.mesh_tri = std::move(tri);              // the old pair is freed as xyz / tri leave scope: nothing queued names it
+        D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = rv; D.capt = rt;
+        ProfScope ps(c, "tsdf_mesh");
+        { const int rc = tsdf_mesh_write_launch(c, D); if (rc) return rc; }
+    }
+    v.mesh_nv = nv; v.mesh_nt = nt; v.have_mesh = true;
+    a->n_vertices = nv; a->n_triangles = nt;
+    if ((a->xyz && a->cap_vertices < nv) || (a->tri && a->cap_triangles < nt))
+        return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: a cap is below what the mesh holds (n_vertices, n_triangles); the device mesh is built");
+    if (a->xyz && nv > 0) NALO_HIP(c, hipMemcpyAsync(a->xyz, v.mesh_xyz.p, 3 * (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
+    if (a->tri && nt > 0) NALO_HIP(c, hipMemcpyAsync(a->tri, v.mesh_tri.p, 3 * (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((a->xyz && nv > 0) || (a->tri && nt > 0)) NALO_HIP(c, hipStreamSynchronize(c->stream));
+    return NALO_OK;
+}
+
+int nalo_tsdf_mesh_view(nalo_ctx* c, nalo_tsdf_mesh_dev* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_mesh_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh_view: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    if (!v.have_mesh) return fail(c, NALO_ERR_STATE, "nalo_tsdf_mesh_view: no mesh has been built from this volume (nalo_tsdf_mesh)");
+    out->xyz = v.mesh_xyz.p; out->tri = v.mesh_tri.p; out->n_vertices = v.mesh_nv; out->n_triangles = v.mesh_nt;
+    out->stream = (void*)(hipStream_t)c->stream;
     return NALO_OK;
 }

@@ -472,6 +472,16 @@ struct TsdfSurfaceDev {
     float* xyz; long long cap;                                                  // written only when the sum fits
 };
 int tsdf_surface_launch(nalo_ctx* c, const TsdfSurfaceDev& D);                  // count, scan, write on c->stream
+// nalo_tsdf_mesh (kernels_tsdf_mesh.hip, built without FMA contraction): the surface points' work split, kTsdfSurfVoxPerBlock voxels of the sub-box to a workgroup
+struct TsdfMeshDev {
+    const float *tsdf, *weight; int nx, ny, nz, lo[3], size[3], total, nb;      // total: voxels of the sub-box (<= 2^28); nb: its workgroups
+    float origin[3], vs, min_weight;
+    unsigned char* vmask; int* vbase;                                           // [total + 3] each (a lane stores its four at once): a voxel's edges that carry a vertex (bit m - 1), the index of its first vertex
+    int *cntv, *cntt;                                                           // [nb + 1] each: vertices / triangles per workgroup, scanned; [nb] the sums (cntt read as unsigned)
+    float* xyz; int* tri; long long capv, capt;                                 // written only when both sums fit
+};
+int tsdf_mesh_classify_launch(nalo_ctx* c, const TsdfMeshDev& D);               // classify and both scans on c->stream
+int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D);                  // the vertex and the triangle pass
 // nalo_tsdf_integrate_frame's plane: D[v][u] = 1.0f / idepth of the record with the highest position at (u, v), 0 without one. key: w h words, zero between calls.
 // segs is HOST memory: the segments travel as kernel arguments, kTsdfSegsPerLaunch to a launch, so the call stages nothing that a later call could overwrite
 constexpr int kTsdfSegsPerLaunch = 32;

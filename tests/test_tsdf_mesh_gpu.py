@@ -1,0 +1,388 @@
+"""nalo_tsdf_mesh on the device (include/nalo_gpu.h, "The mesh") against tests/tsdf_mesh_model.py. Positions are compared bit for bit (a NaN as a NaN), indices
+and both counts exactly: the definition contains only correctly rounded float operations and integer rules. Volumes are planted through nalo_tsdf_set unless a
+test says otherwise."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import tsdf_mesh_model as mm
+import tsdf_model as tm
+from nalo_slam_amd import binding
+from test_tsdf_cpu import wavy_depth
+from test_tsdf_gpu import GRIDS, H0, K0, POSES, W0, bits_eq, ctx, integrate_both, make, state
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+ERR_ARG, ERR_STATE = -1, -4
+
+
+def grid(dims, origin=(-0.7, 0.3, 1.1), vs=0.125):
+    return dict(origin=origin, vs=vs, dims=dims, trunc=0.4, mw=4.0)
+
+
+def plant(c, vol):
+    c.tsdf_set((0, 0, 0), vol["tsdf"], vol["weight"])
+
+
+def random_field(vol, seed, p_invalid=0.1):
+    """a seeded sign field with a random valid mask; NaN, both zeros and +inf sprinkled in (an infinite t1 against a finite t0 gives s = 0, an infinite t0 a NaN
+    position: both are defined)"""
+    rng = np.random.RandomState(seed)
+    T = rng.uniform(-1, 1, vol["tsdf"].shape).astype(F)
+    flat = T.reshape(-1)
+    for value, step in ((np.nan, 41), (0.0, 43), (-0.0, 47), (np.inf, 53)):
+        flat[rng.randint(0, step)::step] = value
+    vol["tsdf"][:] = T
+    vol["weight"][:] = np.where(rng.rand(*T.shape) < p_invalid, 0.5, rng.randint(1, 4, T.shape)).astype(F)
+    return vol
+
+
+def mesh_once(c, mw, capv, capt, lo=None, size=None, fill=None):
+    """ONE library call with host arrays of the given caps (None: no array): (rc, xyz, tri, n_vertices, n_triangles); the arrays come back whole"""
+    assert capv is None or capv >= 0
+    a = binding.TsdfMeshArgs()
+    if lo is not None:
+        a.use_box = 1
+        a.lo[:] = [int(v) for v in lo]
+        a.size[:] = [int(v) for v in size]
+    a.min_weight = mw
+    xyz = None if capv is None else np.full((max(capv, 1), 3), 0.0 if fill is None else fill, F)      # a cap of 0 still comes with an array
+    tri = None if capt is None else np.full((max(capt, 1), 3), 0 if fill is None else int(fill), np.int32)
+    a.cap_vertices, a.cap_triangles = capv or 0, capt or 0
+    a.xyz = None if xyz is None else xyz.ctypes.data_as(binding.c_fp)
+    a.tri = None if tri is None else tri.ctypes.data_as(binding.c_ip)
+    rc = c.L.nalo_tsdf_mesh(c.h_, C.byref(a))
+    return rc, xyz, tri, int(a.n_vertices), int(a.n_triangles)
+
+
+def mesh_both(c, vol, mw, lo=None, size=None, literal=False, tag=""):
+    xyz, tri = c.tsdf_mesh(mw, lo, size)
+    want = mm.mesh_literal(vol, mw, lo, size)[:2] if literal else mm.mesh(vol, mw, lo, size)
+    assert c.tsdf_mesh_counts == (len(want[0]), len(want[1])), (tag, c.tsdf_mesh_counts, len(want[0]), len(want[1]))
+    assert mm.same_floats(xyz, want[0]) and np.array_equal(tri, want[1]), tag
+    return xyz, tri
+
+
+# ------------------------------------------------------------------------------------------------ one cell
+def cell_volume(pattern, mags):
+    vol = tm.volume((0.25, -0.5, 1.0), 0.5, (2, 2, 2), 0.5, 4.0)
+    vol["weight"][:] = 1.0
+    for b in range(8):
+        vol["tsdf"][(b >> 2) & 1, (b >> 1) & 1, b & 1] = -mags[b] if (pattern >> b) & 1 else mags[b]
+    return vol
+
+
+def one_call_equals_literal(c, vol, mw=1.0):
+    plant(c, vol)
+    rc, xyz, tri, nv, nt = mesh_once(c, mw, 56, 12)
+    wx, wt, _ = mm.mesh_literal(vol, mw)
+    assert rc == 0 and (nv, nt) == (len(wx), len(wt)) and mm.same_floats(xyz[:nv], wx) and np.array_equal(tri[:nt], wt)
+    return nv, nt
+
+
+def test_all_256_sign_patterns_of_one_cell():
+    c = ctx()
+    make(c, dict(origin=(0.25, -0.5, 1.0), vs=0.5, dims=(2, 2, 2), trunc=0.5, mw=4.0))
+    mags = np.array([0.3, 0.9, 0.5, 0.7, 0.2, 0.6, 1.0, 0.4], F)               # eight magnitudes: every cut edge has an s of its own
+    total = 0
+    for pattern in range(256):
+        nv, nt = one_call_equals_literal(c, cell_volume(pattern, mags))
+        assert (nt == 0) == (pattern in (0, 255)) and nt <= 12
+        total += nt
+    # per tetrahedron the 16 masks hold 20 triangles, and a cell's 256 patterns show every mask of every tetrahedron 16 times
+    assert total == 6 * 20 * 16
+    c.close()
+
+
+def test_one_cell_with_a_corner_below_min_weight_or_nan_or_zero():
+    c = ctx()
+    make(c, dict(origin=(0.25, -0.5, 1.0), vs=0.5, dims=(2, 2, 2), trunc=0.5, mw=4.0))
+    mags = np.array([0.3, 0.9, 0.5, 0.7, 0.2, 0.6, 1.0, 0.4], F)
+    kept = 0
+    for pattern in range(256):
+        for b in range(8):
+            vol = cell_volume(pattern, mags)
+            vol["weight"][(b >> 2) & 1, (b >> 1) & 1, b & 1] = np.nextafter(F(1.0), F(0.0))       # just below min_weight = 1
+            nv, nt = one_call_equals_literal(c, vol)
+            assert nt == 0                                                      # the cell is not live; the vertices between valid corners stay
+            kept += nv
+    assert kept > 256 * 8
+    for pattern in (0b01101001, 0b10010110, 0b00001111, 0b00000001, 0b11111110):
+        for b in range(8):
+            for value in (np.nan, 0.0, -0.0):
+                vol = cell_volume(pattern, mags)
+                vol["tsdf"][(b >> 2) & 1, (b >> 1) & 1, b & 1] = value
+                nv, nt = one_call_equals_literal(c, vol)
+                assert not (np.isnan(value) and nt)
+    # an infinite far end: s = t0 / (t0 - inf) is a zero, the vertex sits on v's centre
+    vol = cell_volume(0b00000001, mags)
+    vol["tsdf"][0, 0, 1] = np.inf
+    assert one_call_equals_literal(c, vol) == (7, 6)
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ the work split
+@pytest.mark.parametrize("dims", [(1, 1, 1), (2, 2, 2), (5, 3, 2), (33, 17, 5), (32, 24, 40)])
+def test_seams_of_the_work_split_on_a_random_field(dims):
+    """a lane takes four consecutive voxels, a workgroup 1024: cells and owners either side of every such border, x sizes that are no multiple of four, rows that
+    start inside a lane's four. 33x17x5 is three workgroups, 32x24x40 thirty. The literal model at min_weight 1, the vectorised one (tests/test_tsdf_mesh_cpu.py
+    holds it to the literal one) at 0.5"""
+    c = ctx()
+    g = grid(dims)
+    vol = random_field(make(c, g), sum(dims))
+    plant(c, vol)
+    for mw in (1.0, 0.5):
+        xyz, tri = mesh_both(c, vol, mw, literal=mw == 1.0, tag=(dims, mw))
+        if min(dims) >= 3:
+            assert len(tri) > 100 and np.isnan(xyz).any() and len(np.unique(tri)) < len(xyz)       # triangles, a NaN position, and vertices no triangle names
+    if dims == (32, 24, 40):
+        vx, vt, axis = mm.mesh(vol, 1.0, with_axis=True)
+        assert set(axis.tolist()) == {1, 2, 3, 4, 5, 6, 7} and len(vx) > (1 << 14)               # more than the device mesh's first capacity: the grow path ran
+        # the small sizes again as sub-boxes of this field, where their rows start anywhere in a lane's four and their voxels lie workgroups apart in the grid
+        for lo, size in (((7, 5, 9), (1, 1, 1)), ((29, 21, 37), (2, 2, 2)), ((13, 11, 17), (5, 3, 2)), ((0, 3, 33), (32, 17, 5))):
+            mesh_both(c, vol, 1.0, lo, size, literal=True, tag=(lo, size))
+    c.close()
+
+
+def test_interior_sub_box_at_every_phase_of_its_x_start():
+    """sub-boxes inside the grid with lo[0] mod 4 = 0..3 and sign changes planted beyond every face: nothing across a face appears, indices restart at 0"""
+    c = ctx()
+    g = grid((23, 11, 9))
+    vol = random_field(make(c, g), 5, p_invalid=0.05)
+    plant(c, vol)
+    for phase in range(4):
+        for lo, size in (((4 + phase, 2, 1), (9, 5, 4)), ((phase, 0, 0), (7, 11, 9)), ((8 + phase, 3, 2), (11, 7, 6)), ((12 + phase, 10, 8), (2, 1, 1))):
+            assert lo[0] % 4 == phase
+            xyz, tri = mesh_both(c, vol, 1.0, lo, size, literal=True, tag=(lo, size))
+            assert len(tri) == 0 or (tri.min() >= 0 and tri.max() < len(xyz))
+    # a sign change across every face of a sub-box and none inside it: an empty mesh
+    vol["tsdf"][:], vol["weight"][:] = 1.0, 2.0
+    vol["tsdf"][3:6, 4:8, 6:12] = -0.5
+    plant(c, vol)
+    assert mesh_both(c, vol, 1.0, (6, 4, 3), (6, 4, 3))[0].shape == (0, 3)
+    xyz, tri = mesh_both(c, vol, 1.0, (5, 3, 2), (8, 6, 5))
+    assert mm.is_closed_and_oriented(tri) and mm.signed_volume(xyz, tri) > 0
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ fused volumes, surface points, the sphere
+@pytest.fixture(scope="module")
+def fused():
+    """tests/test_tsdf_gpu.py's two grids after its three poses of a 64x48 depth image: (context, model volume, grid)"""
+    out = []
+    for gi, g in enumerate(GRIDS):
+        c = ctx()
+        vol = make(c, g)
+        for pi, c2w in enumerate(POSES):
+            integrate_both(c, vol, wavy_depth(W0, H0, 10 * gi + pi), K0, c2w, 0.5, 3.5, tag=(gi, pi))
+        out.append((c, vol, g))
+    yield out
+    for c, _, _ in out:
+        c.close()
+
+
+def test_mesh_of_the_fused_volumes(fused):
+    for c, vol, g in fused:
+        xyz, tri = mesh_both(c, vol, 1.0, literal=g["dims"][2] == 5, tag=g["dims"])
+        assert len(tri) > 200 and len(mesh_both(c, vol, 3.0)[1]) < len(tri)
+        nx, ny, nz = g["dims"]
+        mesh_both(c, vol, 1.0, (1, 2, 1), (nx - 3, ny - 5, nz - 2))
+        mesh_both(c, vol, 2.0, (nx - 2, 0, 0), (2, ny, nz))
+        # a fused surface is oriented towards the cameras, which look along +z: the normals' z components are negative on the whole
+        p = xyz.astype(np.float64)
+        n = np.cross(p[tri[:, 1]] - p[tri[:, 0]], p[tri[:, 2]] - p[tri[:, 0]])
+        assert n[:, 2].sum() < 0
+
+
+def test_axis_vertices_are_the_surface_points(fused):
+    cases = [(c, vol, 1.0, None, None) for c, vol, _ in fused] + [(fused[0][0], fused[0][1], 2.0, (3, 1, 2), (21, 17, 30))]
+    c2 = ctx()
+    vol2 = random_field(make(c2, grid((33, 17, 5))), 9)
+    plant(c2, vol2)
+    cases.append((c2, vol2, 1.0, None, None))
+    cases.append((c2, vol2, 0.5, (2, 1, 0), (30, 15, 5)))
+    for c, vol, mw, lo, size in cases:
+        xyz, tri = c.tsdf_mesh(mw, lo, size)
+        axis = mm.mesh(vol, mw, lo, size, with_axis=True)[2]
+        pts = c.tsdf_surface_points(mw, lo, size)
+        sel = xyz[np.isin(axis, (1, 2, 4))]
+        assert len(pts) > 50 and sel.shape == pts.shape and mm.same_floats(sel, pts)
+    c2.close()
+
+
+def test_planted_sphere_is_watertight_and_outward():
+    c = ctx()
+    ref = mm.sphere()
+    g = dict(origin=tuple(float(v) for v in ref["origin"]), vs=float(ref["vs"]), dims=ref["dims"], trunc=1.0, mw=4.0)
+    make(c, g)
+    plant(c, ref)
+    xyz, tri = mesh_both(c, ref, 1.0, literal=True)
+    assert len(tri) > 500 and mm.is_closed_and_oriented(tri)
+    v = mm.signed_volume(xyz, tri)
+    assert v > 0
+    comp = mm.sphere(complement=True)
+    plant(c, comp)
+    cx, ct = mesh_both(c, comp, 1.0)
+    assert mm.is_closed_and_oriented(ct) and abs(mm.signed_volume(cx, ct) + v) < 1e-3 * v
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ buffers and views
+def test_growing_buffers_views_and_repeatability():
+    c = ctx()
+    g = grid((32, 24, 40))
+    vol = random_field(make(c, g), 21)
+    plant(c, vol)
+    big = mm.mesh(vol, 1.0)
+    small_box = ((3, 2, 1), (6, 5, 4))
+    assert len(big[0]) > (1 << 14) and len(big[1]) > (1 << 15)                  # beyond the first capacity of both buffers
+    first = mesh_both(c, vol, 1.0, tag="larger than the first capacity")
+    mesh_both(c, vol, 1.0, *small_box, literal=True, tag="a smaller one")
+    again = mesh_both(c, vol, 1.0, tag="the larger again")
+    assert first[0].tobytes() == again[0].tobytes() and first[1].tobytes() == again[1].tobytes()       # two runs give the same bytes
+    # download=False, then the view's tensors against the downloaded twin
+    assert c.tsdf_mesh(1.0, download=False) == (len(big[0]), len(big[1]))
+    vx, vt = c.tsdf_mesh_view()
+    assert vx.shape == (len(big[0]), 3) and vt.shape == (len(big[1]), 3) and vx.stream == c.L.nalo_stream(c.h_)
+    c.sync()
+    tx, tt = torch.as_tensor(vx, device="cuda"), torch.as_tensor(vt, device="cuda")
+    assert tx.data_ptr() == vx.ptr and tt.data_ptr() == vt.ptr and tx.dtype == torch.float32 and tt.dtype == torch.int32
+    assert mm.same_floats(tx.cpu().numpy(), first[0]) and np.array_equal(tt.cpu().numpy(), first[1])
+    # the view follows the next mesh: the small one's counts, in the same buffers
+    assert c.tsdf_mesh(1.0, *small_box, download=False) == tuple(len(a) for a in mm.mesh(vol, 1.0, *small_box))
+    sx, st = c.tsdf_mesh_view()
+    assert sx.ptr == vx.ptr and sx.shape[0] < vx.shape[0]
+    # only one of the two arrays asked for
+    rc, xyz, tri, nv, nt = mesh_once(c, 1.0, None, len(big[1]))
+    assert rc == 0 and (nv, nt) == (len(big[0]), len(big[1])) and np.array_equal(tri, big[1])
+    rc, xyz, tri, nv, nt = mesh_once(c, 1.0, len(big[0]) + 3, None, fill=7.0)
+    assert rc == 0 and mm.same_floats(xyz[:nv], big[0]) and (xyz[nv:] == 7.0).all()
+    # a fresh context whose FIRST mesh is the large one
+    c2 = ctx()
+    make(c2, g)
+    plant(c2, vol)
+    assert c2.tsdf_mesh(1.0, download=False) == (len(big[0]), len(big[1]))
+    c2.sync()
+    ux, ut = (torch.as_tensor(v, device="cuda").cpu().numpy() for v in c2.tsdf_mesh_view())
+    assert mm.same_floats(ux, big[0]) and np.array_equal(ut, big[1])
+    c2.close()
+    c.close()
+
+
+# ------------------------------------------------------------------------------------------------ the device chain
+def test_three_keyframes_of_the_device_chain_with_a_mesh_after_each(monkeypatch):
+    """tests/test_tsdf_gpu.py's chain (1224x368 into 256x64x256, three keyframes) with nalo_tsdf_mesh after every integration, against the vectorised model of the
+    volume as it stands; a twin that never meshes ends with the same volume and window state"""
+    import test_tsdf_gpu as tg
+    twin = tg.run_chain(True)
+    made, counts = {}, []
+    create, integrate = binding.Context.tsdf_create, binding.Context.tsdf_integrate_frame
+
+    def create_and_note(self, origin, voxel_size, dims, trunc, max_weight):
+        made["vol"] = tm.volume(origin, voxel_size, dims, trunc, max_weight)
+        return create(self, origin, voxel_size, dims, trunc, max_weight)
+
+    def integrate_and_mesh(self, *a, **k):
+        integrate(self, *a, **k)
+        vol = made["vol"]
+        vol["tsdf"], vol["weight"] = self.tsdf_get()
+        xyz, tri = mesh_both(self, vol, 1.0, tag="chain")
+        counts.append((len(xyz), len(tri)))
+
+    monkeypatch.setattr(binding.Context, "tsdf_create", create_and_note)
+    monkeypatch.setattr(binding.Context, "tsdf_integrate_frame", integrate_and_mesh)
+    meshed = tg.run_chain(True)
+    print("TSDF mesh, chain 1224x368 into 256x64x256 (vertices, triangles) per keyframe:", counts)
+    assert len(counts) == 3 and all(nt > 100 for _, nt in counts) and counts[2] != counts[0]
+    assert meshed[0] == twin[0] and meshed[1] == twin[1] and meshed[2] == twin[2]
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def test_refusals_leave_volume_context_and_the_previous_mesh():
+    c = ctx()
+    a = binding.TsdfMeshArgs()
+    a.min_weight = 1.0
+    v = binding.TsdfMeshDev()
+    assert c.L.nalo_tsdf_mesh(c.h_, C.byref(a)) == ERR_STATE and c.L.nalo_tsdf_mesh_view(c.h_, C.byref(v)) == ERR_STATE      # no volume
+    g = GRIDS[1]
+    vol = make(c, g)
+    integrate_both(c, vol, wavy_depth(W0, H0, 30), K0, POSES[0], 0.5, 3.5)
+    with pytest.raises(binding.NaloError, match="nalo error %d:" % ERR_STATE):
+        c.tsdf_mesh_view()                                                      # a volume, but no mesh yet
+    assert c.L.nalo_tsdf_mesh(c.h_, None) == ERR_ARG
+    want = mesh_both(c, vol, 1.0, literal=True)
+    nv, nt = len(want[0]), len(want[1])
+    assert nv > 50 and nt > 50
+
+    def device_mesh():
+        c.sync()
+        return tuple(torch.as_tensor(t, device="cuda").cpu().numpy().tobytes() for t in c.tsdf_mesh_view())
+
+    before, mesh_before = state(c), device_mesh()
+    nx, ny, nz = g["dims"]
+    # refused before anything is queued: both counts 0, the host arrays untouched
+    for kw in (dict(mw=np.nan), dict(lo=(-1, 0, 0), size=(1, 1, 1)), dict(lo=(nx, 0, 0), size=(1, 1, 1)), dict(lo=(0, 0, 0), size=(nx + 1, 1, 1)), dict(lo=(0, 0, 0), size=(1, 0, 1)),
+               dict(lo=(0, ny - 1, 0), size=(1, 2, 1)), dict(lo=(0, 0, nz - 1), size=(1, 1, 2))):
+        rc, xyz, tri, n1, n2 = mesh_once(c, kw.get("mw", 1.0), nv, nt, kw.get("lo"), kw.get("size"), fill=9.0)
+        assert rc == ERR_ARG and (n1, n2) == (0, 0) and (xyz == 9.0).all() and (tri == 9).all(), kw
+    for field, value in (("cap_vertices", -1), ("cap_triangles", -1), ("cap_vertices", 5), ("cap_triangles", 5)):      # a negative cap; a cap without an array
+        b = binding.TsdfMeshArgs()
+        b.min_weight = 1.0
+        setattr(b, field, value)
+        assert c.L.nalo_tsdf_mesh(c.h_, C.byref(b)) == ERR_ARG and (b.n_vertices, b.n_triangles) == (0, 0)
+    assert state(c) == before and device_mesh() == mesh_before
+    # caps one below each count: refused behind the scans with both counts reported, the sentinel-filled arrays intact
+    for capv, capt in ((nv - 1, nt), (nv, nt - 1), (nv - 1, nt - 1), (0, nt), (nv, 0)):
+        rc, xyz, tri, n1, n2 = mesh_once(c, 1.0, capv, capt, fill=9.0)
+        assert rc == ERR_ARG and (n1, n2) == (nv, nt) and (xyz == 9.0).all() and (tri == 9).all(), (capv, capt)
+        assert state(c) == before and device_mesh() == mesh_before               # the mesh the call built is the same mesh
+    with pytest.raises(binding.NaloError, match="nalo error %d:" % ERR_ARG):
+        c.tsdf_mesh(1.0, (0, 0, 0), (nx + 1, ny, nz))
+    assert c.tsdf_mesh_counts == (0, 0)
+    # exactly enough is taken; the next legal calls are correct
+    rc, xyz, tri, n1, n2 = mesh_once(c, 1.0, nv, nt)
+    assert rc == 0 and mm.same_floats(xyz, want[0]) and np.array_equal(tri, want[1])
+    mesh_both(c, vol, 2.0, (1, 1, 0), (20, 9, 5), literal=True)
+    assert state(c) == before
+    integrate_both(c, vol, wavy_depth(W0, H0, 31), K0, POSES[1], 0.5, 3.5)
+    mesh_both(c, vol, 1.0, literal=True)
+    # a new volume has no mesh; neither has a context after nalo_tsdf_destroy
+    make(c, GRIDS[0])
+    with pytest.raises(binding.NaloError, match="nalo error %d:" % ERR_STATE):
+        c.tsdf_mesh_view()
+    c.tsdf_destroy()
+    assert c.L.nalo_tsdf_mesh(c.h_, C.byref(a)) == ERR_STATE
+    c.close()
+
+
+def test_a_volume_above_2_to_the_28_voxels_is_refused_whole_and_meshed_in_part():
+    c = ctx()
+    dims, vs = (1024, 512, 514), F(0.01)
+    assert dims[0] * dims[1] * dims[2] > (1 << 28)
+    c.tsdf_create((0.0, 0.0, 0.0), vs, dims, 0.05, 4.0)
+    rc, xyz, tri, nv, nt = mesh_once(c, 0.0, 4, 4, fill=9.0)
+    assert rc == ERR_ARG and (nv, nt) == (0, 0) and (xyz == 9.0).all() and (tri == 9).all()
+    with pytest.raises(binding.NaloError, match="nalo error %d:" % ERR_STATE):
+        c.tsdf_mesh_view()
+    assert c.tsdf_mesh(0.0, (0, 0, 0), (1024, 512, 512), download=False) == (0, 0)      # exactly 2^28 voxels is legal; the initial values hold nothing to cut
+    # a block planted in the far corner of the grid, linear indices beyond 2^28: the whole grid is still refused, the block as a sub-box is the model's mesh
+    corner = random_field(tm.volume((0.0, 0.0, 0.0), vs, (9, 6, 5), 0.05, 4.0), 3)
+    lo = (1015, 506, 509)
+    c.tsdf_set(lo, corner["tsdf"], corner["weight"])
+    assert mesh_once(c, 1.0, 4, 4)[0] == ERR_ARG
+    t, w = c.tsdf_get(lo, (9, 6, 5))
+    assert bits_eq(t, corner["tsdf"]) and bits_eq(w, corner["weight"])
+    xyz, tri = c.tsdf_mesh(1.0, lo, (9, 6, 5))
+    wx, wt, owner = mm.mesh_literal(corner, 1.0)
+    assert len(wt) > 20 and np.array_equal(tri, wt) and len(xyz) == len(wx)
+    cs = [F(0.0) + (np.arange(n, dtype=F) + F(0.5)) * vs for n in dims]        # the centres where the block lies
+    for p, (i, j, k, m) in zip(xyz, owner):
+        t0, t1 = corner["tsdf"][k, j, i], corner["tsdf"][k + ((m >> 2) & 1), j + ((m >> 1) & 1), i + (m & 1)]
+        with np.errstate(all="ignore"):
+            prod = vs * (t0 / (t0 - t1))
+            q = [cs[0][lo[0] + i], cs[1][lo[1] + j], cs[2][lo[2] + k]]
+            q = [q[a] + prod if (m >> a) & 1 else q[a] for a in range(3)]
+        assert mm.same_floats(np.array(q, F), p)
+    c.close()
