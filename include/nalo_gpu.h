@@ -1476,8 +1476,9 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
 /* ------------------------------------------------------------------------------------------------
  * tsdf=1: the dense map fused into a TSDF volume on the device. The reference constructs a cpu_tsdf::TSDFVolumeOctree (FullSystem.cpp:192-198), saves a point
  * file "for tsdf" (SampleOutputWrapper.h:150-176, nalo_map_dense_world_points here) and leaves the fusion to a third-party tool it neither vendors nor pins. This
- * section is a DEFINED operation instead: a projective integration of one depth image into a dense voxel volume that lives in the context. No colour
- * (setIntegrateColor(false)), no octree, no de-integration; nalo_ba_snapshot / nalo_ba_restore do not include the volume.
+ * section is a DEFINED operation instead: a projective integration of one depth image into a dense voxel volume that lives in the context. Colour is opt-in
+ * ("Colour" below; the reference's switch is tsdf->setIntegrateColor, FullSystem.cpp:195). No octree, no de-integration; nalo_ba_snapshot / nalo_ba_restore do
+ * not include the volume.
  *
  * nalo_tsdf_create   origin: world position of the CORNER of voxel (0,0,0); dims = {nx, ny, nz}. Storage: two contiguous F32 arrays [nz][ny][nx], x fastest;
  *                    tsdf starts at 1.0f, weight at 0.0f. NALO_ERR_ARG: a dimension outside [1, 2048], nx ny nz above 2^29, voxel_size / trunc / max_weight not
@@ -1558,6 +1559,39 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    of a view": good until the next nalo_tsdf_mesh, nalo_tsdf_create, nalo_tsdf_destroy or nalo_destroy. NALO_ERR_STATE before the first mesh.
  * nalo_tsdf_mesh_table  host only, needs no context: the table the kernels use, built from the rules above at compile time. For tetrahedron t and mask the six
  *                    entries are the vertices of up to two triangles in output order, each coded 8 p + (q ^ p), -1 as padding; 120 triangles in all.
+ *
+ * Colour. Opt-in: a context that never calls nalo_tsdf_color_enable queues what it queued before and produces the same bits. Everything in float, no FMA
+ * contraction, each operation rounded once; no float atomic, the same bytes on every run.
+ * nalo_tsdf_color_enable   three contiguous F32 arrays [3][nz][ny][nx], the planes in B, G, R order (as the slots store colour), each laid out as tsdf; they start
+ *                    at 0.0f. NALO_ERR_STATE without a volume; already enabled: NALO_OK and nothing changes; a failed allocation (NALO_ERR_HIP) leaves volume
+ *                    and context as they were. Enable BEFORE the first integration if the colour is to be the average of every observation: enabling later is
+ *                    legal, and the running average then starts from 0 under the weight that is already there (the first colours are pulled towards black).
+ * nalo_tsdf_color_disable  frees the planes (it waits for the main stream first); not enabled: NALO_OK. nalo_tsdf_reset sets them to 0.0f; nalo_tsdf_create
+ *                    replaces the volume WITHOUT colour; nalo_tsdf_destroy and nalo_destroy free them.
+ * nalo_tsdf_integrate_depth_color   nalo_tsdf_integrate_depth, and at every voxel its definition updates, with (pu, pv) that voxel's pixel, w0 the weight BEFORE
+ *                    this update and (b, g, r) the colour bytes at the pixel, for each plane X with byte x:   X = (X0 * w0 + (float)x) / (w0 + 1.0f).
+ *                    A voxel the definition does not update keeps its three words bit for bit. colour: U8, three channels, exactly the depth plane's w x h, any
+ *                    strides nalo_dev_plane_check accepts (HWC, CHW, pitched, x-strided); colour_is_rgb: channel 0 is R. NALO_ERR_ARG otherwise, also for a
+ *                    NULL colour; NALO_ERR_STATE without colour enabled; the refusals of nalo_tsdf_integrate_depth are unchanged and a refused call queues
+ *                    nothing. Stream order and nalo_tsdf_release as there: producer_stream produces both planes, and the recorded event lies behind the one
+ *                    kernel that reads either. The colour of a lane's four voxels is loaded and stored only where tsdf and weight are stored.
+ *                    nalo_tsdf_integrate_depth on a coloured volume stays legal: it updates tsdf and weight and leaves the colour untouched, so the average
+ *                    counts that observation as one more of the colour the voxel already holds: its weight grows, its colour does not move.
+ *                    nalo_tsdf_integrate_frame on a coloured volume integrates colour too: the colour at (u, v) is the bgr of the same LAST record that
+ *                    supplies idepth, (0, 0, 0) where there is none (this shows when min_depth <= 0 makes D = 0 usable), settled by the same integer key.
+ * nalo_tsdf_color_get / nalo_tsdf_color_set   the sub-block [lo, lo + size) as [3][size[2]][size[1]][size[0]] floats, planes B, G, R, bit for bit (NaN payloads
+ *                    pass). Refusals as nalo_tsdf_get / nalo_tsdf_set, and NALO_ERR_STATE without colour. Synchronous.
+ * nalo_tsdf_color_view   host code only, launches nothing: the pointer of the [3][nz][ny][nx] block, the dimensions and the producing stream, under "Lifetime of
+ *                    a view": good until nalo_tsdf_color_disable / nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy. NALO_ERR_STATE without colour.
+ * nalo_tsdf_mesh_color   everything nalo_tsdf_mesh does - the same definition, order, counts, growth protocol and refusals - and one colour per vertex, in vertex
+ *                    order, into a context-owned device buffer [n_vertices][4] of bytes that grows with xyz. For the vertex on edge (v, m) with far end n and the
+ *                    s = t0 / (t0 - t1) of its position, per plane:   cX = X(v) + s * (X(n) - X(v));   byte = (uint8)(int)(fminf(fmaxf(cX, 0.0f), 255.0f) + 0.5f).
+ *                    A NaN gives 0 through fmaxf (a NaN s from an infinite corner among them). The four bytes are R, G, B, 255: one aligned store per vertex,
+ *                    written by the vertex pass. NALO_ERR_STATE without colour. NALO_ERR_ARG, with nothing written to ANY host array: a NULL argument, a
+ *                    negative cap, cap > 0 with a NULL rgba, and an rgba that is given with cap below n_vertices (known behind the scans: the device mesh is
+ *                    built and the counts are set, as for xyz).
+ * nalo_tsdf_mesh_color_view   host code only, launches nothing: the device colours of the last mesh. NALO_ERR_STATE unless the LAST mesh call was
+ *                    nalo_tsdf_mesh_color: a plain nalo_tsdf_mesh afterwards invalidates it. nalo_tsdf_mesh_view keeps working after either.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1598,6 +1632,17 @@ typedef struct nalo_tsdf_mesh_dev { float* xyz; int* tri; long long n_vertices, 
 int nalo_tsdf_mesh(nalo_ctx* ctx, nalo_tsdf_mesh_args* args);
 int nalo_tsdf_mesh_view(nalo_ctx* ctx, nalo_tsdf_mesh_dev* out);     /* host only, launches nothing */
 int nalo_tsdf_mesh_table(signed char out[6][16][6]);                 /* host only, no context */
+typedef struct nalo_tsdf_color_volume_view { float* bgr; int dims[3]; void* stream; } nalo_tsdf_color_volume_view;   /* bgr: [3][nz][ny][nx] */
+typedef struct nalo_tsdf_mesh_color_args { long long cap; uint8_t* rgba; } nalo_tsdf_mesh_color_args;               /* host, [cap][4]; NULL: leave the colours on the device */
+typedef struct nalo_tsdf_mesh_color_dev { uint8_t* rgba; long long n_vertices; void* stream; } nalo_tsdf_mesh_color_dev;
+int nalo_tsdf_color_enable(nalo_ctx* ctx);
+int nalo_tsdf_color_disable(nalo_ctx* ctx);
+int nalo_tsdf_integrate_depth_color(nalo_ctx* ctx, const nalo_tsdf_integrate_args* args, const nalo_dev_plane* colour, int colour_is_rgb);
+int nalo_tsdf_color_get(nalo_ctx* ctx, const int lo[3], const int size[3], float* bgr);
+int nalo_tsdf_color_set(nalo_ctx* ctx, const int lo[3], const int size[3], const float* bgr);
+int nalo_tsdf_color_view(nalo_ctx* ctx, nalo_tsdf_color_volume_view* out);   /* host only, launches nothing */
+int nalo_tsdf_mesh_color(nalo_ctx* ctx, nalo_tsdf_mesh_args* args, nalo_tsdf_mesh_color_args* colour);
+int nalo_tsdf_mesh_color_view(nalo_ctx* ctx, nalo_tsdf_mesh_color_dev* out); /* host only, launches nothing */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",

@@ -14,6 +14,13 @@ extern "C" {
  * count, a missing array, an index outside [0, nv). NALO_IO_ERR_FILE for a path that cannot be written. */
 int nalo_io_write_ply_mesh(const char* path, long long nv, const float* xyz, long long nt, const int* tri);
 
+/* the coloured mesh of nalo_tsdf_mesh_color: the same file with `property uchar red|green|blue|alpha` behind z, so that a vertex is 12 + 4 bytes (rgba:
+ * [nv][4] bytes, R, G, B, A as that call writes them); faces as above. The header, byte for byte:
+ *   "ply\nformat binary_little_endian 1.0\nelement vertex <nv>\nproperty float x\nproperty float y\nproperty float z\nproperty uchar red\n
+ *    property uchar green\nproperty uchar blue\nproperty uchar alpha\nelement face <nt>\nproperty list uchar int vertex_indices\nend_header\n"
+ * Refusals as nalo_io_write_ply_mesh, and NALO_IO_ERR_ARG for a NULL rgba with nv > 0. */
+int nalo_io_write_ply_mesh_rgba(const char* path, long long nv, const float* xyz, const unsigned char* rgba, long long nt, const int* tri);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ EXPORTS = [
     "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
+    "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -191,6 +192,18 @@ class TsdfMeshDev(C.Structure):                           # nalo_tsdf_mesh_dev
     _fields_ = [("xyz", C.c_void_p), ("tri", C.c_void_p), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong), ("stream", C.c_void_p)]
 
 
+class TsdfColorVolumeView(C.Structure):                   # nalo_tsdf_color_volume_view
+    _fields_ = [("bgr", C.c_void_p), ("dims", C.c_int * 3), ("stream", C.c_void_p)]
+
+
+class TsdfMeshColorArgs(C.Structure):                     # nalo_tsdf_mesh_color_args
+    _fields_ = [("cap", C.c_longlong), ("rgba", c_u8p)]
+
+
+class TsdfMeshColorDev(C.Structure):                      # nalo_tsdf_mesh_color_dev
+    _fields_ = [("rgba", C.c_void_p), ("n_vertices", C.c_longlong), ("stream", C.c_void_p)]
+
+
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
@@ -286,6 +299,7 @@ def host_lib():
         L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
         L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
+        L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
         _HOST_LIB = L
     return _HOST_LIB
 
@@ -343,12 +357,19 @@ def tsdf_mesh_table():
     return out
 
 
-def write_ply_mesh(path, xyz, tri):
-    """nalo_io_write_ply_mesh: xyz float32 [nv][3] and tri int32 [nt][3] as a binary little-endian PLY file; needs no device"""
+def write_ply_mesh(path, xyz, tri, rgba=None):
+    """nalo_io_write_ply_mesh: xyz float32 [nv][3] and tri int32 [nt][3] as a binary little-endian PLY file; with rgba (uint8 [nv][4], tsdf_mesh's colours)
+    nalo_io_write_ply_mesh_rgba: the same file with red, green, blue, alpha behind every vertex. Needs no device"""
     x, t = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3), np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
-    rc = host_lib().nalo_io_write_ply_mesh(os.fsencode(path), len(x), _f(x), len(t), _i(t))
+    if rgba is None:
+        rc, who = host_lib().nalo_io_write_ply_mesh(os.fsencode(path), len(x), _f(x), len(t), _i(t)), "nalo_io_write_ply_mesh"
+    else:
+        c = np.ascontiguousarray(rgba, np.uint8).reshape(-1, 4)
+        if len(c) != len(x):
+            raise NaloError("write_ply_mesh: rgba holds %d colours for %d vertices" % (len(c), len(x)))
+        rc, who = host_lib().nalo_io_write_ply_mesh_rgba(os.fsencode(path), len(x), _f(x), _u8(c), len(t), _i(t)), "nalo_io_write_ply_mesh_rgba"
     if rc != 0:
-        raise NaloError("nalo_io_write_ply_mesh: error %d (-1: an index outside the vertices, -2: the file cannot be written)" % rc)
+        raise NaloError("%s: error %d (-1: an index outside the vertices, -2: the file cannot be written)" % (who, rc))
 
 
 def _ground_argtypes(L):
@@ -525,6 +546,14 @@ def load():
     L.nalo_tsdf_mesh.argtypes = [vp, C.POINTER(TsdfMeshArgs)]
     L.nalo_tsdf_mesh_view.argtypes = [vp, C.POINTER(TsdfMeshDev)]
     L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
+    L.nalo_tsdf_color_enable.argtypes = [vp]
+    L.nalo_tsdf_color_disable.argtypes = [vp]
+    L.nalo_tsdf_integrate_depth_color.argtypes = [vp, C.POINTER(TsdfIntegrateArgs), C.POINTER(DevPlane), C.c_int]
+    L.nalo_tsdf_color_get.argtypes = [vp, c_ip, c_ip, c_fp]
+    L.nalo_tsdf_color_set.argtypes = [vp, c_ip, c_ip, c_fp]
+    L.nalo_tsdf_color_view.argtypes = [vp, C.POINTER(TsdfColorVolumeView)]
+    L.nalo_tsdf_mesh_color.argtypes = [vp, C.POINTER(TsdfMeshArgs), C.POINTER(TsdfMeshColorArgs)]
+    L.nalo_tsdf_mesh_color_view.argtypes = [vp, C.POINTER(TsdfMeshColorDev)]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
@@ -1497,10 +1526,42 @@ class Context:
     def tsdf_destroy(self):
         self._ck(self.L.nalo_tsdf_destroy(self.h_))
 
-    def tsdf_integrate_depth(self, depth, K, cam_to_world, min_depth, max_depth, stream=None, release=True):
+    def tsdf_color_enable(self):
+        """nalo_tsdf_color_enable: three float32 planes [3][nz][ny][nx] (B, G, R) at 0.0 next to the volume; enable before the first integration if the colour is to
+        be the average of every observation"""
+        self._ck(self.L.nalo_tsdf_color_enable(self.h_))
+
+    def tsdf_color_disable(self):
+        self._ck(self.L.nalo_tsdf_color_disable(self.h_))
+
+    def tsdf_color_get(self, lo=None, size=None):
+        """nalo_tsdf_color_get -> float32 [3][sz][sy][sx] (planes B, G, R) of the sub-block [lo, lo + size); the whole grid by default"""
+        lo_a = np.zeros(3, np.int32) if lo is None else np.ascontiguousarray(lo, np.int32)
+        size_a = np.asarray(self.tsdf_dims, np.int32) if size is None else np.ascontiguousarray(size, np.int32)
+        out = np.zeros((3,) + tuple(max(int(v), 0) for v in size_a[::-1]), np.float32)
+        self._ck(self.L.nalo_tsdf_color_get(self.h_, _i(lo_a), _i(size_a), _f(out)))
+        return out
+
+    def tsdf_color_set(self, lo, bgr):
+        """nalo_tsdf_color_set: a float32 block [3][sz][sy][sx] written at lo, bit for bit"""
+        b = np.ascontiguousarray(bgr, np.float32)
+        if b.ndim != 4 or b.shape[0] != 3:
+            raise NaloError("tsdf_color_set: bgr is a [3][sz][sy][sx] block")
+        lo_a, size_a = np.ascontiguousarray(lo, np.int32), np.asarray(b.shape[:0:-1], np.int32)
+        self._ck(self.L.nalo_tsdf_color_set(self.h_, _i(lo_a), _i(size_a), _f(b)))
+
+    def tsdf_color_view(self):
+        """nalo_tsdf_color_view -> a DeviceView of shape [3, nz, ny, nx] (planes B, G, R): torch.as_tensor(view, device="cuda") is a zero-copy tensor. Launches
+        nothing."""
+        v = TsdfColorVolumeView()
+        self._ck(self.L.nalo_tsdf_color_view(self.h_, C.byref(v)))
+        return DeviceView(v.bgr, (3, v.dims[2], v.dims[1], v.dims[0]), "<f4", None, v.stream, self)
+
+    def tsdf_integrate_depth(self, depth, K, cam_to_world, min_depth, max_depth, stream=None, release=True, colour=None, colour_is_rgb=False):
         """nalo_tsdf_integrate_depth: depth is a 2-D float32 device array (anything with __cuda_array_interface__, or a DevPlane), read where it lies through its
         strides; K = (fx, fy, cx, cy) for ITS size. stream / release as frame_ingest: the producing hipStream_t (None: torch's current stream of a tensor, a
-        DeviceView's own, else the null stream), and whether that stream waits on the device until the plane has been read. Returns without waiting."""
+        DeviceView's own, else the null stream), and whether that stream waits on the device until the plane has been read. Returns without waiting.
+        colour (a uint8 device array [h][w][3], or a DevPlane of three channels) routes to nalo_tsdf_integrate_depth_color; colour_is_rgb: channel 0 is R."""
         a = TsdfIntegrateArgs()
         a.depth = depth if isinstance(depth, DevPlane) else dev_plane(depth)
         if stream is None:
@@ -1513,7 +1574,11 @@ class Context:
         a.K[:] = [float(v) for v in K]
         a.camToWorld[:] = [float(v) for v in np.asarray(cam_to_world, np.float64).reshape(-1)]
         a.min_depth, a.max_depth, a.producer_stream = float(min_depth), float(max_depth), stream or None
-        self._ck(self.L.nalo_tsdf_integrate_depth(self.h_, C.byref(a)))
+        if colour is None:
+            self._ck(self.L.nalo_tsdf_integrate_depth(self.h_, C.byref(a)))
+        else:
+            cp = colour if isinstance(colour, DevPlane) else dev_plane(colour, "hwc")
+            self._ck(self.L.nalo_tsdf_integrate_depth_color(self.h_, C.byref(a), C.byref(cp), int(bool(colour_is_rgb))))
         if release:
             self.tsdf_release(stream)
 
@@ -1585,31 +1650,34 @@ class Context:
         self._ck(rc)
         return xyz[:int(a.n)].copy()
 
-    def tsdf_mesh(self, min_weight, lo=None, size=None, download=True):
+    def tsdf_mesh(self, min_weight, lo=None, size=None, download=True, colour=False):
         """nalo_tsdf_mesh -> (xyz float32 [nv][3], tri int32 [nt][3]): the marching-tetrahedra mesh of the sub-box [lo, lo + size) or of the whole grid, in the
         header's order. The mesh is always built on the device (tsdf_mesh_view); download=False returns the counts (nv, nt) only, after one library call and one
         wait. With the download the arrays are sized from that call's counts and a second call fills them. self.tsdf_mesh_counts holds the counts of the last
-        call, a refusal included"""
+        call, a refusal included. colour=True: nalo_tsdf_mesh_color -> (xyz, tri, rgba uint8 [nv][4]), the colours on the device under tsdf_mesh_color_view"""
+        cc = TsdfMeshColorArgs()
+        call = (lambda a: self.L.nalo_tsdf_mesh_color(self.h_, C.byref(a), C.byref(cc))) if colour else (lambda a: self.L.nalo_tsdf_mesh(self.h_, C.byref(a)))
         a = TsdfMeshArgs()
         if lo is not None:
             a.use_box = 1
             a.lo[:] = [int(v) for v in lo]
             a.size[:] = [int(v) for v in size]
         a.min_weight = float(min_weight)
-        rc = self.L.nalo_tsdf_mesh(self.h_, C.byref(a))
+        rc = call(a)
         self.tsdf_mesh_counts = (int(a.n_vertices), int(a.n_triangles))
         self._ck(rc)
         if not download:
             return self.tsdf_mesh_counts
         nv, nt = self.tsdf_mesh_counts
-        xyz, tri = np.zeros((nv, 3), np.float32), np.zeros((nt, 3), np.int32)
+        xyz, tri, rgba = np.zeros((nv, 3), np.float32), np.zeros((nt, 3), np.int32), np.zeros((nv, 4), np.uint8)
         if nv == 0 and nt == 0:
-            return xyz, tri
+            return (xyz, tri, rgba) if colour else (xyz, tri)
         a.cap_vertices, a.cap_triangles, a.xyz, a.tri = nv, nt, (_f(xyz) if nv else None), (_i(tri) if nt else None)
-        rc = self.L.nalo_tsdf_mesh(self.h_, C.byref(a))
+        cc.cap, cc.rgba = nv, (_u8(rgba) if nv else None)
+        rc = call(a)
         self.tsdf_mesh_counts = (int(a.n_vertices), int(a.n_triangles))
         self._ck(rc)
-        return xyz, tri
+        return (xyz, tri, rgba) if colour else (xyz, tri)
 
     def tsdf_mesh_view(self):
         """nalo_tsdf_mesh_view -> (xyz, tri) as DeviceViews of shape [nv, 3] float32 and [nt, 3] int32: torch.as_tensor(view, device="cuda") is a zero-copy
@@ -1617,6 +1685,13 @@ class Context:
         v = TsdfMeshDev()
         self._ck(self.L.nalo_tsdf_mesh_view(self.h_, C.byref(v)))
         return DeviceView(v.xyz, (v.n_vertices, 3), "<f4", None, v.stream, self), DeviceView(v.tri, (v.n_triangles, 3), "<i4", None, v.stream, self)
+
+    def tsdf_mesh_color_view(self):
+        """nalo_tsdf_mesh_color_view -> a DeviceView of shape [nv, 4] uint8 (R, G, B, 255): the colours of the device mesh the last tsdf_mesh(colour=True) built.
+        Launches nothing; a plain tsdf_mesh afterwards invalidates it."""
+        v = TsdfMeshColorDev()
+        self._ck(self.L.nalo_tsdf_mesh_color_view(self.h_, C.byref(v)))
+        return DeviceView(v.rgba, (v.n_vertices, 4), "|u1", None, v.stream, self)
 
     def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
         """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes

@@ -72,22 +72,27 @@ int nalo_io_write_pcd_points(const char* path, int append, int n, const float* u
     return f.fail() ? NALO_IO_ERR_FILE : NALO_IO_OK;
 }
 
-int nalo_io_write_ply_mesh(const char* path, long long nv, const float* xyz, long long nt, const int* tri) {
-    if (!path || nv < 0 || nt < 0 || (nv > 0 && !xyz) || (nt > 0 && !tri)) return NALO_IO_ERR_ARG;
+// nalo_io_write_ply_mesh (coloured = false; rgba is not looked at) and nalo_io_write_ply_mesh_rgba
+static int write_ply_mesh(const char* path, long long nv, const float* xyz, bool coloured, const uint8_t* rgba, long long nt, const int* tri) {
+    if (!path || nv < 0 || nt < 0 || (nv > 0 && !xyz) || (nt > 0 && !tri) || (coloured && nv > 0 && !rgba)) return NALO_IO_ERR_ARG;
     for (long long k = 0; k < 3 * nt; ++k) if (tri[k] < 0 || tri[k] >= nv) return NALO_IO_ERR_ARG;      // before the file is opened: a refused mesh leaves no file behind
     std::ofstream f(path, std::ios::binary | std::ios::trunc);
     if (!f.good()) return NALO_IO_ERR_FILE;
-    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv << "\nproperty float x\nproperty float y\nproperty float z\nelement face " << nt
+    f << "ply\nformat binary_little_endian 1.0\nelement vertex " << nv << "\nproperty float x\nproperty float y\nproperty float z\n"
+      << (coloured ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "") << "element face " << nt
       << "\nproperty list uchar int vertex_indices\nend_header\n";
     // the values byte by byte, least significant first, whatever the host's own order is
     std::vector<char> buf;
     buf.reserve(1 << 16);
     auto put32 = [&](uint32_t u) { for (int b = 0; b < 4; ++b) buf.push_back((char)((u >> (8 * b)) & 0xFFu)); };
     auto flush = [&]() { f.write(buf.data(), (std::streamsize)buf.size()); buf.clear(); };
-    for (long long k = 0; k < 3 * nv; ++k) {
-        uint32_t u;
-        std::memcpy(&u, xyz + k, 4);
-        put32(u);
+    for (long long k = 0; k < nv; ++k) {
+        for (int a = 0; a < 3; ++a) {
+            uint32_t u;
+            std::memcpy(&u, xyz + 3 * k + a, 4);
+            put32(u);
+        }
+        if (coloured) for (int a = 0; a < 4; ++a) buf.push_back((char)rgba[4 * k + a]);
         if (buf.size() >= (1 << 16) - 16) flush();
     }
     for (long long t = 0; t < nt; ++t) {
@@ -98,6 +103,10 @@ int nalo_io_write_ply_mesh(const char* path, long long nv, const float* xyz, lon
     flush();
     f.close();
     return f.fail() ? NALO_IO_ERR_FILE : NALO_IO_OK;
+}
+int nalo_io_write_ply_mesh(const char* path, long long nv, const float* xyz, long long nt, const int* tri) { return write_ply_mesh(path, nv, xyz, false, nullptr, nt, tri); }
+int nalo_io_write_ply_mesh_rgba(const char* path, long long nv, const float* xyz, const uint8_t* rgba, long long nt, const int* tri) {
+    return write_ply_mesh(path, nv, xyz, true, rgba, nt, tri);
 }
 
 

@@ -25,7 +25,13 @@ struct TsdfVolume {
     DevBuf<unsigned char> mesh_mask; DevBuf<int> mesh_base, mesh_cntv, mesh_cntt; HostBuf<int> mesh_cnt_h;
     DevBuf<float> mesh_xyz; DevBuf<int> mesh_tri;
     long long mesh_nv = 0, mesh_nt = 0; bool have_mesh = false;
+    // colour (nalo_tsdf_color_enable): [3][nz][ny][nx], planes B, G, R; no memory while colour is off. cplane: nalo_tsdf_integrate_frame's packed colour plane, w h
+    // words; mesh_rgba: one word per vertex of the device mesh, as many as mesh_xyz has room for; mesh_coloured: the last mesh call wrote it
+    DevBuf<float> colour; DevBuf<unsigned> cplane, mesh_rgba; bool mesh_coloured = false;
 };
+
+// a caller's colour plane as the integration kernel reads it: byte strides, sc[X] the offset of the channel that feeds plane X (B, G, R)
+struct TsdfColourSrc { const unsigned char* p; long long sy, sx, sc[3]; };
 
 constexpr long long kTsdfMeshMaxVoxels = 1LL << 28;                               // seven vertices a voxel must fit an int index
 constexpr long long kTsdfMeshFirstVertices = 1LL << 14, kTsdfMeshFirstTriangles = 1LL << 15;   // the device mesh's first capacity; it grows to what a call finds plus a quarter
@@ -52,7 +58,7 @@ static int tsdf_integrate_check(nalo_ctx* c, const char* who, const TsdfVolume& 
 
 // everything is validated: zero the count, the kernel over the box, the call's record for nalo_tsdf_last. Enqueues only.
 static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth, long long sy, long long sx, int w, int h, const float K[4], const float M[12], float min_depth,
-                                  float max_depth, const int lo[3], const int hi[3]) {
+                                  float max_depth, const int lo[3], const int hi[3], const TsdfColourSrc* colour = nullptr) {
     NALO_HIP(c, hipMemsetAsync(v.updated.p, 0, sizeof(unsigned long long), c->stream));
     nalo_tsdf_stats st{};
     if (hi[0] > lo[0]) {
@@ -63,6 +69,11 @@ static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth,
         std::copy(M, M + 12, D.M);
         D.fx = K[0]; D.fy = K[1]; D.cx = K[2]; D.cy = K[3]; D.min_depth = min_depth; D.max_depth = max_depth;
         D.depth = depth; D.sy = sy; D.sx = sx; D.w = w; D.h = h; D.updated = v.updated.p;
+        if (colour) {
+            D.col = v.colour.p; D.col_plane = v.n;
+            D.colour = colour->p; D.csy = colour->sy; D.csx = colour->sx;
+            for (int X = 0; X < 3; ++X) D.csc[X] = colour->sc[X];
+        }
         st.visited = (long long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
         const int rc = tsdf_integrate_launch(c, D); if (rc) return rc;
     }
@@ -97,7 +108,31 @@ int nalo_tsdf_reset(nalo_ctx* c) {
     { const int rc = tsdf_need(c, "nalo_tsdf_reset"); if (rc) return rc; }
     NALO_HIP(c, hipSetDevice(c->device));
     c->tsdf->have_last = false;
+    if (c->tsdf->colour.p) NALO_HIP(c, hipMemsetAsync(c->tsdf->colour.p, 0, 3 * c->tsdf->n * sizeof(float), c->stream));      // 0.0f is all bits zero
     return tsdf_fill_launch(c, c->tsdf->tsdf.p, c->tsdf->weight.p, c->tsdf->n);
+}
+
+int nalo_tsdf_color_enable(nalo_ctx* c) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_color_enable"); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (v.colour.p) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    DevBuf<float> col;
+    const hipError_t e = col.reserve(3 * v.n);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_color_enable: ") + hipGetErrorString(e)); }
+    NALO_HIP(c, hipMemsetAsync(col.p, 0, 3 * v.n * sizeof(float), c->stream));
+    v.colour = std::move(col);
+    return NALO_OK;
+}
+
+int nalo_tsdf_color_disable(nalo_ctx* c) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_color_disable"); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (!v.colour.p) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                              // kernels that name the planes may still be queued
+    v.colour.release(); v.cplane.release(); v.mesh_rgba.release(); v.mesh_coloured = false;
+    return NALO_OK;
 }
 
 int nalo_tsdf_destroy(nalo_ctx* c) {
@@ -109,14 +144,24 @@ int nalo_tsdf_destroy(nalo_ctx* c) {
     return NALO_OK;
 }
 
-int nalo_tsdf_integrate_depth(nalo_ctx* c, const nalo_tsdf_integrate_args* a) {
-    const char* who = "nalo_tsdf_integrate_depth";
+// nalo_tsdf_integrate_depth (coloured = false; colour is not looked at) and nalo_tsdf_integrate_depth_color
+static int tsdf_integrate_depth(nalo_ctx* c, const char* who, const nalo_tsdf_integrate_args* a, bool coloured, const nalo_dev_plane* colour, int colour_is_rgb) {
     { const int rc = tsdf_need(c, who); if (rc) return rc; }
-    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_integrate_depth: bad argument");
+    if (!a) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
     TsdfVolume& v = *c->tsdf;
+    if (coloured && !v.colour.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (coloured && !colour) return fail(c, NALO_ERR_ARG, std::string(who) + ": no colour plane");
     { const int rc = nalo_dev_plane_check(c, &a->depth); if (rc) return rc; }
-    if (a->depth.dtype != NALO_DT_F32 || a->depth.channels != 1) return fail(c, NALO_ERR_ARG, "nalo_tsdf_integrate_depth: the depth plane is one channel of F32");
+    if (a->depth.dtype != NALO_DT_F32 || a->depth.channels != 1) return fail(c, NALO_ERR_ARG, std::string(who) + ": the depth plane is one channel of F32");
+    TsdfColourSrc src{};
+    if (coloured) {
+        { const int rc = nalo_dev_plane_check(c, colour); if (rc) return rc; }
+        if (colour->dtype != NALO_DT_U8 || colour->channels != 3 || colour->w != a->depth.w || colour->h != a->depth.h)
+            return fail(c, NALO_ERR_ARG, std::string(who) + ": the colour plane is three channels of U8 in the depth plane's size");
+        src.p = static_cast<const unsigned char*>(colour->ptr); src.sy = colour->stride_y; src.sx = colour->stride_x;
+        for (int X = 0; X < 3; ++X) src.sc[X] = (colour_is_rgb ? 2 - X : X) * colour->stride_c;      // the planes are B, G, R
+    }
     float M[12]; int lo[3], hi[3];
     { const int rc = tsdf_integrate_check(c, who, v, a->depth.w, a->depth.h, a->K, a->camToWorld, a->min_depth, a->max_depth, M, lo, hi); if (rc) return rc; }
     // ---- accepted: from here on only the runtime can fail
@@ -124,10 +169,14 @@ int nalo_tsdf_integrate_depth(nalo_ctx* c, const nalo_tsdf_integrate_args* a) {
     hipStream_t prod = (hipStream_t)a->producer_stream;                      // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
     if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
     { const int rc = tsdf_integrate_enqueue(c, v, static_cast<const char*>(a->depth.ptr), a->depth.stride_y, a->depth.stride_x, a->depth.w, a->depth.h, a->K, M, a->min_depth,
-                                            a->max_depth, lo, hi); if (rc) return rc; }
-    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));                         // the caller's plane has been read: nalo_tsdf_release
+                                            a->max_depth, lo, hi, coloured ? &src : nullptr); if (rc) return rc; }
+    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));                         // the caller's planes have been read (one kernel reads both): nalo_tsdf_release
     v.read_pending = true;
     return NALO_OK;
+}
+int nalo_tsdf_integrate_depth(nalo_ctx* c, const nalo_tsdf_integrate_args* a) { return tsdf_integrate_depth(c, "nalo_tsdf_integrate_depth", a, false, nullptr, 0); }
+int nalo_tsdf_integrate_depth_color(nalo_ctx* c, const nalo_tsdf_integrate_args* a, const nalo_dev_plane* colour, int colour_is_rgb) {
+    return tsdf_integrate_depth(c, "nalo_tsdf_integrate_depth_color", a, true, colour, colour_is_rgb);
 }
 
 int nalo_tsdf_release(nalo_ctx* c, void* stream) {
@@ -156,12 +205,16 @@ int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld
         NALO_HIP(c, hipMemsetAsync(key.p, 0, npx * sizeof(unsigned long long), c->stream));
         v.key = std::move(key); v.plane = std::move(plane);
     }
+    const bool coloured = v.colour.p != nullptr;
+    if (coloured) NALO_HIP(c, v.cplane.reserve(npx));                          // every call writes every word of it: a winner's colour, or zero behind the resolve
     HostTimer ht(c, "tsdf_integrate_frame");
     if (v.key_dirty) NALO_HIP(c, hipMemsetAsync(v.key.p, 0, npx * sizeof(unsigned long long), c->stream));
     v.key_dirty = true;                                                        // until the resolve pass, which clears every key, is queued
-    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, c->w, c->h); if (rc) return rc; }
+    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, coloured ? v.cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
     v.key_dirty = false;
-    return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi);
+    // the packed plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
+    const TsdfColourSrc src = {reinterpret_cast<const unsigned char*>(v.cplane.p), (long long)c->w * 4, 4, {0, 1, 2}};
+    return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi, coloured ? &src : nullptr);
 }
 
 int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
@@ -178,10 +231,12 @@ int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
 }
 
 // nalo_tsdf_get (to_volume = 0) and nalo_tsdf_set (1)
-static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int size[3], float* tsdf, float* weight, int to_volume) {
+// and nalo_tsdf_color_get / _set (bgr != NULL, tsdf = weight = NULL): the three planes of the block, one after the other
+static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int size[3], float* tsdf, float* weight, int to_volume, float* bgr = nullptr, bool colour = false) {
     { const int rc = tsdf_need(c, who); if (rc) return rc; }
     TsdfVolume& v = *c->tsdf;
-    if (!lo || !size || (!tsdf && !weight)) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
+    if (colour && !v.colour.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (!lo || !size || (!tsdf && !weight && !bgr)) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
     for (int a = 0; a < 3; ++a)
         if (lo[a] < 0 || size[a] < 1 || lo[a] > v.d.dims[a] - size[a]) return fail(c, NALO_ERR_ARG, std::string(who) + ": the block is empty or leaves the grid");
     NALO_HIP(c, hipSetDevice(c->device));
@@ -189,8 +244,10 @@ static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int s
     const size_t slice = (size_t)size[0] * size[1];
     const int zs = (int)std::max<size_t>(1, std::min<size_t>((size_t)size[2], kTsdfTileFloats / slice));
     NALO_HIP(c, v.block.reserve(slice * zs));
-    float* host[2] = {tsdf, weight}; float* vol[2] = {v.tsdf.p, v.weight.p};
-    for (int k = 0; k < 2; ++k) {
+    const size_t blk = slice * size[2];
+    float* host[5] = {tsdf, weight, bgr, bgr ? bgr + blk : nullptr, bgr ? bgr + 2 * blk : nullptr};
+    float* vol[5] = {v.tsdf.p, v.weight.p, v.colour.p, bgr ? v.colour.p + v.n : nullptr, bgr ? v.colour.p + 2 * v.n : nullptr};
+    for (int k = 0; k < 5; ++k) {
         if (!host[k]) continue;
         for (int z0 = 0; z0 < size[2]; z0 += zs) {
             const int tlo[3] = {lo[0], lo[1], lo[2] + z0}, tsz[3] = {size[0], size[1], std::min(zs, size[2] - z0)};
@@ -207,6 +264,21 @@ static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int s
 int nalo_tsdf_get(nalo_ctx* c, const int lo[3], const int size[3], float* tsdf, float* weight) { return tsdf_block(c, "nalo_tsdf_get", lo, size, tsdf, weight, 0); }
 int nalo_tsdf_set(nalo_ctx* c, const int lo[3], const int size[3], const float* tsdf, const float* weight) {
     return tsdf_block(c, "nalo_tsdf_set", lo, size, const_cast<float*>(tsdf), const_cast<float*>(weight), 1);
+}
+int nalo_tsdf_color_get(nalo_ctx* c, const int lo[3], const int size[3], float* bgr) { return tsdf_block(c, "nalo_tsdf_color_get", lo, size, nullptr, nullptr, 0, bgr, true); }
+int nalo_tsdf_color_set(nalo_ctx* c, const int lo[3], const int size[3], const float* bgr) {
+    return tsdf_block(c, "nalo_tsdf_color_set", lo, size, nullptr, nullptr, 1, const_cast<float*>(bgr), true);
+}
+
+int nalo_tsdf_color_view(nalo_ctx* c, nalo_tsdf_color_volume_view* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_color_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_color_view: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    if (!v.colour.p) return fail(c, NALO_ERR_STATE, "nalo_tsdf_color_view: the volume holds no colour (nalo_tsdf_color_enable)");
+    out->bgr = v.colour.p;
+    for (int a = 0; a < 3; ++a) out->dims[a] = v.d.dims[a];
+    out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
 }
 
 int nalo_tsdf_view(nalo_ctx* c, nalo_tsdf_volume_view* out) {
@@ -257,23 +329,25 @@ int nalo_tsdf_surface_points(nalo_ctx* c, nalo_tsdf_surface_args* a) {
     return NALO_OK;
 }
 
-int nalo_tsdf_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* a) {
-    const char* who = "nalo_tsdf_mesh";
-    { const int rc = tsdf_need(c, who); if (rc) return rc; }
-    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: bad argument");
+// nalo_tsdf_mesh (coloured = false; cc is not looked at) and nalo_tsdf_mesh_color
+static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a, bool coloured, nalo_tsdf_mesh_color_args* cc) {
+    { const int rc = tsdf_need(c, who.c_str()); if (rc) return rc; }
+    if (!a || (coloured && !cc)) return fail(c, NALO_ERR_ARG, who + ": bad argument");
     a->n_vertices = 0; a->n_triangles = 0;
     TsdfVolume& v = *c->tsdf;
-    if (a->cap_vertices < 0 || a->cap_triangles < 0 || (a->cap_vertices > 0 && !a->xyz) || (a->cap_triangles > 0 && !a->tri) || std::isnan(a->min_weight))
-        return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: bad argument");
+    if (coloured && !v.colour.p) return fail(c, NALO_ERR_STATE, who + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (a->cap_vertices < 0 || a->cap_triangles < 0 || (a->cap_vertices > 0 && !a->xyz) || (a->cap_triangles > 0 && !a->tri) || std::isnan(a->min_weight) ||
+        (coloured && (cc->cap < 0 || (cc->cap > 0 && !cc->rgba))))
+        return fail(c, NALO_ERR_ARG, who + ": bad argument");
     TsdfMeshDev D{};
     long long total = 1;
     for (int k = 0; k < 3; ++k) {
         D.lo[k] = a->use_box ? a->lo[k] : 0; D.size[k] = a->use_box ? a->size[k] : v.d.dims[k];
-        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: the sub-box is empty or leaves the grid");
+        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, who + ": the sub-box is empty or leaves the grid");
         D.origin[k] = v.d.origin[k];
         total *= D.size[k];
     }
-    if (total > kTsdfMeshMaxVoxels) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: the sub-box holds more than 2^28 voxels");
+    if (total > kTsdfMeshMaxVoxels) return fail(c, NALO_ERR_ARG, who + ": the sub-box holds more than 2^28 voxels");
     // ---- accepted: from here on only the runtime can fail, or a host array turn out too small for what the device found
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "tsdf_mesh");
@@ -289,6 +363,11 @@ int nalo_tsdf_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* a) {
     }
     D.vmask = v.mesh_mask.p; D.vbase = v.mesh_base.p; D.cntv = v.mesh_cntv.p; D.cntt = v.mesh_cntt.p;
     D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = (long long)(v.mesh_xyz.cap / 3); D.capt = (long long)(v.mesh_tri.cap / 3);
+    if (coloured) {
+        // a word per vertex xyz has room for. It can be short only behind plain meshes that grew xyz, and then holds no mesh's colours (mesh_coloured is false)
+        if (v.mesh_rgba.cap < (size_t)D.capv) { v.mesh_coloured = false; NALO_HIP(c, v.mesh_rgba.reserve((size_t)D.capv)); }
+        D.col = v.colour.p; D.col_plane = v.n; D.rgba = v.mesh_rgba.p;
+    }
     // all four passes against the room there is: the steady state waits once, for the two totals
     {
         ProfScope ps(c, "tsdf_mesh");
@@ -299,28 +378,35 @@ int nalo_tsdf_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* a) {
     NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p + 1, D.cntt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     const long long nv = v.mesh_cnt_h.p[0], nt = (long long)(unsigned)v.mesh_cnt_h.p[1];
-    if (nv < 0 || nv > 7 * total || nt > 12 * total) return fail(c, NALO_ERR_HIP, "nalo_tsdf_mesh: the device counted more than the sub-box can hold");
+    if (nv < 0 || nv > 7 * total || nt > 12 * total) return fail(c, NALO_ERR_HIP, who + ": the device counted more than the sub-box can hold");
     if (nv > D.capv || nt > D.capt) {
         // nothing was written: the previous mesh is still whole, and stays if the new room cannot be had
-        DevBuf<float> xyz; DevBuf<int> tri;
+        DevBuf<float> xyz; DevBuf<int> tri; DevBuf<unsigned> rgba;
         const long long rv = std::max(D.capv, nv + nv / 4), rt = std::max(D.capt, nt + nt / 4);
         hipError_t e = xyz.reserve(3 * (size_t)rv);
         if (e == hipSuccess) e = tri.reserve(3 * (size_t)rt);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_mesh: ") + hipGetErrorString(e)); }
+        if (e == hipSuccess && coloured) e = rgba.reserve((size_t)rv);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, who + ": " + hipGetErrorString(e)); }
         v.mesh_xyz = std::move(xyz); v.mesh_tri = std::move(tri);              // the old pair is freed as xyz / tri leave scope: nothing queued names it
         D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = rv; D.capt = rt;
+        if (coloured) { v.mesh_rgba = std::move(rgba); D.rgba = v.mesh_rgba.p; }
         ProfScope ps(c, "tsdf_mesh");
         { const int rc = tsdf_mesh_write_launch(c, D); if (rc) return rc; }
     }
-    v.mesh_nv = nv; v.mesh_nt = nt; v.have_mesh = true;
+    v.mesh_nv = nv; v.mesh_nt = nt; v.have_mesh = true; v.mesh_coloured = coloured;
     a->n_vertices = nv; a->n_triangles = nt;
-    if ((a->xyz && a->cap_vertices < nv) || (a->tri && a->cap_triangles < nt))
-        return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh: a cap is below what the mesh holds (n_vertices, n_triangles); the device mesh is built");
+    uint8_t* rgba = coloured ? cc->rgba : nullptr;
+    if ((a->xyz && a->cap_vertices < nv) || (a->tri && a->cap_triangles < nt) || (rgba && cc->cap < nv))
+        return fail(c, NALO_ERR_ARG, who + ": a cap is below what the mesh holds (n_vertices, n_triangles); the device mesh is built");
     if (a->xyz && nv > 0) NALO_HIP(c, hipMemcpyAsync(a->xyz, v.mesh_xyz.p, 3 * (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
     if (a->tri && nt > 0) NALO_HIP(c, hipMemcpyAsync(a->tri, v.mesh_tri.p, 3 * (size_t)nt * 4, hipMemcpyDeviceToHost, c->stream));
-    if ((a->xyz && nv > 0) || (a->tri && nt > 0)) NALO_HIP(c, hipStreamSynchronize(c->stream));
+    if (rgba && nv > 0) NALO_HIP(c, hipMemcpyAsync(rgba, v.mesh_rgba.p, (size_t)nv * 4, hipMemcpyDeviceToHost, c->stream));
+    if ((a->xyz && nv > 0) || (a->tri && nt > 0) || (rgba && nv > 0)) NALO_HIP(c, hipStreamSynchronize(c->stream));
     return NALO_OK;
 }
+int nalo_tsdf_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* a) { return tsdf_mesh(c, "nalo_tsdf_mesh", a, false, nullptr); }
+int nalo_tsdf_mesh_color(nalo_ctx* c, nalo_tsdf_mesh_args* a, nalo_tsdf_mesh_color_args* cc) { return tsdf_mesh(c, "nalo_tsdf_mesh_color", a, true, cc); }
+
 
 int nalo_tsdf_mesh_view(nalo_ctx* c, nalo_tsdf_mesh_dev* out) {
     { const int rc = tsdf_need(c, "nalo_tsdf_mesh_view"); if (rc) return rc; }
@@ -328,6 +414,16 @@ int nalo_tsdf_mesh_view(nalo_ctx* c, nalo_tsdf_mesh_dev* out) {
     const TsdfVolume& v = *c->tsdf;
     if (!v.have_mesh) return fail(c, NALO_ERR_STATE, "nalo_tsdf_mesh_view: no mesh has been built from this volume (nalo_tsdf_mesh)");
     out->xyz = v.mesh_xyz.p; out->tri = v.mesh_tri.p; out->n_vertices = v.mesh_nv; out->n_triangles = v.mesh_nt;
+    out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
+}
+
+int nalo_tsdf_mesh_color_view(nalo_ctx* c, nalo_tsdf_mesh_color_dev* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_mesh_color_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_mesh_color_view: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    if (!v.have_mesh || !v.mesh_coloured) return fail(c, NALO_ERR_STATE, "nalo_tsdf_mesh_color_view: the last mesh of this volume was not built by nalo_tsdf_mesh_color");
+    out->rgba = reinterpret_cast<uint8_t*>(v.mesh_rgba.p); out->n_vertices = v.mesh_nv;
     out->stream = (void*)(hipStream_t)c->stream;
     return NALO_OK;
 }

@@ -8,9 +8,13 @@ namespace nalo {
 // ---- integration. Lanes run along x: a lane owns four voxels that are consecutive in memory and 16-byte aligned (the arrays are allocations of their own, so
 // alignment is a matter of the linear index), one 16-byte load and store per array where all four lie in the box's x range, scalar accesses at a row's two ends.
 // A workgroup is (1 << txl) lanes along x by (256 >> txl) rows of the box, so that a narrow box does not idle most of a wave.
+// Colour (nalo_tsdf_color_enable) is a compile-time flag: the uncoloured kernel is the instantiation without it. The coloured one keeps w0 and the colour bytes
+// of the voxels it updates and touches the three colour planes only in lanes that store tsdf and weight, so the visited-but-untouched box moves no colour byte.
 struct TsdfRow { float m1y, m2z, m5y, m6z, m9y, m10z; };                        // the products of M with py and pz: a row's own, the same operands as per voxel
 
-__device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const TsdfRow& R, int i, float& t, float& w) {
+// kColour: a voxel that is updated also hands back the weight BEFORE the update and its pixel's colour bytes, packed B | G << 8 | R << 16
+template <bool kColour>
+__device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const TsdfRow& R, int i, float& t, float& w, float& wb, unsigned& bgr) {
     const float px = P.origin[0] + ((float)i + 0.5f) * P.vs;
     const float xc = ((P.M[0] * px + R.m1y) + R.m2z) + P.M[3];
     const float yc = ((P.M[4] * px + R.m5y) + R.m6z) + P.M[7];
@@ -27,9 +31,19 @@ __device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const Tsdf
     const float t0 = t, w0 = w;
     t = (t0 * w0 + d) / (w0 + 1.0f);
     w = fminf(w0 + 1.0f, P.max_weight);
+    if constexpr (kColour) {
+        const unsigned char* px = P.colour + (long long)pv * P.csy + (long long)pu * P.csx;
+        wb = w0;
+        bgr = (unsigned)px[P.csc[0]] | ((unsigned)px[P.csc[1]] << 8) | ((unsigned)px[P.csc[2]] << 16);
+    }
     return true;
 }
+// plane X of an updated voxel: X = (X0 * w0 + (float)x) / (w0 + 1.0f), x the pixel's byte for that plane
+__device__ __forceinline__ float tsdf_colour(float x0, float w0, unsigned bgr, int plane) {
+    return (x0 * w0 + (float)((bgr >> (8 * plane)) & 0xFFu)) / (w0 + 1.0f);
+}
 
+template <bool kColour>
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P, int txl, int gx, int rows) {
     __shared__ int wsum[4];
     const int tx = 1 << txl, ry = 256 >> txl;
@@ -49,15 +63,38 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P,
             if (g >= rb && g + 4 <= re) {
                 float4 t = *reinterpret_cast<const float4*>(P.tsdf + g), w = *reinterpret_cast<const float4*>(P.weight + g);
                 const int i = (int)(g - base);
-                n += tsdf_voxel(P, R, i, t.x, w.x);
-                n += tsdf_voxel(P, R, i + 1, t.y, w.y);
-                n += tsdf_voxel(P, R, i + 2, t.z, w.z);
-                n += tsdf_voxel(P, R, i + 3, t.w, w.w);
+                float4 wb; uint4 bgr;                                               // kColour only: of the voxels that were updated
+                const bool u0 = tsdf_voxel<kColour>(P, R, i, t.x, w.x, wb.x, bgr.x);
+                const bool u1 = tsdf_voxel<kColour>(P, R, i + 1, t.y, w.y, wb.y, bgr.y);
+                const bool u2 = tsdf_voxel<kColour>(P, R, i + 2, t.z, w.z, wb.z, bgr.z);
+                const bool u3 = tsdf_voxel<kColour>(P, R, i + 3, t.w, w.w, wb.w, bgr.w);
+                n += (int)u0 + (int)u1 + (int)u2 + (int)u3;
                 if (n) { *reinterpret_cast<float4*>(P.tsdf + g) = t; *reinterpret_cast<float4*>(P.weight + g) = w; }
+                if constexpr (kColour) {
+                    // the colour of a lane moves only when one of its four voxels was updated; a voxel that was not goes back with the word that was loaded
+                    if (n) {
+#pragma unroll
+                        for (int X = 0; X < 3; ++X) {
+                            float4* at = reinterpret_cast<float4*>(P.col + (size_t)X * P.col_plane + g);
+                            float4 cv = *at;
+                            if (u0) cv.x = tsdf_colour(cv.x, wb.x, bgr.x, X);
+                            if (u1) cv.y = tsdf_colour(cv.y, wb.y, bgr.y, X);
+                            if (u2) cv.z = tsdf_colour(cv.z, wb.z, bgr.z, X);
+                            if (u3) cv.w = tsdf_colour(cv.w, wb.w, bgr.w, X);
+                            *at = cv;
+                        }
+                    }
+                }
             } else {
                 for (long long q = g < rb ? rb : g; q < g + 4 && q < re; ++q) {
-                    float t = P.tsdf[q], w = P.weight[q];
-                    if (tsdf_voxel(P, R, (int)(q - base), t, w)) { P.tsdf[q] = t; P.weight[q] = w; ++n; }
+                    float t = P.tsdf[q], w = P.weight[q], wb; unsigned bgr;
+                    if (tsdf_voxel<kColour>(P, R, (int)(q - base), t, w, wb, bgr)) {
+                        P.tsdf[q] = t; P.weight[q] = w; ++n;
+                        if constexpr (kColour) {
+#pragma unroll
+                            for (int X = 0; X < 3; ++X) { float* at = P.col + (size_t)X * P.col_plane + q; *at = tsdf_colour(*at, wb, bgr, X); }
+                        }
+                    }
                 }
             }
         }
@@ -83,7 +120,8 @@ int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D) {
     const long long blocks = (long long)gx * ((rows + ry - 1) / ry);
     if (blocks > INT32_MAX) return fail(c, NALO_ERR_ARG, "tsdf_integrate_launch: the box needs more workgroups than a grid has");
     ProfScope ps(c, "tsdf_integrate");
-    tsdf_integrate_kernel<<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
+    if (D.col) tsdf_integrate_kernel<true><<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
+    else tsdf_integrate_kernel<false><<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
 }
@@ -203,26 +241,43 @@ __global__ __launch_bounds__(256) void tsdf_frame_scatter_kernel(TsdfSegs S, uns
     if (r.u >= w || r.v >= h) return;
     atomicMax(&key[(size_t)r.v * w + r.u], ((unsigned long long)(q + 1) << 32) | (unsigned long long)__float_as_uint(r.idepth));
 }
-__global__ __launch_bounds__(256) void tsdf_frame_resolve_kernel(unsigned long long* key, float* plane, int n) {
+// behind every scatter launch: the record whose position the pixel's key holds is the one winner, and it alone stores its colour, packed B | G << 8 | R << 16
+__global__ __launch_bounds__(256) void tsdf_frame_colour_kernel(TsdfSegs S, const unsigned long long* key, unsigned* colour, int w, int h) {
+    const long long ql = (long long)S.start[0] + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ql >= S.start[S.nseg]) return;
+    const int q = (int)ql;
+    int s = 0;
+    while (s + 1 < S.nseg && q >= S.start[s + 1]) ++s;
+    const nalo_dense_point r = S.p[s][q - S.start[s]];
+    if (r.u >= w || r.v >= h) return;
+    const size_t p = (size_t)r.v * w + r.u;
+    if ((unsigned)(key[p] >> 32) == (unsigned)q + 1u) colour[p] = (unsigned)r.bgr[0] | ((unsigned)r.bgr[1] << 8) | ((unsigned)r.bgr[2] << 16);
+}
+template <bool kColour>
+__global__ __launch_bounds__(256) void tsdf_frame_resolve_kernel(unsigned long long* key, float* plane, unsigned* colour, int n) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const unsigned long long k = key[p];
     plane[p] = k ? 1.0f / __uint_as_float((unsigned)(k & 0xFFFFFFFFull)) : 0.0f;
     if (k) key[p] = 0;
+    if constexpr (kColour) if (!k) colour[p] = 0;                                 // a pixel without a record is (0, 0, 0)
 }
-int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, int w, int h) {
-    for (int s0 = 0; s0 < nseg; s0 += kTsdfSegsPerLaunch) {
-        TsdfSegs S{};
-        S.nseg = std::min(kTsdfSegsPerLaunch, nseg - s0);
-        for (int k = 0; k < S.nseg; ++k) { S.p[k] = static_cast<const nalo_dense_point*>(segs[s0 + k].p); S.start[k] = segs[s0 + k].start; }
-        S.start[S.nseg] = segs[s0 + S.nseg - 1].start + segs[s0 + S.nseg - 1].n;
-        const int n = S.start[S.nseg] - S.start[0];
-        if (n <= 0) continue;
-        tsdf_frame_scatter_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(S, key, w, h);
-        NALO_HIP(c, hipGetLastError());
-    }
+int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, unsigned* colour, int w, int h) {
+    for (int pass = 0; pass < (colour ? 2 : 1); ++pass)                           // every scatter is queued before the first colour pass
+        for (int s0 = 0; s0 < nseg; s0 += kTsdfSegsPerLaunch) {
+            TsdfSegs S{};
+            S.nseg = std::min(kTsdfSegsPerLaunch, nseg - s0);
+            for (int k = 0; k < S.nseg; ++k) { S.p[k] = static_cast<const nalo_dense_point*>(segs[s0 + k].p); S.start[k] = segs[s0 + k].start; }
+            S.start[S.nseg] = segs[s0 + S.nseg - 1].start + segs[s0 + S.nseg - 1].n;
+            const int n = S.start[S.nseg] - S.start[0];
+            if (n <= 0) continue;
+            if (pass == 0) tsdf_frame_scatter_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(S, key, w, h);
+            else tsdf_frame_colour_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(S, key, colour, w, h);
+            NALO_HIP(c, hipGetLastError());
+        }
     const int n = w * h;
-    tsdf_frame_resolve_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(key, plane, n);
+    if (colour) tsdf_frame_resolve_kernel<true><<<(n + 255) / 256, 256, 0, c->stream>>>(key, plane, colour, n);
+    else tsdf_frame_resolve_kernel<false><<<(n + 255) / 256, 256, 0, c->stream>>>(key, plane, colour, n);
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
 }

@@ -4,7 +4,7 @@
 // centre(v) + voxel_size * (t0 / (t0 - t1)), one rounding per operation, the surface points' own expression.
 //   classify   per voxel the 7-bit mask of the edges it owns that carry a vertex (one byte of scratch) and its cell's triangle count; per workgroup both sums
 //   scan       both count arrays
-//   vertices   per voxel the index of its first vertex (an int of scratch), and the positions
+//   vertices   per voxel the index of its first vertex (an int of scratch), and the positions; nalo_tsdf_mesh_color's instantiation also the colours
 //   triangles  per live cell the six tetrahedra through the table in __constant__ memory; a vertex's index is its owner's first index plus the set bits below its edge
 // The two write kernels store nothing into xyz / tri when the scanned totals exceed the buffers (the host grows them and runs the two again).
 // What is skipped: a voxel that is not valid owns no vertex and its cell is not live, so its seven neighbours are not read; a cell that yields a triangle has a
@@ -106,6 +106,14 @@ __device__ __forceinline__ bool tsdf_mesh_fits(const TsdfMeshDev& P) {
     return (long long)P.cntv[P.nb] <= P.capv && (long long)(unsigned)P.cntt[P.nb] <= P.capt;
 }
 
+// nalo_tsdf_mesh_color: plane X of the vertex on (v, n) is X(v) + s * (X(n) - X(v)), its byte (uint8)(int)(fminf(fmaxf(cX, 0.0f), 255.0f) + 0.5f); a NaN is 0
+__device__ __forceinline__ unsigned tsdf_mesh_colour_byte(float xv, float xn, float s) {
+    const float cx = xv + s * (xn - xv);
+    return (unsigned)(int)(fminf(fmaxf(cx, 0.0f), 255.0f) + 0.5f);
+}
+
+// kColour: the vertex pass also writes one colour per vertex, R, G, B, 255 as one aligned word
+template <bool kColour>
 __global__ __launch_bounds__(256) void tsdf_mesh_vertex_kernel(TsdfMeshDev P) {
     const long long q0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     unsigned m[4] = {0, 0, 0, 0};
@@ -134,12 +142,19 @@ __global__ __launch_bounds__(256) void tsdf_mesh_vertex_kernel(TsdfMeshDev P) {
 #pragma unroll
         for (int d = 1; d < 8; ++d) {
             if (!((m[e] >> (d - 1)) & 1u)) continue;
-            const float t1 = P.tsdf[v + (d & 1) + (size_t)((d >> 1) & 1) * P.nx + (size_t)((d >> 2) & 1) * P.nx * P.ny];
+            const size_t nb = v + (d & 1) + (size_t)((d >> 1) & 1) * P.nx + (size_t)((d >> 2) & 1) * P.nx * P.ny;
+            const float t1 = P.tsdf[nb];
             const float s = t0 / (t0 - t1);
             const float prod = P.vs * s;
             P.xyz[3 * at] = (d & 1) ? c[0] + prod : c[0];
             P.xyz[3 * at + 1] = (d & 2) ? c[1] + prod : c[1];
             P.xyz[3 * at + 2] = (d & 4) ? c[2] + prod : c[2];
+            if constexpr (kColour) {
+                const unsigned b = tsdf_mesh_colour_byte(P.col[v], P.col[nb], s);
+                const unsigned g = tsdf_mesh_colour_byte(P.col[P.col_plane + v], P.col[P.col_plane + nb], s);
+                const unsigned r = tsdf_mesh_colour_byte(P.col[2 * P.col_plane + v], P.col[2 * P.col_plane + nb], s);
+                P.rgba[at] = r | (g << 8) | (b << 16) | 0xFF000000u;
+            }
             ++at;
         }
     }
@@ -204,7 +219,8 @@ int tsdf_mesh_classify_launch(nalo_ctx* c, const TsdfMeshDev& D) {
     return scan_ints_launch(c, D.cntt, D.nb);
 }
 int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D) {
-    tsdf_mesh_vertex_kernel<<<D.nb, 256, 0, c->stream>>>(D);
+    if (D.col) tsdf_mesh_vertex_kernel<true><<<D.nb, 256, 0, c->stream>>>(D);
+    else tsdf_mesh_vertex_kernel<false><<<D.nb, 256, 0, c->stream>>>(D);
     NALO_HIP(c, hipGetLastError());
     tsdf_mesh_triangle_kernel<<<D.nb, 256, 0, c->stream>>>(D);
     NALO_HIP(c, hipGetLastError());

@@ -459,6 +459,10 @@ struct TsdfIntegrateDev {
     float origin[3], vs, trunc, max_weight, M[12], fx, fy, cx, cy, min_depth, max_depth;
     const char* depth; long long sy, sx; int w, h;                              // the plane by byte strides
     unsigned long long* updated;                                                // zero before
+    // colour, behind everything the uncoloured kernel reads: col != NULL selects the coloured instantiation. col: [3][nz][ny][nx], planes B, G, R, col_plane
+    // floats apart; the pixel's bytes lie at colour + pv csy + pu csx + csc[plane] (csc already holds the B, G, R order of the caller's channels)
+    float* col; size_t col_plane;
+    const unsigned char* colour; long long csy, csx, csc[3];
 };
 int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D);
 int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
@@ -479,13 +483,15 @@ struct TsdfMeshDev {
     unsigned char* vmask; int* vbase;                                           // [total + 3] each (a lane stores its four at once): a voxel's edges that carry a vertex (bit m - 1), the index of its first vertex
     int *cntv, *cntt;                                                           // [nb + 1] each: vertices / triangles per workgroup, scanned; [nb] the sums (cntt read as unsigned)
     float* xyz; int* tri; long long capv, capt;                                 // written only when both sums fit
+    const float* col; size_t col_plane; unsigned* rgba;                         // nalo_tsdf_mesh_color (col != NULL): the colour planes, and [capv] vertex colours R | G << 8 | B << 16 | 255 << 24
 };
 int tsdf_mesh_classify_launch(nalo_ctx* c, const TsdfMeshDev& D);               // classify and both scans on c->stream
 int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D);                  // the vertex and the triangle pass
 // nalo_tsdf_integrate_frame's plane: D[v][u] = 1.0f / idepth of the record with the highest position at (u, v), 0 without one. key: w h words, zero between calls.
+// colour != NULL (a coloured volume): w h words, that record's B | G << 8 | R << 16, 0 without one - a U8 plane of three channels with stride_x 4, stride_c 1
 // segs is HOST memory: the segments travel as kernel arguments, kTsdfSegsPerLaunch to a launch, so the call stages nothing that a later call could overwrite
 constexpr int kTsdfSegsPerLaunch = 32;
-int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, int w, int h);
+int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, unsigned* colour, int w, int h);
 void tsdf_destroy(nalo_ctx* c);
 // host_ba.hip: frame_id (nalo_frame_state) of window frame host_frame, which ba_plane_inputs has validated
 int ba_frame_id(nalo_ctx* c, int host_frame);
