@@ -1592,6 +1592,52 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    built and the counts are set, as for xyz).
  * nalo_tsdf_mesh_color_view   host code only, launches nothing: the device colours of the last mesh. NALO_ERR_STATE unless the LAST mesh call was
  *                    nalo_tsdf_mesh_color: a plain nalo_tsdf_mesh afterwards invalidates it. nalo_tsdf_mesh_view keeps working after either.
+ *
+ * The ray-cast. What the fused model looks like from a pose: a depth, a normal and a colour image of the volume's zero crossing, without a mesh and without a GL
+ * context. The reference never reads its octree, so nalo_tsdf_raycast is a DEFINED operation: a march at a fixed step, trilinear over cells whose eight corners
+ * are all valid, the first front face. Everything in float, no FMA contraction, each operation rounded once; no float atomic, the same bytes on every run.
+ *   Ray: for pixel (u, v) of the w x h view with K = {fx, fy, cx, cy} (any size, not the context's):  rx = ((float)u - cx) / fx,  ry = ((float)v - cy) / fy - the
+ *     inverse of the integration's (int)(fx * (xc / zc) + cx + 0.5f) at the pixel centre. With R and t the entries of camToWorld, each rounded to float:
+ *     d_a = (R[a][0] * rx + R[a][1] * ry) + R[a][2],  o_a = t_a  (a = x, y, z). The ray is parametrised by camera-z: its point at z is p_a = o_a + d_a * z.
+ *   Samples: z_n = min_depth + (float)n * step. N is the number of n in 0..4096 with z_n <= max_depth, evaluated in float with that expression (they form a
+ *     prefix: z_n does not decrease with n). nalo_tsdf_raycast_steps computes N and refuses (NALO_ERR_ARG) when z_4096 <= max_depth, so 1 <= N <= 4096.
+ *     The grid coordinate of a point is q_a = ((p_a - origin_a) / voxel_size) - 0.5f: voxel centres are the integers.
+ *   Field S(q): i_a = floorf(q_a), f_a = q_a - i_a. The sample is VALID iff for every axis i_a >= 0.0f && i_a <= (float)(dim_a - 2), compared in float BEFORE
+ *     any conversion (a NaN or an infinity fails; a grid with a dimension of 1 has no cell), and the eight corners (ix + dx, iy + dy, iz + dz), dx, dy, dz in
+ *     {0, 1}, are all valid in the mesh's sense: weight >= min_weight and tsdf not NaN. With t_zyx the tsdf of corner (dx, dy, dz) = (x, y, z) - the digits of t
+ *     read z, y, x, so t001 is the corner one step along +x - and a_yz the value interpolated along x on the edge with those y and z:
+ *       a00 = t000 + fx * (t001 - t000),  a10 = t010 + fx * (t011 - t010),  a01 = t100 + fx * (t101 - t100),  a11 = t110 + fx * (t111 - t110)   (fx = f_x here),
+ *       b0 = a00 + fy * (a10 - a00),  b1 = a01 + fy * (a11 - a01),  S = b0 + fz * (b1 - b0).
+ *     A NaN S (inf - inf among infinite corners) makes the sample INVALID.
+ *   March: the smallest n in [1, N) whose samples n - 1 and n are both VALID and differ in (S < 0) ends the ray. S_{n-1} >= 0 && S_n < 0 is a HIT (-0.0f is
+ *     outside, as in the mesh); the other order is a BACK face and the pixel is a miss. An invalid sample breaks the pairs on both its sides: nothing is
+ *     interpolated across it. No such n, or N < 2: a miss.
+ *   Hit: s = S_{n-1} / (S_{n-1} - S_n),  depth = z_{n-1} + step * s;  q* is the grid coordinate of the ray's point at z = depth.
+ *   Normal (with_normals): G_a = S(q* + e_a) - S(q* - e_a), the shifted coordinate q*_a + 1.0f and q*_a - 1.0f in float. All six samples must be VALID, else the
+ *     normal is (0, 0, 0) and the pixel stays a hit. len = sqrt((Gx * Gx + Gy * Gy) + Gz * Gz), correctly rounded; if len > 0 and finite the normal is G_a / len,
+ *     else zeros. World axes (the grid is axis-aligned); it points from tsdf < 0 to tsdf >= 0, towards the camera that saw the surface: the mesh's orientation.
+ *   Colour (with_colour): per plane the trilinear expression above at q* on the colour plane; only the index test applies, the weights are not consulted.
+ *     byte = (uint8)(int)(fminf(fmaxf(c, 0.0f), 255.0f) + 0.5f), the mesh colour's conversion (a NaN gives 0); the bytes are R, G, B, 255. Where the index
+ *     test fails at q* (a NaN depth): 0, 0, 0, 255.
+ *   Miss: depth 0.0f, normal zeros, rgba 0, 0, 0, 0. nalo_tsdf_integrate_depth ignores a depth of 0 for min_depth > 0: the plane can be integrated as it stands.
+ *   The kernel: one lane per pixel, a wave an 8 x 8 tile, a workgroup 16 x 16. A lane visits only a conservative interval of n: the slab test of its ray against
+ *     the cells' region, widened and clipped to [0, N). Samples outside the region fail the index test and an invalid sample never forms a pair, so the result
+ *     equals the definition evaluated at every n. n_hit, n_back (rays a back face ended) and n_normal (non-zero normals) are integer sums: wave reductions,
+ *     then one atomic per workgroup.
+ * nalo_tsdf_raycast  reads the volume only. The images live in context-owned device buffers that grow when a larger view is asked for, are never shrunk and are
+ *                    freed with the volume. A host array that is given is filled through pinned staging, and only on success; NULL leaves that image on the
+ *                    device. One host wait per call, for the counts and whatever is downloaded. A context that never ray-casts queues what it queued before.
+ *                    NALO_ERR_STATE: no volume; with_colour without colour enabled. NALO_ERR_ARG: NULL args; w or h < 1 or w * h > 2^26; a non-finite entry
+ *                    of K or camToWorld; fx or fy equal to 0; min_depth, max_depth or step not finite, min_depth < 0, min_depth > max_depth, step <= 0, more
+ *                    than 4096 steps; a NaN min_weight; a host normal or rgba given without its with_ flag. A refused call queues nothing, leaves volume,
+ *                    context, the previous device images and every host array as they were, and zeroes the counts. A failed allocation (NALO_ERR_HIP)
+ *                    leaves the previous images whole.
+ * nalo_tsdf_raycast_view   host code only, launches nothing: the images of the last ray-cast as nalo_dev_plane descriptors (depth: F32, one channel, what
+ *                    nalo_tsdf_integrate_depth takes as it is; normal: F32, three channels interleaved; rgba: U8, the channels R, G, B at stride_x 4 - the
+ *                    alpha byte lies between pixels - so a colour plane with colour_is_rgb = 1) and the producing stream, under "Lifetime of a view": good
+ *                    until the next nalo_tsdf_raycast, nalo_tsdf_create, nalo_tsdf_destroy or nalo_destroy. An image the last call was not asked for has a
+ *                    NULL ptr. NALO_ERR_STATE before the first ray-cast.
+ * nalo_tsdf_raycast_steps  host only, needs no context: N of the definition. NALO_ERR_ARG as nalo_tsdf_raycast refuses the three values, and for a NULL n_steps.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1643,10 +1689,24 @@ int nalo_tsdf_color_set(nalo_ctx* ctx, const int lo[3], const int size[3], const
 int nalo_tsdf_color_view(nalo_ctx* ctx, nalo_tsdf_color_volume_view* out);   /* host only, launches nothing */
 int nalo_tsdf_mesh_color(nalo_ctx* ctx, nalo_tsdf_mesh_args* args, nalo_tsdf_mesh_color_args* colour);
 int nalo_tsdf_mesh_color_view(nalo_ctx* ctx, nalo_tsdf_mesh_color_dev* out); /* host only, launches nothing */
+typedef struct nalo_tsdf_raycast_args {
+    int w, h; float K[4];                   /* fx, fy, cx, cy of the view: any size, not the context's */
+    double camToWorld[12];
+    float min_depth, max_depth, step;       /* camera-z of the first sample, the last allowed one, the spacing */
+    float min_weight;
+    int with_normals, with_colour;
+    float* depth; float* normal; uint8_t* rgba;   /* host, optional: [h][w], [h][w][3], [h][w][4]; NULL = leave on the device */
+    long long n_hit, n_back, n_normal;      /* out */
+    int n_steps;                            /* out: N */
+} nalo_tsdf_raycast_args;
+typedef struct nalo_tsdf_raycast_dev { nalo_dev_plane depth, normal, rgba; int w, h; void* stream; } nalo_tsdf_raycast_dev;
+int nalo_tsdf_raycast(nalo_ctx* ctx, nalo_tsdf_raycast_args* args);
+int nalo_tsdf_raycast_view(nalo_ctx* ctx, nalo_tsdf_raycast_dev* out);       /* host only, launches nothing */
+int nalo_tsdf_raycast_steps(float min_depth, float max_depth, float step, int* n_steps);   /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -42,6 +42,7 @@ EXPORTS = [
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
     "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
+    "nalo_tsdf_raycast", "nalo_tsdf_raycast_view", "nalo_tsdf_raycast_steps",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -204,6 +205,16 @@ class TsdfMeshColorDev(C.Structure):                      # nalo_tsdf_mesh_color
     _fields_ = [("rgba", C.c_void_p), ("n_vertices", C.c_longlong), ("stream", C.c_void_p)]
 
 
+class TsdfRaycastArgs(C.Structure):                       # nalo_tsdf_raycast_args
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("K", C.c_float * 4), ("camToWorld", C.c_double * 12), ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float),
+                ("min_weight", C.c_float), ("with_normals", C.c_int), ("with_colour", C.c_int), ("depth", c_fp), ("normal", c_fp), ("rgba", c_u8p),
+                ("n_hit", C.c_longlong), ("n_back", C.c_longlong), ("n_normal", C.c_longlong), ("n_steps", C.c_int)]
+
+
+class TsdfRaycastDev(C.Structure):                        # nalo_tsdf_raycast_dev
+    _fields_ = [("depth", DevPlane), ("normal", DevPlane), ("rgba", DevPlane), ("w", C.c_int), ("h", C.c_int), ("stream", C.c_void_p)]
+
+
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
@@ -298,6 +309,7 @@ def host_lib():
         L.nalo_trk_motion_tries.argtypes = [c_dp, c_dp, C.c_int, c_dp]
         L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
         L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
+        L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
         _HOST_LIB = L
@@ -355,6 +367,16 @@ def tsdf_mesh_table():
     if rc != 0:
         raise NaloError("nalo_tsdf_mesh_table: error %d" % rc)
     return out
+
+
+def tsdf_raycast_steps(min_depth, max_depth, step):
+    """nalo_tsdf_raycast_steps: N, the number of samples z_n = min_depth + (float)n * step <= max_depth of a ray-cast (1 .. 4096); NaloError for values
+    nalo_tsdf_raycast refuses, more than 4096 steps among them. Needs no device"""
+    n = np.zeros(1, np.int32)
+    rc = host_lib().nalo_tsdf_raycast_steps(C.c_float(min_depth), C.c_float(max_depth), C.c_float(step), _i(n))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_raycast_steps: bad argument (%d)" % rc)
+    return int(n[0])
 
 
 def write_ply_mesh(path, xyz, tri, rgba=None):
@@ -554,6 +576,9 @@ def load():
     L.nalo_tsdf_color_view.argtypes = [vp, C.POINTER(TsdfColorVolumeView)]
     L.nalo_tsdf_mesh_color.argtypes = [vp, C.POINTER(TsdfMeshArgs), C.POINTER(TsdfMeshColorArgs)]
     L.nalo_tsdf_mesh_color_view.argtypes = [vp, C.POINTER(TsdfMeshColorDev)]
+    L.nalo_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastArgs)]
+    L.nalo_tsdf_raycast_view.argtypes = [vp, C.POINTER(TsdfRaycastDev)]
+    L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
@@ -1692,6 +1717,43 @@ class Context:
         v = TsdfMeshColorDev()
         self._ck(self.L.nalo_tsdf_mesh_color_view(self.h_, C.byref(v)))
         return DeviceView(v.rgba, (v.n_vertices, 4), "|u1", None, v.stream, self)
+
+    def tsdf_raycast(self, w, h, K, cam_to_world, min_depth, max_depth, step, min_weight, normals=False, colour=False, download=True):
+        """nalo_tsdf_raycast -> dict(depth float32 [h][w], normal float32 [h][w][3] (normals), rgba uint8 [h][w][4] (colour), n_hit, n_back, n_normal, n_steps):
+        the volume's first front face along every pixel's ray of a w x h view with K = (fx, fy, cx, cy), sampled at z_n = min_depth + n * step <= max_depth.
+        A miss has depth 0. One library call and one wait; download=False leaves the images on the device (tsdf_raycast_view) and returns the counts only.
+        self.tsdf_raycast_counts holds (n_hit, n_back, n_normal, n_steps) of the last call, a refusal included"""
+        a = TsdfRaycastArgs()
+        a.w, a.h = int(w), int(h)
+        a.K[:] = [float(v) for v in K]
+        a.camToWorld[:] = [float(v) for v in np.asarray(cam_to_world, np.float64).reshape(-1)]
+        a.min_depth, a.max_depth, a.step, a.min_weight = float(min_depth), float(max_depth), float(step), float(min_weight)
+        a.with_normals, a.with_colour = int(bool(normals)), int(bool(colour))
+        out = {}
+        if download and a.w > 0 and a.h > 0:
+            out["depth"] = np.zeros((a.h, a.w), np.float32)
+            a.depth = _f(out["depth"])
+            if normals:
+                out["normal"] = np.zeros((a.h, a.w, 3), np.float32)
+                a.normal = _f(out["normal"])
+            if colour:
+                out["rgba"] = np.zeros((a.h, a.w, 4), np.uint8)
+                a.rgba = _u8(out["rgba"])
+        rc = self.L.nalo_tsdf_raycast(self.h_, C.byref(a))
+        self.tsdf_raycast_counts = (int(a.n_hit), int(a.n_back), int(a.n_normal), int(a.n_steps))
+        self._ck(rc)
+        out.update(n_hit=int(a.n_hit), n_back=int(a.n_back), n_normal=int(a.n_normal), n_steps=int(a.n_steps))
+        return out
+
+    def tsdf_raycast_view(self):
+        """nalo_tsdf_raycast_view -> dict(depth [h, w] float32, normal [h, w, 3] float32 or None, rgba [h, w, 4] uint8 or None) of DeviceViews on the images the
+        last tsdf_raycast wrote: torch.as_tensor(view, device="cuda") is a zero-copy tensor, and the depth view is what tsdf_integrate_depth takes as it is.
+        Launches nothing; good until the next tsdf_raycast / tsdf_create / tsdf_destroy / close"""
+        v = TsdfRaycastDev()
+        self._ck(self.L.nalo_tsdf_raycast_view(self.h_, C.byref(v)))
+        return dict(depth=DeviceView(v.depth.ptr, (v.h, v.w), "<f4", None, v.stream, self),
+                    normal=DeviceView(v.normal.ptr, (v.h, v.w, 3), "<f4", None, v.stream, self) if v.normal.ptr else None,
+                    rgba=DeviceView(v.rgba.ptr, (v.h, v.w, 4), "|u1", None, v.stream, self) if v.rgba.ptr else None)
 
     def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
         """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes

@@ -75,3 +75,19 @@ extern "C" int nalo_tsdf_mesh_table(signed char out[6][16][6]) {
             for (int k = 0; k < 6; ++k) out[t][m][k] = T.e[t][m][k];
     return NALO_OK;
 }
+
+extern "C" int nalo_tsdf_raycast_steps(float min_depth, float max_depth, float step, int* n_steps) {
+    if (!n_steps) return NALO_ERR_ARG;
+    *n_steps = 0;
+    if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || !std::isfinite(step) || min_depth < 0.0f || min_depth > max_depth || !(step > 0.0f)) return NALO_ERR_ARG;
+    // z_n = min_depth + (float)n * step does not decrease with n, so the n with z_n <= max_depth form a prefix; n = 0 is always one of them
+    int n = 0;
+    while (n <= 4096) {
+        const float z = min_depth + (float)n * step;
+        if (!(z <= max_depth)) break;
+        ++n;
+    }
+    if (n > 4096) return NALO_ERR_ARG;                                          // z_4096 <= max_depth: more than 4096 steps
+    *n_steps = n;
+    return NALO_OK;
+}

@@ -28,6 +28,11 @@ struct TsdfVolume {
     // colour (nalo_tsdf_color_enable): [3][nz][ny][nx], planes B, G, R; no memory while colour is off. cplane: nalo_tsdf_integrate_frame's packed colour plane, w h
     // words; mesh_rgba: one word per vertex of the device mesh, as many as mesh_xyz has room for; mesh_coloured: the last mesh call wrote it
     DevBuf<float> colour; DevBuf<unsigned> cplane, mesh_rgba; bool mesh_coloured = false;
+    // nalo_tsdf_raycast: the device images (nalo_tsdf_raycast_view names them), sized by the largest view so far and never shrunk; rc_normal_on / rc_rgba_on:
+    // the last call wrote that image. Their pinned staging, and the three counts
+    DevBuf<float> rc_depth, rc_normal; DevBuf<unsigned> rc_rgba; DevBuf<unsigned long long> rc_cnt;
+    HostBuf<float> rc_depth_h, rc_normal_h; HostBuf<unsigned> rc_rgba_h; HostBuf<unsigned long long> rc_cnt_h;
+    int rc_w = 0, rc_h = 0; bool have_rc = false, rc_normal_on = false, rc_rgba_on = false;
 };
 
 // a caller's colour plane as the integration kernel reads it: byte strides, sc[X] the offset of the channel that feeds plane X (B, G, R)
@@ -424,6 +429,89 @@ int nalo_tsdf_mesh_color_view(nalo_ctx* c, nalo_tsdf_mesh_color_dev* out) {
     const TsdfVolume& v = *c->tsdf;
     if (!v.have_mesh || !v.mesh_coloured) return fail(c, NALO_ERR_STATE, "nalo_tsdf_mesh_color_view: the last mesh of this volume was not built by nalo_tsdf_mesh_color");
     out->rgba = reinterpret_cast<uint8_t*>(v.mesh_rgba.p); out->n_vertices = v.mesh_nv;
+    out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
+}
+
+int nalo_tsdf_raycast(nalo_ctx* c, nalo_tsdf_raycast_args* a) {
+    const char* who = "nalo_tsdf_raycast";
+    if (!c) return NALO_ERR_ARG;
+    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: bad argument");
+    a->n_hit = a->n_back = a->n_normal = 0; a->n_steps = 0;
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (a->with_colour && !v.colour.p) return fail(c, NALO_ERR_STATE, "nalo_tsdf_raycast: the volume holds no colour (nalo_tsdf_color_enable)");
+    if (a->w < 1 || a->h < 1 || (long long)a->w * a->h > (1LL << 26)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: w or h < 1, or more than 2^26 pixels");
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(a->K[i])) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: K is not finite");
+    if (a->K[0] == 0.0f || a->K[1] == 0.0f) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: fx or fy is 0");
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(a->camToWorld[i])) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: camToWorld is not finite");
+    int N = 0;
+    if (nalo_tsdf_raycast_steps(a->min_depth, a->max_depth, a->step, &N) != NALO_OK)
+        return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: min_depth / max_depth / step not finite, min_depth < 0 or > max_depth, step <= 0, or more than 4096 steps");
+    if (std::isnan(a->min_weight)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: min_weight is NaN");
+    if ((a->normal && !a->with_normals) || (a->rgba && !a->with_colour)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: a host normal / rgba array without its with_ flag");
+    // ---- accepted: from here on only the runtime can fail
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "tsdf_raycast");
+    const size_t npx = (size_t)a->w * a->h;
+    const bool nrm = a->with_normals != 0, col = a->with_colour != 0;
+    // everything that has to grow is allocated before anything is replaced: a failed allocation leaves the previous images whole
+    {
+        DevBuf<float> depth, normal; DevBuf<unsigned> rgba;
+        hipError_t e = hipSuccess;
+        if (v.rc_depth.cap < npx) e = depth.reserve(npx);
+        if (e == hipSuccess && nrm && v.rc_normal.cap < 3 * npx) e = normal.reserve(3 * npx);
+        if (e == hipSuccess && col && v.rc_rgba.cap < npx) e = rgba.reserve(npx);
+        if (e == hipSuccess) e = v.rc_cnt.reserve(3);
+        if (e == hipSuccess) e = v.rc_cnt_h.reserve(3);
+        if (e == hipSuccess && a->depth) e = v.rc_depth_h.reserve(npx);
+        if (e == hipSuccess && a->normal) e = v.rc_normal_h.reserve(3 * npx);
+        if (e == hipSuccess && a->rgba) e = v.rc_rgba_h.reserve(npx);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_raycast: ") + hipGetErrorString(e)); }
+        if (depth.p) v.rc_depth = std::move(depth);                            // the old images are freed as the locals leave scope (hipFree waits for the device)
+        if (normal.p) v.rc_normal = std::move(normal);
+        if (rgba.p) v.rc_rgba = std::move(rgba);
+    }
+    TsdfRaycastDev D{};
+    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
+    for (int k = 0; k < 3; ++k) {
+        D.origin[k] = v.d.origin[k]; D.t[k] = (float)a->camToWorld[4 * k + 3];
+        for (int j = 0; j < 3; ++j) D.R[3 * k + j] = (float)a->camToWorld[4 * k + j];
+    }
+    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
+    D.fx = a->K[0]; D.fy = a->K[1]; D.cx = a->K[2]; D.cy = a->K[3]; D.w = a->w; D.h = a->h;
+    D.min_depth = a->min_depth; D.step = a->step; D.N = N;
+    D.col = col ? v.colour.p : nullptr; D.col_plane = v.n;
+    D.depth = v.rc_depth.p; D.normal = nrm ? v.rc_normal.p : nullptr; D.rgba = col ? v.rc_rgba.p : nullptr; D.cnt = v.rc_cnt.p;
+    v.have_rc = false;                                                         // until the new images are queued
+    NALO_HIP(c, hipMemsetAsync(v.rc_cnt.p, 0, 3 * sizeof(unsigned long long), c->stream));
+    { const int rc = tsdf_raycast_launch(c, D); if (rc) return rc; }
+    v.rc_w = a->w; v.rc_h = a->h; v.rc_normal_on = nrm; v.rc_rgba_on = col; v.have_rc = true;
+    // one wait, for the counts and whatever is downloaded; the images reach the caller's arrays only behind it
+    NALO_HIP(c, hipMemcpyAsync(v.rc_cnt_h.p, v.rc_cnt.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if (a->depth) NALO_HIP(c, hipMemcpyAsync(v.rc_depth_h.p, v.rc_depth.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    if (a->normal) NALO_HIP(c, hipMemcpyAsync(v.rc_normal_h.p, v.rc_normal.p, 3 * npx * 4, hipMemcpyDeviceToHost, c->stream));
+    if (a->rgba) NALO_HIP(c, hipMemcpyAsync(v.rc_rgba_h.p, v.rc_rgba.p, npx * 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const unsigned long long* n = v.rc_cnt_h.p;
+    if (n[0] + n[1] > npx || n[2] > n[0]) return fail(c, NALO_ERR_HIP, "nalo_tsdf_raycast: the device counted more than the view holds");
+    if (a->depth) std::copy(v.rc_depth_h.p, v.rc_depth_h.p + npx, a->depth);
+    if (a->normal) std::copy(v.rc_normal_h.p, v.rc_normal_h.p + 3 * npx, a->normal);
+    if (a->rgba) std::copy(reinterpret_cast<const uint8_t*>(v.rc_rgba_h.p), reinterpret_cast<const uint8_t*>(v.rc_rgba_h.p) + 4 * npx, a->rgba);
+    a->n_hit = (long long)n[0]; a->n_back = (long long)n[1]; a->n_normal = (long long)n[2]; a->n_steps = N;
+    return NALO_OK;
+}
+
+int nalo_tsdf_raycast_view(nalo_ctx* c, nalo_tsdf_raycast_dev* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_raycast_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast_view: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    if (!v.have_rc) return fail(c, NALO_ERR_STATE, "nalo_tsdf_raycast_view: this volume has not been ray-cast (nalo_tsdf_raycast)");
+    const long long w = v.rc_w;
+    out->depth = nalo_dev_plane{v.rc_depth.p, NALO_DT_F32, v.rc_w, v.rc_h, 1, 4 * w, 4, 0};
+    out->normal = nalo_dev_plane{v.rc_normal_on ? v.rc_normal.p : nullptr, NALO_DT_F32, v.rc_w, v.rc_h, 3, 12 * w, 12, 4};
+    out->rgba = nalo_dev_plane{v.rc_rgba_on ? v.rc_rgba.p : nullptr, NALO_DT_U8, v.rc_w, v.rc_h, 3, 4 * w, 4, 1};   // R, G, B as three channels; the alpha byte lies between pixels
+    out->w = v.rc_w; out->h = v.rc_h;
     out->stream = (void*)(hipStream_t)c->stream;
     return NALO_OK;
 }

@@ -492,6 +492,17 @@ int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D);                  
 // segs is HOST memory: the segments travel as kernel arguments, kTsdfSegsPerLaunch to a launch, so the call stages nothing that a later call could overwrite
 constexpr int kTsdfSegsPerLaunch = 32;
 int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, unsigned* colour, int w, int h);
+// nalo_tsdf_raycast (kernels_tsdf_raycast.hip, built without FMA contraction): one lane per pixel, an 8 x 8 tile to a wave. It reads the volume only.
+struct TsdfRaycastDev {
+    const float *tsdf, *weight; int nx, ny, nz;
+    float origin[3], vs, min_weight;
+    float R[9], t[3], fx, fy, cx, cy; int w, h;                                 // camToWorld rounded to float; the view
+    float min_depth, step; int N;                                               // z_n = min_depth + (float)n * step, n < N
+    const float* col; size_t col_plane;                                         // with_colour: the planes B, G, R, col_plane floats apart
+    float* depth; float* normal; unsigned* rgba;                                // [h][w], [h][w][3] (with_normals), [h][w] words R | G << 8 | B << 16 | A << 24 (with_colour)
+    unsigned long long* cnt;                                                    // n_hit, n_back, n_normal: zero before
+};
+int tsdf_raycast_launch(nalo_ctx* c, const TsdfRaycastDev& D);
 void tsdf_destroy(nalo_ctx* c);
 // host_ba.hip: frame_id (nalo_frame_state) of window frame host_frame, which ba_plane_inputs has validated
 int ba_frame_id(nalo_ctx* c, int host_frame);
