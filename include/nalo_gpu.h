@@ -1519,7 +1519,7 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    neighbour of v along +a INSIDE the sub-box, (v, a, n) is a crossing iff both weights are >= min_weight and (t0 < 0 && t1 >= 0) || (t0 >= 0 &&
  *                    t1 < 0) (a NaN fails both clauses); its point is centre(v) + e_a * (voxel_size * (t0 / (t0 - t1))), centre(v) the px, py, pz above.
  *                    Output in that order: a count pass, a scan, a write pass; no atomic append. n_needed is always set; cap < n_needed: NALO_ERR_ARG and nothing
- *                    is written. One wait.
+ *                    is written. One wait. The call uses 1 B of context-owned scratch per sub-box voxel (the mesh's mask bytes: these are its axis vertices).
  * nalo_tsdf_frustum_box   host only, needs no context: the culling box. In double: the world box of the camera apex (camToWorld's t) and the four far corners, the
  *                    rays through (uf, vf) in {0, w} x {0, h}, i.e. x = ((uf - 0.5) - cx) / fx, y = ((vf - 0.5) - cy) / fy, at z = max_depth + trunc. Per axis
  *                    lo = floor((min - origin) / voxel_size - 0.5) - 1 and hi = ceil((max - origin) / voxel_size - 0.5) + 2, clipped to [0, dim]: the voxels whose

@@ -1,5 +1,5 @@
 // The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
-// arithmetic lives in kernels_tsdf.hip and kernels_tsdf_mesh.hip (device) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table).
+// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_mesh.hip and kernels_tsdf_raycast.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table).
 #include <algorithm>
 #include <cmath>
 
@@ -17,11 +17,12 @@ struct TsdfVolume {
     DevBuf<unsigned long long> updated; HostBuf<unsigned long long> updated_h;
     nalo_tsdf_stats last{}; bool have_last = false;
     DevBuf<float> block;                             // nalo_tsdf_get / _set staging: one tile of z slices of the sub-block
-    DevBuf<int> cnt; HostBuf<int> cnt_h; DevBuf<float> xyz; HostBuf<float> xyz_h;   // nalo_tsdf_surface_points
+    DevBuf<float> xyz; HostBuf<float> xyz_h;         // nalo_tsdf_surface_points: as many points as the caller had room for
     DevBuf<unsigned long long> key; DevBuf<float> plane;                            // nalo_tsdf_integrate_frame: w h words each; key is zero between calls,
     bool key_dirty = false;                                                         // unless a call failed between its scatter and its resolve: the next one zeroes it
     std::vector<MapSeg> segs;                                                       // the frame's segments, host memory: they travel as kernel arguments
-    // nalo_tsdf_mesh: 5 B of scratch per sub-box voxel, the two count arrays, and the device mesh itself (nalo_tsdf_mesh_view names mesh_xyz / mesh_tri)
+    // nalo_tsdf_mesh: 5 B of scratch per sub-box voxel, the two count arrays, and the device mesh itself (nalo_tsdf_mesh_view names mesh_xyz / mesh_tri).
+    // nalo_tsdf_surface_points shares mesh_mask, mesh_cntv and mesh_cnt_h (tsdf_mesh_dev): every call rewrites them before it reads them
     DevBuf<unsigned char> mesh_mask; DevBuf<int> mesh_base, mesh_cntv, mesh_cntt; HostBuf<int> mesh_cnt_h;
     DevBuf<float> mesh_xyz; DevBuf<int> mesh_tri;
     long long mesh_nv = 0, mesh_nt = 0; bool have_mesh = false;
@@ -50,6 +51,46 @@ static int tsdf_need(nalo_ctx* c, const char* who) {
     if (!c->tsdf) return fail(c, NALO_ERR_STATE, std::string(who) + ": no volume (nalo_tsdf_create)");
     return NALO_OK;
 }
+static int tsdf_need_colour(nalo_ctx* c, const TsdfVolume& v, const std::string& who) {
+    return v.colour.p ? NALO_OK : fail(c, NALO_ERR_STATE, who + ": the volume holds no colour (nalo_tsdf_color_enable)");
+}
+
+// the grid as every kernel takes it; colour: with the colour planes (tsdf_need_colour has passed)
+static TsdfGridDev tsdf_grid(const TsdfVolume& v, bool colour) {
+    TsdfGridDev g{};
+    g.tsdf = v.tsdf.p; g.weight = v.weight.p; g.nx = v.d.dims[0]; g.ny = v.d.dims[1]; g.nz = v.d.dims[2];
+    for (int a = 0; a < 3; ++a) g.origin[a] = v.d.origin[a];
+    g.vs = v.d.voxel_size; g.col = colour ? v.colour.p : nullptr; g.col_plane = v.n;
+    return g;
+}
+
+// the box [lo, lo + size) a call works on, the caller's (use_box) or the whole grid, and its voxels (<= 2^29: nalo_tsdf_create). `what` names it in the refusal.
+// B may be NULL: the check alone, for a caller that goes on with its own lo and size
+struct TsdfBox { int lo[3], size[3]; long long total; };
+static int tsdf_sub_box(nalo_ctx* c, const std::string& who, const char* what, const TsdfVolume& v, bool use_box, const int lo[3], const int size[3], TsdfBox* B) {
+    TsdfBox own; if (!B) B = &own;
+    B->total = 1;
+    for (int k = 0; k < 3; ++k) {
+        B->lo[k] = use_box ? lo[k] : 0; B->size[k] = use_box ? size[k] : v.d.dims[k];
+        if (B->lo[k] < 0 || B->size[k] < 1 || B->lo[k] > v.d.dims[k] - B->size[k]) return fail(c, NALO_ERR_ARG, who + ": the " + what + " is empty or leaves the grid");
+        B->total *= B->size[k];
+    }
+    return NALO_OK;
+}
+
+// the TsdfMeshDev of a sub-box, with the scratch reserved that the mesh and the surface points share: a mask byte per voxel, the vertex counts, the pinned words
+// the totals come up in. The outputs (xyz, capv, and the mesh's vbase, cntt, tri, capt, rgba) are the caller's to fill in.
+static int tsdf_mesh_dev(nalo_ctx* c, TsdfVolume& v, const TsdfBox& B, float min_weight, bool coloured, TsdfMeshDev* D) {
+    *D = TsdfMeshDev{};
+    D->g = tsdf_grid(v, coloured);
+    for (int k = 0; k < 3; ++k) { D->lo[k] = B.lo[k]; D->size[k] = B.size[k]; }
+    D->total = (int)B.total; D->nb = (int)((B.total + kTsdfVoxPerBlock - 1) / kTsdfVoxPerBlock);
+    D->min_weight = min_weight;
+    NALO_HIP(c, v.mesh_mask.reserve((size_t)B.total + 3));                     // whole lanes of four voxels
+    NALO_HIP(c, v.mesh_cntv.reserve((size_t)D->nb + 1)); NALO_HIP(c, v.mesh_cnt_h.reserve(2));
+    D->vmask = v.mesh_mask.p; D->cntv = v.mesh_cntv.p;
+    return NALO_OK;
+}
 
 // the checks of both integrations behind the plane's own; M and the box on success
 static int tsdf_integrate_check(nalo_ctx* c, const char* who, const TsdfVolume& v, int w, int h, const float K[4], const double camToWorld[12], float min_depth, float max_depth,
@@ -68,14 +109,13 @@ static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth,
     nalo_tsdf_stats st{};
     if (hi[0] > lo[0]) {
         TsdfIntegrateDev D{};
-        D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
-        for (int a = 0; a < 3; ++a) { D.lo[a] = st.lo[a] = lo[a]; D.hi[a] = st.hi[a] = hi[a]; D.origin[a] = v.d.origin[a]; }
-        D.vs = v.d.voxel_size; D.trunc = v.d.trunc; D.max_weight = v.d.max_weight;
+        D.g = tsdf_grid(v, colour != nullptr);
+        for (int a = 0; a < 3; ++a) { D.lo[a] = st.lo[a] = lo[a]; D.hi[a] = st.hi[a] = hi[a]; }
+        D.trunc = v.d.trunc; D.max_weight = v.d.max_weight;
         std::copy(M, M + 12, D.M);
         D.fx = K[0]; D.fy = K[1]; D.cx = K[2]; D.cy = K[3]; D.min_depth = min_depth; D.max_depth = max_depth;
         D.depth = depth; D.sy = sy; D.sx = sx; D.w = w; D.h = h; D.updated = v.updated.p;
         if (colour) {
-            D.col = v.colour.p; D.col_plane = v.n;
             D.colour = colour->p; D.csy = colour->sy; D.csx = colour->sx;
             for (int X = 0; X < 3; ++X) D.csc[X] = colour->sc[X];
         }
@@ -155,7 +195,7 @@ static int tsdf_integrate_depth(nalo_ctx* c, const char* who, const nalo_tsdf_in
     if (!a) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
     NALO_HIP(c, hipSetDevice(c->device));
     TsdfVolume& v = *c->tsdf;
-    if (coloured && !v.colour.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (coloured) { const int rc = tsdf_need_colour(c, v, who); if (rc) return rc; }
     if (coloured && !colour) return fail(c, NALO_ERR_ARG, std::string(who) + ": no colour plane");
     { const int rc = nalo_dev_plane_check(c, &a->depth); if (rc) return rc; }
     if (a->depth.dtype != NALO_DT_F32 || a->depth.channels != 1) return fail(c, NALO_ERR_ARG, std::string(who) + ": the depth plane is one channel of F32");
@@ -240,10 +280,9 @@ int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
 static int tsdf_block(nalo_ctx* c, const char* who, const int lo[3], const int size[3], float* tsdf, float* weight, int to_volume, float* bgr = nullptr, bool colour = false) {
     { const int rc = tsdf_need(c, who); if (rc) return rc; }
     TsdfVolume& v = *c->tsdf;
-    if (colour && !v.colour.p) return fail(c, NALO_ERR_STATE, std::string(who) + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (colour) { const int rc = tsdf_need_colour(c, v, who); if (rc) return rc; }
     if (!lo || !size || (!tsdf && !weight && !bgr)) return fail(c, NALO_ERR_ARG, std::string(who) + ": bad argument");
-    for (int a = 0; a < 3; ++a)
-        if (lo[a] < 0 || size[a] < 1 || lo[a] > v.d.dims[a] - size[a]) return fail(c, NALO_ERR_ARG, std::string(who) + ": the block is empty or leaves the grid");
+    { const int rc = tsdf_sub_box(c, who, "block", v, true, lo, size, nullptr); if (rc) return rc; }
     NALO_HIP(c, hipSetDevice(c->device));
     // the block goes through a staging tile of whole z slices, at most kTsdfTileFloats (or one slice, at most 2048 x 2048 floats): never a second volume
     const size_t slice = (size_t)size[0] * size[1];
@@ -279,7 +318,7 @@ int nalo_tsdf_color_view(nalo_ctx* c, nalo_tsdf_color_volume_view* out) {
     { const int rc = tsdf_need(c, "nalo_tsdf_color_view"); if (rc) return rc; }
     if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_color_view: bad argument");
     const TsdfVolume& v = *c->tsdf;
-    if (!v.colour.p) return fail(c, NALO_ERR_STATE, "nalo_tsdf_color_view: the volume holds no colour (nalo_tsdf_color_enable)");
+    { const int rc = tsdf_need_colour(c, v, "nalo_tsdf_color_view"); if (rc) return rc; }
     out->bgr = v.colour.p;
     for (int a = 0; a < 3; ++a) out->dims[a] = v.d.dims[a];
     out->stream = (void*)(hipStream_t)c->stream;
@@ -303,29 +342,28 @@ int nalo_tsdf_surface_points(nalo_ctx* c, nalo_tsdf_surface_args* a) {
     a->n = 0; a->n_needed = 0;
     TsdfVolume& v = *c->tsdf;
     if (a->cap < 0 || (a->cap > 0 && !a->xyz) || std::isnan(a->min_weight)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: bad argument");
-    TsdfSurfaceDev D{};
-    for (int k = 0; k < 3; ++k) {
-        D.lo[k] = a->use_box ? a->lo[k] : 0; D.size[k] = a->use_box ? a->size[k] : v.d.dims[k];
-        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: the sub-box is empty or leaves the grid");
-        D.origin[k] = v.d.origin[k];
-    }
+    TsdfBox B;
+    { const int rc = tsdf_sub_box(c, who, "sub-box", v, a->use_box != 0, a->lo, a->size, &B); if (rc) return rc; }
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "tsdf_surface_points");
-    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
-    D.total = D.size[0] * D.size[1] * D.size[2];                               // <= 2^29; three crossings a voxel stay below 2^31
-    D.nb = (D.total + kTsdfSurfVoxPerBlock - 1) / kTsdfSurfVoxPerBlock;
-    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
+    // the mesh's vertices on the axis edges: its classify and vertex pass, into this call's own xyz. The device mesh is not touched. Three crossings a voxel
+    // of 2^29 stay below 2^31
+    TsdfMeshDev D;
+    { const int rc = tsdf_mesh_dev(c, v, B, a->min_weight, false, &D); if (rc) return rc; }
     // the device holds room for what the caller has room for, and never for more than the sub-box can give
     const long long room = std::min<long long>(a->cap, 3LL * D.total);
-    NALO_HIP(c, v.cnt.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.cnt_h.reserve(1));
     NALO_HIP(c, v.xyz.reserve(3 * (size_t)std::max<long long>(room, 1))); NALO_HIP(c, v.xyz_h.reserve(3 * (size_t)std::max<long long>(room, 1)));
-    D.cnt = v.cnt.p; D.xyz = v.xyz.p; D.cap = room;
-    { const int rc = tsdf_surface_launch(c, D); if (rc) return rc; }
+    D.xyz = v.xyz.p; D.capv = room;
+    {
+        ProfScope ps(c, "tsdf_surface");
+        { const int rc = tsdf_mesh_classify_launch(c, D, true); if (rc) return rc; }
+        if (room > 0) { const int rc = tsdf_mesh_write_launch(c, D, true); if (rc) return rc; }
+    }
     // the count is known only behind the scan: everything the call may have written comes up in the one wait
-    NALO_HIP(c, hipMemcpyAsync(v.cnt_h.p, D.cnt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p, D.cntv + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
     if (room > 0) NALO_HIP(c, hipMemcpyAsync(v.xyz_h.p, v.xyz.p, 3 * (size_t)room * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
-    const long long need = v.cnt_h.p[0];
+    const long long need = v.mesh_cnt_h.p[0];
     if (need < 0 || need > 3LL * D.total) return fail(c, NALO_ERR_HIP, "nalo_tsdf_surface_points: the device counted more crossings than the sub-box can hold");
     a->n_needed = need;
     if (a->cap < need) return fail(c, NALO_ERR_ARG, "nalo_tsdf_surface_points: cap is below the crossings found (n_needed)");
@@ -340,44 +378,37 @@ static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a
     if (!a || (coloured && !cc)) return fail(c, NALO_ERR_ARG, who + ": bad argument");
     a->n_vertices = 0; a->n_triangles = 0;
     TsdfVolume& v = *c->tsdf;
-    if (coloured && !v.colour.p) return fail(c, NALO_ERR_STATE, who + ": the volume holds no colour (nalo_tsdf_color_enable)");
+    if (coloured) { const int rc = tsdf_need_colour(c, v, who); if (rc) return rc; }
     if (a->cap_vertices < 0 || a->cap_triangles < 0 || (a->cap_vertices > 0 && !a->xyz) || (a->cap_triangles > 0 && !a->tri) || std::isnan(a->min_weight) ||
         (coloured && (cc->cap < 0 || (cc->cap > 0 && !cc->rgba))))
         return fail(c, NALO_ERR_ARG, who + ": bad argument");
-    TsdfMeshDev D{};
-    long long total = 1;
-    for (int k = 0; k < 3; ++k) {
-        D.lo[k] = a->use_box ? a->lo[k] : 0; D.size[k] = a->use_box ? a->size[k] : v.d.dims[k];
-        if (D.lo[k] < 0 || D.size[k] < 1 || D.lo[k] > v.d.dims[k] - D.size[k]) return fail(c, NALO_ERR_ARG, who + ": the sub-box is empty or leaves the grid");
-        D.origin[k] = v.d.origin[k];
-        total *= D.size[k];
-    }
+    TsdfBox B;
+    { const int rc = tsdf_sub_box(c, who, "sub-box", v, a->use_box != 0, a->lo, a->size, &B); if (rc) return rc; }
+    const long long total = B.total;
     if (total > kTsdfMeshMaxVoxels) return fail(c, NALO_ERR_ARG, who + ": the sub-box holds more than 2^28 voxels");
     // ---- accepted: from here on only the runtime can fail, or a host array turn out too small for what the device found
     NALO_HIP(c, hipSetDevice(c->device));
     HostTimer ht(c, "tsdf_mesh");
-    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
-    D.total = (int)total; D.nb = (D.total + kTsdfSurfVoxPerBlock - 1) / kTsdfSurfVoxPerBlock;
-    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
-    NALO_HIP(c, v.mesh_mask.reserve((size_t)total + 3)); NALO_HIP(c, v.mesh_base.reserve((size_t)total + 3));      // whole lanes of four voxels
-    NALO_HIP(c, v.mesh_cntv.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.mesh_cntt.reserve((size_t)D.nb + 1)); NALO_HIP(c, v.mesh_cnt_h.reserve(2));
+    TsdfMeshDev D;
+    { const int rc = tsdf_mesh_dev(c, v, B, a->min_weight, coloured, &D); if (rc) return rc; }
+    NALO_HIP(c, v.mesh_base.reserve((size_t)total + 3)); NALO_HIP(c, v.mesh_cntt.reserve((size_t)D.nb + 1));      // mesh_base: whole lanes of four voxels
     if (!v.mesh_xyz.p || !v.mesh_tri.p) {                                      // both or neither: a failure leaves neither
         DevBuf<float> xyz; DevBuf<int> tri;
         NALO_HIP(c, xyz.reserve(3 * (size_t)kTsdfMeshFirstVertices)); NALO_HIP(c, tri.reserve(3 * (size_t)kTsdfMeshFirstTriangles));
         v.mesh_xyz = std::move(xyz); v.mesh_tri = std::move(tri);
     }
-    D.vmask = v.mesh_mask.p; D.vbase = v.mesh_base.p; D.cntv = v.mesh_cntv.p; D.cntt = v.mesh_cntt.p;
+    D.vbase = v.mesh_base.p; D.cntt = v.mesh_cntt.p;
     D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = (long long)(v.mesh_xyz.cap / 3); D.capt = (long long)(v.mesh_tri.cap / 3);
     if (coloured) {
         // a word per vertex xyz has room for. It can be short only behind plain meshes that grew xyz, and then holds no mesh's colours (mesh_coloured is false)
         if (v.mesh_rgba.cap < (size_t)D.capv) { v.mesh_coloured = false; NALO_HIP(c, v.mesh_rgba.reserve((size_t)D.capv)); }
-        D.col = v.colour.p; D.col_plane = v.n; D.rgba = v.mesh_rgba.p;
+        D.rgba = v.mesh_rgba.p;
     }
     // all four passes against the room there is: the steady state waits once, for the two totals
     {
         ProfScope ps(c, "tsdf_mesh");
-        { const int rc = tsdf_mesh_classify_launch(c, D); if (rc) return rc; }
-        { const int rc = tsdf_mesh_write_launch(c, D); if (rc) return rc; }
+        { const int rc = tsdf_mesh_classify_launch(c, D, false); if (rc) return rc; }
+        { const int rc = tsdf_mesh_write_launch(c, D, false); if (rc) return rc; }
     }
     NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p, D.cntv + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(v.mesh_cnt_h.p + 1, D.cntt + D.nb, 4, hipMemcpyDeviceToHost, c->stream));
@@ -396,7 +427,7 @@ static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a
         D.xyz = v.mesh_xyz.p; D.tri = v.mesh_tri.p; D.capv = rv; D.capt = rt;
         if (coloured) { v.mesh_rgba = std::move(rgba); D.rgba = v.mesh_rgba.p; }
         ProfScope ps(c, "tsdf_mesh");
-        { const int rc = tsdf_mesh_write_launch(c, D); if (rc) return rc; }
+        { const int rc = tsdf_mesh_write_launch(c, D, false); if (rc) return rc; }
     }
     v.mesh_nv = nv; v.mesh_nt = nt; v.have_mesh = true; v.mesh_coloured = coloured;
     a->n_vertices = nv; a->n_triangles = nt;
@@ -440,7 +471,7 @@ int nalo_tsdf_raycast(nalo_ctx* c, nalo_tsdf_raycast_args* a) {
     a->n_hit = a->n_back = a->n_normal = 0; a->n_steps = 0;
     { const int rc = tsdf_need(c, who); if (rc) return rc; }
     TsdfVolume& v = *c->tsdf;
-    if (a->with_colour && !v.colour.p) return fail(c, NALO_ERR_STATE, "nalo_tsdf_raycast: the volume holds no colour (nalo_tsdf_color_enable)");
+    if (a->with_colour) { const int rc = tsdf_need_colour(c, v, who); if (rc) return rc; }
     if (a->w < 1 || a->h < 1 || (long long)a->w * a->h > (1LL << 26)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: w or h < 1, or more than 2^26 pixels");
     for (int i = 0; i < 4; ++i) if (!std::isfinite(a->K[i])) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: K is not finite");
     if (a->K[0] == 0.0f || a->K[1] == 0.0f) return fail(c, NALO_ERR_ARG, "nalo_tsdf_raycast: fx or fy is 0");
@@ -473,15 +504,14 @@ int nalo_tsdf_raycast(nalo_ctx* c, nalo_tsdf_raycast_args* a) {
         if (rgba.p) v.rc_rgba = std::move(rgba);
     }
     TsdfRaycastDev D{};
-    D.tsdf = v.tsdf.p; D.weight = v.weight.p; D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2];
+    D.g = tsdf_grid(v, col);
     for (int k = 0; k < 3; ++k) {
-        D.origin[k] = v.d.origin[k]; D.t[k] = (float)a->camToWorld[4 * k + 3];
+        D.t[k] = (float)a->camToWorld[4 * k + 3];
         for (int j = 0; j < 3; ++j) D.R[3 * k + j] = (float)a->camToWorld[4 * k + j];
     }
-    D.vs = v.d.voxel_size; D.min_weight = a->min_weight;
+    D.min_weight = a->min_weight;
     D.fx = a->K[0]; D.fy = a->K[1]; D.cx = a->K[2]; D.cy = a->K[3]; D.w = a->w; D.h = a->h;
     D.min_depth = a->min_depth; D.step = a->step; D.N = N;
-    D.col = col ? v.colour.p : nullptr; D.col_plane = v.n;
     D.depth = v.rc_depth.p; D.normal = nrm ? v.rc_normal.p : nullptr; D.rgba = col ? v.rc_rgba.p : nullptr; D.cnt = v.rc_cnt.p;
     v.have_rc = false;                                                         // until the new images are queued
     NALO_HIP(c, hipMemsetAsync(v.rc_cnt.p, 0, 3 * sizeof(unsigned long long), c->stream));

@@ -1,7 +1,8 @@
-// The TSDF volume's kernels (include/nalo_gpu.h, "tsdf=1"): the projective integration of one depth plane over the culling box, the surface points as an ordered
-// compaction, the sub-block copies and the plane nalo_tsdf_integrate_frame makes of a frame's dense list. Built WITHOUT FMA contraction: every expression below
-// is the header's definition, one rounding per operation.
+// The TSDF volume's kernels (include/nalo_gpu.h, "tsdf=1"): the projective integration of one depth plane over the culling box, the sub-block copies and the
+// plane nalo_tsdf_integrate_frame makes of a frame's dense list. (The surface points are kernels_tsdf_mesh.hip's: the mesh's passes on the axis edges.) Built
+// WITHOUT FMA contraction: every expression below is the header's definition, one rounding per operation.
 #include "nalo_internal.h"
+#include "tsdf_device.h"
 
 namespace nalo {
 
@@ -15,7 +16,7 @@ struct TsdfRow { float m1y, m2z, m5y, m6z, m9y, m10z; };                        
 // kColour: a voxel that is updated also hands back the weight BEFORE the update and its pixel's colour bytes, packed B | G << 8 | R << 16
 template <bool kColour>
 __device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const TsdfRow& R, int i, float& t, float& w, float& wb, unsigned& bgr) {
-    const float px = P.origin[0] + ((float)i + 0.5f) * P.vs;
+    const float px = tsdf_centre(P.g, 0, i);
     const float xc = ((P.M[0] * px + R.m1y) + R.m2z) + P.M[3];
     const float yc = ((P.M[4] * px + R.m5y) + R.m6z) + P.M[7];
     const float zc = ((P.M[8] * px + R.m9y) + R.m10z) + P.M[11];
@@ -54,14 +55,14 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P,
     if (row < rows) {
         const int bny = P.hi[1] - P.lo[1];
         const int j = P.lo[1] + row % bny, k = P.lo[2] + row / bny;
-        const long long base = ((long long)k * P.ny + j) * P.nx;                 // linear index of voxel (0, j, k)
+        const long long base = tsdf_index(P.g, k, j, 0);
         const long long rb = base + P.lo[0], re = base + P.hi[0];
         const long long g = (rb & ~3LL) + 4LL * ((long long)bx * tx + lx);
         if (g < re) {
-            const float py = P.origin[1] + ((float)j + 0.5f) * P.vs, pz = P.origin[2] + ((float)k + 0.5f) * P.vs;
+            const float py = tsdf_centre(P.g, 1, j), pz = tsdf_centre(P.g, 2, k);
             const TsdfRow R = {P.M[1] * py, P.M[2] * pz, P.M[5] * py, P.M[6] * pz, P.M[9] * py, P.M[10] * pz};
             if (g >= rb && g + 4 <= re) {
-                float4 t = *reinterpret_cast<const float4*>(P.tsdf + g), w = *reinterpret_cast<const float4*>(P.weight + g);
+                float4 t = *reinterpret_cast<const float4*>(P.g.tsdf + g), w = *reinterpret_cast<const float4*>(P.g.weight + g);
                 const int i = (int)(g - base);
                 float4 wb; uint4 bgr;                                               // kColour only: of the voxels that were updated
                 const bool u0 = tsdf_voxel<kColour>(P, R, i, t.x, w.x, wb.x, bgr.x);
@@ -69,13 +70,13 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P,
                 const bool u2 = tsdf_voxel<kColour>(P, R, i + 2, t.z, w.z, wb.z, bgr.z);
                 const bool u3 = tsdf_voxel<kColour>(P, R, i + 3, t.w, w.w, wb.w, bgr.w);
                 n += (int)u0 + (int)u1 + (int)u2 + (int)u3;
-                if (n) { *reinterpret_cast<float4*>(P.tsdf + g) = t; *reinterpret_cast<float4*>(P.weight + g) = w; }
+                if (n) { *reinterpret_cast<float4*>(P.g.tsdf + g) = t; *reinterpret_cast<float4*>(P.g.weight + g) = w; }
                 if constexpr (kColour) {
                     // the colour of a lane moves only when one of its four voxels was updated; a voxel that was not goes back with the word that was loaded
                     if (n) {
 #pragma unroll
                         for (int X = 0; X < 3; ++X) {
-                            float4* at = reinterpret_cast<float4*>(P.col + (size_t)X * P.col_plane + g);
+                            float4* at = reinterpret_cast<float4*>(P.g.col + (size_t)X * P.g.col_plane + g);
                             float4 cv = *at;
                             if (u0) cv.x = tsdf_colour(cv.x, wb.x, bgr.x, X);
                             if (u1) cv.y = tsdf_colour(cv.y, wb.y, bgr.y, X);
@@ -87,12 +88,12 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P,
                 }
             } else {
                 for (long long q = g < rb ? rb : g; q < g + 4 && q < re; ++q) {
-                    float t = P.tsdf[q], w = P.weight[q], wb; unsigned bgr;
+                    float t = P.g.tsdf[q], w = P.g.weight[q], wb; unsigned bgr;
                     if (tsdf_voxel<kColour>(P, R, (int)(q - base), t, w, wb, bgr)) {
-                        P.tsdf[q] = t; P.weight[q] = w; ++n;
+                        P.g.tsdf[q] = t; P.g.weight[q] = w; ++n;
                         if constexpr (kColour) {
 #pragma unroll
-                            for (int X = 0; X < 3; ++X) { float* at = P.col + (size_t)X * P.col_plane + q; *at = tsdf_colour(*at, wb, bgr, X); }
+                            for (int X = 0; X < 3; ++X) { float* at = P.g.col + (size_t)X * P.g.col_plane + q; *at = tsdf_colour(*at, wb, bgr, X); }
                         }
                     }
                 }
@@ -120,7 +121,7 @@ int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D) {
     const long long blocks = (long long)gx * ((rows + ry - 1) / ry);
     if (blocks > INT32_MAX) return fail(c, NALO_ERR_ARG, "tsdf_integrate_launch: the box needs more workgroups than a grid has");
     ProfScope ps(c, "tsdf_integrate");
-    if (D.col) tsdf_integrate_kernel<true><<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
+    if (D.g.col) tsdf_integrate_kernel<true><<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
     else tsdf_integrate_kernel<false><<<(unsigned)blocks, 256, 0, c->stream>>>(D, txl, gx, (int)rows);
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
@@ -141,12 +142,12 @@ int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n) {
     return NALO_OK;
 }
 
-struct TsdfBlock { int nx, ny, lo[3], size[3]; };
+struct TsdfBlock { int nx, ny, lo[3], size[3]; };                               // the copy serves any one array of the grid: it takes the two dims the index needs
 __global__ __launch_bounds__(256) void tsdf_block_kernel(float* vol, float* block, TsdfBlock B, int total, int to_volume) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= total) return;
     const int x = q % B.size[0], y = (q / B.size[0]) % B.size[1], z = q / (B.size[0] * B.size[1]);
-    const size_t at = ((size_t)(B.lo[2] + z) * B.ny + (B.lo[1] + y)) * B.nx + (B.lo[0] + x);
+    const size_t at = ((size_t)(B.lo[2] + z) * B.ny + (B.lo[1] + y)) * B.nx + (B.lo[0] + x);      // tsdf_index of the voxel, on the two dims the copy holds
     if (to_volume) vol[at] = block[q]; else block[q] = vol[at];
 }
 int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume) {
@@ -154,77 +155,6 @@ int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], 
     const int total = size[0] * size[1] * size[2];                               // <= 2^29, checked by the caller
     tsdf_block_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(vol, block, B, total, to_volume);
     NALO_HIP(c, hipGetLastError());
-    return NALO_OK;
-}
-
-// ---- surface points: voxel order (k, j, i) of the sub-box, axis order x, y, z. A lane takes four consecutive voxels of the sub-box, so lane order is output order.
-__device__ __forceinline__ bool tsdf_crossing(float t0, float w0, float t1, float w1, float min_weight) {
-    return w0 >= min_weight && w1 >= min_weight && ((t0 < 0.0f && t1 >= 0.0f) || (t0 >= 0.0f && t1 < 0.0f));
-}
-// the crossings of sub-box voxel q; out != NULL: their points, 3 floats each
-__device__ __forceinline__ int tsdf_surface_voxel(const TsdfSurfaceDev& P, int q, float* out) {
-    const int x = q % P.size[0], y = (q / P.size[0]) % P.size[1], z = q / (P.size[0] * P.size[1]);
-    const int i = P.lo[0] + x, j = P.lo[1] + y, k = P.lo[2] + z;
-    const size_t at = ((size_t)k * P.ny + j) * P.nx + i;
-    const float t0 = P.tsdf[at], w0 = P.weight[at];
-    const size_t step[3] = {1, (size_t)P.nx, (size_t)P.nx * P.ny};
-    const bool inside[3] = {x + 1 < P.size[0], y + 1 < P.size[1], z + 1 < P.size[2]};
-    int n = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (!inside[a]) continue;
-        const float t1 = P.tsdf[at + step[a]], w1 = P.weight[at + step[a]];
-        if (!tsdf_crossing(t0, w0, t1, w1, P.min_weight)) continue;
-        if (out) {
-            float p[3] = {P.origin[0] + ((float)i + 0.5f) * P.vs, P.origin[1] + ((float)j + 0.5f) * P.vs, P.origin[2] + ((float)k + 0.5f) * P.vs};
-            p[a] = p[a] + P.vs * (t0 / (t0 - t1));
-            out[3 * n] = p[0]; out[3 * n + 1] = p[1]; out[3 * n + 2] = p[2];
-        }
-        ++n;
-    }
-    return n;
-}
-// exclusive prefix of v over the workgroup's 256 lanes; *sum: the workgroup's total
-__device__ __forceinline__ int tsdf_block_scan(int v, int* sum) {
-    __shared__ int ws[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-    if (lane == 63) ws[wv] = inc;
-    __syncthreads();
-    int off = 0;
-    for (int q = 0; q < wv; ++q) off += ws[q];
-    *sum = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-    return off + inc - v;
-}
-__global__ __launch_bounds__(256) void tsdf_surface_count_kernel(TsdfSurfaceDev P) {
-    const long long q0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    int n = 0;
-    for (int e = 0; e < 4; ++e) if (q0 + e < P.total) n += tsdf_surface_voxel(P, (int)(q0 + e), nullptr);
-    int sum;
-    (void)tsdf_block_scan(n, &sum);
-    if (threadIdx.x == 0) P.cnt[blockIdx.x] = sum;
-}
-__global__ __launch_bounds__(256) void tsdf_surface_write_kernel(TsdfSurfaceDev P) {
-    const long long q0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-    float pts[4][9];
-    int ne[4] = {0, 0, 0, 0}, n = 0;
-    const bool fits = (long long)P.cnt[P.nb] <= P.cap;                            // the scanned sum: nothing is written when the caller's room is too small
-    if (fits) for (int e = 0; e < 4; ++e) if (q0 + e < P.total) { ne[e] = tsdf_surface_voxel(P, (int)(q0 + e), pts[e]); n += ne[e]; }
-    int sum;
-    long long at = (long long)P.cnt[blockIdx.x] + tsdf_block_scan(n, &sum);
-    for (int e = 0; e < 4; ++e)
-        for (int m = 0; m < ne[e]; ++m, ++at) { P.xyz[3 * at] = pts[e][3 * m]; P.xyz[3 * at + 1] = pts[e][3 * m + 1]; P.xyz[3 * at + 2] = pts[e][3 * m + 2]; }
-}
-int tsdf_surface_launch(nalo_ctx* c, const TsdfSurfaceDev& D) {
-    ProfScope ps(c, "tsdf_surface");
-    tsdf_surface_count_kernel<<<D.nb, 256, 0, c->stream>>>(D);
-    NALO_HIP(c, hipGetLastError());
-    { const int rc = scan_ints_launch(c, D.cnt, D.nb); if (rc) return rc; }
-    if (D.cap > 0) {
-        tsdf_surface_write_kernel<<<D.nb, 256, 0, c->stream>>>(D);
-        NALO_HIP(c, hipGetLastError());
-    }
     return NALO_OK;
 }
 

@@ -5,6 +5,7 @@
 #include <cfloat>
 
 #include "nalo_internal.h"
+#include "tsdf_device.h"
 
 namespace nalo {
 
@@ -13,12 +14,13 @@ namespace nalo {
 template <bool kWeights>
 __device__ __forceinline__ bool tsdf_rc_field(const TsdfRaycastDev& P, const float* __restrict__ vol, float qx, float qy, float qz, float& S) {
     const float ix = floorf(qx), iy = floorf(qy), iz = floorf(qz);
-    if (!(ix >= 0.0f && ix <= (float)(P.nx - 2) && iy >= 0.0f && iy <= (float)(P.ny - 2) && iz >= 0.0f && iz <= (float)(P.nz - 2))) return false;
+    if (!(ix >= 0.0f && ix <= (float)(P.g.nx - 2) && iy >= 0.0f && iy <= (float)(P.g.ny - 2) && iz >= 0.0f && iz <= (float)(P.g.nz - 2))) return false;
     const float fx = qx - ix, fy = qy - iy, fz = qz - iz;
-    const long long sy = P.nx, sz = (long long)P.nx * P.ny;
-    const long long at = ((long long)(int)iz * P.ny + (long long)(int)iy) * P.nx + (long long)(int)ix;   // corner (1, 1, 1) is at most voxel (nx - 1, ny - 1, nz - 1)
+    const long long sy = P.g.nx, sz = (long long)P.g.nx * P.g.ny;
+    // tsdf_index of the cell, written out: each conversion sits where the sum takes it up, and the compiler's order of this kernel's instructions follows that
+    const long long at = ((long long)(int)iz * P.g.ny + (long long)(int)iy) * P.g.nx + (long long)(int)ix;   // corner (1, 1, 1) is at most voxel (nx - 1, ny - 1, nz - 1)
     if constexpr (kWeights) {
-        const float* w = P.weight + at;
+        const float* w = P.g.weight + at;
         const float mw = P.min_weight;
         const bool ok = (w[0] >= mw) & (w[1] >= mw) & (w[sy] >= mw) & (w[sy + 1] >= mw) & (w[sz] >= mw) & (w[sz + 1] >= mw) & (w[sz + sy] >= mw) & (w[sz + sy + 1] >= mw);
         if (!ok) return false;
@@ -37,7 +39,7 @@ __device__ __forceinline__ void tsdf_rc_point(const TsdfRaycastDev& P, const flo
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float p = P.t[a] + d[a] * z;
-        q[a] = ((p - P.origin[a]) / P.vs) - 0.5f;
+        q[a] = ((p - P.g.origin[a]) / P.g.vs) - 0.5f;
     }
 }
 
@@ -46,13 +48,13 @@ __device__ __forceinline__ void tsdf_rc_point(const TsdfRaycastDev& P, const flo
 // the definition's p, q and z_n is below 1e-6 of them), the interval by two steps either side, clipped to [0, N). Empty: n0 > n1.
 __device__ __forceinline__ void tsdf_rc_interval(const TsdfRaycastDev& P, const float d[3], int& n0, int& n1) {
     n0 = 0; n1 = -1;
-    const int dim[3] = {P.nx, P.ny, P.nz};
+    const int dim[3] = {P.g.nx, P.g.ny, P.g.nz};
     const double zl = (double)P.min_depth + (double)(P.N - 1) * (double)P.step;
     double zlo = -1e300, zhi = 1e300;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         if (!(fabsf(d[a]) <= FLT_MAX) || dim[a] < 2) return;                     // a direction that is not finite makes every p, hence every sample, invalid
-        const double o = (double)P.t[a], g = (double)P.origin[a], vs = (double)P.vs, da = (double)d[a];
+        const double o = (double)P.t[a], g = (double)P.g.origin[a], vs = (double)P.g.vs, da = (double)d[a];
         const double m = vs + 1e-5 * (fabs(o) + fabs(g) + fabs(da) * zl + (double)dim[a] * vs);
         const double lo = g + 0.5 * vs - m, hi = g + ((double)dim[a] - 0.5) * vs + m;
         if (da == 0.0) { if (o < lo || o > hi) return; continue; }
@@ -66,8 +68,6 @@ __device__ __forceinline__ void tsdf_rc_interval(const TsdfRaycastDev& P, const 
     if (!(a <= b)) return;                                                     // compared as doubles before the conversion
     n0 = (int)a; n1 = (int)b;
 }
-
-__device__ __forceinline__ unsigned tsdf_rc_byte(float c) { return (unsigned)(int)(fminf(fmaxf(c, 0.0f), 255.0f) + 0.5f); }
 
 template <bool kNormals, bool kColour>
 __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int gx) {
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
             const float z = P.min_depth + (float)n * P.step;
             float q[3], S = 0.0f;
             tsdf_rc_point(P, d, z, q);
-            const bool ok = tsdf_rc_field<true>(P, P.tsdf, q[0], q[1], q[2], S);
+            const bool ok = tsdf_rc_field<true>(P, P.g.tsdf, q[0], q[1], q[2], S);
             if (ok && pv && ((ps < 0.0f) != (S < 0.0f))) {
                 if (!(ps < 0.0f)) {                                            // outside to inside: the front face (-0.0f is outside)
                     hit = 1;
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
             for (int a = 0; a < 3; ++a) {
                 float qp[3] = {q[0], q[1], q[2]}, qm[3] = {q[0], q[1], q[2]}, sp = 0.0f, sm = 0.0f;
                 qp[a] = q[a] + 1.0f; qm[a] = q[a] - 1.0f;
-                const bool okp = tsdf_rc_field<true>(P, P.tsdf, qp[0], qp[1], qp[2], sp), okm = tsdf_rc_field<true>(P, P.tsdf, qm[0], qm[1], qm[2], sm);
+                const bool okp = tsdf_rc_field<true>(P, P.g.tsdf, qp[0], qp[1], qp[2], sp), okm = tsdf_rc_field<true>(P, P.g.tsdf, qm[0], qm[1], qm[2], sm);
                 all = all && okp && okm;
                 G[a] = sp - sm;
             }
@@ -132,10 +132,10 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
         if constexpr (kColour) {
             float cb = 0.0f, cg = 0.0f, cr = 0.0f;
             rgba = 0xFF000000u;                                                // the index test fails at q*: 0, 0, 0, 255
-            if (tsdf_rc_field<false>(P, P.col, q[0], q[1], q[2], cb)) {
-                (void)tsdf_rc_field<false>(P, P.col + P.col_plane, q[0], q[1], q[2], cg);
-                (void)tsdf_rc_field<false>(P, P.col + 2 * P.col_plane, q[0], q[1], q[2], cr);
-                rgba = tsdf_rc_byte(cr) | (tsdf_rc_byte(cg) << 8) | (tsdf_rc_byte(cb) << 16) | 0xFF000000u;
+            if (tsdf_rc_field<false>(P, P.g.col, q[0], q[1], q[2], cb)) {
+                (void)tsdf_rc_field<false>(P, P.g.col + P.g.col_plane, q[0], q[1], q[2], cg);
+                (void)tsdf_rc_field<false>(P, P.g.col + 2 * P.g.col_plane, q[0], q[1], q[2], cr);
+                rgba = tsdf_colour_byte(cr) | (tsdf_colour_byte(cg) << 8) | (tsdf_colour_byte(cb) << 16) | 0xFF000000u;
             }
         }
     }

@@ -14,6 +14,7 @@
 #include "../../include/nalo_gpu.h"
 #include "host_math.h"
 #include "ref_constants.h"
+#include "tsdf_device.h"
 
 namespace nalo {
 
@@ -451,42 +452,37 @@ int dense_update_finish(nalo_ctx* c, int slot, const nalo_plane_cluster* cluster
 // nothing is queued or staged). NALO_ERR_STATE without the dense archive or on a sharded window, NALO_ERR_ARG for a frame_id the archive has never seen; a frame
 // without points gives total = 0
 int map_dense_segments(nalo_ctx* c, const char* who, int frame_id, std::vector<MapSeg>* segs, int* total);
-// ---- the TSDF volume (nalo_tsdf_*; host_tsdf.hip, host_tsdf.cpp, kernels_tsdf.hip). kernels_tsdf.hip is built without FMA contraction: its arithmetic is the
-// definition in include/nalo_gpu.h, operation by operation.
+// ---- the TSDF volume (nalo_tsdf_*; host_tsdf.hip, host_tsdf.cpp, kernels_tsdf*.hip). The kernel files are built without FMA contraction: their arithmetic is the
+// definition in include/nalo_gpu.h, operation by operation. Every kernel-argument struct below embeds the grid (tsdf_device.h: TsdfGridDev), which
+// host_tsdf.hip fills in one place.
 struct TsdfIntegrateDev {
-    float *tsdf, *weight; int nx, ny, nz;
+    TsdfGridDev g;                                                              // g.col != NULL selects the coloured instantiation; tsdf, weight and col are written
     int lo[3], hi[3];                                                           // the culling box, hi exclusive, not empty
-    float origin[3], vs, trunc, max_weight, M[12], fx, fy, cx, cy, min_depth, max_depth;
+    float trunc, max_weight, M[12], fx, fy, cx, cy, min_depth, max_depth;
     const char* depth; long long sy, sx; int w, h;                              // the plane by byte strides
     unsigned long long* updated;                                                // zero before
-    // colour, behind everything the uncoloured kernel reads: col != NULL selects the coloured instantiation. col: [3][nz][ny][nx], planes B, G, R, col_plane
-    // floats apart; the pixel's bytes lie at colour + pv csy + pu csx + csc[plane] (csc already holds the B, G, R order of the caller's channels)
-    float* col; size_t col_plane;
+    // colour: the pixel's bytes lie at colour + pv csy + pu csx + csc[plane] (csc already holds the B, G, R order of the caller's channels)
     const unsigned char* colour; long long csy, csx, csc[3];
 };
 int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D);
 int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
 // one array's sub-block [lo, lo + size) to (to_volume = 0) or from (1) a contiguous block, x fastest
 int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume);
-constexpr int kTsdfSurfVoxPerBlock = 1024;                                      // 256 lanes x 4 consecutive voxels of the sub-box
-struct TsdfSurfaceDev {
-    const float *tsdf, *weight; int nx, ny, nz, lo[3], size[3], total, nb;      // total: voxels of the sub-box; nb: its workgroups
-    float origin[3], vs, min_weight;
-    int* cnt;                                                                   // [nb + 1]: crossings per workgroup, scanned; [nb] the sum
-    float* xyz; long long cap;                                                  // written only when the sum fits
-};
-int tsdf_surface_launch(nalo_ctx* c, const TsdfSurfaceDev& D);                  // count, scan, write on c->stream
-// nalo_tsdf_mesh (kernels_tsdf_mesh.hip, built without FMA contraction): the surface points' work split, kTsdfSurfVoxPerBlock voxels of the sub-box to a workgroup
+// nalo_tsdf_mesh and nalo_tsdf_surface_points (kernels_tsdf_mesh.hip): an ordered compaction over the sub-box, kTsdfVoxPerBlock voxels to a workgroup. The
+// surface points are the mesh's vertices on the axis edges: they run the classify and the vertex pass restricted to those, and no triangle pass.
+constexpr int kTsdfVoxPerBlock = 1024;                                          // 256 lanes x 4 consecutive voxels of the sub-box
 struct TsdfMeshDev {
-    const float *tsdf, *weight; int nx, ny, nz, lo[3], size[3], total, nb;      // total: voxels of the sub-box (<= 2^28); nb: its workgroups
-    float origin[3], vs, min_weight;
+    int lo[3], size[3], total, nb;                                              // total: voxels of the sub-box (<= 2^28; the surface points: 2^29); nb: its workgroups
+    TsdfGridDev g;                                                              // read only; g.col != NULL: nalo_tsdf_mesh_color. Behind the box: the triangle pass keeps its instruction order so
+    float min_weight;
     unsigned char* vmask; int* vbase;                                           // [total + 3] each (a lane stores its four at once): a voxel's edges that carry a vertex (bit m - 1), the index of its first vertex
     int *cntv, *cntt;                                                           // [nb + 1] each: vertices / triangles per workgroup, scanned; [nb] the sums (cntt read as unsigned)
     float* xyz; int* tri; long long capv, capt;                                 // written only when both sums fit
-    const float* col; size_t col_plane; unsigned* rgba;                         // nalo_tsdf_mesh_color (col != NULL): the colour planes, and [capv] vertex colours R | G << 8 | B << 16 | 255 << 24
+    unsigned* rgba;                                                             // nalo_tsdf_mesh_color: [capv] vertex colours R | G << 8 | B << 16 | 255 << 24
 };
-int tsdf_mesh_classify_launch(nalo_ctx* c, const TsdfMeshDev& D);               // classify and both scans on c->stream
-int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D);                  // the vertex and the triangle pass
+// axis_only (the surface points): vbase, cntt, tri, capt and rgba are not looked at
+int tsdf_mesh_classify_launch(nalo_ctx* c, const TsdfMeshDev& D, bool axis_only);   // classify and the scans on c->stream
+int tsdf_mesh_write_launch(nalo_ctx* c, const TsdfMeshDev& D, bool axis_only);      // the vertex pass, and the mesh's triangle pass
 // nalo_tsdf_integrate_frame's plane: D[v][u] = 1.0f / idepth of the record with the highest position at (u, v), 0 without one. key: w h words, zero between calls.
 // colour != NULL (a coloured volume): w h words, that record's B | G << 8 | R << 16, 0 without one - a U8 plane of three channels with stride_x 4, stride_c 1
 // segs is HOST memory: the segments travel as kernel arguments, kTsdfSegsPerLaunch to a launch, so the call stages nothing that a later call could overwrite
@@ -494,11 +490,10 @@ constexpr int kTsdfSegsPerLaunch = 32;
 int tsdf_frame_plane_launch(nalo_ctx* c, const MapSeg* segs, int nseg, unsigned long long* key, float* plane, unsigned* colour, int w, int h);
 // nalo_tsdf_raycast (kernels_tsdf_raycast.hip, built without FMA contraction): one lane per pixel, an 8 x 8 tile to a wave. It reads the volume only.
 struct TsdfRaycastDev {
-    const float *tsdf, *weight; int nx, ny, nz;
-    float origin[3], vs, min_weight;
+    TsdfGridDev g;                                                              // read only; g.col != NULL: with_colour
+    float min_weight;
     float R[9], t[3], fx, fy, cx, cy; int w, h;                                 // camToWorld rounded to float; the view
     float min_depth, step; int N;                                               // z_n = min_depth + (float)n * step, n < N
-    const float* col; size_t col_plane;                                         // with_colour: the planes B, G, R, col_plane floats apart
     float* depth; float* normal; unsigned* rgba;                                // [h][w], [h][w][3] (with_normals), [h][w] words R | G << 8 | B << 16 | A << 24 (with_colour)
     unsigned long long* cnt;                                                    // n_hit, n_back, n_normal: zero before
 };

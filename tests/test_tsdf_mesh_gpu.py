@@ -271,6 +271,67 @@ def test_growing_buffers_views_and_repeatability():
     c.close()
 
 
+# ------------------------------------------------------------------------------------------------ the scratch the surface points share with the mesh
+def device_mesh(c, colour=False):
+    """the device mesh as the views name it: pointer, shape and bytes of xyz, tri and (colour) rgba"""
+    c.sync()
+    views = c.tsdf_mesh_view() + ((c.tsdf_mesh_color_view(),) if colour else ())
+    return [(v.ptr, v.shape, torch.as_tensor(v, device="cuda").cpu().numpy().tobytes()) for v in views]
+
+
+def test_surface_points_leave_the_device_mesh_alone():
+    """nalo_tsdf_surface_points runs the mesh's classify and vertex pass and shares the mesh's mask bytes and per-workgroup vertex counts (mesh_mask, mesh_cntv),
+    which here have to GROW under a built mesh: from the 120 voxels of the small box to the whole grid's 30720. The mesh's own buffers (xyz, tri, rgba), its
+    counts and its colour state are not the surface points' to touch, whether the call is served or refused. The scratch grows in the uncoloured pass only:
+    by the coloured one it is at full size, and that pass holds the colour buffer and mesh_coloured to the same."""
+    c = ctx()
+    vol = random_field(make(c, grid((32, 24, 40))), 21)
+    plant(c, vol)
+    small_box = ((3, 2, 1), (6, 5, 4))
+    want = tm.surface_points(vol, 1.0)
+    assert len(want) > 1000
+    for colour in (False, True):
+        if colour:
+            c.tsdf_color_enable()
+            c.tsdf_color_set((0, 0, 0), np.random.RandomState(5).uniform(0, 255, (3,) + vol["tsdf"].shape).astype(F))
+        nv, nt = c.tsdf_mesh(1.0, *small_box, download=False, colour=colour)
+        assert nv > 0 and nt > 0
+        before = device_mesh(c, colour)
+        pts = c.tsdf_surface_points(1.0)
+        assert pts.shape == want.shape and bits_eq(pts, want)
+        with pytest.raises(binding.NaloError, match="nalo error %d:" % ERR_ARG):
+            c.tsdf_surface_points(1.0, cap=len(want) - 1)
+        assert c.tsdf_surface_needed == len(want)
+        assert device_mesh(c, colour) == before
+        mesh_both(c, vol, 1.0, tag="the whole grid behind the surface points, colour %s" % colour)
+    c.close()
+
+
+def test_surface_points_and_the_mesh_reuse_one_scratch_across_sizes():
+    """The shared scratch (mesh_mask, mesh_cntv, and the pinned words the totals come up in, mesh_cnt_h) used large, small and large again by the surface
+    points, then by the mesh and by the surface points in turn: no call may read what an earlier one of another size or kind left there. The field is the
+    planted one of test_surface_points_of_planted_volumes: NaN and zero tsdf, NaN weights, eleven workgroups with the last one partial."""
+    c = ctx()
+    vol = make(c, dict(origin=(-1.0, 0.5, 2.0), vs=0.125, dims=(37, 9, 31), trunc=0.25, mw=4.0))
+    rng = np.random.RandomState(3)
+    vol["tsdf"][:] = rng.choice(np.array([-1.0, -0.25, 0.0, -0.0, 0.5, 1.0, np.nan], F), vol["tsdf"].shape).astype(F)
+    vol["weight"][:] = rng.choice(np.array([0.0, 0.5, 1.0, 2.0, np.nan], F), vol["weight"].shape).astype(F)
+    plant(c, vol)
+    corner = ((35, 7, 29), (2, 2, 2))
+    whole = c.tsdf_surface_points(1.0)
+    small = c.tsdf_surface_points(1.0, *corner)
+    again = c.tsdf_surface_points(1.0)
+    assert len(whole) > 1000 and bits_eq(whole, tm.surface_points(vol, 1.0)) and whole.tobytes() == again.tobytes()
+    assert bits_eq(small, tm.surface_points(vol, 1.0, *corner))
+    box = ((3, 2, 5), (30, 6, 20))
+    xyz, tri = mesh_both(c, vol, 1.0, *box, tag="the mesh behind the surface points")
+    axis = mm.mesh(vol, 1.0, *box, with_axis=True)[2]
+    pts = c.tsdf_surface_points(1.0, *box)
+    sel = xyz[np.isin(axis, (1, 2, 4))]
+    assert len(pts) > 50 and sel.shape == pts.shape and mm.same_floats(sel, pts)
+    c.close()
+
+
 # ------------------------------------------------------------------------------------------------ the device chain
 def test_three_keyframes_of_the_device_chain_with_a_mesh_after_each(monkeypatch):
     """tests/test_tsdf_gpu.py's chain (1224x368 into 256x64x256, three keyframes) with nalo_tsdf_mesh after every integration, against the vectorised model of the
