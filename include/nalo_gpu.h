@@ -249,6 +249,39 @@ int nalo_trk_set_ref_resident(nalo_ctx* ctx, int slot_ref);
  * fix = 1 one (nalo_ba_optimize ends with one), or the window is sharded (a rank holds its own points only: collect the inputs and call
  * nalo_trk_set_ref). The block of nalo_trk_ref_upload is left alone. */
 int nalo_trk_set_ref_from_window(nalo_ctx* ctx);
+/* a2 fed from a depth plane that lies on the device: the ray-cast of the fused model (nalo_tsdf_raycast_view's depth), a depth sensor's plane, a densified
+ * keyframe. DEFINED as nalo_trk_set_ref(ctx, slot_ref, n, Ku, Kv, new_idepth, HdiF) on the list of the passing pixels in raster order (v outer, u inner), with
+ *     pass(u, v) = u % step == 0 && v % step == 0 && D >= min_depth && D <= max_depth && (min_grad == 0.0f || absg >= min_grad)
+ *     D = the plane's element (u, v), absg = the level-0 absSquaredGrad of slot_ref at (u, v) (what nalo_frame_download(slot_ref, 0) returns), every comparison
+ *     a float comparison on the values as they stand, before any conversion: a NaN D or absg fails, -0.0f and 0.0f fail min_depth > 0; min_grad == 0.0f (or
+ *     -0.0f) switches the gradient test off and absg is not read
+ *     Ku = (float)u, Kv = (float)v, new_idepth = 1.0f / D (one correctly rounded division), HdiF = hdi,
+ *     hence weight = sqrtf((float)(1e-3 / ((double)hdi + 1e-12))) for every point (CoarseTracker.cpp:397)
+ * Results are that call's, bit for bit, in both maps of every level, in pc_n, in the four cloud arrays of every level and in slot_ref; n_seeded = n. No pixel
+ * passes (a ray-cast that hit nothing): legal, the result of nalo_trk_set_ref with n = 0. Nothing crosses to the host but pc_n and n_seeded; the list is never
+ * formed: every pixel takes at most one hit, so one kernel writes idepth[0] and weightSums[0] and sums every coarser level in the same pass, in place of the zero
+ * fill, the scatter, its ordered redo and the sum pyramid; dilation, count, scan and write follow as in every nalo_trk_set_ref*.
+ * depth   F32, one channel, exactly the context's w x h, any strides nalo_dev_plane_check accepts (pitched, x-strided); no byte outside the described elements
+ *         is read. It must not overlap the reference's own buffers (what nalo_trk_ref_export describes): as in nalo_trk_ref_import this is the caller's to keep,
+ *         it is not checked.
+ * Stream order as nalo_tsdf_integrate_depth: the main stream waits, on the device, for what producer_stream (NULL: the null stream) has queued at the time of
+ *         the call - skipped when that is the context's own stream. The call ends with the host poll for pc_n that every nalo_trk_set_ref* ends with, and that
+ *         poll lies behind the only kernel that reads the plane: when the call returns the plane HAS been read and may be overwritten or freed - there is no
+ *         release call. No other host wait; with the buffers sized, no allocation.
+ * Everything is checked before anything is queued or reserved; a refused call leaves the reference bit-identical - slot_ref included - and sets n_seeded = 0.
+ *         NALO_ERR_ARG: a NULL ctx or args; a bad slot_ref; a plane nalo_dev_plane_check refuses; a dtype other than F32, or three channels; w or h that differ
+ *         from the context's; min_depth not finite or <= 0; max_depth not finite, or min_depth > max_depth; hdi not finite or < 0; step < 1; a NaN min_grad.
+ *         NALO_ERR_STATE: slot_ref holds no pyramid. */
+typedef struct nalo_trk_depth_ref_args {
+    nalo_dev_plane depth;        /* F32, one channel, exactly the context's w x h, any strides nalo_dev_plane_check accepts */
+    float min_depth, max_depth;  /* D is usable iff D >= min_depth && D <= max_depth (a NaN fails); min_depth > 0 */
+    float hdi;                   /* the HdiF every point gets; weight = sqrtf((float)(1e-3 / ((double)hdi + 1e-12))) as in step 1 */
+    int step;                    /* >= 1: only pixels with u % step == 0 && v % step == 0 */
+    float min_grad;              /* only pixels whose level-0 absSquaredGrad of slot_ref is >= min_grad; 0.0f switches the test off (absg is not read) */
+    void* producer_stream;       /* whose queued work produces the plane; NULL = the null stream */
+    int n_seeded;                /* out: the pixels that passed */
+} nalo_trk_depth_ref_args;
+int nalo_trk_set_ref_from_depth(nalo_ctx* ctx, int slot_ref, nalo_trk_depth_ref_args* args);
 /* direct injection of one level's point cloud (synthetic stress windows) */
 int nalo_trk_set_pc(nalo_ctx* ctx, int slot_ref, int lvl, int n, const float* u, const float* v,
                     const float* idepth, const float* color);

@@ -29,7 +29,7 @@ INJECT_LM_LOST_BLOCK, INJECT_GATED_SOLVE = 1, 2       # nalo_test_inject's `what
 EXPORTS = [
     "nalo_create", "nalo_destroy", "nalo_last_error", "nalo_levels", "nalo_sync", "nalo_stream", "nalo_test_inject",
     "nalo_frame_upload", "nalo_frame_upload_raw", "nalo_frame_upload_raw_async", "nalo_undist_set", "nalo_frame_upload_async", "nalo_frame_wait", "nalo_frame_ingest_device", "nalo_frame_release", "nalo_dev_plane_check", "nalo_frame_attach", "nalo_host_alloc", "nalo_host_free", "nalo_frame_rebuild", "nalo_frame_download", "nalo_frame_download_mask", "nalo_frame_plane",
-    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_ref_export", "nalo_trk_ref_import", "nalo_trk_ref_release", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_track_tries", "nalo_trk_motion_tries", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
+    "nalo_trk_make_k", "nalo_trk_set_ref", "nalo_trk_ref_upload", "nalo_trk_set_ref_resident", "nalo_trk_set_ref_from_window", "nalo_trk_set_ref_from_depth", "nalo_trk_set_pc", "nalo_trk_get_pc", "nalo_trk_append_plane_points", "nalo_trk_get_depth", "nalo_trk_set_depth", "nalo_trk_ref_export", "nalo_trk_ref_import", "nalo_trk_ref_release", "nalo_trk_depth_image", "nalo_trk_eval", "nalo_trk_track", "nalo_trk_track_tries", "nalo_trk_motion_tries", "nalo_trk_last_evals", "nalo_trk_get_launch_config", "nalo_trk_set_shard",
     "nalo_ba_set_window", "nalo_ba_set_points", "nalo_ba_set_residuals", "nalo_ba_set_prior", "nalo_ba_get_prior",
     "nalo_ba_linearize", "nalo_ba_accumulate", "nalo_ba_accumulate_sc", "nalo_ba_solve_system", "nalo_ba_backup_state",
     "nalo_ba_do_step", "nalo_ba_optimize", "nalo_ba_marginalize_points", "nalo_ba_marginalize_frame", "nalo_ba_set_prior_carry", "nalo_ba_calc_l_energy", "nalo_ba_calc_m_energy", "nalo_ba_plane_scale_fix", "nalo_ba_sw_gray_optimize", "nalo_ba_optimize_stats", "nalo_get_settings", "nalo_set_settings", "nalo_constants", "nalo_constants_device", "nalo_ba_get_frames", "nalo_ba_get_points",
@@ -62,6 +62,11 @@ class DevPlane(C.Structure):                              # nalo_dev_plane; dev_
 class FrameIngestArgs(C.Structure):                       # nalo_frame_ingest_args
     _fields_ = [("image", C.POINTER(DevPlane)), ("exposure_time", C.c_float), ("factor", C.c_float), ("mask", C.POINTER(DevPlane)), ("colour", C.POINTER(DevPlane)),
                 ("colour_is_rgb", C.c_int), ("gammaB", c_fp), ("producer_stream", C.c_void_p)]
+
+
+class TrkDepthRefArgs(C.Structure):                       # nalo_trk_depth_ref_args
+    _fields_ = [("depth", DevPlane), ("min_depth", C.c_float), ("max_depth", C.c_float), ("hdi", C.c_float), ("step", C.c_int), ("min_grad", C.c_float),
+                ("producer_stream", C.c_void_p), ("n_seeded", C.c_int)]
 
 
 MAX_LEVELS = 6                                           # NALO_MAX_LEVELS
@@ -498,6 +503,7 @@ def load():
     L.nalo_trk_ref_upload.argtypes = [vp, C.c_int, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_set_ref_resident.argtypes = [vp, C.c_int]
     L.nalo_trk_set_ref_from_window.argtypes = [vp]
+    L.nalo_trk_set_ref_from_depth.argtypes = [vp, C.c_int, C.POINTER(TrkDepthRefArgs)]
     L.nalo_trk_set_pc.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_get_pc.argtypes = [vp, C.c_int, c_ip, c_fp, c_fp, c_fp, c_fp]
     L.nalo_trk_get_depth.argtypes = [vp, C.c_int, c_fp, c_fp]
@@ -992,6 +998,28 @@ class Context:
         """setCoarseTrackingRef from this context's BA window (nalo_trk_set_ref_from_window): the IN residuals to the newest frame as the last
         linearizeAll(true) left them, gathered on the device; the reference slot is the newest window frame's"""
         self._ck(self.L.nalo_trk_set_ref_from_window(self.h_))
+
+    def trk_set_ref_from_depth(self, slot, depth, min_depth, max_depth, hdi, step=1, min_grad=0.0, stream=None):
+        """setCoarseTrackingRef from a depth plane on the device (nalo_trk_set_ref_from_depth): every pixel with u % step == 0, v % step == 0, min_depth <= D <=
+        max_depth and (min_grad != 0) absSquaredGrad >= min_grad becomes a point (u, v, 1 / D, hdi); the result is trk_set_ref's on that list, bit for bit.
+        depth is a 2-D float32 device array of the context's size (anything with __cuda_array_interface__: a torch tensor or view, the depth DeviceView of
+        tsdf_raycast_view) or a DevPlane. stream: the producing hipStream_t (None: a DeviceView's own, torch's current stream of a tensor, else the null stream).
+        The plane has been read when the call returns. Returns n_seeded; self.trk_depth_ref_seeded holds it too, 0 after a refusal."""
+        a = TrkDepthRefArgs()
+        a.depth = depth if isinstance(depth, DevPlane) else dev_plane(depth)
+        if stream is None:
+            stream = 0
+            torch = sys.modules.get("torch")
+            if isinstance(depth, DeviceView):
+                stream = depth.stream
+            elif torch is not None and isinstance(depth, torch.Tensor):
+                stream = torch.cuda.current_stream(depth.device).cuda_stream
+        a.min_depth, a.max_depth, a.hdi, a.step, a.min_grad, a.producer_stream = float(min_depth), float(max_depth), float(hdi), int(step), float(min_grad), stream or None
+        a.n_seeded = -1
+        rc = self.L.nalo_trk_set_ref_from_depth(self.h_, slot, C.byref(a))
+        self.trk_depth_ref_seeded = int(a.n_seeded)
+        self._ck(rc)
+        return int(a.n_seeded)
 
     def trk_set_pc(self, slot, lvl, u, v, idepth, color):
         a = [np.ascontiguousarray(x, np.float32) for x in (u, v, idepth, color)]

@@ -515,6 +515,30 @@ int nalo_trk_set_ref_from_window(nalo_ctx* c) {
     c->slot_ref = slot;
     return trk_build_ref(c, n, b, b + n, b + 2 * (size_t)n, b + 3 * (size_t)n);
 }
+// a2 fed from a depth plane on the device. Everything is tested before anything is queued or reserved, and slot_ref moves only once the call is accepted; then
+// the main stream waits (on the device) for the producer, ONE kernel reads the plane and the call ends on the pc_n poll behind it.
+int nalo_trk_set_ref_from_depth(nalo_ctx* c, int slot_ref, nalo_trk_depth_ref_args* a) {
+    if (a) a->n_seeded = 0;
+    if (!c || !a) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: bad argument");
+    if (slot_ref < 0 || slot_ref >= (int)c->slots.size()) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: bad slot_ref");
+    NALO_HIP(c, hipSetDevice(c->device));
+    { const int rc = dev_plane_validate(c, &a->depth, "nalo_trk_set_ref_from_depth", "depth"); if (rc) return rc; }
+    if (a->depth.dtype != NALO_DT_F32 || a->depth.channels != 1) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: the depth plane is one channel of F32");
+    if (a->depth.w != c->w || a->depth.h != c->h) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: the depth plane's w x h differ from the context's");
+    if (!std::isfinite(a->min_depth) || !(a->min_depth > 0.0f)) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: min_depth must be finite and > 0");
+    if (!std::isfinite(a->max_depth) || a->min_depth > a->max_depth) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: max_depth must be finite and >= min_depth");
+    if (!std::isfinite(a->hdi) || a->hdi < 0.0f) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: hdi must be finite and >= 0");
+    if (a->step < 1) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: step must be >= 1");
+    if (a->min_grad != a->min_grad) return fail(c, NALO_ERR_ARG, "nalo_trk_set_ref_from_depth: min_grad is NaN");
+    if (!c->slots[slot_ref].valid) return fail(c, NALO_ERR_STATE, "nalo_trk_set_ref_from_depth: reference slot has no pyramid");
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "trk_set_ref_from_depth");
+    NALO_HIP(c, c->ev_prod.create(hipEventDisableTiming));
+    hipStream_t prod = (hipStream_t)a->producer_stream;                    // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    c->slot_ref = slot_ref;
+    return trk_build_ref_from_depth(c, a->depth, a->min_depth, a->max_depth, a->hdi, a->step, a->min_grad, &a->n_seeded);
+}
 
 int nalo_trk_set_pc(nalo_ctx* c, int slot_ref, int lvl, int n, const float* u, const float* v, const float* idepth, const float* color) {
     if (!c || slot_ref < 0 || slot_ref >= (int)c->slots.size() || lvl < 0 || lvl >= c->levels || n < 0) return fail(c, NALO_ERR_ARG, "nalo_trk_set_pc: bad argument");

@@ -269,22 +269,10 @@ __global__ __launch_bounds__(256) void trk_zero2_kernel(float* __restrict__ a, f
 // step 2 (:408-433): 2x2 SUM pyramid, every level from one pass over level 0. A block owns a 32x32 level-0 tile = 16x16 level-1 pixels, and
 // walks up through LDS (8x8, 4x4, 2x2, 1); each parent is a + b + c + d of its four children in the reference's order, so the values
 // are those of the level-by-level loop bit for bit.
-__global__ __launch_bounds__(256) void trk_sum_down_all_kernel(TrkLevels P) {
-    __shared__ float sid[2][16 * 16], sws[2][16 * 16];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int tiles_x = (P.wl[1] + 15) / 16;
-    const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-    {
-        const int x = bx * 16 + tx, y = by * 16 + ty, w0 = P.wl[0];
-        float a = 0.f, b = 0.f;
-        if (x < P.wl[1] && y < P.hl[1]) {
-            const int o = 2 * x + 2 * y * w0;
-            a = P.id[0][o] + P.id[0][o + 1] + P.id[0][o + w0] + P.id[0][o + w0 + 1];
-            b = P.ws[0][o] + P.ws[0][o + 1] + P.ws[0][o + w0] + P.ws[0][o + w0 + 1];
-            P.id[1][x + y * P.wl[1]] = a; P.ws[1][x + y * P.wl[1]] = b;
-        }
-        sid[0][ty * 16 + tx] = a; sws[0][ty * 16 + tx] = b;
-    }
+// The walk above level 1, shared by trk_sum_down_all_kernel and trk_seed_depth_kernel: lane (tx, ty) of tile (bx, by) hands in its level-1 pair (a, b), zeros where
+// the tile leaves the level.
+__device__ __forceinline__ void trk_sum_walk_up(const TrkLevels& P, int bx, int by, int tx, int ty, float a, float b, float (*sid)[16 * 16], float (*sws)[16 * 16]) {
+    sid[0][ty * 16 + tx] = a; sws[0][ty * 16 + tx] = b;
     int side = 16, cur = 0;
     for (int l = 2; l < P.L; ++l) {
         __syncthreads();
@@ -299,6 +287,127 @@ __global__ __launch_bounds__(256) void trk_sum_down_all_kernel(TrkLevels P) {
         }
         cur ^= 1;
     }
+}
+__global__ __launch_bounds__(256) void trk_sum_down_all_kernel(TrkLevels P) {
+    __shared__ float sid[2][16 * 16], sws[2][16 * 16];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int tiles_x = (P.wl[1] + 15) / 16;
+    const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const int x = bx * 16 + tx, y = by * 16 + ty, w0 = P.wl[0];
+    float a = 0.f, b = 0.f;
+    if (x < P.wl[1] && y < P.hl[1]) {
+        const int o = 2 * x + 2 * y * w0;
+        a = P.id[0][o] + P.id[0][o + 1] + P.id[0][o + w0] + P.id[0][o + w0 + 1];
+        b = P.ws[0][o] + P.ws[0][o + 1] + P.ws[0][o + w0] + P.ws[0][o + w0 + 1];
+        P.id[1][x + y * P.wl[1]] = a; P.ws[1][x + y * P.wl[1]] = b;
+    }
+    trk_sum_walk_up(P, bx, by, tx, ty, a, b, sid, sws);
+}
+// nalo_trk_set_ref_from_depth: steps 1 and 2 in ONE launch, for a seed in which every level-0 pixel takes at most one hit (no atomics, no hit counts, no hot list).
+// A workgroup owns a 32x32 level-0 tile as above, a lane its 2x2 quad: the four depths come through the plane's byte strides (and, with the gradient test on, the
+// four absSquaredGrad values of the slot), idepth[0] = (1 / D) * weight and weightSums[0] = weight go out for a passing pixel and 0, 0 for every other one - the
+// old path's zero fill plus one atomic add onto 0.0f, which is the addend itself for the values that occur here (a positive quotient times a positive weight).
+// The product is rounded on its own (__fmul_rn: it must not contract into the level-1 sums), the quotient is the correctly rounded one, the weight is the
+// scatter's expression. Level 1 is a + b + c + d from registers in the reference's order, the levels above are the shared walk. The tiles cover level 0, not
+// level 1: the last column / row of an odd w / h and the pixels of partial tiles are written too (the old path zeroes all w*h). VEC: w is even and the plane's
+// rows are 8-byte friendly - a quad's row is one 8-byte access, so a wave reads and writes four pairs of contiguous 128-byte rows; otherwise word by word.
+// n_seeded: every workgroup adds {1 ticket | its passing pixels} to ONE 64-bit word with one atomic; the one that draws the last ticket publishes the total to
+// the host-mapped block (read behind the pc_n flag, which a later kernel of the stream stores) and re-arms the word for the next stream-ordered call. These
+// atomics queue at the one address, some 11 ns each: 5 of the kernel's 10 us at 1224x368 (435 workgroups). Two other forms were measured and are slower: one
+// atomic a wave issued ahead of the stores (27 us), and plain per-wave stores to a host-mapped array that the host adds up (the kernel's end waits for the
+// writes to arrive: 6 to 35 us, and the call 30 us longer).
+constexpr int kTrkSeedOut = 96 + NALO_MAX_LEVELS + 2;    // n_seeded in trk_out_host: behind pc_n [96 ..] and its flag [96 + NALO_MAX_LEVELS]
+struct TrkDepthSeed {
+    const char* depth; long long sy, sx;              // the plane: element (u, v) at depth + v * sy + u * sx
+    const float* absg;                                // level-0 absSquaredGrad of the slot (read only with min_grad != 0)
+    float min_depth, max_depth, hdi, min_grad;
+    int step;
+    unsigned long long* ticket;                       // {arrived workgroups << 32 | passing pixels}, zero between calls
+    double* n_out;                                    // host-mapped
+};
+template <bool VEC>
+__global__ __launch_bounds__(256) void trk_seed_depth_kernel(TrkLevels P, TrkDepthSeed S) {
+    __shared__ float sid[2][16 * 16], sws[2][16 * 16];
+    __shared__ int wave_cnt[4];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int w0 = P.wl[0], h0 = P.hl[0];
+    const int tiles_x = (w0 + 31) / 32;
+    const int bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+    const int x = bx * 16 + tx, y = by * 16 + ty;     // the lane's level-1 pixel; its quad is (2x .. 2x+1, 2y .. 2y+1)
+    const int u0 = 2 * x, v0 = 2 * y;
+    const float weight = sqrtf((float)(1e-3 / ((double)S.hdi + 1e-12)));
+    const bool grad = S.min_grad != 0.0f;
+    // in-image flags of the quad's pixels, row-major: with VEC the two pixels of a row stand or fall together
+    const bool in[4] = {u0 < w0 && v0 < h0, u0 + 1 < w0 && v0 < h0, u0 < w0 && v0 + 1 < h0, u0 + 1 < w0 && v0 + 1 < h0};
+    float D[4] = {0.f, 0.f, 0.f, 0.f}, G[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const char* row = S.depth + (long long)(v0 + r) * S.sy + (long long)u0 * S.sx;
+        const size_t o = (size_t)u0 + (size_t)w0 * (v0 + r);
+        if (VEC) {
+            if (in[2 * r]) {
+                const float2 d = *reinterpret_cast<const float2*>(row); D[2 * r] = d.x; D[2 * r + 1] = d.y;
+                if (grad) { const float2 g = *reinterpret_cast<const float2*>(S.absg + o); G[2 * r] = g.x; G[2 * r + 1] = g.y; }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (in[2 * r + k]) {
+                    D[2 * r + k] = *reinterpret_cast<const float*>(row + k * S.sx);
+                    if (grad) G[2 * r + k] = S.absg[o + k];
+                }
+        }
+    }
+    bool on[4] = {true, true, true, true};
+    if (S.step != 1) {                                // uniform; x % step == 0 for x = c + 1 iff c % step == step - 1
+        const int ru = u0 % S.step, rv = v0 % S.step;
+        const bool su0 = ru == 0, su1 = ru + 1 == S.step, sv0 = rv == 0, sv1 = rv + 1 == S.step;
+        on[0] = su0 && sv0; on[1] = su1 && sv0; on[2] = su0 && sv1; on[3] = su1 && sv1;
+    }
+    float pi[4], pw[4];
+    int passed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // the predicate of include/nalo_gpu.h: float comparisons as they stand (a NaN fails each of them)
+        const bool pass = in[k] && on[k] && D[k] >= S.min_depth && D[k] <= S.max_depth && (!grad || G[k] >= S.min_grad);
+        pi[k] = pass ? __fmul_rn(__fdiv_rn(1.0f, D[k]), weight) : 0.0f;
+        pw[k] = pass ? weight : 0.0f;
+        passed += pass ? 1 : 0;
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const size_t o = (size_t)u0 + (size_t)w0 * (v0 + r);
+        if (VEC) {
+            if (in[2 * r]) {
+                *reinterpret_cast<float2*>(P.id[0] + o) = make_float2(pi[2 * r], pi[2 * r + 1]);
+                *reinterpret_cast<float2*>(P.ws[0] + o) = make_float2(pw[2 * r], pw[2 * r + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (in[2 * r + k]) { P.id[0][o + k] = pi[2 * r + k]; P.ws[0][o + k] = pw[2 * r + k]; }
+        }
+    }
+    float a = 0.f, b = 0.f;
+    if (P.L > 1 && x < P.wl[1] && y < P.hl[1]) {      // all four pixels are inside then
+        a = pi[0] + pi[1] + pi[2] + pi[3];
+        b = pw[0] + pw[1] + pw[2] + pw[3];
+        P.id[1][x + y * P.wl[1]] = a; P.ws[1][x + y * P.wl[1]] = b;
+    }
+    // the count: the four waves' sums meet in LDS, one atomic a workgroup
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) passed += __shfl_xor(passed, o);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = passed;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned long long mine = (unsigned long long)(wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]);
+        const unsigned long long old = __hip_atomic_fetch_add(S.ticket, (1ull << 32) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((old >> 32) == gridDim.x - 1ull) {        // the last workgroup: every other one's add is in `old`
+            __hip_atomic_store(S.n_out, (double)((old & 0xffffffffull) + mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(S.ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    trk_sum_walk_up(P, bx, by, tx, ty, a, b, sid, sws);
 }
 // steps 3/4 (:437-489): 1-px dilation, diagonal (levels 0,1) or axis (levels >= 2), flat-index neighbours. The reference dilates in place
 // against a backup copy of the weights; here the undilated weights ws stay read-only and the result goes to wb (the buffers swap roles
@@ -512,13 +621,19 @@ int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref,
     return NALO_OK;
 }
 
-int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi) {
-    const int L = c->levels;
+// makeCoarseDepthL0 on the host side, in three parts: the level table and the buffers (trk_ref_prepare), a seed that leaves idepth[] / weightSums[] of every
+// level as steps 1 and 2 do (the scatter of trk_build_ref, the depth plane of trk_build_ref_from_depth), and steps 3-5 with the pc_n poll (trk_ref_finish).
+struct TrkRefPlan {
     TrkLevels P;
-    std::memset(&P, 0, sizeof(P));
+    int dil_blocks, cmp_blocks;
+    int dil0[NALO_MAX_LEVELS + 1], cmp0[NALO_MAX_LEVELS + 1];
+};
+static int trk_ref_prepare(nalo_ctx* c, TrkRefPlan& R) {
+    const int L = c->levels;
+    std::memset(&R, 0, sizeof(R));
+    TrkLevels& P = R.P;
     P.L = L;
     int dil_blocks = 0, cmp_blocks = 0, scan_total = 0;
-    int dil0[NALO_MAX_LEVELS + 1] = {0}, cmp0[NALO_MAX_LEVELS + 1] = {0};
     for (int l = 0; l < L; ++l) {
         const size_t npx = (size_t)c->wl[l] * c->hl[l];
         NALO_HIP(c, c->trk_idepth[l].reserve(npx)); NALO_HIP(c, c->trk_wsum[l].reserve(npx)); NALO_HIP(c, c->trk_wbak[l].reserve(npx));
@@ -526,14 +641,39 @@ int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const 
         P.id[l] = c->trk_idepth[l].p; P.ws[l] = c->trk_wsum[l].p; P.wb[l] = c->trk_wbak[l].p; P.dI[l] = c->slots[c->slot_ref].dI[l].p;
         P.pu[l] = c->pc_u[l].p; P.pv[l] = c->pc_v[l].p; P.pid[l] = c->pc_id[l].p; P.pcol[l] = c->pc_col[l].p;
         P.wl[l] = c->wl[l]; P.hl[l] = c->hl[l];
-        dil0[l] = dil_blocks; dil_blocks += (int)((npx + 255) / 256);
+        R.dil0[l] = dil_blocks; dil_blocks += (int)((npx + 255) / 256);
         const int total = (c->wl[l] - 4) * (c->hl[l] - 4);
         const int nb = total > 0 ? (total + kCompactChunk - 1) / kCompactChunk : 0;
-        cmp0[l] = cmp_blocks; cmp_blocks += nb;
+        R.cmp0[l] = cmp_blocks; cmp_blocks += nb;
         P.scan0[l] = scan_total; scan_total += 2 * nb + 2;
     }
-    dil0[L] = dil_blocks; cmp0[L] = cmp_blocks; P.scan0[L] = scan_total;
+    R.dil0[L] = dil_blocks; R.cmp0[L] = cmp_blocks; P.scan0[L] = scan_total;
+    R.dil_blocks = dil_blocks; R.cmp_blocks = cmp_blocks;
     NALO_HIP(c, c->scan_tmp.reserve((size_t)scan_total));
+    return NALO_OK;
+}
+static int trk_ref_finish(nalo_ctx* c, TrkRefPlan& R) {
+    TrkLevels& P = R.P;
+    const int L = P.L;
+    for (int l = 0; l <= L; ++l) P.blk0[l] = R.dil0[l];
+    trk_dilate_all_kernel<<<R.dil_blocks, 256, 0, c->stream>>>(P);
+    for (int l = 0; l <= L; ++l) P.blk0[l] = R.cmp0[l];
+    double* const dout = c->trk_out_host.dev;
+    const double seq = (double)(++c->trk_seq);
+    if (R.cmp_blocks > 0) trk_compact_all_kernel<0><<<R.cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
+    trk_scan_all_kernel<<<1, 1024, 0, c->stream>>>(P, c->scan_tmp.p, dout + 96, seq);
+    if (R.cmp_blocks > 0) trk_compact_all_kernel<1><<<R.cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
+    NALO_HIP(c, hipGetLastError());
+    for (int l = 0; l < L; ++l) std::swap(c->trk_wsum[l], c->trk_wbak[l]);      // the dilated (then normalised) weights are the level's weightSums now
+    if (!poll_flag(c, &c->trk_out_host.p[96 + NALO_MAX_LEVELS], seq)) return NALO_ERR_HIP;   // pc_n for the host; the point clouds follow in stream order
+    for (int l = 0; l < L; ++l) c->pc_n[l] = (int)c->trk_out_host.p[96 + l];
+    return NALO_OK;
+}
+
+int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi) {
+    TrkRefPlan R;
+    { const int rc = trk_ref_prepare(c, R); if (rc) return rc; }
+    const TrkLevels& P = R.P;
     const int n0 = c->wl[0] * c->hl[0];
     NALO_HIP(c, c->trk_cnt.reserve((size_t)n0 + 2 + std::max(n, 0)));        // hits per level-0 pixel, then the hot list's counter, its ticket and room for every residual
     trk_zero2_kernel<<<(n0 + 255) / 256, 256, 0, c->stream>>>(P.id[0], P.ws[0], c->trk_cnt.p, n0);
@@ -541,19 +681,27 @@ int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const 
         trk_scatter_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(dKu, dKv, dId, dHdi, n, c->wl[0], c->hl[0], P.id[0], P.ws[0], c->trk_cnt.p);
         trk_scatter_hot_kernel<<<(n + 255) / 256, 256, 0, c->stream>>>(dKu, dKv, dId, dHdi, n, c->wl[0], c->hl[0], P.id[0], P.ws[0], c->trk_cnt.p, c->trk_cnt.p + n0);
     }
-    if (L > 1) trk_sum_down_all_kernel<<<((c->wl[1] + 15) / 16) * ((c->hl[1] + 15) / 16), 256, 0, c->stream>>>(P);
-    for (int l = 0; l <= L; ++l) P.blk0[l] = dil0[l];
-    trk_dilate_all_kernel<<<dil_blocks, 256, 0, c->stream>>>(P);
-    for (int l = 0; l <= L; ++l) P.blk0[l] = cmp0[l];
-    double* const dout = c->trk_out_host.dev;
-    const double seq = (double)(++c->trk_seq);
-    if (cmp_blocks > 0) trk_compact_all_kernel<0><<<cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
-    trk_scan_all_kernel<<<1, 1024, 0, c->stream>>>(P, c->scan_tmp.p, dout + 96, seq);
-    if (cmp_blocks > 0) trk_compact_all_kernel<1><<<cmp_blocks, 256, 0, c->stream>>>(P, c->scan_tmp.p);
-    NALO_HIP(c, hipGetLastError());
-    for (int l = 0; l < L; ++l) std::swap(c->trk_wsum[l], c->trk_wbak[l]);      // the dilated (then normalised) weights are the level's weightSums now
-    if (!poll_flag(c, &c->trk_out_host.p[96 + NALO_MAX_LEVELS], seq)) return NALO_ERR_HIP;   // pc_n for the host; the point clouds follow in stream order
-    for (int l = 0; l < L; ++l) c->pc_n[l] = (int)c->trk_out_host.p[96 + l];
+    if (P.L > 1) trk_sum_down_all_kernel<<<((c->wl[1] + 15) / 16) * ((c->hl[1] + 15) / 16), 256, 0, c->stream>>>(P);
+    return trk_ref_finish(c, R);
+}
+
+// nalo_trk_set_ref_from_depth behind its checks (host_api.hip): c->slot_ref is the new reference slot and the main stream already waits for the producer
+int trk_build_ref_from_depth(nalo_ctx* c, const nalo_dev_plane& d, float min_depth, float max_depth, float hdi, int step, float min_grad, int* n_seeded) {
+    TrkRefPlan R;
+    { const int rc = trk_ref_prepare(c, R); if (rc) return rc; }
+    TrkDepthSeed S;
+    S.depth = static_cast<const char*>(d.ptr); S.sy = d.stride_y; S.sx = d.stride_x;
+    S.absg = c->slots[c->slot_ref].absg[0].p;
+    S.min_depth = min_depth; S.max_depth = max_depth; S.hdi = hdi; S.min_grad = min_grad; S.step = step;
+    const int w0 = c->wl[0], h0 = c->hl[0];
+    const int blocks = ((w0 + 31) / 32) * ((h0 + 31) / 32);
+    if (!c->trk_seed_ticket.p) { NALO_HIP(c, c->trk_seed_ticket.reserve(1)); NALO_HIP(c, hipMemsetAsync(c->trk_seed_ticket.p, 0, 8, c->stream)); }
+    S.ticket = c->trk_seed_ticket.p; S.n_out = c->trk_out_host.dev + kTrkSeedOut;
+    const bool vec = w0 % 2 == 0 && d.stride_x == 4 && d.stride_y % 8 == 0 && (uintptr_t)d.ptr % 8 == 0;
+    if (vec) trk_seed_depth_kernel<true><<<blocks, 256, 0, c->stream>>>(R.P, S);
+    else trk_seed_depth_kernel<false><<<blocks, 256, 0, c->stream>>>(R.P, S);
+    { const int rc = trk_ref_finish(c, R); if (rc) return rc; }
+    *n_seeded = (int)c->trk_out_host.p[kTrkSeedOut];            // stored by the seed kernel, in stream order before the flag the poll has just seen
     return NALO_OK;
 }
 

@@ -154,6 +154,7 @@ struct nalo_ctx {
     // scanned range, sized once) and the pinned block the boxes and results come up and the batch table goes down through
     nalo::DevBuf<uint4> dn_tab, dn_blk, dn_pts; nalo::HostBuf<int> dn_host;
     nalo::DevBuf<int> trk_cnt;               // hits per level-0 pixel of the reference scatter (ordered redo of pixels with >= 3 hits)
+    nalo::DevBuf<unsigned long long> trk_seed_ticket;   // nalo_trk_set_ref_from_depth: {arrived workgroups << 32 | passing pixels} of the seed kernel (zero between launches)
     nalo::DevBuf<float> upload_tmp;
     nalo::HostBuf<float> pinned_f;           // nalo_trk_set_ref's staging (upload4)
     // nalo_trk_depth_image (kernels_depth_image.hip), sized on first use: the select's histograms, state and results; the painted image; the pinned block it comes up through
@@ -568,6 +569,8 @@ constexpr int kDepthImageScratchWords = 2048 + 2 * 2048 + 2 * 512 + 16 + 8;
 int depth_image_launch(nalo_ctx* c, const float* idepth, const float* I, float io_min, float io_max, int have_io, unsigned* scr, uint8_t* bgr);
 // kernels_tracker.hip
 int trk_build_ref(nalo_ctx* c, int n, const float* dKu, const float* dKv, const float* dId, const float* dHdi);
+// the same reference from a depth plane (nalo_trk_set_ref_from_depth, already checked): one seed kernel in place of the scatter and the sum pyramid
+int trk_build_ref_from_depth(nalo_ctx* c, const nalo_dev_plane& d, float min_depth, float max_depth, float hdi, int step, float min_grad, int* n_seeded);
 int trk_append_plane_launch(nalo_ctx* c, const float* mask, const float4* dIref, const float dir[3], float dis, float refColor, int x0, int nx, int y0, int ny, int n0, int* n_dev);
 // the append loop of CoarseTracker.cpp:582-666 over the records nalo_trk_fit_planes has just written on the device (hdr: kernels_plane.hip's header words)
 int trk_append_clusters_launch(nalo_ctx* c, const float* mask, const float4* dIref, nalo_plane_cluster* rec, int* hdr, int cap_clusters);
