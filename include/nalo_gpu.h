@@ -1510,7 +1510,7 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  * tsdf=1: the dense map fused into a TSDF volume on the device. The reference constructs a cpu_tsdf::TSDFVolumeOctree (FullSystem.cpp:192-198), saves a point
  * file "for tsdf" (SampleOutputWrapper.h:150-176, nalo_map_dense_world_points here) and leaves the fusion to a third-party tool it neither vendors nor pins. This
  * section is a DEFINED operation instead: a projective integration of one depth image into a dense voxel volume that lives in the context. Colour is opt-in
- * ("Colour" below; the reference's switch is tsdf->setIntegrateColor, FullSystem.cpp:195). No octree, no de-integration; nalo_ba_snapshot / nalo_ba_restore do
+ * ("Colour" below; the reference's switch is tsdf->setIntegrateColor, FullSystem.cpp:195). No octree, no de-integration; a volume that follows the camera: nalo_tsdf_shift; nalo_ba_snapshot / nalo_ba_restore do
  * not include the volume.
  *
  * nalo_tsdf_create   origin: world position of the CORNER of voxel (0,0,0); dims = {nx, ny, nz}. Storage: two contiguous F32 arrays [nz][ny][nx], x fastest;
@@ -1546,7 +1546,7 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    NULL (not both). nalo_tsdf_set is to this volume what nalo_trk_set_depth is to the tracker. NALO_ERR_ARG for a block that is empty or leaves the
  *                    grid. Synchronous.
  * nalo_tsdf_view     host code only, launches nothing: the pointers of both arrays, the dimensions and the producing stream (nalo_stream), under "Lifetime of
- *                    a view" above: good until nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy; the calls that rewrite what it names are nalo_tsdf_reset,
+ *                    a view" above: good until a non-zero nalo_tsdf_shift / nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy; the calls that rewrite what it names are nalo_tsdf_reset,
  *                    nalo_tsdf_set and the two integrations.
  * nalo_tsdf_surface_points   over the sub-box [lo, lo + size) (use_box == 0: the whole grid): for voxel v in ascending (k, j, i) and axis a = x, y, z, with n the
  *                    neighbour of v along +a INSIDE the sub-box, (v, a, n) is a crossing iff both weights are >= min_weight and (t0 < 0 && t1 >= 0) || (t0 >= 0 &&
@@ -1615,7 +1615,7 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  * nalo_tsdf_color_get / nalo_tsdf_color_set   the sub-block [lo, lo + size) as [3][size[2]][size[1]][size[0]] floats, planes B, G, R, bit for bit (NaN payloads
  *                    pass). Refusals as nalo_tsdf_get / nalo_tsdf_set, and NALO_ERR_STATE without colour. Synchronous.
  * nalo_tsdf_color_view   host code only, launches nothing: the pointer of the [3][nz][ny][nx] block, the dimensions and the producing stream, under "Lifetime of
- *                    a view": good until nalo_tsdf_color_disable / nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy. NALO_ERR_STATE without colour.
+ *                    a view": good until a non-zero nalo_tsdf_shift / nalo_tsdf_color_disable / nalo_tsdf_create / nalo_tsdf_destroy / nalo_destroy. NALO_ERR_STATE without colour.
  * nalo_tsdf_mesh_color   everything nalo_tsdf_mesh does - the same definition, order, counts, growth protocol and refusals - and one colour per vertex, in vertex
  *                    order, into a context-owned device buffer [n_vertices][4] of bytes that grows with xyz. For the vertex on edge (v, m) with far end n and the
  *                    s = t0 / (t0 - t1) of its position, per plane:   cX = X(v) + s * (X(n) - X(v));   byte = (uint8)(int)(fminf(fmaxf(cX, 0.0f), 255.0f) + 0.5f).
@@ -1671,6 +1671,45 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    until the next nalo_tsdf_raycast, nalo_tsdf_create, nalo_tsdf_destroy or nalo_destroy. An image the last call was not asked for has a
  *                    NULL ptr. NALO_ERR_STATE before the first ray-cast.
  * nalo_tsdf_raycast_steps  host only, needs no context: N of the definition. NALO_ERR_ARG as nalo_tsdf_raycast refuses the three values, and for a NULL n_steps.
+ *
+ * A volume that follows the camera. The volume keeps the origin it was created with, origin0, and an integer base[3], zero at nalo_tsdf_create. The origin
+ * every other call of this section uses is origin[a] = origin0[a] + (float)base[a] * voxel_size, in float, the product rounded, then the sum, no FMA: recomputed
+ * from origin0 at every shift and never accumulated, so a base that returns to 0 returns origin0 bit for bit.
+ * nalo_tsdf_shift    with s = shift and n = dims: after the call voxel (i, j, k) holds, in tsdf, weight and (with colour enabled) the three colour planes, the
+ *                    words voxel (i + s[0], j + s[1], k + s[2]) held before it, copied as 32-bit words: NaN payloads, -0.0f and denormals pass unchanged.
+ *                    Where that voxel lies outside the grid, the voxel takes the initial values: tsdf 1.0f, weight 0.0f, colour 0.0f. base[a] += s[a]: a
+ *                    positive s[a] moves the box towards +a in the world, the slab of s[a] voxels at the low end leaves and a slab of initial values enters
+ *                    at the high end. The pass is out of place (a parallel move in place would overwrite words another workgroup still has to read): it
+ *                    writes a second set of arrays and swaps the two sets. The spare tsdf and weight arrays are allocated at the first non-zero shift, the
+ *                    spare colour block at the first non-zero shift of a coloured volume; they are kept, and freed with the volume or the colour: A VOLUME THAT
+ *                    HAS BEEN SHIFTED HOLDS TWICE ITS MEMORY. With the spares in place a shift allocates nothing, makes no host wait and enqueues on the main
+ *                    stream only. A failed allocation (NALO_ERR_HIP) leaves everything as it was. A shift of (0, 0, 0) is NALO_OK and queues, swaps and
+ *                    allocates nothing. A context that never shifts queues exactly what it queued before.
+ *                    Behind a non-zero shift: nalo_tsdf_last is NALO_ERR_STATE until the next integration (its box was in the old indices); the device mesh
+ *                    and the ray-cast images stay valid (they are in world coordinates); the event nalo_tsdf_release waits for is untouched. nalo_tsdf_reset
+ *                    resets the values and keeps base; nalo_tsdf_create starts from base = 0; nalo_tsdf_color_enable works as before; nalo_tsdf_color_disable
+ *                    frees both colour blocks. Lifetime of a view: nalo_tsdf_view and nalo_tsdf_color_view are good only until the next non-zero
+ *                    nalo_tsdf_shift, because the pointers swap.
+ *                    NALO_ERR_STATE without a volume; NALO_ERR_ARG for a NULL shift, for any |base[a] + s[a]| > 2^24 (the sum taken in 64 bits; at the bound
+ *                    the conversion to float is still exact) and for a resulting origin that is not finite. A refused call queues nothing and leaves volume,
+ *                    colour, geometry, views and nalo_tsdf_last as they were.
+ *                    The kernel is driven from the destination: as in the integration a lane owns four voxels consecutive in memory and 16-byte aligned by
+ *                    linear index and issues one 16-byte store per array; its loads are 16 bytes where the four sources lie in one row at a 16-byte aligned
+ *                    index (for nx a multiple of four: s[0] % 4 == 0), else four words. It reads 4 B and writes 4 B per voxel and array: 16 B per voxel, 40 B
+ *                    with colour.
+ * nalo_tsdf_geometry host only, launches nothing: desc with the CURRENT origin - the descriptor nalo_tsdf_frustum_box wants after a shift, and what a twin
+ *                    volume is created from - origin0 and base. NALO_ERR_STATE without a volume.
+ * nalo_tsdf_shift_for   host only, needs no context: the shift that puts the voxel containing `centre` at index dims[a] / 2, with a dead band. In double:
+ *                    q = floor((centre[a] - origin[a]) / voxel_size); d = q - (double)(dims[a] / 2); shift[a] = |d| > margin[a] ? (int)d : 0. NALO_ERR_ARG for
+ *                    a descriptor nalo_tsdf_create refuses, a non-finite centre, a negative margin, |d| > 2^24, a NULL pointer; shift is then not written.
+ * nalo_tsdf_shift_boxes host only, needs no context: the sub-boxes of the volume as it is BEFORE nalo_tsdf_shift(shift) that a caller meshes (or reads surface
+ *                    points or a block from) so that no cell is lost. Per axis, with n voxels and shift s, the kept voxels are [s, n) for s > 0 and [0, n + s)
+ *                    for s < 0; a cell survives iff all eight of its corners are kept. The leaving voxel range includes the seam voxel: [0, min(s + 1, n)) for
+ *                    s > 0, [max(n + s - 1, 0), n) for s < 0. |s| >= n on any axis: everything leaves, the one box is the whole grid and kept_lo / kept_size
+ *                    are zeros. Otherwise up to three boxes, in this order: X = leaving x by all y by all z; Y = kept x by leaving y by all z; Z = kept x by
+ *                    kept y by leaving z; an axis with s = 0 contributes none. The cells of the boxes are pairwise disjoint and their union is exactly the
+ *                    cells that do not survive (nalo_tsdf_mesh cuts cells at a sub-box's faces). Unused entries of lo / size are zero. NALO_ERR_ARG for a
+ *                    NULL pointer or a dimension outside [1, 2048].
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1736,10 +1775,17 @@ typedef struct nalo_tsdf_raycast_dev { nalo_dev_plane depth, normal, rgba; int w
 int nalo_tsdf_raycast(nalo_ctx* ctx, nalo_tsdf_raycast_args* args);
 int nalo_tsdf_raycast_view(nalo_ctx* ctx, nalo_tsdf_raycast_dev* out);       /* host only, launches nothing */
 int nalo_tsdf_raycast_steps(float min_depth, float max_depth, float step, int* n_steps);   /* host only, no context */
+/* the two structs share their call's name, so they are named by their tags: `struct nalo_tsdf_geometry g;` (a typedef would collide with the function in C) */
+struct nalo_tsdf_geometry { nalo_tsdf_desc desc; float origin0[3]; int base[3]; };                 /* desc.origin: the current origin */
+struct nalo_tsdf_shift_boxes { int n_boxes; int lo[3][3], size[3][3]; int kept_lo[3], kept_size[3]; };   /* lo[b], size[b]: box b < n_boxes, voxel indices */
+int nalo_tsdf_shift(nalo_ctx* ctx, const int shift[3]);
+int nalo_tsdf_geometry(nalo_ctx* ctx, struct nalo_tsdf_geometry* out);       /* host only, launches nothing */
+int nalo_tsdf_shift_for(const nalo_tsdf_desc* now, const double centre[3], const int margin[3], int shift[3]);   /* host only, no context */
+int nalo_tsdf_shift_boxes(const int dims[3], const int shift[3], struct nalo_tsdf_shift_boxes* out);            /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift". Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -43,6 +43,7 @@ EXPORTS = [
     "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
     "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
     "nalo_tsdf_raycast", "nalo_tsdf_raycast_view", "nalo_tsdf_raycast_steps",
+    "nalo_tsdf_shift", "nalo_tsdf_geometry", "nalo_tsdf_shift_for", "nalo_tsdf_shift_boxes",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -220,6 +221,14 @@ class TsdfRaycastDev(C.Structure):                        # nalo_tsdf_raycast_de
     _fields_ = [("depth", DevPlane), ("normal", DevPlane), ("rgba", DevPlane), ("w", C.c_int), ("h", C.c_int), ("stream", C.c_void_p)]
 
 
+class TsdfGeometry(C.Structure):                          # struct nalo_tsdf_geometry
+    _fields_ = [("desc", TsdfDesc), ("origin0", C.c_float * 3), ("base", C.c_int * 3)]
+
+
+class TsdfShiftBoxes(C.Structure):                        # struct nalo_tsdf_shift_boxes
+    _fields_ = [("n_boxes", C.c_int), ("lo", (C.c_int * 3) * 3), ("size", (C.c_int * 3) * 3), ("kept_lo", C.c_int * 3), ("kept_size", C.c_int * 3)]
+
+
 class DepthImageArgs(C.Structure):
     """nalo_depth_image_args (include/nalo_gpu.h)"""
     _fields_ = [("minmax_io", c_fp), ("bgr", c_u8p), ("idepth", c_fp), ("n_positive", C.c_int), ("min_new", C.c_float), ("max_new", C.c_float),
@@ -315,6 +324,8 @@ def host_lib():
         L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
         L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
         L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
+        L.nalo_tsdf_shift_for.argtypes = [C.POINTER(TsdfDesc), c_dp, c_ip, c_ip]
+        L.nalo_tsdf_shift_boxes.argtypes = [c_ip, c_ip, C.POINTER(TsdfShiftBoxes)]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
         _HOST_LIB = L
@@ -382,6 +393,32 @@ def tsdf_raycast_steps(min_depth, max_depth, step):
     if rc != 0:
         raise NaloError("nalo_tsdf_raycast_steps: bad argument (%d)" % rc)
     return int(n[0])
+
+
+def tsdf_shift_for(desc, centre, margin=(0, 0, 0)):
+    """nalo_tsdf_shift_for: the whole-voxel shift (int32 [3]) that puts the voxel containing `centre` at index dims / 2 of the volume `desc` describes (a
+    TsdfDesc with the CURRENT origin: tsdf_geometry()["desc"]); an axis whose distance is within margin[a] voxels stays. Needs no device"""
+    ce = np.ascontiguousarray(centre, np.float64).reshape(-1)
+    mg = np.ascontiguousarray(margin, np.int32).reshape(-1)
+    assert ce.size == 3 and mg.size == 3
+    out = np.zeros(3, np.int32)
+    rc = host_lib().nalo_tsdf_shift_for(C.byref(desc), _d(ce), _i(mg), _i(out))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_shift_for: bad argument (%d)" % rc)
+    return out
+
+
+def tsdf_shift_boxes(dims, shift):
+    """nalo_tsdf_shift_boxes -> dict(boxes=[(lo, size), ...], kept_lo, kept_size): the sub-boxes of the volume BEFORE tsdf_shift(shift) whose meshes (or surface
+    points, or blocks) hold every cell the shift loses, in the header's order; kept_*: the voxels that stay, zeros when none does. Needs no device"""
+    dm = np.ascontiguousarray(dims, np.int32).reshape(-1)
+    sh = np.ascontiguousarray(shift, np.int32).reshape(-1)
+    assert dm.size == 3 and sh.size == 3
+    b = TsdfShiftBoxes()
+    rc = host_lib().nalo_tsdf_shift_boxes(_i(dm), _i(sh), C.byref(b))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_shift_boxes: bad argument (%d)" % rc)
+    return dict(boxes=[(tuple(b.lo[k]), tuple(b.size[k])) for k in range(b.n_boxes)], kept_lo=tuple(b.kept_lo), kept_size=tuple(b.kept_size))
 
 
 def write_ply_mesh(path, xyz, tri, rgba=None):
@@ -585,6 +622,8 @@ def load():
     L.nalo_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastArgs)]
     L.nalo_tsdf_raycast_view.argtypes = [vp, C.POINTER(TsdfRaycastDev)]
     L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
+    L.nalo_tsdf_shift.argtypes = [vp, c_ip]
+    L.nalo_tsdf_geometry.argtypes = [vp, C.POINTER(TsdfGeometry)]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
@@ -1578,6 +1617,23 @@ class Context:
 
     def tsdf_destroy(self):
         self._ck(self.L.nalo_tsdf_destroy(self.h_))
+
+    def tsdf_shift(self, shift):
+        """nalo_tsdf_shift: voxel (i, j, k) takes the words of voxel (i + s0, j + s1, k + s2), the initial values where that lies outside the grid, and the origin
+        moves by s voxels: the box follows the camera. Enqueues only once the spare arrays exist (the first non-zero shift allocates them: a shifted volume holds
+        twice its memory). tsdf_view / tsdf_color_view taken before a non-zero shift are stale after it; tsdf_last needs a new integration"""
+        s = np.ascontiguousarray(shift, np.int32).reshape(-1)
+        if s.size != 3:
+            raise NaloError("tsdf_shift: shift is three whole voxels")
+        self._ck(self.L.nalo_tsdf_shift(self.h_, _i(s)))
+
+    def tsdf_geometry(self):
+        """nalo_tsdf_geometry -> dict(desc (a TsdfDesc with the CURRENT origin: what tsdf_frustum_box and a twin's tsdf_create take), origin, origin0 float32 [3],
+        base int32 [3], voxel_size, dims); launches nothing"""
+        g = TsdfGeometry()
+        self._ck(self.L.nalo_tsdf_geometry(self.h_, C.byref(g)))
+        return dict(desc=g.desc, origin=np.array(g.desc.origin[:], np.float32), origin0=np.array(g.origin0[:], np.float32), base=np.array(g.base[:], np.int32),
+                    voxel_size=np.float32(g.desc.voxel_size), dims=tuple(g.desc.dims[:]))
 
     def tsdf_color_enable(self):
         """nalo_tsdf_color_enable: three float32 planes [3][nz][ny][nx] (B, G, R) at 0.0 next to the volume; enable before the first integration if the colour is to

@@ -1,5 +1,6 @@
-// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, the culling box nalo_tsdf_frustum_box and the mesh's triangle table. Plain C++ with no
-// device call, built without FMA contraction: every line below is the operation order the header defines, in double.
+// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, the culling box nalo_tsdf_frustum_box, the mesh's triangle table and the
+// geometry of a shifted volume (the origin, nalo_tsdf_shift_for, nalo_tsdf_shift_boxes). Plain C++ with no device call, built without FMA contraction: every
+// line below is the operation order the header defines, in double (the shifted origin: in float).
 #include <cmath>
 
 #include "tsdf_host.h"
@@ -33,7 +34,69 @@ bool tsdf_world_to_cam(const double c[12], float M[12]) {
     return true;
 }
 
+constexpr long long kTsdfMaxBase = 1LL << 24;                                  // |base| up to here converts to float exactly
+
+const char* tsdf_shift_geometry(const float origin0[3], float voxel_size, const int base[3], const int shift[3], int new_base[3], float origin[3]) {
+    int nb[3]; float o[3];
+    for (int a = 0; a < 3; ++a) {
+        const long long b = (long long)base[a] + (long long)shift[a];
+        if (b > kTsdfMaxBase || b < -kTsdfMaxBase) return "base + shift beyond 2^24 voxels";
+        nb[a] = (int)b;
+        const float step = (float)nb[a] * voxel_size;                           // rounded here; the file is built without contraction, so the sum rounds on its own
+        o[a] = origin0[a] + step;
+        if (!std::isfinite(o[a])) return "the shifted origin is not finite";
+    }
+    for (int a = 0; a < 3; ++a) { new_base[a] = nb[a]; origin[a] = o[a]; }
+    return nullptr;
+}
+
 }  // namespace nalo
+
+extern "C" int nalo_tsdf_shift_for(const nalo_tsdf_desc* now, const double centre[3], const int margin[3], int shift[3]) {
+    if (!centre || !margin || !shift || nalo::tsdf_desc_refusal(now)) return NALO_ERR_ARG;
+    int s[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(centre[a]) || margin[a] < 0) return NALO_ERR_ARG;
+        const double q = std::floor((centre[a] - (double)now->origin[a]) / (double)now->voxel_size);
+        const double d = q - (double)(now->dims[a] / 2);
+        if (!(std::fabs(d) <= (double)nalo::kTsdfMaxBase)) return NALO_ERR_ARG;     // an infinite quotient fails here too
+        s[a] = std::fabs(d) > (double)margin[a] ? (int)d : 0;
+    }
+    for (int a = 0; a < 3; ++a) shift[a] = s[a];
+    return NALO_OK;
+}
+
+extern "C" int nalo_tsdf_shift_boxes(const int dims[3], const int shift[3], struct nalo_tsdf_shift_boxes* out) {
+    if (!dims || !shift || !out) return NALO_ERR_ARG;
+    for (int a = 0; a < 3; ++a) if (dims[a] < 1 || dims[a] > 2048) return NALO_ERR_ARG;
+    *out = {};
+    // per axis in 64 bits (s + 1 and -s of any int): the kept voxels [klo, klo + kn) and the leaving ones, the seam voxel among them, [llo, llo + ln)
+    long long klo[3], kn[3], llo[3], ln[3];
+    bool all = false;
+    for (int a = 0; a < 3; ++a) {
+        const long long n = dims[a], s = shift[a];
+        if (s >= n || -s >= n) all = true;
+        klo[a] = s > 0 ? s : 0; kn[a] = n - (s > 0 ? s : -s);
+        llo[a] = s > 0 ? 0 : s < 0 ? (n + s - 1 > 0 ? n + s - 1 : 0) : 0;
+        ln[a] = s > 0 ? (s + 1 < n ? s + 1 : n) : s < 0 ? n - llo[a] : 0;
+    }
+    if (all) {                                                                  // nothing is kept: the whole grid is the one box
+        out->n_boxes = 1;
+        for (int a = 0; a < 3; ++a) out->size[0][a] = dims[a];
+        return NALO_OK;
+    }
+    for (int a = 0; a < 3; ++a) { out->kept_lo[a] = (int)klo[a]; out->kept_size[a] = (int)kn[a]; }
+    for (int b = 0; b < 3; ++b) {                                               // box b: kept on the axes before b, leaving on b, everything behind it
+        if (shift[b] == 0) continue;
+        int* lo = out->lo[out->n_boxes]; int* size = out->size[out->n_boxes];
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = a < b ? (int)klo[a] : a == b ? (int)llo[a] : 0;
+            size[a] = a < b ? (int)kn[a] : a == b ? (int)ln[a] : dims[a];
+        }
+        ++out->n_boxes;                                                         // every extent is >= 1 here: |s| < n on every axis
+    }
+    return NALO_OK;
+}
 
 extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, const float K[4], const double c[12], float max_depth, int lo[3], int hi[3]) {
     if (!K || !c || !lo || !hi || w < 1 || h < 1 || nalo::tsdf_desc_refusal(d) || !std::isfinite(max_depth)) return NALO_ERR_ARG;

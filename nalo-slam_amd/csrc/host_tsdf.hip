@@ -9,9 +9,11 @@
 namespace nalo {
 
 struct TsdfVolume {
-    nalo_tsdf_desc d{};
+    nalo_tsdf_desc d{};                              // d.origin: the CURRENT origin, origin0 + (float)base * voxel_size (tsdf_shift_geometry)
+    float origin0[3] = {0, 0, 0}; int base[3] = {0, 0, 0};   // nalo_tsdf_shift: the origin of nalo_tsdf_create and the whole voxels shifted since
     size_t n = 0;
     DevBuf<float> tsdf, weight;
+    DevBuf<float> tsdf2, weight2, colour2;           // nalo_tsdf_shift's spares, empty until the first non-zero shift (colour2: of a coloured volume); each shift swaps them in
     Event ev_read;                                   // behind the last kernel that read a caller's depth plane (nalo_tsdf_release)
     bool read_pending = false;
     DevBuf<unsigned long long> updated; HostBuf<unsigned long long> updated_h;
@@ -137,6 +139,7 @@ int nalo_tsdf_create(nalo_ctx* c, const nalo_tsdf_desc* desc) {
     // the new volume is complete before the old one goes: a failed allocation leaves the context as it was
     TsdfVolume* v = new TsdfVolume();
     v->d = *desc; v->n = (size_t)desc->dims[0] * desc->dims[1] * desc->dims[2];
+    std::copy(desc->origin, desc->origin + 3, v->origin0);
     hipError_t e = v->tsdf.reserve(v->n);
     if (e == hipSuccess) e = v->weight.reserve(v->n);
     if (e == hipSuccess) e = v->updated.reserve(1);
@@ -176,7 +179,52 @@ int nalo_tsdf_color_disable(nalo_ctx* c) {
     if (!v.colour.p) return NALO_OK;
     NALO_HIP(c, hipSetDevice(c->device));
     NALO_HIP(c, hipStreamSynchronize(c->stream));                              // kernels that name the planes may still be queued
-    v.colour.release(); v.cplane.release(); v.mesh_rgba.release(); v.mesh_coloured = false;
+    v.colour.release(); v.colour2.release(); v.cplane.release(); v.mesh_rgba.release(); v.mesh_coloured = false;
+    return NALO_OK;
+}
+
+int nalo_tsdf_shift(nalo_ctx* c, const int shift[3]) {
+    const char* who = "nalo_tsdf_shift";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!shift) return fail(c, NALO_ERR_ARG, "nalo_tsdf_shift: bad argument");
+    TsdfVolume& v = *c->tsdf;
+    int base[3]; float origin[3];
+    if (const char* why = tsdf_shift_geometry(v.origin0, v.d.voxel_size, v.base, shift, base, origin)) return fail(c, NALO_ERR_ARG, std::string("nalo_tsdf_shift: ") + why);
+    if (!shift[0] && !shift[1] && !shift[2]) return NALO_OK;
+    // ---- accepted: from here on only the runtime can fail
+    NALO_HIP(c, hipSetDevice(c->device));
+    HostTimer ht(c, "tsdf_shift");
+    const bool coloured = v.colour.p != nullptr;
+    if (!v.tsdf2.p || (coloured && !v.colour2.p)) {                            // the first shift (of a coloured volume): whatever is missing, all of it or none
+        DevBuf<float> t2, w2, c2;
+        hipError_t e = hipSuccess;
+        if (!v.tsdf2.p) { e = t2.reserve(v.n); if (e == hipSuccess) e = w2.reserve(v.n); }
+        if (e == hipSuccess && coloured && !v.colour2.p) e = c2.reserve(3 * v.n);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_shift: ") + hipGetErrorString(e)); }
+        if (t2.p) { v.tsdf2 = std::move(t2); v.weight2 = std::move(w2); }
+        if (c2.p) v.colour2 = std::move(c2);
+    }
+    TsdfShiftDev D{};
+    D.src_tsdf = reinterpret_cast<const unsigned*>(v.tsdf.p); D.src_weight = reinterpret_cast<const unsigned*>(v.weight.p);
+    D.dst_tsdf = reinterpret_cast<unsigned*>(v.tsdf2.p); D.dst_weight = reinterpret_cast<unsigned*>(v.weight2.p);
+    if (coloured) { D.src_col = reinterpret_cast<const unsigned*>(v.colour.p); D.dst_col = reinterpret_cast<unsigned*>(v.colour2.p); }
+    D.nx = v.d.dims[0]; D.ny = v.d.dims[1]; D.nz = v.d.dims[2]; D.n = (long long)v.n;
+    for (int a = 0; a < 3; ++a) D.s[a] = std::max(-v.d.dims[a], std::min(v.d.dims[a], shift[a]));      // beyond the grid's extent nothing is kept either way
+    { const int rc = tsdf_shift_launch(c, D); if (rc) return rc; }
+    // the kernel is queued: everything behind it on the main stream reads the arrays it writes
+    std::swap(v.tsdf, v.tsdf2); std::swap(v.weight, v.weight2);
+    if (coloured) std::swap(v.colour, v.colour2);
+    for (int a = 0; a < 3; ++a) { v.base[a] = base[a]; v.d.origin[a] = origin[a]; }
+    v.have_last = false;                                                       // the last integration's box was in the old indices
+    return NALO_OK;
+}
+
+int nalo_tsdf_geometry(nalo_ctx* c, struct nalo_tsdf_geometry* out) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_geometry"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_geometry: bad argument");
+    const TsdfVolume& v = *c->tsdf;
+    out->desc = v.d;
+    for (int a = 0; a < 3; ++a) { out->origin0[a] = v.origin0[a]; out->base[a] = v.base[a]; }
     return NALO_OK;
 }
 

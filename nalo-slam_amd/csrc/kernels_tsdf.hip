@@ -1,5 +1,5 @@
-// The TSDF volume's kernels (include/nalo_gpu.h, "tsdf=1"): the projective integration of one depth plane over the culling box, the sub-block copies and the
-// plane nalo_tsdf_integrate_frame makes of a frame's dense list. (The surface points are kernels_tsdf_mesh.hip's: the mesh's passes on the axis edges.) Built
+// The TSDF volume's kernels (include/nalo_gpu.h, "tsdf=1"): the projective integration of one depth plane over the culling box, the sub-block copies, the whole-voxel shift
+// (nalo_tsdf_shift) and the plane nalo_tsdf_integrate_frame makes of a frame's dense list. (The surface points are kernels_tsdf_mesh.hip's: the mesh's passes on the axis edges.) Built
 // WITHOUT FMA contraction: every expression below is the header's definition, one rounding per operation.
 #include "nalo_internal.h"
 #include "tsdf_device.h"
@@ -154,6 +154,96 @@ int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], 
     TsdfBlock B = {dims[0], dims[1], {lo[0], lo[1], lo[2]}, {size[0], size[1], size[2]}};
     const int total = size[0] * size[1] * size[2];                               // <= 2^29, checked by the caller
     tsdf_block_kernel<<<(total + 255) / 256, 256, 0, c->stream>>>(vol, block, B, total, to_volume);
+    NALO_HIP(c, hipGetLastError());
+    return NALO_OK;
+}
+
+// ---- nalo_tsdf_shift. A pure copy, driven from the destination and out of place: dst voxel (i, j, k) takes the words of src voxel (i + s0, j + s1, k + s2), or
+// the initial values where that lies outside the grid. As in the integration a lane owns four voxels that are consecutive in memory and 16-byte aligned by
+// linear index, here over the whole array, so where nx is no multiple of four a group straddles rows. The n % 4 voxels behind the last whole group go one to a
+// lane, word by word: no access reaches past the arrays. A group is classified once and every array (tsdf, weight, the three colour planes) moves by it:
+//   kTsdfShiftInit   the group lies in one row and all four sources lie outside the grid: the initial values are stored, nothing is loaded
+//   kTsdfShiftRow    the group lies in one row and so do its four sources, inside the grid: they are consecutive at g + delta, one 16-byte load where delta is a
+//                    multiple of four (for nx a multiple of four: s0 % 4 == 0), else four words
+//   kTsdfShiftMixed  everything else (a row's two ends, a group that straddles rows): each voxel on its own index
+// Words move as unsigned: no float operation touches them, so NaN payloads, -0.0f and denormals pass. Colour is a compile-time flag.
+enum { kTsdfShiftInit = 0, kTsdfShiftRow = 1, kTsdfShiftMixed = 2 };
+struct TsdfShiftGroup { long long g, at[4]; int mode, in; };                   // at[e]: the source index of voxel g + e where bit e of `in` is set
+
+// the source of the voxel with linear index idx (below 2^29: its split into (i, j, k) is 32-bit arithmetic, the addresses are not); false: outside the grid
+__device__ __forceinline__ bool tsdf_shift_source(const TsdfShiftDev& P, unsigned idx, long long& at) {
+    const unsigned row = idx / (unsigned)P.nx, k = row / (unsigned)P.ny;
+    const int si = (int)(idx - row * (unsigned)P.nx) + P.s[0], sj = (int)(row - k * (unsigned)P.ny) + P.s[1], sk = (int)k + P.s[2];
+    at = ((long long)sk * P.ny + sj) * P.nx + si;
+    return si >= 0 && si < P.nx && sj >= 0 && sj < P.ny && sk >= 0 && sk < P.nz;
+}
+
+// V4: four words as one access. tsdf and weight are allocations of their own, so a group is 16-byte aligned: uint4. A colour plane begins n words into its
+// block, 16-byte aligned only where n is a multiple of four: TsdfWords4 says so to the compiler, which still issues one 16-byte access (global memory takes it
+// at any 4-byte aligned address), at full rate where the address is aligned
+typedef uint4 __attribute__((aligned(4))) TsdfWords4;
+template <typename V4>
+__device__ __forceinline__ void tsdf_shift_array(const unsigned* __restrict__ src, unsigned* __restrict__ dst, const TsdfShiftGroup& G, long long delta, unsigned init) {
+    uint4 v = make_uint4(init, init, init, init);
+    if (G.mode == kTsdfShiftRow) {
+        const unsigned* p = src + (G.g + delta);
+        if ((delta & 3) == 0) v = *reinterpret_cast<const V4*>(p);
+        else { v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3]; }
+    } else if (G.mode == kTsdfShiftMixed) {
+        if (G.in & 1) v.x = src[G.at[0]];
+        if (G.in & 2) v.y = src[G.at[1]];
+        if (G.in & 4) v.z = src[G.at[2]];
+        if (G.in & 8) v.w = src[G.at[3]];
+    }
+    *reinterpret_cast<V4*>(dst + G.g) = v;
+}
+
+template <bool kColour>
+__global__ __launch_bounds__(256) void tsdf_shift_kernel(TsdfShiftDev P) {
+    const long long groups = P.n / 4, stride = (long long)gridDim.x * blockDim.x;  // whole groups
+    const long long delta = ((long long)P.s[2] * P.ny + P.s[1]) * P.nx + P.s[0];   // source index - destination index wherever both lie in the grid
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
+        TsdfShiftGroup G;
+        G.g = 4 * q;
+        G.in = 0;
+        const unsigned gu = (unsigned)G.g, row = gu / (unsigned)P.nx, k = row / (unsigned)P.ny;
+        const int i = (int)(gu - row * (unsigned)P.nx), j = (int)(row - k * (unsigned)P.ny);
+        const int si = i + P.s[0], sj = j + P.s[1], sk = (int)k + P.s[2];
+        const bool one_row = i + 3 < P.nx, row_in = sj >= 0 && sj < P.ny && sk >= 0 && sk < P.nz;
+        if (one_row && (!row_in || si + 3 < 0 || si >= P.nx)) G.mode = kTsdfShiftInit;
+        else if (one_row && si >= 0 && si + 3 < P.nx) G.mode = kTsdfShiftRow;      // row_in holds here: the branch above took the rest
+        else {
+            G.mode = kTsdfShiftMixed;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) if (tsdf_shift_source(P, gu + (unsigned)e, G.at[e])) G.in |= 1 << e;
+        }
+        tsdf_shift_array<uint4>(P.src_tsdf, P.dst_tsdf, G, delta, 0x3F800000u);   // 1.0f
+        tsdf_shift_array<uint4>(P.src_weight, P.dst_weight, G, delta, 0u);
+        if constexpr (kColour) {
+#pragma unroll
+            for (int X = 0; X < 3; ++X) tsdf_shift_array<TsdfWords4>(P.src_col + (size_t)X * P.n, P.dst_col + (size_t)X * P.n, G, delta, 0u);
+        }
+    }
+    // the n % 4 voxels behind the last whole group
+    if (blockIdx.x == 0 && (long long)threadIdx.x < P.n - 4 * groups) {
+        const long long idx = 4 * groups + threadIdx.x;
+        long long at;
+        const bool in = tsdf_shift_source(P, (unsigned)idx, at);
+        P.dst_tsdf[idx] = in ? P.src_tsdf[at] : 0x3F800000u;
+        P.dst_weight[idx] = in ? P.src_weight[at] : 0u;
+        if constexpr (kColour) {
+#pragma unroll
+            for (int X = 0; X < 3; ++X) P.dst_col[(size_t)X * P.n + idx] = in ? P.src_col[(size_t)X * P.n + at] : 0u;
+        }
+    }
+}
+int tsdf_shift_launch(nalo_ctx* c, const TsdfShiftDev& D) {
+    if (D.n < 1 || D.n > (1LL << 29) || D.n != (long long)D.nx * D.ny * D.nz) return fail(c, NALO_ERR_ARG, "tsdf_shift_launch: bad grid");
+    for (int a = 0; a < 3; ++a) { const int n = a == 0 ? D.nx : a == 1 ? D.ny : D.nz; if (D.s[a] > n || D.s[a] < -n) return fail(c, NALO_ERR_ARG, "tsdf_shift_launch: shift not clamped"); }
+    const long long want = std::max<long long>((D.n / 4 + 255) / 256, 1);        // memory-bound: at most 2048 workgroups, the rest by the grid stride
+    ProfScope ps(c, "tsdf_shift");
+    if (D.src_col) tsdf_shift_kernel<true><<<(unsigned)std::min<long long>(want, 2048), 256, 0, c->stream>>>(D);
+    else tsdf_shift_kernel<false><<<(unsigned)std::min<long long>(want, 2048), 256, 0, c->stream>>>(D);
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;
 }

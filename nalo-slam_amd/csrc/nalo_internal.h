@@ -469,6 +469,16 @@ int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D);
 int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
 // one array's sub-block [lo, lo + size) to (to_volume = 0) or from (1) a contiguous block, x fastest
 int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume);
+// nalo_tsdf_shift: dst voxel (i, j, k) = src voxel (i + s[0], j + s[1], k + s[2]) as 32-bit words, the initial values where that lies outside the grid. Out of
+// place: src is read only, every word of dst is written, the two never alias. src_col != NULL selects the coloured instantiation; the other touches neither
+// colour pointer
+struct TsdfShiftDev {
+    const unsigned *src_tsdf, *src_weight, *src_col;                            // col: [3][n], the planes n words apart
+    unsigned *dst_tsdf, *dst_weight, *dst_col;
+    int nx, ny, nz, s[3];                                                       // |s[a]| <= dims[a]: the host clamps, beyond it nothing is kept either way
+    long long n;                                                                // nx ny nz <= 2^29
+};
+int tsdf_shift_launch(nalo_ctx* c, const TsdfShiftDev& D);
 // nalo_tsdf_mesh and nalo_tsdf_surface_points (kernels_tsdf_mesh.hip): an ordered compaction over the sub-box, kTsdfVoxPerBlock voxels to a workgroup. The
 // surface points are the mesh's vertices on the axis edges: they run the classify and the vertex pass restricted to those, and no triangle pass.
 constexpr int kTsdfVoxPerBlock = 1024;                                          // 256 lanes x 4 consecutive voxels of the sub-box

@@ -9,5 +9,8 @@ namespace nalo {
 const char* tsdf_desc_refusal(const nalo_tsdf_desc* d);
 // M = worldToCam in float from camToWorld in double (R^T and -(R^T t), each row summed left to right in double); false: an entry is not finite
 bool tsdf_world_to_cam(const double camToWorld[12], float M[12]);
+// nalo_tsdf_shift's host half: new_base = base + shift (refused beyond 2^24 in magnitude, the sum taken in 64 bits) and origin[a] = origin0[a] +
+// (float)new_base[a] * voxel_size, the product rounded, then the sum. NULL when good, else the reason (a static string); the outputs are written only when good
+const char* tsdf_shift_geometry(const float origin0[3], float voxel_size, const int base[3], const int shift[3], int new_base[3], float origin[3]);
 
 }  // namespace nalo
