@@ -1710,6 +1710,63 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    kept y by leaving z; an axis with s = 0 contributes none. The cells of the boxes are pairwise disjoint and their union is exactly the
  *                    cells that do not survive (nalo_tsdf_mesh cuts cells at a sub-box's faces). Unused entries of lo / size are zero. NALO_ERR_ARG for a
  *                    NULL pointer or a dimension outside [1, 2048].
+ *
+ * The mesh archive. The meshes of the boxes that leave a following volume, kept on the device as ONE indexed triangle list and welded by vertex identity, not by
+ * position: the seam voxels stay in the volume and keep integrating, and the origin is recomputed at every shift, so the later copy of a seam vertex lies
+ * somewhere else in its last bits or more. The archive lives in the context next to the volume and outlives it: nalo_tsdf_create, nalo_tsdf_destroy and
+ * nalo_tsdf_reset leave its contents alone (a drive may replace its volume); nalo_destroy frees it.
+ *   Identity: the vertex nalo_tsdf_mesh places on edge (v, m) of sub-box [lo, lo + size) has the KEY (gx, gy, gz, m), g = base + lo + (i, j, k) of v with the
+ *     base nalo_tsdf_geometry reports at the time of the call: four ints, one 16-byte word. |base| <= 2^24 and a dimension <= 2048: nothing overflows. Two
+ *     vertices are the same vertex iff their keys are equal. Within one mesh all keys are distinct (an edge carries at most one vertex); duplicates arise
+ *     only between a piece and what was archived before it.
+ *   Append of a piece (the device mesh a mesh call left): its vertices are visited in the piece's order. A vertex whose key the archive holds is dropped and
+ *     its index maps to the archived one: the FIRST occurrence's position and colour win. Every other vertex is added at the end, in order, its xyz, rgba and
+ *     key copied as words (a NaN position passes). Then all the piece's triangles are added at the end, in order, with mapped indices. Triangles are never
+ *     deduplicated: the same box archived twice adds no vertex and every triangle a second time.
+ *   Lattice: the archive belongs to one lattice. Its first successful append records the volume's origin0 and voxel_size as words (nalo_tsdf_archive_reset
+ *     forgets them); the same lattice re-created is accepted.
+ * nalo_tsdf_archive_enable   allocates the archive (4096 vertices, 8192 triangles, 8192 table slots) and empties it. It is COLOURED iff there is a volume and its
+ *                    colour is enabled at that moment. Already enabled: NALO_OK, nothing changes. A failed allocation (NALO_ERR_HIP) leaves the context as it
+ *                    was. A context that never enables the archive queues exactly what it queued before.
+ * nalo_tsdf_archive_disable  frees it (it waits for the main stream first); not enabled: NALO_OK.
+ * nalo_tsdf_archive_reset    empties it and keeps its buffers and its colour state; queues one fill of the table, no wait.
+ * nalo_tsdf_archive_mesh     DEFINED as nalo_tsdf_mesh(ctx, m) - nalo_tsdf_mesh_color with no host colours when the archive is coloured - followed by the append
+ *                    of the device mesh. The host arrays and caps in m are honoured as nalo_tsdf_mesh honours them; the device mesh and nalo_tsdf_mesh_view
+ *                    (and nalo_tsdf_mesh_color_view) behind the call are exactly what the mesh call alone leaves. out (may be NULL): the vertices added, the
+ *                    vertices welded and the triangles added by this call, and what nalo_tsdf_archive_stats reports.
+ *                    The passes, all on the main stream: a key pass directly behind the mesh (it reads the mesh passes' scratch, which
+ *                    nalo_tsdf_surface_points would overwrite); a read-only lookup, one lane per piece vertex, through an open-addressed table of 32-bit
+ *                    slots (an archived index or empty; keys are compared through the archive's key array, one 16-byte load); a scan of the "new" flags; a
+ *                    pass that writes the new vertices and inserts them with one 32-bit atomicCAS on an empty slot each (all inserted keys are distinct and
+ *                    absent); a triangle pass. Which slot a key lands in is not observable; everything observable is fixed by the definition: the same
+ *                    bytes on every run, no float atomic. Before launching, the host makes room for the worst case, every piece vertex new: buffers grow to
+ *                    what is needed plus a quarter (contents copied on the device), the table to the power of two that keeps its load at or below one half,
+ *                    rebuilt from the key array in one pass. Every probe loop is bounded by the slot count; a lane that exhausts it raises a device flag,
+ *                    the call returns NALO_ERR_HIP and the table is rebuilt from the vertices the archive held: nothing spins.
+ *                    Host waits: the mesh call's own (one, two when its buffers grow or a host array is filled) and ONE for the append, for the count of new
+ *                    vertices and the flag. An empty piece appends without a wait.
+ *                    NALO_ERR_STATE: the archive is not enabled, or there is no volume - nothing is queued. Every refusal of nalo_tsdf_mesh applies unchanged,
+ *                    and a cap below the count of a host array that is given (the device mesh IS built) appends nothing. NALO_ERR_STATE, with the plain
+ *                    nalo_tsdf_mesh of the box built as a mesh call would: a volume whose colour state differs from the archive's, or whose origin0 or
+ *                    voxel_size differ from the recorded ones. NALO_ERR_ARG, behind the mesh: an archive that would pass 2^31 - 1 vertices or triangles with
+ *                    every piece vertex counted as new. A refused or failed call, a failed growth (NALO_ERR_HIP) included, leaves the archive as it was,
+ *                    bit for bit.
+ * nalo_tsdf_archive_stats    host only, launches nothing: the last nalo_tsdf_archive_mesh's three counts (zeros behind enable and reset), the totals, the
+ *                    capacities, the table's slots, the colour state and the lattice (have_lattice 0: none recorded yet).
+ * nalo_tsdf_archive_get      copies to the host: xyz [n_vertices][3], tri [n_triangles][3], rgba [n_vertices][4], key [n_vertices][4], each optional (NULL) and
+ *                    each with its own cap, under the cap / count protocol of nalo_tsdf_mesh: n_vertices / n_triangles are always set; NALO_ERR_ARG with
+ *                    nothing written to ANY array for a negative cap, a cap > 0 with a NULL array, or a cap below the count of an array that is given.
+ *                    NALO_ERR_STATE for an rgba given to an uncoloured archive. One wait when anything is copied.
+ * nalo_tsdf_archive_view     host only, launches nothing: the device arrays (rgba NULL in an uncoloured archive), the counts and the producing stream, under
+ *                    "Lifetime of a view": good until the next nalo_tsdf_archive_mesh that grows a buffer, or until nalo_tsdf_archive_reset,
+ *                    nalo_tsdf_archive_disable or nalo_destroy. A later append that does not grow only adds behind the counts the view holds.
+ * nalo_tsdf_archive_get, _view and _stats are NALO_ERR_STATE before nalo_tsdf_archive_enable.
+ * nalo_tsdf_follow   the loop that keeps a volume around the camera, DEFINED as exactly these calls, in order, with nothing new underneath:
+ *                    nalo_tsdf_geometry; nalo_tsdf_shift_for(desc, centre, margin); if the shift is non-zero, nalo_tsdf_shift_boxes and
+ *                    nalo_tsdf_archive_mesh(box, min_weight, no host arrays) on each box in order; nalo_tsdf_shift. The first call that fails ends it with that
+ *                    call's code (a refusal of nalo_tsdf_shift_for or nalo_tsdf_shift_boxes: NALO_ERR_ARG). shift_out (may be NULL) takes the shift; stats
+ *                    (may be NULL) the number of boxes, the sums of the three per-call counts and the archive's totals. NALO_ERR_STATE with the archive
+ *                    disabled or without a volume, before anything else.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1782,10 +1839,31 @@ int nalo_tsdf_shift(nalo_ctx* ctx, const int shift[3]);
 int nalo_tsdf_geometry(nalo_ctx* ctx, struct nalo_tsdf_geometry* out);       /* host only, launches nothing */
 int nalo_tsdf_shift_for(const nalo_tsdf_desc* now, const double centre[3], const int margin[3], int shift[3]);   /* host only, no context */
 int nalo_tsdf_shift_boxes(const int dims[3], const int shift[3], struct nalo_tsdf_shift_boxes* out);            /* host only, no context */
+struct nalo_tsdf_archive_stats {                                             /* named by its tag, as nalo_tsdf_geometry */
+    long long added_vertices, welded_vertices, added_triangles;             /* the last nalo_tsdf_archive_mesh */
+    long long n_vertices, n_triangles;                                      /* the archive */
+    long long cap_vertices, cap_triangles, table_slots;
+    int coloured, have_lattice; float origin0[3], voxel_size;
+};
+typedef struct nalo_tsdf_archive_get_args {
+    long long cap_vertices, cap_triangles, cap_rgba, cap_key;               /* rows each array has room for */
+    float* xyz; int* tri; uint8_t* rgba; int* key;                          /* host, [cap][3], [cap][3], [cap][4], [cap][4]; NULL: not asked for */
+    long long n_vertices, n_triangles;                                      /* out */
+} nalo_tsdf_archive_get_args;
+typedef struct nalo_tsdf_archive_dev { float* xyz; int* tri; uint8_t* rgba; int* key; long long n_vertices, n_triangles; void* stream; } nalo_tsdf_archive_dev;
+typedef struct nalo_tsdf_follow_stats { int n_boxes; long long added_vertices, welded_vertices, added_triangles, n_vertices, n_triangles; } nalo_tsdf_follow_stats;
+int nalo_tsdf_archive_enable(nalo_ctx* ctx);
+int nalo_tsdf_archive_disable(nalo_ctx* ctx);
+int nalo_tsdf_archive_reset(nalo_ctx* ctx);
+int nalo_tsdf_archive_mesh(nalo_ctx* ctx, nalo_tsdf_mesh_args* m, struct nalo_tsdf_archive_stats* out);
+int nalo_tsdf_archive_stats(nalo_ctx* ctx, struct nalo_tsdf_archive_stats* out);   /* host only, launches nothing */
+int nalo_tsdf_archive_get(nalo_ctx* ctx, nalo_tsdf_archive_get_args* args);
+int nalo_tsdf_archive_view(nalo_ctx* ctx, nalo_tsdf_archive_dev* out);             /* host only, launches nothing */
+int nalo_tsdf_follow(nalo_ctx* ctx, const double centre[3], const int margin[3], float min_weight, int shift_out[3], nalo_tsdf_follow_stats* stats);
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift". Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh). Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

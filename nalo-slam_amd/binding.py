@@ -44,6 +44,7 @@ EXPORTS = [
     "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
     "nalo_tsdf_raycast", "nalo_tsdf_raycast_view", "nalo_tsdf_raycast_steps",
     "nalo_tsdf_shift", "nalo_tsdf_geometry", "nalo_tsdf_shift_for", "nalo_tsdf_shift_boxes",
+    "nalo_tsdf_archive_enable", "nalo_tsdf_archive_disable", "nalo_tsdf_archive_reset", "nalo_tsdf_archive_mesh", "nalo_tsdf_archive_stats", "nalo_tsdf_archive_get", "nalo_tsdf_archive_view", "nalo_tsdf_follow",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
     "nalo_pixsel_set_random", "nalo_pixsel_select", "nalo_pixsel_make_maps", "nalo_pixsel_make_maps_lidar", "nalo_pixsel_get_selected",
@@ -227,6 +228,26 @@ class TsdfGeometry(C.Structure):                          # struct nalo_tsdf_geo
 
 class TsdfShiftBoxes(C.Structure):                        # struct nalo_tsdf_shift_boxes
     _fields_ = [("n_boxes", C.c_int), ("lo", (C.c_int * 3) * 3), ("size", (C.c_int * 3) * 3), ("kept_lo", C.c_int * 3), ("kept_size", C.c_int * 3)]
+
+
+class TsdfArchiveStats(C.Structure):                      # struct nalo_tsdf_archive_stats
+    _fields_ = [("added_vertices", C.c_longlong), ("welded_vertices", C.c_longlong), ("added_triangles", C.c_longlong), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong),
+                ("cap_vertices", C.c_longlong), ("cap_triangles", C.c_longlong), ("table_slots", C.c_longlong), ("coloured", C.c_int), ("have_lattice", C.c_int),
+                ("origin0", C.c_float * 3), ("voxel_size", C.c_float)]
+
+
+class TsdfArchiveGetArgs(C.Structure):                    # nalo_tsdf_archive_get_args
+    _fields_ = [("cap_vertices", C.c_longlong), ("cap_triangles", C.c_longlong), ("cap_rgba", C.c_longlong), ("cap_key", C.c_longlong),
+                ("xyz", c_fp), ("tri", c_ip), ("rgba", c_u8p), ("key", c_ip), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong)]
+
+
+class TsdfArchiveDev(C.Structure):                        # nalo_tsdf_archive_dev
+    _fields_ = [("xyz", C.c_void_p), ("tri", C.c_void_p), ("rgba", C.c_void_p), ("key", C.c_void_p), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong), ("stream", C.c_void_p)]
+
+
+class TsdfFollowStats(C.Structure):                       # nalo_tsdf_follow_stats
+    _fields_ = [("n_boxes", C.c_int), ("added_vertices", C.c_longlong), ("welded_vertices", C.c_longlong), ("added_triangles", C.c_longlong), ("n_vertices", C.c_longlong),
+                ("n_triangles", C.c_longlong)]
 
 
 class DepthImageArgs(C.Structure):
@@ -625,6 +646,14 @@ def load():
     L.nalo_tsdf_shift.argtypes = [vp, c_ip]
     L.nalo_tsdf_geometry.argtypes = [vp, C.POINTER(TsdfGeometry)]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
+    L.nalo_tsdf_archive_enable.argtypes = [vp]
+    L.nalo_tsdf_archive_disable.argtypes = [vp]
+    L.nalo_tsdf_archive_reset.argtypes = [vp]
+    L.nalo_tsdf_archive_mesh.argtypes = [vp, C.POINTER(TsdfMeshArgs), C.POINTER(TsdfArchiveStats)]
+    L.nalo_tsdf_archive_stats.argtypes = [vp, C.POINTER(TsdfArchiveStats)]
+    L.nalo_tsdf_archive_get.argtypes = [vp, C.POINTER(TsdfArchiveGetArgs)]
+    L.nalo_tsdf_archive_view.argtypes = [vp, C.POINTER(TsdfArchiveDev)]
+    L.nalo_tsdf_follow.argtypes = [vp, c_dp, c_ip, C.c_float, c_ip, C.POINTER(TsdfFollowStats)]
     L.nalo_ba_get_points.argtypes = [vp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
     L.nalo_ba_get_residuals.argtypes = [vp, c_i8p, c_u8p, c_fp, c_fp, c_fp]
     L.nalo_ba_get_acc13.argtypes = [vp, c_dp]
@@ -1838,6 +1867,86 @@ class Context:
         return dict(depth=DeviceView(v.depth.ptr, (v.h, v.w), "<f4", None, v.stream, self),
                     normal=DeviceView(v.normal.ptr, (v.h, v.w, 3), "<f4", None, v.stream, self) if v.normal.ptr else None,
                     rgba=DeviceView(v.rgba.ptr, (v.h, v.w, 4), "|u1", None, v.stream, self) if v.rgba.ptr else None)
+
+    # ---- the mesh archive (nalo_tsdf_archive_*)
+    @staticmethod
+    def _archive_stats(st):
+        return dict(added_vertices=int(st.added_vertices), welded_vertices=int(st.welded_vertices), added_triangles=int(st.added_triangles), n_vertices=int(st.n_vertices),
+                    n_triangles=int(st.n_triangles), cap_vertices=int(st.cap_vertices), cap_triangles=int(st.cap_triangles), table_slots=int(st.table_slots),
+                    coloured=bool(st.coloured), have_lattice=bool(st.have_lattice), origin0=np.array(st.origin0, np.float32), voxel_size=np.float32(st.voxel_size))
+
+    def tsdf_archive_enable(self):
+        """nalo_tsdf_archive_enable: an empty welded mesh archive in this context, coloured iff the volume's colour is enabled now; it outlives volumes"""
+        self._ck(self.L.nalo_tsdf_archive_enable(self.h_))
+
+    def tsdf_archive_disable(self):
+        self._ck(self.L.nalo_tsdf_archive_disable(self.h_))
+
+    def tsdf_archive_reset(self):
+        """nalo_tsdf_archive_reset: empties the archive, keeps its buffers and colour state, forgets its lattice"""
+        self._ck(self.L.nalo_tsdf_archive_reset(self.h_))
+
+    def tsdf_archive_stats(self):
+        """nalo_tsdf_archive_stats -> dict(added_vertices, welded_vertices, added_triangles (the last tsdf_archive_mesh), n_vertices, n_triangles, cap_vertices,
+        cap_triangles, table_slots, coloured, have_lattice, origin0, voxel_size). Launches nothing"""
+        st = TsdfArchiveStats()
+        self._ck(self.L.nalo_tsdf_archive_stats(self.h_, C.byref(st)))
+        return self._archive_stats(st)
+
+    def tsdf_archive_mesh(self, min_weight, box=None):
+        """nalo_tsdf_archive_mesh: tsdf_mesh of box = (lo, size) (None: the whole grid), left on the device, and its append to the archive: a vertex whose key
+        (global voxel, edge) the archive holds is welded to the archived one, the others and every triangle are added at the end. -> the dict of
+        tsdf_archive_stats. self.tsdf_mesh_counts holds the piece's counts, a refusal included"""
+        a, st = TsdfMeshArgs(), TsdfArchiveStats()
+        if box is not None:
+            a.use_box = 1
+            a.lo[:] = [int(v) for v in box[0]]
+            a.size[:] = [int(v) for v in box[1]]
+        a.min_weight = float(min_weight)
+        rc = self.L.nalo_tsdf_archive_mesh(self.h_, C.byref(a), C.byref(st))
+        self.tsdf_mesh_counts = (int(a.n_vertices), int(a.n_triangles))
+        self._ck(rc)
+        return self._archive_stats(st)
+
+    def tsdf_archive_get(self, keys=False):
+        """nalo_tsdf_archive_get -> xyz float32 [nv][3], tri int32 [nt][3][, rgba uint8 [nv][4] of a coloured archive][, key int32 [nv][4] = (gx, gy, gz, m)]:
+        the whole archive, sized from tsdf_archive_stats; what write_ply_mesh takes as it comes"""
+        st = self.tsdf_archive_stats()
+        nv, nt = st["n_vertices"], st["n_triangles"]
+        xyz, tri = np.zeros((nv, 3), np.float32), np.zeros((nt, 3), np.int32)
+        rgba = np.zeros((nv, 4), np.uint8) if st["coloured"] else None
+        key = np.zeros((nv, 4), np.int32) if keys else None
+        a = TsdfArchiveGetArgs()
+        a.cap_vertices, a.xyz = nv, (_f(xyz) if nv else None)
+        a.cap_triangles, a.tri = nt, (_i(tri) if nt else None)
+        if rgba is not None:
+            a.cap_rgba, a.rgba = nv, (_u8(rgba) if nv else None)
+        if key is not None:
+            a.cap_key, a.key = nv, (_i(key) if nv else None)
+        self._ck(self.L.nalo_tsdf_archive_get(self.h_, C.byref(a)))
+        return tuple(x for x in (xyz, tri, rgba, key) if x is not None)
+
+    def tsdf_archive_view(self):
+        """nalo_tsdf_archive_view -> dict(xyz [nv, 3] float32, tri [nt, 3] int32, rgba [nv, 4] uint8 or None, key [nv, 4] int32) of DeviceViews:
+        torch.as_tensor(view, device="cuda") is a zero-copy tensor. Launches nothing; good until a tsdf_archive_mesh that grows a buffer, tsdf_archive_reset,
+        tsdf_archive_disable or close"""
+        v = TsdfArchiveDev()
+        self._ck(self.L.nalo_tsdf_archive_view(self.h_, C.byref(v)))
+        nv, nt = v.n_vertices, v.n_triangles
+        return dict(xyz=DeviceView(v.xyz, (nv, 3), "<f4", None, v.stream, self), tri=DeviceView(v.tri, (nt, 3), "<i4", None, v.stream, self),
+                    rgba=DeviceView(v.rgba, (nv, 4), "|u1", None, v.stream, self) if v.rgba else None, key=DeviceView(v.key, (nv, 4), "<i4", None, v.stream, self))
+
+    def tsdf_follow(self, centre, margin, min_weight):
+        """nalo_tsdf_follow: tsdf_geometry, tsdf_shift_for(centre, margin), tsdf_archive_mesh of every box of tsdf_shift_boxes in order, tsdf_shift, as one call
+        -> dict(shift int32 [3], n_boxes, added_vertices, welded_vertices, added_triangles, n_vertices, n_triangles)"""
+        ce = np.ascontiguousarray(centre, np.float64).reshape(-1)
+        mg = np.ascontiguousarray(margin, np.int32).reshape(-1)
+        if ce.size != 3 or mg.size != 3:
+            raise NaloError("tsdf_follow: centre and margin hold three values each")
+        shift, st = np.zeros(3, np.int32), TsdfFollowStats()
+        self._ck(self.L.nalo_tsdf_follow(self.h_, _d(ce), _i(mg), C.c_float(min_weight), _i(shift), C.byref(st)))
+        return dict(shift=shift, n_boxes=int(st.n_boxes), added_vertices=int(st.added_vertices), welded_vertices=int(st.welded_vertices),
+                    added_triangles=int(st.added_triangles), n_vertices=int(st.n_vertices), n_triangles=int(st.n_triangles))
 
     def map_dense_cloud(self, frame_id, draws=None, cap=None, n_draws=None):
         """refreshPC() for one frame's dense points -> dict(xyz [n][3] float32, rgb [n][3] uint8, records, survivors, n_needed); cap / n_draws override the sizes

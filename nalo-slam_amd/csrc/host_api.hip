@@ -60,6 +60,7 @@ void nalo_destroy(nalo_ctx* c) {
     map_destroy(c);
     map_dense_destroy(c);
     tsdf_destroy(c);
+    tsdf_archive_destroy(c);
     if (c->copy) (void)hipStreamSynchronize(c->copy);
     // the profiling events are raw handles (they move between the pool and the pending pairs): this is where they end
     for (auto& kv : c->prof) for (auto& ev : kv.second.pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }

@@ -38,15 +38,31 @@ struct TsdfVolume {
     int rc_w = 0, rc_h = 0; bool have_rc = false, rc_normal_on = false, rc_rgba_on = false;
 };
 
+// The mesh archive (nalo_tsdf_archive_*): it hangs off the context, not the volume, and outlives volumes. xyz, rgba and key have room for cap_v vertices, tri for
+// cap_t triangles; the table is `slots` ints, a power of two, at most half of them taken after any append. The piece's keys, its index map and the counts of new
+// vertices are scratch of one append.
+struct TsdfArchive {
+    bool coloured = false, have_lattice = false;
+    unsigned origin0[3] = {0, 0, 0}, voxel_size = 0;                             // the lattice, as words
+    DevBuf<float> xyz; DevBuf<unsigned> rgba; DevBuf<int4> key; DevBuf<int> tri, table;
+    long long nv = 0, nt = 0, cap_v = 0, cap_t = 0, slots = 0;
+    DevBuf<int4> p_key; DevBuf<int> p_map, cnt, err; HostBuf<int> back;          // back: the count of new vertices and the flag, as they come up
+    long long added_v = 0, welded_v = 0, added_t = 0;                            // the last append
+};
+
 // a caller's colour plane as the integration kernel reads it: byte strides, sc[X] the offset of the channel that feeds plane X (B, G, R)
 struct TsdfColourSrc { const unsigned char* p; long long sy, sx, sc[3]; };
 
 constexpr long long kTsdfMeshMaxVoxels = 1LL << 28;                               // seven vertices a voxel must fit an int index
 constexpr long long kTsdfMeshFirstVertices = 1LL << 14, kTsdfMeshFirstTriangles = 1LL << 15;   // the device mesh's first capacity; it grows to what a call finds plus a quarter
 
+constexpr long long kTsdfArchiveFirstVertices = 1LL << 12, kTsdfArchiveFirstTriangles = 1LL << 13, kTsdfArchiveFirstSlots = 1LL << 13;
+constexpr long long kTsdfArchiveMax = 2147483647LL;                                // an index is an int
+
 constexpr size_t kTsdfTileFloats = (size_t)1 << 22;   // nalo_tsdf_get / _set: 16 MiB of staging
 
 void tsdf_destroy(nalo_ctx* c) { delete c->tsdf; c->tsdf = nullptr; }
+void tsdf_archive_destroy(nalo_ctx* c) { delete c->tsdf_archive; c->tsdf_archive = nullptr; }
 
 static int tsdf_need(nalo_ctx* c, const char* who) {
     if (!c) return NALO_ERR_ARG;
@@ -420,8 +436,8 @@ int nalo_tsdf_surface_points(nalo_ctx* c, nalo_tsdf_surface_args* a) {
     return NALO_OK;
 }
 
-// nalo_tsdf_mesh (coloured = false; cc is not looked at) and nalo_tsdf_mesh_color
-static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a, bool coloured, nalo_tsdf_mesh_color_args* cc) {
+// nalo_tsdf_mesh (coloured = false; cc is not looked at) and nalo_tsdf_mesh_color. Dout (nalo_tsdf_archive_mesh): what the passes ran with, once the device mesh is built
+static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a, bool coloured, nalo_tsdf_mesh_color_args* cc, TsdfMeshDev* Dout = nullptr) {
     { const int rc = tsdf_need(c, who.c_str()); if (rc) return rc; }
     if (!a || (coloured && !cc)) return fail(c, NALO_ERR_ARG, who + ": bad argument");
     a->n_vertices = 0; a->n_triangles = 0;
@@ -478,6 +494,7 @@ static int tsdf_mesh(nalo_ctx* c, const std::string& who, nalo_tsdf_mesh_args* a
         { const int rc = tsdf_mesh_write_launch(c, D, false); if (rc) return rc; }
     }
     v.mesh_nv = nv; v.mesh_nt = nt; v.have_mesh = true; v.mesh_coloured = coloured;
+    if (Dout) *Dout = D;
     a->n_vertices = nv; a->n_triangles = nt;
     uint8_t* rgba = coloured ? cc->rgba : nullptr;
     if ((a->xyz && a->cap_vertices < nv) || (a->tri && a->cap_triangles < nt) || (rgba && cc->cap < nv))
@@ -591,5 +608,246 @@ int nalo_tsdf_raycast_view(nalo_ctx* c, nalo_tsdf_raycast_dev* out) {
     out->rgba = nalo_dev_plane{v.rc_rgba_on ? v.rc_rgba.p : nullptr, NALO_DT_U8, v.rc_w, v.rc_h, 3, 4 * w, 4, 1};   // R, G, B as three channels; the alpha byte lies between pixels
     out->w = v.rc_w; out->h = v.rc_h;
     out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
+}
+
+// ---- the mesh archive
+static int tsdf_archive_need(nalo_ctx* c, const char* who) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->tsdf_archive) return fail(c, NALO_ERR_STATE, std::string(who) + ": the archive is not enabled (nalo_tsdf_archive_enable)");
+    return NALO_OK;
+}
+static void tsdf_archive_fill_stats(const TsdfArchive& A, struct nalo_tsdf_archive_stats* out) {
+    out->added_vertices = A.added_v; out->welded_vertices = A.welded_v; out->added_triangles = A.added_t;
+    out->n_vertices = A.nv; out->n_triangles = A.nt;
+    out->cap_vertices = A.cap_v; out->cap_triangles = A.cap_t; out->table_slots = A.slots;
+    out->coloured = A.coloured ? 1 : 0; out->have_lattice = A.have_lattice ? 1 : 0;
+    std::memcpy(out->origin0, A.origin0, sizeof A.origin0); std::memcpy(&out->voxel_size, &A.voxel_size, 4);
+}
+static unsigned tsdf_word(float f) { unsigned u; std::memcpy(&u, &f, 4); return u; }
+// the smallest power of two of slots that holds nv vertices at a load of one half or less
+static long long tsdf_archive_slots_for(long long nv) {
+    long long s = kTsdfArchiveFirstSlots;
+    while (s < 2 * nv) s *= 2;
+    return s;
+}
+
+int nalo_tsdf_archive_enable(nalo_ctx* c) {
+    if (!c) return NALO_ERR_ARG;
+    if (c->tsdf_archive) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfArchive* A = new TsdfArchive();
+    A->coloured = c->tsdf && c->tsdf->colour.p;
+    hipError_t e = A->xyz.reserve(3 * (size_t)kTsdfArchiveFirstVertices);
+    if (e == hipSuccess) e = A->key.reserve((size_t)kTsdfArchiveFirstVertices);
+    if (e == hipSuccess && A->coloured) e = A->rgba.reserve((size_t)kTsdfArchiveFirstVertices);
+    if (e == hipSuccess) e = A->tri.reserve(3 * (size_t)kTsdfArchiveFirstTriangles);
+    if (e == hipSuccess) e = A->table.reserve((size_t)kTsdfArchiveFirstSlots);
+    if (e == hipSuccess) e = A->err.reserve(1);
+    if (e == hipSuccess) e = A->back.reserve(2);
+    if (e == hipSuccess) e = hipMemsetAsync(A->table.p, 0xFF, (size_t)kTsdfArchiveFirstSlots * sizeof(int), c->stream);      // kTsdfArchiveEmpty is all bits set
+    if (e == hipSuccess) e = hipMemsetAsync(A->err.p, 0, sizeof(int), c->stream);
+    if (e != hipSuccess) { delete A; (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_archive_enable: ") + hipGetErrorString(e)); }
+    A->cap_v = kTsdfArchiveFirstVertices; A->cap_t = kTsdfArchiveFirstTriangles; A->slots = kTsdfArchiveFirstSlots;
+    c->tsdf_archive = A;
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_disable(nalo_ctx* c) {
+    if (!c) return NALO_ERR_ARG;
+    if (!c->tsdf_archive) return NALO_OK;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));                              // kernels that name the arrays may still be queued
+    tsdf_archive_destroy(c);
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_reset(nalo_ctx* c) {
+    { const int rc = tsdf_archive_need(c, "nalo_tsdf_archive_reset"); if (rc) return rc; }
+    TsdfArchive& A = *c->tsdf_archive;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipMemsetAsync(A.table.p, 0xFF, (size_t)A.slots * sizeof(int), c->stream));
+    A.nv = A.nt = 0; A.added_v = A.welded_v = A.added_t = 0; A.have_lattice = false;
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_stats(nalo_ctx* c, struct nalo_tsdf_archive_stats* out) {
+    { const int rc = tsdf_archive_need(c, "nalo_tsdf_archive_stats"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_stats: bad argument");
+    tsdf_archive_fill_stats(*c->tsdf_archive, out);
+    return NALO_OK;
+}
+
+// an all-empty table of `slots` filled from the first nv keys
+static int tsdf_archive_rebuild(nalo_ctx* c, TsdfArchive& A, int* table, long long slots, long long nv) {
+    NALO_HIP(c, hipMemsetAsync(table, 0xFF, (size_t)slots * sizeof(int), c->stream));
+    return tsdf_archive_rebuild_launch(c, A.key.p, (int)nv, table, (unsigned)(slots - 1), A.err.p);
+}
+
+// the append behind a mesh call that succeeded: D is what its passes ran with, v.mesh_* the device mesh
+static int tsdf_archive_append(nalo_ctx* c, TsdfArchive& A, TsdfVolume& v, const TsdfMeshDev& D) {
+    const char* who = "nalo_tsdf_archive_mesh";
+    const long long nv = v.mesh_nv, nt = v.mesh_nt;
+    const long long need_v = A.nv + nv, need_t = A.nt + nt;                       // the worst case: every piece vertex is new
+    if (need_v > kTsdfArchiveMax || need_t > kTsdfArchiveMax) return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_mesh: the archive would pass 2^31 - 1 vertices or triangles");
+    if (nv == 0) {                                                             // no vertex, so no triangle: nothing to queue
+        A.added_v = A.welded_v = A.added_t = 0;
+        if (!A.have_lattice) { for (int k = 0; k < 3; ++k) A.origin0[k] = tsdf_word(v.origin0[k]); A.voxel_size = tsdf_word(v.d.voxel_size); A.have_lattice = true; }
+        return NALO_OK;
+    }
+    // everything that has to grow is allocated before anything is replaced: a failed allocation leaves the archive as it was
+    const long long rv = need_v > A.cap_v ? std::min(kTsdfArchiveMax, need_v + need_v / 4) : A.cap_v;
+    const long long rt = need_t > A.cap_t ? std::min(kTsdfArchiveMax, need_t + need_t / 4) : A.cap_t;
+    const long long slots = std::max(A.slots, tsdf_archive_slots_for(need_v));
+    const int nb = (int)((nv + 255) / 256);
+    {
+        DevBuf<float> xyz; DevBuf<unsigned> rgba; DevBuf<int4> key; DevBuf<int> tri, table;
+        hipError_t e = hipSuccess;
+        if (rv > A.cap_v) {
+            e = xyz.reserve(3 * (size_t)rv);
+            if (e == hipSuccess) e = key.reserve((size_t)rv);
+            if (e == hipSuccess && A.coloured) e = rgba.reserve((size_t)rv);
+        }
+        if (e == hipSuccess && rt > A.cap_t) e = tri.reserve(3 * (size_t)rt);
+        if (e == hipSuccess && slots > A.slots) e = table.reserve((size_t)slots);
+        if (e == hipSuccess) e = A.p_key.reserve((size_t)nv);
+        if (e == hipSuccess) e = A.p_map.reserve((size_t)nv);
+        if (e == hipSuccess) e = A.cnt.reserve((size_t)nb + 1);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+        // the contents move on the main stream, behind everything that wrote them; the old arrays are freed as the locals leave scope (hipFree waits for the device)
+        if (xyz.p) {
+            if (A.nv > 0) {
+                NALO_HIP(c, hipMemcpyAsync(xyz.p, A.xyz.p, 3 * (size_t)A.nv * 4, hipMemcpyDeviceToDevice, c->stream));
+                NALO_HIP(c, hipMemcpyAsync(key.p, A.key.p, (size_t)A.nv * sizeof(int4), hipMemcpyDeviceToDevice, c->stream));
+                if (A.coloured) NALO_HIP(c, hipMemcpyAsync(rgba.p, A.rgba.p, (size_t)A.nv * 4, hipMemcpyDeviceToDevice, c->stream));
+            }
+            A.xyz = std::move(xyz); A.key = std::move(key); if (A.coloured) A.rgba = std::move(rgba);
+            A.cap_v = rv;
+        }
+        if (tri.p) {
+            if (A.nt > 0) NALO_HIP(c, hipMemcpyAsync(tri.p, A.tri.p, 3 * (size_t)A.nt * 4, hipMemcpyDeviceToDevice, c->stream));
+            A.tri = std::move(tri); A.cap_t = rt;
+        }
+        if (table.p) {
+            { const int rc = tsdf_archive_rebuild(c, A, table.p, slots, A.nv); if (rc) return rc; }
+            A.table = std::move(table); A.slots = slots;
+        }
+    }
+    TsdfArchiveDev P{};
+    P.vmask = D.vmask; P.vbase = D.vbase; P.total = D.total;
+    for (int k = 0; k < 3; ++k) { P.lo[k] = D.lo[k]; P.size[k] = D.size[k]; P.base[k] = v.base[k]; }
+    P.p_xyz = v.mesh_xyz.p; P.p_rgba = A.coloured ? v.mesh_rgba.p : nullptr; P.p_tri = v.mesh_tri.p; P.p_nv = (int)nv; P.p_nt = (int)nt;
+    P.p_key = A.p_key.p; P.p_map = A.p_map.p; P.cnt = A.cnt.p; P.nb = nb;
+    P.xyz = A.xyz.p; P.rgba = A.coloured ? A.rgba.p : nullptr; P.key = A.key.p; P.tri = A.tri.p; P.nv = (int)A.nv; P.nt = (int)A.nt;
+    P.table = A.table.p; P.mask = (unsigned)(A.slots - 1); P.err = A.err.p;
+    {
+        ProfScope ps(c, "tsdf_archive");
+        { const int rc = tsdf_archive_keys_launch(c, P); if (rc) return rc; }
+        { const int rc = tsdf_archive_append_launch(c, P); if (rc) return rc; }
+    }
+    // the one wait of the append: how many vertices were new, and the flag
+    NALO_HIP(c, hipMemcpyAsync(A.back.p, P.cnt + nb, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(A.back.p + 1, A.err.p, 4, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const long long added = A.back.p[0];
+    if (A.back.p[1] != 0 || added < 0 || added > nv) {
+        // what the passes wrote lies behind nv and nt and is not part of the archive; the table may name it, so it is made again from the vertices that are
+        NALO_HIP(c, hipMemsetAsync(A.err.p, 0, sizeof(int), c->stream));
+        { const int rc = tsdf_archive_rebuild(c, A, A.table.p, A.slots, A.nv); if (rc) return rc; }
+        return fail(c, NALO_ERR_HIP, "nalo_tsdf_archive_mesh: a probe ran through the whole table, or the device counted more new vertices than the piece holds");
+    }
+    A.nv += added; A.nt += nt;
+    A.added_v = added; A.welded_v = nv - added; A.added_t = nt;
+    if (!A.have_lattice) { for (int k = 0; k < 3; ++k) A.origin0[k] = tsdf_word(v.origin0[k]); A.voxel_size = tsdf_word(v.d.voxel_size); A.have_lattice = true; }
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_mesh(nalo_ctx* c, nalo_tsdf_mesh_args* m, struct nalo_tsdf_archive_stats* out) {
+    const char* who = "nalo_tsdf_archive_mesh";
+    if (out) { const struct nalo_tsdf_archive_stats none = {}; *out = none; }
+    { const int rc = tsdf_archive_need(c, who); if (rc) return rc; }
+    TsdfArchive& A = *c->tsdf_archive;
+    if (out) { tsdf_archive_fill_stats(A, out); out->added_vertices = out->welded_vertices = out->added_triangles = 0; }
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    const bool other_colour = (v.colour.p != nullptr) != A.coloured;
+    bool other_lattice = false;
+    if (A.have_lattice) {
+        for (int k = 0; k < 3; ++k) other_lattice |= tsdf_word(v.origin0[k]) != A.origin0[k];
+        other_lattice |= tsdf_word(v.d.voxel_size) != A.voxel_size;
+    }
+    if (other_colour || other_lattice) {
+        // refused, but behind a mesh call: the plain mesh of the box is built as nalo_tsdf_mesh would build it
+        { const int rc = tsdf_mesh(c, who, m, false, nullptr); if (rc) return rc; }
+        return fail(c, NALO_ERR_STATE, other_colour ? "nalo_tsdf_archive_mesh: the volume's colour state differs from the archive's (the device mesh is built)"
+                                                    : "nalo_tsdf_archive_mesh: the volume's origin0 or voxel_size differ from the archive's lattice (the device mesh is built)");
+    }
+    TsdfMeshDev D;
+    nalo_tsdf_mesh_color_args cc{0, nullptr};
+    { const int rc = tsdf_mesh(c, who, m, A.coloured, &cc, &D); if (rc) return rc; }
+    HostTimer ht(c, "tsdf_archive");
+    { const int rc = tsdf_archive_append(c, A, v, D); if (rc) return rc; }
+    if (out) tsdf_archive_fill_stats(A, out);
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_get(nalo_ctx* c, nalo_tsdf_archive_get_args* a) {
+    const char* who = "nalo_tsdf_archive_get";
+    { const int rc = tsdf_archive_need(c, who); if (rc) return rc; }
+    if (!a) return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_get: bad argument");
+    TsdfArchive& A = *c->tsdf_archive;
+    a->n_vertices = A.nv; a->n_triangles = A.nt;
+    if (a->cap_vertices < 0 || a->cap_triangles < 0 || a->cap_rgba < 0 || a->cap_key < 0 || (a->cap_vertices > 0 && !a->xyz) || (a->cap_triangles > 0 && !a->tri) ||
+        (a->cap_rgba > 0 && !a->rgba) || (a->cap_key > 0 && !a->key))
+        return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_get: bad argument");
+    if (a->rgba && !A.coloured) return fail(c, NALO_ERR_STATE, "nalo_tsdf_archive_get: the archive holds no colour");
+    if ((a->xyz && a->cap_vertices < A.nv) || (a->tri && a->cap_triangles < A.nt) || (a->rgba && a->cap_rgba < A.nv) || (a->key && a->cap_key < A.nv))
+        return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_get: a cap is below what the archive holds (n_vertices, n_triangles)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    bool any = false;
+    if (a->xyz && A.nv > 0) { NALO_HIP(c, hipMemcpyAsync(a->xyz, A.xyz.p, 3 * (size_t)A.nv * 4, hipMemcpyDeviceToHost, c->stream)); any = true; }
+    if (a->tri && A.nt > 0) { NALO_HIP(c, hipMemcpyAsync(a->tri, A.tri.p, 3 * (size_t)A.nt * 4, hipMemcpyDeviceToHost, c->stream)); any = true; }
+    if (a->rgba && A.nv > 0) { NALO_HIP(c, hipMemcpyAsync(a->rgba, A.rgba.p, (size_t)A.nv * 4, hipMemcpyDeviceToHost, c->stream)); any = true; }
+    if (a->key && A.nv > 0) { NALO_HIP(c, hipMemcpyAsync(a->key, A.key.p, (size_t)A.nv * sizeof(int4), hipMemcpyDeviceToHost, c->stream)); any = true; }
+    if (any) NALO_HIP(c, hipStreamSynchronize(c->stream));
+    return NALO_OK;
+}
+
+int nalo_tsdf_archive_view(nalo_ctx* c, nalo_tsdf_archive_dev* out) {
+    { const int rc = tsdf_archive_need(c, "nalo_tsdf_archive_view"); if (rc) return rc; }
+    if (!out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_archive_view: bad argument");
+    const TsdfArchive& A = *c->tsdf_archive;
+    out->xyz = A.xyz.p; out->tri = A.tri.p; out->rgba = A.coloured ? reinterpret_cast<uint8_t*>(A.rgba.p) : nullptr; out->key = reinterpret_cast<int*>(A.key.p);
+    out->n_vertices = A.nv; out->n_triangles = A.nt;
+    out->stream = (void*)(hipStream_t)c->stream;
+    return NALO_OK;
+}
+
+int nalo_tsdf_follow(nalo_ctx* c, const double centre[3], const int margin[3], float min_weight, int shift_out[3], nalo_tsdf_follow_stats* stats) {
+    const char* who = "nalo_tsdf_follow";
+    if (stats) *stats = nalo_tsdf_follow_stats{};
+    { const int rc = tsdf_archive_need(c, who); if (rc) return rc; }
+    struct nalo_tsdf_geometry g;
+    { const int rc = nalo_tsdf_geometry(c, &g); if (rc) return rc; }
+    int shift[3];
+    if (nalo_tsdf_shift_for(&g.desc, centre, margin, shift) != NALO_OK) return fail(c, NALO_ERR_ARG, "nalo_tsdf_follow: nalo_tsdf_shift_for refused centre or margin");
+    if (shift_out) std::copy(shift, shift + 3, shift_out);
+    if (shift[0] || shift[1] || shift[2]) {
+        struct nalo_tsdf_shift_boxes B;
+        if (nalo_tsdf_shift_boxes(g.desc.dims, shift, &B) != NALO_OK) return fail(c, NALO_ERR_ARG, "nalo_tsdf_follow: nalo_tsdf_shift_boxes refused the shift");
+        for (int b = 0; b < B.n_boxes; ++b) {
+            nalo_tsdf_mesh_args m{};
+            m.use_box = 1; m.min_weight = min_weight;
+            for (int k = 0; k < 3; ++k) { m.lo[k] = B.lo[b][k]; m.size[k] = B.size[b][k]; }
+            struct nalo_tsdf_archive_stats st;
+            { const int rc = nalo_tsdf_archive_mesh(c, &m, &st); if (rc) return rc; }
+            if (stats) {
+                stats->n_boxes = b + 1;
+                stats->added_vertices += st.added_vertices; stats->welded_vertices += st.welded_vertices; stats->added_triangles += st.added_triangles;
+            }
+        }
+    }
+    { const int rc = nalo_tsdf_shift(c, shift); if (rc) return rc; }
+    if (stats) { stats->n_vertices = c->tsdf_archive->nv; stats->n_triangles = c->tsdf_archive->nt; }
     return NALO_OK;
 }

@@ -106,6 +106,7 @@ struct Initializer;
 struct MapArchive;
 struct DenseArchive;
 struct TsdfVolume;
+struct TsdfArchive;
 
 }  // namespace nalo
 
@@ -186,6 +187,7 @@ struct nalo_ctx {
     nalo::MapArchive* map = nullptr;         // the archive of removed points and the clouds made from it (host_map.hip); NULL until nalo_map_enable
     nalo::DenseArchive* dmap = nullptr;      // the dense map: FrameHessian::mapPoints on the device (host_map.hip); NULL until nalo_map_dense_enable
     nalo::TsdfVolume* tsdf = nullptr;        // the TSDF volume and its scratch (host_tsdf.hip); NULL until nalo_tsdf_create
+    nalo::TsdfArchive* tsdf_archive = nullptr;   // the welded mesh archive (nalo_tsdf_archive_*, host_tsdf.hip); NULL until nalo_tsdf_archive_enable. It outlives volumes
     // the keyframe graph (nalo_map_graph_*, host_map.hip): EnergyFunctional::connectivityMap's keys, (host frame_id << 32) + target frame_id, with the count [1] of
     // marginalised residuals; the count [0] of live residuals is taken from the resident slots when the graph is read
     bool graph_on = false;
@@ -510,6 +512,26 @@ struct TsdfRaycastDev {
 };
 int tsdf_raycast_launch(nalo_ctx* c, const TsdfRaycastDev& D);
 void tsdf_destroy(nalo_ctx* c);
+// nalo_tsdf_archive_* (kernels_tsdf_archive.hip): the welded mesh archive. Integers and words only: nothing here depends on the contraction policy. A vertex's key is
+// (gx, gy, gz, m) as one int4; the table is open-addressed with linear probing, 32-bit slots that hold an archived vertex index or kTsdfArchiveEmpty, a power of
+// two of them, and the host keeps its load at or below one half BEFORE a launch (every piece vertex counted as new). Every probe loop is bounded by the slot count;
+// a lane that exhausts it raises *err and stops.
+constexpr int kTsdfArchiveEmpty = -1;
+struct TsdfArchiveDev {
+    // the piece: the device mesh behind nalo_tsdf_mesh and the scratch its passes left (vmask, vbase), the sub-box and the volume's base at the time of the call
+    const unsigned char* vmask; const int* vbase; int lo[3], size[3], base[3], total;
+    const float* p_xyz; const unsigned* p_rgba; const int* p_tri; int p_nv, p_nt;   // p_rgba NULL: an uncoloured archive
+    int4* p_key; int* p_map;                                                    // [p_nv] each: the piece's keys; the archived index of every piece vertex (-1 behind the lookup: new)
+    int* cnt; int nb;                                                           // [nb + 1]: new vertices per workgroup of 256 piece vertices, scanned; [nb] their sum
+    // the archive
+    float* xyz; unsigned* rgba; int4* key; int* tri; int nv, nt;                // nv, nt: what it holds before this append; the buffers have room for nv + p_nv and nt + p_nt
+    int* table; unsigned mask;                                                  // slots - 1
+    int* err;                                                                   // raised to 1 by a lane whose probe ran through every slot
+};
+int tsdf_archive_keys_launch(nalo_ctx* c, const TsdfArchiveDev& D);             // the piece's keys from vmask / vbase
+int tsdf_archive_append_launch(nalo_ctx* c, const TsdfArchiveDev& D);           // lookup, scan, insert, triangles
+int tsdf_archive_rebuild_launch(nalo_ctx* c, const int4* key, int nv, int* table, unsigned mask, int* err);   // an all-empty table filled from the key array in one pass
+void tsdf_archive_destroy(nalo_ctx* c);
 // host_ba.hip: frame_id (nalo_frame_state) of window frame host_frame, which ba_plane_inputs has validated
 int ba_frame_id(nalo_ctx* c, int host_frame);
 // host_ba.hip
