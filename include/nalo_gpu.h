@@ -1445,6 +1445,77 @@ int nalo_map_render(nalo_ctx* ctx, nalo_map_render_args* args);
 int nalo_view_look_at(const double eye[3], const double target[3], const double up[3], double viewFromWorld[12]);   /* host only */
 
 /* ------------------------------------------------------------------------------------------------
+ * The mesh in the 3-D panel. nalo_map_render_mesh(ctx, r, m) is DEFINED as nalo_map_render(ctx, r) with a third kind of candidate in the same depth test: the
+ * triangles of up to three meshes that lie in device memory - the welded archive (nalo_tsdf_archive_view's arrays), the device mesh the last mesh call left
+ * (nalo_tsdf_mesh_view, nalo_tsdf_mesh_color_view) and a caller's. Every candidate - point, line sample, triangle pixel - is entered into the key plane before
+ * the resolve pass; the key plane, the resolve pass and the ONE host wait are nalo_map_render's. A DEFINED rasteriser: the same bytes on every run, equal bit for
+ * bit to the literal model tests/render_mesh_model.py. nalo_map_render itself, its struct and its bytes are unchanged, and with no source selected the outputs of
+ * nalo_map_render_mesh equal nalo_map_render's bit for bit. No side effect on volume, archive, device mesh, window or any other state of the context.
+ *
+ *   Sources     visited in the order archive, live mesh, user. The order is not observable except through the counts, which are sums. Mesh positions are world
+ *               coordinates: vertex (x, y, z) goes through V_f = (float)viewFromWorld with the rounded `apply` of "Transforms" above, as the world-space lines do,
+ *               to its view-space (xv, yv, zv).
+ *   Classes     per triangle (i0, i1, i2) of a source with nv vertices the class is the FIRST rule that fires:
+ *               1 bad index   some index is < 0 or >= nv (the user source only: the library's own meshes hold none).
+ *               2 near        some view-space coordinate is not finite, or some zv fails zv > znear. A DELIBERATE difference from GL and from the lines above:
+ *                             there is NO near-plane clipping; a triangle that reaches the near plane is not drawn. Mesh triangles are at most a voxel across.
+ *               3 guard       per vertex u = fx * (xv / zv) + cx and v = fy * (yv / zv) + cy in float, as for points; the rule fires unless
+ *                             -131072 < u && u < 131072 and the same for v (a NaN falls out through the comparisons). Then the vertex is snapped to 8 sub-pixel
+ *                             bits, every operation rounded in float:  X = (int)floorf(u * 256.0f + 0.5f),  Y = (int)floorf(v * 256.0f + 0.5f).
+ *               4 degenerate  A = (X1 - X0) * (Y2 - Y0) - (Y1 - Y0) * (X2 - X0) in 64-bit integers; A == 0 fires. If A < 0, vertices 1 and 2 are exchanged with
+ *                             everything they carry (z, colour), so that A > 0 from here on.
+ *               5 large       the box of the pixels (ix, iy) whose centres (256 ix + 128, 256 iy + 128) lie inside [minX, maxX] x [minY, maxY] is clipped to the
+ *                             viewport; a box of more than max_box_pixels pixels (0 = 65536) fires. A call's work is bounded by n_triangles * max_box_pixels
+ *                             whatever a caller submits.
+ *               0 drawn       otherwise. An empty box draws nothing.
+ *   Coverage    for the edges 0->1, 1->2, 2->0 (after the exchange) from A to B, with d = B - A and E(P) = dx * (Py - Ay) - dy * (Px - Ax) in 64-bit integers at
+ *               the pixel centre P: the pixel is covered iff every edge has E > 0, or E == 0 and the edge is top-left, dy < 0 || (dy == 0 && dx > 0). A mesh
+ *               whose edges run through pixel centres covers every pixel exactly once; two triangles that share an edge never both take a pixel. The weights
+ *               are w0 = E12(P), w1 = E20(P), w2 = E01(P); they sum to A. With the guard and vw, vh <= 65536 every product stays below 2^52, so the conversions
+ *               to double below are exact.
+ *   Depth       in double, z_i the float zv of vertex i: t_i = (double)w_i / (double)z_i, q = (t0 + t1) + t2, depth = (float)((double)A / q). The pixel gets a
+ *               candidate iff depth > znear && depth < zfar; n_tri_pixels counts these.
+ *   Colour      colour_mode 0, per channel with c_i the vertex's byte: val = (((t0 * c0) + (t1 * c1)) + (t2 * c2)) / q, byte = min(255, (int)floor(val + 0.5)).
+ *               Alpha is ignored. colour_mode 1, once per triangle, in double from the float view-space vertices in SUBMITTED order: e1 = P1 - P0, e2 = P2 - P0,
+ *               n = e1 x e2 (nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz = e1x e2y - e1y e2x: two rounded products and a rounded difference each),
+ *               len = sqrt((nx nx + ny ny) + nz nz), s = len > 0 ? fabs(nz) / len : 0, g = (int)floor(64.0 + 191.0 * s), colour (g, g, g): a triangle seen
+ *               edge-on is 64, one that faces the viewer 255.
+ *   Key         (depth bits << 32) | R << 16 | G << 8 | B, one 64-bit integer minimum, as for points and lines: among equal depths the smaller colour word
+ *               wins, whatever kind of candidate it belongs to.
+ *   Arithmetic  the double divisions and the square root are the correctly rounded ones, no operation is contracted.
+ *   Counts      n_triangles: the triangles of the selected sources; n_tri_bad_index .. n_tri_large: those of classes 1-5; n_tri_pixels above.
+ *   Stream      a user source's arrays are read behind everything queued on its producer_stream at the time of the call (an event, on the device, as
+ *               nalo_tsdf_integrate_depth); the call ends with its host wait, so the arrays are the caller's again when it returns.
+ *   Refusals    nothing is queued; rgb, depth, the context, the device mesh and the archive stay as they were; all eleven counts are zeroed. Every refusal of
+ *               nalo_map_render applies, with one exception: a window is required only when n_frames > 0, show_kf_cams or show_current_cam is set - a context
+ *               that has only a volume can draw its mesh (and the world-space strips). NALO_ERR_ARG: NULL m; vw or vh > 65536; colour_mode outside 0..1;
+ *               negative max_box_pixels; a user source with a negative count, a count > 2^31 - 1, or a NULL xyz / tri with a positive count. NALO_ERR_STATE:
+ *               with_archive without an enabled archive; with_live_mesh before any mesh call; colour_mode 0 with a selected source that has no colours - an
+ *               uncoloured archive, a live mesh left by the plain nalo_tsdf_mesh, a user rgba that is NULL with n_vertices > 0.
+ *   Cost        one more kernel on the context's stream (all sources in one launch), between the lines and the resolve pass; still ONE wait.
+ * nalo_view_triangle (host only, no context): rules 2-5 for one triangle given by its view-space vertices, through the function the kernel calls. Of cam it
+ *   reads vw, vh, fx, fy, cx, cy, znear. cls: 0 drawn, or 2..5. X, Y: the snapped coordinates after the exchange (0 where rule 2 or 3 fired). box: the clipped
+ *   box x0, x1, y0, y1, inclusive; (0, -1, 0, -1), so x1 < x0, when it is empty or rules 2-4 fired. NALO_ERR_ARG (nothing written): a NULL argument, vw or vh
+ *   outside 1..65536, a negative max_box_pixels.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nalo_render_mesh_src {            /* a caller's mesh in device memory */
+    const float* xyz; const int* tri; const uint8_t* rgba;   /* [nv][3], [nt][3], [nv][4] or NULL */
+    long long n_vertices, n_triangles;
+    void* producer_stream;                       /* as nalo_tsdf_integrate_args; NULL = the null stream */
+} nalo_render_mesh_src;
+typedef struct nalo_map_render_mesh_args {
+    int with_archive;                            /* the triangles of nalo_tsdf_archive_view */
+    int with_live_mesh;                          /* the device mesh the last mesh call left (nalo_tsdf_mesh_view) */
+    const nalo_render_mesh_src* user;            /* optional third source */
+    int colour_mode;                             /* 0 vertex colours, 1 shaded grey */
+    long long max_box_pixels;                    /* 0 = 65536 */
+    long long n_triangles, n_tri_bad_index, n_tri_near, n_tri_guard, n_tri_degenerate, n_tri_large, n_tri_pixels;  /* out */
+} nalo_map_render_mesh_args;
+int nalo_map_render_mesh(nalo_ctx* ctx, nalo_map_render_args* r, nalo_map_render_mesh_args* m);
+int nalo_view_triangle(const nalo_map_render_args* cam, const float view_xyz[3][3], long long max_box_pixels,
+                       int* cls, int X[3], int Y[3], int box[4]);   /* host only, no context */
+
+/* ------------------------------------------------------------------------------------------------
  * densemap=1: DenseMapping::updateMap (FullSystem/MapPoint.cpp:234-332, call site FullSystem.cpp:1488-1496) in one call, and FrameHessian::mapPoints as a
  * device archive beside the sparse one. The per-cluster route (nalo_dense_fit_planes, then nalo_dense_make_map per cluster) stays as it is.
  *
@@ -1863,7 +1934,7 @@ int nalo_tsdf_follow(nalo_ctx* ctx, const double centre[3], const int margin[3],
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh). Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -38,7 +38,7 @@ EXPORTS = [
     "nalo_ba_carry_window", "nalo_ba_carry_map", "nalo_ba_carry_last",
     "nalo_ba_window_from_initializer", "nalo_ba_init_window_map", "nalo_ba_init_window_last",
     "nalo_map_enable", "nalo_map_reset", "nalo_map_counts", "nalo_map_get_frame", "nalo_map_world_points", "nalo_map_world_points_host", "nalo_map_frame_cloud",
-    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at",
+    "nalo_map_graph_enable", "nalo_map_graph", "nalo_map_graph_connections", "nalo_map_window_plot", "nalo_map_render", "nalo_view_look_at", "nalo_map_render_mesh", "nalo_view_triangle",
     "nalo_dense_update_map", "nalo_map_dense_enable", "nalo_map_dense_counts", "nalo_map_dense_get", "nalo_map_dense_world_points", "nalo_map_dense_cloud",
     "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
     "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
@@ -291,6 +291,20 @@ class MapRenderArgs(C.Structure):
                 ("n_line_samples", C.c_longlong)]
 
 
+class RenderMeshSrc(C.Structure):
+    """nalo_render_mesh_src (include/nalo_gpu.h)"""
+    _fields_ = [("xyz", C.c_void_p), ("tri", C.c_void_p), ("rgba", C.c_void_p), ("n_vertices", C.c_longlong), ("n_triangles", C.c_longlong), ("producer_stream", C.c_void_p)]
+
+
+class MapRenderMeshArgs(C.Structure):
+    """nalo_map_render_mesh_args (include/nalo_gpu.h)"""
+    _fields_ = [("with_archive", C.c_int), ("with_live_mesh", C.c_int), ("user", C.POINTER(RenderMeshSrc)), ("colour_mode", C.c_int), ("max_box_pixels", C.c_longlong),
+                ("n_triangles", C.c_longlong), ("n_tri_bad_index", C.c_longlong), ("n_tri_near", C.c_longlong), ("n_tri_guard", C.c_longlong),
+                ("n_tri_degenerate", C.c_longlong), ("n_tri_large", C.c_longlong), ("n_tri_pixels", C.c_longlong)]
+
+
+MESH_COUNTS = ("n_triangles", "n_tri_bad_index", "n_tri_near", "n_tri_guard", "n_tri_degenerate", "n_tri_large", "n_tri_pixels")
+
 TRK_MAX_TRIES = 64                                        # NALO_TRK_MAX_TRIES
 
 
@@ -341,6 +355,7 @@ def host_lib():
         L = C.CDLL(lib_path())
         _ground_argtypes(L)
         L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
+        L.nalo_view_triangle.argtypes = [C.POINTER(MapRenderArgs), c_fp, C.c_longlong, c_ip, c_ip, c_ip, c_ip]
         L.nalo_trk_motion_tries.argtypes = [c_dp, c_dp, C.c_int, c_dp]
         L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
         L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
@@ -373,6 +388,20 @@ def view_look_at(eye, target=(0.0, 0.0, 0.0), up=(0.0, -1.0, 0.0)):
     if host_lib().nalo_view_look_at(e.ctypes.data_as(c_dp), t.ctypes.data_as(c_dp), u.ctypes.data_as(c_dp), out.ctypes.data_as(c_dp)) != 0:
         raise NaloError("nalo_view_look_at: degenerate view (up parallel to the viewing direction, eye == target, or a value that is not finite)")
     return out.reshape(3, 4)
+
+
+def view_triangle(vw, vh, view_xyz, fx=400.0, fy=400.0, cx=None, cy=None, znear=0.1, max_box_pixels=0):
+    """nalo_view_triangle: rules 2-5 of nalo_map_render_mesh for one triangle given by its view-space vertices [3][3], through the function the kernel calls ->
+    dict(cls 0 drawn or 2..5, X [3], Y [3] snapped coordinates after the exchange, box (x0, x1, y0, y1), x1 < x0 when empty); needs no device"""
+    a = MapRenderArgs()
+    a.vw, a.vh, a.fx, a.fy, a.znear = int(vw), int(vh), float(fx), float(fy), float(znear)
+    a.cx, a.cy = float(vw / 2 if cx is None else cx), float(vh / 2 if cy is None else cy)
+    P = np.ascontiguousarray(view_xyz, np.float32).reshape(9)
+    cls, X, Y, box = np.zeros(1, np.int32), np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(4, np.int32)
+    rc = host_lib().nalo_view_triangle(C.byref(a), _f(P), int(max_box_pixels), _i(cls), _i(X), _i(Y), _i(box))
+    if rc != 0:
+        raise NaloError("nalo_view_triangle: bad argument (%d)" % rc)
+    return dict(cls=int(cls[0]), X=X.tolist(), Y=Y.tolist(), box=tuple(box.tolist()))
 
 
 def tsdf_desc(origin, voxel_size, dims, trunc, max_weight):
@@ -607,6 +636,7 @@ def load():
     L.nalo_map_world_points_host.argtypes = [C.c_int, c_fp, c_fp, c_fp, c_fp, c_dp, c_dp]
     L.nalo_map_frame_cloud.argtypes = [vp, C.POINTER(MapCloudArgs)]
     L.nalo_map_render.argtypes = [vp, C.POINTER(MapRenderArgs)]
+    L.nalo_map_render_mesh.argtypes = [vp, C.POINTER(MapRenderArgs), C.POINTER(MapRenderMeshArgs)]
     L.nalo_view_look_at.argtypes = [c_dp, c_dp, c_dp, c_dp]
     L.nalo_map_graph_enable.argtypes = [vp, C.c_int]
     L.nalo_map_graph.argtypes = [vp, vp, C.c_int, c_ip]
@@ -1563,6 +1593,58 @@ class Context:
         del keep
         return dict(rgb=rgb, depth=depth, n_vertices=int(a.n_vertices), n_drawn_points=int(a.n_drawn_points), n_segments=int(a.n_segments),
                     n_line_samples=int(a.n_line_samples))
+
+    @staticmethod
+    def render_mesh_src(mesh, stream=None):
+        """a filled RenderMeshSrc from mesh = (xyz [nv][3] float32, tri [nt][3] int32, rgba [nv][4] uint8 or None), each anything with __cuda_array_interface__
+        (dense, C-contiguous), read where it lies; stream: the hipStream_t (an int) whose queued work produces the arrays, None / 0 = the null stream. Returns
+        (src, what it points into): keep the second alive"""
+        xyz, tri, rgba = mesh
+        src = RenderMeshSrc()
+
+        def dense(obj, what, typestrs, cols):
+            cai = getattr(obj, "__cuda_array_interface__", None)
+            if cai is None:
+                raise TypeError("map_render_mesh: %s: %s has no __cuda_array_interface__ (device arrays only: nothing is copied to the device here)" % (what, type(obj).__name__))
+            shape = tuple(int(v) for v in cai["shape"])
+            if cai["typestr"] not in typestrs or len(shape) != 2 or shape[1] != cols:
+                raise NaloError("map_render_mesh: %s: typestr %r shape %r, expected %s [n][%d]" % (what, cai["typestr"], shape, typestrs[0], cols))
+            item = int(typestrs[0][2])
+            st = cai.get("strides")
+            if st is not None and shape[0] > 0 and ((shape[0] > 1 and int(st[0]) != cols * item) or int(st[1]) != item):
+                raise NaloError("map_render_mesh: %s: strides %r are not dense (make it contiguous on the producer's side)" % (what, tuple(st)))
+            return (int(cai["data"][0]) or None) if shape[0] > 0 else None, shape[0]
+
+        src.xyz, src.n_vertices = dense(xyz, "xyz", ("<f4",), 3)
+        src.tri, src.n_triangles = dense(tri, "tri", ("<i4",), 3)
+        if rgba is not None:
+            src.rgba, n = dense(rgba, "rgba", ("|u1", "<u1"), 4)
+            if n != src.n_vertices:
+                raise NaloError("map_render_mesh: rgba has %d rows, xyz %d" % (n, src.n_vertices))
+        src.producer_stream = int(stream) if stream else None
+        return src, (xyz, tri, rgba)
+
+    def map_render_mesh(self, vw, vh, view, frames=(), archive=False, live=False, mesh=None, colour_mode=0, max_box_pixels=0, mesh_stream=None, want_depth=True, **kw):
+        """nalo_map_render_mesh: map_render with the triangles of the TSDF meshes in the same depth test (keywords: map_render_args) -> map_render's dict plus
+        n_triangles, n_tri_bad_index, n_tri_near, n_tri_guard, n_tri_degenerate, n_tri_large, n_tri_pixels. archive: the welded archive (tsdf_archive_view's
+        arrays); live: the device mesh the last tsdf_mesh left; mesh: a caller's (xyz, tri, rgba-or-None) device arrays in WORLD coordinates, produced by the
+        work queued on mesh_stream (a hipStream_t as an int; None = the null stream). colour_mode 0: vertex colours, 1: shaded grey. One call, one wait"""
+        a, keep = self.map_render_args(vw, vh, view, frames, **kw)
+        rgb = np.zeros((int(vh), int(vw), 3), np.uint8)
+        depth = np.zeros((int(vh), int(vw)), np.float32) if want_depth else None
+        a.rgb, a.depth = _u8(rgb), _f(depth)
+        m = MapRenderMeshArgs()
+        m.with_archive, m.with_live_mesh, m.colour_mode, m.max_box_pixels = int(bool(archive)), int(bool(live)), int(colour_mode), int(max_box_pixels)
+        src = None
+        if mesh is not None:
+            src, keep_mesh = self.render_mesh_src(mesh, mesh_stream)
+            m.user = C.pointer(src)
+        self._ck(self.L.nalo_map_render_mesh(self.h_, C.byref(a), C.byref(m)))
+        del keep, src
+        out = dict(rgb=rgb, depth=depth, n_vertices=int(a.n_vertices), n_drawn_points=int(a.n_drawn_points), n_segments=int(a.n_segments),
+                   n_line_samples=int(a.n_line_samples))
+        out.update({k: int(getattr(m, k)) for k in MESH_COUNTS})
+        return out
 
     # ---- the keyframe graph: EnergyFunctional::connectivityMap from the device chain
     def map_graph_enable(self, on=True):

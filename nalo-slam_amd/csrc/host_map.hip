@@ -508,10 +508,23 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
 // The 3-D panel of PangolinDSOViewer (kernels_map_render.hip; the definition: include/nalo_gpu.h). Every check stands before the first enqueue; kernels on the main
 // stream; counters and images come up through one pinned block behind ONE wait (the graph's count, when a constraint flag is set, is nalo_map_graph's own) and
 // reach the caller only when the call succeeds.
-int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
-    const char* const who = "nalo_map_render: ";
+//
+// nalo_map_render_mesh is the same call with the triangles of up to three meshes entered into the key plane between the lines and the resolve pass (mesh != NULL;
+// kernels_map_render_mesh.hip). Its own refusals stand with the others, before the first enqueue; a window is needed only for what reads one.
+static int map_render_impl(nalo_ctx* c, nalo_map_render_args* a, nalo_map_render_mesh_args* mesh, const char* who) {
+    if (mesh) mesh->n_triangles = mesh->n_tri_bad_index = mesh->n_tri_near = mesh->n_tri_guard = mesh->n_tri_degenerate = mesh->n_tri_large = mesh->n_tri_pixels = 0;
+    if (a && mesh) a->n_vertices = a->n_drawn_points = a->n_segments = a->n_line_samples = 0;     // every refusal of the mesh call zeroes all eleven counts
     if (!c || !a || !a->rgb) return fail(c, NALO_ERR_ARG, std::string(who) + "bad argument");
     a->n_vertices = a->n_drawn_points = a->n_segments = a->n_line_samples = 0;
+    if (mesh) {
+        if (a->vw > kMrMaxView || a->vh > kMrMaxView) return fail(c, NALO_ERR_ARG, std::string(who) + "vw and vh must be at most 65536");
+        if (mesh->colour_mode < 0 || mesh->colour_mode > 1) return fail(c, NALO_ERR_ARG, std::string(who) + "colour_mode must be 0 or 1");
+        if (mesh->max_box_pixels < 0) return fail(c, NALO_ERR_ARG, std::string(who) + "max_box_pixels is negative");
+        if (const nalo_render_mesh_src* u = mesh->user) {
+            if (u->n_vertices < 0 || u->n_triangles < 0 || u->n_vertices > INT32_MAX || u->n_triangles > INT32_MAX) return fail(c, NALO_ERR_ARG, std::string(who) + "a count of the user mesh is negative or above 2^31 - 1");
+            if ((u->n_vertices > 0 && !u->xyz) || (u->n_triangles > 0 && !u->tri)) return fail(c, NALO_ERR_ARG, std::string(who) + "an array of the user mesh is NULL with a positive count");
+        }
+    }
     if (a->vw < 1 || a->vh < 1 || (long long)a->vw * a->vh > (1ll << 26)) return fail(c, NALO_ERR_ARG, std::string(who) + "vw, vh must be at least 1 and vw * vh at most 2^26");
     for (float f : {a->fx, a->fy, a->cx, a->cy, a->znear, a->zfar}) if (!std::isfinite(f)) return fail(c, NALO_ERR_ARG, std::string(who) + "the camera values must be finite");
     for (double d : a->viewFromWorld) if (!std::isfinite(d)) return fail(c, NALO_ERR_ARG, std::string(who) + "viewFromWorld must be finite");
@@ -526,7 +539,11 @@ int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
     const bool constraints = a->show_active_constraints || a->show_all_constraints;
     if (constraints && !c->graph_on) return fail(c, NALO_ERR_STATE, std::string(who) + "a constraint flag is set and the graph is off (nalo_map_graph_enable)");
     MapWindowView V0;
-    { const int rc = ba_map_view(c, -1, &V0); if (rc) return rc; }
+    if (!mesh || a->n_frames > 0 || a->show_kf_cams || a->show_current_cam) { const int rc = ba_map_view(c, -1, &V0); if (rc) return rc; }
+    else {                                                                      // a mesh call that reads no window: a context with only a volume can draw its mesh
+        const std::string err = c->err;
+        if (ba_map_view(c, -1, &V0) != NALO_OK) { V0 = MapWindowView{}; c->err = err; }
+    }
     if (V0.sharded) return fail(c, NALO_ERR_STATE, std::string(who) + "the window is sharded (a rank holds only its own points)");
     NALO_HIP(c, hipSetDevice(c->device));
     // the record list of all listed frames: per frame what nalo_map_frame_cloud lists, then its dense pieces
@@ -553,6 +570,37 @@ int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
         if (f) { map_push_runs(*arch, f, 2, segs, total, i); map_push_runs(*arch, f, 3, segs, total, i); }
         if (dense && df) map_push_runs(*dense, df, 4, segs, total, i);
         if (total > INT32_MAX) return fail(c, NALO_ERR_UNSUPPORTED, std::string(who) + "more records than a 32-bit index can hold");
+    }
+    // the mesh sources in the order archive, live mesh, user: the views are host code and launch nothing
+    MrTrisDev T{};
+    hipStream_t user_stream = nullptr; bool user_wait = false;
+    long long n_triangles = 0;                                                   // reaches the caller with the other counts, behind the wait
+    if (mesh) {
+        auto add_src = [&](const float* xyz, const int* tri, const uint8_t* rgba, long long nv, long long nt) {
+            n_triangles += nt;
+            if (nt > 0) T.src[T.n_src++] = MrTriSrc{xyz, tri, mesh->colour_mode == 0 ? rgba : nullptr, (int)nv, (int)nt};
+        };
+        const std::string no_colour = "colour_mode 0 and a selected source has no colours: ";
+        if (mesh->with_archive) {
+            nalo_tsdf_archive_dev v;
+            if (nalo_tsdf_archive_view(c, &v) != NALO_OK) return fail(c, NALO_ERR_STATE, std::string(who) + "with_archive and the mesh archive is not enabled (nalo_tsdf_archive_enable)");
+            if (mesh->colour_mode == 0 && !v.rgba) return fail(c, NALO_ERR_STATE, std::string(who) + no_colour + "the archive is uncoloured");
+            add_src(v.xyz, v.tri, v.rgba, v.n_vertices, v.n_triangles);
+        }
+        if (mesh->with_live_mesh) {
+            nalo_tsdf_mesh_dev v; nalo_tsdf_mesh_color_dev vc{};
+            if (!c->tsdf || nalo_tsdf_mesh_view(c, &v) != NALO_OK) return fail(c, NALO_ERR_STATE, std::string(who) + "with_live_mesh before any mesh call (nalo_tsdf_mesh, nalo_tsdf_mesh_color)");
+            if (mesh->colour_mode == 0 && nalo_tsdf_mesh_color_view(c, &vc) != NALO_OK) return fail(c, NALO_ERR_STATE, std::string(who) + no_colour + "the live mesh was left by the plain nalo_tsdf_mesh");
+            add_src(v.xyz, v.tri, vc.rgba, v.n_vertices, v.n_triangles);
+        }
+        if (const nalo_render_mesh_src* u = mesh->user) {
+            if (mesh->colour_mode == 0 && !u->rgba && u->n_vertices > 0) return fail(c, NALO_ERR_STATE, std::string(who) + no_colour + "the user mesh's rgba is NULL");
+            add_src(u->xyz, u->tri, u->rgba, u->n_vertices, u->n_triangles);
+            user_stream = (hipStream_t)u->producer_stream; user_wait = u->n_triangles > 0 && user_stream != (hipStream_t)c->stream;
+        }
+        for (int s = 0; s < T.n_src; ++s) T.blk0[s + 1] = T.blk0[s] + (unsigned)(((long long)T.src[s].nt + 255) / 256);
+        for (int i = 0; i < 12; ++i) T.V[i] = (float)a->viewFromWorld[i];
+        T.colour_mode = mesh->colour_mode; T.max_box = mesh->max_box_pixels == 0 ? kMrDefaultBox : mesh->max_box_pixels;
     }
     std::vector<nalo_graph_connection> conn;
     if (constraints) { const int rc = graph_connections(c, "nalo_map_render", conn); if (rc) return rc; }
@@ -603,11 +651,11 @@ int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
     { const int rc = map_send_segs(c, m, segs, (int)total, D.S); if (rc) return rc; }
     D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n; std::memcpy(D.S.imm_frame, imm_frame, sizeof(imm_frame));
     if (have_window) { D.S.flags = VW.flags; D.S.geo = VW.geo; D.S.col0 = VW.col0; D.S.col1 = VW.col1; D.S.acc = VW.acc; D.S.prior = VW.prior; D.S.relbs = VW.relbs; }
-    const size_t npx = (size_t)a->vw * a->vh, padded = map_render_padded_pixels(npx), off_rgb = 64, off_depth = (off_rgb + 3 * npx + 15) / 16 * 16;
+    const size_t npx = (size_t)a->vw * a->vh, padded = map_render_padded_pixels(npx), off_rgb = 128, off_depth = (off_rgb + 3 * npx + 15) / 16 * 16;
     NALO_HIP(c, m.mr_M_h.reserve(M.size())); NALO_HIP(c, m.mr_M_d.reserve(M.size()));
     NALO_HIP(c, m.mr_lines_h.reserve(std::max<size_t>(lines.size(), 1))); NALO_HIP(c, m.mr_lines_d.reserve(std::max<size_t>(lines.size(), 1)));
     NALO_HIP(c, m.mr_rgb.reserve(3 * padded)); NALO_HIP(c, m.mr_depth.reserve(padded)); NALO_HIP(c, m.mr_host.reserve(off_depth + 4 * npx));
-    if (!m.mr_cnt.p) { NALO_HIP(c, m.mr_cnt.reserve(8)); NALO_HIP(c, hipMemsetAsync(m.mr_cnt.p, 0, 8 * 8, c->stream)); m.mr_cnt_buf = 0; }
+    if (!m.mr_cnt.p) { NALO_HIP(c, m.mr_cnt.reserve(2 * kMrCounters)); NALO_HIP(c, hipMemsetAsync(m.mr_cnt.p, 0, 2 * kMrCounters * 8, c->stream)); m.mr_cnt_buf = 0; }
     if (padded > m.mr_key.cap) m.mr_key_clean = false;
     NALO_HIP(c, m.mr_key.reserve(padded));
     if (!m.mr_key_clean) NALO_HIP(c, hipMemsetAsync(m.mr_key.p, 0xFF, m.mr_key.cap * 8, c->stream));   // a new plane, or a call that failed between its passes
@@ -618,20 +666,38 @@ int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) {
     if (!lines.empty()) NALO_HIP(c, hipMemcpyAsync(m.mr_lines_d.p, m.mr_lines_h.p, lines.size() * sizeof(MrLine), hipMemcpyHostToDevice, c->stream));
     D.M = m.mr_M_d.p; D.mode = a->display_mode; D.scaledTH = a->scaledTH; D.absTH = a->absTH; D.minRelBS = a->minRelBS; std::memcpy(D.ci, V0.ci, sizeof(D.ci)); D.cam = cam;
     D.lines = m.mr_lines_d.p; D.n_lines = (int)lines.size(); D.key = m.mr_key.p; D.padded = padded;
-    D.cnt = m.mr_cnt.p + 4 * m.mr_cnt_buf; m.mr_cnt_buf ^= 1; D.cnt_next = m.mr_cnt.p + 4 * m.mr_cnt_buf;
+    D.cnt = m.mr_cnt.p + kMrCounters * m.mr_cnt_buf; m.mr_cnt_buf ^= 1; D.cnt_next = m.mr_cnt.p + kMrCounters * m.mr_cnt_buf;
     D.rgb = m.mr_rgb.p; D.depth = m.mr_depth.p; D.background = ((unsigned)a->background[0] << 16) | ((unsigned)a->background[1] << 8) | a->background[2];
-    { const int rc = map_render_launch(c, D); if (rc) return rc; }
+    if (user_wait) {                                                           // the caller's arrays: everything queued on producer_stream so far comes first, on the device
+        NALO_HIP(c, c->ev_prod.create(hipEventDisableTiming));
+        NALO_HIP(c, hipEventRecord(c->ev_prod, user_stream)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0));
+    }
+    { const int rc = map_render_launch(c, D, mesh ? &T : nullptr); if (rc) return rc; }
     m.mr_key_clean = true;
-    NALO_HIP(c, hipMemcpyAsync(m.mr_host.p, D.cnt, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipMemcpyAsync(m.mr_host.p, D.cnt, kMrCounters * 8, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_rgb, m.mr_rgb.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
     if (a->depth) NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_depth, m.mr_depth.p, 4 * npx, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
-    unsigned long long cnt[4];
+    unsigned long long cnt[kMrCounters];
     std::memcpy(cnt, m.mr_host.p, sizeof(cnt));
     a->n_vertices = (long long)cnt[0]; a->n_drawn_points = (long long)cnt[1]; a->n_segments = n_segments; a->n_line_samples = (long long)cnt[2];
+    if (mesh) {
+        mesh->n_triangles = n_triangles; mesh->n_tri_bad_index = (long long)cnt[4]; mesh->n_tri_near = (long long)cnt[5]; mesh->n_tri_guard = (long long)cnt[6];
+        mesh->n_tri_degenerate = (long long)cnt[7]; mesh->n_tri_large = (long long)cnt[8]; mesh->n_tri_pixels = (long long)cnt[9];
+    }
     std::memcpy(a->rgb, m.mr_host.p + off_rgb, 3 * npx);
     if (a->depth) std::memcpy(a->depth, m.mr_host.p + off_depth, 4 * npx);
     return NALO_OK;
+}
+
+int nalo_map_render(nalo_ctx* c, nalo_map_render_args* a) { return map_render_impl(c, a, nullptr, "nalo_map_render: "); }
+
+int nalo_map_render_mesh(nalo_ctx* c, nalo_map_render_args* a, nalo_map_render_mesh_args* mesh) {
+    if (!mesh) {
+        if (a) a->n_vertices = a->n_drawn_points = a->n_segments = a->n_line_samples = 0;
+        return fail(c, NALO_ERR_ARG, "nalo_map_render_mesh: bad argument");
+    }
+    return map_render_impl(c, a, mesh, "nalo_map_render_mesh: ");
 }
 
 int nalo_map_graph_enable(nalo_ctx* c, int on) {

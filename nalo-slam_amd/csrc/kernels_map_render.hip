@@ -7,6 +7,7 @@
 //                      integer atomicMin: a positive float orders like its bits, so the smallest key is the nearest candidate and, among equal depths, the smallest colour.
 //  mr_lines_kernel     one wave per clipped segment (MrLine: the host has dropped, near-clipped, projected and viewport-clipped it in double), lanes striding over
 //                      its samples; the same key update for every pixel of the width block.
+//  (mr_tris_kernel     nalo_map_render_mesh's triangles enter the same plane between the lines and the resolve pass: kernels_map_render_mesh.hip)
 //  mr_resolve_kernel   one lane per four pixels: the winner's colour and depth or the background and +inf; the keys it found lowered go back to all-ones, so the
 //                      plane is filled only when it is allocated or grown. The 12 colour bytes of a lane go through LDS and leave as 16-byte stores.
 //
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void mr_lines_kernel(MapRenderDev D) {
 __global__ __launch_bounds__(256) void mr_resolve_kernel(MapRenderDev D) {
     __shared__ unsigned stage[3 * 256];
     const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && tid < 4) D.cnt_next[tid] = 0ull;                      // the NEXT call's counters (two buffers): no fill on the path
+    if (blockIdx.x == 0 && tid < kMrCounters) D.cnt_next[tid] = 0ull;            // the NEXT call's counters (two buffers): no fill on the path
     const size_t g0 = ((size_t)blockIdx.x * 256 + tid) * 4;                      // < padded: the grid is padded / kMrPix workgroups
     ulonglong2* const kp = reinterpret_cast<ulonglong2*>(D.key + g0);
     const ulonglong2 a = kp[0], b = kp[1];
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void mr_resolve_kernel(MapRenderDev D) {
 
 size_t map_render_padded_pixels(size_t pixels) { return (pixels + kMrPix - 1) / kMrPix * kMrPix; }
 
-int map_render_launch(nalo_ctx* c, const MapRenderDev& D) {
+int map_render_launch(nalo_ctx* c, const MapRenderDev& D, MrTrisDev* T) {
     if (D.S.nb > 0) {
         ProfScope ps(c, "map_render_points");
         mr_points_kernel<<<D.S.nb, 256, 0, c->stream>>>(D);
@@ -164,6 +165,11 @@ int map_render_launch(nalo_ctx* c, const MapRenderDev& D) {
     if (D.n_lines > 0) {
         ProfScope ps(c, "map_render_lines");
         mr_lines_kernel<<<(D.n_lines + 3) / 4, 256, 0, c->stream>>>(D);
+    }
+    if (T && T->n_src > 0) {                                                     // nalo_map_render_mesh: a third kind of candidate in the same key plane
+        T->cam = D.cam; T->key = D.key; T->cnt = D.cnt;
+        const int rc = map_render_tris_launch(c, *T);
+        if (rc) return rc;
     }
     {
         ProfScope ps(c, "map_render_resolve");

@@ -15,6 +15,7 @@
 #include "host_math.h"
 #include "ref_constants.h"
 #include "tsdf_device.h"
+#include "map_render_tri.h"
 
 namespace nalo {
 
@@ -365,13 +366,13 @@ int ba_map_view(nalo_ctx* c, int frame_id, MapWindowView* V);
 // ---- the 3-D panel (nalo_map_render; host_map.hip, kernels_map_render.hip). The host half of kernels_map_render.hip is the call's arithmetic: that file is built
 // without FMA contraction, so the products below are the ones include/nalo_gpu.h defines, operation by operation.
 struct MrLine { double ua, va, ub, vb, za, zb, n, k0; int count, width; unsigned col; int pad; };   // a clipped, projected segment: samples k0 .. k0 + count - 1 of n
-struct MrCam { int vw, vh; float fx, fy, cx, cy, znear, zfar; };
+// MrCam { vw, vh, fx, fy, cx, cy, znear, zfar }: map_render_tri.h, with the triangle set-up that host and device share
 struct MapRenderDev {
     MapSrcDev S; const float* M;                                                // M: [n_frames][12], row MapSeg::frame
     int mode; float scaledTH, absTH, minRelBS, ci[4]; MrCam cam;
     const MrLine* lines; int n_lines;
     unsigned long long* key; size_t padded;                                     // one word per pixel, rounded up to whole resolve workgroups; all-ones between calls
-    unsigned long long *cnt, *cnt_next;                                         // n_vertices, n_drawn_points, n_line_samples, 0; the idle buffer zeroed for the next call
+    unsigned long long *cnt, *cnt_next;                                         // kMrCounters words: n_vertices, n_drawn_points, n_line_samples, 0, then the triangles' six (MrTrisDev); the idle buffer zeroed for the next call
     uint8_t* rgb; float* depth; unsigned background;                            // rgb: 3 bytes per key word; depth: 4
 };
 size_t map_render_padded_pixels(size_t pixels);
@@ -380,7 +381,18 @@ void map_render_apply(const float M[12], const float p[3], float out[3]);       
 // one segment in view space (float endpoints) through the drop rules, the near clip, the projection and the viewport clip; false: dropped (no segment counted)
 bool map_render_line(const MrCam& cam, const float a[3], const float b[3], unsigned col, int width, MrLine* out);
 void map_render_frustum(const float cf[4], int w, int h, float sz, float pts[5][3]);                  // drawCam's apex and four corners (:630-649), camera space
-int map_render_launch(nalo_ctx* c, const MapRenderDev& D);                     // points, lines, resolve on c->stream
+// the triangles of nalo_map_render_mesh (kernels_map_render_mesh.hip): up to three sources behind one another in ONE launch; workgroup b serves source s when
+// blk0[s] <= b < blk0[s + 1]. rgba: 4 bytes per vertex, read bytewise (a caller's array needs no alignment), NULL in colour_mode 1. cnt: the call's counter
+// block; words 4..9 are n_tri_bad_index, n_tri_near, n_tri_guard, n_tri_degenerate, n_tri_large, n_tri_pixels
+constexpr int kMrCounters = 12;
+struct MrTriSrc { const float* xyz; const int* tri; const uint8_t* rgba; int nv, nt; };
+struct MrTrisDev {
+    MrTriSrc src[3]; unsigned blk0[4]; int n_src;
+    float V[12]; MrCam cam; int colour_mode; long long max_box;
+    unsigned long long *key, *cnt;
+};
+int map_render_tris_launch(nalo_ctx* c, const MrTrisDev& T);
+int map_render_launch(nalo_ctx* c, const MapRenderDev& D, MrTrisDev* T = nullptr);   // points, lines, (T: triangles, its cam / key / cnt filled in here,) resolve on c->stream
 // ---- the window panel (nalo_map_window_plot; host_map.hip, kernels_window_plot.hip): FullSystem::debugPlot from resident data
 // host_ba.hip: the whole window as the painter reads it. Per window frame: frame_id, slot, its seg entries of the (host, submission) map and how many are valid
 struct PlotWindowView {
