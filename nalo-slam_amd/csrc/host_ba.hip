@@ -110,9 +110,9 @@ struct BAWindow {
     // nalo_ba_window_from_initializer: [the constructor's verdict per level-0 point | sumID] on the device and in pinned memory, and what the last call reports
     DevBuf<uint8_t> iw_scr; HostBuf<uint8_t> iw_host;
     std::vector<int> iw_map_h; float iw_scale[3] = {}; int iw_stats[4] = {}; bool iw_have = false;   // nalo_ba_init_window_map / nalo_ba_init_window_last
-    // nalo_ba_residual_plot (kernels_residual_plot.hip), sized on first use: the key plane (zero between calls: the resolve pass leaves it so), the colours, the
-    // painted images, the counters and the pinned block counters and images come up through
-    DevBuf<unsigned> rp_key, rp_col; DevBuf<uint8_t> rp_bgr; DevBuf<int> rp_cnt; HostBuf<uint8_t> rp_host; bool rp_key_clean = false;
+    // nalo_ba_residual_plot (kernels_residual_plot.hip), sized on first use: the key plane (a KeyPlane, zero between calls), the colours, the painted images, the
+    // counters and the pinned block counters and images come up through
+    KeyPlane<unsigned, 0> rp_key; DevBuf<unsigned> rp_col; DevBuf<uint8_t> rp_bgr; DevBuf<int> rp_cnt; HostBuf<uint8_t> rp_host;
 };
 
 void ba_destroy(nalo_ctx* c) {
@@ -1003,6 +1003,20 @@ int ba_plot_view(nalo_ctx* c, PlotWindowView* V) {
         ++V->seg[i]; V->n_valid[i] += (w.flags_h[d] & PT_VALID) != 0;
     }
     for (int i = 0; i < w.W; ++i) if (V->seg[i]) V->kmap[i] = w.ref_kmap.p + first[i];
+    return NALO_OK;
+}
+
+int ba_plot_frames(nalo_ctx* c, const char* who, const PlotWindowView& V, unsigned frame_mask, int out_of[NALO_MAX_WINDOW], int frame_of[NALO_MAX_WINDOW],
+                   const float* I[NALO_MAX_WINDOW], int* n_frames) {
+    const unsigned mask = frame_mask ? frame_mask : (1u << V.W) - 1u;
+    *n_frames = 0;
+    for (int i = 0; i < NALO_MAX_WINDOW; ++i) out_of[i] = frame_of[i] = -1;
+    for (int i = 0; i < V.W; ++i) {
+        if (!(mask >> i & 1u)) continue;
+        const int s = V.slot[i];
+        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].I[0].p) return fail(c, NALO_ERR_STATE, std::string(who) + ": a window frame's slot has no pyramid");
+        I[*n_frames] = c->slots[s].I[0].p; frame_of[*n_frames] = i; out_of[i] = (*n_frames)++;
+    }
     return NALO_OK;
 }
 
@@ -1926,34 +1940,26 @@ int nalo_ba_residual_plot(nalo_ctx* c, nalo_residual_plot_args* a) {
     if (a->frame_mask >> V.W) return fail(c, NALO_ERR_ARG, "nalo_ba_residual_plot: frame_mask names a frame outside the window");
     if (V.sharded) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: the window is sharded (a rank holds only its own points)");
     if (!V.pts_ok || !w.dev.pre) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: the window's points are unset: carry or re-issue the window first");
-    const unsigned mask = a->frame_mask ? a->frame_mask : (1u << V.W) - 1u;
     ResidualPlotDev D{};
     residual_plot_bind(w, c, D);
+    int frame_of[NALO_MAX_WINDOW];                                          // while the point arrays stand, frame i is residual row i (bind_points)
+    { const int rc = ba_plot_frames(c, "nalo_ba_residual_plot", V, a->frame_mask, D.out_of, frame_of, D.I, &D.n_frames); if (rc) return rc; }
     const HostFrame& fh = w.frames[a->host];
-    int frame_of[NALO_MAX_WINDOW];
-    for (int i = 0; i < NALO_MAX_WINDOW; ++i) D.out_of[i] = -1;
-    for (int i = 0; i < V.W; ++i) {                                         // while the point arrays stand, frame i is residual row i (bind_points)
-        if (!(mask >> i & 1u)) continue;
-        const int s = V.slot[i];
-        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].I[0].p) return fail(c, NALO_ERR_STATE, "nalo_ba_residual_plot: a window frame's slot has no pyramid");
-        const HostFrame& f2 = w.frames[i];
+    for (int j = 0; j < D.n_frames; ++j) {
+        const HostFrame& f2 = w.frames[frame_of[j]];
         // Vec2 affL = AffLight::fromToVecExposure(f2->ab_exposure, f->ab_exposure, f2->aff_g2l(), f->aff_g2l());
-        aff_from_to(f2.ab_exposure, fh.ab_exposure, f2.state_scaled[6], f2.state_scaled[7], fh.state_scaled[6], fh.state_scaled[7], D.aff[D.n_frames]);
-        D.I[D.n_frames] = c->slots[s].I[0].p; frame_of[D.n_frames] = i; D.out_of[i] = D.n_frames++;
+        aff_from_to(f2.ab_exposure, fh.ab_exposure, f2.state_scaled[6], f2.state_scaled[7], fh.state_scaled[6], fh.state_scaled[7], D.aff[j]);
     }
     HostTimer ht(c, "ba_residual_plot");
     D.kmap = V.kmap[a->host]; D.seg = V.seg[a->host]; D.host_row = a->host; D.energy_mode = a->free_debug_param5 == 0.f ? 1 : 0; D.rainbow_scale = a->rainbow_scale;
-    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = residual_plot_padded_pixels(px), off_bgr = 64;
+    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = resolve_padded_pixels(px), off_bgr = 64;
     NALO_HIP(c, w.rp_col.reserve(std::max<size_t>((size_t)D.seg * D.n_frames, 1))); NALO_HIP(c, w.rp_bgr.reserve(3 * padded)); NALO_HIP(c, w.rp_cnt.reserve(4));
     NALO_HIP(c, w.rp_host.reserve(off_bgr + 3 * px));
-    if (padded > w.rp_key.cap) w.rp_key_clean = false;
-    NALO_HIP(c, w.rp_key.reserve(padded));
-    if (!w.rp_key_clean) NALO_HIP(c, hipMemsetAsync(w.rp_key.p, 0, w.rp_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
-    w.rp_key_clean = false;
+    NALO_HIP(c, w.rp_key.begin(padded, c->stream));
     NALO_HIP(c, hipMemsetAsync(w.rp_cnt.p, 0, 16, c->stream));
     D.key = w.rp_key.p; D.col = w.rp_col.p; D.bgr = w.rp_bgr.p; D.cnt = w.rp_cnt.p;
     { const int rc = residual_plot_launch(c, D); if (rc) return rc; }
-    w.rp_key_clean = true;
+    w.rp_key.settled();
     NALO_HIP(c, hipMemcpyAsync(w.rp_host.p, w.rp_cnt.p, 16, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(w.rp_host.p + off_bgr, w.rp_bgr.p, 3 * px, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));

@@ -231,9 +231,9 @@ struct Initializer {
     int jb_cur = 0;
     HostBuf<float> pin;                                  // pinned staging: the first half (pin.cap / 2 floats) host -> device, the second half device -> host
     HostBuf<double> sums_host; double sums_seq = 0;      // an evaluation's 94 sums land in mapped host memory, sequence number last: polled, no copy, no sync
-    // nalo_init_depth_image (kernels_init_plot.hip), sized on first use: the key plane (zero between calls: the resolve pass leaves it so), the points' colours, the
-    // results, the painted image and the pinned block results and image come up through
-    DevBuf<unsigned> ip_key, ip_col, ip_res; DevBuf<uint8_t> ip_bgr; HostBuf<uint8_t> ip_host; bool ip_key_clean = false;
+    // nalo_init_depth_image (kernels_init_plot.hip), sized on first use: the key plane (a KeyPlane, zero between calls), the points' colours, the results, the
+    // painted image and the pinned block results and image come up through
+    KeyPlane<unsigned, 0> ip_key; DevBuf<unsigned> ip_col, ip_res; DevBuf<uint8_t> ip_bgr; HostBuf<uint8_t> ip_host;
 };
 
 // word offsets inside a level's device block: the static members, then the members a level's LM loop changes ("dyn": one packed upload / download per level), the last
@@ -813,20 +813,17 @@ int nalo_init_depth_image(nalo_ctx* c, nalo_init_plot_args* a) {
     const InitLevel& P = I.L[lvl];
     const LvlOff o = lvl_off((size_t)P.n);
     const float* d = I.lvl_dev[lvl].p;
-    const size_t npx = (size_t)c->wl[lvl] * c->hl[lvl], padded = init_plot_padded_pixels(npx), off_bgr = 64;
+    const size_t npx = (size_t)c->wl[lvl] * c->hl[lvl], padded = resolve_padded_pixels(npx), off_bgr = 64;
     NALO_HIP(c, I.ip_col.reserve(std::max<size_t>((size_t)P.n, 1))); NALO_HIP(c, I.ip_res.reserve(4)); NALO_HIP(c, I.ip_bgr.reserve(3 * padded));
     NALO_HIP(c, I.ip_host.reserve(off_bgr + 3 * npx));
-    if (padded > I.ip_key.cap) I.ip_key_clean = false;
-    NALO_HIP(c, I.ip_key.reserve(padded));
-    if (!I.ip_key_clean) NALO_HIP(c, hipMemsetAsync(I.ip_key.p, 0, I.ip_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
-    I.ip_key_clean = false;
+    NALO_HIP(c, I.ip_key.begin(padded, c->stream));
     InitPlotDev D{};
     D.n = P.n; D.w = c->wl[lvl]; D.h = c->hl[lvl]; D.rainbow_scale = a->rainbow_scale;
     D.u = d + o.u; D.v = d + o.v; D.iR = d + o.iR; D.good = (const uint8_t*)(d + o.isGood);
     D.dI = c->slots[s].dI[lvl].p;                                              // dIp[lvl][i][0]: the one-pass pyramid does not fill the planar I[] of the upper levels
     D.key = I.ip_key.p; D.col = I.ip_col.p; D.res = I.ip_res.p; D.bgr = I.ip_bgr.p;
     { const int rc = init_plot_launch(c, D); if (rc) return rc; }
-    I.ip_key_clean = true;
+    I.ip_key.settled();
     NALO_HIP(c, hipMemcpyAsync(I.ip_host.p, I.ip_res.p, 16, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(I.ip_host.p + off_bgr, I.ip_bgr.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));

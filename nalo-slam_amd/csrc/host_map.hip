@@ -27,14 +27,14 @@ struct MapArchive {
     HostBuf<MapSeg> seg_h; DevBuf<MapSeg> seg_d; HostBuf<int> draws_h; DevBuf<int> draws_d, qcnt;
     DevBuf<double> wxyz; HostBuf<double> wxyz_h;
     DevBuf<float> cxyz; DevBuf<uint8_t> crgb; HostBuf<float> cxyz_h; HostBuf<uint8_t> crgb_h; HostBuf<int> stats_h;
-    // the window panel (nalo_map_window_plot): segment table (pinned staging + device), the key plane (zero between calls: the resolve pass leaves it so), the sources'
-    // colours, the images, the select's results, the ring counters (two buffers, the idle one zero) and the pinned block results, counters and images come up through
-    HostBuf<PlotSeg> wp_seg_h; DevBuf<PlotSeg> wp_seg_d; DevBuf<unsigned> wp_key, wp_col, wp_res; DevBuf<uint8_t> wp_bgr; DevBuf<int> wp_cnt; int wp_cnt_buf = 0;
-    HostBuf<uint8_t> wp_host; bool wp_key_clean = false;
-    // the 3-D panel (nalo_map_render): the transform table and the clipped segments (pinned staging + device), the 64-bit key plane (all-ones between calls: the
-    // resolve pass leaves it so), the counters (two buffers, the idle one zero), the images and the pinned block counters and images come up through
+    // the window panel (nalo_map_window_plot): segment table (pinned staging + device), the key plane (zero between calls), the sources' colours, the images, the
+    // select's results, the ring counters (two buffers, the idle one zero; refilled with the plane) and the pinned block results, counters and images come up through
+    HostBuf<PlotSeg> wp_seg_h; DevBuf<PlotSeg> wp_seg_d; KeyPlane<unsigned, 0> wp_key; DevBuf<unsigned> wp_col, wp_res; DevBuf<uint8_t> wp_bgr; DevBuf<int> wp_cnt; int wp_cnt_buf = 0;
+    HostBuf<uint8_t> wp_host;
+    // the 3-D panel (nalo_map_render): the transform table and the clipped segments (pinned staging + device), the 64-bit key plane (all-ones between calls), the
+    // counters (two buffers, the idle one zero; refilled with the plane), the images and the pinned block counters and images come up through
     HostBuf<float> mr_M_h; DevBuf<float> mr_M_d, mr_depth; HostBuf<MrLine> mr_lines_h; DevBuf<MrLine> mr_lines_d;
-    DevBuf<unsigned long long> mr_key, mr_cnt; int mr_cnt_buf = 0; bool mr_key_clean = false;
+    KeyPlane<unsigned long long, 0xFF> mr_key; DevBuf<unsigned long long> mr_cnt; int mr_cnt_buf = 0;
     DevBuf<uint8_t> mr_rgb; HostBuf<uint8_t> mr_host;
 };
 
@@ -423,15 +423,9 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
     if (a->frame_mask >> V.W) return fail(c, NALO_ERR_ARG, "nalo_map_window_plot: frame_mask names a frame outside the window");
     if (V.sharded) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: the window is sharded (a rank holds only its own points)");
     if (!V.pts_ok) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: the window's points are unset: carry or re-issue the window first");
-    const unsigned mask = a->frame_mask ? a->frame_mask : (1u << V.W) - 1u;
     WindowPlotDev D{};
-    for (int i = 0; i < NALO_MAX_WINDOW; ++i) D.out_of[i] = -1;
-    for (int i = 0; i < V.W; ++i) {
-        if (!(mask >> i & 1u)) continue;
-        const int s = V.slot[i];
-        if (s < 0 || s >= (int)c->slots.size() || !c->slots[s].valid || !c->slots[s].I[0].p) return fail(c, NALO_ERR_STATE, "nalo_map_window_plot: a window frame's slot has no pyramid");
-        D.I[D.n_frames] = c->slots[s].I[0].p; D.out_of[i] = D.n_frames++;
-    }
+    int frame_of[NALO_MAX_WINDOW];
+    { const int rc = ba_plot_frames(c, "nalo_map_window_plot", V, a->frame_mask, D.out_of, frame_of, D.I, &D.n_frames); if (rc) return rc; }
     HostTimer ht(c, "map_window_plot");
     // the sources: a painted frame's sublist in painting order. Mode 7 lists every frame (allID does not know the mask)
     const MapArchive* const arch = c->map;
@@ -458,16 +452,14 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
     }
     if (!c->map) c->map = new MapArchive();                                 // the call's scratch lives there (the archive stays off)
     MapArchive& m = *c->map;
-    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = window_plot_padded_pixels(px);
+    const size_t npx = (size_t)c->w * c->h, px = npx * (size_t)D.n_frames, padded = resolve_padded_pixels(px);
     const size_t nseg = std::max<size_t>(segs.size(), 1), off_cnt = 64, off_bgr = 512;
     constexpr int kCnt = 4 * NALO_MAX_WINDOW;
     NALO_HIP(c, m.wp_seg_h.reserve(nseg)); NALO_HIP(c, m.wp_seg_d.reserve(nseg)); NALO_HIP(c, m.wp_col.reserve(std::max<size_t>((size_t)total, 1)));
     NALO_HIP(c, m.wp_bgr.reserve(3 * padded)); NALO_HIP(c, m.wp_res.reserve(kPlotResWords)); NALO_HIP(c, m.wp_host.reserve(off_bgr + 3 * px));
-    if (!m.wp_cnt.p) { NALO_HIP(c, m.wp_cnt.reserve(2 * kCnt)); NALO_HIP(c, hipMemsetAsync(m.wp_cnt.p, 0, 2 * kCnt * 4, c->stream)); m.wp_cnt_buf = 0; }
-    if (padded > m.wp_key.cap) m.wp_key_clean = false;
-    NALO_HIP(c, m.wp_key.reserve(padded));
-    if (!m.wp_key_clean) NALO_HIP(c, hipMemsetAsync(m.wp_key.p, 0, m.wp_key.cap * 4, c->stream));   // a new plane, or a call that failed between its two passes
-    m.wp_key_clean = false;
+    bool refilled = false;
+    NALO_HIP(c, m.wp_cnt.reserve(2 * kCnt)); NALO_HIP(c, m.wp_key.begin(padded, c->stream, &refilled));
+    if (refilled) { NALO_HIP(c, hipMemsetAsync(m.wp_cnt.p, 0, 2 * kCnt * 4, c->stream)); m.wp_cnt_buf = 0; }   // the counters are idle exactly when the plane is
     std::copy(segs.begin(), segs.end(), m.wp_seg_h.p);
     if (!segs.empty()) NALO_HIP(c, hipMemcpyAsync(m.wp_seg_d.p, m.wp_seg_h.p, segs.size() * sizeof(PlotSeg), hipMemcpyHostToDevice, c->stream));
     D.segs = m.wp_seg_d.p; D.nseg = (int)segs.size(); D.total = (int)total;
@@ -478,7 +470,7 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
     const bool io = mode == 7 && a->minmax_io != nullptr;
     D.io_min = io ? a->minmax_io[0] : 0.f; D.io_max = io ? a->minmax_io[1] : 0.f; D.have_io = io ? 1 : 0;
     { const int rc = window_plot_launch(c, D); if (rc) return rc; }
-    m.wp_key_clean = true;
+    m.wp_key.settled();
     if (mode == 7) NALO_HIP(c, hipMemcpyAsync(m.wp_host.p, m.wp_res.p, kPlotResWords * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(m.wp_host.p + off_cnt, D.cnt, kCnt * 4, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(m.wp_host.p + off_bgr, m.wp_bgr.p, 3 * px, hipMemcpyDeviceToHost, c->stream));
@@ -495,10 +487,8 @@ int nalo_map_window_plot(nalo_ctx* c, nalo_window_plot_args* a) {
     int cnt[kCnt];
     std::memcpy(cnt, m.wp_host.p + off_cnt, sizeof(cnt));
     for (int i = 0; i < NALO_MAX_WINDOW; ++i) { a->frame_id[i] = 0; for (int k = 0; k < 4; ++k) a->sources[i][k] = 0; }
-    for (int i = 0; i < V.W; ++i) {
-        const int j = D.out_of[i];
-        if (j < 0) continue;
-        a->frame_id[j] = V.frame_id[i];
+    for (int j = 0; j < D.n_frames; ++j) {
+        a->frame_id[j] = V.frame_id[frame_of[j]];
         for (int k = 0; k < 4; ++k) a->sources[j][k] = cnt[4 * j + k];
     }
     std::memcpy(a->bgr, m.wp_host.p + off_bgr, 3 * px);
@@ -651,15 +641,13 @@ static int map_render_impl(nalo_ctx* c, nalo_map_render_args* a, nalo_map_render
     { const int rc = map_send_segs(c, m, segs, (int)total, D.S); if (rc) return rc; }
     D.S.imm = c->imm_res.p; D.S.immN = c->imm_res_n; std::memcpy(D.S.imm_frame, imm_frame, sizeof(imm_frame));
     if (have_window) { D.S.flags = VW.flags; D.S.geo = VW.geo; D.S.col0 = VW.col0; D.S.col1 = VW.col1; D.S.acc = VW.acc; D.S.prior = VW.prior; D.S.relbs = VW.relbs; }
-    const size_t npx = (size_t)a->vw * a->vh, padded = map_render_padded_pixels(npx), off_rgb = 128, off_depth = (off_rgb + 3 * npx + 15) / 16 * 16;
+    const size_t npx = (size_t)a->vw * a->vh, padded = resolve_padded_pixels(npx), off_rgb = 128, off_depth = (off_rgb + 3 * npx + 15) / 16 * 16;
     NALO_HIP(c, m.mr_M_h.reserve(M.size())); NALO_HIP(c, m.mr_M_d.reserve(M.size()));
     NALO_HIP(c, m.mr_lines_h.reserve(std::max<size_t>(lines.size(), 1))); NALO_HIP(c, m.mr_lines_d.reserve(std::max<size_t>(lines.size(), 1)));
     NALO_HIP(c, m.mr_rgb.reserve(3 * padded)); NALO_HIP(c, m.mr_depth.reserve(padded)); NALO_HIP(c, m.mr_host.reserve(off_depth + 4 * npx));
-    if (!m.mr_cnt.p) { NALO_HIP(c, m.mr_cnt.reserve(2 * kMrCounters)); NALO_HIP(c, hipMemsetAsync(m.mr_cnt.p, 0, 2 * kMrCounters * 8, c->stream)); m.mr_cnt_buf = 0; }
-    if (padded > m.mr_key.cap) m.mr_key_clean = false;
-    NALO_HIP(c, m.mr_key.reserve(padded));
-    if (!m.mr_key_clean) NALO_HIP(c, hipMemsetAsync(m.mr_key.p, 0xFF, m.mr_key.cap * 8, c->stream));   // a new plane, or a call that failed between its passes
-    m.mr_key_clean = false;
+    bool refilled = false;
+    NALO_HIP(c, m.mr_cnt.reserve(2 * kMrCounters)); NALO_HIP(c, m.mr_key.begin(padded, c->stream, &refilled));
+    if (refilled) { NALO_HIP(c, hipMemsetAsync(m.mr_cnt.p, 0, 2 * kMrCounters * 8, c->stream)); m.mr_cnt_buf = 0; }   // the counters are idle exactly when the plane is
     std::copy(M.begin(), M.end(), m.mr_M_h.p);
     NALO_HIP(c, hipMemcpyAsync(m.mr_M_d.p, m.mr_M_h.p, M.size() * 4, hipMemcpyHostToDevice, c->stream));
     std::copy(lines.begin(), lines.end(), m.mr_lines_h.p);
@@ -673,7 +661,7 @@ static int map_render_impl(nalo_ctx* c, nalo_map_render_args* a, nalo_map_render
         NALO_HIP(c, hipEventRecord(c->ev_prod, user_stream)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0));
     }
     { const int rc = map_render_launch(c, D, mesh ? &T : nullptr); if (rc) return rc; }
-    m.mr_key_clean = true;
+    m.mr_key.settled();
     NALO_HIP(c, hipMemcpyAsync(m.mr_host.p, D.cnt, kMrCounters * 8, hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_rgb, m.mr_rgb.p, 3 * npx, hipMemcpyDeviceToHost, c->stream));
     if (a->depth) NALO_HIP(c, hipMemcpyAsync(m.mr_host.p + off_depth, m.mr_depth.p, 4 * npx, hipMemcpyDeviceToHost, c->stream));

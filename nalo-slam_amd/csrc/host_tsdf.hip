@@ -20,8 +20,7 @@ struct TsdfVolume {
     nalo_tsdf_stats last{}; bool have_last = false;
     DevBuf<float> block;                             // nalo_tsdf_get / _set staging: one tile of z slices of the sub-block
     DevBuf<float> xyz; HostBuf<float> xyz_h;         // nalo_tsdf_surface_points: as many points as the caller had room for
-    DevBuf<unsigned long long> key; DevBuf<float> plane;                            // nalo_tsdf_integrate_frame: w h words each; key is zero between calls,
-    bool key_dirty = false;                                                         // unless a call failed between its scatter and its resolve: the next one zeroes it
+    KeyPlane<unsigned long long, 0> key; DevBuf<float> plane;                       // nalo_tsdf_integrate_frame: w h words each; key is zero between calls
     std::vector<MapSeg> segs;                                                       // the frame's segments, host memory: they travel as kernel arguments
     // nalo_tsdf_mesh: 5 B of scratch per sub-box voxel, the two count arrays, and the device mesh itself (nalo_tsdf_mesh_view names mesh_xyz / mesh_tri).
     // nalo_tsdf_surface_points shares mesh_mask, mesh_cntv and mesh_cnt_h (tsdf_mesh_dev): every call rewrites them before it reads them
@@ -308,19 +307,13 @@ int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld
     int total = 0;
     { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }
     const size_t npx = (size_t)c->w * c->h;
-    if (v.key.cap < npx) {                                                     // first use: the key plane starts zero and every call leaves it zero
-        DevBuf<unsigned long long> key; DevBuf<float> plane;
-        NALO_HIP(c, key.reserve(npx)); NALO_HIP(c, plane.reserve(npx));
-        NALO_HIP(c, hipMemsetAsync(key.p, 0, npx * sizeof(unsigned long long), c->stream));
-        v.key = std::move(key); v.plane = std::move(plane);
-    }
+    NALO_HIP(c, v.plane.reserve(npx));
     const bool coloured = v.colour.p != nullptr;
     if (coloured) NALO_HIP(c, v.cplane.reserve(npx));                          // every call writes every word of it: a winner's colour, or zero behind the resolve
     HostTimer ht(c, "tsdf_integrate_frame");
-    if (v.key_dirty) NALO_HIP(c, hipMemsetAsync(v.key.p, 0, npx * sizeof(unsigned long long), c->stream));
-    v.key_dirty = true;                                                        // until the resolve pass, which clears every key, is queued
+    NALO_HIP(c, v.key.begin(npx, c->stream));
     { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, coloured ? v.cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
-    v.key_dirty = false;
+    v.key.settled();
     // the packed plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
     const TsdfColourSrc src = {reinterpret_cast<const unsigned char*>(v.cplane.p), (long long)c->w * 4, 4, {0, 1, 2}};
     return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi, coloured ? &src : nullptr);

@@ -6,7 +6,8 @@
 //                      fac = (float)n_good / sid in one lane. Nothing visits the host between the sum and the painting.
 //  ip_scatter_kernel   one lane per point: its colour (black when it is not good, else makeRainbow3B(iR * fac)) into col[], and the key word of the square's pixels
 //                      inside the image raised to index + 1 with an integer atomicMax. Points are painted in ascending index, so the largest key IS the last writer.
-//  ip_resolve_kernel   one lane per four pixels: the base value (:300-301) or the winner's colour; the key words it found raised are zeroed for the next call.
+//  ip_resolve_kernel   one lane per four pixels: the base value (:300-301) or the winner's colour, between the painters' shared front end and tail
+//                      (plot_take_keys, plot_store4: plot_device.h).
 //
 // No float atomic; the bytes are the same on every run. Built without FMA contraction (build.py: NO_CONTRACT).
 #include "nalo_internal.h"
@@ -16,8 +17,6 @@
 namespace nalo {
 
 namespace {
-
-constexpr int kIpPix = 1024;                                // pixels per workgroup of the resolve pass (256 lanes x 4); the key plane is rounded up to it
 
 __global__ __launch_bounds__(64) void ip_sum_kernel(InitPlotDev D) {
     const int lane = threadIdx.x;
@@ -58,10 +57,8 @@ __global__ __launch_bounds__(256) void ip_resolve_kernel(InitPlotDev D) {
     __shared__ unsigned stage[3 * 256];
     const size_t npx = (size_t)D.w * D.h;
     const size_t g0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    uint4* const kp = reinterpret_cast<uint4*>(D.key + g0);
-    const uint4 k4 = *kp;
-    const unsigned key[4] = {k4.x, k4.y, k4.z, k4.w};
-    if (k4.x | k4.y | k4.z | k4.w) *kp = make_uint4(0u, 0u, 0u, 0u);
+    unsigned key[4];
+    plot_take_keys<0>(D.key, g0, key);
     float iv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) if (g0 + k < npx) iv[k] = D.dI[g0 + k].x;         // firstFrame->dIp[lvl][i][0]
@@ -72,12 +69,10 @@ __global__ __launch_bounds__(256) void ip_resolve_kernel(InitPlotDev D) {
         col[k] = g0 + k < npx ? (unsigned)(unsigned char)__float2int_rz(iv[k]) * 0x010101u : 0u;
         if (key[k] && g0 + k < npx && key[k] <= (unsigned)D.n) col[k] = D.col[key[k] - 1u];
     }
-    plot_store4(stage, col, D.bgr + (size_t)blockIdx.x * (3 * kIpPix));
+    plot_store4(stage, col, D.bgr + (size_t)blockIdx.x * (3 * kResolvePix));
 }
 
 }  // namespace
-
-size_t init_plot_padded_pixels(size_t pixels) { return (pixels + kIpPix - 1) / kIpPix * kIpPix; }
 
 int init_plot_launch(nalo_ctx* c, const InitPlotDev& D) {
     {
@@ -90,7 +85,7 @@ int init_plot_launch(nalo_ctx* c, const InitPlotDev& D) {
     }
     {
         ProfScope ps(c, "init_plot_resolve");
-        ip_resolve_kernel<<<(unsigned)(init_plot_padded_pixels((size_t)D.w * D.h) / kIpPix), 256, 0, c->stream>>>(D);
+        ip_resolve_kernel<<<(unsigned)(resolve_padded_pixels((size_t)D.w * D.h) / kResolvePix), 256, 0, c->stream>>>(D);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;

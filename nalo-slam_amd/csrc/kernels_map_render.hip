@@ -8,13 +8,14 @@
 //  mr_lines_kernel     one wave per clipped segment (MrLine: the host has dropped, near-clipped, projected and viewport-clipped it in double), lanes striding over
 //                      its samples; the same key update for every pixel of the width block.
 //  (mr_tris_kernel     nalo_map_render_mesh's triangles enter the same plane between the lines and the resolve pass: kernels_map_render_mesh.hip)
-//  mr_resolve_kernel   one lane per four pixels: the winner's colour and depth or the background and +inf; the keys it found lowered go back to all-ones, so the
-//                      plane is filled only when it is allocated or grown. The 12 colour bytes of a lane go through LDS and leave as 16-byte stores.
+//  mr_resolve_kernel   one lane per four pixels: the winner's colour and depth or the background and +inf, between the painters' shared front end and tail
+//                      (plot_take_keys with all-ones as the idle key, plot_store4: plot_device.h); R and B change places first, the image being R first.
 //
 // The counts are integer atomics, summed per workgroup in LDS first. No float atomic; an integer minimum does not depend on arrival order: the bytes are the same on
 // every run. Built without FMA contraction (build.py: NO_CONTRACT), the host half below included.
 #include "nalo_internal.h"
 #include "map_cloud_device.h"
+#include "plot_device.h"
 
 #include <cmath>
 
@@ -22,8 +23,7 @@ namespace nalo {
 
 namespace {
 
-constexpr int kMrPix = 1024;                                // pixels per workgroup of the resolve pass (256 lanes x 4); the key plane is rounded up to it
-constexpr unsigned long long kMrEmpty = ~0ull;
+constexpr unsigned long long kMrEmpty = ~0ull;              // a key of the idle plane (KeyPlane<unsigned long long, 0xFF>)
 
 // the sum of v over the wave's 64 lanes, valid in lane 0 (every lane calls)
 __device__ __forceinline__ unsigned mr_wave_sum(unsigned v) {
@@ -129,33 +129,23 @@ __global__ __launch_bounds__(256) void mr_resolve_kernel(MapRenderDev D) {
     __shared__ unsigned stage[3 * 256];
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid < kMrCounters) D.cnt_next[tid] = 0ull;            // the NEXT call's counters (two buffers): no fill on the path
-    const size_t g0 = ((size_t)blockIdx.x * 256 + tid) * 4;                      // < padded: the grid is padded / kMrPix workgroups
-    ulonglong2* const kp = reinterpret_cast<ulonglong2*>(D.key + g0);
-    const ulonglong2 a = kp[0], b = kp[1];
-    const unsigned long long key[4] = {a.x, a.y, b.x, b.y};
-    if ((a.x & a.y & b.x & b.y) != kMrEmpty) { kp[0] = make_ulonglong2(kMrEmpty, kMrEmpty); kp[1] = make_ulonglong2(kMrEmpty, kMrEmpty); }
+    const size_t g0 = ((size_t)blockIdx.x * 256 + tid) * 4;                      // < padded: the grid is padded / kResolvePix workgroups
+    unsigned long long key[4];
+    plot_take_keys<0xFF>(D.key, g0, key);
     unsigned col[4];
     float z[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const bool hit = key[k] != kMrEmpty;
-        col[k] = hit ? (unsigned)key[k] & 0xFFFFFFu : D.background;
+        const unsigned rgb = hit ? (unsigned)key[k] : D.background;              // R << 16 | G << 8 | B; the image is R first, so R goes where plot_store4 reads B
+        col[k] = (rgb >> 16 & 0xFFu) | (rgb & 0xFF00u) | (rgb & 0xFFu) << 16;
         z[k] = hit ? __uint_as_float((unsigned)(key[k] >> 32)) : __uint_as_float(0x7F800000u);
     }
     *reinterpret_cast<float4*>(D.depth + g0) = make_float4(z[0], z[1], z[2], z[3]);
-    // 12 bytes per lane, R first: colour word = R << 16 | G << 8 | B
-    unsigned char by[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { by[3 * k] = (unsigned char)(col[k] >> 16); by[3 * k + 1] = (unsigned char)(col[k] >> 8); by[3 * k + 2] = (unsigned char)col[k]; }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) stage[3 * tid + q] = by[4 * q] | (by[4 * q + 1] << 8) | (by[4 * q + 2] << 16) | ((unsigned)by[4 * q + 3] << 24);
-    __syncthreads();
-    if (tid < 192) reinterpret_cast<uint4*>(D.rgb + (size_t)blockIdx.x * (3 * kMrPix))[tid] = reinterpret_cast<const uint4*>(stage)[tid];
+    plot_store4(stage, col, D.rgb + (size_t)blockIdx.x * (3 * kResolvePix));
 }
 
 }  // namespace
-
-size_t map_render_padded_pixels(size_t pixels) { return (pixels + kMrPix - 1) / kMrPix * kMrPix; }
 
 int map_render_launch(nalo_ctx* c, const MapRenderDev& D, MrTrisDev* T) {
     if (D.S.nb > 0) {
@@ -173,7 +163,7 @@ int map_render_launch(nalo_ctx* c, const MapRenderDev& D, MrTrisDev* T) {
     }
     {
         ProfScope ps(c, "map_render_resolve");
-        mr_resolve_kernel<<<(unsigned)(D.padded / kMrPix), 256, 0, c->stream>>>(D);
+        mr_resolve_kernel<<<(unsigned)(D.padded / kResolvePix), 256, 0, c->stream>>>(D);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;

@@ -8,8 +8,8 @@
 //  rp_scatter_kernel   one lane per (point of the host, window row): row t < W is the residual to that target - its colour into col[] and the key word of every
 //                      pattern pixel that passes the guard raised to (the point's position in the host's list + 1) with an integer atomicMax -, row W is the
 //                      point's 3x3 square on the host's own image. The list is in painting order, so the largest key IS the last writer.
-//  rp_resolve_kernel   one lane per four pixels of all painted images: the brightness-transferred base value (:72-82) or the winner's colour; the key words it
-//                      found raised are zeroed for the next call.
+//  rp_resolve_kernel   one lane per four pixels of all painted images: the brightness-transferred base value (:72-82) or the winner's colour, between the
+//                      painters' shared front end and tail (plot_take_keys, plot_store4: plot_device.h).
 //
 // No float atomic; the bytes are the same on every run. Built without FMA contraction (build.py: NO_CONTRACT).
 #include "nalo_internal.h"
@@ -20,7 +20,6 @@ namespace nalo {
 
 namespace {
 
-constexpr int kRpPix = 1024;                                // pixels per workgroup of the resolve pass (256 lanes x 4); the key plane is rounded up to it
 constexpr uint8_t kRsOOB = 1, kRsOutlier = 2;               // ResState {IN, OOB, OUTLIER} in the state byte's low bits (IN = 0)
 
 // Ku / Kv of the eight pattern pixels: `Vec3f ptp = KRKi * Vec3f(u_pt, v_pt, 1) + Kt * idepth; Ku = ptp[0] / ptp[2]; Kv = ptp[1] / ptp[2];`
@@ -134,10 +133,8 @@ __global__ __launch_bounds__(256) void rp_resolve_kernel(ResidualPlotDev D) {
     __shared__ unsigned stage[3 * 256];
     const size_t npx = (size_t)D.w * D.h, px_total = npx * D.n_frames;
     const size_t g0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    uint4* const kp = reinterpret_cast<uint4*>(D.key + g0);
-    const uint4 k4 = *kp;
-    const unsigned key[4] = {k4.x, k4.y, k4.z, k4.w};
-    if (k4.x | k4.y | k4.z | k4.w) *kp = make_uint4(0u, 0u, 0u, 0u);
+    unsigned key[4];
+    plot_take_keys<0>(D.key, g0, key);
     unsigned col[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -152,12 +149,10 @@ __global__ __launch_bounds__(256) void rp_resolve_kernel(ResidualPlotDev D) {
         col[k] = plot_byte(colL) * 0x010101u;
         if (key[k] && key[k] <= (unsigned)D.seg) col[k] = D.col[(size_t)f * D.seg + key[k] - 1u];
     }
-    plot_store4(stage, col, D.bgr + (size_t)blockIdx.x * (3 * kRpPix));
+    plot_store4(stage, col, D.bgr + (size_t)blockIdx.x * (3 * kResolvePix));
 }
 
 }  // namespace
-
-size_t residual_plot_padded_pixels(size_t pixels) { return (pixels + kRpPix - 1) / kRpPix * kRpPix; }
 
 int residual_projections_launch(nalo_ctx* c, const ResidualPlotDev& D) {
     ProfScope ps(c, "ba_pattern_projections");
@@ -173,8 +168,8 @@ int residual_plot_launch(nalo_ctx* c, const ResidualPlotDev& D) {
     }
     {
         ProfScope ps(c, "residual_plot_resolve");
-        const size_t padded = residual_plot_padded_pixels((size_t)D.w * D.h * D.n_frames);
-        rp_resolve_kernel<<<(unsigned)(padded / kRpPix), 256, 0, c->stream>>>(D);
+        const size_t padded = resolve_padded_pixels((size_t)D.w * D.h * D.n_frames);
+        rp_resolve_kernel<<<(unsigned)(padded / kResolvePix), 256, 0, c->stream>>>(D);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;

@@ -8,8 +8,8 @@
 //  wp_scatter_kernel   one lane per entry of the virtual source list (PlotSeg, nalo_internal.h). A source that is drawn stores its colour in col[] and raises the key
 //                      word of the ring's pixels inside the image to (its position in its frame's sublist + 1) with an integer atomicMax. The sublist is laid out in
 //                      the reference's painting order, so the largest key IS the last writer; an integer maximum does not depend on arrival order.
-//  wp_resolve_kernel   one lane per four pixels of all painted frames: the grey base value (:180-185) or the winner's colour; the key words it found raised are zeroed
-//                      for the next call. 16-byte loads of the keys and the irradiance, the 12 bytes of a lane go through LDS and leave as 16-byte stores.
+//  wp_resolve_kernel   one lane per four pixels of all painted frames: the grey base value (:180-185) or the winner's colour, between the painters' shared front end
+//                      and tail (plot_take_keys, plot_store4: plot_device.h). The irradiance in 16-byte loads where a lane's four pixels are one frame's.
 //
 // No float atomic, no atomic append; the bytes are the same on every run. Built without FMA contraction (build.py: NO_CONTRACT).
 #include "nalo_internal.h"
@@ -20,8 +20,6 @@
 namespace nalo {
 
 namespace {
-
-constexpr int kWpPix = 1024;                                // pixels per workgroup of the resolve pass (256 lanes x 4); the key plane is rounded up to it
 
 struct WpSrc { int kind, widx, fstart, t; float u, v, idepth; };
 
@@ -199,13 +197,10 @@ __global__ __launch_bounds__(256) void wp_scatter_kernel(WindowPlotDev D) {
 
 __global__ __launch_bounds__(256) void wp_resolve_kernel(WindowPlotDev D) {
     __shared__ unsigned stage[3 * 256];
-    const int tid = threadIdx.x;
     const size_t npx = (size_t)D.w * D.h, px_total = npx * D.n_frames;
-    const size_t g0 = ((size_t)blockIdx.x * 256 + tid) * 4;
-    uint4* const kp = reinterpret_cast<uint4*>(D.key + g0);
-    const uint4 k4 = *kp;
-    const unsigned key[4] = {k4.x, k4.y, k4.z, k4.w};
-    if (k4.x | k4.y | k4.z | k4.w) *kp = make_uint4(0u, 0u, 0u, 0u);
+    const size_t g0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    unsigned key[4];
+    plot_take_keys<0>(D.key, g0, key);
     int f = (int)(g0 / npx);
     size_t q = g0 - (size_t)f * npx;
     float iv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -230,20 +225,10 @@ __global__ __launch_bounds__(256) void wp_resolve_kernel(WindowPlotDev D) {
             if (src < D.total) col[k] = D.col[src];
         }
     }
-    // 12 bytes per lane: {b g r b | g r b g | r b g r}
-    stage[3 * tid] = (col[0] & 0xFFFFFFu) | (col[1] << 24);
-    stage[3 * tid + 1] = ((col[1] >> 8) & 0xFFFFu) | (col[2] << 16);
-    stage[3 * tid + 2] = ((col[2] >> 16) & 0xFFu) | (col[3] << 8);
-    __syncthreads();
-    if (tid < 192) {
-        const uint4 o = reinterpret_cast<const uint4*>(stage)[tid];
-        reinterpret_cast<uint4*>(D.bgr + (size_t)blockIdx.x * (3 * kWpPix))[tid] = o;
-    }
+    plot_store4(stage, col, D.bgr + (size_t)blockIdx.x * (3 * kResolvePix));
 }
 
 }  // namespace
-
-size_t window_plot_padded_pixels(size_t pixels) { return (pixels + kWpPix - 1) / kWpPix * kWpPix; }
 
 int window_plot_launch(nalo_ctx* c, const WindowPlotDev& D) {
     if (D.mode == 7) {
@@ -256,8 +241,8 @@ int window_plot_launch(nalo_ctx* c, const WindowPlotDev& D) {
     }
     {
         ProfScope ps(c, "window_plot_resolve");
-        const size_t padded = window_plot_padded_pixels((size_t)D.w * D.h * D.n_frames);
-        wp_resolve_kernel<<<(unsigned)(padded / kWpPix), 256, 0, c->stream>>>(D);
+        const size_t padded = resolve_padded_pixels((size_t)D.w * D.h * D.n_frames);
+        wp_resolve_kernel<<<(unsigned)(padded / kResolvePix), 256, 0, c->stream>>>(D);
     }
     NALO_HIP(c, hipGetLastError());
     return NALO_OK;

@@ -42,6 +42,30 @@ struct DevBuf {                  // device buffer, grows on demand (contents are
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// A painter's per-pixel key plane: a DevBuf whose every byte is FillByte while no call is in flight. The scatter passes move keys with integer atomics and the
+// resolve pass puts back what it found moved (plot_take_keys, plot_device.h), so a call pays for a fill only when the plane is new or has grown, or when the
+// call before it failed between begin() and settled(). What lives beside the plane and is kept idle the same way (a painter's counters) follows `refilled`.
+template <typename T, int FillByte>
+struct KeyPlane : private DevBuf<T> {
+    using DevBuf<T>::p;
+    // room for `words` keys; the fill, when one is due, covers the whole capacity and is queued on s in front of the caller's scatter
+    hipError_t begin(size_t words, hipStream_t s, bool* refilled = nullptr) {
+        const bool refill = words > this->cap || !idle;
+        if (refilled) *refilled = refill;
+        idle = false;
+        hipError_t e = this->reserve(words);
+        if (e == hipSuccess && refill) e = hipMemsetAsync(p, FillByte, this->cap * sizeof(T), s);
+        return e;
+    }
+    void settled() { idle = true; }                                             // the resolve pass that restores every key has been queued
+private:
+    bool idle = false;
+};
+
+// pixels per workgroup of a resolve pass (256 lanes x 4 pixels): key planes and the images resolved from them are sized in whole workgroups
+constexpr int kResolvePix = 1024;
+inline size_t resolve_padded_pixels(size_t pixels) { return (pixels + kResolvePix - 1) / kResolvePix * kResolvePix; }
+
 template <typename T>
 struct HostBuf {                 // pinned host block with DevBuf's grow rule; cap is the allocation, in elements
     T* p = nullptr;
@@ -371,11 +395,10 @@ struct MapRenderDev {
     MapSrcDev S; const float* M;                                                // M: [n_frames][12], row MapSeg::frame
     int mode; float scaledTH, absTH, minRelBS, ci[4]; MrCam cam;
     const MrLine* lines; int n_lines;
-    unsigned long long* key; size_t padded;                                     // one word per pixel, rounded up to whole resolve workgroups; all-ones between calls
+    unsigned long long* key; size_t padded;                                     // one word per pixel, rounded up (resolve_padded_pixels); all-ones between calls
     unsigned long long *cnt, *cnt_next;                                         // kMrCounters words: n_vertices, n_drawn_points, n_line_samples, 0, then the triangles' six (MrTrisDev); the idle buffer zeroed for the next call
     uint8_t* rgb; float* depth; unsigned background;                            // rgb: 3 bytes per key word; depth: 4
 };
-size_t map_render_padded_pixels(size_t pixels);
 void map_render_transform(const double view[12], const double camToWorld[12], float M[12]);          // (float)(view . camToWorld)
 void map_render_apply(const float M[12], const float p[3], float out[3]);                              // ((M0 x + M1 y) + M2 z) + M3 per row, in float
 // one segment in view space (float endpoints) through the drop rules, the near clip, the projection and the viewport clip; false: dropped (no segment counted)
@@ -401,6 +424,10 @@ struct PlotWindowView {
     const uint8_t* flags; const float4* geo;
 };
 int ba_plot_view(nalo_ctx* c, PlotWindowView* V);
+// the frames a panel paints: those frame_mask names (0: all), in window order. out_of: window frame -> painted frame or -1; per painted frame its window frame and
+// level-0 irradiance. who: the caller's name in the refusal of a frame whose slot has no pyramid
+int ba_plot_frames(nalo_ctx* c, const char* who, const PlotWindowView& V, unsigned frame_mask, int out_of[NALO_MAX_WINDOW], int frame_of[NALO_MAX_WINDOW],
+                   const float* I[NALO_MAX_WINDOW], int* n_frames);
 // the sources: a virtual list of segments, a frame's in the reference's painting order (its kmap segment, its archive runs once for status 2 and once for status 3), so
 // that a source's position in its frame's sublist IS its priority. kind as MapSeg's; kind 0 is the whole resident set once (fstart 0, the frame from host_idx).
 // widx: the window frame; fstart: where the frame's sublist starts
@@ -413,19 +440,17 @@ struct WindowPlotDev {
     const uint8_t* flags; const float4* geo;
     int out_of[NALO_MAX_WINDOW];                                                // window frame -> painted frame, -1: masked out
     int fstart[NALO_MAX_WINDOW]; const float* I[NALO_MAX_WINDOW];               // per PAINTED frame: its sublist's start, its level-0 irradiance
-    unsigned *key, *col; uint8_t* bgr;                                          // key: n_frames w h words rounded up to 16, zero between calls; col: total words; bgr: 3 bytes per key word
+    unsigned *key, *col; uint8_t* bgr;                                          // key: n_frames w h words rounded up (resolve_padded_pixels), zero between calls; col: total words; bgr: 3 bytes per key word
     unsigned* res; int *cnt, *cnt_next;                                         // res [kPlotResWords]; cnt [NALO_MAX_WINDOW][4] rings per painted frame and class, the idle buffer zeroed for the next call
     float io_min, io_max; int have_io;
 };
-size_t window_plot_padded_pixels(size_t pixels);                                // what key (words) and bgr (3 bytes each) are sized by: whole workgroups of the resolve pass
 int window_plot_launch(nalo_ctx* c, const WindowPlotDev& D);                   // [select, mode 7] scatter, resolve on c->stream
 // ---- the initialiser's depth panel (nalo_init_depth_image; host_init.hip, kernels_init_plot.hip): CoarseInitializer::debugPlot from the resident Pnt arrays
 struct InitPlotDev {
     int n, w, h; float rainbow_scale;
     const float *u, *v, *iR; const uint8_t* good; const float4* dI;             // the level's points and the first frame's texels of that level (x: the irradiance)
-    unsigned *key, *col, *res; uint8_t* bgr;                                    // key: w h words rounded up (init_plot_padded_pixels), zero between calls; col: n words;
+    unsigned *key, *col, *res; uint8_t* bgr;                                    // key: w h words rounded up (resolve_padded_pixels), zero between calls; col: n words;
 };                                                                              // res: {n_good, sid, fac, 0}; bgr: 3 bytes per key word
-size_t init_plot_padded_pixels(size_t pixels);
 int init_plot_launch(nalo_ctx* c, const InitPlotDev& D);                       // sum, scatter, resolve on c->stream
 // ---- the residual panel (nalo_ba_residual_plot) and the read-back of projectedTo / state_energy (nalo_ba_get_pattern_projections); host_ba.hip,
 // kernels_residual_plot.hip. Rows are the window's residual rows = its frames while the point arrays stand.
@@ -438,9 +463,8 @@ struct ResidualPlotDev {
     const int* kmap; int seg, host_row, energy_mode, n_frames; float rainbow_scale;
     int out_of[NALO_MAX_WINDOW];                                                // residual row -> painted image, -1: masked out
     const float* I[NALO_MAX_WINDOW]; double aff[NALO_MAX_WINDOW][2];            // per PAINTED image: its level-0 irradiance and the affL it is transferred with
-    unsigned *key, *col; uint8_t* bgr; int* cnt;                                // key: n_frames w h words rounded up, zero between calls; col: n_frames x seg words; bgr: 3 bytes
+    unsigned *key, *col; uint8_t* bgr; int* cnt;                                // key: n_frames w h words rounded up (resolve_padded_pixels), zero between calls; col: n_frames x seg words; bgr: 3 bytes
 };                                                                              // per key word; cnt: {points, residuals, pattern pixels}, zero before
-size_t residual_plot_padded_pixels(size_t pixels);
 int residual_projections_launch(nalo_ctx* c, const ResidualPlotDev& D);        // rp_get_kernel on c->stream
 int residual_plot_launch(nalo_ctx* c, const ResidualPlotDev& D);               // scatter, resolve on c->stream
 // ---- the dense map (nalo_dense_update_map, nalo_map_dense_*)

@@ -1,6 +1,7 @@
 // Device functions the painters share (kernels_depth_image.hip: debugPlotIDepthMap, kernels_window_plot.hip: FullSystem::debugPlot, kernels_init_plot.hip:
-// CoarseInitializer::debugPlot, kernels_residual_plot.hip: debugPlotTracking): the grey base value, the colour maps of util/globalFuncs.h, the float -> byte conversion
-// of a colour (kernels_map.hip's clouds too), the packed store of a resolve pass, and the search step of the radix select. Every file that
+// CoarseInitializer::debugPlot, kernels_residual_plot.hip: debugPlotTracking, kernels_map_render.hip: the 3-D panel): the grey base value, the colour maps of
+// util/globalFuncs.h, the float -> byte conversion of a colour (kernels_map.hip's clouds too), the two ends of a resolve pass - the key load that leaves the
+// plane idle and the packed store -, and the search step of the radix select. Every file that
 // includes it is built without FMA contraction (build.py: NO_CONTRACT). Conversions the reference leaves undefined are DEFINED as include/nalo_gpu.h states them.
 #pragma once
 #include "nalo_internal.h"
@@ -52,6 +53,24 @@ __device__ __forceinline__ unsigned plot_rainbow(float id, float scale) {
     if (icP == 0) return a | (b << 8);
     if (icP == 1) return (a << 8) | (b << 16);
     return b | (a << 16);
+}
+
+// The front end of a resolve pass (256 lanes x 4 pixels, kResolvePix per workgroup; g0: the lane's first pixel, below the plane's padded size): the lane's four keys
+// of a KeyPlane<K, FillByte> in 16-byte loads, and the idle value written back only where a key was moved, so that the plane needs no fill before the next call.
+template <int FillByte, typename K>
+__device__ __forceinline__ void plot_take_keys(K* plane, size_t g0, K key[4]) {
+    constexpr K idle = (K)~(K)0 / 0xFF * FillByte;
+    constexpr unsigned idle_word = 0x01010101u * FillByte;
+    constexpr int NV = sizeof(K) / 4;
+    uint4* const kp = reinterpret_cast<uint4*>(plane + g0);
+    uint4 v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = kp[j];
+    __builtin_memcpy(key, v, sizeof(v));
+    if ((key[0] ^ idle) | (key[1] ^ idle) | (key[2] ^ idle) | (key[3] ^ idle)) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) kp[j] = make_uint4(idle_word, idle_word, idle_word, idle_word);
+    }
 }
 
 // The four pixels of a lane of a resolve pass (256 lanes x 4 pixels, byte k of a Vec3b in bits 8k..8k+7 of col[]) as 12 bytes {b g r b | g r b g | r b g r}: through

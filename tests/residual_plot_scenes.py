@@ -11,9 +11,9 @@ from nalo_slam_amd import synth
 from nalo_slam_amd.synth import PATTERN
 
 F = np.float32
-SHIFT = [(0.0, 0.0), (-1.6, -1.3), (1.2, 0.7)]                                   # pixels at idepth 1, per frame
-EXPOSURE = [1.0, 1.5, 0.8]
-AFF = [(0.0, 0.0), (0.2, -30.0), (-0.1, 12.0)]                                   # aff_g2l (a, b) per frame
+SHIFT = [(0.0, 0.0), (-1.6, -1.3), (1.2, 0.7), (0.9, -1.1)]                      # pixels at idepth 1, per frame (W <= 4)
+EXPOSURE = [1.0, 1.5, 0.8, 1.2]
+AFF = [(0.0, 0.0), (0.2, -30.0), (-0.1, 12.0), (0.05, -8.0)]                     # aff_g2l (a, b) per frame
 STEP = 60.0                                                                     # the brightness step on the right half of the last frame
 
 

@@ -3,7 +3,8 @@
 The model is fed with what the read-back route returns: nalo_init_get_points (u, v, iR, isGood of the level) and nalo_frame_download (the first frame's irradiance
 at the level). "Equal" is byte for byte for the image and bit for bit for sum_iR and fac (a NaN equals a NaN: include/nalo_gpu.h leaves its sign and payload open).
 
-  1  640x480, every level: after nalo_init_set_first and after three nalo_init_track_frame; the coarser levels overlap (asserted on the host); two calls, same bytes
+  1  640x480, every level: after nalo_init_set_first and after three nalo_init_track_frame; the coarser levels overlap (asserted on the host); two calls, same bytes;
+     a fresh context through its coarsest level, level 0 and the coarsest again (the key plane grows, then is used far below its capacity)
   2  states planted through nalo_init_set_points: no good point, one good point, alternating, the special values of iR, the sum-order set
   3  a first frame whose irradiance leaves [0, 255]
   4  level 0 at 1224x368 after a tracked frame; all ~61 k points of 1920x1072 in one call
@@ -105,6 +106,16 @@ def test_every_level_after_set_first_and_after_three_frames():
         assert again["bgr"].tobytes() == got["bgr"].tobytes() and ip.same_float(again["fac"], got["fac"]) and ip.same_float(again["sum_iR"], got["sum_iR"])
     check(c, 0, scale=0.37, what="rainbow_scale 0.37")
     check(c, 1, scale=4.0, what="rainbow_scale 4")
+
+
+def test_plane_cleans_itself():
+    """a context that has painted nothing yet paints its coarsest level, then level 0, then the coarsest again: the key plane grows, then is used far below its
+    capacity; every call's bytes and results equal the model's"""
+    c, _ = ctx("walk", 640, 480, 2)
+    top = c.levels - 1
+    assert top >= 3
+    for lvl in (top, 0, top):
+        check(c, lvl, what="the plane's walk")
 
 
 def plant(c, lvl, iR=None, good=None):

@@ -8,7 +8,8 @@
      nalo_ba_get_points and args.aff returned; args.aff is within 1e-14 relative of the numpy formula. Planted windows (tests/residual_plot_scenes.py) at 64x32
      (W = 2) and 80x48 (W = 3) with hosts of 1, 63, 64, 65 and 257 points: two points on the same pixels with different energies, OOB residuals, a frame with a
      brightness step (IN and OUTLIER both occur), coordinates in (1.1, 2], exposures and affine parameters that make both clamps of the base fire; both colour
-     modes, every host, two frame_mask subsets; two calls give the same bytes
+     modes, every host, two frame_mask subsets; two calls give the same bytes; one context through 1, 4, 1 and 3 painted images of 70x50 (W = 4: the key
+     plane grows, is used below its capacity and again after that)
   3  three keyframes of the device chain at 1224x368, W = 8: after each nalo_ba_optimize the images equal the model fed from a TWIN context that never plots,
      and the twin's next nalo_ba_optimize and nalo_ba_flag_points give bit-equal results; between nalo_ba_marginalize_frame and the carry the call is refused
   4  every other refusal, with sentinel outputs
@@ -159,6 +160,23 @@ def test_planted_windows(w, h, W, sizes, masks):
             colL = a[f2][0] * rb["I"][f2].astype(np.float64) + a[f2][1]
             clamps |= ({"low"} if (colL < 0).any() else set()) | ({"high"} if (colL > 255).any() else set())
     assert clamps == {"low", "high"}, "the base image's clamps do not both fire"
+    c.close()
+
+
+def test_plane_cleans_itself():
+    """ONE context paints 1, then all 4, then 1, then 3 images of 70x50: 3500 pixels an image are no multiple of the resolve pass's 1024, so every image after
+    the first straddles workgroups and the last workgroup has a tail. The key plane grows, is used below its capacity, and is used again after that; every call's
+    bytes and counts equal the model's, in both colour modes and for a host inside and outside the mask."""
+    w, h, W = 70, 50, 4
+    win, aff, ex = scenes.planted(w, h, W, (65, 63, 130, 64), seed=w)
+    fids = [70 + 5 * i for i in range(W)]
+    c = make_ctx(win, aff=aff, exposure=ex, frame_ids=fids)
+    c.ba_linearize(False)
+    rb = read_back(c, list(range(W)))
+    for mask in (0b0100, 0b1111, 0b0010, 0b1011):
+        for host, p5 in ((2, 0.0), (1, 1.0)):
+            got, _ = check_plot(c, rb, win.host, win.u, win.v, host, p5, mask, fids=fids, fn=rp.literal, what="the plane's walk")
+            assert got["n_residuals"] > 0 and got["n_pattern_pixels"] > 0
     c.close()
 
 

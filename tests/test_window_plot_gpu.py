@@ -7,7 +7,8 @@ loops one to one and serves the small shapes; `fast` is its vectorised twin (tes
 
   1  planted windows at 64x32 (W = 2), 80x48 (W = 3) and 70x33 (W = 2, a pixel count that is no multiple of the resolve pass's four pixels per lane): active and
      immature lists of 0, 1, 2, 63, 64, 65 and 257 points, centres on and around every border and either side of every edge of both kernels' work split, positions
-     either side of .5, overlapping rings of one list, special inverse depths and irradiances, every mode
+     either side of .5, overlapping rings of one list, special inverse depths and irradiances, every mode; one context through 1, 4, 1 and 3 painted frames of
+     70x50 (the key plane grows, is used below its capacity and again after that)
   2  the archive lists, planted through the chain's own calls as tests/test_map_gpu.py plants its hosts (640x480, W = 6): hosts with 0, 1, 2, 63 and 65 planted
      removals, then 64 and 257 more (which of them are marginalised and which dropped is the data's choice), a host that loses nothing and one that loses only
      points without a residual; a second issue of the window puts an active ring on top of every archived one
@@ -182,6 +183,20 @@ def test_planted_windows_every_mode(w, h, W, sizes, imm_sizes, levels):
     for mask in [1 << i for i in range(W)] + [(1 << W) - 1, 0b101 & ((1 << W) - 1)]:
         check(c, frames, w, h, 1, mask, fids=S["fids"])
         check(c, frames, w, h, 4, mask, fids=S["fids"])
+    c.close()
+
+
+def test_plane_cleans_itself():
+    """ONE context paints 1, then all 4, then 1, then 3 frames of 70x50: 3500 pixels a frame are no multiple of the resolve pass's 1024, so every frame after the
+    first straddles workgroups and the last workgroup has a tail. The key plane and the counters beside it grow, are used below their capacity, and are used again
+    after that; every call's bytes and ring counts equal the model's."""
+    w, h, W = 70, 50, 4
+    c, S = planted_window(w, h, W, (65, 130, 63, 257), seed=w + h, levels=1)
+    planted_immature(c, w, h, (64, 70, 1, 129), seed=h)
+    frames = read_frames(c, S["slots"], S["fids"], S["host"], S["u"], S["v"], S["valid"])
+    for mask in (0b0100, 0b1111, 0b0010, 0b1011):
+        for mode in (1, 4):
+            check(c, frames, w, h, mode, mask, fids=S["fids"], fn=model.literal, what="the plane's walk")
     c.close()
 
 
