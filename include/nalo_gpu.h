@@ -1838,6 +1838,50 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *                    call's code (a refusal of nalo_tsdf_shift_for or nalo_tsdf_shift_boxes: NALO_ERR_ARG). shift_out (may be NULL) takes the shift; stats
  *                    (may be NULL) the number of boxes, the sums of the three per-call counts and the archive's totals. NALO_ERR_STATE with the archive
  *                    disabled or without a volume, before anything else.
+ *
+ * The alignment. Whether a depth plane fits the model it is about to be fused into: a direct alignment of the plane against the signed-distance field, the
+ * step every dense fusion pipeline has in front of its integration (the reference fuses with the pose it is given). DEFINED here; it reads volume and plane and
+ * changes neither. The estimate is (R, t, s): camToWorld as nalo_tsdf_integrate_depth takes it (12 doubles, rigid) and a scale s > 0, 1 unless the monocular
+ * window's gauge is in doubt; dof = 6 keeps s fixed, dof = 7 estimates it.
+ * nalo_tsdf_align_eval   one evaluation at one estimate, in ONE kernel launch. Per pixel everything in float, no FMA contraction, each operation rounded once:
+ *     Visited: pixel (u, v) of the plane iff u % step == 0 && v % step == 0. The plane: F32, one channel, its own w x h and K, any strides nalo_dev_plane_check accepts.
+ *     D is usable iff D >= min_depth && D <= max_depth (a NaN fails). rx, ry as in the ray-cast; pc = (rx * D, ry * D, D).
+ *     M = [s R | t], 3 x 4, each entry formed in double (s * R[a][j]; t[a]) and rounded to float; pw_a = ((M_a0 pcx + M_a1 pcy) + M_a2 pcz) + M_a3;
+ *     q_a = ((pw_a - origin_a) / voxel_size) - 0.5f, the ray-cast's grid coordinate.
+ *     r = S(q), the ray-cast's field with its validity rule and min_weight (one device function serves both kernels). G_a = S(q + e_a) - S(q - e_a) as for the
+ *     ray-cast's normal, all six samples VALID; g_a = G_a * (0.5f / voxel_size), the quotient computed once.
+ *     State, the first rule that fires: 1 D not usable; 2 S(q) invalid; 3 a gradient sample invalid; 0 used.
+ *     J = (g, pw x g, g . (pw - tf)), tf = M_a3: each entry of the cross product two rounded products and a rounded difference, (pw_y g_z - pw_z g_y,
+ *     pw_z g_x - pw_x g_z, pw_x g_y - pw_y g_x); the dot summed left to right; J_6 is 0.0f for dof = 6. The tangent is translation, then rotation, then log s.
+ *     hw = fabsf(r) <= huber ? 1.0f : huber / fabsf(r);  Jw_i = hw * J_i.
+ *   Sums over the used pixels, in double: H_ij = sum (double)Jw_i (double)J_j for i <= j; b_i = sum (double)Jw_i (double)r; rr = sum (double)r (double)r -
+ *     every term an exact product of two floats - and E = sum rho, rho = (double)r (double)r for fabsf(r) <= huber, else huber * (2.0 * |r| - huber) in double.
+ *     nalo_tsdf_align_sums holds the 37: H's upper triangle row-major (H[0][0..6], H[1][1..6], ...), b, E, rr; and count[state], four integers.
+ *   No float or double atomic: lanes reduce inside the wave, waves through LDS, each workgroup writes one partial record, and the workgroup that draws the last
+ *     (integer) ticket adds the records in workgroup order: the same bytes on every run of the same launch configuration (plane size and step).
+ *   records (optional, DEVICE memory, records_cap floats >= h w 10): [h][w][10] = r, hw, J0..J6, (float)state, written at visited pixels only; every field but
+ *     the state is 0.0f unless the state is 0. Without it the kernel stores nothing per pixel.
+ *   Stream order as nalo_tsdf_integrate_depth (producer_stream, the event nalo_tsdf_release waits for). The sums come up through host-mapped memory: one host wait.
+ * nalo_tsdf_align_step   host only, needs no context: one Levenberg-Marquardt step in fp64. Hl = H with its diagonal scaled by 1 + lambda; inc = solve(Hl, -b)
+ *     over the leading dof x dof block by Cholesky (inc[6] = 0 for dof = 6); (R, t) <- exp(inc[0..5]) . (R, t), s <- s * exp(inc[6]). NALO_ERR_ARG, with
+ *     nothing written: a NULL pointer, dof outside {6, 7}, a lambda that is negative or not finite, an Hl or b that is not finite or an Hl that is not positive
+ *     definite, an estimate or an update that is not finite.
+ * nalo_tsdf_align_depth  the Levenberg-Marquardt loop, driven by the host: one launch per evaluation, its 37 doubles and four counts read from host-mapped
+ *     memory behind one wait, the 7 x 7 system solved on the host (nalo_tsdf_align_step). With n = count[0]:
+ *       evaluate est_in; fewer than max(min_used, 1) used pixels: NALO_TSDF_ALIGN_TOO_FEW. lambda = lambda0 (0: the default 0.01). Then up to max_iterations times:
+ *       (inc, cand) = step(H, b, lambda) of the current estimate (refused: NALO_TSDF_ALIGN_SOLVE_FAILED, the loop ends); evaluate cand; it is accepted iff
+ *       n_new >= max(min_used, 1) && E_new / n_new < E / n - then it becomes the current estimate and lambda *= 0.5, else lambda *= 4; then, if
+ *       sqrt(sum inc_i^2) <= eps: NALO_TSDF_ALIGN_CONVERGED. All iterations used: NALO_TSDF_ALIGN_ITERATION_LIMIT.
+ *     result: the current estimate (est_in itself when no step was accepted), status, iterations (steps taken), evaluations, E and n of the first evaluation and
+ *     of the current estimate, the current estimate's sums, and a trace the caller caps: one entry per evaluation, in order - estimate, the lambda its step was
+ *     solved with (lambda0 for the first), E, the counts, accepted (1 for the first). n_trace = min(evaluations, trace_cap).
+ * nalo_tsdf_align_frame  to nalo_tsdf_align_depth what nalo_tsdf_integrate_frame is to nalo_tsdf_integrate_depth: the same context-owned plane of the frame's
+ *     dense list (last-record rule, one code path), args->K for the context's w x h; args->depth and producer_stream are not looked at. The same refusals.
+ * Refusals: nothing is queued; volume, context, plane and outputs stay as they were; the counts (count[], iterations, evaluations, n_first, n_last, n_trace)
+ *     are zeroed. NALO_ERR_STATE: no volume. NALO_ERR_ARG: a NULL pointer; a plane nalo_tsdf_integrate_depth would refuse; step < 1; dof outside {6, 7}; a
+ *     non-finite pose, K, s or threshold (min_depth, max_depth, huber); s <= 0; huber <= 0; min_depth > max_depth; a NaN min_weight; records given with
+ *     records_cap < h w 10; and for the loop max_iterations outside 1..64, a lambda0 or eps that is negative or not finite, a negative trace_cap, trace_cap > 0
+ *     with a NULL trace.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -1931,10 +1975,36 @@ int nalo_tsdf_archive_stats(nalo_ctx* ctx, struct nalo_tsdf_archive_stats* out);
 int nalo_tsdf_archive_get(nalo_ctx* ctx, nalo_tsdf_archive_get_args* args);
 int nalo_tsdf_archive_view(nalo_ctx* ctx, nalo_tsdf_archive_dev* out);             /* host only, launches nothing */
 int nalo_tsdf_follow(nalo_ctx* ctx, const double centre[3], const int margin[3], float min_weight, int shift_out[3], nalo_tsdf_follow_stats* stats);
+typedef struct nalo_tsdf_align_est { double camToWorld[12]; double s; } nalo_tsdf_align_est;
+typedef struct nalo_tsdf_align_args {
+    nalo_dev_plane depth;                   /* F32, one channel, w x h of its own (nalo_tsdf_align_frame: not looked at) */
+    float K[4];                             /* fx, fy, cx, cy for that size */
+    float min_depth, max_depth, min_weight, huber;
+    int step, dof;                          /* every step-th pixel both ways; 6 or 7 */
+    void* producer_stream;                  /* as nalo_tsdf_integrate_args */
+    float* records; long long records_cap;  /* DEVICE, optional: [h][w][10]; the floats there is room for */
+    int max_iterations, min_used;           /* the loop only: 1..64; the fewest used pixels an estimate may have */
+    double lambda0, eps;                    /* the loop only: 0 = 0.01; the norm of the increment that ends it */
+} nalo_tsdf_align_args;
+typedef struct nalo_tsdf_align_sums { double H[28], b[7], E, rr; long long count[4]; } nalo_tsdf_align_sums;   /* count[state]; count[0] = n */
+typedef struct nalo_tsdf_align_trace { nalo_tsdf_align_est est; double lambda, E; long long count[4]; int accepted; } nalo_tsdf_align_trace;
+enum { NALO_TSDF_ALIGN_CONVERGED = 0, NALO_TSDF_ALIGN_ITERATION_LIMIT = 1, NALO_TSDF_ALIGN_TOO_FEW = 2, NALO_TSDF_ALIGN_SOLVE_FAILED = 3 };
+typedef struct nalo_tsdf_align_result {
+    nalo_tsdf_align_est est;
+    int status, iterations, evaluations;
+    double E_first, E_last; long long n_first, n_last;
+    nalo_tsdf_align_sums last;              /* the sums at est */
+    nalo_tsdf_align_trace* trace; int trace_cap;   /* in: host, optional */
+    int n_trace;
+} nalo_tsdf_align_result;
+int nalo_tsdf_align_eval(nalo_ctx* ctx, const nalo_tsdf_align_args* args, const nalo_tsdf_align_est* est, nalo_tsdf_align_sums* out);
+int nalo_tsdf_align_depth(nalo_ctx* ctx, const nalo_tsdf_align_args* args, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* result);
+int nalo_tsdf_align_frame(nalo_ctx* ctx, int frame_id, const nalo_tsdf_align_args* args, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* result);
+int nalo_tsdf_align_step(const double H[28], const double b[7], double lambda, int dof, const nalo_tsdf_align_est* est, double inc[7], nalo_tsdf_align_est* est_out);   /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_align", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -43,6 +43,7 @@ EXPORTS = [
     "nalo_tsdf_create", "nalo_tsdf_reset", "nalo_tsdf_destroy", "nalo_tsdf_integrate_depth", "nalo_tsdf_release", "nalo_tsdf_integrate_frame", "nalo_tsdf_last", "nalo_tsdf_get", "nalo_tsdf_set", "nalo_tsdf_view", "nalo_tsdf_surface_points", "nalo_tsdf_frustum_box", "nalo_tsdf_mesh", "nalo_tsdf_mesh_view", "nalo_tsdf_mesh_table",
     "nalo_tsdf_color_enable", "nalo_tsdf_color_disable", "nalo_tsdf_integrate_depth_color", "nalo_tsdf_color_get", "nalo_tsdf_color_set", "nalo_tsdf_color_view", "nalo_tsdf_mesh_color", "nalo_tsdf_mesh_color_view",
     "nalo_tsdf_raycast", "nalo_tsdf_raycast_view", "nalo_tsdf_raycast_steps",
+    "nalo_tsdf_align_eval", "nalo_tsdf_align_depth", "nalo_tsdf_align_frame", "nalo_tsdf_align_step",
     "nalo_tsdf_shift", "nalo_tsdf_geometry", "nalo_tsdf_shift_for", "nalo_tsdf_shift_boxes",
     "nalo_tsdf_archive_enable", "nalo_tsdf_archive_disable", "nalo_tsdf_archive_reset", "nalo_tsdf_archive_mesh", "nalo_tsdf_archive_stats", "nalo_tsdf_archive_get", "nalo_tsdf_archive_view", "nalo_tsdf_follow",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
@@ -222,6 +223,34 @@ class TsdfRaycastDev(C.Structure):                        # nalo_tsdf_raycast_de
     _fields_ = [("depth", DevPlane), ("normal", DevPlane), ("rgba", DevPlane), ("w", C.c_int), ("h", C.c_int), ("stream", C.c_void_p)]
 
 
+class TsdfAlignEst(C.Structure):                          # nalo_tsdf_align_est
+    _fields_ = [("camToWorld", C.c_double * 12), ("s", C.c_double)]
+
+
+class TsdfAlignArgs(C.Structure):                         # nalo_tsdf_align_args
+    _fields_ = [("depth", DevPlane), ("K", C.c_float * 4), ("min_depth", C.c_float), ("max_depth", C.c_float), ("min_weight", C.c_float), ("huber", C.c_float),
+                ("step", C.c_int), ("dof", C.c_int), ("producer_stream", C.c_void_p), ("records", C.c_void_p), ("records_cap", C.c_longlong),
+                ("max_iterations", C.c_int), ("min_used", C.c_int), ("lambda0", C.c_double), ("eps", C.c_double)]
+
+
+class TsdfAlignSums(C.Structure):                         # nalo_tsdf_align_sums
+    _fields_ = [("H", C.c_double * 28), ("b", C.c_double * 7), ("E", C.c_double), ("rr", C.c_double), ("count", C.c_longlong * 4)]
+
+
+class TsdfAlignTrace(C.Structure):                        # nalo_tsdf_align_trace
+    _fields_ = [("est", TsdfAlignEst), ("lambda_", C.c_double), ("E", C.c_double), ("count", C.c_longlong * 4), ("accepted", C.c_int)]
+
+
+class TsdfAlignResult(C.Structure):                       # nalo_tsdf_align_result
+    _fields_ = [("est", TsdfAlignEst), ("status", C.c_int), ("iterations", C.c_int), ("evaluations", C.c_int), ("E_first", C.c_double), ("E_last", C.c_double),
+                ("n_first", C.c_longlong), ("n_last", C.c_longlong), ("last", TsdfAlignSums), ("trace", C.POINTER(TsdfAlignTrace)), ("trace_cap", C.c_int),
+                ("n_trace", C.c_int)]
+
+
+ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW, ALIGN_SOLVE_FAILED = 0, 1, 2, 3      # NALO_TSDF_ALIGN_*
+ALIGN_MAX_EVALUATIONS = 65                               # the first evaluation and one per iteration, at most 64 of them
+
+
 class TsdfGeometry(C.Structure):                          # struct nalo_tsdf_geometry
     _fields_ = [("desc", TsdfDesc), ("origin0", C.c_float * 3), ("base", C.c_int * 3)]
 
@@ -361,6 +390,7 @@ def host_lib():
         L.nalo_tsdf_mesh_table.argtypes = [C.c_void_p]
         L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
         L.nalo_tsdf_shift_for.argtypes = [C.POINTER(TsdfDesc), c_dp, c_ip, c_ip]
+        L.nalo_tsdf_align_step.argtypes = [c_dp, c_dp, C.c_double, C.c_int, C.POINTER(TsdfAlignEst), c_dp, C.POINTER(TsdfAlignEst)]
         L.nalo_tsdf_shift_boxes.argtypes = [c_ip, c_ip, C.POINTER(TsdfShiftBoxes)]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
@@ -443,6 +473,38 @@ def tsdf_raycast_steps(min_depth, max_depth, step):
     if rc != 0:
         raise NaloError("nalo_tsdf_raycast_steps: bad argument (%d)" % rc)
     return int(n[0])
+
+
+def tsdf_align_est(cam_to_world, s=1.0):
+    """nalo_tsdf_align_est (a TsdfAlignEst): camToWorld [3][4] and the scale"""
+    e = TsdfAlignEst()
+    m = np.asarray(cam_to_world, np.float64).reshape(-1)
+    if m.size != 12:
+        raise NaloError("tsdf_align_est: camToWorld is 3 x 4")
+    e.camToWorld[:] = [float(v) for v in m]
+    e.s = float(s)
+    return e
+
+
+def _align_sums(S):
+    return dict(H=np.array(S.H[:], np.float64), b=np.array(S.b[:], np.float64), E=float(S.E), rr=float(S.rr), count=tuple(int(v) for v in S.count))
+
+
+def _align_est(e):
+    return np.array(e.camToWorld[:], np.float64).reshape(3, 4), float(e.s)
+
+
+def tsdf_align_step(H, b, lam, dof, cam_to_world, s=1.0):
+    """nalo_tsdf_align_step: one Levenberg-Marquardt step in fp64 -> (inc float64 [7], camToWorld [3][4], s). H is the 28 entries of the upper triangle, row-major.
+    NaloError for a system that is not finite or not positive definite. Needs no device"""
+    Hh, bb = np.ascontiguousarray(H, np.float64).reshape(-1), np.ascontiguousarray(b, np.float64).reshape(-1)
+    if Hh.size != 28 or bb.size != 7:
+        raise NaloError("tsdf_align_step: H holds 28 entries, b 7")
+    e, out, inc = tsdf_align_est(cam_to_world, s), TsdfAlignEst(), np.zeros(7, np.float64)
+    rc = host_lib().nalo_tsdf_align_step(_d(Hh), _d(bb), C.c_double(lam), int(dof), C.byref(e), _d(inc), C.byref(out))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_align_step: refused (%d)" % rc)
+    return (inc,) + _align_est(out)
 
 
 def tsdf_shift_for(desc, centre, margin=(0, 0, 0)):
@@ -673,6 +735,10 @@ def load():
     L.nalo_tsdf_raycast.argtypes = [vp, C.POINTER(TsdfRaycastArgs)]
     L.nalo_tsdf_raycast_view.argtypes = [vp, C.POINTER(TsdfRaycastDev)]
     L.nalo_tsdf_raycast_steps.argtypes = [C.c_float, C.c_float, C.c_float, c_ip]
+    L.nalo_tsdf_align_eval.argtypes = [vp, C.POINTER(TsdfAlignArgs), C.POINTER(TsdfAlignEst), C.POINTER(TsdfAlignSums)]
+    L.nalo_tsdf_align_depth.argtypes = [vp, C.POINTER(TsdfAlignArgs), C.POINTER(TsdfAlignEst), C.POINTER(TsdfAlignResult)]
+    L.nalo_tsdf_align_frame.argtypes = [vp, C.c_int, C.POINTER(TsdfAlignArgs), C.POINTER(TsdfAlignEst), C.POINTER(TsdfAlignResult)]
+    L.nalo_tsdf_align_step.argtypes = [c_dp, c_dp, C.c_double, C.c_int, C.POINTER(TsdfAlignEst), c_dp, C.POINTER(TsdfAlignEst)]
     L.nalo_tsdf_shift.argtypes = [vp, c_ip]
     L.nalo_tsdf_geometry.argtypes = [vp, C.POINTER(TsdfGeometry)]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
@@ -1949,6 +2015,80 @@ class Context:
         return dict(depth=DeviceView(v.depth.ptr, (v.h, v.w), "<f4", None, v.stream, self),
                     normal=DeviceView(v.normal.ptr, (v.h, v.w, 3), "<f4", None, v.stream, self) if v.normal.ptr else None,
                     rgba=DeviceView(v.rgba.ptr, (v.h, v.w, 4), "|u1", None, v.stream, self) if v.rgba.ptr else None)
+
+    # ---- the alignment (nalo_tsdf_align_*)
+    def _align_args(self, depth, K, min_depth, max_depth, min_weight, huber, step, dof, stream, records, max_iterations=1, min_used=1, lambda0=0.0, eps=0.0):
+        a = TsdfAlignArgs()
+        if depth is not None:
+            a.depth = depth if isinstance(depth, DevPlane) else dev_plane(depth)
+        if stream is None:
+            stream = 0
+            torch = sys.modules.get("torch")
+            if isinstance(depth, DeviceView):
+                stream = depth.stream
+            elif torch is not None and isinstance(depth, torch.Tensor):
+                stream = torch.cuda.current_stream(depth.device).cuda_stream
+        a.K[:] = [float(v) for v in K]
+        a.min_depth, a.max_depth, a.min_weight, a.huber = float(min_depth), float(max_depth), float(min_weight), float(huber)
+        a.step, a.dof, a.producer_stream = int(step), int(dof), stream or None
+        if records is not None:
+            cai = records.__cuda_array_interface__
+            if cai["typestr"] != "<f4" or cai.get("strides") is not None:
+                raise NaloError("tsdf_align: records is a contiguous float32 device array")
+            a.records, a.records_cap = int(cai["data"][0]) or None, int(np.prod(cai["shape"]))
+        a.max_iterations, a.min_used, a.lambda0, a.eps = int(max_iterations), int(min_used), float(lambda0), float(eps)
+        return a, stream
+
+    def tsdf_align_eval(self, depth, K, cam_to_world, s=1.0, min_depth=0.0, max_depth=1e30, min_weight=1.0, huber=1.0, step=1, dof=6, stream=None, release=True, records=None):
+        """nalo_tsdf_align_eval -> dict(H float64 [28] (upper triangle, row-major), b [7], E, rr, count (used, no depth, no field, no gradient)): one evaluation of
+        the depth plane (as tsdf_integrate_depth takes it, K for ITS size) against the volume at the estimate (camToWorld, s). records: a contiguous float32
+        device array of at least h w 10 elements, written at visited pixels as [h][w][10] = r, hw, J0..J6, state. One launch, one wait.
+        self.tsdf_align_counts holds the counts of the last call, a refusal included"""
+        a, stream = self._align_args(depth, K, min_depth, max_depth, min_weight, huber, step, dof, stream, records)
+        e, S = tsdf_align_est(cam_to_world, s), TsdfAlignSums()
+        rc = self.L.nalo_tsdf_align_eval(self.h_, C.byref(a), C.byref(e), C.byref(S))
+        self.tsdf_align_counts = tuple(int(v) for v in S.count)
+        self._ck(rc)
+        if release:
+            self.tsdf_release(stream)
+        return _align_sums(S)
+
+    def _align_result(self, rc, r, trace):
+        self.tsdf_align_counts = (int(r.iterations), int(r.evaluations), int(r.n_first), int(r.n_last), int(r.n_trace))
+        self._ck(rc)
+        T, s = _align_est(r.est)
+        tr = []
+        for t in trace[:r.n_trace]:
+            Tt, st = _align_est(t.est)
+            tr.append(dict(cam_to_world=Tt, s=st, lam=float(t.lambda_), E=float(t.E), count=tuple(int(v) for v in t.count), accepted=bool(t.accepted)))
+        return dict(cam_to_world=T, s=s, status=int(r.status), iterations=int(r.iterations), evaluations=int(r.evaluations), E_first=float(r.E_first), E_last=float(r.E_last),
+                    n_first=int(r.n_first), n_last=int(r.n_last), last=_align_sums(r.last), trace=tr)
+
+    def tsdf_align_depth(self, depth, K, cam_to_world, s=1.0, min_depth=0.0, max_depth=1e30, min_weight=1.0, huber=1.0, step=1, dof=6, max_iterations=12, min_used=1,
+                         lambda0=0.0, eps=1e-6, trace_cap=ALIGN_MAX_EVALUATIONS, stream=None, release=True, records=None):
+        """nalo_tsdf_align_depth -> dict(cam_to_world [3][4], s, status (ALIGN_*), iterations, evaluations, E_first, E_last, n_first, n_last, last (the sums at
+        the answer), trace: one dict(cam_to_world, s, lam, E, count, accepted) per evaluation, at most trace_cap): the Levenberg-Marquardt alignment of the depth
+        plane against the volume from the start (cam_to_world, s). One launch and one wait per evaluation.
+        self.tsdf_align_counts holds (iterations, evaluations, n_first, n_last, n_trace) of the last call, a refusal included"""
+        a, stream = self._align_args(depth, K, min_depth, max_depth, min_weight, huber, step, dof, stream, records, max_iterations, min_used, lambda0, eps)
+        e, r = tsdf_align_est(cam_to_world, s), TsdfAlignResult()
+        trace = (TsdfAlignTrace * max(int(trace_cap), 1))()
+        r.trace, r.trace_cap = trace, int(trace_cap)
+        rc = self.L.nalo_tsdf_align_depth(self.h_, C.byref(a), C.byref(e), C.byref(r))
+        out = self._align_result(rc, r, trace)
+        if release:
+            self.tsdf_release(stream)
+        return out
+
+    def tsdf_align_frame(self, frame_id, K, cam_to_world, s=1.0, min_depth=0.0, max_depth=1e30, min_weight=1.0, huber=1.0, step=1, dof=6, max_iterations=12, min_used=1,
+                         lambda0=0.0, eps=1e-6, trace_cap=ALIGN_MAX_EVALUATIONS):
+        """nalo_tsdf_align_frame: tsdf_align_depth on the plane tsdf_integrate_frame would integrate (the frame's dense list, K for the context's size)"""
+        a, _ = self._align_args(None, K, min_depth, max_depth, min_weight, huber, step, dof, 0, None, max_iterations, min_used, lambda0, eps)
+        e, r = tsdf_align_est(cam_to_world, s), TsdfAlignResult()
+        trace = (TsdfAlignTrace * max(int(trace_cap), 1))()
+        r.trace, r.trace_cap = trace, int(trace_cap)
+        rc = self.L.nalo_tsdf_align_frame(self.h_, int(frame_id), C.byref(a), C.byref(e), C.byref(r))
+        return self._align_result(rc, r, trace)
 
     # ---- the mesh archive (nalo_tsdf_archive_*)
     @staticmethod

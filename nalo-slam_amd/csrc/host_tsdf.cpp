@@ -3,6 +3,7 @@
 // line below is the operation order the header defines, in double (the shifted origin: in float).
 #include <cmath>
 
+#include "host_math.h"
 #include "tsdf_host.h"
 #include "tsdf_mesh_table.h"
 
@@ -136,6 +137,53 @@ extern "C" int nalo_tsdf_mesh_table(signed char out[6][16][6]) {
     for (int t = 0; t < 6; ++t)
         for (int m = 0; m < 16; ++m)
             for (int k = 0; k < 6; ++k) out[t][m][k] = T.e[t][m][k];
+    return NALO_OK;
+}
+
+extern "C" int nalo_tsdf_align_step(const double H[28], const double b[7], double lambda, int dof, const nalo_tsdf_align_est* est, double inc[7], nalo_tsdf_align_est* est_out) {
+    if (!H || !b || !est || !inc || !est_out || (dof != 6 && dof != 7) || !std::isfinite(lambda) || lambda < 0.0) return NALO_ERR_ARG;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(est->camToWorld[i])) return NALO_ERR_ARG;
+    if (!std::isfinite(est->s) || est->s <= 0.0) return NALO_ERR_ARG;
+    // Hl = H with its diagonal scaled, the leading dof x dof block, from the row-major upper triangle; L L^T = Hl in place of its lower triangle
+    double L[7][7], x[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0, k = 0; i < 7; ++i)
+        for (int j = i; j < 7; ++j, ++k) {
+            if (j >= dof) continue;
+            const double h = i == j ? H[k] * (1.0 + lambda) : H[k];
+            if (!std::isfinite(h)) return NALO_ERR_ARG;
+            L[j][i] = h;
+        }
+    for (int i = 0; i < dof; ++i) if (!std::isfinite(b[i])) return NALO_ERR_ARG;
+    for (int j = 0; j < dof; ++j) {
+        double d = L[j][j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > 0.0) || !std::isfinite(d)) return NALO_ERR_ARG;              // not positive definite (a NaN fails the comparison)
+        const double l = std::sqrt(d);
+        L[j][j] = l;
+        for (int i = j + 1; i < dof; ++i) {
+            double s = L[i][j];
+            for (int k = 0; k < j; ++k) s -= L[i][k] * L[j][k];
+            L[i][j] = s / l;
+        }
+    }
+    for (int i = 0; i < dof; ++i) {                                            // L y = -b
+        double s = -b[i];
+        for (int k = 0; k < i; ++k) s -= L[i][k] * x[k];
+        x[i] = s / L[i][i];
+    }
+    for (int i = dof - 1; i >= 0; --i) {                                       // L^T x = y
+        double s = x[i];
+        for (int k = i + 1; k < dof; ++k) s -= L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    const nalo::SE3 T = nalo::se3_exp(x) * nalo::SE3::from(est->camToWorld);
+    const double s = est->s * std::exp(x[6]);
+    for (int i = 0; i < 7; ++i) if (!std::isfinite(x[i])) return NALO_ERR_ARG;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(T.m[i])) return NALO_ERR_ARG;
+    if (!std::isfinite(s) || s <= 0.0) return NALO_ERR_ARG;
+    for (int i = 0; i < 7; ++i) inc[i] = x[i];
+    for (int i = 0; i < 12; ++i) est_out->camToWorld[i] = T.m[i];
+    est_out->s = s;
     return NALO_OK;
 }
 

@@ -1,5 +1,5 @@
 // The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
-// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_mesh.hip and kernels_tsdf_raycast.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table).
+// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table, the alignment's step).
 #include <algorithm>
 #include <cmath>
 
@@ -34,7 +34,8 @@ struct TsdfVolume {
     // the last call wrote that image. Their pinned staging, and the three counts
     DevBuf<float> rc_depth, rc_normal; DevBuf<unsigned> rc_rgba; DevBuf<unsigned long long> rc_cnt;
     HostBuf<float> rc_depth_h, rc_normal_h; HostBuf<unsigned> rc_rgba_h; HostBuf<unsigned long long> rc_cnt_h;
-    int rc_w = 0, rc_h = 0; bool have_rc = false, rc_normal_on = false, rc_rgba_on = false;
+    int rc_w = 0, rc_h = 0; bool have_rc = false, rc_normal_on = false, rc_rgba_on = false;    // nalo_tsdf_align_*: the workgroups' partial records, the arrival ticket (zero between launches) and the mapped words an evaluation's sums come up in
+    DevBuf<double> al_partial; DevBuf<unsigned> al_ticket; HostBuf<double> al_out;
 };
 
 // The mesh archive (nalo_tsdf_archive_*): it hangs off the context, not the volume, and outlives volumes. xyz, rgba and key have room for cap_v vertices, tri for
@@ -295,6 +296,21 @@ int nalo_tsdf_release(nalo_ctx* c, void* stream) {
     return NALO_OK;
 }
 
+// the context-owned plane of a frame's dense list (the header's last-record rule) for nalo_tsdf_integrate_frame and nalo_tsdf_align_frame: v.plane, and
+// v.cplane on a coloured volume when `colour` is asked for. Its refusals are map_dense_segments'. Enqueues only.
+static int tsdf_frame_plane(nalo_ctx* c, const char* who, TsdfVolume& v, int frame_id, bool colour) {
+    NALO_HIP(c, hipSetDevice(c->device));
+    int total = 0;
+    { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }
+    const size_t npx = (size_t)c->w * c->h;
+    NALO_HIP(c, v.plane.reserve(npx));
+    if (colour) NALO_HIP(c, v.cplane.reserve(npx));                            // every call writes every word of it: a winner's colour, or zero behind the resolve
+    NALO_HIP(c, v.key.begin(npx, c->stream));
+    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, colour ? v.cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
+    v.key.settled();
+    return NALO_OK;
+}
+
 int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld[12], const float K[4], float min_depth, float max_depth) {
     const char* who = "nalo_tsdf_integrate_frame";
     { const int rc = tsdf_need(c, who); if (rc) return rc; }
@@ -303,17 +319,9 @@ int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld
     TsdfVolume& v = *c->tsdf;
     float M[12]; int lo[3], hi[3];
     { const int rc = tsdf_integrate_check(c, who, v, c->w, c->h, K, camToWorld, min_depth, max_depth, M, lo, hi); if (rc) return rc; }
-    NALO_HIP(c, hipSetDevice(c->device));
-    int total = 0;
-    { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }
-    const size_t npx = (size_t)c->w * c->h;
-    NALO_HIP(c, v.plane.reserve(npx));
     const bool coloured = v.colour.p != nullptr;
-    if (coloured) NALO_HIP(c, v.cplane.reserve(npx));                          // every call writes every word of it: a winner's colour, or zero behind the resolve
     HostTimer ht(c, "tsdf_integrate_frame");
-    NALO_HIP(c, v.key.begin(npx, c->stream));
-    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, coloured ? v.cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
-    v.key.settled();
+    { const int rc = tsdf_frame_plane(c, who, v, frame_id, coloured); if (rc) return rc; }
     // the packed plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
     const TsdfColourSrc src = {reinterpret_cast<const unsigned char*>(v.cplane.p), (long long)c->w * 4, 4, {0, 1, 2}};
     return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi, coloured ? &src : nullptr);
@@ -602,6 +610,172 @@ int nalo_tsdf_raycast_view(nalo_ctx* c, nalo_tsdf_raycast_dev* out) {
     out->w = v.rc_w; out->h = v.rc_h;
     out->stream = (void*)(hipStream_t)c->stream;
     return NALO_OK;
+}
+
+// ---- the alignment (nalo_tsdf_align_*)
+// the checks every alignment call makes of args and estimate behind the plane's own; NULL when good, else the reason
+static const char* tsdf_align_refusal(const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* e, int w, int h) {
+    if (a->step < 1) return "step < 1";
+    if (a->dof != 6 && a->dof != 7) return "dof is 6 or 7";
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(e->camToWorld[i])) return "camToWorld is not finite";
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(a->K[i])) return "K is not finite";
+    if (!std::isfinite(e->s) || e->s <= 0.0) return "s is not finite or <= 0";
+    if (!std::isfinite(a->huber) || a->huber <= 0.0f) return "huber is not finite or <= 0";
+    if (!std::isfinite(a->min_depth) || !std::isfinite(a->max_depth) || a->min_depth > a->max_depth) return "min_depth / max_depth not finite, or min_depth > max_depth";
+    if (std::isnan(a->min_weight)) return "min_weight is NaN";
+    if (a->records && a->records_cap < (long long)w * h * 10) return "records_cap is below h w 10";
+    return nullptr;
+}
+static const char* tsdf_align_loop_refusal(const nalo_tsdf_align_args* a, const nalo_tsdf_align_result* r) {
+    if (a->max_iterations < 1 || a->max_iterations > 64) return "max_iterations outside 1..64";
+    if (!std::isfinite(a->lambda0) || a->lambda0 < 0.0 || !std::isfinite(a->eps) || a->eps < 0.0) return "lambda0 or eps is negative or not finite";
+    if (r->trace_cap < 0 || (r->trace_cap > 0 && !r->trace)) return "a negative trace_cap, or a trace_cap without a trace";
+    return nullptr;
+}
+static void tsdf_align_zero(nalo_tsdf_align_result* r) { r->iterations = r->evaluations = r->n_trace = 0; r->n_first = r->n_last = 0; }
+
+// one plane as the kernel reads it
+struct TsdfAlignPlane { const char* p; long long sy, sx; int w, h; };
+
+// everything is validated: one launch, one wait, the sums. The scratch is sized here, before anything is queued
+static int tsdf_align_evaluate(nalo_ctx* c, TsdfVolume& v, const TsdfAlignPlane& pl, const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* e, nalo_tsdf_align_sums* out) {
+    TsdfAlignDev D{};
+    D.g = tsdf_grid(v, false);
+    D.min_weight = a->min_weight;
+    for (int k = 0; k < 3; ++k) {
+        for (int j = 0; j < 3; ++j) D.M[4 * k + j] = (float)(e->s * e->camToWorld[4 * k + j]);
+        D.M[4 * k + 3] = (float)e->camToWorld[4 * k + 3];
+    }
+    D.fx = a->K[0]; D.fy = a->K[1]; D.cx = a->K[2]; D.cy = a->K[3];
+    D.min_depth = a->min_depth; D.max_depth = a->max_depth; D.huber = a->huber; D.step = a->step; D.dof = a->dof;
+    D.depth = pl.p; D.sy = pl.sy; D.sx = pl.sx; D.w = pl.w; D.h = pl.h;
+    D.vw = (int)(((long long)pl.w + a->step - 1) / a->step); D.vh = (int)(((long long)pl.h + a->step - 1) / a->step);
+    D.records = a->records;
+    const size_t nb = (size_t)tsdf_align_blocks(D.vw, D.vh);
+    NALO_HIP(c, v.al_partial.reserve(nb * kTsdfAlignStride));
+    if (!v.al_ticket.p) { NALO_HIP(c, v.al_ticket.reserve(4)); NALO_HIP(c, hipMemsetAsync(v.al_ticket.p, 0, 16, c->stream)); }
+    NALO_HIP(c, v.al_out.reserve(48, hipHostMallocMapped));
+    D.partial = v.al_partial.p; D.ticket = v.al_ticket.p; D.out = v.al_out.dev;
+    { const int rc = tsdf_align_launch(c, D); if (rc) return rc; }
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    const double* o = v.al_out.p;
+    std::copy(o, o + 28, out->H); std::copy(o + 28, o + 35, out->b); out->E = o[35]; out->rr = o[36];
+    long long total = 0;
+    for (int k = 0; k < 4; ++k) { out->count[k] = (long long)reinterpret_cast<const unsigned long long*>(o)[kTsdfAlignSums + k]; total += out->count[k]; }
+    if (total != (long long)D.vw * D.vh) return fail(c, NALO_ERR_HIP, "nalo_tsdf_align: the device's state counts do not add up to the visited pixels");
+    return NALO_OK;
+}
+
+// the Levenberg-Marquardt loop of the header over tsdf_align_evaluate; everything is validated
+static int tsdf_align_loop(nalo_ctx* c, TsdfVolume& v, const TsdfAlignPlane& pl, const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* r) {
+    const long long need = std::max(a->min_used, 1);
+    auto trace = [&](const nalo_tsdf_align_est& e, double lambda, const nalo_tsdf_align_sums& s, int accepted) {
+        if (r->evaluations < r->trace_cap) {
+            nalo_tsdf_align_trace& t = r->trace[r->evaluations];
+            t.est = e; t.lambda = lambda; t.E = s.E; std::copy(s.count, s.count + 4, t.count); t.accepted = accepted;
+            r->n_trace = r->evaluations + 1;
+        }
+        ++r->evaluations;
+    };
+    tsdf_align_zero(r);
+    nalo_tsdf_align_est cur = *est_in;
+    nalo_tsdf_align_sums S{};
+    double lambda = a->lambda0 == 0.0 ? 0.01 : a->lambda0;
+    { const int rc = tsdf_align_evaluate(c, v, pl, a, &cur, &S); if (rc) return rc; }
+    trace(cur, lambda, S, 1);
+    r->E_first = S.E; r->n_first = S.count[0];
+    r->status = NALO_TSDF_ALIGN_ITERATION_LIMIT;
+    if (S.count[0] < need) r->status = NALO_TSDF_ALIGN_TOO_FEW;
+    else
+        for (int it = 0; it < a->max_iterations; ++it) {
+            double inc[7]; nalo_tsdf_align_est cand; nalo_tsdf_align_sums Sn{};
+            if (nalo_tsdf_align_step(S.H, S.b, lambda, a->dof, &cur, inc, &cand) != NALO_OK) { r->status = NALO_TSDF_ALIGN_SOLVE_FAILED; break; }
+            ++r->iterations;
+            { const int rc = tsdf_align_evaluate(c, v, pl, a, &cand, &Sn); if (rc) return rc; }
+            const bool ok = Sn.count[0] >= need && Sn.E / (double)Sn.count[0] < S.E / (double)S.count[0];
+            trace(cand, lambda, Sn, ok ? 1 : 0);
+            if (ok) { cur = cand; S = Sn; lambda *= 0.5; } else lambda *= 4.0;
+            double n2 = 0.0;
+            for (int i = 0; i < 7; ++i) n2 += inc[i] * inc[i];
+            if (std::sqrt(n2) <= a->eps) { r->status = NALO_TSDF_ALIGN_CONVERGED; break; }
+        }
+    r->est = cur; r->last = S; r->E_last = S.E; r->n_last = S.count[0];
+    return NALO_OK;
+}
+
+// the caller's plane, checked as nalo_tsdf_integrate_depth checks its own
+static int tsdf_align_plane(nalo_ctx* c, const char* who, const nalo_dev_plane* d, TsdfAlignPlane* pl) {
+    { const int rc = nalo_dev_plane_check(c, d); if (rc) return rc; }
+    if (d->dtype != NALO_DT_F32 || d->channels != 1) return fail(c, NALO_ERR_ARG, std::string(who) + ": the depth plane is one channel of F32");
+    *pl = TsdfAlignPlane{static_cast<const char*>(d->ptr), d->stride_y, d->stride_x, d->w, d->h};
+    return NALO_OK;
+}
+// the main stream behind the plane's producer, as nalo_tsdf_integrate_depth; tsdf_align_read behind the last kernel that reads the plane
+static int tsdf_align_order(nalo_ctx* c, void* producer) {
+    hipStream_t prod = (hipStream_t)producer;
+    NALO_HIP(c, c->ev_prod.create(hipEventDisableTiming));
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    return NALO_OK;
+}
+static int tsdf_align_read(nalo_ctx* c, TsdfVolume& v) {
+    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));
+    v.read_pending = true;
+    return NALO_OK;
+}
+
+int nalo_tsdf_align_eval(nalo_ctx* c, const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* est, nalo_tsdf_align_sums* out) {
+    const char* who = "nalo_tsdf_align_eval";
+    if (!c) return NALO_ERR_ARG;
+    if (out) std::fill(out->count, out->count + 4, 0LL);
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a || !est || !out) return fail(c, NALO_ERR_ARG, "nalo_tsdf_align_eval: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    TsdfAlignPlane pl;
+    { const int rc = tsdf_align_plane(c, who, &a->depth, &pl); if (rc) return rc; }
+    if (const char* why = tsdf_align_refusal(a, est, pl.w, pl.h)) return fail(c, NALO_ERR_ARG, std::string(who) + ": " + why);
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_align_eval");
+    { const int rc = tsdf_align_order(c, a->producer_stream); if (rc) return rc; }
+    nalo_tsdf_align_sums S{};
+    { const int rc = tsdf_align_evaluate(c, v, pl, a, est, &S); if (rc) return rc; }
+    *out = S;
+    return tsdf_align_read(c, v);
+}
+
+int nalo_tsdf_align_depth(nalo_ctx* c, const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* r) {
+    const char* who = "nalo_tsdf_align_depth";
+    if (!c) return NALO_ERR_ARG;
+    if (r) tsdf_align_zero(r);
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a || !est_in || !r) return fail(c, NALO_ERR_ARG, "nalo_tsdf_align_depth: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    TsdfAlignPlane pl;
+    { const int rc = tsdf_align_plane(c, who, &a->depth, &pl); if (rc) return rc; }
+    if (const char* why = tsdf_align_refusal(a, est_in, pl.w, pl.h)) return fail(c, NALO_ERR_ARG, std::string(who) + ": " + why);
+    if (const char* why = tsdf_align_loop_refusal(a, r)) return fail(c, NALO_ERR_ARG, std::string(who) + ": " + why);
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_align_depth");
+    { const int rc = tsdf_align_order(c, a->producer_stream); if (rc) return rc; }
+    { const int rc = tsdf_align_loop(c, v, pl, a, est_in, r); if (rc) return rc; }
+    return tsdf_align_read(c, v);
+}
+
+int nalo_tsdf_align_frame(nalo_ctx* c, int frame_id, const nalo_tsdf_align_args* a, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* r) {
+    const char* who = "nalo_tsdf_align_frame";
+    if (!c) return NALO_ERR_ARG;
+    if (r) tsdf_align_zero(r);
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!a || !est_in || !r) return fail(c, NALO_ERR_ARG, "nalo_tsdf_align_frame: bad argument");
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, "nalo_tsdf_align_frame: the dense archive is not enabled (nalo_map_dense_enable)");
+    TsdfVolume& v = *c->tsdf;
+    if (const char* why = tsdf_align_refusal(a, est_in, c->w, c->h)) return fail(c, NALO_ERR_ARG, std::string(who) + ": " + why);
+    if (const char* why = tsdf_align_loop_refusal(a, r)) return fail(c, NALO_ERR_ARG, std::string(who) + ": " + why);
+    HostTimer ht(c, "tsdf_align_frame");
+    { const int rc = tsdf_frame_plane(c, who, v, frame_id, false); if (rc) return rc; }
+    const TsdfAlignPlane pl = {reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h};
+    return tsdf_align_loop(c, v, pl, a, est_in, r);
 }
 
 // ---- the mesh archive

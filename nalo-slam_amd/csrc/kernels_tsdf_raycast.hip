@@ -9,31 +9,6 @@
 
 namespace nalo {
 
-// S(q) on `vol`. kWeights: the field of the march and of the normal, VALID only with eight valid corners; without it the colour planes' plain index test.
-// Every conversion to int sits behind the float comparisons (a NaN or an infinity fails them), and the linear index is 64-bit: 2^29 voxels of 4 B.
-template <bool kWeights>
-__device__ __forceinline__ bool tsdf_rc_field(const TsdfRaycastDev& P, const float* __restrict__ vol, float qx, float qy, float qz, float& S) {
-    const float ix = floorf(qx), iy = floorf(qy), iz = floorf(qz);
-    if (!(ix >= 0.0f && ix <= (float)(P.g.nx - 2) && iy >= 0.0f && iy <= (float)(P.g.ny - 2) && iz >= 0.0f && iz <= (float)(P.g.nz - 2))) return false;
-    const float fx = qx - ix, fy = qy - iy, fz = qz - iz;
-    const long long sy = P.g.nx, sz = (long long)P.g.nx * P.g.ny;
-    // tsdf_index of the cell, written out: each conversion sits where the sum takes it up, and the compiler's order of this kernel's instructions follows that
-    const long long at = ((long long)(int)iz * P.g.ny + (long long)(int)iy) * P.g.nx + (long long)(int)ix;   // corner (1, 1, 1) is at most voxel (nx - 1, ny - 1, nz - 1)
-    if constexpr (kWeights) {
-        const float* w = P.g.weight + at;
-        const float mw = P.min_weight;
-        const bool ok = (w[0] >= mw) & (w[1] >= mw) & (w[sy] >= mw) & (w[sy + 1] >= mw) & (w[sz] >= mw) & (w[sz + 1] >= mw) & (w[sz + sy] >= mw) & (w[sz + sy + 1] >= mw);
-        if (!ok) return false;
-    }
-    const float* t = vol + at;
-    const float t000 = t[0], t001 = t[1], t010 = t[sy], t011 = t[sy + 1], t100 = t[sz], t101 = t[sz + 1], t110 = t[sz + sy], t111 = t[sz + sy + 1];   // t_zyx
-    const float a00 = t000 + fx * (t001 - t000), a10 = t010 + fx * (t011 - t010), a01 = t100 + fx * (t101 - t100), a11 = t110 + fx * (t111 - t110);   // a_yz
-    const float b0 = a00 + fy * (a10 - a00), b1 = a01 + fy * (a11 - a01);
-    S = b0 + fz * (b1 - b0);
-    if constexpr (kWeights) return S == S;            // a NaN corner reaches S through every path (0 * NaN is NaN), and so does inf - inf
-    return true;
-}
-
 // the grid coordinate of the point at camera-z `z` on the ray
 __device__ __forceinline__ void tsdf_rc_point(const TsdfRaycastDev& P, const float d[3], float z, float q[3]) {
 #pragma unroll
@@ -94,7 +69,7 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
             const float z = P.min_depth + (float)n * P.step;
             float q[3], S = 0.0f;
             tsdf_rc_point(P, d, z, q);
-            const bool ok = tsdf_rc_field<true>(P, P.g.tsdf, q[0], q[1], q[2], S);
+            const bool ok = tsdf_rc_field<true>(P.g, P.min_weight, P.g.tsdf, q[0], q[1], q[2], S);
             if (ok && pv && ((ps < 0.0f) != (S < 0.0f))) {
                 if (!(ps < 0.0f)) {                                            // outside to inside: the front face (-0.0f is outside)
                     hit = 1;
@@ -119,7 +94,7 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
             for (int a = 0; a < 3; ++a) {
                 float qp[3] = {q[0], q[1], q[2]}, qm[3] = {q[0], q[1], q[2]}, sp = 0.0f, sm = 0.0f;
                 qp[a] = q[a] + 1.0f; qm[a] = q[a] - 1.0f;
-                const bool okp = tsdf_rc_field<true>(P, P.g.tsdf, qp[0], qp[1], qp[2], sp), okm = tsdf_rc_field<true>(P, P.g.tsdf, qm[0], qm[1], qm[2], sm);
+                const bool okp = tsdf_rc_field<true>(P.g, P.min_weight, P.g.tsdf, qp[0], qp[1], qp[2], sp), okm = tsdf_rc_field<true>(P.g, P.min_weight, P.g.tsdf, qm[0], qm[1], qm[2], sm);
                 all = all && okp && okm;
                 G[a] = sp - sm;
             }
@@ -132,9 +107,9 @@ __global__ __launch_bounds__(256) void tsdf_raycast_kernel(TsdfRaycastDev P, int
         if constexpr (kColour) {
             float cb = 0.0f, cg = 0.0f, cr = 0.0f;
             rgba = 0xFF000000u;                                                // the index test fails at q*: 0, 0, 0, 255
-            if (tsdf_rc_field<false>(P, P.g.col, q[0], q[1], q[2], cb)) {
-                (void)tsdf_rc_field<false>(P, P.g.col + P.g.col_plane, q[0], q[1], q[2], cg);
-                (void)tsdf_rc_field<false>(P, P.g.col + 2 * P.g.col_plane, q[0], q[1], q[2], cr);
+            if (tsdf_rc_field<false>(P.g, P.min_weight, P.g.col, q[0], q[1], q[2], cb)) {
+                (void)tsdf_rc_field<false>(P.g, P.min_weight, P.g.col + P.g.col_plane, q[0], q[1], q[2], cg);
+                (void)tsdf_rc_field<false>(P.g, P.min_weight, P.g.col + 2 * P.g.col_plane, q[0], q[1], q[2], cr);
                 rgba = tsdf_colour_byte(cr) | (tsdf_colour_byte(cg) << 8) | (tsdf_colour_byte(cb) << 16) | 0xFF000000u;
             }
         }

@@ -547,6 +547,23 @@ struct TsdfRaycastDev {
     unsigned long long* cnt;                                                    // n_hit, n_back, n_normal: zero before
 };
 int tsdf_raycast_launch(nalo_ctx* c, const TsdfRaycastDev& D);
+// nalo_tsdf_align_eval (kernels_tsdf_align.hip, built without FMA contraction): one lane per visited pixel, an 8 x 8 tile of them to a wave. It reads volume and
+// plane and writes only what is named here. The sums: H's upper triangle row-major (28), b (7), E, sum r r.
+constexpr int kTsdfAlignSums = 37, kTsdfAlignStride = 40;                       // a workgroup's partial record: 37 doubles and two words of counts, padded to 320 B
+struct TsdfAlignDev {
+    TsdfGridDev g;                                                              // read only
+    float min_weight;
+    float M[12], fx, fy, cx, cy;                                                // [s R | t] rounded to float, rows of four; K of the plane
+    float min_depth, max_depth, huber; int step, dof;
+    const char* depth; long long sy, sx; int w, h;                              // the plane by byte strides
+    int vw, vh;                                                                 // visited pixels per row and column: ceil(w / step), ceil(h / step)
+    float* records;                                                             // NULL, or [h][w][10]: written at visited pixels only
+    double* partial;                                                            // [workgroups][kTsdfAlignStride]: the 37 sums, then the four counts in two words
+    unsigned* ticket;                                                           // zero between launches
+    double* out;                                                                // host-mapped: 37 doubles, then the four counts as 64-bit integers
+};
+int tsdf_align_launch(nalo_ctx* c, const TsdfAlignDev& D);
+long long tsdf_align_blocks(int vw, int vh);                                    // the workgroups tsdf_align_launch starts
 void tsdf_destroy(nalo_ctx* c);
 // nalo_tsdf_archive_* (kernels_tsdf_archive.hip): the welded mesh archive. Integers and words only: nothing here depends on the contraction policy. A vertex's key is
 // (gx, gy, gz, m) as one int4; the table is open-addressed with linear probing, 32-bit slots that hold an archived vertex index or kTsdfArchiveEmpty, a power of
