@@ -1581,7 +1581,7 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  * tsdf=1: the dense map fused into a TSDF volume on the device. The reference constructs a cpu_tsdf::TSDFVolumeOctree (FullSystem.cpp:192-198), saves a point
  * file "for tsdf" (SampleOutputWrapper.h:150-176, nalo_map_dense_world_points here) and leaves the fusion to a third-party tool it neither vendors nor pins. This
  * section is a DEFINED operation instead: a projective integration of one depth image into a dense voxel volume that lives in the context. Colour is opt-in
- * ("Colour" below; the reference's switch is tsdf->setIntegrateColor, FullSystem.cpp:195). No octree, no de-integration; a volume that follows the camera: nalo_tsdf_shift; nalo_ba_snapshot / nalo_ba_restore do
+ * ("Colour" below; the reference's switch is tsdf->setIntegrateColor, FullSystem.cpp:195). No octree; taking a fused plane back, or fusing at a corrected pose and scale: "The replacement" below; a volume that follows the camera: nalo_tsdf_shift; nalo_ba_snapshot / nalo_ba_restore do
  * not include the volume.
  *
  * nalo_tsdf_create   origin: world position of the CORNER of voxel (0,0,0); dims = {nx, ny, nz}. Storage: two contiguous F32 arrays [nz][ny][nx], x fastest;
@@ -1882,6 +1882,72 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *     non-finite pose, K, s or threshold (min_depth, max_depth, huber); s <= 0; huber <= 0; min_depth > max_depth; a NaN min_weight; records given with
  *     records_cap < h w 10; and for the loop max_iterations outside 1..64, a lambda0 or eps that is negative or not finite, a negative trace_cap, trace_cap > 0
  *     with a NULL trace.
+ *
+ * The replacement. A keyframe is fused with the pose and depth it has when it is made; the window then moves its pose (nalo_ba_optimize), the scale fix rescales
+ * it (nalo_ba_plane_scale_fix), and nalo_tsdf_align_depth with dof = 7 returns an estimate (R, t, s) the plain integration cannot take. This is the DEFINED
+ * removal of one plane's contribution and its fusion again at another estimate, without nalo_tsdf_reset and a second fusion of every frame.
+ * A side (nalo_tsdf_side) is a depth plane, optionally a colour plane (ptr NULL: none), K for that size, an estimate est = (camToWorld, s) and a depth range.
+ *     With Rt = R^T and s = est.s, M in double: M_aj = Rt[a][j] / s, M_a3 = -(((Rt_a0 t0 + Rt_a1 t1) + Rt_a2 t2)) / s; every entry then rounded to float
+ *     (nalo_tsdf_est_world_to_cam). For s == 1 this is nalo_tsdf_integrate_depth's M bit for bit: a quotient by 1.0 is exact.
+ *     The per-voxel predicate is nalo_tsdf_integrate_depth's, word for word, up to sdf (one device function serves both kernels). Then sdf = (D - zc) * (float)s;
+ *     the voxel is skipped when sdf < -trunc; d = fminf(1.0f, sdf / trunc). For s == 1 the product is exact: an add at s == 1 IS nalo_tsdf_integrate_depth
+ *     (nalo_tsdf_integrate_depth_color with a colour plane), bit for bit, nalo_tsdf_last included.
+ *   Add, at a voxel the side's predicate accepts: as the integration. tsdf = (t0 * w0 + d) / (w0 + 1.0f); weight = fminf(w0 + 1.0f, max_weight); with a colour plane
+ *     X = (X0 * w0 + (float)x) / (w0 + 1.0f) for the three planes.
+ *   Remove, at a voxel the side's predicate accepts, with w1 = w0 - 1.0f: if !(w1 > 0.0f) - w0 <= 1, a NaN weight, a voxel never seen - tsdf = 1.0f, weight = 0.0f
+ *     and, on a side with a colour plane, the three colour words 0.0f: the initial values ("reset"). Else tsdf = (t0 * w0 - d) / w1; weight = w1; colour
+ *     X = (X0 * w0 - (float)x) / w1.
+ *     What this is: the exact algebraic inverse of the add while the voxel's weight never reached max_weight; in floats an inverse up to rounding (three
+ *     roundings: |error| <= 3 * 2^-24 * (|t0| w0 + |d|) / w1 to first order), and exact again when the last contribution goes (the reset). What it is not: on
+ *     a voxel whose weight sat at max_weight the running mean has forgotten how many planes it holds, and the removal is a defined approximation. A caller who
+ *     wants faithful removal gives max_weight room. Nor is it tied to the voxels the add touched: it is the side's predicate evaluated on the grid AS IT IS
+ *     NOW. Behind a nalo_tsdf_shift the origin is origin0 + (float)base * voxel_size, rounded anew, so a voxel's centre can differ in its last bit from the one
+ *     the frame was fused with, and at the rim of the frustum or of the truncation band the predicate can come out the other way: a voxel removed that was
+ *     not added, or one left with its contribution. The operation stays defined (it is what the model computes on the shifted geometry); it is exact bookkeeping
+ *     only between shifts.
+ *   Replace: remove on side `remove`, then add on side `add`, per voxel, in that order - DEFINED as the two operations one after the other, computed in one
+ *     launch over the hull of the two sides' culling boxes, every voxel loaded and stored at most once. Either side may be NULL: remove only is the de-integration,
+ *     add only the integration at an estimate. use_box: the REMOVE side applies only to voxels of [lo, lo + size); the add side always sees the whole grid. A
+ *     side with a colour plane moves colour and needs a coloured volume; a side without one leaves the colour words alone, as nalo_tsdf_integrate_depth does.
+ *     No float atomic, one lane owns a voxel: the same bytes on every run.
+ * nalo_tsdf_replace_depth   stream order as nalo_tsdf_integrate_depth: the main stream waits on the device for producer_stream, an event is recorded behind the
+ *     kernel, nalo_tsdf_release applies; with the volume allocated the call makes no host wait. Afterwards nalo_tsdf_last reports the hull box, visited = its voxel
+ *     count and updated = the voxels written. Refusals queue nothing and leave volume, colour and nalo_tsdf_last as they were: NALO_ERR_ARG for both sides NULL,
+ *     anything nalo_tsdf_integrate_depth[_color] refuses about a plane, K, range or pose, an s that is not finite or <= 0, a box that is empty or leaves the grid;
+ *     NALO_ERR_STATE for a colour plane on an uncoloured volume (and without a volume).
+ * nalo_tsdf_replace_last    waits once: the hull box, visited, and the voxels removed, reset (removed and back at the initial values), added and written (either).
+ *     Integer sums: a wave reduction, then one atomic instruction per workgroup. NALO_ERR_STATE when the last operation on the volume was not a replacement.
+ * The fusion log: so that a fused frame can be replaced with its frame_id and the new estimate alone. The plane of a fused frame is rebuilt from the dense
+ *     archive (nalo_tsdf_integrate_frame's plane), so nothing per frame is kept on the device; an entry (nalo_tsdf_log_entry) is host memory: frame_id, n_records
+ *     (the length of the frame's dense list that was fused), the estimate, K and range it was fused with, whether that fusion moved colour, and the RESIDENT BOX [lo, lo + size): the voxels that
+ *     have held this frame's contribution without a break since it was fused. The log belongs to the context and is OFF by default; while it is off nothing in
+ *     the library behaves differently. nalo_tsdf_log_enable(ctx, on) and nalo_tsdf_log_get(ctx, out, cap, n) are host only and launch nothing (n: the entries
+ *     there are; min(n, cap) are copied, in the order the frames were first fused; out may be NULL with cap 0). With the log on:
+ *       nalo_tsdf_integrate_frame of a frame without an entry adds one (s = 1, box = the whole grid), the volume's bytes exactly as without the log; of a
+ *       frame that has an entry it returns NALO_ERR_STATE (use the replacement) and does nothing.
+ *       A non-zero nalo_tsdf_shift, the one inside nalo_tsdf_follow too, maps every entry's box through nalo_tsdf_box_shift and drops the entries whose box is
+ *       empty: the voxels a shift brings in are fresh, and a later removal must not touch what other frames fused into them.
+ *       nalo_tsdf_reset, nalo_tsdf_create, nalo_tsdf_destroy and nalo_tsdf_log_enable(ctx, 0) clear the log. nalo_tsdf_set, nalo_tsdf_color_set,
+ *       nalo_tsdf_integrate_depth[_color], nalo_tsdf_replace_depth and nalo_ba_snapshot / nalo_ba_restore do not touch it: what a caller writes into the volume
+ *       by those is the caller's to keep track of.
+ * nalo_tsdf_replace_frame   DEFINED as nalo_tsdf_replace_depth with
+ *       remove = the entry's estimate, K and range on the last-record plane of the FIRST n_records records of the frame's dense list, restricted to the entry's
+ *                box; absent when the frame has no entry;
+ *       add    = est_new (NULL: absent), K and range of this call on the last-record plane of the WHOLE list as it is now;
+ *     colour from the records: on the add side iff the volume holds colour now, on the remove side iff the frame's fusion moved colour (the entry's `coloured`: the
+ *     volume held colour when the frame was last fused; nalo_tsdf_color_disable clears it in every entry) - a frame fused before nalo_tsdf_color_enable is taken
+ *     out of tsdf and weight only, its colour words, which never held it, are left alone. The one context-owned plane serves both sides when the list has not grown since the frame was
+ *     fused, a second context-owned plane is built when it has. With est_new the entry becomes {est_new, the current length, K, range, the whole grid} (a frame
+ *     without an entry gets it); with NULL the entry is dropped. nalo_tsdf_last / nalo_tsdf_replace_last as after nalo_tsdf_replace_depth. Enqueues only.
+ *     NALO_ERR_STATE: no volume, the log off, no dense archive, a sharded window, a list shorter than n_records (the dense archive was reset). NALO_ERR_ARG: a
+ *     frame_id the dense archive has never seen, NULL with no entry, a K, estimate or range nalo_tsdf_replace_depth refuses. A refusal queues nothing and leaves
+ *     volume, colour, log and nalo_tsdf_last as they were.
+ * nalo_tsdf_est_world_to_cam   host only, no context: the M above. NALO_ERR_ARG for a non-finite pose or an s that is not finite or <= 0.
+ * nalo_tsdf_frustum_box_est    host only, no context: nalo_tsdf_frustum_box with z = max_depth + trunc / s in double and each far corner at
+ *     (((c0 X + c1 Y) + c2 z) * s) + c3. For s == 1 it is nalo_tsdf_frustum_box's box exactly (one function computes both). It is conservative for every voxel
+ *     either operation touches: such a voxel has 0 < zc <= max_depth + trunc / s in the estimate's camera, which maps to the world by p -> s R p + t.
+ * nalo_tsdf_box_shift   host only, no context: the box [lo, lo + size) of a volume translated by -shift - where its voxels lie after nalo_tsdf_shift(shift) - and
+ *     clipped to the grid, in place; all zeros when nothing of it is left (or a size was < 1). 64-bit arithmetic on any int. NALO_ERR_ARG: a dimension outside [1, 2048].
  * ------------------------------------------------------------------------------------------------ */
 typedef struct nalo_tsdf_desc { float origin[3]; float voxel_size; int dims[3]; float trunc; float max_weight; } nalo_tsdf_desc;
 typedef struct nalo_tsdf_integrate_args {
@@ -2001,10 +2067,39 @@ int nalo_tsdf_align_eval(nalo_ctx* ctx, const nalo_tsdf_align_args* args, const 
 int nalo_tsdf_align_depth(nalo_ctx* ctx, const nalo_tsdf_align_args* args, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* result);
 int nalo_tsdf_align_frame(nalo_ctx* ctx, int frame_id, const nalo_tsdf_align_args* args, const nalo_tsdf_align_est* est_in, nalo_tsdf_align_result* result);
 int nalo_tsdf_align_step(const double H[28], const double b[7], double lambda, int dof, const nalo_tsdf_align_est* est, double inc[7], nalo_tsdf_align_est* est_out);   /* host only, no context */
+typedef struct nalo_tsdf_side {
+    nalo_dev_plane depth;                   /* F32, one channel, w x h of its own */
+    nalo_dev_plane colour;                  /* ptr NULL: none; else U8, three channels, the depth plane's size */
+    int colour_is_rgb;                      /* channel 0 is R (else B) */
+    float K[4];                             /* fx, fy, cx, cy for that size */
+    nalo_tsdf_align_est est;                /* camToWorld and the scale s > 0 */
+    float min_depth, max_depth;
+} nalo_tsdf_side;
+typedef struct nalo_tsdf_replace_args {
+    const nalo_tsdf_side* remove;           /* NULL: add only */
+    const nalo_tsdf_side* add;              /* NULL: remove only */
+    int use_box; int lo[3], size[3];        /* use_box != 0: the remove side applies to these voxels only */
+    void* producer_stream;                  /* as nalo_tsdf_integrate_args, for the planes of both sides */
+} nalo_tsdf_replace_args;
+typedef struct nalo_tsdf_replace_stats { int lo[3], hi[3]; long long visited, removed, reset, added, written; } nalo_tsdf_replace_stats;
+int nalo_tsdf_replace_depth(nalo_ctx* ctx, const nalo_tsdf_replace_args* args);
+int nalo_tsdf_replace_last(nalo_ctx* ctx, nalo_tsdf_replace_stats* stats);
+typedef struct nalo_tsdf_log_entry {
+    int frame_id, n_records;                /* n_records: the length of the frame's dense list that was fused */
+    nalo_tsdf_align_est est; float K[4]; float min_depth, max_depth;   /* what it was fused with */
+    int lo[3], size[3];                     /* the resident box */
+    int coloured;                           /* the fusion moved colour: a removal takes the frame out of the colour words too */
+} nalo_tsdf_log_entry;
+int nalo_tsdf_log_enable(nalo_ctx* ctx, int on);                                       /* host only, launches nothing */
+int nalo_tsdf_log_get(nalo_ctx* ctx, nalo_tsdf_log_entry* out, int cap, int* n);       /* host only, launches nothing */
+int nalo_tsdf_replace_frame(nalo_ctx* ctx, int frame_id, const nalo_tsdf_align_est* est_new /* NULL: remove only */, const float K[4], float min_depth, float max_depth);
+int nalo_tsdf_est_world_to_cam(const nalo_tsdf_align_est* est, float M[12]);   /* host only, no context */
+int nalo_tsdf_frustum_box_est(const nalo_tsdf_desc* desc, int w, int h, const float K[4], const nalo_tsdf_align_est* est, float max_depth, int lo[3], int hi[3]);   /* host only, no context */
+int nalo_tsdf_box_shift(const int dims[3], const int shift[3], int lo[3], int size[3]);   /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_align", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_replace", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_align", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -45,6 +45,8 @@ EXPORTS = [
     "nalo_tsdf_raycast", "nalo_tsdf_raycast_view", "nalo_tsdf_raycast_steps",
     "nalo_tsdf_align_eval", "nalo_tsdf_align_depth", "nalo_tsdf_align_frame", "nalo_tsdf_align_step",
     "nalo_tsdf_shift", "nalo_tsdf_geometry", "nalo_tsdf_shift_for", "nalo_tsdf_shift_boxes",
+    "nalo_tsdf_replace_depth", "nalo_tsdf_replace_last", "nalo_tsdf_replace_frame", "nalo_tsdf_log_enable", "nalo_tsdf_log_get", "nalo_tsdf_est_world_to_cam", "nalo_tsdf_frustum_box_est",
+    "nalo_tsdf_box_shift",
     "nalo_tsdf_archive_enable", "nalo_tsdf_archive_disable", "nalo_tsdf_archive_reset", "nalo_tsdf_archive_mesh", "nalo_tsdf_archive_stats", "nalo_tsdf_archive_get", "nalo_tsdf_archive_view", "nalo_tsdf_follow",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
@@ -251,6 +253,24 @@ ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW, ALIGN_SOLVE_FAILED = 0, 1
 ALIGN_MAX_EVALUATIONS = 65                               # the first evaluation and one per iteration, at most 64 of them
 
 
+class TsdfSide(C.Structure):                              # nalo_tsdf_side; tsdf_side() builds one
+    _fields_ = [("depth", DevPlane), ("colour", DevPlane), ("colour_is_rgb", C.c_int), ("K", C.c_float * 4), ("est", TsdfAlignEst), ("min_depth", C.c_float), ("max_depth", C.c_float)]
+
+
+class TsdfReplaceArgs(C.Structure):                       # nalo_tsdf_replace_args
+    _fields_ = [("remove", C.POINTER(TsdfSide)), ("add", C.POINTER(TsdfSide)), ("use_box", C.c_int), ("lo", C.c_int * 3), ("size", C.c_int * 3), ("producer_stream", C.c_void_p)]
+
+
+class TsdfReplaceStats(C.Structure):                      # nalo_tsdf_replace_stats
+    _fields_ = [("lo", C.c_int * 3), ("hi", C.c_int * 3), ("visited", C.c_longlong), ("removed", C.c_longlong), ("reset", C.c_longlong), ("added", C.c_longlong),
+                ("written", C.c_longlong)]
+
+
+class TsdfLogEntry(C.Structure):                          # nalo_tsdf_log_entry
+    _fields_ = [("frame_id", C.c_int), ("n_records", C.c_int), ("est", TsdfAlignEst), ("K", C.c_float * 4), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("lo", C.c_int * 3), ("size", C.c_int * 3), ("coloured", C.c_int)]
+
+
 class TsdfGeometry(C.Structure):                          # struct nalo_tsdf_geometry
     _fields_ = [("desc", TsdfDesc), ("origin0", C.c_float * 3), ("base", C.c_int * 3)]
 
@@ -392,6 +412,9 @@ def host_lib():
         L.nalo_tsdf_shift_for.argtypes = [C.POINTER(TsdfDesc), c_dp, c_ip, c_ip]
         L.nalo_tsdf_align_step.argtypes = [c_dp, c_dp, C.c_double, C.c_int, C.POINTER(TsdfAlignEst), c_dp, C.POINTER(TsdfAlignEst)]
         L.nalo_tsdf_shift_boxes.argtypes = [c_ip, c_ip, C.POINTER(TsdfShiftBoxes)]
+        L.nalo_tsdf_est_world_to_cam.argtypes = [C.POINTER(TsdfAlignEst), c_fp]
+        L.nalo_tsdf_frustum_box_est.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, C.POINTER(TsdfAlignEst), C.c_float, c_ip, c_ip]
+        L.nalo_tsdf_box_shift.argtypes = [c_ip, c_ip, c_ip, c_ip]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
         _HOST_LIB = L
@@ -531,6 +554,64 @@ def tsdf_shift_boxes(dims, shift):
     if rc != 0:
         raise NaloError("nalo_tsdf_shift_boxes: bad argument (%d)" % rc)
     return dict(boxes=[(tuple(b.lo[k]), tuple(b.size[k])) for k in range(b.n_boxes)], kept_lo=tuple(b.kept_lo), kept_size=tuple(b.kept_size))
+
+
+def tsdf_est_world_to_cam(cam_to_world, s=1.0):
+    """nalo_tsdf_est_world_to_cam -> float32 [3][4]: R^T / s and -(R^T t) / s of an estimate; for s = 1 the integration's worldToCam bit for bit. NaloError for
+    a non-finite pose, or an s that is not finite or <= 0. Needs no device"""
+    e, M = tsdf_align_est(cam_to_world, s), np.zeros(12, np.float32)
+    rc = host_lib().nalo_tsdf_est_world_to_cam(C.byref(e), _f(M))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_est_world_to_cam: bad argument (%d)" % rc)
+    return M.reshape(3, 4)
+
+
+def tsdf_frustum_box_est(desc, w, h, K, cam_to_world, s, max_depth):
+    """nalo_tsdf_frustum_box_est: the culling box (lo, hi) of a removal or an add at the estimate (cam_to_world, s), hi exclusive, all zeros when it is empty;
+    for s = 1 tsdf_frustum_box's. Needs no device"""
+    Kf = np.ascontiguousarray(K, np.float32).reshape(-1)
+    assert Kf.size == 4
+    e = tsdf_align_est(cam_to_world, s)
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    rc = host_lib().nalo_tsdf_frustum_box_est(C.byref(desc), int(w), int(h), _f(Kf), C.byref(e), C.c_float(max_depth), _i(lo), _i(hi))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_frustum_box_est: bad argument (%d)" % rc)
+    return lo, hi
+
+
+def tsdf_box_shift(dims, shift, lo, size):
+    """nalo_tsdf_box_shift -> (lo, size) int32 [3]: where the voxels of the box [lo, lo + size) lie after tsdf_shift(shift), clipped to the grid; all zeros when
+    none is left. Needs no device"""
+    dm, sh = np.ascontiguousarray(dims, np.int32).reshape(-1), np.ascontiguousarray(shift, np.int32).reshape(-1)
+    l, z = np.array(lo, np.int32).reshape(-1), np.array(size, np.int32).reshape(-1)
+    assert dm.size == 3 and sh.size == 3 and l.size == 3 and z.size == 3
+    rc = host_lib().nalo_tsdf_box_shift(_i(dm), _i(sh), _i(l), _i(z))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_box_shift: bad argument (%d)" % rc)
+    return l, z
+
+
+def tsdf_side(depth, K, cam_to_world, s, min_depth, max_depth, colour=None, colour_is_rgb=False):
+    """nalo_tsdf_side (a TsdfSide) for tsdf_replace_depth: depth a 2-D float32 device array (or a DevPlane) read where it lies, K = (fx, fy, cx, cy) for ITS
+    size, the estimate (cam_to_world [3][4], s), the depth range; colour: a uint8 device array [h][w][3] or a DevPlane of three channels. The side keeps the
+    arrays alive; `stream` is the stream of the DEPTH plane alone, as tsdf_integrate_depth works it out (a colour plane from another stream is the caller's
+    to order: see tsdf_replace_depth)"""
+    sd = TsdfSide()
+    sd.depth = depth if isinstance(depth, DevPlane) else dev_plane(depth)
+    if colour is not None:
+        sd.colour = colour if isinstance(colour, DevPlane) else dev_plane(colour, "hwc")
+    sd.colour_is_rgb = int(bool(colour_is_rgb))
+    sd.K[:] = [float(v) for v in K]
+    sd.est = tsdf_align_est(cam_to_world, s)
+    sd.min_depth, sd.max_depth = float(min_depth), float(max_depth)
+    sd.keep = (depth, colour)
+    sd.stream = 0
+    torch = sys.modules.get("torch")
+    if isinstance(depth, DeviceView):
+        sd.stream = depth.stream
+    elif torch is not None and isinstance(depth, torch.Tensor):
+        sd.stream = torch.cuda.current_stream(depth.device).cuda_stream
+    return sd
 
 
 def write_ply_mesh(path, xyz, tri, rgba=None):
@@ -742,6 +823,11 @@ def load():
     L.nalo_tsdf_shift.argtypes = [vp, c_ip]
     L.nalo_tsdf_geometry.argtypes = [vp, C.POINTER(TsdfGeometry)]
     L.nalo_tsdf_frustum_box.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, c_dp, C.c_float, c_ip, c_ip]
+    L.nalo_tsdf_replace_depth.argtypes = [vp, C.POINTER(TsdfReplaceArgs)]
+    L.nalo_tsdf_replace_last.argtypes = [vp, C.POINTER(TsdfReplaceStats)]
+    L.nalo_tsdf_replace_frame.argtypes = [vp, C.c_int, C.POINTER(TsdfAlignEst), c_fp, C.c_float, C.c_float]
+    L.nalo_tsdf_log_enable.argtypes = [vp, C.c_int]
+    L.nalo_tsdf_log_get.argtypes = [vp, C.POINTER(TsdfLogEntry), C.c_int, c_ip]
     L.nalo_tsdf_archive_enable.argtypes = [vp]
     L.nalo_tsdf_archive_disable.argtypes = [vp]
     L.nalo_tsdf_archive_reset.argtypes = [vp]
@@ -1884,6 +1970,55 @@ class Context:
         st = TsdfStats()
         self._ck(self.L.nalo_tsdf_last(self.h_, C.byref(st)))
         return dict(lo=tuple(st.lo), hi=tuple(st.hi), visited=int(st.visited), updated=int(st.updated))
+
+    def tsdf_replace_depth(self, remove=None, add=None, box=None, stream=None, release=True):
+        """nalo_tsdf_replace_depth: per voxel the removal of side `remove`, then the add of side `add` (tsdf_side() builds them; either may be None), in one
+        launch. box = (lo, size) restricts the REMOVE side to those voxels. stream / release as tsdf_integrate_depth; None: the stream tsdf_side() found for
+        the ADD side's depth plane, else the remove side's. ONE stream is waited for and released: a caller whose planes (the two sides', or a colour plane)
+        come from more than one producer passes `stream` and orders the others behind it, or synchronises first. Returns without waiting."""
+        a = TsdfReplaceArgs()
+        if remove is not None:
+            a.remove = C.pointer(remove)
+        if add is not None:
+            a.add = C.pointer(add)
+        if box is not None:
+            a.use_box = 1
+            a.lo[:] = [int(v) for v in box[0]]
+            a.size[:] = [int(v) for v in box[1]]
+        if stream is None:
+            stream = next((sd.stream for sd in (add, remove) if sd is not None and getattr(sd, "stream", 0)), 0)
+        a.producer_stream = stream or None
+        self._ck(self.L.nalo_tsdf_replace_depth(self.h_, C.byref(a)))
+        if release:
+            self.tsdf_release(stream)
+
+    def tsdf_replace_last(self):
+        """nalo_tsdf_replace_last -> dict(lo, hi, visited, removed, reset, added, written) of the last replacement (hi exclusive); waits"""
+        st = TsdfReplaceStats()
+        self._ck(self.L.nalo_tsdf_replace_last(self.h_, C.byref(st)))
+        return dict(lo=tuple(st.lo), hi=tuple(st.hi), visited=int(st.visited), removed=int(st.removed), reset=int(st.reset), added=int(st.added), written=int(st.written))
+
+    def tsdf_replace_frame(self, frame_id, cam_to_world, K, min_depth, max_depth, s=1.0):
+        """nalo_tsdf_replace_frame: the logged contribution of the frame removed and its dense list as it is now fused at (cam_to_world, s); cam_to_world None:
+        remove only. Needs tsdf_log_enable and the dense archive"""
+        Kf = np.ascontiguousarray(K, np.float32).reshape(-1)
+        assert Kf.size == 4
+        e = None if cam_to_world is None else C.byref(tsdf_align_est(cam_to_world, s))
+        self._ck(self.L.nalo_tsdf_replace_frame(self.h_, int(frame_id), e, _f(Kf), C.c_float(min_depth), C.c_float(max_depth)))
+
+    def tsdf_log_enable(self, on=True):
+        """nalo_tsdf_log_enable: the fusion log, what tsdf_replace_frame removes by; off by default, and off it changes nothing. Turning it off clears it"""
+        self._ck(self.L.nalo_tsdf_log_enable(self.h_, int(bool(on))))
+
+    def tsdf_log_get(self):
+        """nalo_tsdf_log_get -> a list of dict(frame_id, n_records, cam_to_world [3][4], s, K, min_depth, max_depth, lo, size, coloured) in the order the frames were
+        first fused; launches nothing"""
+        n = np.zeros(1, np.int32)
+        self._ck(self.L.nalo_tsdf_log_get(self.h_, None, 0, _i(n)))
+        out = (TsdfLogEntry * max(int(n[0]), 1))()
+        self._ck(self.L.nalo_tsdf_log_get(self.h_, out, int(n[0]), _i(n)))
+        return [dict(frame_id=int(e.frame_id), n_records=int(e.n_records), cam_to_world=_align_est(e.est)[0], s=float(e.est.s), K=tuple(float(k) for k in e.K),
+                     min_depth=float(e.min_depth), max_depth=float(e.max_depth), lo=tuple(e.lo), size=tuple(e.size), coloured=bool(e.coloured)) for e in out[:int(n[0])]]
 
     def tsdf_get(self, lo=None, size=None):
         """nalo_tsdf_get -> (tsdf, weight) of the sub-block [lo, lo + size) as float32 [sz][sy][sx]; the whole grid by default"""

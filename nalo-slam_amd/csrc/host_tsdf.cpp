@@ -1,5 +1,5 @@
-// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam, the culling box nalo_tsdf_frustum_box, the mesh's triangle table and the
-// geometry of a shifted volume (the origin, nalo_tsdf_shift_for, nalo_tsdf_shift_boxes). Plain C++ with no device call, built without FMA contraction: every
+// The TSDF section's host-only arithmetic (include/nalo_gpu.h): the descriptor's refusals, worldToCam (and at an estimate: nalo_tsdf_est_world_to_cam), the culling box
+// nalo_tsdf_frustum_box[_est], the mesh's triangle table and the geometry of a shifted volume (the origin, nalo_tsdf_shift_for, nalo_tsdf_shift_boxes, nalo_tsdf_box_shift). Plain C++ with no device call, built without FMA contraction: every
 // line below is the operation order the header defines, in double (the shifted origin: in float).
 #include <cmath>
 
@@ -99,11 +99,14 @@ extern "C" int nalo_tsdf_shift_boxes(const int dims[3], const int shift[3], stru
     return NALO_OK;
 }
 
-extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, const float K[4], const double c[12], float max_depth, int lo[3], int hi[3]) {
+// nalo_tsdf_frustum_box (s = 1) and nalo_tsdf_frustum_box_est: the one statement of the culling box. With s = 1 the quotient trunc / s and the product with s
+// are exact, so the first is the second at a scale of one, bit for bit
+static int tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, const float K[4], const double c[12], double s, float max_depth, int lo[3], int hi[3]) {
     if (!K || !c || !lo || !hi || w < 1 || h < 1 || nalo::tsdf_desc_refusal(d) || !std::isfinite(max_depth)) return NALO_ERR_ARG;
     for (int i = 0; i < 4; ++i) if (!std::isfinite(K[i])) return NALO_ERR_ARG;
     for (int i = 0; i < 12; ++i) if (!std::isfinite(c[i])) return NALO_ERR_ARG;
-    const double z = (double)max_depth + (double)d->trunc;
+    if (!std::isfinite(s) || s <= 0.0) return NALO_ERR_ARG;
+    const double z = (double)max_depth + (double)d->trunc / s;
     double mn[3] = {c[3], c[7], c[11]}, mx[3] = {c[3], c[7], c[11]};          // the apex
     bool bad[3] = {false, false, false};
     for (int cv = 0; cv < 2; ++cv)
@@ -111,7 +114,7 @@ extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, cons
             const double uf = cu ? (double)w : 0.0, vf = cv ? (double)h : 0.0;
             const double X = (((uf - 0.5) - (double)K[2]) / (double)K[0]) * z, Y = (((vf - 0.5) - (double)K[3]) / (double)K[1]) * z;
             for (int a = 0; a < 3; ++a) {
-                const double p = ((c[4 * a] * X + c[4 * a + 1] * Y) + c[4 * a + 2] * z) + c[4 * a + 3];
+                const double p = (((c[4 * a] * X + c[4 * a + 1] * Y) + c[4 * a + 2] * z) * s) + c[4 * a + 3];
                 if (std::isnan(p)) bad[a] = true;                                // inf - inf at an absurd pose: the axis takes the whole grid below
                 if (p < mn[a]) mn[a] = p;
                 if (p > mx[a]) mx[a] = p;
@@ -128,6 +131,44 @@ extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, cons
         if (lo[a] >= hi[a]) empty = true;
     }
     if (empty) for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
+    return NALO_OK;
+}
+extern "C" int nalo_tsdf_frustum_box(const nalo_tsdf_desc* d, int w, int h, const float K[4], const double c[12], float max_depth, int lo[3], int hi[3]) {
+    return tsdf_frustum_box(d, w, h, K, c, 1.0, max_depth, lo, hi);
+}
+extern "C" int nalo_tsdf_frustum_box_est(const nalo_tsdf_desc* d, int w, int h, const float K[4], const nalo_tsdf_align_est* est, float max_depth, int lo[3], int hi[3]) {
+    if (!est) return NALO_ERR_ARG;
+    return tsdf_frustum_box(d, w, h, K, est->camToWorld, est->s, max_depth, lo, hi);
+}
+
+extern "C" int nalo_tsdf_est_world_to_cam(const nalo_tsdf_align_est* est, float M[12]) {
+    if (!est || !M) return NALO_ERR_ARG;
+    const double* c = est->camToWorld; const double s = est->s;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(c[i])) return NALO_ERR_ARG;
+    if (!std::isfinite(s) || s <= 0.0) return NALO_ERR_ARG;
+    for (int r = 0; r < 3; ++r) {
+        // row r of R^T is column r of R; tsdf_world_to_cam's sums, every entry over s (s = 1: the same bits, a quotient by 1.0 is exact)
+        const double a = c[0 + r], b = c[4 + r], e = c[8 + r];
+        M[4 * r + 0] = (float)(a / s); M[4 * r + 1] = (float)(b / s); M[4 * r + 2] = (float)(e / s);
+        M[4 * r + 3] = (float)(-((a * c[3] + b * c[7]) + e * c[11]) / s);
+    }
+    return NALO_OK;
+}
+
+extern "C" int nalo_tsdf_box_shift(const int dims[3], const int shift[3], int lo[3], int size[3]) {
+    if (!dims || !shift || !lo || !size) return NALO_ERR_ARG;
+    for (int a = 0; a < 3; ++a) if (dims[a] < 1 || dims[a] > 2048) return NALO_ERR_ARG;
+    // per axis in 64 bits (lo - shift and lo + size of any ints): the translated range cut to [0, dims)
+    long long l[3], u[3];
+    bool empty = false;
+    for (int a = 0; a < 3; ++a) {
+        l[a] = (long long)lo[a] - (long long)shift[a];
+        u[a] = l[a] + (long long)size[a];
+        if (l[a] < 0) l[a] = 0;
+        if (u[a] > dims[a]) u[a] = dims[a];
+        if (size[a] < 1 || l[a] >= u[a]) empty = true;
+    }
+    for (int a = 0; a < 3; ++a) { lo[a] = empty ? 0 : (int)l[a]; size[a] = empty ? 0 : (int)(u[a] - l[a]); }
     return NALO_OK;
 }
 

@@ -1,5 +1,5 @@
 // The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
-// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table, the alignment's step).
+// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_replace.hip, kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table, the alignment's step).
 #include <algorithm>
 #include <cmath>
 
@@ -17,9 +17,10 @@ struct TsdfVolume {
     Event ev_read;                                   // behind the last kernel that read a caller's depth plane (nalo_tsdf_release)
     bool read_pending = false;
     DevBuf<unsigned long long> updated; HostBuf<unsigned long long> updated_h;
-    nalo_tsdf_stats last{}; bool have_last = false;
+    nalo_tsdf_stats last{}; bool have_last = false, last_replace = false;   // updated: [4], the integration's count in [0]; a replacement's written, removed, reset, added
     DevBuf<float> block;                             // nalo_tsdf_get / _set staging: one tile of z slices of the sub-block
     DevBuf<float> xyz; HostBuf<float> xyz_h;         // nalo_tsdf_surface_points: as many points as the caller had room for
+    DevBuf<float> plane2; DevBuf<unsigned> cplane2;                                 // nalo_tsdf_replace_frame: the plane of the records that were fused, when the frame's list has grown since
     KeyPlane<unsigned long long, 0> key; DevBuf<float> plane;                       // nalo_tsdf_integrate_frame: w h words each; key is zero between calls
     std::vector<MapSeg> segs;                                                       // the frame's segments, host memory: they travel as kernel arguments
     // nalo_tsdf_mesh: 5 B of scratch per sub-box voxel, the two count arrays, and the device mesh itself (nalo_tsdf_mesh_view names mesh_xyz / mesh_tri).
@@ -61,7 +62,7 @@ constexpr long long kTsdfArchiveMax = 2147483647LL;                             
 
 constexpr size_t kTsdfTileFloats = (size_t)1 << 22;   // nalo_tsdf_get / _set: 16 MiB of staging
 
-void tsdf_destroy(nalo_ctx* c) { delete c->tsdf; c->tsdf = nullptr; }
+void tsdf_destroy(nalo_ctx* c) { delete c->tsdf; c->tsdf = nullptr; c->tsdf_log.clear(); }
 void tsdf_archive_destroy(nalo_ctx* c) { delete c->tsdf_archive; c->tsdf_archive = nullptr; }
 
 static int tsdf_need(nalo_ctx* c, const char* who) {
@@ -140,8 +141,81 @@ static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth,
         st.visited = (long long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
         const int rc = tsdf_integrate_launch(c, D); if (rc) return rc;
     }
-    v.last = st; v.have_last = true;
+    v.last = st; v.have_last = true; v.last_replace = false;
     return NALO_OK;
+}
+
+// ---- the replacement (nalo_tsdf_replace_*)
+// the camera half of a side's checks, for a plane of w x h: K, the estimate, the range; M, the side's own culling box and on = 1 on success. `who` already names the side
+static int tsdf_side_camera(nalo_ctx* c, const std::string& who, const TsdfVolume& v, int w, int h, const float K[4], const nalo_tsdf_align_est* est, float min_depth, float max_depth,
+                            TsdfSideDev* S) {
+    for (int i = 0; i < 4; ++i) if (!std::isfinite(K[i])) return fail(c, NALO_ERR_ARG, who + ": K is not finite");
+    if (nalo_tsdf_est_world_to_cam(est, S->M) != NALO_OK) return fail(c, NALO_ERR_ARG, who + ": camToWorld is not finite, or s is not finite or <= 0");
+    if (!std::isfinite(min_depth) || !std::isfinite(max_depth) || min_depth > max_depth) return fail(c, NALO_ERR_ARG, who + ": min_depth / max_depth not finite, or min_depth > max_depth");
+    if (nalo_tsdf_frustum_box_est(&v.d, w, h, K, est, max_depth, S->lo, S->hi) != NALO_OK) return fail(c, NALO_ERR_ARG, who + ": the culling box refused the arguments");
+    S->on = 1;
+    S->fx = K[0]; S->fy = K[1]; S->cx = K[2]; S->cy = K[3]; S->min_depth = min_depth; S->max_depth = max_depth; S->s = (float)est->s; S->w = w; S->h = h;
+    return NALO_OK;
+}
+// a caller's side behind its checks: the kernel's side with the side's own culling box, on = 1. `who` already names the side. Refusals as tsdf_integrate_depth's
+static int tsdf_side_check(nalo_ctx* c, const std::string& who, const TsdfVolume& v, const nalo_tsdf_side* s, TsdfSideDev* S) {
+    *S = TsdfSideDev{};
+    const bool coloured = s->colour.ptr != nullptr;
+    if (coloured) { const int rc = tsdf_need_colour(c, v, who); if (rc) return rc; }
+    { const int rc = nalo_dev_plane_check(c, &s->depth); if (rc) return rc; }
+    if (s->depth.dtype != NALO_DT_F32 || s->depth.channels != 1) return fail(c, NALO_ERR_ARG, who + ": the depth plane is one channel of F32");
+    if (coloured) {
+        { const int rc = nalo_dev_plane_check(c, &s->colour); if (rc) return rc; }
+        if (s->colour.dtype != NALO_DT_U8 || s->colour.channels != 3 || s->colour.w != s->depth.w || s->colour.h != s->depth.h)
+            return fail(c, NALO_ERR_ARG, who + ": the colour plane is three channels of U8 in the depth plane's size");
+        S->colour = static_cast<const unsigned char*>(s->colour.ptr); S->csy = s->colour.stride_y; S->csx = s->colour.stride_x;
+        for (int X = 0; X < 3; ++X) S->csc[X] = (s->colour_is_rgb ? 2 - X : X) * s->colour.stride_c;      // the planes are B, G, R
+    }
+    S->coloured = coloured;
+    S->depth = static_cast<const char*>(s->depth.ptr); S->sy = s->depth.stride_y; S->sx = s->depth.stride_x;
+    return tsdf_side_camera(c, who, v, s->depth.w, s->depth.h, s->K, &s->est, s->min_depth, s->max_depth, S);
+}
+static void tsdf_side_settle(TsdfSideDev& S) { for (int a = 0; a < 3; ++a) if (S.lo[a] >= S.hi[a]) S.on = 0; }   // an empty box: the side touches nothing
+
+// everything is validated; box (NULL: none) cuts the remove side. Zero the counts, the kernel over the hull, the call's record for nalo_tsdf_last /
+// nalo_tsdf_replace_last. Enqueues only.
+static int tsdf_replace_enqueue(nalo_ctx* c, TsdfVolume& v, TsdfSideDev rem, TsdfSideDev add, const TsdfBox* box) {
+    if (rem.on && box) for (int a = 0; a < 3; ++a) { rem.lo[a] = std::max(rem.lo[a], box->lo[a]); rem.hi[a] = std::min(rem.hi[a], box->lo[a] + box->size[a]); }
+    tsdf_side_settle(rem); tsdf_side_settle(add);
+    NALO_HIP(c, hipMemsetAsync(v.updated.p, 0, 4 * sizeof(unsigned long long), c->stream));
+    nalo_tsdf_stats st{};
+    if (rem.on || add.on) {
+        TsdfReplaceDev D{};
+        D.g = tsdf_grid(v, rem.coloured || add.coloured);
+        for (int a = 0; a < 3; ++a) {
+            D.lo[a] = st.lo[a] = !add.on ? rem.lo[a] : !rem.on ? add.lo[a] : std::min(rem.lo[a], add.lo[a]);
+            D.hi[a] = st.hi[a] = !add.on ? rem.hi[a] : !rem.on ? add.hi[a] : std::max(rem.hi[a], add.hi[a]);
+        }
+        D.trunc = v.d.trunc; D.max_weight = v.d.max_weight; D.rem = rem; D.add = add; D.counts = v.updated.p;
+        st.visited = (long long)(D.hi[0] - D.lo[0]) * (D.hi[1] - D.lo[1]) * (D.hi[2] - D.lo[2]);
+        const int rc = tsdf_replace_launch(c, D); if (rc) return rc;
+    }
+    v.last = st; v.have_last = true; v.last_replace = true;
+    return NALO_OK;
+}
+
+// ---- the fusion log (nalo_tsdf_log_*): c->tsdf_log, host memory
+static nalo_tsdf_log_entry* tsdf_log_find(nalo_ctx* c, int frame_id) {
+    for (nalo_tsdf_log_entry& e : c->tsdf_log) if (e.frame_id == frame_id) return &e;
+    return nullptr;
+}
+// the frame's entry, new or rewritten in place: what it was fused with just now (with colour iff the volume holds colour now), resident in the whole grid
+static void tsdf_log_put(nalo_ctx* c, const TsdfVolume& v, int frame_id, int n_records, const nalo_tsdf_align_est& est, const float K[4], float min_depth, float max_depth) {
+    nalo_tsdf_log_entry* e = tsdf_log_find(c, frame_id);
+    if (!e) { c->tsdf_log.push_back(nalo_tsdf_log_entry{}); e = &c->tsdf_log.back(); }
+    e->frame_id = frame_id; e->n_records = n_records; e->coloured = v.colour.p ? 1 : 0; e->est = est; std::copy(K, K + 4, e->K); e->min_depth = min_depth; e->max_depth = max_depth;
+    for (int a = 0; a < 3; ++a) { e->lo[a] = 0; e->size[a] = v.d.dims[a]; }
+}
+// behind a non-zero shift: every resident box moves with its voxels, and an entry whose voxels have all left goes
+static void tsdf_log_shift(nalo_ctx* c, const TsdfVolume& v, const int shift[3]) {
+    std::vector<nalo_tsdf_log_entry> kept;
+    for (nalo_tsdf_log_entry e : c->tsdf_log) { nalo_tsdf_box_shift(v.d.dims, shift, e.lo, e.size); if (e.size[0] > 0) kept.push_back(e); }
+    c->tsdf_log.swap(kept);
 }
 
 }  // namespace nalo
@@ -158,13 +232,14 @@ int nalo_tsdf_create(nalo_ctx* c, const nalo_tsdf_desc* desc) {
     std::copy(desc->origin, desc->origin + 3, v->origin0);
     hipError_t e = v->tsdf.reserve(v->n);
     if (e == hipSuccess) e = v->weight.reserve(v->n);
-    if (e == hipSuccess) e = v->updated.reserve(1);
-    if (e == hipSuccess) e = v->updated_h.reserve(1);
+    if (e == hipSuccess) e = v->updated.reserve(4);
+    if (e == hipSuccess) e = v->updated_h.reserve(4);
     if (e == hipSuccess) e = v->ev_read.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_prod.create(hipEventDisableTiming);
     if (e != hipSuccess) { delete v; (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_create: ") + hipGetErrorString(e)); }
     if (c->tsdf) { NALO_HIP(c, hipStreamSynchronize(c->stream)); tsdf_destroy(c); }      // kernels of the old volume may still be queued
     c->tsdf = v;
+    c->tsdf_log.clear();
     return tsdf_fill_launch(c, v->tsdf.p, v->weight.p, v->n);
 }
 
@@ -172,6 +247,7 @@ int nalo_tsdf_reset(nalo_ctx* c) {
     { const int rc = tsdf_need(c, "nalo_tsdf_reset"); if (rc) return rc; }
     NALO_HIP(c, hipSetDevice(c->device));
     c->tsdf->have_last = false;
+    c->tsdf_log.clear();
     if (c->tsdf->colour.p) NALO_HIP(c, hipMemsetAsync(c->tsdf->colour.p, 0, 3 * c->tsdf->n * sizeof(float), c->stream));      // 0.0f is all bits zero
     return tsdf_fill_launch(c, c->tsdf->tsdf.p, c->tsdf->weight.p, c->tsdf->n);
 }
@@ -195,7 +271,8 @@ int nalo_tsdf_color_disable(nalo_ctx* c) {
     if (!v.colour.p) return NALO_OK;
     NALO_HIP(c, hipSetDevice(c->device));
     NALO_HIP(c, hipStreamSynchronize(c->stream));                              // kernels that name the planes may still be queued
-    v.colour.release(); v.colour2.release(); v.cplane.release(); v.mesh_rgba.release(); v.mesh_coloured = false;
+    v.colour.release(); v.colour2.release(); v.cplane.release(); v.cplane2.release(); v.mesh_rgba.release(); v.mesh_coloured = false;
+    for (nalo_tsdf_log_entry& e : c->tsdf_log) e.coloured = 0;                 // the colour words the logged frames were fused into are gone
     return NALO_OK;
 }
 
@@ -232,6 +309,7 @@ int nalo_tsdf_shift(nalo_ctx* c, const int shift[3]) {
     if (coloured) std::swap(v.colour, v.colour2);
     for (int a = 0; a < 3; ++a) { v.base[a] = base[a]; v.d.origin[a] = origin[a]; }
     v.have_last = false;                                                       // the last integration's box was in the old indices
+    if (c->tsdf_log_on) tsdf_log_shift(c, v, shift);
     return NALO_OK;
 }
 
@@ -296,19 +374,25 @@ int nalo_tsdf_release(nalo_ctx* c, void* stream) {
     return NALO_OK;
 }
 
+// the plane of the segments in `segs` (a frame's, or a prefix of them) into plane / cplane. Enqueues only.
+static int tsdf_frame_plane_of(nalo_ctx* c, TsdfVolume& v, const std::vector<MapSeg>& segs, bool colour, DevBuf<float>& plane, DevBuf<unsigned>& cplane) {
+    const size_t npx = (size_t)c->w * c->h;
+    NALO_HIP(c, plane.reserve(npx));
+    if (colour) NALO_HIP(c, cplane.reserve(npx));                              // every call writes every word of it: a winner's colour, or zero behind the resolve
+    NALO_HIP(c, v.key.begin(npx, c->stream));
+    { const int rc = tsdf_frame_plane_launch(c, segs.data(), (int)segs.size(), v.key.p, plane.p, colour ? cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
+    v.key.settled();
+    return NALO_OK;
+}
 // the context-owned plane of a frame's dense list (the header's last-record rule) for nalo_tsdf_integrate_frame and nalo_tsdf_align_frame: v.plane, and
 // v.cplane on a coloured volume when `colour` is asked for. Its refusals are map_dense_segments'. Enqueues only.
-static int tsdf_frame_plane(nalo_ctx* c, const char* who, TsdfVolume& v, int frame_id, bool colour) {
+// total (may be NULL): the length of the frame's list.
+static int tsdf_frame_plane(nalo_ctx* c, const char* who, TsdfVolume& v, int frame_id, bool colour, int* total_out = nullptr) {
     NALO_HIP(c, hipSetDevice(c->device));
     int total = 0;
     { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }
-    const size_t npx = (size_t)c->w * c->h;
-    NALO_HIP(c, v.plane.reserve(npx));
-    if (colour) NALO_HIP(c, v.cplane.reserve(npx));                            // every call writes every word of it: a winner's colour, or zero behind the resolve
-    NALO_HIP(c, v.key.begin(npx, c->stream));
-    { const int rc = tsdf_frame_plane_launch(c, v.segs.data(), (int)v.segs.size(), v.key.p, v.plane.p, colour ? v.cplane.p : nullptr, c->w, c->h); if (rc) return rc; }
-    v.key.settled();
-    return NALO_OK;
+    if (total_out) *total_out = total;
+    return tsdf_frame_plane_of(c, v, v.segs, colour, v.plane, v.cplane);
 }
 
 int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld[12], const float K[4], float min_depth, float max_depth) {
@@ -319,12 +403,79 @@ int nalo_tsdf_integrate_frame(nalo_ctx* c, int frame_id, const double camToWorld
     TsdfVolume& v = *c->tsdf;
     float M[12]; int lo[3], hi[3];
     { const int rc = tsdf_integrate_check(c, who, v, c->w, c->h, K, camToWorld, min_depth, max_depth, M, lo, hi); if (rc) return rc; }
+    if (c->tsdf_log_on && tsdf_log_find(c, frame_id)) return fail(c, NALO_ERR_STATE, "nalo_tsdf_integrate_frame: the fusion log holds this frame (nalo_tsdf_replace_frame)");
     const bool coloured = v.colour.p != nullptr;
     HostTimer ht(c, "tsdf_integrate_frame");
-    { const int rc = tsdf_frame_plane(c, who, v, frame_id, coloured); if (rc) return rc; }
+    int total = 0;
+    { const int rc = tsdf_frame_plane(c, who, v, frame_id, coloured, &total); if (rc) return rc; }
     // the packed plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
     const TsdfColourSrc src = {reinterpret_cast<const unsigned char*>(v.cplane.p), (long long)c->w * 4, 4, {0, 1, 2}};
-    return tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi, coloured ? &src : nullptr);
+    { const int rc = tsdf_integrate_enqueue(c, v, reinterpret_cast<const char*>(v.plane.p), (long long)c->w * 4, 4, c->w, c->h, K, M, min_depth, max_depth, lo, hi, coloured ? &src : nullptr); if (rc) return rc; }
+    if (c->tsdf_log_on) {
+        nalo_tsdf_align_est est{}; std::copy(camToWorld, camToWorld + 12, est.camToWorld); est.s = 1.0;
+        tsdf_log_put(c, v, frame_id, total, est, K, min_depth, max_depth);
+    }
+    return NALO_OK;
+}
+
+int nalo_tsdf_log_enable(nalo_ctx* c, int on) {
+    if (!c) return NALO_ERR_ARG;
+    c->tsdf_log_on = on != 0;
+    if (!on) c->tsdf_log.clear();
+    return NALO_OK;
+}
+
+int nalo_tsdf_log_get(nalo_ctx* c, nalo_tsdf_log_entry* out, int cap, int* n) {
+    if (!c) return NALO_ERR_ARG;
+    if (!n || cap < 0 || (cap > 0 && !out)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_log_get: bad argument");
+    *n = (int)c->tsdf_log.size();
+    std::copy(c->tsdf_log.begin(), c->tsdf_log.begin() + std::min(*n, cap), out);
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_frame(nalo_ctx* c, int frame_id, const nalo_tsdf_align_est* est_new, const float K[4], float min_depth, float max_depth) {
+    const char* who = "nalo_tsdf_replace_frame";
+    { const int rc = tsdf_need(c, who); if (rc) return rc; }
+    if (!c->tsdf_log_on) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_frame: the fusion log is not enabled (nalo_tsdf_log_enable)");
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_frame: the dense archive is not enabled (nalo_map_dense_enable)");
+    if (est_new && !K) return fail(c, NALO_ERR_ARG, "nalo_tsdf_replace_frame: bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    int total = 0;
+    { const int rc = map_dense_segments(c, who, frame_id, &v.segs, &total); if (rc) return rc; }       // a sharded window, a frame the archive has never seen
+    const nalo_tsdf_log_entry* e = tsdf_log_find(c, frame_id);
+    if (!e && !est_new) return fail(c, NALO_ERR_ARG, "nalo_tsdf_replace_frame: nothing to remove (the log has no entry of this frame) and nothing to add");
+    if (e && total < e->n_records) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_frame: the frame's dense list is shorter than when it was fused");
+    // the add side moves colour iff the volume holds colour now; the remove side iff the frame's fusion moved colour (the entry says so) into planes that still exist (so col_rem implies col_add)
+    const bool col_add = v.colour.p != nullptr, col_rem = e && e->coloured && v.colour.p != nullptr;
+    TsdfSideDev rem{}, add{};
+    if (e) { const int rc = tsdf_side_camera(c, std::string(who) + ", the logged side", v, c->w, c->h, e->K, &e->est, e->min_depth, e->max_depth, &rem); if (rc) return rc; }
+    if (est_new) { const int rc = tsdf_side_camera(c, who, v, c->w, c->h, K, est_new, min_depth, max_depth, &add); if (rc) return rc; }
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_replace_frame");
+    // the whole list's plane serves both sides unless the list has grown since the frame was fused: then the first n_records records get a plane of their own
+    const bool own = e && est_new && total > e->n_records;
+    if (e && (own || !est_new)) {
+        std::vector<MapSeg> head;
+        for (const MapSeg& sg : v.segs) if (sg.start < e->n_records) { head.push_back(sg); head.back().n = std::min(sg.n, e->n_records - sg.start); }
+        { const int rc = tsdf_frame_plane_of(c, v, head, col_rem, own ? v.plane2 : v.plane, own ? v.cplane2 : v.cplane); if (rc) return rc; }
+    }
+    if (est_new) { const int rc = tsdf_frame_plane_of(c, v, v.segs, col_add, v.plane, v.cplane); if (rc) return rc; }
+    // a packed colour plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
+    for (TsdfSideDev* S : {&rem, &add}) {
+        if (!S->on) continue;
+        const bool second = S == &rem && own;
+        S->depth = reinterpret_cast<const char*>(second ? v.plane2.p : v.plane.p); S->sy = (long long)c->w * 4; S->sx = 4;
+        const bool coloured = S == &rem ? col_rem : col_add;
+        S->coloured = coloured;
+        if (coloured) { S->colour = reinterpret_cast<const unsigned char*>(second ? v.cplane2.p : v.cplane.p); S->csy = (long long)c->w * 4; S->csx = 4; S->csc[0] = 0; S->csc[1] = 1; S->csc[2] = 2; }
+    }
+    TsdfBox B{};
+    if (e) for (int a = 0; a < 3; ++a) { B.lo[a] = e->lo[a]; B.size[a] = e->size[a]; }
+    { const int rc = tsdf_replace_enqueue(c, v, rem, add, e ? &B : nullptr); if (rc) return rc; }
+    if (est_new) tsdf_log_put(c, v, frame_id, total, *est_new, K, min_depth, max_depth);
+    else c->tsdf_log.erase(c->tsdf_log.begin() + (e - c->tsdf_log.data()));
+    return NALO_OK;
 }
 
 int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
@@ -337,6 +488,41 @@ int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     *stats = v.last;
     stats->updated = (long long)v.updated_h.p[0];
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_depth(nalo_ctx* c, const nalo_tsdf_replace_args* a) {
+    const std::string who = "nalo_tsdf_replace_depth";
+    { const int rc = tsdf_need(c, who.c_str()); if (rc) return rc; }
+    if (!a || (!a->remove && !a->add)) return fail(c, NALO_ERR_ARG, who + ": bad argument (a side, remove or add, is needed)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    TsdfSideDev rem{}, add{};
+    if (a->remove) { const int rc = tsdf_side_check(c, who + ", remove", v, a->remove, &rem); if (rc) return rc; }
+    if (a->add) { const int rc = tsdf_side_check(c, who + ", add", v, a->add, &add); if (rc) return rc; }
+    TsdfBox B;
+    if (a->use_box) { const int rc = tsdf_sub_box(c, who, "box", v, true, a->lo, a->size, &B); if (rc) return rc; }
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_replace_depth");
+    hipStream_t prod = (hipStream_t)a->producer_stream;                      // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
+    if (prod != (hipStream_t)c->stream) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    { const int rc = tsdf_replace_enqueue(c, v, rem, add, a->use_box ? &B : nullptr); if (rc) return rc; }
+    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));                         // the callers' planes have been read (one kernel reads all of them): nalo_tsdf_release
+    v.read_pending = true;
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_last(nalo_ctx* c, nalo_tsdf_replace_stats* stats) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_replace_last"); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (!stats) return fail(c, NALO_ERR_ARG, "nalo_tsdf_replace_last: bad argument");
+    if (!v.have_last || !v.last_replace) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_last: the last operation on this volume was not a replacement");
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) { stats->lo[k] = v.last.lo[k]; stats->hi[k] = v.last.hi[k]; }
+    stats->visited = v.last.visited;
+    stats->written = (long long)v.updated_h.p[0]; stats->removed = (long long)v.updated_h.p[1]; stats->reset = (long long)v.updated_h.p[2]; stats->added = (long long)v.updated_h.p[3];
     return NALO_OK;
 }
 

@@ -3,6 +3,7 @@
 // WITHOUT FMA contraction: every expression below is the header's definition, one rounding per operation.
 #include "nalo_internal.h"
 #include "tsdf_device.h"
+#include "tsdf_voxel_device.h"
 
 namespace nalo {
 
@@ -11,37 +12,20 @@ namespace nalo {
 // A workgroup is (1 << txl) lanes along x by (256 >> txl) rows of the box, so that a narrow box does not idle most of a wave.
 // Colour (nalo_tsdf_color_enable) is a compile-time flag: the uncoloured kernel is the instantiation without it. The coloured one keeps w0 and the colour bytes
 // of the voxels it updates and touches the three colour planes only in lanes that store tsdf and weight, so the visited-but-untouched box moves no colour byte.
-struct TsdfRow { float m1y, m2z, m5y, m6z, m9y, m10z; };                        // the products of M with py and pz: a row's own, the same operands as per voxel
-
-// kColour: a voxel that is updated also hands back the weight BEFORE the update and its pixel's colour bytes, packed B | G << 8 | R << 16
+// kColour: a voxel that is updated also hands back the weight BEFORE the update and its pixel's colour bytes, packed B | G << 8 | R << 16. The predicate and d
+// are tsdf_voxel_device.h's, the one statement nalo_tsdf_replace_depth's kernel reads too
 template <bool kColour>
 __device__ __forceinline__ bool tsdf_voxel(const TsdfIntegrateDev& P, const TsdfRow& R, int i, float& t, float& w, float& wb, unsigned& bgr) {
-    const float px = tsdf_centre(P.g, 0, i);
-    const float xc = ((P.M[0] * px + R.m1y) + R.m2z) + P.M[3];
-    const float yc = ((P.M[4] * px + R.m5y) + R.m6z) + P.M[7];
-    const float zc = ((P.M[8] * px + R.m9y) + R.m10z) + P.M[11];
-    const float uf = ((P.fx * (xc / zc)) + P.cx) + 0.5f;
-    const float vf = ((P.fy * (yc / zc)) + P.cy) + 0.5f;
-    if (!(zc > 0.0f && uf >= 0.0f && uf < (float)P.w && vf >= 0.0f && vf < (float)P.h)) return false;
-    const int pu = (int)uf, pv = (int)vf;                                       // 0 <= pu < w, 0 <= pv < h: the comparisons above were made in float
-    const float D = *reinterpret_cast<const float*>(P.depth + (long long)pv * P.sy + (long long)pu * P.sx);
-    if (!(D >= P.min_depth && D <= P.max_depth)) return false;
-    const float sdf = D - zc;
-    if (sdf < -P.trunc) return false;
-    const float d = fminf(1.0f, sdf / P.trunc);
+    float d; int pu, pv;
+    if (!tsdf_sample<false>(P.g, P, P.trunc, 1.0f, R, i, d, pu, pv)) return false;
     const float t0 = t, w0 = w;
     t = (t0 * w0 + d) / (w0 + 1.0f);
     w = fminf(w0 + 1.0f, P.max_weight);
     if constexpr (kColour) {
-        const unsigned char* px = P.colour + (long long)pv * P.csy + (long long)pu * P.csx;
         wb = w0;
-        bgr = (unsigned)px[P.csc[0]] | ((unsigned)px[P.csc[1]] << 8) | ((unsigned)px[P.csc[2]] << 16);
+        bgr = tsdf_pixel_bgr(P, pu, pv);
     }
     return true;
-}
-// plane X of an updated voxel: X = (X0 * w0 + (float)x) / (w0 + 1.0f), x the pixel's byte for that plane
-__device__ __forceinline__ float tsdf_colour(float x0, float w0, unsigned bgr, int plane) {
-    return (x0 * w0 + (float)((bgr >> (8 * plane)) & 0xFFu)) / (w0 + 1.0f);
 }
 
 template <bool kColour>
@@ -60,7 +44,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfIntegrateDev P,
         const long long g = (rb & ~3LL) + 4LL * ((long long)bx * tx + lx);
         if (g < re) {
             const float py = tsdf_centre(P.g, 1, j), pz = tsdf_centre(P.g, 2, k);
-            const TsdfRow R = {P.M[1] * py, P.M[2] * pz, P.M[5] * py, P.M[6] * pz, P.M[9] * py, P.M[10] * pz};
+            const TsdfRow R = tsdf_row(P.M, py, pz);
             if (g >= rb && g + 4 <= re) {
                 float4 t = *reinterpret_cast<const float4*>(P.g.tsdf + g), w = *reinterpret_cast<const float4*>(P.g.weight + g);
                 const int i = (int)(g - base);

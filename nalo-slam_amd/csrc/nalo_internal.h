@@ -213,6 +213,10 @@ struct nalo_ctx {
     nalo::DenseArchive* dmap = nullptr;      // the dense map: FrameHessian::mapPoints on the device (host_map.hip); NULL until nalo_map_dense_enable
     nalo::TsdfVolume* tsdf = nullptr;        // the TSDF volume and its scratch (host_tsdf.hip); NULL until nalo_tsdf_create
     nalo::TsdfArchive* tsdf_archive = nullptr;   // the welded mesh archive (nalo_tsdf_archive_*, host_tsdf.hip); NULL until nalo_tsdf_archive_enable. It outlives volumes
+    // the fusion log (nalo_tsdf_log_*, host_tsdf.hip): what nalo_tsdf_replace_frame removes by, in the order the frames were first fused. Host memory only; the
+    // switch outlives volumes, the entries do not. Off, no call looks at it
+    bool tsdf_log_on = false;
+    std::vector<nalo_tsdf_log_entry> tsdf_log;
     // the keyframe graph (nalo_map_graph_*, host_map.hip): EnergyFunctional::connectivityMap's keys, (host frame_id << 32) + target frame_id, with the count [1] of
     // marginalised residuals; the count [0] of live residuals is taken from the resident slots when the graph is read
     bool graph_on = false;
@@ -504,6 +508,23 @@ struct TsdfIntegrateDev {
     const unsigned char* colour; long long csy, csx, csc[3];
 };
 int tsdf_integrate_launch(nalo_ctx* c, const TsdfIntegrateDev& D);
+// nalo_tsdf_replace_depth (kernels_tsdf_replace.hip, built without FMA contraction): remove on one side, then add on the other, per voxel, in one launch over the
+// hull of the two sides' boxes. A side is a camera at an estimate and its planes; the predicate reads it as it reads TsdfIntegrateDev (tsdf_voxel_device.h).
+struct TsdfSideDev {
+    int on, coloured;                                                           // on: the side exists and its box is not empty; coloured: it moves the colour words
+    int lo[3], hi[3];                                                           // the voxels the side may touch, hi exclusive: its culling box (remove: cut by the caller's box)
+    float M[12], fx, fy, cx, cy, min_depth, max_depth, s;                      // M: nalo_tsdf_est_world_to_cam; s: (float)est.s
+    const char* depth; long long sy, sx; int w, h;                              // the plane by byte strides
+    const unsigned char* colour; long long csy, csx, csc[3];                    // as TsdfIntegrateDev's
+};
+struct TsdfReplaceDev {
+    TsdfGridDev g;                                                              // g.col != NULL selects the coloured instantiation (a side is coloured); tsdf, weight and col are written
+    int lo[3], hi[3];                                                           // the hull of the sides that are on, hi exclusive, not empty
+    float trunc, max_weight;
+    TsdfSideDev rem, add;
+    unsigned long long* counts;                                                 // [4], zero before: written, removed, reset, added
+};
+int tsdf_replace_launch(nalo_ctx* c, const TsdfReplaceDev& D);
 int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
 // one array's sub-block [lo, lo + size) to (to_volume = 0) or from (1) a contiguous block, x fastest
 int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume);
