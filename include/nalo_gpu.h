@@ -1942,6 +1942,40 @@ int nalo_map_dense_cloud(nalo_ctx* ctx, nalo_map_dense_cloud_args* args);
  *     NALO_ERR_STATE: no volume, the log off, no dense archive, a sharded window, a list shorter than n_records (the dense archive was reset). NALO_ERR_ARG: a
  *     frame_id the dense archive has never seen, NULL with no entry, a K, estimate or range nalo_tsdf_replace_depth refuses. A refusal queues nothing and leaves
  *     volume, colour, log and nalo_tsdf_last as they were.
+ *
+ * The window replacement. nalo_ba_optimize moves every keyframe of the window at once and nalo_ba_plane_scale_fix rescales all of them; looping the single
+ * replacement sweeps nearly the same voxels once per frame. An ordered list of n pairs, 1 <= n <= 16 (the largest window the library accepts), each a
+ * nalo_tsdf_replace_args: a remove side or NULL, an add side or NULL, its own use_box / lo / size, its own producer_stream.
+ *   DEFINED: the result is the volume after nalo_tsdf_replace_depth(pair[0]), nalo_tsdf_replace_depth(pair[1]), ... nalo_tsdf_replace_depth(pair[n-1]) in that
+ *     order, bit for bit in tsdf, weight and the colour words. A replacement's arithmetic at a voxel reads only that voxel's own tsdf, weight and colour words,
+ *     so the chain is computed per voxel in registers: ONE launch over the hull of all sides' culling boxes (each side's box computed exactly as for the single
+ *     call, the remove sides cut by their pair's box), every voxel loaded at most once and stored at most once; rows of the hull in no side's box are left before
+ *     any voxel is loaded. The order is part of the definition: pair k's removal sees what pair k - 1's add left - a weight that sat at max_weight, a voxel one
+ *     pair reset and a later one adds into. The colour words go through the chain side by side. No float atomic, one lane owns a voxel: the same bytes on every
+ *     run. n = 1 IS nalo_tsdf_replace_depth, nalo_tsdf_last and nalo_tsdf_replace_last included.
+ * nalo_tsdf_replace_depth_n   stream order as nalo_tsdf_replace_depth: the main stream waits on the device for every distinct producer_stream of the list, one
+ *     event is recorded behind the kernel, nalo_tsdf_release applies; with the volume allocated the call makes no host wait (the sides travel through one of four
+ *     pinned staging slots, each guarded by an event: only a fifth call queued behind four that have not started waits, for the first one's copy). Every pair is
+ *     checked before anything is queued. Refusals queue nothing and leave volume, colour, log and nalo_tsdf_last as they were: NALO_ERR_ARG for n outside
+ *     1..16, a NULL list, a pair with both sides NULL; for a pair nalo_tsdf_replace_depth would refuse, that call's code, with "pair k" in the message.
+ *     Afterwards nalo_tsdf_last reports the hull, visited = its voxel count, updated = written_total: the voxels where ANY pair fired, each counted once.
+ *     nalo_tsdf_replace_last reports the hull, written = written_total, and removed / reset / added summed over the pairs.
+ * nalo_tsdf_replace_last_n    waits once: `total` (may be NULL) as nalo_tsdf_replace_last, and per pair removed, reset, added and written (the voxels where
+ *     that pair fired at all): min(n, cap) rows are copied, *n is the number there are. Exact integers: wave ballots and population counts, summed per workgroup
+ *     in LDS, one atomic instruction per counter per workgroup. NALO_ERR_STATE when the last operation on the volume was not a window replacement.
+ * nalo_tsdf_replace_frames    DEFINED as nalo_tsdf_replace_frame(frame_id[k], has_est[k] ? &est_new[k] : NULL, K, min_depth, max_depth) for k = 0 .. n - 1 in
+ *     order: the volume and the log afterwards are those of that loop, bit for bit, and nalo_tsdf_log_get's order (first fusion) with them. The work is the
+ *     plane builds, one after the other on the context's stream into a pool of planes the volume owns (one per frame, two when its list has grown; it grows on
+ *     demand and goes with the volume), and the ONE launch above; each entry's resident box cuts its pair's remove side. All or nothing: every refusal of
+ *     nalo_tsdf_replace_frame, for any k, refuses the whole call ("frame k" in the message), and a frame_id that appears twice is NALO_ERR_ARG (the loop would
+ *     allow it; one transaction on the log does not need to). A refused call leaves log, volume, colour and nalo_tsdf_last unchanged; an accepted one updates
+ *     the log for all pairs. skip_unchanged != 0: a frame that has an entry, whose est_new, K and range equal the entry's bit for bit and whose dense list is as
+ *     long as n_records, is no pair; its entry stays as it is and it is counted in n_skipped. A call whose frames are all skipped launches nothing, returns
+ *     NALO_OK and leaves nalo_tsdf_last as it was. nalo_tsdf_replace_frame, nalo_tsdf_integrate_frame and nalo_tsdf_align_frame keep their planes.
+ * nalo_tsdf_replace_frames_plan   host only, no context: the list's own checks and skip_unchanged's predicate on a log given as an array. list_len[k]: the
+ *     length of frame k's dense list now (NULL: nothing is skipped). skip[k] = 1 for a skipped frame, written for every k < n on NALO_OK. NALO_ERR_ARG: NULL
+ *     args or skip, n outside 1..16, a NULL frame_id list, a frame_id twice, and - for a frame that has an estimate - a pose that is not finite, an s that is
+ *     not finite or <= 0, a K that is not finite, a range that is not finite or has min_depth > max_depth.
  * nalo_tsdf_est_world_to_cam   host only, no context: the M above. NALO_ERR_ARG for a non-finite pose or an s that is not finite or <= 0.
  * nalo_tsdf_frustum_box_est    host only, no context: nalo_tsdf_frustum_box with z = max_depth + trunc / s in double and each far corner at
  *     (((c0 X + c1 Y) + c2 z) * s) + c3. For s == 1 it is nalo_tsdf_frustum_box's box exactly (one function computes both). It is conservative for every voxel
@@ -2093,13 +2127,26 @@ typedef struct nalo_tsdf_log_entry {
 int nalo_tsdf_log_enable(nalo_ctx* ctx, int on);                                       /* host only, launches nothing */
 int nalo_tsdf_log_get(nalo_ctx* ctx, nalo_tsdf_log_entry* out, int cap, int* n);       /* host only, launches nothing */
 int nalo_tsdf_replace_frame(nalo_ctx* ctx, int frame_id, const nalo_tsdf_align_est* est_new /* NULL: remove only */, const float K[4], float min_depth, float max_depth);
+typedef struct nalo_tsdf_replace_pair_stats { long long removed, reset, added, written; } nalo_tsdf_replace_pair_stats;
+int nalo_tsdf_replace_depth_n(nalo_ctx* ctx, const nalo_tsdf_replace_args* pairs, int n);       /* 1 <= n <= 16 */
+int nalo_tsdf_replace_last_n(nalo_ctx* ctx, nalo_tsdf_replace_stats* total /* may be NULL */, nalo_tsdf_replace_pair_stats* per_pair, int cap, int* n);
+typedef struct nalo_tsdf_replace_frames_args {
+    int n; const int* frame_id;             /* 1 <= n <= 16, no frame_id twice */
+    const nalo_tsdf_align_est* est_new;     /* [n]; NULL: remove only, for every frame */
+    const unsigned char* has_est;           /* optional [n]: 0 = this frame is removed only; NULL = all have one */
+    float K[4]; float min_depth, max_depth;
+    int skip_unchanged;
+    int n_skipped;                          /* out */
+} nalo_tsdf_replace_frames_args;
+int nalo_tsdf_replace_frames(nalo_ctx* ctx, nalo_tsdf_replace_frames_args* args);
+int nalo_tsdf_replace_frames_plan(const nalo_tsdf_replace_frames_args* args, const nalo_tsdf_log_entry* log, int n_log, const int* list_len, unsigned char* skip);   /* host only, no context */
 int nalo_tsdf_est_world_to_cam(const nalo_tsdf_align_est* est, float M[12]);   /* host only, no context */
 int nalo_tsdf_frustum_box_est(const nalo_tsdf_desc* desc, int w, int h, const float K[4], const nalo_tsdf_align_est* est, float max_depth, int lo[3], int hi[3]);   /* host only, no context */
 int nalo_tsdf_box_shift(const int dims[3], const int shift[3], int lo[3], int size[3]);   /* host only, no context */
 
 /* ------------------------------------------------------------------------------------------------
  * Profiling: per-kernel HIP-event timing on the ctx stream. Names: "trk_eval", "ba_linearize",
- * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_replace", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_align", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
+ * "ba_sc", "ba_reduce", "ba_resub", "pyramid", "trk_lm", "imm_trace", "imm_optimize", "pixsel", "dist_bfs", "dense_bbox", "dense_map", "dense_extent", "dense_boxes", "dense_update_map", "map_dense_world_points", "map_dense_cloud", "ingest", "tsdf_integrate", "tsdf_replace", "tsdf_replace_n", "tsdf_surface", "tsdf_mesh", "tsdf_raycast", "tsdf_align", "tsdf_shift", "tsdf_archive" (the key pass and the append of nalo_tsdf_archive_mesh, not its mesh), "map_render_tris" (the triangle pass of nalo_map_render_mesh). Enable, run, then query (sync inside).
  * nalo_profile_select(ctx, name) restricts the brackets to ONE scope (NULL = all): a recorded event pair costs ~10 us of pipeline bubbles on a
  * latency-bound window, so a timed run brackets only the kernel it reports ("ba_linearize" carries its timestamps in the dispatch itself).
  * ------------------------------------------------------------------------------------------------ */

@@ -47,6 +47,7 @@ EXPORTS = [
     "nalo_tsdf_shift", "nalo_tsdf_geometry", "nalo_tsdf_shift_for", "nalo_tsdf_shift_boxes",
     "nalo_tsdf_replace_depth", "nalo_tsdf_replace_last", "nalo_tsdf_replace_frame", "nalo_tsdf_log_enable", "nalo_tsdf_log_get", "nalo_tsdf_est_world_to_cam", "nalo_tsdf_frustum_box_est",
     "nalo_tsdf_box_shift",
+    "nalo_tsdf_replace_depth_n", "nalo_tsdf_replace_last_n", "nalo_tsdf_replace_frames", "nalo_tsdf_replace_frames_plan",
     "nalo_tsdf_archive_enable", "nalo_tsdf_archive_disable", "nalo_tsdf_archive_reset", "nalo_tsdf_archive_mesh", "nalo_tsdf_archive_stats", "nalo_tsdf_archive_get", "nalo_tsdf_archive_view", "nalo_tsdf_follow",
     "nalo_imm_create", "nalo_imm_trace", "nalo_imm_optimize", "nalo_imm_resident_set", "nalo_imm_resident_optimize", "nalo_imm_resident_trace", "nalo_imm_resident_get", "nalo_imm_resident_set_type", "nalo_imm_resident_activate", "nalo_imm_activate_last",
     "nalo_imm_resident_carry", "nalo_imm_resident_carry_map", "nalo_imm_resident_carry_last", "nalo_imm_resident_get_points", "nalo_init_calc_res_and_gs", "nalo_init_do_step", "nalo_init_set_first", "nalo_init_track_frame", "nalo_init_get_state", "nalo_init_get_points", "nalo_init_set_state", "nalo_init_set_points", "nalo_init_get_carried", "nalo_init_sweep", "nalo_init_depth_image", "nalo_dist_make_map", "nalo_pixsel_make_hists",
@@ -271,6 +272,15 @@ class TsdfLogEntry(C.Structure):                          # nalo_tsdf_log_entry
                 ("lo", C.c_int * 3), ("size", C.c_int * 3), ("coloured", C.c_int)]
 
 
+class TsdfReplacePairStats(C.Structure):                  # nalo_tsdf_replace_pair_stats
+    _fields_ = [("removed", C.c_longlong), ("reset", C.c_longlong), ("added", C.c_longlong), ("written", C.c_longlong)]
+
+
+class TsdfReplaceFramesArgs(C.Structure):                 # nalo_tsdf_replace_frames_args; tsdf_replace_frames_args() builds one
+    _fields_ = [("n", C.c_int), ("frame_id", c_ip), ("est_new", C.POINTER(TsdfAlignEst)), ("has_est", c_u8p), ("K", C.c_float * 4), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("skip_unchanged", C.c_int), ("n_skipped", C.c_int)]
+
+
 class TsdfGeometry(C.Structure):                          # struct nalo_tsdf_geometry
     _fields_ = [("desc", TsdfDesc), ("origin0", C.c_float * 3), ("base", C.c_int * 3)]
 
@@ -415,6 +425,7 @@ def host_lib():
         L.nalo_tsdf_est_world_to_cam.argtypes = [C.POINTER(TsdfAlignEst), c_fp]
         L.nalo_tsdf_frustum_box_est.argtypes = [C.POINTER(TsdfDesc), C.c_int, C.c_int, c_fp, C.POINTER(TsdfAlignEst), C.c_float, c_ip, c_ip]
         L.nalo_tsdf_box_shift.argtypes = [c_ip, c_ip, c_ip, c_ip]
+        L.nalo_tsdf_replace_frames_plan.argtypes = [C.POINTER(TsdfReplaceFramesArgs), C.POINTER(TsdfLogEntry), C.c_int, c_ip, c_u8p]
         L.nalo_io_write_ply_mesh.argtypes = [C.c_char_p, C.c_longlong, c_fp, C.c_longlong, c_ip]
         L.nalo_io_write_ply_mesh_rgba.argtypes = [C.c_char_p, C.c_longlong, c_fp, c_u8p, C.c_longlong, c_ip]
         _HOST_LIB = L
@@ -612,6 +623,52 @@ def tsdf_side(depth, K, cam_to_world, s, min_depth, max_depth, colour=None, colo
     elif torch is not None and isinstance(depth, torch.Tensor):
         sd.stream = torch.cuda.current_stream(depth.device).cuda_stream
     return sd
+
+
+def tsdf_replace_frames_args(frame_ids, cam_to_world, K, min_depth, max_depth, s=1.0, skip_unchanged=False):
+    """nalo_tsdf_replace_frames_args (a TsdfReplaceFramesArgs): frame_ids a list of ints; cam_to_world a list of [3][4] poses, None in it for a frame that is
+    removed only, or None for the whole list (every frame removed only); s a scale or a list of them. The struct keeps its arrays alive. n may be anything:
+    the library refuses what it refuses"""
+    a = TsdfReplaceFramesArgs()
+    n = len(frame_ids)
+    ids = np.ascontiguousarray(frame_ids, np.int32).reshape(-1)
+    a.n, a.frame_id = n, _i(ids) if n else None
+    a.keep = [ids]
+    if cam_to_world is not None:
+        assert len(cam_to_world) == n
+        ss = list(s) if np.ndim(s) else [s] * n
+        est = (TsdfAlignEst * max(n, 1))()
+        has = np.zeros(max(n, 1), np.uint8)
+        for k, m in enumerate(cam_to_world):
+            if m is not None:
+                est[k], has[k] = tsdf_align_est(m, ss[k]), 1
+        a.est_new, a.has_est = est, has.ctypes.data_as(c_u8p)
+        a.keep += [est, has]
+    a.K[:] = [float(v) for v in K]
+    a.min_depth, a.max_depth, a.skip_unchanged = float(min_depth), float(max_depth), int(bool(skip_unchanged))
+    return a
+
+
+def tsdf_log_entry(frame_id, n_records, cam_to_world, s, K, min_depth, max_depth, lo=(0, 0, 0), size=(1, 1, 1), coloured=False):
+    """a nalo_tsdf_log_entry (a TsdfLogEntry) built by hand, for tsdf_replace_frames_plan"""
+    e = TsdfLogEntry()
+    e.frame_id, e.n_records, e.est = int(frame_id), int(n_records), tsdf_align_est(cam_to_world, s)
+    e.K[:] = [float(v) for v in K]
+    e.min_depth, e.max_depth, e.coloured = float(min_depth), float(max_depth), int(bool(coloured))
+    e.lo[:], e.size[:] = [int(v) for v in lo], [int(v) for v in size]
+    return e
+
+
+def tsdf_replace_frames_plan(args, log, list_len):
+    """nalo_tsdf_replace_frames_plan, host only: the list's own checks and skip_unchanged's predicate. args: tsdf_replace_frames_args(); log: a list of
+    TsdfLogEntry; list_len: the length of each frame's dense list now, or None. Returns the skip flags as a list of bools; raises NaloError on a refusal"""
+    arr = (TsdfLogEntry * max(len(log), 1))(*log)
+    ll = None if list_len is None else np.ascontiguousarray(list_len, np.int32)
+    skip = np.zeros(64, np.uint8)
+    rc = host_lib().nalo_tsdf_replace_frames_plan(C.byref(args), arr, len(log), None if ll is None else _i(ll), skip.ctypes.data_as(c_u8p))
+    if rc != 0:
+        raise NaloError("nalo_tsdf_replace_frames_plan: bad argument (%d)" % rc)
+    return [bool(v) for v in skip[:args.n]]
 
 
 def write_ply_mesh(path, xyz, tri, rgba=None):
@@ -826,6 +883,9 @@ def load():
     L.nalo_tsdf_replace_depth.argtypes = [vp, C.POINTER(TsdfReplaceArgs)]
     L.nalo_tsdf_replace_last.argtypes = [vp, C.POINTER(TsdfReplaceStats)]
     L.nalo_tsdf_replace_frame.argtypes = [vp, C.c_int, C.POINTER(TsdfAlignEst), c_fp, C.c_float, C.c_float]
+    L.nalo_tsdf_replace_depth_n.argtypes = [vp, C.POINTER(TsdfReplaceArgs), C.c_int]
+    L.nalo_tsdf_replace_last_n.argtypes = [vp, C.POINTER(TsdfReplaceStats), C.POINTER(TsdfReplacePairStats), C.c_int, c_ip]
+    L.nalo_tsdf_replace_frames.argtypes = [vp, C.POINTER(TsdfReplaceFramesArgs)]
     L.nalo_tsdf_log_enable.argtypes = [vp, C.c_int]
     L.nalo_tsdf_log_get.argtypes = [vp, C.POINTER(TsdfLogEntry), C.c_int, c_ip]
     L.nalo_tsdf_archive_enable.argtypes = [vp]
@@ -2005,6 +2065,51 @@ class Context:
         assert Kf.size == 4
         e = None if cam_to_world is None else C.byref(tsdf_align_est(cam_to_world, s))
         self._ck(self.L.nalo_tsdf_replace_frame(self.h_, int(frame_id), e, _f(Kf), C.c_float(min_depth), C.c_float(max_depth)))
+
+    def tsdf_replace_depth_n(self, pairs, release=True):
+        """nalo_tsdf_replace_depth_n: the chain tsdf_replace_depth(pairs[0]), tsdf_replace_depth(pairs[1]), ... per voxel in ONE launch. pairs: a list (1 .. 16) of
+        dict(remove=, add=, box=, stream=) with tsdf_replace_depth's meanings, or of (remove, add) / (remove, add, box) tuples. Every distinct producer stream of
+        the list is waited for on the device, and released when `release`. Returns without waiting."""
+        n = len(pairs)
+        arr = (TsdfReplaceArgs * max(n, 1))()
+        streams = []
+        for k, p in enumerate(pairs):
+            if not isinstance(p, dict):
+                p = dict(zip(("remove", "add", "box"), p))
+            remove, add, box, stream = p.get("remove"), p.get("add"), p.get("box"), p.get("stream")
+            a = arr[k]
+            if remove is not None:
+                a.remove = C.pointer(remove)
+            if add is not None:
+                a.add = C.pointer(add)
+            if box is not None:
+                a.use_box = 1
+                a.lo[:] = [int(v) for v in box[0]]
+                a.size[:] = [int(v) for v in box[1]]
+            if stream is None:
+                stream = next((sd.stream for sd in (add, remove) if sd is not None and getattr(sd, "stream", 0)), 0)
+            a.producer_stream = stream or None
+            if stream not in streams:
+                streams.append(stream)
+        self._ck(self.L.nalo_tsdf_replace_depth_n(self.h_, arr if n else None, n))
+        if release:
+            for st in streams:
+                self.tsdf_release(st)
+
+    def tsdf_replace_last_n(self):
+        """nalo_tsdf_replace_last_n -> (total, per_pair): total as tsdf_replace_last (written: the voxels where any pair fired, each once), per_pair a list of
+        dict(removed, reset, added, written); waits"""
+        st, rows, n = TsdfReplaceStats(), (TsdfReplacePairStats * 16)(), np.zeros(1, np.int32)
+        self._ck(self.L.nalo_tsdf_replace_last_n(self.h_, C.byref(st), rows, 16, _i(n)))
+        total = dict(lo=tuple(st.lo), hi=tuple(st.hi), visited=int(st.visited), removed=int(st.removed), reset=int(st.reset), added=int(st.added), written=int(st.written))
+        return total, [dict(removed=int(r.removed), reset=int(r.reset), added=int(r.added), written=int(r.written)) for r in rows[:int(n[0])]]
+
+    def tsdf_replace_frames(self, frame_ids, cam_to_world, K, min_depth, max_depth, s=1.0, skip_unchanged=False):
+        """nalo_tsdf_replace_frames: tsdf_replace_frame for every frame of the list, in order, in ONE launch, the log updated all or nothing. Arguments as
+        tsdf_replace_frames_args(). Returns n_skipped."""
+        a = tsdf_replace_frames_args(frame_ids, cam_to_world, K, min_depth, max_depth, s, skip_unchanged)
+        self._ck(self.L.nalo_tsdf_replace_frames(self.h_, C.byref(a)))
+        return int(a.n_skipped)
 
     def tsdf_log_enable(self, on=True):
         """nalo_tsdf_log_enable: the fusion log, what tsdf_replace_frame removes by; off by default, and off it changes nothing. Turning it off clears it"""

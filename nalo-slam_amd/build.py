@@ -4,9 +4,9 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = ["host_api.hip", "host_ba.hip", "kernels_pyramid.hip", "kernels_ingest_dev.hip", "kernels_handoff.hip", "kernels_tracker.hip", "kernels_trk_lm.hip", "kernels_ba.hip", "kernels_ba_lin.hip", "kernels_ba_carry.hip", "kernels_dense.hip", "kernels_plane.hip", "kernels_imm.hip", "kernels_imm_carry.hip", "kernels_map.hip", "kernels_map_render.hip", "kernels_map_render_mesh.hip", "host_map_render_mesh.cpp", "host_map.hip", "kernels_tsdf.hip", "kernels_tsdf_replace.hip", "kernels_tsdf_mesh.hip", "kernels_tsdf_raycast.hip", "kernels_tsdf_align.hip", "kernels_tsdf_archive.hip", "host_tsdf.hip", "host_tsdf.cpp", "kernels_init.hip", "kernels_init_window.hip", "kernels_pixsel.hip", "kernels_depth_image.hip", "kernels_window_plot.hip", "kernels_init_plot.hip", "kernels_residual_plot.hip", "host_io.cpp", "host_ground.cpp", "host_rccl.hip", "host_init.hip"]
+SRC = ["host_api.hip", "host_ba.hip", "kernels_pyramid.hip", "kernels_ingest_dev.hip", "kernels_handoff.hip", "kernels_tracker.hip", "kernels_trk_lm.hip", "kernels_ba.hip", "kernels_ba_lin.hip", "kernels_ba_carry.hip", "kernels_dense.hip", "kernels_plane.hip", "kernels_imm.hip", "kernels_imm_carry.hip", "kernels_map.hip", "kernels_map_render.hip", "kernels_map_render_mesh.hip", "host_map_render_mesh.cpp", "host_map.hip", "kernels_tsdf.hip", "kernels_tsdf_replace.hip", "kernels_tsdf_replace_n.hip", "kernels_tsdf_mesh.hip", "kernels_tsdf_raycast.hip", "kernels_tsdf_align.hip", "kernels_tsdf_archive.hip", "host_tsdf.hip", "host_tsdf.cpp", "kernels_init.hip", "kernels_init_window.hip", "kernels_pixsel.hip", "kernels_depth_image.hip", "kernels_window_plot.hip", "kernels_init_plot.hip", "kernels_residual_plot.hip", "host_io.cpp", "host_ground.cpp", "host_rccl.hip", "host_init.hip"]
 OUT = os.path.join(HERE, "libnalo_gpu.so")
-NO_CONTRACT = {"kernels_pyramid.hip", "kernels_ingest_dev.hip", "kernels_plane.hip", "kernels_imm.hip", "kernels_imm_carry.hip", "kernels_map.hip", "kernels_map_render.hip", "kernels_map_render_mesh.hip", "host_map_render_mesh.cpp", "kernels_init.hip", "kernels_init_window.hip", "kernels_pixsel.hip", "kernels_depth_image.hip", "kernels_window_plot.hip", "kernels_init_plot.hip", "kernels_residual_plot.hip", "host_init.hip", "host_ground.cpp", "kernels_tsdf.hip", "kernels_tsdf_replace.hip", "kernels_tsdf_mesh.hip", "kernels_tsdf_raycast.hip", "kernels_tsdf_align.hip", "host_tsdf.cpp"}   # a1 is bit-exact vs the reference's scalar fp32 code: no FMA contraction
+NO_CONTRACT = {"kernels_pyramid.hip", "kernels_ingest_dev.hip", "kernels_plane.hip", "kernels_imm.hip", "kernels_imm_carry.hip", "kernels_map.hip", "kernels_map_render.hip", "kernels_map_render_mesh.hip", "host_map_render_mesh.cpp", "kernels_init.hip", "kernels_init_window.hip", "kernels_pixsel.hip", "kernels_depth_image.hip", "kernels_window_plot.hip", "kernels_init_plot.hip", "kernels_residual_plot.hip", "host_init.hip", "host_ground.cpp", "kernels_tsdf.hip", "kernels_tsdf_replace.hip", "kernels_tsdf_replace_n.hip", "kernels_tsdf_mesh.hip", "kernels_tsdf_raycast.hip", "kernels_tsdf_align.hip", "host_tsdf.cpp"}   # a1 is bit-exact vs the reference's scalar fp32 code: no FMA contraction
 
 
 def build(force=False, verbose=False):

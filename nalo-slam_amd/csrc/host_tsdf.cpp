@@ -2,6 +2,7 @@
 // nalo_tsdf_frustum_box[_est], the mesh's triangle table and the geometry of a shifted volume (the origin, nalo_tsdf_shift_for, nalo_tsdf_shift_boxes, nalo_tsdf_box_shift). Plain C++ with no device call, built without FMA contraction: every
 // line below is the operation order the header defines, in double (the shifted origin: in float).
 #include <cmath>
+#include <cstring>
 
 #include "host_math.h"
 #include "tsdf_host.h"
@@ -170,6 +171,44 @@ extern "C" int nalo_tsdf_box_shift(const int dims[3], const int shift[3], int lo
     }
     for (int a = 0; a < 3; ++a) { lo[a] = empty ? 0 : (int)l[a]; size[a] = empty ? 0 : (int)(u[a] - l[a]); }
     return NALO_OK;
+}
+
+// nalo_tsdf_replace_frames' host half that needs neither a context nor a device: the list's own refusals, and which frames skip_unchanged leaves out
+const char* nalo::tsdf_replace_frames_plan(const nalo_tsdf_replace_frames_args* a, const nalo_tsdf_log_entry* log, int n_log, const int* list_len, unsigned char* skip) {
+    if (!a || !skip || n_log < 0 || (n_log > 0 && !log)) return "bad argument";
+    if (a->n < 1 || a->n > 16) return "n outside 1 .. 16";
+    if (!a->frame_id) return "bad argument";
+    for (int k = 0; k < a->n; ++k) skip[k] = 0;
+    for (int k = 1; k < a->n; ++k) for (int q = 0; q < k; ++q) if (a->frame_id[q] == a->frame_id[k]) return "a frame_id appears twice";
+    bool any_est = false;
+    for (int k = 0; k < a->n; ++k) {
+        if (!a->est_new || (a->has_est && !a->has_est[k])) continue;
+        any_est = true;
+        const nalo_tsdf_align_est& e = a->est_new[k];
+        for (int i = 0; i < 12; ++i) if (!std::isfinite(e.camToWorld[i])) return "an estimate's camToWorld is not finite";
+        if (!std::isfinite(e.s) || e.s <= 0.0) return "an estimate's s is not finite or <= 0";
+    }
+    if (any_est) {
+        for (int i = 0; i < 4; ++i) if (!std::isfinite(a->K[i])) return "K is not finite";
+        if (!std::isfinite(a->min_depth) || !std::isfinite(a->max_depth) || a->min_depth > a->max_depth) return "min_depth / max_depth not finite, or min_depth > max_depth";
+    }
+    if (!a->skip_unchanged) return nullptr;
+    // unchanged: the frame has an entry, its estimate, K and range are the entry's bit for bit, and its dense list is as long as when it was fused
+    for (int k = 0; k < a->n; ++k) {
+        if (!a->est_new || (a->has_est && !a->has_est[k]) || !list_len) continue;
+        for (int q = 0; q < n_log; ++q) {
+            const nalo_tsdf_log_entry& e = log[q];
+            if (e.frame_id != a->frame_id[k]) continue;
+            skip[k] = std::memcmp(e.est.camToWorld, a->est_new[k].camToWorld, sizeof e.est.camToWorld) == 0 && std::memcmp(&e.est.s, &a->est_new[k].s, sizeof e.est.s) == 0 &&
+                      std::memcmp(e.K, a->K, sizeof e.K) == 0 && std::memcmp(&e.min_depth, &a->min_depth, sizeof(float)) == 0 &&
+                      std::memcmp(&e.max_depth, &a->max_depth, sizeof(float)) == 0 && list_len[k] == e.n_records;
+            break;
+        }
+    }
+    return nullptr;
+}
+extern "C" int nalo_tsdf_replace_frames_plan(const nalo_tsdf_replace_frames_args* args, const nalo_tsdf_log_entry* log, int n_log, const int* list_len, unsigned char* skip) {
+    return nalo::tsdf_replace_frames_plan(args, log, n_log, list_len, skip) ? NALO_ERR_ARG : NALO_OK;
 }
 
 extern "C" int nalo_tsdf_mesh_table(signed char out[6][16][6]) {

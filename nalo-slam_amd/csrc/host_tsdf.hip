@@ -1,5 +1,5 @@
 // The TSDF volume of a context (include/nalo_gpu.h, "tsdf=1"): its memory and scratch, the checks of every call, the stream order of an integration. The
-// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_replace.hip, kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table, the alignment's step).
+// arithmetic lives in kernels_tsdf.hip, kernels_tsdf_replace.hip, kernels_tsdf_replace_n.hip, kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip (device; the grid's own definitions in tsdf_device.h) and host_tsdf.cpp (worldToCam, the culling box, the mesh's triangle table, the alignment's step).
 #include <algorithm>
 #include <cmath>
 
@@ -17,7 +17,13 @@ struct TsdfVolume {
     Event ev_read;                                   // behind the last kernel that read a caller's depth plane (nalo_tsdf_release)
     bool read_pending = false;
     DevBuf<unsigned long long> updated; HostBuf<unsigned long long> updated_h;
-    nalo_tsdf_stats last{}; bool have_last = false, last_replace = false;   // updated: [4], the integration's count in [0]; a replacement's written, removed, reset, added
+    nalo_tsdf_stats last{}; bool have_last = false, last_replace = false;   // updated: the integration's count in [0]; a replacement's written, removed, reset, added in [0..4)
+    int last_n = 0;                                  // > 0: the last operation was a window replacement of last_n pairs: updated holds [4 last_n + 1], per pair removed, reset, added, written, then written_total
+    // nalo_tsdf_replace_depth_n: the side tables. kTsdfSideRing slots of 2 * kTsdfReplaceMaxPairs sides each, in pinned staging and on the device; side_ev[q] lies behind
+    // the copy out of staging slot q, and a call that comes round to a slot waits for it (only when kTsdfSideRing calls are still queued)
+    HostBuf<TsdfSideDev> side_stage; DevBuf<TsdfSideDev> side_tab; Event side_ev[4]; bool side_used[4] = {false, false, false, false}; int side_slot = 0;
+    // nalo_tsdf_replace_frames: one plane per side that needs one (and a packed colour plane each on a coloured volume); grows on demand, freed with the volume
+    std::vector<DevBuf<float>> pool; std::vector<DevBuf<unsigned>> cpool;
     DevBuf<float> block;                             // nalo_tsdf_get / _set staging: one tile of z slices of the sub-block
     DevBuf<float> xyz; HostBuf<float> xyz_h;         // nalo_tsdf_surface_points: as many points as the caller had room for
     DevBuf<float> plane2; DevBuf<unsigned> cplane2;                                 // nalo_tsdf_replace_frame: the plane of the records that were fused, when the frame's list has grown since
@@ -59,6 +65,9 @@ constexpr long long kTsdfMeshFirstVertices = 1LL << 14, kTsdfMeshFirstTriangles 
 
 constexpr long long kTsdfArchiveFirstVertices = 1LL << 12, kTsdfArchiveFirstTriangles = 1LL << 13, kTsdfArchiveFirstSlots = 1LL << 13;
 constexpr long long kTsdfArchiveMax = 2147483647LL;                                // an index is an int
+
+constexpr int kTsdfSideRing = 4;                                                   // TsdfVolume::side_ev
+constexpr int kTsdfCounts = 4 * kTsdfReplaceMaxPairs + 1;                           // TsdfVolume::updated
 
 constexpr size_t kTsdfTileFloats = (size_t)1 << 22;   // nalo_tsdf_get / _set: 16 MiB of staging
 
@@ -141,7 +150,7 @@ static int tsdf_integrate_enqueue(nalo_ctx* c, TsdfVolume& v, const char* depth,
         st.visited = (long long)(hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]);
         const int rc = tsdf_integrate_launch(c, D); if (rc) return rc;
     }
-    v.last = st; v.have_last = true; v.last_replace = false;
+    v.last = st; v.have_last = true; v.last_replace = false; v.last_n = 0;
     return NALO_OK;
 }
 
@@ -195,7 +204,45 @@ static int tsdf_replace_enqueue(nalo_ctx* c, TsdfVolume& v, TsdfSideDev rem, Tsd
         st.visited = (long long)(D.hi[0] - D.lo[0]) * (D.hi[1] - D.lo[1]) * (D.hi[2] - D.lo[2]);
         const int rc = tsdf_replace_launch(c, D); if (rc) return rc;
     }
-    v.last = st; v.have_last = true; v.last_replace = true;
+    v.last = st; v.have_last = true; v.last_replace = true; v.last_n = 0;
+    return NALO_OK;
+}
+
+// the window replacement: sides[2k] / sides[2k + 1] are pair k's remove / add side (on = 0: absent), validated, the remove sides already cut by their boxes.
+// Zero the 4 n + 1 counts, the table through a staging slot, ONE kernel over the hull, the call's record. Enqueues only (but see TsdfVolume::side_ev).
+static int tsdf_replace_n_enqueue(nalo_ctx* c, TsdfVolume& v, std::vector<TsdfSideDev>& sides) {
+    const int n = (int)sides.size() / 2;
+    bool any = false, coloured = false;
+    nalo_tsdf_stats st{};
+    for (TsdfSideDev& S : sides) {
+        tsdf_side_settle(S);
+        if (!S.on) continue;
+        for (int a = 0; a < 3; ++a) { st.lo[a] = any ? std::min(st.lo[a], S.lo[a]) : S.lo[a]; st.hi[a] = any ? std::max(st.hi[a], S.hi[a]) : S.hi[a]; }
+        any = true; coloured = coloured || S.coloured;
+    }
+    if (any) {
+        // everything that can refuse comes before the first thing that is queued
+        NALO_HIP(c, v.side_stage.reserve((size_t)kTsdfSideRing * 2 * kTsdfReplaceMaxPairs));
+        NALO_HIP(c, v.side_tab.reserve((size_t)kTsdfSideRing * 2 * kTsdfReplaceMaxPairs));
+        for (Event& e : v.side_ev) NALO_HIP(c, e.create(hipEventDisableTiming));
+    }
+    NALO_HIP(c, hipMemsetAsync(v.updated.p, 0, (size_t)(4 * n + 1) * sizeof(unsigned long long), c->stream));
+    if (any) {
+        const int q = v.side_slot;
+        const size_t at = (size_t)q * 2 * kTsdfReplaceMaxPairs;
+        if (v.side_used[q]) NALO_HIP(c, hipEventSynchronize(v.side_ev[q]));    // the copy of kTsdfSideRing calls ago: long done unless that many calls are still queued
+        std::copy(sides.begin(), sides.end(), v.side_stage.p + at);
+        NALO_HIP(c, hipMemcpyAsync(v.side_tab.p + at, v.side_stage.p + at, sides.size() * sizeof(TsdfSideDev), hipMemcpyHostToDevice, c->stream));
+        NALO_HIP(c, hipEventRecord(v.side_ev[q], c->stream));
+        v.side_used[q] = true; v.side_slot = (q + 1) % kTsdfSideRing;
+        TsdfReplaceNDev D{};
+        D.g = tsdf_grid(v, coloured);
+        for (int a = 0; a < 3; ++a) { D.lo[a] = st.lo[a]; D.hi[a] = st.hi[a]; }
+        D.trunc = v.d.trunc; D.max_weight = v.d.max_weight; D.n = n; D.sides = v.side_tab.p + at; D.counts = v.updated.p;
+        st.visited = (long long)(D.hi[0] - D.lo[0]) * (D.hi[1] - D.lo[1]) * (D.hi[2] - D.lo[2]);
+        const int rc = tsdf_replace_n_launch(c, D); if (rc) return rc;
+    }
+    v.last = st; v.have_last = true; v.last_replace = true; v.last_n = n;
     return NALO_OK;
 }
 
@@ -218,6 +265,24 @@ static void tsdf_log_shift(nalo_ctx* c, const TsdfVolume& v, const int shift[3])
     c->tsdf_log.swap(kept);
 }
 
+// the counts of the last window replacement: one copy, one wait. total: the hull, written = written_total, removed / reset / added summed over the pairs;
+// per_pair (may be NULL): min(last_n, cap) rows
+static int tsdf_replace_last_n(nalo_ctx* c, TsdfVolume& v, nalo_tsdf_replace_stats* total, nalo_tsdf_replace_pair_stats* per_pair, int cap) {
+    const int n = v.last_n;
+    NALO_HIP(c, hipSetDevice(c->device));
+    NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p, (size_t)(4 * n + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    NALO_HIP(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) { total->lo[k] = v.last.lo[k]; total->hi[k] = v.last.hi[k]; }
+    total->visited = v.last.visited; total->removed = total->reset = total->added = 0;
+    total->written = (long long)v.updated_h.p[4 * n];
+    for (int k = 0; k < n; ++k) {
+        const unsigned long long* q = v.updated_h.p + 4 * k;
+        total->removed += (long long)q[0]; total->reset += (long long)q[1]; total->added += (long long)q[2];
+        if (k < cap) per_pair[k] = nalo_tsdf_replace_pair_stats{(long long)q[0], (long long)q[1], (long long)q[2], (long long)q[3]};
+    }
+    return NALO_OK;
+}
+
 }  // namespace nalo
 
 using namespace nalo;
@@ -232,8 +297,8 @@ int nalo_tsdf_create(nalo_ctx* c, const nalo_tsdf_desc* desc) {
     std::copy(desc->origin, desc->origin + 3, v->origin0);
     hipError_t e = v->tsdf.reserve(v->n);
     if (e == hipSuccess) e = v->weight.reserve(v->n);
-    if (e == hipSuccess) e = v->updated.reserve(4);
-    if (e == hipSuccess) e = v->updated_h.reserve(4);
+    if (e == hipSuccess) e = v->updated.reserve(kTsdfCounts);
+    if (e == hipSuccess) e = v->updated_h.reserve(kTsdfCounts);
     if (e == hipSuccess) e = v->ev_read.create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->ev_prod.create(hipEventDisableTiming);
     if (e != hipSuccess) { delete v; (void)hipGetLastError(); return fail(c, NALO_ERR_HIP, std::string("nalo_tsdf_create: ") + hipGetErrorString(e)); }
@@ -484,7 +549,8 @@ int nalo_tsdf_last(nalo_ctx* c, nalo_tsdf_stats* stats) {
     if (!stats) return fail(c, NALO_ERR_ARG, "nalo_tsdf_last: bad argument");
     if (!v.have_last) return fail(c, NALO_ERR_STATE, "nalo_tsdf_last: nothing has been integrated into this volume");
     NALO_HIP(c, hipSetDevice(c->device));
-    NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    // behind a window replacement the voxels written, each counted once, lie behind the pairs' counts
+    NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p + 4 * v.last_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     *stats = v.last;
     stats->updated = (long long)v.updated_h.p[0];
@@ -518,11 +584,146 @@ int nalo_tsdf_replace_last(nalo_ctx* c, nalo_tsdf_replace_stats* stats) {
     if (!stats) return fail(c, NALO_ERR_ARG, "nalo_tsdf_replace_last: bad argument");
     if (!v.have_last || !v.last_replace) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_last: the last operation on this volume was not a replacement");
     NALO_HIP(c, hipSetDevice(c->device));
+    if (v.last_n) return tsdf_replace_last_n(c, v, stats, nullptr, 0);
     NALO_HIP(c, hipMemcpyAsync(v.updated_h.p, v.updated.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     NALO_HIP(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 3; ++k) { stats->lo[k] = v.last.lo[k]; stats->hi[k] = v.last.hi[k]; }
     stats->visited = v.last.visited;
     stats->written = (long long)v.updated_h.p[0]; stats->removed = (long long)v.updated_h.p[1]; stats->reset = (long long)v.updated_h.p[2]; stats->added = (long long)v.updated_h.p[3];
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_last_n(nalo_ctx* c, nalo_tsdf_replace_stats* total, nalo_tsdf_replace_pair_stats* per_pair, int cap, int* n) {
+    { const int rc = tsdf_need(c, "nalo_tsdf_replace_last_n"); if (rc) return rc; }
+    TsdfVolume& v = *c->tsdf;
+    if (!n || cap < 0 || (cap > 0 && !per_pair)) return fail(c, NALO_ERR_ARG, "nalo_tsdf_replace_last_n: bad argument");
+    if (!v.have_last || !v.last_replace || !v.last_n) return fail(c, NALO_ERR_STATE, "nalo_tsdf_replace_last_n: the last operation on this volume was not a window replacement");
+    nalo_tsdf_replace_stats own;
+    { const int rc = tsdf_replace_last_n(c, v, total ? total : &own, per_pair, cap); if (rc) return rc; }
+    *n = v.last_n;
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_depth_n(nalo_ctx* c, const nalo_tsdf_replace_args* pairs, int n) {
+    const std::string who = "nalo_tsdf_replace_depth_n";
+    { const int rc = tsdf_need(c, who.c_str()); if (rc) return rc; }
+    if (!pairs || n < 1 || n > kTsdfReplaceMaxPairs) return fail(c, NALO_ERR_ARG, who + ": bad argument (a list of 1 .. 16 pairs is needed)");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    // every pair is checked before anything is queued; a refusal is nalo_tsdf_replace_depth's of that pair, with the pair's index in front
+    std::vector<TsdfSideDev> sides((size_t)2 * n);
+    for (int k = 0; k < n; ++k) {
+        const nalo_tsdf_replace_args& a = pairs[k];
+        const std::string pk = who + ", pair " + std::to_string(k);
+        if (!a.remove && !a.add) return fail(c, NALO_ERR_ARG, pk + ": a side, remove or add, is needed");
+        int rc = NALO_OK;
+        if (a.remove) rc = tsdf_side_check(c, pk + ", remove", v, a.remove, &sides[2 * k]);
+        if (!rc && a.add) rc = tsdf_side_check(c, pk + ", add", v, a.add, &sides[2 * k + 1]);
+        TsdfBox B;
+        if (!rc && a.use_box) rc = tsdf_sub_box(c, pk, "box", v, true, a.lo, a.size, &B);
+        if (rc) return c->err.compare(0, pk.size(), pk) == 0 ? rc : fail(c, rc, pk + ": " + c->err);
+        TsdfSideDev& R = sides[2 * k];
+        if (R.on && a.use_box) for (int x = 0; x < 3; ++x) { R.lo[x] = std::max(R.lo[x], B.lo[x]); R.hi[x] = std::min(R.hi[x], B.lo[x] + B.size[x]); }
+    }
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_replace_depth_n");
+    for (int k = 0; k < n; ++k) {                                               // every distinct producer stream, once
+        hipStream_t prod = (hipStream_t)pairs[k].producer_stream;              // NULL: the null stream, which the context's non-blocking stream does not wait for by itself
+        bool seen = prod == (hipStream_t)c->stream;
+        for (int q = 0; q < k && !seen; ++q) seen = (hipStream_t)pairs[q].producer_stream == prod;
+        if (!seen) { NALO_HIP(c, hipEventRecord(c->ev_prod, prod)); NALO_HIP(c, hipStreamWaitEvent(c->stream, c->ev_prod, 0)); }
+    }
+    { const int rc = tsdf_replace_n_enqueue(c, v, sides); if (rc) return rc; }
+    NALO_HIP(c, hipEventRecord(v.ev_read, c->stream));                         // the callers' planes have been read (one kernel reads all of them): nalo_tsdf_release
+    v.read_pending = true;
+    return NALO_OK;
+}
+
+int nalo_tsdf_replace_frames(nalo_ctx* c, nalo_tsdf_replace_frames_args* a) {
+    const std::string who = "nalo_tsdf_replace_frames";
+    { const int rc = tsdf_need(c, who.c_str()); if (rc) return rc; }
+    if (!c->tsdf_log_on) return fail(c, NALO_ERR_STATE, who + ": the fusion log is not enabled (nalo_tsdf_log_enable)");
+    if (!map_dense_on(c)) return fail(c, NALO_ERR_STATE, who + ": the dense archive is not enabled (nalo_map_dense_enable)");
+    if (!a) return fail(c, NALO_ERR_ARG, who + ": bad argument");
+    NALO_HIP(c, hipSetDevice(c->device));
+    TsdfVolume& v = *c->tsdf;
+    // ---- every frame is checked before anything is queued or the log is touched. No frame_id appears twice, so what the loop of nalo_tsdf_replace_frame would
+    // find in the log at its call k is what the log holds now
+    struct Frame { const nalo_tsdf_log_entry* e; bool has_est, own; int total; std::vector<MapSeg> segs; TsdfSideDev rem{}, add{}; };
+    int list_len[kTsdfReplaceMaxPairs]; unsigned char skip[kTsdfReplaceMaxPairs];
+    const int n = a->n;
+    if (n < 1 || n > kTsdfReplaceMaxPairs) return fail(c, NALO_ERR_ARG, who + ": n outside 1 .. 16");
+    if (!a->frame_id) return fail(c, NALO_ERR_ARG, who + ": bad argument");
+    std::vector<Frame> fr((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const int rc = map_dense_segments(c, who.c_str(), a->frame_id[k], &fr[k].segs, &fr[k].total);      // a sharded window, a frame the archive has never seen
+        if (rc) return fail(c, rc, who + ", frame " + std::to_string(k) + ": " + c->err);
+        list_len[k] = fr[k].total;
+    }
+    if (const char* why = tsdf_replace_frames_plan(a, c->tsdf_log.data(), (int)c->tsdf_log.size(), list_len, skip)) return fail(c, NALO_ERR_ARG, who + ": " + why);
+    const bool col_now = v.colour.p != nullptr;
+    int n_pairs = 0;
+    for (int k = 0; k < n; ++k) {
+        Frame& f = fr[k];
+        const std::string fk = who + ", frame " + std::to_string(k);
+        f.e = tsdf_log_find(c, a->frame_id[k]);
+        f.has_est = a->est_new && (!a->has_est || a->has_est[k]);
+        if (!f.e && !f.has_est) return fail(c, NALO_ERR_ARG, fk + ": nothing to remove (the log has no entry of this frame) and nothing to add");
+        if (f.e && f.total < f.e->n_records) return fail(c, NALO_ERR_STATE, fk + ": the frame's dense list is shorter than when it was fused");
+        if (skip[k]) continue;
+        if (f.e) { const int rc = tsdf_side_camera(c, fk + ", the logged side", v, c->w, c->h, f.e->K, &f.e->est, f.e->min_depth, f.e->max_depth, &f.rem); if (rc) return rc; }
+        if (f.has_est) { const int rc = tsdf_side_camera(c, fk, v, c->w, c->h, a->K, &a->est_new[k], a->min_depth, a->max_depth, &f.add); if (rc) return rc; }
+        f.own = f.e && f.has_est && f.total > f.e->n_records;
+        ++n_pairs;
+    }
+    a->n_skipped = n - n_pairs;
+    if (!n_pairs) return NALO_OK;                                              // every frame is where it was fused: nothing is launched, nalo_tsdf_last stays
+    // ---- accepted: from here on only the runtime can fail
+    HostTimer ht(c, "tsdf_replace_frames");
+    size_t need = 0;
+    for (int k = 0; k < n; ++k) if (!skip[k]) need += (fr[k].e && (fr[k].own || !fr[k].has_est) ? 1 : 0) + (fr[k].has_est ? 1 : 0);
+    if (v.pool.size() < need) v.pool.resize(need);
+    if (col_now && v.cpool.size() < need) v.cpool.resize(need);
+    if (v.cpool.empty()) v.cpool.resize(1);                                    // tsdf_frame_plane_of names one, and leaves it alone without colour
+    std::vector<TsdfSideDev> sides; sides.reserve((size_t)2 * n_pairs);
+    size_t at = 0;
+    for (int k = 0; k < n; ++k) {
+        Frame& f = fr[k];
+        if (skip[k]) continue;
+        // the add side moves colour iff the volume holds colour now; the remove side iff the frame's fusion moved colour into planes that still exist
+        const bool col_add = col_now, col_rem = f.e && f.e->coloured && col_now;
+        // the whole list's plane serves both sides unless the list has grown since the frame was fused: then the first n_records records get a plane of their own
+        size_t p_rem = 0, p_add = 0;
+        if (f.e && (f.own || !f.has_est)) {
+            std::vector<MapSeg> head;
+            for (const MapSeg& sg : f.segs) if (sg.start < f.e->n_records) { head.push_back(sg); head.back().n = std::min(sg.n, f.e->n_records - sg.start); }
+            p_rem = at++;
+            const int rc = tsdf_frame_plane_of(c, v, head, col_rem, v.pool[p_rem], v.cpool[col_rem ? p_rem : 0]); if (rc) return rc;
+        }
+        if (f.has_est) {
+            p_add = at++;
+            const int rc = tsdf_frame_plane_of(c, v, f.segs, col_add, v.pool[p_add], v.cpool[col_add ? p_add : 0]); if (rc) return rc;
+            if (f.e && !f.own) p_rem = p_add;
+        }
+        // a packed colour plane is a U8 plane of three channels, B first: stride_x 4, stride_c 1
+        for (TsdfSideDev* S : {&f.rem, &f.add}) {
+            if (!S->on) continue;
+            const size_t pl = S == &f.rem ? p_rem : p_add;
+            S->depth = reinterpret_cast<const char*>(v.pool[pl].p); S->sy = (long long)c->w * 4; S->sx = 4;
+            const bool coloured = S == &f.rem ? col_rem : col_add;
+            S->coloured = coloured;
+            if (coloured) { S->colour = reinterpret_cast<const unsigned char*>(v.cpool[pl].p); S->csy = (long long)c->w * 4; S->csx = 4; S->csc[0] = 0; S->csc[1] = 1; S->csc[2] = 2; }
+        }
+        if (f.rem.on) for (int x = 0; x < 3; ++x) { f.rem.lo[x] = std::max(f.rem.lo[x], f.e->lo[x]); f.rem.hi[x] = std::min(f.rem.hi[x], f.e->lo[x] + f.e->size[x]); }      // the resident box
+        sides.push_back(f.rem); sides.push_back(f.add);
+    }
+    { const int rc = tsdf_replace_n_enqueue(c, v, sides); if (rc) return rc; }
+    // the log, for all pairs, as the loop would leave it, in the loop's order. tsdf_log_put may move the entries: the frames' pointers are dead from here on
+    for (int k = 0; k < n; ++k) {
+        if (skip[k]) continue;
+        if (fr[k].has_est) tsdf_log_put(c, v, a->frame_id[k], fr[k].total, a->est_new[k], a->K, a->min_depth, a->max_depth);
+        else { const nalo_tsdf_log_entry* e = tsdf_log_find(c, a->frame_id[k]); c->tsdf_log.erase(c->tsdf_log.begin() + (e - c->tsdf_log.data())); }
+    }
     return NALO_OK;
 }
 

@@ -1,9 +1,11 @@
 // nalo_tsdf_replace_depth's kernel (include/nalo_gpu.h, "The replacement"): per voxel the removal of one plane's contribution at one estimate, then the add of
 // another plane at another, in ONE pass over the hull of the two sides' boxes. Built WITHOUT FMA contraction: every expression below is the header's
-// definition, one rounding per operation. The predicate and d are tsdf_voxel_device.h's, the statement the integration reads too.
+// definition, one rounding per operation. The predicate and d are tsdf_voxel_device.h's, the statement the integration reads too; the steps of tsdf, weight
+// and colour are tsdf_replace_device.h's, the statement the window replacement (kernels_tsdf_replace_n.hip) reads too.
 #include "nalo_internal.h"
 #include "tsdf_device.h"
 #include "tsdf_voxel_device.h"
+#include "tsdf_replace_device.h"
 
 namespace nalo {
 
@@ -11,7 +13,6 @@ namespace nalo {
 // load and store per array where all four lie in the hull's x range, scalar accesses at a row's two ends; a workgroup is (1 << txl) lanes along x by
 // (256 >> txl) rows. Colour is a compile-time flag: the instantiation without it serves two uncoloured sides. The coloured one keeps, per voxel and side, the
 // weight before that side's step and the pixel's bytes, and touches the three colour planes only in lanes that store tsdf and weight.
-enum : unsigned { kTsdfRemoved = 1u, kTsdfReset = 2u, kTsdfAdded = 4u };
 struct TsdfRepColour { float wr, wa; unsigned cr, ca; };                        // wr / cr: the weight before the removal and its pixel; wa / ca: before the add
 
 // one voxel through both sides: the flags of what fired. in_r / in_a: the voxel's row lies in that side's box (and the side is on)
@@ -20,23 +21,20 @@ __device__ __forceinline__ unsigned tsdf_replace_voxel(const TsdfReplaceDev& P, 
     unsigned f = 0;
     float d; int pu, pv;
     if (in_r && i >= P.rem.lo[0] && i < P.rem.hi[0] && tsdf_sample<true>(P.g, P.rem, P.trunc, P.rem.s, Rr, i, d, pu, pv)) {
-        const float t0 = t, w0 = w, w1 = w0 - 1.0f;
-        if (!(w1 > 0.0f)) { t = 1.0f; w = 0.0f; f = kTsdfRemoved | kTsdfReset; }   // w0 <= 1, a NaN, a voxel never seen: the initial values
-        else { t = (t0 * w0 - d) / w1; w = w1; f = kTsdfRemoved; }
+        const float w0 = w;
+        f = tsdf_remove_step(t, w, d);
         if constexpr (kColour) if (P.rem.coloured) { V.wr = w0; V.cr = tsdf_pixel_bgr(P.rem, pu, pv); }
     }
     if (in_a && i >= P.add.lo[0] && i < P.add.hi[0] && tsdf_sample<true>(P.g, P.add, P.trunc, P.add.s, Ra, i, d, pu, pv)) {
-        const float t0 = t, w0 = w;
-        t = (t0 * w0 + d) / (w0 + 1.0f);
-        w = fminf(w0 + 1.0f, P.max_weight);
-        f |= kTsdfAdded;
+        const float w0 = w;
+        f |= tsdf_add_step(t, w, d, P.max_weight);
         if constexpr (kColour) if (P.add.coloured) { V.wa = w0; V.ca = tsdf_pixel_bgr(P.add, pu, pv); }
     }
     return f;
 }
 // plane X of a voxel with flags f: the removal X = (X0 * w0 - (float)x) / (w0 - 1.0f), or 0.0f where the voxel went back to its initial values; then the add
 __device__ __forceinline__ float tsdf_replace_colour(const TsdfReplaceDev& P, float x, unsigned f, const TsdfRepColour& V, int plane) {
-    if ((f & kTsdfRemoved) && P.rem.coloured) x = (f & kTsdfReset) ? 0.0f : (x * V.wr - (float)((V.cr >> (8 * plane)) & 0xFFu)) / (V.wr - 1.0f);
+    if ((f & kTsdfRemoved) && P.rem.coloured) x = tsdf_remove_colour(x, V.wr, V.cr, plane, (f & kTsdfReset) != 0);
     if ((f & kTsdfAdded) && P.add.coloured) x = tsdf_colour(x, V.wa, V.ca, plane);
     return x;
 }

@@ -525,6 +525,18 @@ struct TsdfReplaceDev {
     unsigned long long* counts;                                                 // [4], zero before: written, removed, reset, added
 };
 int tsdf_replace_launch(nalo_ctx* c, const TsdfReplaceDev& D);
+// nalo_tsdf_replace_depth_n (kernels_tsdf_replace_n.hip, built without FMA contraction): the chain of n pairs per voxel in one launch over the hull of every
+// side's box. 2 n sides do not fit the kernel arguments: they lie in a device table, pair k's remove side at [2k] and its add side at [2k + 1] (on = 0: absent).
+constexpr int kTsdfReplaceMaxPairs = 16;                                        // the largest window the library accepts
+struct TsdfReplaceNDev {
+    TsdfGridDev g;                                                              // g.col != NULL selects the coloured instantiation (some side is coloured); tsdf, weight and col are written
+    int lo[3], hi[3];                                                           // the hull of the sides that are on, hi exclusive, not empty
+    float trunc, max_weight;
+    int n;                                                                      // pairs, 1 .. kTsdfReplaceMaxPairs
+    const TsdfSideDev* sides;                                                   // [2 n], device memory, read only
+    unsigned long long* counts;                                                 // [4 n + 1], zero before: per pair removed, reset, added, written; then written_total
+};
+int tsdf_replace_n_launch(nalo_ctx* c, const TsdfReplaceNDev& D);
 int tsdf_fill_launch(nalo_ctx* c, float* tsdf, float* weight, size_t n);       // 1.0f / 0.0f
 // one array's sub-block [lo, lo + size) to (to_volume = 0) or from (1) a contiguous block, x fastest
 int tsdf_block_launch(nalo_ctx* c, float* vol, float* block, const int dims[3], const int lo[3], const int size[3], int to_volume);

@@ -1,9 +1,9 @@
 // The TSDF grid as the device sees it (include/nalo_gpu.h, "tsdf=1"): where a voxel lies in memory, where its centre lies in the world, and how a colour becomes
-// a byte, and the ray-cast's field S(q). The header's definitions are stated here once; kernels_tsdf.hip, kernels_tsdf_replace.hip, kernels_tsdf_mesh.hip,
-// kernels_tsdf_raycast.hip and kernels_tsdf_align.hip use them, and all five are built
+// a byte, and the ray-cast's field S(q). The header's definitions are stated here once; kernels_tsdf.hip, kernels_tsdf_replace.hip, kernels_tsdf_replace_n.hip,
+// kernels_tsdf_mesh.hip, kernels_tsdf_raycast.hip and kernels_tsdf_align.hip use them, and all six are built
 // WITHOUT FMA contraction (build.py: NO_CONTRACT): one rounding per operation. Nothing else belongs here.
 // nalo_internal.h includes this file too, for the struct its kernel-argument structs embed, so every file of the library sees the functions below. Only the
-// five files above may call them: tsdf_centre compiled with contraction would round differently from the header's definition.
+// six files above may call them: tsdf_centre compiled with contraction would round differently from the header's definition.
 #pragma once
 #include <hip/hip_runtime.h>
 

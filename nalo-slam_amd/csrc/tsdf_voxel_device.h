@@ -1,6 +1,6 @@
 // The per-voxel predicate of the TSDF integration (include/nalo_gpu.h, nalo_tsdf_integrate_depth and "The replacement"), stated ONCE: which pixel a voxel
-// reads, whether its depth is usable, and d; and the colour mean of an add. kernels_tsdf.hip (the integration) and kernels_tsdf_replace.hip (remove / add at an
-// estimate) call them, and both are built WITHOUT FMA contraction (build.py: NO_CONTRACT): one rounding per operation. Nothing else belongs here.
+// reads, whether its depth is usable, and d; and the colour mean of an add. kernels_tsdf.hip (the integration), kernels_tsdf_replace.hip (remove / add at an
+// estimate) and kernels_tsdf_replace_n.hip (the window's pairs in one launch) call them, and all three are built WITHOUT FMA contraction (build.py: NO_CONTRACT): one rounding per operation. Nothing else belongs here.
 #pragma once
 #include "tsdf_device.h"
 
